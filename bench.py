@@ -2,14 +2,18 @@
 """Throughput bench of the hot path: CombSub 44.1 kHz synthesis, batch = 64 x 2 s clips per GPU
 (BASELINE.json configs[1]), units/f0/volume/spk_id -> rendered audio, inputs resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]                      # N = 1
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]      # N = 1
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full forward (`CombSub.forward`) over the per-GPU batch.  With N > 1 utterances are sharded
 over the ranks (weak scaling: 64 per GPU) and the rendered audio is all-gathered over RCCL/xGMI on a side
 stream, overlapped with the next step's compute (the gather of the last step is inside the timed region).
-Rank 0 prints ONE JSON line; `roofline` is measured live with HIP events around the dominant kernel,
-`cpu_baseline` times the CPU oracle (a port of the reference's PyTorch CPU path) on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports the headline
+(`value`, `ms_per_step`); `--dump-outputs DIR` then writes what the last timed step returned (rank 0) as
+DIR/<name>.npy - the inputs, weights and noise seeds are fixed, so two builds can be compared output for output.
+`--full` adds everything else: the fp32-MFMA leg, the strong-scaling leg, `roofline` (measured live with HIP events
+around the dominant kernels on sampled steps of the timed region), the per-family breakdown pass, the parity sample
+and `cpu_baseline`, which times the CPU oracle (a port of the reference's PyTorch CPU path) on a bounded sample.
 """
 import argparse
 import json
@@ -119,9 +123,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the fp32-MFMA leg, the strong-scaling leg, "
+                         "the sampled roofline brackets, the per-family breakdown pass, the parity sample against the CPU "
+                         "oracle, the CPU baseline (synth), the back-to-back block pace (realtime)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the parity sample and the CPU baseline")
     ap.add_argument("--profile-every", type=int, default=5,
-                    help="the roofline's HIP events bracket every n-th step of the timed region (1 = every step: ~6 %% slower steps)")
+                    help="with --full: the roofline's HIP events bracket every n-th step of the timed region (1 = every step: ~6 %% slower steps)")
     ap.add_argument("--model", default="CombSub", choices=["CombSub", "Sins256", "CombSubFast"])
     ap.add_argument("--mode", default="synth", choices=["synth", "train", "realtime"],
                     help="synth (default, BASELINE configs[1]): forward only; train (configs[3]): one full training "
@@ -181,6 +191,29 @@ def cpu_baseline(seed, inp_cpu):
                       f"threads ({t_all * 1e3:.0f} ms each); 1 thread: the first 8 clips, median of 3 ({t_one * 1e3:.0f} ms each)"}
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> dirname/<name>.npy, float64 kept, every other dtype as float32; at most 64 MB."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).contiguous().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > 64 << 20:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the 64 MB budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def synth_outputs(res):
+    """The arrays a caller of `model.forward` receives from the last timed step: the signal in full, the phase and the
+    harmonic / noise parts of every fourth clip (0, 4, ..., 60: a fixed sample that keeps the dump under 64 MB for every
+    model, the sample-rate phase of Sins included)."""
+    sig, phase, (harm, noise) = res
+    return {"signal": sig, "phase": phase[::4], "harmonic": harm[::4], "noise": noise[::4]}
+
+
 def parity_sample(model_cpu_sd, cfg, model, inp, inp_cpu, seed, ctx, dev):
     """RMS error of the BENCHED arithmetic against the CPU oracle: the whole 64-clip batch is rendered once more with an
     injected noise draw (same kernels and batch-dependent kernel choices as the timed steps), 8 of the 64 clips are
@@ -235,29 +268,33 @@ def realtime_mode(args, model, dev, dist, world, rank):
     t_all = time.perf_counter()
     for i in range(args.steps):
         t0 = time.perf_counter()
-        one(args.warmup + i)
+        last = one(args.warmup + i)
         torch.cuda.synchronize()
         lat.append((time.perf_counter() - t0) * 1e3)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t_all
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"block": last})
     lat.sort()
     mean, p99 = sum(lat) / len(lat), lat[min(len(lat) - 1, int(0.99 * len(lat)))]
-    # back-to-back blocks without the per-block host synchronisation: the device-side pace of the chain
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(args.steps):
-        one(i)
-    e1.record()
-    torch.cuda.synchronize()
-    pace = e0.elapsed_time(e1) / args.steps
+    pace = 0.0
+    if args.full:
+        # back-to-back blocks without the per-block host synchronisation: the device-side pace of the chain
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(args.steps):
+            one(i)
+        e1.record()
+        torch.cuda.synchronize()
+        pace = e0.elapsed_time(e1) / args.steps
     stats = torch.tensor([dt, mean, p99, pace], device=dev, dtype=torch.float64)
     if dist is not None:
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
     dt, mean, p99, pace = [float(v) for v in stats]
     if rank == 0:
-        print(json.dumps({
+        out = {
             "metric": "audio samples/sec @44.1kHz CombSub real-time streams (0.2 s blocks, SOLA splice, one stream per GPU)",
             "value": world * r.block / (mean * 1e-3), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": mean, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -268,10 +305,13 @@ def realtime_mode(args, model, dev, dist, world, rank):
                                    f"({r.frames} frames), block {r.block}, cross-fade {r.splicer.xfade}, search {r.splicer.search}; "
                                    "window -> volume -> model (HIP-graph replay) -> gate -> SOLA per block",
                        "sharding": "replicas only (one stream per GPU, no collective)"},
-            "ms_per_block_mean": mean, "ms_per_block_p99": p99, "ms_per_block_back_to_back": pace,
+            "ms_per_block_mean": mean, "ms_per_block_p99": p99,
             "x_realtime_per_stream": 200.0 / mean,
             "timed_region_s": dt,
-        }), flush=True)
+        }
+        if args.full:
+            out["ms_per_block_back_to_back"] = pace
+        print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -340,13 +380,14 @@ def main():
 
         def step(i):
             with torch.no_grad():
-                sig, _, _ = model(inp["units"], inp["f0"], inp["volume"], inp["spk_id"], noise_seed=1000 + i)
+                res = model(inp["units"], inp["f0"], inp["volume"], inp["spk_id"], noise_seed=1000 + i)
             if gather is not None:
-                gather.submit(sig)
-            return sig
+                gather.submit(res[0])
+            return res
 
-    def timed_leg(base):
-        """W warm-up steps, then exactly K steps between barrier + synchronize pairs; max over ranks."""
+    def timed_leg(base, profile):
+        """W warm-up steps, then exactly K steps between barrier + synchronize pairs; max over ranks.  Returns the time,
+        the families' event timings (`profile` only) and what the last timed step returned."""
         for i in range(args.warmup):
             step(base + i)
         if gather is not None:
@@ -361,16 +402,22 @@ def main():
         # ... and around a SAMPLE of the timed steps only (every `--profile-every`-th, default 5): an event record costs ~2 us of
         # stream time and serialises the kernels around it - 38 records per step took 6 % of the step (1.27 against 1.19 ms for
         # the same loop without them, r03_c), which is a distortion of `value`, not a property of the path
-        ctx.profile_begin(list(FAMILIES_TIMED))
+        # (a plain run times the steps alone: the brackets exist for the --full figures)
+        if profile:
+            ctx.profile_begin(list(FAMILIES_TIMED))
         every = max(1, args.profile_every)
+        last = None
         t0 = time.perf_counter()
         for i in range(args.steps):
-            if every > 1:
+            if profile and every > 1:
                 if i % every == 0:
                     ctx.profile_mask(list(FAMILIES_TIMED))
                 elif i % every == 1:
                     ctx.profile_mask([])
-            step(base + args.warmup + i)
+            if i == args.steps - 1:
+                last = step(base + args.warmup + i)
+            else:
+                step(base + args.warmup + i)
         if gather is not None:
             gather.wait()
         torch.cuda.synchronize()
@@ -378,28 +425,35 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        timed = ctx.profile_end()
+        timed = ctx.profile_end() if profile else None
         if dist is not None:
             tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        return dt, timed
+        return dt, timed, last
 
     # leg 1 (`value`): the library's default product arithmetic (split-bf16x3 at this batch)
-    dt, timed = timed_leg(0)
+    dt, timed, last = timed_leg(0, args.full)
+    if args.dump_outputs and rank == 0:
+        if args.mode == "synth":
+            dump_outputs(args.dump_outputs, synth_outputs(last))
+        else:   # a training step returns the loss; the caller also holds the parameters it updated
+            dump_outputs(args.dump_outputs, {"loss": last, "parameters": torch.cat([p.detach().reshape(-1)
+                                                                                    for p in model.parameters()])})
+    del last
     # leg 2 (`value_fp32_mfma`): the same steps with every contraction on the fp32 matrix pipe (the reference's precision
     # class); the training step's backward is fp32 in both, so the second leg is a synth-mode figure
     dt32 = timed32 = None
-    if args.mode == "synth":
+    if args.full and args.mode == "synth":
         ctx.set_math(hipddsp.MATH_FP32)
-        dt32, timed32 = timed_leg(100_000)
+        dt32, timed32, _ = timed_leg(100_000, True)
         ctx.set_math(hipddsp.MATH_SPLIT_BF16)
 
     # strong scaling (a FIXED 64-clip job, what a main.py / gui.py batch looks like): at N = 1 the per-GPU share of an 8-GPU
     # run of that job - 8 clips - is timed with the same protocol (the one-GPU job itself is leg 1); at N > 1 the 64 clips are
     # sharded over the ranks (64 / N each) and gathered like the weak-scaled leg
     strong = None
-    if args.mode == "synth":
+    if args.full and args.mode == "synth":
         shard = 8 if world == 1 else max(1, B_PER_GPU // world)
         sub = {k: v[:shard].contiguous() for k, v in inp.items()}
         g2 = sharding.AudioGather(world, shard, T, dev) if world > 1 else None
@@ -412,7 +466,7 @@ def main():
                 g2.submit(sig)
             return sig
         gather = g2
-        dts, _ = timed_leg(200_000)
+        dts, _, _ = timed_leg(200_000, True)
         step, gather = keep_step, keep_gather
         strong = {"job": f"{B_PER_GPU if world > 1 else 64} clips x 2 s in total", "clips_per_gpu": shard,
                   "ms_per_step": dts / args.steps * 1e3}
@@ -452,16 +506,17 @@ def main():
         out["ms_per_step_fp32_mfma"] = dt32 / args.steps * 1e3
     if strong is not None:
         out["strong_scaling"] = strong
-    # untimed breakdown pass: every kernel family bracketed by events (adds launch gaps, so not part of `value`)
-    ctx.profile_begin()
-    nb = 3
-    for i in range(nb):
-        step(10_000 + i)
-    if gather is not None:
-        gather.wait()
-    torch.cuda.synchronize()
-    fam = ctx.profile_end()
-    if rank == 0:
+    if args.full:
+        # untimed breakdown pass: every kernel family bracketed by events (adds launch gaps, so not part of `value`)
+        ctx.profile_begin()
+        nb = 3
+        for i in range(nb):
+            step(10_000 + i)
+        if gather is not None:
+            gather.wait()
+        torch.cuda.synchronize()
+        fam = ctx.profile_end()
+    if rank == 0 and args.full:
         sampled_steps = len(range(0, args.steps, max(1, args.profile_every)))
 
         def roofline_of(name, timed, split):
@@ -500,6 +555,7 @@ def main():
             cpu_sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
             out["parity_vs_oracle"] = parity_sample(cpu_sd, cfg, model, inp, inp_cpu, seed, ctx, dev)
             out["cpu_baseline"] = cpu_baseline(seed, inp_cpu)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
