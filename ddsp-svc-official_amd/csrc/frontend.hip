@@ -1,6 +1,7 @@
 // SURVEY 8(f) rank 2 - the two device-side steps immediately BEFORE the synthesis path that need no pretrained model:
-//   * frame-wise RMS volume (`Volume_Extractor.extract`, ddsp/vocoder.py:116-137): reflect-pad by (hop/2, (hop+1)/2),
-//     mean of squares over non-overlapping hop-sized blocks, square root; T/hop + 1 frames;
+//   * frame-wise RMS volume (`Volume_Extractor.extract`, ddsp/vocoder.py:116-137): reflect-pad by (hop//2, (hop+1)//2),
+//     mean of squares over non-overlapping blocks [int(n*hop), int((n+1)*hop)), square root; int(T//hop) + 1 frames - for
+//     an integral hop and for the fractional one a device at another rate than the model's gives (main.py:72,109);
 //   * nearest-frame alignment of encoder units to the synthesiser's frame rate (`Units_Encoder.encode`,
 //     ddsp/vocoder.py:201-211): frame i takes unit row min(rint(fp32(ratio) * i), Lu - 1), rint = half to even.
 // Both are HBM-bound streaming kernels: 4 B read per sample / 8 B per copied feature.
@@ -8,17 +9,23 @@
 
 namespace {
 
-// one wavefront per (utterance, frame)
-__global__ void __launch_bounds__(256) volume_kernel(const float* __restrict__ audio, int64_t T, int hop, int64_t n_frames,
-                                                     int64_t total, float* __restrict__ vol) {
+// one wavefront per (utterance, frame).  Block n is padded[int(n*h) : min(int((n+1)*h), Tp)] of the signal reflect-padded
+// by pad_l in front (Tp = padded length), bounds in fp64 like the reference's Python floats; its mean divides by the
+// block's own length.  An integral hop gives start n*hop and length hop exactly, so both entry points share this kernel.
+__global__ void __launch_bounds__(256) volume_kernel(const float* __restrict__ audio, int64_t T, double hop, int64_t pad_l,
+                                                     int64_t Tp, int64_t n_frames, int64_t total, float* __restrict__ vol) {
     const int lane = threadIdx.x & 63;
     const int64_t fidx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (fidx >= total) return;
     const int64_t b = fidx / n_frames, n = fidx - b * n_frames;
     const float* x = audio + b * T;
-    const int64_t first = n * hop - hop / 2;          // index of the block's first sample in the UNpadded signal
+    const int64_t start = (int64_t)((double)n * hop);
+    int64_t end = (int64_t)((double)(n + 1) * hop);
+    end = end < Tp ? end : Tp;                        // numpy truncates the slice at the padded length
+    const int64_t len = end - start;
+    const int64_t first = start - pad_l;              // index of the block's first sample in the UNpadded signal
     double s = 0.0;                                   // (numpy sums the fp32 squares pairwise; fp64 is at least as close)
-    for (int j = lane; j < hop; j += 64) {
+    for (int64_t j = lane; j < len; j += 64) {
         int64_t i = first + j;
         if (i < 0) i = -i;                            // numpy 'reflect': edge sample not repeated
         if (i >= T) i = 2 * (T - 1) - i;
@@ -26,7 +33,7 @@ __global__ void __launch_bounds__(256) volume_kernel(const float* __restrict__ a
         s += (double)(v * v);                         // the square is rounded to fp32 first, like `audio ** 2`
     }
     s = wave_sum_d(s);
-    if (lane == 0) vol[fidx] = sqrtf((float)(s / (double)hop));
+    if (lane == 0) vol[fidx] = sqrtf((float)(s / (double)len));
 }
 
 // one wavefront per output row (utterance, frame)
@@ -89,6 +96,30 @@ extern "C" int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int6
     return DDSP_OK;
 }
 
+// Python's float floor division `a // b` (CPython float_floor_div: fmod, exact quotient of the remainder-free part, floor,
+// round-half correction), so that frame counts and pads equal the reference's `int(T // h)` / `int(h // 2)` bit for bit
+static double py_floordiv(double a, double b) {
+    double mod = fmod(a, b);
+    double div = (a - mod) / b;
+    if (mod != 0.0 && ((b < 0) != (mod < 0))) div -= 1.0;
+    if (div == 0.0) return copysign(0.0, a / b);
+    double fl = floor(div);
+    if (div - fl > 0.5) fl += 1.0;
+    return fl;
+}
+
+static int volume_launch(ddsp_ctx* ctx, hipStream_t st, const float* audio, int64_t B, int64_t T, double hop, int64_t n_frames,
+                         int64_t pad_l, int64_t pad_r, float* volume) {
+    DDSP_ENTER_DEVICE(ctx);
+    const int64_t total = B * n_frames;
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(volume_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, audio, T, hop, pad_l,
+                       T + pad_l + pad_r, n_frames, total, volume);
+    ddsp_prof_end(ctx, st, 2.0 * B * T, 4.0 * (B * (double)T + total));
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
 extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
                                    float* volume) {
     DDSP_REQUIRE(ctx, ctx && audio && volume, "ddsp_volume_extract: null argument");
@@ -96,15 +127,19 @@ extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* aud
     // numpy's reflect padding needs the pad (at most (hop+1)/2) to be smaller than the signal
     DDSP_REQUIRE(ctx, T > (hop + 1) / 2, "ddsp_volume_extract: signal shorter than the reflect padding");
     if (B == 0) return DDSP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DDSP_ENTER_DEVICE(ctx);
-    const int64_t n_frames = T / hop + 1, total = B * n_frames;
-    ddsp_prof_begin(ctx, st, PF_OTHER);
-    hipLaunchKernelGGL(volume_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, audio, T, hop, n_frames, total,
-                       volume);
-    ddsp_prof_end(ctx, st, 2.0 * B * T, 4.0 * (B * (double)T + total));
-    DDSP_LAUNCH_CHECK(ctx);
-    return DDSP_OK;
+    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume);
+}
+
+extern "C" int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, double hop_size,
+                                        float* volume) {
+    DDSP_REQUIRE(ctx, ctx && audio && volume, "ddsp_volume_extract_frac: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && T >= 0 && hop_size >= 1.0 && hop_size <= (double)(1 << 20),
+                 "ddsp_volume_extract_frac: bad shape or hop");       // (also refuses a NaN hop)
+    const int64_t pad_l = (int64_t)py_floordiv(hop_size, 2.0), pad_r = (int64_t)py_floordiv(hop_size + 1.0, 2.0);
+    DDSP_REQUIRE(ctx, T > pad_r, "ddsp_volume_extract_frac: signal shorter than the reflect padding");
+    if (B == 0) return DDSP_OK;
+    const int64_t n_frames = (int64_t)py_floordiv((double)T, hop_size) + 1;
+    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, hop_size, n_frames, pad_l, pad_r, volume);
 }
 
 extern "C" int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,

@@ -44,7 +44,10 @@ class Volume_Extractor:
         if not x.is_cuda:
             raise RuntimeError("Volume_Extractor runs on a HIP device only (no CPU fallback)")
         flat = x.dim() == 1
-        vol = hipddsp.context_for(x.device).volume_extract(x.reshape(1, -1) if flat else x, int(self.hop_size))
+        # an integral hop (int or float) takes the integer entry point; block_size * sr / model_sr of an input at another
+        # rate than the model's (main.py:72,109) is fractional and keeps its fraction, as the reference's float slicing does
+        hop = int(self.hop_size) if float(self.hop_size).is_integer() else float(self.hop_size)
+        vol = hipddsp.context_for(x.device).volume_extract(x.reshape(1, -1) if flat else x, hop)
         vol = vol[0] if flat else vol
         return vol.cpu().numpy() if is_np else vol
 
@@ -52,8 +55,9 @@ class Volume_Extractor:
 def align_units(units, n_samples, sample_rate, hop_size, encoder_sample_rate=16000, encoder_hop_size=320):
     """Nearest-frame alignment of encoder units (B, Lu, C) to the synthesiser's frames - the tail of the reference's
     `Units_Encoder.encode` (`ddsp/vocoder.py:201-211`), for callers that keep the reference's encoders and want the
-    gather on the device: n_frames = n_samples // hop_size + 1, row i takes unit min(round(ratio * i), Lu - 1)."""
-    n_frames = int(n_samples) // int(hop_size) + 1
+    gather on the device: n_frames = int(n_samples // hop_size) + 1 (a float hop keeps its fraction, like the
+    reference's), row i takes unit min(round(ratio * i), Lu - 1)."""
+    n_frames = int(int(n_samples) // hop_size) + 1
     ratio = (hop_size / sample_rate) / (encoder_hop_size / encoder_sample_rate)
     return hipddsp.context_for(units.device).align_units(units, n_frames, ratio)
 

@@ -13,8 +13,10 @@ What makes the capture safe:
     a host seed per call, which a graph would freeze);
   * inputs are copied into static tensors, outputs are static tensors valid until the next replay.
 Weights are read by the captured kernels at replay time (the weight-preparation kernel is part of the graph), so
-in-place weight updates are honoured; `spk_mix_dict` and `initial_phase` are host-side arguments and not supported
-here.  Forward only.
+in-place weight updates are honoured.  `spk_mix_dict` ({speaker id: weight}) is captured with the graph: its ids and
+weights become kernel arguments, so a capture is valid for that mix only (a new mix needs a new `GraphedSynth`;
+`realtime.StreamRenderer.set_speaker` does that), while `spk_id` stays a static input.  `initial_phase` is a host-side
+argument and not supported here.  Forward only.
 """
 import torch
 
@@ -22,13 +24,14 @@ import hipddsp
 
 
 class GraphedSynth:
-    def __init__(self, model, B, Fr, warmup=3):
+    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None):
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("GraphedSynth needs the model on a HIP device (no CPU fallback)")
         self.model = model.eval()
         self.device = p.device
         self.B, self.Fr = int(B), int(Fr)
+        self.spk_mix_dict = None if spk_mix_dict is None else dict(spk_mix_dict)
         hop = int(model.block_size)
         n_unit = model.unit2ctrl.n_unit
         dev = self.device
@@ -52,7 +55,7 @@ class GraphedSynth:
         self.ctx.freeze()
 
     def _run(self):
-        return self.model(self.units, self.f0, self.volume, self.spk_id, noise=self.noise)
+        return self.model(self.units, self.f0, self.volume, self.spk_id, spk_mix_dict=self.spk_mix_dict, noise=self.noise)
 
     @torch.no_grad()
     def __call__(self, units, f0, volume, spk_id, noise=None):

@@ -91,6 +91,7 @@ SIGNATURES = {
     "ddsp_volume_gate": (_int, [_vp, _vp, _vp, _vp, _f32, _i64, _i64, _int]),
     "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "ddsp_volume_extract": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
+    "ddsp_volume_extract_frac": (_int, [_vp, _vp, _vp, _i64, _i64, _f64, _vp]),
     "ddsp_align_units": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
     "ddsp_gemm_res_ln": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _int]),
     "ddsp_conv1d_pair_supported": (_int, [_vp, _int, _int, _int]),
@@ -420,13 +421,20 @@ class Context:
 
     # -- front-end steps -----------------------------------------------------
     def volume_extract(self, audio, hop):
-        """audio (B,T) fp32 -> (B, T//hop + 1) block RMS with numpy-'reflect' padding (ddsp/vocoder.py:116-137)."""
+        """audio (B,T) fp32 -> (B, int(T // hop) + 1) block RMS with numpy-'reflect' padding (ddsp/vocoder.py:116-137).
+        `hop` may be a non-integral float (an input at another rate than the model's: block_size * sr / model_sr); an
+        integral one, int or float, takes the integer entry point."""
         audio = audio.contiguous().float()
         B, T = audio.shape
-        out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
-        if B == 0:
+        if float(hop).is_integer():
+            out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
+            if B == 0:
+                return out
+            self.call("ddsp_volume_extract", _ptr(audio), B, T, int(hop), _ptr(out))
             return out
-        self.call("ddsp_volume_extract", _ptr(audio), B, T, int(hop), _ptr(out))
+        hop = float(hop)
+        out = torch.empty(B, int(T // hop) + 1, device=audio.device, dtype=torch.float32)
+        self.call("ddsp_volume_extract_frac", _ptr(audio), B, T, hop, _ptr(out))
         return out
 
     def align_units(self, units, n_frames, ratio):

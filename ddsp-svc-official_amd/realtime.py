@@ -2,9 +2,54 @@
 window bookkeeping is the caller's (PortAudio), the SOLA search + sin^2 cross-fade + tail hand-over run as two
 kernels on the stream's own GPU with no host synchronisation.  One `Splicer` per stream (eight
 independent streams = eight replicas, no collective)."""
+import numpy as np
 import torch
 
 import hipddsp
+
+
+# ---- the size and key arithmetic of the reference's callback that does not touch audio ------------------------------------
+def input_frames(samplerate, block_time, crossfade_time, buffer_num, search_time=0.01, delay_time=0.02):
+    """Length of the sliding input window at the device rate (`gui.py:319-325`)."""
+    block = int(block_time * samplerate)
+    return max(block + int(crossfade_time * samplerate) + int(search_time * samplerate) + 2 * int(delay_time * samplerate),
+               (1 + buffer_num) * block)
+
+
+def hop_size(block_size, samplerate, model_sr):
+    """Analysis hop of the window in device samples (`gui.py:94`): a float, non-integral when the device rate differs
+    from the model's (557.29 for 512 at 48 kHz over 44.1 kHz)."""
+    return block_size * samplerate / model_sr
+
+
+def window_frames(n_in, hop):
+    """Frames of an n_in-sample window at hop `hop` (`Volume_Extractor.extract`, ddsp/vocoder.py:125)."""
+    return int(n_in // hop) + 1
+
+
+def silence_front(block_time, buffer_num, crossfade_time):
+    """Seconds of the window's front that the enhancer skips and the f0 extractor may treat as silence
+    (`f_safe_prefix_pad_length`, gui.py:326, turned into `silence_front` by gui.py:88-91)."""
+    safe = block_time * buffer_num - crossfade_time - 0.01 - 0.02
+    return safe - 0.03 if safe > 0.03 else 0
+
+
+def key_cut_frames(silence, model_sr, block_size):
+    """Frames of the f0 track the enhancer drops before it looks at the pitch (`enhancer.py:27-29`)."""
+    return int(silence * model_sr / block_size)
+
+
+def auto_key(f0_max):
+    """`adaptive_key='auto'` of `Enhancer.enhance` (enhancer.py:34-38) from the highest f0 of the cut track: the smallest
+    non-negative whole number of semitones that brings it to 760 Hz or below (the quotient in fp32, as torch forms it)."""
+    with np.errstate(divide="ignore"):
+        return int(max(0, np.ceil(12 * np.log2(float(np.float32(f0_max) / np.float32(760))))))
+
+
+def output_rate(model_sr, enhancer=None):
+    """Rate of what the chain hands to the splice before any resampling: the enhancer's when one is chained
+    (`Enhancer.enhance` returns audio at its own rate), otherwise the model's."""
+    return int(enhancer.enhancer_sample_rate) if enhancer is not None else int(model_sr)
 
 
 def phase_vocoder(a, b, fade_out, fade_in):
@@ -57,56 +102,142 @@ class StreamRenderer:
     """One real-time stream on one GPU: the device half of the reference's callback chain
     (`gui.GUI.audio_callback`, gui.py:367-433, calling `gui.SvcDDSP.infer`, gui.py:69-140).
 
-    Per block of `block` input samples:
+    Per block of `block` input samples at the device rate `samplerate`:
       1. the sliding input window takes the block (`input_wav[:] = append(input_wav[block:], indata)`, gui.py:373-374);
-      2. frame volume of the window (`Volume_Extractor.extract`, gui.py:105-106) -> `ddsp_volume_extract`;
+      2. frame volume of the window at hop `hop_size = block_size * samplerate / model_sr` (`Volume_Extractor.extract`,
+         gui.py:94,105-106) -> `ddsp_volume_extract`, or `ddsp_volume_extract_frac` when that hop is not integral;
       3. units / f0 of the window from the caller's analysis front end (`features(window) -> (units (1,Fr,C), f0 (1,Fr,1))`:
-         the f0 extractor and the units encoder are third-party models outside this path, SURVEY section 2);
-      4. the synthesiser forward (gui.py:125-126), eager or replayed from a HIP graph (`graphed.GraphedSynth`);
-      5. `output *= mask` with the 9-frame dilated volume gate (gui.py:107-112,127) -> `ddsp_volume_gate`, in place;
-      6. SOLA search + cross-fade + tail hand-over (gui.py:405-430) -> `Splicer.push`.
-    Nothing in the chain synchronises with the host; the returned (block,) tensor is what the callback copies out.
+         the f0 extractor and the units encoder are third-party models outside this path); f0 is
+         shifted by `pitch_adjust` semitones (gui.py:102);
+      4. the synthesiser forward (gui.py:125-126) with `spk_id` or `spk_mix_dict`, eager or replayed from a HIP graph
+         (`graphed.GraphedSynth`, captured for the current mix);
+      5. `output *= mask` with the 9-frame dilated volume gate at the model's `block_size` (gui.py:107-112,127) ->
+         `ddsp_volume_gate`, in place;
+      6. optionally `enhancer.enhance(...)` (gui.py:128-134), eager, with the adaptive key decided here (see below);
+      7. resampling from the model's (or enhancer's) rate to `samplerate` when they differ (gui.py:399-404);
+      8. SOLA search + cross-fade + tail hand-over (gui.py:405-430) -> `Splicer.push`.
+    Without the enhancer nothing in the chain synchronises with the host; the returned (block,) tensor is what the callback
+    copies out.  With `enhancer_adaptive_key='auto'` the key (it decides tensor lengths) is taken before the synthesis is
+    enqueued: on the host when f0 arrives as a CPU tensor, else by one scalar read-back of the f0 maximum.
     Streams are independent: eight streams are eight renderers on eight GPUs (replicas only)."""
 
     def __init__(self, model, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0, spk_id=1,
-                 features=None, use_graph=True, use_phase_vocoder=False):
+                 features=None, use_graph=True, use_phase_vocoder=False, pitch_adjust=0, spk_mix_dict=None, enhancer=None,
+                 enhancer_adaptive_key="auto"):
         self.model = model.eval()
         self.device = torch.device(device)
-        self.hop = int(model.block_size)
+        self.block_size = int(model.block_size)
+        self.model_sr = int(model.sampling_rate)
+        self.samplerate = samplerate
+        self.hop = self.block_size                                   # the model's hop: gate, synthesis
+        self.hop_size = hop_size(self.block_size, samplerate, self.model_sr)   # the window's analysis hop
         self.threshold_db = float(threshold_db)
+        self.pitch_adjust = float(pitch_adjust)
         self.splicer = Splicer(samplerate, block_time, crossfade_time, self.device, use_phase_vocoder=use_phase_vocoder)
         self.block = self.splicer.block
         self.n_in = self.splicer.input_frames(buffer_num)
-        self.frames = self.n_in // self.hop + 1                      # frames of the window (f0 / units / volume alike)
+        self.frames = window_frames(self.n_in, self.hop_size)       # frames of the window (f0 / units / volume alike)
         self.window = torch.zeros(self.n_in, device=self.device)   # `self.input_wav`, gui.py:346
+        self.silence_front = silence_front(block_time, buffer_num, crossfade_time)
+        if isinstance(enhancer_adaptive_key, str) and enhancer_adaptive_key != "auto":
+            raise ValueError(f"enhancer_adaptive_key must be a number or 'auto', got {enhancer_adaptive_key!r}")
+        self.enhancer = enhancer
+        self.enhancer_adaptive_key = enhancer_adaptive_key
+        self.last_key = None                                         # the key the last block was enhanced with
+        self.out_sr = output_rate(self.model_sr, enhancer)
+        if self.out_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, self.out_sr, int(samplerate)) < 0:
+            raise ValueError(f"StreamRenderer: cannot resample {self.out_sr} Hz to {samplerate} Hz")
+        self._resamplers = {}
         self.spk_id = torch.full((1, 1), int(spk_id), dtype=torch.int64, device=self.device)
+        self.spk_mix_dict = self._checked_mix(spk_mix_dict)
         self.features = features
+        self.use_graph = bool(use_graph)
         self.graph = None
-        if use_graph:
-            import graphed
-            self.graph = graphed.GraphedSynth(self.model, 1, self.frames)
+        self.graph_builds = 0                                        # captures so far (a mix change re-captures)
+        if self.use_graph:
+            self._capture()
+
+    def _capture(self):
+        import graphed
+        self.graph = None                                            # the old capture is released before the new one
+        self.graph = graphed.GraphedSynth(self.model, 1, self.frames, spk_mix_dict=self.spk_mix_dict)
+        self.graph_builds += 1
+
+    def _checked_mix(self, spk_mix_dict):
+        if spk_mix_dict is None:
+            return None
+        n_spk = int(self.model.unit2ctrl.n_spk)
+        mix = {int(k): float(v) for k, v in spk_mix_dict.items()}
+        if not 1 <= len(mix) <= 16 or any(not 1 <= k <= n_spk for k in mix):
+            raise ValueError(f"StreamRenderer: a speaker mix holds 1 to 16 ids in [1, {n_spk}], got {spk_mix_dict}")
+        return mix
+
+    def set_speaker(self, spk_id=None, spk_mix_dict=None):
+        """Live speaker change (the GUI's speaker id / "set mix"): `spk_mix_dict` replaces the mix (None = use `spk_id`),
+        `spk_id` (if given) replaces the id.  A new mix re-captures the graph (its weights are kernel arguments); an id
+        alone does not (it is a static input of the capture)."""
+        n_spk = int(self.model.unit2ctrl.n_spk)
+        if spk_id is not None and not 1 <= int(spk_id) <= n_spk:
+            raise ValueError(f"StreamRenderer: spk_id must be in [1, {n_spk}], got {spk_id}")
+        mix = self._checked_mix(spk_mix_dict)
+        if spk_id is not None:
+            self.spk_id.fill_(int(spk_id))
+        if mix != self.spk_mix_dict:
+            self.spk_mix_dict = mix
+            if self.use_graph:
+                self._capture()
+
+    def _key(self, f0):
+        """The enhancer's key for this window: a number as configured, or the reference's 'auto' rule over the track
+        after the enhancer's front cut (host arithmetic on a CPU track, one scalar read-back otherwise)."""
+        if not isinstance(self.enhancer_adaptive_key, str):
+            return self.enhancer_adaptive_key
+        cut = key_cut_frames(self.silence_front, self.model_sr, self.block_size)
+        return auto_key(float(torch.max(f0[:, cut:])))
+
+    def _to_device_rate(self, audio, rate):
+        if rate == int(self.samplerate):
+            return audio
+        pair = (int(rate), int(self.samplerate))
+        if pair not in self._resamplers:
+            from resample import Resample
+            self._resamplers[pair] = Resample(pair[0], pair[1], lowpass_filter_width=128)
+        return self._resamplers[pair](audio)
 
     @torch.no_grad()
-    def push_block(self, block_in, units=None, f0=None, noise=None):
+    def push_block(self, block_in, units=None, f0=None, noise=None, rand_ini=None):
         """block_in (block,) device samples of the stream -> (block,) samples to play.  `units` (1, Fr, C) and `f0`
         (1, Fr, 1) of the CURRENT window may be passed instead of a `features` callable; `noise` (1, Fr*hop) in [0, 1)
-        replaces the fresh draw (parity tests)."""
+        replaces the fresh draw and `rand_ini` (9,) the enhancer's source phases (parity tests)."""
         if block_in.numel() != self.block:
             raise ValueError(f"StreamRenderer: a block is {self.block} samples, got {block_in.numel()}")
         self.window = torch.cat([self.window[self.block:], block_in.reshape(-1).to(self.device, torch.float32)])
         ctx = hipddsp.context_for(self.device)
-        volume = ctx.volume_extract(self.window[None], self.hop)       # (1, Fr)
         if units is None or f0 is None:
             if self.features is None:
                 raise ValueError("StreamRenderer: pass units and f0, or construct it with a `features` callable")
             units, f0 = self.features(self.window)
-        if units.shape[1] != self.frames or f0.shape[1] != self.frames or volume.shape[1] != self.frames:
+        if units.shape[1] != self.frames or f0.shape[1] != self.frames:
+            raise ValueError(f"StreamRenderer: the window has {self.frames} frames")
+        if self.pitch_adjust != 0:
+            f0 = f0 * 2 ** (self.pitch_adjust / 12)
+        key = None
+        if self.enhancer is not None:
+            key = self._key(f0)                                      # before anything of this block is enqueued
+        units, f0 = units.to(self.device), f0.to(self.device)
+        volume = ctx.volume_extract(self.window[None], self.hop_size)   # (1, Fr)
+        if volume.shape[1] != self.frames:
             raise ValueError(f"StreamRenderer: the window has {self.frames} frames")
         if self.graph is not None:
             sig = self.graph(units, f0, volume, self.spk_id, noise=noise)[0]
         elif noise is not None:
-            sig = self.model(units, f0, volume, self.spk_id, noise=noise)[0]
+            sig = self.model(units, f0, volume, self.spk_id, spk_mix_dict=self.spk_mix_dict, noise=noise)[0]
         else:
-            sig = self.model(units, f0, volume, self.spk_id)[0]
+            sig = self.model(units, f0, volume, self.spk_id, spk_mix_dict=self.spk_mix_dict)[0]
         ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
-        return self.splicer.push(sig[0])
+        rate = self.model_sr
+        if self.enhancer is not None:
+            sig, rate = self.enhancer.enhance(sig, self.model_sr, f0, self.block_size, adaptive_key=key,
+                                              silence_front=self.silence_front, rand_ini=rand_ini)
+            self.last_key = key
+        return self.splicer.push(self._to_device_rate(sig, rate)[0])

@@ -261,6 +261,13 @@ int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, const float* vo
  * exceed (hop+1)/2). */
 int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
                         float* volume);
+/* the same at the non-integral hop `block_size * sample_rate / model_rate` that an input at another rate than the model's
+ * gives (main.py:72,109, gui.py:94): volume (B, int(T // hop_size) + 1), block n = padded[int(n * hop_size) :
+ * int((n + 1) * hop_size)] of the signal reflect-padded by (int(hop_size // 2), int((hop_size + 1) // 2)), all in fp64
+ * like the reference's Python floats; each block's mean divides by its own length.  1 <= hop_size <= 2^20, and T must
+ * exceed int((hop_size + 1) // 2).  An integral hop_size gives exactly what ddsp_volume_extract gives. */
+int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, double hop_size,
+                             float* volume);
 /* replaces the alignment tail of ddsp/vocoder.py:201-211 `Units_Encoder.encode`: out[b][i][:] = units[b][j][:] with
  * j = min(rint(ratio * i), Lu - 1), ratio = (hop/sample_rate) / (encoder_hop/encoder_sample_rate) as fp32, rint =
  * round half to even (torch.round); units (B,Lu,C) -> out (B,n_frames,C). */
