@@ -52,7 +52,7 @@ extern "C" int ddsp_ctx_destroy(ddsp_ctx* ctx) {
 
 extern "C" int ddsp_ctx_set_math(ddsp_ctx* ctx, int math) {
     if (!ctx) return DDSP_ERR_ARG;
-    // (4: split-bf16 with the operand split inside the GEMM loops - measurement aid, see unit2ctrl.hip)
+    // (4: split-bf16 with every operand split inside the GEMM loops, test_presplit_operands_give_the_same_bits)
     DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16 || math == 4, "ddsp_ctx_set_math: unknown mode");
     ctx->math = math;
     return DDSP_OK;

@@ -309,15 +309,6 @@ __global__ void __launch_bounds__(256) fir_act_bwd_kernel(int mode, const float*
 }  // namespace
 
 
-static bool dyn_fast() {   // DDSP_FIR_DYN_FAST=0: the exact window arithmetic in every mode (measurement aid)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_FIR_DYN_FAST");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
 extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const float* ctrl, int64_t ctrl_ld,
                                   int n_mag, const float* f0_frames, int64_t rows, int sr, float* ir) {
     DDSP_REQUIRE(ctx, ctx && ctrl && ir, "ddsp_fir_from_ctrl: null argument");
@@ -351,12 +342,7 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
     // operands already split (the DMA kernel is certain at these sizes; B = B_split makes a fallback fail loudly)
     const bool presplit = tap_major && tab_split && rows >= 8192 && M % 8 == 0 && ctx->math != 4;
     ddsp_prof_begin(ctx, st, PF_FIR_ACT);
-    static int act_wide = -1;   // DDSP_FIR_ACT_WIDE=0: one bin per lane and pass at every shape (measurement aid)
-    if (act_wide < 0) {
-        const char* e = getenv("DDSP_FIR_ACT_WIDE");
-        act_wide = (e && e[0] == '0') ? 0 : 1;
-    }
-    const bool wide = act_wide && M % 8 == 0 && ctrl_ld % 4 == 0 && lda % 8 == 0 && ((uintptr_t)ctrl % 16) == 0;
+    const bool wide = M % 8 == 0 && ctrl_ld % 4 == 0 && lda % 8 == 0 && ((uintptr_t)ctrl % 16) == 0;
     if (wide && mode != DDSP_FIR_ALLPASS)
         hipLaunchKernelGGL(fir_act_exp8_kernel, dim3((unsigned)ceil_div64(rows * (M / 8), 256)), dim3(256), 0, st,
                            mode == DDSP_FIR_STATIC ? 1.0f / 128.0f : 1.0f, ctrl, ctrl_ld, M, lda, rows, act, presplit ? 1 : 0);
@@ -391,7 +377,7 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
         // even filter: taps 0..n/2 from the GEMM, the rest mirrored by the epilogue
         gemm::Args g = gemm::make(act, lda, tab, ldb, (int)rows, n / 2 + 1, K);
         if (mode == DDSP_FIR_DYNAMIC)
-            run(g, EpiDynWindow{ir, n, f0_frames, 1.5f * (float)sr, (tap_major && ctx->math != DDSP_MATH_FP32 && dyn_fast()) ? 1 : 0});
+            run(g, EpiDynWindow{ir, n, f0_frames, 1.5f * (float)sr, (tap_major && ctx->math != DDSP_MATH_FP32) ? 1 : 0});
         else
             run(g, EpiMirrorStore{ir, n});
     }
@@ -416,14 +402,9 @@ extern "C" int ddsp_fir_from_ctrl_bwd(ddsp_ctx* ctx, void* stream, int mode, con
     const int lda = ddsp_pad4(K);
     // The contraction over the n taps (510 / 1022: rows of d_ir are not 16-byte aligned) is a linear map of the gradient: with
     // split-bf16 products allowed it runs on the LDS-DMA kernel from a copy of d_ir with the table's row pitch (512 / 1024, zero
-    // pad columns) instead of the register-staged fp32 kernel.  DDSP_FIR_BWD_DMA=0: the fp32 kernel (measurement aid)
-    static int bwd_dma = -1;
-    if (bwd_dma < 0) {
-        const char* e = getenv("DDSP_FIR_BWD_DMA");
-        bwd_dma = (e && e[0] == '0') ? 0 : 1;
-    }
+    // pad columns) instead of the register-staged fp32 kernel
     const int ldp = ddsp_pad4(n);
-    const bool repack = bwd_dma && ctx->math != DDSP_MATH_FP32 && ldp % 32 == 0 && rows >= 1024;
+    const bool repack = ctx->math != DDSP_MATH_FP32 && ldp % 32 == 0 && rows >= 1024;
     int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)rows * (lda + (repack ? ldp : 0)) * sizeof(float) + 8192);
     if (rc) return rc;
     ddsp_scratch_reset(ctx);

@@ -69,7 +69,8 @@ struct Args {
     // (the leftover tiles_m % 8 row blocks are dealt round-robin as before).
     int xcd;
     // ... and the launch covers all tiles but the last xcd_cut of the linear order (a multiple of 8, at most the leftover
-    // region: every XCD's queue is one tile shorter per 8), which a second launch runs as quadrant tiles (sub_from)
+    // region: every XCD's queue is one tile shorter per 8), which a second launch runs as quadrant tiles (sub_from).
+    // Every launcher leaves it 0: the XCD-order tail cut measured slower and was removed (gemm::launch).
     int xcd_cut;
     // DMA kernel: batch index z also starts its k range kz floats into A's and B's rows (the taps of an implicit-im2col
     // convolution follow from the shifted k): a K-split whose partial products the caller's epilogue stores per z
@@ -747,20 +748,13 @@ inline void launch_dma(hipStream_t st, const Args& g, int batch, const Epi& epi,
 // launch_dma with the product arithmetic chosen at run time (Args::math)
 // XCD-aware tile order: on for the split-bf16 GEMMs, whose loops no longer hide the eightfold A re-reads of the
 // round-robin order (r02: Linear family 0.395 -> 0.373 ms, HBM/fabric traffic of a pw1 call 114 -> ~35 MB); off for fp32
-// products, where round 1 measured it slower (0.76 -> 0.84 ms).  DDSP_GEMM_XCD = 0 / 1 forces it (measurement aid).
-inline int xcd_default(int math) {
-    static int env = -2;
-    if (env == -2) {
-        const char* e = getenv("DDSP_GEMM_XCD");
-        env = e ? (e[0] == '1' ? 1 : 0) : -1;
-    }
-    return env >= 0 ? env : (math == 3 ? 1 : 0);
-}
+// products, where round 1 measured it slower (0.76 -> 0.84 ms).
+inline int xcd_default(int math) { return math == 3 ? 1 : 0; }
 
 template <int BM, int BN, class Epi, int NS = 3, int NW = 8, int A_MODE = A_PLAIN>
 inline void dma_go(hipStream_t st, const Args& g0, int batch, const Epi& epi, int total_override = -1) {
     Args g = g0;
-    if (g.xcd < 0) g.xcd = (batch == 1 && (total_override < 0 || g.xcd_cut > 0)) ? xcd_default(g.math) : 0;
+    if (g.xcd < 0) g.xcd = (batch == 1 && total_override < 0) ? xcd_default(g.math) : 0;
     if (g.math == 3 && g.B_split && g.A_split) {
         Args h = g;
         h.B = g.B_split;
@@ -771,8 +765,6 @@ inline void dma_go(hipStream_t st, const Args& g0, int batch, const Epi& epi, in
         launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 7>(st, h, batch, epi, total_override);
     } else if (g.math == 3)
         launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 3>(st, g, batch, epi, total_override);
-    else if (g.math == 6)   // three bf16 pieces per operand, six products: fp32-class error (2.4e-7), callers that ask for it
-        launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 6>(st, g, batch, epi, total_override);
     else
         launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 0>(st, g, batch, epi, total_override);
 }
@@ -783,17 +775,13 @@ inline void launch_tile(hipStream_t st, const Args& g, int batch, const Epi& epi
     hipLaunchKernelGGL((kernel<BM, BN, A_KC, B_KC, A_MODE, Epi, NW>), grid, dim3(64 * NW), 0, st, g, epi);
 }
 
-// workgroups from which the 128x128 tile is preferred to 128x64 (DDSP_GEMM_T128_MIN: measurement aid; 256 instead of 512:
-// training step 6.40 -> 6.51 ms, the B = 47 forward 1.05 -> 1.14 ms - unlike the enhancer's dilated convolutions, which gain
-// from 128x128 tiles from 256 workgroups on, nsf.hip)
-inline int64_t t128_min() {
-    static int64_t v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_GEMM_T128_MIN");
-        v = e ? atoll(e) : 512;
-    }
-    return v;
-}
+// workgroups from which the 128x128 tile is preferred to 128x64 (256 instead of 512: training step 6.40 -> 6.51 ms, the
+// B = 47 forward 1.05 -> 1.14 ms - unlike the enhancer's dilated convolutions, which gain from 128x128 tiles from 256
+// workgroups on, nsf.hip)
+constexpr int64_t T128_MIN = 512;
+
+// DMA ring stages of the small-problem 64x64 tile (r02: real-time block replay 0.449 / 0.422 / 0.427 ms with 3 / 4 / 6 stages)
+constexpr int SMALL_NS = 4;
 
 // Tile choice (measured on MI355X, tools/gemm_ab.py, fp32 TFLOP/s at M = 11008):
 //   K%32==0, row-major A, [N][K] B  -> persistent LDS-DMA kernel, 128x64 tiles, 8 waves  (69-83 at K=256, N=512..1536)
@@ -801,26 +789,6 @@ inline int64_t t128_min() {
 //                                       64x64 / 4 waves for small or skinny problems.
 // Larger tiles raise FLOP per staged byte (the L2->LDS operand stream, ~4-6 TB/s chip-wide, is what caps these
 // K=256..768 shapes near 85 TFLOP/s) but leave CUs idle at 11008 = 2*43*128 rows; see DESIGN.md section 9.
-inline bool half_tiles() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_GEMM_HALF_TILES");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
-// DDSP_GEMM_TAIL_CUT=1 (measurement aid, off): with the XCD-aware order too, the few tiles of a last, nearly empty round are cut
-// out of the launch and run as quadrant tiles in a second one.  Measured at the bench shape (QKV: 1032 = 2 x 512 + 8 tiles):
-// Linear family 0.361 -> 0.372 ms - the eight tail tiles run alone on their CUs and take about what the second launch costs.
-inline bool tail_cut() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_GEMM_TAIL_CUT");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
-}
 
 template <bool A_KC, bool B_KC, int A_MODE, class Epi>
 inline void launch(hipStream_t st, const Args& g, int batch, const Epi& epi) {
@@ -831,7 +799,7 @@ inline void launch(hipStream_t st, const Args& g, int batch, const Epi& epi) {
         // implicit-im2col convs (N = 256): the 4-wave 64x64 DMA tile with one source pointer per tap
         if (dma_ok(g) && g.zeros && g.Cin % 32 == 0 && g.Cin + 32 <= DDSP_ZERO_FLOATS && g.N <= 256) {
             // (also for a few tiles: see the small-problem note below)
-            if (half_tiles() && blocks(64, 64) < 128 && blocks(64, 64) > 16)
+            if (blocks(64, 64) < 128 && blocks(64, 64) > 16)
                 dma_go<32, 64, Epi, 4, 2, A_CONV3>(st, g, batch, epi);
             else
                 dma_go<64, 64, Epi, 3, 4, A_CONV3>(st, g, batch, epi);
@@ -841,28 +809,16 @@ inline void launch(hipStream_t st, const Args& g, int batch, const Epi& epi) {
     if constexpr (A_KC && B_KC && A_MODE == A_PLAIN) {
         // a few tiles and a long K (the 87-frame real-time block: 8 workgroups walking K = 512): the 3-stage DMA ring keeps
         // two k-tiles in flight, the register-staged kernel's one-tile prefetch leaves a global-load latency per k-tile
-        // exposed (real-time block 0.67 -> 0.50 ms).  DDSP_GEMM_SMALL_DMA=0 restores the old choice (measurement aid).
-        static int small_dma = -1;
-        if (small_dma < 0) {
-            const char* e = getenv("DDSP_GEMM_SMALL_DMA");
-            small_dma = (e && e[0] == '0') ? 0 : 1;
-        }
+        // exposed (real-time block 0.67 -> 0.50 ms).
         // Fewer than half the CUs busy with 64x64 tiles (B = 8: 1376 rows x 256 columns = 88 tiles): what bounds a workgroup
         // there is its CU's operand load path, so 32x64 tiles on two waves - twice the workgroups, 3/4 of the bytes each - finish
-        // sooner although they stage more in total.  DDSP_GEMM_HALF_TILES=0 restores 64x64 (measurement aid).
-        if (small_dma && half_tiles() && dma_ok(g) && blocks(64, 64) < 128 && blocks(64, 64) > 16 && g.K >= 256) {
+        // sooner although they stage more in total.
+        if (dma_ok(g) && blocks(64, 64) < 128 && blocks(64, 64) > 16 && g.K >= 256) {
             dma_go<32, 64, Epi, 4, 2>(st, g, batch, epi);
             return;
         }
-        if (small_dma && dma_ok(g) && blocks(64, 64) < 256 && g.K >= 256) {
-            static int small_ns = -1;
-            if (small_ns < 0) {
-                const char* e = getenv("DDSP_GEMM_SMALL_NS");
-                small_ns = e ? atoi(e) : 4;   // r02: real-time block replay 0.449 / 0.422 / 0.427 ms with 3 / 4 / 6 stages
-            }
-            if (small_ns == 6) dma_go<64, 64, Epi, 6, 4>(st, g, batch, epi);
-            else if (small_ns == 4) dma_go<64, 64, Epi, 4, 4>(st, g, batch, epi);
-            else dma_go<64, 64, Epi, 3, 4>(st, g, batch, epi);
+        if (dma_ok(g) && blocks(64, 64) < 256 && g.K >= 256) {
+            dma_go<64, 64, Epi, SMALL_NS, 4>(st, g, batch, epi);
             return;
         }
         if (dma_ok(g) && g.N <= 256 && blocks(64, 64) >= 256) {
@@ -879,7 +835,7 @@ inline void launch(hipStream_t st, const Args& g, int batch, const Epi& epi) {
             // (tools/gemm_ab.py, M=11008: N=256 K=512 35.3 vs 38.8 us, K=768 49.2 vs 54.8 us)
             if (g.N <= 256)
                 dma_go<64, 64, Epi, 3, 4>(st, g, batch, epi);
-            else if (blocks(128, 128) >= t128_min()) {
+            else if (blocks(128, 128) >= T128_MIN) {
                 // 512 resident workgroups walk the tiles in rounds.  When the last round holds only a few tiles (QKV at
                 // the bench shape: 1032 = 2 * 512 + 8) those run alone on their CUs for a whole tile time; they are
                 // cut out of this launch and run as 64x64 tiles on 4 waves instead (4 small workgroups per tile).
@@ -887,15 +843,12 @@ inline void launch(hipStream_t st, const Args& g, int batch, const Epi& epi) {
                 const int rem = total % 512;
                 bool split = false;
                 if constexpr (!epi_is_gated<Epi>::value) {
+                    // Not with the XCD-aware order: there the cut measured slower at the bench shape (Linear family
+                    // 0.361 -> 0.372 ms - the eight tail tiles take about what the second launch costs).
                     const bool xcd_on = g.xcd > 0 || (g.xcd < 0 && xcd_default(g.math));
-                    // (XCD order: the cut tiles must come off every XCD's queue evenly and out of the leftover row blocks)
-                    const int tm = (g.M + 127) / 128, tn = (g.N + 127) / 128;
-                    const bool cut_ok = !xcd_on || (tail_cut() && rem % 8 == 0 && rem <= (tm % 8) * tn);
-                    if (batch == 1 && rem > 0 && rem <= 64 && cut_ok) {
+                    if (batch == 1 && rem > 0 && rem <= 64 && !xcd_on) {
                         split = true;
-                        Args m = g;
-                        if (xcd_on) m.xcd_cut = rem;
-                        dma_go<128, 128, Epi, 2>(st, m, batch, epi, total - rem);
+                        dma_go<128, 128, Epi, 2>(st, g, batch, epi, total - rem);
                         Args r = g;
                         r.xcd = 0;
                         r.sub_from = total - rem;

@@ -318,13 +318,7 @@ inline hipError_t launch_res_ln_rb(hipStream_t st, const LnArgs& g, const Pre& p
 }
 // a_split: A is in the pre-split layout (else fp32 rows)
 inline hipError_t launch_res_ln(hipStream_t st, const LnArgs& g, bool a_split = true) {
-    static int rb = -1;     // DDSP_GEMM_LN_RB=1: sixteen waves of one 32 x 32 block each (measurement aid)
-    if (rb < 0) {
-        const char* e = getenv("DDSP_GEMM_LN_RB");
-        rb = (e && e[0] == '1') ? 1 : 2;
-    }
-    if (!a_split) return launch_res_ln_rb<2, false>(st, g);
-    return rb == 1 ? launch_res_ln_rb<1, true>(st, g) : launch_res_ln_rb<2, true>(st, g);
+    return a_split ? launch_res_ln_rb<2, true>(st, g) : launch_res_ln_rb<2, false>(st, g);
 }
 
 }  // namespace gemm

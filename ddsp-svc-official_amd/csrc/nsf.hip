@@ -15,7 +15,6 @@
 // These kernels are correct-first: fp32 MFMA on the register-staged GEMM kernel, no tuning (the enhancer is the step after
 // the hot path, not part of the benchmarked one).
 #include "gemm_f32.h"
-#include "gemm_ws.h"
 
 #include <stdlib.h>
 
@@ -801,15 +800,6 @@ static int launch_conv_small32_bf16(ddsp_ctx* ctx, hipStream_t st, const ConvSma
     return DDSP_OK;
 }
 
-static bool conv_small32_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_CONV_SMALL32");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
-}
-
 template <int C>
 static int launch_conv_small(ddsp_ctx* ctx, hipStream_t st, const ConvSmallArgs& g) {
     const int halo = (g.ktaps - 1) / 2 * g.dil, rows = CS_TW + 2 * halo;
@@ -858,45 +848,6 @@ struct EpiAddBias {   // y = acc + bias[n] (+ res): C = y and / or Cact = leaky_
             else
                 *(f32x4*)(Cact + o) = v;
         }
-    }
-};
-
-// EpiAddBias for the wave-specialised kernel (gemm_ws.h): bias through the loaders' LDS copy, the residual tile (RES) too
-template <bool RES>
-struct WsConv {
-    float* C;
-    float* Cact;
-    const float* res;
-    int64_t ldc;
-    const float* bias;
-    float slope;
-    int act_split;
-    static constexpr bool kExtra = RES, kGated = false;
-    __device__ __forceinline__ f32x4 bias4(int n) const { return bias ? *(const gemm::f32x4_u*)(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f}; }
-    __device__ __forceinline__ float bias1(int n) const { return bias ? bias[n] : 0.f; }
-    __device__ __forceinline__ const float* extra_ptr() const { return res; }
-    __device__ __forceinline__ void emit4(int, int m, int n, f32x4 v, f32x4 e) const {
-        const int64_t o = (int64_t)m * ldc + n;
-        if constexpr (RES) v = v + e;
-        if (C) *(f32x4*)(C + o) = v;
-        if (Cact) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * slope;
-            if (act_split)   // the lane 4 further on holds the other half of this group of 8 columns (same row)
-                *(ddsp_u32x4*)(Cact + o) = ddsp_split4_pair(v, (n & 4) != 0, 4);
-            else
-                *(f32x4*)(Cact + o) = v;
-        }
-    }
-    __device__ __forceinline__ void emit1(int, int m, int n, float v) const {   // (edge path: never taken, the launcher asks for whole tiles)
-        const int64_t o = (int64_t)m * ldc + n;
-        if (RES) v += res[o];
-        if (C) C[o] = v;
-        if (Cact && !act_split) Cact[o] = v > 0.f ? v : v * slope;
-    }
-    __host__ __device__ const float* bias_ptr() const { return bias; }
-    __host__ bool vec_ok() const {
-        return (((uintptr_t)C | (uintptr_t)Cact | (uintptr_t)res | (uintptr_t)bias) % 16) == 0 && ldc % 4 == 0;
     }
 };
 
@@ -1188,20 +1139,16 @@ extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const fl
     ddsp_prof_begin(ctx, st, PF_OTHER);
     if (Cin == Cout && Cin == 16 && !x_split && !act_split && ((uintptr_t)x % 16) == 0 && (ktaps - 1) / 2 * dil <= CS_MAX_HALO) {
         // the narrow last stage: fp32 matrix products on tiles of its own width (conv_small_kernel; 1.87 -> 0.74 ms for the 18
-        // convolutions of the 16-channel stage at 860 frames).  The 32-channel instantiation is kept for measurements
-        // (DDSP_CONV_SMALL32=1): at 1.48 ms per stage it does not beat the LDS-DMA GEMM's 1.28 - one wave per SIMD (105 KB of
-        // LDS per workgroup) on the fp32 matrix pipe reaches a third of its rate.
+        // convolutions of the 16-channel stage at 860 frames).  A 32-channel fp32 instantiation was measured and removed: at
+        // 1.48 ms per stage it did not beat the LDS-DMA GEMM's 1.28 - one wave per SIMD (105 KB of LDS per workgroup) on the
+        // fp32 matrix pipe reaches a third of its rate.
         ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, T, ktaps, dil, in_slope, act_slope};
         if (int rc = launch_conv_small<16>(ctx, st, a)) return rc;
-    } else if (Cin == Cout && Cin == 32 && ctx->math != DDSP_MATH_FP32 && !conv_small32_enabled() && !x_split && !act_split &&
+    } else if (Cin == Cout && Cin == 32 && ctx->math != DDSP_MATH_FP32 && !x_split && !act_split &&
                (((uintptr_t)x | (uintptr_t)w_packed) % 16) == 0 && (ktaps - 1) / 2 * dil <= CS_MAX_HALO) {
         // the 32-channel stage in split-bf16 arithmetic: the narrow kernel with bf16 fragments
         ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, T, ktaps, dil, in_slope, act_slope};
         if (int rc = launch_conv_small32_bf16(ctx, st, a)) return rc;
-    } else if (Cin == Cout && Cin == 32 && conv_small32_enabled() && !x_split && !act_split && ((uintptr_t)x % 16) == 0 &&
-               (ktaps - 1) / 2 * dil <= CS_MAX_HALO) {
-        ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, T, ktaps, dil, in_slope, act_slope};
-        if (int rc = launch_conv_small<32>(ctx, st, a)) return rc;
     } else if (dma) {
         // an input that needs no activation on load: the LDS-DMA kernel with per-tap row pointers, products in the context's
         // arithmetic (split-bf16 by default, ddsp_ctx_set_math(FP32) for fp32 products)
@@ -1212,63 +1159,22 @@ extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const fl
             g.A_split = x_split ? 1 : 0;
             if (x_split) g.B = w_split;   // (mode 8 reads only the split copies)
         }
-        // Long products with pre-split weights at sizes that fill the chip CAN run on the wave-specialised kernel (gemm_ws.h) with
-        // per-tap row pointers - 128x128 tiles without a residual, 128x64 with one (its tile travels through the LDS too).
-        // Measured at 860 frames (rocprofv3, per launch): 128x128 without residual 53.4 -> 48.7 us; 128x64 without residual 45.2 ->
-        // 44.9; with the residual tile (128x64 also for the 128-channel stage, whose rows are then staged twice) 63 us against
-        // 45 - 53 on kernel_dma; the generator as a whole 3.66 ms with either choice (3.69 with the 128x128 form, 3.64 with all).
-        // OFF by default: DDSP_CONV_WS bit 1 = the 128x128 form, bit 2 = the 128x64 forms as well (measurement aid).
-        static int conv_ws = -1;
-        if (conv_ws < 0) {
-            const char* ev = getenv("DDSP_CONV_WS");
-            conv_ws = ev ? atoi(ev) : 0;
-        }
-        if (conv_ws && g.math == DDSP_MATH_SPLIT_BF16 && g.B_split && Cout % 64 == 0 && gemm::ws_ok(g, 5, residual != nullptr)) {
-            hipError_t he = hipErrorInvalidValue;
-            bool ran = false;
-            if (residual) {
-                WsConv<true> ew{out, out_act, residual, Cout, bias, act_slope, act_split ? 1 : 0};
-                if ((conv_ws & 2) && ew.vec_ok() && blocks(128, 64) >= 256) {
-                    he = gemm::ws_conv_go<128, 64, WsConv<true>, 5>(st, g, ew);
-                    ran = true;
-                }
-            } else {
-                WsConv<false> ew{out, out_act, nullptr, Cout, bias, act_slope, act_split ? 1 : 0};
-                if (ew.vec_ok() && Cout % 128 == 0 && blocks(128, 128) >= 256) {
-                    he = gemm::ws_conv_go<128, 128, WsConv<false>, 4>(st, g, ew);
-                    ran = true;
-                } else if ((conv_ws & 2) && ew.vec_ok() && blocks(128, 64) >= 256) {
-                    he = gemm::ws_conv_go<128, 64, WsConv<false>, 5>(st, g, ew);
-                    ran = true;
-                }
-            }
-            if (ran) {
-                DDSP_HIP(ctx, he);
-                ddsp_prof_end(ctx, st, 2.0 * T * (double)Cout * ktaps * Cin, 4.0 * T * ((double)Cin + Cout));
-                DDSP_LAUNCH_CHECK(ctx);
-                return DDSP_OK;
-            }
-        }
-        static int conv_tile = -1;
-        if (conv_tile < 0) {
-            // tile choice (860 frames, generator 5.86 / 5.53 / 5.19 ms with 0 / 1 / 2): 0 = 64x64 on 4 waves everywhere,
-            // 1 = 128x64 on 8 waves where that still gives 512 workgroups, 2 = also 128x128 for 128-channel multiples from 256
-            // workgroups (the 128-channel stage: 1.45 -> 0.99 ms, one column tile instead of two re-reading the input)
-            // 3 = also 64x128 on 4 waves for the 128-channel multiples that fill neither (the 256-channel stage at 6880 rows and
-            // the transposed convolutions: 5.17 -> 4.98 ms; 4 = 128x128 there instead: 5.18)
-            const char* ev = getenv("DDSP_CONV_TILE");
-            conv_tile = ev ? atoi(ev) : 3;
-        }
+        // The wave-specialised kernel (gemm_ws.h) with per-tap row pointers was measured here and removed: at 860 frames
+        // (rocprofv3, per launch) 128x128 without residual 53.4 -> 48.7 us, 128x64 without residual 45.2 -> 44.9, with the
+        // residual tile 63 us against 45 - 53 on kernel_dma; the generator as a whole 3.66 ms with either choice.
+        // Tile choice (860 frames, generator 5.86 / 5.53 / 5.19 ms with the first / second / third rule below): 64x64 on 4 waves
+        // everywhere, 128x64 on 8 waves where that still gives 512 workgroups, also 128x128 for 128-channel multiples from 256
+        // workgroups (the 128-channel stage: 1.45 -> 0.99 ms, one column tile instead of two re-reading the input); then also
+        // 64x128 on 4 waves for the 128-channel multiples that fill neither (the 256-channel stage at 6880 rows and the
+        // transposed convolutions: 5.17 -> 4.98 ms; 128x128 there instead: 5.18)
         if (Cout > 256 && blocks(128, 128) >= 512)
             gemm::dma_go<128, 128, EpiAddBias, 2, 8, gemm::A_CONVK>(st, g, 1, e);
-        else if (conv_tile >= 2 && Cout % 128 == 0 && blocks(128, 128) >= 256)
+        else if (Cout % 128 == 0 && blocks(128, 128) >= 256)
             gemm::dma_go<128, 128, EpiAddBias, 2, 8, gemm::A_CONVK>(st, g, 1, e);
-        else if (conv_tile >= 1 && blocks(128, 64) >= 512)
+        else if (blocks(128, 64) >= 512)
             gemm::dma_go<128, 64, EpiAddBias, 3, 8, gemm::A_CONVK>(st, g, 1, e);
-        else if (conv_tile == 3 && Cout % 128 == 0 && blocks(64, 128) >= 128)
+        else if (Cout % 128 == 0 && blocks(64, 128) >= 128)
             gemm::dma_go<64, 128, EpiAddBias, 3, 4, gemm::A_CONVK>(st, g, 1, e);
-        else if (conv_tile == 4 && Cout % 128 == 0 && blocks(128, 128) >= 64)
-            gemm::dma_go<128, 128, EpiAddBias, 2, 8, gemm::A_CONVK>(st, g, 1, e);
         else
             gemm::dma_go<64, 64, EpiAddBias, 3, 4, gemm::A_CONVK>(st, g, 1, e);
     } else if (blocks(128, 64) >= 512)

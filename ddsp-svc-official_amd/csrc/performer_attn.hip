@@ -216,29 +216,6 @@ __global__ void __launch_bounds__(256, 4) performer_kv_split_kernel(const float*
     performer_kv_item<true>(k, v, P, Fr, ctxT, ks, bh, jt, wave, part);
 }
 
-// Measurement variant (DDSP_ATTN_PERSIST=1, tools/attn_dispatch.py): as many waves as the chip holds at once, each
-// pulling (utterance-head, tile) items from a counter until none is left - no partly filled last round.  Consecutive
-// item numbers are consecutive tiles of one (utterance, head), so the waves of a workgroup still share rows in L1.
-__global__ void __launch_bounds__(256, 4) performer_kv_persist_kernel(const float* __restrict__ k, const float* __restrict__ v,
-                                                                      const float* __restrict__ P, int Fr,
-                                                                      float* __restrict__ ctxT, float* __restrict__ ks,
-                                                                      int* __restrict__ counter, int n_items) {
-    // n_items = workgroup items per XCD; counter[xcd]: the same (utterance-head -> XCD, 4 neighbouring tiles per
-    // workgroup) mapping as the grid version, only pulled instead of dispatched
-    const int xcd = blockIdx.x & 7;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    __shared__ int s_item;
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = atomicAdd(counter + xcd, 1);
-        __syncthreads();
-        const int slot = s_item;
-        if (slot >= n_items) return;
-        const int grp = slot % KV_GROUPS, bh = (slot / KV_GROUPS) * 8 + xcd, jt = 4 * grp + wave;
-        if (jt < NJT) performer_kv_item<false>(k, v, P, Fr, ctxT, ks, bh, jt);
-    }
-}
-
 // PART = false: one wavefront walks all 17 feature tiles of its frame tile and stores the result.
 // PART = true (few work items: the real-time block, strong-scaled shards): the wavefront walks the feature tiles jt0 .. jt1-1
 // only and leaves (row maximum, D, out^T) relative to ITS maximum in `part` - the four waves of a workgroup share one frame
@@ -415,26 +392,6 @@ __global__ void __launch_bounds__(256, 4) performer_q_split_kernel(const float* 
 #pragma unroll
     for (int r = 0; r < 4; ++r) res[r] = (o[r] + __shfl(cs_eps, 16 * wave + 4 * g + r, 64)) * dinv;
     if (frame < Fr) *(f32x4_t*)(attn + ((int64_t)b * Fr + frame) * INNER + h * DH + 4 * g + 16 * wave) = res;
-}
-
-__global__ void __launch_bounds__(256, 4) performer_q_persist_kernel(const float* __restrict__ q, const float* __restrict__ P,
-                                                                     const float* __restrict__ ctxT,
-                                                                     const float* __restrict__ ks, int Fr,
-                                                                     float* __restrict__ attn, int* __restrict__ counter,
-                                                                     int n_items, int n_ft) {
-    const int xcd = blockIdx.x & 7;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n_grp = (n_ft + 3) / 4;
-    __shared__ int s_item;
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_item = atomicAdd(counter + xcd, 1);
-        __syncthreads();
-        const int slot = s_item;
-        if (slot >= n_items) return;
-        const int grp = slot % n_grp, bh = (slot / n_grp) * 8 + xcd, ft = 4 * grp + wave;
-        if (ft < n_ft) performer_q_item<false>(q, P, ctxT, ks, Fr, attn, bh, ft);
-    }
 }
 
 // ---- causal linear attention in chunks (ddsp/pcmer.py:170-188, `c: true`; round 3) ---------------------------------------------
@@ -653,30 +610,13 @@ __global__ void __launch_bounds__(256, 2) performer_causal_kernel(const float* _
 
 }  // namespace
 
-// measurement switch: DDSP_ATTN_PERSIST=1 runs the persistent variants (a device counter per launch, zeroed on the stream)
-static int* persist_counter() {
-    static int* ctr = nullptr;
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("DDSP_ATTN_PERSIST");
-        on = (e && e[0] == '1') ? 1 : 0;
-        if (on && hipMalloc((void**)&ctr, 128) != hipSuccess) on = 0;
-    }
-    return on ? ctr : nullptr;
-}
+// (utterance, head) pairs up to which the frame tiles of an item are dealt over four waves
+constexpr int KV_SPLIT_MAX = 128;
+// work items up to which the feature range is split over four waves
+constexpr int Q_SPLIT_MAX = 1024;
 
 void performer_kv(hipStream_t st, const float* k, const float* v, const float* P, int B, int Fr, float* ctxT, float* ks) {
-    if (int* ctr = persist_counter()) {
-        (void)hipMemsetAsync(ctr, 0, 32, st);
-        hipLaunchKernelGGL(performer_kv_persist_kernel, dim3(1024), dim3(256), 0, st, k, v, P, Fr, ctxT, ks, ctr, KV_GROUPS * B);
-        return;
-    }
-    static int kv_split_max = -1;   // DDSP_ATTN_KVSPLIT_MAX: (utterance, head) pairs up to which the frame tiles of an item are dealt over four waves
-    if (kv_split_max < 0) {
-        const char* e = getenv("DDSP_ATTN_KVSPLIT_MAX");
-        kv_split_max = e ? atoi(e) : 128;
-    }
-    if (B * H <= kv_split_max) {
+    if (B * H <= KV_SPLIT_MAX) {
         hipLaunchKernelGGL(performer_kv_split_kernel, dim3((unsigned)(NJT * B * H)), dim3(256), 0, st, k, v, P, Fr, ctxT, ks);
         return;
     }
@@ -687,20 +627,8 @@ void performer_kv(hipStream_t st, const float* k, const float* v, const float* P
 void performer_q(hipStream_t st, const float* q, const float* P, const float* ctxT, const float* ks, int B, int Fr,
                  float* attn) {
     const int n_grp = ((Fr + 15) / 16 + 3) / 4;
-    if (int* ctr = persist_counter()) {
-        const int n_ft = (Fr + 15) / 16;
-        (void)hipMemsetAsync(ctr + 8, 0, 32, st);
-        hipLaunchKernelGGL(performer_q_persist_kernel, dim3(1024), dim3(256), 0, st, q, P, ctxT, ks, Fr, attn, ctr + 8,
-                           n_grp * B, n_ft);
-        return;
-    }
     const int n_ft = (Fr + 15) / 16;
-    static int split_max = -1;      // DDSP_ATTN_QSPLIT_MAX: work items up to which the feature range is split over four waves
-    if (split_max < 0) {
-        const char* e = getenv("DDSP_ATTN_QSPLIT_MAX");
-        split_max = e ? atoi(e) : 1024;
-    }
-    if ((int64_t)n_ft * B * H <= split_max) {
+    if ((int64_t)n_ft * B * H <= Q_SPLIT_MAX) {
         hipLaunchKernelGGL(performer_q_split_kernel, dim3((unsigned)(n_ft * B * H)), dim3(256), 0, st, q, P, ctxT, ks, Fr, n_ft, attn);
         return;
     }

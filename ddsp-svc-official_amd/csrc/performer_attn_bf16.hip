@@ -952,28 +952,18 @@ void performer_kv_bf16(hipStream_t st, const float* k, const float* v, const voi
 }
 
 void performer_q_bf16(hipStream_t st, const float* q, const void* p3, const float* ctxS, const float* ks, int B, int Fr,
-                      float* attn, int ablate, int out_split) {
+                      float* attn, int ablate) {
     const int n_fg = ((Fr + 31) / 32 + QW - 1) / QW;
 #define Q_ABL(A)                                                                                                       \
     if (ablate == A) {                                                                                                 \
         hipLaunchKernelGGL(performer_q_bf16_kernel<A>, dim3((unsigned)(n_fg * B * H)), dim3(64 * QW), 0, st, q,        \
-                           (const uint4*)p3, (const uint4*)ctxS, ks, Fr, n_fg, attn, out_split);                       \
+                           (const uint4*)p3, (const uint4*)ctxS, ks, Fr, n_fg, attn, 0);                               \
         return;                                                                                                        \
     }
     Q_ABL(1) Q_ABL(2) Q_ABL(4) Q_ABL(6) Q_ABL(7)
 #undef Q_ABL
     hipLaunchKernelGGL(performer_q_bf16_kernel<0>, dim3((unsigned)(n_fg * B * H)), dim3(64 * QW), 0, st, q, (const uint4*)p3,
-                       (const uint4*)ctxS, ks, Fr, n_fg, attn, out_split);
-}
-
-// DDSP_ATTN_FUSED=0: the round-2 kernel pair (measurement aid)
-bool performer_fused_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("DDSP_ATTN_FUSED");
-        on = (e && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
+                       (const uint4*)ctxS, ks, Fr, n_fg, attn, 0);
 }
 
 hipError_t performer_fused_bf16(hipStream_t st, const float* q, const float* k, const float* v, const void* p3, int B, int Fr,
@@ -1024,7 +1014,7 @@ extern "C" int ddsp_performer_attention(ddsp_ctx* ctx, void* stream, const float
     if ((rc = ddsp_scratch_get(ctx, n_cx * sizeof(float), (void**)&cx))) return rc;
     if ((rc = ddsp_scratch_get(ctx, n_ks * sizeof(float), (void**)&ksb))) return rc;
     if ((rc = ddsp_scratch_get(ctx, PERFORMER_P3_BYTES, &p3))) return rc;
-    if (math == DDSP_MATH_SPLIT_BF16 && performer_fused_enabled() && !want_pair) {
+    if (math == DDSP_MATH_SPLIT_BF16 && !want_pair) {
         performer_p3(st, proj, nullptr, nullptr, p3);
         ddsp_prof_begin(ctx, st, PF_U2C_GEMM_CTX);
         DDSP_HIP(ctx, performer_fused_bf16(st, q, k, v, p3, (int)B, (int)Fr, out, 0));

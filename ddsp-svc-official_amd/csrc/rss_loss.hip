@@ -285,6 +285,7 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     // scratch sized for the worst scale: the two tables, the framed copy of both signals, S_t, S_p, X_p
+    // DDSP_LOSS_TABLE_1D=0: the direct table kernel (test_tables_from_1d_factors_are_bit_identical)
     static const bool table_1d = [] { const char* e = getenv("DDSP_LOSS_TABLE_1D"); return !(e && e[0] == '0'); }();
     const bool use_1d = table_1d && n_scale <= T1_SCALES;
     size_t t1_doubles = 0;
@@ -315,23 +316,13 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
         }
     }
     // product arithmetic of the two DFT contractions: fp32 matrix products.  (The error of the spectra enters the gradient
-    // through 1/S in near-empty bins, so the split-bf16 x3 class is not an option here; DDSP_LOSS_MATH=6 selects the
-    // six-product form for measurements.)
-    static int loss_math = -1;
-    if (loss_math < 0) {
-        const char* e = getenv("DDSP_LOSS_MATH");
-        loss_math = e ? atoi(e) : 0;
-    }
+    // through 1/S in near-empty bins, so the split-bf16 x3 class is not an option here.)
+    constexpr int LOSS_MATH = DDSP_MATH_FP32;
 
     // The adjoint contraction dXf = dX T^T is a LINEAR map of the spectral gradient: a 4e-6 product error there is a 4e-6 relative
     // error of the gradient, nothing is amplified (unlike the forward spectra, whose error meets 1 / S) - it runs in the context's
-    // arithmetic (split-bf16 by default; DDSP_LOSS_BWD_MATH=0 forces fp32 products, ddsp_ctx_set_math(FP32) does too).
-    static int loss_bwd_env = -2;
-    if (loss_bwd_env == -2) {
-        const char* e = getenv("DDSP_LOSS_BWD_MATH");
-        loss_bwd_env = e ? atoi(e) : -1;
-    }
-    const int loss_bwd_math = loss_bwd_env >= 0 ? loss_bwd_env : (ctx->math == DDSP_MATH_FP32 ? 0 : DDSP_MATH_SPLIT_BF16);
+    // arithmetic (split-bf16 by default, fp32 products under ddsp_ctx_set_math(FP32)).
+    const int loss_bwd_math = ctx->math == DDSP_MATH_FP32 ? 0 : DDSP_MATH_SPLIT_BF16;
     ddsp_prof_begin(ctx, st, PF_RSS_LOSS);
     double flops = 0.0;
     for (int s = 0; s < n_scale; ++s) {
@@ -350,7 +341,7 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
         {
             gemm::Args g = gemm::make(Xf, Kp, tabT, Kp, (int)M, 2 * Mb, Kp);
             g.sA_hi = M * Kp;   // z = 0 target, 1 prediction
-            g.math = loss_math;
+            g.math = LOSS_MATH;
             EpiMag e{St, Sp, Xp, Mb, Kb, eps};
             gemm::launch<true, true, gemm::A_PLAIN>(st, g, 2, e);
         }

@@ -296,12 +296,7 @@ extern "C" int ddsp_sins_bank_bwd(ddsp_ctx* ctx, void* stream, const float* ctrl
     float* partial = nullptr;
     if ((rc = ddsp_scratch_get(ctx, pf * sizeof(float), (void**)&partial))) return rc;
     ddsp_prof_begin(ctx, st, PF_SINS_BANK);
-    static int bwd32 = -1;   // DDSP_SINS_BWD32=0: the per-harmonic reduction at every shape (measurement aid)
-    if (bwd32 < 0) {
-        const char* e = getenv("DDSP_SINS_BWD32");
-        bwd32 = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (bwd32 && hop <= 512 && n_harmonics % 32 == 0)
+    if (hop <= 512 && n_harmonics % 32 == 0)
         hipLaunchKernelGGL(sins_bank_bwd_partial32_kernel, dim3((unsigned)Fr, (unsigned)B), dim3(256), 0, st, phase, d_out,
                            n_harmonics, (int)Fr, hop, partial);
     else

@@ -456,6 +456,10 @@ struct LnPending {
 };
 constexpr int KS_SPLITS = 4;
 constexpr int KS_MAX_ROWS = 256;   // up to 4 row tiles x 4 column tiles x 4 splits = 64 workgroups (344 rows measured slower than whole-K launches)
+// rows from which the inference forward writes its activations pre-split (with the fused-GLU 128x128 tiling)
+constexpr int64_t U2C_PRESPLIT_MIN_ROWS = 8192;
+// (utterance, head) pairs from which the non-causal inference attention runs on the fused split-bf16 kernel
+constexpr int64_t ATTN_BF16_MIN = 256;
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int64_t rows,
                                                         float* __restrict__ out, int split, LnPending pend = LnPending{nullptr, nullptr, nullptr, 0}) {
@@ -573,26 +577,6 @@ __global__ void __launch_bounds__(256) attn_denominator_kernel(const float* __re
     for (int j = lane; j < NF; j += 64) s = fmaf(q[j], k[j], s);
     s = wave_sum(s);
     if (lane == 0) dinv[r] = 1.0f / (s + 1e-8f);
-}
-
-// DDSP_CONV_LN=0: the second prenet convolution and the first LayerNorm as two launches at every size (measurement aid)
-static bool conv_ln_on() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_CONV_LN");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
-// DDSP_CAUSAL_CHUNKED=0: the causal network's inference attention on the sequential kernel below (measurement aid)
-static bool causal_chunked() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_CAUSAL_CHUNKED");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
 }
 
 // ---- causal linear attention (ddsp/pcmer.py:170-188, `c: true`), inference ---------------------------------------------------
@@ -1421,7 +1405,6 @@ struct FeatBwdArgs {
     int Fr;
     const ddsp_u32x4* mat_t; // key side: d_ctx of every (utterance, head) in the projection's layout, for d_v = k' d_ctx; or null
     float* out_v;            // d_v (M, 512)
-    int ablate;              // timing experiments only (DDSP_FEAT_ABLATE): 1 no feature-row loads, 2 no first product, 4 no second product, 8 no staging
 };
 typedef __bf16 fb_bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int FB_WAVES = 4;                                 // 16-frame tiles per workgroup
@@ -1459,7 +1442,7 @@ __global__ void __launch_bounds__(64 * FB_WAVES, 2) attn_feat_bwd_kernel(FeatBwd
             const int j = 16 * blk + (el & 15);
             mu[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             mv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (e < 17 * 2 * 64 && j < NF && !(a.ablate & 8)) {
+            if (e < 17 * 2 * 64 && j < NF) {
                 const float* p = mat + (int64_t)j * DH + 32 * kh + 8 * (el >> 4);
                 mu[i] = *(const f32x4*)p;
                 mv[i] = *(const f32x4*)(p + 4);
@@ -1496,7 +1479,7 @@ __global__ void __launch_bounds__(64 * FB_WAVES, 2) attn_feat_bwd_kernel(FeatBwd
 #pragma unroll
     for (int blk = 0; blk < 17; ++blk) {
         fvv[blk] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (16 * blk + 4 * g < NF && !(a.ablate & 1)) fvv[blk] = *(const f32x4*)(fr + 16 * blk + 4 * g);   // (rows are LDF = 268 floats: the last group that holds a feature is 264..267)
+        if (16 * blk + 4 * g < NF) fvv[blk] = *(const f32x4*)(fr + 16 * blk + 4 * g);   // (rows are LDF = 268 floats: the last group that holds a feature is 264..267)
     }
     const float rs = QUERY ? a.rowscale[row] : 1.0f;
     f32x4 s4[4];
@@ -1507,7 +1490,7 @@ __global__ void __launch_bounds__(64 * FB_WAVES, 2) attn_feat_bwd_kernel(FeatBwd
 #pragma unroll
     for (int blk = 0; blk < 17; ++blk) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (active && !(a.ablate & 2)) {
+        if (active) {
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh) {
                 const ddsp_u32x4* p = mats + (blk * 2 + kh) * 128 + lane;
@@ -1629,7 +1612,6 @@ __global__ void __launch_bounds__(64 * FB_WAVES, 2) attn_feat_bwd_kernel(FeatBwd
         ddsp_u32x4 hi, lo;
         ddsp_split8(y, hi, lo);
         const fb_bf16x8 yh = __builtin_bit_cast(fb_bf16x8, hi), yl = __builtin_bit_cast(fb_bf16x8, lo);
-        if (a.ablate & 4) continue;
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
             const ddsp_u32x4* p = pts + (ks * 4 + blk) * 128 + lane;
@@ -1991,25 +1973,19 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
     const size_t n_w1 = (size_t)D * 3 * w.n_unit, n_w2 = (size_t)D * 3 * D, n_wh = (size_t)w.n_out * D;
     // product arithmetic of the Linear / conv GEMMs (gemm::Args::math): inference uses the split-bf16 mode, the
     // training forward (activations kept for the backward pass) stays on fp32 MFMA like the backward GEMMs
-    // (ctx->math 4 = split-bf16 products with every operand split inside the GEMM loops: the pre-round-2 path, kept as a
-    // measurement / bit-identity aid)
+    // (ctx->math 4 = split-bf16 products with every operand split inside the GEMM loops: the pre-round-2 path, kept for
+    // test_presplit_operands_give_the_same_bits)
     const int lin_math = bf.l[0].pre ? 0 : (ctx->math == 4 ? DDSP_MATH_SPLIT_BF16 : ctx->math);
     const float* zero_page = nullptr;   // source of the conv taps that fall off an utterance (LDS-DMA conv GEMM)
     if (int rc = ddsp_zero_page(ctx, &zero_page)) return rc;
     int* dev_err = nullptr;
     if (int rc = ddsp_dev_error_ptr(ctx, &dev_err)) return rc;
-    // Inference, and enough rows that the Linear layers run the 128x128 DMA tile anyway: GLU is formed inside the pw1
-    // GEMM (half the store, no glu kernel).  Training keeps pw1's raw output for the backward pass; small batches keep
-    // the tile shapes that suit them and the separate glu kernel.
-    // (round 3: at smaller batches too, on 64x128 tiles of 4 waves - one launch and one round trip of the 2 x 512-wide pw1
-    // output fewer per layer; DDSP_GLU_SMALL=0 restores the separate glu kernel below 8065 rows, measurement aid)
-    static int glu_small = -1;
-    if (glu_small < 0) {
-        const char* e = getenv("DDSP_GLU_SMALL");
-        glu_small = (e && e[0] == '0') ? 0 : 1;
-    }
+    // Inference: GLU is formed inside the pw1 GEMM (half the store, no glu kernel) - on the 128x128 DMA tile when there are
+    // enough rows for it (glu_large), else on 64x128 tiles of 4 waves (round 3: one launch and one round trip of the
+    // 2 x 512-wide pw1 output fewer per layer).  Training keeps pw1's raw output for the backward pass and the separate
+    // glu kernel.
     const bool glu_large = !bf.l[0].pre && (int64_t)((M + 127) / 128) * (2 * INNER / 128) >= 512;
-    bool fuse_glu = !bf.l[0].pre && (glu_large || glu_small);
+    bool fuse_glu = !bf.l[0].pre;
     for (int l = 0; l < 3; ++l)
         fuse_glu = fuse_glu && ((uintptr_t)w.layer[l].cm_pw1_w % 16) == 0;
     // Split-bf16 products at a size where every GEMM of the network runs the LDS-DMA kernel: nothing is split inside the
@@ -2021,28 +1997,13 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
     // tiling is used)
     const bool presplit_w = lin_math == DDSP_MATH_SPLIT_BF16 && ctx->math != 4 && w.n_unit % 32 == 0 &&
                             w.n_unit + 32 <= DDSP_ZERO_FLOATS && w.n_out >= 256 && ((uintptr_t)in.units % 16) == 0;
-    static int64_t presplit_min_rows = -1;   // DDSP_U2C_PRESPLIT_MIN_ROWS: measurement aid
-    if (presplit_min_rows < 0) {
-        const char* e = getenv("DDSP_U2C_PRESPLIT_MIN_ROWS");
-        presplit_min_rows = e ? atoll(e) : 8192;
-    }
-    const bool presplit = presplit_w && fuse_glu && glu_large && M >= presplit_min_rows;
-    static int64_t attn_bf16_min = -1;   // DDSP_ATTN_BF16_MIN: (utterance, head) pairs from which the split-bf16 attention runs
-    if (attn_bf16_min < 0) {
-        const char* e = getenv("DDSP_ATTN_BF16_MIN");
-        attn_bf16_min = e ? atoll(e) : 256;
-    }
-    const bool attn_bf16 = !bf.l[0].pre && lin_math == DDSP_MATH_SPLIT_BF16 && B * H >= attn_bf16_min && !w.causal;
+    const bool presplit = presplit_w && fuse_glu && glu_large && M >= U2C_PRESPLIT_MIN_ROWS;
+    const bool attn_bf16 = !bf.l[0].pre && lin_math == DDSP_MATH_SPLIT_BF16 && B * H >= ATTN_BF16_MIN && !w.causal;
     const int asplit = presplit ? 1 : 0;
     // A handful of rows (the real-time block: 87): the N = 256, K = 512 residual GEMMs (out-projection, pw2) would run on 8
     // workgroups walking 16 k-steps each.  Their K range is cut over KS_SPLITS workgroups per tile instead (32-96 workgroups,
     // 4 k-steps each, partial products stored) and the sum + bias + residual is formed by the LayerNorm that follows.
-    static int ksplit_on = -1;
-    if (ksplit_on < 0) {
-        const char* e = getenv("DDSP_U2C_KSPLIT");   // measurement aid: 0 restores whole-K launches
-        ksplit_on = (e && e[0] == '0') ? 0 : 1;
-    }
-    const bool ksplit = ksplit_on && !bf.l[0].pre && M <= KS_MAX_ROWS;
+    const bool ksplit = !bf.l[0].pre && M <= KS_MAX_ROWS;
     LnPending pending{nullptr, nullptr, nullptr, 0};
     auto residual_gemm = [&](gemm::Args g, const float* x_res, float* x_dst, const float* bias) {
         // x_dst = x_res + A B^T + bias, now or (ksplit) when the next LayerNorm reads it
@@ -2061,13 +2022,14 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
         return (const float*)x_dst;
     };
     // Large batches with pre-split operands: the residual layer AND the LayerNorm that follows it in one kernel (gemm_ln.h: a
-    // workgroup owns 64 rows x all 256 columns; same bits as the two launches).  DDSP_GEMM_LN=0 restores the pair.
+    // workgroup owns 64 rows x all 256 columns; same bits as the two launches).
+    // DDSP_GEMM_LN=0 restores the pair (test_residual_layernorm_in_the_model_is_bit_identical)
     static int gemm_ln_on = -1;
     if (gemm_ln_on < 0) {
         const char* e = getenv("DDSP_GEMM_LN");
         gemm_ln_on = (e && e[0] == '0') ? 0 : 1;
     }
-    static int64_t gemm_ln_min = -1;   // DDSP_GEMM_LN_MIN: rows from which the fused kernel runs (measurement aid)
+    static int64_t gemm_ln_min = -1;   // DDSP_GEMM_LN_MIN: rows from which the fused kernel runs (the same test lowers it)
     if (gemm_ln_min < 0) {
         const char* e = getenv("DDSP_GEMM_LN_MIN");
         // (measured: B = 8 / 1376 rows 0.476 -> 0.519 ms, B = 24 / 4128 rows 0.826 -> 0.839 ms per forward WITH the fused kernel -
@@ -2130,25 +2092,8 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
             g.A_split = a_is_split;
         }
     };
-    // Large batches: the wave-specialised kernel (gemm_ws.h: loader / product waves, epilogue pieces riding in the next tile)
-    // for the K = 256 Linear layers with wide outputs, once its 128x128 tiles make at least two rounds over the 256 CUs.  Same
-    // bits as kernel_dma.  Which layers: measured INSIDE the forward (rocprofv3, B = 64: DESIGN section 9) - the head gains
-    // (31.7 -> 28.4 us), QKV and pw1 + GLU do not (42.5 -> 43.9, 25.0 -> 27.9 us, although alone, with operands resident in the
-    // L2, they run 44.5 -> 38.8 and 30.0 -> 25.3), so only the head uses it.  DDSP_GEMM_WS = bit mask 1 QKV | 2 GLU | 4 head.
-    static int ws_mask = -1;
-    if (ws_mask < 0) {
-        const char* e = getenv("DDSP_GEMM_WS");
-        ws_mask = e ? atoi(e) : 4;
-    }
-    auto use_ws = [&](const gemm::Args& g, int layer_bit) {
-        return (ws_mask & layer_bit) && presplit_w && g.math == DDSP_MATH_SPLIT_BF16 && gemm::ws_ok(g) && g.N % 128 == 0 &&
-               (int64_t)((g.M + 127) / 128) * (g.N / 128) >= 512;
-    };
-    static int dw_pair = -1;   // DDSP_DW_PAIR (measurement aid): 0 the one-channel depthwise kernel at every size, 1 / 2 the register pair kernel (runs of 16 / 14 frames), 3 (default) the LDS-tiled kernel
-    if (dw_pair < 0) {
-        const char* e = getenv("DDSP_DW_PAIR");
-        dw_pair = e ? atoi(e) : 3;
-    }
+    // DDSP_DW_PAIR=1: the register pair kernel instead of the LDS-tiled one (test_tiled_depthwise_convolution_matches_the_register_kernel)
+    static const bool dw_tiled = [] { const char* e = getenv("DDSP_DW_PAIR"); return !(e && e[0] == '1'); }();
     bool conv_split = false;
     // ---- prenet: conv k3 -> GroupNorm(4) -> LeakyReLU -> conv k3 ----
     {
@@ -2205,7 +2150,7 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
             la.Cin = D;
             la.tap_shift = g.tap_shift;
             la.zeros = zero_page;
-            if (conv_ln_on() && ln_fusable(g, la) && g.A_split && D + 32 <= DDSP_ZERO_FLOATS) {
+            if (ln_fusable(g, la) && g.A_split && D + 32 <= DDSP_ZERO_FLOATS) {
                 PROF(PF_U2C_GEMM_CONV3, 2.0 * M * D * 3 * D, 12.0 * M * D,
                      DDSP_HIP(ctx, (gemm::launch_res_ln_rb<2, true, gemm::A_CONV3, PreEmbed>(st, la, PreEmbed{e}))));
                 ln_done = true;
@@ -2230,30 +2175,17 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
             gemm::Args g = gemm::make(b.y, D, bf.wqkv + (size_t)l * 3 * INNER * D, D, iM, 3 * INNER, D);
             set_b(g, bf.wqkv + (size_t)l * 3 * INNER * D, asplit);
             EpiSplit3 e{{b.q, b.k, b.v}, bf.bqkv + (size_t)l * 3 * INNER};
-            gemm::WsSplit3 ew{{b.q, b.k, b.v}, bf.bqkv + (size_t)l * 3 * INNER};
-            if (use_ws(g, 1) && ew.vec_ok()) {
-                PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * 3 * INNER * D, 4.0 * M * (D + 3 * INNER),
-                     DDSP_HIP(ctx, (gemm::ws_go<128, 128, gemm::WsSplit3, 4>(st, g, ew))));
-            } else {
-                PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * 3 * INNER * D, 4.0 * M * (D + 3 * INNER),
-                     (gemm::launch<true, true, gemm::A_PLAIN>(st, g, 1, e)));
-            }
+            PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * 3 * INNER * D, 4.0 * M * (D + 3 * INNER),
+                 (gemm::launch<true, true, gemm::A_PLAIN>(st, g, 1, e)));
         }
         if (attn_bf16) {
             // inference, split-bf16 products, enough (utterance, head) pairs to fill the chip with one workgroup each:
             // the LDS-staged bf16 kernels (performer_attn_bf16.hip); the output is written as the out-projection's A operand
             void* p3 = (char*)bf.p3 + (size_t)l * PERFORMER_P3_BYTES;
-            if (performer_fused_enabled()) {
-                // both sides in one kernel per (utterance, head): ctx and ks stay in its LDS (round 3)
-                PROF(PF_U2C_GEMM_CTX, 8.0 * M8 * NF * DH, 4.0 * M * 4 * INNER,
-                     DDSP_HIP(ctx, performer_fused_bf16(st, b.q, b.k, b.v, p3, (int)B, (int)Fr, b.attn, asplit)));
-            } else {
-                PROF(PF_U2C_GEMM_CTX, 4.0 * M8 * NF * DH, 4.0 * M * 2 * INNER,
-                     performer_kv_bf16(st, b.k, b.v, p3, (int)B, (int)Fr, b.cx, b.ks));
-                PROF(PF_U2C_GEMM_ATTNOUT, 4.0 * M8 * NF * DH, 4.0 * M * 2 * INNER,
-                     performer_q_bf16(st, b.q, p3, b.cx, b.ks, (int)B, (int)Fr, b.attn, 0, asplit));
-            }
-        } else if (w.causal && !b.pre && causal_chunked()) {
+            // both sides in one kernel per (utterance, head): ctx and ks stay in its LDS (round 3)
+            PROF(PF_U2C_GEMM_CTX, 8.0 * M8 * NF * DH, 4.0 * M * 4 * INNER,
+                 DDSP_HIP(ctx, performer_fused_bf16(st, b.q, b.k, b.v, p3, (int)B, (int)Fr, b.attn, asplit)));
+        } else if (w.causal && !b.pre) {
             // causal mode, inference: chunked linear attention in one kernel (performer_attn.hip); q' / k' never reach HBM
             PROF(PF_U2C_GEMM_ATTNOUT, 2.0 * M8 * (3.0 * NF * DH + 16.0 * (NF + DH)) + 4.0 * M8 * NF * DH, 4.0 * M * 4 * INNER,
                  performer_causal(st, b.q, b.k, b.v, L.proj, (int)B, (int)Fr, b.attn));
@@ -2342,11 +2274,7 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
             set_b(g, bf.wglu + (size_t)l * 2 * INNER * D, asplit);
             EpiGlu e{b.glu, bf.bglu + (size_t)l * 2 * INNER};
             DDSP_REQUIRE(ctx, gemm::dma_ok(g) && ((uintptr_t)b.glu % 16) == 0, "unit2ctrl: fused GLU needs aligned activations");
-            gemm::WsGlu ew{b.glu, INNER, bf.bglu + (size_t)l * 2 * INNER};
-            if (use_ws(g, 2) && ew.vec_ok()) {
-                PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * 2 * INNER * D, 4.0 * M * (D + INNER),
-                     DDSP_HIP(ctx, (gemm::ws_go<128, 128, gemm::WsGlu, 4>(st, g, ew))));
-            } else if (glu_large) {
+            if (glu_large) {
                 PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * 2 * INNER * D, 4.0 * M * (D + INNER),
                      (gemm::dma_go<128, 128, EpiGlu, 2>(st, g, 1, e)));
             } else {
@@ -2365,16 +2293,13 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
                  hipLaunchKernelGGL(glu_kernel, dim3(grid_for(M * (INNER / 4))), dim3(256), 0, st, b.g1, M, b.glu));
         }
         PROF(PF_U2C_ROWWISE, 2.0 * M * INNER * DWK, 8.0 * M * INNER,
-             if (!b.pre && dw_pair == 3 && B * ((Fr + 15) / 16) >= 512)
+             if (!b.pre && dw_tiled && B * ((Fr + 15) / 16) >= 512)
                  // inference, large batches: LDS-staged tiles of 64 frames x 64 channels
                  hipLaunchKernelGGL(dwconv_tile_kernel, dim3(INNER / DWT_C, (unsigned)(B * ((Fr + DWT_F - 1) / DWT_F))), dim3(256), 0, st,
                                     b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit);
-             else if (!b.pre && dw_pair == 1 && B * ((Fr + 15) / 16) >= 512)
+             else if (!b.pre && B * ((Fr + 15) / 16) >= 512)
                  // inference, large batches: two channels per thread on packed multiply-adds, runs of 16 frames
                  hipLaunchKernelGGL((dwconv_pair_kernel<16>), dim3(1, (unsigned)(B * ((Fr + 15) / 16))), dim3(256), 0, st,
-                                    b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit);
-             else if (!b.pre && dw_pair == 2 && B * ((Fr + 13) / 14) >= 512)
-                 hipLaunchKernelGGL((dwconv_pair_kernel<14>), dim3(1, (unsigned)(B * ((Fr + 13) / 14))), dim3(256), 0, st,
                                     b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit);
              else if (B * ((Fr + DW_RUN - 1) / DW_RUN) >= 64)
                  hipLaunchKernelGGL((dwconv_kernel<true, false>), dim3(INNER / 256, (unsigned)(B * ((Fr + DW_RUN - 1) / DW_RUN))),
@@ -2409,7 +2334,14 @@ static int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w,
         set_b(g, bf.wh, asplit);
         gemm::EpiStore e{ctrl, w.n_out, w.head_b, 1, 0, 0};
         gemm::WsStore ew{ctrl, w.n_out, w.head_b};
-        if (use_ws(g, 4) && ew.vec_ok()) {
+        // Large batches: the wave-specialised kernel (gemm_ws.h: loader / product waves, epilogue pieces riding in the next
+        // tile) once its 128x128 tiles make at least two rounds over the 256 CUs.  Same bits as kernel_dma.  Which layers:
+        // measured INSIDE the forward (rocprofv3, B = 64: DESIGN section 9) - the head gains (31.7 -> 28.4 us), QKV and
+        // pw1 + GLU do not (42.5 -> 43.9, 25.0 -> 27.9 us, although alone, with operands resident in the L2, they run
+        // 44.5 -> 38.8 and 30.0 -> 25.3), so only the head uses it.
+        const bool use_ws = presplit_w && g.math == DDSP_MATH_SPLIT_BF16 && gemm::ws_ok(g) && g.N % 128 == 0 &&
+                            (int64_t)((g.M + 127) / 128) * (g.N / 128) >= 512;
+        if (use_ws && ew.vec_ok()) {
             PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * w.n_out * D, 4.0 * M * (D + w.n_out),
                  DDSP_HIP(ctx, (gemm::ws_go<128, 128, gemm::WsStore, 4>(st, g, ew))));
         } else {
@@ -2608,28 +2540,6 @@ static int colsum_pair(ddsp_ctx* ctx, hipStream_t st, const float* X0, const flo
 // (O, 3*C) matrix) from the same dY.  With split-bf16 products (the context's default arithmetic) one launch of the
 // transposing bf16 kernel (wgrad_bf16.h) produces the split partials of both and two small kernels add them; with
 // ddsp_ctx_set_math(FP32) the round-1 path runs: fp32-MFMA split-K batches, shifted copies of X per tap, a separate column sum.
-static int wgrad_tile_choice() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DDSP_WGRAD_TILE");   // measurement aid: 11, 21, 12, 22 = (TM, TN)
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-static bool attn_feat_fused_on() {   // DDSP_ATTN_FEAT_FUSED=0: the feature-map adjoints back on the five-launch chain through HBM
-    static const bool v = [] {
-        const char* e = getenv("DDSP_ATTN_FEAT_FUSED");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-static bool attn_wgrad_on() {   // DDSP_ATTN_WGRAD=0: the K = frames product of the attention adjoint back on the register-staged fp32 kernel
-    static const bool v = [] {
-        const char* e = getenv("DDSP_ATTN_WGRAD");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
 static int layer_grads(ddsp_ctx* ctx, hipStream_t st, const float* dY, int64_t ldy, int O, const float* X, int64_t ldx, int C,
                        int taps, int Fr, int64_t M, float* wpart, float* cpart, float* xs, float* w_out, int64_t ldo,
                        float* b_out, int tap_shift = 0, WgDefer* defer = nullptr) {   // tap_shift: 0 centred taps, -1 causal taps (taps == 3 only)
@@ -2658,12 +2568,7 @@ static int layer_grads(ddsp_ctx* ctx, hipStream_t st, const float* dY, int64_t l
     g.tap_shift = taps == 3 ? tap_shift : 0;
     g.Fr = Fr;
     g.M = M;
-    static const int want_splits = [] {   // DDSP_WGRAD_SPLITS (1..16): row splits of a weight-gradient product (buffers are sized for 16)
-        const char* e = getenv("DDSP_WGRAD_SPLITS");
-        const int v = e ? atoi(e) : WG_SPLITS;
-        return v < 1 ? 1 : (v > WG_SPLITS ? WG_SPLITS : v);
-    }();
-    g.chunk = wgrad::chunk_for(M, want_splits);
+    g.chunk = wgrad::chunk_for(M, WG_SPLITS);
     const int nz = wgrad::splits_for(M, g.chunk), N = taps * C;
     // deferred: partial sums into regions of the caller's pool, added up by ONE launch at the end of the backward pass
     float* dpart = nullptr;
@@ -2680,15 +2585,10 @@ static int layer_grads(ddsp_ctx* ctx, hipStream_t st, const float* dY, int64_t l
     g.partial = dpart ? dpart : wpart;
     g.bias_partial = b_out ? (dpart ? dbias : cpart) : nullptr;
     ddsp_prof_begin(ctx, st, PF_U2C_BWD);
-    int tile = wgrad_tile_choice();
     // 64x64 tiles: with 16 splits every layer of the network gives 512-1280 workgroups; the larger tiles stage less per
     // product but leave CUs idle at these sizes (r02, training step B=32: 8.30 ms against 8.45 / 8.45 / 8.59 with 128x64 /
     // 64x128 / 128x128)
-    if (tile == 0) tile = 11;
-    if (tile == 22) wgrad::launch<2, 2>(st, g);
-    else if (tile == 21) wgrad::launch<2, 1>(st, g);
-    else if (tile == 12) wgrad::launch<1, 2>(st, g);
-    else wgrad::launch<1, 1>(st, g);
+    wgrad::launch<1, 1>(st, g);
     if (dpart) {
         defer->push(dpart, w_out, nz, O, N, ldo);
         if (b_out) defer->push(dbias, b_out, nz, 1, O, O);
@@ -2925,7 +2825,8 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
         static_assert(TS_MAX >= 19, "table too small");
         hipLaunchKernelGGL(transpose_split_kernel, dim3(64, n), dim3(256), 0, st, ts);
     }
-    const bool feat_fused = ctx->math != DDSP_MATH_FP32 && !w.causal && attn_feat_fused_on();
+    // split-bf16, non-causal: the feature-map adjoints in attn_feat_bwd_kernel; fp32 and causal: the five-launch chain
+    const bool feat_fused = ctx->math != DDSP_MATH_FP32 && !w.causal;
     if (feat_fused)
         for (int l = 0; l < 3; ++l)
             hipLaunchKernelGGL(feat_proj_prep_kernel, dim3((FB_KS * 4 * 64 + 255) / 256), dim3(256), 0, st, w.layer[l].proj,
@@ -2933,12 +2834,7 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
     WgDefer df{};
     df.pool = wpool;
     df.cap = wpool_floats;
-    static int defer_on = -1;   // DDSP_WGRAD_DEFER=0: every layer's partial sums reduced right behind its product (measurement aid)
-    if (defer_on < 0) {
-        const char* e = getenv("DDSP_WGRAD_DEFER");
-        defer_on = (e && e[0] == '0') ? 0 : 1;
-    }
-    WgDefer* const dfp = defer_on ? &df : nullptr;
+    WgDefer* const dfp = &df;
     // ---- head: ctrl = LN(x) W^T + b, W = g v/|v| ----
     if ((rc = layer_grads(ctx, st, d_ctrl, NO, NO, bf.y_final, D, D, 1, (int)Fr, M, wpart, cpart, xs, dWh, D, G(head_b)))) return rc;
     hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3((NO + 3) / 4), dim3(256), 0, st, w.head_g, w.head_v, dWh, NO, D,
@@ -2996,7 +2892,6 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
             hipLaunchKernelGGL(causal_attn_bwd_v_kernel, dim3((unsigned)(B * H)), dim3(256), 0, st, b.qf, b.kf, dB512, dD, (int)Fr,
                                dV512);
         } else {
-            bool dv_done = false;   // d_v folded into the key side of attn_feat_bwd_kernel
             hipLaunchKernelGGL(attn_out_bwd_kernel, dim3(rows8_g), dim3(256), 0, st, dB512, b.attn, b.dinv, M8, dD);  // d_num, d_D
             if (!feat_fused) {   // d_q' = d_num ctx^T + d_D ks^T
                 gemm::Args g = gemm::make(dB512, INNER, b.cx, DH, (int)Fr, NF, DH);
@@ -3008,8 +2903,8 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
                 EpiRowOuter e{dQF, dD, b.ks, (int)Fr};
                 attn_k64(st, g, (int)(B * H), e);
             }
-            if (ctx->math != DDSP_MATH_FP32 && attn_wgrad_on()) {   // d_ctx = q'^T d_num: the frames are the slow axis of both operands,
-                wgrad::Args g;                                        // the weight-gradient kernel with one problem per (utterance, head)
+            if (feat_fused) {   // d_ctx = q'^T d_num: the frames are the slow axis of both operands,
+                wgrad::Args g;  // the weight-gradient kernel with one problem per (utterance, head)
                 g.dY = b.qf;
                 g.ldy = (int64_t)H * LDF;
                 g.O = NF;
@@ -3034,7 +2929,7 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
                 g.sX_hi = (int64_t)Fr * INNER;
                 g.sX_lo = DH;
                 wgrad::launch<1, 1>(st, g, (int)(B * H));   // (128-row tiles: no difference, 5.72 / 5.75 ms over two runs)
-            } else {   // d_ctx = q'^T d_num
+            } else {   // d_ctx = q'^T d_num, d_ks = q'^T d_D
                 gemm::Args g = gemm::make(b.qf, (int64_t)H * LDF, dB512, INNER, NF, DH, (int)Fr);
                 g.zdiv = H;
                 g.sA_hi = (int64_t)Fr * H * LDF;
@@ -3043,24 +2938,20 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
                 g.sB_lo = DH;
                 gemm::EpiStore e{dcx, DH, nullptr, 1, (int64_t)NF * DH, 0};
                 gemm::launch_tile<64, 64, false, false, gemm::A_PLAIN>(st, g, (int)(B * H), e);
-            }
-            if (!(ctx->math != DDSP_MATH_FP32 && attn_wgrad_on()))
                 hipLaunchKernelGGL(weighted_key_sum_kernel, dim3((unsigned)(B * H)), dim3(KS_T * 8), 0, st, b.qf, dD, (int)Fr, dks);
+            }
             if (feat_fused) {   // d_q (in place of d_num, which the d_ctx launch above has consumed) and d_k: attn_feat_bwd_kernel
                 const dim3 fgrid((unsigned)(B * H), (unsigned)((Fr + 16 * FB_WAVES - 1) / (16 * FB_WAVES)));
                 DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)attn_feat_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS_BYTES));
                                      DDSP_HIP(ctx, hipFuncSetAttribute((const void*)attn_feat_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS_BYTES)));
                 const ddsp_u32x4* pt = reinterpret_cast<const ddsp_u32x4*>(ptp) + (size_t)l * FB_PT_VEC;
-                static const int ablate = [] { const char* e = getenv("DDSP_FEAT_ABLATE"); return e ? atoi(e) : 0; }();
-                static const bool fold_v = [] { const char* e = getenv("DDSP_ATTN_DV_FOLD"); return !(e && e[0] == '0'); }();
-                if (fold_v)
-                    hipLaunchKernelGGL(feat_proj_prep_kernel, dim3((FB_KS * 4 * 64 + 255) / 256, (unsigned)(B * H)), dim3(256), 0, st, dcx,
-                                       reinterpret_cast<ddsp_u32x4*>(dcxt));
-                dv_done = fold_v;
-                FeatBwdArgs fq{dB512, b.cx, dD, b.ks, b.qf, pt, L.proj, b.q, dB512, (int)Fr, nullptr, nullptr, ablate};
+                // d_v = k' d_ctx folded into the key side: d_ctx of every (utterance, head) in the projection's layout
+                hipLaunchKernelGGL(feat_proj_prep_kernel, dim3((FB_KS * 4 * 64 + 255) / 256, (unsigned)(B * H)), dim3(256), 0, st, dcx,
+                                   reinterpret_cast<ddsp_u32x4*>(dcxt));
+                FeatBwdArgs fq{dB512, b.cx, dD, b.ks, b.qf, pt, L.proj, b.q, dB512, (int)Fr, nullptr, nullptr};
                 hipLaunchKernelGGL(attn_feat_bwd_kernel<true>, fgrid, dim3(64 * FB_WAVES), FB_LDS_BYTES, st, fq);
                 FeatBwdArgs fk{b.v, dcx, nullptr, dks, b.kf, pt, nullptr, b.k, dC512, (int)Fr,
-                               fold_v ? reinterpret_cast<const ddsp_u32x4*>(dcxt) : nullptr, dV512, ablate};
+                               reinterpret_cast<const ddsp_u32x4*>(dcxt), dV512};
                 hipLaunchKernelGGL(attn_feat_bwd_kernel<false>, fgrid, dim3(64 * FB_WAVES), FB_LDS_BYTES, st, fk);
             } else {   // d_k' = v d_ctx^T + d_ks^T
                 gemm::Args g = gemm::make(b.v, INNER, dcx, DH, (int)Fr, NF, DH);
@@ -3072,7 +2963,7 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
                 EpiRowOuter e{dKF, nullptr, dks, (int)Fr};
                 attn_k64(st, g, (int)(B * H), e);
             }
-            if (!dv_done) {   // d_v = k' d_ctx
+            if (!feat_fused) {   // d_v = k' d_ctx
                 gemm::Args g = gemm::make(b.kf, (int64_t)H * LDF, dcx, DH, (int)Fr, DH, NF);
                 g.zdiv = H;
                 g.sA_hi = (int64_t)Fr * H * LDF;
@@ -3083,11 +2974,9 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
                 gemm::launch_tile<64, 64, true, false, gemm::A_PLAIN>(st, g, (int)(B * H), e);
             }
         }
-        if (!(feat_fused && !w.causal)) {
-        hipLaunchKernelGGL(feature_map_bwd_kernel<true>, dim3(rows8_g), dim3(256), 0, st, b.qf, dQF, M8, coefq);
-        hipLaunchKernelGGL(feature_map_bwd_kernel<false>, dim3(rows8_g), dim3(256), 0, st, b.kf, dKF, M8, coefk);
-        }
-        if (!(feat_fused && !w.causal)) {   // d_q = d_raw_q P + coef_q q   (rows = (frame, head), 64 columns == the (M, 512) layout of q)
+        if (!feat_fused) {   // d_q = d_raw_q P + coef_q q   (rows = (frame, head), 64 columns == the (M, 512) layout of q)
+            hipLaunchKernelGGL(feature_map_bwd_kernel<true>, dim3(rows8_g), dim3(256), 0, st, b.qf, dQF, M8, coefq);
+            hipLaunchKernelGGL(feature_map_bwd_kernel<false>, dim3(rows8_g), dim3(256), 0, st, b.kf, dKF, M8, coefk);
             gemm::Args g = gemm::make(dQF, LDF, L.proj, DH, (int)M8, DH, NF);
             EpiAxpyRow e{dB512, coefq, b.q, DH};
             gemm::launch<true, false, gemm::A_PLAIN>(st, g, 1, e);

@@ -15,8 +15,6 @@ import torch.nn as nn
 
 import hipddsp
 
-_WEIGHT_CACHE = os.environ.get("DDSP_U2C_WCACHE", "1") != "0"   # measurement aid: 0 = prepare the weights on every forward
-
 NDIM = 256
 N_LAYERS = 3
 N_HEADS = 8
@@ -258,7 +256,7 @@ class Unit2Control(nn.Module):
         # inference: the library may keep its prepared copies of these weights while their values stand (every in-place change of
         # a tensor - optimizer step, load_state_dict, copy_ - advances its `_version`); training steps prepare them every time
         # (the nonce tells two model objects apart whose tensors the allocator placed at the same addresses)
-        if grad_mode or not _WEIGHT_CACHE:
+        if grad_mode:
             w.version = 0
         else:
             if not hasattr(self, "_weights_nonce"):

@@ -22,8 +22,6 @@ import torch.nn.functional as F
 import hipddsp
 from resample import Resample
 
-PAIR_FUSION = os.environ.get("DDSP_CONV_PAIR", "1") != "0"   # measurement aid: 0 = two launches per residual pair
-
 LRELU_SLOPE = 0.1
 
 
@@ -278,7 +276,7 @@ class Generator(torch.nn.Module):
             s_out = can_split(cin, cout)
             # a narrow stage whose residual pairs run fused (x in, x out, activations on load: csrc/nsf.hip, conv_pair*) needs no
             # activated copies at all
-            fused = PAIR_FUSION and all(c.conv1d_pair_supported(cout, k, d) for convs in P["res"][i] for (_, _, _, d, _, _, _, k) in convs)
+            fused = all(c.conv1d_pair_supported(cout, k, d) for convs in P["res"][i] for (_, _, _, d, _, _, _, k) in convs)
             up, up_act = c.conv1d(cur_act, w_up, b_up, 3, 1, 1.0, residual=x_source.reshape(T, u * cout),
                                   act_slope=None if fused else LRELU_SLOPE,
                                   w_split=w_up_s if (act_s or s_out) else None, x_split=act_s, act_split=s_out), None
