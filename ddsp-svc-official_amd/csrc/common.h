@@ -58,6 +58,9 @@ struct ddsp_ctx {
     // packed control-net weights (prepared by ddsp_u2c_prepare)
     float* packed;
     size_t packed_bytes;
+    // prepared weights of the units encoder (ddsp_hubert_weights::version != 0): one slot
+    char* hcache;
+    uint64_t hcache_key, hcache_version;
     // 8 KiB of zeros: the source of out-of-range conv taps in the LDS-DMA GEMM (a DMA cannot be predicated to zero)
     float* zero_page;
     // device-side contract violations (a speaker id outside the table): one int in host-mapped memory that kernels set

@@ -1,0 +1,623 @@
+// HuBERT-Soft units encoder (reference encoder/hubert/model.py `HubertSoft.units`, ddsp/vocoder.py:140-229) on gfx950.
+//
+// Activations are frame-major (frames x channels) fp32 throughout.  Every contraction but conv0 and the attention is a call of
+// the library's GEMM (gemm_f32.h) in the context's product arithmetic:
+//   * the strided convolutions are plain GEMMs over OVERLAPPING rows: A(m, k) = x[m * stride * Cin + k], k = tap * Cin + ci,
+//     lda = stride * Cin <= K (the LDS-DMA kernel clamps rows to M - 1, so its reads end at x[(M-1)*lda + K - 1], inside the
+//     input); the weights are repacked once to (Cout, tap * Cin + ci);
+//   * the positional convolution (groups 16, 48 channels, 128 taps, padding 64) is one implicit GEMM per (utterance, group)
+//     over a zero-padded group-major copy of the activations: A(m, k) = xg[m * 48 + k], k = tap * 48 + ci, K = 6144;
+//     its weight norm (one norm per tap, weight_norm(dim=2)) is folded once into the packed weights.
+// The conv0 / GroupNorm front, the LayerNorms and the softmax attention are the kernels of this file.
+#include "gemm_f32.h"
+
+#include <algorithm>
+#include <math.h>
+#include <stddef.h>
+
+namespace {
+
+constexpr int HC = 512;                              // conv channels
+constexpr int HD = 768;                              // model width
+constexpr int HFF = 3072;                            // feed-forward width
+constexpr int HU = 256;                              // units
+constexpr int HHEADS = 12, HDH = 64;                 // heads x head dim
+constexpr int POS_K = 128, POS_G = 16, POS_C = 48;   // positional conv: taps, groups, channels per group
+constexpr int POS_KK = POS_K * POS_C;                // its GEMM K
+constexpr int GN_PARTS = 1024;                       // frame ranges of the GroupNorm statistics (blocks of conv0_kernel per utterance)
+constexpr int CONV_TAPS[6] = {3, 3, 3, 3, 2, 2};
+constexpr int HPAD = 40;                             // (400 - 320) / 2 zeros on each side of the audio
+
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
+
+// ---- GEMM epilogues --------------------------------------------------------------------------------------
+struct EpiGelu {   // C[z] = gelu(acc + bias[n]), batch z at C + z * sC
+    float* C;
+    int64_t ldc;
+    const float* bias;
+    int64_t sC;
+    __device__ __forceinline__ float col(int n) const { return bias ? bias[n] : 0.f; }
+    __device__ __forceinline__ void operator()(int z, int m, int n, float v, float cb) const {
+        C[(int64_t)z * sC + (int64_t)m * ldc + n] = gelu_erf(v + cb);
+    }
+    static constexpr bool kStore4 = true;
+    __device__ __forceinline__ bool vec_ok() const { return ((uintptr_t)C % 16) == 0 && ldc % 4 == 0 && sC % 4 == 0; }
+    __device__ __forceinline__ void store4(int z, int m, int n, f32x4 v) const {
+        if (bias) v += *(const gemm::f32x4_u*)(bias + n);
+        f32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = gelu_erf(v[i]);
+        *(f32x4*)(C + (int64_t)z * sC + (int64_t)m * ldc + n) = r;
+    }
+};
+
+// positional conv, batch z = utterance * 16 + group: y[b*L + m][g*48 + n] = x[..] + gelu(acc + bias[g*48 + n])
+struct EpiPos {
+    float* y;
+    const float* x;
+    const float* bias;
+    int L;
+    __device__ __forceinline__ float col(int) const { return 0.f; }
+    __device__ __forceinline__ void operator()(int z, int m, int n, float v, float) const {
+        const int b = z / POS_G, c = (z % POS_G) * POS_C + n;
+        const int64_t o = ((int64_t)b * L + m) * HD + c;
+        y[o] = x[o] + gelu_erf(v + bias[c]);
+    }
+};
+
+// ---- conv0 (1 -> 512, kernel 10, stride 5, no bias) + GroupNorm(512, 512) statistics ------------------------
+// grid (GN_PARTS, B), block 512 = one channel per thread; the block walks frames [T0*p/P, T0*(p+1)/P) and writes the
+// fp64 sum and sum of squares of its channel over them (reduced in a fixed order by gn_finalize_kernel)
+__global__ void __launch_bounds__(512) conv0_kernel(const float* __restrict__ wav, int64_t T, const float* __restrict__ w0,
+                                                    float* __restrict__ y, int64_t T0, double* __restrict__ part) {
+    const int b = blockIdx.y, p = blockIdx.x, c = threadIdx.x;
+    float w[10];
+#pragma unroll
+    for (int t = 0; t < 10; ++t) w[t] = w0[c * 10 + t];
+    const int64_t f0 = T0 * p / GN_PARTS, f1 = T0 * (p + 1) / GN_PARTS;
+    const float* x = wav + (int64_t)b * T;
+    float* yb = y + (int64_t)b * T0 * HC;
+    double s = 0.0, ss = 0.0;
+    for (int64_t f = f0; f < f1; ++f) {
+        float acc = 0.f;
+#pragma unroll
+        for (int t = 0; t < 10; ++t) {
+            const int64_t i = f * 5 + t - HPAD;
+            const float xv = (i >= 0 && i < T) ? x[i] : 0.f;
+            acc = fmaf(w[t], xv, acc);
+        }
+        yb[f * HC + c] = acc;
+        s += (double)acc;
+        ss += (double)acc * (double)acc;
+    }
+    double* pp = part + ((int64_t)b * GN_PARTS + p) * 2 * HC;
+    pp[c] = s;
+    pp[HC + c] = ss;
+}
+
+// per (utterance, channel): scale = gamma / sqrt(var + eps), shift = beta - mean * scale (biased variance, fp64).  grid (8, B),
+// block 1024: 64 channels x 16 slices of the GN_PARTS partial sums, the slices added in a fixed order
+__global__ void __launch_bounds__(1024) gn_finalize_kernel(const double* __restrict__ part, int64_t T0, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, float* __restrict__ aff) {
+    __shared__ double red[2][16][64];
+    const int b = blockIdx.y, cl = threadIdx.x & 63, sl = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
+    double s = 0.0, ss = 0.0;
+    for (int p = sl; p < GN_PARTS; p += 16) {
+        const double* pp = part + ((int64_t)b * GN_PARTS + p) * 2 * HC;
+        s += pp[c];
+        ss += pp[HC + c];
+    }
+    red[0][sl][cl] = s;
+    red[1][sl][cl] = ss;
+    __syncthreads();
+    if (sl != 0) return;
+    s = 0.0;
+    ss = 0.0;
+    for (int i = 0; i < 16; ++i) {
+        s += red[0][i][cl];
+        ss += red[1][i][cl];
+    }
+    const double mean = s / (double)T0;
+    double var = ss / (double)T0 - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const double sc = (double)gamma[c] / sqrt(var + 1e-5);
+    aff[(b * HC + c) * 2] = (float)sc;
+    aff[(b * HC + c) * 2 + 1] = (float)((double)beta[c] - mean * sc);
+}
+
+// y = gelu(y * scale[c] + shift[c]) in place over (B, T0, 512)
+__global__ void __launch_bounds__(256) gn_apply_kernel(float* __restrict__ y, int64_t T0, int64_t n4, const float* __restrict__ aff) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const int64_t e = i * 4;
+        const int64_t b = e / (T0 * HC);
+        const int c = (int)(e % HC);
+        f32x4 v = *(f32x4*)(y + e);
+        const float* a = aff + (b * HC + c) * 2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = gelu_erf(fmaf(v[j], a[2 * j], a[2 * j + 1]));
+        *(f32x4*)(y + e) = v;
+    }
+}
+
+// ---- LayerNorm over C columns (eps 1e-5) of x (+ r): one wave per row, in place allowed --------------------
+template <int C>
+__global__ void __launch_bounds__(256) layernorm_kernel(const float* x, const float* __restrict__ r, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, float* y, int64_t rows) {
+    constexpr int NV = C / 256;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    f32x4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int64_t o = row * C + (i * 64 + lane) * 4;
+        v[i] = *(const f32x4*)(x + o);
+        if (r) v[i] += *(const f32x4*)(r + o);
+        s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+    const float mean = wave_sum(s) * (1.f / C);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i] -= mean;
+        q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(q) * (1.f / C) + 1e-5f);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        const f32x4 g = *(const f32x4*)(gamma + c), bb = *(const f32x4*)(beta + c);
+        *(f32x4*)(y + row * C + c) = v[i] * rstd * g + bb;
+    }
+}
+
+// ---- positional conv operand: x (B*L, 768) -> xg[b][g][L + 128][48], 64 zero rows before and after ---------------
+__global__ void __launch_bounds__(256) pos_pack_kernel(const float* __restrict__ x, int L, int64_t n4, float* __restrict__ xg) {
+    const int64_t rows = L + POS_K;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const int64_t e = i * 4;
+        const int c = (int)(e % POS_C);
+        const int64_t r = (e / POS_C) % rows, bg = e / (POS_C * rows);
+        const int64_t b = bg / POS_G, g = bg % POS_G;
+        const int64_t src = r - POS_K / 2;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (src >= 0 && src < L) v = *(const f32x4*)(x + (b * L + src) * HD + g * POS_C + c);
+        *(f32x4*)(xg + e) = v;
+    }
+}
+
+// ---- weight preparation ------------------------------------------------------------------------------------
+// (Cout, Cin, taps) -> (Cout, tap * Cin + ci)
+__global__ void __launch_bounds__(256) conv_repack_kernel(const float* __restrict__ w, int taps, int64_t n, float* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t co = i / (HC * taps);
+        const int rem = (int)(i % (HC * taps));
+        const int t = rem / HC, ci = rem % HC;
+        out[i] = w[(co * HC + ci) * taps + t];
+    }
+}
+
+// weight_norm(dim=2): scale[k] = g[k] / ||v[:, :, k]||  (fp64 sum of squares), one block per tap
+__global__ void __launch_bounds__(256) pos_norm_kernel(const float* __restrict__ v, const float* __restrict__ g, float* __restrict__ scale) {
+    __shared__ double red[4];
+    const int k = blockIdx.x;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < HD * POS_C; i += 256) {
+        const double a = v[(int64_t)i * POS_K + k];
+        s += a * a;
+    }
+    s = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) scale[k] = (float)((double)g[k] / sqrt((red[0] + red[1]) + (red[2] + red[3])));
+}
+
+// w[g][n][tap * 48 + ci] = v[g*48 + n][ci][tap] * scale[tap]
+__global__ void __launch_bounds__(256) pos_weight_kernel(const float* __restrict__ v, const float* __restrict__ scale, float* __restrict__ out) {
+    const int64_t n = (int64_t)HD * POS_KK;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t co = i / POS_KK;                 // = g * 48 + n
+        const int kk = (int)(i % POS_KK), t = kk / POS_C, ci = kk % POS_C;
+        out[i] = v[(co * POS_C + ci) * POS_K + t] * scale[t];
+    }
+}
+
+// ---- softmax attention (flash form: online softmax, no L x L matrix) ---------------------------------------------
+// q, k, v: rows (b * L + i) at stride ld, head h at column h * 64; out likewise at stride ldo.  One workgroup per (QT queries,
+// utterance, head); thread t owns query t % QT and the keys j = s, s + S, ... (s = t / QT, S = 256 / QT) of every 64-key tile
+// staged in LDS; the S partial (max, sum, accumulator) triples of a query are merged through LDS at the end.  fp32 products.
+constexpr int ATT_KT = 64, ATT_LD = HDH + 4;   // keys per LDS tile; padded row (4 rows read at once by a wave when QT = 16)
+
+template <int QT>
+__global__ void __launch_bounds__(256) attention_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                        const float* __restrict__ v, int64_t ld, float* __restrict__ out,
+                                                        int64_t ldo, int L, int heads, float scale) {
+    constexpr int S = 256 / QT, KPT = ATT_KT / S;    // key splits, keys per thread and tile
+    constexpr int MERGE = S * QT * HDH;              // floats of the merge buffer
+    __shared__ __attribute__((aligned(16))) float smem[MERGE + 2 * 256];
+    float* const ks = smem;
+    float* const vs = smem + ATT_KT * ATT_LD;
+    const int tid = threadIdx.x, qi = tid % QT, s = tid / QT;
+    const int b = blockIdx.y / heads, h = blockIdx.y % heads;
+    const int qrow = blockIdx.x * QT + qi;
+    const int64_t base = (int64_t)b * L;
+    float qr[HDH], acc[HDH];
+    {
+        const float* qp = q + (base + (qrow < L ? qrow : L - 1)) * ld + h * HDH;
+#pragma unroll
+        for (int d = 0; d < HDH; d += 4) {
+            const f32x4 t = *(const f32x4*)(qp + d);
+            qr[d] = t[0] * scale; qr[d + 1] = t[1] * scale; qr[d + 2] = t[2] * scale; qr[d + 3] = t[3] * scale;
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < HDH; ++d) acc[d] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    for (int kt0 = 0; kt0 < L; kt0 += ATT_KT) {
+        __syncthreads();   // the previous tile's readers are done
+#pragma unroll
+        for (int i = 0; i < ATT_KT * HDH / 4 / 256; ++i) {
+            const int idx = tid + i * 256, row = idx >> 4, c4 = (idx & 15) * 4;
+            const int key = kt0 + row;
+            f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+            if (key < L) {
+                kv = *(const f32x4*)(k + (base + key) * ld + h * HDH + c4);
+                vv = *(const f32x4*)(v + (base + key) * ld + h * HDH + c4);
+            }
+            *(f32x4*)(ks + row * ATT_LD + c4) = kv;
+            *(f32x4*)(vs + row * ATT_LD + c4) = vv;
+        }
+        __syncthreads();
+        const int nk = L - kt0 < ATT_KT ? L - kt0 : ATT_KT;
+        float sc[KPT];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < KPT; ++u) {
+            const int j = s + u * S;
+            float a = -INFINITY;
+            if (j < nk) {
+                a = 0.f;
+                const float* kr = ks + j * ATT_LD;
+#pragma unroll
+                for (int d = 0; d < HDH; d += 4) {
+                    const f32x4 t = *(const f32x4*)(kr + d);
+                    a = fmaf(qr[d], t[0], a);
+                    a = fmaf(qr[d + 1], t[1], a);
+                    a = fmaf(qr[d + 2], t[2], a);
+                    a = fmaf(qr[d + 3], t[3], a);
+                }
+            }
+            sc[u] = a;
+            tmax = fmaxf(tmax, a);
+        }
+        if (tmax == -INFINITY) continue;   // no key of this tile for this thread (uniform across the barrier-free rest)
+        const float mn = fmaxf(m, tmax);
+        const float corr = expf(m - mn);   // m = -inf on the first tile: 0
+        l *= corr;
+#pragma unroll
+        for (int d = 0; d < HDH; ++d) acc[d] *= corr;
+#pragma unroll
+        for (int u = 0; u < KPT; ++u) {
+            const int j = s + u * S;
+            if (j < nk) {
+                const float p = expf(sc[u] - mn);
+                l += p;
+                const float* vr = vs + j * ATT_LD;
+#pragma unroll
+                for (int d = 0; d < HDH; d += 4) {
+                    const f32x4 t = *(const f32x4*)(vr + d);
+                    acc[d] = fmaf(p, t[0], acc[d]);
+                    acc[d + 1] = fmaf(p, t[1], acc[d + 1]);
+                    acc[d + 2] = fmaf(p, t[2], acc[d + 2]);
+                    acc[d + 3] = fmaf(p, t[3], acc[d + 3]);
+                }
+            }
+        }
+        m = mn;
+    }
+    // merge the S partial results of every query (layout [s][d][qi]: consecutive threads, consecutive words)
+    __syncthreads();
+    float* const red = smem;
+    float* const mred = smem + MERGE;
+    float* const lred = mred + 256;
+#pragma unroll
+    for (int d = 0; d < HDH; ++d) red[(s * HDH + d) * QT + qi] = acc[d];
+    mred[s * QT + qi] = m;
+    lred[s * QT + qi] = l;
+    __syncthreads();
+    constexpr int DPT = HDH / S;   // output dims per thread
+    const int q2 = tid % QT, dg = tid / QT;
+    const int orow = blockIdx.x * QT + q2;
+    if (orow >= L) return;
+    float M = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < S; ++t) M = fmaxf(M, mred[t * QT + q2]);
+    float wsum = 0.f, wt[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) {
+        wt[t] = expf(mred[t * QT + q2] - M);   // a split without keys: exp(-inf) = 0
+        wsum = fmaf(lred[t * QT + q2], wt[t], wsum);
+    }
+    const float inv = 1.f / wsum;
+    float* op = out + (base + orow) * ldo + h * HDH + dg * DPT;
+#pragma unroll
+    for (int e = 0; e < DPT; ++e) {
+        const int d = dg * DPT + e;
+        float a = 0.f;
+#pragma unroll
+        for (int t = 0; t < S; ++t) a = fmaf(red[(t * HDH + d) * QT + q2], wt[t], a);
+        op[e] = a * inv;
+    }
+}
+
+int attention_launch(hipStream_t st, const float* q, const float* k, const float* v, int64_t ld, float* out, int64_t ldo,
+                     int64_t B, int L, int heads) {
+    // the largest query tile whose grid still covers the 256 CUs (small L: more, shorter workgroups)
+    const int64_t bh = B * heads;
+    const float scale = 0.125f;   // 1 / sqrt(64)
+    if (bh * ceil_div64(L, 64) >= 256) {
+        hipLaunchKernelGGL(attention_kernel<64>, dim3((unsigned)ceil_div64(L, 64), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale);
+    } else if (bh * ceil_div64(L, 32) >= 256) {
+        hipLaunchKernelGGL(attention_kernel<32>, dim3((unsigned)ceil_div64(L, 32), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale);
+    } else {
+        hipLaunchKernelGGL(attention_kernel<16>, dim3((unsigned)ceil_div64(L, 16), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale);
+    }
+    return 0;
+}
+
+// ---- GEMM helper --------------------------------------------------------------------------------------------
+template <class Epi>
+void hub_gemm(hipStream_t st, int math, const float* A, int64_t lda, int64_t sA, const float* W, int64_t ldw, int64_t sW_lo,
+              int M, int N, int K, int batch, int zdiv, const Epi& e) {
+    gemm::Args g = gemm::make(A, lda, W, ldw, M, N, K);
+    g.zdiv = zdiv;
+    if (zdiv > 1) {   // z = (outer, inner): A moves by sA per outer, by (L + 128) * 48 per inner; W by sW_lo per inner
+        g.sA_hi = sA * zdiv;
+        g.sA_lo = sA;
+        g.sB_lo = sW_lo;
+    } else {
+        g.sA_hi = sA;
+    }
+    g.math = math == DDSP_MATH_FP32 ? 0 : 3;
+    gemm::launch<true, true, gemm::A_PLAIN>(st, g, batch, e);
+}
+
+int64_t frames_of(int64_t T, int64_t (&t)[7]) {
+    if (T < 0) return -1;
+    int64_t n = T + 2 * HPAD;
+    if (n < 10) return 0;
+    n = (n - 10) / 5 + 1;
+    t[0] = n;
+    for (int i = 0; i < 6; ++i) {
+        const int kt = CONV_TAPS[i];
+        if (n < kt) return 0;
+        n = (n - kt) / 2 + 1;
+        t[i + 1] = n;
+    }
+    return n;
+}
+
+struct HubPlan {
+    size_t off[16];
+    size_t total;
+};
+enum { S_Y0, S_Y1, S_PART, S_AFF, S_Z, S_X, S_Y, S_QKV, S_CTX, S_H, S_XG, S_WCONV, S_WPOS, S_PSCALE, S_N };
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// bytes of the prepared weights: the six repacked conv matrices, the folded positional weights, the tap scales
+size_t wconv_floats() { return (size_t)HC * HC * (3 * 4 + 2 * 2); }
+size_t wpos_floats() { return (size_t)HD * POS_KK; }
+size_t prep_bytes() { return align256(wconv_floats() * 4) + align256(wpos_floats() * 4) + align256(POS_K * 4); }
+
+HubPlan plan(int64_t B, const int64_t (&t)[7]) {
+    const int64_t L = t[6];
+    size_t sz[S_N];
+    sz[S_Y0] = (size_t)B * t[0] * HC * 4;
+    sz[S_Y1] = (size_t)B * t[1] * HC * 4;
+    sz[S_PART] = (size_t)B * GN_PARTS * 2 * HC * 8;
+    sz[S_AFF] = (size_t)B * HC * 2 * 4;
+    sz[S_Z] = (size_t)B * L * HC * 4;
+    sz[S_X] = (size_t)B * L * HD * 4;
+    sz[S_Y] = (size_t)B * L * HD * 4;
+    sz[S_QKV] = (size_t)B * L * 3 * HD * 4;
+    sz[S_CTX] = (size_t)B * L * HD * 4;
+    sz[S_H] = (size_t)B * L * HFF * 4;
+    sz[S_XG] = (size_t)B * POS_G * (L + POS_K) * POS_C * 4;
+    sz[S_WCONV] = wconv_floats() * 4;
+    sz[S_WPOS] = wpos_floats() * 4;
+    sz[S_PSCALE] = POS_K * 4;
+    HubPlan p;
+    size_t o = 0;
+    for (int i = 0; i < S_N; ++i) {
+        p.off[i] = o;
+        o += align256(sz[i]);
+    }
+    p.total = o;
+    return p;
+}
+
+int prepare_weights(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights& w, float* wconv, float* wpos, float* pscale) {
+    size_t o = 0;
+    for (int i = 0; i < 6; ++i) {
+        const int64_t n = (int64_t)HC * HC * CONV_TAPS[i];
+        hipLaunchKernelGGL(conv_repack_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n, 256), 4096)), dim3(256), 0, st,
+                           w.conv_w[i], CONV_TAPS[i], n, wconv + o);
+        o += n;
+    }
+    hipLaunchKernelGGL(pos_norm_kernel, dim3(POS_K), dim3(256), 0, st, w.pos_v, w.pos_g, pscale);
+    hipLaunchKernelGGL(pos_weight_kernel, dim3(4096), dim3(256), 0, st, w.pos_v, pscale, wpos);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+bool weights_complete(const ddsp_hubert_weights& w) {
+    const float* const* p = (const float* const*)&w;
+    const size_t n = offsetof(ddsp_hubert_weights, version) / sizeof(const float*);
+    for (size_t i = 0; i < n; ++i)
+        if (!p[i]) return false;
+    return true;
+}
+
+// stop: -1 = conv stack output (B, Fr, 512); 0..12 = hidden state after that many transformer layers (B, Fr, 768);
+// 13 = units (B, Fr, 256)
+int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, const float* wav, int64_t B, int64_t T, int stop,
+               float* out) {
+    DDSP_REQUIRE(ctx, ctx && wp && wav && out, "ddsp_hubert: null argument");
+    DDSP_REQUIRE(ctx, weights_complete(*wp), "ddsp_hubert: a weight pointer is null");
+    DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && stop >= -1 && stop <= 13, "ddsp_hubert: bad shape or layer");
+    int64_t t[7];
+    const int64_t Fr = frames_of(T, t);
+    DDSP_REQUIRE(ctx, Fr >= 1, "ddsp_hubert: audio too short for the conv stack (ddsp_hubert_frames(T) == 0)");
+    DDSP_REQUIRE(ctx, B * t[0] < ((int64_t)1 << 31) && B * Fr * HFF < ((int64_t)1 << 31), "ddsp_hubert: input too long");
+    const ddsp_hubert_weights w = *wp;
+    DDSP_ENTER_DEVICE(ctx);
+    const int L = (int)Fr;
+    const int64_t rows = B * Fr;
+    const int math = ctx->math;
+
+    // prepared weights: the context's slot when the caller gives a change counter and the stream is not being captured (a graph
+    // replay must prepare the weights of ITS time), else scratch
+    const float *wconv = nullptr, *wpos = nullptr;
+    bool cached = false;
+    if (w.version != 0) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) cs = hipStreamCaptureStatusActive;
+        if (cs == hipStreamCaptureStatusNone) {
+            uint64_t key = 1469598103934665603ull;   // FNV-1a over the pointers
+            const unsigned char* bytes = (const unsigned char*)&w;
+            for (size_t i = 0; i < offsetof(ddsp_hubert_weights, version); ++i) key = (key ^ bytes[i]) * 1099511628211ull;
+            if (key == 0) key = 1;
+            if (!ctx->hcache) {
+                DDSP_HIP(ctx, hipMalloc((void**)&ctx->hcache, prep_bytes()));
+                ctx->hcache_key = 0;
+            }
+            char* base = ctx->hcache;
+            wconv = (const float*)base;
+            wpos = (const float*)(base + align256(wconv_floats() * 4));
+            float* pscale = (float*)(base + align256(wconv_floats() * 4) + align256(wpos_floats() * 4));
+            if (ctx->hcache_key != key || ctx->hcache_version != w.version) {
+                int rc = prepare_weights(ctx, st, w, (float*)wconv, (float*)wpos, pscale);
+                if (rc) return rc;
+                ctx->hcache_key = key;
+                ctx->hcache_version = w.version;
+            }
+            cached = true;
+        }
+    }
+    // (the arena always has room for the prepared weights: a capture after cached warm-up calls must not have to grow it)
+    const HubPlan p = plan(B, t);
+    int rc = ddsp_scratch_reserve_bytes(ctx, p.total + 4096);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    void* arena = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, p.total, &arena))) return rc;
+    char* a = (char*)arena;
+    auto buf = [&](int i) { return (float*)(a + p.off[i]); };
+    if (!cached) {
+        wconv = buf(S_WCONV);
+        wpos = buf(S_WPOS);
+        if ((rc = prepare_weights(ctx, st, w, buf(S_WCONV), buf(S_WPOS), buf(S_PSCALE)))) return rc;
+    }
+
+    // ---- feature extractor ----
+    float* y0 = buf(S_Y0);
+    float* y1 = buf(S_Y1);
+    hipLaunchKernelGGL(conv0_kernel, dim3(GN_PARTS, (unsigned)B), dim3(512), 0, st, wav, T, w.conv0_w, y0, t[0], (double*)buf(S_PART));
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(HC / 64, (unsigned)B), dim3(1024), 0, st, (const double*)buf(S_PART), t[0], w.norm0_w, w.norm0_b,
+                       buf(S_AFF));
+    {
+        const int64_t n4 = B * t[0] * HC / 4;
+        hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, st, y0, t[0], n4,
+                           (const float*)buf(S_AFF));
+    }
+    float* cur = y0;
+    float* nxt = y1;
+    size_t wo = 0;
+    for (int i = 0; i < 6; ++i) {
+        const int kt = CONV_TAPS[i];
+        EpiGelu e{nxt, HC, nullptr, t[i + 1] * HC};
+        hub_gemm(st, math, cur, 2 * HC, t[i] * HC, wconv + wo, (int64_t)kt * HC, 0, (int)t[i + 1], HC, kt * HC, (int)B, 1, e);
+        wo += (size_t)HC * HC * kt;
+        float* s = cur;
+        cur = nxt;
+        nxt = s;
+    }
+    if (stop == -1) {
+        DDSP_HIP(ctx, hipMemcpyAsync(out, cur, (size_t)rows * HC * 4, hipMemcpyDeviceToDevice, st));
+        DDSP_LAUNCH_CHECK(ctx);
+        return DDSP_OK;
+    }
+    // ---- feature projection, positional embedding, norm ----
+    const unsigned ln_grid = (unsigned)ceil_div64(rows, 4);
+    float* z = buf(S_Z);
+    float* X = buf(S_X);
+    float* Y = buf(S_Y);
+    hipLaunchKernelGGL(layernorm_kernel<HC>, dim3(ln_grid), dim3(256), 0, st, cur, nullptr, w.fp_norm_w, w.fp_norm_b, z, rows);
+    hub_gemm(st, math, z, HC, 0, w.fp_proj_w, HC, 0, (int)rows, HD, HC, 1, 1, gemm::EpiStore{X, HD, w.fp_proj_b, 1, 0, 0});
+    {
+        const int64_t n4 = B * POS_G * (L + POS_K) * POS_C / 4;
+        hipLaunchKernelGGL(pos_pack_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, st, X, L, n4,
+                           buf(S_XG));
+        hub_gemm(st, math, buf(S_XG), POS_C, (int64_t)(L + POS_K) * POS_C, wpos, POS_KK, (int64_t)POS_C * POS_KK, L, POS_C, POS_KK,
+                 (int)(B * POS_G), POS_G, EpiPos{Y, X, w.pos_b, L});
+    }
+    hipLaunchKernelGGL(layernorm_kernel<HD>, dim3(ln_grid), dim3(256), 0, st, Y, nullptr, w.norm_w, w.norm_b, X, rows);
+    // ---- transformer (post-norm) ----
+    float* qkv = buf(S_QKV);
+    float* cx = buf(S_CTX);
+    float* hh = buf(S_H);
+    const int nl = stop >= 12 ? 12 : stop;
+    for (int li = 0; li < nl; ++li) {
+        const ddsp_hubert_layer& ly = w.layer[li];
+        hub_gemm(st, math, X, HD, 0, ly.in_proj_w, HD, 0, (int)rows, 3 * HD, HD, 1, 1, gemm::EpiStore{qkv, 3 * HD, ly.in_proj_b, 1, 0, 0});
+        attention_launch(st, qkv, qkv + HD, qkv + 2 * HD, 3 * HD, cx, HD, B, L, HHEADS);
+        hub_gemm(st, math, cx, HD, 0, ly.out_proj_w, HD, 0, (int)rows, HD, HD, 1, 1, gemm::EpiResidual{Y, X, HD, ly.out_proj_b});
+        hipLaunchKernelGGL(layernorm_kernel<HD>, dim3(ln_grid), dim3(256), 0, st, Y, nullptr, ly.norm1_w, ly.norm1_b, X, rows);
+        hub_gemm(st, math, X, HD, 0, ly.linear1_w, HD, 0, (int)rows, HFF, HD, 1, 1, EpiGelu{hh, HFF, ly.linear1_b, 0});
+        hub_gemm(st, math, hh, HFF, 0, ly.linear2_w, HFF, 0, (int)rows, HD, HFF, 1, 1, gemm::EpiResidual{Y, X, HD, ly.linear2_b});
+        hipLaunchKernelGGL(layernorm_kernel<HD>, dim3(ln_grid), dim3(256), 0, st, Y, nullptr, ly.norm2_w, ly.norm2_b, X, rows);
+    }
+    if (stop <= 12) {
+        DDSP_HIP(ctx, hipMemcpyAsync(out, X, (size_t)rows * HD * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+        hub_gemm(st, math, X, HD, 0, w.proj_w, HD, 0, (int)rows, HU, HD, 1, 1, gemm::EpiStore{out, HU, w.proj_b, 1, 0, 0});
+    }
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t ddsp_hubert_frames(int64_t T) {
+    int64_t t[7];
+    return frames_of(T, t);
+}
+
+extern "C" int ddsp_hubert_soft_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
+                                      int64_t T, float* units) {
+    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, 13, units);
+}
+
+extern "C" int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
+                                  int layer, float* out) {
+    DDSP_REQUIRE(ctx, layer >= -1 && layer <= 12, "ddsp_hubert_encode: layer must be -1 (conv stack) or 0..12");
+    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out);
+}
+
+extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
+                                      int64_t L, int heads, float* out, int math) {
+    DDSP_REQUIRE(ctx, ctx && q && k && v && out, "ddsp_softmax_attention: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && L >= 0 && L < (1 << 30) && heads >= 1 && heads <= 4096, "ddsp_softmax_attention: bad shape");
+    DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16, "ddsp_softmax_attention: unknown math");
+    DDSP_REQUIRE(ctx, (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 16) == 0, "ddsp_softmax_attention: 16-byte aligned operands");
+    if (B == 0 || L == 0) return DDSP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    attention_launch(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads);
+    ddsp_prof_end(ctx, st, 4.0 * B * heads * (double)L * L * HDH, 16.0 * B * L * heads * HDH);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}

@@ -1,0 +1,188 @@
+"""HuBERT-Soft units encoder (the reference's `encoder/hubert/model.py` `HubertSoft`) executed by libddsp_amd.
+
+`HubertSoft` has exactly the reference's state-dict keys and shapes (166, including `masked_spec_embed` and
+`label_embedding.weight`, which `units` does not read), so the released checkpoint loads with `strict=True`.
+`units(wav (B,1,T)) -> (B, Fr, 256)` runs on the device only (a CPU tensor raises RuntimeError); `encode(wav, layer)` gives
+the conv stack's output (layer=-1) or the hidden state after `layer` transformer layers.  Inference only: nothing here
+records gradients (the reference runs the encoder under `torch.inference_mode`).
+
+The library keeps its prepared copies of the weights (repacked convolutions, the folded weight norm) while the parameters'
+values stand: every in-place write (`load_state_dict`, `copy_`, an optimizer step) advances a tensor's `_version`, and the
+struct handed to the library carries their sum.
+"""
+import os
+
+import torch
+from torch import nn
+
+import hipddsp
+
+SAMPLE_RATE = 16000
+HOP_SIZE = 320
+
+
+def n_frames(T):
+    """Encoder frames of T samples at 16 kHz (`ddsp_hubert_frames`); ValueError when the audio is too short for the conv stack."""
+    n = hipddsp.hubert_frames(int(T))
+    if n <= 0:
+        raise ValueError(f"HubertSoft: {int(T)} samples are too short for the conv stack")
+    return n
+
+
+class _WeightNormConv(nn.Module):
+    """`positional_embedding.conv` after `weight_norm(dim=2)`: its keys are `bias`, `weight_g`, `weight_v`."""
+
+    def __init__(self):
+        super().__init__()
+        self.bias = nn.Parameter(torch.zeros(768))
+        self.weight_g = nn.Parameter(torch.ones(1, 1, 128))
+        self.weight_v = nn.Parameter(torch.zeros(768, 48, 128))
+
+
+class _Linear(nn.Module):
+    def __init__(self, n_in, n_out):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(n_out, n_in))
+        self.bias = nn.Parameter(torch.zeros(n_out))
+
+
+class _Norm(nn.Module):
+    def __init__(self, n):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(n))
+        self.bias = nn.Parameter(torch.zeros(n))
+
+
+class _Conv(nn.Module):
+    def __init__(self, c_in, c_out, k):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(c_out, c_in, k))
+
+
+class _Attention(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.zeros(2304, 768))
+        self.in_proj_bias = nn.Parameter(torch.zeros(2304))
+        self.out_proj = _Linear(768, 768)
+
+
+class _Layer(nn.Module):
+    """`nn.TransformerEncoderLayer(768, 12, 3072, activation="gelu", batch_first=True)`, post-norm."""
+
+    def __init__(self):
+        super().__init__()
+        self.self_attn = _Attention()
+        self.linear1 = _Linear(768, 3072)
+        self.linear2 = _Linear(3072, 768)
+        self.norm1 = _Norm(768)
+        self.norm2 = _Norm(768)
+
+
+class _FeatureExtractor(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.conv0 = _Conv(1, 512, 10)
+        self.norm0 = _Norm(512)
+        for i, k in enumerate((3, 3, 3, 3, 2, 2)):
+            setattr(self, f"conv{i + 1}", _Conv(512, 512, k))
+
+
+class _FeatureProjection(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.norm = _Norm(512)
+        self.projection = _Linear(512, 768)
+
+
+class _PositionalEmbedding(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.conv = _WeightNormConv()
+
+
+class _Encoder(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.layers = nn.ModuleList([_Layer() for _ in range(12)])
+
+
+class HubertSoft(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.masked_spec_embed = nn.Parameter(torch.zeros(768))
+        self.feature_extractor = _FeatureExtractor()
+        self.feature_projection = _FeatureProjection()
+        self.positional_embedding = _PositionalEmbedding()
+        self.norm = _Norm(768)
+        self.encoder = _Encoder()
+        self.proj = _Linear(768, 256)
+        self.label_embedding = nn.Embedding(100, 256)
+        self._ws = None
+
+    # ---- pointer table ---------------------------------------------------------------------------
+    def _named_tensors(self):
+        """(HubertWeights field, tensor) in the order of `ddsp_hubert_weights`."""
+        fe, fp, pc = self.feature_extractor, self.feature_projection, self.positional_embedding.conv
+        out = [("conv0_w", fe.conv0.weight), ("norm0_w", fe.norm0.weight), ("norm0_b", fe.norm0.bias)]
+        out += [(f"conv{i}_w", getattr(fe, f"conv{i}").weight) for i in range(1, 7)]
+        out += [("fp_norm_w", fp.norm.weight), ("fp_norm_b", fp.norm.bias), ("fp_proj_w", fp.projection.weight),
+                ("fp_proj_b", fp.projection.bias), ("pos_b", pc.bias), ("pos_g", pc.weight_g), ("pos_v", pc.weight_v),
+                ("norm_w", self.norm.weight), ("norm_b", self.norm.bias)]
+        for i, ly in enumerate(self.encoder.layers):
+            t = (ly.self_attn.in_proj_weight, ly.self_attn.in_proj_bias, ly.self_attn.out_proj.weight,
+                 ly.self_attn.out_proj.bias, ly.linear1.weight, ly.linear1.bias, ly.linear2.weight, ly.linear2.bias,
+                 ly.norm1.weight, ly.norm1.bias, ly.norm2.weight, ly.norm2.bias)
+            out += [(f"l{i}_{n}", x) for n, x in zip(hipddsp.HUBERT_LAYER_FIELDS, t)]
+        out += [("proj_w", self.proj.weight), ("proj_b", self.proj.bias)]
+        return out
+
+    def _weights_struct(self):
+        named = self._named_tensors()
+        tensors = [t for _, t in named]
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        if self._ws is not None and self._ws[0] == key:
+            return self._ws[1]
+        w = hipddsp.HubertWeights()
+        keep = []
+        for name, t in named:
+            if not t.is_cuda:
+                raise RuntimeError("HubertSoft parameters must live on a HIP device (no CPU fallback)")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("HubertSoft parameters must be contiguous fp32")
+            keep.append(t)
+            setattr(w, name, t.data_ptr())
+        # the nonce tells two modules apart whose tensors the allocator placed at the same addresses
+        if not hasattr(self, "_weights_nonce"):
+            self._weights_nonce = int.from_bytes(os.urandom(6), "little") << 16
+        w.version = (self._weights_nonce + 1 + sum(int(t._version) for t in tensors)) & ((1 << 64) - 1)
+        self._ws = (key, w, keep)
+        return w
+
+    def _wav(self, wav):
+        if not wav.is_cuda:
+            raise RuntimeError("HubertSoft runs on a HIP device only (no CPU fallback)")
+        if wav.dim() != 3 or wav.shape[1] != 1:
+            raise ValueError("HubertSoft: wav must be (B, 1, T)")
+        n_frames(wav.shape[-1])
+        return wav[:, 0].contiguous().float()
+
+    @torch.no_grad()
+    def units(self, wav):
+        """:: (B, 1, T) 16 kHz -> (B, Frame, 256)"""
+        x = self._wav(wav)
+        return hipddsp.context_for(x.device).hubert_units(self._weights_struct(), x)
+
+    @torch.no_grad()
+    def encode(self, wav, layer=None):
+        """:: (B, 1, T) -> the hidden state (B, Frame, 768) after `layer` transformer layers (all 12 when None), or the conv
+        stack's output (B, Frame, 512) for layer=-1.  Unlike the reference's `encode`, the audio is padded here as `units`
+        pads it, and no mask is returned."""
+        x = self._wav(wav)
+        layer = 12 if layer is None else int(layer)
+        if not -1 <= layer <= 12:
+            raise ValueError("HubertSoft.encode: layer in -1..12")
+        return hipddsp.context_for(x.device).hubert_encode(self._weights_struct(), x, layer)
+
+    def forward(self, wav):
+        return self.units(wav)

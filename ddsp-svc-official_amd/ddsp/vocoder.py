@@ -62,6 +62,70 @@ def align_units(units, n_samples, sample_rate, hop_size, encoder_sample_rate=160
     return hipddsp.context_for(units.device).align_units(units, n_frames, ratio)
 
 
+class Audio2HubertSoft(torch.nn.Module):
+    """Reference `ddsp/vocoder.py:214-229`: the HuBERT-Soft checkpoint (`module.` prefix stripped) behind `forward(audio (B,T))
+    -> units (B, Frame, 256)`, executed by libddsp_amd (`ddsp.hubert.HubertSoft`).  The module is built on `device` (default:
+    the current HIP device) because there is no CPU execution path."""
+
+    def __init__(self, path, h_sample_rate=16000, h_hop_size=320, device=None):
+        super().__init__()
+        from torch.nn.modules.utils import consume_prefix_in_state_dict_if_present
+        from .hubert import HubertSoft
+        print(' [Encoder Model] HuBERT Soft')
+        self.hubert = HubertSoft()
+        print(' [Loading] ' + path)
+        checkpoint = torch.load(path, map_location="cpu")
+        consume_prefix_in_state_dict_if_present(checkpoint, "module.")
+        self.hubert.load_state_dict(checkpoint)
+        self.hubert.eval()
+        if device is not None:
+            self.hubert.to(device)
+
+    def forward(self, audio):
+        """ :: (B, T) -> (B, 1, T) -> (B, Frame, Feat=256) """
+        return self.hubert.units(audio.unsqueeze(1))
+
+
+class Units_Encoder:
+    """Reference `ddsp/vocoder.py:140-211` for `encoder='hubertsoft'`: resampling to the encoder's rate (`ddsp_resample`,
+    lowpass_filter_width=128, as the reference's torchaudio Resample), the encoder and the nearest-frame alignment
+    (`align_units`), all on the device.
+
+    Differences a caller can observe, all additive: audio (B,T) with B > 1 returns every row aligned (the reference
+    returns row 0 only); the other encoder names raise NotImplementedError - `hubertsoft` is the device encoder, and callers
+    that keep the reference's encoders can align their units on the device with `align_units`."""
+
+    def __init__(self, encoder, encoder_ckpt, encoder_sample_rate=16000, encoder_hop_size=320, device=None):
+        if encoder in ('hubertbase', 'hubertbase768', 'contentvec', 'contentvec768', 'xunit', 'yunit'):
+            raise NotImplementedError(
+                f"units encoder '{encoder}' has no device implementation: 'hubertsoft' is the device encoder; callers that "
+                "keep the reference's encoders can align their units on the device with ddsp.vocoder.align_units")
+        if encoder != 'hubertsoft':
+            raise ValueError(f" [x] Unknown units encoder: {encoder}")
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
+            device = "cuda"
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback); got device=%r" % (device,))
+        self.device = device
+        self.model = Audio2HubertSoft(encoder_ckpt, device=device)
+        self.model = self.model.eval()
+        self.encoder_sample_rate = encoder_sample_rate
+        self.encoder_hop_size = encoder_hop_size
+
+    def encode(self, audio, sample_rate, hop_size):
+        """audio (B,T) at `sample_rate` -> units (B, int(T // hop_size) + 1, 256) aligned to frames of `hop_size` samples
+        (a float hop keeps its fraction, like the reference's)."""
+        if not audio.is_cuda:
+            raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
+        ctx = hipddsp.context_for(audio.device)
+        audio_res = audio if sample_rate == self.encoder_sample_rate else \
+            ctx.resample(audio, int(sample_rate), int(self.encoder_sample_rate), lowpass_filter_width=128)
+        units = self.model(audio_res)
+        return align_units(units, audio.size(-1), sample_rate, hop_size, self.encoder_sample_rate, self.encoder_hop_size)
+
+
 class DotDict(dict):
     """Attribute access to nested config dicts (reference `ddsp/vocoder.py:335-341`)."""
 

@@ -19,7 +19,7 @@ COMB_NONE, COMB_SINC, COMB_SINC_GATED = 0, 1, 2
 FIR_ALLPASS, FIR_DYNAMIC, FIR_STATIC = 0, 1, 2
 EXC_AUDIO, EXC_UNIT_NOISE, EXC_GENERATE = 0, 1, 2
 FIR_FP32, FIR_SPLIT_BF16 = 0, 3   # ddsp_ltv_fir `math` (include/ddsp_amd.h)
-ABI_VERSION = 5                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights)
+ABI_VERSION = 6                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights)
 MATH_FP32, MATH_SPLIT_BF16 = 0, 3  # ddsp_ctx_set_math
 ATTENTION_CAUSAL = 200            # ddsp_performer_attention: causal_linear_attention (pcmer.py:170-188)
 
@@ -38,6 +38,22 @@ class U2CWeights(_c.Structure):
             "norm_w", "norm_b", "q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "proj", "out_w", "out_b",
             "cm_ln_w", "cm_ln_b", "cm_pw1_w", "cm_pw1_b", "cm_dw_w", "cm_dw_b", "cm_pw2_w", "cm_pw2_b")]
         + [(n, _vp) for n in ("final_ln_w", "final_ln_b", "head_g", "head_v", "head_b")]
+        + [("version", _c.c_uint64)]     # change counter of the weight values (0: prepare the weights on every call)
+    )
+
+
+HUBERT_LAYER_FIELDS = ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "linear1_w", "linear1_b", "linear2_w",
+                       "linear2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")
+
+
+class HubertWeights(_c.Structure):
+    """Mirror of `ddsp_hubert_weights` (include/ddsp_amd.h): device pointers into the HubertSoft state dict."""
+    _fields_ = (
+        [(n, _vp) for n in ("conv0_w", "norm0_w", "norm0_b")]
+        + [(f"conv{i + 1}_w", _vp) for i in range(6)]
+        + [(n, _vp) for n in ("fp_norm_w", "fp_norm_b", "fp_proj_w", "fp_proj_b", "pos_b", "pos_g", "pos_v", "norm_w", "norm_b")]
+        + [(f"l{i}_{n}", _vp) for i in range(12) for n in HUBERT_LAYER_FIELDS]
+        + [(n, _vp) for n in ("proj_w", "proj_b")]
         + [("version", _c.c_uint64)]     # change counter of the weight values (0: prepare the weights on every call)
     )
 
@@ -109,6 +125,10 @@ SIGNATURES = {
     "ddsp_adamw_step_multi": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i64]),
     "ddsp_gemm_f32": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _i64, _int, _vp, _vp, _i64, _int, _int, _int, _int, _int]),
     "ddsp_performer_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _int]),
+    "ddsp_hubert_frames": (_i64, [_i64]),
+    "ddsp_hubert_soft_units": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp]),
+    "ddsp_hubert_encode": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _int, _vp]),
+    "ddsp_softmax_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int]),
     "ddsp_profile_begin": (_int, [_vp, _u64]),
     "ddsp_profile_mask": (_int, [_vp, _u64]),
     "ddsp_profile_end": (_int, [_vp, _c.POINTER(ProfEntry), _int, _c.POINTER(_int)]),
@@ -596,6 +616,38 @@ class Context:
         self.call("ddsp_performer_attention", _ptr(q), _ptr(k), _ptr(v), _ptr(proj), int(B), int(Fr), _ptr(out), int(math))
         return out
 
+    def softmax_attention(self, q, k, v, B, L, heads, math=MATH_SPLIT_BF16):
+        """q, k, v (B*L, heads*64) -> softmax(q k^T / 8) v per (utterance, head), merged heads (B*L, heads*64)."""
+        out = torch.empty(B * L, heads * 64, device=q.device, dtype=torch.float32)
+        self.call("ddsp_softmax_attention", _ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math))
+        return out
+
+    # -- units encoder -------------------------------------------------------------------------
+    def hubert_units(self, weights, wav):
+        """weights: a HubertWeights struct; wav (B,T) 16 kHz fp32 -> units (B, Fr, 256)."""
+        B, T = wav.shape
+        Fr = hubert_frames(T)
+        if Fr <= 0:
+            raise ValueError(f"hubert: {T} samples are too short for the conv stack")
+        wav = wav.contiguous().float()
+        out = torch.empty(B, Fr, 256, device=wav.device, dtype=torch.float32)
+        if B:
+            self.call("ddsp_hubert_soft_units", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(out))
+        return out
+
+    def hubert_encode(self, weights, wav, layer):
+        """The conv stack's output (B, Fr, 512) for layer -1, else the hidden state (B, Fr, 768) after `layer` of the 12
+        transformer layers."""
+        B, T = wav.shape
+        Fr = hubert_frames(T)
+        if Fr <= 0:
+            raise ValueError(f"hubert: {T} samples are too short for the conv stack")
+        wav = wav.contiguous().float()
+        out = torch.empty(B, Fr, 512 if layer == -1 else 768, device=wav.device, dtype=torch.float32)
+        if B:
+            self.call("ddsp_hubert_encode", ctypes.byref(weights), _ptr(wav), int(B), int(T), int(layer), _ptr(out))
+        return out
+
     # -- a10 -----------------------------------------------------------------------------------
     def sins_bank(self, ctrl2d, col0, n_harmonics, f0_frames, phase, B, Fr, hop, sr):
         out = torch.empty(B, Fr * hop, device=ctrl2d.device, dtype=torch.float32)
@@ -681,6 +733,11 @@ _ctx_lock = threading.Lock()
 
 
 _override = threading.local()
+
+
+def hubert_frames(T):
+    """Encoder frames of T samples (`ddsp_hubert_frames`, a host computation): 0 when the audio is too short."""
+    return int(load_library().ddsp_hubert_frames(int(T)))
 
 
 class use_context:

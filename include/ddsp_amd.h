@@ -380,6 +380,55 @@ int ddsp_gemm_res_ln(ddsp_ctx* ctx, void* stream, const float* A_split, const fl
 int ddsp_performer_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v,
                              const float* proj, int64_t B, int64_t Fr, float* out, int math);
 
+/* ---- the units encoder (HuBERT-Soft, encoder/hubert/model.py; ddsp/vocoder.py:140-229) ------------------- */
+/* Device pointers into the HubertSoft state dict, fp32, dense, in the reference's key order (the two keys `units` does not
+ * read, `masked_spec_embed` and `label_embedding.weight`, are left out):
+ *   conv0_w  feature_extractor.conv0.weight (512,1,10)      norm0_w/_b  feature_extractor.norm0.{weight,bias} (512)
+ *   conv_w[i] feature_extractor.conv{i+1}.weight (512,512,3) for i < 4, (512,512,2) for i = 4, 5
+ *   fp_norm_w/_b, fp_proj_w/_b  feature_projection.norm (512), feature_projection.projection (768,512), (768)
+ *   pos_b, pos_g, pos_v  positional_embedding.conv.{bias (768), weight_g (1,1,128), weight_v (768,48,128)}
+ *   norm_w/_b  norm (768)
+ *   layer[i]   encoder.layers.i.{self_attn.in_proj_weight (2304,768), self_attn.in_proj_bias, self_attn.out_proj.weight
+ *              (768,768), .bias, linear1.weight (3072,768), .bias, linear2.weight (768,3072), .bias, norm1.*, norm2.*}
+ *   proj_w/_b  proj (256,768), (256)
+ * `version` as in ddsp_u2c_weights: 0 = prepare the weights (conv repacking, weight-norm fold: ~36 MB) on every call;
+ * otherwise the context keeps its prepared copy while every pointer AND the version are what they were. */
+typedef struct ddsp_hubert_layer {
+    const float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} ddsp_hubert_layer;
+
+typedef struct ddsp_hubert_weights {
+    const float *conv0_w, *norm0_w, *norm0_b;
+    const float* conv_w[6];
+    const float *fp_norm_w, *fp_norm_b, *fp_proj_w, *fp_proj_b;
+    const float *pos_b, *pos_g, *pos_v;
+    const float *norm_w, *norm_b;
+    ddsp_hubert_layer layer[12];
+    const float *proj_w, *proj_b;
+    uint64_t version;
+} ddsp_hubert_weights;
+
+/* Encoder frames of T samples at 16 kHz: T' = T + 80, (T' - 10) / 5 + 1, then (n - 3) / 2 + 1 four times and (n - 2) / 2 + 1
+ * twice; 0 when the audio is too short for the conv stack, -1 for T < 0.  Host only. */
+int64_t ddsp_hubert_frames(int64_t T);
+/* replaces `HubertSoft.units(wav (B,1,T))` (encoder/hubert/model.py): wav (B,T) 16 kHz -> units (B, Fr, 256),
+ * Fr = ddsp_hubert_frames(T).  The GEMMs use the context's product arithmetic (ddsp_ctx_set_math); conv0, the norms and
+ * the softmax attention run in fp32.  No host synchronisation once the scratch arena (and the prepared-weight slot) exist,
+ * so the call can be captured into a HIP graph. */
+int ddsp_hubert_soft_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
+                           float* units);
+/* `Hubert.encode(wav, layer)` without the final projection, for tests and callers of intermediate features:
+ * layer -1 = the conv stack's output (B, Fr, 512); 0..12 = the hidden state (B, Fr, 768) after that many transformer layers. */
+int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
+                       int layer, float* out);
+/* building block: softmax attention softmax(q k^T / 8) v per (utterance, head), no mask, any L (online softmax: no L x L
+ * matrix).  q, k, v, out (B*L, heads*64) rows, head h at columns 64h..64h+63.  math: DDSP_MATH_FP32 or
+ * DDSP_MATH_SPLIT_BF16; both run fp32 products (the attention is ~3 % of the encoder's work at a 4.5 s window).  Exposed for
+ * unit tests. */
+int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B, int64_t L,
+                           int heads, float* out, int math);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream --------------------- */
 /* ddsp_profile_begin arms the families in `family_mask` (bit i = family i, see the name returned); while armed,
  * each kernel launch of such a family is bracketed by hipEventRecord on the caller's stream.  ddsp_profile_end
