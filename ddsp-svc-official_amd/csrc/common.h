@@ -34,6 +34,14 @@ struct ddsp_prof_rec {
 };
 #define DDSP_PROF_CAP 16384
 
+// One network's prepared weights, kept in the context between calls (ddsp_weight_slot_take)
+struct ddsp_weight_slot {
+    char* dev;
+    size_t bytes;
+    uint64_t key, version;   // hash of the caller's struct without its counter (pointers, sizes) / its change counter; key 0 = empty
+    int state;               // what the slot holds, as its entry point defines it; 0 whenever the key or the version changes
+};
+
 struct ddsp_ctx {
     int device;
     int math;   // product arithmetic of the inference GEMMs (ddsp_ctx_set_math): DDSP_MATH_SPLIT_BF16 (default) or DDSP_MATH_FP32
@@ -47,20 +55,12 @@ struct ddsp_ctx {
     char* scratch;
     size_t scratch_bytes;
     size_t scratch_used;
-    // prepared weights of the control network (ddsp_u2c_weights::version != 0): one slot
-    char* wcache;
-    size_t wcache_bytes;
-    uint64_t wcache_key, wcache_version;   // hash of the caller's struct (pointers, sizes) / its change counter; key 0 = empty
-    int wcache_flags;                      // what the slot holds: bit 0 split copies, bit 1 fused-GLU order, bit 2 attention pieces
+    // prepared weights of the control network (ddsp_u2c_weights::version != 0) and of the units encoder
+    // (ddsp_hubert_weights::version != 0)
+    ddsp_weight_slot u2c_slot, hubert_slot;
     ddsp_table tables[64];
     int n_tables;
     uint64_t table_clock;
-    // packed control-net weights (prepared by ddsp_u2c_prepare)
-    float* packed;
-    size_t packed_bytes;
-    // prepared weights of the units encoder (ddsp_hubert_weights::version != 0): one slot
-    char* hcache;
-    uint64_t hcache_key, hcache_version;
     // 8 KiB of zeros: the source of out-of-range conv taps in the LDS-DMA GEMM (a DMA cannot be predicated to zero)
     float* zero_page;
     // device-side contract violations (a speaker id outside the table): one int in host-mapped memory that kernels set
@@ -137,6 +137,11 @@ inline const char*& ddsp_launch_refusal() {
 int ddsp_scratch_reset(ddsp_ctx* ctx);
 int ddsp_scratch_get(ddsp_ctx* ctx, size_t bytes, void** out);
 int ddsp_scratch_reserve_bytes(ddsp_ctx* ctx, size_t bytes);
+// prepared-weight slot (ctx.hip): *out = `slot`, grown to `bytes`, for a call whose weight struct `w` has the change counter
+// `version` (`key_bytes`: the struct's bytes before that counter); null - prepare into scratch - when version == 0 or the
+// stream is being captured (a graph replay must prepare the weights of ITS time)
+int ddsp_weight_slot_take(ddsp_ctx* ctx, hipStream_t st, ddsp_weight_slot& slot, const void* w, size_t key_bytes,
+                          uint64_t version, size_t bytes, ddsp_weight_slot** out);
 // tables (tables.hip)
 int ddsp_get_table(ddsp_ctx* ctx, hipStream_t st, int kind, int n0, int n1, float** out);
 // device pointer to DDSP_ZERO_FLOATS zeros (allocated on first use; a first-use synchronisation like the tables)

@@ -33,10 +33,9 @@ extern "C" int ddsp_ctx_destroy(ddsp_ctx* ctx) {
     (void)guard.enter(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->packed) (void)hipFree(ctx->packed);
     if (ctx->zero_page) (void)hipFree(ctx->zero_page);
-    if (ctx->wcache) (void)hipFree(ctx->wcache);
-    if (ctx->hcache) (void)hipFree(ctx->hcache);
+    if (ctx->u2c_slot.dev) (void)hipFree(ctx->u2c_slot.dev);
+    if (ctx->hubert_slot.dev) (void)hipFree(ctx->hubert_slot.dev);
     if (ctx->dev_error_host) (void)hipHostFree(ctx->dev_error_host);
     if (ctx->prof) {
         for (int i = 0; i < ctx->prof_events_made; ++i) {
@@ -77,6 +76,35 @@ int ddsp_scratch_reserve_bytes(ddsp_ctx* ctx, size_t bytes) {
     if (e != hipSuccess) return ddsp_fail(ctx, DDSP_ERR_OOM, "scratch hipMalloc", hipGetErrorString(e));
     ctx->scratch = (char*)p;
     ctx->scratch_bytes = want;
+    return DDSP_OK;
+}
+
+int ddsp_weight_slot_take(ddsp_ctx* ctx, hipStream_t st, ddsp_weight_slot& slot, const void* w, size_t key_bytes,
+                          uint64_t version, size_t bytes, ddsp_weight_slot** out) {
+    *out = nullptr;
+    if (version == 0) return DDSP_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return DDSP_OK;
+    uint64_t key = 1469598103934665603ull;   // FNV-1a
+    const unsigned char* p = (const unsigned char*)w;
+    for (size_t i = 0; i < key_bytes; ++i) key = (key ^ p[i]) * 1099511628211ull;
+    if (key == 0) key = 1;
+    if (slot.bytes < bytes) {
+        if (slot.dev) {
+            // (the stream may still read the old buffer: wait for it before it goes)
+            DDSP_HIP(ctx, hipStreamSynchronize(st));
+            (void)hipFree(slot.dev);
+        }
+        slot = ddsp_weight_slot{};
+        DDSP_HIP(ctx, hipMalloc((void**)&slot.dev, bytes));
+        slot.bytes = bytes;
+    }
+    if (slot.key != key || slot.version != version) {
+        slot.key = key;
+        slot.version = version;
+        slot.state = 0;
+    }
+    *out = &slot;
     return DDSP_OK;
 }
 

@@ -477,38 +477,26 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     const int64_t rows = B * Fr;
     const int math = ctx->math;
 
-    // prepared weights: the context's slot when the caller gives a change counter and the stream is not being captured (a graph
-    // replay must prepare the weights of ITS time), else scratch
+    // prepared weights: the context's slot (state bit 0: prepared), else scratch
     const float *wconv = nullptr, *wpos = nullptr;
-    bool cached = false;
-    if (w.version != 0) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) cs = hipStreamCaptureStatusActive;
-        if (cs == hipStreamCaptureStatusNone) {
-            uint64_t key = 1469598103934665603ull;   // FNV-1a over the pointers
-            const unsigned char* bytes = (const unsigned char*)&w;
-            for (size_t i = 0; i < offsetof(ddsp_hubert_weights, version); ++i) key = (key ^ bytes[i]) * 1099511628211ull;
-            if (key == 0) key = 1;
-            if (!ctx->hcache) {
-                DDSP_HIP(ctx, hipMalloc((void**)&ctx->hcache, prep_bytes()));
-                ctx->hcache_key = 0;
-            }
-            char* base = ctx->hcache;
-            wconv = (const float*)base;
-            wpos = (const float*)(base + align256(wconv_floats() * 4));
-            float* pscale = (float*)(base + align256(wconv_floats() * 4) + align256(wpos_floats() * 4));
-            if (ctx->hcache_key != key || ctx->hcache_version != w.version) {
-                int rc = prepare_weights(ctx, st, w, (float*)wconv, (float*)wpos, pscale);
-                if (rc) return rc;
-                ctx->hcache_key = key;
-                ctx->hcache_version = w.version;
-            }
-            cached = true;
+    ddsp_weight_slot* slot;
+    int rc = ddsp_weight_slot_take(ctx, st, ctx->hubert_slot, &w, offsetof(ddsp_hubert_weights, version), w.version, prep_bytes(),
+                                   &slot);
+    if (rc) return rc;
+    const bool cached = slot != nullptr;
+    if (cached) {
+        char* base = slot->dev;
+        wconv = (const float*)base;
+        wpos = (const float*)(base + align256(wconv_floats() * 4));
+        float* pscale = (float*)(base + align256(wconv_floats() * 4) + align256(wpos_floats() * 4));
+        if (!(slot->state & 1)) {
+            if ((rc = prepare_weights(ctx, st, w, (float*)wconv, (float*)wpos, pscale))) return rc;
+            slot->state = 1;
         }
     }
     // (the arena always has room for the prepared weights: a capture after cached warm-up calls must not have to grow it)
     const HubPlan p = plan(B, t);
-    int rc = ddsp_scratch_reserve_bytes(ctx, p.total + 4096);
+    rc = ddsp_scratch_reserve_bytes(ctx, p.total + 4096);
     if (rc) return rc;
     ddsp_scratch_reset(ctx);
     void* arena = nullptr;

@@ -2676,42 +2676,19 @@ extern "C" int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_we
     DDSP_ENTER_DEVICE(ctx);
     const ddsp_u2c_weights w = *wp;
     U2CBufs bf;
-    // prepared-weight slot of the context (ddsp_u2c_weights::version != 0; never while the stream is being captured: a graph
-    // replay must prepare the weights of ITS time)
-    bool cached = false;
-    if (w.version != 0) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) cs = hipStreamCaptureStatusActive;
-        if (cs == hipStreamCaptureStatusNone) {
-            uint64_t key = 1469598103934665603ull;   // FNV-1a over the struct without its counter: pointers and sizes
-            const unsigned char* bytes = (const unsigned char*)&w;
-            for (size_t i = 0; i < offsetof(ddsp_u2c_weights, version); ++i) key = (key ^ bytes[i]) * 1099511628211ull;
-            if (key == 0) key = 1;
-            Arena wdry{ctx, true, 0, 0};
-            plan_weights(wdry, bf, w);
-            if (ctx->wcache_bytes < wdry.total) {
-                // (the stream may still read the old buffer: wait for it before it goes)
-                DDSP_HIP(ctx, hipStreamSynchronize(st));
-                if (ctx->wcache) (void)hipFree(ctx->wcache);
-                ctx->wcache = nullptr;
-                ctx->wcache_bytes = 0;
-                ctx->wcache_key = 0;
-                DDSP_HIP(ctx, hipMalloc((void**)&ctx->wcache, wdry.total));
-                ctx->wcache_bytes = wdry.total;
-            }
-            if (ctx->wcache_key != key || ctx->wcache_version != w.version) {
-                ctx->wcache_key = key;
-                ctx->wcache_version = w.version;
-                ctx->wcache_flags = 0;
-            }
-            Arena wa{ctx, false, 0, 0};
-            wa.ext = ctx->wcache;
-            wa.ext_cap = ctx->wcache_bytes;
-            plan_weights(wa, bf, w);
-            if (wa.rc) return wa.rc;
-            bf.wstate = &ctx->wcache_flags;
-            cached = true;
-        }
+    Arena wdry{ctx, true, 0, 0};
+    plan_weights(wdry, bf, w);
+    ddsp_weight_slot* slot;
+    if ((rc = ddsp_weight_slot_take(ctx, st, ctx->u2c_slot, &w, offsetof(ddsp_u2c_weights, version), w.version, wdry.total, &slot)))
+        return rc;
+    const bool cached = slot != nullptr;
+    if (cached) {
+        Arena wa{ctx, false, 0, 0};
+        wa.ext = slot->dev;
+        wa.ext_cap = slot->bytes;
+        plan_weights(wa, bf, w);
+        if (wa.rc) return wa.rc;
+        bf.wstate = &slot->state;
     }
     // (the arena is sized for a call WITHOUT the slot too: a capture that follows warm-up calls must not have to grow it)
     Arena dry{ctx, true, 0, 0};

@@ -7,11 +7,8 @@ the conv stack's output (layer=-1) or the hidden state after `layer` transformer
 records gradients (the reference runs the encoder under `torch.inference_mode`).
 
 The library keeps its prepared copies of the weights (repacked convolutions, the folded weight norm) while the parameters'
-values stand: every in-place write (`load_state_dict`, `copy_`, an optimizer step) advances a tensor's `_version`, and the
-struct handed to the library carries their sum.
+values stand, as `hipddsp.WeightTable` describes: a write that torch does not count (into `p.data`) needs `rebind()`.
 """
-import os
-
 import torch
 from torch import nn
 
@@ -118,7 +115,7 @@ class HubertSoft(nn.Module):
         self.encoder = _Encoder()
         self.proj = _Linear(768, 256)
         self.label_embedding = nn.Embedding(100, 256)
-        self._ws = None
+        self._table = hipddsp.WeightTable(hipddsp.HubertWeights, HubertSoft._named_tensors, "HubertSoft")
 
     # ---- pointer table ---------------------------------------------------------------------------
     def _named_tensors(self):
@@ -137,27 +134,13 @@ class HubertSoft(nn.Module):
         out += [("proj_w", self.proj.weight), ("proj_b", self.proj.bias)]
         return out
 
+    def rebind(self):
+        """Forget the weight struct and have the library re-prepare the weights: after a submodule was replaced, or after a
+        write `_version` does not count (`hipddsp.WeightTable`)."""
+        self._table.invalidate()
+
     def _weights_struct(self):
-        named = self._named_tensors()
-        tensors = [t for _, t in named]
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        if self._ws is not None and self._ws[0] == key:
-            return self._ws[1]
-        w = hipddsp.HubertWeights()
-        keep = []
-        for name, t in named:
-            if not t.is_cuda:
-                raise RuntimeError("HubertSoft parameters must live on a HIP device (no CPU fallback)")
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("HubertSoft parameters must be contiguous fp32")
-            keep.append(t)
-            setattr(w, name, t.data_ptr())
-        # the nonce tells two modules apart whose tensors the allocator placed at the same addresses
-        if not hasattr(self, "_weights_nonce"):
-            self._weights_nonce = int.from_bytes(os.urandom(6), "little") << 16
-        w.version = (self._weights_nonce + 1 + sum(int(t._version) for t in tensors)) & ((1 << 64) - 1)
-        self._ws = (key, w, keep)
-        return w
+        return self._table.struct(self)[0]
 
     def _wav(self, wav):
         if not wav.is_cuda:

@@ -8,8 +8,6 @@ Only the non-causal configuration (`c: false`, every shipped config) exists; `c=
 """
 import math
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -156,7 +154,9 @@ class Unit2Control(nn.Module):
         self.spk_embed.weight = nn.Parameter(torch.randn(self.n_spk, NDIM))
         self.dec_post = nn.Sequential(_PCmer(NDIM), _Affine((NDIM,), NDIM, ones=True),
                                       _WeightNormHead(NDIM, self.n_out))
-        self._packed_version = None
+        self._table = hipddsp.WeightTable(hipddsp.U2CWeights, Unit2Control._named_tensors, "Unit2Control", copy=True,
+                                          grad_uncached=True, n_spk=self.n_spk, n_unit=self.n_unit, n_out=self.n_out,
+                                          causal=int(self.causal))
 
     # ---- raw pointer table ---------------------------------------------------------------------
     def _named_tensors(self):
@@ -212,60 +212,13 @@ class Unit2Control(nn.Module):
             ctx.unit2ctrl_bwd(w, g, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, d_ctrl)
         return grads
 
-    def _tensor_slots(self):
-        """(struct field, owning dict, key) for every tensor of `ddsp_u2c_weights`, built once: reading `d[k]` costs a dict
-        lookup where `module.weight` goes through nn.Module.__getattr__ (the walk over the 75 tensors took longer on the host than
-        a B = 1 forward takes on the device).  A Parameter replaced by setattr lands in the same dict and is seen; after replacing
-        a whole SUBMODULE call `rebind()`."""
-        slots = getattr(self, "_slots", None)
-        if slots is None:
-            by_id = {}
-            for mod in self.modules():
-                for d in (mod._parameters, mod._buffers):
-                    for k, t in d.items():
-                        if t is not None:
-                            by_id[id(t)] = (d, k)
-            slots = self._slots = [(name,) + by_id[id(t)] for name, t in self._named_tensors()]
-        return slots
-
     def rebind(self):
-        """Forget the cached tensor slots / weight struct (after a submodule of this network was replaced)."""
-        self._slots = None
-        self._ws = None
+        """Forget the weight struct and have the library re-prepare the weights: after a submodule of this network was replaced,
+        or after a write `_version` does not count (`hipddsp.WeightTable`)."""
+        self._table.invalidate()
 
     def _weights_struct(self):
-        slots = self._tensor_slots()
-        tensors = [d[k] for _, d, k in slots]
-        grad_mode = torch.is_grad_enabled()
-        key = (grad_mode,) + tuple([(t.data_ptr(), t._version) for t in tensors])
-        ws = getattr(self, "_ws", None)
-        if ws is not None and ws[0] == key:
-            return ws[1], ws[2]
-        w = hipddsp.U2CWeights()
-        keep = []
-        for (name, _, _), t in zip(slots, tensors):
-            if not t.is_cuda:
-                raise RuntimeError("Unit2Control parameters must live on a HIP device (no CPU fallback)")
-            t = t.detach()
-            if not t.is_contiguous() or t.dtype != torch.float32:
-                t = t.contiguous().float()
-            keep.append(t)
-            setattr(w, name, t.data_ptr())
-        w.n_spk, w.n_unit, w.n_out = self.n_spk, self.n_unit, self.n_out
-        w.causal = 1 if self.causal else 0
-        # inference: the library may keep its prepared copies of these weights while their values stand (every in-place change of
-        # a tensor - optimizer step, load_state_dict, copy_ - advances its `_version`); training steps prepare them every time
-        # (the nonce tells two model objects apart whose tensors the allocator placed at the same addresses)
-        if grad_mode:
-            w.version = 0
-        else:
-            if not hasattr(self, "_weights_nonce"):
-                self._weights_nonce = int.from_bytes(os.urandom(6), "little") << 16
-            w.version = (self._weights_nonce + 1 + sum(int(t._version) for t in tensors)) & ((1 << 64) - 1)
-        # (a copy made by `contiguous().float()` above has a new address every time: such a struct is not worth keeping)
-        if all(a is b or a.data_ptr() == b.data_ptr() for a, b in zip(keep, tensors)):
-            self._ws = (key, w, keep)
-        return w, keep
+        return self._table.struct(self)
 
     def forward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict=None):
         """(B, Fr, n_out) fused control matrix (the split views are taken by `forward`)."""

@@ -58,6 +58,61 @@ class HubertWeights(_c.Structure):
     )
 
 
+class WeightTable:
+    """The weight struct (U2CWeights, HubertWeights) of one model, built from `named_tensors(module)` -> [(field, tensor)].
+
+    The library keeps the weights it prepares from the struct while its pointers, integers and `version` stand.  `version` is
+    a per-model nonce (two models whose tensors the allocator placed at the same addresses differ in it) plus the sum of
+    the tensors' `_version` counters, so every write torch counts re-prepares them: an in-place op, `load_state_dict`, an
+    optimizer step (`training.AdamW` calls `torch.autograd.graph.increment_version`).  A write torch does not count - into
+    `p.data`, or a foreign kernel writing through the pointer - needs `invalidate()` or `increment_version(p)`.
+
+    `copy`: a tensor that is not contiguous fp32 is passed as a contiguous fp32 copy (and the struct is not kept); otherwise
+    it raises.  `grad_uncached`: in grad mode `version` is 0 (prepare on every call).  `ints`: the struct's integer fields."""
+
+    def __init__(self, struct_cls, named_tensors, owner, copy=False, grad_uncached=False, **ints):
+        self.struct_cls, self.named_tensors, self.owner = struct_cls, named_tensors, owner
+        self.copy, self.grad_uncached, self.ints = copy, grad_uncached, ints
+        self.invalidate()
+
+    def invalidate(self):
+        """Forget the tensor slots and the struct, and draw a new nonce: the next call re-reads the module (after a submodule
+        was replaced) and the library re-prepares the weights."""
+        self._slots = self._ws = None
+        self._nonce = int.from_bytes(os.urandom(6), "little") << 16
+
+    def struct(self, module):
+        """-> (struct, the tensors it points into: hold them until the call has been queued)."""
+        if self._slots is None:
+            # (field, owning dict, key), built once: reading `d[k]` costs a dict lookup where `module.weight` goes through
+            # nn.Module.__getattr__.  A Parameter replaced by setattr lands in the same dict and is seen.
+            by_id = {id(t): (d, k) for mod in module.modules() for d in (mod._parameters, mod._buffers)
+                     for k, t in d.items() if t is not None}
+            self._slots = [(name,) + by_id[id(t)] for name, t in self.named_tensors(module)]
+        tensors = [d[k] for _, d, k in self._slots]
+        uncached = self.grad_uncached and torch.is_grad_enabled()
+        key = (uncached,) + tuple([(t.data_ptr(), t._version) for t in tensors])
+        if self._ws is not None and self._ws[0] == key:
+            return self._ws[1], self._ws[2]
+        w = self.struct_cls(**self.ints)
+        keep = []
+        for (name, _, _), t in zip(self._slots, tensors):
+            if not t.is_cuda:
+                raise RuntimeError(f"{self.owner} parameters must live on a HIP device (no CPU fallback)")
+            t = t.detach()
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                if not self.copy:
+                    raise ValueError(f"{self.owner} parameters must be contiguous fp32")
+                t = t.contiguous().float()
+            keep.append(t)
+            setattr(w, name, t.data_ptr())
+        w.version = 0 if uncached else (self._nonce + 1 + sum(int(t._version) for t in tensors)) & ((1 << 64) - 1)
+        # (a copy has a new address every time: such a struct is not worth keeping)
+        if all(a.data_ptr() == b.data_ptr() for a, b in zip(keep, tensors)):
+            self._ws = (key, w, keep)
+        return w, keep
+
+
 class ProfEntry(_c.Structure):
     """Mirror of `ddsp_prof_entry`."""
     _fields_ = [("family", _int), ("name", _c.c_char * 36), ("launches", _i64), ("ms_total", _c.c_double),

@@ -36,11 +36,14 @@ class AdamW(torch.optim.Optimizer):
                 if not p.data.is_contiguous():
                     raise ValueError("AdamW kernel needs contiguous parameters")
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                batches.setdefault((p.device, int(st["step"])), []).append((p.data, g, st["exp_avg"], st["exp_avg_sq"]))
+                batches.setdefault((p.device, int(st["step"])), []).append((p, g, st["exp_avg"], st["exp_avg_sq"]))
             for (device, step), items in batches.items():
                 ps, gs, ms, vs = zip(*items)
                 hipddsp.context_for(device).adamw_step_multi(ps, gs, ms, vs, group["lr"], b1, b2, group["eps"],
                                                              group["weight_decay"], step)
+                # the kernel writes through the pointers: count the write as torch.optim.AdamW's in-place updates do, so that
+                # the models' prepared weights (hipddsp.WeightTable) follow the step
+                torch.autograd.graph.increment_version(ps)
         return loss
 
 

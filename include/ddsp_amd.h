@@ -139,9 +139,11 @@ typedef struct ddsp_u2c_weights {
     /* The caller's change counter of the weight VALUES, or 0.  ddsp_unit2ctrl_fwd prepares the weights for its kernels on every
      * call (weight norm of the head, re-ordered pw1 rows, bf16 hi/lo copies: two launches, ~1.5 % of a 64-clip forward).  With
      * version != 0 it keeps the prepared copies in the context and reuses them while every pointer and integer of this struct
-     * AND the version are what they were - so bump it whenever a tensor's contents change (torch: the sum of the parameters'
-     * `_version` counters does that).  Ignored while the stream is being captured into a HIP graph (a replay must see the
-     * weights of its own time) and by the training entry points. */
+     * AND the version are what they were - so bump it whenever a tensor's contents change.  (torch: the sum of the parameters'
+     * `_version` counters does that for every write torch counts; a write through the pointer - `.data`, a foreign kernel -
+     * must advance the counter itself, `torch.autograd.graph.increment_version`, as ddsp_adamw_step's caller does.)  Ignored
+     * while the stream is being captured into a HIP graph (a replay must see the weights of its own time) and by the training
+     * entry points. */
     uint64_t version;
 } ddsp_u2c_weights;
 
@@ -392,7 +394,8 @@ int ddsp_performer_attention(ddsp_ctx* ctx, void* stream, const float* q, const 
  *              (768,768), .bias, linear1.weight (3072,768), .bias, linear2.weight (768,3072), .bias, norm1.*, norm2.*}
  *   proj_w/_b  proj (256,768), (256)
  * `version` as in ddsp_u2c_weights: 0 = prepare the weights (conv repacking, weight-norm fold: ~36 MB) on every call;
- * otherwise the context keeps its prepared copy while every pointer AND the version are what they were. */
+ * otherwise the context keeps its prepared copy while every pointer AND the version are what they were, so the caller
+ * advances the version with every write to a weight. */
 typedef struct ddsp_hubert_layer {
     const float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b;
     const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;

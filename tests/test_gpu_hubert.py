@@ -162,6 +162,36 @@ def test_load_state_dict_after_a_forward_reprepares_the_weights(model, dev):
 
 
 @pytest.mark.gpu
+def test_prepared_weights_follow_in_place_writes_and_models(model, dev):
+    """Two models on one context keep their prepared weights apart; an in-place write under no_grad, and a `.data` write
+    followed by `rebind()`, reach the next call - each bit for bit what a fresh model computes."""
+    from ddsp.hubert import HubertSoft
+
+    def fresh(sd):
+        f = HubertSoft().to(dev)
+        f.load_state_dict(sd)
+        return f.units(x)
+
+    x = HC.audio("short").unsqueeze(1).to(dev)
+    m1, m2 = HubertSoft().to(dev), HubertSoft().to(dev)
+    m1.load_state_dict(model.state_dict())
+    m2.load_state_dict({k: v * 0.9 if k.endswith("weight_v") else v for k, v in model.state_dict().items()})
+    u1, u2 = m1.units(x), m2.units(x)
+    assert not torch.equal(u1, u2)
+    assert torch.equal(m1.units(x), u1) and torch.equal(u1, fresh(m1.state_dict()))
+    assert torch.equal(m2.units(x), u2) and torch.equal(u2, fresh(m2.state_dict()))
+    with torch.no_grad():
+        m1.feature_extractor.conv1.weight.mul_(0.9)
+    after = m1.units(x)
+    assert not torch.equal(after, u1) and torch.equal(after, fresh(m1.state_dict()))
+    w = m1.positional_embedding.conv.weight_g
+    w.data.copy_(w.data * 1.1)
+    m1.rebind()
+    again = m1.units(x)
+    assert not torch.equal(again, after) and torch.equal(again, fresh(m1.state_dict()))
+
+
+@pytest.mark.gpu
 def test_graph_capture_replays_bit_identically(model, dev):
     import hipddsp
     x = HC.audio("gui").unsqueeze(1).to(dev)

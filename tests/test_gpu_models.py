@@ -564,10 +564,10 @@ def test_combsubfast_shipped_encoder_widths(dev, lib_path, n_unit, B):
     assert err < GATE, (n_unit, B, err, rms(sig_o))
 
 
-def test_prepared_weight_cache_follows_the_weights(dev, lib_path):
-    """Inference keeps the control network's prepared weights (weight norm, re-ordered / bf16 copies) in the context between
-    calls (`ddsp_u2c_weights::version`): an in-place change of a parameter, a load_state_dict and a second model on the same
-    context must each be seen by the next forward - bit for bit what a fresh context computes."""
+@pytest.fixture
+def u2c_calls(dev):
+    """(run, fresh) on one small input: a no_grad `forward_flat` of a model's control network, and the same forward with
+    preparation forced (grad mode on: version 0)."""
     import hipddsp
     B, Fr = 4, 40
     inp = _to(synthetic.make_inputs(5, B, Fr, with_noise=False), dev)
@@ -577,13 +577,21 @@ def test_prepared_weight_cache_follows_the_weights(dev, lib_path):
         with torch.no_grad():
             return model.unit2ctrl.forward_flat(inp["units"], inp["f0"], phase, inp["volume"], inp["spk_id"], None).clone()
 
-    def fresh(model):   # the same forward with preparation forced (grad mode on: version 0)
+    def fresh(model):
         with torch.enable_grad():
             w, keep = model.unit2ctrl._weights_struct()
             assert w.version == 0
             ctx = hipddsp.context_for(dev)
             return ctx.unit2ctrl(w, inp["units"], inp["f0"], phase, inp["volume"], inp["spk_id"], None, model.unit2ctrl.n_out).clone()
 
+    return run, fresh
+
+
+def test_prepared_weight_cache_follows_the_weights(dev, lib_path, u2c_calls):
+    """Inference keeps the control network's prepared weights (weight norm, re-ordered / bf16 copies) in the context between
+    calls (`ddsp_u2c_weights::version`): an in-place change of a parameter, a load_state_dict and a second model on the same
+    context must each be seen by the next forward - bit for bit what a fresh context computes."""
+    run, fresh = u2c_calls
     m1, _ = synthetic.build_model("CombSub", seed=21, device=dev)
     m2, _ = synthetic.build_model("CombSub", seed=22, device=dev)
     a1 = run(m1)
@@ -597,6 +605,36 @@ def test_prepared_weight_cache_follows_the_weights(dev, lib_path):
     assert not torch.equal(b1, a1) and torch.equal(b1, fresh(m1))
     m1.load_state_dict(m2.state_dict())
     assert torch.equal(run(m1), a2)
+
+
+def test_prepared_weights_follow_an_adamw_step(dev, lib_path, u2c_calls):
+    """`training.AdamW` writes the parameters in a kernel, through their pointers: the next inference forward must still see
+    the step (the reference's train -> validate -> train -> validate loop) - bit for bit what a forward that prepares computes."""
+    import training
+    from ddsp.loss import RSSLoss
+    run, fresh = u2c_calls
+    m, _ = synthetic.build_model("CombSub", seed=23, device=dev)
+    a = run(m)
+    B, Fr = 2, 24
+    batch = _to(synthetic.make_inputs(7, B, Fr), dev)
+    batch["audio"] = (0.1 * torch.randn(B, Fr * HOP, generator=torch.Generator().manual_seed(8))).to(dev)
+    m.train()
+    training.train_step(m, training.AdamW(m.parameters(), lr=5e-4), RSSLoss(256, 2048, 4, device=dev), batch,
+                        scales=[300, 777, 1531, 2047])
+    b = run(m)
+    assert not torch.equal(b, a) and torch.equal(b, fresh(m))
+
+
+def test_prepared_weights_follow_a_data_write_after_rebind(dev, lib_path, u2c_calls):
+    """A write into `p.data` does not advance the parameter's `_version`: after `rebind()` the next forward prepares again."""
+    run, fresh = u2c_calls
+    m, _ = synthetic.build_model("CombSub", seed=24, device=dev)
+    a = run(m)
+    g = m.unit2ctrl.dec_post[2].weight_g
+    g.data.copy_(g.data * 1.5)
+    m.unit2ctrl.rebind()
+    b = run(m)
+    assert not torch.equal(b, a) and torch.equal(b, fresh(m))
 
 
 @pytest.mark.parametrize("causal", [0, 1])
