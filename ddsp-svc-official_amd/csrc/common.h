@@ -55,9 +55,9 @@ struct ddsp_ctx {
     char* scratch;
     size_t scratch_bytes;
     size_t scratch_used;
-    // prepared weights of the control network (ddsp_u2c_weights::version != 0) and of the units encoder
-    // (ddsp_hubert_weights::version != 0)
-    ddsp_weight_slot u2c_slot, hubert_slot;
+    // prepared weights of the control network (ddsp_u2c_weights::version != 0), of the units encoder
+    // (ddsp_hubert_weights::version != 0) and of the f0 extractor (ddsp_crepe_weights::version != 0)
+    ddsp_weight_slot u2c_slot, hubert_slot, crepe_slot;
     ddsp_table tables[64];
     int n_tables;
     uint64_t table_clock;

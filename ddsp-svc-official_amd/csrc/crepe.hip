@@ -1,0 +1,701 @@
+// CREPE pitch tracker (the 'crepe' branch of the reference's F0_Extractor, ddsp/vocoder.py:39-113: torchcrepe.predict with
+// pad=True, hop 80, the Viterbi decoder, then the reference's median / threshold / masked-average post-filter) on gfx950.
+//
+// Network (torchcrepe's 'full' or 'tiny'; frame-major fp32 activations, one row per (CREPE frame, position)):
+//   * framing: each 1024-sample frame normalised (fp64 mean and unbiased std) and written with the conv1 padding (254 zeros
+//     on each side: 1532 floats per frame);
+//   * conv1 (1 -> W0, 512 taps, stride 4): a GEMM over OVERLAPPING rows, batched over the frames: A(m, k) = frame[4m + k],
+//     lda = 4 < K = 512, frames 1532 floats apart (gemm_f32.h, A_FRAMES note); the weights are already (Cout, K);
+//   * conv2..conv6 (64 taps, padding (31, 32)): the A_CONVK implicit-im2col loader with Fr = positions per CREPE frame - its
+//     centring (ktaps - 1) / 2 = 31 is exactly the (31, 32) padding, and m % Fr keeps every frame's zeros inside the frame;
+//     weights repacked once to (Cout, tap * Cin + ci);
+//   * each conv's epilogue (EpiPool) is bias -> ReLU -> batch norm folded to a scale and shift -> max over row pairs (the
+//     2x1 pool), storing half the rows;
+//   * classifier (4 * W5 -> 360), then the sigmoid.
+// The network runs over at most NET_CHUNK frames at a time (torchcrepe's batch_size of the reference's call).
+// Decode: one row kernel (mask, softmax, log) and one workgroup per (utterance, segment) for the Viterbi recursion.
+#include "gemm_f32.h"
+
+#include <algorithm>
+#include <math.h>
+#include <stddef.h>
+
+namespace {
+
+constexpr int WIN = 1024;                  // samples per CREPE frame
+constexpr int C1_TAPS = 512, C1_STRIDE = 4, C1_PAD = 254;
+constexpr int FRAME_LD = WIN + 2 * C1_PAD;  // 1532 floats per padded frame
+constexpr int C1_POS = 256;                // conv1 output positions per frame
+constexpr int TAPS = 64;                   // conv2..conv6
+constexpr int BINS = 360;
+constexpr int NET_CHUNK = 512;             // frames per network pass
+constexpr float BN_EPS = 0.0010000000474974513f;
+constexpr float CENTS0 = 1997.3794084376191f;
+// librosa.sequence.viterbi in fp64: log(1/360 + tiny) (uniform start) and log(0 + tiny) (an out-of-band transition), tiny =
+// fp32's smallest normal (util.tiny of the fp32 emissions)
+constexpr double LOG_INIT = -0x1.78b5edaefba8cp+2;   // -5.886104031450156
+constexpr double LOG_EPS = -0x1.5d589f2fe5107p+6;    // -87.3365447505531
+constexpr float TINY_F = 1.17549435e-38f;
+constexpr int BAND = 23;                   // in-band transitions |i - j| <= 11
+
+// ---- GEMM epilogues --------------------------------------------------------------------------------------
+// out[z * sO + (m / 2) * ldo + n] = max(y(m), y(m + 1)),  y = relu(acc + bias[n]) * scale[n] + shift[n]
+struct EpiPool {
+    float* out;
+    int64_t ldo, sO;
+    const float* bias;
+    const float* scale;
+    const float* shift;
+    static constexpr bool kRowPair = true;
+    __device__ __forceinline__ float col(int n) const { return bias[n]; }
+    __device__ __forceinline__ void pair(int z, int m, int n, float a, float b, float cb) const {
+        const float s = scale[n], t = shift[n];
+        const float ya = fmaxf(a + cb, 0.f) * s + t;
+        const float yb = fmaxf(b + cb, 0.f) * s + t;
+        out[(int64_t)z * sO + (int64_t)(m >> 1) * ldo + n] = fmaxf(ya, yb);
+    }
+};
+
+// in place: x = sigmoid(x) (the classifier's activation; a separate pass keeps expf out of the GEMM epilogue's registers)
+__global__ void __launch_bounds__(256) sigmoid_kernel(float* __restrict__ x, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = 1.0f / (1.0f + expf(-x[i]));
+}
+
+// ---- framing -----------------------------------------------------------------------------------------------
+// block per frame z (of the chunk starting at frame z0 of the B * Fr flattened frames): 1532 floats, 254 zeros, the 1024
+// normalised samples, 254 zeros.  Sample s of frame f reads audio[f * hop + s - 512] (zero outside the utterance).
+__global__ void __launch_bounds__(256) frame_kernel(const float* __restrict__ audio, int64_t T, int64_t Fr, int hop, int64_t z0,
+                                                    float* __restrict__ frames) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int64_t z = z0 + blockIdx.x;
+    const int64_t b = z / Fr, f = z % Fr;
+    const float* x = audio + b * T;
+    float v[4];
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t idx = f * hop + tid + 256 * i - WIN / 2;
+        v[i] = (idx >= 0 && idx < T) ? x[idx] : 0.f;
+        s += (double)v[i];
+    }
+    s = wave_sum_d(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    const double mean = ((red[0] + red[1]) + (red[2] + red[3])) / WIN;
+    __syncthreads();
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double d = (double)v[i] - mean;
+        q += d * d;
+    }
+    q = wave_sum_d(q);
+    if ((tid & 63) == 0) red[tid >> 6] = q;
+    __syncthreads();
+    const double sd = sqrt(((red[0] + red[1]) + (red[2] + red[3])) / (WIN - 1));
+    const double den = sd > 1e-10 ? sd : 1e-10;
+    float* out = frames + (int64_t)blockIdx.x * FRAME_LD;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[C1_PAD + tid + 256 * i] = (float)(((double)v[i] - mean) / den);
+    if (tid < C1_PAD) {
+        out[tid] = 0.f;
+        out[C1_PAD + WIN + tid] = 0.f;
+    }
+}
+
+// ---- weight preparation (one launch) ------------------------------------------------------------------------
+struct PrepArgs {
+    const float* w[6];
+    const float* bn_w[6];
+    const float* bn_b[6];
+    const float* bn_mean[6];
+    const float* bn_var[6];
+    float* wpk[6];      // repacked conv2..conv6 (index 0 unused)
+    float* scale[6];
+    float* shift[6];
+    int cin[6], cout[6];
+    int64_t end[12];    // prefix ends of the work items: repack of layers 1..5, then the fold of layers 0..5
+};
+
+__global__ void __launch_bounds__(256) prep_kernel(PrepArgs a) {
+    const int64_t total = a.end[10];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        int s = 0;
+        while (i >= a.end[s]) ++s;
+        const int64_t r = i - (s ? a.end[s - 1] : 0);
+        if (s < 5) {
+            // (Cout, Cin, 64, 1) -> (Cout, tap * Cin + ci)
+            const int l = s + 1, cin = a.cin[l];
+            const int64_t co = r / ((int64_t)TAPS * cin);
+            const int kk = (int)(r % ((int64_t)TAPS * cin)), t = kk / cin, ci = kk % cin;
+            a.wpk[l][r] = a.w[l][(co * cin + ci) * TAPS + t];
+        } else {
+            const int l = s - 5, c = (int)r;
+            const double sc = (double)a.bn_w[l][c] / sqrt((double)a.bn_var[l][c] + (double)BN_EPS);
+            a.scale[l][c] = (float)sc;
+            a.shift[l][c] = (float)((double)a.bn_b[l][c] - (double)a.bn_mean[l][c] * sc);
+        }
+    }
+}
+
+// ---- decode -------------------------------------------------------------------------------------------------
+// one wave per frame: emissions log(softmax(masked probs) + tiny) (fp32), the mask [0, lo) and [hi, 360)
+__global__ void __launch_bounds__(256) emission_kernel(const float* __restrict__ probs, int64_t rows, int lo, int hi,
+                                                       float* __restrict__ logp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* p = probs + row * BINS;
+    float x[6];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int j = lane + 64 * i;
+        x[i] = (j < BINS && j >= lo && j < hi) ? p[j] : -INFINITY;
+        mx = fmaxf(mx, x[i]);
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        x[i] = expf(x[i] - mx);   // masked: exp(-inf) = 0
+        s += x[i];
+    }
+    s = wave_sum(s);
+    float* o = logp + row * BINS;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int j = lane + 64 * i;
+        if (j < BINS) o[j] = logf(x[i] / s + TINY_F);
+    }
+}
+
+__device__ __forceinline__ uint32_t hash32(uint64_t seed, uint64_t idx) {
+    // the counter hash of the noise generator (ltv_fir.hip noise_u): two rounds of the lowbias32 finaliser
+    uint32_t x = (uint32_t)idx ^ (uint32_t)seed;
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    x += (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32);
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+constexpr int VT = 384;        // threads of the Viterbi workgroup (6 waves; states j < 360)
+constexpr int BT_ROWS = 64;    // back-pointer rows staged in LDS per backtracking block
+constexpr int PF = 8;          // emission frames per prefetch block of the Viterbi recursion
+
+__device__ __forceinline__ void argmax_merge(double& v, int& i, double v2, int i2) {
+    if (v2 > v || (v2 == v && i2 < i)) {
+        v = v2;
+        i = i2;
+    }
+}
+
+// grid (segments, B).  Frames [t0, t1) of utterance b, decoded on their own from a uniform start:
+//   value[t][j] = logp[t][j] + max_i(value[t-1][i] + logT[i][j])  (fp64, first i on ties)
+// computed exactly from the 23 in-band candidates and the out-of-band term value[t-1][g] + log(tiny), g = the first global
+// argmax of value[t-1]: every in-band logT exceeds log(tiny), so an out-of-band i beats the band only if it is g.
+__global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ logp, const float* __restrict__ probs, int64_t Fr,
+                                                     int64_t seg, int lo, int hi, uint16_t* __restrict__ ptr, uint64_t seed,
+                                                     int dither, float* __restrict__ f0, float* __restrict__ pd,
+                                                     int32_t* __restrict__ bins_out) {
+    __shared__ double band[BINS * BAND];        // logT[j + d - 11][j] at [j * 23 + d]; reused for back-pointer rows
+    __shared__ double val[2][BINS];
+    __shared__ double rv[2][8];
+    __shared__ int ri[2][8];
+    __shared__ int16_t state[1024];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y;
+    const int64_t t0 = (int64_t)blockIdx.x * seg;
+    const int n = (int)std::min<int64_t>(seg, Fr - t0);
+    const float* lp = logp + ((int64_t)b * Fr + t0) * BINS;
+    uint16_t* pt = ptr + ((int64_t)b * Fr + t0) * BINS;
+    // transition table: row i of T is max(12 - |i - j|, 0) / sum_j(...), the sum exact in integers
+    for (int e = tid; e < BINS * BAND; e += VT) {
+        const int j = e / BAND, d = e % BAND, i = j + d - 11;
+        double v = -INFINITY;
+        if (i >= 0 && i < BINS) {
+            int rowsum = 0;
+            for (int u = -11; u <= 11; ++u)
+                if (i + u >= 0 && i + u < BINS) rowsum += 12 - (u < 0 ? -u : u);
+            const int dd = d - 11 < 0 ? 11 - d : d - 11;
+            v = log((double)(12 - dd) / (double)rowsum);   // (+ tiny: below half an ulp of any in-band entry)
+        }
+        band[e] = v;
+    }
+    // value[0] and its argmax
+    double v = -INFINITY;
+    if (tid < BINS) {
+        v = (double)lp[tid] + LOG_INIT;
+        val[0][tid] = v;
+    }
+    double wv = v;
+    int wi = tid < BINS ? tid : 1 << 20;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v2 = __shfl_xor(wv, o, 64);
+        const int i2 = __shfl_xor(wi, o, 64);
+        argmax_merge(wv, wi, v2, i2);
+    }
+    if (lane == 0) {
+        rv[0][wave] = wv;
+        ri[0][wave] = wi;
+    }
+    __syncthreads();
+    // one step of the recursion (emission e of frame s); the barrier orders the LDS only - a __syncthreads() would also wait for
+    // every outstanding global access of the thread (its back-pointer stores, the emission prefetch) on every step
+    auto step = [&](int s, float e) {
+        const int pb = (s - 1) & 1, cbuf = s & 1;
+        double gv = rv[pb][0];
+        int g = ri[pb][0];
+        for (int w = 1; w < VT / 64; ++w) argmax_merge(gv, g, rv[pb][w], ri[pb][w]);
+        double nv = -INFINITY;
+        int ni = 1 << 20;
+        if (tid < BINS) {
+            const int j = tid;
+            double best = -INFINITY;
+            int bi = -1;
+#pragma unroll
+            for (int d = 0; d < BAND; ++d) {
+                const int i = j + d - 11;
+                if (i >= 0 && i < BINS) {
+                    const double c = val[pb][i] + band[j * BAND + d];
+                    if (c > best) {
+                        best = c;
+                        bi = i;
+                    }
+                }
+            }
+            if (g < j - 11 || g > j + 11) {
+                const double c = gv + LOG_EPS;
+                if (c > best || (c == best && g < bi)) {
+                    best = c;
+                    bi = g;
+                }
+            }
+            nv = (double)e + best;
+            ni = j;
+            val[cbuf][j] = nv;
+            pt[(int64_t)s * BINS + j] = (uint16_t)bi;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const double v2 = __shfl_xor(nv, o, 64);
+            const int i2 = __shfl_xor(ni, o, 64);
+            argmax_merge(nv, ni, v2, i2);
+        }
+        if (lane == 0) {
+            rv[cbuf][wave] = nv;
+            ri[cbuf][wave] = ni;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    // emissions PF frames ahead: the block after the current one is in flight while the current one is consumed
+    float cur[PF], nxt[PF];
+    auto load_block = [&](int base, float (&dst)[PF]) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) dst[u] = (tid < BINS && base + u < n) ? lp[(int64_t)(base + u) * BINS + tid] : 0.f;
+    };
+    load_block(1, cur);
+    for (int base = 1; base < n; base += PF) {
+        load_block(base + PF, nxt);
+#pragma unroll
+        for (int u = 0; u < PF; ++u)
+            if (base + u < n) step(base + u, cur[u]);
+#pragma unroll
+        for (int u = 0; u < PF; ++u) cur[u] = nxt[u];
+    }
+    // backtrack from the first argmax of the last values; back-pointer rows staged through LDS, BT_ROWS at a time
+    {
+        const int pb = (n - 1) & 1;
+        double gv = rv[pb][0];
+        int g = ri[pb][0];
+        for (int w = 1; w < VT / 64; ++w) argmax_merge(gv, g, rv[pb][w], ri[pb][w]);
+        if (tid == 0) state[n - 1] = (int16_t)g;
+    }
+    uint16_t* rows = (uint16_t*)band;
+    for (int hiRow = n - 1; hiRow >= 1; hiRow -= BT_ROWS) {
+        const int loRow = hiRow - BT_ROWS + 1 > 1 ? hiRow - BT_ROWS + 1 : 1;
+        __syncthreads();   // (the previous block's chase is done with the staging rows; state[] of hiRow + 1 is written)
+        const int cnt = (hiRow - loRow + 1) * BINS;
+        for (int e = tid; e < cnt; e += VT) rows[e] = pt[(int64_t)loRow * BINS + e];
+        __syncthreads();
+        if (tid == 0) {
+            int st = state[hiRow];
+            for (int r = hiRow; r >= loRow; --r) {
+                st = rows[(r - loRow) * BINS + st];
+                state[r - 1] = (int16_t)st;
+            }
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < n; t += VT) {
+        const int bin = state[t];
+        const int64_t o = (int64_t)b * Fr + t0 + t;
+        float cents = (float)(20 * bin) + CENTS0;
+        if (dither) {
+            const float u1 = (float)(hash32(seed, 2 * (uint64_t)o) >> 8) * (1.0f / 16777216.0f);
+            const float u2 = (float)(hash32(seed, 2 * (uint64_t)o + 1) >> 8) * (1.0f / 16777216.0f);
+            cents = cents + 20.0f * ((u1 + u2) - 1.0f);   // triangular on (-20, 20), mode 0 (scipy triang(c=0.5))
+        }
+        f0[o] = 10.0f * exp2f(cents / 1200.0f);
+        pd[o] = (bin >= lo && bin < hi) ? probs[o * BINS + bin] : -INFINITY;
+        if (bins_out) bins_out[o] = bin;
+    }
+}
+
+// ---- post-filter (one workgroup per utterance) -------------------------------------------------------------------
+__device__ __forceinline__ int64_t reflect_idx(int64_t i, int64_t n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+
+__global__ void __launch_bounds__(256) postfilter_kernel(const float* __restrict__ f0, const float* __restrict__ pd, int64_t Fr,
+                                                         int sr, double hop, int64_t n_frames, int64_t start_frame, float thr,
+                                                         int uv_interp, float f0_min, float* __restrict__ pooled,
+                                                         float* __restrict__ out) {
+    __shared__ int64_t first_v[256], last_v[256];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* f = f0 + (int64_t)b * Fr;
+    const float* p = pd + (int64_t)b * Fr;
+    float* pl = pooled + (int64_t)b * Fr;
+    float* o = out + (int64_t)b * n_frames;
+    // MedianPool1d(pd, 4) -> At(thr) -> MaskedAvgPool1d(f0, 4); window i = reflect(i - 1 .. i + 2)
+    for (int64_t i = tid; i < Fr; i += 256) {
+        float sum = 0.f, cnt = 0.f;
+        float q[4], fv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t c = reflect_idx(i - 1 + k, Fr);
+            // the median window of this position c of the threshold step: pd at reflect(c - 1 .. c + 2)
+            float w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = p[reflect_idx(c - 1 + u, Fr)];
+            // lower median of 4: the second smallest (sorting network)
+            float a0 = fminf(w[0], w[1]), a1 = fmaxf(w[0], w[1]), a2 = fminf(w[2], w[3]), a3 = fmaxf(w[2], w[3]);
+            const float lo2 = fmaxf(a0, a2), hi2 = fminf(a1, a3);
+            q[k] = fminf(lo2, hi2);
+            fv[k] = q[k] < thr ? NAN : f[c];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool ok = !isnan(fv[k]);
+            sum = sum + (ok ? fv[k] : 0.f);
+            cnt = cnt + (ok ? 1.f : 0.f);
+        }
+        pl[i] = sum / (cnt > 1.f ? cnt : 1.f);
+    }
+    __syncthreads();
+    for (int64_t n = tid; n < n_frames; n += 256) {
+        float v = 0.f;
+        if (n >= start_frame) {
+            const double x = (double)(n - start_frame) * hop / (double)sr / 0.005;
+            int64_t idx = (int64_t)rint(x);
+            idx = idx < Fr - 1 ? idx : Fr - 1;
+            v = pl[idx];
+        }
+        o[n] = v;
+    }
+    if (!uv_interp) return;
+    __syncthreads();
+    const int64_t chunk = (n_frames + 255) / 256, c0 = tid * chunk, c1 = std::min<int64_t>(n_frames, c0 + chunk);
+    int64_t fv = n_frames, lv = -1;
+    for (int64_t i = c0; i < c1; ++i)
+        if (o[i] != 0.f) {
+            if (fv == n_frames) fv = i;
+            lv = i;
+        }
+    first_v[tid] = fv;
+    last_v[tid] = lv;
+    __syncthreads();
+    int64_t prev = -1, next = n_frames, any = n_frames;
+    for (int u = 0; u < 256; ++u) {
+        if (u < tid) prev = last_v[u] > prev ? last_v[u] : prev;
+        if (u > tid) next = first_v[u] < next ? first_v[u] : next;
+        any = first_v[u] < any ? first_v[u] : any;
+    }
+    if (any < n_frames) {
+        // numpy.interp over the zero frames: runs [i, k) of zeros between voiced neighbours xl < i and xr >= k
+        int64_t i = c0;
+        while (i < c1) {
+            if (o[i] != 0.f) {
+                prev = i;
+                ++i;
+                continue;
+            }
+            int64_t k = i;
+            while (k < c1 && o[k] == 0.f) ++k;
+            const int64_t xr = k < c1 ? k : next, xl = prev;
+            for (int64_t x = i; x < k; ++x) {
+                double r;
+                if (xl < 0) {
+                    r = (double)o[xr];
+                } else if (xr >= n_frames) {
+                    r = (double)o[xl];
+                } else {
+                    const double yl = (double)o[xl], yr = (double)o[xr];
+                    const double slope = (yr - yl) / ((double)xr - (double)xl);
+                    r = slope * ((double)x - (double)xl) + yl;
+                }
+                o[x] = (float)r;
+            }
+            i = k;
+        }
+    }
+    __syncthreads();
+    for (int64_t x = c0; x < c1; ++x)
+        if (o[x] < f0_min) o[x] = f0_min;
+}
+
+// ---- network -------------------------------------------------------------------------------------------------
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Dims {
+    int cin[6], cout[6], pos[6];   // input channels, output channels, output positions per frame (before the pool)
+    int feat;                      // classifier inputs
+};
+
+Dims dims_of(const ddsp_crepe_weights& w) {
+    Dims d;
+    for (int l = 0; l < 6; ++l) {
+        d.cout[l] = w.width[l];
+        d.cin[l] = l ? w.width[l - 1] : 1;
+        d.pos[l] = C1_POS >> l;
+    }
+    d.feat = 4 * w.width[5];
+    return d;
+}
+
+size_t prep_floats(const Dims& d, size_t (&off)[13]) {
+    // wpk[1..5], scale[0..5], shift[0..5]
+    size_t o = 0;
+    for (int l = 1; l < 6; ++l) {
+        off[l - 1] = o;
+        o += align256((size_t)d.cout[l] * d.cin[l] * TAPS * 4) / 4;
+    }
+    for (int l = 0; l < 6; ++l) {
+        off[5 + l] = o;
+        o += 2 * (align256((size_t)d.cout[l] * 4) / 4);
+    }
+    off[11] = o;
+    return o;
+}
+
+int prepare(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights& w, const Dims& d, float* base) {
+    size_t off[13];
+    prep_floats(d, off);
+    PrepArgs a;
+    int64_t e = 0;
+    for (int l = 0; l < 6; ++l) {
+        a.w[l] = w.conv_w[l];
+        a.bn_w[l] = w.bn_w[l];
+        a.bn_b[l] = w.bn_b[l];
+        a.bn_mean[l] = w.bn_mean[l];
+        a.bn_var[l] = w.bn_var[l];
+        a.cin[l] = d.cin[l];
+        a.cout[l] = d.cout[l];
+        a.wpk[l] = l ? base + off[l - 1] : nullptr;
+        a.scale[l] = base + off[5 + l];
+        a.shift[l] = base + off[5 + l] + align256((size_t)d.cout[l] * 4) / 4;
+    }
+    for (int l = 1; l < 6; ++l) a.end[l - 1] = (e += (int64_t)d.cout[l] * d.cin[l] * TAPS);
+    for (int l = 0; l < 6; ++l) a.end[5 + l] = (e += d.cout[l]);
+    a.end[11] = e;
+    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(e, 256), 8192)), dim3(256), 0, st, a);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+bool weights_complete(const ddsp_crepe_weights& w) {
+    const float* const* p = (const float* const*)&w;
+    const size_t n = offsetof(ddsp_crepe_weights, width) / sizeof(const float*);
+    for (size_t i = 0; i < n; ++i)
+        if (!p[i] || ((uintptr_t)p[i] % 16) != 0) return false;
+    for (int l = 0; l < 6; ++l)
+        if (w.width[l] < 16 || w.width[l] % 16 || w.width[l] > 4096) return false;
+    return true;
+}
+
+// implicit-im2col conv of one layer (l >= 1) with the pooling epilogue: tile by the launch size; Cin % 32 == 0 -> LDS-DMA
+template <class Epi>
+void conv_gemm(hipStream_t st, gemm::Args g, const Epi& e) {
+    auto blocks = [&](int bm, int bn) { return (int64_t)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn); };
+    if (g.Cin % 32 == 0 && g.zeros) {
+        if (g.N % 128 == 0 && blocks(128, 128) >= 256)
+            gemm::dma_go<128, 128, Epi, 2, 8, gemm::A_CONVK>(st, g, 1, e);
+        else if (blocks(128, 64) >= 256)
+            gemm::dma_go<128, 64, Epi, 3, 8, gemm::A_CONVK>(st, g, 1, e);
+        else
+            gemm::dma_go<64, 64, Epi, 3, 4, gemm::A_CONVK>(st, g, 1, e);
+    } else if (blocks(128, 64) >= 512) {
+        gemm::launch_tile<128, 64, true, true, gemm::A_CONVK, Epi, 8>(st, g, 1, e);
+    } else {
+        gemm::launch_tile<64, 64, true, true, gemm::A_CONVK, Epi, 4>(st, g, 1, e);
+    }
+}
+
+int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const float* audio, int64_t B, int64_t T, int hop,
+              float* probs) {
+    DDSP_REQUIRE(ctx, ctx && wp && audio && probs, "ddsp_crepe_activations: null argument");
+    DDSP_REQUIRE(ctx, weights_complete(*wp), "ddsp_crepe_activations: a weight pointer is null or not 16-byte aligned, or a width is not a multiple of 16");
+    DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && hop >= 1, "ddsp_crepe_activations: bad shape");
+    const int64_t Fr = 1 + T / hop;
+    DDSP_REQUIRE(ctx, B * Fr < ((int64_t)1 << 31) / BINS && (Fr - 1) * (int64_t)hop < ((int64_t)1 << 40), "ddsp_crepe_activations: input too long");
+    const ddsp_crepe_weights w = *wp;
+    const Dims d = dims_of(w);
+    DDSP_ENTER_DEVICE(ctx);
+    const int math = ctx->math == DDSP_MATH_FP32 ? 0 : 3;
+    const float* zeros = nullptr;
+    int rc = ddsp_zero_page(ctx, &zeros);
+    if (rc) return rc;
+
+    size_t off[13];
+    const size_t pfl = prep_floats(d, off);
+    ddsp_weight_slot* slot;
+    rc = ddsp_weight_slot_take(ctx, st, ctx->crepe_slot, &w, offsetof(ddsp_crepe_weights, version), w.version, pfl * 4, &slot);
+    if (rc) return rc;
+    float* prep = nullptr;
+    if (slot) {
+        prep = (float*)slot->dev;
+        if (!(slot->state & 1)) {
+            if ((rc = prepare(ctx, st, w, d, prep))) return rc;
+            slot->state = 1;
+        }
+    }
+    // arena: [prepared weights (when not cached)] [ping: frames / conv2 / conv4 / conv6 outputs] [pong: conv1 / conv3 / conv5]
+    const int64_t zc_max = std::min<int64_t>(B * Fr, NET_CHUNK);
+    size_t ping = (size_t)zc_max * FRAME_LD, pong = 0;
+    for (int l = 0; l < 6; ++l) {
+        const size_t sz = (size_t)zc_max * (d.pos[l] / 2) * d.cout[l];
+        if (l & 1) ping = std::max(ping, sz); else pong = std::max(pong, sz);
+    }
+    const size_t total = align256(pfl * 4) + align256(ping * 4) + align256(pong * 4);
+    // (the arena always has room for the prepared weights: a capture after cached warm-up calls must not have to grow it)
+    if ((rc = ddsp_scratch_reserve_bytes(ctx, total + 4096))) return rc;
+    ddsp_scratch_reset(ctx);
+    void* arena = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, total, &arena))) return rc;
+    char* a = (char*)arena;
+    if (!prep) {
+        prep = (float*)a;
+        if ((rc = prepare(ctx, st, w, d, prep))) return rc;
+    }
+    float* P = (float*)(a + align256(pfl * 4));
+    float* Q = (float*)(a + align256(pfl * 4) + align256(ping * 4));
+    auto scale_of = [&](int l) { return prep + off[5 + l]; };
+    auto shift_of = [&](int l) { return prep + off[5 + l] + align256((size_t)d.cout[l] * 4) / 4; };
+
+    for (int64_t z0 = 0; z0 < B * Fr; z0 += NET_CHUNK) {
+        const int zc = (int)std::min<int64_t>(B * Fr - z0, NET_CHUNK);
+        hipLaunchKernelGGL(frame_kernel, dim3((unsigned)zc), dim3(256), 0, st, audio, T, Fr, hop, z0, P);
+        {   // conv1: batched over the frames, rows 4 floats apart
+            gemm::Args g = gemm::make(P, C1_STRIDE, w.conv_w[0], C1_TAPS, C1_POS, d.cout[0], C1_TAPS);
+            g.sA_hi = FRAME_LD;
+            g.math = math;
+            EpiPool e{Q, d.cout[0], (int64_t)(C1_POS / 2) * d.cout[0], w.conv_b[0], scale_of(0), shift_of(0)};
+            if (d.cout[0] % 128 == 0)
+                gemm::dma_go<128, 128, EpiPool, 2>(st, g, zc, e);
+            else
+                gemm::dma_go<64, 64, EpiPool, 3, 4>(st, g, zc, e);
+        }
+        float* x = Q;
+        float* y = P;
+        for (int l = 1; l < 6; ++l) {
+            const int Fin = d.pos[l - 1] / 2;   // positions per frame of this layer's input (= its output before the pool)
+            gemm::Args g = gemm::make(x, d.cin[l], prep + off[l - 1], (int64_t)TAPS * d.cin[l], zc * Fin, d.cout[l], TAPS * d.cin[l]);
+            g.Fr = Fin;
+            g.Cin = d.cin[l];
+            g.ktaps = TAPS;
+            g.dil = 1;
+            g.zeros = zeros;
+            g.math = math;
+            EpiPool e{y, d.cout[l], 0, w.conv_b[l], scale_of(l), shift_of(l)};
+            conv_gemm(st, g, e);
+            std::swap(x, y);
+        }
+        // classifier over (position, channel) features: rows of 4 * W5 floats
+        {
+            gemm::Args g = gemm::make(x, d.feat, w.cls_w, d.feat, zc, BINS, d.feat);
+            g.math = math;
+            gemm::launch<true, true, gemm::A_PLAIN>(st, g, 1, gemm::EpiStore{probs + z0 * BINS, BINS, w.cls_b, 1, 0, 0});
+            const int64_t n = (int64_t)zc * BINS;
+            hipLaunchKernelGGL(sigmoid_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, probs + z0 * BINS, n);
+        }
+    }
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+// torchcrepe.convert.frequency_to_bins in fp32, then Python's slice rules for [:minidx] / [maxidx:] over 360 bins
+int bin_of(float f, bool ceil_) {
+    const float c = 1200.f * log2f(f / 10.f);
+    const float x = (c - CENTS0) / 20.f;
+    return (int)(ceil_ ? ceilf(x) : floorf(x));
+}
+int slice_pos(int k) { return k < 0 ? std::max(BINS + k, 0) : std::min(k, BINS); }
+
+}  // namespace
+
+extern "C" int64_t ddsp_crepe_frames(int64_t T16, int hop) {
+    if (T16 < 0 || hop < 1) return -1;
+    return 1 + T16 / hop;
+}
+
+extern "C" int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16, int64_t B,
+                                      int64_t T, int hop, float* probs) {
+    return crepe_run(ctx, (hipStream_t)stream, w, audio16, B, T, hop, probs);
+}
+
+extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
+                                 int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity,
+                                 int32_t* bins) {
+    DDSP_REQUIRE(ctx, ctx && probs && f0 && periodicity, "ddsp_crepe_decode: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && Fr >= 1 && B * Fr < ((int64_t)1 << 31) / BINS, "ddsp_crepe_decode: bad shape");
+    DDSP_REQUIRE(ctx, fmin > 0.f && fmax > 0.f && isfinite(fmin) && isfinite(fmax), "ddsp_crepe_decode: fmin, fmax > 0");
+    DDSP_REQUIRE(ctx, segment >= 0, "ddsp_crepe_decode: segment >= 0");
+    const int64_t seg = segment == 0 ? Fr : std::min<int64_t>(segment, Fr);
+    DDSP_REQUIRE(ctx, seg <= 1024, "ddsp_crepe_decode: segments of at most 1024 frames");
+    const int lo = slice_pos(bin_of(fmin, false)), hi = slice_pos(bin_of(fmax, true));
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    const size_t rows = (size_t)B * Fr;
+    const size_t total = align256(rows * BINS * 4) + align256(rows * BINS * 2);
+    int rc = ddsp_scratch_reserve_bytes(ctx, total + 4096);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    void* arena = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, total, &arena))) return rc;
+    float* logp = (float*)arena;
+    uint16_t* ptr = (uint16_t*)((char*)arena + align256(rows * BINS * 4));
+    hipLaunchKernelGGL(emission_kernel, dim3((unsigned)ceil_div64((int64_t)rows, 4)), dim3(256), 0, st, probs, (int64_t)rows, lo, hi, logp);
+    hipLaunchKernelGGL(viterbi_kernel, dim3((unsigned)ceil_div64(Fr, seg), (unsigned)B), dim3(VT), 0, st, logp, probs, Fr, seg, lo, hi,
+                       ptr, dither_seed, use_dither ? 1 : 0, f0, periodicity, bins);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr,
+                                  double hop, int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min,
+                                  float* out) {
+    DDSP_REQUIRE(ctx, ctx && f0 && pd && out, "ddsp_f0_postfilter: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && B < 65536 && Fr >= 3, "ddsp_f0_postfilter: B >= 1 and at least 3 frames (the reflect padding)");
+    DDSP_REQUIRE(ctx, sr > 0 && hop > 0.0 && isfinite(hop), "ddsp_f0_postfilter: sr, hop > 0");
+    DDSP_REQUIRE(ctx, n_frames >= 1 && start_frame >= 0 && start_frame <= n_frames, "ddsp_f0_postfilter: bad frame counts");
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    const size_t total = align256((size_t)B * Fr * 4);
+    int rc = ddsp_scratch_reserve_bytes(ctx, total + 4096);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    void* arena = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, total, &arena))) return rc;
+    hipLaunchKernelGGL(postfilter_kernel, dim3((unsigned)B), dim3(256), 0, st, f0, pd, Fr, sr, hop, n_frames, start_frame, threshold,
+                       uv_interp ? 1 : 0, f0_min, (float*)arena, out);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}

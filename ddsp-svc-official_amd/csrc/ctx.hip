@@ -3,7 +3,7 @@
 
 #include <stdlib.h>
 
-#define DDSP_ABI_VERSION 6   // 2: ddsp_rss_loss takes the hops; 3: ddsp_conv1d / ddsp_nsf_mean emit activated (split) copies, kept-activation entry points; 4: ddsp_retime_f0; 5: ddsp_u2c_weights::version (prepared-weight cache); 6: ddsp_hubert_weights
+#define DDSP_ABI_VERSION 7   // 2: ddsp_rss_loss takes the hops; 3: ddsp_conv1d / ddsp_nsf_mean emit activated (split) copies, kept-activation entry points; 4: ddsp_retime_f0; 5: ddsp_u2c_weights::version (prepared-weight cache); 6: ddsp_hubert_weights; 7: ddsp_crepe_weights
 
 extern "C" int ddsp_abi_version(void) { return DDSP_ABI_VERSION; }
 
@@ -36,6 +36,7 @@ extern "C" int ddsp_ctx_destroy(ddsp_ctx* ctx) {
     if (ctx->zero_page) (void)hipFree(ctx->zero_page);
     if (ctx->u2c_slot.dev) (void)hipFree(ctx->u2c_slot.dev);
     if (ctx->hubert_slot.dev) (void)hipFree(ctx->hubert_slot.dev);
+    if (ctx->crepe_slot.dev) (void)hipFree(ctx->crepe_slot.dev);
     if (ctx->dev_error_host) (void)hipHostFree(ctx->dev_error_host);
     if (ctx->prof) {
         for (int i = 0; i < ctx->prof_events_made; ++i) {

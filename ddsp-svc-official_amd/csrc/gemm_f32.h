@@ -12,9 +12,12 @@
 //                 m + (t - (ktaps-1)/2)*dil): the dilated convolutions of the NSF-HiFiGAN generator.  The register-staged
 //                 kernel can apply a leaky-ReLU (slope `in_slope`) to A as it is loaded; the LDS-DMA kernel (Cin % 32 == 0,
 //                 in_slope == 1, `zeros` set) cannot - its callers feed it activated inputs.
-//   A_MODE = A_FRAMES: rows are non-overlapping length-lda frames of B signals: row m lives at
-//                 A[(m / Fr)*sA_hi + (m % Fr)*lda] (Fr frames per signal, signals sA_hi apart) - the STFT framing of
-//                 the spectral loss without a copy.
+//   A_MODE = A_FRAMES: rows are length-K frames of B signals: row m lives at A[(m / Fr)*sA_hi + (m % Fr)*lda] (Fr frames
+//                 per signal, signals sA_hi apart) - the STFT framing of the spectral loss without a copy.  Frames may
+//                 overlap (lda < K): the loaders read A(m, k) for k < K only.  The LDS-DMA kernel has no such mode; its
+//                 callers batch over the signals instead (z = signal, sA_hi apart, A_PLAIN rows lda apart), which is the
+//                 same addressing - the DMA also reads only A(m, k), k < K, of rows clamped to M - 1 (crepe.hip conv1:
+//                 lda = 4, K = 512).
 //   B_KC = true : B(k,n) = B[n*ldb + k]   (weights stored [N][K] like nn.Linear)
 //   B_KC = false: B(k,n) = B[k*ldb + n]   (stored K x N)
 //
@@ -102,6 +105,14 @@ template <class E, class = void>
 struct epi_is_gated : std::false_type {};
 template <class E>
 struct epi_is_gated<E, std::void_t<decltype(E::kGatedPair)>> : std::true_type {};
+
+// An epilogue that declares `kRowPair` is called once per pair of rows (m, m + 1), m even, as epi.pair(z, m, n, v_m, v_m+1, cb):
+// rows 2p and 2p + 1 of the 32x32 MFMA C map sit in the same lane (accumulator registers r and r + 1), so a max-pool over row
+// pairs needs no data exchange.  The caller keeps M even (a pair never straddles the edge).
+template <class E, class = void>
+struct epi_is_rowpair : std::false_type {};
+template <class E>
+struct epi_is_rowpair<E, std::void_t<decltype(E::kRowPair)>> : std::true_type {};
 
 // 4x4 transpose across the four lanes of a quad: in x[i] = (row i, column q) for lane q; out x[k] = (row q, column k)
 __device__ __forceinline__ void quad_transpose(float (&x)[4], int q) {
@@ -347,7 +358,9 @@ __global__ void __launch_bounds__(64 * NW) kernel(Args g, Epi epi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if constexpr (epi_wants_pair<Epi>::value) {
+                if constexpr (epi_is_rowpair<Epi>::value) {
+                    if ((r & 1) == 0 && n_ok && m < g.M) epi.pair(z, m, n, acc[i][j][r], acc[i][j][r + 1], cb);
+                } else if constexpr (epi_wants_pair<Epi>::value) {
                     // columns (2f, 2f+1) sit on adjacent lanes: hand each lane its neighbour's value too
                     const float other = __shfl_xor(acc[i][j][r], 1, 64);
                     if (n_ok && m < g.M) epi(z, m, n, acc[i][j][r], other);
@@ -708,7 +721,9 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if constexpr (epi_wants_pair<Epi>::value) {
+                        if constexpr (epi_is_rowpair<Epi>::value) {
+                            if ((r & 1) == 0 && n_ok && m < g.M) epi.pair(z, m, n, acc[i][j][r], acc[i][j][r + 1], cb);
+                        } else if constexpr (epi_wants_pair<Epi>::value) {
                             const float other = __shfl_xor(acc[i][j][r], 1, 64);
                             if (n_ok && m < g.M) epi(z, m, n, acc[i][j][r], other);
                         } else if constexpr ((ABLATE & 4) != 0) {

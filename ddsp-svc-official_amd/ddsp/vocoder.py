@@ -52,6 +52,96 @@ class Volume_Extractor:
         return vol.cpu().numpy() if is_np else vol
 
 
+def _find_torchcrepe_checkpoint(model="full"):
+    """`assets/<model>.pth` of an installed torchcrepe, located with importlib.util.find_spec (the package is not imported)."""
+    import importlib.util
+    try:
+        spec = importlib.util.find_spec("torchcrepe")
+    except (ImportError, ValueError):
+        spec = None
+    for d in (list(spec.submodule_search_locations or []) if spec is not None else []):
+        p = os.path.join(d, "assets", f"{model}.pth")
+        if os.path.isfile(p):
+            return p
+    raise FileNotFoundError(
+        f"F0_Extractor('crepe'): no CREPE checkpoint given and no installed torchcrepe with assets/{model}.pth was found; pass "
+        "crepe_ckpt='/path/to/full.pth' (torchcrepe's state dict) or a ddsp.crepe.Crepe module")
+
+
+class F0_Extractor:
+    """Reference `ddsp/vocoder.py:18-113` for `f0_extractor='crepe'`: resampling to 16 kHz (`ddsp_resample`,
+    lowpass_filter_width=128), the CREPE network, the Viterbi decode and the reference's post-filter, all on the device.
+
+    `extract(audio, uv_interp=False, device=None, silence_front=0)`: a numpy array (T,) returns a numpy fp32 array
+    (n_frames,) like the reference's (one synchronisation); a device tensor (T,) or (B,T) returns a device tensor (n_frames,)
+    or (B, n_frames) without a host synchronisation, so the call can be captured into a HIP graph.
+    Differences a caller can observe, all additive:
+      * keyword arguments `crepe_ckpt` (a path to torchcrepe's `full.pth` / `tiny.pth` state dict, or a `ddsp.crepe.Crepe`;
+        None looks for an installed torchcrepe's `assets/full.pth`) and `device` (default: the current HIP device);
+      * `extract(..., dither=True, seed=None)`: torchcrepe dithers the decoded pitch by a random triangular offset of up to
+        +-20 cents (a bin is 20 cents); `dither=False` makes the output deterministic, `seed` fixes the draw (default: drawn
+        from torch's generator);
+      * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError."""
+
+    def __init__(self, f0_extractor, sample_rate=44100, hop_size=512, f0_min=65, f0_max=800, *, crepe_ckpt=None, device=None):
+        if f0_extractor in ('parselmouth', 'dio', 'harvest'):
+            raise NotImplementedError(
+                f"f0 extractor '{f0_extractor}' has no device implementation (it is a CPU library): 'crepe' is the device "
+                "extractor; keep the reference's F0_Extractor for the others")
+        if f0_extractor != 'crepe':
+            raise ValueError(f" [x] Unknown f0 extractor: {f0_extractor}")
+        self.f0_extractor, self.sample_rate, self.hop_size, self.f0_min, self.f0_max = \
+            f0_extractor, sample_rate, hop_size, f0_min, f0_max
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
+            device = "cuda"
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback); got device=%r" % (device,))
+        from .crepe import Crepe
+        if isinstance(crepe_ckpt, Crepe):
+            model = crepe_ckpt
+        else:
+            path = crepe_ckpt if crepe_ckpt is not None else _find_torchcrepe_checkpoint("full")
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+            model = Crepe("tiny" if sd["conv1.weight"].shape[0] == 128 else "full")
+            model.load_state_dict(sd)
+        self.model = model.to(device).eval()
+        self.device = device
+
+    def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None):
+        """audio (T,) numpy / (T,) or (B,T) device tensor at `sample_rate` -> f0 [Hz] (n_frames,) / (B, n_frames),
+        n_frames = int(T // hop_size) + 1.  `device` is accepted for the reference's signature (the model's device is used)."""
+        import numpy as np
+        from .crepe import HOP, SAMPLE_RATE
+        is_np = isinstance(audio, np.ndarray)
+        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
+        if not x.is_cuda:
+            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
+        flat = x.dim() == 1
+        if x.dim() not in (1, 2):
+            raise ValueError("F0_Extractor.extract: audio must be (T,) or (B, T)")
+        x = x.reshape(1, -1) if flat else x
+        sr, hop = self.sample_rate, self.hop_size
+        n_frames = int(x.shape[-1] // hop) + 1
+        start_frame = int(silence_front * sr / hop)
+        real_silence_front = start_frame * hop / sr
+        x = x[:, int(np.round(real_silence_front * sr)):].contiguous().float()
+        ctx = hipddsp.context_for(x.device)
+        x16 = x if int(sr) == SAMPLE_RATE else ctx.resample(x, int(sr), SAMPLE_RATE, lowpass_filter_width=128)
+        fr = hipddsp.crepe_frames(x16.shape[-1], HOP)
+        if fr < 3:
+            raise ValueError(f"F0_Extractor('crepe'): {x16.shape[-1]} samples at 16 kHz give {fr} CREPE frames; the reference's "
+                             "reflect-padded filters need at least 3 (audio of at least 160 samples at 16 kHz)")
+        probs = self.model.activations(x16, HOP)
+        if dither and seed is None:
+            seed = _seed_from_torch()
+        f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither_seed=int(seed or 0), dither=dither)
+        out = ctx.f0_postfilter(f0, pd, sr, hop, n_frames, start_frame, 0.05, uv_interp, self.f0_min)
+        out = out[0] if flat else out
+        return out.cpu().numpy() if is_np else out
+
+
 def align_units(units, n_samples, sample_rate, hop_size, encoder_sample_rate=16000, encoder_hop_size=320):
     """Nearest-frame alignment of encoder units (B, Lu, C) to the synthesiser's frames - the tail of the reference's
     `Units_Encoder.encode` (`ddsp/vocoder.py:201-211`), for callers that keep the reference's encoders and want the

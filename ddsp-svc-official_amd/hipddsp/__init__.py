@@ -19,7 +19,7 @@ COMB_NONE, COMB_SINC, COMB_SINC_GATED = 0, 1, 2
 FIR_ALLPASS, FIR_DYNAMIC, FIR_STATIC = 0, 1, 2
 EXC_AUDIO, EXC_UNIT_NOISE, EXC_GENERATE = 0, 1, 2
 FIR_FP32, FIR_SPLIT_BF16 = 0, 3   # ddsp_ltv_fir `math` (include/ddsp_amd.h)
-ABI_VERSION = 6                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights)
+ABI_VERSION = 7                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights, CrepeWeights)
 MATH_FP32, MATH_SPLIT_BF16 = 0, 3  # ddsp_ctx_set_math
 ATTENTION_CAUSAL = 200            # ddsp_performer_attention: causal_linear_attention (pcmer.py:170-188)
 
@@ -54,6 +54,18 @@ class HubertWeights(_c.Structure):
         + [(n, _vp) for n in ("fp_norm_w", "fp_norm_b", "fp_proj_w", "fp_proj_b", "pos_b", "pos_g", "pos_v", "norm_w", "norm_b")]
         + [(f"l{i}_{n}", _vp) for i in range(12) for n in HUBERT_LAYER_FIELDS]
         + [(n, _vp) for n in ("proj_w", "proj_b")]
+        + [("version", _c.c_uint64)]     # change counter of the weight values (0: prepare the weights on every call)
+    )
+
+
+class CrepeWeights(_c.Structure):
+    """Mirror of `ddsp_crepe_weights` (include/ddsp_amd.h): device pointers into a CREPE state dict (torchcrepe's keys) and the
+    output channels of its six convolutions."""
+    _fields_ = (
+        [(f"{n}{i + 1}_{s}", _vp) for n, s in (("conv", "w"), ("conv", "b"), ("bn", "w"), ("bn", "b"), ("bn", "mean"),
+                                                 ("bn", "var")) for i in range(6)]
+        + [("cls_w", _vp), ("cls_b", _vp)]
+        + [("width", _int * 6)]
         + [("version", _c.c_uint64)]     # change counter of the weight values (0: prepare the weights on every call)
     )
 
@@ -184,6 +196,10 @@ SIGNATURES = {
     "ddsp_hubert_soft_units": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp]),
     "ddsp_hubert_encode": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _int, _vp]),
     "ddsp_softmax_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int]),
+    "ddsp_crepe_frames": (_i64, [_i64, _int]),
+    "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _int, _vp]),
+    "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
+    "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _f64, _i64, _i64, _f32, _int, _f32, _vp]),
     "ddsp_profile_begin": (_int, [_vp, _u64]),
     "ddsp_profile_mask": (_int, [_vp, _u64]),
     "ddsp_profile_end": (_int, [_vp, _c.POINTER(ProfEntry), _int, _c.POINTER(_int)]),
@@ -703,6 +719,45 @@ class Context:
             self.call("ddsp_hubert_encode", ctypes.byref(weights), _ptr(wav), int(B), int(T), int(layer), _ptr(out))
         return out
 
+    # -- f0 extractor (CREPE) --------------------------------------------------------------------
+    def crepe_activations(self, weights, audio16, hop=80):
+        """weights: a CrepeWeights struct; audio16 (B,T) 16 kHz fp32 -> sigmoid activations (B, 1 + T // hop, 360)."""
+        B, T = audio16.shape
+        Fr = crepe_frames(T, hop)
+        x = audio16.contiguous().float()
+        out = torch.empty(B, Fr, 360, device=x.device, dtype=torch.float32)
+        if B:
+            self.call("ddsp_crepe_activations", ctypes.byref(weights), _ptr(x), int(B), int(T), int(hop), _ptr(out))
+        return out
+
+    def crepe_decode(self, probs, fmin, fmax, segment=512, dither_seed=0, dither=False, want_bins=False):
+        """probs (B, Fr, 360) -> (f0 (B, Fr), periodicity (B, Fr)[, bins (B, Fr) int32]): the range mask, the Viterbi decode
+        in independent pieces of `segment` frames (0: whole track), bins to Hz with the optional triangular dither."""
+        p = probs.contiguous().float()
+        B, Fr, _ = p.shape
+        f0 = torch.empty(B, Fr, device=p.device, dtype=torch.float32)
+        pd = torch.empty_like(f0)
+        bins = torch.empty(B, Fr, device=p.device, dtype=torch.int32) if want_bins else None
+        if B and Fr:
+            self.call("ddsp_crepe_decode", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
+                      int(dither_seed) & ((1 << 64) - 1), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
+        return (f0, pd, bins) if want_bins else (f0, pd)
+
+    def f0_postfilter(self, f0, pd, sr, hop, n_frames, start_frame=0, threshold=0.05, uv_interp=False, f0_min=65.0):
+        """f0, pd (B, Fr) at the CREPE rate -> (B, n_frames): the reference's median / threshold / masked-average filter,
+        re-timed to frames of `hop` samples at `sr` (a float hop keeps its fraction), `start_frame` zeros in front, and
+        with uv_interp the numpy.interp fill of the zero frames and the clamp to f0_min (ddsp/vocoder.py:96-113)."""
+        f0 = f0.contiguous().float()
+        pd = pd.contiguous().float()
+        B, Fr = f0.shape
+        if pd.shape != f0.shape:
+            raise ValueError("f0_postfilter: f0 and pd must have the same shape")
+        out = torch.empty(B, int(n_frames), device=f0.device, dtype=torch.float32)
+        if B:
+            self.call("ddsp_f0_postfilter", _ptr(f0), _ptr(pd), int(B), int(Fr), int(sr), float(hop), int(n_frames),
+                      int(start_frame), float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
+        return out
+
     # -- a10 -----------------------------------------------------------------------------------
     def sins_bank(self, ctrl2d, col0, n_harmonics, f0_frames, phase, B, Fr, hop, sr):
         out = torch.empty(B, Fr * hop, device=ctrl2d.device, dtype=torch.float32)
@@ -793,6 +848,14 @@ _override = threading.local()
 def hubert_frames(T):
     """Encoder frames of T samples (`ddsp_hubert_frames`, a host computation): 0 when the audio is too short."""
     return int(load_library().ddsp_hubert_frames(int(T)))
+
+
+def crepe_frames(T16, hop=80):
+    """CREPE frames of T16 samples at 16 kHz with pad=True (`ddsp_crepe_frames`, a host computation): 1 + T16 // hop."""
+    n = int(load_library().ddsp_crepe_frames(int(T16), int(hop)))
+    if n < 0:
+        raise ValueError(f"crepe_frames: bad length {T16} or hop {hop}")
+    return n
 
 
 class use_context:

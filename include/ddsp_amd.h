@@ -432,6 +432,51 @@ int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w
 int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B, int64_t L,
                            int heads, float* out, int math);
 
+/* ---- the f0 extractor (CREPE, ddsp/vocoder.py:39-113 with torchcrepe.predict and librosa's Viterbi restated) ---------- */
+/* Device pointers into a CREPE state dict (torchcrepe's keys), fp32, dense: conv_w[i] = `conv{i+1}.weight` (Cout, Cin, k, 1),
+ * conv_b[i] = `conv{i+1}.bias`, bn_*[i] = `conv{i+1}_BN.{weight,bias,running_mean,running_var}`, cls_w / cls_b =
+ * `classifier.{weight,bias}` (360, 4 * width[5]).  width = output channels of conv1..conv6: {1024, 128, 128, 128, 256, 512}
+ * for 'full', every one / 8 for 'tiny' (each a multiple of 16).  `version`: as ddsp_hubert_weights::version (the prepared
+ * copies - repacked convolutions, batch norms folded into a scale and shift - are kept in the context while it and the
+ * struct's other bytes stand; 0 = prepare on every call). */
+typedef struct ddsp_crepe_weights {
+    const float* conv_w[6];
+    const float* conv_b[6];
+    const float* bn_w[6];
+    const float* bn_b[6];
+    const float* bn_mean[6];
+    const float* bn_var[6];
+    const float *cls_w, *cls_b;
+    int width[6];
+    uint64_t version;
+} ddsp_crepe_weights;
+
+/* CREPE frames of T16 samples at 16 kHz with pad=True: 1 + T16 / hop; -1 for T16 < 0 or hop < 1.  Host only. */
+int64_t ddsp_crepe_frames(int64_t T16, int hop);
+/* torchcrepe.infer over the frames of torchcrepe.preprocess(pad=True): audio16 (B,T) 16 kHz -> probs (B, Fr, 360) sigmoid
+ * activations, Fr = ddsp_crepe_frames(T, hop).  Each 1024-sample frame (zero padding of 512 on each side of the audio) is
+ * normalised by its mean and unbiased standard deviation (fp64 statistics, divisor max(1e-10, std)).  The convolutions and
+ * the classifier are GEMMs in the context's product arithmetic; ReLU, batch norm and the 2x1 max-pool are their epilogue.
+ * No host synchronisation once the scratch arena (and the prepared-weight slot) exist. */
+int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16, int64_t B, int64_t T,
+                           int hop, float* probs);
+/* torchcrepe.postprocess with the Viterbi decoder: bins [:minidx] and [maxidx:] of probs (B, Fr, 360) masked (minidx =
+ * floor, maxidx = ceil of (1200 log2(f / 10) - 1997.3794084376191) / 20 in fp32, Python slice rules), emissions
+ * log(softmax + fp32 tiny), transitions log(max(12 - |i - j|, 0) / row sum + tiny), uniform start, fp64 values, first index
+ * on ties (librosa.sequence.viterbi).  The track is decoded in independent pieces of `segment` frames (torchcrepe.predict
+ * decodes each batch of `batch_size` frames on its own; 0 = the whole track).  Outputs (B, Fr): f0 = 10 * 2^(cents / 1200),
+ * cents = 20 * bin + 1997.3794084376191 (+ a triangular dither on (-20, 20) cents drawn from a counter hash of
+ * `dither_seed` when use_dither != 0); periodicity = the masked activation at the chosen bin; bins (int32, may be null). */
+int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
+                      int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity, int32_t* bins);
+/* The crepe tail of F0_Extractor.extract (ddsp/vocoder.py:96-113): f0, pd (B, Fr) -> out (B, n_frames): MedianPool1d(pd, 4),
+ * f0 = NaN where that is < threshold, MaskedAvgPool1d(f0, 4) (reflect padding (1, 2), Fr >= 3), the re-timing
+ * out[start_frame + n] = f0[min(rint(n * hop / sr / 0.005), Fr - 1)] for n < n_frames - start_frame (fp64 index arithmetic,
+ * hop may be fractional), zeros before start_frame, then with uv_interp != 0 numpy.interp over the zero frames (fp64, when
+ * any frame is non-zero) and out = max(out, f0_min). */
+int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr, double hop,
+                       int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min, float* out);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream --------------------- */
 /* ddsp_profile_begin arms the families in `family_mask` (bit i = family i, see the name returned); while armed,
  * each kernel launch of such a family is bracketed by hipEventRecord on the caller's stream.  ddsp_profile_end
