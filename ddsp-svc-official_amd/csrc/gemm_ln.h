@@ -78,7 +78,7 @@ constexpr size_t LN_LDS_BYTES = (size_t)LN_NS * LN_STAGE * sizeof(float);
 // NS ring stages; RB row blocks of 32 per wave: 1 = 16 waves (2 x 8 grid), 2 = 8 waves (each both row blocks); ASPLIT: A arrives in
 // the pre-split layout (else fp32 rows, split into bf16 hi / lo per fragment in the loop like kernel_dma's mode 7: the same bits)
 // A_MODE: A_PLAIN or A_CONV3 (the loader moves an A row's source by the tap's frame offset, or to the zero page); Pre: what joins the
-// product before the LayerNorm (PreResidual; unit2ctrl.hip's PreEmbed for the second prenet convolution)
+// product before the LayerNorm (PreResidual; unit2ctrl_fwd.hip's PreEmbed for the second prenet convolution)
 template <int NS, int RB, bool ASPLIT, int A_MODE, class Pre>
 __global__ void __launch_bounds__(1024 / RB) kernel_res_ln(LnArgs g, Pre pre) {
     extern __shared__ __attribute__((aligned(1024))) float ln_lds[];

@@ -2,7 +2,7 @@
 // feature-map round trip through HBM.
 //
 // Replaces, for inference, the chain  [k P^T GEMM -> exp pass -> key sums -> k'^T v GEMM]  and
-// [q P^T GEMM -> max/exp pass -> 1/D pass -> q' ctx GEMM]  of ddsp/pcmer.py:69-77,123-159 (unit2ctrl.hip keeps
+// [q P^T GEMM -> max/exp pass -> 1/D pass -> q' ctx GEMM]  of ddsp/pcmer.py:69-77,123-159 (unit2ctrl_fwd.hip keeps
 // the unfused chain for training, whose backward needs q' and k').  The 94 MB q'/k' matrices per layer never
 // exist: a 16 x 16 tile of projected values lives in the MFMA accumulator (4 registers), is exponentiated in place
 // and is fed straight back as the next product's operand - accumulator register t of lane group g is the index

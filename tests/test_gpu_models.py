@@ -28,7 +28,7 @@ def _to(d, dev):
 
 
 def test_unit2ctrl_large_batch_fused_glu_matches_oracle(dev, lib_path):
-    """Inference forms the conformer's GLU inside the pw1 GEMM (gated-pair epilogue on re-ordered weights, unit2ctrl.hip):
+    """Inference forms the conformer's GLU inside the pw1 GEMM (gated-pair epilogue on re-ordered weights, unit2ctrl_fwd.hip):
     from 8065 rows on with 128x128 tiles (and pre-split activations), below with 64x128 tiles.  B*Fr = 8256 rows against
     the oracle at the same tolerances as the small cases, plus a check (launch counts of the row-kernel family) that the
     fused path is the one that ran at both sizes."""
