@@ -139,9 +139,13 @@ int ddsp_scratch_get(ddsp_ctx* ctx, size_t bytes, void** out);
 int ddsp_scratch_reserve_bytes(ddsp_ctx* ctx, size_t bytes);
 // prepared-weight slot (ctx.hip): *out = `slot`, grown to `bytes`, for a call whose weight struct `w` has the change counter
 // `version` (`key_bytes`: the struct's bytes before that counter); null - prepare into scratch - when version == 0 or the
-// stream is being captured (a graph replay must prepare the weights of ITS time)
+// stream is being captured (a graph replay must prepare the weights of ITS time: the control network, whose weights a
+// training loop updates in place under a captured validation forward).  `keep_in_capture` (the inference-only analysis
+// networks, 95 M and 22 M parameters): a captured call gets the slot when eager warm-up calls on this context already
+// prepared exactly these weights in it - the graph then reads the copies of its capture time and does not repeat the
+// preparation on every replay; a change of those weights needs a new capture.
 int ddsp_weight_slot_take(ddsp_ctx* ctx, hipStream_t st, ddsp_weight_slot& slot, const void* w, size_t key_bytes,
-                          uint64_t version, size_t bytes, ddsp_weight_slot** out);
+                          uint64_t version, size_t bytes, ddsp_weight_slot** out, bool keep_in_capture = false);
 // tables (tables.hip)
 int ddsp_get_table(ddsp_ctx* ctx, hipStream_t st, int kind, int n0, int n1, float** out);
 // device pointer to DDSP_ZERO_FLOATS zeros (allocated on first use; a first-use synchronisation like the tables)

@@ -199,14 +199,23 @@ __device__ __forceinline__ void argmax_merge(double& v, int& i, double v2, int i
     }
 }
 
+// The dither seed of ddsp_crepe_decode_dseed moves to its successor (one 64-bit LCG step, Knuth's MMIX constants: full
+// period, both 32-bit halves change from call to call).  One thread, enqueued behind the decode that read the word.
+__global__ void seed_advance_kernel(uint64_t* __restrict__ seed) {
+    *seed = *seed * 6364136223846793005ull + 1442695040888963407ull;
+}
+
 // grid (segments, B).  Frames [t0, t1) of utterance b, decoded on their own from a uniform start:
 //   value[t][j] = logp[t][j] + max_i(value[t-1][i] + logT[i][j])  (fp64, first i on ties)
 // computed exactly from the 23 in-band candidates and the out-of-band term value[t-1][g] + log(tiny), g = the first global
 // argmax of value[t-1]: every in-band logT exceeds log(tiny), so an out-of-band i beats the band only if it is g.
 __global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ logp, const float* __restrict__ probs, int64_t Fr,
-                                                     int64_t seg, int lo, int hi, uint16_t* __restrict__ ptr, uint64_t seed,
-                                                     int dither, float* __restrict__ f0, float* __restrict__ pd,
+                                                     int64_t seg, int lo, int hi, uint16_t* __restrict__ ptr, uint64_t seed_arg,
+                                                     const uint64_t* __restrict__ seed_dev, int dither,
+                                                     float* __restrict__ f0, float* __restrict__ pd,
                                                      int32_t* __restrict__ bins_out) {
+    // the dither seed: the argument, or (ddsp_crepe_decode_dseed) the device word a captured graph re-reads on every replay
+    const uint64_t seed = seed_dev ? *seed_dev : seed_arg;
     __shared__ double band[BINS * BAND];        // logT[j + d - 11][j] at [j * 23 + d]; reused for back-pointer rows
     __shared__ double val[2][BINS];
     __shared__ double rv[2][8];
@@ -557,7 +566,7 @@ int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const
     size_t off[13];
     const size_t pfl = prep_floats(d, off);
     ddsp_weight_slot* slot;
-    rc = ddsp_weight_slot_take(ctx, st, ctx->crepe_slot, &w, offsetof(ddsp_crepe_weights, version), w.version, pfl * 4, &slot);
+    rc = ddsp_weight_slot_take(ctx, st, ctx->crepe_slot, &w, offsetof(ddsp_crepe_weights, version), w.version, pfl * 4, &slot, true);
     if (rc) return rc;
     float* prep = nullptr;
     if (slot) {
@@ -651,9 +660,9 @@ extern "C" int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_cr
     return crepe_run(ctx, (hipStream_t)stream, w, audio16, B, T, hop, probs);
 }
 
-extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
-                                 int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity,
-                                 int32_t* bins) {
+static int crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
+                        int64_t segment, uint64_t dither_seed, uint64_t* seed_dev, int use_dither, float* f0, float* periodicity,
+                        int32_t* bins) {
     DDSP_REQUIRE(ctx, ctx && probs && f0 && periodicity, "ddsp_crepe_decode: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && Fr >= 1 && B * Fr < ((int64_t)1 << 31) / BINS, "ddsp_crepe_decode: bad shape");
     DDSP_REQUIRE(ctx, fmin > 0.f && fmax > 0.f && isfinite(fmin) && isfinite(fmax), "ddsp_crepe_decode: fmin, fmax > 0");
@@ -674,9 +683,24 @@ extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs
     uint16_t* ptr = (uint16_t*)((char*)arena + align256(rows * BINS * 4));
     hipLaunchKernelGGL(emission_kernel, dim3((unsigned)ceil_div64((int64_t)rows, 4)), dim3(256), 0, st, probs, (int64_t)rows, lo, hi, logp);
     hipLaunchKernelGGL(viterbi_kernel, dim3((unsigned)ceil_div64(Fr, seg), (unsigned)B), dim3(VT), 0, st, logp, probs, Fr, seg, lo, hi,
-                       ptr, dither_seed, use_dither ? 1 : 0, f0, periodicity, bins);
+                       ptr, dither_seed, (const uint64_t*)seed_dev, use_dither ? 1 : 0, f0, periodicity, bins);
+    // every workgroup of the decode has read the word when this one-thread kernel, next on the stream, advances it
+    if (seed_dev) hipLaunchKernelGGL(seed_advance_kernel, dim3(1), dim3(1), 0, st, seed_dev);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
+                                 int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity,
+                                 int32_t* bins) {
+    return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, dither_seed, nullptr, use_dither, f0, periodicity, bins);
+}
+
+extern "C" int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin,
+                                       float fmax, int64_t segment, uint64_t* seed_dev, int use_dither, float* f0,
+                                       float* periodicity, int32_t* bins) {
+    DDSP_REQUIRE(ctx, ctx && seed_dev && ((uintptr_t)seed_dev & 7) == 0, "ddsp_crepe_decode_dseed: seed_dev null or not 8-byte aligned");
+    return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, 0, seed_dev, use_dither, f0, periodicity, bins);
 }
 
 extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr,

@@ -81,15 +81,22 @@ int ddsp_scratch_reserve_bytes(ddsp_ctx* ctx, size_t bytes) {
 }
 
 int ddsp_weight_slot_take(ddsp_ctx* ctx, hipStream_t st, ddsp_weight_slot& slot, const void* w, size_t key_bytes,
-                          uint64_t version, size_t bytes, ddsp_weight_slot** out) {
+                          uint64_t version, size_t bytes, ddsp_weight_slot** out, bool keep_in_capture) {
     *out = nullptr;
     if (version == 0) return DDSP_OK;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return DDSP_OK;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (capturing && !keep_in_capture) return DDSP_OK;
     uint64_t key = 1469598103934665603ull;   // FNV-1a
     const unsigned char* p = (const unsigned char*)w;
     for (size_t i = 0; i < key_bytes; ++i) key = (key ^ p[i]) * 1099511628211ull;
     if (key == 0) key = 1;
+    if (capturing) {
+        // nothing is allocated, synchronised or prepared while a stream is captured: the slot is handed out only as the
+        // warm-up calls left it, for exactly these weights
+        if (slot.dev && slot.bytes >= bytes && slot.key == key && slot.version == version && slot.state) *out = &slot;
+        return DDSP_OK;
+    }
     if (slot.bytes < bytes) {
         if (slot.dev) {
             // (the stream may still read the old buffer: wait for it before it goes)

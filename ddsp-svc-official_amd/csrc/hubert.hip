@@ -481,7 +481,7 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     const float *wconv = nullptr, *wpos = nullptr;
     ddsp_weight_slot* slot;
     int rc = ddsp_weight_slot_take(ctx, st, ctx->hubert_slot, &w, offsetof(ddsp_hubert_weights, version), w.version, prep_bytes(),
-                                   &slot);
+                                   &slot, true);
     if (rc) return rc;
     const bool cached = slot != nullptr;
     if (cached) {

@@ -2,6 +2,8 @@
 // SOLA splice (gui.py:405-430, windows gui.py:349-351) and the volume gate (main.py:111-116,159 / gui.py:108-112,127).
 #include "common.h"
 
+#include <algorithm>
+
 namespace {
 
 // score[l] = sum_i x[l+i]*buf[i] / sqrt(sum_i x[l+i]^2 + 1e-8),  l = 0..search   (one workgroup per lag)
@@ -172,6 +174,14 @@ __global__ void __launch_bounds__(256) pv_synth_kernel(const float* __restrict__
     }
 }
 
+// ---- sliding input window (gui.py:373-374) ----------------------------------------------------------------------
+// dst[i] = a[i] for i < na, then b[i - na] for the next nb elements (nb may be 0); dst overlaps neither source
+__global__ void __launch_bounds__(256) concat_copy_kernel(const float* __restrict__ a, int64_t na, const float* __restrict__ b,
+                                                          int64_t nb, float* __restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < na + nb; i += (int64_t)gridDim.x * 256)
+        dst[i] = i < na ? a[i] : b[i - na];
+}
+
 }  // namespace
 
 extern "C" int ddsp_phase_vocoder(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
@@ -232,6 +242,31 @@ extern "C" int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, cons
     hipLaunchKernelGGL(volume_gate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, signal, volume, threshold, B,
                        (int)Fr, hop);
     ddsp_prof_end(ctx, st, 0.0, 8.0 * total);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int64_t n_in, const float* block_in, int64_t block) {
+    DDSP_REQUIRE(ctx, ctx && window && block_in, "ddsp_stream_push: null argument");
+    DDSP_REQUIRE(ctx, block >= 1 && block < n_in && n_in < ((int64_t)1 << 31), "ddsp_stream_push: 1 <= block < n_in < 2^31");
+    DDSP_REQUIRE(ctx, block_in + block <= window || block_in >= window + n_in, "ddsp_stream_push: block_in lies inside the window");
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    // window[:] = append(window[block:], block_in).  The shift overlaps itself, and workgroups of one launch run in no
+    // order, so the kept part goes through the arena: launch 1 copies window[block:] out, launch 2 (stream order: after every
+    // read of launch 1) writes it back to the front with the new block behind it.  No launch reads what it writes.
+    const int64_t keep = n_in - block;
+    int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)keep * sizeof(float) + 4096);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    float* stage = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, (size_t)keep * sizeof(float), (void**)&stage))) return rc;
+    const unsigned g1 = (unsigned)std::min<int64_t>(ceil_div64(keep, 256), 1024), g2 = (unsigned)std::min<int64_t>(ceil_div64(n_in, 256), 1024);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(concat_copy_kernel, dim3(g1), dim3(256), 0, st, (const float*)window + block, keep, (const float*)nullptr,
+                       (int64_t)0, stage);
+    hipLaunchKernelGGL(concat_copy_kernel, dim3(g2), dim3(256), 0, st, (const float*)stage, keep, block_in, block, window);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * (double)(keep + n_in));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

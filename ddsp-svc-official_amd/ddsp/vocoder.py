@@ -80,7 +80,8 @@ class F0_Extractor:
         None looks for an installed torchcrepe's `assets/full.pth`) and `device` (default: the current HIP device);
       * `extract(..., dither=True, seed=None)`: torchcrepe dithers the decoded pitch by a random triangular offset of up to
         +-20 cents (a bin is 20 cents); `dither=False` makes the output deterministic, `seed` fixes the draw (default: drawn
-        from torch's generator);
+        from torch's generator); `seed_dev` (a (1,) int64 device tensor) holds the seed on the device instead and is advanced
+        by every call (`ddsp_crepe_decode_dseed`), so a call captured into a HIP graph dithers anew on every replay;
       * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError."""
 
     def __init__(self, f0_extractor, sample_rate=44100, hop_size=512, f0_min=65, f0_max=800, *, crepe_ckpt=None, device=None):
@@ -109,7 +110,7 @@ class F0_Extractor:
         self.model = model.to(device).eval()
         self.device = device
 
-    def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None):
+    def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None, seed_dev=None):
         """audio (T,) numpy / (T,) or (B,T) device tensor at `sample_rate` -> f0 [Hz] (n_frames,) / (B, n_frames),
         n_frames = int(T // hop_size) + 1.  `device` is accepted for the reference's signature (the model's device is used)."""
         import numpy as np
@@ -134,9 +135,12 @@ class F0_Extractor:
             raise ValueError(f"F0_Extractor('crepe'): {x16.shape[-1]} samples at 16 kHz give {fr} CREPE frames; the reference's "
                              "reflect-padded filters need at least 3 (audio of at least 160 samples at 16 kHz)")
         probs = self.model.activations(x16, HOP)
-        if dither and seed is None:
-            seed = _seed_from_torch()
-        f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither_seed=int(seed or 0), dither=dither)
+        if seed_dev is not None:
+            f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither=dither, seed_dev=seed_dev)
+        else:
+            if dither and seed is None:
+                seed = _seed_from_torch()
+            f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither_seed=int(seed or 0), dither=dither)
         out = ctx.f0_postfilter(f0, pd, sr, hop, n_frames, start_frame, 0.05, uv_interp, self.f0_min)
         out = out[0] if flat else out
         return out.cpu().numpy() if is_np else out

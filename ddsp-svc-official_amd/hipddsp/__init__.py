@@ -199,6 +199,8 @@ SIGNATURES = {
     "ddsp_crepe_frames": (_i64, [_i64, _int]),
     "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _int, _vp]),
     "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
+    "ddsp_crepe_decode_dseed": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _vp, _int, _vp, _vp, _vp]),
+    "ddsp_stream_push": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
     "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _f64, _i64, _i64, _f32, _int, _f32, _vp]),
     "ddsp_profile_begin": (_int, [_vp, _u64]),
     "ddsp_profile_mask": (_int, [_vp, _u64]),
@@ -730,15 +732,22 @@ class Context:
             self.call("ddsp_crepe_activations", ctypes.byref(weights), _ptr(x), int(B), int(T), int(hop), _ptr(out))
         return out
 
-    def crepe_decode(self, probs, fmin, fmax, segment=512, dither_seed=0, dither=False, want_bins=False):
+    def crepe_decode(self, probs, fmin, fmax, segment=512, dither_seed=0, dither=False, want_bins=False, seed_dev=None):
         """probs (B, Fr, 360) -> (f0 (B, Fr), periodicity (B, Fr)[, bins (B, Fr) int32]): the range mask, the Viterbi decode
-        in independent pieces of `segment` frames (0: whole track), bins to Hz with the optional triangular dither."""
+        in independent pieces of `segment` frames (0: whole track), bins to Hz with the optional triangular dither.
+        `seed_dev`: a (1,) int64 device tensor that holds the dither seed instead of `dither_seed` and is advanced to
+        `next_dither_seed` of its value by the call (`ddsp_crepe_decode_dseed`: what a captured graph needs)."""
         p = probs.contiguous().float()
         B, Fr, _ = p.shape
         f0 = torch.empty(B, Fr, device=p.device, dtype=torch.float32)
         pd = torch.empty_like(f0)
         bins = torch.empty(B, Fr, device=p.device, dtype=torch.int32) if want_bins else None
-        if B and Fr:
+        if seed_dev is not None and (seed_dev.dtype != torch.int64 or seed_dev.numel() != 1 or seed_dev.device != p.device):
+            raise ValueError("crepe_decode: seed_dev must be a (1,) int64 tensor on the device of probs")
+        if B and Fr and seed_dev is not None:
+            self.call("ddsp_crepe_decode_dseed", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
+                      _ptr(seed_dev), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
+        elif B and Fr:
             self.call("ddsp_crepe_decode", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
                       int(dither_seed) & ((1 << 64) - 1), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
         return (f0, pd, bins) if want_bins else (f0, pd)
@@ -816,6 +825,14 @@ class Context:
                   _ptr(sola_buffer), _ptr(emitted), _ptr(shift))
         return emitted, shift
 
+    def stream_push_(self, window, block_in):
+        """In place: window (n_in,) = append(window[block:], block_in (block,)) (gui.py:373-374); the window keeps its
+        address (`ddsp_stream_push`)."""
+        if window.dtype != torch.float32 or block_in.dtype != torch.float32 or window.dim() != 1 or block_in.dim() != 1:
+            raise ValueError("stream_push_: window and block_in must be 1-D fp32 tensors")
+        self.call("ddsp_stream_push", _ptr(window), window.numel(), _ptr(block_in), block_in.numel())
+        return window
+
     def phase_vocoder(self, a, b, fade_out, fade_in):
         """gui.py:14-31: cross-fade of the kept tail `a` into the new head `b` (both (n,)) with a phase-interpolated
         oscillator term; returns (n,)."""
@@ -843,6 +860,11 @@ _ctx_lock = threading.Lock()
 
 
 _override = threading.local()
+
+
+def next_dither_seed(seed):
+    """The value `ddsp_crepe_decode_dseed` leaves in its seed word after a call that read `seed` (a host computation)."""
+    return (int(seed) * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
 
 
 def hubert_frames(T):

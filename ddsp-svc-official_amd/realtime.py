@@ -106,24 +106,29 @@ class StreamRenderer:
       1. the sliding input window takes the block (`input_wav[:] = append(input_wav[block:], indata)`, gui.py:373-374);
       2. frame volume of the window at hop `hop_size = block_size * samplerate / model_sr` (`Volume_Extractor.extract`,
          gui.py:94,105-106) -> `ddsp_volume_extract`, or `ddsp_volume_extract_frac` when that hop is not integral;
-      3. units / f0 of the window from the caller's analysis front end (`features(window) -> (units (1,Fr,C), f0 (1,Fr,1))`:
-         the f0 extractor and the units encoder are third-party models outside this path); f0 is
-         shifted by `pitch_adjust` semitones (gui.py:102);
+      3. f0 and units of the window (gui.py:94-102,114-116).  `push_audio` computes them on the device with this package's
+         `F0_Extractor('crepe')` (uv_interp, the silent front, bounds `f0_min` / `f0_max`, both at the device rate and the
+         window's hop) and `Units_Encoder('hubertsoft')`, given as `f0_extractor=` / `units_encoder=`; `push_block` takes them
+         from the caller instead (`units=`, `f0=`, or a `features(window) -> (units (1,Fr,C), f0 (1,Fr,1))` callable: other
+         extractors and encoders).  f0 is shifted by `pitch_adjust` semitones (gui.py:102);
       4. the synthesiser forward (gui.py:125-126) with `spk_id` or `spk_mix_dict`, eager or replayed from a HIP graph
-         (`graphed.GraphedSynth`, captured for the current mix);
+         captured for the current mix: `graphed.GraphedSynth` under `push_block`; under `push_audio` steps 1-5 are ONE graph
+         (`graphed.GraphedBlock`), replayed with one host call per block;
       5. `output *= mask` with the 9-frame dilated volume gate at the model's `block_size` (gui.py:107-112,127) ->
          `ddsp_volume_gate`, in place;
       6. optionally `enhancer.enhance(...)` (gui.py:128-134), eager, with the adaptive key decided here (see below);
       7. resampling from the model's (or enhancer's) rate to `samplerate` when they differ (gui.py:399-404);
       8. SOLA search + cross-fade + tail hand-over (gui.py:405-430) -> `Splicer.push`.
-    Without the enhancer nothing in the chain synchronises with the host; the returned (block,) tensor is what the callback
-    copies out.  With `enhancer_adaptive_key='auto'` the key (it decides tensor lengths) is taken before the synthesis is
+    Without the enhancer nothing in the chain synchronises with the host, the analysis included; the returned (block,) tensor
+    is what the callback copies out.  After a `push_audio`, `last_f0` (1, Fr, 1) (shifted), `last_units` (1, Fr, C) and
+    `last_volume` (1, Fr) hold the window's analysis (under the graph: static tensors, valid until the next block).  With `enhancer_adaptive_key='auto'` the key (it decides tensor lengths) is taken before the synthesis is
     enqueued: on the host when f0 arrives as a CPU tensor, else by one scalar read-back of the f0 maximum.
     Streams are independent: eight streams are eight renderers on eight GPUs (replicas only)."""
 
     def __init__(self, model, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0, spk_id=1,
                  features=None, use_graph=True, use_phase_vocoder=False, pitch_adjust=0, spk_mix_dict=None, enhancer=None,
-                 enhancer_adaptive_key="auto"):
+                 enhancer_adaptive_key="auto", units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100, f0_dither=True,
+                 crepe_ckpt=None):
         self.model = model.eval()
         self.device = torch.device(device)
         self.block_size = int(model.block_size)
@@ -151,17 +156,44 @@ class StreamRenderer:
         self.spk_id = torch.full((1, 1), int(spk_id), dtype=torch.int64, device=self.device)
         self.spk_mix_dict = self._checked_mix(spk_mix_dict)
         self.features = features
+        # the analysis front end of `push_audio` (gui.py:81-82,93-99: a crepe extractor with these bounds at the device rate)
+        if f0_extractor == "crepe":
+            from ddsp.vocoder import F0_Extractor
+            f0_extractor = F0_Extractor("crepe", samplerate, self.hop_size, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt,
+                                        device=self.device)
+        if (units_encoder is None) != (f0_extractor is None):
+            raise ValueError("StreamRenderer: push_audio needs both units_encoder and f0_extractor (or neither)")
+        if f0_extractor is not None:
+            if not (hasattr(f0_extractor, "extract") and hasattr(units_encoder, "encode")):
+                raise ValueError("StreamRenderer: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
+            if f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != self.hop_size:
+                raise ValueError(f"StreamRenderer: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
+                                 f"{f0_extractor.hop_size}; this renderer's window is at {samplerate} Hz with hop {self.hop_size}")
+        self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
+        self.last_f0 = self.last_units = self.last_volume = None
         self.use_graph = bool(use_graph)
-        self.graph = None
+        self.graph = None                                            # the synthesis graph of `push_block`
+        self.block_graph = None                                      # the whole-block graph of `push_audio`
         self.graph_builds = 0                                        # captures so far (a mix change re-captures)
         if self.use_graph:
             self._capture()
 
     def _capture(self):
+        """(Re-)captures for the current mix: the whole-block graph when the analysis is configured (the synthesis-only graph
+        of `push_block(units=, f0=)` is then captured on its first use), else the synthesis graph."""
         import graphed
-        self.graph = None                                            # the old capture is released before the new one
-        self.graph = graphed.GraphedSynth(self.model, 1, self.frames, spk_mix_dict=self.spk_mix_dict)
+        self.graph = self.block_graph = None                         # the old captures are released before the new one
+        if self.f0_extractor is not None:
+            self.block_graph = graphed.GraphedBlock(
+                self.model, self.units_encoder, self.f0_extractor, self.window, self.block, self.samplerate, self.hop_size,
+                self.silence_front, self._pitch_factor(), self.threshold_db, spk_mix_dict=self.spk_mix_dict,
+                f0_dither=self.f0_dither)
+        else:
+            self.graph = graphed.GraphedSynth(self.model, 1, self.frames, spk_mix_dict=self.spk_mix_dict)
         self.graph_builds += 1
+
+    def _pitch_factor(self):
+        return 2 ** (self.pitch_adjust / 12) if self.pitch_adjust != 0 else 1
 
     def _checked_mix(self, spk_mix_dict):
         if spk_mix_dict is None:
@@ -211,8 +243,13 @@ class StreamRenderer:
         replaces the fresh draw and `rand_ini` (9,) the enhancer's source phases (parity tests)."""
         if block_in.numel() != self.block:
             raise ValueError(f"StreamRenderer: a block is {self.block} samples, got {block_in.numel()}")
-        self.window = torch.cat([self.window[self.block:], block_in.reshape(-1).to(self.device, torch.float32)])
+        if (units is None or f0 is None) and self.features is None and self.f0_extractor is not None:
+            return self.push_audio(block_in, noise=noise, rand_ini=rand_ini)
         ctx = hipddsp.context_for(self.device)
+        if self.f0_extractor is None:
+            self.window = torch.cat([self.window[self.block:], block_in.reshape(-1).to(self.device, torch.float32)])
+        else:   # a whole-block graph may hold the window's address: the same shift, in place
+            ctx.stream_push_(self.window, block_in.reshape(-1).to(self.device, torch.float32).contiguous())
         if units is None or f0 is None:
             if self.features is None:
                 raise ValueError("StreamRenderer: pass units and f0, or construct it with a `features` callable")
@@ -228,6 +265,10 @@ class StreamRenderer:
         volume = ctx.volume_extract(self.window[None], self.hop_size)   # (1, Fr)
         if volume.shape[1] != self.frames:
             raise ValueError(f"StreamRenderer: the window has {self.frames} frames")
+        if self.use_graph and self.graph is None:                    # (a renderer whose captures so far were whole blocks)
+            import graphed
+            self.graph = graphed.GraphedSynth(self.model, 1, self.frames, spk_mix_dict=self.spk_mix_dict)
+            self.graph_builds += 1
         if self.graph is not None:
             sig = self.graph(units, f0, volume, self.spk_id, noise=noise)[0]
         elif noise is not None:
@@ -237,6 +278,33 @@ class StreamRenderer:
         ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
         rate = self.model_sr
         if self.enhancer is not None:
+            sig, rate = self.enhancer.enhance(sig, self.model_sr, f0, self.block_size, adaptive_key=key,
+                                              silence_front=self.silence_front, rand_ini=rand_ini)
+            self.last_key = key
+        return self.splicer.push(self._to_device_rate(sig, rate)[0])
+
+    @torch.no_grad()
+    def push_audio(self, block_in, noise=None, rand_ini=None):
+        """block_in (block,) raw samples of the stream at the device rate -> (block,) samples to play: the whole of
+        gui.py:373-430, the analysis included (class docstring, steps 1-8).  With `use_graph` steps 1-5 are one graph replay,
+        else the same calls run eagerly; `noise` and `rand_ini` as in `push_block`."""
+        if self.f0_extractor is None:
+            raise ValueError("StreamRenderer: push_audio needs units_encoder= and f0_extractor= at construction")
+        if block_in.numel() != self.block:
+            raise ValueError(f"StreamRenderer: a block is {self.block} samples, got {block_in.numel()}")
+        block_in = block_in.reshape(-1).to(self.device, torch.float32).contiguous()
+        if self.block_graph is not None:
+            sig, f0, units, volume = self.block_graph(block_in, self.spk_id, noise=noise)
+        else:
+            import graphed
+            sig, f0, units, volume = graphed.block_chain(
+                hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, self.window, block_in,
+                self.samplerate, self.hop_size, self.silence_front, self._pitch_factor(), self.threshold_db, self.hop,
+                self.spk_id, self.spk_mix_dict, noise, self.f0_dither)
+        self.last_f0, self.last_units, self.last_volume = f0, units, volume
+        rate = self.model_sr
+        if self.enhancer is not None:
+            key = self._key(f0)                                      # (one scalar read-back under 'auto': it decides lengths)
             sig, rate = self.enhancer.enhance(sig, self.model_sr, f0, self.block_size, adaptive_key=key,
                                               silence_front=self.silence_front, rand_ini=rand_ini)
             self.last_key = key

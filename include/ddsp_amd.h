@@ -246,6 +246,12 @@ int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float*
 int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int64_t n_audio, int block, int xfade, int search,
               int delay, float* sola_buffer, float* emitted, int* shift);
 
+/* the sliding input window of the real-time callback (gui.py:373-374), in place on a buffer whose address never changes
+ * (a captured graph reads it): window[:] = append(window[block:], block_in); window (n_in), block_in (block) outside the
+ * window, 1 <= block < n_in (DDSP_ERR_ARG otherwise, nothing written).  The kept part is staged through the context's
+ * scratch arena (two launches in stream order), so the overlapping shift is exact whatever order workgroups run in. */
+int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int64_t n_in, const float* block_in, int64_t block);
+
 /* ---- a15: volume gate ------------------------------------------------------------------------ */
 /* replaces gui.py:14-31 `phase_vocoder(a, b, fade_out, fade_in)` (the optional cross-fade of gui.py:417-423; SURVEY
  * 8(f) rank 3): a = kept tail, b = head of the new block, both (n), fade windows (n), out (n).  n <= 65536. */
@@ -469,6 +475,12 @@ int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights
  * `dither_seed` when use_dither != 0); periodicity = the masked activation at the chosen bin; bins (int32, may be null). */
 int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
                       int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity, int32_t* bins);
+/* The same with the dither seed in device memory (8-byte aligned): the decode uses *seed_dev exactly as ddsp_crepe_decode uses
+ * dither_seed (bit-identical outputs for the same value), and a one-thread kernel behind it replaces the word by
+ * seed * 6364136223846793005 + 1442695040888963407 (mod 2^64), use_dither or not.  Captured into a HIP graph, every replay
+ * therefore dithers with a new seed (a by-value seed would be frozen at its capture-time value). */
+int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
+                            int64_t segment, uint64_t* seed_dev, int use_dither, float* f0, float* periodicity, int32_t* bins);
 /* The crepe tail of F0_Extractor.extract (ddsp/vocoder.py:96-113): f0, pd (B, Fr) -> out (B, n_frames): MedianPool1d(pd, 4),
  * f0 = NaN where that is < threshold, MaskedAvgPool1d(f0, 4) (reflect padding (1, 2), Fr >= 3), the re-timing
  * out[start_frame + n] = f0[min(rint(n * hop / sr / 0.005), Fr - 1)] for n < n_frames - start_frame (fp64 index arithmetic,
