@@ -167,6 +167,14 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Frames of batch row b: all Fr of a rectangular call (n_frames == null), else the row's own count of a ragged one, held
+// inside [1, Fr] whatever the array says (the host checks it; an index is never formed from an unchecked value)
+__device__ __forceinline__ int ddsp_row_frames(const int* __restrict__ n_frames, int64_t b, int Fr) {
+    if (!n_frames) return Fr;
+    const int n = n_frames[b];
+    return n < 1 ? 1 : (n > Fr ? Fr : n);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -22,9 +22,12 @@ void performer_q_bf16(hipStream_t st, const float* q, const void* p3, const floa
                       float* attn, int ablate = 0);
 // both sides in one kernel (round 3): ctx and ks stay in the LDS of the (utterance, head)'s workgroup
 hipError_t performer_fused_bf16(hipStream_t st, const float* q, const float* k, const float* v, const void* p3, int B, int Fr,
-                                float* attn, int out_split = 0);
+                                float* attn, int out_split = 0, const int* n_frames = nullptr);
 // ctxT[(b*8+h)][e][j] (64 x 272: the context matrix TRANSPOSED, pad features zero) and ks[(b*8+h)] (PERFORMER_KS_STRIDE floats each) from k, v (B*Fr, 512) and P (266, 64)
-void performer_kv(hipStream_t st, const float* k, const float* v, const float* P, int B, int Fr, float* ctxT, float* ks);
+// n_frames (both kernels above and below): device array of B per-row frame counts of a ragged batch - the key sums and the
+// context run over frames < n_frames[b] only; null: all Fr
+void performer_kv(hipStream_t st, const float* k, const float* v, const float* P, int B, int Fr, float* ctxT, float* ks,
+                  const int* n_frames = nullptr);
 // attn (B*Fr, 512) from q (B*Fr, 512), P, ctxT, ks
 void performer_q(hipStream_t st, const float* q, const float* P, const float* ctxT, const float* ks, int B, int Fr,
                  float* attn);

@@ -76,9 +76,9 @@ __device__ __forceinline__ float group_max(float x) {
 // in the LDS - for few (utterance, head) pairs, where one wave per item walks all tiles alone and the chip is mostly empty
 template <bool PART>
 __device__ __forceinline__ void performer_kv_item(const float* __restrict__ k, const float* __restrict__ v,
-                                                  const float* __restrict__ P, int Fr, float* __restrict__ ctxT,
-                                                  float* __restrict__ ks, int bh, int jt, int ft_first = 0,
-                                                  float* __restrict__ part = nullptr) {
+                                                  const float* __restrict__ P, int Fr, const int* __restrict__ n_frames,
+                                                  float* __restrict__ ctxT, float* __restrict__ ks, int bh, int jt,
+                                                  int ft_first = 0, float* __restrict__ part = nullptr) {
     constexpr int FSTEP = PART ? 4 : 1;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
@@ -88,12 +88,14 @@ __device__ __forceinline__ void performer_kv_item(const float* __restrict__ k, c
     load_quarter_row(P + (int64_t)(j < NF ? j : NF - 1) * DH + 16 * g, pb);
 #pragma unroll
     for (int s = 0; s < 16; ++s) pb[s] *= PSCALE;
-    const int n_ft = (Fr + 15) / 16;
+    // the sums run over the row's own frames: all Fr, or (ragged batch) the first nv of them
+    const int nv = ddsp_row_frames(n_frames, b, Fr);
+    const int n_ft = (nv + 15) / 16;
     f32x4_t c_full, c_last;                      // C init of a full frame tile / of the last (ragged) one
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         c_full[r] = j < NF ? KOFF : MASKED;
-        c_last[r] = (j < NF && 16 * (n_ft - 1) + 4 * g + r < Fr) ? KOFF : MASKED;
+        c_last[r] = (j < NF && 16 * (n_ft - 1) + 4 * g + r < nv) ? KOFF : MASKED;
     }
     f32x4_t acc[4];
 #pragma unroll
@@ -101,7 +103,7 @@ __device__ __forceinline__ void performer_kv_item(const float* __restrict__ k, c
     f32x4_t ksum4 = {0.f, 0.f, 0.f, 0.f};
     const float* kb = k + ((int64_t)b * Fr) * INNER + h * DH;     // wave-uniform bases, 32-bit lane offsets
     const float* vb = v + ((int64_t)b * Fr) * INNER + h * DH;
-    const int last = Fr - 1;
+    const int last = nv - 1;
     // One frame tile.  `cur` holds its k rows, `nxt` receives the next tile's: the two buffers swap roles from tile to
     // tile (loop unrolled by two below).  A copy `ka = kn` at the end of the tile looks harmless but the compiler
     // spreads its v_movs through the FIRST product, which then waits for rows loaded a few MFMAs earlier - the
@@ -113,12 +115,12 @@ __device__ __forceinline__ void performer_kv_item(const float* __restrict__ k, c
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             int f = 16 * ft + 4 * g + t;
-            f = f < Fr ? f : last;
+            f = f < nv ? f : last;
             vv[t] = *(const f32x4_t*)(vb + f * INNER + 4 * c);
         }
         // next tile's k rows (used only in the next call)
         int nf = 16 * (ft + FSTEP) + c;
-        nf = nf < Fr ? nf : last;
+        nf = nf < nv ? nf : last;
         load_quarter_row(kb + nf * INNER + 16 * g, nxt);
         // all eight loads of the tile are issued HERE, a whole product ahead of their first use
         __builtin_amdgcn_sched_barrier(0);
@@ -148,7 +150,7 @@ __device__ __forceinline__ void performer_kv_item(const float* __restrict__ k, c
     float ka[16], kc[16];
     {
         const int f0 = 16 * ft_first + c;
-        load_quarter_row(kb + (f0 < Fr ? f0 : last) * INNER + 16 * g, ka);
+        load_quarter_row(kb + (f0 < nv ? f0 : last) * INNER + 16 * g, ka);
     }
 #pragma unroll 1
     for (int ft = ft_first; ft < n_ft; ft += 2 * FSTEP) {
@@ -194,7 +196,8 @@ __device__ __forceinline__ void performer_kv_item(const float* __restrict__ k, c
 
 __global__ void __launch_bounds__(256, 4) performer_kv_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                               const float* __restrict__ P, int Fr,
-                                                              float* __restrict__ ctxT, float* __restrict__ ks) {
+                                                              float* __restrict__ ctxT, float* __restrict__ ks,
+                                                              const int* __restrict__ n_frames) {
     // 1-D grid, XCD-aware: workgroups id and id+8 share an XCD (and its L2), so all feature tiles of one
     // (utterance, head) - which re-read the same k and v rows - are dealt to ONE XCD (id & 7)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -202,18 +205,19 @@ __global__ void __launch_bounds__(256, 4) performer_kv_kernel(const float* __res
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int jt = 4 * grp + wave;
     if (jt >= NJT) return;
-    performer_kv_item<false>(k, v, P, Fr, ctxT, ks, bh, jt);
+    performer_kv_item<false>(k, v, P, Fr, n_frames, ctxT, ks, bh, jt);
 }
 
 // one (utterance, head, feature tile) per workgroup, its frame tiles over the four waves (few work items: see PART above)
 __global__ void __launch_bounds__(256, 4) performer_kv_split_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                                     const float* __restrict__ P, int Fr,
-                                                                    float* __restrict__ ctxT, float* __restrict__ ks) {
+                                                                    float* __restrict__ ctxT, float* __restrict__ ks,
+                                                                    const int* __restrict__ n_frames) {
     __shared__ float part[3 * 5 * 64 * 4];
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int jt = slot % NJT, bh = (slot / NJT) * 8 + xcd;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    performer_kv_item<true>(k, v, P, Fr, ctxT, ks, bh, jt, wave, part);
+    performer_kv_item<true>(k, v, P, Fr, n_frames, ctxT, ks, bh, jt, wave, part);
 }
 
 // PART = false: one wavefront walks all 17 feature tiles of its frame tile and stores the result.
@@ -615,13 +619,14 @@ constexpr int KV_SPLIT_MAX = 128;
 // work items up to which the feature range is split over four waves
 constexpr int Q_SPLIT_MAX = 1024;
 
-void performer_kv(hipStream_t st, const float* k, const float* v, const float* P, int B, int Fr, float* ctxT, float* ks) {
+void performer_kv(hipStream_t st, const float* k, const float* v, const float* P, int B, int Fr, float* ctxT, float* ks,
+                  const int* n_frames) {
     if (B * H <= KV_SPLIT_MAX) {
-        hipLaunchKernelGGL(performer_kv_split_kernel, dim3((unsigned)(NJT * B * H)), dim3(256), 0, st, k, v, P, Fr, ctxT, ks);
+        hipLaunchKernelGGL(performer_kv_split_kernel, dim3((unsigned)(NJT * B * H)), dim3(256), 0, st, k, v, P, Fr, ctxT, ks, n_frames);
         return;
     }
     // B*H is a multiple of 8, so the XCD-aware decode of the 1-D grid covers every (head, tile group) exactly once
-    hipLaunchKernelGGL(performer_kv_kernel, dim3((unsigned)(KV_GROUPS * B * H)), dim3(256), 0, st, k, v, P, Fr, ctxT, ks);
+    hipLaunchKernelGGL(performer_kv_kernel, dim3((unsigned)(KV_GROUPS * B * H)), dim3(256), 0, st, k, v, P, Fr, ctxT, ks, n_frames);
 }
 
 void performer_q(hipStream_t st, const float* q, const float* P, const float* ctxT, const float* ks, int B, int Fr,

@@ -536,7 +536,8 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_fused_bf16_
                                                                                  const float* __restrict__ k,
                                                                                  const float* __restrict__ v,
                                                                                  const uint4* __restrict__ p3, int Fr,
-                                                                                 float* __restrict__ attn, int out_split) {
+                                                                                 float* __restrict__ attn, int out_split,
+                                                                                 const int* __restrict__ n_frames) {
     extern __shared__ __attribute__((aligned(1024))) uint4 lds[];
     float* const sks = (float*)(lds + F_S);                   // ks[288] | cpart[9][64] | kpart[9]
     constexpr int S_CPART = 288, S_KPART = 288 + NJT * DH;
@@ -544,6 +545,8 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_fused_bf16_
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
     const int n_ft = (Fr + 31) / 32;
+    // key phase: the sums run over the row's own frames - all Fr, or (ragged batch) the first nk of them
+    const int nk = ddsp_row_frames(n_frames, b, Fr), n_ftk = (nk + 31) / 32;
 
     // ============================== key phase ==============================
     if (wave >= KG) {
@@ -555,16 +558,16 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_fused_bf16_
         auto load_round = [&](int r, int ft, float (&x)[8]) __attribute__((always_inline)) {
             if (r < 4) {
                 const int fi = 8 * r + (lane & 7), f = 32 * ft + fi;
-                const float* src = kb + (int64_t)(f < Fr ? f : Fr - 1) * INNER + 8 * (lane >> 3);
+                const float* src = kb + (int64_t)(f < nk ? f : nk - 1) * INNER + 8 * (lane >> 3);
                 const f32x4_t a0 = *(const f32x4_t*)src, a1 = *(const f32x4_t*)(src + 4);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = f < Fr ? (e < 4 ? a0[e & 3] : a1[e & 3]) : 0.f;
+                for (int e = 0; e < 8; ++e) x[e] = f < nk ? (e < 4 ? a0[e & 3] : a1[e & 3]) : 0.f;
             } else if (r < 8) {
                 const int o = r - 4;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int f = 32 * ft + 16 * (o >> 1) + 4 * (o & 1) + (e & 3) + 8 * (e >> 2);
-                    x[e] = f < Fr ? vb[(int64_t)f * INNER + lane] : 0.f;
+                    x[e] = f < nk ? vb[(int64_t)f * INNER + lane] : 0.f;
                 }
             }
         };
@@ -603,10 +606,10 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_fused_bf16_
 #pragma unroll
         for (int i = 0; i < 3; ++i) load_round(ws + 3 * i, 0, x[i]);
 #pragma unroll 1
-        for (int ft = 0; ft < n_ft; ++ft) {
+        for (int ft = 0; ft < n_ftk; ++ft) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) store_round(ws + 3 * i, ft, x[i]);
-            if (ft + 1 < n_ft) {
+            if (ft + 1 < n_ftk) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) load_round(ws + 3 * i, ft + 1, x[i]);
             }
@@ -635,15 +638,15 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_fused_bf16_
         const float c_init = 32 * jt + l31 < NF ? KOFF : MASKED;
         __syncthreads();                   // tile 0 is staged
 #pragma unroll 1
-        for (int ft = 0; ft < n_ft; ++ft) {
+        for (int ft = 0; ft < n_ftk; ++ft) {
             const uint4* st = lds + F_A + (ft & 1) * K_STAGE;
             f32x16 S;
 #pragma unroll
             for (int r = 0; r < 16; ++r) S[r] = c_init;
-            if (ft == n_ft - 1) {
+            if (ft == n_ftk - 1) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (32 * ft + (r & 3) + 8 * (r >> 2) + 4 * lh >= Fr) S[r] = MASKED;
+                    if (32 * ft + (r & 3) + 8 * (r >> 2) + 4 * lh >= nk) S[r] = MASKED;
             }
             bf16x8 a[2][3];
             const uint4* kp = st + K_KP + lh * 32 + l31;
@@ -967,7 +970,7 @@ void performer_q_bf16(hipStream_t st, const float* q, const void* p3, const floa
 }
 
 hipError_t performer_fused_bf16(hipStream_t st, const float* q, const float* k, const float* v, const void* p3, int B, int Fr,
-                                float* attn, int out_split) {
+                                float* attn, int out_split, const int* n_frames) {
     static std::atomic<uint64_t> done{0};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -979,7 +982,7 @@ hipError_t performer_fused_bf16(hipStream_t st, const float* q, const float* k, 
         done.fetch_or(bit, std::memory_order_release);
     }
     hipLaunchKernelGGL(performer_fused_bf16_kernel, dim3((unsigned)(B * H)), dim3(64 * (KG + KS_WAVES)), F_UNITS * 16, st, q, k, v,
-                       (const uint4*)p3, Fr, attn, out_split);
+                       (const uint4*)p3, Fr, attn, out_split, n_frames);
     return hipSuccess;
 }
 

@@ -63,7 +63,8 @@ template <bool SILU, bool FLIP, int RUN = DW_RUN>
 __global__ void __launch_bounds__(256) dwconv_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ bias, int B, int Fr,
                                                      float* __restrict__ out, float* __restrict__ pre, int wsc, int wst,
-                                                     int left, int split) {   // left = DWK / 2: centred taps; DWK - 1: causal taps (frames t-30 .. t)
+                                                     int left, int split,     // left = DWK / 2: centred taps; DWK - 1: causal taps (frames t-30 .. t)
+                                                     const int* __restrict__ n_frames = nullptr) {   // ragged batch: input frames >= n_b read as 0
     // split != 0 (forward, inference): `out` is written as bf16 hi/lo groups of 8 channels (A operand of the pw2 GEMM)
     const int c = blockIdx.x * 256 + threadIdx.x;       // channel (INNER = 512 -> 2 blocks in x)
     const int runs = (Fr + RUN - 1) / RUN;
@@ -72,11 +73,12 @@ __global__ void __launch_bounds__(256) dwconv_kernel(const float* __restrict__ x
 #pragma unroll
     for (int t = 0; t < DWK; ++t) wt[t] = w[c * wsc + (FLIP ? DWK - 1 - t : t) * wst];
     const float* xb = x + ((int64_t)b * Fr) * INNER + c;
+    const int n_in = ddsp_row_frames(n_frames, b, Fr);
     float win[RUN + DWK - 1];
 #pragma unroll
     for (int i = 0; i < RUN + DWK - 1; ++i) {
         const int f = f0 + i - left;
-        win[i] = (f >= 0 && f < Fr) ? xb[(int64_t)f * INNER] : 0.f;
+        win[i] = (f >= 0 && f < n_in) ? xb[(int64_t)f * INNER] : 0.f;
     }
     const float bi = FLIP ? 0.f : bias[c];
 #pragma unroll
@@ -160,6 +162,7 @@ struct U2CInputs {
     int64_t n_spk_id;
     MixArgs mix;
     int64_t B, Fr;
+    const int* n_frames = nullptr;   // device, B entries: frames of each row of a ragged batch; null: every row has Fr
 };
 
 // the buffers of a forward pass from the arena; keep: training (every layer's activations), else inference (one aliased set);

@@ -213,12 +213,15 @@ constexpr int GN_LANES = 16;   // frame lanes (waves) per block of the statistic
 // (rows = all frames of the call) and written back for the normalisation pass.
 __global__ void __launch_bounds__(64 * GN_LANES) groupnorm_stats_kernel(float* __restrict__ x, int Fr, float* __restrict__ stats,
                                                                        const float* __restrict__ part = nullptr,
-                                                                       const float* __restrict__ bias = nullptr, int64_t rows = 0) {
+                                                                       const float* __restrict__ bias = nullptr, int64_t rows = 0,
+                                                                       const int* __restrict__ n_frames = nullptr) {
     // block = (group g, utterance b); 1024 threads = 64 channels x 16 frame lanes.  (With 4 frame lanes every thread
     // walked 43 dependent loads, one in flight at a time: 14 us for 11 MB.  The sums are combined in a fixed order.)
     const int g = blockIdx.x, b = blockIdx.y;
     const int c = threadIdx.x & 63, fl = threadIdx.x >> 6;
     float* base = x + ((int64_t)b * Fr) * D + g * 64 + c;
+    // ragged batch: the statistics run over the row's own nv frames (the completed rows are still written for all Fr)
+    const int nv = ddsp_row_frames(n_frames, b, Fr);
     double s = 0.0, ss = 0.0;
     int f = fl;
     if (part) {
@@ -228,17 +231,19 @@ __global__ void __launch_bounds__(64 * GN_LANES) groupnorm_stats_kernel(float* _
             const int64_t o = (int64_t)ff * D;
             const float v = ((pb[o] + pb[rows * D + o]) + (pb[2 * rows * D + o] + pb[3 * rows * D + o])) + bc;
             base[o] = v;
-            s += (double)v;
-            ss += (double)v * (double)v;
+            if (ff < nv) {
+                s += (double)v;
+                ss += (double)v * (double)v;
+            }
         }
         f = Fr;
     }
-    for (; f + GN_LANES < Fr; f += 2 * GN_LANES) {          // two independent loads per trip
+    for (; f + GN_LANES < nv; f += 2 * GN_LANES) {          // two independent loads per trip
         const double v0 = (double)base[(int64_t)f * D], v1 = (double)base[(int64_t)(f + GN_LANES) * D];
         s += v0 + v1;
         ss += v0 * v0 + v1 * v1;
     }
-    if (f < Fr) {
+    if (f < nv) {
         const double v = (double)base[(int64_t)f * D];
         s += v;
         ss += v * v;
@@ -252,7 +257,7 @@ __global__ void __launch_bounds__(64 * GN_LANES) groupnorm_stats_kernel(float* _
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double n = 64.0 * Fr;
+        const double n = 64.0 * nv;
         double S = 0.0, SS = 0.0;
         for (int i = 0; i < GN_LANES; ++i) {
             S += red[i];
@@ -269,7 +274,9 @@ __global__ void __launch_bounds__(64 * GN_LANES) groupnorm_stats_kernel(float* _
 __global__ void __launch_bounds__(256) groupnorm_lrelu_kernel(const float* __restrict__ x, const float* __restrict__ stats,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, int64_t rows, int Fr,
-                                                              float* __restrict__ out, int split) {
+                                                              float* __restrict__ out, int split,
+                                                              const int* __restrict__ n_frames = nullptr) {
+    // ragged batch: frames past a row's own count are written as 0 - the second prenet convolution pads with zeros there
     // split != 0: the output is the A operand of a split-bf16 GEMM and is written as bf16 hi/lo groups (8 channels = two
     // neighbouring threads; rows * 64 threads, so a pair never straddles a wave)
     const int64_t total = rows * (D / 4);
@@ -286,6 +293,7 @@ __global__ void __launch_bounds__(256) groupnorm_lrelu_kernel(const float* __res
             const float y = fmaf((v[j] - mean) * rstd, ga[j], be[j]);
             o[j] = y > 0.f ? y : 0.01f * y;
         }
+        if (n_frames && (int)(m % Fr) >= ddsp_row_frames(n_frames, b, Fr)) o = f32x4{0.f, 0.f, 0.f, 0.f};
         if (split)
             *(ddsp_u32x4*)(out + m * D + c4) = ddsp_split4_pair(o, (i & 1) != 0, 1);
         else
@@ -598,7 +606,8 @@ typedef float f32x2_dw __attribute__((ext_vector_type(2)));
 template <int RUN>
 __global__ void __launch_bounds__(256, 3) dwconv_pair_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, int B, int Fr,
-                                                          float* __restrict__ out, int left, int split) {
+                                                          float* __restrict__ out, int left, int split,
+                                                          const int* __restrict__ n_frames = nullptr) {
     const int cp = blockIdx.x * 256 + threadIdx.x;      // channel pair (INNER / 2 = 256 pairs: one block in x)
     const int c = 2 * cp;
     const int runs = (Fr + RUN - 1) / RUN;
@@ -607,11 +616,12 @@ __global__ void __launch_bounds__(256, 3) dwconv_pair_kernel(const float* __rest
 #pragma unroll
     for (int t = 0; t < DWK; ++t) wt[t] = *(const f32x2_dw*)(w + t * INNER + c);      // [tap][channel] copy
     const float* xb = x + ((int64_t)b * Fr) * INNER + c;
+    const int n_in = ddsp_row_frames(n_frames, b, Fr);   // ragged batch: input frames >= n_b read as 0
     f32x2_dw win[RUN + DWK - 1];
 #pragma unroll
     for (int i = 0; i < RUN + DWK - 1; ++i) {
         const int f = f0 + i - left;
-        win[i] = (f >= 0 && f < Fr) ? *(const f32x2_dw*)(xb + (int64_t)f * INNER) : f32x2_dw{0.f, 0.f};
+        win[i] = (f >= 0 && f < n_in) ? *(const f32x2_dw*)(xb + (int64_t)f * INNER) : f32x2_dw{0.f, 0.f};
     }
     const f32x2_dw bi = *(const f32x2_dw*)(bias + c);
     const int q = threadIdx.x & 3;                       // position in the channel octet
@@ -657,7 +667,8 @@ __global__ void __launch_bounds__(256, 3) dwconv_pair_kernel(const float* __rest
 constexpr int DWT_F = 64, DWT_C = 64, DWT_RUN = 8;
 __global__ void __launch_bounds__(256, 3) dwconv_tile_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ bias, int B, int Fr,
-                                                             float* __restrict__ out, int left, int split) {
+                                                             float* __restrict__ out, int left, int split,
+                                                             const int* __restrict__ n_frames = nullptr) {
     constexpr int ROWS = DWT_F + DWK - 1;
     __shared__ float tile[ROWS * DWT_C];
     __shared__ float taps[DWK * DWT_C];
@@ -666,6 +677,7 @@ __global__ void __launch_bounds__(256, 3) dwconv_tile_kernel(const float* __rest
     const int ftiles = (Fr + DWT_F - 1) / DWT_F;
     const int b = blockIdx.y / ftiles, f0 = (blockIdx.y % ftiles) * DWT_F;
     const float* xb = x + ((int64_t)b * Fr) * INNER + c0;
+    const int n_in = ddsp_row_frames(n_frames, b, Fr);   // ragged batch: input frames >= n_b read as 0
 #pragma unroll
     for (int k = 0; k < (ROWS * (DWT_C / 4) + 255) / 256; ++k) {
         const int i = tid + 256 * k;
@@ -673,7 +685,7 @@ __global__ void __launch_bounds__(256, 3) dwconv_tile_kernel(const float* __rest
             const int row = i / (DWT_C / 4), c4 = i % (DWT_C / 4);
             const int f = f0 + row - left;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (f >= 0 && f < Fr) v = *(const f32x4*)(xb + (int64_t)f * INNER + 4 * c4);
+            if (f >= 0 && f < n_in) v = *(const f32x4*)(xb + (int64_t)f * INNER + 4 * c4);
             *(f32x4*)(tile + row * DWT_C + 4 * c4) = v;
         }
     }
@@ -947,10 +959,10 @@ int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const 
     }
     PROF(PF_U2C_ROWWISE, 0, 4.0 * M * D,
          hipLaunchKernelGGL(groupnorm_stats_kernel, dim3(4, (unsigned)B), dim3(64 * GN_LANES), 0, st, bf.t1, (int)Fr, bf.gst,
-                            conv_split ? bf.kpart : nullptr, w.prenet_conv1_b, M));
+                            conv_split ? bf.kpart : nullptr, w.prenet_conv1_b, M, in.n_frames));
     PROF(PF_U2C_ROWWISE, 0, 8.0 * M * D,
          hipLaunchKernelGGL(groupnorm_lrelu_kernel, dim3(grid_for(M * (D / 4))), dim3(256), 0, st, bf.t1, bf.gst,
-                            w.prenet_gn_w, w.prenet_gn_b, M, (int)Fr, bf.t2, asplit));
+                            w.prenet_gn_w, w.prenet_gn_b, M, (int)Fr, bf.t2, asplit, in.n_frames));
     float* x = bf.l[0].x_in;
     {
         gemm::Args g = gemm::make(bf.t2, D, bf.w2, 3 * D, iM, D, 3 * D);
@@ -1024,7 +1036,7 @@ int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const 
             void* p3 = (char*)bf.p3 + (size_t)l * PERFORMER_P3_BYTES;
             // both sides in one kernel per (utterance, head): ctx and ks stay in its LDS (round 3)
             PROF(PF_U2C_GEMM_CTX, 8.0 * M8 * NF * DH, 4.0 * M * 4 * INNER,
-                 DDSP_HIP(ctx, performer_fused_bf16(st, b.q, b.k, b.v, p3, (int)B, (int)Fr, b.attn, asplit)));
+                 DDSP_HIP(ctx, performer_fused_bf16(st, b.q, b.k, b.v, p3, (int)B, (int)Fr, b.attn, asplit, in.n_frames)));
         } else if (w.causal && !b.pre) {
             // causal mode, inference: chunked linear attention in one kernel (performer_attn.hip); q' / k' never reach HBM
             PROF(PF_U2C_GEMM_ATTNOUT, 2.0 * M8 * (3.0 * NF * DH + 16.0 * (NF + DH)) + 4.0 * M8 * NF * DH, 4.0 * M * 4 * INNER,
@@ -1037,7 +1049,7 @@ int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const 
         } else if (!b.pre) {
             // inference: fused feature maps + linear attention (performer_attn.hip); q'/k' never reach HBM
             PROF(PF_U2C_GEMM_CTX, 4.0 * M8 * NF * DH, 4.0 * M * 2 * INNER,
-                 performer_kv(st, b.k, b.v, L.proj, (int)B, (int)Fr, b.cx, b.ks));
+                 performer_kv(st, b.k, b.v, L.proj, (int)B, (int)Fr, b.cx, b.ks, in.n_frames));
             PROF(PF_U2C_GEMM_ATTNOUT, 4.0 * M8 * NF * DH, 4.0 * M * 2 * INNER,
                  performer_q(st, b.q, L.proj, b.cx, b.ks, (int)B, (int)Fr, b.attn));
         } else {
@@ -1114,17 +1126,17 @@ int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const 
              if (!b.pre && dw_tiled && B * ((Fr + 15) / 16) >= 512)
                  // inference, large batches: LDS-staged tiles of 64 frames x 64 channels
                  hipLaunchKernelGGL(dwconv_tile_kernel, dim3(INNER / DWT_C, (unsigned)(B * ((Fr + DWT_F - 1) / DWT_F))), dim3(256), 0, st,
-                                    b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit);
+                                    b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit, in.n_frames);
              else if (!b.pre && B * ((Fr + 15) / 16) >= 512)
                  // inference, large batches: two channels per thread on packed multiply-adds, runs of 16 frames
                  hipLaunchKernelGGL((dwconv_pair_kernel<16>), dim3(1, (unsigned)(B * ((Fr + 15) / 16))), dim3(256), 0, st,
-                                    b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit);
+                                    b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, w.causal ? DWK - 1 : DWK / 2, asplit, in.n_frames);
              else if (B * ((Fr + DW_RUN - 1) / DW_RUN) >= 64)
                  hipLaunchKernelGGL((dwconv_kernel<true, false>), dim3(INNER / 256, (unsigned)(B * ((Fr + DW_RUN - 1) / DW_RUN))),
-                                    dim3(256), 0, st, b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, b.pre, 1, INNER, w.causal ? DWK - 1 : DWK / 2, asplit);
+                                    dim3(256), 0, st, b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, b.pre, 1, INNER, w.causal ? DWK - 1 : DWK / 2, asplit, in.n_frames);
              else   // a few utterances (the real-time block): runs of 8 frames, four times as many workgroups
                  hipLaunchKernelGGL((dwconv_kernel<true, false, 8>), dim3(INNER / 256, (unsigned)(B * ((Fr + 7) / 8))),
-                                    dim3(256), 0, st, b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, b.pre, 1, INNER, w.causal ? DWK - 1 : DWK / 2, asplit));
+                                    dim3(256), 0, st, b.glu, bf.wdw + (size_t)l * DWK * INNER, L.cm_dw_b, (int)B, (int)Fr, b.dwo, b.pre, 1, INNER, w.causal ? DWK - 1 : DWK / 2, asplit, in.n_frames));
         {
             gemm::Args g = gemm::make(b.dwo, INNER, L.cm_pw2_w, INNER, iM, D, INNER);
             set_b(g, bf.wpw2 + (size_t)l * D * INNER, asplit);
@@ -1201,14 +1213,16 @@ int check_inputs(ddsp_ctx* ctx, const ddsp_u2c_weights* wp, const float* units, 
 
 }  // namespace u2c
 
-extern "C" int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                  const float* f0_frames, const float* phase_frames, const float* volume,
-                                  const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                  const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, float* ctrl) {
+// the inference forward behind ddsp_unit2ctrl_fwd (n_frames null) and ddsp_unit2ctrl_fwd_ragged: the same launches
+static int unit2ctrl_fwd_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                             const float* f0_frames, const float* phase_frames, const float* volume,
+                             const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                             const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, float* ctrl) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
     if (rc) return rc;
+    in.n_frames = (const int*)n_frames;
     DDSP_REQUIRE(ctx, ctrl, "ddsp_unit2ctrl_fwd: null ctrl");
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
     if (B == 0) return DDSP_OK;
@@ -1243,6 +1257,29 @@ extern "C" int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_we
     plan_forward(a, bf, w, B, Fr, false, cached);
     if (a.rc) return a.rc;
     return u2c_forward(ctx, st, w, in, bf, ctrl);
+}
+
+extern "C" int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                  const float* f0_frames, const float* phase_frames, const float* volume,
+                                  const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                  const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, float* ctrl) {
+    return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
+                             n_mix, B, Fr, nullptr, ctrl);
+}
+
+// Ragged batch: row b has n_frames[b] frames (device array, int32, 1 <= n_frames[b] <= Fr) inside the padded (B, Fr, ...)
+// inputs.  The places that look across frames stop at the row's own end: the GroupNorm statistics, the zero padding of the
+// second prenet convolution, the key sums and the context of the linear attention, the depthwise convolution's input.
+// The first convolution reads its input as the caller left it: units of frames >= n_frames[b] must be 0
+// (ddsp_ragged_frames).  Rows of ctrl past a row's count hold values that mean nothing.
+extern "C" int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                         const float* f0_frames, const float* phase_frames, const float* volume,
+                                         const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                         const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                         float* ctrl) {
+    DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_unit2ctrl_fwd_ragged: null n_frames");
+    return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
+                             n_mix, B, Fr, n_frames, ctrl);
 }
 
 // ---- a training step's pair: a forward that leaves its activations in a caller-owned region, a backward that starts from them ----

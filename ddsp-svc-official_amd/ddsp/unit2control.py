@@ -220,11 +220,37 @@ class Unit2Control(nn.Module):
     def _weights_struct(self):
         return self._table.struct(self)
 
-    def forward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict=None):
-        """(B, Fr, n_out) fused control matrix (the split views are taken by `forward`)."""
+    def forward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, n_frames=None):
+        """(B, Fr, n_out) fused control matrix (the split views are taken by `forward`).
+        `n_frames` (a sequence of B ints or a CPU integer tensor (B,), 1 <= n_frames[b] <= Fr): a ragged batch - the first
+        n_frames[b] rows of ctrl[b] are what the network gives for that row alone at its own length, whatever the padding of
+        the inputs holds; the rows after them carry no meaning.  Inference only."""
+        if n_frames is not None:
+            vals = hipddsp.check_n_frames(n_frames, units.shape[0], units.shape[1])
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                raise NotImplementedError("n_frames= (ragged batches) is inference only: there is no ragged backward pass; call "
+                                          "the network under torch.no_grad()")
+            ctx = hipddsp.context_for(units.device)
+            n_dev = ctx.ragged_counts(vals)
+            B, Fr = units.shape[0], units.shape[1]
+            # the padding is replaced by selection before anything reads it (the chunked causal attention, for one, multiplies
+            # a whole 16-frame tile before it masks: a NaN there would not stay in its own frame)
+            return self.forward_ragged(ctx, ctx.ragged_frames(units, n_dev, hold=False),
+                                       ctx.ragged_frames(f0.reshape(B, Fr), n_dev, hold=True),
+                                       ctx.ragged_frames(phase.reshape(B, Fr), n_dev, hold=False),
+                                       ctx.ragged_frames(volume.reshape(B, Fr), n_dev, hold=False), spk_id, spk_mix_dict,
+                                       n_dev, hold=False)
         ctx = hipddsp.context_for(units.device)
         w, keep = self._weights_struct()
         return ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out)
+
+    def forward_ragged(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=True):
+        """The control matrix of a ragged batch whose counts are on the device (`Context.ragged_counts`) and whose units are 0
+        past every row's count.  hold: every row's last control frame is repeated over its padding - the form in which the
+        DSP kernels take a ragged batch (`csrc/ragged.hip`)."""
+        w, keep = self._weights_struct()
+        ctrl = ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, n_frames=n_dev)
+        return ctx.ragged_frames(ctrl, n_dev, hold=True, out=ctrl) if hold else ctrl
 
     def forward_flat_keep(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, ctx=None):
         """Training forward: (control matrix, kept activations) - PyTorch keeps a module's activations for `backward`

@@ -9,6 +9,12 @@ Differences a caller can observe, all additive:
     generator (so `torch.manual_seed` still makes a run repeatable) or from `noise_seed`.
   * `c=True` (causal convolutions + causal linear attention): forward and training; the two third-party primitives
     behind it are restated from their definitions.
+  * `forward(..., n_frames=None)`: a RAGGED batch.  `n_frames` (a sequence of B ints or a CPU integer tensor (B,),
+    1 <= n_frames[b] <= Fr) gives the frames of each row inside the padded (B, Fr, ...) inputs; row b of every returned
+    tensor is then, over its first n_frames[b] frames / n_frames[b] * block_size samples, what the model returns for that
+    row alone at its own length, and exactly 0.0 after them.  What the padding of units / f0 / volume / noise holds (zeros,
+    garbage, NaN) does not matter.  Inference only: with grad mode on and a parameter that wants a gradient it raises
+    NotImplementedError.  With `noise_seed=` the draw is repeatable but not the draw of the rows' solo calls.
 """
 import os
 
@@ -280,6 +286,33 @@ class _SynthBase(torch.nn.Module):
         ctx = hipddsp.context_for(f0_frames.device)
         return ctx, ctx.phase_scan(f0_frames, self._hop, self._sr, initial_phase, bool(infer), comb_mode, **want)
 
+    def _ragged_front(self, units, f0_frames, volume, n_frames, initial_phase, infer, comb_mode, **want):
+        """Head of a ragged forward: checks `n_frames` (ValueError before anything is launched) and uploads it once, puts
+        the frame-rate inputs into held form (units and volume 0, f0 its last frame over a row's padding: `csrc/ragged.hip`)
+        and runs the phase scan on them.  -> (ctx, n_dev, units, f0 (B,Fr,1), volume, phase-scan outputs)."""
+        B, Fr = units.shape[0], units.shape[1]
+        vals = hipddsp.check_n_frames(n_frames, B, Fr)
+        if self._training_graph():
+            raise NotImplementedError("n_frames= (ragged batches) is inference only: there is no ragged backward pass; call the "
+                                      "model under torch.no_grad() (training crops every clip to one length)")
+        if not f0_frames.is_cuda:
+            raise RuntimeError("the synthesiser runs on a HIP device only (no CPU fallback): move the model and its "
+                               "inputs to 'cuda'")
+        if self._hop % 4:
+            raise ValueError("n_frames= needs a block_size that is a multiple of 4")
+        ctx = hipddsp.context_for(f0_frames.device)
+        n_dev = ctx.ragged_counts(vals)
+        units = ctx.ragged_frames(units, n_dev, hold=False)
+        f0 = ctx.ragged_frames(f0_frames.reshape(B, Fr), n_dev, hold=True).reshape(B, Fr, 1)
+        volume = ctx.ragged_frames(volume.reshape(B, Fr), n_dev, hold=False)
+        ps = ctx.phase_scan(f0, self._hop, self._sr, initial_phase, bool(infer), comb_mode, **want)
+        return ctx, n_dev, units, f0, volume, ps
+
+    def _ragged_noise(self, ctx, n_dev, B, Fr, noise, noise_seed):
+        """(unit-noise draw (B,T) with 0.5 - no excitation - past every row's end, EXC_UNIT_NOISE, 0)."""
+        seed = 0 if noise is not None else (_seed_from_torch() if noise_seed is None else int(noise_seed))
+        return ctx.ragged_noise(noise, seed, n_dev, B, Fr, self._hop), EXC_UNIT_NOISE, 0
+
     def _empty_result(self, f0_frames, sample_rate_phase=False, shared=False):
         """The (signal, phase, (harmonic, noise)) tuple of an empty batch (nothing is launched)."""
         Fr = f0_frames.shape[1]
@@ -404,28 +437,43 @@ class CombSub(_SynthBase):
         ctx.fir_from_ctrl_bwd(FIR_ALLPASS, c2, 0, na, rows, sr, d_ir, d_ctrl)
         return d_ctrl
 
-    def synth_from_ctrl(self, ctx, ctrl, f0_frames, comb, noise=None, noise_seed=None):
-        """DSP stage: fused control matrix (B,Fr,sum) + combtooth -> (signal, harmonic, noise)."""
+    def synth_from_ctrl(self, ctx, ctrl, f0_frames, comb, noise=None, noise_seed=None, n_dev=None):
+        """DSP stage: fused control matrix (B,Fr,sum) + combtooth -> (signal, harmonic, noise).
+        `n_dev`: the counts of a ragged batch whose ctrl and f0 are held over the padding (`_ragged_front`); every signal is
+        then cropped to its row before it enters the next filter - the all-pass output too, as the reference crops per call."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
         rows, sr, hop = B * Fr, self._sr, self._hop
         na, nh, nn_ = self.n_mags
         c2 = ctrl.reshape(rows, -1)
+        crop = (lambda *xs: ctx.ragged_crop_(n_dev, Fr, hop, *xs)) if n_dev is not None else (lambda *xs: None)
+        crop(comb)
         ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, 0, na, rows, sr)
         h, _ = ctx.ltv_fir(comb, ir, B, Fr, hop, math=ctx.fir_math)
+        crop(h)
         ir = ctx.fir_from_ctrl(FIR_DYNAMIC, c2, na, nh, rows, sr, f0_frames)
         harmonic, _ = ctx.ltv_fir(h, ir, B, Fr, hop, math=ctx.fir_math)
+        crop(harmonic)
         ir = ctx.fir_from_ctrl(FIR_STATIC, c2, na + nh, nn_, rows, sr)
-        nz, exc, seed = self._noise_args(noise, noise_seed)
+        nz, exc, seed = self._noise_args(noise, noise_seed) if n_dev is None else \
+            self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
         noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
                                         math=ctx.fir_math)
+        crop(noise_out, signal)
         return signal, harmonic, noise_out
 
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
-                infer=True, noise=None, noise_seed=None, **kwargs):
+                infer=True, noise=None, noise_seed=None, n_frames=None, **kwargs):
         """units (B,Fr,n_unit), f0 (B,Fr,1) Hz, volume (B,Fr), spk_id (B,1)|(1,1) int64 1-based ->
-        (signal (B,T), phase_frames (B,Fr,1), (harmonic (B,T), noise (B,T)))."""
+        (signal (B,T), phase_frames (B,Fr,1), (harmonic (B,T), noise (B,T))).  `n_frames`: ragged batch (module docstring)."""
         if units_frames.shape[0] == 0:
             return self._empty_result(f0_frames)
+        if n_frames is not None:
+            ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
+                                                                initial_phase, infer, COMB_SINC)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev)
+            signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0, ps["comb"], noise, noise_seed, n_dev)
+            pf = ctx.ragged_frames(ps["phase_frames"], n_dev, hold=False, out=ps["phase_frames"])
+            return signal, pf.unsqueeze(-1), (harmonic, noise_out)
         if self._training_graph():
             pf, signal, harmonic, noise_out = _SynthTrainFn.apply(
                 self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
@@ -484,27 +532,40 @@ class Sins(_SynthBase):
         ctx.sins_bank_bwd(c2, 0, nhm, f0_frames, phase, d_sin, B, Fr, hop, sr, d_ctrl)
         return d_ctrl
 
-    def synth_from_ctrl(self, ctx, ctrl, f0_frames, phase, noise=None, noise_seed=None):
+    def synth_from_ctrl(self, ctx, ctrl, f0_frames, phase, noise=None, noise_seed=None, n_dev=None):
+        """`n_dev`: the counts of a ragged batch (see CombSub.synth_from_ctrl)."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
         rows, sr, hop = B * Fr, self._sr, self._hop
         nhm, na, nn_ = self.n_mags
         c2 = ctrl.reshape(rows, -1)
+        crop = (lambda *xs: ctx.ragged_crop_(n_dev, Fr, hop, *xs)) if n_dev is not None else (lambda *xs: None)
         sinusoids = ctx.sins_bank(c2, 0, nhm, f0_frames, phase, B, Fr, hop, sr)
+        crop(sinusoids)
         ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, nhm, na, rows, sr)
         harmonic, _ = ctx.ltv_fir(sinusoids, ir, B, Fr, hop, math=ctx.fir_math)
+        crop(harmonic)
         ir = ctx.fir_from_ctrl(FIR_STATIC, c2, nhm + na, nn_, rows, sr)
-        nz, exc, seed = self._noise_args(noise, noise_seed)
+        nz, exc, seed = self._noise_args(noise, noise_seed) if n_dev is None else \
+            self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
         noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
                                         math=ctx.fir_math)
+        crop(noise_out, signal)
         return signal, harmonic, noise_out
 
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
-                infer=True, max_upsample_dim=32, noise=None, noise_seed=None):
+                infer=True, max_upsample_dim=32, noise=None, noise_seed=None, n_frames=None):
         """Same contract as CombSub.forward except that the returned phase is sample-rate (B,T,1)
         (reference `ddsp/vocoder.py:423`).  `max_upsample_dim` is accepted and ignored: the bank kernel never
         materialises the (B,T,chunk) tensors the reference chunks to bound."""
         if units_frames.shape[0] == 0:
             return self._empty_result(f0_frames, sample_rate_phase=True)
+        if n_frames is not None:
+            ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
+                                                                initial_phase, infer, COMB_NONE, want_phase=True)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev)
+            signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0, ps["phase"], noise, noise_seed, n_dev)
+            ctx.ragged_crop_(n_dev, f0.shape[1], self._hop, ps["phase"])
+            return signal, ps["phase"].unsqueeze(-1), (harmonic, noise_out)
         if self._training_graph():
             ph, signal, harmonic, noise_out = _SynthTrainFn.apply(
                 self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
@@ -544,17 +605,33 @@ class CombSubFast(_SynthBase):
         return ctx.spectral_ola_bwd(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, _sum_grads(comb, *d_outs), B, Fr,
                                     self._hop)
 
-    def synth_from_ctrl(self, ctx, ctrl, comb, noise=None, noise_seed=None):
+    def synth_from_ctrl(self, ctx, ctrl, comb, noise=None, noise_seed=None, n_dev=None):
+        """`n_dev`: the counts of a ragged batch whose ctrl is held over the padding: with the comb and the excitation 0
+        past a row's end, frames 0..n_b of the row are the frames of the row rendered alone (frame n_b on frame n_b - 1's
+        filters, 512 zeros behind the row)."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
-        nz, exc, seed = self._noise_args(noise, noise_seed)
-        return ctx.spectral_ola(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, B, Fr, self._hop)
+        if n_dev is None:
+            nz, exc, seed = self._noise_args(noise, noise_seed)
+            return ctx.spectral_ola(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, B, Fr, self._hop)
+        ctx.ragged_crop_(n_dev, Fr, self._hop, comb)
+        nz, exc, seed = self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
+        signal = ctx.spectral_ola(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, B, Fr, self._hop)
+        ctx.ragged_crop_(n_dev, Fr, self._hop, signal)
+        return signal
 
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
-                infer=True, noise=None, noise_seed=None, **kwargs):
+                infer=True, noise=None, noise_seed=None, n_frames=None, **kwargs):
         """Returns (signal, phase_frames (B,Fr,1), (signal, signal)) - the same tensor three times, like the
-        reference (`ddsp/vocoder.py:492`)."""
+        reference (`ddsp/vocoder.py:492`).  `n_frames`: ragged batch (module docstring)."""
         if units_frames.shape[0] == 0:
             return self._empty_result(f0_frames, shared=True)
+        if n_frames is not None:
+            ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
+                                                                initial_phase, infer, COMB_SINC_GATED)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev)
+            signal = self.synth_from_ctrl(ctx, ctrl, ps["comb"], noise, noise_seed, n_dev)
+            pf = ctx.ragged_frames(ps["phase_frames"], n_dev, hold=False, out=ps["phase_frames"])
+            return signal, pf.unsqueeze(-1), (signal, signal)
         if self._training_graph():
             pf, signal = _SynthTrainFn.apply(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict,
                                              initial_phase, infer, noise, noise_seed, *self.unit2ctrl.parameters())

@@ -5,6 +5,7 @@ current HIP stream.  There is NO CPU fallback: without the shared library or wit
 calls raise.
 """
 import ctypes
+import numbers
 import os
 import threading
 
@@ -209,6 +210,11 @@ SIGNATURES = {
                                   _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp]),
     "ddsp_unit2ctrl_bwd": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
                                   _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _c.POINTER(U2CWeights), _vp]),
+    "ddsp_unit2ctrl_fwd_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
+                                         _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp]),
+    "ddsp_ragged_frames": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
+    "ddsp_ragged_crop": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int]),
+    "ddsp_ragged_noise": (_int, [_vp, _vp, _vp, _u64, _vp, _i64, _i64, _int, _vp]),
     "ddsp_ltv_fir": (_int, [_vp, _vp, _vp, _int, _u64, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _int]),
     "ddsp_unit2ctrl_keep_bytes": (_i64, [_c.POINTER(U2CWeights), _i64, _i64]),
     "ddsp_unit2ctrl_fwd_keep": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
@@ -241,6 +247,32 @@ def load_library():
                                    "rebuild it (`python ddsp-svc-official_amd/hipddsp/build.py`)")
             _lib = lib
     return _lib
+
+
+def check_n_frames(n_frames, B, Fr):
+    """The per-row frame counts of a ragged batch as a list of B Python ints, 1 <= n <= Fr; anything else raises ValueError
+    (a host check: nothing is launched).  Accepted: a sequence of ints, or a CPU integer tensor of shape (B,)."""
+    if isinstance(n_frames, torch.Tensor):
+        if n_frames.is_cuda:
+            raise ValueError("n_frames must be a CPU tensor or a sequence of ints (it is checked on the host)")
+        if n_frames.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or n_frames.dim() != 1:
+            raise ValueError(f"n_frames must be an integer tensor of shape (B,), got {n_frames.dtype} {tuple(n_frames.shape)}")
+        vals = n_frames.tolist()
+    else:
+        try:
+            vals = list(n_frames)
+        except TypeError:
+            raise ValueError("n_frames must be a sequence of B ints or a CPU integer tensor of shape (B,)") from None
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError(f"n_frames must hold ints, got {type(v).__name__} {v!r}")
+        vals = [int(v) for v in vals]
+    if len(vals) != int(B):
+        raise ValueError(f"n_frames must hold B={int(B)} counts, got {len(vals)}")
+    for b, v in enumerate(vals):
+        if not 1 <= v <= int(Fr):
+            raise ValueError(f"n_frames[{b}] = {v} is outside 1..Fr={int(Fr)}")
+    return vals
 
 
 def _ptr(t):
@@ -384,7 +416,8 @@ class Context:
         return {"rot": rot, "phase": phase, "comb": comb, "f0_up": f0_up, "phase_frames": pf}
 
     # -- a4 ------------------------------------------------------------------------------------
-    def unit2ctrl(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out):
+    def unit2ctrl(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out, n_frames=None):
+        """n_frames: the (B,) int32 device tensor of a ragged batch (`ragged_counts`); units past a row's count must be 0."""
         B, Fr, _ = units.shape
         dev = units.device
         units = units.contiguous().float()
@@ -403,9 +436,51 @@ class Context:
             n_sid = sid.numel()
             if n_sid not in (1, B):
                 raise ValueError(f"spk_id must hold 1 or B={B} ids, got {n_sid}")
+        if n_frames is not None:
+            self.call("ddsp_unit2ctrl_fwd_ragged", ctypes.byref(weights), _ptr(units), _ptr(f0), _ptr(ph), _ptr(vol), _ptr(sid),
+                      n_sid, ids, ws, n_mix, B, Fr, _ptr(n_frames), _ptr(ctrl))
+            return ctrl
         self.call("ddsp_unit2ctrl_fwd", ctypes.byref(weights), _ptr(units), _ptr(f0), _ptr(ph), _ptr(vol), _ptr(sid),
                   n_sid, ids, ws, n_mix, B, Fr, _ptr(ctrl))
         return ctrl
+
+    # -- ragged batches (include/ddsp_amd.h): held frames, cropped signals, the noise draw ---------
+    def ragged_counts(self, counts):
+        """counts: the list `check_n_frames` returned -> the (B,) int32 device tensor the ragged calls take (one upload)."""
+        return torch.tensor(counts, dtype=torch.int32).to(self.device)
+
+    def ragged_frames(self, x, n_dev, hold, out=None):
+        """x (B,Fr,C) or (B,Fr) -> frames past a row's count replaced by its last frame (hold) or by 0; `out=x`: in place."""
+        B, Fr = x.shape[0], x.shape[1]
+        C = x.numel() // max(B * Fr, 1)
+        if out is None:
+            x = x.contiguous().float()
+            out = torch.empty_like(x)
+        elif x.dtype != torch.float32 or not x.is_contiguous() or out.data_ptr() != x.data_ptr():
+            raise ValueError("ragged_frames: `out` is for the in-place call, out=x, on a contiguous fp32 tensor")
+        self.call("ddsp_ragged_frames", _ptr(x), _ptr(n_dev), B, Fr, C, 1 if hold else 0, _ptr(out))
+        return out
+
+    def ragged_crop_(self, n_dev, Fr, hop, *signals):
+        """In place: up to three (B, Fr*hop) fp32 signals are set to 0 from sample n_b * hop on."""
+        xs = [s for s in signals if s is not None]
+        for s in xs:
+            if s.dtype != torch.float32 or not s.is_contiguous() or s.dim() != 2 or s.shape[1] != int(Fr) * int(hop):
+                raise ValueError("ragged_crop_: contiguous fp32 (B, Fr*hop) signals")
+        for i in range(0, len(xs), 3):
+            grp = xs[i:i + 3] + [None] * (3 - len(xs[i:i + 3]))
+            self.call("ddsp_ragged_crop", _ptr(grp[0]), _ptr(grp[1]), _ptr(grp[2]), _ptr(n_dev), grp[0].shape[0], int(Fr), int(hop))
+
+    def ragged_noise(self, noise, noise_seed, n_dev, B, Fr, hop):
+        """The unit-noise draw (B, Fr*hop) of a ragged batch for EXC_UNIT_NOISE: the caller's `noise` or a hash of the seed
+        inside a row, 0.5 (-> exactly 0 excitation) past its end."""
+        out = torch.empty(B, Fr * hop, device=self.device, dtype=torch.float32)
+        if noise is not None:
+            noise = noise.contiguous().float()
+            if tuple(noise.shape) != (B, Fr * hop):
+                raise ValueError(f"noise must be (B, Fr*hop) = {(B, Fr * hop)}, got {tuple(noise.shape)}")
+        self.call("ddsp_ragged_noise", _ptr(noise), int(noise_seed) & ((1 << 64) - 1), _ptr(n_dev), B, Fr, int(hop), _ptr(out))
+        return out
 
     def unit2ctrl_bwd(self, weights, grads, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out,
                       d_ctrl, want_ctrl=False):

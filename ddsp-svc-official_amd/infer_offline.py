@@ -3,7 +3,8 @@
 The reference's `main.py` is broken as shipped (`.astype` on a tensor at :112, key shift applied twice at :105/:120,
 SURVEY 0.3), so this module restates what it intends.  `render` takes analysed features and does what happens from there:
 per-slice `model(...)[0]`, the volume gate multiplied into the returned signal in place, optional enhancer, silence padding /
-cross-fade of slices.  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
+cross-fade of slices; with `batch_frames=` the slices are rendered in ragged batches (`model(..., n_frames=)`) instead of
+one after the other.  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
 (`Units_Encoder`) on the device, then `render`.  Cutting the audio into slices (`slicer.Slicer`, a librosa-based silence
 detector) stays with the caller: `convert` takes the slice boundaries.
 """
@@ -11,6 +12,7 @@ import numpy as np
 import torch
 
 import hipddsp
+from sharding import stack_rows
 
 
 def cross_fade(a: np.ndarray, b: np.ndarray, idx: int):
@@ -31,23 +33,69 @@ def volume_mask(volume, threshold_db, block_size):
     return ctx.volume_gate_(ones, volume, threshold_db, block_size)
 
 
+def group_segments(lengths, batch_frames):
+    """Groups of segment indices for ragged batches: segments sorted by length (longest first, ties in their own order)
+    are taken greedily into a group while its padded size, len(group) * longest, stays <= batch_frames; a segment longer
+    than batch_frames is a group of its own.  Every index is in exactly one group."""
+    groups = []
+    for i in sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i)):
+        if groups and (len(groups[-1]) + 1) * int(lengths[groups[-1][0]]) <= batch_frames:
+            groups[-1].append(i)
+        else:
+            groups.append([i])
+    return groups
+
+
+def _render_ragged(model, segments, f0, volume, spk_id, spk_mix_dict, noise_seed, batch_frames, block, noise=None):
+    """Every segment's signal (1, n * block), in the order of `segments`, from one ragged forward per group.  All groups are
+    rendered before the stitch starts, so the whole file's audio is on the device at once (4 bytes per sample)."""
+    lengths = [units.size(1) for _, units in segments]
+    for (start, _), n in zip(segments, lengths):
+        if start < 0 or start + n > f0.shape[1] or start + n > volume.shape[1]:
+            raise ValueError(f"render: the segment at frame {start} has {n} frames of units but f0 / volume cover "
+                             f"{f0.shape[1]} / {volume.shape[1]} frames of the file")
+    rendered = [None] * len(segments)
+    for group in group_segments(lengths, batch_frames):
+        u, counts = stack_rows([segments[i][1][0] for i in group])
+        f, _ = stack_rows([f0[0, segments[i][0]:segments[i][0] + lengths[i]] for i in group])
+        v, _ = stack_rows([volume[0, segments[i][0]:segments[i][0] + lengths[i]] for i in group])
+        kw = {} if noise_seed is None else {"noise_seed": noise_seed + min(segments[i][0] for i in group)}
+        if noise is not None:
+            kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
+        signal = model(u, f, v, spk_id=spk_id, spk_mix_dict=spk_mix_dict, n_frames=counts, **kw)[0]
+        for j, i in enumerate(group):
+            rendered[i] = signal[j:j + 1, :counts[j] * block].clone()
+    return rendered
+
+
 @torch.no_grad()
 def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, threshold_db=-60, enhancer=None,
-           enhancer_adaptive_key=0, noise_seed=None):
+           enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None):
     """segments: list of (start_frame, units (1, Fr_seg, n_unit)) as `main.py:143-151` produces them;
-    f0 (1, Fr, 1), volume (1, Fr) cover the whole file.  Returns (float64 numpy waveform, sample rate)."""
+    f0 (1, Fr, 1), volume (1, Fr) cover the whole file.  Returns (float64 numpy waveform, sample rate).
+    batch_frames: None renders slice after slice at batch 1; a number renders the slices in ragged batches of at most that
+    many padded frames (`group_segments`), one forward per group, each slice as if rendered alone; gate, enhancer, silence
+    and cross-fade then run per slice in the original order, so the file is stitched the same way.
+    noise: a list with one (n * block,) U[0,1) draw per segment that stands where the model draws its noise (parity runs)."""
     block = int(args.data.block_size)
     sr = int(args.data.sampling_rate)
     ctx = hipddsp.context_for(f0.device)
     result = np.zeros(0)
     current = 0
     sr_o = sr
-    for start, units in segments:
+    rendered = None if batch_frames is None else \
+        _render_ragged(model, segments, f0, volume, spk_id, spk_mix_dict, noise_seed, int(batch_frames), block, noise)
+    for i, (start, units) in enumerate(segments):
         n = units.size(1)
         seg_f0 = f0[:, start:start + n, :]
         seg_vol = volume[:, start:start + n]
-        kw = {} if noise_seed is None else {"noise_seed": noise_seed + start}
-        out = model(units, seg_f0, seg_vol, spk_id=spk_id, spk_mix_dict=spk_mix_dict, **kw)[0]
+        if rendered is not None:
+            out = rendered[i]
+        else:
+            kw = {} if noise_seed is None else {"noise_seed": noise_seed + start}
+            if noise is not None:
+                kw["noise"] = noise[i].reshape(1, -1)
+            out = model(units, seg_f0, seg_vol, spk_id=spk_id, spk_mix_dict=spk_mix_dict, **kw)[0]
         # the gate of the WHOLE file sliced to this segment (main.py:159): dilation sees the neighbours
         gate = volume_mask(volume, threshold_db, block)[:, start * block:(start + n) * block]
         out *= gate
@@ -75,7 +123,20 @@ def convert(model, args, audio, sample_rate, slices, units_encoder, f0_extractor
     (main.py:41-46: start_frame = int(start // hop_size), end_frame = int(end // hop_size), audio[int(start_frame *
     hop_size) : int(end_frame * hop_size)], empty slices dropped), the units of that slice's audio (main.py:148-151), then
     `render`.  `units_encoder` / `f0_extractor`: `ddsp.vocoder.Units_Encoder` / `F0_Extractor` built for `sample_rate` and
-    that hop (ValueError otherwise).  Returns (float64 numpy waveform, sample rate)."""
+    that hop (ValueError otherwise).  Returns (float64 numpy waveform, sample rate).
+    `convert_batched` is the same call with the slices rendered in ragged batches."""
+    return convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, None, key=key,
+                           spk_mix_dict=spk_mix_dict, threshold_db=threshold_db, enhancer=enhancer,
+                           enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed)
+
+
+@torch.no_grad()
+def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, batch_frames, key=0,
+                    spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None):
+    """`convert` with `render`'s `batch_frames`: the slices are rendered in ragged batches of at most that many padded frames
+    (None: slice after slice, which is `convert`).  The units are still encoded slice by slice, the enhancer still runs per
+    slice.  (A function of its own and not a keyword of `convert`: tests/test_stream_audio_host.py pins `convert`'s
+    parameter list.)"""
     hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
     if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
         raise ValueError(f"convert: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop {f0_extractor.hop_size}; "
@@ -95,4 +156,4 @@ def convert(model, args, audio, sample_rate, slices, units_encoder, f0_extractor
             seg = x[None, int(start_frame * hop_size):int(end_frame * hop_size)]
             segments.append((start_frame, units_encoder.encode(seg, sample_rate, hop_size)))
     return render(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
-                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed)
+                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames)

@@ -22,6 +22,16 @@ def shard_batch(batch, world, rank):
     return {k: (v[lo:hi] if v.shape[0] == B else v) for k, v in batch.items()}
 
 
+def stack_rows(rows):
+    """Rows of different length (n_i, ...) -> ((B, max n_i, ...) tensor padded with zeros, [n_i]): the padded layout of a
+    ragged batch (`forward(..., n_frames=)`)."""
+    counts = [int(r.shape[0]) for r in rows]
+    out = rows[0].new_zeros((len(rows), max(counts)) + tuple(rows[0].shape[1:]))
+    for j, r in enumerate(rows):
+        out[j, :counts[j]] = r
+    return out, counts
+
+
 class AudioGather:
     """all_gather of (B_local, T) fp32 audio into (world*B_local, T), overlapped with compute."""
 
@@ -66,11 +76,12 @@ class AudioGather:
 
 class RaggedPlan:
     """Utterances of different lengths over the ranks (sort by length, pad to frame multiples, gather with
-    counts).  An utterance cannot be padded INSIDE the network (GroupNorm statistics and the linear-attention sums run
-    over all its frames), so every utterance is rendered at its own length; what is padded is the exchange: each rank
-    packs its rendered utterances back to back into one flat buffer of `slot` samples (the largest rank total, the same
-    on every rank because the plan is a pure function of the lengths), one `all_gather_into_tensor` moves the slots, and
-    `unpack` cuts the gathered buffer by the counts into the original order.
+    counts).  A rank renders its utterances in ONE ragged forward (`render_local`: the padded batch with per-row frame
+    counts, `model(..., n_frames=)`, in which the GroupNorm statistics, the linear-attention sums and every filter stop at
+    the row's own end, so each utterance comes out as if rendered alone at its own length).  The exchange is padded too:
+    each rank packs its rendered utterances back to back into one flat buffer of `slot` samples (the largest rank total,
+    the same on every rank because the plan is a pure function of the lengths), one `all_gather_into_tensor` moves the
+    slots, and `unpack` cuts the gathered buffer by the counts into the original order.
     Assignment: utterances sorted by length (longest first) are dealt to the rank with the least work so far."""
 
     def __init__(self, n_frames, world, hop=512):
@@ -89,6 +100,23 @@ class RaggedPlan:
     def local(self, rank):
         """Indices (into the caller's list) of the utterances `rank` renders, in packing order."""
         return list(self.assign[rank])
+
+    @torch.no_grad()
+    def render_local(self, model, rank, units, f0, volume, spk_id, spk_mix_dict=None, **kw):
+        """Renders the utterances of `rank` with one ragged forward.  units / f0 / volume: the caller's lists over ALL
+        utterances, entry i of shape (n_frames[i], n_unit) / (n_frames[i], 1) / (n_frames[i],) (a leading batch dimension of 1
+        is accepted); spk_id (1,1), or (N,1) with one id per utterance.  `kw` goes to the model (noise_seed=, infer=).
+        -> this rank's (T_i,) audio tensors in `local(rank)` order: what `pack` expects."""
+        idx = self.local(rank)
+        if not idx:
+            return []
+        row = lambda t, i, tail: t[i].reshape((self.n_frames[i],) + tail)
+        u, counts = stack_rows([row(units, i, (units[i].shape[-1],)) for i in idx])
+        f, _ = stack_rows([row(f0, i, (1,)) for i in idx])
+        v, _ = stack_rows([row(volume, i, ()) for i in idx])
+        sid = spk_id if spk_id.shape[0] == 1 else spk_id[idx]
+        signal = model(u, f, v, sid, spk_mix_dict=spk_mix_dict, n_frames=counts, **kw)[0]
+        return [signal[j, :n * self.hop] for j, n in enumerate(counts)]
 
     def pack(self, rank, rendered, device="cpu"):
         """rendered: this rank's (T_i,) audio tensors in `local(rank)` order -> (slot,) flat buffer (zero tail)."""

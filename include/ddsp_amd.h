@@ -158,6 +158,40 @@ int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weig
                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
                        const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, float* ctrl);
 
+/* ---- ragged batches: rows of different length in one padded (B, Fr, ...) call, inference only ------------------------------
+ * n_frames: DEVICE array of B int32, 1 <= n_frames[b] <= Fr (the caller checks it; the kernels hold a value outside the range
+ * at its nearest bound).  Row b comes out as if it had been computed alone with Fr = n_frames[b].
+ *
+ * ddsp_unit2ctrl_fwd_ragged is ddsp_unit2ctrl_fwd with the same launches, in which every place that looks across frames
+ * stops at the row's own end: the GroupNorm statistics (count included), the zero padding of the second prenet convolution,
+ * the key sums and the context of the linear attention, the input of the depthwise convolution.  Its first convolution
+ * reads `units` as they are: frames >= n_frames[b] must hold 0 (ddsp_ragged_frames, hold = 0).  Rows of ctrl past a row's
+ * count carry no meaning.
+ *
+ * The DSP entry points (ddsp_phase_scan, ddsp_fir_from_ctrl, ddsp_ltv_fir, ddsp_sins_bank, ddsp_spectral_ola) take a ragged
+ * batch unchanged once it is in HELD form, which the three calls below produce by selection (never by a product with a
+ * mask, so NaN or infinities in the padding are not read into arithmetic):
+ *   ddsp_ragged_frames  dst[b][i][:] = i < n_b ? src[b][i][:] : (hold ? src[b][n_b - 1][:] : 0); src == dst is allowed.
+ *                       hold = 1 for f0 and the control matrix (the kernels interpolate towards frame min(i + 1, Fr - 1) and
+ *                       reuse the last filter for frame Fr: over held frames that IS min(i + 1, n_b - 1)); hold = 0 for
+ *                       units, volume and the returned frame phases.
+ *   ddsp_ragged_crop    x[b][t] = 0 for t >= n_b * hop in up to three (B, Fr*hop) signals (x1, x2 may be NULL): every
+ *                       sample-rate signal before it enters a filter (a filter tail then reads the zeros a row rendered
+ *                       alone is padded with) and every output.  hop % 4 == 0, 16-byte aligned buffers.
+ *   ddsp_ragged_noise   out (B, Fr*hop) = the unit-noise draw U[0,1) for DDSP_EXC_UNIT_NOISE: inside a row noise[b][t], or
+ *                       (noise == NULL) a counter hash of (noise_seed, b, t); 0.5 past the row's end (2u - 1 = 0 exactly). */
+int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
+                              const float* f0_frames, const float* phase_frames, const float* volume,
+                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                              float* ctrl);
+int ddsp_ragged_frames(ddsp_ctx* ctx, void* stream, const float* src, const int32_t* n_frames, int64_t B, int64_t Fr,
+                       int64_t C, int hold, float* dst);
+int ddsp_ragged_crop(ddsp_ctx* ctx, void* stream, float* x0, float* x1, float* x2, const int32_t* n_frames, int64_t B,
+                     int64_t Fr, int hop);
+int ddsp_ragged_noise(ddsp_ctx* ctx, void* stream, const float* noise, uint64_t noise_seed, const int32_t* n_frames,
+                      int64_t B, int64_t Fr, int hop, float* out);
+
 /* Backward of ddsp_unit2ctrl_fwd for training (reference: autograd through Unit2Control, solver.py:113).  The call
  * re-runs the forward keeping its activations in the scratch arena, then back-propagates d_ctrl (B,Fr,n_out) to
  * every parameter.  `grads_host` has the layout of ddsp_u2c_weights; each pointer receives the gradient of the
