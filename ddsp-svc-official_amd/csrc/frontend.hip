@@ -36,20 +36,36 @@ __global__ void __launch_bounds__(256) volume_kernel(const float* __restrict__ a
     if (lane == 0) vol[fidx] = sqrtf((float)(s / (double)len));
 }
 
-// one wavefront per output row (utterance, frame)
+// one wavefront per output row (utterance, frame).  Ragged batch (n_units != nullptr): row b has n_out[b] frames of its own,
+// gathered from its own n_units[b] unit rows (the source index stops at n_units[b] - 1), and zeros after them.
 __global__ void __launch_bounds__(256) align_units_kernel(const float* __restrict__ units, int64_t Lu, int64_t C,
                                                           int64_t n_frames, float ratio, int64_t total,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out, const int32_t* __restrict__ n_units,
+                                                          const int32_t* __restrict__ n_out) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= total) return;
     const int64_t b = row / n_frames, i = row - b * n_frames;
+    float* d = out + row * C;
+    const bool vec = (C & 3) == 0 && (((uintptr_t)units | (uintptr_t)out) & 15) == 0;
+    int64_t last = Lu - 1;
+    if (n_units) {
+        if (i >= (int64_t)n_out[b]) {
+            if (vec) {
+                for (int64_t c = 4 * lane; c < C; c += 256) *(f32x4*)(d + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                for (int64_t c = lane; c < C; c += 64) d[c] = 0.f;
+            }
+            return;
+        }
+        const int64_t lb = (int64_t)n_units[b] - 1;
+        last = lb < last ? lb : last;
+    }
     int64_t src = (int64_t)rintf(__fmul_rn(ratio, (float)i));     // torch.round of an fp32 product: half to even
-    src = src < Lu - 1 ? src : Lu - 1;
+    src = src < last ? src : last;
     src = src < 0 ? 0 : src;
     const float* s = units + (b * Lu + src) * C;
-    float* d = out + row * C;
-    if ((C & 3) == 0 && (((uintptr_t)units | (uintptr_t)out) & 15) == 0) {
+    if (vec) {
         for (int64_t c = 4 * lane; c < C; c += 256) *(f32x4*)(d + c) = *(const f32x4*)(s + c);
     } else {
         for (int64_t c = lane; c < C; c += 64) d[c] = s[c];
@@ -153,7 +169,24 @@ extern "C" int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units,
     const int64_t total = B * n_frames;
     ddsp_prof_begin(ctx, st, PF_OTHER);
     hipLaunchKernelGGL(align_units_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, units, Lu, C, n_frames,
-                       ratio, total, out);
+                       ratio, total, out, (const int32_t*)nullptr, (const int32_t*)nullptr);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * total * (double)C);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
+                                       int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
+    DDSP_REQUIRE(ctx, ctx && units && out && n_units && n_out, "ddsp_align_units_ragged: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && Lu >= 1 && C >= 1 && n_frames >= 0 && ratio >= 0.f && ratio == ratio,
+                 "ddsp_align_units_ragged: bad shape or ratio");
+    if (B == 0 || n_frames == 0) return DDSP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    const int64_t total = B * n_frames;
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(align_units_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, units, Lu, C, n_frames,
+                       ratio, total, out, n_units, n_out);
     ddsp_prof_end(ctx, st, 0.0, 8.0 * total * (double)C);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;

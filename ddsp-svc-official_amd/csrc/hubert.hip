@@ -65,41 +65,81 @@ struct EpiPos {
     }
 };
 
+// ---- ragged batches: per-row counts -----------------------------------------------------------------------
+// cnt[b][0] = the row's own samples (held inside 0..T), cnt[b][1..7] = the frames after conv0 and after each strided
+// convolution (frames_of on the device; a row too short for the stack, which the caller refuses, counts 0 from there on)
+constexpr int HCNT = 8;
+__global__ void hub_counts_kernel(const int32_t* __restrict__ n_samples, int64_t B, int64_t T, int32_t* __restrict__ cnt) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int64_t n = n_samples[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    int32_t* c = cnt + b * HCNT;
+    c[0] = (int32_t)n;
+    int64_t f = (n + 2 * HPAD - 10) / 5 + 1;   // n >= 0: at least 15
+    c[1] = (int32_t)f;
+    for (int i = 0; i < 6; ++i) {
+        const int kt = i < 4 ? 3 : 2;
+        f = f < kt ? 0 : (f - kt) / 2 + 1;
+        c[i + 2] = (int32_t)f;
+    }
+}
+
 // ---- conv0 (1 -> 512, kernel 10, stride 5, no bias) + GroupNorm(512, 512) statistics ------------------------
 // grid (GN_PARTS, B), block 512 = one channel per thread; the block walks frames [T0*p/P, T0*(p+1)/P) and writes the
 // fp64 sum and sum of squares of its channel over them (reduced in a fixed order by gn_finalize_kernel)
+// RAGGED (cnt != nullptr): samples past the row's own n_b are SELECTED as 0 (the padding may hold NaN), so the 40 zeros
+// a solo call pads with fall out of the same bounds test; the block walks the row's own t0_b frames partitioned as a solo
+// call partitions them (the fp64 sums then add in the same order, empty partitions included).  Frames t0_b..T0-1 of the
+// padded buffer, which no frame of the row ever reads, are written by the blocks' second loop so that everything
+// downstream of them is finite; they stay out of the statistics.
+template <bool RAGGED>
 __global__ void __launch_bounds__(512) conv0_kernel(const float* __restrict__ wav, int64_t T, const float* __restrict__ w0,
-                                                    float* __restrict__ y, int64_t T0, double* __restrict__ part) {
+                                                    float* __restrict__ y, int64_t T0, double* __restrict__ part,
+                                                    const int32_t* __restrict__ cnt) {
     const int b = blockIdx.y, p = blockIdx.x, c = threadIdx.x;
     float w[10];
 #pragma unroll
     for (int t = 0; t < 10; ++t) w[t] = w0[c * 10 + t];
-    const int64_t f0 = T0 * p / GN_PARTS, f1 = T0 * (p + 1) / GN_PARTS;
+    const int64_t n = RAGGED ? (int64_t)cnt[b * HCNT] : T;       // samples of the row
+    const int64_t tb = RAGGED ? (int64_t)cnt[b * HCNT + 1] : T0;   // its conv0 frames
+    const int64_t f0 = tb * p / GN_PARTS, f1 = tb * (p + 1) / GN_PARTS;
     const float* x = wav + (int64_t)b * T;
     float* yb = y + (int64_t)b * T0 * HC;
-    double s = 0.0, ss = 0.0;
-    for (int64_t f = f0; f < f1; ++f) {
+    auto frame = [&](int64_t f) {
         float acc = 0.f;
 #pragma unroll
         for (int t = 0; t < 10; ++t) {
             const int64_t i = f * 5 + t - HPAD;
-            const float xv = (i >= 0 && i < T) ? x[i] : 0.f;
+            const float xv = (i >= 0 && i < n) ? x[i] : 0.f;
             acc = fmaf(w[t], xv, acc);
         }
         yb[f * HC + c] = acc;
+        return acc;
+    };
+    double s = 0.0, ss = 0.0;
+    for (int64_t f = f0; f < f1; ++f) {
+        const float acc = frame(f);
         s += (double)acc;
         ss += (double)acc * (double)acc;
     }
     double* pp = part + ((int64_t)b * GN_PARTS + p) * 2 * HC;
     pp[c] = s;
     pp[HC + c] = ss;
+    if (RAGGED) {
+        const int64_t r = T0 - tb;
+        for (int64_t f = tb + r * p / GN_PARTS; f < tb + r * (p + 1) / GN_PARTS; ++f) frame(f);
+    }
 }
 
 // per (utterance, channel): scale = gamma / sqrt(var + eps), shift = beta - mean * scale (biased variance, fp64).  grid (8, B),
 // block 1024: 64 channels x 16 slices of the GN_PARTS partial sums, the slices added in a fixed order
+// (cnt: the per-row counts of a ragged batch, whose statistics divide by the row's own t0_b; nullptr: T0)
 __global__ void __launch_bounds__(1024) gn_finalize_kernel(const double* __restrict__ part, int64_t T0, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, float* __restrict__ aff) {
+                                                           const float* __restrict__ beta, float* __restrict__ aff,
+                                                           const int32_t* __restrict__ cnt) {
     __shared__ double red[2][16][64];
+    if (cnt) T0 = cnt[blockIdx.y * HCNT + 1];
     const int b = blockIdx.y, cl = threadIdx.x & 63, sl = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
     double s = 0.0, ss = 0.0;
     for (int p = sl; p < GN_PARTS; p += 16) {
@@ -173,7 +213,9 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* x, const fl
 }
 
 // ---- positional conv operand: x (B*L, 768) -> xg[b][g][L + 128][48], 64 zero rows before and after ---------------
-__global__ void __launch_bounds__(256) pos_pack_kernel(const float* __restrict__ x, int L, int64_t n4, float* __restrict__ xg) {
+// (cnt: ragged batch, frames >= L_b are selected as 0 too: the zero edge a row encoded alone sees)
+__global__ void __launch_bounds__(256) pos_pack_kernel(const float* __restrict__ x, int L, int64_t n4, float* __restrict__ xg,
+                                                       const int32_t* __restrict__ cnt) {
     const int64_t rows = L + POS_K;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const int64_t e = i * 4;
@@ -182,7 +224,8 @@ __global__ void __launch_bounds__(256) pos_pack_kernel(const float* __restrict__
         const int64_t b = bg / POS_G, g = bg % POS_G;
         const int64_t src = r - POS_K / 2;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (src >= 0 && src < L) v = *(const f32x4*)(x + (b * L + src) * HD + g * POS_C + c);
+        const int64_t Lb = cnt ? (int64_t)cnt[b * HCNT + 7] : (int64_t)L;
+        if (src >= 0 && src < Lb) v = *(const f32x4*)(x + (b * L + src) * HD + g * POS_C + c);
         *(f32x4*)(xg + e) = v;
     }
 }
@@ -229,10 +272,14 @@ __global__ void __launch_bounds__(256) pos_weight_kernel(const float* __restrict
 // staged in LDS; the S partial (max, sum, accumulator) triples of a query are merged through LDS at the end.  fp32 products.
 constexpr int ATT_KT = 64, ATT_LD = HDH + 4;   // keys per LDS tile; padded row (4 rows read at once by a wave when QT = 16)
 
-template <int QT>
+// RAGGED: keys[b * kstride] is the key count L_b of utterance b (held inside 0..L); rows are still L apart.  Tile loop, nk
+// and staging test against L_b, so the online softmax of a row walks the tiles it walks alone; a query tile wholly past L_b
+// returns before it stages anything and query rows >= L_b are not written.
+template <int QT, bool RAGGED>
 __global__ void __launch_bounds__(256) attention_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                         const float* __restrict__ v, int64_t ld, float* __restrict__ out,
-                                                        int64_t ldo, int L, int heads, float scale) {
+                                                        int64_t ldo, int Lpad, int heads, float scale,
+                                                        const int32_t* __restrict__ keys, int kstride) {
     constexpr int S = 256 / QT, KPT = ATT_KT / S;    // key splits, keys per thread and tile
     constexpr int MERGE = S * QT * HDH;              // floats of the merge buffer
     __shared__ __attribute__((aligned(16))) float smem[MERGE + 2 * 256];
@@ -240,8 +287,14 @@ __global__ void __launch_bounds__(256) attention_kernel(const float* __restrict_
     float* const vs = smem + ATT_KT * ATT_LD;
     const int tid = threadIdx.x, qi = tid % QT, s = tid / QT;
     const int b = blockIdx.y / heads, h = blockIdx.y % heads;
+    int L = Lpad;
+    if (RAGGED) {
+        L = keys[(int64_t)b * kstride];
+        L = L < 0 ? 0 : (L > Lpad ? Lpad : L);
+        if ((int)blockIdx.x * QT >= L) return;   // (uniform over the workgroup)
+    }
     const int qrow = blockIdx.x * QT + qi;
-    const int64_t base = (int64_t)b * L;
+    const int64_t base = (int64_t)b * Lpad;
     float qr[HDH], acc[HDH];
     {
         const float* qp = q + (base + (qrow < L ? qrow : L - 1)) * ld + h * HDH;
@@ -351,19 +404,33 @@ __global__ void __launch_bounds__(256) attention_kernel(const float* __restrict_
     }
 }
 
+template <bool RAGGED>
 int attention_launch(hipStream_t st, const float* q, const float* k, const float* v, int64_t ld, float* out, int64_t ldo,
-                     int64_t B, int L, int heads) {
-    // the largest query tile whose grid still covers the 256 CUs (small L: more, shorter workgroups)
+                     int64_t B, int L, int heads, const int32_t* keys = nullptr, int kstride = 0) {
+    // the largest query tile whose grid still covers the 256 CUs (small L: more, shorter workgroups); a ragged batch chooses
+    // by its padded L
     const int64_t bh = B * heads;
     const float scale = 0.125f;   // 1 / sqrt(64)
     if (bh * ceil_div64(L, 64) >= 256) {
-        hipLaunchKernelGGL(attention_kernel<64>, dim3((unsigned)ceil_div64(L, 64), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale);
+        hipLaunchKernelGGL((attention_kernel<64, RAGGED>), dim3((unsigned)ceil_div64(L, 64), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale, keys, kstride);
     } else if (bh * ceil_div64(L, 32) >= 256) {
-        hipLaunchKernelGGL(attention_kernel<32>, dim3((unsigned)ceil_div64(L, 32), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale);
+        hipLaunchKernelGGL((attention_kernel<32, RAGGED>), dim3((unsigned)ceil_div64(L, 32), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale, keys, kstride);
     } else {
-        hipLaunchKernelGGL(attention_kernel<16>, dim3((unsigned)ceil_div64(L, 16), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale);
+        hipLaunchKernelGGL((attention_kernel<16, RAGGED>), dim3((unsigned)ceil_div64(L, 16), (unsigned)bh), dim3(256), 0, st, q, k, v, ld, out, ldo, L, heads, scale, keys, kstride);
     }
     return 0;
+}
+
+// ---- last step of a ragged batch: dst[b][i][:] = i < L_b ? src[b][i][:] : 0 over (B, L, C); src == dst is allowed -----
+// A selection, never a product: the rows >= L_b of src may hold NaN (hubert_run, RAGGED INVARIANT).  16-byte aligned dst.
+__global__ void __launch_bounds__(256) hub_crop_kernel(const float* src, float* dst, int64_t L, int C4, int64_t n4,
+                                                       const int32_t* __restrict__ cnt) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / C4, b = row / L, fr = row - b * L;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (fr < (int64_t)cnt[b * HCNT + 7]) v = *(const f32x4*)(src + i * 4);
+        *(f32x4*)(dst + i * 4) = v;
+    }
 }
 
 // ---- GEMM helper --------------------------------------------------------------------------------------------
@@ -402,7 +469,7 @@ struct HubPlan {
     size_t off[16];
     size_t total;
 };
-enum { S_Y0, S_Y1, S_PART, S_AFF, S_Z, S_X, S_Y, S_QKV, S_CTX, S_H, S_XG, S_WCONV, S_WPOS, S_PSCALE, S_N };
+enum { S_Y0, S_Y1, S_PART, S_AFF, S_Z, S_X, S_Y, S_QKV, S_CTX, S_H, S_XG, S_WCONV, S_WPOS, S_PSCALE, S_CNT, S_N };
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -428,6 +495,7 @@ HubPlan plan(int64_t B, const int64_t (&t)[7]) {
     sz[S_WCONV] = wconv_floats() * 4;
     sz[S_WPOS] = wpos_floats() * 4;
     sz[S_PSCALE] = POS_K * 4;
+    sz[S_CNT] = (size_t)B * HCNT * 4;
     HubPlan p;
     size_t o = 0;
     for (int i = 0; i < S_N; ++i) {
@@ -461,16 +529,23 @@ bool weights_complete(const ddsp_hubert_weights& w) {
 }
 
 // stop: -1 = conv stack output (B, Fr, 512); 0..12 = hidden state after that many transformer layers (B, Fr, 768);
-// 13 = units (B, Fr, 256)
+// 13 = units (B, Fr, 256).  n_samples: nullptr, or the DEVICE array of a ragged batch's B sample counts (never read back:
+// the per-row frame counts are derived on the device); the launches are the rectangular call's plus the counts kernel and
+// the final crop, over the padded shapes.
 int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, const float* wav, int64_t B, int64_t T, int stop,
-               float* out) {
-    DDSP_REQUIRE(ctx, ctx && wp && wav && out, "ddsp_hubert: null argument");
-    DDSP_REQUIRE(ctx, weights_complete(*wp), "ddsp_hubert: a weight pointer is null");
-    DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && stop >= -1 && stop <= 13, "ddsp_hubert: bad shape or layer");
+               float* out, const int32_t* n_samples = nullptr) {
+    // ("ddsp_hubert" / "ddsp_hubert_ragged": the family of entry points that was called)
+#define HUB_MSG(text) (n_samples ? "ddsp_hubert_ragged: " text : "ddsp_hubert: " text)
+    DDSP_REQUIRE(ctx, ctx && wp && wav && out, HUB_MSG("null argument"));
+    DDSP_REQUIRE(ctx, weights_complete(*wp), HUB_MSG("a weight pointer is null"));
+    DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && stop >= -1 && stop <= 13, HUB_MSG("bad shape or layer"));
+    // the final crop of a ragged batch moves 16 bytes at a time
+    DDSP_REQUIRE(ctx, !n_samples || ((uintptr_t)out % 16) == 0, "ddsp_hubert_ragged: the output must be 16-byte aligned");
     int64_t t[7];
     const int64_t Fr = frames_of(T, t);
-    DDSP_REQUIRE(ctx, Fr >= 1, "ddsp_hubert: audio too short for the conv stack (ddsp_hubert_frames(T) == 0)");
-    DDSP_REQUIRE(ctx, B * t[0] < ((int64_t)1 << 31) && B * Fr * HFF < ((int64_t)1 << 31), "ddsp_hubert: input too long");
+    DDSP_REQUIRE(ctx, Fr >= 1, HUB_MSG("audio too short for the conv stack (ddsp_hubert_frames(T) == 0)"));
+    DDSP_REQUIRE(ctx, B * t[0] < ((int64_t)1 << 31) && B * Fr * HFF < ((int64_t)1 << 31), HUB_MSG("input too long"));
+#undef HUB_MSG
     const ddsp_hubert_weights w = *wp;
     DDSP_ENTER_DEVICE(ctx);
     const int L = (int)Fr;
@@ -512,9 +587,18 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     // ---- feature extractor ----
     float* y0 = buf(S_Y0);
     float* y1 = buf(S_Y1);
-    hipLaunchKernelGGL(conv0_kernel, dim3(GN_PARTS, (unsigned)B), dim3(512), 0, st, wav, T, w.conv0_w, y0, t[0], (double*)buf(S_PART));
+    const bool ragged = n_samples != nullptr;
+    int32_t* cnt = ragged ? (int32_t*)buf(S_CNT) : nullptr;
+    if (ragged) {
+        hipLaunchKernelGGL(hub_counts_kernel, dim3((unsigned)ceil_div64(B, 256)), dim3(256), 0, st, n_samples, B, T, cnt);
+        hipLaunchKernelGGL(conv0_kernel<true>, dim3(GN_PARTS, (unsigned)B), dim3(512), 0, st, wav, T, w.conv0_w, y0, t[0],
+                           (double*)buf(S_PART), (const int32_t*)cnt);
+    } else {
+        hipLaunchKernelGGL(conv0_kernel<false>, dim3(GN_PARTS, (unsigned)B), dim3(512), 0, st, wav, T, w.conv0_w, y0, t[0],
+                           (double*)buf(S_PART), (const int32_t*)nullptr);
+    }
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(HC / 64, (unsigned)B), dim3(1024), 0, st, (const double*)buf(S_PART), t[0], w.norm0_w, w.norm0_b,
-                       buf(S_AFF));
+                       buf(S_AFF), (const int32_t*)cnt);
     {
         const int64_t n4 = B * t[0] * HC / 4;
         hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, st, y0, t[0], n4,
@@ -523,6 +607,9 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     float* cur = y0;
     float* nxt = y1;
     size_t wo = 0;
+    // A ragged batch needs nothing here: frame j < t_{i+1}(b) of a row reads frames 2j .. 2j + taps - 1 <= t_i(b) - 1, its
+    // own.  The frames past a row's count are computed too, from conv0's selected zeros and the row's own GroupNorm
+    // affine: up to the transformer they are finite, and nothing of the row reads them.
     for (int i = 0; i < 6; ++i) {
         const int kt = CONV_TAPS[i];
         EpiGelu e{nxt, HC, nullptr, t[i + 1] * HC};
@@ -532,8 +619,17 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
         cur = nxt;
         nxt = s;
     }
+    // ragged: rows >= L_b of whatever is returned are written as exact zeros, by selection
+    auto crop = [&](const float* src, int C) {
+        const int64_t n4 = rows * C / 4;
+        hipLaunchKernelGGL(hub_crop_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, st, src, out,
+                           Fr, C / 4, n4, (const int32_t*)cnt);
+    };
     if (stop == -1) {
-        DDSP_HIP(ctx, hipMemcpyAsync(out, cur, (size_t)rows * HC * 4, hipMemcpyDeviceToDevice, st));
+        if (ragged)
+            crop(cur, HC);
+        else
+            DDSP_HIP(ctx, hipMemcpyAsync(out, cur, (size_t)rows * HC * 4, hipMemcpyDeviceToDevice, st));
         DDSP_LAUNCH_CHECK(ctx);
         return DDSP_OK;
     }
@@ -547,7 +643,7 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     {
         const int64_t n4 = B * POS_G * (L + POS_K) * POS_C / 4;
         hipLaunchKernelGGL(pos_pack_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, st, X, L, n4,
-                           buf(S_XG));
+                           buf(S_XG), (const int32_t*)cnt);
         hub_gemm(st, math, buf(S_XG), POS_C, (int64_t)(L + POS_K) * POS_C, wpos, POS_KK, (int64_t)POS_C * POS_KK, L, POS_C, POS_KK,
                  (int)(B * POS_G), POS_G, EpiPos{Y, X, w.pos_b, L});
     }
@@ -560,7 +656,14 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     for (int li = 0; li < nl; ++li) {
         const ddsp_hubert_layer& ly = w.layer[li];
         hub_gemm(st, math, X, HD, 0, ly.in_proj_w, HD, 0, (int)rows, 3 * HD, HD, 1, 1, gemm::EpiStore{qkv, 3 * HD, ly.in_proj_b, 1, 0, 0});
-        attention_launch(st, qkv, qkv + HD, qkv + 2 * HD, 3 * HD, cx, HD, B, L, HHEADS);
+        // RAGGED INVARIANT: the query rows >= L_b of cx keep what the arena held - possibly NaN or inf - and from here on so
+        // may those rows of Y, X and hh.  That is sound only because (1) every step below is row-wise (GEMM rows, LayerNorm),
+        // (2) the key loop stops at L_b, and (3) the returned rows >= L_b are written by SELECTION in hub_crop_kernel.  A crop
+        // that multiplies by a mask, or any new step that mixes rows, must first zero those rows of cx.
+        if (ragged)
+            attention_launch<true>(st, qkv, qkv + HD, qkv + 2 * HD, 3 * HD, cx, HD, B, L, HHEADS, cnt + 7, HCNT);
+        else
+            attention_launch<false>(st, qkv, qkv + HD, qkv + 2 * HD, 3 * HD, cx, HD, B, L, HHEADS);
         hub_gemm(st, math, cx, HD, 0, ly.out_proj_w, HD, 0, (int)rows, HD, HD, 1, 1, gemm::EpiResidual{Y, X, HD, ly.out_proj_b});
         hipLaunchKernelGGL(layernorm_kernel<HD>, dim3(ln_grid), dim3(256), 0, st, Y, nullptr, ly.norm1_w, ly.norm1_b, X, rows);
         hub_gemm(st, math, X, HD, 0, ly.linear1_w, HD, 0, (int)rows, HFF, HD, 1, 1, EpiGelu{hh, HFF, ly.linear1_b, 0});
@@ -568,9 +671,13 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
         hipLaunchKernelGGL(layernorm_kernel<HD>, dim3(ln_grid), dim3(256), 0, st, Y, nullptr, ly.norm2_w, ly.norm2_b, X, rows);
     }
     if (stop <= 12) {
-        DDSP_HIP(ctx, hipMemcpyAsync(out, X, (size_t)rows * HD * 4, hipMemcpyDeviceToDevice, st));
+        if (ragged)
+            crop(X, HD);
+        else
+            DDSP_HIP(ctx, hipMemcpyAsync(out, X, (size_t)rows * HD * 4, hipMemcpyDeviceToDevice, st));
     } else {
         hub_gemm(st, math, X, HD, 0, w.proj_w, HD, 0, (int)rows, HU, HD, 1, 1, gemm::EpiStore{out, HU, w.proj_b, 1, 0, 0});
+        if (ragged) crop(out, HU);
     }
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
@@ -604,7 +711,37 @@ extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* 
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     ddsp_prof_begin(ctx, st, PF_OTHER);
-    attention_launch(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads);
+    attention_launch<false>(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads);
+    ddsp_prof_end(ctx, st, 4.0 * B * heads * (double)L * L * HDH, 16.0 * B * L * heads * HDH);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_hubert_soft_units_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav,
+                                             int64_t B, int64_t T, const int32_t* n_samples, float* units) {
+    DDSP_REQUIRE(ctx, n_samples, "ddsp_hubert_soft_units_ragged: null n_samples");
+    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, 13, units, n_samples);
+}
+
+extern "C" int ddsp_hubert_encode_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
+                                         int64_t T, const int32_t* n_samples, int layer, float* out) {
+    DDSP_REQUIRE(ctx, n_samples, "ddsp_hubert_encode_ragged: null n_samples");
+    DDSP_REQUIRE(ctx, layer >= -1 && layer <= 12, "ddsp_hubert_encode_ragged: layer must be -1 (conv stack) or 0..12");
+    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out, n_samples);
+}
+
+extern "C" int ddsp_softmax_attention_ragged(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v,
+                                             int64_t B, int64_t L, int heads, float* out, int math, const int32_t* n_keys) {
+    DDSP_REQUIRE(ctx, ctx && q && k && v && out && n_keys, "ddsp_softmax_attention_ragged: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && L >= 0 && L < (1 << 30) && heads >= 1 && heads <= 4096, "ddsp_softmax_attention_ragged: bad shape");
+    DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16, "ddsp_softmax_attention_ragged: unknown math");
+    DDSP_REQUIRE(ctx, (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 16) == 0,
+                 "ddsp_softmax_attention_ragged: 16-byte aligned operands");
+    if (B == 0 || L == 0) return DDSP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    attention_launch<true>(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads, n_keys, 1);
     ddsp_prof_end(ctx, st, 4.0 * B * heads * (double)L * L * HDH, 16.0 * B * L * heads * HDH);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;

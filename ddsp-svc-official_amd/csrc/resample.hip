@@ -32,14 +32,28 @@ __global__ void __launch_bounds__(256) resample_taps_kernel(float* __restrict__ 
     taps[i] = (float)(s * c * c * (base / (double)orig));
 }
 
+// Ragged batch (ns != nullptr): row b holds ns[b] samples of its own (held inside 0..T); what follows them is never read
+// (the window stops at the row's end, as it does at T for a row resampled alone) and the outputs from
+// ceil(new * ns[b] / orig) on are written as 0.
+__device__ __forceinline__ int64_t row_samples(const int32_t* __restrict__ ns, int64_t b, int64_t T) {
+    if (!ns) return T;
+    const int64_t n = ns[b];
+    return n < 0 ? 0 : (n > T ? T : n);
+}
+
 __global__ void __launch_bounds__(256) resample_kernel(const float* __restrict__ x, const float* __restrict__ taps,
-                                                       int64_t T, int64_t T_out, int orig, int nw, int width, int K,
-                                                       int64_t total, float* __restrict__ out) {
+                                                       int64_t Tpad, int64_t T_out, int orig, int nw, int width, int K,
+                                                       int64_t total, float* __restrict__ out, const int32_t* __restrict__ ns) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / T_out, o = i - b * T_out;
         const int64_t l = o / nw;
         const int p = (int)(o - l * nw);
-        const float* xr = x + b * T;
+        const float* xr = x + b * Tpad;
+        const int64_t T = row_samples(ns, b, Tpad);
+        if (o >= (nw * T + orig - 1) / orig) {   // (never in a rectangular call)
+            out[i] = 0.f;
+            continue;
+        }
         const float* tp = taps + p;   // [k][phase]
         const int64_t first = l * orig - width;
         int k0 = first < 0 ? (int)(-first) : 0;
@@ -61,14 +75,16 @@ __global__ void __launch_bounds__(256) resample_kernel(const float* __restrict__
 
 constexpr int RS_RB = 8;   // input frames per thread
 __global__ void __launch_bounds__(256) resample_blocked_kernel(const float* __restrict__ x, const float* __restrict__ taps,
-                                                               int64_t T, int64_t T_out, int orig, int nw, int width, int K,
-                                                               float* __restrict__ out) {
+                                                               int64_t Tpad, int64_t T_out, int orig, int nw, int width, int K,
+                                                               float* __restrict__ out, const int32_t* __restrict__ ns) {
     extern __shared__ float win[];
     const int p = blockIdx.x * 256 + threadIdx.x;
     const int64_t l0 = (int64_t)blockIdx.y * RS_RB, b = blockIdx.z;
     const int wlen = (RS_RB - 1) * orig + K;
     const int64_t first = l0 * orig - width;
-    const float* xr = x + b * T;
+    const float* xr = x + b * Tpad;
+    const int64_t T = row_samples(ns, b, Tpad);
+    const int64_t T_row = ((int64_t)nw * T + orig - 1) / orig;   // the row's own outputs (T_out in a rectangular call)
     for (int i = threadIdx.x; i < wlen; i += 256) {
         const int64_t pos = first + i;
         win[i] = (pos >= 0 && pos < T) ? xr[pos] : 0.f;
@@ -96,7 +112,7 @@ __global__ void __launch_bounds__(256) resample_blocked_kernel(const float* __re
 #pragma unroll
     for (int r = 0; r < RS_RB; ++r) {
         const int64_t o = (l0 + r) * nw + p;
-        if (o < T_out) out[b * T_out + o] = acc[r][0] + acc[r][1];
+        if (o < T_out) out[b * T_out + o] = o < T_row ? acc[r][0] + acc[r][1] : 0.f;
     }
 }
 
@@ -125,23 +141,26 @@ extern "C" int64_t ddsp_resample_length(int64_t T, int orig_freq, int new_freq) 
     return (n * T + o - 1) / o;
 }
 
-extern "C" int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
-                             int lowpass_filter_width, float* out) {
-    DDSP_REQUIRE(ctx, ctx && x && out, "ddsp_resample: null argument");
+static int resample_run(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
+                        int lowpass_filter_width, float* out, const int32_t* ns) {
+    // (the messages name the entry point that was called)
+#define RS_MSG(text) (ns ? "ddsp_resample_ragged: " text : "ddsp_resample: " text)
+    DDSP_REQUIRE(ctx, ctx && x && out, RS_MSG("null argument"));
     DDSP_REQUIRE(ctx, B >= 0 && T >= 1 && orig_freq >= 1 && new_freq >= 1 && lowpass_filter_width >= 1 &&
                           lowpass_filter_width <= 4096,
-                 "ddsp_resample: bad argument");
+                 RS_MSG("bad argument"));
     if (B == 0) return DDSP_OK;
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const int g = gcd_int(orig_freq, new_freq);
     const int orig = orig_freq / g, nw = new_freq / g;
-    DDSP_REQUIRE(ctx, orig < 65536 && nw < 65536, "ddsp_resample: rate ratio too fine (reduced rates must be < 65536)");
+    DDSP_REQUIRE(ctx, orig < 65536 && nw < 65536, RS_MSG("rate ratio too fine (reduced rates must be < 65536)"));
     const double rolloff = 0.99;
     const double base = (double)(orig < nw ? orig : nw) * rolloff;
     const int width = (int)ceil((double)lowpass_filter_width * (double)orig / base);
     const int K = 2 * width + orig;
-    DDSP_REQUIRE(ctx, (int64_t)nw * K < (1 << 28), "ddsp_resample: tap table too large");
+    DDSP_REQUIRE(ctx, (int64_t)nw * K < (1 << 28), RS_MSG("tap table too large"));
+#undef RS_MSG
     float* taps = nullptr;
     const int key0 = orig, key1 = nw * 8192 + lowpass_filter_width;
     const uint64_t now = ++ctx->table_clock;
@@ -187,11 +206,22 @@ extern "C" int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_
     const int64_t n_frames = (T_out + nw - 1) / nw;
     if (lds <= 64 * 1024 && B < 65536 && (n_frames + RS_RB - 1) / RS_RB < 65536)
         hipLaunchKernelGGL(resample_blocked_kernel, dim3((unsigned)((nw + 255) / 256), (unsigned)((n_frames + RS_RB - 1) / RS_RB), (unsigned)B),
-                           dim3(256), lds, st, x, taps, T, T_out, orig, nw, width, K, out);
+                           dim3(256), lds, st, x, taps, T, T_out, orig, nw, width, K, out, ns);
     else
         hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, taps, T, T_out, orig, nw, width, K, total,
-                           out);
+                           out, ns);
     ddsp_prof_end(ctx, st, 2.0 * total * K, 4.0 * (B * T + total));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
+                             int lowpass_filter_width, float* out) {
+    return resample_run(ctx, stream, x, B, T, orig_freq, new_freq, lowpass_filter_width, out, nullptr);
+}
+
+extern "C" int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples,
+                                    int orig_freq, int new_freq, int lowpass_filter_width, float* out) {
+    DDSP_REQUIRE(ctx, n_samples, "ddsp_resample_ragged: null n_samples");
+    return resample_run(ctx, stream, x, B, T, orig_freq, new_freq, lowpass_filter_width, out, n_samples);
 }

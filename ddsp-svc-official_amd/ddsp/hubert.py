@@ -26,6 +26,15 @@ def n_frames(T):
     return n
 
 
+class RaggedCounts:
+    """Checked per-row sample counts of a ragged batch together with their (B,) int32 device tensor (`HubertSoft.counts`):
+    pass it as `n_samples=` to skip the host check and the upload, e.g. inside a HIP graph capture, where nothing may be
+    uploaded.  The caller keeps it alive as long as a captured graph reads it."""
+
+    def __init__(self, values, T, dev_tensor):
+        self.values, self.T, self.dev = list(values), int(T), dev_tensor
+
+
 class _WeightNormConv(nn.Module):
     """`positional_embedding.conv` after `weight_norm(dim=2)`: its keys are `bias`, `weight_g`, `weight_v`."""
 
@@ -150,22 +159,49 @@ class HubertSoft(nn.Module):
         n_frames(wav.shape[-1])
         return wav[:, 0].contiguous().float()
 
-    @torch.no_grad()
-    def units(self, wav):
-        """:: (B, 1, T) 16 kHz -> (B, Frame, 256)"""
-        x = self._wav(wav)
-        return hipddsp.context_for(x.device).hubert_units(self._weights_struct(), x)
+    @staticmethod
+    def counts(n_samples, B, T, device):
+        """`n_samples` of a ragged (B, 1, T) batch, checked on the host and uploaded once -> `RaggedCounts`."""
+        vals = hipddsp.check_hubert_n_samples(n_samples, B, T)
+        return RaggedCounts(vals, T, hipddsp.context_for(device).ragged_counts(vals))
+
+    @staticmethod
+    def _counts(wav, n_samples):
+        """`n_samples` checked on the host (ValueError before anything is launched) -> its (B,) int32 device tensor, or None."""
+        if n_samples is None:
+            return None
+        if wav.dim() != 3 or wav.shape[1] != 1:
+            raise ValueError("HubertSoft: wav must be (B, 1, T)")
+        if isinstance(n_samples, RaggedCounts):
+            if len(n_samples.values) != wav.shape[0] or n_samples.T != wav.shape[-1] or n_samples.dev.device != wav.device:
+                raise ValueError("HubertSoft: these RaggedCounts were made for another batch shape or device")
+            return n_samples.dev
+        vals = hipddsp.check_hubert_n_samples(n_samples, wav.shape[0], wav.shape[-1])
+        if not wav.is_cuda:
+            raise RuntimeError("HubertSoft runs on a HIP device only (no CPU fallback)")
+        return hipddsp.context_for(wav.device).ragged_counts(vals)
 
     @torch.no_grad()
-    def encode(self, wav, layer=None):
+    def units(self, wav, n_samples=None):
+        """:: (B, 1, T) 16 kHz -> (B, Frame, 256).  `n_samples` (a sequence of B ints or a CPU integer tensor (B,), 1 <=
+        n_samples[b] <= T, each long enough for the conv stack): a RAGGED batch.  Row b is then, over its own
+        `n_frames(n_samples[b])` frames, what `units(wav[b:b+1, :, :n_samples[b]])` returns, and exactly 0 after them; the
+        samples past a row's count may hold anything (they are replaced by selection, never multiplied by a mask)."""
+        n_dev = self._counts(wav, n_samples)
+        x = self._wav(wav)
+        return hipddsp.context_for(x.device).hubert_units(self._weights_struct(), x, n_dev)
+
+    @torch.no_grad()
+    def encode(self, wav, layer=None, n_samples=None):
         """:: (B, 1, T) -> the hidden state (B, Frame, 768) after `layer` transformer layers (all 12 when None), or the conv
         stack's output (B, Frame, 512) for layer=-1.  Unlike the reference's `encode`, the audio is padded here as `units`
-        pads it, and no mask is returned."""
-        x = self._wav(wav)
+        pads it, and no mask is returned.  `n_samples`: ragged batch, as in `units`."""
         layer = 12 if layer is None else int(layer)
         if not -1 <= layer <= 12:
             raise ValueError("HubertSoft.encode: layer in -1..12")
-        return hipddsp.context_for(x.device).hubert_encode(self._weights_struct(), x, layer)
+        n_dev = self._counts(wav, n_samples)
+        x = self._wav(wav)
+        return hipddsp.context_for(x.device).hubert_encode(self._weights_struct(), x, layer, n_dev)
 
-    def forward(self, wav):
-        return self.units(wav)
+    def forward(self, wav, n_samples=None):
+        return self.units(wav, n_samples)

@@ -29,6 +29,7 @@ from hipddsp import (COMB_SINC, COMB_SINC_GATED, COMB_NONE, EXC_AUDIO, EXC_GENER
 # work from the saved inputs in fp32 products): the context's mode (`hipddsp.Context.set_math`, default split-bf16);
 # `ctx.ltv_fir` itself defaults to fp32 products.
 
+from .hubert import RaggedCounts
 from .unit2control import Unit2Control
 
 
@@ -181,9 +182,9 @@ class Audio2HubertSoft(torch.nn.Module):
         if device is not None:
             self.hubert.to(device)
 
-    def forward(self, audio):
-        """ :: (B, T) -> (B, 1, T) -> (B, Frame, Feat=256) """
-        return self.hubert.units(audio.unsqueeze(1))
+    def forward(self, audio, n_samples=None):
+        """ :: (B, T) -> (B, 1, T) -> (B, Frame, Feat=256); `n_samples`: ragged batch (`HubertSoft.units`) """
+        return self.hubert.units(audio.unsqueeze(1), n_samples)
 
 
 class Units_Encoder:
@@ -214,9 +215,15 @@ class Units_Encoder:
         self.encoder_sample_rate = encoder_sample_rate
         self.encoder_hop_size = encoder_hop_size
 
-    def encode(self, audio, sample_rate, hop_size):
+    def encode(self, audio, sample_rate, hop_size, n_samples=None):
         """audio (B,T) at `sample_rate` -> units (B, int(T // hop_size) + 1, 256) aligned to frames of `hop_size` samples
-        (a float hop keeps its fraction, like the reference's)."""
+        (a float hop keeps its fraction, like the reference's).
+        `n_samples` (a sequence of B ints or a CPU integer tensor (B,), counts at `sample_rate`): a RAGGED batch.  Row b is
+        encoded as audio[b, :n_samples[b]] alone - resampling, encoder and alignment each stop at the row's own end, and
+        what follows a row's samples may hold anything.  Returns (B, int(max(n_samples) // hop_size) + 1, 256); row b
+        carries int(n_samples[b] // hop_size) + 1 frames and zeros after them."""
+        if n_samples is not None:
+            return self._encode_ragged(audio, sample_rate, hop_size, n_samples)
         if not audio.is_cuda:
             raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
         ctx = hipddsp.context_for(audio.device)
@@ -224,6 +231,30 @@ class Units_Encoder:
             ctx.resample(audio, int(sample_rate), int(self.encoder_sample_rate), lowpass_filter_width=128)
         units = self.model(audio_res)
         return align_units(units, audio.size(-1), sample_rate, hop_size, self.encoder_sample_rate, self.encoder_hop_size)
+
+    def _encode_ragged(self, audio, sample_rate, hop_size, n_samples):
+        if audio.dim() != 2:
+            raise ValueError("Units_Encoder.encode: a ragged batch is (B, T) audio")
+        B, T = audio.shape
+        vals = hipddsp.check_n_samples(n_samples, B, T)
+        resampled = sample_rate != self.encoder_sample_rate
+        lib = hipddsp.load_library()
+        n16 = [int(lib.ddsp_resample_length(v, int(sample_rate), int(self.encoder_sample_rate))) for v in vals] \
+            if resampled else vals
+        T16 = int(lib.ddsp_resample_length(T, int(sample_rate), int(self.encoder_sample_rate))) if resampled else T
+        n16 = hipddsp.check_hubert_n_samples(n16, B, T16)     # (before any launch)
+        if not audio.is_cuda:
+            raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
+        ctx = hipddsp.context_for(audio.device)
+        n_units = [hipddsp.hubert_frames(v) for v in n16]
+        n_out = [int(v // hop_size) + 1 for v in vals]
+        # one upload for the four count vectors
+        dev = ctx.ragged_counts(vals + n16 + n_units + n_out).reshape(4, B)
+        audio_res = ctx.resample_ragged(audio, dev[0], int(sample_rate), int(self.encoder_sample_rate),
+                                        lowpass_filter_width=128) if resampled else audio
+        units = self.model(audio_res, RaggedCounts(n16, T16, dev[1]))
+        ratio = (hop_size / sample_rate) / (self.encoder_hop_size / self.encoder_sample_rate)
+        return ctx.align_units_ragged(units, max(n_out), ratio, dev[2], dev[3])
 
 
 class DotDict(dict):

@@ -197,6 +197,11 @@ SIGNATURES = {
     "ddsp_hubert_soft_units": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp]),
     "ddsp_hubert_encode": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _int, _vp]),
     "ddsp_softmax_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int]),
+    "ddsp_hubert_soft_units_ragged": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _vp]),
+    "ddsp_hubert_encode_ragged": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _int, _vp]),
+    "ddsp_softmax_attention_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp]),
+    "ddsp_resample_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _int, _vp]),
+    "ddsp_align_units_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
     "ddsp_crepe_frames": (_i64, [_i64, _int]),
     "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _int, _vp]),
     "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
@@ -249,29 +254,55 @@ def load_library():
     return _lib
 
 
+def _check_counts(name, counts, B):
+    """A ragged batch's per-row counts as a list of B Python ints (a host check; the callers check the range)."""
+    if isinstance(counts, torch.Tensor):
+        if counts.is_cuda:
+            raise ValueError(f"{name} must be a CPU tensor or a sequence of ints (it is checked on the host)")
+        if counts.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or counts.dim() != 1:
+            raise ValueError(f"{name} must be an integer tensor of shape (B,), got {counts.dtype} {tuple(counts.shape)}")
+        vals = counts.tolist()
+    else:
+        try:
+            vals = list(counts)
+        except TypeError:
+            raise ValueError(f"{name} must be a sequence of B ints or a CPU integer tensor of shape (B,)") from None
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError(f"{name} must hold ints, got {type(v).__name__} {v!r}")
+        vals = [int(v) for v in vals]
+    if len(vals) != int(B):
+        raise ValueError(f"{name} must hold B={int(B)} counts, got {len(vals)}")
+    return vals
+
+
 def check_n_frames(n_frames, B, Fr):
     """The per-row frame counts of a ragged batch as a list of B Python ints, 1 <= n <= Fr; anything else raises ValueError
     (a host check: nothing is launched).  Accepted: a sequence of ints, or a CPU integer tensor of shape (B,)."""
-    if isinstance(n_frames, torch.Tensor):
-        if n_frames.is_cuda:
-            raise ValueError("n_frames must be a CPU tensor or a sequence of ints (it is checked on the host)")
-        if n_frames.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or n_frames.dim() != 1:
-            raise ValueError(f"n_frames must be an integer tensor of shape (B,), got {n_frames.dtype} {tuple(n_frames.shape)}")
-        vals = n_frames.tolist()
-    else:
-        try:
-            vals = list(n_frames)
-        except TypeError:
-            raise ValueError("n_frames must be a sequence of B ints or a CPU integer tensor of shape (B,)") from None
-        for v in vals:
-            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-                raise ValueError(f"n_frames must hold ints, got {type(v).__name__} {v!r}")
-        vals = [int(v) for v in vals]
-    if len(vals) != int(B):
-        raise ValueError(f"n_frames must hold B={int(B)} counts, got {len(vals)}")
+    vals = _check_counts("n_frames", n_frames, B)
     for b, v in enumerate(vals):
         if not 1 <= v <= int(Fr):
             raise ValueError(f"n_frames[{b}] = {v} is outside 1..Fr={int(Fr)}")
+    return vals
+
+
+def check_n_samples(n_samples, B, T):
+    """The per-row sample counts of a ragged batch of audio (B, T) as a list of B Python ints, 1 <= n <= T; anything else
+    raises ValueError (a host check: nothing is launched).  Accepted: what `check_n_frames` accepts."""
+    vals = _check_counts("n_samples", n_samples, B)
+    for b, v in enumerate(vals):
+        if not 1 <= v <= int(T):
+            raise ValueError(f"n_samples[{b}] = {v} is outside 1..T={int(T)}")
+    return vals
+
+
+def check_hubert_n_samples(n_samples, B, T):
+    """`check_n_samples` for the units encoder: every row must also be long enough for the conv stack
+    (`hubert_frames(n) >= 1`)."""
+    vals = check_n_samples(n_samples, B, T)
+    for b, v in enumerate(vals):
+        if hubert_frames(v) < 1:
+            raise ValueError(f"n_samples[{b}] = {v} samples are too short for the conv stack")
     return vals
 
 
@@ -615,6 +646,18 @@ class Context:
         self.call("ddsp_align_units", _ptr(units), B, Lu, C, int(n_frames), float(ratio), _ptr(out))
         return out
 
+    def align_units_ragged(self, units, n_frames, ratio, n_units_dev, n_out_dev):
+        """`align_units` of a ragged batch: row b gathers its own n_out[b] frames from its own n_units[b] unit rows and is 0
+        after them; both counts are (B,) int32 device tensors (`ragged_counts`)."""
+        units = units.contiguous().float()
+        B, Lu, C = units.shape
+        out = torch.empty(B, int(n_frames), C, device=units.device, dtype=torch.float32)
+        if B == 0 or int(n_frames) == 0:
+            return out
+        self.call("ddsp_align_units_ragged", _ptr(units), B, Lu, C, int(n_frames), float(ratio), _ptr(n_units_dev),
+                  _ptr(n_out_dev), _ptr(out))
+        return out
+
     def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst):
         """f0 (n,) device track -> (n_dst,): numpy.interp(i * step_dst; knots (step_num * j) / div, values fl32(f0 * scale)),
         end values held (enhancer.py:56-62), without leaving the device."""
@@ -637,6 +680,21 @@ class Context:
         if B and T:
             self.call("ddsp_resample", _ptr(x), B, T, int(orig_freq), int(new_freq), int(lowpass_filter_width), _ptr(out))
         return out[0] if flat else out
+
+    def resample_ragged(self, audio, n_dev, orig_freq, new_freq, lowpass_filter_width=6):
+        """`resample` of a ragged batch (B,T): n_dev is the (B,) int32 device tensor of the rows' own sample counts
+        (`ragged_counts`); what follows a row's samples is never read into arithmetic, and its outputs from
+        ceil(n_b * new / orig) on are 0."""
+        x = audio.contiguous().float()
+        B, T = x.shape
+        T_out = self.lib.ddsp_resample_length(T, int(orig_freq), int(new_freq))
+        if T_out < 0:
+            raise ValueError("resample: bad rates")
+        out = torch.empty(B, T_out, device=x.device, dtype=torch.float32)
+        if B and T:
+            self.call("ddsp_resample_ragged", _ptr(x), B, T, _ptr(n_dev), int(orig_freq), int(new_freq),
+                      int(lowpass_filter_width), _ptr(out))
+        return out
 
     # -- SURVEY 8(f) rank 1: NSF-HiFiGAN post-net building blocks --------------------------------
     def conv1d(self, x, w_packed, bias, ktaps, dil, in_slope, residual=None, want_out=True, act_slope=None, w_split=None,
@@ -770,29 +828,47 @@ class Context:
         self.call("ddsp_softmax_attention", _ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math))
         return out
 
+    def softmax_attention_ragged(self, q, k, v, B, L, heads, n_keys_dev, math=MATH_SPLIT_BF16, out=None):
+        """`softmax_attention` in which utterance b attends over its first n_keys[b] rows only ((B,) int32 device tensor);
+        only those rows of `out` (given, or new and uninitialised) are written."""
+        if out is None:
+            out = torch.empty(B * L, heads * 64, device=q.device, dtype=torch.float32)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B * L, heads * 64):
+            raise ValueError("softmax_attention_ragged: `out` must be fp32 (B*L, heads*64)")
+        self.call("ddsp_softmax_attention_ragged", _ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math),
+                  _ptr(n_keys_dev))
+        return out
+
     # -- units encoder -------------------------------------------------------------------------
-    def hubert_units(self, weights, wav):
-        """weights: a HubertWeights struct; wav (B,T) 16 kHz fp32 -> units (B, Fr, 256)."""
+    def hubert_units(self, weights, wav, n_dev=None):
+        """weights: a HubertWeights struct; wav (B,T) 16 kHz fp32 -> units (B, Fr, 256).  n_dev: the (B,) int32 device tensor
+        of a ragged batch's sample counts (`ragged_counts` of `check_hubert_n_samples`): every row as if encoded alone, 0
+        after its own frames."""
         B, T = wav.shape
         Fr = hubert_frames(T)
         if Fr <= 0:
             raise ValueError(f"hubert: {T} samples are too short for the conv stack")
         wav = wav.contiguous().float()
         out = torch.empty(B, Fr, 256, device=wav.device, dtype=torch.float32)
-        if B:
+        if B and n_dev is not None:
+            self.call("ddsp_hubert_soft_units_ragged", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), _ptr(out))
+        elif B:
             self.call("ddsp_hubert_soft_units", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(out))
         return out
 
-    def hubert_encode(self, weights, wav, layer):
+    def hubert_encode(self, weights, wav, layer, n_dev=None):
         """The conv stack's output (B, Fr, 512) for layer -1, else the hidden state (B, Fr, 768) after `layer` of the 12
-        transformer layers."""
+        transformer layers.  n_dev: as in `hubert_units`."""
         B, T = wav.shape
         Fr = hubert_frames(T)
         if Fr <= 0:
             raise ValueError(f"hubert: {T} samples are too short for the conv stack")
         wav = wav.contiguous().float()
         out = torch.empty(B, Fr, 512 if layer == -1 else 768, device=wav.device, dtype=torch.float32)
-        if B:
+        if B and n_dev is not None:
+            self.call("ddsp_hubert_encode_ragged", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), int(layer),
+                      _ptr(out))
+        elif B:
             self.call("ddsp_hubert_encode", ctypes.byref(weights), _ptr(wav), int(B), int(T), int(layer), _ptr(out))
         return out
 

@@ -68,6 +68,19 @@ def _render_ragged(model, segments, f0, volume, spk_id, spk_mix_dict, noise_seed
     return rendered
 
 
+def _encode_ragged(units_encoder, pieces, sample_rate, hop_size, units_batch_samples):
+    """pieces: [(start_frame, audio (1, n))] -> [(start_frame, units (1, int(n // hop_size) + 1, n_unit))] in the same order,
+    from one ragged `Units_Encoder.encode` per group of `group_segments` over the sample lengths."""
+    lengths = [seg.shape[-1] for _, seg in pieces]
+    out = [None] * len(pieces)
+    for group in group_segments(lengths, int(units_batch_samples)):
+        wav, counts = stack_rows([pieces[i][1][0] for i in group])
+        units = units_encoder.encode(wav, sample_rate, hop_size, n_samples=counts)
+        for j, i in enumerate(group):
+            out[i] = (pieces[i][0], units[j:j + 1, :int(counts[j] // hop_size) + 1].clone())
+    return out
+
+
 @torch.no_grad()
 def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, threshold_db=-60, enhancer=None,
            enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None):
@@ -132,11 +145,14 @@ def convert(model, args, audio, sample_rate, slices, units_encoder, f0_extractor
 
 @torch.no_grad()
 def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, batch_frames, key=0,
-                    spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None):
+                    spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
+                    units_batch_samples=None):
     """`convert` with `render`'s `batch_frames`: the slices are rendered in ragged batches of at most that many padded frames
-    (None: slice after slice, which is `convert`).  The units are still encoded slice by slice, the enhancer still runs per
-    slice.  (A function of its own and not a keyword of `convert`: tests/test_stream_audio_host.py pins `convert`'s
-    parameter list.)"""
+    (None: slice after slice, which is `convert`).  `units_batch_samples`: None encodes the units slice by slice; a number
+    encodes them in ragged groups too (`Units_Encoder.encode(..., n_samples=)`), `group_segments` over the slices' sample
+    lengths with at most that many padded samples (at `sample_rate`) per group, every slice as if encoded alone.  The
+    enhancer still runs per slice.  (A function of its own and not a keyword of `convert`:
+    tests/test_stream_audio_host.py pins `convert`'s parameter list.)"""
     hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
     if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
         raise ValueError(f"convert: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop {f0_extractor.hop_size}; "
@@ -154,6 +170,9 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
         start_frame, end_frame = int(int(start) // hop_size), int(int(end) // hop_size)
         if end_frame > start_frame:
             seg = x[None, int(start_frame * hop_size):int(end_frame * hop_size)]
-            segments.append((start_frame, units_encoder.encode(seg, sample_rate, hop_size)))
+            segments.append((start_frame, seg if units_batch_samples is not None else
+                             units_encoder.encode(seg, sample_rate, hop_size)))
+    if units_batch_samples is not None:
+        segments = _encode_ragged(units_encoder, segments, sample_rate, hop_size, units_batch_samples)
     return render(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
                   enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames)

@@ -315,6 +315,11 @@ int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, in
  * round half to even (torch.round); units (B,Lu,C) -> out (B,n_frames,C). */
 int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
                      int64_t n_frames, float ratio, float* out);
+/* ddsp_align_units over a ragged batch: row b has n_out[b] <= n_frames frames of its own, taken from its own n_units[b] <= Lu
+ * unit rows (j = min(rint(ratio * i), n_units[b] - 1)), and exact zeros from frame n_out[b] on.  n_units, n_out: DEVICE arrays
+ * of B int32. */
+int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
+                            int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out);
 
 /* replaces the host-side f0 re-timing of enhancer.py:56-62 (`f0_np *= real_factor`; `np.interp(time_frame, time_org, f0_np,
  * left=f0_np[0], right=f0_np[-1])`): out[i] = interp(i * step_dst) over the knots x_j = (step_num * j) / div with values
@@ -330,6 +335,11 @@ int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, 
 int64_t ddsp_resample_length(int64_t T, int orig_freq, int new_freq);
 int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
                   int lowpass_filter_width, float* out);
+/* ddsp_resample over a ragged batch: n_samples is a DEVICE array of B int32, row b holds n_samples[b] <= T samples of its
+ * own.  x[b][i] is selected as 0 for i >= n_samples[b] where it is loaded (the padding may hold anything), so the row's
+ * first ddsp_resample_length(n_samples[b], ...) outputs are those of the row resampled alone; the outputs after them are 0. */
+int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples,
+                         int orig_freq, int new_freq, int lowpass_filter_width, float* out);
 
 /* ---- the NSF-HiFiGAN post-net (enhancer.py:24-101, nsf_hifigan/models.py:106-276, nvSTFT.py:65-119) ---- */
 /* One utterance per call; activations frame-major (T, C) fp32.
@@ -471,6 +481,25 @@ int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w
  * unit tests. */
 int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B, int64_t L,
                            int heads, float* out, int math);
+
+/* ---- the units encoder over a ragged batch (inference only, like the encoder) ---------------------------------------------
+ * n_samples: DEVICE array of B int32, the 16 kHz samples of each row inside the padded (B, T) wav; the caller checks
+ * 1 <= n_samples[b] <= T and ddsp_hubert_frames(n_samples[b]) >= 1 (the kernels hold a count inside 0..T).  The per-row frame
+ * counts are derived on the device and nothing is read back, so the call can be captured like the rectangular one.
+ * Row b of the result is, over its own ddsp_hubert_frames(n_samples[b]) frames, what the rectangular call returns for
+ * wav[b][:n_samples[b]] alone, and exactly 0 after them.  wav[b][i] for i >= n_samples[b] may hold anything (NaN included): it
+ * is replaced by selection where it is loaded.  Every place that looks across frames stops at the row's own end: conv0's
+ * zero padding, the GroupNorm statistics (partitioned and divided as for the row alone), the zero edge of the positional
+ * convolution, the keys of the softmax attention.  The GEMMs run over all B * Fr padded rows.  `units` / `out` must be
+ * 16-byte aligned (DDSP_ERR_ARG otherwise). */
+int ddsp_hubert_soft_units_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
+                                  int64_t T, const int32_t* n_samples, float* units);
+int ddsp_hubert_encode_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
+                              const int32_t* n_samples, int layer, float* out);
+/* ddsp_softmax_attention with a per-utterance key count: n_keys is a DEVICE array of B int32 (held inside 0..L); utterance b
+ * attends over its first n_keys[b] rows, which are also the only rows of `out` that are written. */
+int ddsp_softmax_attention_ragged(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
+                                  int64_t L, int heads, float* out, int math, const int32_t* n_keys);
 
 /* ---- the f0 extractor (CREPE, ddsp/vocoder.py:39-113 with torchcrepe.predict and librosa's Viterbi restated) ---------- */
 /* Device pointers into a CREPE state dict (torchcrepe's keys), fp32, dense: conv_w[i] = `conv{i+1}.weight` (Cout, Cin, k, 1),
