@@ -388,10 +388,9 @@ __global__ void __launch_bounds__(64 * NW) kernel(Args g, Epi epi) {
 // N = 256 layers, whose 128-row tilings leave a third of the CUs without work).
 // MATH: 0 = fp32 MFMA; 3 = split-bf16 (Args::math == 3: the inference GEMMs): each fp32 operand is split into bf16 hi and
 // lo pieces in registers and the product formed from 3 bf16 MFMAs (32x32x16: hi*hi + hi*lo + lo*hi) with fp32 accumulation;
-// 7 = the same with B read already split (Args::B_split); 8 = A and B both already split (Args::A_split); 6 = three pieces,
-// 6 MFMAs (ddsp_gemm_f32 tile 31 only).
+// 7 = the same with B read already split (Args::B_split); 8 = A and B both already split (Args::A_split).
 // Speed and error: DESIGN.md section 9.
-template <int BM, int BN, class Epi, int NS = 3, int ABLATE = 0, int NW = 8, int A_MODE = A_PLAIN, int MATH = 0>  // ABLATE bit mask (timing experiments only): 1 no MFMA, 2 no DMA, 4 no epilogue stores, 8 no barrier
+template <int BM, int BN, class Epi, int NS = 3, int NW = 8, int A_MODE = A_PLAIN, int MATH = 0>
 __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ? 4 : 2)) kernel_dma(Args g, Epi epi, int tiles_m, int tiles_n, int total_tiles) {
     constexpr int WGM = NW / 2, WGN = 2;
     constexpr int TM = BM / (32 * WGM), TN = BN / (32 * WGN);
@@ -517,7 +516,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
     if (steps > 0) tile_src(tile_of(0), src_cur);
     auto issue_next = [&]() {
         if (issued >= steps) return;
-        if (!(ABLATE & 2)) issue(src_cur, issue_kt, issued % NS);
+        issue(src_cur, issue_kt, issued % NS);
         ++issued;
         if (++issue_kt == nk) {
             issue_kt = 0;
@@ -547,7 +546,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // ... and every other wave says the same; the barrier also fences the reads of stage (step+2)%3 (step-1)
-        if (!(ABLATE & 8)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         issue_next();  // step + 2
         const float* st = lds + (step % NS) * STAGE;
         f32x4 av[TM][4], bv[TN][4];
@@ -565,13 +564,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
 #pragma unroll
             for (int c = 0; c < 4; ++c) bv[j][c] = *(const f32x4*)(rp + 4 * ((4 * lh + c) ^ ((row >> 1) & 7)));
         }
-        if (ABLATE & 1) {
-            // keep the operand reads alive without the matrix pipe
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j][0] += av[i][0][0] + bv[j][3][3];
-        } else if constexpr (MATH != 0) {
+        if constexpr (MATH != 0) {
             // split-bf16 experiment: the lane's 16 k-values form two K=16 steps of 8 values per lane half; A and B use the
             // same (half, element) slots, so whatever k order the instruction assigns to them the pairs match
             typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -580,8 +573,11 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
             typedef float f32x2p __attribute__((ext_vector_type(2)));
             typedef __bf16 bf16x2p __attribute__((ext_vector_type(2)));
             typedef uint32_t u32x4p __attribute__((ext_vector_type(4)));
+            // (two pieces, hi and lo.  The arrays keep the extent 3 of the retired three-piece form, the last slot unused: the
+            // compiler's register allocation follows the extent - with [2] most of the split instantiations come out with
+            // other schedules and several with 4..8 more VGPRs)
             auto split = [](const f32x4& x0, const f32x4& x1, bf16x8 (&p)[3]) {
-                constexpr int NQ = MATH == 6 ? 3 : 2;
+                constexpr int NQ = 2;
                 u32x4p w[3];
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
@@ -625,11 +621,6 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
                         auto mm = [&](int x, int y) {
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[i][x], bp[j][y], acc[i][j], 0, 0, 0);
                         };
-                        if constexpr (MATH == 6) {      // smallest terms first
-                            mm(2, 0);
-                            mm(0, 2);
-                            mm(1, 1);
-                        }
                         mm(1, 0);
                         mm(0, 1);
                         mm(0, 0);
@@ -700,11 +691,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
                                 float x[4] = {acc[i][j][4 * rg], acc[i][j][4 * rg + 1], acc[i][j][4 * rg + 2], acc[i][j][4 * rg + 3]};
                                 quad_transpose(x, q);
                                 const int m = m0 + wm + 32 * i + q + 8 * rg + 4 * lh;
-                                if constexpr ((ABLATE & 4) != 0) {
-                                    if (x[0] == 12345.678f) epi.store4(z, m, n, f32x4{x[0], x[1], x[2], x[3]});
-                                } else {
-                                    if (m < g.M) epi.store4(z, m, n, f32x4{x[0], x[1], x[2], x[3]});
-                                }
+                                if (m < g.M) epi.store4(z, m, n, f32x4{x[0], x[1], x[2], x[3]});
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) acc[i][j][4 * rg + r] = 0.f;
                             }
@@ -726,8 +713,6 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
                         } else if constexpr (epi_wants_pair<Epi>::value) {
                             const float other = __shfl_xor(acc[i][j][r], 1, 64);
                             if (n_ok && m < g.M) epi(z, m, n, acc[i][j][r], other);
-                        } else if constexpr ((ABLATE & 4) != 0) {
-                            if (acc[i][j][r] == 12345.678f) epi(z, m, n, acc[i][j][r], cb);
                         } else {
                             if (n_ok && m < g.M) epi(z, m, n, acc[i][j][r], cb);
                         }
@@ -745,7 +730,7 @@ inline bool dma_ok(const Args& g) {
            g.sA_hi % 4 == 0 && g.sA_lo % 4 == 0 && g.sB_hi % 4 == 0 && g.sB_lo % 4 == 0;
 }
 
-template <int BM, int BN, class Epi, int NS = 3, int ABLATE = 0, int NW = 8, int A_MODE = A_PLAIN, int MATH = 0>
+template <int BM, int BN, class Epi, int NS = 3, int NW = 8, int A_MODE = A_PLAIN, int MATH = 0>
 inline void launch_dma(hipStream_t st, const Args& g, int batch, const Epi& epi, int total_override = -1) {
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
     const int total = total_override >= 0 ? total_override : tiles_m * tiles_n * batch;
@@ -757,7 +742,7 @@ inline void launch_dma(hipStream_t st, const Args& g, int batch, const Epi& epi,
     constexpr int per_cu = by_lds < by_waves ? by_lds : by_waves;
     int grid = 256 * per_cu;
     if (grid > total) grid = total;
-    hipLaunchKernelGGL((kernel_dma<BM, BN, Epi, NS, ABLATE, NW, A_MODE, MATH>), dim3(grid), dim3(64 * NW), 0, st, g, epi, tiles_m, tiles_n, total);
+    hipLaunchKernelGGL((kernel_dma<BM, BN, Epi, NS, NW, A_MODE, MATH>), dim3(grid), dim3(64 * NW), 0, st, g, epi, tiles_m, tiles_n, total);
 }
 
 // launch_dma with the product arithmetic chosen at run time (Args::math)
@@ -773,15 +758,15 @@ inline void dma_go(hipStream_t st, const Args& g0, int batch, const Epi& epi, in
     if (g.math == 3 && g.B_split && g.A_split) {
         Args h = g;
         h.B = g.B_split;
-        launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 8>(st, h, batch, epi, total_override);
+        launch_dma<BM, BN, Epi, NS, NW, A_MODE, 8>(st, h, batch, epi, total_override);
     } else if (g.math == 3 && g.B_split) {
         Args h = g;
         h.B = g.B_split;
-        launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 7>(st, h, batch, epi, total_override);
+        launch_dma<BM, BN, Epi, NS, NW, A_MODE, 7>(st, h, batch, epi, total_override);
     } else if (g.math == 3)
-        launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 3>(st, g, batch, epi, total_override);
+        launch_dma<BM, BN, Epi, NS, NW, A_MODE, 3>(st, g, batch, epi, total_override);
     else
-        launch_dma<BM, BN, Epi, NS, 0, NW, A_MODE, 0>(st, g, batch, epi, total_override);
+        launch_dma<BM, BN, Epi, NS, NW, A_MODE, 0>(st, g, batch, epi, total_override);
 }
 
 template <int BM, int BN, bool A_KC, bool B_KC, int A_MODE, class Epi, int NW = 4>

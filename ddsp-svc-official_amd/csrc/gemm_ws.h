@@ -1,10 +1,10 @@
 // Wave-specialised LDS-DMA GEMM for gfx950 (round 3): C = epilogue(A B^T), row-major A (M x K), nn.Linear-layout B (N x K),
 // K % 32 == 0, K >= 256, 16-byte aligned rows - the Linear / 1x1-conv layers of the control network at large batches.
 //
-// Why a second kernel beside gemm::kernel_dma (gemm_f32.h): the round-2 ablation of that kernel at the QKV shape
-// (M = 11008, N = 1536, K = 256, split-bf16 products) gave 40 us whole and ~30 us with the operand DMA, the matrix
-// instructions or the epilogue stores removed - three ~10 us phases that every wave runs one after the other.  Two
-// structural reasons, both removed here:
+// Why a second kernel beside gemm::kernel_dma (gemm_f32.h): that kernel, measured at the QKV shape (M = 11008, N = 1536,
+// K = 256, split-bf16 products), took 40 us whole and ~30 us with the operand DMA, the matrix instructions or the epilogue
+// stores taken out - three ~10 us phases that every wave runs one after the other.  Two structural reasons,
+// both removed here:
 //   * `s_waitcnt vmcnt` counts a wave's loads, LDS-DMA pieces AND stores in issue order, so a wave that stores its tile
 //     and then waits for its next operand pieces also waits for the stores to reach L2;
 //   * every wave reads its fragments right after the barrier that publishes them, so the matrix pipe idles for an LDS
@@ -94,9 +94,7 @@ constexpr int WS_PRODUCT_WAVES = 8, WS_LOADER_WAVES = 4, WS_THREADS = 64 * (WS_P
 
 // MATH: 0 fp32 MFMA (32x32x2), 3 split-bf16 with both operands split in the loop, 7 B pre-split, 8 both pre-split.
 // VEC: the epilogue's rows are 16-byte aligned and N % BN == 0 (checked by the launcher); else dword stores per element.
-// ABLATE (timing experiments only): 1 no matrix instructions, 2 no DMA, 4 no epilogue stores, 8 product waves only join the
-// barriers, 16 no lgkmcnt(0) before the barrier (WRONG results), 32 no epilogue pieces at all, 64 loaders issue every other piece.
-template <int BM, int BN, class Epi, int NS, int MATH, bool VEC, int ABLATE = 0>
+template <int BM, int BN, class Epi, int NS, int MATH, bool VEC>
 __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int tiles_m, int tiles_n, int total_tiles) {
     constexpr int TM = BM / 128, TN = BN / 64;            // 32x32 accumulator tiles per product wave (4 x 2 wave grid)
     static_assert(BM % 128 == 0 && BN % 64 == 0 && TM >= 1 && TN >= 1, "tile must split over the 4 x 2 product waves");
@@ -183,15 +181,13 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
                                                  (__attribute__((address_space(3))) void*)(lds + BIAS_AT + (itile & 1) * 256),
                                                  16, 0, 0);
             }
-            if (!(ABLATE & 2)) {
 #pragma unroll
-                for (int i = 0; i < PPL; i += ((ABLATE & 64) ? 2 : 1)) {
-                    const int piece = lw + WS_LOADER_WAVES * i;
-                    const float* p = src[i] + ikt * 32;
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
-                                                     (__attribute__((address_space(3))) void*)(lds + istage * STAGE + piece * 256),
-                                                     16, 0, 0);
-                }
+            for (int i = 0; i < PPL; ++i) {
+                const int piece = lw + WS_LOADER_WAVES * i;
+                const float* p = src[i] + ikt * 32;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
+                                                 (__attribute__((address_space(3))) void*)(lds + istage * STAGE + piece * 256),
+                                                 16, 0, 0);
             }
             if constexpr (Epi::kExtra && VEC) {
                 // The residual tile of tile `itile` travels behind the pieces of its LAST k-step: it is complete at the
@@ -236,7 +232,7 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * PPL) : "memory");
             else
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (!(ABLATE & 256)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             issue_next();   // step s + NS into stage s % NS
         }
         return;
@@ -300,12 +296,7 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
     };
     auto mfma_half = [&](auto CUR, auto H) {
         constexpr int cur = decltype(CUR)::value, h = decltype(H)::value;
-        if constexpr ((ABLATE & 1) != 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[cur][i][j][0] += fa[h][i][0][0] + fb[h][j][1][3];
-        } else if constexpr (MATH == 0) {
+        if constexpr (MATH == 0) {
 #pragma unroll
             for (int s = 0; s < 8; ++s)
 #pragma unroll
@@ -373,8 +364,7 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
             }
             quad_transpose(x, q);
             const int oc = ((pn0 + wn) >> 1) + (lr & ~3);
-            if (!(ABLATE & 4) || x[0] == 12345.678f)
-                if (m < g.M) epi.emit4(pz, m, oc, f32x4{x[0], x[1], x[2], x[3]}, extra);
+            if (m < g.M) epi.emit4(pz, m, oc, f32x4{x[0], x[1], x[2], x[3]}, extra);
         } else {
             constexpr int i = G / (TN * 4), j = (G / 4) % TN;
             if constexpr (VEC) {
@@ -382,8 +372,7 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
                               acc[prev][i][j][4 * rg + 3]};
                 quad_transpose(x, q);
                 const f32x4 v = f32x4{x[0], x[1], x[2], x[3]} + bvec[prev][j];
-                if (!(ABLATE & 4) || x[0] == 12345.678f)
-                    if (m < g.M) epi.emit4(pz, m, piece_n(G), v, extra);
+                if (m < g.M) epi.emit4(pz, m, piece_n(G), v, extra);
             } else {
                 // edge tiles / unaligned outputs: one dword per accumulator register (column = lane, rows in the registers)
                 const int n = pn0 + wn + 32 * j + lr;
@@ -426,9 +415,8 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
     // one k-step of tile set CUR; PS >= 0: it also carries pieces PS*PPS .. of the pending set
     auto step = [&](auto CUR, auto PSI) {
         constexpr int cur = decltype(CUR)::value, PS = decltype(PSI)::value;
-        if constexpr (!(ABLATE & 16)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragments of this step are in registers ...
-        if constexpr (!(ABLATE & 256)) __builtin_amdgcn_s_barrier();   // ... the next step has landed, this step's stage is free
-        if constexpr ((ABLATE & 8) != 0) return;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragments of this step are in registers ...
+        __builtin_amdgcn_s_barrier();   // ... the next step has landed, this step's stage is free
         const float* st = next_stage();
         if constexpr (PS >= 0 && Epi::kExtra && VEC) {
             // residual operands of this step's pieces, from the LDS copy of the pending tile
@@ -438,10 +426,10 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
             });
         }
         mfma_half(CUR, ic<0>{});
-        if constexpr (!(ABLATE & 128)) read_half(st, ic<0>{});
+        read_half(st, ic<0>{});
         mfma_half(CUR, ic<1>{});
-        if constexpr (!(ABLATE & 128)) read_half(st, ic<1>{});
-        if constexpr (PS >= 0 && !(ABLATE & 32)) {
+        read_half(st, ic<1>{});
+        if constexpr (PS >= 0) {
             if (pend) {
                 static_for<0, PPS>([&](auto P) {
                     constexpr int G = PS * PPS + decltype(P)::value;
@@ -497,12 +485,12 @@ __global__ void __launch_bounds__(WS_THREADS) kernel_ws(Args g, Epi epi, int til
     }
 }
 
-template <int BM, int BN, class Epi, int NS, int MATH, bool VEC, int ABLATE = 0>
+template <int BM, int BN, class Epi, int NS, int MATH, bool VEC>
 inline hipError_t launch_ws_one(hipStream_t st, const Args& g, const Epi& epi) {
     constexpr size_t lds_bytes = (size_t)NS * (BM + BN) * 128 + 2048 + (Epi::kExtra ? (size_t)BM * BN * 4 : 0);   // ring + bias + residual tile
     static_assert(lds_bytes <= 160 * 1024, "ring does not fit the LDS");
     static_assert(lds_bytes > 80 * 1024, "one workgroup per CU is assumed");
-    auto kfn = kernel_ws<BM, BN, Epi, NS, MATH, VEC, ABLATE>;
+    auto kfn = kernel_ws<BM, BN, Epi, NS, MATH, VEC>;
     static std::atomic<uint64_t> done{0};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);

@@ -16,10 +16,9 @@ constexpr int PERFORMER_CTXS_FLOATS = 9 * 512 * 4;        // per (utterance, hea
 constexpr int PERFORMER_P3_BYTES = 9 * 768 * 16;          // per layer: the scaled projection matrix as three bf16 pieces
 // p3 <- pieces of dn*log2(e)*P (266, 64), once per forward and layer
 void performer_p3(hipStream_t st, const float* P0, const float* P1, const float* P2, void* p3);   // P1, P2 may be null
-void performer_kv_bf16(hipStream_t st, const float* k, const float* v, const void* p3, int B, int Fr, float* ctxS, float* ks,
-                       int ablate = 0);
+void performer_kv_bf16(hipStream_t st, const float* k, const float* v, const void* p3, int B, int Fr, float* ctxS, float* ks);
 void performer_q_bf16(hipStream_t st, const float* q, const void* p3, const float* ctxS, const float* ks, int B, int Fr,
-                      float* attn, int ablate = 0);
+                      float* attn);
 // both sides in one kernel (round 3): ctx and ks stay in the LDS of the (utterance, head)'s workgroup
 hipError_t performer_fused_bf16(hipStream_t st, const float* q, const float* k, const float* v, const void* p3, int B, int Fr,
                                 float* attn, int out_split = 0, const int* n_frames = nullptr);

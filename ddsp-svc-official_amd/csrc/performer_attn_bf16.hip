@@ -92,8 +92,6 @@ __global__ void __launch_bounds__(256) performer_p3_kernel(const float* __restri
 // LDS stage (16-byte units): Kp[(s*3 + piece)*2 + h][i] (768) | Kd[h][i] (64) | Vp[((step*2 + piece)*2 + ctile)*2 + h][n] (512)
 constexpr int K_KP = 0, K_KD = 768, K_VP = 832, K_STAGE = 1344;      // 21504 bytes per stage
 
-// ABL (measurement only, tools/attn_ablate.py): 1 = the staging wave does no work, 2 = no first product, 4 = no second product
-template <int ABL>
 __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_kernel(const float* __restrict__ k,
                                                                              const float* __restrict__ v,
                                                                              const uint4* __restrict__ p3, int Fr,
@@ -118,13 +116,7 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_ker
         const float* kb = k + ((int64_t)b * Fr) * INNER + h * DH;
         const float* vb = v + ((int64_t)b * Fr) * INNER + h * DH;
         if (ws == 0) lds[(lane >> 5) * K_STAGE + K_KD + 32 + l31] = uint4{0u, 0u, 0u, 0u};   // half 1 of the extra A operand
-        float sink = 0.f;
         auto load_round = [&](int r, int ft, float (&x)[8]) __attribute__((always_inline)) {
-            if (ABL & 16) {              // no loads
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = 0.25f * (float)(lane + e + ft);
-                return;
-            }
             if (r < 4) {
                 const int fi = 8 * r + (lane & 7), f = 32 * ft + fi;
                 const float* src = kb + (int64_t)(f < Fr ? f : Fr - 1) * INNER + 8 * (lane >> 3);
@@ -141,11 +133,6 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_ker
             }
         };
         auto store_round = [&](int r, int ft, const float (&x)[8]) __attribute__((always_inline)) {
-            if (ABL & 8) {               // loads only: consume the values
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sink += x[e];
-                return;
-            }
             uint4* st = lds + (ft & 1) * K_STAGE;
             if (r < 4) {
                 const int fi = 8 * r + (lane & 7), c8 = lane >> 3;
@@ -180,24 +167,19 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_ker
         // flight while this wave waits for the product waves (one register set; the wait before the conversion is a plain
         // vmcnt(0) - with two sets the compiler cannot count the loads of the two tiles apart and waits for both)
         float x[3][8];
-        if (!(ABL & 1)) {
 #pragma unroll
-            for (int i = 0; i < 3; ++i) load_round(ws + 3 * i, 0, x[i]);
-        }
+        for (int i = 0; i < 3; ++i) load_round(ws + 3 * i, 0, x[i]);
 #pragma unroll 1
         for (int ft = 0; ft < n_ft; ++ft) {
-            if (!(ABL & 1)) {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) store_round(ws + 3 * i, ft, x[i]);
-                if (ft + 1 < n_ft) {
+            for (int i = 0; i < 3; ++i) store_round(ws + 3 * i, ft, x[i]);
+            if (ft + 1 < n_ft) {
 #pragma unroll
-                    for (int i = 0; i < 3; ++i) load_round(ws + 3 * i, ft + 1, x[i]);
-                }
+                for (int i = 0; i < 3; ++i) load_round(ws + 3 * i, ft + 1, x[i]);
             }
             __syncthreads();           // tile ft is staged (and the product waves have finished tile ft - 1)
         }
         __syncthreads();
-        if ((ABL & 8) && sink == 12345.678f) ks[0] = sink;
         return;
     }
 
@@ -244,7 +226,7 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_ker
         for (int q = 0; q < 3; ++q) a[0][q] = __builtin_bit_cast(bf16x8, kp[q * 64]);
         const bf16x8 ad = __builtin_bit_cast(bf16x8, st[K_KD + lh * 32 + l31]);
 #pragma unroll
-        for (int s = 0; s < ((ABL & 2) ? 0 : 4); ++s) {
+        for (int s = 0; s < 4; ++s) {
             if (s + 1 < 4) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) a[(s + 1) & 1][q] = __builtin_bit_cast(bf16x8, kp[((s + 1) * 3 + q) * 64]);
@@ -274,7 +256,7 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_ker
         }
         // ---- ctx_jt += k'^T v: the accumulator registers are the k-slots ----
 #pragma unroll
-        for (int step = 0; step < ((ABL & 4) ? 0 : 2); ++step) {
+        for (int step = 0; step < 2; ++step) {
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = kf[8 * step + e];
@@ -330,8 +312,6 @@ __global__ void __launch_bounds__(64 * (KG + KS_WAVES), 3) performer_kv_bf16_ker
 // LDS stage (16-byte units): Pp[(s*3 + piece)*2 + h][i] (768) | Cp[((step*2 + piece)*2 + ctile)*2 + h][i] (512) | ks (8)
 constexpr int Q_PP = 0, Q_CP = 768, Q_KS = 1280, Q_STAGE = 1344;     // 21504 bytes per stage (1 KiB aligned pieces)
 
-// ABL (measurement only): 1 = no DMA staging, 2 = no first product, 4 = no second product
-template <int ABL>
 __global__ void __launch_bounds__(64 * QW, 3) performer_q_bf16_kernel(const float* __restrict__ q, const uint4* __restrict__ p3,
                                                                    const uint4* __restrict__ ctxS, const float* __restrict__ ks,
                                                                    int Fr, int n_fg, float* __restrict__ attn, int out_split) {
@@ -351,7 +331,7 @@ __global__ void __launch_bounds__(64 * QW, 3) performer_q_bf16_kernel(const floa
 #pragma unroll
         for (int i = 0; i < (20 + QW - 1) / QW; ++i) {
             const int piece = wave + QW * i;
-            if (piece < 20 && !(ABL & 1)) {
+            if (piece < 20) {
                 const uint4* src = piece < 12 ? p3 + (jt * 12 + piece) * 64 + lane : cd + (jt * 8 + piece - 12) * 64 + lane;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(lds + buf * Q_STAGE + piece * 64),
@@ -422,7 +402,7 @@ __global__ void __launch_bounds__(64 * QW, 3) performer_q_bf16_kernel(const floa
 #pragma unroll
         for (int p = 0; p < 3; ++p) a[0][p] = __builtin_bit_cast(bf16x8, pp[p * 64]);
 #pragma unroll
-        for (int s = 0; s < ((ABL & 2) ? 0 : 4); ++s) {
+        for (int s = 0; s < 4; ++s) {
             if (s + 1 < 4) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p) a[(s + 1) & 1][p] = __builtin_bit_cast(bf16x8, pp[((s + 1) * 3 + p) * 64]);
@@ -467,7 +447,7 @@ __global__ void __launch_bounds__(64 * QW, 3) performer_q_bf16_kernel(const floa
 #pragma unroll
             for (int e = 0; e < 4; ++e) Dacc = fmaf(u[4 * g4 + e], kv[g4][e], Dacc);
 #pragma unroll
-        for (int step = 0; step < ((ABL & 4) ? 0 : 2); ++step) {
+        for (int step = 0; step < 2; ++step) {
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = u[8 * step + e];
@@ -940,32 +920,15 @@ void performer_p3(hipStream_t st, const float* P0, const float* P1, const float*
                        (uint4*)p3);
 }
 
-void performer_kv_bf16(hipStream_t st, const float* k, const float* v, const void* p3, int B, int Fr, float* ctxS, float* ks,
-                       int ablate) {
-#define KV_ABL(A)                                                                                                      \
-    if (ablate == A) {                                                                                                 \
-        hipLaunchKernelGGL(performer_kv_bf16_kernel<A>, dim3((unsigned)(B * H)), dim3(64 * (KG + KS_WAVES)), 0, st, k, \
-                           v, (const uint4*)p3, Fr, (uint4*)ctxS, ks);                                                 \
-        return;                                                                                                        \
-    }
-    KV_ABL(1) KV_ABL(2) KV_ABL(4) KV_ABL(6) KV_ABL(7) KV_ABL(14) KV_ABL(22)
-#undef KV_ABL
-    hipLaunchKernelGGL(performer_kv_bf16_kernel<0>, dim3((unsigned)(B * H)), dim3(64 * (KG + KS_WAVES)), 0, st, k, v,
+void performer_kv_bf16(hipStream_t st, const float* k, const float* v, const void* p3, int B, int Fr, float* ctxS, float* ks) {
+    hipLaunchKernelGGL(performer_kv_bf16_kernel, dim3((unsigned)(B * H)), dim3(64 * (KG + KS_WAVES)), 0, st, k, v,
                        (const uint4*)p3, Fr, (uint4*)ctxS, ks);
 }
 
 void performer_q_bf16(hipStream_t st, const float* q, const void* p3, const float* ctxS, const float* ks, int B, int Fr,
-                      float* attn, int ablate) {
+                      float* attn) {
     const int n_fg = ((Fr + 31) / 32 + QW - 1) / QW;
-#define Q_ABL(A)                                                                                                       \
-    if (ablate == A) {                                                                                                 \
-        hipLaunchKernelGGL(performer_q_bf16_kernel<A>, dim3((unsigned)(n_fg * B * H)), dim3(64 * QW), 0, st, q,        \
-                           (const uint4*)p3, (const uint4*)ctxS, ks, Fr, n_fg, attn, 0);                               \
-        return;                                                                                                        \
-    }
-    Q_ABL(1) Q_ABL(2) Q_ABL(4) Q_ABL(6) Q_ABL(7)
-#undef Q_ABL
-    hipLaunchKernelGGL(performer_q_bf16_kernel<0>, dim3((unsigned)(n_fg * B * H)), dim3(64 * QW), 0, st, q, (const uint4*)p3,
+    hipLaunchKernelGGL(performer_q_bf16_kernel, dim3((unsigned)(n_fg * B * H)), dim3(64 * QW), 0, st, q, (const uint4*)p3,
                        (const uint4*)ctxS, ks, Fr, n_fg, attn, 0);
 }
 
@@ -1000,10 +963,8 @@ extern "C" int ddsp_performer_attention(ddsp_ctx* ctx, void* stream, const float
         DDSP_LAUNCH_CHECK(ctx);
         return DDSP_OK;
     }
-    // (math = 100 + ablation mask: measurement aid of tools/attn_ablate.py, results are meaningless)
-    const int ablate = math >= 100 ? math - 100 : 0;
-    const bool want_pair = math >= 100;      // 100 + mask: the round-2 kernel pair (mask 0: nothing switched off)
-    if (math >= 100) math = DDSP_MATH_SPLIT_BF16;
+    const bool want_pair = math == DDSP_ATTENTION_PAIR;   // the round-2 kernel pair in place of the fused kernel
+    if (want_pair) math = DDSP_MATH_SPLIT_BF16;
     DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16, "ddsp_performer_attention: unknown math");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
@@ -1025,10 +986,10 @@ extern "C" int ddsp_performer_attention(ddsp_ctx* ctx, void* stream, const float
     } else if (math == DDSP_MATH_SPLIT_BF16) {
         performer_p3(st, proj, nullptr, nullptr, p3);
         ddsp_prof_begin(ctx, st, PF_U2C_GEMM_CTX);
-        performer_kv_bf16(st, k, v, p3, (int)B, (int)Fr, cx, ksb, ablate);
+        performer_kv_bf16(st, k, v, p3, (int)B, (int)Fr, cx, ksb);
         ddsp_prof_end(ctx, st, 4.0 * B * Fr * H * NF * DH, 4.0 * B * Fr * 2 * INNER);
         ddsp_prof_begin(ctx, st, PF_U2C_GEMM_ATTNOUT);
-        performer_q_bf16(st, q, p3, cx, ksb, (int)B, (int)Fr, out, ablate);
+        performer_q_bf16(st, q, p3, cx, ksb, (int)B, (int)Fr, out);
         ddsp_prof_end(ctx, st, 4.0 * B * Fr * H * NF * DH, 4.0 * B * Fr * 2 * INNER);
     } else {
         ddsp_prof_begin(ctx, st, PF_U2C_GEMM_CTX);

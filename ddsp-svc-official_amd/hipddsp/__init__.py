@@ -23,6 +23,7 @@ FIR_FP32, FIR_SPLIT_BF16 = 0, 3   # ddsp_ltv_fir `math` (include/ddsp_amd.h)
 ABI_VERSION = 7                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights, CrepeWeights)
 MATH_FP32, MATH_SPLIT_BF16 = 0, 3  # ddsp_ctx_set_math
 ATTENTION_CAUSAL = 200            # ddsp_performer_attention: causal_linear_attention (pcmer.py:170-188)
+ATTENTION_PAIR = 100              # ddsp_performer_attention: the split-bf16 key / query kernel pair instead of the fused kernel
 
 _c = ctypes
 _vp, _i64, _u64, _int, _f32, _f64 = _c.c_void_p, _c.c_int64, _c.c_uint64, _c.c_int, _c.c_float, _c.c_double

@@ -406,8 +406,20 @@ int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* con
 /* ---- building block: fp32-in / fp32-accumulate MFMA GEMM ---------------------------------------- */
 /* C[m][n] = sum_k A(m,k) B(k,n) (+ bias[n]).  a_k_contig: A(m,k) = A[m*lda+k] else A[k*lda+m];
  * b_k_contig: B(k,n) = B[n*ldb+k] (nn.Linear weight layout) else B[k*ldb+n].  Rows must start 16-byte aligned
- * (lda, ldb multiples of 4).  tile: 0 = auto, 1 = 64x64, 2 = 64x128, 3 = 128x128; variant: schedule A/B switch.
- * Exposed for unit tests of the block every contraction of the path is built on and for tile tuning. */
+ * (lda, ldb multiples of 4).  Exposed for unit tests of the block every contraction of the path is built on.
+ * tile selects the kernel and its tiling; a code from 10 on that is not listed here is DDSP_ERR_ARG and launches nothing:
+ *   0        what the network's layers run: the choice by shape and math mode (any layout)
+ *   1..6     register-staged kernel (any layout): 64x64, 64x128, 128x128 on 4 waves; 128x128, 128x64, 256x128 on 8 waves
+ *            (every other code below 10 runs 6)
+ *   10..16   LDS-DMA kernel, fp32 products (row-major A, [N][K] B, K % 32 == 0): 10 128x64, 11 128x128, 12 256x128 with a
+ *            3-stage ring; 13 128x128, 14 128x64 with 2 stages; 15 64x64, 16 64x128 on 4 waves
+ *   30       LDS-DMA kernel, 128x128 with 2 stages, split-bf16 products
+ *   70, 75   wave-specialised kernel (as 10.., and K >= 256, N % 64 == 0, 16-byte aligned C): 70 128x128, 75 128x64 tiles
+ * variant is read by tiles 70 and 75 only, as products + epilogue (any other bit is DDSP_ERR_ARG):
+ *   products  0 fp32, 3 split-bf16 (operands split in the loop), 8 split-bf16 on operands that arrive in the pre-split
+ *             layout (ddsp_gemm_res_ln below); tile 75 takes 8 only
+ *   epilogue  + 0 C = A B^T + bias; + 16 (tile 75) C += A B^T + bias; + 32 (tile 70, bias, N % 128 == 0) gated pair:
+ *             C gets N / 2 columns */
 int ddsp_gemm_f32(ddsp_ctx* ctx, void* stream, const float* A, int64_t lda, int a_k_contig, const float* B,
                   int64_t ldb, int b_k_contig, const float* bias, float* C, int64_t ldc, int M, int N, int K, int tile,
                   int variant);
@@ -427,8 +439,11 @@ int ddsp_gemm_res_ln(ddsp_ctx* ctx, void* stream, const float* A_split, const fl
  * piece products - they enter an exponential -, the two context products from three).  Exposed for unit tests of the
  * kernels ddsp_unit2ctrl_fwd runs at inference (it picks the split kernels from 32 utterances on).
  * math = DDSP_ATTENTION_CAUSAL: `causal_linear_attention` (pcmer.py:170-188, `c: true` networks) instead - the running sums
- * over the frames up to and including each one, as chunked products with fp32 arithmetic. */
+ * over the frames up to and including each one, as chunked products with fp32 arithmetic.
+ * math = DDSP_ATTENTION_PAIR: DDSP_MATH_SPLIT_BF16 with the key side and the query side as two kernels (the fused kernel's
+ * independent comparison in the tests).  Any other code is DDSP_ERR_ARG. */
 #define DDSP_ATTENTION_CAUSAL 200
+#define DDSP_ATTENTION_PAIR 100
 int ddsp_performer_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v,
                              const float* proj, int64_t B, int64_t Fr, float* out, int math);
 

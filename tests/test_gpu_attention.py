@@ -108,6 +108,15 @@ def test_attention_large_exponents(ctx, dev, math):
     assert err < (5e-6 if math == 0 else 2e-5), (err, big)
 
 
+@pytest.mark.parametrize("math", [1, 4, 101, 107, 199])
+def test_unknown_attention_codes_are_refused(ctx, dev, math):
+    """Only the two math modes, ATTENTION_PAIR and ATTENTION_CAUSAL select a kernel; any other code is an argument error."""
+    B, Fr = 2, 33
+    q, k, v, P = make(11, B, Fr, 1.0, dev)
+    with pytest.raises(ValueError):
+        ctx.performer_attention(q, k, v, P, B, Fr, math=math)
+
+
 def test_attention_modes_agree_in_the_model(dev, lib_path):
     """ddsp_unit2ctrl_fwd picks the split kernels from 32 utterances on: the control matrix with them equals the one with
     the fp32 kernels to the accuracy of the split GEMMs around them."""
@@ -133,11 +142,12 @@ def test_attention_modes_agree_in_the_model(dev, lib_path):
 def test_fused_kernel_against_the_kernel_pair(ctx, dev, monkeypatch):
     """Round 3: key and query side of the split attention in one kernel per (utterance, head).  Its feature tiles are summed
     in another order (even / odd tiles on two waves, combined at their common row maximum), so it equals the round-2 kernel
-    pair (ablation code 100 = the pair, nothing switched off) to rounding, not to the bit."""
+    pair (math = ATTENTION_PAIR) to rounding, not to the bit."""
+    import hipddsp
     B, Fr = 48, 172
     q, k, v, P = make(5, B, Fr, 1.5, dev)
     fused = ctx.performer_attention(q, k, v, P, B, Fr, math=3)
-    pair = ctx.performer_attention(q, k, v, P, B, Fr, math=100)
+    pair = ctx.performer_attention(q, k, v, P, B, Fr, math=hipddsp.ATTENTION_PAIR)
     assert float((fused - pair).norm() / pair.norm()) < 2e-6
     for _ in range(3):
         assert torch.equal(ctx.performer_attention(q, k, v, P, B, Fr, math=3), fused)      # run-to-run bit stability

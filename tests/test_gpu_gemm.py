@@ -53,6 +53,25 @@ def test_dma_requires_alignment(ctx, dev):
         ctx.gemm(A, B, tile=10)        # K % 32 != 0
 
 
+def test_unknown_tile_codes_are_refused(ctx, dev):
+    """A tile or variant code that names no kernel is an argument error that launches nothing (it used to fall through
+    to some kernel and return success); the context works as before afterwards."""
+    A, B = _mk((128, 256), 9, dev), _mk((128, 256), 10, dev)
+    for tile in (24, 31, 38, 50, 60, 69, 72, 99):
+        with pytest.raises(ValueError):
+            ctx.gemm(A, B, tile=tile)
+    with pytest.raises(ValueError):
+        ctx.gemm(A, B, tile=70, variant=8 + 256)
+    with pytest.raises(ValueError):
+        ctx.gemm(A, B, tile=70, variant=64)
+    C = ctx.gemm(A, B, tile=10)
+    want = A.double().cpu() @ B.double().cpu().t()
+    scale = float(want.abs().max())
+    assert float((C.double().cpu() - want).abs().max()) < 2e-6 * scale * max(1.0, 256 ** 0.5 / 4)
+    torch.cuda.synchronize(dev)
+    ctx.poll_error()
+
+
 # ---- the wave-specialised kernel (csrc/gemm_ws.h): tiles 70+ ---------------------------------------------------------
 def _presplit(X):
     """(rows, K) fp32 -> the (8 bf16 hi | 8 bf16 lo) operand layout with lo = 0, and the bf16-rounded values it encodes."""

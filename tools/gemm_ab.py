@@ -17,7 +17,7 @@ for (M, N, K) in shapes:
         for var in (0,):
             C = ctx.gemm(A, B, tile=tile, variant=var)
             err = float((C - ref).abs().max())
-            assert tile >= 20 or err < 1e-2, (tile, var, err)
+            assert err < 1e-2, (tile, var, err)
             res[(tile, var)] = []
     for rnd in range(5):
         for key in res:
