@@ -73,11 +73,25 @@ __global__ void __launch_bounds__(256) align_units_kernel(const float* __restric
 }
 
 // f0 track re-timed for the enhancer (enhancer.py:56-62): out[i] = numpy.interp(i * step_dst, knots j * step_num / div,
-// fl32(f0[j] * scale)) with the end values held outside the knots; one thread per output frame, fp64 like numpy.
+// fl32(f0[j] * scale)) with the end values held outside the knots; one thread per output frame, fp64 like numpy.  Ragged batch
+// (ns != nullptr): blockIdx.y is the row, with ns[b] <= n_src knots and nd[b] <= n_dst targets of its own - the ends are held
+// at the row's own first and last frame, what follows them in f0 is not read, and the outputs from nd[b] on are 0.
 __global__ void __launch_bounds__(256) retime_f0_kernel(const float* __restrict__ f0, int64_t n_src, double step_num, double div,
-                                                        float scale, double step_dst, int64_t n_dst, float* __restrict__ out) {
+                                                        float scale, double step_dst, int64_t n_dst, float* __restrict__ out,
+                                                        const int32_t* __restrict__ ns, const int32_t* __restrict__ nd) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_dst) return;
+    if (ns) {
+        const int64_t b = blockIdx.y;
+        f0 += b * n_src;
+        out += b * n_dst;
+        if (i >= (int64_t)nd[b]) {
+            out[i] = 0.f;
+            return;
+        }
+        const int64_t nb = ns[b];
+        n_src = nb < 1 ? 1 : (nb < n_src ? nb : n_src);
+    }
     auto knot = [&](int64_t j) { return (step_num * (double)j) / div; };              // (hop / sr) * arange(n) / real_factor
     auto val = [&](int64_t j) { return (double)__fmul_rn(f0[j], scale); };            // the fp32 in-place `f0_np *= real_factor`
     const double x = step_dst * (double)i;
@@ -107,7 +121,21 @@ extern "C" int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int6
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     hipLaunchKernelGGL(retime_f0_kernel, dim3((unsigned)ceil_div64(n_dst, 256)), dim3(256), 0, st, f0, n_src, step_num, div, scale,
-                       step_dst, n_dst, out);
+                       step_dst, n_dst, out, (const int32_t*)nullptr, (const int32_t*)nullptr);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
+                                     double step_num, double div, float scale, double step_dst, int64_t n_dst,
+                                     const int32_t* n_dst_rows, float* out) {
+    DDSP_REQUIRE(ctx, ctx && f0 && out && n_src_rows && n_dst_rows, "ddsp_retime_f0_ragged: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && n_src >= 1 && n_dst >= 1 && step_num > 0 && div > 0 && step_dst > 0,
+                 "ddsp_retime_f0_ragged: bad shape or step");
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    hipLaunchKernelGGL(retime_f0_kernel, dim3((unsigned)ceil_div64(n_dst, 256), (unsigned)B), dim3(256), 0, st, f0, n_src, step_num, div,
+                       scale, step_dst, n_dst, out, n_src_rows, n_dst_rows);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

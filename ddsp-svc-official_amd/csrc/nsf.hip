@@ -1,6 +1,11 @@
 // SURVEY 8(f) rank 1 - the NSF-HiFiGAN post-net of the reference's `Enhancer` (enhancer.py:24-101, nsf_hifigan/models.py:
 // 106-276): harmonic source (SineGen + SourceModuleHnNSF), the generator's convolution stack, and the log-mel front end
-// (nsf_hifigan/nvSTFT.py:65-119).  Batch 1 (the reference calls it with one utterance), activations frame-major (T, C).
+// (nsf_hifigan/nvSTFT.py:65-119).  Activations frame-major (T, C); the reference calls it with one utterance, the `_ragged`
+// entry points take B rows of different length as one padded batch, flattened on the time axis: (B * T, C), row b valid
+// for its first T_b = n[b] * scale frames (n: a DEVICE array of B int32, never read back).  ONE RULE keeps the rows apart:
+// every tensor a convolution reads is exactly 0 at t >= T_b, and every producer selects 0 there when it WRITES (bias, residual
+// and source terms would make the padding non-zero).  A tap that leaves [0, T_b) then reads 0 like a solo call's "same"
+// padding; taps never cross into a neighbour (the GEMM loader wraps with m % T, the window kernels cut windows per row).
 //   * every Conv1d / ConvTranspose1d with more than one input channel is a GEMM on the fp32 matrix pipe with an implicit
 //     im2col loader (gemm_f32.h, A_CONVK: k taps `dil` frames apart, "same" padding, the preceding leaky-ReLU applied while
 //     the operand is loaded; bias and the residual / source addition in the epilogue).  A transposed convolution of stride
@@ -30,9 +35,17 @@ constexpr int NH = 9;   // harmonics of the source module (harmonic_num = 8, nsf
 // exclusive scan of those sums, and each lane then writes the prefixes of its own frames.  (One lane per harmonic walking all
 // frames took 130 us at 860 frames - a serial chain of fmod, divide and fp64 add per frame.)  The running value is reduced
 // mod 1 after every addition as before, so every partial result stays below 2 and the fp64 rounding stays at the 1e-16 level.
+// Ragged batch: blockIdx.y is the row; its scan runs over its own n[b] frames from its own rand_ini (the lanes' shares follow
+// the row's own length, so a row's sums are those of a solo call), f0 past n[b] is not read.
 __global__ void __launch_bounds__(64) nsf_frame_prefix_kernel(const float* __restrict__ f0, const float* __restrict__ rand_ini,
-                                                              int L, int upp, float sr, double* __restrict__ prefix) {
+                                                              int L, int upp, float sr, double* __restrict__ prefix,
+                                                              const int* __restrict__ n) {
     const int h = blockIdx.x, lane = threadIdx.x;
+    const int64_t b = blockIdx.y;
+    f0 += b * L;
+    rand_ini += b * NH;
+    prefix += b * L * NH;
+    L = ddsp_row_frames(n, b, L);
     const int per = (L + 63) / 64;
     const int l0 = lane * per, l1 = l0 + per < L ? l0 + per : L;
     auto inc = [&](int l) -> double {
@@ -67,10 +80,19 @@ __global__ void __launch_bounds__(64) nsf_frame_prefix_kernel(const float* __res
 __global__ void __launch_bounds__(256) nsf_source_kernel(const float* __restrict__ f0, const float* __restrict__ rand_ini,
                                                          const double* __restrict__ prefix, const float* __restrict__ w,
                                                          const float* __restrict__ b, int L, int upp, float sr, float amp,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, const int* __restrict__ nfr) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= (int64_t)L * upp) return;
+    const int64_t row = blockIdx.y;
+    f0 += row * L;
+    rand_ini += row * NH;
+    prefix += row * L * NH;
+    out += row * L * upp;
     const int l = (int)(n / upp), j = (int)(n - (int64_t)l * upp);
+    if (l >= ddsp_row_frames(nfr, row, L)) {      // past the row's own end: no source, f0 is not read
+        out[n] = 0.f;
+        return;
+    }
     float s = b[0];
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
@@ -94,6 +116,8 @@ __global__ void __launch_bounds__(256) nsf_noise_conv_kernel(const float* __rest
                                                              int64_t T_out, int C, int K, int stride, int pad,
                                                              float* __restrict__ out) {
     extern __shared__ float win[];
+    src += (int64_t)blockIdx.z * T_src;          // a batch row (taps are row-local: the source is 0 past the row's own end)
+    out += (int64_t)blockIdx.z * T_out * C;
     const int Cb = C < 256 ? C : 256;            // channels per block (blockIdx.y walks wider layers)
     const int G = 256 / Cb;                      // frame groups per block
     const int c = blockIdx.y * Cb + threadIdx.x % Cb, gq = threadIdx.x / Cb;
@@ -130,8 +154,13 @@ __global__ void __launch_bounds__(256) nsf_noise_conv_kernel(const float* __rest
 // budget take the direct path.
 __global__ void __launch_bounds__(256) nsf_post_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ b, int64_t T, int C, int K, float slope,
-                                                       float* __restrict__ out, int use_lds) {
+                                                       float* __restrict__ out, int use_lds, const int* __restrict__ n,
+                                                       int nscale) {
     extern __shared__ float win[];
+    // a batch row: its taps stay inside [0, T) of the row, x is 0 from the row's own end Te on, the output is written 0 there
+    x += (int64_t)blockIdx.y * T * C;
+    out += (int64_t)blockIdx.y * T;
+    const int64_t Te = n ? (int64_t)ddsp_row_frames(n, blockIdx.y, (int)(T / nscale)) * nscale : T;
     const int64_t t0 = (int64_t)blockIdx.x * 256, t = t0 + threadIdx.x;
     const int hk = (K - 1) / 2;
     if (use_lds) {
@@ -153,7 +182,7 @@ __global__ void __launch_bounds__(256) nsf_post_kernel(const float* __restrict__
             const float* xr = win + (threadIdx.x + j) * P;
             for (int c = 0; c < C; ++c) acc = fmaf(w[j * C + c], xr[c], acc);
         }
-        out[t] = tanhf(acc);
+        out[t] = t < Te ? tanhf(acc) : 0.f;
         return;
     }
     if (t >= T) return;
@@ -167,9 +196,10 @@ __global__ void __launch_bounds__(256) nsf_post_kernel(const float* __restrict__
             acc = fmaf(w[j * C + c], v > 0.f ? v : v * slope, acc);
         }
     }
-    out[t] = tanhf(acc);
+    out[t] = t < Te ? tanhf(acc) : 0.f;
 }
 
+// (ragged batches: nothing to do here - the mean of tensors that are 0 past a row's end is 0 there, and so is its activated copy)
 __global__ void __launch_bounds__(256) nsf_mean_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                        const float* __restrict__ c, int n_terms, int64_t n,
                                                        float* __restrict__ out, float* __restrict__ out_act, float slope) {
@@ -243,7 +273,19 @@ struct ConvSmallArgs {
     int64_t T;
     int ktaps, dil;
     float in_slope, act_slope;
+    int B;               // rows of a batch, T frames each (x, res, out: (B * T, C)); 1 for one utterance
+    const int* n;        // ragged batch: row b is n[b] * nscale frames long, reads past that select 0, writes past it store 0
+    int nscale;
 };
+// Windows are cut per row of the batch, never across two: window `chunk` of `cpr` per row, `tw` frames each
+struct WinAt {
+    int64_t base, t0, Te;   // first flattened frame of the row, the window's first frame inside it, the row's own end
+};
+template <class A>
+__device__ __forceinline__ WinAt win_at(int64_t chunk, int64_t cpr, int tw, const A& g) {
+    const int64_t b = chunk / cpr;
+    return WinAt{b * g.T, (chunk - b * cpr) * tw, g.n ? (int64_t)ddsp_row_frames(g.n, b, (int)(g.T / g.nscale)) * g.nscale : g.T};
+}
 constexpr int CS_TW = 64;   // frames per window
 constexpr int CS_MAX_HALO = 25;   // (k - 1) / 2 * dilation the register prefetch is sized for (11 taps, dilation 5)
 
@@ -260,19 +302,21 @@ __global__ void __launch_bounds__(256) conv_small_kernel(ConvSmallArgs g) {
         wl[r * C + co] = g.w[i];
     }
     __syncthreads();
-    const int64_t nchunks = (g.T + CS_TW - 1) / CS_TW;
+    const int64_t cpr = (g.T + CS_TW - 1) / CS_TW, nchunks = cpr * g.B;
     // the next window's rows travel global -> registers while the current one feeds the matrix pipe, and are written to the
     // LDS (activated) after its last read: one wave per SIMD cannot hide a global-load latency per row otherwise
     constexpr int NV = ((CS_TW + 2 * CS_MAX_HALO) * C / 4 + 63) / 64;
     const int nvec = rows * C / 4;
     f32x4 pre[NV];
-    auto load_window = [&](int64_t t0) {
+    auto load_window = [&](int64_t chunk) {
+        const WinAt a = win_at(chunk, cpr, CS_TW, g);
+        const int64_t t0 = a.t0;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int e = (lane + 64 * i) * 4;
             const int64_t t = t0 - halo + e / C;
             pre[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (lane + 64 * i < nvec && t >= 0 && t < g.T) pre[i] = *(const f32x4*)(g.x + t * C + e % C);
+            if (lane + 64 * i < nvec && t >= 0 && t < a.Te) pre[i] = *(const f32x4*)(g.x + (a.base + t) * C + e % C);
         }
     };
     auto store_window = [&]() {
@@ -288,13 +332,14 @@ __global__ void __launch_bounds__(256) conv_small_kernel(ConvSmallArgs g) {
     };
     const int64_t first = (int64_t)blockIdx.x * 4 + wave, step = (int64_t)gridDim.x * 4;
     if (first < nchunks) {
-        load_window(first * CS_TW);
+        load_window(first);
         store_window();
     }
     for (int64_t chunk = first; chunk < nchunks; chunk += step) {
-        const int64_t t0 = chunk * CS_TW;
+        const WinAt a = win_at(chunk, cpr, CS_TW, g);
+        const int64_t t0 = a.t0;
         const bool more = chunk + step < nchunks;
-        if (more) load_window((chunk + step) * CS_TW);
+        if (more) load_window(chunk + step);
         __builtin_amdgcn_wave_barrier();
         if constexpr (C == 16) {
             f32x4 acc[4];
@@ -320,9 +365,10 @@ __global__ void __launch_bounds__(256) conv_small_kernel(ConvSmallArgs g) {
                 for (int r = 0; r < 4; ++r) {
                     const int64_t t = t0 + tt * 16 + 4 * lk + r;
                     if (t < g.T) {
-                        const int64_t o = t * C + li;
+                        const int64_t o = (a.base + t) * C + li;
                         float y = acc[tt][r] + bc;
                         if (g.res) y += g.res[o];
+                        if (t >= a.Te) y = 0.f;
                         if (g.out) g.out[o] = y;
                         if (g.out_act) g.out_act[o] = y > 0.f ? y : y * g.act_slope;
                     }
@@ -353,9 +399,10 @@ __global__ void __launch_bounds__(256) conv_small_kernel(ConvSmallArgs g) {
                 for (int r = 0; r < 16; ++r) {
                     const int64_t t = t0 + tt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
                     if (t < g.T) {
-                        const int64_t o = t * C + li;
+                        const int64_t o = (a.base + t) * C + li;
                         float y = acc[tt][r] + bc;
                         if (g.res) y += g.res[o];
+                        if (t >= a.Te) y = 0.f;
                         if (g.out) g.out[o] = y;
                         if (g.out_act) g.out_act[o] = y > 0.f ? y : y * g.act_slope;
                     }
@@ -380,6 +427,9 @@ struct ConvPairRawArgs {
     int64_t T;
     int ktaps, dil;
     float slope;          // of the activations in front of c1 and c2, and of out_act
+    int B;                // as in ConvSmallArgs
+    const int* n;
+    int nscale;
 };
 typedef uint32_t ddsp_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int CP_MID = 80;          // c1 output rows per window: 64 + 2 * 5 halo rows of c2, whole 16-row tiles
@@ -400,17 +450,19 @@ __global__ void __launch_bounds__(256) conv_pair16_kernel(ConvPairRawArgs g) {
         wl2[r * C + co] = g.w2[i];
     }
     __syncthreads();
-    const int64_t nchunks = (g.T + CS_TW - 1) / CS_TW;
+    const int64_t cpr = (g.T + CS_TW - 1) / CS_TW, nchunks = cpr * g.B;
     constexpr int NV = ((CS_TW + 2 * CP_MAX_HALO) * C / 4 + 63) / 64;
     const int nvec = rows * C / 4;
     f32x4 pre[NV];
-    auto load_window = [&](int64_t t0) {
+    auto load_window = [&](int64_t chunk) {
+        const WinAt a = win_at(chunk, cpr, CS_TW, g);
+        const int64_t t0 = a.t0;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int e = (lane + 64 * i) * 4;
             const int64_t t = t0 - halo + e / C;
             pre[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (lane + 64 * i < nvec && t >= 0 && t < g.T) pre[i] = *(const f32x4*)(g.x + t * C + e % C);
+            if (lane + 64 * i < nvec && t >= 0 && t < a.Te) pre[i] = *(const f32x4*)(g.x + (a.base + t) * C + e % C);
         }
     };
     auto store_window = [&]() {
@@ -428,13 +480,14 @@ __global__ void __launch_bounds__(256) conv_pair16_kernel(ConvPairRawArgs g) {
     const float bc1 = g.b1 ? g.b1[li] : 0.f, bc2 = g.b2 ? g.b2[li] : 0.f;
     const int64_t first = (int64_t)blockIdx.x * 4 + wave, step = (int64_t)gridDim.x * 4;
     if (first < nchunks) {
-        load_window(first * CS_TW);
+        load_window(first);
         store_window();
     }
     for (int64_t chunk = first; chunk < nchunks; chunk += step) {
-        const int64_t t0 = chunk * CS_TW;
+        const WinAt a = win_at(chunk, cpr, CS_TW, g);
+        const int64_t t0 = a.t0;
         const bool more = chunk + step < nchunks;
-        if (more) load_window((chunk + step) * CS_TW);
+        if (more) load_window(chunk + step);
         __builtin_amdgcn_wave_barrier();
         // ---- c1 on frames t0 - h2 .. t0 - h2 + 79 (window row of output u at tap: u + h1 + (tap - h2) * dil) ----
         {
@@ -464,7 +517,7 @@ __global__ void __launch_bounds__(256) conv_pair16_kernel(ConvPairRawArgs g) {
                     const int64_t t = t0 - h2 + u;
                     float y = acc[tt][r] + bc1;
                     y = y > 0.f ? y : y * g.slope;
-                    mid[u * P + li] = (t >= 0 && t < g.T) ? y : 0.f;       // c2 zero-pads its input
+                    mid[u * P + li] = (t >= 0 && t < a.Te) ? y : 0.f;      // c2 zero-pads its input, at the row's own ends
                 }
         }
         __builtin_amdgcn_wave_barrier();
@@ -490,8 +543,8 @@ __global__ void __launch_bounds__(256) conv_pair16_kernel(ConvPairRawArgs g) {
                 for (int r = 0; r < 4; ++r) {
                     const int64_t t = t0 + tt * 16 + 4 * lk + r;
                     if (t < g.T) {
-                        const int64_t o = t * C + li;
-                        const float y = acc[tt][r] + bc2 + g.x[o];
+                        const int64_t o = (a.base + t) * C + li;
+                        const float y = t < a.Te ? acc[tt][r] + bc2 + g.x[o] : 0.f;
                         if (g.out) g.out[o] = y;
                         if (g.out_act) g.out_act[o] = y > 0.f ? y : y * g.slope;
                     }
@@ -557,17 +610,19 @@ __global__ void __launch_bounds__(512) conv_pair16_bf16_kernel(ConvPairRawArgs g
         }
     }
     __syncthreads();
-    const int64_t nchunks = (g.T + tw - 1) / tw;
+    const int64_t cpr = (g.T + tw - 1) / tw, nchunks = cpr * g.B;
     constexpr int NV = ((RT + 2 * 25) * C / 4 + 63) / 64;
     const int nvec = rows * C / 4;
     f32x4 pre[NV];
-    auto load_window = [&](int64_t t0) {
+    auto load_window = [&](int64_t chunk) {
+        const WinAt a = win_at(chunk, cpr, tw, g);
+        const int64_t t0 = a.t0;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int e = (lane + 64 * i) * 4;
             const int64_t t = t0 - h2 - h1 + e / C;
             pre[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (lane + 64 * i < nvec && t >= 0 && t < g.T) pre[i] = *(const f32x4*)(g.x + t * C + e % C);
+            if (lane + 64 * i < nvec && t >= 0 && t < a.Te) pre[i] = *(const f32x4*)(g.x + (a.base + t) * C + e % C);
         }
     };
     auto store_window = [&]() {
@@ -592,7 +647,7 @@ __global__ void __launch_bounds__(512) conv_pair16_bf16_kernel(ConvPairRawArgs g
     const f32x4 bc2 = g.b2 ? *(const f32x4*)(g.b2 + 4 * lk) : f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t first = (int64_t)blockIdx.x * nwaves + wave, step = (int64_t)gridDim.x * nwaves;
     if (first < nchunks) {
-        load_window(first * tw);
+        load_window(first);
         store_window();
     }
     // one convolution over NT tiles of 16 rows: `src` row of (output row u, tap) = u + tap * dd
@@ -617,16 +672,17 @@ __global__ void __launch_bounds__(512) conv_pair16_bf16_kernel(ConvPairRawArgs g
         }
     };
     for (int64_t chunk = first; chunk < nchunks; chunk += step) {
-        const int64_t t0 = chunk * tw;
+        const WinAt a = win_at(chunk, cpr, tw, g);
+        const int64_t t0 = a.t0;
         const bool more = chunk + step < nchunks;
         f32x4 res[NT];                                         // the residual rows in the accumulator layout (cache hits: the
 #pragma unroll                                                 // window load fetched the same lines), asked for before the products
         for (int tt = 0; tt < NT; ++tt) {
             const int o = tt * 16 + li;
             res[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (o < tw && t0 + o < g.T) res[tt] = *(const f32x4*)(g.x + (t0 + o) * C + 4 * lk);
+            if (o < tw && t0 + o < a.Te) res[tt] = *(const f32x4*)(g.x + (a.base + t0 + o) * C + 4 * lk);
         }
-        if (more) load_window((chunk + step) * tw);
+        if (more) load_window(chunk + step);
         __builtin_amdgcn_wave_barrier();
         f32x4 acc[NT];
         conv(wl1, win, g.dil, acc);                            // c1 on frames t0 - h2 .. t0 - h2 + RT - 1
@@ -637,7 +693,7 @@ __global__ void __launch_bounds__(512) conv_pair16_bf16_kernel(ConvPairRawArgs g
             const int64_t t = t0 - h2 + u;
             f32x4 y = acc[tt] + bc1;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) y[r] = (t >= 0 && t < g.T) ? (y[r] > 0.f ? y[r] : y[r] * g.slope) : 0.f;
+            for (int r = 0; r < 4; ++r) y[r] = (t >= 0 && t < a.Te) ? (y[r] > 0.f ? y[r] : y[r] * g.slope) : 0.f;
             uint32_t ha, la, hb, lb;
             split2(y[0], y[1], ha, la);
             split2(y[2], y[3], hb, lb);
@@ -651,8 +707,9 @@ __global__ void __launch_bounds__(512) conv_pair16_bf16_kernel(ConvPairRawArgs g
         for (int tt = 0; tt < NT; ++tt) {
             const int o = tt * 16 + li;
             if (o < tw && t0 + o < g.T) {
-                const int64_t at = (t0 + o) * C + 4 * lk;
+                const int64_t at = (a.base + t0 + o) * C + 4 * lk;
                 f32x4 y = acc[tt] + bc2 + res[tt];
+                if (t0 + o >= a.Te) y = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (g.out) *(f32x4*)(g.out + at) = y;
                 if (g.out_act) {
 #pragma unroll
@@ -688,17 +745,19 @@ __global__ void __launch_bounds__(512) conv_small32_bf16_kernel(ConvSmallArgs g)
         p[17] = l1;
     }
     __syncthreads();
-    const int64_t nchunks = (g.T + TWK - 1) / TWK;
+    const int64_t cpr = (g.T + TWK - 1) / TWK, nchunks = cpr * g.B;
     constexpr int NV = ((TWK + 2 * CS_MAX_HALO) * C / 4 + 63) / 64;
     const int nvec = rows * C / 4;
     f32x4 pre[NV];
-    auto load_window = [&](int64_t t0) {
+    auto load_window = [&](int64_t chunk) {
+        const WinAt a = win_at(chunk, cpr, TWK, g);
+        const int64_t t0 = a.t0;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int e = (lane + 64 * i) * 4;
             const int64_t t = t0 - halo + e / C;
             pre[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (lane + 64 * i < nvec && t >= 0 && t < g.T) pre[i] = *(const f32x4*)(g.x + t * C + e % C);
+            if (lane + 64 * i < nvec && t >= 0 && t < a.Te) pre[i] = *(const f32x4*)(g.x + (a.base + t) * C + e % C);
         }
     };
     auto store_window = [&]() {
@@ -722,14 +781,15 @@ __global__ void __launch_bounds__(512) conv_small32_bf16_kernel(ConvSmallArgs g)
     };
     const int64_t first = (int64_t)blockIdx.x * nwaves + wave, step = (int64_t)gridDim.x * nwaves;
     if (first < nchunks) {
-        load_window(first * TWK);
+        load_window(first);
         store_window();
     }
     const int li = lane & 31, lh = lane >> 5;
     for (int64_t chunk = first; chunk < nchunks; chunk += step) {
-        const int64_t t0 = chunk * TWK;
+        const WinAt a = win_at(chunk, cpr, TWK, g);
+        const int64_t t0 = a.t0;
         const bool more = chunk + step < nchunks;
-        if (more) load_window((chunk + step) * TWK);
+        if (more) load_window(chunk + step);
         __builtin_amdgcn_wave_barrier();
         f32x16 acc[NT];
 #pragma unroll
@@ -762,9 +822,10 @@ __global__ void __launch_bounds__(512) conv_small32_bf16_kernel(ConvSmallArgs g)
             for (int r = 0; r < 16; ++r) {
                 const int64_t t = t0 + tt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (t < g.T) {
-                    const int64_t o = t * C + li;
+                    const int64_t o = (a.base + t) * C + li;
                     float y = acc[tt][r] + bc;
                     if (g.res) y += g.res[o];
+                    if (t >= a.Te) y = 0.f;
                     if (g.out) g.out[o] = y;
                     if (g.out_act) g.out_act[o] = y > 0.f ? y : y * g.act_slope;
                 }
@@ -790,7 +851,7 @@ static int launch_conv_small32_bf16(ddsp_ctx* ctx, hipStream_t st, const ConvSma
     const size_t lds = w_bytes + nw * win_bytes;
     DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_small32_bf16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                          DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_small32_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
-    const int64_t nchunks = (g.T + twk - 1) / twk;
+    const int64_t nchunks = (g.T + twk - 1) / twk * g.B;
     int64_t blocks = (nchunks + nw - 1) / nw;
     if (blocks > 256) blocks = 256;
     if (nt == 2)
@@ -806,7 +867,7 @@ static int launch_conv_small(ddsp_ctx* ctx, hipStream_t st, const ConvSmallArgs&
     const size_t lds = ((size_t)g.ktaps * C * C + 4 * (size_t)rows * (C + 1)) * sizeof(float);
     if (lds > 160 * 1024) return ddsp_fail(ctx, DDSP_ERR_ARG, "ddsp_conv1d", "window too long for the LDS");
     DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_small_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
-    const int64_t nchunks = (g.T + CS_TW - 1) / CS_TW;
+    const int64_t nchunks = (g.T + CS_TW - 1) / CS_TW * g.B;
     int64_t blocks = (nchunks + 3) / 4;
     const int64_t cap = 256 * (lds > 80 * 1024 ? 1 : lds > 53 * 1024 ? 2 : 3);
     if (blocks > cap) blocks = cap;
@@ -823,11 +884,19 @@ struct EpiAddBias {   // y = acc + bias[n] (+ res): C = y and / or Cact = leaky_
     const float* bias;
     float slope;
     int act_split;   // Cact is written as bf16 hi/lo groups (the A operand layout of gemm::Args::A_split); vector path only
+    const int* nfr;  // ragged batch: row m = b * Tmax + t is past its row's end when t >= nfr[b] * nscale, and is written as 0
+    int nscale, Tmax;
+    __device__ __forceinline__ bool past(int m) const {
+        if (!nfr) return false;
+        const int b = m / Tmax;
+        return m - b * Tmax >= ddsp_row_frames(nfr, b, Tmax / nscale) * nscale;
+    }
     __device__ __forceinline__ float col(int n) const { return bias ? bias[n] : 0.f; }
     __device__ __forceinline__ void operator()(int, int m, int n, float v, float cb) const {
         const int64_t o = (int64_t)m * ldc + n;
         float y = v + cb;
         if (res) y += res[o];
+        if (past(m)) y = 0.f;
         if (C) C[o] = y;
         if (Cact) Cact[o] = y > 0.f ? y : y * slope;
     }
@@ -839,6 +908,7 @@ struct EpiAddBias {   // y = acc + bias[n] (+ res): C = y and / or Cact = leaky_
         const int64_t o = (int64_t)m * ldc + n;
         if (bias) v += *(const gemm::f32x4_u*)(bias + n);
         if (res) v += *(const f32x4*)(res + o);
+        if (past(m)) v = f32x4{0.f, 0.f, 0.f, 0.f};
         if (C) *(f32x4*)(C + o) = v;
         if (Cact) {
 #pragma unroll
@@ -887,17 +957,19 @@ __global__ void __launch_bounds__(512) conv_pair32_bf16_kernel(ConvPairRawArgs g
         bias[threadIdx.x] = b ? b[threadIdx.x % C] : 0.f;
     }
     __syncthreads();
-    const int64_t nchunks = (g.T + tw - 1) / tw;
+    const int64_t cpr = (g.T + tw - 1) / tw, nchunks = cpr * g.B;
     constexpr int NV = ((RT + 2 * 25) * C / 4 + 63) / 64;
     const int nvec = rows * C / 4;
     f32x4 pre[NV];
-    auto load_window = [&](int64_t t0) {
+    auto load_window = [&](int64_t chunk) {
+        const WinAt a = win_at(chunk, cpr, tw, g);
+        const int64_t t0 = a.t0;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int e = (lane + 64 * i) * 4;
             const int64_t t = t0 - h2 - h1 + e / C;
             pre[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (lane + 64 * i < nvec && t >= 0 && t < g.T) pre[i] = *(const f32x4*)(g.x + t * C + e % C);
+            if (lane + 64 * i < nvec && t >= 0 && t < a.Te) pre[i] = *(const f32x4*)(g.x + (a.base + t) * C + e % C);
         }
     };
     auto store_window = [&]() {
@@ -920,7 +992,7 @@ __global__ void __launch_bounds__(512) conv_pair32_bf16_kernel(ConvPairRawArgs g
     const int li = lane & 31, lh = lane >> 5;
     const int64_t first = (int64_t)blockIdx.x * nwaves + wave, step = (int64_t)gridDim.x * nwaves;
     if (first < nchunks) {
-        load_window(first * tw);
+        load_window(first);
         store_window();
     }
     // D[co = (r & 3) + 8 (r >> 2) + 4 lh][frame = li] = bias[co] + sum over (tap, ci) of W[co][tap, ci] * src[frame + tap * dd][ci]
@@ -952,7 +1024,8 @@ __global__ void __launch_bounds__(512) conv_pair32_bf16_kernel(ConvPairRawArgs g
         }
     };
     for (int64_t chunk = first; chunk < nchunks; chunk += step) {
-        const int64_t t0 = chunk * tw;
+        const WinAt a = win_at(chunk, cpr, tw, g);
+        const int64_t t0 = a.t0;
         const bool more = chunk + step < nchunks;
         f32x4 res[NT][4];
 #pragma unroll
@@ -961,10 +1034,10 @@ __global__ void __launch_bounds__(512) conv_pair32_bf16_kernel(ConvPairRawArgs g
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 res[tt][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (o < tw && t0 + o < g.T) res[tt][q] = *(const f32x4*)(g.x + (t0 + o) * C + 8 * q + 4 * lh);
+                if (o < tw && t0 + o < a.Te) res[tt][q] = *(const f32x4*)(g.x + (a.base + t0 + o) * C + 8 * q + 4 * lh);
             }
         }
-        if (more) load_window((chunk + step) * tw);
+        if (more) load_window(chunk + step);
         __builtin_amdgcn_wave_barrier();
         f32x16 acc[NT];
         conv(wl1, bias, win, g.dil, acc);
@@ -973,7 +1046,7 @@ __global__ void __launch_bounds__(512) conv_pair32_bf16_kernel(ConvPairRawArgs g
         for (int tt = 0; tt < NT; ++tt) {
             const int u = tt * 32 + li;
             const int64_t t = t0 - h2 + u;
-            const bool in = t >= 0 && t < g.T;
+            const bool in = t >= 0 && t < a.Te;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float y[4];
@@ -998,10 +1071,10 @@ __global__ void __launch_bounds__(512) conv_pair32_bf16_kernel(ConvPairRawArgs g
             if (o < tw && t0 + o < g.T) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int64_t at = (t0 + o) * C + 8 * q + 4 * lh;
+                    const int64_t at = (a.base + t0 + o) * C + 8 * q + 4 * lh;
                     f32x4 y = res[tt][q];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) y[r] += acc[tt][4 * q + r];
+                    for (int r = 0; r < 4; ++r) y[r] = t0 + o < a.Te ? y[r] + acc[tt][4 * q + r] : 0.f;
                     if (g.out) *(f32x4*)(g.out + at) = y;
                     if (g.out_act) {
 #pragma unroll
@@ -1058,10 +1131,12 @@ extern "C" int ddsp_conv1d_pair_supported(ddsp_ctx* ctx, int C, int ktaps, int d
     }
     return 0;
 }
-extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
-                                const float* b2, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act) {
+static int conv1d_pair_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
+                          const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act,
+                          const int32_t* n_frames, int frame_scale) {
     DDSP_REQUIRE(ctx, ctx && x && w1 && w2 && (out || out_act), "ddsp_conv1d_pair: null argument");
-    DDSP_REQUIRE(ctx, T >= 1 && T < (1 << 30), "ddsp_conv1d_pair: bad length");
+    DDSP_REQUIRE(ctx, B >= 1 && T >= 1 && B * T < (1 << 30), "ddsp_conv1d_pair: bad length");
+    DDSP_REQUIRE(ctx, frame_scale >= 1 && T % frame_scale == 0, "ddsp_conv1d_pair: T must be whole frames of frame_scale");
     DDSP_REQUIRE(ctx, ddsp_conv1d_pair_supported(ctx, C, ktaps, dil) == 1,
                  "ddsp_conv1d_pair: 16 channels (32 with split-bf16 products), odd tap counts up to 11, dilation up to 5 (ask ddsp_conv1d_pair_supported)");
     DDSP_REQUIRE(ctx, (((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)out | (uintptr_t)out_act) % 16) == 0 &&
@@ -1069,7 +1144,7 @@ extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, con
                  "ddsp_conv1d_pair: 16-byte aligned tensors, not in place");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
-    ConvPairRawArgs a{x, w1, b1, w2, b2, out, out_act, T, ktaps, dil, slope};
+    ConvPairRawArgs a{x, w1, b1, w2, b2, out, out_act, T, ktaps, dil, slope, (int)B, (const int*)n_frames, frame_scale};
     ddsp_prof_begin(ctx, st, PF_OTHER);
     if (C == 32) {
         int nt, nw;
@@ -1078,7 +1153,7 @@ extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, con
         DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_pair32_bf16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                              DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_pair32_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
         const int tw = 32 * nt - (ktaps - 1);
-        const int64_t nchunks = (T + tw - 1) / tw;
+        const int64_t nchunks = (T + tw - 1) / tw * B;
         int64_t blocks = (nchunks + nw - 1) / nw;
         if (blocks > 256) blocks = 256;
         if (nt == 2)
@@ -1089,7 +1164,7 @@ extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, con
         const int halo = (ktaps - 1) / 2 * (dil + 1), rows = CS_TW + 2 * halo;
         const size_t lds = ((size_t)2 * ktaps * C * C + 4 * (size_t)(rows + CP_MID) * (C + 1)) * sizeof(float);
         DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_pair16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
-        const int64_t nchunks = (T + CS_TW - 1) / CS_TW;
+        const int64_t nchunks = (T + CS_TW - 1) / CS_TW * B;
         int64_t blocks = (nchunks + 3) / 4;
         const int64_t cap = 256 * (lds > 80 * 1024 ? 1 : lds > 53 * 1024 ? 2 : 3);
         if (blocks > cap) blocks = cap;
@@ -1101,20 +1176,31 @@ extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, con
         const size_t lds = pair16_bf16_lds(ktaps, dil, NT, nw);
         DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)conv_pair16_bf16_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
         const int tw = 16 * NT - (ktaps - 1);
-        const int64_t nchunks = (T + tw - 1) / tw;
+        const int64_t nchunks = (T + tw - 1) / tw * B;
         int64_t blocks = (nchunks + nw - 1) / nw;
         if (blocks > 256) blocks = 256;       // (210 VGPRs: the 8 wavefronts of one workgroup are a CU's share)
         hipLaunchKernelGGL(conv_pair16_bf16_kernel<NT>, dim3((unsigned)blocks), dim3(64 * nw), lds, st, a);
     }
-    ddsp_prof_end(ctx, st, 4.0 * T * C * C * ktaps, 8.0 * T * C);
+    ddsp_prof_end(ctx, st, 4.0 * B * T * C * C * ktaps, 8.0 * B * T * C);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
+extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
+                                const float* b2, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act) {
+    return conv1d_pair_go(ctx, stream, x, w1, b1, w2, b2, 1, T, C, ktaps, dil, slope, out, out_act, nullptr, 1);
+}
+extern "C" int ddsp_conv1d_pair_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1,
+                                       const float* w2, const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil,
+                                       float slope, float* out, float* out_act, const int32_t* n_frames, int frame_scale) {
+    return conv1d_pair_go(ctx, stream, x, w1, b1, w2, b2, B, T, C, ktaps, dil, slope, out, out_act, n_frames, frame_scale);
+}
 
-extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t T,
-                           int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out,
-                           float* out_act, float act_slope, const float* w_split, int flags) {
+static int conv1d_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B, int64_t Tr,
+                     int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out,
+                     float* out_act, float act_slope, const float* w_split, int flags, const int32_t* n_frames, int frame_scale) {
     DDSP_REQUIRE(ctx, ctx && x && w_packed && (out || out_act), "ddsp_conv1d: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && Tr >= 1 && frame_scale >= 1 && Tr % frame_scale == 0, "ddsp_conv1d: bad batch (T must be whole frames of frame_scale)");
+    const int64_t T = B * Tr;      // rows of the GEMM: the batch flattened on the time axis, taps wrap with m % Tr
     DDSP_REQUIRE(ctx, T >= 1 && T < (1 << 30) && Cin >= 4 && Cin % 4 == 0 && Cout >= 1 && ktaps >= 1 && ktaps % 2 == 1 &&
                           ktaps <= 63 && dil >= 1 && dil <= 64,
                  "ddsp_conv1d: bad shape (Cin % 4 == 0, odd tap count)");
@@ -1122,13 +1208,13 @@ extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const fl
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     gemm::Args g = gemm::make(x, Cin, w_packed, (int64_t)ktaps * Cin, (int)T, Cout, ktaps * Cin);
-    g.Fr = (int)T;
+    g.Fr = (int)Tr;
     g.Cin = Cin;
     g.ktaps = ktaps;
     g.dil = dil;
     g.in_slope = in_slope;
     const bool x_split = (flags & DDSP_CONV_X_SPLIT) != 0, act_split = (flags & DDSP_CONV_ACT_SPLIT) != 0;
-    EpiAddBias e{out, out_act, residual, Cout, bias, act_slope, act_split ? 1 : 0};
+    EpiAddBias e{out, out_act, residual, Cout, bias, act_slope, act_split ? 1 : 0, (const int*)n_frames, frame_scale, (int)Tr};
     const bool dma = in_slope == 1.0f && Cin % 32 == 0 && gemm::dma_ok(g);
     DDSP_REQUIRE(ctx, !(x_split || act_split) || (dma && ctx->math != DDSP_MATH_FP32 && w_split && gemm::dma_ok(g)),
                  "ddsp_conv1d: split operands need the LDS-DMA path (in_slope = 1, Cin % 32 == 0), split-bf16 arithmetic and w_split");
@@ -1142,12 +1228,12 @@ extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const fl
         // convolutions of the 16-channel stage at 860 frames).  A 32-channel fp32 instantiation was measured and removed: at
         // 1.48 ms per stage it did not beat the LDS-DMA GEMM's 1.28 - one wave per SIMD (105 KB of LDS per workgroup) on the
         // fp32 matrix pipe reaches a third of its rate.
-        ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, T, ktaps, dil, in_slope, act_slope};
+        ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, Tr, ktaps, dil, in_slope, act_slope, (int)B, (const int*)n_frames, frame_scale};
         if (int rc = launch_conv_small<16>(ctx, st, a)) return rc;
     } else if (Cin == Cout && Cin == 32 && ctx->math != DDSP_MATH_FP32 && !x_split && !act_split &&
                (((uintptr_t)x | (uintptr_t)w_packed) % 16) == 0 && (ktaps - 1) / 2 * dil <= CS_MAX_HALO) {
         // the 32-channel stage in split-bf16 arithmetic: the narrow kernel with bf16 fragments
-        ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, T, ktaps, dil, in_slope, act_slope};
+        ConvSmallArgs a{x, w_packed, bias, residual, out, out_act, Tr, ktaps, dil, in_slope, act_slope, (int)B, (const int*)n_frames, frame_scale};
         if (int rc = launch_conv_small32_bf16(ctx, st, a)) return rc;
     } else if (dma) {
         // an input that needs no activation on load: the LDS-DMA kernel with per-tap row pointers, products in the context's
@@ -1185,30 +1271,56 @@ extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const fl
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
+extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t T,
+                           int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out,
+                           float* out_act, float act_slope, const float* w_split, int flags) {
+    return conv1d_go(ctx, stream, x, w_packed, bias, 1, T, Cin, Cout, ktaps, dil, in_slope, residual, out, out_act, act_slope,
+                     w_split, flags, nullptr, 1);
+}
+extern "C" int ddsp_conv1d_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B,
+                                  int64_t T, int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual,
+                                  float* out, float* out_act, float act_slope, const float* w_split, int flags,
+                                  const int32_t* n_frames, int frame_scale) {
+    return conv1d_go(ctx, stream, x, w_packed, bias, B, T, Cin, Cout, ktaps, dil, in_slope, residual, out, out_act, act_slope,
+                     w_split, flags, n_frames, frame_scale);
+}
 
-extern "C" int ddsp_nsf_source(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
-                               const float* lin_b, int64_t L, int upp, int sr, float sine_amp, float* out) {
+static int nsf_source_go(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
+                         const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp, const int32_t* n_frames,
+                         float* out) {
     DDSP_REQUIRE(ctx, ctx && f0 && rand_ini && lin_w && lin_b && out, "ddsp_nsf_source: null argument");
-    DDSP_REQUIRE(ctx, L >= 1 && L < (1 << 24) && upp >= 1 && upp <= 65536 && sr >= 1, "ddsp_nsf_source: bad shape");
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && L >= 1 && B * L < (1 << 24) && upp >= 1 && upp <= 65536 && sr >= 1,
+                 "ddsp_nsf_source: bad shape");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
-    int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)L * NH * sizeof(double) + 4096);
+    const size_t bytes = (size_t)B * L * NH * sizeof(double);      // the scan's scratch grows with the batch
+    int rc = ddsp_scratch_reserve_bytes(ctx, bytes + 4096);
     if (rc) return rc;
     ddsp_scratch_reset(ctx);
     double* prefix = nullptr;
-    if ((rc = ddsp_scratch_get(ctx, (size_t)L * NH * sizeof(double), (void**)&prefix))) return rc;
-    hipLaunchKernelGGL(nsf_frame_prefix_kernel, dim3(NH), dim3(64), 0, st, f0, rand_ini, (int)L, upp, (float)sr, prefix);
+    if ((rc = ddsp_scratch_get(ctx, bytes, (void**)&prefix))) return rc;
+    hipLaunchKernelGGL(nsf_frame_prefix_kernel, dim3(NH, (unsigned)B), dim3(64), 0, st, f0, rand_ini, (int)L, upp, (float)sr, prefix,
+                       (const int*)n_frames);
     const int64_t n = L * upp;
-    hipLaunchKernelGGL(nsf_source_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f0, rand_ini, prefix, lin_w, lin_b,
-                       (int)L, upp, (float)sr, sine_amp, out);
+    hipLaunchKernelGGL(nsf_source_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, st, f0, rand_ini, prefix,
+                       lin_w, lin_b, (int)L, upp, (float)sr, sine_amp, out, (const int*)n_frames);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
+extern "C" int ddsp_nsf_source(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
+                               const float* lin_b, int64_t L, int upp, int sr, float sine_amp, float* out) {
+    return nsf_source_go(ctx, stream, f0, rand_ini, lin_w, lin_b, 1, L, upp, sr, sine_amp, nullptr, out);
+}
+extern "C" int ddsp_nsf_source_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
+                                      const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp,
+                                      const int32_t* n_frames, float* out) {
+    return nsf_source_go(ctx, stream, f0, rand_ini, lin_w, lin_b, B, L, upp, sr, sine_amp, n_frames, out);
+}
 
-extern "C" int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src, int64_t T_src, const float* w,
-                                   const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
+static int nsf_noise_conv_go(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
+                             const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
     DDSP_REQUIRE(ctx, ctx && src && w && b && out, "ddsp_nsf_noise_conv: null argument");
-    DDSP_REQUIRE(ctx, T_src >= 1 && T_out >= 1 && C >= 1 && K >= 1 && stride >= 1 && pad >= 0 && T_out * C < ((int64_t)1 << 40),
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && T_src >= 1 && T_out >= 1 && C >= 1 && K >= 1 && stride >= 1 && pad >= 0 && T_out * C < ((int64_t)1 << 40),
                  "ddsp_nsf_noise_conv: bad shape");
     DDSP_REQUIRE(ctx, (T_out - 1) * stride - pad < T_src, "ddsp_nsf_noise_conv: output longer than the source allows");
     hipStream_t st = (hipStream_t)stream;
@@ -1216,24 +1328,42 @@ extern "C" int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src
     const int Cb = C < 256 ? C : 256, G = 256 / Cb;
     const size_t lds = ((size_t)(G * NC_TT - 1) * stride + K) * sizeof(float);
     DDSP_REQUIRE(ctx, lds <= 64 * 1024, "ddsp_nsf_noise_conv: source window too long for the LDS");
-    hipLaunchKernelGGL(nsf_noise_conv_kernel, dim3((unsigned)((T_out + (int64_t)G * NC_TT - 1) / ((int64_t)G * NC_TT)), (unsigned)((C + Cb - 1) / Cb)), dim3(256), lds, st, src,
+    hipLaunchKernelGGL(nsf_noise_conv_kernel, dim3((unsigned)((T_out + (int64_t)G * NC_TT - 1) / ((int64_t)G * NC_TT)), (unsigned)((C + Cb - 1) / Cb), (unsigned)B), dim3(256), lds, st, src,
                        T_src, w, b, T_out, C, K, stride, pad, out);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
+extern "C" int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src, int64_t T_src, const float* w,
+                                   const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
+    return nsf_noise_conv_go(ctx, stream, src, 1, T_src, w, b, C, K, stride, pad, T_out, out);
+}
+extern "C" int ddsp_nsf_noise_conv_ragged(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
+                                          const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
+    return nsf_noise_conv_go(ctx, stream, src, B, T_src, w, b, C, K, stride, pad, T_out, out);
+}
 
-extern "C" int ddsp_nsf_post(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t T, int C, int K,
-                             float slope, float* out) {
+static int nsf_post_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T, int C,
+                       int K, float slope, float* out, const int32_t* n_frames, int frame_scale) {
     DDSP_REQUIRE(ctx, ctx && x && w && b && out, "ddsp_nsf_post: null argument");
-    DDSP_REQUIRE(ctx, T >= 1 && C >= 1 && K >= 1 && K % 2 == 1, "ddsp_nsf_post: bad shape");
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && T >= 1 && T < ((int64_t)1 << 31) && C >= 1 && K >= 1 && K % 2 == 1 && frame_scale >= 1 &&
+                          T % frame_scale == 0,
+                 "ddsp_nsf_post: bad shape");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const size_t lds = (size_t)(256 + K - 1) * (C + 1) * sizeof(float);
     const int use_lds = lds <= 64 * 1024 ? 1 : 0;
-    hipLaunchKernelGGL(nsf_post_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), use_lds ? lds : 0, st, x, w, b, T, C, K, slope, out,
-                       use_lds);
+    hipLaunchKernelGGL(nsf_post_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), use_lds ? lds : 0, st, x, w, b, T, C,
+                       K, slope, out, use_lds, (const int*)n_frames, frame_scale);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+extern "C" int ddsp_nsf_post(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t T, int C, int K,
+                             float slope, float* out) {
+    return nsf_post_go(ctx, stream, x, w, b, 1, T, C, K, slope, out, nullptr, 1);
+}
+extern "C" int ddsp_nsf_post_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T,
+                                    int C, int K, float slope, float* out, const int32_t* n_frames, int frame_scale) {
+    return nsf_post_go(ctx, stream, x, w, b, B, T, C, K, slope, out, n_frames, frame_scale);
 }
 
 extern "C" int ddsp_nsf_mean(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* c, int n_terms, int64_t n,
@@ -1288,6 +1418,49 @@ extern "C" int ddsp_log_mel(ddsp_ctx* ctx, void* stream, const float* frames, co
     }
     hipLaunchKernelGGL(nsf_logclamp_kernel, dim3((unsigned)((n_frames * n_mels + 255) / 256)), dim3(256), 0, st, out,
                        n_frames * n_mels, clip);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+// ---- STFT framing of a (ragged) batch: `STFT.get_mel`'s padding rule (nvSTFT.py:88-98) chosen PER ROW -------------------------
+// Row b has Tb = n_samples[b] samples: pad_left = (n - hop) / 2, pad_right = max((n - hop + 1) / 2, n - Tb - pad_left), reflect
+// padding where pad_right < Tb and zeros otherwise, L_b = (Tb + pad_left + pad_right - n) / hop + 1 frames; frames >= L_b hold 0.
+// What follows a row's samples is never read.
+namespace {
+__global__ void __launch_bounds__(256) nsf_stft_frames_kernel(const float* __restrict__ audio, int64_t T, const int* __restrict__ n,
+                                                              int n_fft, int hop, int64_t L, float* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= L * n_fft) return;
+    const int64_t b = blockIdx.y, l = idx / n_fft;
+    const int j = (int)(idx - l * n_fft);
+    int64_t Tb = n ? (int64_t)n[b] : T;
+    Tb = Tb < 1 ? 1 : (Tb > T ? T : Tb);
+    const int64_t pl = (n_fft - hop) / 2, pr0 = (n_fft - hop + 1) / 2, pr1 = n_fft - Tb - pl, pr = pr0 > pr1 ? pr0 : pr1;
+    const bool reflect = pr < Tb;
+    const int64_t Lb = (Tb + pl + pr - n_fft) / hop + 1;
+    float v = 0.f;
+    if (l < Lb) {
+        int64_t i = l * hop + j - pl;
+        if (i < 0)
+            i = reflect ? -i : -1;
+        else if (i >= Tb)
+            i = reflect ? 2 * (Tb - 1) - i : -1;
+        if (i >= 0 && i < Tb) v = audio[b * T + i];
+    }
+    out[(b * L + l) * n_fft + j] = v;
+}
+}  // namespace
+
+extern "C" int ddsp_stft_frames_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
+                                       const int32_t* n_samples, int n_fft, int hop, int64_t L, float* out) {
+    DDSP_REQUIRE(ctx, ctx && audio && out, "ddsp_stft_frames_ragged: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && T >= 1 && n_fft >= 1 && hop >= 1 && hop <= n_fft && L >= 1 &&
+                          B * L * n_fft < ((int64_t)1 << 40) && L * n_fft < ((int64_t)1 << 38),
+                 "ddsp_stft_frames_ragged: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    hipLaunchKernelGGL(nsf_stft_frames_kernel, dim3((unsigned)((L * n_fft + 255) / 256), (unsigned)B), dim3(256), 0, st, audio, T,
+                       (const int*)n_samples, n_fft, hop, L, out);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

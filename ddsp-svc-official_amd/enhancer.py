@@ -4,6 +4,10 @@ libddsp_amd on the device (no CPU path).
 
     Enhancer(enhancer_type, enhancer_ckpt, device).enhance(audio (1,T), sample_rate, f0 (1,Fr,1), hop_size,
                                                            adaptive_key=0 | 'auto', silence_front=0) -> (audio (1,T'), sr)
+    Enhancer.enhance_batch(audio (B,T), sample_rate, f0 (B,Fr,1), hop_size, n_samples, adaptive_key=0 | 'auto')
+                                                           -> (audio (B,T'_max), sr, n_out): rows of different length in one
+    padded batch, every row as if enhanced alone at its own length and 0 after it (`Generator.forward(..., n_frames=)`,
+    `STFT.get_mel(..., n_samples=)`, `NsfHifiGAN.forward(..., n_samples=)` are the same contract one level down).
 
 Checkpoints are read with `torch.load(weights_only=True)` (`{'generator': state_dict}` next to a `config.json`, as
 `nsf_hifigan/models.py:24-39` expects); weight-normed layers (`weight_g`, `weight_v`) are folded at load time like the
@@ -20,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 import hipddsp
+from ddsp.hubert import RaggedCounts
 from resample import Resample
 
 LRELU_SLOPE = 0.1
@@ -68,7 +73,9 @@ def mel_filterbank(sr, n_fft, n_mels, fmin, fmax):
 
 class STFT:
     """`nsf_hifigan/nvSTFT.py:52-119` for keyshift = 0, speed = 1: reflect padding, Hann(periodic) window, magnitude with the
-    1e-9 floor, mel projection, log of the clamped value.  `get_mel(y (1,T)) -> (1, n_mels, frames)`."""
+    1e-9 floor, mel projection, log of the clamped value.  `get_mel(y (1,T)) -> (1, n_mels, frames)`;
+    `get_mel(y (B,T), n_samples=)` -> (B, n_mels, L_max): a ragged batch, row b framed and padded as its own n_samples[b]
+    samples would be alone (reflect or zeros, chosen per row), 0 in the frames after its own `frame_count(n_samples[b])`."""
 
     def __init__(self, sr=22050, n_mels=80, n_fft=1024, win_size=1024, hop_length=256, fmin=20, fmax=11025, clip_val=1e-5):
         if win_size != n_fft:
@@ -94,13 +101,23 @@ class STFT:
             self._tables[key] = (tab.float().to(device).contiguous(), mel.to(device).contiguous())
         return self._tables[key]
 
-    def get_mel(self, y, keyshift=0, speed=1, center=False):
+    def frame_count(self, n_samples):
+        """Frames `get_mel` gives for a signal of n_samples (host integers: nvSTFT.py:88-98 pads, torch.stft frames)."""
+        n, hop = self.n_fft, self.hop_length
+        pad_left = (n - hop) // 2
+        pad_right = max((n - hop + 1) // 2, n - int(n_samples) - pad_left)
+        return (int(n_samples) + pad_left + pad_right - n) // hop + 1
+
+    def get_mel(self, y, keyshift=0, speed=1, center=False, n_samples=None):
         if keyshift != 0 or speed != 1 or center:
             raise ValueError("only keyshift = 0, speed = 1, center = False (how the Enhancer calls it) is built")
+        if y.dim() != 2:
+            raise ValueError("STFT.get_mel: y must be (B, T)")
+        vals = None if n_samples is None else hipddsp.check_n_samples(n_samples, y.shape[0], y.shape[1])
         if not y.is_cuda:
             raise RuntimeError("STFT.get_mel runs on a HIP device only (no CPU fallback)")
-        if y.shape[0] != 1:
-            raise ValueError("one utterance per call, like the reference's Enhancer")
+        if y.shape[0] != 1 or vals is not None:
+            return self._get_mel_batch(y, vals)
         n, hop = self.n_fft, self.hop_length
         pad_left = (n - hop) // 2
         pad_right = max((n - hop + 1) // 2, n - y.size(-1) - pad_left)
@@ -110,6 +127,21 @@ class STFT:
         tab, mel = self._device_tables(y.device)
         out = hipddsp.context_for(y.device).log_mel(frames, tab, mel, self.clip_val)      # (frames, n_mels)
         return out.t().unsqueeze(0)
+
+    def _get_mel_batch(self, y, vals):
+        """Rows of different length (vals: checked counts, None = every row whole): framing on the device with the padding
+        rule chosen per row, then the spectral half on B * L_max rows."""
+        B, T = y.shape
+        c = hipddsp.context_for(y.device)
+        frames_of = [self.frame_count(v) for v in (vals if vals is not None else [T] * B)]
+        L = max(frames_of)
+        n_dev = None if vals is None else c.ragged_counts(vals)
+        frames = c.stft_frames_ragged(y, n_dev, self.n_fft, self.hop_length, L)
+        tab, mel = self._device_tables(y.device)
+        out = c.log_mel(frames.reshape(B * L, self.n_fft), tab, mel, self.clip_val).reshape(B, L, self.n_mels)
+        if vals is not None:          # log-mel of an empty frame is log(clip), not 0
+            out = c.ragged_frames(out, c.ragged_counts(frames_of), hold=False)
+        return out.transpose(1, 2)
 
 
 # ---- the generator -------------------------------------------------------------------------------------------------------------
@@ -155,9 +187,13 @@ def _pack_conv_transpose(w, stride):
 
 
 class Generator(torch.nn.Module):
-    """`nsf_hifigan/models.py:219-276` (inference).  Built from the reference's state dict; `forward(x (1, n_mels, L), f0 (1, L))
-    -> (1, 1, L * prod(upsample_rates))`.  `rand_ini` (9,) injects the harmonics' random initial phases (the reference draws
-    them with torch.rand; element 0 is forced to 0 like there)."""
+    """`nsf_hifigan/models.py:219-276` (inference).  Built from the reference's state dict; `forward(x (B, n_mels, L), f0 (B, L))
+    -> (B, 1, L * prod(upsample_rates))`.  `rand_ini` (9,) or (B, 9) injects the harmonics' random initial phases (the
+    reference draws them with torch.rand; element 0 is forced to 0 like there).
+    `n_frames` (a sequence of B ints or a CPU integer tensor, 1 <= n_frames[b] <= L; checked on the host, uploaded once): a
+    RAGGED batch - row b comes out, over its first n_frames[b] * upp samples, as the row run alone at its own length, and
+    exactly 0 after them, whatever x and f0 hold past n_frames[b].  None: every row is L long.  `Generator.counts` checks and
+    uploads ahead of the call (inside a HIP graph capture nothing may be uploaded): pass what it returns as `n_frames`."""
 
     def __init__(self, h, state_dict=None):
         super().__init__()
@@ -234,21 +270,50 @@ class Generator(torch.nn.Module):
             self._dev = (device, {k: mv(v) for k, v in self._packed.items()})
         return self._dev[1]
 
+    @staticmethod
+    def counts(n_frames, B, L, device):
+        """`n_frames` of a ragged (B, n_mels, L) batch, checked on the host and uploaded once -> `RaggedCounts`."""
+        vals = hipddsp.check_n_frames(n_frames, B, L)
+        return RaggedCounts(vals, L, hipddsp.context_for(device).ragged_counts(vals))
+
     @torch.no_grad()
-    def forward(self, x, f0, rand_ini=None):
+    def forward(self, x, f0, rand_ini=None, n_frames=None):
+        if x.dim() != 3:
+            raise ValueError("Generator: x must be (B, n_mels, L)")
+        B, n_mels, L = x.shape
+        if isinstance(n_frames, RaggedCounts):
+            if len(n_frames.values) != B or n_frames.T != L or n_frames.dev.device != x.device:
+                raise ValueError("Generator: these RaggedCounts were made for another batch shape or device")
+            n_dev = n_frames.dev
+        elif n_frames is not None:
+            n_frames = hipddsp.check_n_frames(n_frames, B, L)          # ValueError before anything is launched
         if not x.is_cuda:
             raise RuntimeError("the NSF-HiFiGAN generator runs on a HIP device only (no CPU fallback)")
-        if x.shape[0] != 1:
-            raise ValueError("one utterance per call, like the reference's Enhancer")
         P = self._on(x.device)
         c = hipddsp.context_for(x.device)
-        L = x.shape[-1]
-        f0 = f0.reshape(-1)[:L].contiguous().float()
+        if n_frames is None:
+            n_dev = None
+        elif not isinstance(n_frames, RaggedCounts):
+            n_dev = c.ragged_counts(n_frames)
+        # B rows flattened on the time axis, (B * T, C); `rows(scale)` tells a call where each row ends at the current rate
+        # (None: the solo entry points, one utterance and no counts)
+        batched = B != 1 or n_dev is not None
+
+        def rows(scale):
+            return (B, n_dev, scale) if batched else None
+
+        f0 = f0.reshape(B, -1)[:, :L].contiguous().float()
         if rand_ini is None:
-            rand_ini = torch.rand(9)
-        rand_ini = rand_ini.clone().float().reshape(9)
-        rand_ini[0] = 0
-        src = c.nsf_source(f0, rand_ini.to(x.device), P["lin_w"], P["lin_b"], self.upp, int(self.h.sampling_rate), 0.1)
+            rand_ini = torch.rand(B, 9)
+        rand_ini = rand_ini.float()
+        rand_ini = (rand_ini.reshape(1, 9).expand(B, 9) if rand_ini.numel() == 9 else rand_ini.reshape(B, 9)).clone()
+        rand_ini[:, 0] = 0
+        rand_ini = rand_ini.to(x.device)
+        sr = int(self.h.sampling_rate)
+        if batched:
+            src = c.nsf_source_ragged(f0, rand_ini, P["lin_w"], P["lin_b"], self.upp, sr, 0.1, n_dev)       # (B, L * upp)
+        else:
+            src = c.nsf_source(f0[0], rand_ini[0], P["lin_w"], P["lin_b"], self.upp, sr, 0.1)
         # Every convolution below reads leaky_relu(., 0.1) of its producer's result (models.py:60-62, 251): the producers
         # write that activated copy themselves (`act_slope`), next to the raw result where a residual path or the stage mean
         # needs it, so that the consumers take their input as it is (in_slope = 1) and run on the LDS-DMA GEMM.  With
@@ -261,29 +326,38 @@ class Generator(torch.nn.Module):
             its output rows are whole 64-column tiles."""
             return use_split and cin % 32 == 0 and cout % 64 == 0
 
-        n_mels = x.shape[1]
         ch0 = int(self.h.upsample_initial_channel)
         act_s = can_split(n_mels, ch0)               # is the current activated tensor in the split layout?
-        _, cur_act = c.conv1d(x[0].t().contiguous(), P["pre_w"], P["pre_b"], P["pre_k"], 1, 1.0, want_out=False,
-                              act_slope=LRELU_SLOPE, w_split=P["pre_ws"] if act_s else None, act_split=act_s)   # (L, C0)
+        xin = x.transpose(1, 2).contiguous()         # (B, L, n_mels)
+        if n_dev is not None:                        # what a convolution reads is 0 past the row's end: the mel may hold anything
+            xin = c.ragged_frames(xin.float(), n_dev, hold=False)
+        _, cur_act = c.conv1d(xin.reshape(B * L, n_mels), P["pre_w"], P["pre_b"], P["pre_k"], 1, 1.0, want_out=False,
+                              act_slope=LRELU_SLOPE, w_split=P["pre_ws"] if act_s else None, act_split=act_s,
+                              rows=rows(1))          # (B * L, C0)
         T, cin = L, ch0
         cur = None
         for i in range(self.num_upsamples):
             w_up, w_up_s, b_up, u, cout = P["ups"][i]
             nw, nb, (nk, ns, npad) = P["noise"][i]
             T_out = T * u
-            x_source = c.nsf_noise_conv(src, nw, nb, nk, ns, npad, T_out)                          # (T_out, cout)
+            if batched:
+                x_source = c.nsf_noise_conv_ragged(src, nw, nb, nk, ns, npad, T_out)               # (B * T_out, cout)
+            else:
+                x_source = c.nsf_noise_conv(src, nw, nb, nk, ns, npad, T_out)                      # (T_out, cout)
             s_out = can_split(cin, cout)
             # a narrow stage whose residual pairs run fused (x in, x out, activations on load: csrc/nsf.hip, conv_pair*) needs no
             # activated copies at all
             fused = all(c.conv1d_pair_supported(cout, k, d) for convs in P["res"][i] for (_, _, _, d, _, _, _, k) in convs)
-            up, up_act = c.conv1d(cur_act, w_up, b_up, 3, 1, 1.0, residual=x_source.reshape(T, u * cout),
+            # (the (B * T, u * cout) result is the (B * T_out, cout) output, u samples of one row per line: masked per INPUT row)
+            up, up_act = c.conv1d(cur_act, w_up, b_up, 3, 1, 1.0, residual=x_source.reshape(B * T, u * cout),
                                   act_slope=None if fused else LRELU_SLOPE,
-                                  w_split=w_up_s if (act_s or s_out) else None, x_split=act_s, act_split=s_out), None
+                                  w_split=w_up_s if (act_s or s_out) else None, x_split=act_s, act_split=s_out,
+                                  rows=rows(T // L)), None
             if not fused:
                 up, up_act = up
-            cur, cur_act = up.reshape(T_out, cout), None if fused else up_act.reshape(T_out, cout)
+            cur, cur_act = up.reshape(B * T_out, cout), None if fused else up_act.reshape(B * T_out, cout)
             T = T_out
+            here = rows(T // L)                       # every convolution of this stage runs at this rate
             outs = []
             s = s_out                                 # inside a stage every convolution is cout -> cout
             ws_ok = use_split and cout % 32 == 0      # pre-split weights alone still save the weight half of the in-loop split
@@ -291,15 +365,16 @@ class Generator(torch.nn.Module):
                 xr, xr_act = cur, cur_act
                 for t, (w1, w1s, b1, d, w2, w2s, b2, k) in enumerate(convs):
                     if fused:
-                        xr, _ = c.conv1d_pair(xr, w1, b1, w2, b2, k, d, LRELU_SLOPE)
+                        xr, _ = c.conv1d_pair(xr, w1, b1, w2, b2, k, d, LRELU_SLOPE, rows=here)
                         continue
                     _, xt_act = c.conv1d(xr_act, w1, b1, k, d, 1.0, want_out=False, act_slope=LRELU_SLOPE,
-                                         w_split=w1s if ws_ok else None, x_split=s, act_split=s)
+                                         w_split=w1s if ws_ok else None, x_split=s, act_split=s, rows=here)
                     if t + 1 < len(convs):
                         xr, xr_act = c.conv1d(xt_act, w2, b2, k, 1, 1.0, residual=xr, act_slope=LRELU_SLOPE,
-                                              w_split=w2s if ws_ok else None, x_split=s, act_split=s)
+                                              w_split=w2s if ws_ok else None, x_split=s, act_split=s, rows=here)
                     else:
-                        xr = c.conv1d(xt_act, w2, b2, k, 1, 1.0, residual=xr, w_split=w2s if ws_ok else None, x_split=s)
+                        xr = c.conv1d(xt_act, w2, b2, k, 1, 1.0, residual=xr, w_split=w2s if ws_ok else None, x_split=s,
+                                      rows=here)
                 outs.append(xr)
             if i + 1 < self.num_upsamples:
                 act_s = use_split and cout % 64 == 0   # the mean kernel writes either layout
@@ -307,8 +382,12 @@ class Generator(torch.nn.Module):
             else:
                 cur = c.nsf_mean(outs)
             cin = cout
-        audio = c.nsf_post(cur, P["post_w"], P["post_b"], P["post_k"], 0.01)
-        return audio.reshape(1, 1, -1)
+        # (the stage means need no counts: the mean of tensors that are 0 past a row's end is 0 there)
+        if batched:
+            audio = c.nsf_post_ragged(cur, P["post_w"], P["post_b"], P["post_k"], 0.01, rows(self.upp))
+        else:
+            audio = c.nsf_post(cur, P["post_w"], P["post_b"], P["post_k"], 0.01)
+        return audio.reshape(B, 1, -1)
 
     __call__ = forward
 
@@ -339,14 +418,23 @@ class NsfHifiGAN(torch.nn.Module):
     def hop_size(self):
         return self.h.hop_size
 
-    def forward(self, audio, f0, rand_ini=None):
+    def stft(self):
         h = self.h
         if self._stft is None:
             self._stft = STFT(h.sampling_rate, h.num_mels, h.n_fft, h.win_size, h.hop_size, h.fmin, h.fmax)
+        return self._stft
+
+    def forward(self, audio, f0, rand_ini=None, n_samples=None):
+        """audio (B, T), f0 (B, frames) -> (enhanced (B, T'_max), sample rate).  `n_samples`: a ragged batch, row b being its
+        first n_samples[b] samples; it comes out as the row enhanced alone in its first `frame_count(n_samples[b]) * hop`
+        samples and 0 after them.  f0 must cover every row's own frames; what it holds past them is not read."""
+        stft = self.stft()
+        vals = None if n_samples is None else hipddsp.check_n_samples(n_samples, audio.shape[0], audio.shape[-1])
         with torch.no_grad():
-            mel = self._stft.get_mel(audio)
-            enhanced = self.model(mel, f0[:, :mel.size(-1)], rand_ini=rand_ini)
-            return enhanced.reshape(1, -1), h.sampling_rate
+            mel = stft.get_mel(audio, n_samples=vals)
+            n_frames = None if vals is None else [stft.frame_count(v) for v in vals]
+            enhanced = self.model(mel, f0.reshape(f0.shape[0], -1)[:, :mel.size(-1)], rand_ini=rand_ini, n_frames=n_frames)
+            return enhanced.reshape(audio.shape[0], -1), self.h.sampling_rate
 
 
 class Enhancer:
@@ -410,3 +498,82 @@ class Enhancer:
         if cut_frames > 0:
             enhanced = F.pad(enhanced, (int(np.round(sr_e * cut_seconds)), 0))
         return enhanced, sr_e
+
+    # -- rows of different length in one batch ---------------------------------------------------------------------------
+    def batch_lengths(self, n_samples, sample_rate, work_rate):
+        """Host integers a row of n_samples goes through in `enhance` at a working rate: (samples at the working rate,
+        f0 frames asked of the re-timing, generator frames, generator samples, output samples at the enhancer's rate) -
+        the resampler's length formula, `n // hop + 1`, `STFT.frame_count`, `* hop`, the resampler's again."""
+        length = hipddsp.load_library().ddsp_resample_length
+        sr_e, hop_e = int(self.enhancer_sample_rate), int(self.enhancer_hop_size)
+        n_res = int(n_samples) if int(sample_rate) == int(work_rate) else int(length(int(n_samples), int(sample_rate), int(work_rate)))
+        frames = self.enhancer.stft().frame_count(n_res)
+        n_gen = frames * hop_e
+        n_out = n_gen if int(work_rate) == sr_e else int(length(n_gen, int(work_rate), sr_e))
+        return n_res, n_res // hop_e + 1, frames, n_gen, n_out
+
+    def _enhance_rows(self, audio, sample_rate, f0, hop_size, n_samples, n_f0, key, rand_ini):
+        """One ragged pass at one working rate: audio (B, T), f0 (B, Fr) -> (enhanced (B, T'), n_out)."""
+        c = hipddsp.context_for(audio.device)
+        work_rate, pitch_scale, shrink = self._working_rate(key, None)
+        sr_e, hop_e = self.enhancer_sample_rate, self.enhancer_hop_size
+        lens = [self.batch_lengths(n, sample_rate, work_rate) for n in n_samples]
+        if int(sample_rate) != int(work_rate):
+            audio = c.resample_ragged(audio, c.ragged_counts(n_samples), sample_rate, work_rate, 128)
+        n_dst = [l[1] for l in lens]
+        f0_res = c.retime_f0_ragged(f0, c.ragged_counts(n_f0), hop_size / sample_rate, pitch_scale, pitch_scale, hop_e / sr_e,
+                                    max(n_dst), c.ragged_counts(n_dst))
+        enhanced, _ = self.enhancer(audio, f0_res, rand_ini=rand_ini, n_samples=[l[0] for l in lens])
+        if shrink != 0 and int(work_rate) != int(sr_e):
+            enhanced = c.resample_ragged(enhanced, c.ragged_counts([l[3] for l in lens]), work_rate, sr_e, 128)
+        return enhanced, [l[4] for l in lens]
+
+    def enhance_batch(self, audio, sample_rate, f0, hop_size, n_samples, adaptive_key=0, rand_ini=None, n_f0=None):
+        """Rows of different length through the whole enhancer in one padded batch: audio (B, T) with n_samples[b] samples
+        per row, f0 (B, Fr, 1) with n_f0[b] frames per row (default int(n_samples[b] // hop_size), at least 1) ->
+        (enhanced (B, T'_max), enhancer sample rate, n_out).  Row b holds `enhance(audio[b:b+1, :n_b], sample_rate,
+        f0[b:b+1, :n_f0[b]], hop_size, adaptive_key)` in [:n_out[b]] and exactly 0 after it, whatever audio and f0 hold past
+        the row's own end; n_out is computed on the host (`batch_lengths`), nothing is read back for it.  There is no
+        `silence_front` (a real-time argument).  A numeric adaptive_key is one working rate for the whole batch; 'auto' reads
+        back the rows' f0 maxima once, (B,), then runs one ragged pass per distinct key over the rows that share it.
+        rand_ini: None, (9,) or (B, 9)."""
+        if audio.dim() != 2:
+            raise ValueError("enhance_batch: audio must be (B, T)")
+        B, T = audio.shape
+        n_samples = hipddsp.check_n_samples(n_samples, B, T)
+        f0 = f0.reshape(B, -1)
+        Fr = f0.shape[1]
+        if n_f0 is None:
+            n_f0 = [min(Fr, max(1, int(n // hop_size))) for n in n_samples]
+        n_f0 = hipddsp.check_n_frames(n_f0, B, Fr)
+        if not audio.is_cuda:
+            raise RuntimeError("the enhancer runs on a HIP device only (no CPU fallback)")
+        if rand_ini is not None:
+            rand_ini = rand_ini.float()
+            rand_ini = rand_ini.reshape(1, 9).expand(B, 9) if rand_ini.numel() == 9 else rand_ini.reshape(B, 9)
+        if not isinstance(adaptive_key, str):
+            out, n_out = self._enhance_rows(audio, sample_rate, f0, hop_size, n_samples, n_f0, adaptive_key, rand_ini)
+            return out[:, :max(n_out)], self.enhancer_sample_rate, n_out
+        if adaptive_key != "auto":
+            raise ValueError(f"adaptive_key must be a number or 'auto', got {adaptive_key!r}")
+        # the keys decide tensor LENGTHS: the rows' highest f0 over their own frames is the one read-back, (B,)
+        own = torch.arange(Fr, device=f0.device)[None, :] < hipddsp.context_for(audio.device).ragged_counts(n_f0)[:, None]
+        peaks = torch.where(own, f0.float(), torch.full_like(f0, -float("inf"), dtype=torch.float32)).amax(dim=1).cpu()
+        keys = [max(0, float(np.ceil(12 * np.log2(float(p) / 760)))) if float(p) > 0 else 0 for p in peaks]
+        print("auto_adaptive_key: " + str([int(k) for k in keys]))
+        parts, n_out = {}, [0] * B
+        for key in sorted(set(keys)):
+            idx = [b for b in range(B) if keys[b] == key]
+            sel = torch.tensor(idx, device=audio.device)
+            width = max(n_samples[b] for b in idx)
+            got, n_rows = self._enhance_rows(audio.index_select(0, sel)[:, :width].contiguous(), sample_rate,
+                                             f0.index_select(0, sel), hop_size, [n_samples[b] for b in idx],
+                                             [n_f0[b] for b in idx], key, None if rand_ini is None else rand_ini[idx])
+            parts[key] = (idx, sel, got)
+            for b, n in zip(idx, n_rows):
+                n_out[b] = n
+        out = torch.zeros(B, max(n_out), device=audio.device, dtype=torch.float32)
+        for idx, sel, got in parts.values():
+            w = min(got.shape[1], out.shape[1])          # (a group's padded width may exceed every row's own length)
+            out[sel, :w] = got[:, :w]
+        return out, self.enhancer_sample_rate, n_out

@@ -203,6 +203,14 @@ SIGNATURES = {
     "ddsp_softmax_attention_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp]),
     "ddsp_resample_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _int, _vp]),
     "ddsp_align_units_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
+    "ddsp_conv1d_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _f32, _vp, _vp, _vp, _f32, _vp, _int,
+                                  _vp, _int]),
+    "ddsp_conv1d_pair_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _f32, _vp, _vp, _vp, _int]),
+    "ddsp_nsf_source_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp]),
+    "ddsp_nsf_noise_conv_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _int, _int, _int, _int, _i64, _vp]),
+    "ddsp_nsf_post_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp, _int]),
+    "ddsp_stft_frames_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp]),
+    "ddsp_retime_f0_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _f64, _f32, _f64, _i64, _vp, _vp]),
     "ddsp_crepe_frames": (_i64, [_i64, _int]),
     "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _int, _vp]),
     "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
@@ -659,6 +667,16 @@ class Context:
                   _ptr(n_out_dev), _ptr(out))
         return out
 
+    def retime_f0_ragged(self, f0, n_src_dev, step_num, div, scale, step_dst, n_dst, n_dst_dev):
+        """`retime_f0` of a ragged batch: f0 (B, n_src) -> (B, n_dst); row b has n_src_dev[b] knots and n_dst_dev[b] targets of
+        its own ((B,) int32 device tensors, `ragged_counts`), ends held at its own first and last frame, 0 after its targets."""
+        f0 = f0.contiguous().float()
+        B, n_src = f0.shape
+        out = torch.empty(B, int(n_dst), device=f0.device, dtype=torch.float32)
+        self.call("ddsp_retime_f0_ragged", _ptr(f0), B, n_src, _ptr(n_src_dev), float(step_num), float(div), float(scale),
+                  float(step_dst), int(n_dst), _ptr(n_dst_dev), _ptr(out))
+        return out
+
     def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst):
         """f0 (n,) device track -> (n_dst,): numpy.interp(i * step_dst; knots (step_num * j) / div, values fl32(f0 * scale)),
         end values held (enhancer.py:56-62), without leaving the device."""
@@ -698,8 +716,11 @@ class Context:
         return out
 
     # -- NSF-HiFiGAN post-net building blocks --------------------------------
+    # Ragged batches (include/ddsp_amd.h, "Ragged batches of the post-net"): `rows=(B, n_dev, scale)` runs a call over B rows
+    # flattened on the time axis, (B * T, C), row b valid for n_dev[b] * scale frames (n_dev: (B,) int32 device tensor of
+    # `ragged_counts`, or None for a rectangular batch) and written as 0 after them; rows=None is the solo entry point.
     def conv1d(self, x, w_packed, bias, ktaps, dil, in_slope, residual=None, want_out=True, act_slope=None, w_split=None,
-               x_split=False, act_split=False):
+               x_split=False, act_split=False, rows=None):
         """x (T,Cin), w_packed (Cout, ktaps*Cin) -> y (T,Cout) = conv_same(leaky_relu(x, in_slope)) + bias (+ residual).
         Returns y, or (y | None, leaky_relu(y, act_slope)) when act_slope is given (want_out=False skips y itself).
         Split operands (include/ddsp_amd.h, ddsp_conv1d): `w_split` = presplit(w_packed); `x_split`: x is in the split layout;
@@ -712,9 +733,17 @@ class Context:
         act = torch.empty(T, Cout, device=x.device, dtype=torch.float32) if act_slope is not None else None
         if out is None and act is None:
             raise ValueError("conv1d: nothing to return")
+        flags = (CONV_X_SPLIT if x_split else 0) | (CONV_ACT_SPLIT if act_split else 0)
+        if rows is not None:
+            B, n_dev, scale = rows
+            if T % int(B):
+                raise ValueError("conv1d: x must hold B rows of equal padded length")
+            self.call("ddsp_conv1d_ragged", _ptr(x), _ptr(w_packed), _ptr(bias), int(B), T // int(B), Cin, Cout, int(ktaps), int(dil),
+                      float(in_slope), _ptr(residual), _ptr(out), _ptr(act), float(act_slope if act_slope is not None else 1.0),
+                      _ptr(w_split), flags, _ptr(n_dev), int(scale))
+            return out if act_slope is None else (out, act)
         self.call("ddsp_conv1d", _ptr(x), _ptr(w_packed), _ptr(bias), T, Cin, Cout, int(ktaps), int(dil), float(in_slope),
-                  _ptr(residual), _ptr(out), _ptr(act), float(act_slope if act_slope is not None else 1.0), _ptr(w_split),
-                  (CONV_X_SPLIT if x_split else 0) | (CONV_ACT_SPLIT if act_split else 0))
+                  _ptr(residual), _ptr(out), _ptr(act), float(act_slope if act_slope is not None else 1.0), _ptr(w_split), flags)
         return out if act_slope is None else (out, act)
 
     def gemm_res_ln(self, A_split, W_split, bias, res, gamma, beta, y_split=True, a_fp32=False):
@@ -730,12 +759,19 @@ class Context:
     def conv1d_pair_supported(self, C, ktaps, dil):
         return bool(self.lib.ddsp_conv1d_pair_supported(self.handle, int(C), int(ktaps), int(dil)))
 
-    def conv1d_pair(self, x, w1, b1, w2, b2, ktaps, dil, slope, want_out=True, want_act=False):
+    def conv1d_pair(self, x, w1, b1, w2, b2, ktaps, dil, slope, want_out=True, want_act=False, rows=None):
         """One ResBlock1 pair of a narrow stage: x (T,C) raw -> (x + c2(leaky_relu(c1_dil(leaky_relu(x)))), its activated copy);
         either may be skipped (None)."""
         T, C = x.shape
         out = torch.empty(T, C, device=x.device, dtype=torch.float32) if want_out else None
         act = torch.empty(T, C, device=x.device, dtype=torch.float32) if want_act else None
+        if rows is not None:
+            B, n_dev, scale = rows
+            if T % int(B):
+                raise ValueError("conv1d_pair: x must hold B rows of equal padded length")
+            self.call("ddsp_conv1d_pair_ragged", _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(B), T // int(B), C, int(ktaps),
+                      int(dil), float(slope), _ptr(out), _ptr(act), _ptr(n_dev), int(scale))
+            return out, act
         self.call("ddsp_conv1d_pair", _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), T, C, int(ktaps), int(dil), float(slope),
                   _ptr(out), _ptr(act))
         return out, act
@@ -745,6 +781,44 @@ class Context:
         out = torch.empty(L * int(upp), device=f0.device, dtype=torch.float32)
         self.call("ddsp_nsf_source", _ptr(f0), _ptr(rand_ini.contiguous().float()), _ptr(lin_w), _ptr(lin_b), L, int(upp),
                   int(sr), float(sine_amp), _ptr(out))
+        return out
+
+    def nsf_source_ragged(self, f0, rand_ini, lin_w, lin_b, upp, sr, sine_amp=0.1, n_dev=None):
+        """f0 (B, L), rand_ini (B, 9) -> source (B, L * upp): one phase scan per row from its own initial phases; with n_dev,
+        f0 past a row's count is not read and its source is 0 from n_dev[b] * upp on."""
+        B, L = f0.shape
+        if tuple(rand_ini.shape) != (B, 9):
+            raise ValueError(f"nsf_source_ragged: rand_ini must be (B, 9) = ({B}, 9), got {tuple(rand_ini.shape)}")
+        out = torch.empty(B, L * int(upp), device=f0.device, dtype=torch.float32)
+        self.call("ddsp_nsf_source_ragged", _ptr(f0), _ptr(rand_ini.contiguous().float()), _ptr(lin_w), _ptr(lin_b), B, L, int(upp),
+                  int(sr), float(sine_amp), _ptr(n_dev), _ptr(out))
+        return out
+
+    def nsf_noise_conv_ragged(self, src, w, b, K, stride, pad, T_out):
+        """src (B, T_src) -> (B * T_out, C), taps row-local."""
+        B, T_src = src.shape
+        C = w.shape[0]
+        out = torch.empty(B * int(T_out), C, device=src.device, dtype=torch.float32)
+        self.call("ddsp_nsf_noise_conv_ragged", _ptr(src), B, T_src, _ptr(w), _ptr(b), C, int(K), int(stride), int(pad), int(T_out),
+                  _ptr(out))
+        return out
+
+    def nsf_post_ragged(self, x, w, b, K, slope, rows):
+        """x (B * T, C) -> (B, T), 0 past each row's end (`rows` as in conv1d)."""
+        B, n_dev, scale = rows
+        T, C = x.shape[0] // int(B), x.shape[1]
+        out = torch.empty(int(B), T, device=x.device, dtype=torch.float32)
+        self.call("ddsp_nsf_post_ragged", _ptr(x), _ptr(w), _ptr(b), int(B), T, C, int(K), float(slope), _ptr(out), _ptr(n_dev),
+                  int(scale))
+        return out
+
+    def stft_frames_ragged(self, audio, n_dev, n_fft, hop, L):
+        """audio (B, T) with n_dev[b] samples per row -> frames (B, L, n_fft) padded per row as `STFT.get_mel` pads (reflect or
+        zeros, chosen per row); frames past a row's own count are 0."""
+        audio = audio.contiguous().float()
+        B, T = audio.shape
+        out = torch.empty(B, int(L), int(n_fft), device=audio.device, dtype=torch.float32)
+        self.call("ddsp_stft_frames_ragged", _ptr(audio), B, T, _ptr(n_dev), int(n_fft), int(hop), int(L), _ptr(out))
         return out
 
     def nsf_noise_conv(self, src, w, b, K, stride, pad, T_out):

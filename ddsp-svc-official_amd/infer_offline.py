@@ -4,7 +4,8 @@ The reference's `main.py` is broken as shipped (`.astype` on a tensor at :112, k
 SURVEY 0.3), so this module restates what it intends.  `render` takes analysed features and does what happens from there:
 per-slice `model(...)[0]`, the volume gate multiplied into the returned signal in place, optional enhancer, silence padding /
 cross-fade of slices; with `batch_frames=` the slices are rendered in ragged batches (`model(..., n_frames=)`) instead of
-one after the other.  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
+one after the other, and with `enhancer_batch_samples=` they are enhanced in ragged batches too
+(`Enhancer.enhance_batch`).  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
 (`Units_Encoder`) on the device, then `render`.  Cutting the audio into slices (`slicer.Slicer`, a librosa-based silence
 detector) stays with the caller: `convert` takes the slice boundaries.
 """
@@ -81,15 +82,33 @@ def _encode_ragged(units_encoder, pieces, sample_rate, hop_size, units_batch_sam
     return out
 
 
+def _enhance_ragged(enhancer, gated, segments, f0, sr, block, adaptive_key, enhancer_batch_samples):
+    """Every gated slice (1, n * block) enhanced, in the order of `segments`, from one `Enhancer.enhance_batch` per group of
+    `group_segments` over the sample lengths, each row with its own f0 slice -> ([(1, n_out)], enhancer sample rate)."""
+    lengths = [g.shape[-1] for g in gated]
+    out, sr_o = [None] * len(gated), sr
+    for group in group_segments(lengths, int(enhancer_batch_samples)):
+        wav, counts = stack_rows([gated[i][0] for i in group])
+        tracks, n_f0 = stack_rows([f0[0, segments[i][0]:segments[i][0] + segments[i][1].size(1), 0] for i in group])
+        got, sr_o, n_out = enhancer.enhance_batch(wav, sr, tracks[:, :, None], block, counts, adaptive_key=adaptive_key, n_f0=n_f0)
+        for j, i in enumerate(group):
+            out[i] = got[j:j + 1, :n_out[j]]
+    return out, sr_o
+
+
 @torch.no_grad()
 def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, threshold_db=-60, enhancer=None,
-           enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None):
+           enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None, enhancer_batch_samples=None):
     """segments: list of (start_frame, units (1, Fr_seg, n_unit)) as `main.py:143-151` produces them;
     f0 (1, Fr, 1), volume (1, Fr) cover the whole file.  Returns (float64 numpy waveform, sample rate).
     batch_frames: None renders slice after slice at batch 1; a number renders the slices in ragged batches of at most that
     many padded frames (`group_segments`), one forward per group, each slice as if rendered alone; gate, enhancer, silence
     and cross-fade then run per slice in the original order, so the file is stitched the same way.
-    noise: a list with one (n * block,) U[0,1) draw per segment that stands where the model draws its noise (parity runs)."""
+    noise: a list with one (n * block,) U[0,1) draw per segment that stands where the model draws its noise (parity runs).
+    enhancer_batch_samples: None enhances slice after slice; a number enhances the gated slices in ragged groups
+    (`group_segments` over their sample lengths, at most that many padded samples per group, one `Enhancer.enhance_batch`
+    each with every row's own f0 slice), every slice as if enhanced alone; the gate comes first and the stitch after, as
+    without it.  All slices are then on the device at once."""
     block = int(args.data.block_size)
     sr = int(args.data.sampling_rate)
     ctx = hipddsp.context_for(f0.device)
@@ -98,7 +117,9 @@ def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, thresho
     sr_o = sr
     rendered = None if batch_frames is None else \
         _render_ragged(model, segments, f0, volume, spk_id, spk_mix_dict, noise_seed, int(batch_frames), block, noise)
-    for i, (start, units) in enumerate(segments):
+
+    def gated_slice(i):
+        start, units = segments[i]
         n = units.size(1)
         seg_f0 = f0[:, start:start + n, :]
         seg_vol = volume[:, start:start + n]
@@ -112,8 +133,19 @@ def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, thresho
         # the gate of the WHOLE file sliced to this segment (main.py:159): dilation sees the neighbours
         gate = volume_mask(volume, threshold_db, block)[:, start * block:(start + n) * block]
         out *= gate
-        if enhancer is not None:
-            out, sr_o = enhancer.enhance(out, sr, seg_f0, block, adaptive_key=enhancer_adaptive_key)
+        return out, seg_f0
+
+    enhanced = None
+    if enhancer is not None and enhancer_batch_samples is not None and segments:
+        enhanced, sr_o = _enhance_ragged(enhancer, [gated_slice(i)[0] for i in range(len(segments))], segments, f0, sr, block,
+                                         enhancer_adaptive_key, enhancer_batch_samples)
+    for i, (start, units) in enumerate(segments):
+        if enhanced is not None:
+            out = enhanced[i]
+        else:
+            out, seg_f0 = gated_slice(i)
+            if enhancer is not None:
+                out, sr_o = enhancer.enhance(out, sr, seg_f0, block, adaptive_key=enhancer_adaptive_key)
         out = out.squeeze().cpu().numpy()
         silent = round(start * block * sr_o / sr) - current
         if silent >= 0:
@@ -146,12 +178,14 @@ def convert(model, args, audio, sample_rate, slices, units_encoder, f0_extractor
 @torch.no_grad()
 def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, batch_frames, key=0,
                     spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
-                    units_batch_samples=None):
+                    enhancer_batch_samples=None, units_batch_samples=None):
     """`convert` with `render`'s `batch_frames`: the slices are rendered in ragged batches of at most that many padded frames
     (None: slice after slice, which is `convert`).  `units_batch_samples`: None encodes the units slice by slice; a number
     encodes them in ragged groups too (`Units_Encoder.encode(..., n_samples=)`), `group_segments` over the slices' sample
-    lengths with at most that many padded samples (at `sample_rate`) per group, every slice as if encoded alone.  The
-    enhancer still runs per slice.  (A function of its own and not a keyword of `convert`:
+    lengths with at most that many padded samples (at `sample_rate`) per group, every slice as if encoded alone.
+    `enhancer_batch_samples`: `render`'s keyword of that name - None enhances slice after slice, a number in ragged groups of
+    at most that many padded samples (at the model's rate); it stands before `units_batch_samples`, which
+    tests/test_hubert_ragged_host.py pins as the last parameter.  (A function of its own and not a keyword of `convert`:
     tests/test_stream_audio_host.py pins `convert`'s parameter list.)"""
     hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
     if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
@@ -175,4 +209,5 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
     if units_batch_samples is not None:
         segments = _encode_ragged(units_encoder, segments, sample_rate, hop_size, units_batch_samples)
     return render(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
-                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames)
+                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
+                  enhancer_batch_samples=enhancer_batch_samples)

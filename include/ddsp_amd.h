@@ -326,6 +326,12 @@ int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int
  * fl32(f0[j] * scale), evaluated in fp64 like numpy; f0 (n_src,) -> out (n_dst,).  No host copy of the track. */
 int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, double step_num, double div, float scale,
                    double step_dst, int64_t n_dst, float* out);
+/* ddsp_retime_f0 over a ragged batch: f0 (B, n_src) -> out (B, n_dst); row b has n_src_rows[b] <= n_src knots and
+ * n_dst_rows[b] <= n_dst targets of its own (DEVICE arrays of B int32): the ends are held at the row's own first and last
+ * frame, f0 past the row's knots is never read, and the outputs from n_dst_rows[b] on are 0. */
+int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
+                          double step_num, double div, float scale, double step_dst, int64_t n_dst, const int32_t* n_dst_rows,
+                          float* out);
 
 /* ---- sample-rate conversion ------------------------------------------------------ */
 /* replaces `torchaudio.transforms.Resample(orig_freq, new_freq, lowpass_filter_width)` as the reference uses it (gui.py:399-404,
@@ -342,7 +348,8 @@ int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x, int64_t B,
                          int orig_freq, int new_freq, int lowpass_filter_width, float* out);
 
 /* ---- the NSF-HiFiGAN post-net (enhancer.py:24-101, nsf_hifigan/models.py:106-276, nvSTFT.py:65-119) ---- */
-/* One utterance per call; activations frame-major (T, C) fp32.
+/* One utterance per call, or - the `_ragged` entry points at the end of this section - a padded batch of rows of different
+ * length; activations frame-major (T, C) fp32.
  * ddsp_conv1d: replaces `Conv1d(Cin, Cout, k, dilation=d, padding="same")(leaky_relu(x, in_slope))` (+ residual): the
  *   resblock convolutions (models.py:45-77), conv_pre (:234) and - with weights packed as the host mirror's
  *   `_pack_conv_transpose` does - the ConvTranspose1d upsamplers (:240-243).  x (T,Cin), w_packed (Cout, k*Cin) with column
@@ -390,6 +397,47 @@ int ddsp_nsf_mean(ddsp_ctx* ctx, void* stream, const float* a, const float* b, c
                   float* out, float* out_act, float act_slope, int flags);
 int ddsp_log_mel(ddsp_ctx* ctx, void* stream, const float* frames, const float* dft_table, const float* mel_basis,
                  int64_t n_frames, int n_fft, int n_mels, float clip, float* out);
+/* Ragged batches of the post-net (inference): B rows of different length as ONE padded batch, flattened on the time axis.
+ * Activations are (B * T, C): row b owns the T frames from b * T on and is valid for its first T_b = n_frames[b] * frame_scale
+ * of them (n_frames: a DEVICE array of B int32, 1 <= n_frames[b] <= T / frame_scale, uploaded once and never read back, so the
+ * calls can be captured in a HIP graph; frame_scale = the product of the upsampling rates so far; T % frame_scale == 0).
+ * n_frames = NULL is a rectangular batch: every row T long.  The contract, one rule throughout:
+ *   - every tensor a convolution READS (x, and what a residual adds) must be exactly 0 at t >= T_b;
+ *   - every entry point WRITES exactly 0 at t >= T_b of each output, whatever bias, residual or source would put there.
+ * A tap that leaves [0, T_b) then reads 0 as a solo call's "same" padding does, and no tap reaches a neighbouring row, so
+ * row b of each output is, over [0, T_b), what the solo entry point returns for that row alone at its own length.  A caller
+ * whose first input may hold anything past T_b zeroes it first (ddsp_ragged_frames with hold = 0).  Each solo entry point
+ * above is the B = 1, n_frames = NULL case of its ragged form.
+ * ddsp_conv1d_ragged: x (B*T, Cin), residual / out / out_act (B*T, Cout).  For a transposed convolution in its 3-tap form
+ *   the (B*T, u*Cout) result is the (B*T*u, Cout) output, row t holding samples t*u .. t*u+u-1 of the same batch row: the mask
+ *   stays per input row (frame_scale of the INPUT).
+ * ddsp_conv1d_pair_ragged: windows are cut per batch row, halo reads stop at the row's own ends, and the intermediate
+ *   leaky_relu(c1(x) + b1) is zeroed at t >= T_b before c2 reads it.
+ * ddsp_nsf_source_ragged: f0 (B, L), rand_ini (B, 9): one phase scan per row from the row's own initial phases; f0 past
+ *   n_frames[b] is never read; out (B, L*upp) is 0 from n_frames[b] * upp on.
+ * ddsp_nsf_noise_conv_ragged: src (B, T_src) -> out (B*T_out, C), taps row-local (no counts: its consumer masks).
+ * ddsp_nsf_post_ragged: x (B*T, C) -> out (B, T), tanh(. + b) replaced by 0 at t >= T_b.
+ * (ddsp_nsf_mean needs no ragged form: the mean of masked tensors is masked.)
+ * ddsp_stft_frames_ragged: the framing of `STFT.get_mel` (nvSTFT.py:88-98) for audio (B, T) with n_samples[b] <= T samples
+ *   per row (DEVICE int32, NULL: T): per row pad_left = (n_fft - hop) / 2, pad_right = max((n_fft - hop + 1) / 2,
+ *   n_fft - n_b - pad_left), reflect padding where pad_right < n_b and zeros otherwise - chosen PER ROW -, frames (B, L, n_fft)
+ *   with L_b = (n_b + pad_left + pad_right - n_fft) / hop + 1 frames of the row and 0 in frames >= L_b.  Audio past n_b is
+ *   never read.  ddsp_log_mel then runs on the B * L rows. */
+int ddsp_conv1d_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B, int64_t T,
+                       int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out, float* out_act,
+                       float act_slope, const float* w_split, int flags, const int32_t* n_frames, int frame_scale);
+int ddsp_conv1d_pair_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
+                            const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil, float slope, float* out,
+                            float* out_act, const int32_t* n_frames, int frame_scale);
+int ddsp_nsf_source_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
+                           const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp, const int32_t* n_frames,
+                           float* out);
+int ddsp_nsf_noise_conv_ragged(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
+                               const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out);
+int ddsp_nsf_post_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T, int C,
+                         int K, float slope, float* out, const int32_t* n_frames, int frame_scale);
+int ddsp_stft_frames_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
+                            int n_fft, int hop, int64_t L, float* out);
 
 /* ---- a15: optimiser step --------------------------------------------------------------------- */
 /* replaces one parameter's update of torch.optim.AdamW (train.py:41, solver.py:114): decoupled weight decay,
