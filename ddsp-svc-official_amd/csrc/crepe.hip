@@ -56,21 +56,66 @@ struct EpiPool {
     }
 };
 
-// in place: x = sigmoid(x) (the classifier's activation; a separate pass keeps expf out of the GEMM epilogue's registers)
-__global__ void __launch_bounds__(256) sigmoid_kernel(float* __restrict__ x, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = 1.0f / (1.0f + expf(-x[i]));
+// Ragged batch: packed frame z of the real frames of all rows -> its row b (prefix[b] <= z < prefix[b + 1]; prefix: the (B + 1,)
+// exclusive prefix sums of the rows' frame counts), held inside 0..B-1 whatever the table holds.
+__device__ __forceinline__ int packed_row(const int32_t* __restrict__ prefix, int B, int64_t z) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)prefix[mid] <= z) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// x = sigmoid(x) (the classifier's activation; a separate pass keeps expf out of the GEMM epilogue's registers): in place, or
+// (prefix != nullptr, ragged batch) from the pass's packed rows z0 + i / 360 to out (B, Fr, 360) at the frame's (row, frame)
+__global__ void __launch_bounds__(256) sigmoid_kernel(float* __restrict__ x, int64_t n, const int32_t* __restrict__ prefix, int B,
+                                                      int64_t z0, int64_t Fr, float* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float y = 1.0f / (1.0f + expf(-x[i]));
+        if (!prefix) {
+            x[i] = y;
+            continue;
+        }
+        const int64_t z = z0 + i / BINS;
+        const int b = packed_row(prefix, B, z);
+        const int64_t f = z - (int64_t)prefix[b];
+        if (f >= 0 && f < Fr) out[((int64_t)b * Fr + f) * BINS + i % BINS] = y;
+    }
+}
+
+// ragged batch: one wave per (row, frame) of out (B, Fr, 360); the frames a row does not have are set to 0
+__global__ void __launch_bounds__(256) tail_zero_kernel(float* __restrict__ out, int64_t Fr, int64_t rows,
+                                                        const int32_t* __restrict__ prefix) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t b = row / Fr, f = row - b * Fr;
+    if (f < (int64_t)prefix[b + 1] - (int64_t)prefix[b]) return;
+    for (int j = lane; j < BINS; j += 64) out[row * BINS + j] = 0.f;
 }
 
 // ---- framing -----------------------------------------------------------------------------------------------
 // block per frame z (of the chunk starting at frame z0 of the B * Fr flattened frames): 1532 floats, 254 zeros, the 1024
 // normalised samples, 254 zeros.  Sample s of frame f reads audio[f * hop + s - 512] (zero outside the utterance).
+// Ragged batch (prefix != nullptr): z counts the packed real frames, its (row, frame) comes from the prefix table, and the
+// utterance ends at the row's own n16[b] samples: what follows them is never loaded.
 __global__ void __launch_bounds__(256) frame_kernel(const float* __restrict__ audio, int64_t T, int64_t Fr, int hop, int64_t z0,
-                                                    float* __restrict__ frames) {
+                                                    float* __restrict__ frames, const int32_t* __restrict__ n16,
+                                                    const int32_t* __restrict__ prefix, int B) {
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int64_t z = z0 + blockIdx.x;
-    const int64_t b = z / Fr, f = z % Fr;
-    const float* x = audio + b * T;
+    int64_t b = z / Fr, f = z % Fr;
+    const int64_t ld = T;
+    if (prefix) {
+        b = packed_row(prefix, B, z);
+        f = z - (int64_t)prefix[b];
+        f = f < 0 ? 0 : f;
+        const int64_t nb = n16[b];
+        T = nb < 0 ? 0 : (nb < T ? nb : T);
+    }
+    const float* x = audio + b * ld;
     float v[4];
     double s = 0.0;
 #pragma unroll
@@ -140,12 +185,27 @@ __global__ void __launch_bounds__(256) prep_kernel(PrepArgs a) {
 }
 
 // ---- decode -------------------------------------------------------------------------------------------------
-// one wave per frame: emissions log(softmax(masked probs) + tiny) (fp32), the mask [0, lo) and [hi, 360)
+// one wave per frame: emissions log(softmax(masked probs) + tiny) (fp32), the mask [0, lo) and [hi, 360).  Ragged batch
+// (n_frames != nullptr): a frame its row does not have is skipped - its activations are not read - and its entries of the
+// decode's outputs (B, Fr) are set to 0 here, so the Viterbi workgroups write a row's own frames only.
 __global__ void __launch_bounds__(256) emission_kernel(const float* __restrict__ probs, int64_t rows, int lo, int hi,
-                                                       float* __restrict__ logp) {
+                                                       float* __restrict__ logp, const int32_t* __restrict__ n_frames, int64_t Fr,
+                                                       float* __restrict__ f0, float* __restrict__ pd,
+                                                       int32_t* __restrict__ bins_out) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
+    if (n_frames) {
+        const int64_t b = row / Fr;
+        if (row - b * Fr >= (int64_t)n_frames[b]) {
+            if (lane == 0) {
+                f0[row] = 0.f;
+                pd[row] = 0.f;
+                if (bins_out) bins_out[row] = 0;
+            }
+            return;
+        }
+    }
     const float* p = probs + row * BINS;
     float x[6];
     float mx = -INFINITY;
@@ -205,7 +265,9 @@ __global__ void seed_advance_kernel(uint64_t* __restrict__ seed) {
     *seed = *seed * 6364136223846793005ull + 1442695040888963407ull;
 }
 
-// grid (segments, B).  Frames [t0, t1) of utterance b, decoded on their own from a uniform start:
+// grid (segments, B).  Frames [t0, t1) of utterance b (of its own n_frames[b] <= Fr frames in a ragged batch: a piece that
+// starts at or after them returns at once, the last piece ends - and its backtrack starts - at the row's own last frame, and
+// the dither is drawn for the row-local frame, as a call on the row alone draws it), decoded on their own from a uniform start:
 //   value[t][j] = logp[t][j] + max_i(value[t-1][i] + logT[i][j])  (fp64, first i on ties)
 // computed exactly from the 23 in-band candidates and the out-of-band term value[t-1][g] + log(tiny), g = the first global
 // argmax of value[t-1]: every in-band logT exceeds log(tiny), so an out-of-band i beats the band only if it is g.
@@ -213,7 +275,14 @@ __global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ l
                                                      int64_t seg, int lo, int hi, uint16_t* __restrict__ ptr, uint64_t seed_arg,
                                                      const uint64_t* __restrict__ seed_dev, int dither,
                                                      float* __restrict__ f0, float* __restrict__ pd,
-                                                     int32_t* __restrict__ bins_out) {
+                                                     int32_t* __restrict__ bins_out, const int32_t* __restrict__ n_frames) {
+    const int64_t t0 = (int64_t)blockIdx.x * seg;
+    int64_t Frb = Fr;
+    if (n_frames) {
+        const int64_t nb = n_frames[blockIdx.y];
+        Frb = nb < Fr ? nb : Fr;
+        if (t0 >= Frb) return;
+    }
     // the dither seed: the argument, or (ddsp_crepe_decode_dseed) the device word a captured graph re-reads on every replay
     const uint64_t seed = seed_dev ? *seed_dev : seed_arg;
     __shared__ double band[BINS * BAND];        // logT[j + d - 11][j] at [j * 23 + d]; reused for back-pointer rows
@@ -223,8 +292,7 @@ __global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ l
     __shared__ int16_t state[1024];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y;
-    const int64_t t0 = (int64_t)blockIdx.x * seg;
-    const int n = (int)std::min<int64_t>(seg, Fr - t0);
+    const int n = (int)std::min<int64_t>(seg, Frb - t0);
     const float* lp = logp + ((int64_t)b * Fr + t0) * BINS;
     uint16_t* pt = ptr + ((int64_t)b * Fr + t0) * BINS;
     // transition table: row i of T is max(12 - |i - j|, 0) / sum_j(...), the sum exact in integers
@@ -351,8 +419,9 @@ __global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ l
         const int64_t o = (int64_t)b * Fr + t0 + t;
         float cents = (float)(20 * bin) + CENTS0;
         if (dither) {
-            const float u1 = (float)(hash32(seed, 2 * (uint64_t)o) >> 8) * (1.0f / 16777216.0f);
-            const float u2 = (float)(hash32(seed, 2 * (uint64_t)o + 1) >> 8) * (1.0f / 16777216.0f);
+            const uint64_t h = (uint64_t)(n_frames ? t0 + t : o);
+            const float u1 = (float)(hash32(seed, 2 * h) >> 8) * (1.0f / 16777216.0f);
+            const float u2 = (float)(hash32(seed, 2 * h + 1) >> 8) * (1.0f / 16777216.0f);
             cents = cents + 20.0f * ((u1 + u2) - 1.0f);   // triangular on (-20, 20), mode 0 (scipy triang(c=0.5))
         }
         f0[o] = 10.0f * exp2f(cents / 1200.0f);
@@ -367,13 +436,22 @@ __device__ __forceinline__ int64_t reflect_idx(int64_t i, int64_t n) { return i 
 __global__ void __launch_bounds__(256) postfilter_kernel(const float* __restrict__ f0, const float* __restrict__ pd, int64_t Fr,
                                                          int sr, double hop, int64_t n_frames, int64_t start_frame, float thr,
                                                          int uv_interp, float f0_min, float* __restrict__ pooled,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, const int32_t* __restrict__ n_crepe,
+                                                         const int32_t* __restrict__ n_out) {
     __shared__ int64_t first_v[256], last_v[256];
     const int tid = threadIdx.x, b = blockIdx.x;
     const float* f = f0 + (int64_t)b * Fr;
     const float* p = pd + (int64_t)b * Fr;
     float* pl = pooled + (int64_t)b * Fr;
     float* o = out + (int64_t)b * n_frames;
+    if (n_crepe) {
+        // ragged batch: the row's own frame counts stand for Fr and n_frames from here on (held inside 3..Fr and 0..n_frames),
+        // and the frames of `out` after them are 0 - written once, and looked at by nothing below
+        const int64_t cb = n_crepe[b], ob = n_out[b];
+        for (int64_t n = (ob < 0 ? 0 : ob) + tid; n < n_frames; n += 256) o[n] = 0.f;
+        Fr = cb < 3 ? 3 : (cb < Fr ? cb : Fr);
+        n_frames = ob < 0 ? 0 : (ob < n_frames ? ob : n_frames);
+    }
     // MedianPool1d(pd, 4) -> At(thr) -> MaskedAvgPool1d(f0, 4); window i = reflect(i - 1 .. i + 2)
     for (int64_t i = tid; i < Fr; i += 256) {
         float sum = 0.f, cnt = 0.f;
@@ -548,13 +626,16 @@ void conv_gemm(hipStream_t st, gemm::Args g, const Epi& e) {
     }
 }
 
+// n16 / prefix / n_packed: a ragged batch (ddsp_crepe_activations_ragged) - the network runs over the n_packed real frames
+// of all rows, in passes that may hold frames of several rows; nullptr: the B * Fr frames of a rectangular batch.
 int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const float* audio, int64_t B, int64_t T, int hop,
-              float* probs) {
+              float* probs, const int32_t* n16 = nullptr, const int32_t* prefix = nullptr, int64_t n_packed = 0) {
     DDSP_REQUIRE(ctx, ctx && wp && audio && probs, "ddsp_crepe_activations: null argument");
     DDSP_REQUIRE(ctx, weights_complete(*wp), "ddsp_crepe_activations: a weight pointer is null or not 16-byte aligned, or a width is not a multiple of 16");
     DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && hop >= 1, "ddsp_crepe_activations: bad shape");
     const int64_t Fr = 1 + T / hop;
     DDSP_REQUIRE(ctx, B * Fr < ((int64_t)1 << 31) / BINS && (Fr - 1) * (int64_t)hop < ((int64_t)1 << 40), "ddsp_crepe_activations: input too long");
+    const int64_t n_run = prefix ? n_packed : B * Fr;   // frames the network runs over
     const ddsp_crepe_weights w = *wp;
     const Dims d = dims_of(w);
     DDSP_ENTER_DEVICE(ctx);
@@ -577,13 +658,15 @@ int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const
         }
     }
     // arena: [prepared weights (when not cached)] [ping: frames / conv2 / conv4 / conv6 outputs] [pong: conv1 / conv3 / conv5]
-    const int64_t zc_max = std::min<int64_t>(B * Fr, NET_CHUNK);
+    const int64_t zc_max = std::min<int64_t>(n_run, NET_CHUNK);
     size_t ping = (size_t)zc_max * FRAME_LD, pong = 0;
     for (int l = 0; l < 6; ++l) {
         const size_t sz = (size_t)zc_max * (d.pos[l] / 2) * d.cout[l];
         if (l & 1) ping = std::max(ping, sz); else pong = std::max(pong, sz);
     }
-    const size_t total = align256(pfl * 4) + align256(ping * 4) + align256(pong * 4);
+    // (ragged: the classifier's rows of a pass, before the sigmoid carries them to their (row, frame) of probs)
+    const size_t cls = prefix ? (size_t)zc_max * BINS : 0;
+    const size_t total = align256(pfl * 4) + align256(ping * 4) + align256(pong * 4) + align256(cls * 4);
     // (the arena always has room for the prepared weights: a capture after cached warm-up calls must not have to grow it)
     if ((rc = ddsp_scratch_reserve_bytes(ctx, total + 4096))) return rc;
     ddsp_scratch_reset(ctx);
@@ -596,12 +679,15 @@ int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const
     }
     float* P = (float*)(a + align256(pfl * 4));
     float* Q = (float*)(a + align256(pfl * 4) + align256(ping * 4));
+    float* L = (float*)(a + align256(pfl * 4) + align256(ping * 4) + align256(pong * 4));
     auto scale_of = [&](int l) { return prep + off[5 + l]; };
     auto shift_of = [&](int l) { return prep + off[5 + l] + align256((size_t)d.cout[l] * 4) / 4; };
 
-    for (int64_t z0 = 0; z0 < B * Fr; z0 += NET_CHUNK) {
-        const int zc = (int)std::min<int64_t>(B * Fr - z0, NET_CHUNK);
-        hipLaunchKernelGGL(frame_kernel, dim3((unsigned)zc), dim3(256), 0, st, audio, T, Fr, hop, z0, P);
+    if (prefix)
+        hipLaunchKernelGGL(tail_zero_kernel, dim3((unsigned)ceil_div64(B * Fr, 4)), dim3(256), 0, st, probs, Fr, B * Fr, prefix);
+    for (int64_t z0 = 0; z0 < n_run; z0 += NET_CHUNK) {
+        const int zc = (int)std::min<int64_t>(n_run - z0, NET_CHUNK);
+        hipLaunchKernelGGL(frame_kernel, dim3((unsigned)zc), dim3(256), 0, st, audio, T, Fr, hop, z0, P, n16, prefix, (int)B);
         {   // conv1: batched over the frames, rows 4 floats apart
             gemm::Args g = gemm::make(P, C1_STRIDE, w.conv_w[0], C1_TAPS, C1_POS, d.cout[0], C1_TAPS);
             g.sA_hi = FRAME_LD;
@@ -631,9 +717,11 @@ int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const
         {
             gemm::Args g = gemm::make(x, d.feat, w.cls_w, d.feat, zc, BINS, d.feat);
             g.math = math;
-            gemm::launch<true, true, gemm::A_PLAIN>(st, g, 1, gemm::EpiStore{probs + z0 * BINS, BINS, w.cls_b, 1, 0, 0});
+            float* logits = prefix ? L : probs + z0 * BINS;
+            gemm::launch<true, true, gemm::A_PLAIN>(st, g, 1, gemm::EpiStore{logits, BINS, w.cls_b, 1, 0, 0});
             const int64_t n = (int64_t)zc * BINS;
-            hipLaunchKernelGGL(sigmoid_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, probs + z0 * BINS, n);
+            hipLaunchKernelGGL(sigmoid_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, logits, n, prefix, (int)B, z0, Fr,
+                               probs);
         }
     }
     DDSP_LAUNCH_CHECK(ctx);
@@ -660,9 +748,18 @@ extern "C" int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_cr
     return crepe_run(ctx, (hipStream_t)stream, w, audio16, B, T, hop, probs);
 }
 
+extern "C" int ddsp_crepe_activations_ragged(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16,
+                                             int64_t B, int64_t T, const int32_t* n_samples, const int32_t* frame_prefix,
+                                             int64_t n_packed, int hop, float* probs) {
+    DDSP_REQUIRE(ctx, ctx && n_samples && frame_prefix, "ddsp_crepe_activations_ragged: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && B < ((int64_t)1 << 31) && hop >= 1 && T >= 0 && n_packed >= B && n_packed <= B * (1 + T / hop),
+                 "ddsp_crepe_activations_ragged: n_packed must lie in B..B * frames(T)");
+    return crepe_run(ctx, (hipStream_t)stream, w, audio16, B, T, hop, probs, n_samples, frame_prefix, n_packed);
+}
+
 static int crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
                         int64_t segment, uint64_t dither_seed, uint64_t* seed_dev, int use_dither, float* f0, float* periodicity,
-                        int32_t* bins) {
+                        int32_t* bins, const int32_t* n_frames = nullptr) {
     DDSP_REQUIRE(ctx, ctx && probs && f0 && periodicity, "ddsp_crepe_decode: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && Fr >= 1 && B * Fr < ((int64_t)1 << 31) / BINS, "ddsp_crepe_decode: bad shape");
     DDSP_REQUIRE(ctx, fmin > 0.f && fmax > 0.f && isfinite(fmin) && isfinite(fmax), "ddsp_crepe_decode: fmin, fmax > 0");
@@ -681,9 +778,10 @@ static int crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t
     if ((rc = ddsp_scratch_get(ctx, total, &arena))) return rc;
     float* logp = (float*)arena;
     uint16_t* ptr = (uint16_t*)((char*)arena + align256(rows * BINS * 4));
-    hipLaunchKernelGGL(emission_kernel, dim3((unsigned)ceil_div64((int64_t)rows, 4)), dim3(256), 0, st, probs, (int64_t)rows, lo, hi, logp);
+    hipLaunchKernelGGL(emission_kernel, dim3((unsigned)ceil_div64((int64_t)rows, 4)), dim3(256), 0, st, probs, (int64_t)rows, lo, hi, logp,
+                       n_frames, Fr, f0, periodicity, bins);
     hipLaunchKernelGGL(viterbi_kernel, dim3((unsigned)ceil_div64(Fr, seg), (unsigned)B), dim3(VT), 0, st, logp, probs, Fr, seg, lo, hi,
-                       ptr, dither_seed, (const uint64_t*)seed_dev, use_dither ? 1 : 0, f0, periodicity, bins);
+                       ptr, dither_seed, (const uint64_t*)seed_dev, use_dither ? 1 : 0, f0, periodicity, bins, n_frames);
     // every workgroup of the decode has read the word when this one-thread kernel, next on the stream, advances it
     if (seed_dev) hipLaunchKernelGGL(seed_advance_kernel, dim3(1), dim3(1), 0, st, seed_dev);
     DDSP_LAUNCH_CHECK(ctx);
@@ -696,6 +794,14 @@ extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs
     return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, dither_seed, nullptr, use_dither, f0, periodicity, bins);
 }
 
+extern "C" int ddsp_crepe_decode_ragged(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr,
+                                        const int32_t* n_frames, float fmin, float fmax, int64_t segment, uint64_t dither_seed,
+                                        int use_dither, float* f0, float* periodicity, int32_t* bins) {
+    DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_crepe_decode_ragged: null argument");
+    return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, dither_seed, nullptr, use_dither, f0, periodicity, bins,
+                        n_frames);
+}
+
 extern "C" int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin,
                                        float fmax, int64_t segment, uint64_t* seed_dev, int use_dither, float* f0,
                                        float* periodicity, int32_t* bins) {
@@ -703,9 +809,9 @@ extern "C" int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float*
     return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, 0, seed_dev, use_dither, f0, periodicity, bins);
 }
 
-extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr,
-                                  double hop, int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min,
-                                  float* out) {
+static int f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr, double hop,
+                         int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min, float* out,
+                         const int32_t* n_crepe, const int32_t* n_out) {
     DDSP_REQUIRE(ctx, ctx && f0 && pd && out, "ddsp_f0_postfilter: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B < 65536 && Fr >= 3, "ddsp_f0_postfilter: B >= 1 and at least 3 frames (the reflect padding)");
     DDSP_REQUIRE(ctx, sr > 0 && hop > 0.0 && isfinite(hop), "ddsp_f0_postfilter: sr, hop > 0");
@@ -719,7 +825,21 @@ extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, 
     void* arena = nullptr;
     if ((rc = ddsp_scratch_get(ctx, total, &arena))) return rc;
     hipLaunchKernelGGL(postfilter_kernel, dim3((unsigned)B), dim3(256), 0, st, f0, pd, Fr, sr, hop, n_frames, start_frame, threshold,
-                       uv_interp ? 1 : 0, f0_min, (float*)arena, out);
+                       uv_interp ? 1 : 0, f0_min, (float*)arena, out, n_crepe, n_out);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr,
+                                  double hop, int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min,
+                                  float* out) {
+    return f0_postfilter(ctx, stream, f0, pd, B, Fr, sr, hop, n_frames, start_frame, threshold, uv_interp, f0_min, out, nullptr,
+                         nullptr);
+}
+
+extern "C" int ddsp_f0_postfilter_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr,
+                                         const int32_t* n_crepe, int sr, double hop, int64_t n_frames, const int32_t* n_out,
+                                         float threshold, int uv_interp, float f0_min, float* out) {
+    DDSP_REQUIRE(ctx, ctx && n_crepe && n_out, "ddsp_f0_postfilter_ragged: null argument");
+    return f0_postfilter(ctx, stream, f0, pd, B, Fr, sr, hop, n_frames, 0, threshold, uv_interp, f0_min, out, n_crepe, n_out);
 }

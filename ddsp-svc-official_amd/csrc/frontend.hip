@@ -12,13 +12,25 @@ namespace {
 // one wavefront per (utterance, frame).  Block n is padded[int(n*h) : min(int((n+1)*h), Tp)] of the signal reflect-padded
 // by pad_l in front (Tp = padded length), bounds in fp64 like the reference's Python floats; its mean divides by the
 // block's own length.  An integral hop gives start n*hop and length hop exactly, so both entry points share this kernel.
+// Ragged batch (n_samples != nullptr, integral hop): row b is its first n_samples[b] samples - it reflects at its own end,
+// has n_samples[b] / hop + 1 frames and 0 in the frames after them; what follows its samples is never read.
 __global__ void __launch_bounds__(256) volume_kernel(const float* __restrict__ audio, int64_t T, double hop, int64_t pad_l,
-                                                     int64_t Tp, int64_t n_frames, int64_t total, float* __restrict__ vol) {
+                                                     int64_t Tp, int64_t n_frames, int64_t total, float* __restrict__ vol,
+                                                     const int32_t* __restrict__ n_samples) {
     const int lane = threadIdx.x & 63;
     const int64_t fidx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (fidx >= total) return;
     const int64_t b = fidx / n_frames, n = fidx - b * n_frames;
     const float* x = audio + b * T;
+    if (n_samples) {
+        const int64_t pad = Tp - T, nb = n_samples[b];
+        T = nb < 1 ? 1 : (nb < T ? nb : T);
+        Tp = T + pad;
+        if (n >= T / (int64_t)hop + 1) {
+            if (lane == 0) vol[fidx] = 0.f;
+            return;
+        }
+    }
     const int64_t start = (int64_t)((double)n * hop);
     int64_t end = (int64_t)((double)(n + 1) * hop);
     end = end < Tp ? end : Tp;                        // numpy truncates the slice at the padded length
@@ -29,6 +41,7 @@ __global__ void __launch_bounds__(256) volume_kernel(const float* __restrict__ a
         int64_t i = first + j;
         if (i < 0) i = -i;                            // numpy 'reflect': edge sample not repeated
         if (i >= T) i = 2 * (T - 1) - i;
+        if (n_samples) i = i < 0 ? 0 : (i < T ? i : T - 1);   // (a count below the caller's bound: stay inside the row)
         const float v = x[i];
         s += (double)(v * v);                         // the square is rounded to fp32 first, like `audio ** 2`
     }
@@ -153,12 +166,12 @@ static double py_floordiv(double a, double b) {
 }
 
 static int volume_launch(ddsp_ctx* ctx, hipStream_t st, const float* audio, int64_t B, int64_t T, double hop, int64_t n_frames,
-                         int64_t pad_l, int64_t pad_r, float* volume) {
+                         int64_t pad_l, int64_t pad_r, float* volume, const int32_t* n_samples = nullptr) {
     DDSP_ENTER_DEVICE(ctx);
     const int64_t total = B * n_frames;
     ddsp_prof_begin(ctx, st, PF_OTHER);
     hipLaunchKernelGGL(volume_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, audio, T, hop, pad_l,
-                       T + pad_l + pad_r, n_frames, total, volume);
+                       T + pad_l + pad_r, n_frames, total, volume, n_samples);
     ddsp_prof_end(ctx, st, 2.0 * B * T, 4.0 * (B * (double)T + total));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
@@ -172,6 +185,15 @@ extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* aud
     DDSP_REQUIRE(ctx, T > (hop + 1) / 2, "ddsp_volume_extract: signal shorter than the reflect padding");
     if (B == 0) return DDSP_OK;
     return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume);
+}
+
+extern "C" int ddsp_volume_extract_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
+                                          const int32_t* n_samples, int hop, float* volume) {
+    DDSP_REQUIRE(ctx, ctx && audio && volume && n_samples, "ddsp_volume_extract_ragged: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && hop >= 1 && hop <= (1 << 20), "ddsp_volume_extract_ragged: bad shape");
+    DDSP_REQUIRE(ctx, T > (hop + 1) / 2, "ddsp_volume_extract_ragged: signal shorter than the reflect padding");
+    if (B == 0) return DDSP_OK;
+    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume, n_samples);
 }
 
 extern "C" int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, double hop_size,

@@ -88,15 +88,21 @@ class Crepe(nn.Module):
         return self._table.struct(self)[0]
 
     @torch.no_grad()
-    def activations(self, audio16, hop=HOP):
+    def activations(self, audio16, hop=HOP, n_samples=None, counts_dev=None):
         """:: (B, T) 16 kHz -> sigmoid activations (B, 1 + T // hop, 360) of torchcrepe.infer over torchcrepe.preprocess's
-        frames (pad=True)."""
-        if not audio16.is_cuda:
-            raise RuntimeError("Crepe runs on a HIP device only (no CPU fallback)")
+        frames (pad=True).
+        `n_samples` (a sequence of B ints or a CPU integer tensor (B,), each giving at least 3 frames): a RAGGED batch.  A
+        frame depends on its own 1024 samples only, so the network runs over the rows' own 1 + n_samples[b] // hop frames
+        and over no padding; row b is what the call returns for audio16[b:b+1, :n_samples[b]] and exactly 0 after its
+        frames.  A bad count raises ValueError before anything is launched.  (`counts_dev`: `Context.crepe_activations`.)"""
         if audio16.dim() != 2:
             raise ValueError("Crepe.activations: audio must be (B, T)")
+        if n_samples is not None:
+            n_samples = hipddsp.check_crepe_n_samples(n_samples, audio16.shape[0], audio16.shape[1], hop)
+        if not audio16.is_cuda:
+            raise RuntimeError("Crepe runs on a HIP device only (no CPU fallback)")
         x = audio16.contiguous().float()
-        return hipddsp.context_for(x.device).crepe_activations(self._weights_struct(), x, hop)
+        return hipddsp.context_for(x.device).crepe_activations(self._weights_struct(), x, hop, n_samples, counts_dev)
 
     def forward(self, audio16):
         return self.activations(audio16)

@@ -44,8 +44,20 @@ class Volume_Extractor:
         self.hop_size = hop_size
         self.device = device
 
-    def extract(self, audio):
+    def extract(self, audio, n_samples=None):
+        """`n_samples` (a sequence of B ints or a CPU integer tensor (B,), each > (hop_size + 1) // 2; device tensor (B,T) and
+        an integral hop only): a RAGGED batch - row b reflects at its own ends, carries n_samples[b] // hop_size + 1 frames
+        and is 0 after them, and what follows its samples may hold anything."""
         import numpy as np
+        if n_samples is not None:
+            if not isinstance(audio, torch.Tensor) or audio.dim() != 2:
+                raise ValueError("Volume_Extractor.extract: a ragged batch is a (B, T) tensor")
+            if not float(self.hop_size).is_integer():
+                raise ValueError("Volume_Extractor.extract: a ragged batch needs an integral hop_size")
+            vals = hipddsp.check_volume_n_samples(n_samples, audio.shape[0], audio.shape[1], int(self.hop_size))
+            if not audio.is_cuda:
+                raise RuntimeError("Volume_Extractor runs on a HIP device only (no CPU fallback)")
+            return hipddsp.context_for(audio.device).volume_extract(audio, int(self.hop_size), vals)
         is_np = isinstance(audio, np.ndarray)
         x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
         if not x.is_cuda:
@@ -89,6 +101,7 @@ class F0_Extractor:
         +-20 cents (a bin is 20 cents); `dither=False` makes the output deterministic, `seed` fixes the draw (default: drawn
         from torch's generator); `seed_dev` (a (1,) int64 device tensor) holds the seed on the device instead and is advanced
         by every call (`ddsp_crepe_decode_dseed`), so a call captured into a HIP graph dithers anew on every replay;
+      * `extract(audio (B,T), ..., n_samples=)`: a RAGGED batch of rows of different length (see `extract`);
       * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError."""
 
     def __init__(self, f0_extractor, sample_rate=44100, hop_size=512, f0_min=65, f0_max=800, *, crepe_ckpt=None, device=None):
@@ -117,11 +130,20 @@ class F0_Extractor:
         self.model = model.to(device).eval()
         self.device = device
 
-    def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None, seed_dev=None):
+    def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None, seed_dev=None,
+                n_samples=None):
         """audio (T,) numpy / (T,) or (B,T) device tensor at `sample_rate` -> f0 [Hz] (n_frames,) / (B, n_frames),
-        n_frames = int(T // hop_size) + 1.  `device` is accepted for the reference's signature (the model's device is used)."""
+        n_frames = int(T // hop_size) + 1.  `device` is accepted for the reference's signature (the model's device is used).
+        `n_samples` (a sequence of B ints or a CPU integer tensor (B,), counts at `sample_rate`; device tensor (B,T) only): a
+        RAGGED batch.  Row b is analysed as audio[b, :n_samples[b]] alone - resampling, framing, decode and post-filter
+        each stop at the row's own end, the network computes the rows' own frames only, and what follows a row's samples may
+        hold anything.  Returns (B, int(max(n_samples) // hop_size) + 1); row b carries int(n_samples[b] // hop_size) + 1
+        frames and zeros after them.  Every row must give at least 3 CREPE frames; `silence_front != 0` and `seed_dev` are
+        not available with it (ValueError)."""
         import numpy as np
         from .crepe import HOP, SAMPLE_RATE
+        if n_samples is not None:
+            return self._extract_ragged(audio, uv_interp, silence_front, dither, seed, seed_dev, n_samples)
         is_np = isinstance(audio, np.ndarray)
         x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
         if not x.is_cuda:
@@ -151,6 +173,42 @@ class F0_Extractor:
         out = ctx.f0_postfilter(f0, pd, sr, hop, n_frames, start_frame, 0.05, uv_interp, self.f0_min)
         out = out[0] if flat else out
         return out.cpu().numpy() if is_np else out
+
+
+    def _extract_ragged(self, audio, uv_interp, silence_front, dither, seed, seed_dev, n_samples):
+        from .crepe import HOP, SAMPLE_RATE
+        if silence_front != 0:
+            raise ValueError("F0_Extractor.extract: silence_front is not available with n_samples (a ragged batch)")
+        if seed_dev is not None:
+            raise ValueError("F0_Extractor.extract: seed_dev is not available with n_samples (a ragged batch)")
+        if not isinstance(audio, torch.Tensor) or audio.dim() != 2:
+            raise ValueError("F0_Extractor.extract: a ragged batch is a (B, T) tensor")
+        B, T = audio.shape
+        sr, hop = self.sample_rate, self.hop_size
+        vals = hipddsp.check_n_samples(n_samples, B, T)
+        resampled = int(sr) != SAMPLE_RATE
+        lib = hipddsp.load_library()
+        n16 = [int(lib.ddsp_resample_length(v, int(sr), SAMPLE_RATE)) for v in vals] if resampled else vals
+        T16 = int(lib.ddsp_resample_length(T, int(sr), SAMPLE_RATE)) if resampled else T
+        n16 = hipddsp.check_crepe_n_samples(n16, B, T16, HOP)     # (before any launch)
+        if not audio.is_cuda:
+            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
+        ctx = hipddsp.context_for(audio.device)
+        n_crepe = [hipddsp.crepe_frames(v, HOP) for v in n16]
+        n_out = [int(v // hop) + 1 for v in vals]
+        # one upload: the rows' samples, the activations' table (16 kHz samples, frame prefix), CREPE frames, output frames
+        table = hipddsp.crepe_ragged_table(n16, HOP)
+        dev = ctx.ragged_counts(vals + table + n_crepe + n_out)
+        n_dev, table_dev, nc_dev, no_dev = dev[:B], dev[B:3 * B + 1], dev[3 * B + 1:4 * B + 1], dev[4 * B + 1:]
+        x = audio.contiguous().float()
+        x16 = ctx.resample_ragged(x, n_dev, int(sr), SAMPLE_RATE, lowpass_filter_width=128) if resampled else x
+        probs = self.model.activations(x16, HOP, n16, table_dev)
+        if dither and seed is None:
+            seed = _seed_from_torch()
+        f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither_seed=int(seed or 0), dither=dither,
+                                  n_frames=n_crepe, counts_dev=nc_dev)
+        return ctx.f0_postfilter(f0, pd, sr, hop, max(n_out), 0, 0.05, uv_interp, self.f0_min, n_crepe=n_crepe, n_out=n_out,
+                                 counts_dev=(nc_dev, no_dev))
 
 
 def align_units(units, n_samples, sample_rate, hop_size, encoder_sample_rate=16000, encoder_hop_size=320):

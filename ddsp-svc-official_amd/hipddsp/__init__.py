@@ -211,6 +211,10 @@ SIGNATURES = {
     "ddsp_nsf_post_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp, _int]),
     "ddsp_stft_frames_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp]),
     "ddsp_retime_f0_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _f64, _f32, _f64, _i64, _vp, _vp]),
+    "ddsp_volume_extract_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
+    "ddsp_crepe_activations_ragged": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _vp, _vp, _i64, _int, _vp]),
+    "ddsp_crepe_decode_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
+    "ddsp_f0_postfilter_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _i64, _vp, _f32, _int, _f32, _vp]),
     "ddsp_crepe_frames": (_i64, [_i64, _int]),
     "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _int, _vp]),
     "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
@@ -312,6 +316,26 @@ def check_hubert_n_samples(n_samples, B, T):
     for b, v in enumerate(vals):
         if hubert_frames(v) < 1:
             raise ValueError(f"n_samples[{b}] = {v} samples are too short for the conv stack")
+    return vals
+
+
+def check_crepe_n_samples(n_samples, B, T, hop=80):
+    """`check_n_samples` for the f0 extractor (counts at 16 kHz): every row must also give at least 3 CREPE frames, which the
+    reflect-padded filters behind the decode need (`crepe_frames(n, hop) >= 3`)."""
+    vals = check_n_samples(n_samples, B, T)
+    for b, v in enumerate(vals):
+        if crepe_frames(v, hop) < 3:
+            raise ValueError(f"n_samples[{b}] = {v} samples at 16 kHz give {crepe_frames(v, hop)} CREPE frames; the "
+                             "reflect-padded filters need at least 3")
+    return vals
+
+
+def check_volume_n_samples(n_samples, B, T, hop):
+    """`check_n_samples` for the volume: every row must be longer than its reflect padding, n > (hop + 1) // 2."""
+    vals = check_n_samples(n_samples, B, T)
+    for b, v in enumerate(vals):
+        if v <= (int(hop) + 1) // 2:
+            raise ValueError(f"n_samples[{b}] = {v} samples are not longer than the reflect padding {(int(hop) + 1) // 2}")
     return vals
 
 
@@ -489,6 +513,12 @@ class Context:
         """counts: the list `check_n_frames` returned -> the (B,) int32 device tensor the ragged calls take (one upload)."""
         return torch.tensor(counts, dtype=torch.int32).to(self.device)
 
+    @staticmethod
+    def _counts_dev(t, B):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() == B and t.is_contiguous()):
+            raise ValueError("counts_dev must be a contiguous (B,) int32 device tensor (`ragged_counts`)")
+        return t
+
     def ragged_frames(self, x, n_dev, hold, out=None):
         """x (B,Fr,C) or (B,Fr) -> frames past a row's count replaced by its last frame (hold) or by 0; `out=x`: in place."""
         B, Fr = x.shape[0], x.shape[1]
@@ -628,12 +658,23 @@ class Context:
                   rows, int(sr), _ptr(d_ir), _ptr(d_ctrl2d) + 4 * col0, d_ctrl2d.shape[-1])
 
     # -- front-end steps -----------------------------------------------------
-    def volume_extract(self, audio, hop):
+    def volume_extract(self, audio, hop, n_samples=None):
         """audio (B,T) fp32 -> (B, int(T // hop) + 1) block RMS with numpy-'reflect' padding (ddsp/vocoder.py:116-137).
         `hop` may be a non-integral float (an input at another rate than the model's: block_size * sr / model_sr); an
-        integral one, int or float, takes the integer entry point."""
+        integral one, int or float, takes the integer entry point.
+        `n_samples` (a sequence of B ints or a CPU integer tensor (B,), integral hop only): a RAGGED batch - row b reflects at
+        its own ends, carries n_samples[b] // hop + 1 frames and is 0 after them; its padding is never read."""
         audio = audio.contiguous().float()
         B, T = audio.shape
+        if n_samples is not None:
+            if not float(hop).is_integer():
+                raise ValueError("volume_extract: a ragged batch needs an integral hop")
+            vals = check_volume_n_samples(n_samples, B, T, int(hop))
+            out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
+            if B:
+                n_dev = self.ragged_counts(vals)
+                self.call("ddsp_volume_extract_ragged", _ptr(audio), B, T, _ptr(n_dev), int(hop), _ptr(out))
+            return out
         if float(hop).is_integer():
             out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
             if B == 0:
@@ -948,23 +989,57 @@ class Context:
         return out
 
     # -- f0 extractor (CREPE) --------------------------------------------------------------------
-    def crepe_activations(self, weights, audio16, hop=80):
-        """weights: a CrepeWeights struct; audio16 (B,T) 16 kHz fp32 -> sigmoid activations (B, 1 + T // hop, 360)."""
+    def crepe_activations(self, weights, audio16, hop=80, n_samples=None, counts_dev=None):
+        """weights: a CrepeWeights struct; audio16 (B,T) 16 kHz fp32 -> sigmoid activations (B, 1 + T // hop, 360).
+        `n_samples` (a sequence of B ints or a CPU integer tensor (B,)): a RAGGED batch - the network runs over the packed
+        list of the rows' own 1 + n_samples[b] // hop frames only, row b is what the call returns for audio16[b, :n_samples[b]]
+        alone and 0 after its frames, and what follows a row's samples is never read.  `counts_dev`: a caller that has
+        already uploaded `crepe_ragged_table(n_samples, hop)` passes the (2B + 1,) int32 device tensor (one upload for a chain
+        of ragged calls); None uploads it here."""
         B, T = audio16.shape
         Fr = crepe_frames(T, hop)
         x = audio16.contiguous().float()
+        if n_samples is not None:
+            vals = check_crepe_n_samples(n_samples, B, T, hop)
+            table = crepe_ragged_table(vals, hop)
+            if counts_dev is None:
+                counts_dev = self.ragged_counts(table)
+            elif counts_dev.dtype != torch.int32 or counts_dev.numel() != 2 * B + 1 or not counts_dev.is_contiguous():
+                raise ValueError("crepe_activations: counts_dev must be the (2B + 1,) int32 upload of crepe_ragged_table")
+            out = torch.empty(B, Fr, 360, device=x.device, dtype=torch.float32)
+            if B:
+                self.call("ddsp_crepe_activations_ragged", ctypes.byref(weights), _ptr(x), int(B), int(T), _ptr(counts_dev),
+                          _ptr(counts_dev) + 4 * B, int(table[-1]), int(hop), _ptr(out))
+            return out
         out = torch.empty(B, Fr, 360, device=x.device, dtype=torch.float32)
         if B:
             self.call("ddsp_crepe_activations", ctypes.byref(weights), _ptr(x), int(B), int(T), int(hop), _ptr(out))
         return out
 
-    def crepe_decode(self, probs, fmin, fmax, segment=512, dither_seed=0, dither=False, want_bins=False, seed_dev=None):
+    def crepe_decode(self, probs, fmin, fmax, segment=512, dither_seed=0, dither=False, want_bins=False, seed_dev=None,
+                     n_frames=None, counts_dev=None):
         """probs (B, Fr, 360) -> (f0 (B, Fr), periodicity (B, Fr)[, bins (B, Fr) int32]): the range mask, the Viterbi decode
         in independent pieces of `segment` frames (0: whole track), bins to Hz with the optional triangular dither.
         `seed_dev`: a (1,) int64 device tensor that holds the dither seed instead of `dither_seed` and is advanced to
-        `next_dither_seed` of its value by the call (`ddsp_crepe_decode_dseed`: what a captured graph needs)."""
+        `next_dither_seed` of its value by the call (`ddsp_crepe_decode_dseed`: what a captured graph needs).
+        `n_frames` (a sequence of B ints or a CPU integer tensor (B,)): a RAGGED batch - row b is decoded over its own
+        n_frames[b] frames as a call on probs[b:b+1, :n_frames[b]] with the same seed decodes it, bit for bit, and every
+        output is 0 after them.  `counts_dev`: the (B,) int32 device tensor of the same counts when the caller has
+        uploaded them already (`ragged_counts`); None uploads them here."""
         p = probs.contiguous().float()
         B, Fr, _ = p.shape
+        if n_frames is not None:
+            if seed_dev is not None:
+                raise ValueError("crepe_decode: seed_dev is not available with n_frames (a ragged batch)")
+            vals = check_n_frames(n_frames, B, Fr)
+            n_dev = self._counts_dev(counts_dev, B) if counts_dev is not None else self.ragged_counts(vals)
+            f0 = torch.empty(B, Fr, device=p.device, dtype=torch.float32)
+            pd = torch.empty_like(f0)
+            bins = torch.empty(B, Fr, device=p.device, dtype=torch.int32) if want_bins else None
+            if B and Fr:
+                self.call("ddsp_crepe_decode_ragged", _ptr(p), int(B), int(Fr), _ptr(n_dev), float(fmin), float(fmax),
+                          int(segment), int(dither_seed) & ((1 << 64) - 1), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
+            return (f0, pd, bins) if want_bins else (f0, pd)
         f0 = torch.empty(B, Fr, device=p.device, dtype=torch.float32)
         pd = torch.empty_like(f0)
         bins = torch.empty(B, Fr, device=p.device, dtype=torch.int32) if want_bins else None
@@ -978,15 +1053,40 @@ class Context:
                       int(dither_seed) & ((1 << 64) - 1), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
         return (f0, pd, bins) if want_bins else (f0, pd)
 
-    def f0_postfilter(self, f0, pd, sr, hop, n_frames, start_frame=0, threshold=0.05, uv_interp=False, f0_min=65.0):
+    def f0_postfilter(self, f0, pd, sr, hop, n_frames, start_frame=0, threshold=0.05, uv_interp=False, f0_min=65.0,
+                      n_crepe=None, n_out=None, counts_dev=None):
         """f0, pd (B, Fr) at the CREPE rate -> (B, n_frames): the reference's median / threshold / masked-average filter,
         re-timed to frames of `hop` samples at `sr` (a float hop keeps its fraction), `start_frame` zeros in front, and
-        with uv_interp the numpy.interp fill of the zero frames and the clamp to f0_min (ddsp/vocoder.py:96-113)."""
+        with uv_interp the numpy.interp fill of the zero frames and the clamp to f0_min (ddsp/vocoder.py:96-113).
+        `n_crepe`, `n_out` (both or neither; sequences of B ints or CPU integer tensors (B,)): a RAGGED batch - row b has
+        n_crepe[b] >= 3 CREPE frames and n_out[b] <= n_frames output frames of its own; its windows reflect at its own end,
+        the fill looks at its own frames only, and the output is 0 after them.  start_frame must be 0.  `counts_dev`: the
+        pair of (B,) int32 device tensors of the same counts when the caller has uploaded them already."""
         f0 = f0.contiguous().float()
         pd = pd.contiguous().float()
         B, Fr = f0.shape
         if pd.shape != f0.shape:
             raise ValueError("f0_postfilter: f0 and pd must have the same shape")
+        if (n_crepe is None) != (n_out is None):
+            raise ValueError("f0_postfilter: a ragged batch needs both n_crepe and n_out")
+        if n_crepe is not None:
+            if int(start_frame) != 0:
+                raise ValueError("f0_postfilter: start_frame must be 0 with n_crepe / n_out (a ragged batch)")
+            vals = []
+            for name, c, lo, hi in (("n_crepe", n_crepe, 3, Fr), ("n_out", n_out, 1, int(n_frames))):
+                vals.append(_check_counts(name, c, B))
+                for b, v in enumerate(vals[-1]):
+                    if not lo <= v <= hi:
+                        raise ValueError(f"{name}[{b}] = {v} is outside {lo}..{hi}")
+            if counts_dev is not None:
+                nc, no = (self._counts_dev(c, B) for c in counts_dev)
+            else:
+                nc, no = self.ragged_counts(vals[0] + vals[1]).reshape(2, B)
+            out = torch.empty(B, int(n_frames), device=f0.device, dtype=torch.float32)
+            if B:
+                self.call("ddsp_f0_postfilter_ragged", _ptr(f0), _ptr(pd), int(B), int(Fr), _ptr(nc), int(sr), float(hop),
+                          int(n_frames), _ptr(no), float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
+            return out
         out = torch.empty(B, int(n_frames), device=f0.device, dtype=torch.float32)
         if B:
             self.call("ddsp_f0_postfilter", _ptr(f0), _ptr(pd), int(B), int(Fr), int(sr), float(hop), int(n_frames),
@@ -1104,6 +1204,16 @@ def crepe_frames(T16, hop=80):
     if n < 0:
         raise ValueError(f"crepe_frames: bad length {T16} or hop {hop}")
     return n
+
+
+def crepe_ragged_table(n16, hop=80):
+    """Checked per-row 16 kHz sample counts -> the list of 2B + 1 ints a ragged `crepe_activations` uploads once: the B
+    counts, then the B + 1 exclusive prefix sums of the rows' frame counts (the packed frame list; its last entry is the
+    number of frames the network runs over)."""
+    prefix = [0]
+    for v in n16:
+        prefix.append(prefix[-1] + crepe_frames(v, hop))
+    return list(n16) + prefix
 
 
 class use_context:

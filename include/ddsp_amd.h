@@ -303,7 +303,12 @@ int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, const float* vo
  * exceed (hop+1)/2). */
 int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
                         float* volume);
-/* the same at the non-integral hop `block_size * sample_rate / model_rate` that an input at another rate than the model's
+/* ddsp_volume_extract over a ragged batch: n_samples is a DEVICE array of B int32 (the caller checks (hop+1)/2 <
+ * n_samples[b] <= T); row b reflects at its own ends (i >= n_b -> 2 (n_b - 1) - i), has n_samples[b] / hop + 1 frames
+ * and exact zeros after them; audio[b][i] for i >= n_samples[b] is never read.  volume (B, T/hop + 1). */
+int ddsp_volume_extract_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
+                               const int32_t* n_samples, int hop, float* volume);
+/* ddsp_volume_extract at the non-integral hop `block_size * sample_rate / model_rate` that an input at another rate than the model's
  * gives (main.py:72,109, gui.py:94): volume (B, int(T // hop_size) + 1), block n = padded[int(n * hop_size) :
  * int((n + 1) * hop_size)] of the signal reflect-padded by (int(hop_size // 2), int((hop_size + 1) // 2)), all in fp64
  * like the reference's Python floats; each block's mean divides by its own length.  1 <= hop_size <= 2^20, and T must
@@ -614,6 +619,31 @@ int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float* probs, int
  * any frame is non-zero) and out = max(out, f0_min). */
 int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr, double hop,
                        int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min, float* out);
+
+/* ---- the f0 extractor over a ragged batch --------------------------------------------------------------------------------
+ * Every count is a DEVICE array of B int32 that the caller has checked and that is never read back; a kernel holds a value
+ * outside its range at the nearest bound.  Row b of each result is what the rectangular call returns for the row alone at
+ * its own length, and exactly 0 after it; what the inputs hold past a row's end (NaN included) is never read into arithmetic.
+ * ddsp_crepe_activations_ragged: audio16 (B, T) with n_samples[b] <= T samples per row -> probs (B, Fr, 360), Fr =
+ *   ddsp_crepe_frames(T, hop), row b with Fr_b = ddsp_crepe_frames(n_samples[b], hop) frames.  A frame depends on its own
+ *   1024 samples only, so the network runs over the PACKED list of the rows' real frames: frame_prefix is the DEVICE array
+ *   of B + 1 int32 exclusive prefix sums of Fr_b (frame_prefix[0] = 0) and n_packed = frame_prefix[B] its total, which the
+ *   host knows.  A frame reads samples < 0 or >= n_samples[b] of its row as 0 by a bounds test.
+ * ddsp_crepe_decode_ragged: probs (B, Fr, 360) with n_frames[b] <= Fr frames per row.  The pieces of `segment` frames are cut
+ *   per row, the last one ends at the row's own last frame, and the dither is drawn for the row-local frame: row b equals
+ *   ddsp_crepe_decode of probs[b][:n_frames[b]] alone with the same seed, bit for bit.
+ * ddsp_f0_postfilter_ragged: f0, pd (B, Fr) with n_crepe[b] in 3..Fr frames per row -> out (B, n_frames) with n_out[b] <=
+ *   n_frames frames per row (start_frame = 0): the reflect windows and the re-timing clamp use n_crepe[b], and the
+ *   uv_interp fill looks at the row's own n_out[b] frames only. */
+int ddsp_crepe_activations_ragged(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16, int64_t B,
+                                  int64_t T, const int32_t* n_samples, const int32_t* frame_prefix, int64_t n_packed, int hop,
+                                  float* probs);
+int ddsp_crepe_decode_ragged(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, const int32_t* n_frames,
+                             float fmin, float fmax, int64_t segment, uint64_t dither_seed, int use_dither, float* f0,
+                             float* periodicity, int32_t* bins);
+int ddsp_f0_postfilter_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr,
+                              const int32_t* n_crepe, int sr, double hop, int64_t n_frames, const int32_t* n_out,
+                              float threshold, int uv_interp, float f0_min, float* out);
 
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream --------------------- */
 /* ddsp_profile_begin arms the families in `family_mask` (bit i = family i, see the name returned); while armed,
