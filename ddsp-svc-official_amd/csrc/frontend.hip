@@ -126,31 +126,32 @@ __global__ void __launch_bounds__(256) retime_f0_kernel(const float* __restrict_
 
 }  // namespace
 
-extern "C" int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, double step_num, double div,
-                              float scale, double step_dst, int64_t n_dst, float* out) {
+// both retime entry points: ns == nd == nullptr is the solo call (B = 1, every knot and target)
+static int retime_f0_go(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* ns, double step_num,
+                        double div, float scale, double step_dst, int64_t n_dst, const int32_t* nd, float* out) {
     DDSP_REQUIRE(ctx, ctx && f0 && out, "ddsp_retime_f0: null argument");
-    DDSP_REQUIRE(ctx, n_src >= 1 && n_dst >= 0 && step_num > 0 && div > 0 && step_dst > 0, "ddsp_retime_f0: bad shape or step");
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && n_src >= 1 && n_dst >= 0 && step_num > 0 && div > 0 && step_dst > 0,
+                 "ddsp_retime_f0: bad shape or step");
     if (n_dst == 0) return DDSP_OK;
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
-    hipLaunchKernelGGL(retime_f0_kernel, dim3((unsigned)ceil_div64(n_dst, 256)), dim3(256), 0, st, f0, n_src, step_num, div, scale,
-                       step_dst, n_dst, out, (const int32_t*)nullptr, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(retime_f0_kernel, dim3((unsigned)ceil_div64(n_dst, 256), (unsigned)B), dim3(256), 0, st, f0, n_src, step_num, div,
+                       scale, step_dst, n_dst, out, ns, nd);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, double step_num, double div,
+                              float scale, double step_dst, int64_t n_dst, float* out) {
+    return retime_f0_go(ctx, stream, f0, 1, n_src, nullptr, step_num, div, scale, step_dst, n_dst, nullptr, out);
 }
 
 extern "C" int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
                                      double step_num, double div, float scale, double step_dst, int64_t n_dst,
                                      const int32_t* n_dst_rows, float* out) {
-    DDSP_REQUIRE(ctx, ctx && f0 && out && n_src_rows && n_dst_rows, "ddsp_retime_f0_ragged: null argument");
-    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && n_src >= 1 && n_dst >= 1 && step_num > 0 && div > 0 && step_dst > 0,
-                 "ddsp_retime_f0_ragged: bad shape or step");
-    hipStream_t st = (hipStream_t)stream;
-    DDSP_ENTER_DEVICE(ctx);
-    hipLaunchKernelGGL(retime_f0_kernel, dim3((unsigned)ceil_div64(n_dst, 256), (unsigned)B), dim3(256), 0, st, f0, n_src, step_num, div,
-                       scale, step_dst, n_dst, out, n_src_rows, n_dst_rows);
-    DDSP_LAUNCH_CHECK(ctx);
-    return DDSP_OK;
+    DDSP_REQUIRE(ctx, ctx && n_src_rows && n_dst_rows, "ddsp_retime_f0_ragged: null argument");
+    DDSP_REQUIRE(ctx, n_dst >= 1, "ddsp_retime_f0_ragged: bad shape or step");
+    return retime_f0_go(ctx, stream, f0, B, n_src, n_src_rows, step_num, div, scale, step_dst, n_dst, n_dst_rows, out);
 }
 
 // Python's float floor division `a // b` (CPython float_floor_div: fmod, exact quotient of the remainder-free part, floor,
@@ -166,7 +167,7 @@ static double py_floordiv(double a, double b) {
 }
 
 static int volume_launch(ddsp_ctx* ctx, hipStream_t st, const float* audio, int64_t B, int64_t T, double hop, int64_t n_frames,
-                         int64_t pad_l, int64_t pad_r, float* volume, const int32_t* n_samples = nullptr) {
+                         int64_t pad_l, int64_t pad_r, float* volume, const int32_t* n_samples) {
     DDSP_ENTER_DEVICE(ctx);
     const int64_t total = B * n_frames;
     ddsp_prof_begin(ctx, st, PF_OTHER);
@@ -177,23 +178,26 @@ static int volume_launch(ddsp_ctx* ctx, hipStream_t st, const float* audio, int6
     return DDSP_OK;
 }
 
-extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
-                                   float* volume) {
+// both integral-hop entry points: n_samples == nullptr is the rectangular batch
+static int volume_extract_go(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int hop,
+                             float* volume) {
     DDSP_REQUIRE(ctx, ctx && audio && volume, "ddsp_volume_extract: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && hop >= 1 && hop <= (1 << 20), "ddsp_volume_extract: bad shape");
     // numpy's reflect padding needs the pad (at most (hop+1)/2) to be smaller than the signal
     DDSP_REQUIRE(ctx, T > (hop + 1) / 2, "ddsp_volume_extract: signal shorter than the reflect padding");
     if (B == 0) return DDSP_OK;
-    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume);
+    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume, n_samples);
+}
+
+extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
+                                   float* volume) {
+    return volume_extract_go(ctx, stream, audio, B, T, nullptr, hop, volume);
 }
 
 extern "C" int ddsp_volume_extract_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
                                           const int32_t* n_samples, int hop, float* volume) {
-    DDSP_REQUIRE(ctx, ctx && audio && volume && n_samples, "ddsp_volume_extract_ragged: null argument");
-    DDSP_REQUIRE(ctx, B >= 0 && hop >= 1 && hop <= (1 << 20), "ddsp_volume_extract_ragged: bad shape");
-    DDSP_REQUIRE(ctx, T > (hop + 1) / 2, "ddsp_volume_extract_ragged: signal shorter than the reflect padding");
-    if (B == 0) return DDSP_OK;
-    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume, n_samples);
+    DDSP_REQUIRE(ctx, ctx && n_samples, "ddsp_volume_extract_ragged: null argument");
+    return volume_extract_go(ctx, stream, audio, B, T, n_samples, hop, volume);
 }
 
 extern "C" int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, double hop_size,
@@ -205,31 +209,15 @@ extern "C" int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float
     DDSP_REQUIRE(ctx, T > pad_r, "ddsp_volume_extract_frac: signal shorter than the reflect padding");
     if (B == 0) return DDSP_OK;
     const int64_t n_frames = (int64_t)py_floordiv((double)T, hop_size) + 1;
-    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, hop_size, n_frames, pad_l, pad_r, volume);
+    return volume_launch(ctx, (hipStream_t)stream, audio, B, T, hop_size, n_frames, pad_l, pad_r, volume, nullptr);
 }
 
-extern "C" int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
-                                int64_t n_frames, float ratio, float* out) {
+// both align entry points: n_units == n_out == nullptr is the rectangular batch
+static int align_units_go(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C, int64_t n_frames,
+                          float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
     DDSP_REQUIRE(ctx, ctx && units && out, "ddsp_align_units: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && Lu >= 1 && C >= 1 && n_frames >= 0 && ratio >= 0.f && ratio == ratio,
                  "ddsp_align_units: bad shape or ratio");
-    if (B == 0 || n_frames == 0) return DDSP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DDSP_ENTER_DEVICE(ctx);
-    const int64_t total = B * n_frames;
-    ddsp_prof_begin(ctx, st, PF_OTHER);
-    hipLaunchKernelGGL(align_units_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, units, Lu, C, n_frames,
-                       ratio, total, out, (const int32_t*)nullptr, (const int32_t*)nullptr);
-    ddsp_prof_end(ctx, st, 0.0, 8.0 * total * (double)C);
-    DDSP_LAUNCH_CHECK(ctx);
-    return DDSP_OK;
-}
-
-extern "C" int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
-                                       int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
-    DDSP_REQUIRE(ctx, ctx && units && out && n_units && n_out, "ddsp_align_units_ragged: null argument");
-    DDSP_REQUIRE(ctx, B >= 0 && Lu >= 1 && C >= 1 && n_frames >= 0 && ratio >= 0.f && ratio == ratio,
-                 "ddsp_align_units_ragged: bad shape or ratio");
     if (B == 0 || n_frames == 0) return DDSP_OK;
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
@@ -240,4 +228,15 @@ extern "C" int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float*
     ddsp_prof_end(ctx, st, 0.0, 8.0 * total * (double)C);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
+                                int64_t n_frames, float ratio, float* out) {
+    return align_units_go(ctx, stream, units, B, Lu, C, n_frames, ratio, nullptr, nullptr, out);
+}
+
+extern "C" int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
+                                       int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
+    DDSP_REQUIRE(ctx, ctx && n_units && n_out, "ddsp_align_units_ragged: null argument");
+    return align_units_go(ctx, stream, units, B, Lu, C, n_frames, ratio, n_units, n_out, out);
 }

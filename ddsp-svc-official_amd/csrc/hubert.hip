@@ -701,8 +701,9 @@ extern "C" int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert
     return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out);
 }
 
-extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
-                                      int64_t L, int heads, float* out, int math) {
+// both attention entry points: n_keys == nullptr attends over all L rows
+static int softmax_attention_go(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B, int64_t L,
+                                int heads, float* out, int math, const int32_t* n_keys) {
     DDSP_REQUIRE(ctx, ctx && q && k && v && out, "ddsp_softmax_attention: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && L >= 0 && L < (1 << 30) && heads >= 1 && heads <= 4096, "ddsp_softmax_attention: bad shape");
     DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16, "ddsp_softmax_attention: unknown math");
@@ -711,10 +712,18 @@ extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* 
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     ddsp_prof_begin(ctx, st, PF_OTHER);
-    attention_launch<false>(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads);
+    if (n_keys)
+        attention_launch<true>(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads, n_keys, 1);
+    else
+        attention_launch<false>(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads);
     ddsp_prof_end(ctx, st, 4.0 * B * heads * (double)L * L * HDH, 16.0 * B * L * heads * HDH);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
+                                      int64_t L, int heads, float* out, int math) {
+    return softmax_attention_go(ctx, stream, q, k, v, B, L, heads, out, math, nullptr);
 }
 
 extern "C" int ddsp_hubert_soft_units_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav,
@@ -732,17 +741,6 @@ extern "C" int ddsp_hubert_encode_ragged(ddsp_ctx* ctx, void* stream, const ddsp
 
 extern "C" int ddsp_softmax_attention_ragged(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v,
                                              int64_t B, int64_t L, int heads, float* out, int math, const int32_t* n_keys) {
-    DDSP_REQUIRE(ctx, ctx && q && k && v && out && n_keys, "ddsp_softmax_attention_ragged: null argument");
-    DDSP_REQUIRE(ctx, B >= 0 && L >= 0 && L < (1 << 30) && heads >= 1 && heads <= 4096, "ddsp_softmax_attention_ragged: bad shape");
-    DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16, "ddsp_softmax_attention_ragged: unknown math");
-    DDSP_REQUIRE(ctx, (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 16) == 0,
-                 "ddsp_softmax_attention_ragged: 16-byte aligned operands");
-    if (B == 0 || L == 0) return DDSP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DDSP_ENTER_DEVICE(ctx);
-    ddsp_prof_begin(ctx, st, PF_OTHER);
-    attention_launch<true>(st, q, k, v, (int64_t)heads * HDH, out, (int64_t)heads * HDH, B, (int)L, heads, n_keys, 1);
-    ddsp_prof_end(ctx, st, 4.0 * B * heads * (double)L * L * HDH, 16.0 * B * L * heads * HDH);
-    DDSP_LAUNCH_CHECK(ctx);
-    return DDSP_OK;
+    DDSP_REQUIRE(ctx, ctx && n_keys, "ddsp_softmax_attention_ragged: null argument");
+    return softmax_attention_go(ctx, stream, q, k, v, B, L, heads, out, math, n_keys);
 }

@@ -201,7 +201,7 @@ class F0_Extractor:
         dev = ctx.ragged_counts(vals + table + n_crepe + n_out)
         n_dev, table_dev, nc_dev, no_dev = dev[:B], dev[B:3 * B + 1], dev[3 * B + 1:4 * B + 1], dev[4 * B + 1:]
         x = audio.contiguous().float()
-        x16 = ctx.resample_ragged(x, n_dev, int(sr), SAMPLE_RATE, lowpass_filter_width=128) if resampled else x
+        x16 = ctx.resample(x, int(sr), SAMPLE_RATE, lowpass_filter_width=128, n_dev=n_dev) if resampled else x
         probs = self.model.activations(x16, HOP, n16, table_dev)
         if dither and seed is None:
             seed = _seed_from_torch()
@@ -308,11 +308,11 @@ class Units_Encoder:
         n_out = [int(v // hop_size) + 1 for v in vals]
         # one upload for the four count vectors
         dev = ctx.ragged_counts(vals + n16 + n_units + n_out).reshape(4, B)
-        audio_res = ctx.resample_ragged(audio, dev[0], int(sample_rate), int(self.encoder_sample_rate),
-                                        lowpass_filter_width=128) if resampled else audio
+        audio_res = ctx.resample(audio, int(sample_rate), int(self.encoder_sample_rate), lowpass_filter_width=128,
+                                 n_dev=dev[0]) if resampled else audio
         units = self.model(audio_res, RaggedCounts(n16, T16, dev[1]))
         ratio = (hop_size / sample_rate) / (self.encoder_hop_size / self.encoder_sample_rate)
-        return ctx.align_units_ragged(units, max(n_out), ratio, dev[2], dev[3])
+        return ctx.align_units(units, max(n_out), ratio, n_units_dev=dev[2], n_out_dev=dev[3])
 
 
 class DotDict(dict):

@@ -123,6 +123,7 @@ class STFT:
         pad_right = max((n - hop + 1) // 2, n - y.size(-1) - pad_left)
         mode = "reflect" if pad_right < y.size(-1) else "constant"
         yp = F.pad(y.unsqueeze(1), (pad_left, pad_right), mode=mode).squeeze(1)           # (memory movement only)
+        # (torch framing on purpose: the tests hold `stft_frames`, the device framing of the other shapes, against this path)
         frames = yp[0].unfold(0, n, hop).contiguous()                                      # (frames, n_fft)
         tab, mel = self._device_tables(y.device)
         out = hipddsp.context_for(y.device).log_mel(frames, tab, mel, self.clip_val)      # (frames, n_mels)
@@ -136,7 +137,7 @@ class STFT:
         frames_of = [self.frame_count(v) for v in (vals if vals is not None else [T] * B)]
         L = max(frames_of)
         n_dev = None if vals is None else c.ragged_counts(vals)
-        frames = c.stft_frames_ragged(y, n_dev, self.n_fft, self.hop_length, L)
+        frames = c.stft_frames(y, n_dev, self.n_fft, self.hop_length, L)
         tab, mel = self._device_tables(y.device)
         out = c.log_mel(frames.reshape(B * L, self.n_fft), tab, mel, self.clip_val).reshape(B, L, self.n_mels)
         if vals is not None:          # log-mel of an empty frame is log(clip), not 0
@@ -296,11 +297,9 @@ class Generator(torch.nn.Module):
         elif not isinstance(n_frames, RaggedCounts):
             n_dev = c.ragged_counts(n_frames)
         # B rows flattened on the time axis, (B * T, C); `rows(scale)` tells a call where each row ends at the current rate
-        # (None: the solo entry points, one utterance and no counts)
-        batched = B != 1 or n_dev is not None
-
+        # (n_dev None: every row whole)
         def rows(scale):
-            return (B, n_dev, scale) if batched else None
+            return (B, n_dev, scale)
 
         f0 = f0.reshape(B, -1)[:, :L].contiguous().float()
         if rand_ini is None:
@@ -310,10 +309,7 @@ class Generator(torch.nn.Module):
         rand_ini[:, 0] = 0
         rand_ini = rand_ini.to(x.device)
         sr = int(self.h.sampling_rate)
-        if batched:
-            src = c.nsf_source_ragged(f0, rand_ini, P["lin_w"], P["lin_b"], self.upp, sr, 0.1, n_dev)       # (B, L * upp)
-        else:
-            src = c.nsf_source(f0[0], rand_ini[0], P["lin_w"], P["lin_b"], self.upp, sr, 0.1)
+        src = c.nsf_source(f0, rand_ini, P["lin_w"], P["lin_b"], self.upp, sr, 0.1, n_dev)                  # (B, L * upp)
         # Every convolution below reads leaky_relu(., 0.1) of its producer's result (models.py:60-62, 251): the producers
         # write that activated copy themselves (`act_slope`), next to the raw result where a residual path or the stage mean
         # needs it, so that the consumers take their input as it is (in_slope = 1) and run on the LDS-DMA GEMM.  With
@@ -340,10 +336,7 @@ class Generator(torch.nn.Module):
             w_up, w_up_s, b_up, u, cout = P["ups"][i]
             nw, nb, (nk, ns, npad) = P["noise"][i]
             T_out = T * u
-            if batched:
-                x_source = c.nsf_noise_conv_ragged(src, nw, nb, nk, ns, npad, T_out)               # (B * T_out, cout)
-            else:
-                x_source = c.nsf_noise_conv(src, nw, nb, nk, ns, npad, T_out)                      # (T_out, cout)
+            x_source = c.nsf_noise_conv(src, nw, nb, nk, ns, npad, T_out)                          # (B * T_out, cout)
             s_out = can_split(cin, cout)
             # a narrow stage whose residual pairs run fused (x in, x out, activations on load: csrc/nsf.hip, conv_pair*) needs no
             # activated copies at all
@@ -383,10 +376,7 @@ class Generator(torch.nn.Module):
                 cur = c.nsf_mean(outs)
             cin = cout
         # (the stage means need no counts: the mean of tensors that are 0 past a row's end is 0 there)
-        if batched:
-            audio = c.nsf_post_ragged(cur, P["post_w"], P["post_b"], P["post_k"], 0.01, rows(self.upp))
-        else:
-            audio = c.nsf_post(cur, P["post_w"], P["post_b"], P["post_k"], 0.01)
+        audio = c.nsf_post(cur, P["post_w"], P["post_b"], P["post_k"], 0.01, rows(self.upp))
         return audio.reshape(B, 1, -1)
 
     __call__ = forward
@@ -519,13 +509,13 @@ class Enhancer:
         sr_e, hop_e = self.enhancer_sample_rate, self.enhancer_hop_size
         lens = [self.batch_lengths(n, sample_rate, work_rate) for n in n_samples]
         if int(sample_rate) != int(work_rate):
-            audio = c.resample_ragged(audio, c.ragged_counts(n_samples), sample_rate, work_rate, 128)
+            audio = c.resample(audio, sample_rate, work_rate, 128, n_dev=c.ragged_counts(n_samples))
         n_dst = [l[1] for l in lens]
-        f0_res = c.retime_f0_ragged(f0, c.ragged_counts(n_f0), hop_size / sample_rate, pitch_scale, pitch_scale, hop_e / sr_e,
-                                    max(n_dst), c.ragged_counts(n_dst))
+        f0_res = c.retime_f0(f0, hop_size / sample_rate, pitch_scale, pitch_scale, hop_e / sr_e, max(n_dst),
+                             n_src_dev=c.ragged_counts(n_f0), n_dst_dev=c.ragged_counts(n_dst))
         enhanced, _ = self.enhancer(audio, f0_res, rand_ini=rand_ini, n_samples=[l[0] for l in lens])
         if shrink != 0 and int(work_rate) != int(sr_e):
-            enhanced = c.resample_ragged(enhanced, c.ragged_counts([l[3] for l in lens]), work_rate, sr_e, 128)
+            enhanced = c.resample(enhanced, work_rate, sr_e, 128, n_dev=c.ragged_counts([l[3] for l in lens]))
         return enhanced, [l[4] for l in lens]
 
     def enhance_batch(self, audio, sample_rate, f0, hop_size, n_samples, adaptive_key=0, rand_ini=None, n_f0=None):

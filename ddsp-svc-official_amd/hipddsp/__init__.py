@@ -483,29 +483,12 @@ class Context:
     def unit2ctrl(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out, n_frames=None):
         """n_frames: the (B,) int32 device tensor of a ragged batch (`ragged_counts`); units past a row's count must be 0."""
         B, Fr, _ = units.shape
-        dev = units.device
-        units = units.contiguous().float()
-        f0 = f0_frames.reshape(B, Fr).contiguous().float()
-        ph = phase_frames.reshape(B, Fr).contiguous().float()
-        vol = volume.reshape(B, Fr).contiguous().float()
-        ctrl = torch.empty(B, Fr, n_out, device=dev, dtype=torch.float32)
-        if spk_mix_dict is not None:
-            n_mix = len(spk_mix_dict)
-            ids = (_i64 * max(n_mix, 1))(*[int(k) for k in spk_mix_dict.keys()])
-            ws = (_f32 * max(n_mix, 1))(*[float(v) for v in spk_mix_dict.values()])
-            sid, n_sid = None, 0
-        else:
-            n_mix, ids, ws = 0, None, None
-            sid = spk_id.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-            n_sid = sid.numel()
-            if n_sid not in (1, B):
-                raise ValueError(f"spk_id must hold 1 or B={B} ids, got {n_sid}")
+        ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
+        hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
         if n_frames is not None:
-            self.call("ddsp_unit2ctrl_fwd_ragged", ctypes.byref(weights), _ptr(units), _ptr(f0), _ptr(ph), _ptr(vol), _ptr(sid),
-                      n_sid, ids, ws, n_mix, B, Fr, _ptr(n_frames), _ptr(ctrl))
-            return ctrl
-        self.call("ddsp_unit2ctrl_fwd", ctypes.byref(weights), _ptr(units), _ptr(f0), _ptr(ph), _ptr(vol), _ptr(sid),
-                  n_sid, ids, ws, n_mix, B, Fr, _ptr(ctrl))
+            self.call("ddsp_unit2ctrl_fwd_ragged", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
+        else:
+            self.call("ddsp_unit2ctrl_fwd", ctypes.byref(weights), *args, _ptr(ctrl))
         return ctrl
 
     # -- ragged batches (include/ddsp_amd.h): held frames, cropped signals, the noise draw ---------
@@ -556,27 +539,15 @@ class Context:
                       d_ctrl, want_ctrl=False):
         """Back-propagates d_ctrl (B,Fr,n_out) into the tensors `grads` points at (same struct layout as `weights`)."""
         B, Fr, _ = units.shape
-        dev = units.device
-        units = units.contiguous().float()
-        f0 = f0_frames.reshape(B, Fr).contiguous().float()
-        ph = phase_frames.reshape(B, Fr).contiguous().float()
-        vol = volume.reshape(B, Fr).contiguous().float()
         d_ctrl = d_ctrl.contiguous().float()
-        ctrl = torch.empty(B, Fr, n_out, device=dev, dtype=torch.float32) if want_ctrl else None
-        if spk_mix_dict is not None:
-            n_mix = len(spk_mix_dict)
-            ids = (_i64 * max(n_mix, 1))(*[int(k) for k in spk_mix_dict.keys()])
-            ws = (_f32 * max(n_mix, 1))(*[float(v) for v in spk_mix_dict.values()])
-            sid, n_sid = None, 0
-        else:
-            n_mix, ids, ws = 0, None, None
-            sid = spk_id.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-            n_sid = sid.numel()
-        self.call("ddsp_unit2ctrl_bwd", ctypes.byref(weights), _ptr(units), _ptr(f0), _ptr(ph), _ptr(vol), _ptr(sid),
-                  n_sid, ids, ws, n_mix, B, Fr, _ptr(d_ctrl), ctypes.byref(grads), _ptr(ctrl))
+        ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32) if want_ctrl else None
+        hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
+        self.call("ddsp_unit2ctrl_bwd", ctypes.byref(weights), *args, _ptr(d_ctrl), ctypes.byref(grads), _ptr(ctrl))
         return ctrl
 
     def _u2c_inputs(self, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict):
+        """The inputs every unit2ctrl entry point shares -> (the tensors to hold until the call is queued, its arguments from
+        `units` to `Fr`); the speaker is a mix (host arrays) or spk_id (1 or B ids on the device)."""
         B, Fr, _ = units.shape
         dev = units.device
         units = units.contiguous().float()
@@ -666,100 +637,85 @@ class Context:
         its own ends, carries n_samples[b] // hop + 1 frames and is 0 after them; its padding is never read."""
         audio = audio.contiguous().float()
         B, T = audio.shape
-        if n_samples is not None:
-            if not float(hop).is_integer():
-                raise ValueError("volume_extract: a ragged batch needs an integral hop")
-            vals = check_volume_n_samples(n_samples, B, T, int(hop))
-            out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
-            if B:
-                n_dev = self.ragged_counts(vals)
-                self.call("ddsp_volume_extract_ragged", _ptr(audio), B, T, _ptr(n_dev), int(hop), _ptr(out))
+        if n_samples is not None and not float(hop).is_integer():
+            raise ValueError("volume_extract: a ragged batch needs an integral hop")
+        vals = None if n_samples is None else check_volume_n_samples(n_samples, B, T, int(hop))
+        if not float(hop).is_integer():
+            hop = float(hop)
+            out = torch.empty(B, int(T // hop) + 1, device=audio.device, dtype=torch.float32)
+            self.call("ddsp_volume_extract_frac", _ptr(audio), B, T, hop, _ptr(out))
             return out
-        if float(hop).is_integer():
-            out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
-            if B == 0:
-                return out
+        out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
+        if B and vals is not None:
+            self.call("ddsp_volume_extract_ragged", _ptr(audio), B, T, _ptr(self.ragged_counts(vals)), int(hop), _ptr(out))
+        elif B:
             self.call("ddsp_volume_extract", _ptr(audio), B, T, int(hop), _ptr(out))
-            return out
-        hop = float(hop)
-        out = torch.empty(B, int(T // hop) + 1, device=audio.device, dtype=torch.float32)
-        self.call("ddsp_volume_extract_frac", _ptr(audio), B, T, hop, _ptr(out))
         return out
 
-    def align_units(self, units, n_frames, ratio):
-        """units (B,Lu,C) -> (B,n_frames,C), row i = units[:, min(rint(fp32(ratio)*i), Lu-1)] (ddsp/vocoder.py:201-211)."""
+    def align_units(self, units, n_frames, ratio, n_units_dev=None, n_out_dev=None):
+        """units (B,Lu,C) -> (B,n_frames,C), row i = units[:, min(rint(fp32(ratio)*i), Lu-1)] (ddsp/vocoder.py:201-211).
+        `n_units_dev`, `n_out_dev` (both or neither; (B,) int32 device tensors, `ragged_counts`): a RAGGED batch - row b gathers
+        its own n_out[b] frames from its own n_units[b] unit rows and is 0 after them."""
+        if (n_units_dev is None) != (n_out_dev is None):
+            raise ValueError("align_units: a ragged batch needs both n_units_dev and n_out_dev")
         units = units.contiguous().float()
         B, Lu, C = units.shape
         out = torch.empty(B, int(n_frames), C, device=units.device, dtype=torch.float32)
         if B == 0 or int(n_frames) == 0:
             return out
-        self.call("ddsp_align_units", _ptr(units), B, Lu, C, int(n_frames), float(ratio), _ptr(out))
+        args = (_ptr(units), B, Lu, C, int(n_frames), float(ratio))
+        if n_units_dev is not None:
+            self.call("ddsp_align_units_ragged", *args, _ptr(n_units_dev), _ptr(n_out_dev), _ptr(out))
+        else:
+            self.call("ddsp_align_units", *args, _ptr(out))
         return out
 
-    def align_units_ragged(self, units, n_frames, ratio, n_units_dev, n_out_dev):
-        """`align_units` of a ragged batch: row b gathers its own n_out[b] frames from its own n_units[b] unit rows and is 0
-        after them; both counts are (B,) int32 device tensors (`ragged_counts`)."""
-        units = units.contiguous().float()
-        B, Lu, C = units.shape
-        out = torch.empty(B, int(n_frames), C, device=units.device, dtype=torch.float32)
-        if B == 0 or int(n_frames) == 0:
+    def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst, n_src_dev=None, n_dst_dev=None):
+        """f0 (n,) device track -> (n_dst,): numpy.interp(i * step_dst; knots (step_num * j) / div, values fl32(f0 * scale)),
+        end values held (enhancer.py:56-62), without leaving the device.
+        `n_src_dev`, `n_dst_dev` (both or neither; (B,) int32 device tensors, `ragged_counts`): a RAGGED batch - f0 (B, n_src) ->
+        (B, n_dst); row b has n_src_dev[b] knots and n_dst_dev[b] targets of its own, ends held at its own first and last frame,
+        0 after its targets."""
+        if (n_src_dev is None) != (n_dst_dev is None):
+            raise ValueError("retime_f0: a ragged batch needs both n_src_dev and n_dst_dev")
+        steps = (float(step_num), float(div), float(scale), float(step_dst), int(n_dst))
+        if n_src_dev is None:
+            f0 = f0.reshape(-1).contiguous().float()
+            out = torch.empty(int(n_dst), device=f0.device, dtype=torch.float32)
+            self.call("ddsp_retime_f0", _ptr(f0), f0.numel(), *steps, _ptr(out))
             return out
-        self.call("ddsp_align_units_ragged", _ptr(units), B, Lu, C, int(n_frames), float(ratio), _ptr(n_units_dev),
-                  _ptr(n_out_dev), _ptr(out))
-        return out
-
-    def retime_f0_ragged(self, f0, n_src_dev, step_num, div, scale, step_dst, n_dst, n_dst_dev):
-        """`retime_f0` of a ragged batch: f0 (B, n_src) -> (B, n_dst); row b has n_src_dev[b] knots and n_dst_dev[b] targets of
-        its own ((B,) int32 device tensors, `ragged_counts`), ends held at its own first and last frame, 0 after its targets."""
         f0 = f0.contiguous().float()
         B, n_src = f0.shape
         out = torch.empty(B, int(n_dst), device=f0.device, dtype=torch.float32)
-        self.call("ddsp_retime_f0_ragged", _ptr(f0), B, n_src, _ptr(n_src_dev), float(step_num), float(div), float(scale),
-                  float(step_dst), int(n_dst), _ptr(n_dst_dev), _ptr(out))
-        return out
-
-    def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst):
-        """f0 (n,) device track -> (n_dst,): numpy.interp(i * step_dst; knots (step_num * j) / div, values fl32(f0 * scale)),
-        end values held (enhancer.py:56-62), without leaving the device."""
-        f0 = f0.reshape(-1).contiguous().float()
-        out = torch.empty(int(n_dst), device=f0.device, dtype=torch.float32)
-        self.call("ddsp_retime_f0", _ptr(f0), f0.numel(), float(step_num), float(div), float(scale), float(step_dst), int(n_dst),
-                  _ptr(out))
+        self.call("ddsp_retime_f0_ragged", _ptr(f0), B, n_src, _ptr(n_src_dev), *steps, _ptr(n_dst_dev), _ptr(out))
         return out
 
     # -- SURVEY 8(f) rank 3: sample-rate conversion ---------------------------------------------
-    def resample(self, audio, orig_freq, new_freq, lowpass_filter_width=6):
-        """audio (B,T) or (T,) -> (B, ceil(T*new/orig)): windowed-sinc polyphase (torchaudio.transforms.Resample's algorithm)."""
+    def resample(self, audio, orig_freq, new_freq, lowpass_filter_width=6, n_dev=None):
+        """audio (B,T) or (T,) -> (B, ceil(T*new/orig)): windowed-sinc polyphase (torchaudio.transforms.Resample's algorithm).
+        `n_dev` (the (B,) int32 device tensor of the rows' own sample counts, `ragged_counts`): a RAGGED batch (B,T) - what
+        follows a row's samples is never read into arithmetic, and its outputs from ceil(n_b * new / orig) on are 0."""
         flat = audio.dim() == 1
+        if flat and n_dev is not None:
+            raise ValueError("resample: n_dev needs a (B, T) batch")
         x = (audio.reshape(1, -1) if flat else audio).contiguous().float()
         B, T = x.shape
         T_out = self.lib.ddsp_resample_length(T, int(orig_freq), int(new_freq))
         if T_out < 0:
             raise ValueError("resample: bad rates")
         out = torch.empty(B, T_out, device=x.device, dtype=torch.float32)
-        if B and T:
-            self.call("ddsp_resample", _ptr(x), B, T, int(orig_freq), int(new_freq), int(lowpass_filter_width), _ptr(out))
+        rates = (int(orig_freq), int(new_freq), int(lowpass_filter_width))
+        if B and T and n_dev is not None:
+            self.call("ddsp_resample_ragged", _ptr(x), B, T, _ptr(n_dev), *rates, _ptr(out))
+        elif B and T:
+            self.call("ddsp_resample", _ptr(x), B, T, *rates, _ptr(out))
         return out[0] if flat else out
-
-    def resample_ragged(self, audio, n_dev, orig_freq, new_freq, lowpass_filter_width=6):
-        """`resample` of a ragged batch (B,T): n_dev is the (B,) int32 device tensor of the rows' own sample counts
-        (`ragged_counts`); what follows a row's samples is never read into arithmetic, and its outputs from
-        ceil(n_b * new / orig) on are 0."""
-        x = audio.contiguous().float()
-        B, T = x.shape
-        T_out = self.lib.ddsp_resample_length(T, int(orig_freq), int(new_freq))
-        if T_out < 0:
-            raise ValueError("resample: bad rates")
-        out = torch.empty(B, T_out, device=x.device, dtype=torch.float32)
-        if B and T:
-            self.call("ddsp_resample_ragged", _ptr(x), B, T, _ptr(n_dev), int(orig_freq), int(new_freq),
-                      int(lowpass_filter_width), _ptr(out))
-        return out
 
     # -- SURVEY 8(f) rank 1: NSF-HiFiGAN post-net building blocks --------------------------------
     # Ragged batches (include/ddsp_amd.h, "Ragged batches of the post-net"): `rows=(B, n_dev, scale)` runs a call over B rows
     # flattened on the time axis, (B * T, C), row b valid for n_dev[b] * scale frames (n_dev: (B,) int32 device tensor of
-    # `ragged_counts`, or None for a rectangular batch) and written as 0 after them; rows=None is the solo entry point.
+    # `ragged_counts`, or None for a rectangular batch) and written as 0 after them; rows=None is one utterance, x (T, C), through
+    # the solo symbol - the same launches as rows=(1, None, 1).
     def conv1d(self, x, w_packed, bias, ktaps, dil, in_slope, residual=None, want_out=True, act_slope=None, w_split=None,
                x_split=False, act_split=False, rows=None):
         """x (T,Cin), w_packed (Cout, ktaps*Cin) -> y (T,Cout) = conv_same(leaky_relu(x, in_slope)) + bias (+ residual).
@@ -775,16 +731,15 @@ class Context:
         if out is None and act is None:
             raise ValueError("conv1d: nothing to return")
         flags = (CONV_X_SPLIT if x_split else 0) | (CONV_ACT_SPLIT if act_split else 0)
+        geom = (Cin, Cout, int(ktaps), int(dil), float(in_slope), _ptr(residual), _ptr(out), _ptr(act),
+                float(act_slope if act_slope is not None else 1.0), _ptr(w_split), flags)
         if rows is not None:
             B, n_dev, scale = rows
             if T % int(B):
                 raise ValueError("conv1d: x must hold B rows of equal padded length")
-            self.call("ddsp_conv1d_ragged", _ptr(x), _ptr(w_packed), _ptr(bias), int(B), T // int(B), Cin, Cout, int(ktaps), int(dil),
-                      float(in_slope), _ptr(residual), _ptr(out), _ptr(act), float(act_slope if act_slope is not None else 1.0),
-                      _ptr(w_split), flags, _ptr(n_dev), int(scale))
-            return out if act_slope is None else (out, act)
-        self.call("ddsp_conv1d", _ptr(x), _ptr(w_packed), _ptr(bias), T, Cin, Cout, int(ktaps), int(dil), float(in_slope),
-                  _ptr(residual), _ptr(out), _ptr(act), float(act_slope if act_slope is not None else 1.0), _ptr(w_split), flags)
+            self.call("ddsp_conv1d_ragged", _ptr(x), _ptr(w_packed), _ptr(bias), int(B), T // int(B), *geom, _ptr(n_dev), int(scale))
+        else:
+            self.call("ddsp_conv1d", _ptr(x), _ptr(w_packed), _ptr(bias), T, *geom)
         return out if act_slope is None else (out, act)
 
     def gemm_res_ln(self, A_split, W_split, bias, res, gamma, beta, y_split=True, a_fp32=False):
@@ -806,73 +761,70 @@ class Context:
         T, C = x.shape
         out = torch.empty(T, C, device=x.device, dtype=torch.float32) if want_out else None
         act = torch.empty(T, C, device=x.device, dtype=torch.float32) if want_act else None
+        weights = (_ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2))
+        geom = (C, int(ktaps), int(dil), float(slope), _ptr(out), _ptr(act))
         if rows is not None:
             B, n_dev, scale = rows
             if T % int(B):
                 raise ValueError("conv1d_pair: x must hold B rows of equal padded length")
-            self.call("ddsp_conv1d_pair_ragged", _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(B), T // int(B), C, int(ktaps),
-                      int(dil), float(slope), _ptr(out), _ptr(act), _ptr(n_dev), int(scale))
-            return out, act
-        self.call("ddsp_conv1d_pair", _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), T, C, int(ktaps), int(dil), float(slope),
-                  _ptr(out), _ptr(act))
+            self.call("ddsp_conv1d_pair_ragged", _ptr(x), *weights, int(B), T // int(B), *geom, _ptr(n_dev), int(scale))
+        else:
+            self.call("ddsp_conv1d_pair", _ptr(x), *weights, T, *geom)
         return out, act
 
-    def nsf_source(self, f0, rand_ini, lin_w, lin_b, upp, sr, sine_amp=0.1):
-        L = f0.numel()
-        out = torch.empty(L * int(upp), device=f0.device, dtype=torch.float32)
-        self.call("ddsp_nsf_source", _ptr(f0), _ptr(rand_ini.contiguous().float()), _ptr(lin_w), _ptr(lin_b), L, int(upp),
-                  int(sr), float(sine_amp), _ptr(out))
+    def nsf_source(self, f0, rand_ini, lin_w, lin_b, upp, sr, sine_amp=0.1, n_dev=None):
+        """f0 (L,), rand_ini (9,) -> source (L * upp,), or f0 (B, L), rand_ini (B, 9) -> (B, L * upp): one phase scan per row
+        from its own initial phases; with n_dev ((B,) int32 device tensor), f0 past a row's count is not read and its source
+        is 0 from n_dev[b] * upp on."""
+        solo = f0.dim() == 1
+        if solo and n_dev is not None:
+            raise ValueError("nsf_source: n_dev needs f0 (B, L)")
+        if not solo and tuple(rand_ini.shape) != (f0.shape[0], 9):
+            raise ValueError(f"nsf_source: rand_ini must be (B, 9) = ({f0.shape[0]}, 9), got {tuple(rand_ini.shape)}")
+        L = f0.shape[-1]
+        rand_ini = rand_ini.contiguous().float()
+        out = torch.empty(*f0.shape[:-1], L * int(upp), device=f0.device, dtype=torch.float32)
+        head = (_ptr(f0), _ptr(rand_ini), _ptr(lin_w), _ptr(lin_b))
+        tail = (L, int(upp), int(sr), float(sine_amp))
+        if solo:
+            self.call("ddsp_nsf_source", *head, *tail, _ptr(out))
+        else:
+            self.call("ddsp_nsf_source_ragged", *head, f0.shape[0], *tail, _ptr(n_dev), _ptr(out))
         return out
 
-    def nsf_source_ragged(self, f0, rand_ini, lin_w, lin_b, upp, sr, sine_amp=0.1, n_dev=None):
-        """f0 (B, L), rand_ini (B, 9) -> source (B, L * upp): one phase scan per row from its own initial phases; with n_dev,
-        f0 past a row's count is not read and its source is 0 from n_dev[b] * upp on."""
-        B, L = f0.shape
-        if tuple(rand_ini.shape) != (B, 9):
-            raise ValueError(f"nsf_source_ragged: rand_ini must be (B, 9) = ({B}, 9), got {tuple(rand_ini.shape)}")
-        out = torch.empty(B, L * int(upp), device=f0.device, dtype=torch.float32)
-        self.call("ddsp_nsf_source_ragged", _ptr(f0), _ptr(rand_ini.contiguous().float()), _ptr(lin_w), _ptr(lin_b), B, L, int(upp),
-                  int(sr), float(sine_amp), _ptr(n_dev), _ptr(out))
-        return out
-
-    def nsf_noise_conv_ragged(self, src, w, b, K, stride, pad, T_out):
-        """src (B, T_src) -> (B * T_out, C), taps row-local."""
-        B, T_src = src.shape
+    def nsf_noise_conv(self, src, w, b, K, stride, pad, T_out):
+        """src (T_src,) -> (T_out, C), or src (B, T_src) -> (B * T_out, C) with the taps row-local."""
+        B, T_src = (1, src.numel()) if src.dim() == 1 else src.shape
         C = w.shape[0]
         out = torch.empty(B * int(T_out), C, device=src.device, dtype=torch.float32)
-        self.call("ddsp_nsf_noise_conv_ragged", _ptr(src), B, T_src, _ptr(w), _ptr(b), C, int(K), int(stride), int(pad), int(T_out),
-                  _ptr(out))
+        geom = (_ptr(w), _ptr(b), C, int(K), int(stride), int(pad), int(T_out), _ptr(out))
+        if src.dim() == 1:
+            self.call("ddsp_nsf_noise_conv", _ptr(src), T_src, *geom)
+        else:
+            self.call("ddsp_nsf_noise_conv_ragged", _ptr(src), B, T_src, *geom)
         return out
 
-    def nsf_post_ragged(self, x, w, b, K, slope, rows):
-        """x (B * T, C) -> (B, T), 0 past each row's end (`rows` as in conv1d)."""
+    def nsf_post(self, x, w, b, K, slope, rows=None):
+        """x (T, C) -> (T,), or with `rows` (as in conv1d) x (B * T, C) -> (B, T), 0 past each row's end."""
+        C = x.shape[1]
+        if rows is None:
+            out = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+            self.call("ddsp_nsf_post", _ptr(x), _ptr(w), _ptr(b), x.shape[0], C, int(K), float(slope), _ptr(out))
+            return out
         B, n_dev, scale = rows
-        T, C = x.shape[0] // int(B), x.shape[1]
+        T = x.shape[0] // int(B)
         out = torch.empty(int(B), T, device=x.device, dtype=torch.float32)
         self.call("ddsp_nsf_post_ragged", _ptr(x), _ptr(w), _ptr(b), int(B), T, C, int(K), float(slope), _ptr(out), _ptr(n_dev),
                   int(scale))
         return out
 
-    def stft_frames_ragged(self, audio, n_dev, n_fft, hop, L):
-        """audio (B, T) with n_dev[b] samples per row -> frames (B, L, n_fft) padded per row as `STFT.get_mel` pads (reflect or
-        zeros, chosen per row); frames past a row's own count are 0."""
+    def stft_frames(self, audio, n_dev, n_fft, hop, L):
+        """audio (B, T) with n_dev[b] samples per row (None: every row whole) -> frames (B, L, n_fft) padded per row as
+        `STFT.get_mel` pads (reflect or zeros, chosen per row); frames past a row's own count are 0."""
         audio = audio.contiguous().float()
         B, T = audio.shape
         out = torch.empty(B, int(L), int(n_fft), device=audio.device, dtype=torch.float32)
         self.call("ddsp_stft_frames_ragged", _ptr(audio), B, T, _ptr(n_dev), int(n_fft), int(hop), int(L), _ptr(out))
-        return out
-
-    def nsf_noise_conv(self, src, w, b, K, stride, pad, T_out):
-        C = w.shape[0]
-        out = torch.empty(int(T_out), C, device=src.device, dtype=torch.float32)
-        self.call("ddsp_nsf_noise_conv", _ptr(src), src.numel(), _ptr(w), _ptr(b), C, int(K), int(stride), int(pad),
-                  int(T_out), _ptr(out))
-        return out
-
-    def nsf_post(self, x, w, b, K, slope):
-        T, C = x.shape
-        out = torch.empty(T, device=x.device, dtype=torch.float32)
-        self.call("ddsp_nsf_post", _ptr(x), _ptr(w), _ptr(b), T, C, int(K), float(slope), _ptr(out))
         return out
 
     def nsf_mean(self, terms, want_out=True, act_slope=None, act_split=False):
@@ -938,21 +890,19 @@ class Context:
         self.call("ddsp_performer_attention", _ptr(q), _ptr(k), _ptr(v), _ptr(proj), int(B), int(Fr), _ptr(out), int(math))
         return out
 
-    def softmax_attention(self, q, k, v, B, L, heads, math=MATH_SPLIT_BF16):
-        """q, k, v (B*L, heads*64) -> softmax(q k^T / 8) v per (utterance, head), merged heads (B*L, heads*64)."""
-        out = torch.empty(B * L, heads * 64, device=q.device, dtype=torch.float32)
-        self.call("ddsp_softmax_attention", _ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math))
-        return out
-
-    def softmax_attention_ragged(self, q, k, v, B, L, heads, n_keys_dev, math=MATH_SPLIT_BF16, out=None):
-        """`softmax_attention` in which utterance b attends over its first n_keys[b] rows only ((B,) int32 device tensor);
+    def softmax_attention(self, q, k, v, B, L, heads, math=MATH_SPLIT_BF16, n_keys_dev=None, out=None):
+        """q, k, v (B*L, heads*64) -> softmax(q k^T / 8) v per (utterance, head), merged heads (B*L, heads*64), written into
+        `out` when given.  `n_keys_dev` ((B,) int32 device tensor): utterance b attends over its first n_keys[b] rows only, and
         only those rows of `out` (given, or new and uninitialised) are written."""
         if out is None:
             out = torch.empty(B * L, heads * 64, device=q.device, dtype=torch.float32)
         elif out.dtype != torch.float32 or tuple(out.shape) != (B * L, heads * 64):
-            raise ValueError("softmax_attention_ragged: `out` must be fp32 (B*L, heads*64)")
-        self.call("ddsp_softmax_attention_ragged", _ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math),
-                  _ptr(n_keys_dev))
+            raise ValueError("softmax_attention: `out` must be fp32 (B*L, heads*64)")
+        args = (_ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math))
+        if n_keys_dev is not None:
+            self.call("ddsp_softmax_attention_ragged", *args, _ptr(n_keys_dev))
+        else:
+            self.call("ddsp_softmax_attention", *args)
         return out
 
     # -- units encoder -------------------------------------------------------------------------
@@ -1006,13 +956,11 @@ class Context:
                 counts_dev = self.ragged_counts(table)
             elif counts_dev.dtype != torch.int32 or counts_dev.numel() != 2 * B + 1 or not counts_dev.is_contiguous():
                 raise ValueError("crepe_activations: counts_dev must be the (2B + 1,) int32 upload of crepe_ragged_table")
-            out = torch.empty(B, Fr, 360, device=x.device, dtype=torch.float32)
-            if B:
-                self.call("ddsp_crepe_activations_ragged", ctypes.byref(weights), _ptr(x), int(B), int(T), _ptr(counts_dev),
-                          _ptr(counts_dev) + 4 * B, int(table[-1]), int(hop), _ptr(out))
-            return out
         out = torch.empty(B, Fr, 360, device=x.device, dtype=torch.float32)
-        if B:
+        if B and n_samples is not None:
+            self.call("ddsp_crepe_activations_ragged", ctypes.byref(weights), _ptr(x), int(B), int(T), _ptr(counts_dev),
+                      _ptr(counts_dev) + 4 * B, int(table[-1]), int(hop), _ptr(out))
+        elif B:
             self.call("ddsp_crepe_activations", ctypes.byref(weights), _ptr(x), int(B), int(T), int(hop), _ptr(out))
         return out
 
@@ -1033,24 +981,21 @@ class Context:
                 raise ValueError("crepe_decode: seed_dev is not available with n_frames (a ragged batch)")
             vals = check_n_frames(n_frames, B, Fr)
             n_dev = self._counts_dev(counts_dev, B) if counts_dev is not None else self.ragged_counts(vals)
-            f0 = torch.empty(B, Fr, device=p.device, dtype=torch.float32)
-            pd = torch.empty_like(f0)
-            bins = torch.empty(B, Fr, device=p.device, dtype=torch.int32) if want_bins else None
-            if B and Fr:
-                self.call("ddsp_crepe_decode_ragged", _ptr(p), int(B), int(Fr), _ptr(n_dev), float(fmin), float(fmax),
-                          int(segment), int(dither_seed) & ((1 << 64) - 1), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
-            return (f0, pd, bins) if want_bins else (f0, pd)
         f0 = torch.empty(B, Fr, device=p.device, dtype=torch.float32)
         pd = torch.empty_like(f0)
         bins = torch.empty(B, Fr, device=p.device, dtype=torch.int32) if want_bins else None
         if seed_dev is not None and (seed_dev.dtype != torch.int64 or seed_dev.numel() != 1 or seed_dev.device != p.device):
             raise ValueError("crepe_decode: seed_dev must be a (1,) int64 tensor on the device of probs")
-        if B and Fr and seed_dev is not None:
+        seed = int(dither_seed) & ((1 << 64) - 1)
+        if B and Fr and n_frames is not None:
+            self.call("ddsp_crepe_decode_ragged", _ptr(p), int(B), int(Fr), _ptr(n_dev), float(fmin), float(fmax), int(segment),
+                      seed, 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
+        elif B and Fr and seed_dev is not None:
             self.call("ddsp_crepe_decode_dseed", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
                       _ptr(seed_dev), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
         elif B and Fr:
             self.call("ddsp_crepe_decode", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
-                      int(dither_seed) & ((1 << 64) - 1), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
+                      seed, 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
         return (f0, pd, bins) if want_bins else (f0, pd)
 
     def f0_postfilter(self, f0, pd, sr, hop, n_frames, start_frame=0, threshold=0.05, uv_interp=False, f0_min=65.0,
@@ -1082,15 +1027,14 @@ class Context:
                 nc, no = (self._counts_dev(c, B) for c in counts_dev)
             else:
                 nc, no = self.ragged_counts(vals[0] + vals[1]).reshape(2, B)
-            out = torch.empty(B, int(n_frames), device=f0.device, dtype=torch.float32)
-            if B:
-                self.call("ddsp_f0_postfilter_ragged", _ptr(f0), _ptr(pd), int(B), int(Fr), _ptr(nc), int(sr), float(hop),
-                          int(n_frames), _ptr(no), float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
-            return out
         out = torch.empty(B, int(n_frames), device=f0.device, dtype=torch.float32)
-        if B:
+        tail = (float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
+        if B and n_crepe is not None:
+            self.call("ddsp_f0_postfilter_ragged", _ptr(f0), _ptr(pd), int(B), int(Fr), _ptr(nc), int(sr), float(hop),
+                      int(n_frames), _ptr(no), *tail)
+        elif B:
             self.call("ddsp_f0_postfilter", _ptr(f0), _ptr(pd), int(B), int(Fr), int(sr), float(hop), int(n_frames),
-                      int(start_frame), float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
+                      int(start_frame), *tail)
         return out
 
     # -- a10 -----------------------------------------------------------------------------------

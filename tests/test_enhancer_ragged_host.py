@@ -34,8 +34,13 @@ def test_new_symbols_are_exported_declared_and_bound(lib_path):
         decl = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
         assert decl, f"{name} is not declared in include/ddsp_amd.h"
         assert len(decl.group(1).split(",")) == len(hipddsp.SIGNATURES[name][1]), name
-    for m in ("nsf_source_ragged", "nsf_noise_conv_ragged", "nsf_post_ragged", "stft_frames_ragged", "retime_f0_ragged"):
+    # one binding method per operation: the ragged form is an argument of the un-suffixed method
+    for m, names in (("nsf_source", ["n_dev"]), ("nsf_post", ["rows"]), ("retime_f0", ["n_src_dev", "n_dst_dev"])):
+        for n in names:
+            assert inspect.signature(getattr(hipddsp.Context, m)).parameters[n].default is None, (m, n)
+    for m in ("nsf_noise_conv", "stft_frames"):
         assert hasattr(hipddsp.Context, m), m
+    assert not [a for a in dir(hipddsp.Context) if a.endswith("_ragged")]
     for m in ("conv1d", "conv1d_pair"):
         assert inspect.signature(getattr(hipddsp.Context, m)).parameters["rows"].default is None
 

@@ -212,7 +212,7 @@ def test_extract_is_the_chain_of_the_ragged_calls(ctx, dev, tiny):
     n16 = [int(lib.ddsp_resample_length(n, 44100, 16000)) for n in counts]
     n_crepe = [hipddsp.crepe_frames(n) for n in n16]
     xd = _padded(x, counts, "nan").to(dev)
-    x16 = ctx.resample_ragged(xd, ctx.ragged_counts(counts), 44100, 16000, lowpass_filter_width=128)
+    x16 = ctx.resample(xd, 44100, 16000, lowpass_filter_width=128, n_dev=ctx.ragged_counts(counts))
     probs = tiny.activations(x16, n_samples=n16)
     f0, pd = ctx.crepe_decode(probs, 65, 800, segment=512, dither=False, n_frames=n_crepe)
     want = ctx.f0_postfilter(f0, pd, 44100, 512, max(n_out), 0, 0.05, True, 65, n_crepe=n_crepe, n_out=n_out)

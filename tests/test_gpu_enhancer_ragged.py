@@ -161,8 +161,8 @@ def test_source_module_per_row(ctx, dev):
         f = 150.0 + 500.0 * torch.rand(1, L, generator=g)
         f0[b, :L] = f[0]
         want.append(OE.sine_source(sd, f, upp, 44100, ri[b:b + 1])[0, :, 0])
-    got = ctx.nsf_source_ragged(f0.to(dev), ri.to(dev), sd["m_source.l_linear.weight"].reshape(-1).to(dev),
-                                sd["m_source.l_linear.bias"].to(dev), upp, 44100, 0.1, ctx.ragged_counts(n)).cpu()
+    got = ctx.nsf_source(f0.to(dev), ri.to(dev), sd["m_source.l_linear.weight"].reshape(-1).to(dev),
+                         sd["m_source.l_linear.bias"].to(dev), upp, 44100, 0.1, ctx.ragged_counts(n)).cpu()
     assert got.shape == (3, 40 * upp)
     for b, L in enumerate(n):
         err = float((got[b, :L * upp] - want[b]).abs().max())
@@ -281,8 +281,8 @@ def test_retime_f0_ragged_against_numpy(ctx, dev):
         f0 = np.full((4, max(ns)), np.nan, dtype=np.float32)
         for b, n in enumerate(ns):
             f0[b, :n] = rng.uniform(60, 900, n).astype(np.float32)
-        got = ctx.retime_f0_ragged(torch.from_numpy(f0).to(dev), ctx.ragged_counts(ns), hop / sr, factor, factor, hop_e / sr_e,
-                                   max(nd), ctx.ragged_counts(nd)).cpu().numpy()
+        got = ctx.retime_f0(torch.from_numpy(f0).to(dev), hop / sr, factor, factor, hop_e / sr_e, max(nd),
+                            n_src_dev=ctx.ragged_counts(ns), n_dst_dev=ctx.ragged_counts(nd)).cpu().numpy()
         assert got.shape == (4, max(nd))
         for b, (n, m) in enumerate(zip(ns, nd)):
             vals = f0[b, :n].copy()

@@ -171,8 +171,8 @@ def test_softmax_attention_ragged_against_fp64(ctx, dev, B, H, math):
         bad[b, n:] = True
     poison = lambda t: t.reshape(B, L, -1).masked_fill(bad, float("nan")).reshape(B * L, -1).to(dev)  # noqa: E731
     out = torch.full((B * L, H * 64), 7.0, device=dev)
-    ret = ctx.softmax_attention_ragged(poison(q), poison(k), poison(v), B, L, H, ctx.ragged_counts(keys), out=out,
-                                       math=hipddsp.MATH_FP32 if math == "fp32" else hipddsp.MATH_SPLIT_BF16)
+    ret = ctx.softmax_attention(poison(q), poison(k), poison(v), B, L, H, n_keys_dev=ctx.ragged_counts(keys), out=out,
+                                math=hipddsp.MATH_FP32 if math == "fp32" else hipddsp.MATH_SPLIT_BF16)
     torch.cuda.synchronize()
     assert ret.data_ptr() == out.data_ptr()
     out = out.cpu().reshape(B, L, H * 64)

@@ -25,8 +25,11 @@ def test_new_symbols_are_exported_and_bound(lib_path):
     assert hipddsp.ABI_VERSION == 7 and lib.ddsp_abi_version() == 7
     for m in ("hubert_units", "hubert_encode"):
         assert "n_dev" in inspect.signature(getattr(hipddsp.Context, m)).parameters
-    for m in ("softmax_attention_ragged", "resample_ragged", "align_units_ragged"):
-        assert hasattr(hipddsp.Context, m)
+    # one binding method per operation: the ragged form is an argument of the un-suffixed method
+    for m, names in (("softmax_attention", ["n_keys_dev"]), ("resample", ["n_dev"]), ("align_units", ["n_units_dev", "n_out_dev"])):
+        for n in names:
+            assert inspect.signature(getattr(hipddsp.Context, m)).parameters[n].default is None, (m, n)
+    assert not [a for a in dir(hipddsp.Context) if a.endswith("_ragged")]
 
 
 def _bad_counts():
