@@ -1,15 +1,23 @@
 // a14-a15: caller-side glue of the real-time and offline paths, kept on the device so a stream never leaves HBM:
 // SOLA splice (gui.py:405-430, windows gui.py:349-351) and the volume gate (main.py:111-116,159 / gui.py:108-112,127).
+// The window push, the splice and the phase-vocoder cross-fade also come for S streams of one geometry in one call
+// (ddsp_*_batch, realtime.StreamBank): the same kernels with the stream as a grid dimension, of which the solo calls are the
+// one-row launch, so a row of a batched call equals the solo call on that row bit for bit.
 #include "common.h"
 
 #include <algorithm>
 
 namespace {
 
-// score[l] = sum_i x[l+i]*buf[i] / sqrt(sum_i x[l+i]^2 + 1e-8),  l = 0..search   (one workgroup per lag)
-__global__ void __launch_bounds__(256) sola_score_kernel(const float* __restrict__ x, const float* __restrict__ buf,
-                                                         int xfade, float* __restrict__ score) {
+// score[l] = sum_i x[l+i]*buf[i] / sqrt(sum_i x[l+i]^2 + 1e-8),  l = 0..search   (one workgroup per lag and stream)
+// blockIdx.y is the stream of a batched call: row s of x (stride x_ld), of buf (stride xfade) and of score (stride score_ld).
+// A row's arithmetic does not depend on the grid's second dimension: the solo call is the one-row launch.
+__global__ void __launch_bounds__(256) sola_score_kernel(const float* __restrict__ x, int64_t x_ld, const float* __restrict__ buf,
+                                                         int xfade, float* __restrict__ score, int score_ld) {
     const int l = blockIdx.x;
+    x += blockIdx.y * x_ld;
+    buf += (int64_t)blockIdx.y * xfade;
+    score += (int64_t)blockIdx.y * score_ld;
     float num = 0.f, den = 0.f;
     for (int i = threadIdx.x; i < xfade; i += 256) {
         const float v = x[l + i];
@@ -33,10 +41,16 @@ __global__ void __launch_bounds__(256) sola_score_kernel(const float* __restrict
 }
 
 // argmax (first maximum, like torch.argmax), then cross-fade the head with the kept tail and emit the block
-__global__ void __launch_bounds__(256) sola_splice_kernel(const float* __restrict__ x, const float* __restrict__ score,
-                                                          int search, int block, int xfade,
+// (one workgroup per stream: blockIdx.x picks the row of x, score, sola_buf, emitted and shift_out)
+__global__ void __launch_bounds__(256) sola_splice_kernel(const float* __restrict__ x, int64_t x_ld, const float* __restrict__ score,
+                                                          int score_ld, int search, int block, int xfade,
                                                           float* __restrict__ sola_buf, float* __restrict__ emitted,
                                                           int* __restrict__ shift_out) {
+    x += blockIdx.x * x_ld;
+    score += (int64_t)blockIdx.x * score_ld;
+    sola_buf += (int64_t)blockIdx.x * xfade;
+    emitted += (int64_t)blockIdx.x * block;
+    shift_out += blockIdx.x;
     __shared__ float bv[256];
     __shared__ int bi[256];
     float best = -3.0e38f;
@@ -123,6 +137,12 @@ __global__ void __launch_bounds__(256) pv_spectrum_kernel(const float* __restric
     const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int F = n / 2 + 1;
     if (f >= F) return;
+    // blockIdx.y: the row of a batched call (a, b (S, n); the three spectra (S, 3, F))
+    a += (int64_t)blockIdx.y * n;
+    b += (int64_t)blockIdx.y * n;
+    amp += (int64_t)blockIdx.y * 3 * F;
+    phia += (int64_t)blockIdx.y * 3 * F;
+    wf += (int64_t)blockIdx.y * 3 * F;
     double ra = 0, ia = 0, rb = 0, ib = 0;
     for (int t = lane; t < n; t += 64) {
         const int r = (int)(((int64_t)f * t) % n);
@@ -163,6 +183,12 @@ __global__ void __launch_bounds__(256) pv_synth_kernel(const float* __restrict__
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= n) return;
     const int F = n / 2 + 1;
+    a += (int64_t)blockIdx.y * n;   // the row of a batched call; the fade windows are shared
+    b += (int64_t)blockIdx.y * n;
+    out += (int64_t)blockIdx.y * n;
+    amp += (int64_t)blockIdx.y * 3 * F;
+    phia += (int64_t)blockIdx.y * 3 * F;
+    wf += (int64_t)blockIdx.y * 3 * F;
     const float tt = __fdiv_rn((float)t, (float)n);
     float s = 0.f;
     for (int f = lane; f < F; f += 64) s += __fmul_rn(amp[f], cosf(__fadd_rn(__fmul_rn(wf[f], tt), phia[f])));
@@ -175,32 +201,74 @@ __global__ void __launch_bounds__(256) pv_synth_kernel(const float* __restrict__
 }
 
 // ---- sliding input window (gui.py:373-374) ----------------------------------------------------------------------
-// dst[i] = a[i] for i < na, then b[i - na] for the next nb elements (nb may be 0); dst overlaps neither source
-__global__ void __launch_bounds__(256) concat_copy_kernel(const float* __restrict__ a, int64_t na, const float* __restrict__ b,
-                                                          int64_t nb, float* __restrict__ dst) {
+// dst[i] = a[i] for i < na, then b[i - na] for the next nb elements (nb may be 0); dst overlaps neither source.
+// blockIdx.y: the row of a batched call, at row strides a_ld, nb and d_ld
+__global__ void __launch_bounds__(256) concat_copy_kernel(const float* __restrict__ a, int64_t a_ld, int64_t na,
+                                                          const float* __restrict__ b, int64_t nb, float* __restrict__ dst,
+                                                          int64_t d_ld) {
+    a += blockIdx.y * a_ld;
+    if (nb) b += blockIdx.y * nb;
+    dst += blockIdx.y * d_ld;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < na + nb; i += (int64_t)gridDim.x * 256)
         dst[i] = i < na ? a[i] : b[i - na];
 }
 
 }  // namespace
 
+// S rows of the phase-vocoder cross-fade: the two launches of the solo call with the row as the grid's second dimension
+static int phase_vocoder_rows(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
+                              const float* fade_in, int S, int n, float* out) {
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    const int F = n / 2 + 1;
+    const size_t bytes = (size_t)S * 3 * F * sizeof(float);
+    int rc = ddsp_scratch_reserve_bytes(ctx, bytes + 4096);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    float* spec = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, bytes, (void**)&spec))) return rc;
+    ddsp_prof_begin(ctx, st, PF_SOLA);
+    hipLaunchKernelGGL(pv_spectrum_kernel, dim3((F + 3) / 4, S), dim3(256), 0, st, a, b, n, spec, spec + F, spec + 2 * F);
+    hipLaunchKernelGGL(pv_synth_kernel, dim3((n + 3) / 4, S), dim3(256), 0, st, a, b, fade_out, fade_in, n, spec, spec + F,
+                       spec + 2 * F, out);
+    ddsp_prof_end(ctx, st, 10.0 * S * n * (double)F, 4.0 * 5 * S * n);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
 extern "C" int ddsp_phase_vocoder(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
                                   const float* fade_in, int n, float* out) {
     DDSP_REQUIRE(ctx, ctx && a && b && fade_out && fade_in && out, "ddsp_phase_vocoder: null argument");
     DDSP_REQUIRE(ctx, n >= 2 && n <= (1 << 16), "ddsp_phase_vocoder: bad length");
+    return phase_vocoder_rows(ctx, stream, a, b, fade_out, fade_in, 1, n, out);
+}
+
+extern "C" int ddsp_phase_vocoder_batch(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
+                                        const float* fade_in, int S, int n, float* out) {
+    DDSP_REQUIRE(ctx, ctx && a && b && fade_out && fade_in && out, "ddsp_phase_vocoder_batch: null argument");
+    DDSP_REQUIRE(ctx, n >= 2 && n <= (1 << 16) && S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_phase_vocoder_batch: bad length or row count");
+    return phase_vocoder_rows(ctx, stream, a, b, fade_out, fade_in, S, n, out);
+}
+
+// S rows of the splice: the two launches of the solo call, the stream as a grid dimension.  Each row has its own scores,
+// arg-max, buffer and tail hand-over; no workgroup reads another row.
+static int sola_rows(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade, int search,
+                     int delay, float* sola_buffer, float* emitted, int* shift) {
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
-    const int F = n / 2 + 1;
-    int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)3 * F * sizeof(float) + 4096);
+    const size_t bytes = (size_t)S * (search + 1) * sizeof(float);
+    int rc = ddsp_scratch_reserve_bytes(ctx, bytes + 4096);
     if (rc) return rc;
     ddsp_scratch_reset(ctx);
-    float* spec = nullptr;
-    if ((rc = ddsp_scratch_get(ctx, (size_t)3 * F * sizeof(float), (void**)&spec))) return rc;
+    float* score = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, bytes, (void**)&score))) return rc;
+    // temp_wav = audio[-block-xfade-search-delay : -delay]
+    const float* x = audio + (n_audio - block - xfade - search - delay);
     ddsp_prof_begin(ctx, st, PF_SOLA);
-    hipLaunchKernelGGL(pv_spectrum_kernel, dim3((F + 3) / 4), dim3(256), 0, st, a, b, n, spec, spec + F, spec + 2 * F);
-    hipLaunchKernelGGL(pv_synth_kernel, dim3((n + 3) / 4), dim3(256), 0, st, a, b, fade_out, fade_in, n, spec, spec + F,
-                       spec + 2 * F, out);
-    ddsp_prof_end(ctx, st, 10.0 * n * (double)F, 4.0 * 5 * n);
+    hipLaunchKernelGGL(sola_score_kernel, dim3(search + 1, S), dim3(256), 0, st, x, n_audio, sola_buffer, xfade, score, search + 1);
+    hipLaunchKernelGGL(sola_splice_kernel, dim3(S), dim3(256), 0, st, x, n_audio, score, search + 1, search, block, xfade,
+                       sola_buffer, emitted, shift);
+    ddsp_prof_end(ctx, st, 4.0 * S * (search + 1) * xfade, 4.0 * S * ((double)block * 2 + xfade * 3 + search));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
@@ -210,22 +278,17 @@ extern "C" int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int64_
     DDSP_REQUIRE(ctx, ctx && audio && sola_buffer && emitted && shift, "ddsp_sola: null argument");
     DDSP_REQUIRE(ctx, block >= xfade && xfade >= 1 && search >= 0 && delay >= 1, "ddsp_sola: bad sizes");
     DDSP_REQUIRE(ctx, n_audio >= (int64_t)block + xfade + search + delay, "ddsp_sola: window shorter than block+xfade+search+delay");
-    hipStream_t st = (hipStream_t)stream;
-    DDSP_ENTER_DEVICE(ctx);
-    int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)(search + 1) * sizeof(float) + 4096);
-    if (rc) return rc;
-    ddsp_scratch_reset(ctx);
-    float* score = nullptr;
-    if ((rc = ddsp_scratch_get(ctx, (size_t)(search + 1) * sizeof(float), (void**)&score))) return rc;
-    // temp_wav = audio[-block-xfade-search-delay : -delay]
-    const float* x = audio + (n_audio - block - xfade - search - delay);
-    ddsp_prof_begin(ctx, st, PF_SOLA);
-    hipLaunchKernelGGL(sola_score_kernel, dim3(search + 1), dim3(256), 0, st, x, sola_buffer, xfade, score);
-    hipLaunchKernelGGL(sola_splice_kernel, dim3(1), dim3(256), 0, st, x, score, search, block, xfade, sola_buffer,
-                       emitted, shift);
-    ddsp_prof_end(ctx, st, 4.0 * (search + 1) * xfade, 4.0 * ((double)block * 2 + xfade * 3 + search));
-    DDSP_LAUNCH_CHECK(ctx);
-    return DDSP_OK;
+    return sola_rows(ctx, stream, audio, 1, n_audio, block, xfade, search, delay, sola_buffer, emitted, shift);
+}
+
+extern "C" int ddsp_sola_batch(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade,
+                               int search, int delay, float* sola_buffer, float* emitted, int* shift) {
+    DDSP_REQUIRE(ctx, ctx && audio && sola_buffer && emitted && shift, "ddsp_sola_batch: null argument");
+    DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_sola_batch: 1 <= S <= 4096");
+    DDSP_REQUIRE(ctx, block >= xfade && xfade >= 1 && search >= 0 && search < 65535 && delay >= 1, "ddsp_sola_batch: bad sizes");
+    DDSP_REQUIRE(ctx, n_audio >= (int64_t)block + xfade + search + delay && n_audio < ((int64_t)1 << 31),
+                 "ddsp_sola_batch: rows shorter than block+xfade+search+delay");
+    return sola_rows(ctx, stream, audio, S, n_audio, block, xfade, search, delay, sola_buffer, emitted, shift);
 }
 
 extern "C" int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, float threshold,
@@ -246,27 +309,44 @@ extern "C" int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, cons
     return DDSP_OK;
 }
 
+// S windows take S blocks: window[s][:] = append(window[s][block:], block_in[s]).  The shift overlaps itself, and workgroups of
+// one launch run in no order, so the kept parts go through the arena: launch 1 copies window[s][block:] out, launch 2 (stream
+// order: after every read of launch 1) writes them back to the front with the new blocks behind them.  No launch reads what it
+// writes.
+static int stream_push_rows(ddsp_ctx* ctx, void* stream, float* window, int S, int64_t n_in, const float* block_in, int64_t block) {
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    const int64_t keep = n_in - block;
+    const size_t bytes = (size_t)S * keep * sizeof(float);
+    int rc = ddsp_scratch_reserve_bytes(ctx, bytes + 4096);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    float* stage = nullptr;
+    if ((rc = ddsp_scratch_get(ctx, bytes, (void**)&stage))) return rc;
+    const unsigned g1 = (unsigned)std::min<int64_t>(ceil_div64(keep, 256), 1024), g2 = (unsigned)std::min<int64_t>(ceil_div64(n_in, 256), 1024);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(concat_copy_kernel, dim3(g1, S), dim3(256), 0, st, (const float*)window + block, n_in, keep,
+                       (const float*)nullptr, (int64_t)0, stage, keep);
+    hipLaunchKernelGGL(concat_copy_kernel, dim3(g2, S), dim3(256), 0, st, (const float*)stage, keep, keep, block_in, block, window,
+                       n_in);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * S * (double)(keep + n_in));
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
 extern "C" int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int64_t n_in, const float* block_in, int64_t block) {
     DDSP_REQUIRE(ctx, ctx && window && block_in, "ddsp_stream_push: null argument");
     DDSP_REQUIRE(ctx, block >= 1 && block < n_in && n_in < ((int64_t)1 << 31), "ddsp_stream_push: 1 <= block < n_in < 2^31");
     DDSP_REQUIRE(ctx, block_in + block <= window || block_in >= window + n_in, "ddsp_stream_push: block_in lies inside the window");
-    hipStream_t st = (hipStream_t)stream;
-    DDSP_ENTER_DEVICE(ctx);
-    // window[:] = append(window[block:], block_in).  The shift overlaps itself, and workgroups of one launch run in no
-    // order, so the kept part goes through the arena: launch 1 copies window[block:] out, launch 2 (stream order: after every
-    // read of launch 1) writes it back to the front with the new block behind it.  No launch reads what it writes.
-    const int64_t keep = n_in - block;
-    int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)keep * sizeof(float) + 4096);
-    if (rc) return rc;
-    ddsp_scratch_reset(ctx);
-    float* stage = nullptr;
-    if ((rc = ddsp_scratch_get(ctx, (size_t)keep * sizeof(float), (void**)&stage))) return rc;
-    const unsigned g1 = (unsigned)std::min<int64_t>(ceil_div64(keep, 256), 1024), g2 = (unsigned)std::min<int64_t>(ceil_div64(n_in, 256), 1024);
-    ddsp_prof_begin(ctx, st, PF_OTHER);
-    hipLaunchKernelGGL(concat_copy_kernel, dim3(g1), dim3(256), 0, st, (const float*)window + block, keep, (const float*)nullptr,
-                       (int64_t)0, stage);
-    hipLaunchKernelGGL(concat_copy_kernel, dim3(g2), dim3(256), 0, st, (const float*)stage, keep, block_in, block, window);
-    ddsp_prof_end(ctx, st, 0.0, 8.0 * (double)(keep + n_in));
-    DDSP_LAUNCH_CHECK(ctx);
-    return DDSP_OK;
+    return stream_push_rows(ctx, stream, window, 1, n_in, block_in, block);
+}
+
+extern "C" int ddsp_stream_push_batch(ddsp_ctx* ctx, void* stream, float* windows, int S, int64_t n_in, const float* blocks,
+                                      int64_t block) {
+    DDSP_REQUIRE(ctx, ctx && windows && blocks, "ddsp_stream_push_batch: null argument");
+    DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_stream_push_batch: 1 <= S <= 4096");
+    DDSP_REQUIRE(ctx, block >= 1 && block < n_in && n_in < ((int64_t)1 << 31), "ddsp_stream_push_batch: 1 <= block < n_in < 2^31");
+    DDSP_REQUIRE(ctx, blocks + S * block <= windows || blocks >= windows + S * n_in,
+                 "ddsp_stream_push_batch: blocks lie inside the windows");
+    return stream_push_rows(ctx, stream, windows, S, n_in, blocks, block);
 }

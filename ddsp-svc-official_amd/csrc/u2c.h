@@ -106,11 +106,15 @@ __global__ void __launch_bounds__(256) dwconv_kernel(const float* __restrict__ x
 
 namespace u2c {
 
-// speaker mix of a call (up to 16 table rows and their weights; n == 0: the spk_id path)
+// speaker mix of a call (up to 16 table rows and their weights; n == 0: the spk_id path).  One mix for the whole batch travels
+// by value in ids / w; a mix per batch row (ddsp_unit2ctrl_fwd_rowmix, inference) lives in two device tables of n columns,
+// ids_dev (B, n) 1-based and w_dev (B, n), and ids / w are then unused.
 struct MixArgs {
     int n;
     long long ids[16];
     float w[16];
+    const int* ids_dev = nullptr;
+    const float* w_dev = nullptr;
 };
 
 // ---- buffers of one forward pass --------------------------------------------------------------------------------

@@ -321,7 +321,17 @@ struct EpiEmbed {
         v += fmaf(lf0, w.f0_w[n], w.f0_b[n]);
         v += fmaf(ph, w.phase_w[n], w.phase_b[n]);
         v += fmaf(vol[m], w.volume_w[n], w.volume_b[n]);
-        if (mix.n > 0) {
+        if (mix.ids_dev) {   // the row's own mix from the device tables, terms in slot order
+            const int* ri = mix.ids_dev + (int64_t)(m / Fr) * mix.n;
+            const float* rw = mix.w_dev + (int64_t)(m / Fr) * mix.n;
+            for (int k = 0; k < mix.n; ++k) {
+                const int id = ri[k];
+                if (id >= 1 && id <= w.n_spk)
+                    v += rw[k] * w.spk_table[(id - 1) * D + n];
+                else
+                    __hip_atomic_store(err, DDSP_DEV_ERR_SPK_ID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        } else if (mix.n > 0) {
             for (int k = 0; k < mix.n; ++k) v += mix.w[k] * w.spk_table[(mix.ids[k] - 1) * D + n];
         } else {
             const int64_t id = spk_id[n_spk_id == 1 ? 0 : m / Fr];
@@ -360,7 +370,21 @@ struct EpiEmbed {
             v[j] += fmaf(ph, pw[j], pb[j]);
             v[j] += fmaf(vl, vw[j], vb[j]);
         }
-        if (mix.n > 0) {
+        if (mix.ids_dev) {
+            const int* ri = mix.ids_dev + (int64_t)(m / Fr) * mix.n;
+            const float* rw = mix.w_dev + (int64_t)(m / Fr) * mix.n;
+            for (int k = 0; k < mix.n; ++k) {
+                const int id = ri[k];
+                if (id >= 1 && id <= w.n_spk) {
+                    const v4 e = *(const v4*)(w.spk_table + (id - 1) * D + n);
+                    const float wk = rw[k];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] += wk * e[j];
+                } else {
+                    __hip_atomic_store(err, DDSP_DEV_ERR_SPK_ID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
+        } else if (mix.n > 0) {
             for (int k = 0; k < mix.n; ++k) {
                 const v4 e = *(const v4*)(w.spk_table + (mix.ids[k] - 1) * D + n);
 #pragma unroll
@@ -1217,12 +1241,18 @@ int check_inputs(ddsp_ctx* ctx, const ddsp_u2c_weights* wp, const float* units, 
 static int unit2ctrl_fwd_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                              const float* f0_frames, const float* phase_frames, const float* volume,
                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                             const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, float* ctrl) {
+                             const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, float* ctrl,
+                             const int32_t* mix_ids_dev = nullptr, const float* mix_w_dev = nullptr, int K = 0) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
     if (rc) return rc;
     in.n_frames = (const int*)n_frames;
+    if (mix_ids_dev) {   // a mix per row: K columns of the two device tables replace the by-value arrays
+        in.mix.n = K;
+        in.mix.ids_dev = (const int*)mix_ids_dev;
+        in.mix.w_dev = mix_w_dev;
+    }
     DDSP_REQUIRE(ctx, ctrl, "ddsp_unit2ctrl_fwd: null ctrl");
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
     if (B == 0) return DDSP_OK;
@@ -1280,6 +1310,38 @@ extern "C" int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp
     DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_unit2ctrl_fwd_ragged: null n_frames");
     return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                              n_mix, B, Fr, n_frames, ctrl);
+}
+
+// A speaker mix per batch row from device tables (include/ddsp_amd.h): the launches of ddsp_unit2ctrl_fwd, whose embedding
+// epilogue reads row m / Fr of the tables.  check_inputs sees a one-slot host mix {1: 0} (the speaker path it then needs no
+// spk_id for); unit2ctrl_fwd_any replaces it by the tables.
+static int unit2ctrl_fwd_rowmix_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                    const float* f0_frames, const float* phase_frames, const float* volume,
+                                    const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                    const int32_t* n_frames, float* ctrl) {
+    DDSP_REQUIRE(ctx, ctx && mix_ids_dev && mix_w_dev, "ddsp_unit2ctrl_fwd_rowmix: null mix table");
+    DDSP_REQUIRE(ctx, K >= 1 && K <= 16, "ddsp_unit2ctrl_fwd_rowmix: 1 <= K <= 16 mixed speakers per row");
+    const int64_t one_id = 1;
+    const float zero_w = 0.f;
+    return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, nullptr, 0, &one_id, &zero_w, 1, B, Fr,
+                             n_frames, ctrl, mix_ids_dev, mix_w_dev, K);
+}
+
+extern "C" int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                         const float* f0_frames, const float* phase_frames, const float* volume,
+                                         const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                         float* ctrl) {
+    return unit2ctrl_fwd_rowmix_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, mix_ids_dev, mix_w_dev, K, B, Fr,
+                                    nullptr, ctrl);
+}
+
+extern "C" int ddsp_unit2ctrl_fwd_rowmix_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                                const float* f0_frames, const float* phase_frames, const float* volume,
+                                                const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                                const int32_t* n_frames, float* ctrl) {
+    DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_unit2ctrl_fwd_rowmix_ragged: null n_frames");
+    return unit2ctrl_fwd_rowmix_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, mix_ids_dev, mix_w_dev, K, B, Fr,
+                                    n_frames, ctrl);
 }
 
 // ---- a training step's pair: a forward that leaves its activations in a caller-owned region, a backward that starts from them ----

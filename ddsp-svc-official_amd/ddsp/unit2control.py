@@ -220,8 +220,10 @@ class Unit2Control(nn.Module):
     def _weights_struct(self):
         return self._table.struct(self)
 
-    def forward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, n_frames=None):
+    def forward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, n_frames=None, spk_mix_rows=None):
         """(B, Fr, n_out) fused control matrix (the split views are taken by `forward`).
+        `spk_mix_rows` (ids (B, K) int32, w (B, K) fp32, device tensors): a speaker mix per row in place of `spk_id` /
+        `spk_mix_dict` (`hipddsp.check_mix_rows`; inference only, the callers check that).
         `n_frames` (a sequence of B ints or a CPU integer tensor (B,), 1 <= n_frames[b] <= Fr): a ragged batch - the first
         n_frames[b] rows of ctrl[b] are what the network gives for that row alone at its own length, whatever the padding of
         the inputs holds; the rows after them carry no meaning.  Inference only."""
@@ -239,17 +241,17 @@ class Unit2Control(nn.Module):
                                        ctx.ragged_frames(f0.reshape(B, Fr), n_dev, hold=True),
                                        ctx.ragged_frames(phase.reshape(B, Fr), n_dev, hold=False),
                                        ctx.ragged_frames(volume.reshape(B, Fr), n_dev, hold=False), spk_id, spk_mix_dict,
-                                       n_dev, hold=False)
+                                       n_dev, hold=False, spk_mix_rows=spk_mix_rows)
         ctx = hipddsp.context_for(units.device)
         w, keep = self._weights_struct()
-        return ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out)
+        return ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, mix_dev=spk_mix_rows)
 
-    def forward_ragged(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=True):
+    def forward_ragged(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=True, spk_mix_rows=None):
         """The control matrix of a ragged batch whose counts are on the device (`Context.ragged_counts`) and whose units are 0
         past every row's count.  hold: every row's last control frame is repeated over its padding - the form in which the
         DSP kernels take a ragged batch (`csrc/ragged.hip`)."""
         w, keep = self._weights_struct()
-        ctrl = ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, n_frames=n_dev)
+        ctrl = ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, n_frames=n_dev, mix_dev=spk_mix_rows)
         return ctx.ragged_frames(ctrl, n_dev, hold=True, out=ctrl) if hold else ctrl
 
     def forward_flat_keep(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, ctx=None):

@@ -15,6 +15,14 @@ Differences a caller can observe, all additive:
     row alone at its own length, and exactly 0.0 after them.  What the padding of units / f0 / volume / noise holds (zeros,
     garbage, NaN) does not matter.  Inference only: with grad mode on and a parameter that wants a gradient it raises
     NotImplementedError.  With `noise_seed=` the draw is repeatable but not the draw of the rows' solo calls.
+  * `forward(..., spk_mix_rows=(ids, w))`: a speaker mix PER ROW as device data.  `ids` (B, K) int32 (1-based) and `w`
+    (B, K) fp32, 1 <= K <= 16, both on the model's device; row b adds sum_k w[b, k] * spk_embed[ids[b, k] - 1] in slot
+    order.  A slot {id 1, weight 0} pads a shorter row, the row {id: 1.0} is a plain speaker id
+    (`hipddsp.mix_rows` builds the tables).  `spk_id` is then ignored; together with `spk_mix_dict` it raises ValueError.
+    The kernels read the tables when they run, so a captured graph follows edits to them
+    (`graphed.GraphedSynth(..., spk_mix_rows=True)`, `realtime.StreamBank`).  Works with and without `n_frames=`.
+    Inference only (NotImplementedError under grad mode).  An id outside [1, n_spk] in a device table is reported by the
+    kernel through the context's device error word (ValueError from the next library call).
 """
 import os
 
@@ -411,6 +419,19 @@ class _SynthBase(torch.nn.Module):
         ph = z(0, T, 1) if sample_rate_phase else z(0, Fr, 1)
         return sig, ph, ((sig, sig) if shared else (z(0, T), z(0, T)))
 
+    def _check_mix_rows(self, spk_mix_dict, spk_mix_rows, B):
+        """`forward(..., spk_mix_rows=(ids, w))`: refusals before anything is launched (shapes and dtypes on the host;
+        the ids of device tables are checked by the kernel that reads them, through the context's device error word)."""
+        if spk_mix_dict is not None:
+            raise ValueError("spk_mix_rows= (a mix per row, device tables) and spk_mix_dict (one host mix for the batch) are "
+                             "mutually exclusive")
+        if not (isinstance(spk_mix_rows, (tuple, list)) and len(spk_mix_rows) == 2):
+            raise ValueError("spk_mix_rows must be a pair (ids (B, K) int32, w (B, K) fp32)")
+        hipddsp.check_mix_rows(spk_mix_rows[0], spk_mix_rows[1], B, int(self.unit2ctrl.n_spk))
+        if self._training_graph():
+            raise NotImplementedError("spk_mix_rows= is inference only: the training entries take spk_id or spk_mix_dict; call "
+                                      "the model under torch.no_grad()")
+
     def _training_graph(self):
         """True when the call must be recorded for autograd (grad mode on and some parameter wants a gradient)."""
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.unit2ctrl.parameters())
@@ -551,15 +572,19 @@ class CombSub(_SynthBase):
         return signal, harmonic, noise_out
 
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
-                infer=True, noise=None, noise_seed=None, n_frames=None, **kwargs):
+                infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None, **kwargs):
         """units (B,Fr,n_unit), f0 (B,Fr,1) Hz, volume (B,Fr), spk_id (B,1)|(1,1) int64 1-based ->
-        (signal (B,T), phase_frames (B,Fr,1), (harmonic (B,T), noise (B,T))).  `n_frames`: ragged batch (module docstring)."""
+        (signal (B,T), phase_frames (B,Fr,1), (harmonic (B,T), noise (B,T))).  `n_frames`: ragged batch,
+        `spk_mix_rows`: a speaker mix per row (module docstring)."""
+        if spk_mix_rows is not None:
+            self._check_mix_rows(spk_mix_dict, spk_mix_rows, units_frames.shape[0])
         if units_frames.shape[0] == 0:
             return self._empty_result(f0_frames)
         if n_frames is not None:
             ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
                                                                 initial_phase, infer, COMB_SINC)
-            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev,
+                                                 spk_mix_rows=spk_mix_rows)
             signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0, ps["comb"], noise, noise_seed, n_dev)
             pf = ctx.ragged_frames(ps["phase_frames"], n_dev, hold=False, out=ps["phase_frames"])
             return signal, pf.unsqueeze(-1), (harmonic, noise_out)
@@ -570,7 +595,7 @@ class CombSub(_SynthBase):
             return signal, pf.unsqueeze(-1), (harmonic, noise_out)
         ctx, ps = self._front(f0_frames, initial_phase, infer, COMB_SINC)
         ctrl = self.unit2ctrl.forward_flat(units_frames, f0_frames, ps["phase_frames"], volume_frames, spk_id,
-                                           spk_mix_dict)
+                                           spk_mix_dict, spk_mix_rows=spk_mix_rows)
         signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0_frames, ps["comb"], noise, noise_seed)
         return signal, ps["phase_frames"].unsqueeze(-1), (harmonic, noise_out)
 
@@ -642,16 +667,19 @@ class Sins(_SynthBase):
         return signal, harmonic, noise_out
 
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
-                infer=True, max_upsample_dim=32, noise=None, noise_seed=None, n_frames=None):
+                infer=True, max_upsample_dim=32, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None):
         """Same contract as CombSub.forward except that the returned phase is sample-rate (B,T,1)
         (reference `ddsp/vocoder.py:423`).  `max_upsample_dim` is accepted and ignored: the bank kernel never
         materialises the (B,T,chunk) tensors the reference chunks to bound."""
+        if spk_mix_rows is not None:
+            self._check_mix_rows(spk_mix_dict, spk_mix_rows, units_frames.shape[0])
         if units_frames.shape[0] == 0:
             return self._empty_result(f0_frames, sample_rate_phase=True)
         if n_frames is not None:
             ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
                                                                 initial_phase, infer, COMB_NONE, want_phase=True)
-            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev,
+                                                 spk_mix_rows=spk_mix_rows)
             signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0, ps["phase"], noise, noise_seed, n_dev)
             ctx.ragged_crop_(n_dev, f0.shape[1], self._hop, ps["phase"])
             return signal, ps["phase"].unsqueeze(-1), (harmonic, noise_out)
@@ -662,7 +690,7 @@ class Sins(_SynthBase):
             return signal, ph.unsqueeze(-1), (harmonic, noise_out)
         ctx, ps = self._front(f0_frames, initial_phase, infer, COMB_NONE, want_phase=True)
         ctrl = self.unit2ctrl.forward_flat(units_frames, f0_frames, ps["phase_frames"], volume_frames, spk_id,
-                                           spk_mix_dict)
+                                           spk_mix_dict, spk_mix_rows=spk_mix_rows)
         signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0_frames, ps["phase"], noise, noise_seed)
         return signal, ps["phase"].unsqueeze(-1), (harmonic, noise_out)
 
@@ -709,15 +737,19 @@ class CombSubFast(_SynthBase):
         return signal
 
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
-                infer=True, noise=None, noise_seed=None, n_frames=None, **kwargs):
+                infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None, **kwargs):
         """Returns (signal, phase_frames (B,Fr,1), (signal, signal)) - the same tensor three times, like the
-        reference (`ddsp/vocoder.py:492`).  `n_frames`: ragged batch (module docstring)."""
+        reference (`ddsp/vocoder.py:492`).  `n_frames`: ragged batch,
+        `spk_mix_rows`: a speaker mix per row (module docstring)."""
+        if spk_mix_rows is not None:
+            self._check_mix_rows(spk_mix_dict, spk_mix_rows, units_frames.shape[0])
         if units_frames.shape[0] == 0:
             return self._empty_result(f0_frames, shared=True)
         if n_frames is not None:
             ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
                                                                 initial_phase, infer, COMB_SINC_GATED)
-            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev,
+                                                 spk_mix_rows=spk_mix_rows)
             signal = self.synth_from_ctrl(ctx, ctrl, ps["comb"], noise, noise_seed, n_dev)
             pf = ctx.ragged_frames(ps["phase_frames"], n_dev, hold=False, out=ps["phase_frames"])
             return signal, pf.unsqueeze(-1), (signal, signal)
@@ -727,6 +759,6 @@ class CombSubFast(_SynthBase):
             return signal, pf.unsqueeze(-1), (signal, signal)
         ctx, ps = self._front(f0_frames, initial_phase, infer, COMB_SINC_GATED)
         ctrl = self.unit2ctrl.forward_flat(units_frames, f0_frames, ps["phase_frames"], volume_frames, spk_id,
-                                           spk_mix_dict)
+                                           spk_mix_dict, spk_mix_rows=spk_mix_rows)
         signal = self.synth_from_ctrl(ctx, ctrl, ps["comb"], noise, noise_seed)
         return signal, ps["phase_frames"].unsqueeze(-1), (signal, signal)

@@ -15,11 +15,14 @@ What makes the capture safe:
 Weights are read by the captured kernels at replay time (the weight-preparation kernel is part of the graph), so
 in-place weight updates are honoured.  `spk_mix_dict` ({speaker id: weight}) is captured with the graph: its ids and
 weights become kernel arguments, so a capture is valid for that mix only (a new mix needs a new `GraphedSynth`;
-`realtime.StreamRenderer.set_speaker` does that), while `spk_id` stays a static input.  `initial_phase` is a host-side
-argument and not supported here.  Forward only.
+`realtime.StreamRenderer.set_speaker` does that), while `spk_id` stays a static input.  With `spk_mix_rows=True` (or a K) the
+speaker term is a mix per row held in two static device tables, `mix_ids` (B, K) int32 and `mix_w` (B, K) fp32
+(`forward(..., spk_mix_rows=)`): the captured kernels read them at replay time, so any row's speaker or mix changes by a write to
+its table row, without a new capture.  `initial_phase` is a host-side argument and not supported here.  Forward only.
 
 `GraphedBlock` captures the real-time block from the raw audio on (`block_chain`: window push, volume, f0 extractor, pitch
-shift, units encoder, synthesiser, volume gate) under the same rules, on one stream (a linear graph).  Three networks then
+shift, units encoder, synthesiser, volume gate) under the same rules, on one stream (a linear graph).  `GraphedBank` is the same
+chain over S windows of one geometry (`bank_chain`), with the speaker mix and the pitch factor of every row as device data.  Three networks then
 share the captured context; each has a prepared-weight slot of its own in it.  The control network's weights are prepared
 inside the graph on every replay (in-place updates are honoured, as above); the two analysis networks (HuBERT-Soft, CREPE:
 inference only) are prepared once by the warm-up runs and the captured kernels read those copies
@@ -32,7 +35,19 @@ import hipddsp
 
 
 class GraphedSynth:
-    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None):
+    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None):
+        """`spk_mix_rows`: None / False; True (K = 4 slots per row) or a K for static mix tables of the graph's own; or the
+        caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses."""
+        rows = spk_mix_rows is not None and spk_mix_rows is not False
+        if rows and spk_mix_dict is not None:
+            raise ValueError("GraphedSynth: spk_mix_rows and spk_mix_dict are mutually exclusive")
+        tables = spk_mix_rows if isinstance(spk_mix_rows, (tuple, list)) else None
+        if tables is not None:
+            K = hipddsp.check_mix_rows(tables[0], tables[1], B, int(model.unit2ctrl.n_spk))
+        else:
+            K = 0 if not rows else (4 if spk_mix_rows is True else int(spk_mix_rows))
+            if rows and not 1 <= K <= hipddsp.MAX_MIX:
+                raise ValueError(f"GraphedSynth: 1 to {hipddsp.MAX_MIX} slots per mix row, got {K}")
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("GraphedSynth needs the model on a HIP device (no CPU fallback)")
@@ -48,6 +63,14 @@ class GraphedSynth:
         self.volume = torch.zeros(B, Fr, device=dev)
         self.spk_id = torch.ones(B, 1, dtype=torch.int64, device=dev)
         self.noise = torch.rand(B, Fr * hop, device=dev)
+        # the row mixes (speaker 1 with weight 1 in slot 0, padding behind it, until the caller writes the rows)
+        if tables is not None:
+            self.mix_ids, self.mix_w = tables
+        else:
+            self.mix_ids = torch.ones(B, K, dtype=torch.int32, device=dev) if K else None
+            self.mix_w = torch.zeros(B, K, device=dev) if K else None
+            if K:
+                self.mix_w[:, 0] = 1.0
         self.ctx = hipddsp.Context(dev)
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev)
@@ -63,18 +86,23 @@ class GraphedSynth:
         self.ctx.freeze()
 
     def _run(self):
+        if self.mix_ids is not None:
+            return self.model(self.units, self.f0, self.volume, self.spk_id, spk_mix_rows=(self.mix_ids, self.mix_w),
+                              noise=self.noise)
         return self.model(self.units, self.f0, self.volume, self.spk_id, spk_mix_dict=self.spk_mix_dict, noise=self.noise)
 
     @torch.no_grad()
     def __call__(self, units, f0, volume, spk_id, noise=None):
         """Same positional inputs as `model.forward`; returns the model's result tuple (static tensors, overwritten by
-        the next call).  `noise` (B, T) in [0, 1) replaces the fresh uniform draw (parity tests)."""
+        the next call).  `noise` (B, T) in [0, 1) replaces the fresh uniform draw (parity tests).  With row mixes `spk_id` may
+        be None (the tables `mix_ids` / `mix_w` carry the speakers)."""
         if tuple(units.shape[:2]) != (self.B, self.Fr):
             raise ValueError(f"GraphedSynth captured for (B, Fr) = {(self.B, self.Fr)}, got {tuple(units.shape[:2])}")
         self.units.copy_(units)
         self.f0.copy_(f0.reshape(self.f0.shape))
         self.volume.copy_(volume.reshape(self.volume.shape))
-        self.spk_id.copy_(spk_id.expand_as(self.spk_id) if spk_id.shape[0] == 1 else spk_id.reshape(self.spk_id.shape))
+        if spk_id is not None:
+            self.spk_id.copy_(spk_id.expand_as(self.spk_id) if spk_id.shape[0] == 1 else spk_id.reshape(self.spk_id.shape))
         if noise is None:
             self.noise.uniform_()
         else:
@@ -153,6 +181,82 @@ class GraphedBlock:
         """block_in (block,) -> (sig, f0, units, volume) of the window after it took the block (static tensors)."""
         self.block_in.copy_(block_in.reshape(self.block_in.shape))
         self.spk_id.copy_(spk_id.reshape(self.spk_id.shape))
+        if noise is None:
+            self.noise.uniform_()
+        else:
+            self.noise.copy_(noise)
+        self.graph.replay()
+        return self.sig, self.f0, self.units, self.volume
+
+
+def bank_chain(ctx, model, units_encoder, f0_extractor, windows, blocks, samplerate, hop_size, silence_front, pitch, threshold_db,
+               block_size, mix_ids, mix_w, noise=None, f0_dither=True, seed_dev=None):
+    """`block_chain` over S streams of one geometry, every step one batched call on the device, nothing read back:
+    `windows` (S, n_in) take `blocks` (S, block) in place, then volume, f0 (uv_interp, silent front), the per-row pitch factor
+    `pitch` (S,) applied as f0 * pitch[:, None, None], units, the synthesiser with the row mixes `mix_ids` / `mix_w` (S, K), and
+    the gate.  -> (signal (S, Fr * block_size), f0 (S, Fr, 1) after the shift, units (S, Fr, C), volume (S, Fr))."""
+    ctx.stream_push_(windows, blocks)
+    volume = ctx.volume_extract(windows, hop_size)
+    f0 = f0_extractor.extract(windows, uv_interp=True, silence_front=silence_front, dither=f0_dither, seed_dev=seed_dev)
+    f0 = f0[:, :, None] * pitch[:, None, None]
+    units = units_encoder.encode(windows, samplerate, hop_size)
+    kw = {} if noise is None else {"noise": noise}
+    sig = model(units, f0, volume, None, spk_mix_rows=(mix_ids, mix_w), **kw)[0]
+    ctx.volume_gate_(sig, volume, threshold_db, block_size)
+    return sig, f0, units, volume
+
+
+class GraphedBank:
+    """`bank_chain` for S windows of one fixed (window length, device rate, hop) as one linear HIP graph.  `windows`, `pitch`,
+    `mix_ids` and `mix_w` are the caller's tensors (`realtime.StreamBank`'s state): the graph reads and shifts them at their
+    fixed addresses, so a write to a row between two replays is all a speaker, mix or pitch change takes.  The warm-up runs
+    leave the windows as they found them.  Static inputs: `blocks`, `noise`, `seed`; static outputs (valid until the next
+    replay): `sig`, `f0`, `units`, `volume`."""
+
+    def __init__(self, model, units_encoder, f0_extractor, windows, block, samplerate, hop_size, silence_front, pitch,
+                 threshold_db, mix_ids, mix_w, f0_dither=True, warmup=3):
+        p = next(model.parameters())
+        if not p.is_cuda or any(t.device != p.device for t in (windows, pitch, mix_ids, mix_w)):
+            raise RuntimeError("GraphedBank needs the model and the bank's state on one HIP device (no CPU fallback)")
+        self.model = model.eval()
+        self.device = dev = p.device
+        self.units_encoder, self.f0_extractor = units_encoder, f0_extractor
+        self.windows, self.pitch, self.mix_ids, self.mix_w = windows, pitch, mix_ids, mix_w
+        self.args = (samplerate, hop_size, silence_front, float(threshold_db))
+        self.f0_dither = bool(f0_dither)
+        S = windows.shape[0]
+        frames = int(windows.shape[1] // hop_size) + 1
+        self.block_size = int(model.block_size)
+        self.blocks = torch.zeros(S, int(block), device=dev)
+        self.noise = torch.rand(S, frames * self.block_size, device=dev)
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.ctx = hipddsp.Context(dev)
+        kept = windows.clone()
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
+            for _ in range(max(1, warmup)):   # arena, tap tables and the analysis networks' prepared weights: here, eagerly
+                self._run()
+        cur.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
+            self.sig, self.f0, self.units, self.volume = self._run()
+        self.ctx.freeze()
+        windows.copy_(kept)
+        self.seed.random_(0, 2 ** 62)
+
+    def _run(self):
+        samplerate, hop_size, silence_front, threshold_db = self.args
+        return bank_chain(self.ctx, self.model, self.units_encoder, self.f0_extractor, self.windows, self.blocks, samplerate,
+                          hop_size, silence_front, self.pitch, threshold_db, self.block_size, self.mix_ids, self.mix_w,
+                          self.noise, self.f0_dither, self.seed)
+
+    @torch.no_grad()
+    def __call__(self, blocks, noise=None):
+        """blocks (S, block) -> (sig, f0, units, volume) of the windows after they took the blocks (static tensors)."""
+        self.blocks.copy_(blocks.reshape(self.blocks.shape))
         if noise is None:
             self.noise.uniform_()
         else:

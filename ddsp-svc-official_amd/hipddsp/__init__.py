@@ -230,6 +230,12 @@ SIGNATURES = {
                                   _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _c.POINTER(U2CWeights), _vp]),
     "ddsp_unit2ctrl_fwd_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
                                          _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp]),
+    "ddsp_unit2ctrl_fwd_rowmix": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp]),
+    "ddsp_unit2ctrl_fwd_rowmix_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64,
+                                                _vp, _vp]),
+    "ddsp_stream_push_batch": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _i64]),
+    "ddsp_sola_batch": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "ddsp_phase_vocoder_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "ddsp_ragged_frames": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
     "ddsp_ragged_crop": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int]),
     "ddsp_ragged_noise": (_int, [_vp, _vp, _vp, _u64, _vp, _i64, _i64, _int, _vp]),
@@ -337,6 +343,50 @@ def check_volume_n_samples(n_samples, B, T, hop):
         if v <= (int(hop) + 1) // 2:
             raise ValueError(f"n_samples[{b}] = {v} samples are not longer than the reflect padding {(int(hop) + 1) // 2}")
     return vals
+
+
+MAX_MIX = 16                      # speakers in one mix (MixArgs of csrc/u2c.h; the K of a row-mix table)
+
+
+def check_mix_rows(ids, w, B, n_spk=None):
+    """The per-row speaker-mix tables of `unit2ctrl(..., mix_dev=(ids, w))`: ids (B, K) int32 (1-based) and w (B, K) fp32,
+    contiguous tensors on one device, 1 <= K <= 16; anything else raises ValueError (a host check of shapes and dtypes:
+    nothing is launched and nothing is read back, so device tables are not inspected).  Tables on the CPU (what a caller builds
+    before the upload) are also checked for ids in [1, n_spk] when `n_spk` is given.  -> K."""
+    if not (isinstance(ids, torch.Tensor) and isinstance(w, torch.Tensor)):
+        raise ValueError("a row mix is a pair of tensors (ids (B, K) int32, w (B, K) fp32)")
+    if ids.dtype != torch.int32 or w.dtype != torch.float32:
+        raise ValueError(f"a row mix holds int32 ids and fp32 weights, got {ids.dtype} and {w.dtype}")
+    if ids.dim() != 2 or tuple(w.shape) != tuple(ids.shape) or ids.shape[0] != int(B):
+        raise ValueError(f"a row mix holds two (B={int(B)}, K) tables, got {tuple(ids.shape)} and {tuple(w.shape)}")
+    K = int(ids.shape[1])
+    if not 1 <= K <= MAX_MIX:
+        raise ValueError(f"a row mix holds 1 to {MAX_MIX} speakers per row, got K = {K}")
+    if ids.device != w.device:
+        raise ValueError("the two tables of a row mix must live on one device")
+    if not (ids.is_contiguous() and w.is_contiguous()):
+        raise ValueError("the two tables of a row mix must be contiguous")
+    if n_spk is not None and not ids.is_cuda and ids.numel() and not (int(ids.min()) >= 1 and int(ids.max()) <= int(n_spk)):
+        raise ValueError(f"a row mix holds speaker ids in [1, {int(n_spk)}]")
+    return K
+
+
+def mix_rows(mixes, K, n_spk=None):
+    """[{speaker id: weight} | int id, ...] -> CPU tables (ids (B, K) int32, w (B, K) fp32) in each dict's own order, short rows
+    padded with {id 1, weight 0}; a plain id is the row {id: 1.0}.  ValueError for a row with no or more than K speakers, or an
+    id outside [1, n_spk]."""
+    ids = torch.ones(len(mixes), int(K), dtype=torch.int32)
+    w = torch.zeros(len(mixes), int(K), dtype=torch.float32)
+    for b, mix in enumerate(mixes):
+        if not isinstance(mix, dict):
+            mix = {int(mix): 1.0}
+        if not 1 <= len(mix) <= int(K):
+            raise ValueError(f"row {b}: a speaker mix holds 1 to {int(K)} ids, got {len(mix)}")
+        for k, (i, v) in enumerate(mix.items()):
+            if int(i) < 1 or (n_spk is not None and int(i) > int(n_spk)):
+                raise ValueError(f"row {b}: speaker id {i} is outside [1, {n_spk}]")
+            ids[b, k], w[b, k] = int(i), float(v)
+    return ids, w
 
 
 def _ptr(t):
@@ -480,9 +530,27 @@ class Context:
         return {"rot": rot, "phase": phase, "comb": comb, "f0_up": f0_up, "phase_frames": pf}
 
     # -- a4 ------------------------------------------------------------------------------------
-    def unit2ctrl(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out, n_frames=None):
-        """n_frames: the (B,) int32 device tensor of a ragged batch (`ragged_counts`); units past a row's count must be 0."""
+    def unit2ctrl(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out, n_frames=None,
+                  mix_dev=None):
+        """n_frames: the (B,) int32 device tensor of a ragged batch (`ragged_counts`); units past a row's count must be 0.
+        mix_dev: (ids (B, K) int32, w (B, K) fp32) device tables, a speaker mix per row (`check_mix_rows`) in place of
+        `spk_id` / `spk_mix_dict`; the kernels read them when they run (a captured graph follows edits)."""
         B, Fr, _ = units.shape
+        if mix_dev is not None:
+            if spk_mix_dict is not None:
+                raise ValueError("unit2ctrl: mix_dev= and spk_mix_dict are mutually exclusive")
+            ids, w = mix_dev
+            K = check_mix_rows(ids, w, B, weights.n_spk)
+            if not ids.is_cuda or ids.device != units.device:
+                raise ValueError("unit2ctrl: the mix_dev tables must be on the units' device")
+            ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
+            frames = [units.contiguous().float()] + [t.reshape(B, Fr).contiguous().float() for t in (f0_frames, phase_frames, volume)]
+            args = [_ptr(t) for t in frames] + [_ptr(ids), _ptr(w), K, B, Fr]
+            if n_frames is not None:
+                self.call("ddsp_unit2ctrl_fwd_rowmix_ragged", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
+            else:
+                self.call("ddsp_unit2ctrl_fwd_rowmix", ctypes.byref(weights), *args, _ptr(ctrl))
+            return ctrl
         ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
         if n_frames is not None:
@@ -1087,8 +1155,18 @@ class Context:
 
     # -- a14 -----------------------------------------------------------------------------------
     def sola(self, audio, sola_buffer, block, xfade, search, delay):
-        """audio (N,), sola_buffer (xfade,) updated in place -> (emitted (block,), shift int32 device tensor)."""
+        """audio (N,), sola_buffer (xfade,) updated in place -> (emitted (block,), shift int32 device tensor).
+        S streams: audio (S, N), sola_buffer (S, xfade) -> (emitted (S, block), shift (S,)); row s is the solo call on row s."""
         audio = audio.contiguous().float()
+        if audio.dim() == 2:
+            S = audio.shape[0]
+            if tuple(sola_buffer.shape) != (S, int(xfade)) or sola_buffer.dtype != torch.float32:
+                raise ValueError(f"sola: {S} streams need an fp32 sola_buffer (S, xfade) = {(S, int(xfade))}")
+            emitted = torch.empty(S, int(block), device=audio.device, dtype=torch.float32)
+            shift = torch.empty(S, device=audio.device, dtype=torch.int32)
+            self.call("ddsp_sola_batch", _ptr(audio), S, audio.shape[1], int(block), int(xfade), int(search), int(delay),
+                      _ptr(sola_buffer), _ptr(emitted), _ptr(shift))
+            return emitted, shift
         emitted = torch.empty(block, device=audio.device, dtype=torch.float32)
         shift = torch.empty(1, device=audio.device, dtype=torch.int32)
         self.call("ddsp_sola", _ptr(audio), audio.numel(), int(block), int(xfade), int(search), int(delay),
@@ -1098,6 +1176,12 @@ class Context:
     def stream_push_(self, window, block_in):
         """In place: window (n_in,) = append(window[block:], block_in (block,)) (gui.py:373-374); the window keeps its
         address (`ddsp_stream_push`)."""
+        if window.dtype == torch.float32 and block_in.dtype == torch.float32 and window.dim() == 2:
+            # S streams: windows (S, n_in) take blocks (S, block), every row like the solo call (`ddsp_stream_push_batch`)
+            if block_in.dim() != 2 or block_in.shape[0] != window.shape[0]:
+                raise ValueError("stream_push_: (S, n_in) windows take (S, block) blocks")
+            self.call("ddsp_stream_push_batch", _ptr(window), window.shape[0], window.shape[1], _ptr(block_in), block_in.shape[1])
+            return window
         if window.dtype != torch.float32 or block_in.dtype != torch.float32 or window.dim() != 1 or block_in.dim() != 1:
             raise ValueError("stream_push_: window and block_in must be 1-D fp32 tensors")
         self.call("ddsp_stream_push", _ptr(window), window.numel(), _ptr(block_in), block_in.numel())
@@ -1108,6 +1192,13 @@ class Context:
         oscillator term; returns (n,)."""
         a, b = a.contiguous().float(), b.contiguous().float()
         fo, fi = fade_out.contiguous().float(), fade_in.contiguous().float()
+        if a.dim() == 2:   # S streams: a, b (S, n) with the shared fade windows (n,) -> (S, n), every row like the solo call
+            S, n = a.shape
+            if tuple(b.shape) != (S, n) or not (fo.numel() == fi.numel() == n):
+                raise ValueError("phase_vocoder: a and b must be (S, n) and the fade windows (n,)")
+            out = torch.empty(S, n, device=a.device, dtype=torch.float32)
+            self.call("ddsp_phase_vocoder_batch", _ptr(a), _ptr(b), _ptr(fo), _ptr(fi), S, n, _ptr(out))
+            return out
         n = a.numel()
         if not (b.numel() == fo.numel() == fi.numel() == n):
             raise ValueError("phase_vocoder: a, b and the fade windows must have the same length")

@@ -123,7 +123,8 @@ class StreamRenderer:
     is what the callback copies out.  After a `push_audio`, `last_f0` (1, Fr, 1) (shifted), `last_units` (1, Fr, C) and
     `last_volume` (1, Fr) hold the window's analysis (under the graph: static tensors, valid until the next block).  With `enhancer_adaptive_key='auto'` the key (it decides tensor lengths) is taken before the synthesis is
     enqueued: on the host when f0 arrives as a CPU tensor, else by one scalar read-back of the f0 maximum.
-    Streams are independent: eight streams are eight renderers on eight GPUs (replicas only)."""
+    Streams are independent.  One renderer is one stream; several streams of one geometry on one GPU are a `StreamBank`
+    (one graph replay per block for all of them), and across GPUs they are replicas."""
 
     def __init__(self, model, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0, spk_id=1,
                  features=None, use_graph=True, use_phase_vocoder=False, pitch_adjust=0, spk_mix_dict=None, enhancer=None,
@@ -309,3 +310,204 @@ class StreamRenderer:
                                               silence_front=self.silence_front, rand_ini=rand_ini)
             self.last_key = key
         return self.splicer.push(self._to_device_rate(sig, rate)[0])
+
+
+def bank_sizes(samplerate, block_time, crossfade_time, buffer_num, block_size, model_sr, search_time=0.01, delay_time=0.02):
+    """The sizes a `StreamBank` works with, derived as `Splicer` and `StreamRenderer` derive them (gui.py:319-326): a dict of
+    block, xfade, search, delay, n_in (samples at the device rate), hop_size (float), frames and silence_front (seconds)."""
+    block, xfade = int(block_time * samplerate), int(crossfade_time * samplerate)
+    search, delay = int(search_time * samplerate), int(delay_time * samplerate)
+    n_in = max(block + xfade + search + 2 * delay, (1 + buffer_num) * block)
+    hop = hop_size(block_size, samplerate, model_sr)
+    return {"block": block, "xfade": xfade, "search": search, "delay": delay, "n_in": n_in, "hop_size": hop,
+            "frames": window_frames(n_in, hop), "silence_front": silence_front(block_time, buffer_num, crossfade_time)}
+
+
+class StreamBank:
+    """S real-time streams of ONE geometry (device rate, block, cross-fade, window) on one GPU, all advanced by one block per
+    call: the chain of `StreamRenderer` (its docstring, steps 1-8 without the enhancer) with every step batched over the
+    streams.  Under `push_audio` steps 1-5 of all rows are ONE linear HIP-graph replay (`graphed.GraphedBank`); then come
+    resampling to the device rate and the batched splice (`ddsp_sola_batch`: every row's own arg-max, buffer and tail).
+
+    State, all on the device: `windows` (S, n_in), `sola_buffer` (S, xfade), the speaker mix of every slot `spk_ids` (S, K)
+    int32 / `spk_w` (S, K) fp32 with K = `max_mix`, and `pitch` (S,), a factor.  The captured kernels read the three per-slot
+    tables when they run: `set_speaker`, `set_pitch` and `reset` write device rows only, and `graph_builds` stays at 1 for
+    the life of the bank.  A bank is built for one of two forms: with `units_encoder` / `f0_extractor` it takes raw audio
+    (`push_audio`); without them it takes the caller's units and f0 (`push_block`, over a `graphed.GraphedSynth` with row
+    mixes).
+
+    After a call `last_f0` (S, Fr, 1) (shifted), `last_units` (S, Fr, C), `last_volume` (S, Fr), `last_shift` (S,) int32 and
+    `last_signal` (S, N), the gated and resampled signal the splice consumed, hold that block's values (under the graph:
+    static tensors, valid until the next block).
+
+    Idle slots: there is no activity mask.  An idle slot is a slot that is fed zeros; its rows are computed like every other
+    row, and its output is zero through the volume gate.  Not in the bank: the enhancer (its 'auto' key gives rows different
+    working rates), streams of different geometry, skipping idle rows."""
+
+    def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
+                 use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
+                 f0_dither=True, crepe_ckpt=None, max_mix=4):
+        # every refusal comes before anything is allocated or launched on the device
+        self.S = int(n_streams)
+        if self.S < 1:
+            raise ValueError(f"StreamBank: n_streams must be at least 1, got {n_streams}")
+        self.max_mix = int(max_mix)
+        if not 1 <= self.max_mix <= hipddsp.MAX_MIX:
+            raise ValueError(f"StreamBank: max_mix must be in 1..{hipddsp.MAX_MIX}, got {max_mix}")
+        self.model = model.eval()
+        self.device = torch.device(device)
+        self.block_size = int(model.block_size)
+        self.model_sr = int(model.sampling_rate)
+        self.n_spk = int(model.unit2ctrl.n_spk)
+        self.samplerate = samplerate
+        self.hop = self.block_size
+        z = bank_sizes(samplerate, block_time, crossfade_time, buffer_num, self.block_size, self.model_sr)
+        self.block, self.xfade, self.search, self.delay = z["block"], z["xfade"], z["search"], z["delay"]
+        self.n_in, self.hop_size, self.frames, self.silence_front = z["n_in"], z["hop_size"], z["frames"], z["silence_front"]
+        self.threshold_db = float(threshold_db)
+        if (units_encoder is None) != (f0_extractor is None):
+            raise ValueError("StreamBank: push_audio needs both units_encoder and f0_extractor (or neither)")
+        if f0_extractor is not None and f0_extractor != "crepe":
+            if not (hasattr(f0_extractor, "extract") and hasattr(units_encoder, "encode")):
+                raise ValueError("StreamBank: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
+            if f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != self.hop_size:
+                raise ValueError(f"StreamBank: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
+                                 f"{f0_extractor.hop_size}; this bank's windows are at {samplerate} Hz with hop {self.hop_size}")
+        if self.model_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, self.model_sr, int(samplerate)) < 0:
+            raise ValueError(f"StreamBank: cannot resample {self.model_sr} Hz to {samplerate} Hz")
+        if f0_extractor == "crepe":
+            from ddsp.vocoder import F0_Extractor
+            f0_extractor = F0_Extractor("crepe", samplerate, self.hop_size, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt,
+                                        device=self.device)
+        self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
+        dev = self.device
+        self.windows = torch.zeros(self.S, self.n_in, device=dev)
+        self.sola_buffer = torch.zeros(self.S, self.xfade, device=dev)
+        self.spk_ids = torch.ones(self.S, self.max_mix, dtype=torch.int32, device=dev)   # every slot starts as speaker 1
+        self.spk_w = torch.zeros(self.S, self.max_mix, device=dev)
+        self.spk_w[:, 0] = 1.0
+        self.pitch = torch.ones(self.S, device=dev)
+        self.use_phase_vocoder = bool(use_phase_vocoder)
+        self.fade_in = torch.sin(torch.pi * torch.arange(0, 1, 1 / self.xfade, device=dev)[:self.xfade] / 2) ** 2
+        self.fade_out = 1 - self.fade_in
+        self._resampler = None
+        self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = None
+        self.use_graph = bool(use_graph)
+        self.graph = None                # the synthesis graph of `push_block` (a bank without the analysers)
+        self.bank_graph = None           # the whole-block graph of `push_audio`
+        self.graph_builds = 0
+        if self.use_graph:
+            import graphed
+            if self.f0_extractor is not None:
+                self.bank_graph = graphed.GraphedBank(
+                    self.model, self.units_encoder, self.f0_extractor, self.windows, self.block, self.samplerate, self.hop_size,
+                    self.silence_front, self.pitch, self.threshold_db, self.spk_ids, self.spk_w, f0_dither=self.f0_dither)
+            else:
+                self.graph = graphed.GraphedSynth(self.model, self.S, self.frames, spk_mix_rows=(self.spk_ids, self.spk_w))
+            self.graph_builds = 1
+
+    def _slot(self, slot):
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.S:
+            raise ValueError(f"StreamBank: slot must be an int in [0, {self.S}), got {slot!r}")
+        return slot
+
+    def set_speaker(self, slot, spk_id=None, spk_mix_dict=None):
+        """Slot `slot` sings as `spk_mix_dict` ({speaker id: weight}, 1 to `max_mix` ids) or as the plain `spk_id` (the row
+        {id: 1.0}) from the next block on: one write to that slot's rows of the two device tables, no capture."""
+        slot = self._slot(slot)
+        if (spk_id is None) == (spk_mix_dict is None):
+            raise ValueError("StreamBank.set_speaker: pass spk_id or spk_mix_dict (one of them)")
+        if spk_mix_dict is not None:
+            mix = {int(k): float(v) for k, v in spk_mix_dict.items()}
+            if not 1 <= len(mix) <= self.max_mix:
+                raise ValueError(f"StreamBank: a speaker mix holds 1 to max_mix = {self.max_mix} ids, got {len(mix)}")
+        else:
+            mix = {int(spk_id): 1.0}
+        if any(not 1 <= k <= self.n_spk for k in mix):
+            raise ValueError(f"StreamBank: speaker ids must be in [1, {self.n_spk}], got {sorted(mix)}")
+        ids, w = hipddsp.mix_rows([mix], self.max_mix, self.n_spk)
+        self.spk_ids[slot].copy_(ids[0])
+        self.spk_w[slot].copy_(w[0])
+
+    def set_pitch(self, slot, semitones):
+        """Slot `slot` is shifted by `semitones` from the next block on (f0 * 2 ** (semitones / 12)): one device write."""
+        slot = self._slot(slot)
+        self.pitch[slot:slot + 1].fill_(2 ** (float(semitones) / 12))
+
+    def reset(self, slot):
+        """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (speaker and pitch stay as set)."""
+        slot = self._slot(slot)
+        self.windows[slot].zero_()
+        self.sola_buffer[slot].zero_()
+
+    def _blocks(self, blocks):
+        if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (self.S, self.block):
+            got = tuple(blocks.shape) if isinstance(blocks, torch.Tensor) else type(blocks).__name__
+            raise ValueError(f"StreamBank: a call takes blocks of shape (S, block) = {(self.S, self.block)}, got {got}")
+        return blocks.to(self.device, torch.float32).contiguous()
+
+    def _to_device_rate(self, audio):
+        if self.model_sr == int(self.samplerate):
+            return audio
+        if self._resampler is None:
+            from resample import Resample
+            self._resampler = Resample(self.model_sr, int(self.samplerate), lowpass_filter_width=128)
+        return self._resampler(audio)
+
+    def _splice(self, sig):
+        """Steps 7-8 over the rows: (S, Fr * block_size) at the model's rate -> (S, block) samples to play."""
+        ctx = hipddsp.context_for(self.device)
+        sig = self._to_device_rate(sig).contiguous()
+        self.last_signal = sig
+        kept = self.sola_buffer.clone() if self.use_phase_vocoder else None
+        emitted, shift = ctx.sola(sig, self.sola_buffer, self.block, self.xfade, self.search, self.delay)
+        self.last_shift = shift
+        if self.use_phase_vocoder:
+            # every row's head at its own SOLA shift (the shifts stay on the device: a gather, no host sync)
+            start = sig.shape[1] - self.block - self.xfade - self.search - self.delay
+            idx = start + shift.to(torch.int64)[:, None] + torch.arange(self.xfade, device=self.device)[None, :]
+            emitted[:, :self.xfade] = ctx.phase_vocoder(kept, sig.gather(1, idx), self.fade_out, self.fade_in)
+        return emitted
+
+    @torch.no_grad()
+    def push_audio(self, blocks, noise=None):
+        """blocks (S, block) raw samples at the device rate, one block per stream -> (S, block) samples to play.  `noise`
+        (S, Fr * block_size) in [0, 1) replaces the fresh draw (parity tests)."""
+        if self.f0_extractor is None:
+            raise ValueError("StreamBank: push_audio needs units_encoder= and f0_extractor= at construction")
+        blocks = self._blocks(blocks)
+        if self.bank_graph is not None:
+            sig, f0, units, volume = self.bank_graph(blocks, noise=noise)
+        else:
+            import graphed
+            sig, f0, units, volume = graphed.bank_chain(
+                hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, self.windows, blocks,
+                self.samplerate, self.hop_size, self.silence_front, self.pitch, self.threshold_db, self.hop, self.spk_ids,
+                self.spk_w, noise, self.f0_dither)
+        self.last_f0, self.last_units, self.last_volume = f0, units, volume
+        return self._splice(sig)
+
+    @torch.no_grad()
+    def push_block(self, blocks, units, f0, noise=None):
+        """The analysis-free form: blocks (S, block), and `units` (S, Fr, C) and `f0` (S, Fr, 1) of the CURRENT windows from the
+        caller (before the pitch factor, which is applied here) -> (S, block) samples to play."""
+        blocks = self._blocks(blocks)
+        if self.f0_extractor is not None:
+            raise ValueError("StreamBank: this bank was built for push_audio; build one without units_encoder / f0_extractor "
+                             "for push_block (one capture per bank)")
+        if tuple(units.shape[:2]) != (self.S, self.frames) or tuple(f0.shape) != (self.S, self.frames, 1):
+            raise ValueError(f"StreamBank: units (S, Fr, C) and f0 (S, Fr, 1) with (S, Fr) = {(self.S, self.frames)}, got "
+                             f"{tuple(units.shape)} and {tuple(f0.shape)}")
+        ctx = hipddsp.context_for(self.device)
+        ctx.stream_push_(self.windows, blocks)
+        units = units.to(self.device)
+        f0 = f0.to(self.device, torch.float32) * self.pitch[:, None, None]
+        volume = ctx.volume_extract(self.windows, self.hop_size)
+        if self.graph is not None:
+            sig = self.graph(units, f0, volume, None, noise=noise)[0]
+        else:
+            kw = {} if noise is None else {"noise": noise}
+            sig = self.model(units, f0, volume, None, spk_mix_rows=(self.spk_ids, self.spk_w), **kw)[0]
+        ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
+        self.last_f0, self.last_units, self.last_volume = f0, units, volume
+        return self._splice(sig)

@@ -187,6 +187,24 @@ int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weight
                               float* ctrl);
 int ddsp_ragged_frames(ddsp_ctx* ctx, void* stream, const float* src, const int32_t* n_frames, int64_t B, int64_t Fr,
                        int64_t C, int hold, float* dst);
+
+/* ---- a speaker mix per row, as device data (inference only) -----------------------------------------------------------------
+ * ddsp_unit2ctrl_fwd_rowmix is ddsp_unit2ctrl_fwd whose speaker term comes from two DEVICE tables instead of spk_id or the
+ * host mix: mix_ids_dev (B, K) int32, 1-based, and mix_w_dev (B, K) fp32, 1 <= K <= 16.  Row b of the batch adds
+ *   sum_k mix_w_dev[b][k] * spk_table[mix_ids_dev[b][k] - 1]      (terms in slot order k = 0 .. K-1)
+ * in the embedding epilogue of the second prenet convolution.  A slot {id 1, weight 0} is padding (a row with fewer than K
+ * speakers); the row {id, 1.0} is a plain speaker id.  An id outside [1, n_spk] is not used as an index: the call's device
+ * error word is set (DDSP_ERR_ARG from the next call or ddsp_ctx_poll_error) and the slot adds nothing.  The tables are read
+ * when the kernels run, so a captured HIP graph follows later writes to them: nothing of the mix is a kernel argument.
+ * ddsp_unit2ctrl_fwd_rowmix_ragged adds n_frames as ddsp_unit2ctrl_fwd_ragged does.  The launches and tile choices are those of
+ * ddsp_unit2ctrl_fwd. */
+int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
+                              const float* f0_frames, const float* phase_frames, const float* volume,
+                              const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr, float* ctrl);
+int ddsp_unit2ctrl_fwd_rowmix_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
+                                     const float* f0_frames, const float* phase_frames, const float* volume,
+                                     const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                     const int32_t* n_frames, float* ctrl);
 int ddsp_ragged_crop(ddsp_ctx* ctx, void* stream, float* x0, float* x1, float* x2, const int32_t* n_frames, int64_t B,
                      int64_t Fr, int hop);
 int ddsp_ragged_noise(ddsp_ctx* ctx, void* stream, const float* noise, uint64_t noise_seed, const int32_t* n_frames,
@@ -286,11 +304,26 @@ int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int64_t n_audio, 
  * scratch arena (two launches in stream order), so the overlapping shift is exact whatever order workgroups run in. */
 int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int64_t n_in, const float* block_in, int64_t block);
 
+/* ---- the same glue for S streams of one geometry in one call (realtime.StreamBank) ------------------------------------------
+ * Every tensor gains a leading dimension S (1 <= S <= DDSP_MAX_STREAMS), contiguous rows.  The kernels are those of the solo
+ * calls with the stream as a grid dimension: per row the arithmetic and the order of every reduction are the solo call's, so row
+ * s of every output equals the solo call on row s bit for bit, and no row reads another row's audio, score or buffer.
+ *   ddsp_stream_push_batch    windows (S, n_in) take blocks (S, block) in place, staged through the arena like ddsp_stream_push.
+ *   ddsp_sola_batch           audio (S, n_audio), sola_buffer (S, xfade) in place, emitted (S, block), shift (S) int32: each row
+ *                             splices at its own arg-max (first maximum) and hands over its own tail.
+ *   ddsp_phase_vocoder_batch  a, b, out (S, n); the fade windows (n) are shared. */
+#define DDSP_MAX_STREAMS 4096
+int ddsp_stream_push_batch(ddsp_ctx* ctx, void* stream, float* windows, int S, int64_t n_in, const float* blocks, int64_t block);
+int ddsp_sola_batch(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade, int search,
+                    int delay, float* sola_buffer, float* emitted, int* shift);
+
 /* ---- a15: volume gate ------------------------------------------------------------------------ */
 /* replaces gui.py:14-31 `phase_vocoder(a, b, fade_out, fade_in)` (the optional cross-fade of gui.py:417-423; SURVEY
  * 8(f) rank 3): a = kept tail, b = head of the new block, both (n), fade windows (n), out (n).  n <= 65536. */
 int ddsp_phase_vocoder(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
                        const float* fade_in, int n, float* out);
+int ddsp_phase_vocoder_batch(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
+                             const float* fade_in, int S, int n, float* out);
 
 /* replaces main.py:111-116,159 / gui.py:108-112,127: signal (B,T) *= upsample(dilate9(volume > threshold)),
  * in place (threshold = 10^(dB/20), linear); volume (B,Fr). */

@@ -1,0 +1,150 @@
+"""Per-block time of `realtime.StreamBank.push_audio` (S streams, one graph replay) against S solo `StreamRenderer`s of a
+BASELINE checkout pushed one after the other, each with its own captured graph: what one GPU pays per block period for S
+callers, before and after the bank.
+
+Geometry: the two timings `config5` (0.2 s blocks, buffer 4, 0.04 s cross-fade) and `gui` (1.5 s blocks, buffer 2, 0.03 s
+cross-fade) on a 48 kHz device (fractional-hop volume and the 44.1 -> 48 kHz resampler are in the chain), a 44.1 kHz CombSub
+(seeded random weights), CREPE 'full' and HuBERT-Soft with the deterministic fills of tests/crepe_cases.py / tests/hubert_cases.py,
+f0 dither on.  Cases: S in {1, 4, 16}.  Per case mean / p99 over `--blocks` blocks after `--warmup`, each block timed from the
+push to the (S, block) output being ready on the device.
+
+The two legs load different builds of the library, so each runs in a fresh process of its own: `bank` imports the package of
+THIS tree, `solo` the package of `--baseline-tree`.  The legs alternate `--repeats` times in one session
+(bank, solo, bank, solo, ...), every process under its own `timeout`; a leg that ends abnormally ends the session.  Every
+repeat is written out; nothing is averaged away.
+
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> [--blocks 200] [--warmup 10] [--out profiles/rt_bank_time.json]"""
+import argparse
+import contextlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = {"config5": (0.2, 0.04, 4), "gui": (1.5, 0.03, 2)}
+STREAMS = (1, 4, 16)
+DEVICE_SR = 48000
+TONES = (147.0, 220.0, 330.0, 196.0)
+
+
+def leg(which, tree, blocks, warmup):
+    """One leg in this process: `which` = 'bank' | 'solo', the package taken from `tree`.  Prints one JSON row per case."""
+    sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import torch
+
+    import crepe_cases as CC
+    import hubert_cases as HC
+    import realtime
+    import synthetic
+    from ddsp.crepe import Crepe
+    from ddsp.hubert import HubertSoft
+    from ddsp.vocoder import Units_Encoder
+    if not torch.cuda.is_available():
+        raise SystemExit("rt_bank_time needs a HIP device")
+    dev = torch.device("cuda:0")
+    with contextlib.redirect_stdout(sys.stderr), tempfile.TemporaryDirectory() as tmp:
+        model, _ = synthetic.build_model("CombSub", seed=1, device=dev)
+        crepe = Crepe("full")
+        crepe.load_state_dict(CC.fill("full"))
+        crepe = crepe.to(dev).eval()
+        path = os.path.join(tmp, "hubert-soft.pt")
+        torch.save(HC.fill({k: tuple(v.shape) for k, v in HubertSoft().state_dict().items()}), path)
+        encoder = Units_Encoder("hubertsoft", path, device=dev)
+    for shape, (block_time, xfade_time, buffer_num) in SHAPES.items():
+        for S in STREAMS:
+            kw = dict(buffer_num=buffer_num, threshold_db=-60.0, use_graph=True, units_encoder=encoder, f0_extractor="crepe",
+                      crepe_ckpt=crepe)
+            with contextlib.redirect_stdout(sys.stderr):
+                if which == "bank":
+                    bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
+                    block, frames = bank.block, bank.frames
+                    push = bank.push_audio
+                else:
+                    solo = [realtime.StreamRenderer(model, DEVICE_SR, block_time, xfade_time, dev, spk_id=1, **kw) for _ in range(S)]
+                    block, frames = solo[0].block, solo[0].frames
+
+                    def push(blocks):
+                        return [r.push_audio(blocks[s]) for s, r in enumerate(solo)]
+            rng = np.random.Generator(np.random.PCG64(3))
+            t = np.arange(8 * block) / DEVICE_SR
+            rows = [0.2 * np.sin(2 * np.pi * TONES[s % len(TONES)] * (1 + s // len(TONES)) * t) + 0.01 * rng.standard_normal(t.size)
+                    for s in range(S)]
+            pcm = torch.from_numpy(np.stack(rows).astype(np.float32)).to(dev).reshape(S, 8, block).transpose(0, 1).contiguous()
+            times = []
+            for i in range(warmup + blocks):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                push(pcm[i % 8])
+                torch.cuda.synchronize()
+                if i >= warmup:
+                    times.append((time.perf_counter() - t0) * 1e3)
+            ts = np.array(times)
+            print(json.dumps({"leg": which, "shape": shape, "streams": S, "block_ms": block_time * 1e3, "frames": frames,
+                              "mean_ms": float(ts.mean()), "p99_ms": float(np.percentile(ts, 99)), "blocks": len(ts),
+                              "device": torch.cuda.get_device_name(0)}), flush=True)
+            del push
+            if which == "bank":
+                del bank
+            else:
+                del solo
+            torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--baseline-tree", default=None, help="a checkout of the parent commit with its library built")
+    ap.add_argument("--blocks", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--leg-timeout", type=int, default=420, help="seconds one leg's process may take")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rt_bank_time.json"))
+    ap.add_argument("--leg", default=None, choices=["bank", "solo"], help=argparse.SUPPRESS)
+    ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.leg:
+        return leg(a.leg, a.tree, a.blocks, a.warmup)
+    if not a.baseline_tree or not os.path.isdir(os.path.join(a.baseline_tree, "ddsp-svc-official_amd")):
+        raise SystemExit("rt_bank_time: --baseline-tree must be a checkout of the parent commit (with ddsp-svc-official_amd/)")
+    trees = {"bank": ROOT, "solo": os.path.abspath(a.baseline_tree)}
+    repeats = []
+    for rep in range(a.repeats):
+        for which in ("bank", "solo"):
+            cmd = ["timeout", "-k", "10", str(a.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", which, "--tree",
+                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)]
+            p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+            if p.returncode != 0:   # a fault, an abort or the time limit: nothing more is started on the device
+                raise SystemExit(f"rt_bank_time: leg {which} of repeat {rep} ended with status {p.returncode}; stopping")
+            for line in p.stdout.splitlines():
+                if line.startswith("{"):
+                    row = dict(json.loads(line), repeat=rep)
+                    repeats.append(row)
+                    print(json.dumps(row), flush=True)
+    # per case: every repeat's mean, the spread of each leg between its repeats, the S-fold solo time against the bank
+    cases = []
+    for shape in SHAPES:
+        for S in STREAMS:
+            pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
+            bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
+            med = lambda v: sorted(v)[len(v) // 2]
+            cases.append({"shape": shape, "streams": S, "bank_mean_ms": bm, "solo_mean_ms": sm, "bank_p99_ms": pick("bank", "p99_ms"),
+                          "solo_p99_ms": pick("solo", "p99_ms"), "bank_spread_ms": max(bm) - min(bm),
+                          "solo_spread_ms": max(sm) - min(sm), "bank_median_ms": med(bm), "solo_median_ms": med(sm),
+                          "solo_over_bank": med(sm) / med(bm)})
+    out = {"device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
+           "what": "ms per block period for all S streams: bank = one StreamBank.push_audio; solo = S StreamRenderer.push_audio "
+                   "of the baseline tree one after the other", "cases": cases, "rows": repeats}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+    for c in cases:
+        print(f"{c['shape']:8s} S={c['streams']:2d}: bank {c['bank_median_ms']:8.3f} ms (spread {c['bank_spread_ms']:.3f}), "
+              f"solo x S {c['solo_median_ms']:8.3f} ms (spread {c['solo_spread_ms']:.3f}), ratio {c['solo_over_bank']:.2f}")
+
+
+if __name__ == "__main__":
+    main()
