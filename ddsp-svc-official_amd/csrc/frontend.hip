@@ -88,14 +88,24 @@ __global__ void __launch_bounds__(256) align_units_kernel(const float* __restric
 // f0 track re-timed for the enhancer (enhancer.py:56-62): out[i] = numpy.interp(i * step_dst, knots j * step_num / div,
 // fl32(f0[j] * scale)) with the end values held outside the knots; one thread per output frame, fp64 like numpy.  Ragged batch
 // (ns != nullptr): blockIdx.y is the row, with ns[b] <= n_src knots and nd[b] <= n_dst targets of its own - the ends are held
-// at the row's own first and last frame, what follows them in f0 is not read, and the outputs from nd[b] on are 0.
+// at the row's own first and last frame, what follows them in f0 is not read, and the outputs from nd[b] on are 0.  Keyed batch
+// (key != nullptr, a ragged one): the row's (div, scale) are entry key[b] of two device tables of n_keys entries, the key clamped
+// into them.
 __global__ void __launch_bounds__(256) retime_f0_kernel(const float* __restrict__ f0, int64_t n_src, double step_num, double div,
                                                         float scale, double step_dst, int64_t n_dst, float* __restrict__ out,
-                                                        const int32_t* __restrict__ ns, const int32_t* __restrict__ nd) {
+                                                        const int32_t* __restrict__ ns, const int32_t* __restrict__ nd,
+                                                        const int32_t* __restrict__ key, const double* __restrict__ div_tab,
+                                                        const float* __restrict__ scale_tab, int n_keys) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_dst) return;
     if (ns) {
         const int64_t b = blockIdx.y;
+        if (key) {
+            int k = key[b];
+            k = k < 0 ? 0 : (k >= n_keys ? n_keys - 1 : k);
+            div = div_tab[k];
+            scale = scale_tab[k];
+        }
         f0 += b * n_src;
         out += b * n_dst;
         if (i >= (int64_t)nd[b]) {
@@ -128,7 +138,9 @@ __global__ void __launch_bounds__(256) retime_f0_kernel(const float* __restrict_
 
 // both retime entry points: ns == nd == nullptr is the solo call (B = 1, every knot and target)
 static int retime_f0_go(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* ns, double step_num,
-                        double div, float scale, double step_dst, int64_t n_dst, const int32_t* nd, float* out) {
+                        double div, float scale, double step_dst, int64_t n_dst, const int32_t* nd, float* out,
+                        const int32_t* key = nullptr, const double* div_tab = nullptr, const float* scale_tab = nullptr,
+                        int n_keys = 0) {
     DDSP_REQUIRE(ctx, ctx && f0 && out, "ddsp_retime_f0: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && n_src >= 1 && n_dst >= 0 && step_num > 0 && div > 0 && step_dst > 0,
                  "ddsp_retime_f0: bad shape or step");
@@ -136,7 +148,7 @@ static int retime_f0_go(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B,
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     hipLaunchKernelGGL(retime_f0_kernel, dim3((unsigned)ceil_div64(n_dst, 256), (unsigned)B), dim3(256), 0, st, f0, n_src, step_num, div,
-                       scale, step_dst, n_dst, out, ns, nd);
+                       scale, step_dst, n_dst, out, ns, nd, key, div_tab, scale_tab, n_keys);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
@@ -152,6 +164,55 @@ extern "C" int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f
     DDSP_REQUIRE(ctx, ctx && n_src_rows && n_dst_rows, "ddsp_retime_f0_ragged: null argument");
     DDSP_REQUIRE(ctx, n_dst >= 1, "ddsp_retime_f0_ragged: bad shape or step");
     return retime_f0_go(ctx, stream, f0, B, n_src, n_src_rows, step_num, div, scale, step_dst, n_dst, n_dst_rows, out);
+}
+
+extern "C" int ddsp_retime_f0_keyed(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
+                                    double step_num, const int32_t* key, int n_keys, const double* div_by_key,
+                                    const float* scale_by_key, double step_dst, int64_t n_dst, const int32_t* n_dst_rows, float* out) {
+    DDSP_REQUIRE(ctx, ctx && n_src_rows && n_dst_rows && key && div_by_key && scale_by_key, "ddsp_retime_f0_keyed: null argument");
+    DDSP_REQUIRE(ctx, n_dst >= 1 && n_keys >= 1, "ddsp_retime_f0_keyed: bad shape or table");
+    // (the tables live on the device: their entries are the caller's to keep positive, as `div` is checked in the other forms)
+    return retime_f0_go(ctx, stream, f0, B, n_src, n_src_rows, step_num, 1.0, 1.f, step_dst, n_dst, n_dst_rows, out, key, div_by_key,
+                        scale_by_key, n_keys);
+}
+
+// The enhancer's key of every row, decided on the device (enhancer.py:34-38 without its read-back): one wave per row takes
+// the highest f0 of the frames from `cut` on, forms q = fl32(f0max / 760) and returns the first k with q <= thr[k], thr[k]
+// being the largest fp32 value <= 2^(k/12) (a host table) - the comparison form of ceil(12 log2 q) <= k, which needs no
+// device log2.  request[b] >= 0 is a fixed key instead; both are clamped to max_key.
+namespace {
+__global__ void __launch_bounds__(64) enhancer_keys_kernel(const float* __restrict__ f0, int64_t Fr, int64_t cut, int max_key,
+                                                           const int32_t* __restrict__ request, const float* __restrict__ thr,
+                                                           int32_t* __restrict__ key) {
+    const int64_t b = blockIdx.x;
+    const int want = request[b];
+    if (want >= 0) {
+        if (threadIdx.x == 0) key[b] = want > max_key ? max_key : want;
+        return;
+    }
+    float m = -INFINITY;
+    for (int64_t i = cut + threadIdx.x; i < Fr; i += 64) m = fmaxf(m, f0[b * Fr + i]);
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    if (threadIdx.x != 0) return;
+    int k = 0;
+    if (m > 0.f) {
+        const float q = __fdiv_rn(m, 760.f);
+        while (k < max_key && !(q <= thr[k])) ++k;
+    }
+    key[b] = k;
+}
+}  // namespace
+
+extern "C" int ddsp_enhancer_keys(ddsp_ctx* ctx, void* stream, const float* f0, int64_t S, int64_t Fr, int64_t cut_frames, int max_key,
+                                  const int32_t* request, const float* thresholds, int32_t* key) {
+    DDSP_REQUIRE(ctx, ctx && f0 && request && thresholds && key, "ddsp_enhancer_keys: null argument");
+    DDSP_REQUIRE(ctx, S >= 1 && S <= (1 << 20) && Fr >= 1 && cut_frames >= 0 && cut_frames < Fr && max_key >= 0 && max_key <= 12,
+                 "ddsp_enhancer_keys: bad shape, cut or max_key (0..12; thresholds holds max_key + 1 values)");
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    hipLaunchKernelGGL(enhancer_keys_kernel, dim3((unsigned)S), dim3(64), 0, st, f0, Fr, cut_frames, max_key, request, thresholds, key);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
 }
 
 // Python's float floor division `a // b` (CPython float_floor_div: fmod, exact quotient of the remainder-free part, floor,

@@ -41,45 +41,47 @@ __device__ __forceinline__ int64_t row_samples(const int32_t* __restrict__ ns, i
     return n < 0 ? 0 : (n > T ? T : n);
 }
 
+constexpr int RS_RB = 8;   // input frames per thread of the blocked form
+
+// one output of the one-output-per-thread form: o < the row's own outputs, T the row's own samples
+__device__ __forceinline__ float resample_direct_one(const float* __restrict__ xr, const float* __restrict__ taps, int64_t T,
+                                                     int64_t o, int orig, int nw, int width, int K) {
+    const int64_t l = o / nw;
+    const int p = (int)(o - l * nw);
+    const float* tp = taps + p;   // [k][phase]
+    const int64_t first = l * orig - width;
+    int k0 = first < 0 ? (int)(-first) : 0;
+    int k1 = first + K > T ? (int)(T - first) : K;
+    // four partial sums (the order of a long fp32 sum matters at the 1e-7 level; a blocked sum is closer to the exact
+    // value than a running one)
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int k = k0;
+    for (; k + 3 < k1; k += 4) {
+        a0 = fmaf(xr[first + k], tp[(int64_t)k * nw], a0);
+        a1 = fmaf(xr[first + k + 1], tp[(int64_t)(k + 1) * nw], a1);
+        a2 = fmaf(xr[first + k + 2], tp[(int64_t)(k + 2) * nw], a2);
+        a3 = fmaf(xr[first + k + 3], tp[(int64_t)(k + 3) * nw], a3);
+    }
+    for (; k < k1; ++k) a0 = fmaf(xr[first + k], tp[(int64_t)k * nw], a0);
+    return (a0 + a1) + (a2 + a3);
+}
+
 __global__ void __launch_bounds__(256) resample_kernel(const float* __restrict__ x, const float* __restrict__ taps,
                                                        int64_t Tpad, int64_t T_out, int orig, int nw, int width, int K,
                                                        int64_t total, float* __restrict__ out, const int32_t* __restrict__ ns) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / T_out, o = i - b * T_out;
-        const int64_t l = o / nw;
-        const int p = (int)(o - l * nw);
-        const float* xr = x + b * Tpad;
         const int64_t T = row_samples(ns, b, Tpad);
-        if (o >= (nw * T + orig - 1) / orig) {   // (never in a rectangular call)
-            out[i] = 0.f;
-            continue;
-        }
-        const float* tp = taps + p;   // [k][phase]
-        const int64_t first = l * orig - width;
-        int k0 = first < 0 ? (int)(-first) : 0;
-        int k1 = first + K > T ? (int)(T - first) : K;
-        // four partial sums (the order of a long fp32 sum matters at the 1e-7 level; a blocked sum is closer to the exact
-        // value than a running one)
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int k = k0;
-        for (; k + 3 < k1; k += 4) {
-            a0 = fmaf(xr[first + k], tp[(int64_t)k * nw], a0);
-            a1 = fmaf(xr[first + k + 1], tp[(int64_t)(k + 1) * nw], a1);
-            a2 = fmaf(xr[first + k + 2], tp[(int64_t)(k + 2) * nw], a2);
-            a3 = fmaf(xr[first + k + 3], tp[(int64_t)(k + 3) * nw], a3);
-        }
-        for (; k < k1; ++k) a0 = fmaf(xr[first + k], tp[(int64_t)k * nw], a0);
-        out[i] = (a0 + a1) + (a2 + a3);
+        // (past the row's own outputs: never in a rectangular call)
+        out[i] = o >= (nw * T + orig - 1) / orig ? 0.f : resample_direct_one(x + b * Tpad, taps, T, o, orig, nw, width, K);
     }
 }
 
-constexpr int RS_RB = 8;   // input frames per thread
-__global__ void __launch_bounds__(256) resample_blocked_kernel(const float* __restrict__ x, const float* __restrict__ taps,
-                                                               int64_t Tpad, int64_t T_out, int orig, int nw, int width, int K,
-                                                               float* __restrict__ out, const int32_t* __restrict__ ns) {
-    extern __shared__ float win[];
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const int64_t l0 = (int64_t)blockIdx.y * RS_RB, b = blockIdx.z;
+// the work of one workgroup of the blocked form: phases bx * 256 .. of the input frames l0 .. l0 + RS_RB - 1 of row b
+__device__ __forceinline__ void resample_blocked_body(const float* __restrict__ x, const float* __restrict__ taps, int64_t Tpad,
+                                                      int64_t T_out, int orig, int nw, int width, int K, float* __restrict__ out,
+                                                      const int32_t* __restrict__ ns, float* win, int bx, int64_t l0, int64_t b) {
+    const int p = bx * 256 + threadIdx.x;
     const int wlen = (RS_RB - 1) * orig + K;
     const int64_t first = l0 * orig - width;
     const float* xr = x + b * Tpad;
@@ -113,6 +115,60 @@ __global__ void __launch_bounds__(256) resample_blocked_kernel(const float* __re
     for (int r = 0; r < RS_RB; ++r) {
         const int64_t o = (l0 + r) * nw + p;
         if (o < T_out) out[b * T_out + o] = o < T_row ? acc[r][0] + acc[r][1] : 0.f;
+    }
+}
+
+__global__ void __launch_bounds__(256) resample_blocked_kernel(const float* __restrict__ x, const float* __restrict__ taps,
+                                                               int64_t Tpad, int64_t T_out, int orig, int nw, int width, int K,
+                                                               float* __restrict__ out, const int32_t* __restrict__ ns) {
+    extern __shared__ float win[];
+    resample_blocked_body(x, taps, Tpad, T_out, orig, nw, width, K, out, ns, win, (int)blockIdx.x, (int64_t)blockIdx.y * RS_RB,
+                          (int64_t)blockIdx.z);
+}
+
+// Keyed batch: row b is resampled with the rate pair pairs[key[b]] of a plan (ddsp_resample_keyed_plan).  The pair is uniform
+// over a workgroup, and the grid and the LDS are those of the largest pair of the set: a workgroup that has no output of its
+// row's pair returns at once, one past the row's own outputs writes its zeros and stages nothing, and the others run the body
+// of the kernel `ddsp_resample` would launch for that pair - the same taps in the same order, so the same bits.
+enum { RS_MODE_BLOCKED = 0, RS_MODE_DIRECT = 1, RS_MODE_COPY = 2 };
+struct RsPair {
+    const float* taps;
+    int orig, nw, width, K, mode, pad_;
+};
+
+__global__ void __launch_bounds__(256) resample_keyed_kernel(const float* __restrict__ x, const RsPair* __restrict__ pairs, int n_pairs,
+                                                             int64_t Tpad, int64_t T_out, float* __restrict__ out,
+                                                             const int32_t* __restrict__ ns, const int32_t* __restrict__ key) {
+    extern __shared__ float win[];
+    const int64_t b = blockIdx.z;
+    int k = __builtin_amdgcn_readfirstlane(key[b]);
+    k = k < 0 ? 0 : (k >= n_pairs ? n_pairs - 1 : k);   // a garbage key reads no table it should not
+    const RsPair pr = pairs[k];
+    const int64_t T = row_samples(ns, b, Tpad);
+    if (pr.mode == RS_MODE_BLOCKED) {
+        const int64_t l0 = (int64_t)blockIdx.y * RS_RB;
+        if ((int64_t)blockIdx.x * 256 >= pr.nw || l0 * pr.nw >= T_out) return;   // no output of this pair lives here
+        const int64_t T_row = ((int64_t)pr.nw * T + pr.orig - 1) / pr.orig;
+        if (l0 * pr.nw >= T_row) {                                              // past the row's own extent
+            const int p = blockIdx.x * 256 + threadIdx.x;
+            if (p < pr.nw)
+                for (int r = 0; r < RS_RB; ++r) {
+                    const int64_t o = (l0 + r) * pr.nw + p;
+                    if (o < T_out) out[b * T_out + o] = 0.f;
+                }
+            return;
+        }
+        resample_blocked_body(x, pr.taps, Tpad, T_out, pr.orig, pr.nw, pr.width, pr.K, out, ns, win, (int)blockIdx.x, l0, b);
+        return;
+    }
+    // the one-output-per-thread form and the copy of an identity pair: the row's workgroups stride over its outputs
+    const int64_t G = (int64_t)gridDim.x * gridDim.y * 256;
+    const int64_t T_row = pr.mode == RS_MODE_COPY ? T : ((int64_t)pr.nw * T + pr.orig - 1) / pr.orig;
+    const float* xr = x + b * Tpad;
+    for (int64_t o = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; o < T_out; o += G) {
+        float v = 0.f;
+        if (o < T_row) v = pr.mode == RS_MODE_COPY ? xr[o] : resample_direct_one(xr, pr.taps, T, o, pr.orig, pr.nw, pr.width, pr.K);
+        out[b * T_out + o] = v;
     }
 }
 
@@ -224,4 +280,128 @@ extern "C" int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x,
                                     int orig_freq, int new_freq, int lowpass_filter_width, float* out) {
     DDSP_REQUIRE(ctx, n_samples, "ddsp_resample_ragged: null n_samples");
     return resample_run(ctx, stream, x, B, T, orig_freq, new_freq, lowpass_filter_width, out, n_samples);
+}
+
+// ---- keyed batches: one launch, a rate pair per row ---------------------------------------------------------------------------
+// A plan owns the tap tables of its pairs in ONE allocation of its own (descriptors first, then the tables): they are built
+// when the plan is, all stay resident while it lives, and the context's LRU of solo tables never sees them.
+constexpr int RS_PLAN_MAX_PAIRS = 13;
+
+struct ddsp_resample_plan {
+    int device, n_pairs, lowpass;
+    int orig_freq[RS_PLAN_MAX_PAIRS], new_freq[RS_PLAN_MAX_PAIRS];
+    RsPair host[RS_PLAN_MAX_PAIRS];
+    char* dev;         // RsPair[RS_PLAN_MAX_PAIRS], then the tap tables
+    int max_nw;
+    size_t lds;        // of the largest blocked pair
+};
+
+extern "C" int ddsp_resample_keyed_plan(ddsp_ctx* ctx, void* stream, int n_pairs, const int* orig_freq, const int* new_freq,
+                                        int lowpass_filter_width, ddsp_resample_plan** plan) {
+    DDSP_REQUIRE(ctx, ctx && orig_freq && new_freq && plan, "ddsp_resample_keyed_plan: null argument");
+    DDSP_REQUIRE(ctx, n_pairs >= 1 && n_pairs <= RS_PLAN_MAX_PAIRS && lowpass_filter_width >= 1 && lowpass_filter_width <= 4096,
+                 "ddsp_resample_keyed_plan: bad argument (1 to 13 pairs)");
+    *plan = nullptr;
+    ddsp_resample_plan pl = {};
+    pl.device = ctx->device;
+    pl.n_pairs = n_pairs;
+    pl.lowpass = lowpass_filter_width;
+    size_t floats[RS_PLAN_MAX_PAIRS] = {}, total = 0;
+    double base[RS_PLAN_MAX_PAIRS] = {};
+    for (int i = 0; i < n_pairs; ++i) {
+        DDSP_REQUIRE(ctx, orig_freq[i] >= 1 && new_freq[i] >= 1, "ddsp_resample_keyed_plan: bad rate");
+        pl.orig_freq[i] = orig_freq[i];
+        pl.new_freq[i] = new_freq[i];
+        RsPair& p = pl.host[i];
+        if (orig_freq[i] == new_freq[i]) {   // the row is copied (what the callers of ddsp_resample do for equal rates)
+            p.mode = RS_MODE_COPY;
+            p.orig = p.nw = 1;
+            continue;
+        }
+        // (the arithmetic of resample_run, so that the tables are the ones ddsp_resample builds)
+        const int g = gcd_int(orig_freq[i], new_freq[i]);
+        p.orig = orig_freq[i] / g;
+        p.nw = new_freq[i] / g;
+        DDSP_REQUIRE(ctx, p.orig < 65536 && p.nw < 65536, "ddsp_resample_keyed_plan: rate ratio too fine (reduced rates must be < 65536)");
+        base[i] = (double)(p.orig < p.nw ? p.orig : p.nw) * 0.99;
+        p.width = (int)ceil((double)lowpass_filter_width * (double)p.orig / base[i]);
+        p.K = 2 * p.width + p.orig;
+        DDSP_REQUIRE(ctx, (int64_t)p.nw * p.K < (1 << 28), "ddsp_resample_keyed_plan: tap table too large");
+        const size_t lds = ((size_t)(RS_RB - 1) * p.orig + p.K) * sizeof(float);
+        p.mode = lds <= 64 * 1024 ? RS_MODE_BLOCKED : RS_MODE_DIRECT;
+        if (p.mode == RS_MODE_BLOCKED) {
+            if (lds > pl.lds) pl.lds = lds;
+            if (p.nw > pl.max_nw) pl.max_nw = p.nw;
+        }
+        floats[i] = ((size_t)p.nw * p.K + 63) & ~(size_t)63;
+        total += floats[i];
+    }
+    if (pl.max_nw < 1) pl.max_nw = 1;
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    const size_t head = (sizeof(RsPair) * RS_PLAN_MAX_PAIRS + 255) & ~(size_t)255;
+    hipError_t e = hipMalloc((void**)&pl.dev, head + total * sizeof(float));
+    if (e != hipSuccess) return ddsp_fail(ctx, DDSP_ERR_OOM, "resample plan hipMalloc", hipGetErrorString(e));
+    float* at = (float*)(pl.dev + head);
+    for (int i = 0; i < n_pairs; ++i) {
+        RsPair& p = pl.host[i];
+        if (p.mode == RS_MODE_COPY) continue;
+        p.taps = at;
+        at += floats[i];
+        hipLaunchKernelGGL(resample_taps_kernel, dim3((unsigned)(((int64_t)p.nw * p.K + 255) / 256)), dim3(256), 0, st,
+                           (float*)p.taps, p.orig, p.nw, p.width, p.K, base[i], (double)lowpass_filter_width);
+    }
+    // the plan may be used on any stream of the device afterwards: wait for the tables here, once
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(pl.dev, pl.host, sizeof(RsPair) * RS_PLAN_MAX_PAIRS, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(pl.dev);
+        return ddsp_fail(ctx, DDSP_ERR_HIP, "resample plan tables", hipGetErrorString(e));
+    }
+    *plan = new ddsp_resample_plan(pl);
+    return DDSP_OK;
+}
+
+extern "C" void ddsp_resample_keyed_plan_destroy(ddsp_resample_plan* plan) {
+    if (!plan) return;
+    ddsp_device_guard guard;
+    if (guard.enter(plan->device) == hipSuccess) (void)hipFree(plan->dev);   // (hipFree waits for kernels that read the tables)
+    delete plan;
+}
+
+extern "C" int64_t ddsp_resample_keyed_length(const ddsp_resample_plan* plan, int64_t T) {
+    if (!plan || T < 0) return -1;
+    int64_t best = 0;
+    for (int i = 0; i < plan->n_pairs; ++i) {
+        const int64_t n = ddsp_resample_length(T, plan->orig_freq[i], plan->new_freq[i]);
+        if (n > best) best = n;
+    }
+    return best;
+}
+
+extern "C" int ddsp_resample_keyed(ddsp_ctx* ctx, void* stream, const ddsp_resample_plan* plan, const float* x, int64_t B, int64_t T,
+                                   const int32_t* n_samples, const int32_t* key, float* out) {
+    DDSP_REQUIRE(ctx, ctx && plan && x && out && n_samples && key, "ddsp_resample_keyed: null argument");
+    DDSP_REQUIRE(ctx, plan->device == ctx->device, "ddsp_resample_keyed: the plan lives on another device");
+    DDSP_REQUIRE(ctx, B >= 0 && B < 65536 && T >= 1, "ddsp_resample_keyed: bad argument");
+    if (B == 0) return DDSP_OK;
+    const int64_t T_out = ddsp_resample_keyed_length(plan, T);
+    // the grid of the largest pair: every blocked pair's frames over the padded width, RS_RB to a workgroup
+    int64_t gy = 1;
+    for (int i = 0; i < plan->n_pairs; ++i) {
+        const RsPair& p = plan->host[i];
+        if (p.mode != RS_MODE_BLOCKED) continue;
+        const int64_t groups = ceil_div64(ceil_div64(T_out, p.nw), RS_RB);
+        if (groups > gy) gy = groups;
+    }
+    DDSP_REQUIRE(ctx, gy < 65536, "ddsp_resample_keyed: rows too long for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(resample_keyed_kernel, dim3((unsigned)((plan->max_nw + 255) / 256), (unsigned)gy, (unsigned)B), dim3(256),
+                       plan->lds, st, x, (const RsPair*)plan->dev, plan->n_pairs, T, T_out, out, n_samples, key);
+    ddsp_prof_end(ctx, st, 0.0, 4.0 * (B * T + B * T_out));
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
 }

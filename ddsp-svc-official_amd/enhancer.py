@@ -108,11 +108,24 @@ class STFT:
         pad_right = max((n - hop + 1) // 2, n - int(n_samples) - pad_left)
         return (int(n_samples) + pad_left + pad_right - n) // hop + 1
 
-    def get_mel(self, y, keyshift=0, speed=1, center=False, n_samples=None):
+    def get_mel(self, y, keyshift=0, speed=1, center=False, n_samples=None, n_frames=None):
+        """`n_samples` / `n_frames` as two `RaggedCounts`: a ragged batch whose counts live on the device only (the rows'
+        samples, and their `frame_count` with `n_frames.T` the padded frame axis) - nothing is checked on the host or
+        uploaded, so the call can be captured."""
         if keyshift != 0 or speed != 1 or center:
             raise ValueError("only keyshift = 0, speed = 1, center = False (how the Enhancer calls it) is built")
         if y.dim() != 2:
             raise ValueError("STFT.get_mel: y must be (B, T)")
+        if isinstance(n_samples, RaggedCounts) or isinstance(n_frames, RaggedCounts):
+            if not (isinstance(n_samples, RaggedCounts) and isinstance(n_frames, RaggedCounts)):
+                raise ValueError("STFT.get_mel: device counts need both n_samples and n_frames as RaggedCounts")
+            if n_samples.T != y.shape[1] or len(n_samples.values) != y.shape[0] or len(n_frames.values) != y.shape[0]:
+                raise ValueError("STFT.get_mel: these RaggedCounts were made for another batch shape")
+            if not y.is_cuda:
+                raise RuntimeError("STFT.get_mel runs on a HIP device only (no CPU fallback)")
+            return self._get_mel_batch(y, None, dev_counts=(n_samples.dev, n_frames.dev, n_frames.T))
+        if n_frames is not None:
+            raise ValueError("STFT.get_mel: n_frames goes with n_samples as RaggedCounts")
         vals = None if n_samples is None else hipddsp.check_n_samples(n_samples, y.shape[0], y.shape[1])
         if not y.is_cuda:
             raise RuntimeError("STFT.get_mel runs on a HIP device only (no CPU fallback)")
@@ -129,11 +142,18 @@ class STFT:
         out = hipddsp.context_for(y.device).log_mel(frames, tab, mel, self.clip_val)      # (frames, n_mels)
         return out.t().unsqueeze(0)
 
-    def _get_mel_batch(self, y, vals):
+    def _get_mel_batch(self, y, vals, dev_counts=None):
         """Rows of different length (vals: checked counts, None = every row whole): framing on the device with the padding
-        rule chosen per row, then the spectral half on B * L_max rows."""
+        rule chosen per row, then the spectral half on B * L_max rows.  dev_counts = (samples (B,), frames (B,), L): the counts
+        as device tensors only."""
         B, T = y.shape
         c = hipddsp.context_for(y.device)
+        if dev_counts is not None:
+            n_dev, f_dev, L = dev_counts
+            frames = c.stft_frames(y, n_dev, self.n_fft, self.hop_length, L)
+            tab, mel = self._device_tables(y.device)
+            out = c.log_mel(frames.reshape(B * L, self.n_fft), tab, mel, self.clip_val).reshape(B, L, self.n_mels)
+            return c.ragged_frames(out, f_dev, hold=False).transpose(1, 2)
         frames_of = [self.frame_count(v) for v in (vals if vals is not None else [T] * B)]
         L = max(frames_of)
         n_dev = None if vals is None else c.ragged_counts(vals)
@@ -427,6 +447,62 @@ class NsfHifiGAN(torch.nn.Module):
             return enhanced.reshape(audio.shape[0], -1), self.h.sampling_rate
 
 
+class KeyedPlan:
+    """What `Enhancer.enhance_keyed` needs besides the audio, for one geometry (T samples and Fr f0 frames per row at
+    `sample_rate` / `hop_size`, `silence_front`, keys 0..max_key), built once.
+    Host part (the constructor; no device is touched): `rates[k]`, the working rate of key k, and `lengths[k]`, the five integers
+    of `Enhancer.batch_lengths` for the cut row at that rate; `widths`, the five column maxima that size every buffer; the
+    front cut and the front pad.  Device part (`on(device)`, once per device): the lengths, the key thresholds and the
+    re-timing scalars as tensors, and the two resampler plans (into the working rates and back) with their tap tables.
+    DIVERGENCE: the reference's 'auto' key is unbounded; here keys above `max_key` are clamped to it, because the set of
+    working rates - tap tables, buffer sizes - has to be finite."""
+
+    def __init__(self, enhancer, T, Fr, sample_rate, hop_size, silence_front=0, max_key=12):
+        if isinstance(max_key, bool) or not isinstance(max_key, int) or not 0 <= max_key <= 12:
+            raise ValueError(f"KeyedPlan: max_key must be an int in 0..12, got {max_key!r}")
+        self.T, self.Fr, self.sample_rate, self.hop_size = int(T), int(Fr), int(sample_rate), hop_size
+        self.silence_front, self.max_key = silence_front, max_key
+        self.sr_e, self.hop_e = int(enhancer.enhancer_sample_rate), int(enhancer.enhancer_hop_size)
+        self.cut_frames, self.cut_samples, cut_seconds = enhancer._front_cut(silence_front, sample_rate, hop_size)
+        self.front_pad = int(np.round(self.sr_e * cut_seconds)) if self.cut_frames > 0 else 0
+        self.T_cut, self.Fr_cut = self.T - self.cut_samples, self.Fr - self.cut_frames
+        if self.T_cut < 1 or self.Fr_cut < 1:
+            raise ValueError(f"KeyedPlan: silence_front = {silence_front} leaves no audio or no f0 frame of the row")
+        self.rates, self.pitch_scales = [], []
+        for k in range(max_key + 1):
+            rate, scale, _ = enhancer._working_rate(k, None)
+            for a, b in ((self.sample_rate, rate), (rate, self.sr_e)):
+                g = int(np.gcd(a, b)) if a >= 1 and b >= 1 else 0
+                if g < 1 or a // g >= 65536 or b // g >= 65536:
+                    raise ValueError(f"KeyedPlan: the resampler cannot pair {a} Hz with {b} Hz (key {k})")
+            self.rates.append(rate)
+            self.pitch_scales.append(scale)
+        self.lengths = [tuple(enhancer.batch_lengths(self.T_cut, self.sample_rate, r)) for r in self.rates]
+        self.widths = tuple(max(row[i] for row in self.lengths) for i in range(5))
+        self.pairs_in = [(self.sample_rate, r) for r in self.rates]
+        self.pairs_out = [(r, self.sr_e) for r in self.rates]
+        self.n_out = [row[4] + self.front_pad for row in self.lengths]        # per key, the front pad included
+        self._dev = {}
+
+    def on(self, device):
+        """The device part, built on first use for `device` (uploads and tap tables: before any capture)."""
+        dev = torch.device(device)
+        key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+        if key not in self._dev:
+            c = hipddsp.context_for(dev)
+            d = AttrDict()
+            d.lengths = torch.tensor(self.lengths, dtype=torch.int32).to(dev)                     # (max_key + 1, 5)
+            d.thresholds = torch.from_numpy(hipddsp.key_thresholds(self.max_key)).to(dev)
+            d.div = torch.tensor(self.pitch_scales, dtype=torch.float64).to(dev)
+            d.scale = torch.tensor(self.pitch_scales, dtype=torch.float32).to(dev)
+            d.rs_in = c.resample_plan(self.pairs_in, 128)
+            d.rs_out = c.resample_plan(self.pairs_out, 128)
+            if d.rs_in.length(self.T_cut) != self.widths[0] or d.rs_out.length(self.widths[3]) < self.widths[4]:
+                raise RuntimeError("KeyedPlan: the resampler plans disagree with batch_lengths")
+            self._dev[key] = d
+        return self._dev[key]
+
+
 class Enhancer:
     """`enhancer.py:9-78`, same constructor and `enhance` signature."""
 
@@ -488,6 +564,77 @@ class Enhancer:
         if cut_frames > 0:
             enhanced = F.pad(enhanced, (int(np.round(sr_e * cut_seconds)), 0))
         return enhanced, sr_e
+
+    # -- rows with a key of their own in one batch: nothing asks the host --------------------------------------------------
+    def keyed_plan(self, T, Fr, sample_rate, hop_size, silence_front=0, max_key=12):
+        return KeyedPlan(self, T, Fr, sample_rate, hop_size, silence_front, max_key)
+
+    @staticmethod
+    def check_key_request(adaptive_key, max_key, what="adaptive_key"):
+        """'auto' -> -1, a whole number in 0..max_key -> that int; anything else raises ValueError (a host check)."""
+        if isinstance(adaptive_key, str):
+            if adaptive_key != "auto":
+                raise ValueError(f"{what} must be a number or 'auto', got {adaptive_key!r}")
+            return -1
+        if isinstance(adaptive_key, bool) or not isinstance(adaptive_key, (int, float, np.integer, np.floating)) or \
+                float(adaptive_key) != int(adaptive_key) or not 0 <= int(adaptive_key) <= max_key:
+            raise ValueError(f"{what} must be 'auto' or a whole number in 0..{max_key}, got {adaptive_key!r}")
+        return int(adaptive_key)
+
+    def enhance_keyed(self, audio, sample_rate, f0, hop_size, adaptive_key="auto", silence_front=0, max_key=12, rand_ini=None,
+                      plan=None):
+        """S rows, each with an adaptive key of its own, in ONE pass with no host synchronisation: audio (S, T), f0 (S, Fr, 1)
+        -> (enhanced (S, T'_max), enhancer sample rate, n_out (S,) int32 device, key (S,) int32 device).  Row s holds
+        `enhance(audio[s:s+1], sample_rate, f0[s:s+1], hop_size, adaptive_key=key[s], silence_front=silence_front)` in
+        [:n_out[s]] (front cut and front pad included) and exactly 0 after it.
+        adaptive_key: 'auto' (the reference's rule per row, on the device: `ddsp_enhancer_keys`), one whole number, or a (S,)
+        int32 device tensor of requests (-1 = 'auto').  Keys are clamped to max_key (0..12; the reference has no cap: see
+        `KeyedPlan`).  `plan`: the `KeyedPlan` of this geometry (`keyed_plan`); with one, the call uploads nothing and can be
+        captured in a HIP graph - then pass `rand_ini` (9,) or (S, 9) as a DEVICE tensor too (None draws on the host)."""
+        if audio.dim() != 2 or f0.dim() != 3 or f0.shape[0] != audio.shape[0] or f0.shape[2] != 1:
+            raise ValueError("enhance_keyed: audio must be (S, T) and f0 (S, Fr, 1)")
+        S, T = audio.shape
+        Fr = f0.shape[1]
+        if plan is None:
+            plan = KeyedPlan(self, T, Fr, sample_rate, hop_size, silence_front, max_key)
+        elif (plan.T, plan.Fr, plan.sample_rate, plan.hop_size, plan.silence_front, plan.max_key) != \
+                (T, Fr, int(sample_rate), hop_size, silence_front, max_key):
+            raise ValueError("enhance_keyed: this KeyedPlan was made for another geometry")
+        request = None
+        if isinstance(adaptive_key, torch.Tensor):
+            if adaptive_key.dtype != torch.int32 or tuple(adaptive_key.shape) != (S,):
+                raise ValueError("enhance_keyed: a tensor of key requests must be (S,) int32")
+            request = adaptive_key
+        else:
+            fixed = self.check_key_request(adaptive_key, plan.max_key)
+        if not audio.is_cuda or (request is not None and not request.is_cuda):
+            raise RuntimeError("the enhancer runs on a HIP device only (no CPU fallback)")
+        dev = audio.device
+        c = hipddsp.context_for(dev)
+        d = plan.on(dev)
+        if request is None:
+            request = torch.full((S,), fixed, dtype=torch.int32, device=dev)
+        f0 = f0.reshape(S, Fr).float()
+        key = c.enhancer_keys(f0, plan.cut_frames, plan.max_key, request.contiguous(), d.thresholds)
+        # the five lengths of every row: one gather of the plan's table by the key
+        n_res, n_f0, n_frames, n_gen, n_out = d.lengths.index_select(0, key.long()).t().contiguous().unbind(0)
+        w_res, w_f0, L, w_gen, w_out = plan.widths
+        whole = torch.full((S,), plan.T_cut, dtype=torch.int32, device=dev)
+        audio_res = c.resample_keyed(d.rs_in, audio[:, plan.cut_samples:], whole, key)                     # (S, w_res)
+        f0_res = c.retime_f0(f0[:, plan.cut_frames:], hop_size / sample_rate, None, None, self.enhancer_hop_size / self.enhancer_sample_rate,
+                             w_f0, n_src_dev=torch.full((S,), plan.Fr_cut, dtype=torch.int32, device=dev), n_dst_dev=n_f0,
+                             keyed=(key, d.div, d.scale))
+        stft = self.enhancer.stft()
+        with torch.no_grad():
+            mel = stft.get_mel(audio_res, n_samples=RaggedCounts([w_res] * S, w_res, n_res), n_frames=RaggedCounts([L] * S, L, n_frames))
+            if rand_ini is None:
+                rand_ini = torch.rand(S, 9)
+            enhanced = self.enhancer.model(mel, f0_res[:, :L], rand_ini=rand_ini, n_frames=RaggedCounts([L] * S, L, n_frames))
+        enhanced = c.resample_keyed(d.rs_out, enhanced.reshape(S, -1), n_gen, key)[:, :w_out]
+        if plan.front_pad > 0:
+            enhanced = F.pad(enhanced, (plan.front_pad, 0))
+            n_out = n_out + plan.front_pad
+        return enhanced, self.enhancer_sample_rate, n_out, key
 
     # -- rows of different length in one batch ---------------------------------------------------------------------------
     def batch_lengths(self, n_samples, sample_rate, work_rate):

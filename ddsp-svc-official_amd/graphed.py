@@ -28,6 +28,11 @@ inside the graph on every replay (in-place updates are honoured, as above); the 
 inference only) are prepared once by the warm-up runs and the captured kernels read those copies
 (`ddsp_weight_slot_take(..., keep_in_capture)`), so a change of THEIR weights needs a new capture.  The CREPE dither seed lives
 in a device word that the decode advances (`ddsp_crepe_decode_dseed`): a seed passed by value would be frozen by the capture.
+
+`GraphedBankEnhancer` captures the enhancer stage of a `realtime.StreamBank` (`bank_enhancer_chain`: the per-row adaptive key
+decided on the device, the keyed resamplers, the ragged generator, the resampling to the device rate and the gather of every
+row's own tail) as a second linear graph that is replayed right after the first.  That it can be captured at all is the proof
+that nothing in the stage asks the host: a row whose pitch crosses a key boundary changes device data, not the graph.
 """
 import torch
 
@@ -263,3 +268,65 @@ class GraphedBank:
             self.noise.copy_(noise)
         self.graph.replay()
         return self.sig, self.f0, self.units, self.volume
+
+
+def bank_enhancer_chain(ctx, enhancer, plan, sig, f0, request, rand_ini, model_sr, block_size, samplerate, n_end_by_key, tail_idx):
+    """Steps 6-7 of the `StreamRenderer` chain over S rows, nothing read back: `enhancer.enhance_keyed` on the gated signal
+    `sig` (S, Fr * block_size) and the shifted `f0` (S, Fr, 1) with the per-row key requests `request` (S,) int32 and the bank's
+    `plan` (`enhancer.KeyedPlan`); `ddsp_resample_ragged` from the enhancer's rate to `samplerate` on the device lengths; then
+    every row's last `tail_idx.numel()` samples counted from the row's OWN end (`gui.py:405-406` slices from the end), the
+    end being `n_end_by_key[key]`.  -> (tail (S, n_tail), key (S,) int32)."""
+    out, sr_e, n_out, key = enhancer.enhance_keyed(sig, model_sr, f0, block_size, adaptive_key=request,
+                                                   silence_front=plan.silence_front, max_key=plan.max_key, rand_ini=rand_ini, plan=plan)
+    if int(sr_e) != int(samplerate):
+        out = ctx.resample(out, int(sr_e), int(samplerate), 128, n_dev=n_out)
+    n_end = n_end_by_key.index_select(0, key.long())
+    idx = (n_end.long() - tail_idx.numel())[:, None] + tail_idx[None, :]
+    return out.gather(1, idx), key
+
+
+class GraphedBankEnhancer:
+    """`bank_enhancer_chain` for S rows of one geometry as one linear HIP graph.  `request` is the caller's tensor (the bank's
+    table of key requests, read at its fixed address).  Static inputs: `sig`, `f0`, `rand_ini` (S, 9), refilled before every
+    replay; static outputs (valid until the next replay): `tail`, `key`.  The plan's tap tables and device tables are built by
+    the warm-up runs, before the capture."""
+
+    def __init__(self, enhancer, plan, S, request, model_sr, block_size, samplerate, n_end_by_key, tail_idx, warmup=3):
+        self.device = dev = request.device
+        if dev.type != "cuda":
+            raise RuntimeError("GraphedBankEnhancer needs the bank's state on a HIP device (no CPU fallback)")
+        self.enhancer, self.plan, self.request = enhancer, plan, request
+        self.args = (int(model_sr), int(block_size), samplerate, n_end_by_key, tail_idx)
+        self.sig = torch.zeros(S, plan.T, device=dev)
+        self.f0 = torch.full((S, plan.Fr, 1), 220.0, device=dev)
+        self.rand_ini = torch.rand(S, 9, device=dev)
+        self.ctx = hipddsp.Context(dev)
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
+            for _ in range(max(1, warmup)):
+                self._run()
+        cur.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
+            self.tail, self.key = self._run()
+        self.ctx.freeze()
+
+    def _run(self):
+        model_sr, block_size, samplerate, n_end_by_key, tail_idx = self.args
+        return bank_enhancer_chain(self.ctx, self.enhancer, self.plan, self.sig, self.f0, self.request, self.rand_ini, model_sr,
+                                   block_size, samplerate, n_end_by_key, tail_idx)
+
+    @torch.no_grad()
+    def __call__(self, sig, f0, rand_ini=None):
+        """sig (S, Fr * block_size), f0 (S, Fr, 1) -> (tail, key) (static tensors)."""
+        self.sig.copy_(sig.reshape(self.sig.shape))
+        self.f0.copy_(f0.reshape(self.f0.shape))
+        if rand_ini is None:
+            self.rand_ini.uniform_()
+        else:
+            self.rand_ini.copy_(rand_ini.reshape(-1, 9).expand_as(self.rand_ini))
+        self.graph.replay()
+        return self.tail, self.key

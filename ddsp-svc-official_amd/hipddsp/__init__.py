@@ -211,6 +211,12 @@ SIGNATURES = {
     "ddsp_nsf_post_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp, _int]),
     "ddsp_stft_frames_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp]),
     "ddsp_retime_f0_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _f64, _f32, _f64, _i64, _vp, _vp]),
+    "ddsp_retime_f0_keyed": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _vp, _int, _vp, _vp, _f64, _i64, _vp, _vp]),
+    "ddsp_enhancer_keys": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "ddsp_resample_keyed_plan": (_int, [_vp, _vp, _int, _c.POINTER(_int), _c.POINTER(_int), _int, _c.POINTER(_vp)]),
+    "ddsp_resample_keyed_plan_destroy": (None, [_vp]),
+    "ddsp_resample_keyed_length": (_i64, [_vp, _i64]),
+    "ddsp_resample_keyed": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "ddsp_volume_extract_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
     "ddsp_crepe_activations_ragged": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _vp, _vp, _i64, _int, _vp]),
     "ddsp_crepe_decode_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
@@ -738,14 +744,27 @@ class Context:
             self.call("ddsp_align_units", *args, _ptr(out))
         return out
 
-    def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst, n_src_dev=None, n_dst_dev=None):
+    def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst, n_src_dev=None, n_dst_dev=None, keyed=None):
         """f0 (n,) device track -> (n_dst,): numpy.interp(i * step_dst; knots (step_num * j) / div, values fl32(f0 * scale)),
         end values held (enhancer.py:56-62), without leaving the device.
         `n_src_dev`, `n_dst_dev` (both or neither; (B,) int32 device tensors, `ragged_counts`): a RAGGED batch - f0 (B, n_src) ->
         (B, n_dst); row b has n_src_dev[b] knots and n_dst_dev[b] targets of its own, ends held at its own first and last frame,
-        0 after its targets."""
+        0 after its targets.
+        `keyed` = (key (B,) int32, div_by_key (n,) fp64, scale_by_key (n,) fp32), device tensors: a ragged batch whose row b
+        takes div and scale from entry key[b] of the two tables (`div` and `scale` are then not read; pass None)."""
         if (n_src_dev is None) != (n_dst_dev is None):
             raise ValueError("retime_f0: a ragged batch needs both n_src_dev and n_dst_dev")
+        if keyed is not None:
+            key, div_tab, scale_tab = keyed
+            if n_src_dev is None or div_tab.dtype != torch.float64 or scale_tab.dtype != torch.float32 or \
+                    div_tab.numel() != scale_tab.numel() or div_tab.numel() < 1:
+                raise ValueError("retime_f0: keyed= needs a ragged batch and tables (n,) fp64 / (n,) fp32")
+            f0 = f0.contiguous().float()
+            B, n_src = f0.shape
+            out = torch.empty(B, int(n_dst), device=f0.device, dtype=torch.float32)
+            self.call("ddsp_retime_f0_keyed", _ptr(f0), B, n_src, _ptr(n_src_dev), float(step_num), _ptr(self._counts_dev(key, B)),
+                      div_tab.numel(), _ptr(div_tab), _ptr(scale_tab), float(step_dst), int(n_dst), _ptr(n_dst_dev), _ptr(out))
+            return out
         steps = (float(step_num), float(div), float(scale), float(step_dst), int(n_dst))
         if n_src_dev is None:
             f0 = f0.reshape(-1).contiguous().float()
@@ -778,6 +797,45 @@ class Context:
         elif B and T:
             self.call("ddsp_resample", _ptr(x), B, T, *rates, _ptr(out))
         return out[0] if flat else out
+
+    def resample_plan(self, pairs, lowpass_filter_width=6):
+        """pairs: up to 13 (orig_freq, new_freq) -> `ResamplePlan`: the tap tables of all of them, built now (the call waits
+        for them) and resident together while the plan lives, outside this context's cache of solo tables.  The plan belongs
+        to the device: any context of it, a captured one included, may run `resample_keyed` with it."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        if not 1 <= len(pairs) <= 13:
+            raise ValueError(f"resample_plan: 1 to 13 rate pairs, got {len(pairs)}")
+        n = len(pairs)
+        h = _vp()
+        self.call("ddsp_resample_keyed_plan", n, (_int * n)(*[a for a, _ in pairs]), (_int * n)(*[b for _, b in pairs]),
+                  int(lowpass_filter_width), ctypes.byref(h))
+        return ResamplePlan(self.lib, h, pairs, int(lowpass_filter_width), self.device)
+
+    def resample_keyed(self, plan, audio, n_dev, key):
+        """audio (B, T) with n_dev[b] samples of its own per row, key (B,) int32 (both device tensors) -> (B, plan.length(T)):
+        row b resampled with pair key[b] of the plan - bit for bit `resample` of that row alone at that pair over its own
+        outputs (a pair of equal rates copies the row), exactly 0 after them."""
+        x = audio.contiguous().float()
+        B, T = x.shape
+        if plan.device != x.device:
+            raise ValueError("resample_keyed: the plan lives on another device")
+        out = torch.empty(B, plan.length(T), device=x.device, dtype=torch.float32)
+        if B and T:
+            self.call("ddsp_resample_keyed", plan.handle, _ptr(x), B, T, _ptr(self._counts_dev(n_dev, B)),
+                      _ptr(self._counts_dev(key, B)), _ptr(out))
+        return out
+
+    def enhancer_keys(self, f0, cut_frames, max_key, request, thresholds):
+        """f0 (S, Fr) -> key (S,) int32 on the device: request[s] >= 0 as it is, -1 the reference's 'auto' rule over the frames
+        from `cut_frames` on, decided against `thresholds` (`key_thresholds(max_key)` on the device); clamped to max_key."""
+        f0 = f0.contiguous().float()
+        S, Fr = f0.shape
+        if thresholds.dtype != torch.float32 or thresholds.numel() != int(max_key) + 1:
+            raise ValueError("enhancer_keys: thresholds holds max_key + 1 fp32 values")
+        key = torch.empty(S, device=f0.device, dtype=torch.int32)
+        self.call("ddsp_enhancer_keys", _ptr(f0), S, Fr, int(cut_frames), int(max_key), _ptr(self._counts_dev(request, S)),
+                  _ptr(thresholds), _ptr(key))
+        return key
 
     # -- SURVEY 8(f) rank 1: NSF-HiFiGAN post-net building blocks --------------------------------
     # Ragged batches (include/ddsp_amd.h, "Ragged batches of the post-net"): `rows=(B, n_dev, scale)` runs a call over B rows
@@ -1214,6 +1272,52 @@ class Context:
         self.call("ddsp_volume_gate", _ptr(signal), _ptr(vol), float(10 ** (float(threshold_db) / 20)), B,
                   vol.shape[1], int(hop))
         return signal
+
+
+class ResamplePlan:
+    """The handle of `Context.resample_plan`: frees the plan's tables with the object (a device synchronisation)."""
+
+    def __init__(self, lib, handle, pairs, lowpass_filter_width, device):
+        self.lib, self.handle, self.pairs, self.lowpass_filter_width, self.device = lib, handle, pairs, lowpass_filter_width, device
+
+    def length(self, T):
+        """Padded output width for inputs of width T: the largest `ddsp_resample_length` over the pairs."""
+        return int(self.lib.ddsp_resample_keyed_length(self.handle, int(T)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.lib.ddsp_resample_keyed_plan_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def key_thresholds(max_key=12):
+    """thr[k], k = 0..max_key: the largest fp32 value <= 2^(k/12), from fp64 (a host computation) -> float32 numpy array.  An
+    fp32 quotient q has ceil(12 log2 q) <= k exactly when q <= thr[k]: 2^(k/12) is irrational except at k = 0 and 12, where it
+    is an fp32 value itself, so no fp32 q lies close enough to it for the fp64 rounding of numpy's log2 to matter."""
+    import numpy as np
+    thr = np.empty(int(max_key) + 1, dtype=np.float32)
+    for k in range(int(max_key) + 1):
+        exact = 2.0 ** (k / 12.0)
+        t = np.float32(exact)
+        thr[k] = t if float(t) <= exact else np.nextafter(t, np.float32(0))
+    return thr
+
+
+def key_from_thresholds(f0_max, thr):
+    """The host form of `ddsp_enhancer_keys`' 'auto' rule for one f0 maximum (what the kernel computes; tests hold it against
+    the reference's numpy expression)."""
+    import numpy as np
+    m = np.float32(f0_max)
+    if not m > 0:
+        return 0
+    q = m / np.float32(760)
+    for k in range(len(thr)):
+        if q <= thr[k]:
+            return k
+    return len(thr) - 1
 
 
 _contexts = {}

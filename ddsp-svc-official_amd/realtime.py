@@ -325,9 +325,19 @@ def bank_sizes(samplerate, block_time, crossfade_time, buffer_num, block_size, m
 
 class StreamBank:
     """S real-time streams of ONE geometry (device rate, block, cross-fade, window) on one GPU, all advanced by one block per
-    call: the chain of `StreamRenderer` (its docstring, steps 1-8 without the enhancer) with every step batched over the
-    streams.  Under `push_audio` steps 1-5 of all rows are ONE linear HIP-graph replay (`graphed.GraphedBank`); then come
-    resampling to the device rate and the batched splice (`ddsp_sola_batch`: every row's own arg-max, buffer and tail).
+    call: the chain of `StreamRenderer` (its docstring, steps 1-8) with every step batched over the streams.  Under
+    `push_audio` steps 1-5 of all rows are ONE linear HIP-graph replay (`graphed.GraphedBank`); then come resampling to the
+    device rate and the batched splice (`ddsp_sola_batch`: every row's own arg-max, buffer and tail).
+
+    With `enhancer=` (an `enhancer.Enhancer`) step 6 runs on all rows too, every row with an adaptive key of its own
+    (`Enhancer.enhance_keyed`): the key - the reference's 'auto' rule, or what `set_enhancer_key` fixed for the slot - is decided
+    on the device from the shifted f0, and it picks the row's working rate inside the kernels, so nothing is read back and
+    a pitch that crosses a key boundary captures nothing anew.  The result is resampled to the device rate on the device
+    lengths and every row's last block + xfade + search + delay samples, counted from the row's OWN end (`gui.py:405-406`), go to
+    the splice.  Under `use_graph` the stage is a second graph (`graphed.GraphedBankEnhancer`) replayed right after the first;
+    `graph_builds` stays 1.  `last_key` (S,) int32 holds the keys of the block and `last_signal` the (S, block + xfade + search +
+    delay) tails.  DIVERGENCE: keys are clamped to `enhancer_max_key` (0..12, default 12 = one octave); the reference's key is
+    unbounded, a bank needs a finite set of working rates.
 
     State, all on the device: `windows` (S, n_in), `sola_buffer` (S, xfade), the speaker mix of every slot `spk_ids` (S, K)
     int32 / `spk_w` (S, K) fp32 with K = `max_mix`, and `pitch` (S,), a factor.  The captured kernels read the three per-slot
@@ -341,12 +351,12 @@ class StreamBank:
     static tensors, valid until the next block).
 
     Idle slots: there is no activity mask.  An idle slot is a slot that is fed zeros; its rows are computed like every other
-    row, and its output is zero through the volume gate.  Not in the bank: the enhancer (its 'auto' key gives rows different
-    working rates), streams of different geometry, skipping idle rows."""
+    row, and its output is zero through the volume gate.  Not in the bank: streams of different geometry, skipping idle rows
+    (DESIGN section 7)."""
 
     def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
-                 f0_dither=True, crepe_ckpt=None, max_mix=4):
+                 f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
@@ -373,8 +383,24 @@ class StreamBank:
             if f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != self.hop_size:
                 raise ValueError(f"StreamBank: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
                                  f"{f0_extractor.hop_size}; this bank's windows are at {samplerate} Hz with hop {self.hop_size}")
-        if self.model_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, self.model_sr, int(samplerate)) < 0:
-            raise ValueError(f"StreamBank: cannot resample {self.model_sr} Hz to {samplerate} Hz")
+        self.enhancer, self.enhancer_max_key, self.enhancer_plan = enhancer, enhancer_max_key, None
+        self.out_sr = output_rate(self.model_sr, enhancer)
+        if enhancer is not None:
+            if isinstance(enhancer_max_key, bool) or not isinstance(enhancer_max_key, int) or not 0 <= enhancer_max_key <= 12:
+                raise ValueError(f"StreamBank: enhancer_max_key must be an int in 0..12, got {enhancer_max_key!r}")
+            request = enhancer.check_key_request(enhancer_adaptive_key, enhancer_max_key, "StreamBank: enhancer_adaptive_key")
+            # (host integers only: the working rate and the lengths of every key; refuses rates the resampler cannot pair)
+            self.enhancer_plan = enhancer.keyed_plan(self.frames * self.block_size, self.frames, self.model_sr, self.block_size,
+                                                     self.silence_front, enhancer_max_key)
+        if self.out_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, self.out_sr, int(samplerate)) < 0:
+            raise ValueError(f"StreamBank: cannot resample {self.out_sr} Hz to {samplerate} Hz")
+        if enhancer is not None:
+            length = hipddsp.load_library().ddsp_resample_length
+            ends = [n if self.out_sr == int(samplerate) else int(length(n, self.out_sr, int(samplerate))) for n in self.enhancer_plan.n_out]
+            self.n_tail = self.block + self.xfade + self.search + self.delay
+            if min(ends) < self.n_tail:
+                raise ValueError(f"StreamBank: the enhancer returns {min(ends)} samples at {samplerate} Hz for some key, the splice "
+                                 f"needs {self.n_tail}")
         if f0_extractor == "crepe":
             from ddsp.vocoder import F0_Extractor
             f0_extractor = F0_Extractor("crepe", samplerate, self.hop_size, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt,
@@ -391,10 +417,15 @@ class StreamBank:
         self.fade_in = torch.sin(torch.pi * torch.arange(0, 1, 1 / self.xfade, device=dev)[:self.xfade] / 2) ** 2
         self.fade_out = 1 - self.fade_in
         self._resampler = None
-        self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = None
+        self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
+        if enhancer is not None:
+            self.enhancer_request = torch.full((self.S,), request, dtype=torch.int32, device=dev)   # -1 = 'auto', per slot
+            self._n_end_by_key = torch.tensor(ends, dtype=torch.int32).to(dev)
+            self._tail_idx = torch.arange(self.n_tail, device=dev)
         self.use_graph = bool(use_graph)
         self.graph = None                # the synthesis graph of `push_block` (a bank without the analysers)
         self.bank_graph = None           # the whole-block graph of `push_audio`
+        self.enhancer_graph = None       # the enhancer stage, replayed right after either of them
         self.graph_builds = 0
         if self.use_graph:
             import graphed
@@ -404,6 +435,10 @@ class StreamBank:
                     self.silence_front, self.pitch, self.threshold_db, self.spk_ids, self.spk_w, f0_dither=self.f0_dither)
             else:
                 self.graph = graphed.GraphedSynth(self.model, self.S, self.frames, spk_mix_rows=(self.spk_ids, self.spk_w))
+            if enhancer is not None:
+                self.enhancer_graph = graphed.GraphedBankEnhancer(
+                    enhancer, self.enhancer_plan, self.S, self.enhancer_request, self.model_sr, self.block_size, self.samplerate,
+                    self._n_end_by_key, self._tail_idx)
             self.graph_builds = 1
 
     def _slot(self, slot):
@@ -434,6 +469,15 @@ class StreamBank:
         slot = self._slot(slot)
         self.pitch[slot:slot + 1].fill_(2 ** (float(semitones) / 12))
 
+    def set_enhancer_key(self, slot, key):
+        """Slot `slot` is enhanced with the adaptive key `key` (a whole number in 0..enhancer_max_key) or by the 'auto' rule from
+        the next block on: one write to that slot's row of the device request table, no capture."""
+        slot = self._slot(slot)
+        if self.enhancer is None:
+            raise ValueError("StreamBank.set_enhancer_key: this bank was built without enhancer=")
+        request = self.enhancer.check_key_request(key, self.enhancer_max_key, "StreamBank.set_enhancer_key: key")
+        self.enhancer_request[slot:slot + 1].fill_(request)
+
     def reset(self, slot):
         """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (speaker and pitch stay as set)."""
         slot = self._slot(slot)
@@ -454,10 +498,26 @@ class StreamBank:
             self._resampler = Resample(self.model_sr, int(self.samplerate), lowpass_filter_width=128)
         return self._resampler(audio)
 
-    def _splice(self, sig):
-        """Steps 7-8 over the rows: (S, Fr * block_size) at the model's rate -> (S, block) samples to play."""
+    def _enhanced_tail(self, sig, f0, rand_ini):
+        """Steps 6-7 with the enhancer: -> every row's own tail (S, block + xfade + search + delay) at the device rate."""
+        if self.enhancer_graph is not None:
+            tail, self.last_key = self.enhancer_graph(sig, f0, rand_ini)
+            return tail
+        import graphed
+        if rand_ini is None:
+            rand_ini = torch.rand(self.S, 9, device=self.device)
+        tail, self.last_key = graphed.bank_enhancer_chain(
+            hipddsp.context_for(self.device), self.enhancer, self.enhancer_plan, sig, f0, self.enhancer_request,
+            rand_ini.to(self.device), self.model_sr, self.block_size, self.samplerate, self._n_end_by_key, self._tail_idx)
+        return tail
+
+    def _splice(self, sig, f0=None, rand_ini=None):
+        """Steps 6-8 over the rows: (S, Fr * block_size) at the model's rate -> (S, block) samples to play."""
         ctx = hipddsp.context_for(self.device)
-        sig = self._to_device_rate(sig).contiguous()
+        if self.enhancer is not None:
+            sig = self._enhanced_tail(sig, f0, rand_ini).contiguous()
+        else:
+            sig = self._to_device_rate(sig).contiguous()
         self.last_signal = sig
         kept = self.sola_buffer.clone() if self.use_phase_vocoder else None
         emitted, shift = ctx.sola(sig, self.sola_buffer, self.block, self.xfade, self.search, self.delay)
@@ -470,9 +530,10 @@ class StreamBank:
         return emitted
 
     @torch.no_grad()
-    def push_audio(self, blocks, noise=None):
+    def push_audio(self, blocks, noise=None, rand_ini=None):
         """blocks (S, block) raw samples at the device rate, one block per stream -> (S, block) samples to play.  `noise`
-        (S, Fr * block_size) in [0, 1) replaces the fresh draw (parity tests)."""
+        (S, Fr * block_size) in [0, 1) replaces the fresh draw and `rand_ini` (9,) or (S, 9) the enhancer's source phases
+        (parity tests)."""
         if self.f0_extractor is None:
             raise ValueError("StreamBank: push_audio needs units_encoder= and f0_extractor= at construction")
         blocks = self._blocks(blocks)
@@ -485,10 +546,10 @@ class StreamBank:
                 self.samplerate, self.hop_size, self.silence_front, self.pitch, self.threshold_db, self.hop, self.spk_ids,
                 self.spk_w, noise, self.f0_dither)
         self.last_f0, self.last_units, self.last_volume = f0, units, volume
-        return self._splice(sig)
+        return self._splice(sig, f0, rand_ini)
 
     @torch.no_grad()
-    def push_block(self, blocks, units, f0, noise=None):
+    def push_block(self, blocks, units, f0, noise=None, rand_ini=None):
         """The analysis-free form: blocks (S, block), and `units` (S, Fr, C) and `f0` (S, Fr, 1) of the CURRENT windows from the
         caller (before the pitch factor, which is applied here) -> (S, block) samples to play."""
         blocks = self._blocks(blocks)
@@ -510,4 +571,4 @@ class StreamBank:
             sig = self.model(units, f0, volume, None, spk_mix_rows=(self.spk_ids, self.spk_w), **kw)[0]
         ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
         self.last_f0, self.last_units, self.last_volume = f0, units, volume
-        return self._splice(sig)
+        return self._splice(sig, f0, rand_ini)

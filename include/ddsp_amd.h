@@ -370,6 +370,22 @@ int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, 
 int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
                           double step_num, double div, float scale, double step_dst, int64_t n_dst, const int32_t* n_dst_rows,
                           float* out);
+/* ddsp_retime_f0_ragged with the (div, scale) of row b taken from two DEVICE tables of n_keys entries by the row's key,
+ * key[b] (a DEVICE array of B int32, clamped into 0..n_keys-1 before it indexes anything): per row what
+ * ddsp_retime_f0_ragged gives with div_by_key[key[b]] (fp64) and scale_by_key[key[b]] (fp32). */
+int ddsp_retime_f0_keyed(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
+                         double step_num, const int32_t* key, int n_keys, const double* div_by_key, const float* scale_by_key,
+                         double step_dst, int64_t n_dst, const int32_t* n_dst_rows, float* out);
+
+/* the adaptive key of `Enhancer.enhance` (enhancer.py:34-38) for S rows, decided on the device: f0 (S, Fr) -> key (S) int32 in
+ * [0, max_key], 0 <= max_key <= 12.  request (S) int32: -1 = 'auto', k >= 0 = that key (clamped to max_key).  'auto': with
+ * f0max the highest f0 of the row's frames from cut_frames on and q = fl32(f0max / 760) (an IEEE fp32 division), the first k
+ * with q <= thresholds[k], max_key when there is none, 0 when f0max <= 0.  thresholds: DEVICE array of max_key + 1 fp32, the
+ * largest fp32 value <= 2^(k/12) each (the caller rounds them from fp64): the comparison decides ceil(12 log2 q) <= k exactly
+ * as the reference's numpy expression does, without a device log2.  DIVERGENCE: the reference has no max_key (its key is
+ * unbounded); a keyed batch needs a finite set of working rates, so keys above max_key are clamped to it. */
+int ddsp_enhancer_keys(ddsp_ctx* ctx, void* stream, const float* f0, int64_t S, int64_t Fr, int64_t cut_frames, int max_key,
+                       const int32_t* request, const float* thresholds, int32_t* key);
 
 /* ---- sample-rate conversion ------------------------------------------------------ */
 /* replaces `torchaudio.transforms.Resample(orig_freq, new_freq, lowpass_filter_width)` as the reference uses it (gui.py:399-404,
@@ -384,6 +400,26 @@ int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_
  * first ddsp_resample_length(n_samples[b], ...) outputs are those of the row resampled alone; the outputs after them are 0. */
 int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples,
                          int orig_freq, int new_freq, int lowpass_filter_width, float* out);
+/* Keyed batches: one launch in which row b is resampled with the rate pair key[b] of a set of up to 13 pairs with one lowpass
+ * width (the enhancer's working rates, one per adaptive key).
+ * ddsp_resample_keyed_plan builds the set: the tap tables of all its pairs, the ones ddsp_resample builds for each pair, in
+ *   one allocation owned by the plan.  They are ready when the call returns (it waits for the stream), stay resident
+ *   together until ddsp_resample_keyed_plan_destroy, and are outside the context's cache of solo tables, which can neither
+ *   evict them nor be filled by them.  A plan belongs to the context's DEVICE, not to the context: any context of that
+ *   device may run it, a captured one included (build the plan before the capture).  A pair with orig == new copies the row.
+ * ddsp_resample_keyed_length: the padded output width for inputs of width T, the largest ddsp_resample_length over the pairs.
+ * ddsp_resample_keyed: x (B, T), n_samples and key DEVICE arrays of B int32 -> out (B, ddsp_resample_keyed_length(plan, T)).
+ *   With k = key[b] clamped into the set (before it indexes anything), the row's first
+ *   ddsp_resample_length(n_samples[b], orig[k], new[k]) outputs are bit for bit those of ddsp_resample of that row alone at
+ *   that pair (same taps, same kernel body, same summation order) and every output after them is 0; x past n_samples[b] is
+ *   never read into arithmetic.  The grid and the LDS are sized for the largest pair; the pair is uniform per workgroup. */
+typedef struct ddsp_resample_plan ddsp_resample_plan;
+int ddsp_resample_keyed_plan(ddsp_ctx* ctx, void* stream, int n_pairs, const int* orig_freq, const int* new_freq,
+                             int lowpass_filter_width, ddsp_resample_plan** plan);
+void ddsp_resample_keyed_plan_destroy(ddsp_resample_plan* plan);
+int64_t ddsp_resample_keyed_length(const ddsp_resample_plan* plan, int64_t T);
+int ddsp_resample_keyed(ddsp_ctx* ctx, void* stream, const ddsp_resample_plan* plan, const float* x, int64_t B, int64_t T,
+                        const int32_t* n_samples, const int32_t* key, float* out);
 
 /* ---- the NSF-HiFiGAN post-net (enhancer.py:24-101, nsf_hifigan/models.py:106-276, nvSTFT.py:65-119) ---- */
 /* One utterance per call, or - the `_ragged` entry points at the end of this section - a padded batch of rows of different

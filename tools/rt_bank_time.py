@@ -13,7 +13,13 @@ THIS tree, `solo` the package of `--baseline-tree`.  The legs alternate `--repea
 (bank, solo, bank, solo, ...), every process under its own `timeout`; a leg that ends abnormally ends the session.  Every
 repeat is written out; nothing is averaged away.
 
-    python tools/rt_bank_time.py --baseline-tree <parent checkout> [--blocks 200] [--warmup 10] [--out profiles/rt_bank_time.json]"""
+`--enhancer` puts the NSF-HiFiGAN enhancer at the shipped generator geometry (seeded random weights, as tools/rt_chain.py builds
+it) with `enhancer_adaptive_key='auto'` into both legs, for the `config5` timing only: the bank runs it as its captured keyed
+stage, every solo renderer eagerly with its one read-back per block.  The solo leg needs nothing the parent commit lacks, so
+`--baseline-tree` may then be left out (both legs import this tree).
+
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> [--blocks 200] [--warmup 10] [--out profiles/rt_bank_time.json]
+    python tools/rt_bank_time.py --enhancer [--out profiles/rt_bank_enhancer_time.json]"""
 import argparse
 import contextlib
 import json
@@ -30,7 +36,11 @@ DEVICE_SR = 48000
 TONES = (147.0, 220.0, 330.0, 196.0)
 
 
-def leg(which, tree, blocks, warmup):
+SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16, 4, 4, 4], upsample_initial_channel=512,
+                   num_mels=128, hop_size=512, n_fft=2048, win_size=2048)
+
+
+def leg(which, tree, blocks, warmup, with_enhancer=False):
     """One leg in this process: `which` = 'bank' | 'solo', the package taken from `tree`.  Prints one JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -55,10 +65,23 @@ def leg(which, tree, blocks, warmup):
         path = os.path.join(tmp, "hubert-soft.pt")
         torch.save(HC.fill({k: tuple(v.shape) for k, v in HubertSoft().state_dict().items()}), path)
         encoder = Units_Encoder("hubertsoft", path, device=dev)
+        enh = None
+        if with_enhancer:
+            import glue_cases as GC
+            from enhancer import Enhancer
+            cfg = dict(GC.NSF_CONFIG, **SHIPPED_NSF)
+            with open(os.path.join(tmp, "config.json"), "w") as fh:
+                json.dump(cfg, fh)
+            torch.save({"generator": GC.nsf_state_dict(cfg, seed=91)}, os.path.join(tmp, "model"))
+            enh = Enhancer("nsf-hifigan", os.path.join(tmp, "model"), device=dev)
     for shape, (block_time, xfade_time, buffer_num) in SHAPES.items():
+        if with_enhancer and shape != "config5":
+            continue
         for S in STREAMS:
             kw = dict(buffer_num=buffer_num, threshold_db=-60.0, use_graph=True, units_encoder=encoder, f0_extractor="crepe",
                       crepe_ckpt=crepe)
+            if with_enhancer:
+                kw.update(enhancer=enh, enhancer_adaptive_key="auto")
             with contextlib.redirect_stdout(sys.stderr):
                 if which == "bank":
                     bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
@@ -84,7 +107,7 @@ def leg(which, tree, blocks, warmup):
                 if i >= warmup:
                     times.append((time.perf_counter() - t0) * 1e3)
             ts = np.array(times)
-            print(json.dumps({"leg": which, "shape": shape, "streams": S, "block_ms": block_time * 1e3, "frames": frames,
+            print(json.dumps({"leg": which, "shape": shape, "streams": S, "enhancer": bool(with_enhancer), "block_ms": block_time * 1e3, "frames": frames,
                               "mean_ms": float(ts.mean()), "p99_ms": float(np.percentile(ts, 99)), "blocks": len(ts),
                               "device": torch.cuda.get_device_name(0)}), flush=True)
             del push
@@ -103,11 +126,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds one leg's process may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rt_bank_time.json"))
+    ap.add_argument("--enhancer", action="store_true", help="both legs with the NSF-HiFiGAN enhancer, key 'auto' (config5 only)")
     ap.add_argument("--leg", default=None, choices=["bank", "solo"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
-        return leg(a.leg, a.tree, a.blocks, a.warmup)
+        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer)
+    if a.enhancer and not a.baseline_tree:
+        a.baseline_tree = ROOT
     if not a.baseline_tree or not os.path.isdir(os.path.join(a.baseline_tree, "ddsp-svc-official_amd")):
         raise SystemExit("rt_bank_time: --baseline-tree must be a checkout of the parent commit (with ddsp-svc-official_amd/)")
     trees = {"bank": ROOT, "solo": os.path.abspath(a.baseline_tree)}
@@ -115,7 +141,7 @@ def main():
     for rep in range(a.repeats):
         for which in ("bank", "solo"):
             cmd = ["timeout", "-k", "10", str(a.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", which, "--tree",
-                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)]
+                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)] + (["--enhancer"] if a.enhancer else [])
             p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
             if p.returncode != 0:   # a fault, an abort or the time limit: nothing more is started on the device
                 raise SystemExit(f"rt_bank_time: leg {which} of repeat {rep} ended with status {p.returncode}; stopping")
@@ -126,7 +152,7 @@ def main():
                     print(json.dumps(row), flush=True)
     # per case: every repeat's mean, the spread of each leg between its repeats, the S-fold solo time against the bank
     cases = []
-    for shape in SHAPES:
+    for shape in (["config5"] if a.enhancer else SHAPES):
         for S in STREAMS:
             pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
             bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
@@ -135,7 +161,7 @@ def main():
                           "solo_p99_ms": pick("solo", "p99_ms"), "bank_spread_ms": max(bm) - min(bm),
                           "solo_spread_ms": max(sm) - min(sm), "bank_median_ms": med(bm), "solo_median_ms": med(sm),
                           "solo_over_bank": med(sm) / med(bm)})
-    out = {"device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
+    out = {"enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
            "what": "ms per block period for all S streams: bank = one StreamBank.push_audio; solo = S StreamRenderer.push_audio "
                    "of the baseline tree one after the other", "cases": cases, "rows": repeats}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
