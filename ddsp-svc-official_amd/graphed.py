@@ -1,31 +1,39 @@
-"""HIP-graph replay of a synthesiser's inference forward for one fixed (batch, frames) shape.
+"""HIP-graph replay of the real-time forwards for one fixed shape: the synthesiser alone (`GraphedSynth`), the whole block from
+the raw audio on (`GraphedBlock`) and the enhancer stage of a bank (`GraphedBankEnhancer`).
 
 The real-time caller (`gui.py:360-430`: one 0.2 s block at a time, B = 1, 87 frames) is launch-bound: ~50 kernels of
-a few microseconds each, paced by Python + ctypes + hipLaunch on the host.  `GraphedSynth` captures the whole
-`model(...)` call once (`torch.cuda.graph`: stream capture also records the kernels libddsp_amd launches on that
-stream) and replays it with one host call per block.
+a few microseconds each, paced by Python + ctypes + hipLaunch on the host.  A capture records the whole call once
+(`torch.cuda.graph`: stream capture also records the kernels libddsp_amd launches on that stream) and replays it with one
+host call per block.
 
-What makes the capture safe:
-  * the model's library calls go through a `hipddsp.Context` of their own (`hipddsp.use_context`): the captured kernels
-    point into THAT context's scratch arena, tables and zero page, which are sized by eager warm-up runs before the
-    capture and frozen afterwards (`Context.freeze`) - no later eager call can regrow or reuse them;
-  * the noise excitation comes from a static device tensor that is refilled before every replay (the eager path draws
-    a host seed per call, which a graph would freeze);
+What makes the capture safe is one protocol, `_Captured._capture`, that all three classes go through; its ORDER is the rule:
+  1. the captured library calls go through a `hipddsp.Context` of their own (`hipddsp.use_context`): the captured kernels
+     point into THAT context's scratch arena, tables and zero page;
+  2. those are sized by eager warm-up runs of `_run()` on a side stream (after a `wait_stream` on the caller's, and waited for
+     and synchronised afterwards): first-use allocations, tap tables and the analysis networks' prepared weights happen here;
+  3. `_run()` is captured, on one stream (a linear graph);
+  4. the context is frozen (`Context.freeze`): no later eager call can regrow or reuse what the graph points into;
+  5. caller tensors that `_run()` changes in place (the window(s)) are cloned before step 2 and copied back after step 4, so a
+     re-capture in the middle of a stream keeps the stream; only then is a dither seed drawn.
+Further rules:
+  * random inputs (the noise excitation, the enhancer's source phases) come from static device tensors that are refilled
+    before every replay (`_refill`; the eager path draws a host seed per call, which a graph would freeze);
   * inputs are copied into static tensors, outputs are static tensors valid until the next replay.
 Weights are read by the captured kernels at replay time (the weight-preparation kernel is part of the graph), so
 in-place weight updates are honoured.  `spk_mix_dict` ({speaker id: weight}) is captured with the graph: its ids and
-weights become kernel arguments, so a capture is valid for that mix only (a new mix needs a new `GraphedSynth`;
+weights become kernel arguments, so a capture is valid for that mix only (a new mix needs a new capture;
 `realtime.StreamRenderer.set_speaker` does that), while `spk_id` stays a static input.  With `spk_mix_rows=True` (or a K) the
 speaker term is a mix per row held in two static device tables, `mix_ids` (B, K) int32 and `mix_w` (B, K) fp32
 (`forward(..., spk_mix_rows=)`): the captured kernels read them at replay time, so any row's speaker or mix changes by a write to
 its table row, without a new capture.  `initial_phase` is a host-side argument and not supported here.  Forward only.
 
 `GraphedBlock` captures the real-time block from the raw audio on (`block_chain`: window push, volume, f0 extractor, pitch
-shift, units encoder, synthesiser, volume gate) under the same rules, on one stream (a linear graph).  `GraphedBank` is the same
-chain over S windows of one geometry (`bank_chain`), with the speaker mix and the pitch factor of every row as device data.  Three networks then
-share the captured context; each has a prepared-weight slot of its own in it.  The control network's weights are prepared
-inside the graph on every replay (in-place updates are honoured, as above); the two analysis networks (HuBERT-Soft, CREPE:
-inference only) are prepared once by the warm-up runs and the captured kernels read those copies
+shift, units encoder, synthesiser, volume gate) under the same rules.  It takes one window (n_in,) - the solo kernels, a host
+pitch factor, `spk_id` static and `spk_mix_dict` captured (`realtime.StreamRenderer`) - or S windows (S, n_in) of one geometry -
+the batch kernels, with the speaker mix and the pitch factor of every row as device data (`realtime.StreamBank`).  Three
+networks then share the captured context; each has a prepared-weight slot of its own in it.  The control network's weights are
+prepared inside the graph on every replay (in-place updates are honoured, as above); the two analysis networks (HuBERT-Soft,
+CREPE: inference only) are prepared once by the warm-up runs and the captured kernels read those copies
 (`ddsp_weight_slot_take(..., keep_in_capture)`), so a change of THEIR weights needs a new capture.  The CREPE dither seed lives
 in a device word that the decode advances (`ddsp_crepe_decode_dseed`): a seed passed by value would be frozen by the capture.
 
@@ -39,7 +47,40 @@ import torch
 import hipddsp
 
 
-class GraphedSynth:
+class _Captured:
+    """The capture protocol of the module docstring.  A subclass builds its static tensors, then calls `_capture`, which
+    leaves `self.ctx` and `self.graph` and returns what the captured `_run()` returned (the static outputs)."""
+
+    def _capture(self, dev, warmup, keep=()):
+        """`keep`: the caller's tensors that `_run()` changes in place; they are left as they were found."""
+        self.ctx = hipddsp.Context(dev)
+        kept = [t.clone() for t in keep]
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
+            for _ in range(max(1, warmup)):   # arena, tap tables and the analysis networks' prepared weights: here, eagerly
+                self._run()
+        cur.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
+            out = self._run()
+        self.ctx.freeze()
+        for t, k in zip(keep, kept):
+            t.copy_(k)
+        return out
+
+
+def _refill(static, value):
+    """A static random input before a replay: a fresh uniform draw, or the caller's `value` (parity tests)."""
+    if value is None:
+        static.uniform_()
+    else:
+        static.copy_(value)
+
+
+class GraphedSynth(_Captured):
     def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None):
         """`spk_mix_rows`: None / False; True (K = 4 slots per row) or a K for static mix tables of the graph's own; or the
         caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses."""
@@ -76,19 +117,7 @@ class GraphedSynth:
             self.mix_w = torch.zeros(B, K, device=dev) if K else None
             if K:
                 self.mix_w[:, 0] = 1.0
-        self.ctx = hipddsp.Context(dev)
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
-            for _ in range(max(1, warmup)):          # first-use allocations (arena, tables) happen here, eagerly
-                self._run()
-        cur.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
-            self.out = self._run()
-        self.ctx.freeze()
+        self.out = self._capture(dev, warmup)
 
     def _run(self):
         if self.mix_ids is not None:
@@ -108,164 +137,88 @@ class GraphedSynth:
         self.volume.copy_(volume.reshape(self.volume.shape))
         if spk_id is not None:
             self.spk_id.copy_(spk_id.expand_as(self.spk_id) if spk_id.shape[0] == 1 else spk_id.reshape(self.spk_id.shape))
-        if noise is None:
-            self.noise.uniform_()
-        else:
-            self.noise.copy_(noise)
+        _refill(self.noise, noise)
         self.graph.replay()
         return self.out
 
 
-def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, samplerate, hop_size, silence_front, pitch_factor,
-                threshold_db, block_size, spk_id, spk_mix_dict=None, noise=None, f0_dither=True, seed_dev=None):
+def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, samplerate, hop_size, silence_front, pitch,
+                threshold_db, block_size, speaker, noise=None, f0_dither=True, seed_dev=None):
     """One block of the reference's callback from the raw audio to the gated model output (gui.py:373-374 and
-    `gui.SvcDDSP.infer`, gui.py:87-127), every step on the device, nothing read back:
-    `window` (n_in,) takes `block_in` in place, then volume, f0 (uv_interp, silent front), the pitch shift, units, the
-    synthesiser and the gate.  -> (signal (1, Fr * block_size), f0 (1, Fr, 1) after the shift, units (1, Fr, C), volume (1, Fr))."""
+    `gui.SvcDDSP.infer`, gui.py:87-127), every step on the device, nothing read back: `window` takes `block_in` in place,
+    then volume, f0 (uv_interp, silent front), the pitch shift, units, the synthesiser and the gate.
+    One stream: `window` (n_in,), `block_in` (block,), `pitch` a host factor (no multiply at exactly 1).  S streams of one
+    geometry: `window` (S, n_in), `block_in` (S, block), `pitch` a device (S,) tensor of factors; every step is then one batched
+    call.  The window keeps the rank it comes with down to the library, so each form reaches its own kernels.
+    `speaker`: the speaker term as the model's keyword arguments, {"spk_id": (1, 1) int64, "spk_mix_dict": dict or None} or
+    {"spk_id": None, "spk_mix_rows": (ids (S, K) int32, w (S, K) fp32)}.
+    -> (signal (rows, Fr * block_size), f0 (rows, Fr, 1) after the shift, units (rows, Fr, C), volume (rows, Fr)), rows = 1 or S."""
     ctx.stream_push_(window, block_in)
-    volume = ctx.volume_extract(window[None], hop_size)
+    audio = window if window.dim() == 2 else window[None]
+    volume = ctx.volume_extract(audio, hop_size)
     f0 = f0_extractor.extract(window, uv_interp=True, silence_front=silence_front, dither=f0_dither, seed_dev=seed_dev)
-    f0 = f0[None, :, None]
-    if pitch_factor != 1:
-        f0 = f0 * pitch_factor
-    units = units_encoder.encode(window[None], samplerate, hop_size)
+    f0 = f0.reshape(-1, f0.shape[-1])[:, :, None]
+    if isinstance(pitch, torch.Tensor):
+        f0 = f0 * pitch[:, None, None]
+    elif pitch != 1:
+        f0 = f0 * pitch
+    units = units_encoder.encode(audio, samplerate, hop_size)
     kw = {} if noise is None else {"noise": noise}
-    sig = model(units, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, **kw)[0]
+    sig = model(units, f0, volume, **speaker, **kw)[0]
     ctx.volume_gate_(sig, volume, threshold_db, block_size)          # (`block_size`: the model's, as a host int - no read-back)
     return sig, f0, units, volume
 
 
-class GraphedBlock:
-    """`block_chain` for one fixed (window length, device rate, hop) as one HIP graph.  `window` is the caller's tensor: the
-    graph shifts it in place at its fixed address, and the warm-up runs leave its contents as they found them (a re-capture
-    in the middle of a stream keeps the stream).  Static inputs: `block_in`, `spk_id`, `noise`, `seed`; static outputs
-    (valid until the next replay): `sig`, `f0`, `units`, `volume`."""
+class GraphedBlock(_Captured):
+    """`block_chain` for one fixed (window length, device rate, hop) as one linear HIP graph, over one window (n_in,) or S
+    windows (S, n_in).  `window` is the caller's tensor: the graph shifts it in place at its fixed address, and the capture
+    leaves its contents as it found them.  With `mix_rows=(mix_ids, mix_w)` these tables and a device `pitch` (S,) are the
+    caller's too (`realtime.StreamBank`'s state): the graph reads them at their fixed addresses, so a write to a row between two
+    replays is all a speaker, mix or pitch change takes.  Without it the speaker is the static input `spk_id` and the captured
+    `spk_mix_dict`, and `pitch` a host factor.  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
+    next replay): `sig`, `f0`, `units`, `volume`."""
 
-    def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch_factor,
-                 threshold_db, spk_mix_dict=None, f0_dither=True, warmup=3):
+    def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch,
+                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3):
+        if mix_rows is not None and spk_mix_dict is not None:
+            raise ValueError("GraphedBlock: mix_rows and spk_mix_dict are mutually exclusive")
         p = next(model.parameters())
-        if not p.is_cuda or window.device != p.device:
-            raise RuntimeError("GraphedBlock needs the model and the window on one HIP device (no CPU fallback)")
+        state = [window, *(mix_rows or ())] + ([pitch] if isinstance(pitch, torch.Tensor) else [])
+        if not p.is_cuda or any(t.device != p.device for t in state):
+            raise RuntimeError("GraphedBlock needs the model and the caller's tensors on one HIP device (no CPU fallback)")
         self.model = model.eval()
         self.device = dev = p.device
-        self.units_encoder, self.f0_extractor, self.window = units_encoder, f0_extractor, window
-        self.args = (samplerate, hop_size, silence_front, pitch_factor, float(threshold_db))
-        self.spk_mix_dict = None if spk_mix_dict is None else dict(spk_mix_dict)
-        self.f0_dither = bool(f0_dither)
-        frames = int(window.numel() // hop_size) + 1
-        self.block_size = int(model.block_size)
-        self.block_in = torch.zeros(int(block), device=dev)
-        self.spk_id = torch.ones(1, 1, dtype=torch.int64, device=dev)
-        self.noise = torch.rand(1, frames * self.block_size, device=dev)
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.ctx = hipddsp.Context(dev)
-        kept = window.clone()
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
-            for _ in range(max(1, warmup)):   # arena, tap tables and the analysis networks' prepared weights: here, eagerly
-                self._run()
-        cur.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
-            self.sig, self.f0, self.units, self.volume = self._run()
-        self.ctx.freeze()
-        window.copy_(kept)
-        self.seed.random_(0, 2 ** 62)
-
-    def _run(self):
-        samplerate, hop_size, silence_front, pitch_factor, threshold_db = self.args
-        return block_chain(self.ctx, self.model, self.units_encoder, self.f0_extractor, self.window, self.block_in, samplerate,
-                           hop_size, silence_front, pitch_factor, threshold_db, self.block_size, self.spk_id, self.spk_mix_dict,
-                           self.noise, self.f0_dither, self.seed)
-
-    @torch.no_grad()
-    def __call__(self, block_in, spk_id, noise=None):
-        """block_in (block,) -> (sig, f0, units, volume) of the window after it took the block (static tensors)."""
-        self.block_in.copy_(block_in.reshape(self.block_in.shape))
-        self.spk_id.copy_(spk_id.reshape(self.spk_id.shape))
-        if noise is None:
-            self.noise.uniform_()
-        else:
-            self.noise.copy_(noise)
-        self.graph.replay()
-        return self.sig, self.f0, self.units, self.volume
-
-
-def bank_chain(ctx, model, units_encoder, f0_extractor, windows, blocks, samplerate, hop_size, silence_front, pitch, threshold_db,
-               block_size, mix_ids, mix_w, noise=None, f0_dither=True, seed_dev=None):
-    """`block_chain` over S streams of one geometry, every step one batched call on the device, nothing read back:
-    `windows` (S, n_in) take `blocks` (S, block) in place, then volume, f0 (uv_interp, silent front), the per-row pitch factor
-    `pitch` (S,) applied as f0 * pitch[:, None, None], units, the synthesiser with the row mixes `mix_ids` / `mix_w` (S, K), and
-    the gate.  -> (signal (S, Fr * block_size), f0 (S, Fr, 1) after the shift, units (S, Fr, C), volume (S, Fr))."""
-    ctx.stream_push_(windows, blocks)
-    volume = ctx.volume_extract(windows, hop_size)
-    f0 = f0_extractor.extract(windows, uv_interp=True, silence_front=silence_front, dither=f0_dither, seed_dev=seed_dev)
-    f0 = f0[:, :, None] * pitch[:, None, None]
-    units = units_encoder.encode(windows, samplerate, hop_size)
-    kw = {} if noise is None else {"noise": noise}
-    sig = model(units, f0, volume, None, spk_mix_rows=(mix_ids, mix_w), **kw)[0]
-    ctx.volume_gate_(sig, volume, threshold_db, block_size)
-    return sig, f0, units, volume
-
-
-class GraphedBank:
-    """`bank_chain` for S windows of one fixed (window length, device rate, hop) as one linear HIP graph.  `windows`, `pitch`,
-    `mix_ids` and `mix_w` are the caller's tensors (`realtime.StreamBank`'s state): the graph reads and shifts them at their
-    fixed addresses, so a write to a row between two replays is all a speaker, mix or pitch change takes.  The warm-up runs
-    leave the windows as they found them.  Static inputs: `blocks`, `noise`, `seed`; static outputs (valid until the next
-    replay): `sig`, `f0`, `units`, `volume`."""
-
-    def __init__(self, model, units_encoder, f0_extractor, windows, block, samplerate, hop_size, silence_front, pitch,
-                 threshold_db, mix_ids, mix_w, f0_dither=True, warmup=3):
-        p = next(model.parameters())
-        if not p.is_cuda or any(t.device != p.device for t in (windows, pitch, mix_ids, mix_w)):
-            raise RuntimeError("GraphedBank needs the model and the bank's state on one HIP device (no CPU fallback)")
-        self.model = model.eval()
-        self.device = dev = p.device
-        self.units_encoder, self.f0_extractor = units_encoder, f0_extractor
-        self.windows, self.pitch, self.mix_ids, self.mix_w = windows, pitch, mix_ids, mix_w
+        self.units_encoder, self.f0_extractor, self.window, self.pitch = units_encoder, f0_extractor, window, pitch
         self.args = (samplerate, hop_size, silence_front, float(threshold_db))
         self.f0_dither = bool(f0_dither)
-        S = windows.shape[0]
-        frames = int(windows.shape[1] // hop_size) + 1
+        rows = window.shape[:-1]                                     # () or (S,)
+        frames = int(window.shape[-1] // hop_size) + 1
         self.block_size = int(model.block_size)
-        self.blocks = torch.zeros(S, int(block), device=dev)
-        self.noise = torch.rand(S, frames * self.block_size, device=dev)
+        self.block_in = torch.zeros(*rows, int(block), device=dev)
+        self.spk_id = torch.ones(1, 1, dtype=torch.int64, device=dev) if mix_rows is None else None
+        if mix_rows is None:
+            self.speaker = {"spk_id": self.spk_id, "spk_mix_dict": None if spk_mix_dict is None else dict(spk_mix_dict)}
+        else:
+            self.speaker = {"spk_id": None, "spk_mix_rows": tuple(mix_rows)}
+        self.noise = torch.rand(*(rows or (1,)), frames * self.block_size, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.ctx = hipddsp.Context(dev)
-        kept = windows.clone()
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
-            for _ in range(max(1, warmup)):   # arena, tap tables and the analysis networks' prepared weights: here, eagerly
-                self._run()
-        cur.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
-            self.sig, self.f0, self.units, self.volume = self._run()
-        self.ctx.freeze()
-        windows.copy_(kept)
+        self.sig, self.f0, self.units, self.volume = self._capture(dev, warmup, keep=[window])
         self.seed.random_(0, 2 ** 62)
 
     def _run(self):
         samplerate, hop_size, silence_front, threshold_db = self.args
-        return bank_chain(self.ctx, self.model, self.units_encoder, self.f0_extractor, self.windows, self.blocks, samplerate,
-                          hop_size, silence_front, self.pitch, threshold_db, self.block_size, self.mix_ids, self.mix_w,
-                          self.noise, self.f0_dither, self.seed)
+        return block_chain(self.ctx, self.model, self.units_encoder, self.f0_extractor, self.window, self.block_in, samplerate,
+                           hop_size, silence_front, self.pitch, threshold_db, self.block_size, self.speaker, self.noise,
+                           self.f0_dither, self.seed)
 
     @torch.no_grad()
-    def __call__(self, blocks, noise=None):
-        """blocks (S, block) -> (sig, f0, units, volume) of the windows after they took the blocks (static tensors)."""
-        self.blocks.copy_(blocks.reshape(self.blocks.shape))
-        if noise is None:
-            self.noise.uniform_()
-        else:
-            self.noise.copy_(noise)
+    def __call__(self, block_in, spk_id=None, noise=None):
+        """block_in (block,) or (S, block) -> (sig, f0, units, volume) of the window(s) after they took it (static tensors).
+        `spk_id` (1, 1): the solo form's speaker; the row form reads the caller's tables."""
+        self.block_in.copy_(block_in.reshape(self.block_in.shape))
+        if self.spk_id is not None:
+            self.spk_id.copy_(spk_id.reshape(self.spk_id.shape))
+        _refill(self.noise, noise)
         self.graph.replay()
         return self.sig, self.f0, self.units, self.volume
 
@@ -285,7 +238,7 @@ def bank_enhancer_chain(ctx, enhancer, plan, sig, f0, request, rand_ini, model_s
     return out.gather(1, idx), key
 
 
-class GraphedBankEnhancer:
+class GraphedBankEnhancer(_Captured):
     """`bank_enhancer_chain` for S rows of one geometry as one linear HIP graph.  `request` is the caller's tensor (the bank's
     table of key requests, read at its fixed address).  Static inputs: `sig`, `f0`, `rand_ini` (S, 9), refilled before every
     replay; static outputs (valid until the next replay): `tail`, `key`.  The plan's tap tables and device tables are built by
@@ -300,19 +253,7 @@ class GraphedBankEnhancer:
         self.sig = torch.zeros(S, plan.T, device=dev)
         self.f0 = torch.full((S, plan.Fr, 1), 220.0, device=dev)
         self.rand_ini = torch.rand(S, 9, device=dev)
-        self.ctx = hipddsp.Context(dev)
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side), hipddsp.use_context(self.ctx), torch.no_grad():
-            for _ in range(max(1, warmup)):
-                self._run()
-        cur.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
-            self.tail, self.key = self._run()
-        self.ctx.freeze()
+        self.tail, self.key = self._capture(dev, warmup)
 
     def _run(self):
         model_sr, block_size, samplerate, n_end_by_key, tail_idx = self.args
@@ -324,9 +265,6 @@ class GraphedBankEnhancer:
         """sig (S, Fr * block_size), f0 (S, Fr, 1) -> (tail, key) (static tensors)."""
         self.sig.copy_(sig.reshape(self.sig.shape))
         self.f0.copy_(f0.reshape(self.f0.shape))
-        if rand_ini is None:
-            self.rand_ini.uniform_()
-        else:
-            self.rand_ini.copy_(rand_ini.reshape(-1, 9).expand_as(self.rand_ini))
+        _refill(self.rand_ini, None if rand_ini is None else rand_ini.reshape(-1, 9).expand_as(self.rand_ini))
         self.graph.replay()
         return self.tail, self.key

@@ -1,7 +1,7 @@
 """The splice half of the reference's real-time callback (`gui.py:373-430`) around the device path: sliding input
 window bookkeeping is the caller's (PortAudio), the SOLA search + sin^2 cross-fade + tail hand-over run as two
 kernels on the stream's own GPU with no host synchronisation.  One `Splicer` per stream (eight
-independent streams = eight replicas, no collective)."""
+independent streams = eight replicas, no collective), or one `Splicer(rows=S)` for the S streams of a `StreamBank`."""
 import numpy as np
 import torch
 
@@ -9,11 +9,16 @@ import hipddsp
 
 
 # ---- the size and key arithmetic of the reference's callback that does not touch audio ------------------------------------
+def splice_sizes(samplerate, block_time, crossfade_time, search_time=0.01, delay_time=0.02):
+    """(block, xfade, search, delay) in samples at the device rate, truncated as the reference does (`gui.py:319-322`): the
+    one place that turns the callback's times into sample counts."""
+    return tuple(int(t * samplerate) for t in (block_time, crossfade_time, search_time, delay_time))
+
+
 def input_frames(samplerate, block_time, crossfade_time, buffer_num, search_time=0.01, delay_time=0.02):
-    """Length of the sliding input window at the device rate (`gui.py:319-325`)."""
-    block = int(block_time * samplerate)
-    return max(block + int(crossfade_time * samplerate) + int(search_time * samplerate) + 2 * int(delay_time * samplerate),
-               (1 + buffer_num) * block)
+    """Length of the sliding input window at the device rate (`gui.py:323-325`)."""
+    block, xfade, search, delay = splice_sizes(samplerate, block_time, crossfade_time, search_time, delay_time)
+    return max(block + xfade + search + 2 * delay, (1 + buffer_num) * block)
 
 
 def hop_size(block_size, samplerate, model_sr):
@@ -46,6 +51,16 @@ def auto_key(f0_max):
         return int(max(0, np.ceil(12 * np.log2(float(np.float32(f0_max) / np.float32(760))))))
 
 
+def bank_sizes(samplerate, block_time, crossfade_time, buffer_num, block_size, model_sr, search_time=0.01, delay_time=0.02):
+    """The sizes `StreamRenderer` and `StreamBank` work with (gui.py:319-326): a dict of block, xfade, search, delay, n_in
+    (samples at the device rate), hop_size (float), frames and silence_front (seconds)."""
+    block, xfade, search, delay = splice_sizes(samplerate, block_time, crossfade_time, search_time, delay_time)
+    n_in = input_frames(samplerate, block_time, crossfade_time, buffer_num, search_time, delay_time)
+    hop = hop_size(block_size, samplerate, model_sr)
+    return {"block": block, "xfade": xfade, "search": search, "delay": delay, "n_in": n_in, "hop_size": hop,
+            "frames": window_frames(n_in, hop), "silence_front": silence_front(block_time, buffer_num, crossfade_time)}
+
+
 def output_rate(model_sr, enhancer=None):
     """Rate of what the chain hands to the splice before any resampling: the enhancer's when one is chained
     (`Enhancer.enhance` returns audio at its own rate), otherwise the model's."""
@@ -57,18 +72,58 @@ def phase_vocoder(a, b, fade_out, fade_in):
     return hipddsp.context_for(a.device).phase_vocoder(a, b, fade_out, fade_in)
 
 
+def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop):
+    """The analysis front end of `push_audio` as `name` (a class) is given it: both or neither; `f0_extractor` may be the
+    shorthand "crepe", which `_crepe` builds once every refusal is made."""
+    if (units_encoder is None) != (f0_extractor is None):
+        raise ValueError(f"{name}: push_audio needs both units_encoder and f0_extractor (or neither)")
+    if f0_extractor is None:
+        return
+    crepe = f0_extractor == "crepe"
+    if not ((crepe or hasattr(f0_extractor, "extract")) and hasattr(units_encoder, "encode")):
+        raise ValueError(f"{name}: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
+    if not crepe and (f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != hop):
+        raise ValueError(f"{name}: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
+                         f"{f0_extractor.hop_size}; {window} at {samplerate} Hz with hop {hop}")
+
+
+def _crepe(f0_extractor, samplerate, hop, f0_min, f0_max, crepe_ckpt, device):
+    """gui.py:81-82,93-99: a crepe extractor with these bounds at the device rate and the window's hop, for the shorthand."""
+    if f0_extractor != "crepe":
+        return f0_extractor
+    from ddsp.vocoder import F0_Extractor
+    return F0_Extractor("crepe", samplerate, hop, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt, device=device)
+
+
+def _check_resample(name, out_sr, samplerate):
+    if out_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, out_sr, int(samplerate)) < 0:
+        raise ValueError(f"{name}: cannot resample {out_sr} Hz to {samplerate} Hz")
+
+
+def _to_device_rate(resamplers, audio, rate, samplerate):
+    """`audio` (B, T) at `rate` -> at the device rate; `resamplers` ({(from, to): Resample}) is the caller's cache, filled on
+    first use."""
+    if rate == int(samplerate):
+        return audio
+    pair = (int(rate), int(samplerate))
+    if pair not in resamplers:
+        from resample import Resample
+        resamplers[pair] = Resample(pair[0], pair[1], lowpass_filter_width=128)
+    return resamplers[pair](audio)
+
+
 class Splicer:
     def __init__(self, samplerate, block_time, crossfade_time, device, search_time=0.01, delay_time=0.02,
-                 use_phase_vocoder=False):
-        """Sizes as the reference derives them (`gui.py:319-322`)."""
-        self.block = int(block_time * samplerate)
-        self.xfade = int(crossfade_time * samplerate)
-        self.search = int(search_time * samplerate)
-        self.delay = int(delay_time * samplerate)
+                 use_phase_vocoder=False, rows=None):
+        """Sizes as the reference derives them (`gui.py:319-322`).  `rows`: None for one stream, or S for S streams of this
+        geometry spliced by one batched call, every row with its own buffer and shift."""
+        self.block, self.xfade, self.search, self.delay = splice_sizes(samplerate, block_time, crossfade_time, search_time,
+                                                                       delay_time)
         self.device = torch.device(device)
-        self.buffer = torch.zeros(self.xfade, device=self.device)      # `sola_buffer`, gui.py:347
+        shape = (self.xfade,) if rows is None else (int(rows), self.xfade)
+        self.buffer = torch.zeros(shape, device=self.device)           # `sola_buffer`, gui.py:347
         self.last_shift = None
-        # gui.py:349-351 windows, used by the optional phase-vocoder splice (gui.py:417-423)
+        # gui.py:349-351 windows, used by the optional phase-vocoder splice (gui.py:417-423); all rows share them
         self.use_phase_vocoder = bool(use_phase_vocoder)
         self.fade_in = torch.sin(torch.pi * torch.arange(0, 1, 1 / self.xfade, device=self.device)[:self.xfade] / 2) ** 2
         self.fade_out = 1 - self.fade_in
@@ -79,22 +134,19 @@ class Splicer:
         splicer: each thread gets its own scratch arena)."""
         return hipddsp.context_for(self.device)
 
-    def input_frames(self, buffer_num):
-        """Length of the sliding input window (`gui.py:323-325`)."""
-        return max(self.block + self.xfade + self.search + 2 * self.delay, (1 + buffer_num) * self.block)
-
     def push(self, audio):
-        """audio (N,) model output for the current window -> (block,) samples to play (mono; the reference
-        duplicates them to two channels on the host, `gui.py:430`)."""
+        """audio (N,) model output for the current window -> (block,) samples to play (mono; the reference duplicates them
+        to two channels on the host, `gui.py:430`); with `rows`, (rows, N) -> (rows, block)."""
         kept = self.buffer.clone() if self.use_phase_vocoder else None
         emitted, shift = self.ctx.sola(audio, self.buffer, self.block, self.xfade, self.search, self.delay)
         self.last_shift = shift
         if self.use_phase_vocoder:
-            # head of the new block at the SOLA shift (the shift stays on the device: indexed gather, no host sync)
-            start = audio.numel() - self.block - self.xfade - self.search - self.delay
-            idx = start + shift.to(torch.int64) + torch.arange(self.xfade, device=self.device)
-            head = audio.reshape(-1).index_select(0, idx)
-            emitted[:self.xfade] = self.ctx.phase_vocoder(kept, head, self.fade_out, self.fade_in)
+            # every row's head at its own SOLA shift (the shifts stay on the device: a gather, no host sync)
+            n = audio.shape[-1]
+            start = n - self.block - self.xfade - self.search - self.delay
+            idx = start + shift.to(torch.int64)[:, None] + torch.arange(self.xfade, device=self.device)[None, :]
+            head = audio.reshape(-1, n).gather(1, idx).reshape(kept.shape)
+            emitted[..., :self.xfade] = self.ctx.phase_vocoder(kept, head, self.fade_out, self.fade_in)
         return emitted
 
 
@@ -113,7 +165,7 @@ class StreamRenderer:
          extractors and encoders).  f0 is shifted by `pitch_adjust` semitones (gui.py:102);
       4. the synthesiser forward (gui.py:125-126) with `spk_id` or `spk_mix_dict`, eager or replayed from a HIP graph
          captured for the current mix: `graphed.GraphedSynth` under `push_block`; under `push_audio` steps 1-5 are ONE graph
-         (`graphed.GraphedBlock`), replayed with one host call per block;
+         (`graphed.GraphedBlock` over the one window), replayed with one host call per block;
       5. `output *= mask` with the 9-frame dilated volume gate at the model's `block_size` (gui.py:107-112,127) ->
          `ddsp_volume_gate`, in place;
       6. optionally `enhancer.enhance(...)` (gui.py:128-134), eager, with the adaptive key decided here (see below);
@@ -136,40 +188,26 @@ class StreamRenderer:
         self.model_sr = int(model.sampling_rate)
         self.samplerate = samplerate
         self.hop = self.block_size                                   # the model's hop: gate, synthesis
-        self.hop_size = hop_size(self.block_size, samplerate, self.model_sr)   # the window's analysis hop
         self.threshold_db = float(threshold_db)
         self.pitch_adjust = float(pitch_adjust)
         self.splicer = Splicer(samplerate, block_time, crossfade_time, self.device, use_phase_vocoder=use_phase_vocoder)
-        self.block = self.splicer.block
-        self.n_in = self.splicer.input_frames(buffer_num)
-        self.frames = window_frames(self.n_in, self.hop_size)       # frames of the window (f0 / units / volume alike)
+        z = bank_sizes(samplerate, block_time, crossfade_time, buffer_num, self.block_size, self.model_sr)
+        self.block, self.n_in, self.silence_front = z["block"], z["n_in"], z["silence_front"]
+        self.hop_size, self.frames = z["hop_size"], z["frames"]    # the window's analysis hop; frames of f0 / units / volume alike
         self.window = torch.zeros(self.n_in, device=self.device)   # `self.input_wav`, gui.py:346
-        self.silence_front = silence_front(block_time, buffer_num, crossfade_time)
         if isinstance(enhancer_adaptive_key, str) and enhancer_adaptive_key != "auto":
             raise ValueError(f"enhancer_adaptive_key must be a number or 'auto', got {enhancer_adaptive_key!r}")
         self.enhancer = enhancer
         self.enhancer_adaptive_key = enhancer_adaptive_key
         self.last_key = None                                         # the key the last block was enhanced with
         self.out_sr = output_rate(self.model_sr, enhancer)
-        if self.out_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, self.out_sr, int(samplerate)) < 0:
-            raise ValueError(f"StreamRenderer: cannot resample {self.out_sr} Hz to {samplerate} Hz")
+        _check_resample("StreamRenderer", self.out_sr, samplerate)
         self._resamplers = {}
         self.spk_id = torch.full((1, 1), int(spk_id), dtype=torch.int64, device=self.device)
         self.spk_mix_dict = self._checked_mix(spk_mix_dict)
         self.features = features
-        # the analysis front end of `push_audio` (gui.py:81-82,93-99: a crepe extractor with these bounds at the device rate)
-        if f0_extractor == "crepe":
-            from ddsp.vocoder import F0_Extractor
-            f0_extractor = F0_Extractor("crepe", samplerate, self.hop_size, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt,
-                                        device=self.device)
-        if (units_encoder is None) != (f0_extractor is None):
-            raise ValueError("StreamRenderer: push_audio needs both units_encoder and f0_extractor (or neither)")
-        if f0_extractor is not None:
-            if not (hasattr(f0_extractor, "extract") and hasattr(units_encoder, "encode")):
-                raise ValueError("StreamRenderer: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
-            if f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != self.hop_size:
-                raise ValueError(f"StreamRenderer: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
-                                 f"{f0_extractor.hop_size}; this renderer's window is at {samplerate} Hz with hop {self.hop_size}")
+        _check_analysers("StreamRenderer", "this renderer's window is", units_encoder, f0_extractor, samplerate, self.hop_size)
+        f0_extractor = _crepe(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
         self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
         self.last_f0 = self.last_units = self.last_volume = None
         self.use_graph = bool(use_graph)
@@ -228,15 +266,6 @@ class StreamRenderer:
         cut = key_cut_frames(self.silence_front, self.model_sr, self.block_size)
         return auto_key(float(torch.max(f0[:, cut:])))
 
-    def _to_device_rate(self, audio, rate):
-        if rate == int(self.samplerate):
-            return audio
-        pair = (int(rate), int(self.samplerate))
-        if pair not in self._resamplers:
-            from resample import Resample
-            self._resamplers[pair] = Resample(pair[0], pair[1], lowpass_filter_width=128)
-        return self._resamplers[pair](audio)
-
     @torch.no_grad()
     def push_block(self, block_in, units=None, f0=None, noise=None, rand_ini=None):
         """block_in (block,) device samples of the stream -> (block,) samples to play.  `units` (1, Fr, C) and `f0`
@@ -282,7 +311,7 @@ class StreamRenderer:
             sig, rate = self.enhancer.enhance(sig, self.model_sr, f0, self.block_size, adaptive_key=key,
                                               silence_front=self.silence_front, rand_ini=rand_ini)
             self.last_key = key
-        return self.splicer.push(self._to_device_rate(sig, rate)[0])
+        return self.splicer.push(_to_device_rate(self._resamplers, sig, rate, self.samplerate)[0])
 
     @torch.no_grad()
     def push_audio(self, block_in, noise=None, rand_ini=None):
@@ -301,7 +330,7 @@ class StreamRenderer:
             sig, f0, units, volume = graphed.block_chain(
                 hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, self.window, block_in,
                 self.samplerate, self.hop_size, self.silence_front, self._pitch_factor(), self.threshold_db, self.hop,
-                self.spk_id, self.spk_mix_dict, noise, self.f0_dither)
+                {"spk_id": self.spk_id, "spk_mix_dict": self.spk_mix_dict}, noise, self.f0_dither)
         self.last_f0, self.last_units, self.last_volume = f0, units, volume
         rate = self.model_sr
         if self.enhancer is not None:
@@ -309,25 +338,15 @@ class StreamRenderer:
             sig, rate = self.enhancer.enhance(sig, self.model_sr, f0, self.block_size, adaptive_key=key,
                                               silence_front=self.silence_front, rand_ini=rand_ini)
             self.last_key = key
-        return self.splicer.push(self._to_device_rate(sig, rate)[0])
-
-
-def bank_sizes(samplerate, block_time, crossfade_time, buffer_num, block_size, model_sr, search_time=0.01, delay_time=0.02):
-    """The sizes a `StreamBank` works with, derived as `Splicer` and `StreamRenderer` derive them (gui.py:319-326): a dict of
-    block, xfade, search, delay, n_in (samples at the device rate), hop_size (float), frames and silence_front (seconds)."""
-    block, xfade = int(block_time * samplerate), int(crossfade_time * samplerate)
-    search, delay = int(search_time * samplerate), int(delay_time * samplerate)
-    n_in = max(block + xfade + search + 2 * delay, (1 + buffer_num) * block)
-    hop = hop_size(block_size, samplerate, model_sr)
-    return {"block": block, "xfade": xfade, "search": search, "delay": delay, "n_in": n_in, "hop_size": hop,
-            "frames": window_frames(n_in, hop), "silence_front": silence_front(block_time, buffer_num, crossfade_time)}
+        return self.splicer.push(_to_device_rate(self._resamplers, sig, rate, self.samplerate)[0])
 
 
 class StreamBank:
     """S real-time streams of ONE geometry (device rate, block, cross-fade, window) on one GPU, all advanced by one block per
     call: the chain of `StreamRenderer` (its docstring, steps 1-8) with every step batched over the streams.  Under
-    `push_audio` steps 1-5 of all rows are ONE linear HIP-graph replay (`graphed.GraphedBank`); then come resampling to the
-    device rate and the batched splice (`ddsp_sola_batch`: every row's own arg-max, buffer and tail).
+    `push_audio` steps 1-5 of all rows are ONE linear HIP-graph replay (`graphed.GraphedBlock` over the S windows); then come
+    resampling to the device rate and the batched splice (a `Splicer(rows=S)` -> `ddsp_sola_batch`: every row's own arg-max,
+    buffer and tail).
 
     With `enhancer=` (an `enhancer.Enhancer`) step 6 runs on all rows too, every row with an adaptive key of its own
     (`Enhancer.enhance_keyed`): the key - the reference's 'auto' rule, or what `set_enhancer_key` fixed for the slot - is decided
@@ -375,14 +394,7 @@ class StreamBank:
         self.block, self.xfade, self.search, self.delay = z["block"], z["xfade"], z["search"], z["delay"]
         self.n_in, self.hop_size, self.frames, self.silence_front = z["n_in"], z["hop_size"], z["frames"], z["silence_front"]
         self.threshold_db = float(threshold_db)
-        if (units_encoder is None) != (f0_extractor is None):
-            raise ValueError("StreamBank: push_audio needs both units_encoder and f0_extractor (or neither)")
-        if f0_extractor is not None and f0_extractor != "crepe":
-            if not (hasattr(f0_extractor, "extract") and hasattr(units_encoder, "encode")):
-                raise ValueError("StreamBank: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
-            if f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != self.hop_size:
-                raise ValueError(f"StreamBank: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
-                                 f"{f0_extractor.hop_size}; this bank's windows are at {samplerate} Hz with hop {self.hop_size}")
+        _check_analysers("StreamBank", "this bank's windows are", units_encoder, f0_extractor, samplerate, self.hop_size)
         self.enhancer, self.enhancer_max_key, self.enhancer_plan = enhancer, enhancer_max_key, None
         self.out_sr = output_rate(self.model_sr, enhancer)
         if enhancer is not None:
@@ -392,8 +404,7 @@ class StreamBank:
             # (host integers only: the working rate and the lengths of every key; refuses rates the resampler cannot pair)
             self.enhancer_plan = enhancer.keyed_plan(self.frames * self.block_size, self.frames, self.model_sr, self.block_size,
                                                      self.silence_front, enhancer_max_key)
-        if self.out_sr != int(samplerate) and hipddsp.load_library().ddsp_resample_length(1, self.out_sr, int(samplerate)) < 0:
-            raise ValueError(f"StreamBank: cannot resample {self.out_sr} Hz to {samplerate} Hz")
+        _check_resample("StreamBank", self.out_sr, samplerate)
         if enhancer is not None:
             length = hipddsp.load_library().ddsp_resample_length
             ends = [n if self.out_sr == int(samplerate) else int(length(n, self.out_sr, int(samplerate))) for n in self.enhancer_plan.n_out]
@@ -401,22 +412,17 @@ class StreamBank:
             if min(ends) < self.n_tail:
                 raise ValueError(f"StreamBank: the enhancer returns {min(ends)} samples at {samplerate} Hz for some key, the splice "
                                  f"needs {self.n_tail}")
-        if f0_extractor == "crepe":
-            from ddsp.vocoder import F0_Extractor
-            f0_extractor = F0_Extractor("crepe", samplerate, self.hop_size, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt,
-                                        device=self.device)
+        f0_extractor = _crepe(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
         self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
         dev = self.device
         self.windows = torch.zeros(self.S, self.n_in, device=dev)
-        self.sola_buffer = torch.zeros(self.S, self.xfade, device=dev)
+        self.splicer = Splicer(samplerate, block_time, crossfade_time, dev, use_phase_vocoder=use_phase_vocoder, rows=self.S)
+        self.sola_buffer = self.splicer.buffer                       # (S, xfade): the very tensor the splice updates
         self.spk_ids = torch.ones(self.S, self.max_mix, dtype=torch.int32, device=dev)   # every slot starts as speaker 1
         self.spk_w = torch.zeros(self.S, self.max_mix, device=dev)
         self.spk_w[:, 0] = 1.0
         self.pitch = torch.ones(self.S, device=dev)
-        self.use_phase_vocoder = bool(use_phase_vocoder)
-        self.fade_in = torch.sin(torch.pi * torch.arange(0, 1, 1 / self.xfade, device=dev)[:self.xfade] / 2) ** 2
-        self.fade_out = 1 - self.fade_in
-        self._resampler = None
+        self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
         if enhancer is not None:
             self.enhancer_request = torch.full((self.S,), request, dtype=torch.int32, device=dev)   # -1 = 'auto', per slot
@@ -430,9 +436,10 @@ class StreamBank:
         if self.use_graph:
             import graphed
             if self.f0_extractor is not None:
-                self.bank_graph = graphed.GraphedBank(
+                self.bank_graph = graphed.GraphedBlock(
                     self.model, self.units_encoder, self.f0_extractor, self.windows, self.block, self.samplerate, self.hop_size,
-                    self.silence_front, self.pitch, self.threshold_db, self.spk_ids, self.spk_w, f0_dither=self.f0_dither)
+                    self.silence_front, self.pitch, self.threshold_db, mix_rows=(self.spk_ids, self.spk_w),
+                    f0_dither=self.f0_dither)
             else:
                 self.graph = graphed.GraphedSynth(self.model, self.S, self.frames, spk_mix_rows=(self.spk_ids, self.spk_w))
             if enhancer is not None:
@@ -490,14 +497,6 @@ class StreamBank:
             raise ValueError(f"StreamBank: a call takes blocks of shape (S, block) = {(self.S, self.block)}, got {got}")
         return blocks.to(self.device, torch.float32).contiguous()
 
-    def _to_device_rate(self, audio):
-        if self.model_sr == int(self.samplerate):
-            return audio
-        if self._resampler is None:
-            from resample import Resample
-            self._resampler = Resample(self.model_sr, int(self.samplerate), lowpass_filter_width=128)
-        return self._resampler(audio)
-
     def _enhanced_tail(self, sig, f0, rand_ini):
         """Steps 6-7 with the enhancer: -> every row's own tail (S, block + xfade + search + delay) at the device rate."""
         if self.enhancer_graph is not None:
@@ -513,20 +512,13 @@ class StreamBank:
 
     def _splice(self, sig, f0=None, rand_ini=None):
         """Steps 6-8 over the rows: (S, Fr * block_size) at the model's rate -> (S, block) samples to play."""
-        ctx = hipddsp.context_for(self.device)
         if self.enhancer is not None:
             sig = self._enhanced_tail(sig, f0, rand_ini).contiguous()
         else:
-            sig = self._to_device_rate(sig).contiguous()
+            sig = _to_device_rate(self._resamplers, sig, self.model_sr, self.samplerate).contiguous()
         self.last_signal = sig
-        kept = self.sola_buffer.clone() if self.use_phase_vocoder else None
-        emitted, shift = ctx.sola(sig, self.sola_buffer, self.block, self.xfade, self.search, self.delay)
-        self.last_shift = shift
-        if self.use_phase_vocoder:
-            # every row's head at its own SOLA shift (the shifts stay on the device: a gather, no host sync)
-            start = sig.shape[1] - self.block - self.xfade - self.search - self.delay
-            idx = start + shift.to(torch.int64)[:, None] + torch.arange(self.xfade, device=self.device)[None, :]
-            emitted[:, :self.xfade] = ctx.phase_vocoder(kept, sig.gather(1, idx), self.fade_out, self.fade_in)
+        emitted = self.splicer.push(sig)
+        self.last_shift = self.splicer.last_shift
         return emitted
 
     @torch.no_grad()
@@ -541,10 +533,10 @@ class StreamBank:
             sig, f0, units, volume = self.bank_graph(blocks, noise=noise)
         else:
             import graphed
-            sig, f0, units, volume = graphed.bank_chain(
+            sig, f0, units, volume = graphed.block_chain(
                 hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, self.windows, blocks,
-                self.samplerate, self.hop_size, self.silence_front, self.pitch, self.threshold_db, self.hop, self.spk_ids,
-                self.spk_w, noise, self.f0_dither)
+                self.samplerate, self.hop_size, self.silence_front, self.pitch, self.threshold_db, self.hop,
+                {"spk_id": None, "spk_mix_rows": (self.spk_ids, self.spk_w)}, noise, self.f0_dither)
         self.last_f0, self.last_units, self.last_volume = f0, units, volume
         return self._splice(sig, f0, rand_ini)
 

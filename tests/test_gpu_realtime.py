@@ -194,7 +194,7 @@ def test_splicer_against_reference_callback(dev, lib_path, use_pv):
     block, xfade, search, delay, n_in = [int(v) for v in z["sizes"]]
     sp = realtime.Splicer(GC.GUI_SR, GC.GUI_BLOCK_TIME, GC.GUI_XFADE_TIME, dev, use_phase_vocoder=use_pv)
     assert (sp.block, sp.xfade, sp.search, sp.delay) == (block, xfade, search, delay)
-    assert sp.input_frames(GC.GUI_BUFFER_NUM) == n_in
+    assert realtime.input_frames(GC.GUI_SR, GC.GUI_BLOCK_TIME, GC.GUI_XFADE_TIME, GC.GUI_BUFFER_NUM) == n_in
     tag = "pv" if use_pv else "plain"
     for k in range(GC.GUI_BLOCKS):
         emitted = sp.push(GC.gui_model_output(k).to(dev))
@@ -206,6 +206,35 @@ def test_splicer_against_reference_callback(dev, lib_path, use_pv):
         else:
             assert (e - torch.from_numpy(z["out_plain"][k])).abs().max() < 2e-6, k
     assert (sp.buffer.cpu() - torch.from_numpy(z[f"buffer_{tag}"])).abs().max() < 1e-6
+
+
+@pytest.mark.parametrize("use_pv", [False, True])
+def test_splicer_rows_equal_solo_splicers(dev, lib_path, use_pv):
+    """`Splicer(rows=3)` against three solo `Splicer`s over 4 pushes: the emitted block, the shift and the buffer of every row
+    are the solo ones bit for bit, with and without the phase vocoder.  16 kHz, 0.02 s blocks, 0.01 s cross-fade: block 320,
+    xfade 160, search 160, delay 320; rows of 1200 samples are longer than the 960 the splice reads, so it starts past 0."""
+    import realtime
+    sr, rows, N = 16000, 3, 1200
+    bank = realtime.Splicer(sr, 0.02, 0.01, dev, use_phase_vocoder=use_pv, rows=rows)
+    solo = [realtime.Splicer(sr, 0.02, 0.01, dev, use_phase_vocoder=use_pv) for _ in range(rows)]
+    assert (bank.block, bank.xfade, bank.search, bank.delay) == (320, 160, 160, 320) and bank.buffer.shape == (rows, 160)
+    rng = np.random.Generator(np.random.PCG64(29))
+    tones = ((131.0, 392.0), (185.0, 277.0), (233.0, 523.0))
+    shifts_differ = False
+    for k in range(4):
+        t = (np.arange(N) + k * bank.block + rng.integers(-80, 80, (rows, 1))) / sr     # every row drifts on its own
+        audio = np.stack([0.3 * np.sin(2 * np.pi * a * t[s]) + 0.2 * np.sin(2 * np.pi * b * t[s]) + 0.01 * rng.standard_normal(N)
+                          for s, (a, b) in enumerate(tones)])
+        audio = torch.from_numpy(audio.astype(np.float32)).to(dev)
+        emitted = bank.push(audio)
+        assert emitted.shape == (rows, bank.block) and bank.last_shift.shape == (rows,)
+        for s, sp in enumerate(solo):
+            e = sp.push(audio[s])
+            assert torch.equal(emitted[s], e), (k, s)
+            assert int(bank.last_shift[s]) == int(sp.last_shift), (k, s)
+            assert torch.equal(bank.buffer[s], sp.buffer), (k, s)
+        shifts_differ |= len(set(bank.last_shift.tolist())) == rows
+    assert shifts_differ
 
 
 def test_gate_against_reference_infer(ctx, dev):

@@ -18,7 +18,8 @@ it) with `enhancer_adaptive_key='auto'` into both legs, for the `config5` timing
 stage, every solo renderer eagerly with its one read-back per block.  The solo leg needs nothing the parent commit lacks, so
 `--baseline-tree` may then be left out (both legs import this tree).
 
-    python tools/rt_bank_time.py --baseline-tree <parent checkout> [--blocks 200] [--warmup 10] [--out profiles/rt_bank_time.json]
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> [--blocks 200] [--warmup 10] [--shapes config5]
+                                 [--out profiles/rt_bank_time.json]
     python tools/rt_bank_time.py --enhancer [--out profiles/rt_bank_enhancer_time.json]"""
 import argparse
 import contextlib
@@ -40,7 +41,7 @@ SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16
                    num_mels=128, hop_size=512, n_fft=2048, win_size=2048)
 
 
-def leg(which, tree, blocks, warmup, with_enhancer=False):
+def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES)):
     """One leg in this process: `which` = 'bank' | 'solo', the package taken from `tree`.  Prints one JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -75,7 +76,7 @@ def leg(which, tree, blocks, warmup, with_enhancer=False):
             torch.save({"generator": GC.nsf_state_dict(cfg, seed=91)}, os.path.join(tmp, "model"))
             enh = Enhancer("nsf-hifigan", os.path.join(tmp, "model"), device=dev)
     for shape, (block_time, xfade_time, buffer_num) in SHAPES.items():
-        if with_enhancer and shape != "config5":
+        if shape not in shapes or (with_enhancer and shape != "config5"):
             continue
         for S in STREAMS:
             kw = dict(buffer_num=buffer_num, threshold_db=-60.0, use_graph=True, units_encoder=encoder, f0_extractor="crepe",
@@ -127,11 +128,12 @@ def main():
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds one leg's process may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rt_bank_time.json"))
     ap.add_argument("--enhancer", action="store_true", help="both legs with the NSF-HiFiGAN enhancer, key 'auto' (config5 only)")
+    ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES), help="the timings to run (default: both)")
     ap.add_argument("--leg", default=None, choices=["bank", "solo"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
-        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer)
+        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer, a.shapes)
     if a.enhancer and not a.baseline_tree:
         a.baseline_tree = ROOT
     if not a.baseline_tree or not os.path.isdir(os.path.join(a.baseline_tree, "ddsp-svc-official_amd")):
@@ -141,7 +143,7 @@ def main():
     for rep in range(a.repeats):
         for which in ("bank", "solo"):
             cmd = ["timeout", "-k", "10", str(a.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", which, "--tree",
-                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)] + (["--enhancer"] if a.enhancer else [])
+                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)] + (["--enhancer"] if a.enhancer else []) + ["--shapes", *a.shapes]
             p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
             if p.returncode != 0:   # a fault, an abort or the time limit: nothing more is started on the device
                 raise SystemExit(f"rt_bank_time: leg {which} of repeat {rep} ended with status {p.returncode}; stopping")
@@ -152,7 +154,7 @@ def main():
                     print(json.dumps(row), flush=True)
     # per case: every repeat's mean, the spread of each leg between its repeats, the S-fold solo time against the bank
     cases = []
-    for shape in (["config5"] if a.enhancer else SHAPES):
+    for shape in (["config5"] if a.enhancer else a.shapes):
         for S in STREAMS:
             pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
             bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
