@@ -228,23 +228,39 @@ class Unit2Control(nn.Module):
         n_frames[b] rows of ctrl[b] are what the network gives for that row alone at its own length, whatever the padding of
         the inputs holds; the rows after them carry no meaning.  Inference only."""
         if n_frames is not None:
-            vals = hipddsp.check_n_frames(n_frames, units.shape[0], units.shape[1])
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                raise NotImplementedError("n_frames= (ragged batches) is inference only: there is no ragged backward pass; call "
-                                          "the network under torch.no_grad()")
+            vals = self.check_ragged(n_frames, units.shape[0], units.shape[1], "the network under torch.no_grad()")
             ctx = hipddsp.context_for(units.device)
-            n_dev = ctx.ragged_counts(vals)
-            B, Fr = units.shape[0], units.shape[1]
-            # the padding is replaced by selection before anything reads it (the chunked causal attention, for one, multiplies
-            # a whole 16-frame tile before it masks: a NaN there would not stay in its own frame)
-            return self.forward_ragged(ctx, ctx.ragged_frames(units, n_dev, hold=False),
-                                       ctx.ragged_frames(f0.reshape(B, Fr), n_dev, hold=True),
-                                       ctx.ragged_frames(phase.reshape(B, Fr), n_dev, hold=False),
-                                       ctx.ragged_frames(volume.reshape(B, Fr), n_dev, hold=False), spk_id, spk_mix_dict,
-                                       n_dev, hold=False, spk_mix_rows=spk_mix_rows)
+            n_dev, units, f0, phase, volume = self.hold_ragged(ctx, vals, units, f0, phase, volume)
+            return self.forward_ragged(ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=False,
+                                       spk_mix_rows=spk_mix_rows)
         ctx = hipddsp.context_for(units.device)
         w, keep = self._weights_struct()
         return ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, mix_dev=spk_mix_rows)
+
+    def wants_grad(self):
+        """True when a call must be recorded for autograd (grad mode on and some parameter wants a gradient)."""
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def check_ragged(self, n_frames, B, Fr, advice):
+        """Head of a ragged call, host half, before anything is launched: `n_frames` as a checked list (ValueError), and the
+        inference-only refusal (NotImplementedError; `advice`: what the caller should call under no_grad instead)."""
+        vals = hipddsp.check_n_frames(n_frames, B, Fr)
+        if self.wants_grad():
+            raise NotImplementedError("n_frames= (ragged batches) is inference only: there is no ragged backward pass; call "
+                                      + advice)
+        return vals
+
+    def hold_ragged(self, ctx, vals, units, f0, phase, volume):
+        """Head of a ragged call, device half: uploads the counts once and puts the frame-rate inputs into held form - units,
+        volume and a given phase (None: the caller scans it from the held f0) 0, f0 its last frame over a row's padding
+        (`csrc/ragged.hip`).  The padding is replaced by selection before anything reads it (the chunked causal attention,
+        for one, multiplies a whole 16-frame tile before it masks: a NaN there would not stay in its own frame).
+        -> (n_dev, units, f0 (B,Fr), phase (B,Fr) | None, volume (B,Fr))."""
+        B, Fr = units.shape[0], units.shape[1]
+        n_dev = ctx.ragged_counts(vals)
+        frames = lambda x, hold: ctx.ragged_frames(x.reshape(B, Fr), n_dev, hold=hold)
+        return (n_dev, ctx.ragged_frames(units, n_dev, hold=False), frames(f0, True),
+                None if phase is None else frames(phase, False), frames(volume, False))
 
     def forward_ragged(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=True, spk_mix_rows=None):
         """The control matrix of a ragged batch whose counts are on the device (`Context.ragged_counts`) and whose units are 0

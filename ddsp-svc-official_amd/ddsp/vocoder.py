@@ -33,10 +33,6 @@ import hipddsp
 from hipddsp import (COMB_SINC, COMB_SINC_GATED, COMB_NONE, EXC_AUDIO, EXC_GENERATE, EXC_UNIT_NOISE, FIR_ALLPASS,
                      FIR_DYNAMIC, FIR_STATIC, FIR_SPLIT_BF16)
 
-# Product arithmetic of the frame-varying FIR in the model forwards, inference and training alike (the adjoint kernels
-# work from the saved inputs in fp32 products): the context's mode (`hipddsp.Context.set_math`, default split-bf16);
-# `ctx.ltv_fir` itself defaults to fp32 products.
-
 from .hubert import RaggedCounts
 from .unit2control import Unit2Control
 
@@ -181,7 +177,6 @@ class F0_Extractor:
         out = ctx.f0_postfilter(f0, pd, sr, hop, n_frames, start_frame, 0.05, uv_interp, self.f0_min)
         out = out[0] if flat else out
         return out.cpu().numpy() if is_np else out
-
 
     def _extract_ragged(self, audio, uv_interp, silence_front, dither, seed, seed_dev, n_samples):
         from .crepe import HOP, SAMPLE_RATE
@@ -369,6 +364,10 @@ def _seed_from_torch():
 
 
 class _SynthBase(torch.nn.Module):
+    """What the three synthesisers share: one `forward` body (`_forward`) and the protocol of the autograd node.  A model
+    states `_comb_mode` / `_front_wants` (the comb the phase scan writes, and `want_phase`: nowhere else) and supplies
+    `_render` (its DSP chain, written once) and `_train_backward` (the chain's adjoint)."""
+
     def __init__(self, sampling_rate, block_size):
         super().__init__()
         self.register_buffer("sampling_rate", torch.tensor(sampling_rate))
@@ -376,48 +375,70 @@ class _SynthBase(torch.nn.Module):
         self._sr = int(sampling_rate)
         self._hop = int(block_size)
 
-    def _front(self, f0_frames, initial_phase, infer, comb_mode, **want):
+    def _context(self, f0_frames, ragged=False):
         if not f0_frames.is_cuda:
             raise RuntimeError("the synthesiser runs on a HIP device only (no CPU fallback): move the model and its "
                                "inputs to 'cuda'")
-        ctx = hipddsp.context_for(f0_frames.device)
-        return ctx, ctx.phase_scan(f0_frames, self._hop, self._sr, initial_phase, bool(infer), comb_mode, **want)
-
-    def _ragged_front(self, units, f0_frames, volume, n_frames, initial_phase, infer, comb_mode, **want):
-        """Head of a ragged forward: checks `n_frames` (ValueError before anything is launched) and uploads it once, puts
-        the frame-rate inputs into held form (units and volume 0, f0 its last frame over a row's padding: `csrc/ragged.hip`)
-        and runs the phase scan on them.  -> (ctx, n_dev, units, f0 (B,Fr,1), volume, phase-scan outputs)."""
-        B, Fr = units.shape[0], units.shape[1]
-        vals = hipddsp.check_n_frames(n_frames, B, Fr)
-        if self._training_graph():
-            raise NotImplementedError("n_frames= (ragged batches) is inference only: there is no ragged backward pass; call the "
-                                      "model under torch.no_grad() (training crops every clip to one length)")
-        if not f0_frames.is_cuda:
-            raise RuntimeError("the synthesiser runs on a HIP device only (no CPU fallback): move the model and its "
-                               "inputs to 'cuda'")
-        if self._hop % 4:
+        if ragged and self._hop % 4:
             raise ValueError("n_frames= needs a block_size that is a multiple of 4")
-        ctx = hipddsp.context_for(f0_frames.device)
-        n_dev = ctx.ragged_counts(vals)
-        units = ctx.ragged_frames(units, n_dev, hold=False)
-        f0 = ctx.ragged_frames(f0_frames.reshape(B, Fr), n_dev, hold=True).reshape(B, Fr, 1)
-        volume = ctx.ragged_frames(volume.reshape(B, Fr), n_dev, hold=False)
-        ps = ctx.phase_scan(f0, self._hop, self._sr, initial_phase, bool(infer), comb_mode, **want)
-        return ctx, n_dev, units, f0, volume, ps
+        return hipddsp.context_for(f0_frames.device)
+
+    def _scan(self, ctx, f0_frames, initial_phase, infer):
+        return ctx.phase_scan(f0_frames, self._hop, self._sr, initial_phase, bool(infer), self._comb_mode,
+                              **self._front_wants)
+
+    def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
+        """The model's DSP chain: fused control matrix (B,Fr,sum) + phase-scan outputs `ps` -> (outputs, saved), for
+        inference, ragged inference and the training forward alike.
+        `excitation()` -> (nz, exc, seed) of the noise branch (`_noise_args` / `_ragged_noise`), called where the chain
+        needs it: the ragged draw is a launch and a (B,T) tensor of its own.  `n_dev`: the counts of a ragged batch whose
+        ctrl and f0 are held over the padding; every signal is then cropped to its row before it enters the next filter.
+        `keep`: `saved` is what `_train_backward` needs (else None, and nothing outlives its last use).
+        Product arithmetic of the frame-varying FIR, inference and training alike (the adjoint kernels work from the saved
+        inputs in fp32 products): the context's mode (`hipddsp.Context.set_math`, default split-bf16), passed as
+        `math=ctx.fir_math`; `ctx.ltv_fir` itself defaults to fp32 products."""
+        raise NotImplementedError
+
+    def _stages(self, ctx, n_dev, Fr, keep):
+        """(crop, saved, save) of a chain: `crop(*signals)` zeroes them past every row's end (ragged) or does nothing;
+        `save(tensors)` appends to `saved` in a training forward and drops them in inference, where an impulse-response
+        matrix - the largest tensors of a forward - is released as soon as the next one replaces it."""
+        crop = (lambda *xs: ctx.ragged_crop_(n_dev, Fr, self._hop, *xs)) if n_dev is not None else (lambda *xs: None)
+        saved = [] if keep else None
+        return crop, saved, (saved.extend if keep else (lambda xs: None))
 
     def _ragged_noise(self, ctx, n_dev, B, Fr, noise, noise_seed):
         """(unit-noise draw (B,T) with 0.5 - no excitation - past every row's end, EXC_UNIT_NOISE, 0)."""
         seed = 0 if noise is not None else (_seed_from_torch() if noise_seed is None else int(noise_seed))
         return ctx.ragged_noise(noise, seed, n_dev, B, Fr, self._hop), EXC_UNIT_NOISE, 0
 
-    def _empty_result(self, f0_frames, sample_rate_phase=False, shared=False):
-        """The (signal, phase, (harmonic, noise)) tuple of an empty batch (nothing is launched)."""
+    @staticmethod
+    def _noise_args(noise, noise_seed):
+        if noise is not None:
+            return noise.contiguous().float(), EXC_UNIT_NOISE, 0
+        return None, EXC_GENERATE, (_seed_from_torch() if noise_seed is None else int(noise_seed))
+
+    def _phase_out(self, ctx, ps, n_dev=None):
+        """The phase a forward returns - sample-rate where the model asks the scan for it (Sins), else frame-rate -, 0 over
+        the padding of a ragged batch."""
+        if self._front_wants.get("want_phase"):
+            if n_dev is not None:
+                ctx.ragged_crop_(n_dev, ps["phase_frames"].shape[1], self._hop, ps["phase"])
+            return ps["phase"]
+        pf = ps["phase_frames"]
+        return pf if n_dev is None else ctx.ragged_frames(pf, n_dev, hold=False, out=pf)
+
+    @staticmethod
+    def _result(phase, outs):
+        """(signal, phase (..., 1), (harmonic, noise)); a chain with one output (CombSubFast) returns it three times."""
+        return outs[0], phase.unsqueeze(-1), tuple(outs[1:]) or (outs[0], outs[0])
+
+    def _empty_result(self, f0_frames):
+        """The result tuple of an empty batch (nothing is launched)."""
         Fr = f0_frames.shape[1]
         T = Fr * self._hop
-        z = lambda *shape: torch.zeros(*shape, device=f0_frames.device)
-        sig = z(0, T)
-        ph = z(0, T, 1) if sample_rate_phase else z(0, Fr, 1)
-        return sig, ph, ((sig, sig) if shared else (z(0, T), z(0, T)))
+        z = lambda n: torch.zeros(0, n, device=f0_frames.device)
+        return self._result(z(T if self._front_wants.get("want_phase") else Fr), [z(T) for _ in range(self._n_outs)])
 
     def _check_mix_rows(self, spk_mix_dict, spk_mix_rows, B):
         """`forward(..., spk_mix_rows=(ids, w))`: refusals before anything is launched (shapes and dtypes on the host;
@@ -428,31 +449,56 @@ class _SynthBase(torch.nn.Module):
         if not (isinstance(spk_mix_rows, (tuple, list)) and len(spk_mix_rows) == 2):
             raise ValueError("spk_mix_rows must be a pair (ids (B, K) int32, w (B, K) fp32)")
         hipddsp.check_mix_rows(spk_mix_rows[0], spk_mix_rows[1], B, int(self.unit2ctrl.n_spk))
-        if self._training_graph():
+        if self.unit2ctrl.wants_grad():
             raise NotImplementedError("spk_mix_rows= is inference only: the training entries take spk_id or spk_mix_dict; call "
                                       "the model under torch.no_grad()")
 
-    def _training_graph(self):
-        """True when the call must be recorded for autograd (grad mode on and some parameter wants a gradient)."""
-        return torch.is_grad_enabled() and any(p.requires_grad for p in self.unit2ctrl.parameters())
-
-    @staticmethod
-    def _noise_args(noise, noise_seed):
-        if noise is not None:
-            return noise.contiguous().float(), EXC_UNIT_NOISE, 0
-        return None, EXC_GENERATE, (_seed_from_torch() if noise_seed is None else int(noise_seed))
+    def _forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
+                 noise_seed, n_frames, spk_mix_rows):
+        """The body of every model's `forward`.  Launches, in order: [ragged: the counts' upload and the held form of units,
+        f0 and volume;] the phase scan; the control network; the model's chain; [ragged: the padding of the returned phase
+        cleared].  A call that autograd records is the same sequence inside `_SynthTrainFn.forward`."""
+        B, Fr = units_frames.shape[0], units_frames.shape[1]
+        if spk_mix_rows is not None:
+            self._check_mix_rows(spk_mix_dict, spk_mix_rows, B)
+        if B == 0:
+            return self._empty_result(f0_frames)
+        if n_frames is not None:
+            vals = self.unit2ctrl.check_ragged(n_frames, B, Fr, "the model under torch.no_grad() (training crops every clip to "
+                                               "one length)")
+            ctx = self._context(f0_frames, ragged=True)
+            n_dev, units, f0, _, volume = self.unit2ctrl.hold_ragged(ctx, vals, units_frames, f0_frames, None, volume_frames)
+            f0 = f0.reshape(B, Fr, 1)
+            ps = self._scan(ctx, f0, initial_phase, infer)
+            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], volume, spk_id, spk_mix_dict, n_dev,
+                                                 spk_mix_rows=spk_mix_rows)
+            excitation = lambda: self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
+        elif self.unit2ctrl.wants_grad():
+            phase, *outs = _SynthTrainFn.apply(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict,
+                                               initial_phase, infer, noise, noise_seed, *self.unit2ctrl.parameters())
+            return self._result(phase, outs)
+        else:
+            n_dev, f0 = None, f0_frames
+            ctx = self._context(f0)
+            ps = self._scan(ctx, f0, initial_phase, infer)
+            ctrl = self.unit2ctrl.forward_flat(units_frames, f0, ps["phase_frames"], volume_frames, spk_id, spk_mix_dict,
+                                               spk_mix_rows=spk_mix_rows)
+            excitation = lambda: self._noise_args(noise, noise_seed)
+        outs, _ = self._render(ctx, ctrl, ps, f0, excitation, n_dev)
+        return self._result(self._phase_out(ctx, ps, n_dev), outs)
 
 
 class _SynthTrainFn(torch.autograd.Function):
     """Autograd node of one synthesiser forward: forward and backward are libddsp_amd calls end to end; torch only
     routes the parameter gradients (reference: autograd through `*.forward`, solver.py:111-113).  The model supplies
-    `_train_forward(ctx, ctrl, ps, f0_frames, noise_args) -> (outputs, saved)` and
-    `_train_backward(ctx, saved, f0_frames, noise_args, grads) -> d_ctrl (rows, sum)`."""
+    `_render(ctx, ctrl, ps, f0_frames, excitation, keep=True) -> (outputs, saved)` and
+    `_train_backward(ctx, ctrl, saved, f0_frames, noise_args, grads) -> d_ctrl (rows, sum)`."""
 
     @staticmethod
     def forward(fctx, model, units, f0_frames, volume, spk_id, spk_mix_dict, initial_phase, infer, noise, noise_seed,
                 *params):
-        ctx, ps = model._front(f0_frames, initial_phase, infer, model._comb_mode, **model._front_wants)
+        ctx = model._context(f0_frames)
+        ps = model._scan(ctx, f0_frames, initial_phase, infer)
         # the training forward runs fp32 products throughout (control network, filter synthesis, FIR): the loss gradient
         # amplifies a 4e-6 error of the signal a thousandfold (tools/diag_train_b32.py).  The BACKWARD runs on the
         # context's own mode: its weight / input gradient GEMMs use split-bf16 products by default (a 4e-6 product error
@@ -463,14 +509,14 @@ class _SynthTrainFn(torch.autograd.Function):
             ctrl, kept = model.unit2ctrl.forward_flat_keep(units, f0_frames, ps["phase_frames"], volume, spk_id,
                                                            spk_mix_dict, ctx=ctx)
             nargs = model._noise_args(noise, noise_seed)
-            outs, saved = model._train_forward(ctx, ctrl, ps, f0_frames, nargs)
+            outs, saved = model._render(ctx, ctrl, ps, f0_frames, lambda: nargs, keep=True)
         finally:
             ctx.set_math(keep_math)
         fctx.model, fctx.dsp = model, ctx
         fctx.set_materialize_grads(False)   # outputs the loss does not use arrive as None in backward, not as zero tensors to add
         fctx.args = (units, f0_frames, volume, spk_id, spk_mix_dict, nargs, ps["phase_frames"])
         fctx.saved = (ctrl, saved, kept)
-        phase_out = ps["phase"] if model._front_wants.get("want_phase") else ps["phase_frames"]
+        phase_out = model._phase_out(ctx, ps)
         fctx.mark_non_differentiable(phase_out)
         return (phase_out,) + tuple(outs)
 
@@ -486,7 +532,8 @@ class _SynthTrainFn(torch.autograd.Function):
         grads = model.unit2ctrl.backward_flat(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict,
                                               d_ctrl.reshape(B, Fr, -1), ctx=ctx, kept=kept)
         fctx.saved = None
-        return (None,) * 10 + tuple(grads.get(p) for p in model.unit2ctrl.parameters())
+        params = tuple(grads.get(p) for p in model.unit2ctrl.parameters())
+        return (None,) * (len(fctx.needs_input_grad) - len(params)) + params      # no gradient for what precedes *params
 
 
 def _sum_grads(ref, *gs):
@@ -512,21 +559,33 @@ class CombSub(_SynthBase):
 
     _comb_mode = COMB_SINC
     _front_wants = {}
+    _n_outs = 3
 
-    def _train_forward(self, ctx, ctrl, ps, f0_frames, nargs):
+    def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
+        """Combtooth -> all-pass -> harmonic filter, + filtered noise -> ((signal, harmonic, noise), saved).  Ragged: the
+        all-pass output is cropped too, as the reference crops per call."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
         rows, sr, hop = B * Fr, self._sr, self._hop
         na, nh, nn_ = self.n_mags
         c2 = ctrl.reshape(rows, -1)
-        ir_ap = ctx.fir_from_ctrl(FIR_ALLPASS, c2, 0, na, rows, sr)
-        h1, _ = ctx.ltv_fir(ps["comb"], ir_ap, B, Fr, hop, math=ctx.fir_math)
-        ir_h = ctx.fir_from_ctrl(FIR_DYNAMIC, c2, na, nh, rows, sr, f0_frames)
-        harmonic, _ = ctx.ltv_fir(h1, ir_h, B, Fr, hop, math=ctx.fir_math)
-        ir_n = ctx.fir_from_ctrl(FIR_STATIC, c2, na + nh, nn_, rows, sr)
-        nz, exc, seed = nargs
-        noise_out, signal = ctx.ltv_fir(nz, ir_n, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
+        crop, saved, save = self._stages(ctx, n_dev, Fr, keep)
+        comb = ps["comb"]
+        crop(comb)
+        ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, 0, na, rows, sr)
+        h, _ = ctx.ltv_fir(comb, ir, B, Fr, hop, math=ctx.fir_math)
+        crop(h)
+        save((comb, h, ir))
+        ir = ctx.fir_from_ctrl(FIR_DYNAMIC, c2, na, nh, rows, sr, f0_frames)
+        harmonic, _ = ctx.ltv_fir(h, ir, B, Fr, hop, math=ctx.fir_math)
+        crop(harmonic)
+        save((ir,))
+        ir = ctx.fir_from_ctrl(FIR_STATIC, c2, na + nh, nn_, rows, sr)
+        nz, exc, seed = excitation()
+        noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
                                         math=ctx.fir_math)
-        return (signal, harmonic, noise_out), (ps["comb"], h1, ir_ap, ir_h, ir_n)
+        crop(noise_out, signal)
+        save((ir,))
+        return (signal, harmonic, noise_out), saved
 
     def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs):
         comb, h1, ir_ap, ir_h, ir_n = saved
@@ -547,57 +606,13 @@ class CombSub(_SynthBase):
         ctx.fir_from_ctrl_bwd(FIR_ALLPASS, c2, 0, na, rows, sr, d_ir, d_ctrl)
         return d_ctrl
 
-    def synth_from_ctrl(self, ctx, ctrl, f0_frames, comb, noise=None, noise_seed=None, n_dev=None):
-        """DSP stage: fused control matrix (B,Fr,sum) + combtooth -> (signal, harmonic, noise).
-        `n_dev`: the counts of a ragged batch whose ctrl and f0 are held over the padding (`_ragged_front`); every signal is
-        then cropped to its row before it enters the next filter - the all-pass output too, as the reference crops per call."""
-        B, Fr = ctrl.shape[0], ctrl.shape[1]
-        rows, sr, hop = B * Fr, self._sr, self._hop
-        na, nh, nn_ = self.n_mags
-        c2 = ctrl.reshape(rows, -1)
-        crop = (lambda *xs: ctx.ragged_crop_(n_dev, Fr, hop, *xs)) if n_dev is not None else (lambda *xs: None)
-        crop(comb)
-        ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, 0, na, rows, sr)
-        h, _ = ctx.ltv_fir(comb, ir, B, Fr, hop, math=ctx.fir_math)
-        crop(h)
-        ir = ctx.fir_from_ctrl(FIR_DYNAMIC, c2, na, nh, rows, sr, f0_frames)
-        harmonic, _ = ctx.ltv_fir(h, ir, B, Fr, hop, math=ctx.fir_math)
-        crop(harmonic)
-        ir = ctx.fir_from_ctrl(FIR_STATIC, c2, na + nh, nn_, rows, sr)
-        nz, exc, seed = self._noise_args(noise, noise_seed) if n_dev is None else \
-            self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
-        noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
-                                        math=ctx.fir_math)
-        crop(noise_out, signal)
-        return signal, harmonic, noise_out
-
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
                 infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None, **kwargs):
         """units (B,Fr,n_unit), f0 (B,Fr,1) Hz, volume (B,Fr), spk_id (B,1)|(1,1) int64 1-based ->
         (signal (B,T), phase_frames (B,Fr,1), (harmonic (B,T), noise (B,T))).  `n_frames`: ragged batch,
         `spk_mix_rows`: a speaker mix per row (module docstring)."""
-        if spk_mix_rows is not None:
-            self._check_mix_rows(spk_mix_dict, spk_mix_rows, units_frames.shape[0])
-        if units_frames.shape[0] == 0:
-            return self._empty_result(f0_frames)
-        if n_frames is not None:
-            ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
-                                                                initial_phase, infer, COMB_SINC)
-            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev,
-                                                 spk_mix_rows=spk_mix_rows)
-            signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0, ps["comb"], noise, noise_seed, n_dev)
-            pf = ctx.ragged_frames(ps["phase_frames"], n_dev, hold=False, out=ps["phase_frames"])
-            return signal, pf.unsqueeze(-1), (harmonic, noise_out)
-        if self._training_graph():
-            pf, signal, harmonic, noise_out = _SynthTrainFn.apply(
-                self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
-                noise_seed, *self.unit2ctrl.parameters())
-            return signal, pf.unsqueeze(-1), (harmonic, noise_out)
-        ctx, ps = self._front(f0_frames, initial_phase, infer, COMB_SINC)
-        ctrl = self.unit2ctrl.forward_flat(units_frames, f0_frames, ps["phase_frames"], volume_frames, spk_id,
-                                           spk_mix_dict, spk_mix_rows=spk_mix_rows)
-        signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0_frames, ps["comb"], noise, noise_seed)
-        return signal, ps["phase_frames"].unsqueeze(-1), (harmonic, noise_out)
+        return self._forward(units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
+                             noise_seed, n_frames, spk_mix_rows)
 
 
 class Sins(_SynthBase):
@@ -613,20 +628,28 @@ class Sins(_SynthBase):
 
     _comb_mode = COMB_NONE
     _front_wants = {"want_phase": True}
+    _n_outs = 3
 
-    def _train_forward(self, ctx, ctrl, ps, f0_frames, nargs):
+    def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
+        """Sinusoid bank on the sample-rate phase -> all-pass, + filtered noise -> ((signal, harmonic, noise), saved)."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
         rows, sr, hop = B * Fr, self._sr, self._hop
         nhm, na, nn_ = self.n_mags
         c2 = ctrl.reshape(rows, -1)
+        crop, saved, save = self._stages(ctx, n_dev, Fr, keep)
         sinusoids = ctx.sins_bank(c2, 0, nhm, f0_frames, ps["phase"], B, Fr, hop, sr)
-        ir_ap = ctx.fir_from_ctrl(FIR_ALLPASS, c2, nhm, na, rows, sr)
-        harmonic, _ = ctx.ltv_fir(sinusoids, ir_ap, B, Fr, hop, math=ctx.fir_math)
-        ir_n = ctx.fir_from_ctrl(FIR_STATIC, c2, nhm + na, nn_, rows, sr)
-        nz, exc, seed = nargs
-        noise_out, signal = ctx.ltv_fir(nz, ir_n, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
+        crop(sinusoids)
+        ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, nhm, na, rows, sr)
+        harmonic, _ = ctx.ltv_fir(sinusoids, ir, B, Fr, hop, math=ctx.fir_math)
+        crop(harmonic)
+        save((ps["phase"], sinusoids, ir))
+        ir = ctx.fir_from_ctrl(FIR_STATIC, c2, nhm + na, nn_, rows, sr)
+        nz, exc, seed = excitation()
+        noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
                                         math=ctx.fir_math)
-        return (signal, harmonic, noise_out), (ps["phase"], sinusoids, ir_ap, ir_n)
+        crop(noise_out, signal)
+        save((ir,))
+        return (signal, harmonic, noise_out), saved
 
     def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs):
         phase, sinusoids, ir_ap, ir_n = saved
@@ -646,53 +669,13 @@ class Sins(_SynthBase):
         ctx.sins_bank_bwd(c2, 0, nhm, f0_frames, phase, d_sin, B, Fr, hop, sr, d_ctrl)
         return d_ctrl
 
-    def synth_from_ctrl(self, ctx, ctrl, f0_frames, phase, noise=None, noise_seed=None, n_dev=None):
-        """`n_dev`: the counts of a ragged batch (see CombSub.synth_from_ctrl)."""
-        B, Fr = ctrl.shape[0], ctrl.shape[1]
-        rows, sr, hop = B * Fr, self._sr, self._hop
-        nhm, na, nn_ = self.n_mags
-        c2 = ctrl.reshape(rows, -1)
-        crop = (lambda *xs: ctx.ragged_crop_(n_dev, Fr, hop, *xs)) if n_dev is not None else (lambda *xs: None)
-        sinusoids = ctx.sins_bank(c2, 0, nhm, f0_frames, phase, B, Fr, hop, sr)
-        crop(sinusoids)
-        ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, nhm, na, rows, sr)
-        harmonic, _ = ctx.ltv_fir(sinusoids, ir, B, Fr, hop, math=ctx.fir_math)
-        crop(harmonic)
-        ir = ctx.fir_from_ctrl(FIR_STATIC, c2, nhm + na, nn_, rows, sr)
-        nz, exc, seed = self._noise_args(noise, noise_seed) if n_dev is None else \
-            self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
-        noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
-                                        math=ctx.fir_math)
-        crop(noise_out, signal)
-        return signal, harmonic, noise_out
-
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
                 infer=True, max_upsample_dim=32, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None):
         """Same contract as CombSub.forward except that the returned phase is sample-rate (B,T,1)
         (reference `ddsp/vocoder.py:423`).  `max_upsample_dim` is accepted and ignored: the bank kernel never
         materialises the (B,T,chunk) tensors the reference chunks to bound."""
-        if spk_mix_rows is not None:
-            self._check_mix_rows(spk_mix_dict, spk_mix_rows, units_frames.shape[0])
-        if units_frames.shape[0] == 0:
-            return self._empty_result(f0_frames, sample_rate_phase=True)
-        if n_frames is not None:
-            ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
-                                                                initial_phase, infer, COMB_NONE, want_phase=True)
-            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev,
-                                                 spk_mix_rows=spk_mix_rows)
-            signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0, ps["phase"], noise, noise_seed, n_dev)
-            ctx.ragged_crop_(n_dev, f0.shape[1], self._hop, ps["phase"])
-            return signal, ps["phase"].unsqueeze(-1), (harmonic, noise_out)
-        if self._training_graph():
-            ph, signal, harmonic, noise_out = _SynthTrainFn.apply(
-                self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
-                noise_seed, *self.unit2ctrl.parameters())
-            return signal, ph.unsqueeze(-1), (harmonic, noise_out)
-        ctx, ps = self._front(f0_frames, initial_phase, infer, COMB_NONE, want_phase=True)
-        ctrl = self.unit2ctrl.forward_flat(units_frames, f0_frames, ps["phase_frames"], volume_frames, spk_id,
-                                           spk_mix_dict, spk_mix_rows=spk_mix_rows)
-        signal, harmonic, noise_out = self.synth_from_ctrl(ctx, ctrl, f0_frames, ps["phase"], noise, noise_seed)
-        return signal, ps["phase"].unsqueeze(-1), (harmonic, noise_out)
+        return self._forward(units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
+                             noise_seed, n_frames, spk_mix_rows)
 
 
 class CombSubFast(_SynthBase):
@@ -708,12 +691,21 @@ class CombSubFast(_SynthBase):
 
     _comb_mode = COMB_SINC_GATED
     _front_wants = {}
+    _n_outs = 1
 
-    def _train_forward(self, ctx, ctrl, ps, f0_frames, nargs):
+    def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
+        """One windowed spectral OLA -> ((signal,), saved).  Ragged: with the comb and the excitation 0 past a row's end,
+        frames 0..n_b of the row are the frames of the row rendered alone (frame n_b on frame n_b - 1's filters, 512 zeros
+        behind the row)."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
-        nz, exc, seed = nargs
-        signal = ctx.spectral_ola(ctrl.reshape(B * Fr, -1), ps["comb"], nz, exc, seed, B, Fr, self._hop)
-        return (signal,), (ps["comb"],)
+        crop, saved, save = self._stages(ctx, n_dev, Fr, keep)
+        comb = ps["comb"]
+        crop(comb)
+        nz, exc, seed = excitation()
+        signal = ctx.spectral_ola(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, B, Fr, self._hop)
+        crop(signal)
+        save((comb,))
+        return (signal,), saved
 
     def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs):
         (comb,) = saved
@@ -722,43 +714,10 @@ class CombSubFast(_SynthBase):
         return ctx.spectral_ola_bwd(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, _sum_grads(comb, *d_outs), B, Fr,
                                     self._hop)
 
-    def synth_from_ctrl(self, ctx, ctrl, comb, noise=None, noise_seed=None, n_dev=None):
-        """`n_dev`: the counts of a ragged batch whose ctrl is held over the padding: with the comb and the excitation 0
-        past a row's end, frames 0..n_b of the row are the frames of the row rendered alone (frame n_b on frame n_b - 1's
-        filters, 512 zeros behind the row)."""
-        B, Fr = ctrl.shape[0], ctrl.shape[1]
-        if n_dev is None:
-            nz, exc, seed = self._noise_args(noise, noise_seed)
-            return ctx.spectral_ola(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, B, Fr, self._hop)
-        ctx.ragged_crop_(n_dev, Fr, self._hop, comb)
-        nz, exc, seed = self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
-        signal = ctx.spectral_ola(ctrl.reshape(B * Fr, -1), comb, nz, exc, seed, B, Fr, self._hop)
-        ctx.ragged_crop_(n_dev, Fr, self._hop, signal)
-        return signal
-
     def forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict=None, initial_phase=None,
                 infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None, **kwargs):
         """Returns (signal, phase_frames (B,Fr,1), (signal, signal)) - the same tensor three times, like the
         reference (`ddsp/vocoder.py:492`).  `n_frames`: ragged batch,
         `spk_mix_rows`: a speaker mix per row (module docstring)."""
-        if spk_mix_rows is not None:
-            self._check_mix_rows(spk_mix_dict, spk_mix_rows, units_frames.shape[0])
-        if units_frames.shape[0] == 0:
-            return self._empty_result(f0_frames, shared=True)
-        if n_frames is not None:
-            ctx, n_dev, units, f0, vol, ps = self._ragged_front(units_frames, f0_frames, volume_frames, n_frames,
-                                                                initial_phase, infer, COMB_SINC_GATED)
-            ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], vol, spk_id, spk_mix_dict, n_dev,
-                                                 spk_mix_rows=spk_mix_rows)
-            signal = self.synth_from_ctrl(ctx, ctrl, ps["comb"], noise, noise_seed, n_dev)
-            pf = ctx.ragged_frames(ps["phase_frames"], n_dev, hold=False, out=ps["phase_frames"])
-            return signal, pf.unsqueeze(-1), (signal, signal)
-        if self._training_graph():
-            pf, signal = _SynthTrainFn.apply(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict,
-                                             initial_phase, infer, noise, noise_seed, *self.unit2ctrl.parameters())
-            return signal, pf.unsqueeze(-1), (signal, signal)
-        ctx, ps = self._front(f0_frames, initial_phase, infer, COMB_SINC_GATED)
-        ctrl = self.unit2ctrl.forward_flat(units_frames, f0_frames, ps["phase_frames"], volume_frames, spk_id,
-                                           spk_mix_dict, spk_mix_rows=spk_mix_rows)
-        signal = self.synth_from_ctrl(ctx, ctrl, ps["comb"], noise, noise_seed)
-        return signal, ps["phase_frames"].unsqueeze(-1), (signal, signal)
+        return self._forward(units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
+                             noise_seed, n_frames, spk_mix_rows)

@@ -31,6 +31,30 @@ def test_bad_n_frames_raise_before_any_device_work(name):
             model(*args, n_frames=n)
 
 
+def test_forward_signatures():
+    """The public entries of the synthesisers and of the control network keep their parameter lists and defaults."""
+    import inspect
+    from ddsp.unit2control import Unit2Control
+    from ddsp.vocoder import CombSub, CombSubFast, Sins
+    P = inspect.Parameter
+    req = lambda n: P(n, P.POSITIONAL_OR_KEYWORD)
+    opt = lambda n, d=None: P(n, P.POSITIONAL_OR_KEYWORD, default=d)
+    head = [req("self"), req("units_frames"), req("f0_frames"), req("volume_frames"), req("spk_id"), opt("spk_mix_dict"),
+            opt("initial_phase"), opt("infer", True)]
+    tail = [opt("noise"), opt("noise_seed"), opt("n_frames"), opt("spk_mix_rows")]
+    kwargs = [P("kwargs", P.VAR_KEYWORD)]
+    frames = [req("self"), req("units"), req("f0"), req("phase"), req("volume"), req("spk_id")]
+    want = {CombSub.forward: head + tail + kwargs,
+            Sins.forward: head + [opt("max_upsample_dim", 32)] + tail,
+            CombSubFast.forward: head + tail + kwargs,
+            Unit2Control.forward_flat: frames + [opt("spk_mix_dict"), opt("n_frames"), opt("spk_mix_rows")],
+            Unit2Control.forward_ragged: [req("self"), req("ctx")] + frames[1:] + [req("spk_mix_dict"), req("n_dev"),
+                                                                                   opt("hold", True), opt("spk_mix_rows")],
+            Unit2Control.forward_flat_keep: frames + [opt("spk_mix_dict"), opt("ctx")]}
+    for f, params in want.items():
+        assert list(inspect.signature(f).parameters.values()) == params, f.__qualname__
+
+
 def test_group_segments_rule():
     from infer_offline import group_segments
     rng = np.random.Generator(np.random.PCG64(11))
