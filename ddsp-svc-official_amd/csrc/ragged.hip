@@ -36,6 +36,27 @@ __global__ void __launch_bounds__(256) ragged_frames_kernel(const float* src, co
     }
 }
 
+// The adjoint of the held form, in place on a gradient d (B, Fr, C): frame n_b - 1 was read by every frame behind it, so
+// d[b][n_b - 1][:] += sum_{i >= n_b} d[b][i][:], and the padding frames themselves were never an input: d[b][i >= n_b][:] = 0.
+// One thread per (row, column) walks the frames in ascending order ((d[n-1] + d[n]) + d[n+1] ...): the same bits on every run.
+__global__ void __launch_bounds__(256) ragged_frames_adjoint_kernel(float* __restrict__ d, const int* __restrict__ n_frames,
+                                                                    int64_t B, int Fr, int C) {
+    const int64_t total = B * C;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t b = idx / C;
+        const int c = (int)(idx - b * C);
+        const int n = ddsp_row_frames(n_frames, b, Fr);
+        if (n == Fr) continue;
+        float* col = d + b * Fr * C + c;
+        float acc = col[(int64_t)(n - 1) * C];
+        for (int i = n; i < Fr; ++i) {
+            acc += col[(int64_t)i * C];
+            col[(int64_t)i * C] = 0.f;
+        }
+        col[(int64_t)(n - 1) * C] = acc;
+    }
+}
+
 // x[b][t] = 0 for t >= n_b * hop, in up to three (B, Fr * hop) signals; hop % 4 == 0 and 16-byte aligned rows
 struct CropArgs {
     float* x[3];
@@ -98,6 +119,21 @@ extern "C" int ddsp_ragged_frames(ddsp_ctx* ctx, void* stream, const float* src,
     ddsp_prof_begin(ctx, st, PF_OTHER);
     hipLaunchKernelGGL(ragged_frames_kernel, dim3(ragged_grid(B * Fr * C)), dim3(256), 0, st, src, (const int*)n_frames, B,
                        (int)Fr, (int)C, hold, dst);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * B * Fr * C);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_ragged_frames_adjoint(ddsp_ctx* ctx, void* stream, float* d, const int32_t* n_frames, int64_t B, int64_t Fr,
+                                          int64_t C) {
+    DDSP_REQUIRE(ctx, ctx && d && n_frames, "ddsp_ragged_frames_adjoint: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && Fr >= 1 && C >= 1 && Fr < (1 << 24) && C < (1 << 24), "ddsp_ragged_frames_adjoint: bad shape");
+    if (B == 0) return DDSP_OK;
+    DDSP_ENTER_DEVICE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(ragged_frames_adjoint_kernel, dim3(ragged_grid(B * C)), dim3(256), 0, st, d, (const int*)n_frames, B, (int)Fr,
+                       (int)C);
     ddsp_prof_end(ctx, st, 0.0, 8.0 * B * Fr * C);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;

@@ -98,10 +98,20 @@ __global__ void stft_table_kernel(float* __restrict__ tabT, float* __restrict__ 
     }
 }
 
-// Xf[sig][b*F + f][k] = k < N ? x_sig[b][f*hop + k] : 0   (sig 0 = target, 1 = prediction; row pitch Kp)
+// Rows of different length (n_samples, device, B counts; null: every row has T samples): the whole frames of row b, F_b =
+// (n_b - N) / hop + 1 or 0 when n_b < N.  The matrices keep their B * F rows; the frames a row does not have are written as
+// zeros and left out of every sum BY SELECTION, so that what follows a row's last whole frame is never read into arithmetic.
+__device__ __forceinline__ int row_stft_frames(const int* __restrict__ n_samples, int64_t b, int64_t T, int N, int hop, int F) {
+    if (!n_samples) return F;
+    int64_t n = n_samples[b];
+    if (n > T) n = T;
+    return n < N ? 0 : (int)((n - N) / hop + 1);
+}
+
+// Xf[sig][b*F + f][k] = k < N ? x_sig[b][f*hop + k] : 0   (sig 0 = target, 1 = prediction; row pitch Kp); f >= F_b: a zero row
 __global__ void __launch_bounds__(256) frame_pad_kernel(const float* __restrict__ x_true, const float* __restrict__ x_pred,
                                                         int64_t T, int N, int hop, int F, int64_t M, int Kp,
-                                                        float* __restrict__ Xf) {
+                                                        float* __restrict__ Xf, const int* __restrict__ n_samples) {
     const int q4 = Kp / 4;
     const int64_t total = 2 * M * q4;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -110,7 +120,9 @@ __global__ void __launch_bounds__(256) frame_pad_kernel(const float* __restrict_
         const int64_t m = r >= M ? r - M : r;
         const float* src = (r >= M ? x_pred : x_true) + (m / F) * T + (m % F) * (int64_t)hop + k;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (k + 3 < N) {
+        if (n_samples && (int)(m % F) >= row_stft_frames(n_samples, m / F, T, N, hop, F)) {
+            // a frame the row does not have: zeros, nothing is read
+        } else if (k + 3 < N) {
             v = *(const gemm::f32x4_u*)src;
         } else {
 #pragma unroll
@@ -148,12 +160,16 @@ struct EpiMag {  // z = 0: target, z = 1: prediction.  S_z[m][f] = |X| + eps ; X
 // LS_CHUNKS workgroups per utterance: partial d2, s2, l1 in fp64 (combined by loss_combine_kernel)
 constexpr int LS_CHUNKS = 16;
 __global__ void __launch_bounds__(256) loss_stats_kernel(const float* __restrict__ St, const float* __restrict__ Sp,
-                                                         int64_t per_b, double* __restrict__ stats) {
+                                                         int64_t per_b, double* __restrict__ stats,
+                                                         const int* __restrict__ n_samples, int64_t T, int N, int hop, int F) {
+    // per_b = F * Mb cells are laid out per row, of which the first F_b * Mb exist; the chunks are those of the full row, so
+    // equal lengths give the bits of the flat call
     const int b = blockIdx.x, ch = blockIdx.y;
     const float* t = St + (int64_t)b * per_b;
     const float* p = Sp + (int64_t)b * per_b;
     const int64_t per = (per_b + LS_CHUNKS - 1) / LS_CHUNKS;
-    const int64_t i0 = ch * per, i1 = (i0 + per < per_b) ? i0 + per : per_b;
+    const int64_t have = (per_b / F) * row_stft_frames(n_samples, b, T, N, hop, F);
+    const int64_t i0 = ch * per, i1 = (i0 + per < have) ? i0 + per : have;
     double d2 = 0, s2 = 0, l1 = 0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
         const float a = t[i], c = p[i];
@@ -198,35 +214,48 @@ __global__ void loss_fold_kernel(double* __restrict__ stats, int B) {
     o[2] = l1;
 }
 
-// loss += weight * (mean_b sqrt(d2/s2) + alpha * sum l1 / count)
-__global__ void loss_combine_kernel(const double* __restrict__ stats, int B, double count, double alpha, double weight,
-                                    float* __restrict__ loss, int first) {
+// loss += weight * (mean_b sqrt(d2/s2) + alpha * sum l1 / count); count: the cells that exist, rows_ne: the rows with a frame
+// (the mean of the convergence term runs over them: a row without a frame has no ratio)
+__global__ void loss_combine_kernel(const double* __restrict__ stats, int B, double count, int rows_ne, double alpha, double weight,
+                                    float* __restrict__ loss, int first, const int* __restrict__ n_samples, int64_t T, int N,
+                                    int hop, int F) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double conv = 0.0, l1 = 0.0;
     for (int b = 0; b < B; ++b) {
+        if (row_stft_frames(n_samples, b, T, N, hop, F) == 0) continue;
         conv += sqrt(stats[b * LS_CHUNKS * 3 + 0]) / sqrt(stats[b * LS_CHUNKS * 3 + 1]);
         l1 += stats[b * LS_CHUNKS * 3 + 2];
     }
-    const double v = weight * (conv / B + alpha * l1 / count);
+    const double v = weight * (conv / rows_ne + alpha * l1 / count);
     loss[0] = (first ? 0.f : loss[0]) + (float)v;
 }
 
 // dX[row][2f | 2f+1] = dL/dS_p * (re, im) / |X|
 __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ St, const float* __restrict__ Sp,
                                                         float* __restrict__ X, const double* __restrict__ stats, int B,
-                                                        int F, int Mb, int ldx, double alpha, double weight, float eps) {
+                                                        int F, int Mb, int ldx, double alpha, double weight, float eps,
+                                                        double count, int rows_ne, const int* __restrict__ n_samples, int64_t T,
+                                                        int N, int hop) {
     const int64_t per_b = (int64_t)F * Mb;
     const int64_t total = (int64_t)B * per_b;
-    const double count = (double)total;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)(i / per_b);
         const int64_t row = i / Mb;
         const int f = (int)(i % Mb);
+        if (n_samples && (int)(row - (int64_t)b * F) >= row_stft_frames(n_samples, b, T, N, hop, F)) {
+            // a frame the row does not have: no gradient (its row of the adjoint product is 0)
+            float* xz = X + row * ldx + 2 * f;
+            xz[0] = 0.f;
+            xz[1] = 0.f;
+            if (f == Mb - 1)
+                for (int p = 2 * Mb; p < ldx; ++p) X[row * ldx + p] = 0.f;
+            continue;
+        }
         const double rd = sqrt(stats[b * LS_CHUNKS * 3 + 0]), rs = sqrt(stats[b * LS_CHUNKS * 3 + 1]);
         const float a = St[i], c = Sp[i];
         double g = 0.0;
-        if (rd > 0.0) g += (-(double)(a - c) / (rd * rs)) / B;
-        g += (-rd * (double)(a + c) / (rs * rs * rs)) / B;
+        if (rd > 0.0) g += (-(double)(a - c) / (rd * rs)) / rows_ne;
+        g += (-rd * (double)(a + c) / (rs * rs * rs)) / rows_ne;
         const float dl = logf(c) - logf(a);
         g += alpha * ((dl > 0.f) - (dl < 0.f)) / ((double)c * count);
         g *= weight;
@@ -244,12 +273,14 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
 // grad[b][t] (+)= sum over the frames that cover t of dXf[b*F + f][t - f*hop]   (gather form of the overlap-add: one
 // term with hop == N; samples no frame covers get 0 on the first scale and stay as they are afterwards)
 __global__ void __launch_bounds__(256) frames_ola_kernel(const float* __restrict__ dXf, int Kp, int64_t T, int N, int hop,
-                                                         int F, int64_t B, int accumulate, float* __restrict__ grad) {
+                                                         int F, int64_t B, int accumulate, float* __restrict__ grad,
+                                                         const int* __restrict__ n_samples) {
     const int64_t total = B * T;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = idx / T, t = idx % T;
+        const int Fb = row_stft_frames(n_samples, b, T, N, hop, F);   // (no frame of the row covers t: the sum is empty, 0)
         int64_t f1 = t / hop;
-        if (f1 > F - 1) f1 = F - 1;
+        if (f1 > Fb - 1) f1 = Fb - 1;
         int64_t f0 = t - N + 1 > 0 ? (t - N + hop) / hop : 0;   // ceil((t - N + 1) / hop)
         float s = 0.f;
         for (int64_t f = f0; f <= f1; ++f) s += dXf[(b * F + f) * Kp + (t - f * hop)];
@@ -259,9 +290,10 @@ __global__ void __launch_bounds__(256) frames_ola_kernel(const float* __restrict
 
 }  // namespace
 
-extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B,
-                             int64_t T, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps,
-                             float* loss, float* grad_pred) {
+// ns_host / ns_dev: the rows' sample counts on the host (checks, cell counts) and on the device (the kernels), or both null
+static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                        const int* ns_host, const int* ns_dev, const int* n_ffts_host, const int* hops_host, int n_scale,
+                        float alpha, float eps, float* loss, float* grad_pred) {
     DDSP_REQUIRE(ctx, ctx && x_pred && x_true && n_ffts_host && loss, "ddsp_rss_loss: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 32768 && T >= 4 && n_scale >= 1 && n_scale <= 64, "ddsp_rss_loss: bad shape");
     DDSP_REQUIRE(ctx, T % 4 == 0 && ((uintptr_t)x_pred % 16) == 0 && ((uintptr_t)x_true % 16) == 0,
@@ -275,6 +307,14 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
         DDSP_REQUIRE(ctx, hop >= 1 && hop <= N, "ddsp_rss_loss: hop must lie in [1, n_fft]");
         const size_t Mb = N / 2 + 1, Kp = round32(N), Kb = round32(2 * (int)Mb), M = (size_t)B * (size_t)((T - N) / hop + 1);
         DDSP_REQUIRE(ctx, M * Kp < ((size_t)1 << 31) && 2 * M < ((size_t)1 << 31), "ddsp_rss_loss: too many frames for one call");
+        if (ns_host) {
+            bool any = false;
+            for (int64_t b = 0; b < B; ++b) {
+                DDSP_REQUIRE(ctx, ns_host[b] >= 1 && ns_host[b] <= T, "ddsp_rss_loss_ragged: n_samples outside 1..T");
+                any = any || ns_host[b] >= N;
+            }
+            DDSP_REQUIRE(ctx, any, "ddsp_rss_loss_ragged: no row has a whole frame at one of the scales");
+        }
         tabT_f = std::max(tabT_f, 2 * Mb * Kp);
         tab_f = std::max(tab_f, (size_t)N * Kb);
         xf_f = std::max(xf_f, 2 * M * Kp);
@@ -330,13 +370,26 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
         const int F = (int)((T - N) / hop + 1);
         const int64_t M = B * F;
         const double weight = 1.0 / n_scale;
+        // the cells that exist and the rows that have a frame (all of them without counts)
+        double count = (double)B * F * Mb;
+        int rows_ne = (int)B;
+        if (ns_host) {
+            int64_t frames = 0;
+            rows_ne = 0;
+            for (int64_t b = 0; b < B; ++b)
+                if (ns_host[b] >= N) {
+                    frames += (ns_host[b] - N) / hop + 1;
+                    ++rows_ne;
+                }
+            count = (double)(frames * Mb);
+        }
         if (use_1d) {
             if (s == 0) hipLaunchKernelGGL(stft_table1d_kernel, dim3(8, (unsigned)n_scale), dim3(256), 0, st, t1a);
             hipLaunchKernelGGL(stft_table_from1d_kernel, dim3(1024), dim3(256), 0, st, t1a.t1[s], tabT, tab, N, Kp, Kb);
         } else
             hipLaunchKernelGGL(stft_table_kernel, dim3(1024), dim3(256), 0, st, tabT, tab, N, Kp, Kb);
         hipLaunchKernelGGL(frame_pad_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(2 * M * (Kp / 4), 256), 16384)), dim3(256),
-                           0, st, x_true, x_pred, T, N, hop, F, M, Kp, Xf);
+                           0, st, x_true, x_pred, T, N, hop, F, M, Kp, Xf, ns_dev);
         // (the pad columns of Xp multiply zeros of the table: loss_grad_kernel clears them, the spectra kernel writes the rest)
         {
             gemm::Args g = gemm::make(Xf, Kp, tabT, Kp, (int)M, 2 * Mb, Kp);
@@ -345,17 +398,17 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
             EpiMag e{St, Sp, Xp, Mb, Kb, eps};
             gemm::launch<true, true, gemm::A_PLAIN>(st, g, 2, e);
         }
-        hipLaunchKernelGGL(loss_stats_kernel, dim3((unsigned)B, LS_CHUNKS), dim3(256), 0, st, St, Sp, (int64_t)F * Mb, stats);
+        hipLaunchKernelGGL(loss_stats_kernel, dim3((unsigned)B, LS_CHUNKS), dim3(256), 0, st, St, Sp, (int64_t)F * Mb, stats, ns_dev, T, N, hop, F);
         hipLaunchKernelGGL(loss_fold_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, stats, (int)B);
-        hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(64), 0, st, stats, (int)B, (double)B * F * Mb,
-                           (double)alpha, weight, loss, s == 0 ? 1 : 0);
+        hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(64), 0, st, stats, (int)B, count, rows_ne,
+                           (double)alpha, weight, loss, s == 0 ? 1 : 0, ns_dev, T, N, hop, F);
         flops += 2.0 * 2.0 * M * (double)N * 2 * Mb;
         if (grad_pred) {
             const int64_t total = M * Mb;
             int64_t blocks = ceil_div64(total, 256);
             if (blocks > 8192) blocks = 8192;
             hipLaunchKernelGGL(loss_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, St, Sp, Xp, stats, (int)B, F,
-                               Mb, Kb, (double)alpha, weight, eps);
+                               Mb, Kb, (double)alpha, weight, eps, count, rows_ne, ns_dev, T, N, hop);
             // per-frame gradient dXf = dX x T^T (A = dX (M x Kb), B(k, n) = tab[n][k]) into the framed buffer, then the
             // overlap-add back onto the signal axis
             gemm::Args gb = gemm::make(Xp, Kb, tab, Kb, (int)M, N, Kb);
@@ -363,11 +416,26 @@ extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, c
             gemm::EpiStore eg{Xf, Kp, nullptr, 1, 0, 0};
             gemm::launch<true, true, gemm::A_PLAIN>(st, gb, 1, eg);
             hipLaunchKernelGGL(frames_ola_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(B * T, 256), 16384)), dim3(256), 0,
-                               st, Xf, Kp, T, N, hop, F, B, s == 0 ? 0 : 1, grad_pred);
+                               st, Xf, Kp, T, N, hop, F, B, s == 0 ? 0 : 1, grad_pred, ns_dev);
             flops += 2.0 * M * (double)N * 2 * Mb;
         }
     }
     ddsp_prof_end(ctx, st, flops, 4.0 * B * T * (2.0 * n_scale + (grad_pred ? 1.0 : 0.0)));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B,
+                             int64_t T, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps,
+                             float* loss, float* grad_pred) {
+    return rss_loss_any(ctx, stream, x_pred, x_true, B, T, nullptr, nullptr, n_ffts_host, hops_host, n_scale, alpha, eps, loss,
+                        grad_pred);
+}
+
+extern "C" int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                                    const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host,
+                                    const int* hops_host, int n_scale, float alpha, float eps, float* loss, float* grad_pred) {
+    DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev, "ddsp_rss_loss_ragged: null n_samples");
+    return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
+                        n_scale, alpha, eps, loss, grad_pred);
 }

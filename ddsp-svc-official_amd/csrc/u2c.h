@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256) dwconv_kernel(const float* __restrict__ x
                                                      const float* __restrict__ bias, int B, int Fr,
                                                      float* __restrict__ out, float* __restrict__ pre, int wsc, int wst,
                                                      int left, int split,     // left = DWK / 2: centred taps; DWK - 1: causal taps (frames t-30 .. t)
-                                                     const int* __restrict__ n_frames = nullptr) {   // ragged batch: input frames >= n_b read as 0
+                                                     const int* __restrict__ n_frames = nullptr) {   // ragged batch: input frames >= n_b read as 0 (FLIP: the input gradient is 0 there - the caller clears it)
     // split != 0 (forward, inference): `out` is written as bf16 hi/lo groups of 8 channels (A operand of the pw2 GEMM)
     const int c = blockIdx.x * 256 + threadIdx.x;       // channel (INNER = 512 -> 2 blocks in x)
     const int runs = (Fr + RUN - 1) / RUN;
@@ -100,6 +100,21 @@ __global__ void __launch_bounds__(256) dwconv_kernel(const float* __restrict__ x
             }
         }
     }
+}
+
+// Ragged batch: x[b][f][0 .. C) = 0 for the frames f >= n_b of every row (C % 4 == 0, 16-byte aligned rows).  A selection, so
+// whatever the padding held is gone.  The training forward clears k' with it (the key sums and the context then run over a
+// row's own frames), the backward pass the gradients that a frame sum spread over the padding (d_k, d_v).
+__global__ void __launch_bounds__(256) zero_padding_frames_kernel(float* __restrict__ x, const int* __restrict__ n_frames,
+                                                                  int64_t B, int Fr, int C4) {
+    const int64_t total = B * Fr * C4;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t row = idx / C4;
+        if ((int)(row % Fr) >= ddsp_row_frames(n_frames, row / Fr, Fr)) ((f32x4*)x)[idx] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+inline void zero_padding_frames(hipStream_t st, float* x, const int* n_frames, int64_t B, int64_t Fr, int C) {
+    hipLaunchKernelGGL(zero_padding_frames_kernel, dim3(grid_for(B * Fr * (C / 4))), dim3(256), 0, st, x, n_frames, B, (int)Fr, C / 4);
 }
 
 }  // namespace

@@ -330,19 +330,21 @@ __global__ void __launch_bounds__(256) glu_bwd_kernel(const float* __restrict__ 
 // batch through the L1 and took 79 us per layer at B = 32, memory-instruction bound).  partial[(b, run)][tap][channel]: coalesced 256-byte rows per tap; dw_wgrad_reduce_kernel sums the runs and
 // transposes to the parameter's (512, 1, 31) layout.
 __global__ void __launch_bounds__(256) dwconv_wgrad_run_kernel(const float* __restrict__ dpre, const float* __restrict__ x,
-                                                               int B, int Fr, float* __restrict__ partial, int left) {
+                                                               int B, int Fr, float* __restrict__ partial, int left,
+                                                               const int* __restrict__ n_frames = nullptr) {   // ragged batch: input frames >= n_b read as 0, as the forward read them
     const int c = blockIdx.x * 256 + threadIdx.x;
     const int runs = (Fr + DW_RUN - 1) / DW_RUN;
     const int b = blockIdx.y / runs, f0 = (blockIdx.y % runs) * DW_RUN;
     const float* dp = dpre + ((int64_t)b * Fr) * INNER + c;
     const float* xp = x + ((int64_t)b * Fr) * INNER + c;
+    const int n_in = ddsp_row_frames(n_frames, b, Fr);
     float d[DW_RUN], win[DW_RUN + DWK - 1];
 #pragma unroll
     for (int o = 0; o < DW_RUN; ++o) d[o] = f0 + o < Fr ? dp[(int64_t)(f0 + o) * INNER] : 0.f;
 #pragma unroll
     for (int i = 0; i < DW_RUN + DWK - 1; ++i) {
         const int f = f0 + i - left;
-        win[i] = (f >= 0 && f < Fr) ? xp[(int64_t)f * INNER] : 0.f;
+        win[i] = (f >= 0 && f < n_in) ? xp[(int64_t)f * INNER] : 0.f;
     }
     float* out = partial + ((int64_t)blockIdx.y * DWK) * INNER + c;
 #pragma unroll
@@ -518,14 +520,16 @@ struct EpiAccumulate {  // C += acc
 __global__ void __launch_bounds__(256) groupnorm_bwd_stats_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                   const float* __restrict__ dy, const float* __restrict__ stats,
                                                                   const float* __restrict__ gamma, int Fr,
-                                                                  float* __restrict__ bstats) {
+                                                                  float* __restrict__ bstats,
+                                                                  const int* __restrict__ n_frames = nullptr) {   // ragged batch: the row's own frames
     const int g = blockIdx.x, b = blockIdx.y;
     const int c = threadIdx.x & 63, fl = threadIdx.x >> 6;
     const int ch = g * 64 + c;
     const float mean = stats[(b * 4 + g) * 2], rstd = stats[(b * 4 + g) * 2 + 1];
     const float ga = gamma[ch];
+    const int nv = ddsp_row_frames(n_frames, b, Fr);
     double s1 = 0.0, s2 = 0.0;
-    for (int f = fl; f < Fr; f += 4) {
+    for (int f = fl; f < nv; f += 4) {
         const int64_t i = ((int64_t)b * Fr + f) * D + ch;
         const float slope = y[i] > 0.f ? 1.0f : 0.01f;   // y = lrelu(gn(x)); sign(y) = sign(gn(x))
         const float dgn = dy[i] * slope;
@@ -542,7 +546,7 @@ __global__ void __launch_bounds__(256) groupnorm_bwd_stats_kernel(const float* _
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double n = 64.0 * Fr;
+        const double n = 64.0 * nv;
         bstats[(b * 4 + g) * 2 + 0] = (float)((red[0] + red[1] + red[2] + red[3]) / n);
         bstats[(b * 4 + g) * 2 + 1] = (float)((red[4] + red[5] + red[6] + red[7]) / n);
     }
@@ -554,12 +558,19 @@ __global__ void __launch_bounds__(256) groupnorm_bwd_apply_kernel(const float* _
                                                                   const float* __restrict__ bstats,
                                                                   const float* __restrict__ gamma, int64_t rows, int Fr,
                                                                   float* __restrict__ dx, float* __restrict__ gxh,
-                                                                  float* __restrict__ dgn_out) {
+                                                                  float* __restrict__ dgn_out,
+                                                                  const int* __restrict__ n_frames = nullptr) {   // ragged batch: 0 past a row's own frames
     const int64_t total = rows * D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t m = i / D;
         const int ch = (int)(i % D);
         const int b = (int)(m / Fr), g = ch >> 6;
+        if (n_frames && (int)(m % Fr) >= ddsp_row_frames(n_frames, b, Fr)) {   // (d_t2 there is the conv adjoint's spill: not read)
+            dx[i] = 0.f;
+            gxh[i] = 0.f;
+            dgn_out[i] = 0.f;
+            continue;
+        }
         const float mean = stats[(b * 4 + g) * 2], rstd = stats[(b * 4 + g) * 2 + 1];
         const float m1 = bstats[(b * 4 + g) * 2], m2 = bstats[(b * 4 + g) * 2 + 1];
         const float slope = y[i] > 0.f ? 1.0f : 0.01f;
@@ -966,6 +977,12 @@ __global__ void __launch_bounds__(256) transpose_split_kernel(TsArgs t) {
 
 // the backward pass; `keep` = the activation region a ddsp_unit2ctrl_fwd_keep call filled (then nothing is recomputed), or
 // null: the forward is re-run here with its activations in the scratch arena
+// Ragged batch (in.n_frames): d_ctrl is 0 on every row's padding frames, and the pass keeps the gradient of EVERY activation
+// exactly 0 there.  The row-wise adjoints do so by themselves (a zero gradient row times a finite kept activation), so do the
+// sums over frames of a weight gradient, of d_ctx / d_ks and of the causal scans (they add zeros).  What needs the counts are
+// the places where the forward read the padding as 0 or summed over a row's own frames: the depthwise convolution (its input
+// gradient is 0 there, its weight gradient reads 0 there), d_k and d_v of the attention (the context's gradient reaches every
+// frame), the GroupNorm statistics and d_t1 (conv2's adjoint spills one frame past the row; t2 itself was written as 0 there).
 static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const ddsp_u2c_weights& gr, const U2CInputs& in,
                         int64_t B, int64_t Fr, const float* d_ctrl, float* ctrl_out, void* keep, size_t keep_bytes) {
     int rc;
@@ -1090,12 +1107,13 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
         {
             const int runs = (int)((Fr + DW_RUN - 1) / DW_RUN);
             hipLaunchKernelGGL(dwconv_wgrad_run_kernel, dim3(INNER / 256, (unsigned)(B * runs)), dim3(256), 0, st, dB512, b.glu, (int)B,
-                               (int)Fr, dwpart, w.causal ? DWK - 1 : DWK / 2);
+                               (int)Fr, dwpart, w.causal ? DWK - 1 : DWK / 2, in.n_frames);
             hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3(INNER / 64, DWK), dim3(256), 0, st, dwpart, (int)B * runs, GLP(cm_dw_w));
         }
         if ((rc = colsum(ctx, st, dB512, INNER, M, INNER, nullptr, 0, cpart, GLP(cm_dw_b)))) return rc;
         hipLaunchKernelGGL((dwconv_kernel<false, true>), dim3(INNER / 256, (unsigned)(B * ((Fr + DW_RUN - 1) / DW_RUN))),
                            dim3(256), 0, st, dB512, L.cm_dw_w, nullptr, (int)B, (int)Fr, dC512, nullptr, DWK, 1, w.causal ? 0 : DWK / 2, 0);   // d_glu (adjoint taps: left' = DWK - 1 - left)
+        if (in.n_frames) zero_padding_frames(st, dC512, in.n_frames, B, Fr, INNER);
         hipLaunchKernelGGL(glu_bwd_kernel, dim3(grid_for(M * INNER)), dim3(256), 0, st, b.g1, dC512, M, dG1);
         if ((rc = layer_grads(ctx, st, dG1, 2 * INNER, 2 * INNER, b.y2, D, D, 1, (int)Fr, M, wpart, cpart, xs, GLP(cm_pw1_w), D,
                               GLP(cm_pw1_b), 0, dfp))) return rc;
@@ -1184,6 +1202,10 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
             EpiAxpyRow e2{dC512, coefk, b.k, DH};
             gemm::launch<true, false, gemm::A_PLAIN>(st, g, 1, e2);
         }
+        if (in.n_frames) {   // the context's gradient reaches the padding frames, whose k' and v the forward left out of the sums
+            zero_padding_frames(st, dC512, in.n_frames, B, Fr, INNER);
+            zero_padding_frames(st, dV512, in.n_frames, B, Fr, INNER);
+        }
         DDSP_LAUNCH_CHECK(ctx);
         const float* dqkv[3] = {dB512, dC512, dV512};
         const float* pw[3] = {L.q_w, L.k_w, L.v_w};
@@ -1239,9 +1261,9 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
     }
     // ---- GroupNorm + LeakyReLU ----
     hipLaunchKernelGGL(groupnorm_bwd_stats_kernel, dim3(4, (unsigned)B), dim3(256), 0, st, bf.t1, bf.t2, dA, bf.gst,
-                       w.prenet_gn_w, (int)Fr, gbst);
+                       w.prenet_gn_w, (int)Fr, gbst, in.n_frames);
     hipLaunchKernelGGL(groupnorm_bwd_apply_kernel, dim3(grid_for(M * D)), dim3(256), 0, st, bf.t1, bf.t2, dA, bf.gst, gbst,
-                       w.prenet_gn_w, M, (int)Fr, dX, gx, dA);                                     // dX = d_t1, dA = d_gn
+                       w.prenet_gn_w, M, (int)Fr, dX, gx, dA, in.n_frames);                        // dX = d_t1, dA = d_gn
     if ((rc = colsum_pair(ctx, st, gx, dA, D, M, D, cpart, G(prenet_gn_w), G(prenet_gn_b)))) return rc;
     // ---- prenet conv1 (the units carry no gradient) ----
     if ((rc = layer_grads(ctx, st, dX, D, D, in.units, w.n_unit, w.n_unit, 3, (int)Fr, M, wpart, cpart, xs, pk, 3 * w.n_unit,
@@ -1262,10 +1284,21 @@ extern "C" int ddsp_unit2ctrl_bwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_we
                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
                                   const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const float* d_ctrl,
                                   const ddsp_u2c_weights* grads_host, float* ctrl_out) {
+    return ddsp_unit2ctrl_bwd_ragged(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
+                                     n_mix, B, Fr, nullptr, d_ctrl, grads_host, ctrl_out);
+}
+
+// the two entry points with the counts of a ragged batch (n_frames null: every row has Fr frames)
+extern "C" int ddsp_unit2ctrl_bwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                         const float* f0_frames, const float* phase_frames, const float* volume,
+                                         const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                         const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                         const float* d_ctrl, const ddsp_u2c_weights* grads_host, float* ctrl_out) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
     if (rc) return rc;
+    in.n_frames = (const int*)n_frames;
     DDSP_REQUIRE(ctx, d_ctrl && grads_host, "ddsp_unit2ctrl_bwd: null argument");
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
     if (B == 0) return DDSP_OK;
@@ -1278,10 +1311,21 @@ extern "C" int ddsp_unit2ctrl_bwd_kept(ddsp_ctx* ctx, void* stream, const ddsp_u
                                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
                                        const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep,
                                        int64_t keep_bytes, const float* d_ctrl, const ddsp_u2c_weights* grads_host) {
+    return ddsp_unit2ctrl_bwd_kept_ragged(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host,
+                                          mix_w_host, n_mix, B, Fr, nullptr, keep, keep_bytes, d_ctrl, grads_host);
+}
+
+extern "C" int ddsp_unit2ctrl_bwd_kept_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                              const float* f0_frames, const float* phase_frames, const float* volume,
+                                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                              void* keep, int64_t keep_bytes, const float* d_ctrl,
+                                              const ddsp_u2c_weights* grads_host) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
     if (rc) return rc;
+    in.n_frames = (const int*)n_frames;
     DDSP_REQUIRE(ctx, d_ctrl && grads_host && keep && ((uintptr_t)keep % 256) == 0, "ddsp_unit2ctrl_bwd_kept: null argument or keep not 256-byte aligned");
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
     if (B == 0) return DDSP_OK;

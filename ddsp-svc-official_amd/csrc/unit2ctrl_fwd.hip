@@ -1079,6 +1079,8 @@ int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const 
         } else {
             // training forward, non-causal: the feature maps, key sums, context and output through GEMMs + row kernels
             feature_maps(b, L.proj);
+            // ragged batch: k' = 0 over a row's padding, so that the key sums and the context run over its own frames
+            if (in.n_frames) PROF(PF_U2C_ROWWISE, 0, 0, zero_padding_frames(st, b.kf, in.n_frames, B, Fr, H * LDF));
             PROF(PF_U2C_ROWWISE, 0, 4.0 * M8 * NF,
                  hipLaunchKernelGGL(key_sum_kernel, dim3((unsigned)(B * H)), dim3(KS_T * 8), 0, st, b.kf, (int)Fr, b.ks));
             {   // ctx[b,h] (266 x 64) = k'^T v : A stored [n][j] (K x M), B stored [n][e] (K x N)
@@ -1358,10 +1360,22 @@ extern "C" int ddsp_unit2ctrl_fwd_keep(ddsp_ctx* ctx, void* stream, const ddsp_u
                                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
                                        const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep,
                                        int64_t keep_bytes, float* ctrl) {
+    return ddsp_unit2ctrl_fwd_keep_ragged(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host,
+                                          mix_w_host, n_mix, B, Fr, nullptr, keep, keep_bytes, ctrl);
+}
+
+// The same with the counts of a ragged batch (n_frames null: every row has Fr frames); units of frames >= n_frames[b] must be 0,
+// as for ddsp_unit2ctrl_fwd_ragged.  Activations of the padding frames are kept too, finite and without meaning.
+extern "C" int ddsp_unit2ctrl_fwd_keep_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                              const float* f0_frames, const float* phase_frames, const float* volume,
+                                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                              void* keep, int64_t keep_bytes, float* ctrl) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
     if (rc) return rc;
+    in.n_frames = (const int*)n_frames;
     DDSP_REQUIRE(ctx, ctrl && keep && ((uintptr_t)keep % 256) == 0, "ddsp_unit2ctrl_fwd_keep: null ctrl / keep, or keep not 256-byte aligned");
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
     if (B == 0) return DDSP_OK;

@@ -6,6 +6,14 @@ gradient w.r.t. the prediction come from hand-written kernels; no CPU fallback).
 (`ddsp/loss.py:39`), so seeding torch reproduces the reference's sequence of scales; `set_scales` pins the next
 draw (tests, and data-parallel ranks that must share one draw - SURVEY 8e).  `overlap` sets the hop as the reference
 does, `int(n_fft * (1 - overlap))` (`ddsp/loss.py:13`); its callers use 0 (`train.py:48`).
+
+Additive: `forward(..., n_samples=None)` on both classes - rows of DIFFERENT LENGTH inside the padded (B, T) signals (a sequence
+of B ints or a CPU integer tensor (B,), 1 <= n_samples[b] <= T).  At scale N row b has F_b = (n_samples[b] - N) // hop + 1
+STFT frames, or none if it is shorter than N.  The convergence term is the mean of ||S_t - S_p||_F / ||S_t + S_p||_F over the
+rows that have a frame, each norm over the row's own frames; the log term is the mean of |ln S_t - ln S_p| over the
+sum_b F_b * (N // 2 + 1) cells that exist.  Nothing at or after sample (F_b - 1) * hop + N of a row is read into arithmetic
+(the kernels select), the gradient is exactly 0 from there on, and with every count equal to T value and gradient have the bits
+of the call without counts.  A scale at which no row has a frame raises ValueError before anything is launched.
 """
 import torch
 import torch.nn as nn
@@ -15,11 +23,11 @@ import hipddsp
 
 class _SpectralLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_pred, x_true, n_ffts, alpha, eps, overlap=0):
+    def forward(ctx, x_pred, x_true, n_ffts, alpha, eps, overlap=0, n_samples=None):
         c = hipddsp.context_for(x_pred.device)
         need = x_pred.requires_grad
         hops = None if overlap == 0 else [_hop(n, overlap) for n in n_ffts]
-        loss, grad = c.rss_loss(x_pred, x_true, n_ffts, alpha, eps, want_grad=need, hops=hops)
+        loss, grad = c.rss_loss(x_pred, x_true, n_ffts, alpha, eps, want_grad=need, hops=hops, n_samples=n_samples)
         ctx.grad = grad
         return loss.reshape(())
 
@@ -27,7 +35,7 @@ class _SpectralLossFn(torch.autograd.Function):
     def backward(ctx, g):
         grad = ctx.grad
         ctx.grad = None
-        return (grad * g if grad is not None else None), None, None, None, None, None
+        return (grad * g if grad is not None else None), None, None, None, None, None, None
 
 
 def _hop(n_fft, overlap):
@@ -35,9 +43,18 @@ def _hop(n_fft, overlap):
     return int(n_fft * (1 - overlap))
 
 
-def _check(x_pred, x_true, overlap):
+def _check(x_pred, x_true, overlap, n_samples=None):
+    """Host checks of the arguments -> `n_samples` as a checked list (None: rows of one length)."""
     if not 0 <= overlap < 1:
         raise ValueError("overlap must lie in [0, 1)")
+    if n_samples is None:
+        return None
+    if x_pred.dim() != 2:
+        raise ValueError("n_samples= needs (B, T) signals")
+    return hipddsp.check_n_samples(n_samples, x_pred.shape[0], x_pred.shape[1])
+
+
+def _need_device(x_pred):
     if not x_pred.is_cuda:
         raise RuntimeError("the spectral loss runs on a HIP device only (no CPU fallback)")
 
@@ -49,9 +66,14 @@ class SSSLoss(nn.Module):
         super().__init__()
         self.n_fft, self.alpha, self.overlap, self.eps = int(n_fft), alpha, overlap, eps
 
-    def forward(self, x_true, x_pred):
-        _check(x_pred, x_true, self.overlap)
-        return _SpectralLossFn.apply(x_pred, x_true.to(x_pred.dtype), [self.n_fft], self.alpha, self.eps, self.overlap)
+    def forward(self, x_true, x_pred, n_samples=None):
+        """`n_samples`: rows of different length (module docstring)."""
+        n_samples = _check(x_pred, x_true, self.overlap, n_samples)
+        if n_samples is not None:
+            hipddsp.check_loss_scales(n_samples, [self.n_fft])
+        _need_device(x_pred)
+        return _SpectralLossFn.apply(x_pred, x_true.to(x_pred.dtype), [self.n_fft], self.alpha, self.eps, self.overlap,
+                                     n_samples)
 
 
 class RSSLoss(nn.Module):
@@ -68,12 +90,19 @@ class RSSLoss(nn.Module):
         """Use these scales for the next call instead of drawing (one-shot)."""
         self._pinned = [int(n) for n in n_ffts]
 
-    def forward(self, x_pred, x_true):
-        _check(x_pred, x_true, self.overlap)
+    def forward(self, x_pred, x_true, n_samples=None):
+        """`n_samples`: rows of different length (module docstring).  The scales are drawn (and a pinned draw is used up)
+        before the counts are checked against them."""
+        n_samples = _check(x_pred, x_true, self.overlap, n_samples)
+        if n_samples is None:
+            _need_device(x_pred)
         if self._pinned is not None:
             n_ffts, self._pinned = self._pinned, None
         else:
             n_ffts = [int(v) for v in torch.randint(self.fft_min, self.fft_max, (self.n_scale,))]
         self.last_scales = n_ffts
+        if n_samples is not None:
+            hipddsp.check_loss_scales(n_samples, n_ffts)
+            _need_device(x_pred)
         # cached training audio may be fp16 (reference data_loaders.py:81-83): promote the target
-        return _SpectralLossFn.apply(x_pred, x_true.to(torch.float32), n_ffts, self.alpha, self.eps, self.overlap)
+        return _SpectralLossFn.apply(x_pred, x_true.to(torch.float32), n_ffts, self.alpha, self.eps, self.overlap, n_samples)

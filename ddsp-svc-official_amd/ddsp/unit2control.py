@@ -4,7 +4,6 @@
 The torch modules below are PARAMETER CONTAINERS only (their names reproduce the reference's
 state-dict layout so upstream checkpoints load with `load_state_dict`); none of them has a forward of
 its own.  `Unit2Control.forward` hands raw device pointers to `ddsp_unit2ctrl_fwd`.
-Only the non-causal configuration (`c: false`, every shipped config) exists; `c=True` raises.
 """
 import math
 
@@ -181,12 +180,21 @@ class Unit2Control(nn.Module):
                 ("head_g", head.weight_g), ("head_v", head.weight_v), ("head_b", head.bias)]
         return out
 
-    def backward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict, d_ctrl, ctx=None, kept=None):
+    def backward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict, d_ctrl, ctx=None, kept=None, n_frames=None,
+                      n_dev=None):
         """Gradients of every parameter for an upstream d_ctrl (B,Fr,n_out): {parameter tensor: gradient tensor}.
         `ctx`: the context of the forward call (autograd runs backward on its own thread; reusing the forward's
         context keeps one scratch arena and one profiler per model call).  `kept`: the activation region of a
-        `forward_flat_keep` call on the same inputs and weights - without it the forward is re-run inside the call."""
+        `forward_flat_keep` call on the same inputs and weights - without it the forward is re-run inside the call.
+        `n_frames` (as `forward_flat` takes it): a ragged batch - every gradient is the sum over rows of the gradient that row
+        gives alone at its own length, whatever the padding of the inputs and of d_ctrl holds.  `n_dev` instead: the counts
+        on the device, with the inputs already in held form (`hold_ragged`) and d_ctrl 0 on every row's padding - what
+        the synthesisers' autograd node passes."""
         ctx = ctx or hipddsp.context_for(units.device)
+        if n_frames is not None:
+            vals = self.check_ragged(n_frames, units.shape[0], units.shape[1])
+            n_dev, units, f0, phase, volume = self.hold_ragged(ctx, vals, units, f0, phase, volume)
+            d_ctrl = ctx.ragged_frames(d_ctrl, n_dev, hold=False)
         w, keep = self._weights_struct()
         g = hipddsp.U2CWeights()
         grads = {}
@@ -207,9 +215,9 @@ class Unit2Control(nn.Module):
             setattr(g, name, gt.data_ptr())
         g.n_spk, g.n_unit, g.n_out = self.n_spk, self.n_unit, self.n_out
         if kept is not None:
-            ctx.unit2ctrl_bwd_kept(w, g, units, f0, phase, volume, spk_id, spk_mix_dict, kept, d_ctrl)
+            ctx.unit2ctrl_bwd_kept(w, g, units, f0, phase, volume, spk_id, spk_mix_dict, kept, d_ctrl, n_frames=n_dev)
         else:
-            ctx.unit2ctrl_bwd(w, g, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, d_ctrl)
+            ctx.unit2ctrl_bwd(w, g, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, d_ctrl, n_frames=n_dev)
         return grads
 
     def rebind(self):
@@ -226,9 +234,14 @@ class Unit2Control(nn.Module):
         `spk_mix_dict` (`hipddsp.check_mix_rows`; inference only, the callers check that).
         `n_frames` (a sequence of B ints or a CPU integer tensor (B,), 1 <= n_frames[b] <= Fr): a ragged batch - the first
         n_frames[b] rows of ctrl[b] are what the network gives for that row alone at its own length, whatever the padding of
-        the inputs holds; the rows after them carry no meaning.  Inference only."""
+        the inputs holds; the rows after them carry no meaning.  Inference only: this call records nothing for autograd
+        (NotImplementedError with grad mode on and a parameter that wants a gradient); the training pair of a ragged batch is
+        `forward_ragged_keep` / `backward_flat(n_frames= | n_dev=)`."""
         if n_frames is not None:
-            vals = self.check_ragged(n_frames, units.shape[0], units.shape[1], "the network under torch.no_grad()")
+            vals = self.check_ragged(n_frames, units.shape[0], units.shape[1])
+            if self.wants_grad():
+                raise NotImplementedError("forward_flat(n_frames=) is inference only: it records nothing for autograd; call it "
+                                          "under torch.no_grad() (training: forward_ragged_keep / backward_flat)")
             ctx = hipddsp.context_for(units.device)
             n_dev, units, f0, phase, volume = self.hold_ragged(ctx, vals, units, f0, phase, volume)
             return self.forward_ragged(ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=False,
@@ -241,14 +254,10 @@ class Unit2Control(nn.Module):
         """True when a call must be recorded for autograd (grad mode on and some parameter wants a gradient)."""
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
-    def check_ragged(self, n_frames, B, Fr, advice):
-        """Head of a ragged call, host half, before anything is launched: `n_frames` as a checked list (ValueError), and the
-        inference-only refusal (NotImplementedError; `advice`: what the caller should call under no_grad instead)."""
-        vals = hipddsp.check_n_frames(n_frames, B, Fr)
-        if self.wants_grad():
-            raise NotImplementedError("n_frames= (ragged batches) is inference only: there is no ragged backward pass; call "
-                                      + advice)
-        return vals
+    def check_ragged(self, n_frames, B, Fr):
+        """Head of a ragged call, host half, before anything is launched: `n_frames` as a checked list (ValueError).  (What a
+        caller refuses under grad mode is its own business: the synthesisers an eval-mode model, `forward_flat` every call.)"""
+        return hipddsp.check_n_frames(n_frames, B, Fr)
 
     def hold_ragged(self, ctx, vals, units, f0, phase, volume):
         """Head of a ragged call, device half: uploads the counts once and puts the frame-rate inputs into held form - units,
@@ -277,6 +286,14 @@ class Unit2Control(nn.Module):
         ctx = ctx or hipddsp.context_for(units.device)
         w, keep = self._weights_struct()
         return ctx.unit2ctrl_keep(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out)
+
+    def forward_ragged_keep(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=True):
+        """`forward_flat_keep` of a ragged batch in the form `forward_ragged` takes (counts on the device, inputs from
+        `hold_ragged`): (control matrix, kept activations) for `backward_flat(kept=..., n_dev=...)` on the same inputs.  hold:
+        as there - its adjoint, `Context.ragged_frames_adjoint_`, is then the caller's to apply to d_ctrl."""
+        w, keep = self._weights_struct()
+        ctrl, kept = ctx.unit2ctrl_keep(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, n_frames=n_dev)
+        return (ctx.ragged_frames(ctrl, n_dev, hold=True, out=ctrl) if hold else ctrl), kept
 
     def forward(self, units, f0, phase, volume, spk_id, spk_mix_dict=None):
         """Same contract as the reference `Unit2Control.forward` (`ddsp/unit2control.py:68-101`):

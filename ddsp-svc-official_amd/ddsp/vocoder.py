@@ -13,8 +13,13 @@ Differences a caller can observe, all additive:
     1 <= n_frames[b] <= Fr) gives the frames of each row inside the padded (B, Fr, ...) inputs; row b of every returned
     tensor is then, over its first n_frames[b] frames / n_frames[b] * block_size samples, what the model returns for that
     row alone at its own length, and exactly 0.0 after them.  What the padding of units / f0 / volume / noise holds (zeros,
-    garbage, NaN) does not matter.  Inference only: with grad mode on and a parameter that wants a gradient it raises
-    NotImplementedError.  With `noise_seed=` the draw is repeatable but not the draw of the rows' solo calls.
+    garbage, NaN) does not matter.  With `noise_seed=` the draw is repeatable but not the draw of the rows' solo calls.
+    Training too: on a model in training mode (`model.train()`, as every training loop sets it) the call is recorded under
+    grad mode like the one without counts, and the gradient of every parameter is the sum over rows of the gradient the
+    model gives for that row alone (its inputs, noise and upstream gradients cropped to the row); what the upstream
+    gradients hold past a row's end does not matter either.  A model in eval mode keeps the refusal it always had: with grad
+    mode on and a parameter that wants a gradient a ragged call raises NotImplementedError (an inference caller that forgot
+    torch.no_grad() would otherwise keep the activations of every call).
   * `forward(..., spk_mix_rows=(ids, w))`: a speaker mix PER ROW as device data.  `ids` (B, K) int32 (1-based) and `w`
     (B, K) fp32, 1 <= K <= 16, both on the model's device; row b adds sum_k w[b, k] * spk_embed[ids[b, k] - 1] in slot
     order.  A slot {id 1, weight 0} pads a shorter row, the row {id: 1.0} is a plain speaker id
@@ -366,7 +371,8 @@ def _seed_from_torch():
 class _SynthBase(torch.nn.Module):
     """What the three synthesisers share: one `forward` body (`_forward`) and the protocol of the autograd node.  A model
     states `_comb_mode` / `_front_wants` (the comb the phase scan writes, and `want_phase`: nowhere else) and supplies
-    `_render` (its DSP chain, written once) and `_train_backward` (the chain's adjoint)."""
+    `_render` (its DSP chain, written once) and `_train_backward` (the chain's adjoint; `crop` from `_crop`, applied to a
+    gradient wherever `_render` cropped the signal between two stages - the upstream gradients arrive cropped)."""
 
     def __init__(self, sampling_rate, block_size):
         super().__init__()
@@ -399,13 +405,18 @@ class _SynthBase(torch.nn.Module):
         `math=ctx.fir_math`; `ctx.ltv_fir` itself defaults to fp32 products."""
         raise NotImplementedError
 
+    def _crop(self, ctx, n_dev, Fr):
+        """`crop(*signals)`: zeroes (B, T) signals past every row's end in place (ragged; None entries are skipped) or does
+        nothing.  A chain crops every signal before it enters the next filter; the crop is its own adjoint, so the chain's
+        adjoint (`_train_backward`) crops the gradient at the same places."""
+        return (lambda *xs: ctx.ragged_crop_(n_dev, Fr, self._hop, *xs)) if n_dev is not None else (lambda *xs: None)
+
     def _stages(self, ctx, n_dev, Fr, keep):
-        """(crop, saved, save) of a chain: `crop(*signals)` zeroes them past every row's end (ragged) or does nothing;
-        `save(tensors)` appends to `saved` in a training forward and drops them in inference, where an impulse-response
-        matrix - the largest tensors of a forward - is released as soon as the next one replaces it."""
-        crop = (lambda *xs: ctx.ragged_crop_(n_dev, Fr, self._hop, *xs)) if n_dev is not None else (lambda *xs: None)
+        """(crop, saved, save) of a chain: `crop` as `_crop` gives it; `save(tensors)` appends to `saved` in a training
+        forward and drops them in inference, where an impulse-response matrix - the largest tensors of a forward - is
+        released as soon as the next one replaces it."""
         saved = [] if keep else None
-        return crop, saved, (saved.extend if keep else (lambda xs: None))
+        return self._crop(ctx, n_dev, Fr), saved, (saved.extend if keep else (lambda xs: None))
 
     def _ragged_noise(self, ctx, n_dev, B, Fr, noise, noise_seed):
         """(unit-noise draw (B,T) with 0.5 - no excitation - past every row's end, EXC_UNIT_NOISE, 0)."""
@@ -463,9 +474,16 @@ class _SynthBase(torch.nn.Module):
             self._check_mix_rows(spk_mix_dict, spk_mix_rows, B)
         if B == 0:
             return self._empty_result(f0_frames)
-        if n_frames is not None:
-            vals = self.unit2ctrl.check_ragged(n_frames, B, Fr, "the model under torch.no_grad() (training crops every clip to "
-                                               "one length)")
+        vals = None if n_frames is None else self.unit2ctrl.check_ragged(n_frames, B, Fr)
+        if vals is not None and not self.training and self.unit2ctrl.wants_grad():
+            raise NotImplementedError("n_frames= (ragged batches) on a model in eval mode is inference only: call the model "
+                                      "under torch.no_grad(), or put it into training mode (model.train()) to have the ragged "
+                                      "call recorded for autograd")
+        if self.unit2ctrl.wants_grad():
+            phase, *outs = _SynthTrainFn.apply(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict,
+                                               initial_phase, infer, noise, noise_seed, vals, *self.unit2ctrl.parameters())
+            return self._result(phase, outs)
+        if vals is not None:
             ctx = self._context(f0_frames, ragged=True)
             n_dev, units, f0, _, volume = self.unit2ctrl.hold_ragged(ctx, vals, units_frames, f0_frames, None, volume_frames)
             f0 = f0.reshape(B, Fr, 1)
@@ -473,10 +491,6 @@ class _SynthBase(torch.nn.Module):
             ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], volume, spk_id, spk_mix_dict, n_dev,
                                                  spk_mix_rows=spk_mix_rows)
             excitation = lambda: self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
-        elif self.unit2ctrl.wants_grad():
-            phase, *outs = _SynthTrainFn.apply(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict,
-                                               initial_phase, infer, noise, noise_seed, *self.unit2ctrl.parameters())
-            return self._result(phase, outs)
         else:
             n_dev, f0 = None, f0_frames
             ctx = self._context(f0)
@@ -491,13 +505,23 @@ class _SynthBase(torch.nn.Module):
 class _SynthTrainFn(torch.autograd.Function):
     """Autograd node of one synthesiser forward: forward and backward are libddsp_amd calls end to end; torch only
     routes the parameter gradients (reference: autograd through `*.forward`, solver.py:111-113).  The model supplies
-    `_render(ctx, ctrl, ps, f0_frames, excitation, keep=True) -> (outputs, saved)` and
-    `_train_backward(ctx, ctrl, saved, f0_frames, noise_args, grads) -> d_ctrl (rows, sum)`."""
+    `_render(ctx, ctrl, ps, f0_frames, excitation, n_dev, keep=True) -> (outputs, saved)` and
+    `_train_backward(ctx, ctrl, saved, f0_frames, noise_args, grads, crop) -> d_ctrl (rows, sum)`.
+    `vals`: the checked counts of a ragged batch or None.  Ragged, the forward is the ragged inference forward with its
+    activations kept (held inputs, the control matrix held over the padding, the noise draw of `_ragged_noise`, every
+    signal cropped), and the backward its adjoint: the upstream gradients are cropped to the rows, the chain's adjoint crops
+    where the chain cropped, the adjoint of the hold folds the padding frames of d_ctrl into each row's last frame, and
+    the control network's backward takes the counts."""
 
     @staticmethod
-    def forward(fctx, model, units, f0_frames, volume, spk_id, spk_mix_dict, initial_phase, infer, noise, noise_seed,
+    def forward(fctx, model, units, f0_frames, volume, spk_id, spk_mix_dict, initial_phase, infer, noise, noise_seed, vals,
                 *params):
-        ctx = model._context(f0_frames)
+        ctx = model._context(f0_frames, ragged=vals is not None)
+        B, Fr = units.shape[0], units.shape[1]
+        n_dev = None
+        if vals is not None:
+            n_dev, units, f0, _, volume = model.unit2ctrl.hold_ragged(ctx, vals, units, f0_frames, None, volume)
+            f0_frames = f0.reshape(B, Fr, 1)
         ps = model._scan(ctx, f0_frames, initial_phase, infer)
         # the training forward runs fp32 products throughout (control network, filter synthesis, FIR): the loss gradient
         # amplifies a 4e-6 error of the signal a thousandfold (tools/diag_train_b32.py).  The BACKWARD runs on the
@@ -506,31 +530,42 @@ class _SynthTrainFn(torch.autograd.Function):
         keep_math = ctx.math
         ctx.set_math(hipddsp.MATH_FP32)
         try:
-            ctrl, kept = model.unit2ctrl.forward_flat_keep(units, f0_frames, ps["phase_frames"], volume, spk_id,
-                                                           spk_mix_dict, ctx=ctx)
-            nargs = model._noise_args(noise, noise_seed)
-            outs, saved = model._render(ctx, ctrl, ps, f0_frames, lambda: nargs, keep=True)
+            if n_dev is None:
+                ctrl, kept = model.unit2ctrl.forward_flat_keep(units, f0_frames, ps["phase_frames"], volume, spk_id,
+                                                               spk_mix_dict, ctx=ctx)
+                nargs = model._noise_args(noise, noise_seed)
+            else:
+                ctrl, kept = model.unit2ctrl.forward_ragged_keep(ctx, units, f0_frames, ps["phase_frames"], volume, spk_id,
+                                                                 spk_mix_dict, n_dev)
+                nargs = model._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
+            outs, saved = model._render(ctx, ctrl, ps, f0_frames, lambda: nargs, n_dev, keep=True)
         finally:
             ctx.set_math(keep_math)
         fctx.model, fctx.dsp = model, ctx
         fctx.set_materialize_grads(False)   # outputs the loss does not use arrive as None in backward, not as zero tensors to add
-        fctx.args = (units, f0_frames, volume, spk_id, spk_mix_dict, nargs, ps["phase_frames"])
+        fctx.args = (units, f0_frames, volume, spk_id, spk_mix_dict, nargs, ps["phase_frames"], n_dev)
         fctx.saved = (ctrl, saved, kept)
-        phase_out = model._phase_out(ctx, ps)
+        phase_out = model._phase_out(ctx, ps, n_dev)
         fctx.mark_non_differentiable(phase_out)
         return (phase_out,) + tuple(outs)
 
     @staticmethod
     def backward(fctx, d_phase, *d_outs):
         model, ctx = fctx.model, fctx.dsp
-        units, f0_frames, volume, spk_id, spk_mix_dict, nargs, phase_frames = fctx.args
+        units, f0_frames, volume, spk_id, spk_mix_dict, nargs, phase_frames, n_dev = fctx.args
         if fctx.saved is None:
             raise RuntimeError("this synthesiser forward was already back-propagated (its kept activations are released)")
         ctrl, saved, kept = fctx.saved
         B, Fr = ctrl.shape[0], ctrl.shape[1]
-        d_ctrl = model._train_backward(ctx, ctrl, saved, f0_frames, nargs, d_outs)
-        grads = model.unit2ctrl.backward_flat(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict,
-                                              d_ctrl.reshape(B, Fr, -1), ctx=ctx, kept=kept)
+        crop = model._crop(ctx, n_dev, Fr)
+        if n_dev is not None:   # (copies: the upstream gradients are autograd's)
+            d_outs = tuple(None if g is None else g.float().contiguous().clone() for g in d_outs)
+            crop(*d_outs)
+        d_ctrl = model._train_backward(ctx, ctrl, saved, f0_frames, nargs, d_outs, crop).reshape(B, Fr, -1)
+        if n_dev is not None:
+            ctx.ragged_frames_adjoint_(d_ctrl, n_dev)
+        grads = model.unit2ctrl.backward_flat(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, d_ctrl, ctx=ctx,
+                                              kept=kept, n_dev=n_dev)
         fctx.saved = None
         params = tuple(grads.get(p) for p in model.unit2ctrl.parameters())
         return (None,) * (len(fctx.needs_input_grad) - len(params)) + params      # no gradient for what precedes *params
@@ -587,7 +622,7 @@ class CombSub(_SynthBase):
         save((ir,))
         return (signal, harmonic, noise_out), saved
 
-    def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs):
+    def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs, crop):
         comb, h1, ir_ap, ir_h, ir_n = saved
         d_signal, d_harm, d_noise = d_outs
         B, Fr = ctrl.shape[0], ctrl.shape[1]
@@ -601,6 +636,7 @@ class CombSub(_SynthBase):
         _, d_ir = ctx.ltv_fir_bwd(nz, ir_n, d_n, B, Fr, hop, excitation=exc, noise_seed=seed, want_d_audio=False)
         ctx.fir_from_ctrl_bwd(FIR_STATIC, c2, na + nh, nn_, rows, sr, d_ir, d_ctrl)
         d_h1, d_ir = ctx.ltv_fir_bwd(h1, ir_h, d_h, B, Fr, hop)
+        crop(d_h1)
         ctx.fir_from_ctrl_bwd(FIR_DYNAMIC, c2, na, nh, rows, sr, d_ir, d_ctrl, f0_frames)
         _, d_ir = ctx.ltv_fir_bwd(comb, ir_ap, d_h1, B, Fr, hop, want_d_audio=False)
         ctx.fir_from_ctrl_bwd(FIR_ALLPASS, c2, 0, na, rows, sr, d_ir, d_ctrl)
@@ -651,7 +687,7 @@ class Sins(_SynthBase):
         save((ir,))
         return (signal, harmonic, noise_out), saved
 
-    def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs):
+    def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs, crop):
         phase, sinusoids, ir_ap, ir_n = saved
         d_signal, d_harm, d_noise = d_outs
         B, Fr = ctrl.shape[0], ctrl.shape[1]
@@ -665,6 +701,7 @@ class Sins(_SynthBase):
         _, d_ir = ctx.ltv_fir_bwd(nz, ir_n, d_n, B, Fr, hop, excitation=exc, noise_seed=seed, want_d_audio=False)
         ctx.fir_from_ctrl_bwd(FIR_STATIC, c2, nhm + na, nn_, rows, sr, d_ir, d_ctrl)
         d_sin, d_ir = ctx.ltv_fir_bwd(sinusoids, ir_ap, d_h, B, Fr, hop)
+        crop(d_sin)
         ctx.fir_from_ctrl_bwd(FIR_ALLPASS, c2, nhm, na, rows, sr, d_ir, d_ctrl)
         ctx.sins_bank_bwd(c2, 0, nhm, f0_frames, phase, d_sin, B, Fr, hop, sr, d_ctrl)
         return d_ctrl
@@ -707,7 +744,7 @@ class CombSubFast(_SynthBase):
         save((comb,))
         return (signal,), saved
 
-    def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs):
+    def _train_backward(self, ctx, ctrl, saved, f0_frames, nargs, d_outs, crop):
         (comb,) = saved
         B, Fr = ctrl.shape[0], ctrl.shape[1]
         nz, exc, seed = nargs

@@ -252,6 +252,17 @@ SIGNATURES = {
     "ddsp_unit2ctrl_bwd_kept": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
                                        _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _i64, _vp,
                                        _c.POINTER(U2CWeights)]),
+    "ddsp_unit2ctrl_fwd_keep_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
+                                              _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "ddsp_unit2ctrl_bwd_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
+                                         _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp,
+                                         _c.POINTER(U2CWeights), _vp]),
+    "ddsp_unit2ctrl_bwd_kept_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
+                                              _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _i64, _vp,
+                                              _c.POINTER(U2CWeights)]),
+    "ddsp_ragged_frames_adjoint": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64]),
+    "ddsp_rss_loss_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
+                                    _int, _f32, _f32, _vp, _vp]),
 }
 
 _lib = None
@@ -319,6 +330,15 @@ def check_n_samples(n_samples, B, T):
         if not 1 <= v <= int(T):
             raise ValueError(f"n_samples[{b}] = {v} is outside 1..T={int(T)}")
     return vals
+
+
+def check_loss_scales(n_samples, n_ffts):
+    """The spectral loss over rows of different length (`n_samples`: the list `check_n_samples` returned): at every scale
+    some row must hold a whole frame (n_samples[b] >= n_fft), else there is nothing to average (ValueError, a host check)."""
+    for n in n_ffts:
+        if max(n_samples) < int(n):
+            raise ValueError(f"n_samples: no row holds a whole frame at scale n_fft = {int(n)} (longest row: {max(n_samples)} "
+                             "samples)")
 
 
 def check_hubert_n_samples(n_samples, B, T):
@@ -588,6 +608,15 @@ class Context:
         self.call("ddsp_ragged_frames", _ptr(x), _ptr(n_dev), B, Fr, C, 1 if hold else 0, _ptr(out))
         return out
 
+    def ragged_frames_adjoint_(self, d, n_dev):
+        """In place on a gradient d (B,Fr,C) fp32: the adjoint of `ragged_frames(hold=True)` - frame n_b - 1 of every row
+        collects the gradient of the frames behind it (ascending order), which are then 0."""
+        if d.dtype != torch.float32 or not d.is_contiguous() or d.dim() not in (2, 3):
+            raise ValueError("ragged_frames_adjoint_: a contiguous fp32 (B, Fr, C) or (B, Fr) tensor")
+        B, Fr = d.shape[0], d.shape[1]
+        self.call("ddsp_ragged_frames_adjoint", _ptr(d), _ptr(self._counts_dev(n_dev, B)), B, Fr, d.numel() // max(B * Fr, 1))
+        return d
+
     def ragged_crop_(self, n_dev, Fr, hop, *signals):
         """In place: up to three (B, Fr*hop) fp32 signals are set to 0 from sample n_b * hop on."""
         xs = [s for s in signals if s is not None]
@@ -610,13 +639,19 @@ class Context:
         return out
 
     def unit2ctrl_bwd(self, weights, grads, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out,
-                      d_ctrl, want_ctrl=False):
-        """Back-propagates d_ctrl (B,Fr,n_out) into the tensors `grads` points at (same struct layout as `weights`)."""
+                      d_ctrl, want_ctrl=False, n_frames=None):
+        """Back-propagates d_ctrl (B,Fr,n_out) into the tensors `grads` points at (same struct layout as `weights`).
+        n_frames: the (B,) int32 device tensor of a ragged batch (`ragged_counts`); units and d_ctrl past a row's count must
+        be 0 and the other inputs finite there."""
         B, Fr, _ = units.shape
         d_ctrl = d_ctrl.contiguous().float()
         ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32) if want_ctrl else None
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        self.call("ddsp_unit2ctrl_bwd", ctypes.byref(weights), *args, _ptr(d_ctrl), ctypes.byref(grads), _ptr(ctrl))
+        if n_frames is not None:
+            self.call("ddsp_unit2ctrl_bwd_ragged", ctypes.byref(weights), *args, _ptr(self._counts_dev(n_frames, B)), _ptr(d_ctrl),
+                      ctypes.byref(grads), _ptr(ctrl))
+        else:
+            self.call("ddsp_unit2ctrl_bwd", ctypes.byref(weights), *args, _ptr(d_ctrl), ctypes.byref(grads), _ptr(ctrl))
         return ctrl
 
     def _u2c_inputs(self, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict):
@@ -641,9 +676,10 @@ class Context:
                 raise ValueError(f"spk_id must hold 1 or B={B} ids, got {n_sid}")
         return (units, f0, ph, vol, sid), (_ptr(units), _ptr(f0), _ptr(ph), _ptr(vol), _ptr(sid), n_sid, ids, ws, n_mix, B, Fr)
 
-    def unit2ctrl_keep(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out):
+    def unit2ctrl_keep(self, weights, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out, n_frames=None):
         """Training forward (fp32 products) that keeps its activations: -> (ctrl (B,Fr,n_out), keep) where `keep` is the
-        uint8 device tensor `unit2ctrl_bwd_kept` back-propagates from (the caller holds it until then)."""
+        uint8 device tensor `unit2ctrl_bwd_kept` back-propagates from (the caller holds it until then).
+        n_frames: the (B,) int32 device tensor of a ragged batch, as `unit2ctrl` takes it."""
         B, Fr, _ = units.shape
         nbytes = int(self.lib.ddsp_unit2ctrl_keep_bytes(ctypes.byref(weights), B, Fr))
         if nbytes < 0:
@@ -651,15 +687,25 @@ class Context:
         keep = torch.empty(nbytes, device=units.device, dtype=torch.uint8)
         ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        self.call("ddsp_unit2ctrl_fwd_keep", ctypes.byref(weights), *args, _ptr(keep), nbytes, _ptr(ctrl))
+        if n_frames is not None:
+            self.call("ddsp_unit2ctrl_fwd_keep_ragged", ctypes.byref(weights), *args, _ptr(self._counts_dev(n_frames, B)), _ptr(keep),
+                      nbytes, _ptr(ctrl))
+        else:
+            self.call("ddsp_unit2ctrl_fwd_keep", ctypes.byref(weights), *args, _ptr(keep), nbytes, _ptr(ctrl))
         return ctrl, keep
 
-    def unit2ctrl_bwd_kept(self, weights, grads, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, keep, d_ctrl):
-        """Back-propagates d_ctrl from the activations `unit2ctrl_keep` left in `keep` (no second forward)."""
+    def unit2ctrl_bwd_kept(self, weights, grads, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, keep, d_ctrl,
+                           n_frames=None):
+        """Back-propagates d_ctrl from the activations `unit2ctrl_keep` left in `keep` (no second forward); `n_frames` as
+        that call had it (`unit2ctrl_bwd` says what a ragged batch asks of the inputs)."""
         d_ctrl = d_ctrl.contiguous().float()
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        self.call("ddsp_unit2ctrl_bwd_kept", ctypes.byref(weights), *args, _ptr(keep), keep.numel(), _ptr(d_ctrl),
-                  ctypes.byref(grads))
+        if n_frames is not None:
+            self.call("ddsp_unit2ctrl_bwd_kept_ragged", ctypes.byref(weights), *args, _ptr(self._counts_dev(n_frames, units.shape[0])),
+                      _ptr(keep), keep.numel(), _ptr(d_ctrl), ctypes.byref(grads))
+        else:
+            self.call("ddsp_unit2ctrl_bwd_kept", ctypes.byref(weights), *args, _ptr(keep), keep.numel(), _ptr(d_ctrl),
+                      ctypes.byref(grads))
 
     # -- a5-a6 ---------------------------------------------------------------------------------
     def fir_from_ctrl(self, mode, ctrl2d, col0, n_mag, rows, sr, f0_frames=None):
@@ -1191,9 +1237,10 @@ class Context:
         return d_ctrl
 
     # -- a13 -----------------------------------------------------------------------------------
-    def rss_loss(self, x_pred, x_true, n_ffts, alpha=1.0, eps=1e-7, want_grad=False, hops=None):
+    def rss_loss(self, x_pred, x_true, n_ffts, alpha=1.0, eps=1e-7, want_grad=False, hops=None, n_samples=None):
         """-> (loss (1,) device tensor, d loss/d x_pred (B,T) | None) for the given list of scales; `hops`: one hop per
-        scale (default: hop = n_fft, the reference's overlap = 0)."""
+        scale (default: hop = n_fft, the reference's overlap = 0).  `n_samples`: the list `check_n_samples` returned -
+        rows of different length (include/ddsp_amd.h: ddsp_rss_loss_ragged)."""
         xp = x_pred.detach().contiguous().float()
         xt = x_true.detach().contiguous().float()
         B, T = xp.shape
@@ -1207,8 +1254,13 @@ class Context:
         harr = (_int * len(n_ffts))(*[int(h) for h in hops]) if hops is not None else None
         loss = torch.empty(1, device=xp.device, dtype=torch.float32)
         grad = torch.empty_like(xp) if want_grad else None
-        self.call("ddsp_rss_loss", _ptr(xp), _ptr(xt), B, T, arr, harr, len(n_ffts), float(alpha), float(eps), _ptr(loss),
-                  _ptr(grad))
+        if n_samples is not None:
+            ns = (_int * B)(*n_samples)
+            self.call("ddsp_rss_loss_ragged", _ptr(xp), _ptr(xt), B, T, ns, _ptr(self.ragged_counts(n_samples)), arr, harr,
+                      len(n_ffts), float(alpha), float(eps), _ptr(loss), _ptr(grad))
+        else:
+            self.call("ddsp_rss_loss", _ptr(xp), _ptr(xt), B, T, arr, harr, len(n_ffts), float(alpha), float(eps), _ptr(loss),
+                      _ptr(grad))
         return loss, grad
 
     # -- a14 -----------------------------------------------------------------------------------

@@ -107,16 +107,32 @@ def train_step(model, optimizer, loss_fn, batch, world=1, scales=None, bucket=No
     """One step of `solver.train` (`solver.py:110-114`): zero_grad -> forward(infer=False) -> loss -> backward -> step.
     `scales` pins the loss's n_fft draw (ranks of a data-parallel job must share it; both terms of the loss
     are batch means, `ddsp/loss.py:20-22`, so with equal shards the mean of the rank losses is the global loss and the
-    mean of the rank gradients its gradient).  `bucket`: a GradBucket over the model's parameters (one flat collective)."""
+    mean of the rank gradients its gradient).  `bucket`: a GradBucket over the model's parameters (one flat collective).
+    `batch["n_frames"]` (B ints, optional): a ragged batch of whole utterances - the counts go to the model, and times the
+    block size to the loss, whose terms are then means over the rows' own frames.  One process only: ranks with unequal
+    shards hold unequal numbers of loss cells, so the mean of the rank losses is no longer the global loss (`world > 1`
+    with `n_frames` raises ValueError)."""
+    n_frames = batch.get("n_frames")
+    ragged = {}
+    if n_frames is not None:
+        if world != 1:
+            raise ValueError("train_step: a ragged batch (n_frames) trains on one process - the mean of the rank losses of "
+                             "unequal shards is not the global loss")
+        n_frames = hipddsp.check_n_frames(n_frames, batch["units"].shape[0], batch["units"].shape[1])
+        ragged = {"n_frames": n_frames}
     if bucket is not None:
         bucket.zero()
     else:
         optimizer.zero_grad()
     signal, _, _ = model(batch["units"].float(), batch["f0"], batch["volume"], batch["spk_id"], infer=False,
-                         **({"noise": batch["noise"]} if "noise" in batch else {}))
+                         **({"noise": batch["noise"]} if "noise" in batch else {}), **ragged)
     if scales is not None:
         loss_fn.set_scales(scales)
-    loss = loss_fn(signal, batch["audio"])
+    if n_frames is not None:
+        hop = signal.shape[1] // batch["units"].shape[1]
+        loss = loss_fn(signal, batch["audio"], n_samples=[n * hop for n in n_frames])
+    else:
+        loss = loss_fn(signal, batch["audio"])
     loss.backward()
     if bucket is not None:
         bucket.allreduce(world)

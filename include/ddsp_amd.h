@@ -158,7 +158,7 @@ int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weig
                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
                        const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, float* ctrl);
 
-/* ---- ragged batches: rows of different length in one padded (B, Fr, ...) call, inference only ------------------------------
+/* ---- ragged batches: rows of different length in one padded (B, Fr, ...) call (training: the _ragged forms further down) ----
  * n_frames: DEVICE array of B int32, 1 <= n_frames[b] <= Fr (the caller checks it; the kernels hold a value outside the range
  * at its nearest bound).  Row b comes out as if it had been computed alone with Fr = n_frames[b].
  *
@@ -238,6 +238,29 @@ int ddsp_unit2ctrl_bwd_kept(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights*
                             const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep, int64_t keep_bytes,
                             const float* d_ctrl, const ddsp_u2c_weights* grads_host);
 
+/* Ragged training (n_frames as for ddsp_unit2ctrl_fwd_ragged, or NULL: the calls above).  The forward keeps or re-runs the
+ * ragged forward; units of frames >= n_frames[b] must hold 0 and f0, phase and volume finite values there (ddsp_ragged_frames),
+ * and d_ctrl must be 0 on those frames (ddsp_ragged_frames with hold = 0, or ddsp_ragged_frames_adjoint).  Every gradient is
+ * then the sum over rows of the gradient the row gives alone at its own length. */
+int ddsp_unit2ctrl_fwd_keep_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* w, const float* units,
+                                   const float* f0_frames, const float* phase_frames, const float* volume,
+                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                   const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                   void* keep, int64_t keep_bytes, float* ctrl);
+int ddsp_unit2ctrl_bwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
+                              const float* f0_frames, const float* phase_frames, const float* volume,
+                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                              const float* d_ctrl, const ddsp_u2c_weights* grads_host, float* ctrl_out);
+int ddsp_unit2ctrl_bwd_kept_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* w, const float* units,
+                                   const float* f0_frames, const float* phase_frames, const float* volume,
+                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
+                                   const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                   void* keep, int64_t keep_bytes, const float* d_ctrl, const ddsp_u2c_weights* grads_host);
+/* Adjoint of ddsp_ragged_frames with hold = 1, in place on a gradient d (B, Fr, C): d[b][n_b - 1][:] += sum_{i >= n_b} d[b][i][:]
+ * (i ascending: a fixed order), then d[b][i >= n_b][:] = 0.  ddsp_ragged_crop is its own adjoint. */
+int ddsp_ragged_frames_adjoint(ddsp_ctx* ctx, void* stream, float* d, const int32_t* n_frames, int64_t B, int64_t Fr, int64_t C);
+
 /* ---- backward of a5-a8 (training: reference autograd through frequency_filter, solver.py:113) ------------ */
 /* Adjoints of ddsp_ltv_fir for an upstream gradient d_out (B,T): d_audio (B,T) or NULL = gradient w.r.t. the
  * input signal; d_ir (B,Fr,n) or NULL = gradient w.r.t. the filter frames (needs the forward input: audio with
@@ -289,6 +312,15 @@ int ddsp_spectral_ola_bwd(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_
 int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
                   const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps, float* loss,
                   float* grad_pred);
+/* The same for rows of different length: n_samples_host (B ints, 1 <= n <= T) and the same counts on the device
+ * (n_samples_dev, int32).  Row b has F_b = (n_b - N) / hop + 1 frames at scale N (0 when n_b < N).  The convergence term is the
+ * mean over the rows with F_b > 0, each norm over the row's own frames; the log term the mean over the sum_b F_b * (N/2 + 1)
+ * cells that exist.  Samples from (F_b - 1) * hop + N on are not read into arithmetic (selection), and grad_pred is 0 there.
+ * With every count == T the result has the bits of ddsp_rss_loss.  A scale at which no row has a frame: DDSP_ERR_ARG before
+ * anything is launched. */
+int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                         const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host, const int* hops_host,
+                         int n_scale, float alpha, float eps, float* loss, float* grad_pred);
 
 /* ---- a14: SOLA splice of the real-time path -------------------------------------------------- */
 /* replaces gui.py:405-430: within audio[-block-xfade-search-delay : -delay] find the lag (0..search) that
