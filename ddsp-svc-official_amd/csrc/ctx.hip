@@ -240,6 +240,9 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
     if (code == DDSP_DEV_ERR_SPK_ID)
         return ddsp_fail(ctx, DDSP_ERR_ARG, "spk_id out of range [1, n_spk] in an earlier ddsp_unit2ctrl call",
                          "the speaker embedding of those rows was skipped (the reference's nn.Embedding raises)");
+    if (code == DDSP_DEV_ERR_DATASET)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a (file, start_frame, unit_idx) triple outside its file in an earlier ddsp_dataset_gather call",
+                         "those rows were written as zeros and nothing was read for them");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

@@ -127,6 +127,14 @@ class WeightTable:
         return w, keep
 
 
+class DatasetView(_c.Structure):
+    """Mirror of `ddsp_dataset_view` (include/ddsp_amd.h): device pointers to a packed dataset's arenas and per-file tables."""
+    _fields_ = ([(n, _vp) for n in ("audio", "units", "f0", "volume", "audio_off", "audio_len", "frame_off", "frames",
+                                    "spk_id", "duration", "next_valid")]
+                + [("n_files", _i64), ("total_frames", _i64)]
+                + [(n, _c.c_int32) for n in ("n_aunit", "n_unit", "hop", "sample_rate", "fp16")])
+
+
 class ProfEntry(_c.Structure):
     """Mirror of `ddsp_prof_entry`."""
     _fields_ = [("family", _int), ("name", _c.c_char * 36), ("launches", _i64), ("ms_total", _c.c_double),
@@ -263,6 +271,8 @@ SIGNATURES = {
     "ddsp_ragged_frames_adjoint": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64]),
     "ddsp_rss_loss_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
                                     _int, _f32, _f32, _vp, _vp]),
+    "ddsp_dataset_gather": (_int, [_vp, _vp, _c.POINTER(DatasetView), _vp, _vp, _i64, _i64, _u64, _vp, _i64, _f64, _i64, _i64,
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -637,6 +647,35 @@ class Context:
                 raise ValueError(f"noise must be (B, Fr*hop) = {(B, Fr * hop)}, got {tuple(noise.shape)}")
         self.call("ddsp_ragged_noise", _ptr(noise), int(noise_seed) & ((1 << 64) - 1), _ptr(n_dev), B, Fr, int(hop), _ptr(out))
         return out
+
+    def dataset_gather(self, view, B, Fr_out, triples=None, perm=None, cursor=0, seed=0, len_rows=None, crop_frames=0,
+                       waveform_sec=0.0, out=None):
+        """One training batch of B rows from a packed dataset (`DatasetView`; `data_loaders.AudioDataset` builds one) in one
+        launch.  triples (B,3) int32 device: the rows' (file, start_frame, unit_idx), injected; or perm (n,) int32 device
+        with `cursor` and `seed`: drawn in the kernel.  len_rows (B,) int32 device: the rows' own frame counts (injected only),
+        else `crop_frames` for every row; frames past a row's count are exact zeros.  `out`: a dict of preallocated contiguous
+        outputs to write into.  -> {audio (B,Fr_out*hop), units (B,Fr_out,C), f0 (B,Fr_out,1), volume (B,Fr_out) fp32, spk_id
+        (B,1) int64, draws (B,3) int32: the triples used}.  A triple outside its file raises ValueError from the NEXT call
+        (or `poll_error()` after a synchronise): the kernel cannot fail the call that launched it."""
+        B, Fr_out = int(B), int(Fr_out)
+        for name, t, shape in (("triples", triples, (B, 3)), ("perm", perm, None), ("len_rows", len_rows, (B,))):
+            if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous()
+                                  or (shape is not None and tuple(t.shape) != shape) or (shape is None and t.dim() != 1)):
+                raise ValueError(f"dataset_gather: {name} must be a contiguous int32 device tensor"
+                                 + (f" of shape {shape}" if shape else " of one dimension"))
+        shapes = {"audio": ((B, Fr_out * view.hop), torch.float32), "units": ((B, Fr_out, view.n_unit), torch.float32),
+                  "f0": ((B, Fr_out, 1), torch.float32), "volume": ((B, Fr_out), torch.float32),
+                  "spk_id": ((B, 1), torch.int64), "draws": ((B, 3), torch.int32)}
+        if out is None:
+            out = {k: torch.empty(shape, device=self.device, dtype=dt) for k, (shape, dt) in shapes.items()}
+        else:
+            for k, (shape, dt) in shapes.items():
+                if tuple(out[k].shape) != shape or out[k].dtype != dt:
+                    raise ValueError(f"dataset_gather: out[{k!r}] must be {dt} of shape {shape}")
+        self.call("ddsp_dataset_gather", ctypes.byref(view), _ptr(triples), _ptr(perm), 0 if perm is None else perm.shape[0],
+                  int(cursor), int(seed) & ((1 << 64) - 1), _ptr(len_rows), int(crop_frames), float(waveform_sec), B, Fr_out,
+                  *[_ptr(out[k]) for k in ("audio", "units", "f0", "volume", "spk_id", "draws")])
+        return {k: out[k] for k in shapes}
 
     def unit2ctrl_bwd(self, weights, grads, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, n_out,
                       d_ctrl, want_ctrl=False, n_frames=None):

@@ -261,6 +261,48 @@ int ddsp_unit2ctrl_bwd_kept_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_w
  * (i ascending: a fixed order), then d[b][i >= n_b][:] = 0.  ddsp_ragged_crop is its own adjoint. */
 int ddsp_ragged_frames_adjoint(ddsp_ctx* ctx, void* stream, float* d, const int32_t* n_frames, int64_t B, int64_t Fr, int64_t C);
 
+/* ---- device-resident training dataset: a batch in one launch (reference: B calls of AudioDataset.__getitem__ / get_data,
+ * data_loaders.py:88-146, and the DataLoader's torch.stack collations) -------------------------------------------------------
+ * The dataset is packed once into arenas, all on the device: the files' audio back to back (fp32, or fp16 with fp16 = 1), each
+ * file's first sample at an offset that is a multiple of 8 elements; (n_aunit + 1) units arenas of (total_frames, n_unit)
+ * values of the same type, one behind the other (total_frames * n_unit is padded to a multiple of 8, so every arena starts on
+ * 16 bytes); f0 and volume as (total_frames) fp32.  Per file i: audio_off[i] and audio_len[i] (samples), frame_off[i] (its
+ * first row in the frame arenas) and frames[i], spk_id[i], duration[i] in seconds as the host computed it, and next_valid[i]:
+ * the first file at or cyclically after i with duration >= waveform_sec + 0.1, the reference's skip (-1: there is none). */
+typedef struct ddsp_dataset_view {
+    const void* audio;
+    const void* units;
+    const float* f0;
+    const float* volume;
+    const int64_t* audio_off;
+    const int64_t* audio_len;
+    const int64_t* frame_off;
+    const int32_t* frames;
+    const int64_t* spk_id;
+    const double* duration;
+    const int32_t* next_valid;
+    int64_t n_files, total_frames;
+    int32_t n_aunit, n_unit, hop, sample_rate, fp16;
+} ddsp_dataset_view;
+/* One launch builds B rows.  Row b is the triple (file, start_frame, unit_idx):
+ *   injected: triples (B, 3) int32 on the device (perm = NULL), used as they are;
+ *   drawn:    triples = NULL and perm (n_perm) int32 on the device, cursor + B <= n_perm:
+ *               file = next_valid[perm[cursor + b]], unit_idx uniform in 0..n_aunit,
+ *               start_frame = (int)((u * (duration[file] - waveform_sec - 0.1)) / (hop / sample_rate)) in fp64, u in [0, 1);
+ *             u and unit_idx are counter hashes of (seed, cursor + b), so a row's draw does not depend on the batch it is in.
+ * The row copies len_b frames from start_frame on - len_b = crop_frames, or len_rows[b] (device, (B,) int32, injected triples
+ * only: whole utterances of different length) - and writes exact zeros up to Fr_out: audio (B, Fr_out * hop), units
+ * (B, Fr_out, n_unit), f0 (B, Fr_out[, 1]), volume (B, Fr_out) in fp32 whatever the arenas hold, spk_id (B[, 1]) int64, and
+ * draws (B, 3) int32, the triples it used.  A triple that points outside its file (or a len_b outside [0, Fr_out]) is not
+ * used as an index: the row comes out as zeros with spk_id 0 and the context's device error word is set (DDSP_ERR_ARG from
+ * the next ddsp_dataset_gather / ddsp_unit2ctrl_* call or from ddsp_ctx_poll_error).  16-byte accesses where the widths allow
+ * (fp32: hop % 4 == 0, n_unit % 4 == 0; fp16: hop % 8 == 0, n_unit % 8 == 0, 8-byte loads for n_unit % 4 == 0), scalar
+ * otherwise; any hop >= 1 and n_unit >= 1 work.  Nothing synchronises and nothing is read back. */
+int ddsp_dataset_gather(ddsp_ctx* ctx, void* stream, const ddsp_dataset_view* ds_host, const int32_t* triples,
+                        const int32_t* perm, int64_t n_perm, int64_t cursor, uint64_t seed, const int32_t* len_rows,
+                        int64_t crop_frames, double waveform_sec, int64_t B, int64_t Fr_out, float* audio, float* units,
+                        float* f0, float* volume, int64_t* spk_id, int32_t* draws);
+
 /* ---- backward of a5-a8 (training: reference autograd through frequency_filter, solver.py:113) ------------ */
 /* Adjoints of ddsp_ltv_fir for an upstream gradient d_out (B,T): d_audio (B,T) or NULL = gradient w.r.t. the
  * input signal; d_ir (B,Fr,n) or NULL = gradient w.r.t. the filter frames (needs the forward input: audio with
