@@ -111,14 +111,22 @@ class F0_Extractor:
         from torch's generator); `seed_dev` (a (1,) int64 device tensor) holds the seed on the device instead and is advanced
         by every call (`ddsp_crepe_decode_dseed`), so a call captured into a HIP graph dithers anew on every replay;
       * `extract(audio (B,T), ..., n_samples=)`: a RAGGED batch of rows of different length (see `extract`);
-      * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError."""
+      * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError;
+      * `f0_extractor='ac'`: the autocorrelation method of Boersma (1993) on the device (`ddsp_f0_ac`) - the algorithm behind
+        the reference's 'parselmouth' branch (Praat's `to_pitch_ac`) with that branch's parameters (voicing threshold 0.6,
+        the window of 3 / f0_min seconds, its padding to n_frames), restated from the paper's formulae.  It carries its own
+        name because Praat is not a dependency and agreement with Praat itself is not pinned.  No weights, no resampling, no
+        randomness: `dither`, `seed` and `seed_dev` are accepted and ignored.  Same `extract` contract as 'crepe' (numpy in,
+        numpy out; device tensors without a host synchronisation; `n_samples=` ragged rows, each of at least one window)
+        with the reference's treatment of unvoiced frames: 0 without `uv_interp`, interpolated and clamped to f0_min with it
+        (an all-unvoiced signal becomes all f0_min)."""
 
     def __init__(self, f0_extractor, sample_rate=44100, hop_size=512, f0_min=65, f0_max=800, *, crepe_ckpt=None, device=None):
         if f0_extractor in ('parselmouth', 'dio', 'harvest'):
             raise NotImplementedError(
                 f"f0 extractor '{f0_extractor}' has no device implementation (it is a CPU library): 'crepe' is the device "
                 "extractor; keep the reference's F0_Extractor for the others")
-        if f0_extractor != 'crepe':
+        if f0_extractor not in ('crepe', 'ac'):
             raise ValueError(f" [x] Unknown f0 extractor: {f0_extractor}")
         self.f0_extractor, self.sample_rate, self.hop_size, self.f0_min, self.f0_max = \
             f0_extractor, sample_rate, hop_size, f0_min, f0_max
@@ -128,6 +136,12 @@ class F0_Extractor:
             device = "cuda"
         if torch.device(device).type != "cuda":
             raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback); got device=%r" % (device,))
+        self.device = device
+        if f0_extractor == 'ac':
+            if not float(f0_max) > float(f0_min) > 0:
+                raise ValueError("F0_Extractor('ac'): needs 0 < f0_min < f0_max")
+            self.model = None
+            return
         from .crepe import Crepe
         if isinstance(crepe_ckpt, Crepe):
             model = crepe_ckpt
@@ -137,7 +151,54 @@ class F0_Extractor:
             model = Crepe("tiny" if sd["conv1.weight"].shape[0] == 128 else "full")
             model.load_state_dict(sd)
         self.model = model.to(device).eval()
-        self.device = device
+
+    def min_samples(self):
+        """The shortest row `extract` accepts, in samples at `sample_rate`."""
+        if self.f0_extractor == 'ac':
+            n = max(1, int(3.0 / self.f0_min * self.sample_rate) - 2)
+            while hipddsp.f0_ac_frames(n, self.sample_rate, self.hop_size, self.f0_min) < 1:
+                n += 1
+            return n
+        from .crepe import HOP, SAMPLE_RATE
+        lib, n = hipddsp.load_library(), 1
+        while hipddsp.crepe_frames(n if int(self.sample_rate) == SAMPLE_RATE else
+                                   int(lib.ddsp_resample_length(n, int(self.sample_rate), SAMPLE_RATE)), HOP) < 3:
+            n += 1
+        return n
+
+    def _extract_ac(self, audio, uv_interp, silence_front, n_samples):
+        import numpy as np
+        sr, hop = self.sample_rate, self.hop_size
+        if n_samples is not None:
+            if silence_front != 0:
+                raise ValueError("F0_Extractor.extract: silence_front is not available with n_samples (a ragged batch)")
+            if not isinstance(audio, torch.Tensor) or audio.dim() != 2:
+                raise ValueError("F0_Extractor.extract: a ragged batch is a (B, T) tensor")
+            B, T = audio.shape
+            vals = hipddsp.check_f0_ac_n_samples(n_samples, B, T, sr, hop, self.f0_min)     # (before any launch)
+            if not audio.is_cuda:
+                raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
+            ctx = hipddsp.context_for(audio.device)
+            n_out = int(max(vals) // hop) + 1
+            return ctx.f0_ac(audio, sr, hop, self.f0_min, self.f0_max, n_out, 0, uv_interp, n_dev=ctx.ragged_counts(vals))
+        is_np = isinstance(audio, np.ndarray)
+        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
+        if not x.is_cuda:
+            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
+        if x.dim() not in (1, 2):
+            raise ValueError("F0_Extractor.extract: audio must be (T,) or (B, T)")
+        flat = x.dim() == 1
+        x = x.reshape(1, -1) if flat else x
+        n_frames = int(x.shape[-1] // hop) + 1
+        start_frame = int(silence_front * sr / hop)
+        real_silence_front = start_frame * hop / sr
+        x = x[:, int(np.round(real_silence_front * sr)):]
+        if hipddsp.f0_ac_frames(x.shape[-1], sr, hop, self.f0_min) < 1:
+            raise ValueError(f"F0_Extractor('ac'): {x.shape[-1]} samples at {sr} Hz are shorter than one analysis window of "
+                             f"3 / f0_min = {3.0 / self.f0_min:.4f} s")
+        out = hipddsp.context_for(x.device).f0_ac(x, sr, hop, self.f0_min, self.f0_max, n_frames, start_frame, uv_interp)
+        out = out[0] if flat else out
+        return out.cpu().numpy() if is_np else out
 
     def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None, seed_dev=None,
                 n_samples=None):
@@ -151,6 +212,8 @@ class F0_Extractor:
         not available with it (ValueError)."""
         import numpy as np
         from .crepe import HOP, SAMPLE_RATE
+        if self.f0_extractor == 'ac':
+            return self._extract_ac(audio, uv_interp, silence_front, n_samples)
         if n_samples is not None:
             return self._extract_ragged(audio, uv_interp, silence_front, dither, seed, seed_dev, n_samples)
         is_np = isinstance(audio, np.ndarray)

@@ -235,6 +235,9 @@ SIGNATURES = {
     "ddsp_crepe_decode_dseed": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _vp, _int, _vp, _vp, _vp]),
     "ddsp_stream_push": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
     "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _f64, _i64, _i64, _f32, _int, _f32, _vp]),
+    "ddsp_f0_ac_frames": (_i64, [_i64, _int, _f64, _f64]),
+    "ddsp_f0_ac": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _f64, _f64, _f64, _i64, _i64, _int, _vp, _vp]),
+    "ddsp_f0_ac_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _f64, _f64, _i64, _int, _vp, _vp]),
     "ddsp_profile_begin": (_int, [_vp, _u64]),
     "ddsp_profile_mask": (_int, [_vp, _u64]),
     "ddsp_profile_end": (_int, [_vp, _c.POINTER(ProfEntry), _int, _c.POINTER(_int)]),
@@ -369,6 +372,17 @@ def check_crepe_n_samples(n_samples, B, T, hop=80):
         if crepe_frames(v, hop) < 3:
             raise ValueError(f"n_samples[{b}] = {v} samples at 16 kHz give {crepe_frames(v, hop)} CREPE frames; the "
                              "reflect-padded filters need at least 3")
+    return vals
+
+
+def check_f0_ac_n_samples(n_samples, B, T, sr, hop, f0_min):
+    """`check_n_samples` for the autocorrelation f0 extractor: every row must hold one analysis window of 3 / f0_min seconds
+    (`f0_ac_frames(n, ...) >= 1`)."""
+    vals = check_n_samples(n_samples, B, T)
+    for b, v in enumerate(vals):
+        if f0_ac_frames(v, sr, hop, f0_min) < 1:
+            raise ValueError(f"n_samples[{b}] = {v} samples at {sr} Hz are shorter than one analysis window of 3 / f0_min = "
+                             f"{3.0 / f0_min:.4f} s")
     return vals
 
 
@@ -1248,6 +1262,29 @@ class Context:
                       int(start_frame), *tail)
         return out
 
+    def f0_ac(self, audio, sr, hop, f0_min, f0_max, n_frames, start_frame=0, uv_interp=False, n_dev=None, want_choice=False):
+        """audio (B,T) at `sr` -> f0 (B, n_frames): the autocorrelation extractor (Boersma 1993 with the parameters of the
+        reference's 'parselmouth' call), padded to `n_frames` frames of `hop` samples with `start_frame` extra zeros in front,
+        and with uv_interp the numpy.interp fill of the unvoiced frames and the clamp to f0_min.  The caller has checked that
+        T (every row of a ragged batch) holds one window (`f0_ac_frames(...) >= 1`).
+        `n_dev` ((B,) int32 device tensor, `ragged_counts`): a RAGGED batch - row b is audio[b, :n[b]] analysed alone, with
+        n[b] // hop + 1 frames and 0 after them; start_frame must be 0.  `want_choice`: also the chosen candidate of every
+        analysis frame, (B, f0_ac_frames(T, ...)) int32, 0 = unvoiced."""
+        audio = audio.contiguous().float()
+        B, T = audio.shape
+        if n_dev is not None and int(start_frame) != 0:
+            raise ValueError("f0_ac: start_frame must be 0 with n_dev (a ragged batch)")
+        out = torch.empty(B, int(n_frames), device=audio.device, dtype=torch.float32)
+        choice = torch.empty(B, f0_ac_frames(T, sr, hop, f0_min), device=audio.device, dtype=torch.int32) if want_choice else None
+        head = (_ptr(audio), int(B), int(T))
+        geo = (int(sr), float(hop), float(f0_min), float(f0_max), int(n_frames))
+        tail = (1 if uv_interp else 0, _ptr(out), _ptr(choice) if want_choice else None)
+        if B and n_dev is not None:
+            self.call("ddsp_f0_ac_ragged", *head, _ptr(self._counts_dev(n_dev, B)), *geo, *tail)
+        elif B:
+            self.call("ddsp_f0_ac", *head, *geo, int(start_frame), *tail)
+        return (out, choice) if want_choice else out
+
     # -- a10 -----------------------------------------------------------------------------------
     def sins_bank(self, ctrl2d, col0, n_harmonics, f0_frames, phase, B, Fr, hop, sr):
         out = torch.empty(B, Fr * hop, device=ctrl2d.device, dtype=torch.float32)
@@ -1433,6 +1470,15 @@ def crepe_frames(T16, hop=80):
     n = int(load_library().ddsp_crepe_frames(int(T16), int(hop)))
     if n < 0:
         raise ValueError(f"crepe_frames: bad length {T16} or hop {hop}")
+    return n
+
+
+def f0_ac_frames(T, sr, hop, f0_min):
+    """Analysis frames of T samples for the autocorrelation f0 extractor (`ddsp_f0_ac_frames`, a host computation): 0 when the
+    audio is shorter than one window of 3 / f0_min seconds."""
+    n = int(load_library().ddsp_f0_ac_frames(int(T), int(sr), float(hop), float(f0_min)))
+    if n < 0:
+        raise ValueError(f"f0_ac_frames: bad length {T}, rate {sr}, hop {hop} or f0_min {f0_min}")
     return n
 
 

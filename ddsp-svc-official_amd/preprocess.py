@@ -49,8 +49,9 @@ class _quiet_empty_mean:
         return self._w.__exit__(*exc)
 
 
-def _check_lengths(lengths, sample_rate, hop_size, units_encoder):
-    """Every file must be long enough for each analyser; ValueError names the first one that is not."""
+def _check_lengths(lengths, sample_rate, hop_size, units_encoder, f0_extractor=None):
+    """Every file must be long enough for each analyser; ValueError names the first one that is not.  The f0 extractor's
+    minimum is its own: 3 CREPE frames, or one analysis window for `F0_Extractor('ac')`."""
     import hipddsp
     lib = hipddsp.load_library()
     enc_sr = int(getattr(units_encoder, "encoder_sample_rate", 16000))
@@ -61,7 +62,11 @@ def _check_lengths(lengths, sample_rate, hop_size, units_encoder):
         if n <= int((hop_size + 1) // 2):
             raise ValueError(f"waves[{i}]: {n} samples are not longer than the volume's reflect padding "
                              f"{int((hop_size + 1) // 2)}")
-        if hipddsp.crepe_frames(at(n, 16000)) < 3:
+        if getattr(f0_extractor, "f0_extractor", "crepe") == "ac":
+            if hipddsp.f0_ac_frames(n, f0_extractor.sample_rate, f0_extractor.hop_size, f0_extractor.f0_min) < 1:
+                raise ValueError(f"waves[{i}]: {n} samples are shorter than one analysis window of the 'ac' f0 extractor "
+                                 f"({f0_extractor.min_samples()} samples)")
+        elif hipddsp.crepe_frames(at(n, 16000)) < 3:
             raise ValueError(f"waves[{i}]: {n} samples give fewer than 3 CREPE frames")
         if hipddsp.hubert_frames(at(n, enc_sr)) < 1:
             raise ValueError(f"waves[{i}]: {n} samples are too short for the units encoder's conv stack")
@@ -90,7 +95,7 @@ def analyse_batch(waves, f0_extractor, volume_extractor, units_encoder, sample_r
     xs = [torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32) if isinstance(w, np.ndarray) else w).reshape(-1)
           for w in waves]
     lengths = [int(x.shape[0]) for x in xs]
-    _check_lengths(lengths, sample_rate, hop_size, units_encoder)
+    _check_lengths(lengths, sample_rate, hop_size, units_encoder, f0_extractor)
     n_out = [int(n // hop_size) + 1 for n in lengths]
     records = [None] * len(xs)
     if batch_samples is None:

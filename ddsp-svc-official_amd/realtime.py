@@ -74,12 +74,12 @@ def phase_vocoder(a, b, fade_out, fade_in):
 
 def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop):
     """The analysis front end of `push_audio` as `name` (a class) is given it: both or neither; `f0_extractor` may be the
-    shorthand "crepe", which `_crepe` builds once every refusal is made."""
+    shorthand "crepe" or "ac", which `_crepe` builds once every refusal is made."""
     if (units_encoder is None) != (f0_extractor is None):
         raise ValueError(f"{name}: push_audio needs both units_encoder and f0_extractor (or neither)")
     if f0_extractor is None:
         return
-    crepe = f0_extractor == "crepe"
+    crepe = isinstance(f0_extractor, str) and f0_extractor in ("crepe", "ac")
     if not ((crepe or hasattr(f0_extractor, "extract")) and hasattr(units_encoder, "encode")):
         raise ValueError(f"{name}: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
     if not crepe and (f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != hop):
@@ -88,9 +88,13 @@ def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop)
 
 
 def _crepe(f0_extractor, samplerate, hop, f0_min, f0_max, crepe_ckpt, device):
-    """gui.py:81-82,93-99: a crepe extractor with these bounds at the device rate and the window's hop, for the shorthand."""
-    if f0_extractor != "crepe":
+    """gui.py:81-82,93-99: an extractor with these bounds at the device rate and the window's hop, for the shorthands "crepe"
+    and "ac" (the autocorrelation extractor: no checkpoint)."""
+    if not isinstance(f0_extractor, str):
         return f0_extractor
+    if f0_extractor == "ac":
+        from ddsp.vocoder import F0_Extractor
+        return F0_Extractor("ac", samplerate, hop, float(f0_min), float(f0_max), device=device)
     from ddsp.vocoder import F0_Extractor
     return F0_Extractor("crepe", samplerate, hop, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt, device=device)
 

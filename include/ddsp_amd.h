@@ -788,6 +788,29 @@ int ddsp_f0_postfilter_ragged(ddsp_ctx* ctx, void* stream, const float* f0, cons
                               const int32_t* n_crepe, int sr, double hop, int64_t n_frames, const int32_t* n_out,
                               float threshold, int uv_interp, float f0_min, float* out);
 
+/* ---- the autocorrelation f0 extractor (Boersma 1993; the algorithm behind the reference's 'parselmouth' branch,
+ * ddsp/vocoder.py:55-69,107-113, restated from the paper's formulae: Praat itself is not a dependency and agreement with it
+ * is not pinned) -----------------------------------------------------------------------------------------------------------
+ * Hanning window of 3 / f0_min seconds, autocorrelation by an FFT of nfft >= 1.5 window lengths divided by the window's own,
+ * candidates r > 0.3 refined by Hann-windowed sinc interpolation (depth 30, then Brent on depth 70; fp64), at most
+ * max(15, floor(f0_max / f0_min)) <= 32 per frame with the unvoiced one, and a Viterbi path with voicing threshold 0.6, silence
+ * threshold 0.03, octave cost 0.01, octave-jump cost 0.35 and voiced/unvoiced cost 0.14.  The signal path up to the normalised
+ * autocorrelation is fp32.  Deterministic: there is no dither.
+ * ddsp_f0_ac_frames: analysis frames of T samples, floor((T / sr - 3 / f0_min) / (hop / sr)) + 1 in fp64, 0 when the audio is
+ *   shorter than one window (-1: bad arguments).  A host computation.
+ * ddsp_f0_ac: audio (B, T) at `sr` -> out (B, n_frames): `start_frame + (floor(T / hop) - nF + 1) / 2` zeros, the nF =
+ *   ddsp_f0_ac_frames(T, ...) frames (0 where unvoiced), zeros after; with uv_interp != 0 numpy.interp over the zero frames
+ *   (fp64, when any frame is non-zero) and out = max(out, f0_min).  `choice` (B, nF) int32, may be null: the chosen candidate
+ *   of every analysis frame (0 = unvoiced).  T must hold one window; the FFT is at most 8192 points (DDSP_ERR_ARG otherwise).
+ * ddsp_f0_ac_ragged: n_samples[b] <= T samples per row (a DEVICE array, as in the section above): row b is the row analysed
+ *   alone at its own length, bit for bit, with floor(n_samples[b] / hop) + 1 frames and exactly 0 after them; `choice` is
+ *   (B, ddsp_f0_ac_frames(T, ...)).  The caller has checked that every row holds one window. */
+int64_t ddsp_f0_ac_frames(int64_t T, int sr, double hop, double f0_min);
+int ddsp_f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int sr, double hop, double f0_min,
+               double f0_max, int64_t n_frames, int64_t start_frame, int uv_interp, float* out, int32_t* choice);
+int ddsp_f0_ac_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int sr,
+                      double hop, double f0_min, double f0_max, int64_t n_frames, int uv_interp, float* out, int32_t* choice);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream --------------------- */
 /* ddsp_profile_begin arms the families in `family_mask` (bit i = family i, see the name returned); while armed,
  * each kernel launch of such a family is bracketed by hipEventRecord on the caller's stream.  ddsp_profile_end
