@@ -176,6 +176,25 @@ __device__ __forceinline__ int ddsp_row_frames(const int* __restrict__ n_frames,
     return n < 1 ? 1 : (n > Fr ? Fr : n);
 }
 
+// The counter hash behind every in-kernel draw (FIR noise, ragged unit noise, CREPE dither, dataset crops): a stateless hash
+// of (seed, counter), so every block that needs draw idx regenerates it.  Two rounds of a 32-bit integer finaliser (multiply /
+// xor-shift, constants of the "lowbias32" family); the high words of counter and seed enter between the rounds.
+__device__ __forceinline__ uint32_t ddsp_hash32(uint64_t seed, uint64_t idx) {
+    uint32_t x = (uint32_t)idx ^ (uint32_t)seed;
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    x += (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32);
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

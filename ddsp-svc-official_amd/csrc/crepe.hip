@@ -231,23 +231,6 @@ __global__ void __launch_bounds__(256) emission_kernel(const float* __restrict__
     }
 }
 
-__device__ __forceinline__ uint32_t hash32(uint64_t seed, uint64_t idx) {
-    // the counter hash of the noise generator (ltv_fir.hip noise_u): two rounds of the lowbias32 finaliser
-    uint32_t x = (uint32_t)idx ^ (uint32_t)seed;
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    x += (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32);
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 constexpr int VT = 384;        // threads of the Viterbi workgroup (6 waves; states j < 360)
 constexpr int BT_ROWS = 64;    // back-pointer rows staged in LDS per backtracking block
 constexpr int PF = 8;          // emission frames per prefetch block of the Viterbi recursion
@@ -420,8 +403,8 @@ __global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ l
         float cents = (float)(20 * bin) + CENTS0;
         if (dither) {
             const uint64_t h = (uint64_t)(n_frames ? t0 + t : o);
-            const float u1 = (float)(hash32(seed, 2 * h) >> 8) * (1.0f / 16777216.0f);
-            const float u2 = (float)(hash32(seed, 2 * h + 1) >> 8) * (1.0f / 16777216.0f);
+            const float u1 = (float)(ddsp_hash32(seed, 2 * h) >> 8) * (1.0f / 16777216.0f);
+            const float u2 = (float)(ddsp_hash32(seed, 2 * h + 1) >> 8) * (1.0f / 16777216.0f);
             cents = cents + 20.0f * ((u1 + u2) - 1.0f);   // triangular on (-20, 20), mode 0 (scipy triang(c=0.5))
         }
         f0[o] = 10.0f * exp2f(cents / 1200.0f);

@@ -33,23 +33,6 @@ struct GatherArgs {
     int* err;
 };
 
-// two rounds of the 32-bit finaliser of `ragged_unit_noise` (ragged.hip) / `hash32` (crepe.hip) over (seed, counter)
-__device__ __forceinline__ uint32_t dataset_hash(uint64_t seed, uint64_t idx) {
-    uint32_t x = (uint32_t)idx ^ (uint32_t)seed;
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    x += (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32);
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // dst[e] = e < n_copy ? (float)src[e] : 0 for the items i of this thread; V elements per item.  n_copy and n_out are
 // multiples of V and src + e, dst + e are V-element aligned (the launcher chose V so)
 template <typename T, int V>
@@ -97,11 +80,11 @@ __global__ void __launch_bounds__(256) dataset_gather_kernel(GatherArgs a) {
         const uint64_t k = (uint64_t)(a.cursor + b);
         const int p = a.perm[a.cursor + b];
         file = (p >= 0 && p < ds.n_files) ? ds.next_valid[p] : -1;
-        uidx = (int)(((uint64_t)dataset_hash(a.seed, 2 * k + 1) * (uint64_t)(ds.n_aunit + 1)) >> 32);
+        uidx = (int)(((uint64_t)ddsp_hash32(a.seed, 2 * k + 1) * (uint64_t)(ds.n_aunit + 1)) >> 32);
         start = 0;
         if (file >= 0 && file < ds.n_files) {
             // random.uniform(0, duration - waveform_sec - 0.1) / frame_resolution, `data_loaders.py:128-129`, in fp64
-            const double u = (double)dataset_hash(a.seed, 2 * k) * (1.0 / 4294967296.0);
+            const double u = (double)ddsp_hash32(a.seed, 2 * k) * (1.0 / 4294967296.0);
             const double span = ds.duration[file] - a.waveform_sec - 0.1;
             start = (int)((u * span) / a.frame_sec);
         }

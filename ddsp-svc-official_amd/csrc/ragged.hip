@@ -73,22 +73,10 @@ __global__ void __launch_bounds__(256) ragged_crop_kernel(CropArgs a, const int*
 }
 
 // The unit-noise draw U[0, 1) of a ragged batch, as the synthesis kernels take an injected one (DDSP_EXC_UNIT_NOISE: they
-// form 2u - 1): inside a row the caller's draw, or a counter hash of (seed, b, t) (two rounds of a 32-bit finaliser, as the
-// FIR kernel's generator); 0.5 past the row's end, which 2u - 1 turns into exactly 0.
+// form 2u - 1): inside a row the caller's draw, or the counter hash of (seed, b, t) (`ddsp_hash32`, as the FIR kernel's
+// generator); 0.5 past the row's end, which 2u - 1 turns into exactly 0.
 __device__ __forceinline__ float ragged_unit_noise(uint64_t seed, uint64_t idx) {
-    uint32_t x = (uint32_t)idx ^ (uint32_t)seed;
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    x += (uint32_t)(idx >> 32) * 0x9E3779B9u + (uint32_t)(seed >> 32);
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return (float)(x >> 8) * (1.0f / 16777216.0f);
+    return (float)(ddsp_hash32(seed, idx) >> 8) * (1.0f / 16777216.0f);
 }
 __global__ void __launch_bounds__(256) ragged_noise_kernel(const float* __restrict__ noise, uint64_t seed,
                                                            const int* __restrict__ n_frames, int64_t B, int Fr, int hop,

@@ -38,352 +38,10 @@ import hipddsp
 from hipddsp import (COMB_SINC, COMB_SINC_GATED, COMB_NONE, EXC_AUDIO, EXC_GENERATE, EXC_UNIT_NOISE, FIR_ALLPASS,
                      FIR_DYNAMIC, FIR_STATIC, FIR_SPLIT_BF16)
 
-from .hubert import RaggedCounts
+# the analysers live in ddsp/analysis.py; their names stay importable from here
+from .analysis import (Audio2HubertSoft, F0_Extractor, Units_Encoder, Volume_Extractor,  # noqa: F401
+                       _find_torchcrepe_checkpoint, align_units)
 from .unit2control import Unit2Control
-
-
-class Volume_Extractor:
-    """Frame RMS of an audio signal on the device (reference `ddsp/vocoder.py:116-137`, same constructor and method).
-
-    `extract(audio)`: a numpy array (T,) as the reference's callers pass (`main.py`, `preprocess.py`) comes back as a
-    numpy array (Frame,) - it is copied to `device`, reduced there and copied back; a device tensor (T,) or (B,T)
-    comes back as a device tensor of the same rank.  There is no CPU computation path."""
-
-    def __init__(self, hop_size=512, device="cuda"):
-        self.hop_size = hop_size
-        self.device = device
-
-    def extract(self, audio, n_samples=None):
-        """`n_samples` (a sequence of B ints or a CPU integer tensor (B,), each > (hop_size + 1) // 2; device tensor (B,T) and
-        an integral hop only): a RAGGED batch - row b reflects at its own ends, carries n_samples[b] // hop_size + 1 frames
-        and is 0 after them, and what follows its samples may hold anything."""
-        import numpy as np
-        if n_samples is not None:
-            if not isinstance(audio, torch.Tensor) or audio.dim() != 2:
-                raise ValueError("Volume_Extractor.extract: a ragged batch is a (B, T) tensor")
-            if not float(self.hop_size).is_integer():
-                raise ValueError("Volume_Extractor.extract: a ragged batch needs an integral hop_size")
-            vals = hipddsp.check_volume_n_samples(n_samples, audio.shape[0], audio.shape[1], int(self.hop_size))
-            if not audio.is_cuda:
-                raise RuntimeError("Volume_Extractor runs on a HIP device only (no CPU fallback)")
-            return hipddsp.context_for(audio.device).volume_extract(audio, int(self.hop_size), vals)
-        is_np = isinstance(audio, np.ndarray)
-        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
-        if not x.is_cuda:
-            raise RuntimeError("Volume_Extractor runs on a HIP device only (no CPU fallback)")
-        flat = x.dim() == 1
-        # an integral hop (int or float) takes the integer entry point; block_size * sr / model_sr of an input at another
-        # rate than the model's (main.py:72,109) is fractional and keeps its fraction, as the reference's float slicing does
-        hop = int(self.hop_size) if float(self.hop_size).is_integer() else float(self.hop_size)
-        vol = hipddsp.context_for(x.device).volume_extract(x.reshape(1, -1) if flat else x, hop)
-        vol = vol[0] if flat else vol
-        return vol.cpu().numpy() if is_np else vol
-
-
-def _find_torchcrepe_checkpoint(model="full"):
-    """`assets/<model>.pth` of an installed torchcrepe, located with importlib.util.find_spec (the package is not imported)."""
-    import importlib.util
-    try:
-        spec = importlib.util.find_spec("torchcrepe")
-    except (ImportError, ValueError):
-        spec = None
-    for d in (list(spec.submodule_search_locations or []) if spec is not None else []):
-        p = os.path.join(d, "assets", f"{model}.pth")
-        if os.path.isfile(p):
-            return p
-    raise FileNotFoundError(
-        f"F0_Extractor('crepe'): no CREPE checkpoint given and no installed torchcrepe with assets/{model}.pth was found; pass "
-        "crepe_ckpt='/path/to/full.pth' (torchcrepe's state dict) or a ddsp.crepe.Crepe module")
-
-
-class F0_Extractor:
-    """Reference `ddsp/vocoder.py:18-113` for `f0_extractor='crepe'`: resampling to 16 kHz (`ddsp_resample`,
-    lowpass_filter_width=128), the CREPE network, the Viterbi decode and the reference's post-filter, all on the device.
-
-    `extract(audio, uv_interp=False, device=None, silence_front=0)`: a numpy array (T,) returns a numpy fp32 array
-    (n_frames,) like the reference's (one synchronisation); a device tensor (T,) or (B,T) returns a device tensor (n_frames,)
-    or (B, n_frames) without a host synchronisation, so the call can be captured into a HIP graph.
-    Differences a caller can observe, all additive:
-      * keyword arguments `crepe_ckpt` (a path to torchcrepe's `full.pth` / `tiny.pth` state dict, or a `ddsp.crepe.Crepe`;
-        None looks for an installed torchcrepe's `assets/full.pth`) and `device` (default: the current HIP device);
-      * `extract(..., dither=True, seed=None)`: torchcrepe dithers the decoded pitch by a random triangular offset of up to
-        +-20 cents (a bin is 20 cents); `dither=False` makes the output deterministic, `seed` fixes the draw (default: drawn
-        from torch's generator); `seed_dev` (a (1,) int64 device tensor) holds the seed on the device instead and is advanced
-        by every call (`ddsp_crepe_decode_dseed`), so a call captured into a HIP graph dithers anew on every replay;
-      * `extract(audio (B,T), ..., n_samples=)`: a RAGGED batch of rows of different length (see `extract`);
-      * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError;
-      * `f0_extractor='ac'`: the autocorrelation method of Boersma (1993) on the device (`ddsp_f0_ac`) - the algorithm behind
-        the reference's 'parselmouth' branch (Praat's `to_pitch_ac`) with that branch's parameters (voicing threshold 0.6,
-        the window of 3 / f0_min seconds, its padding to n_frames), restated from the paper's formulae.  It carries its own
-        name because Praat is not a dependency and agreement with Praat itself is not pinned.  No weights, no resampling, no
-        randomness: `dither`, `seed` and `seed_dev` are accepted and ignored.  Same `extract` contract as 'crepe' (numpy in,
-        numpy out; device tensors without a host synchronisation; `n_samples=` ragged rows, each of at least one window)
-        with the reference's treatment of unvoiced frames: 0 without `uv_interp`, interpolated and clamped to f0_min with it
-        (an all-unvoiced signal becomes all f0_min)."""
-
-    def __init__(self, f0_extractor, sample_rate=44100, hop_size=512, f0_min=65, f0_max=800, *, crepe_ckpt=None, device=None):
-        if f0_extractor in ('parselmouth', 'dio', 'harvest'):
-            raise NotImplementedError(
-                f"f0 extractor '{f0_extractor}' has no device implementation (it is a CPU library): 'crepe' is the device "
-                "extractor; keep the reference's F0_Extractor for the others")
-        if f0_extractor not in ('crepe', 'ac'):
-            raise ValueError(f" [x] Unknown f0 extractor: {f0_extractor}")
-        self.f0_extractor, self.sample_rate, self.hop_size, self.f0_min, self.f0_max = \
-            f0_extractor, sample_rate, hop_size, f0_min, f0_max
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
-            device = "cuda"
-        if torch.device(device).type != "cuda":
-            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback); got device=%r" % (device,))
-        self.device = device
-        if f0_extractor == 'ac':
-            if not float(f0_max) > float(f0_min) > 0:
-                raise ValueError("F0_Extractor('ac'): needs 0 < f0_min < f0_max")
-            self.model = None
-            return
-        from .crepe import Crepe
-        if isinstance(crepe_ckpt, Crepe):
-            model = crepe_ckpt
-        else:
-            path = crepe_ckpt if crepe_ckpt is not None else _find_torchcrepe_checkpoint("full")
-            sd = torch.load(path, map_location="cpu", weights_only=True)
-            model = Crepe("tiny" if sd["conv1.weight"].shape[0] == 128 else "full")
-            model.load_state_dict(sd)
-        self.model = model.to(device).eval()
-
-    def min_samples(self):
-        """The shortest row `extract` accepts, in samples at `sample_rate`."""
-        if self.f0_extractor == 'ac':
-            n = max(1, int(3.0 / self.f0_min * self.sample_rate) - 2)
-            while hipddsp.f0_ac_frames(n, self.sample_rate, self.hop_size, self.f0_min) < 1:
-                n += 1
-            return n
-        from .crepe import HOP, SAMPLE_RATE
-        lib, n = hipddsp.load_library(), 1
-        while hipddsp.crepe_frames(n if int(self.sample_rate) == SAMPLE_RATE else
-                                   int(lib.ddsp_resample_length(n, int(self.sample_rate), SAMPLE_RATE)), HOP) < 3:
-            n += 1
-        return n
-
-    def _extract_ac(self, audio, uv_interp, silence_front, n_samples):
-        import numpy as np
-        sr, hop = self.sample_rate, self.hop_size
-        if n_samples is not None:
-            if silence_front != 0:
-                raise ValueError("F0_Extractor.extract: silence_front is not available with n_samples (a ragged batch)")
-            if not isinstance(audio, torch.Tensor) or audio.dim() != 2:
-                raise ValueError("F0_Extractor.extract: a ragged batch is a (B, T) tensor")
-            B, T = audio.shape
-            vals = hipddsp.check_f0_ac_n_samples(n_samples, B, T, sr, hop, self.f0_min)     # (before any launch)
-            if not audio.is_cuda:
-                raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
-            ctx = hipddsp.context_for(audio.device)
-            n_out = int(max(vals) // hop) + 1
-            return ctx.f0_ac(audio, sr, hop, self.f0_min, self.f0_max, n_out, 0, uv_interp, n_dev=ctx.ragged_counts(vals))
-        is_np = isinstance(audio, np.ndarray)
-        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
-        if not x.is_cuda:
-            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
-        if x.dim() not in (1, 2):
-            raise ValueError("F0_Extractor.extract: audio must be (T,) or (B, T)")
-        flat = x.dim() == 1
-        x = x.reshape(1, -1) if flat else x
-        n_frames = int(x.shape[-1] // hop) + 1
-        start_frame = int(silence_front * sr / hop)
-        real_silence_front = start_frame * hop / sr
-        x = x[:, int(np.round(real_silence_front * sr)):]
-        if hipddsp.f0_ac_frames(x.shape[-1], sr, hop, self.f0_min) < 1:
-            raise ValueError(f"F0_Extractor('ac'): {x.shape[-1]} samples at {sr} Hz are shorter than one analysis window of "
-                             f"3 / f0_min = {3.0 / self.f0_min:.4f} s")
-        out = hipddsp.context_for(x.device).f0_ac(x, sr, hop, self.f0_min, self.f0_max, n_frames, start_frame, uv_interp)
-        out = out[0] if flat else out
-        return out.cpu().numpy() if is_np else out
-
-    def extract(self, audio, uv_interp=False, device=None, silence_front=0, *, dither=True, seed=None, seed_dev=None,
-                n_samples=None):
-        """audio (T,) numpy / (T,) or (B,T) device tensor at `sample_rate` -> f0 [Hz] (n_frames,) / (B, n_frames),
-        n_frames = int(T // hop_size) + 1.  `device` is accepted for the reference's signature (the model's device is used).
-        `n_samples` (a sequence of B ints or a CPU integer tensor (B,), counts at `sample_rate`; device tensor (B,T) only): a
-        RAGGED batch.  Row b is analysed as audio[b, :n_samples[b]] alone - resampling, framing, decode and post-filter
-        each stop at the row's own end, the network computes the rows' own frames only, and what follows a row's samples may
-        hold anything.  Returns (B, int(max(n_samples) // hop_size) + 1); row b carries int(n_samples[b] // hop_size) + 1
-        frames and zeros after them.  Every row must give at least 3 CREPE frames; `silence_front != 0` and `seed_dev` are
-        not available with it (ValueError)."""
-        import numpy as np
-        from .crepe import HOP, SAMPLE_RATE
-        if self.f0_extractor == 'ac':
-            return self._extract_ac(audio, uv_interp, silence_front, n_samples)
-        if n_samples is not None:
-            return self._extract_ragged(audio, uv_interp, silence_front, dither, seed, seed_dev, n_samples)
-        is_np = isinstance(audio, np.ndarray)
-        x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device) if is_np else audio
-        if not x.is_cuda:
-            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
-        flat = x.dim() == 1
-        if x.dim() not in (1, 2):
-            raise ValueError("F0_Extractor.extract: audio must be (T,) or (B, T)")
-        x = x.reshape(1, -1) if flat else x
-        sr, hop = self.sample_rate, self.hop_size
-        n_frames = int(x.shape[-1] // hop) + 1
-        start_frame = int(silence_front * sr / hop)
-        real_silence_front = start_frame * hop / sr
-        x = x[:, int(np.round(real_silence_front * sr)):].contiguous().float()
-        ctx = hipddsp.context_for(x.device)
-        x16 = x if int(sr) == SAMPLE_RATE else ctx.resample(x, int(sr), SAMPLE_RATE, lowpass_filter_width=128)
-        fr = hipddsp.crepe_frames(x16.shape[-1], HOP)
-        if fr < 3:
-            raise ValueError(f"F0_Extractor('crepe'): {x16.shape[-1]} samples at 16 kHz give {fr} CREPE frames; the reference's "
-                             "reflect-padded filters need at least 3 (audio of at least 160 samples at 16 kHz)")
-        probs = self.model.activations(x16, HOP)
-        if seed_dev is not None:
-            f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither=dither, seed_dev=seed_dev)
-        else:
-            if dither and seed is None:
-                seed = _seed_from_torch()
-            f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither_seed=int(seed or 0), dither=dither)
-        out = ctx.f0_postfilter(f0, pd, sr, hop, n_frames, start_frame, 0.05, uv_interp, self.f0_min)
-        out = out[0] if flat else out
-        return out.cpu().numpy() if is_np else out
-
-    def _extract_ragged(self, audio, uv_interp, silence_front, dither, seed, seed_dev, n_samples):
-        from .crepe import HOP, SAMPLE_RATE
-        if silence_front != 0:
-            raise ValueError("F0_Extractor.extract: silence_front is not available with n_samples (a ragged batch)")
-        if seed_dev is not None:
-            raise ValueError("F0_Extractor.extract: seed_dev is not available with n_samples (a ragged batch)")
-        if not isinstance(audio, torch.Tensor) or audio.dim() != 2:
-            raise ValueError("F0_Extractor.extract: a ragged batch is a (B, T) tensor")
-        B, T = audio.shape
-        sr, hop = self.sample_rate, self.hop_size
-        vals = hipddsp.check_n_samples(n_samples, B, T)
-        resampled = int(sr) != SAMPLE_RATE
-        lib = hipddsp.load_library()
-        n16 = [int(lib.ddsp_resample_length(v, int(sr), SAMPLE_RATE)) for v in vals] if resampled else vals
-        T16 = int(lib.ddsp_resample_length(T, int(sr), SAMPLE_RATE)) if resampled else T
-        n16 = hipddsp.check_crepe_n_samples(n16, B, T16, HOP)     # (before any launch)
-        if not audio.is_cuda:
-            raise RuntimeError("F0_Extractor runs on a HIP device only (no CPU fallback)")
-        ctx = hipddsp.context_for(audio.device)
-        n_crepe = [hipddsp.crepe_frames(v, HOP) for v in n16]
-        n_out = [int(v // hop) + 1 for v in vals]
-        # one upload: the rows' samples, the activations' table (16 kHz samples, frame prefix), CREPE frames, output frames
-        table = hipddsp.crepe_ragged_table(n16, HOP)
-        dev = ctx.ragged_counts(vals + table + n_crepe + n_out)
-        n_dev, table_dev, nc_dev, no_dev = dev[:B], dev[B:3 * B + 1], dev[3 * B + 1:4 * B + 1], dev[4 * B + 1:]
-        x = audio.contiguous().float()
-        x16 = ctx.resample(x, int(sr), SAMPLE_RATE, lowpass_filter_width=128, n_dev=n_dev) if resampled else x
-        probs = self.model.activations(x16, HOP, n16, table_dev)
-        if dither and seed is None:
-            seed = _seed_from_torch()
-        f0, pd = ctx.crepe_decode(probs, self.f0_min, self.f0_max, segment=512, dither_seed=int(seed or 0), dither=dither,
-                                  n_frames=n_crepe, counts_dev=nc_dev)
-        return ctx.f0_postfilter(f0, pd, sr, hop, max(n_out), 0, 0.05, uv_interp, self.f0_min, n_crepe=n_crepe, n_out=n_out,
-                                 counts_dev=(nc_dev, no_dev))
-
-
-def align_units(units, n_samples, sample_rate, hop_size, encoder_sample_rate=16000, encoder_hop_size=320):
-    """Nearest-frame alignment of encoder units (B, Lu, C) to the synthesiser's frames - the tail of the reference's
-    `Units_Encoder.encode` (`ddsp/vocoder.py:201-211`), for callers that keep the reference's encoders and want the
-    gather on the device: n_frames = int(n_samples // hop_size) + 1 (a float hop keeps its fraction, like the
-    reference's), row i takes unit min(round(ratio * i), Lu - 1)."""
-    n_frames = int(int(n_samples) // hop_size) + 1
-    ratio = (hop_size / sample_rate) / (encoder_hop_size / encoder_sample_rate)
-    return hipddsp.context_for(units.device).align_units(units, n_frames, ratio)
-
-
-class Audio2HubertSoft(torch.nn.Module):
-    """Reference `ddsp/vocoder.py:214-229`: the HuBERT-Soft checkpoint (`module.` prefix stripped) behind `forward(audio (B,T))
-    -> units (B, Frame, 256)`, executed by libddsp_amd (`ddsp.hubert.HubertSoft`).  The module is built on `device` (default:
-    the current HIP device) because there is no CPU execution path."""
-
-    def __init__(self, path, h_sample_rate=16000, h_hop_size=320, device=None):
-        super().__init__()
-        from torch.nn.modules.utils import consume_prefix_in_state_dict_if_present
-        from .hubert import HubertSoft
-        print(' [Encoder Model] HuBERT Soft')
-        self.hubert = HubertSoft()
-        print(' [Loading] ' + path)
-        checkpoint = torch.load(path, map_location="cpu")
-        consume_prefix_in_state_dict_if_present(checkpoint, "module.")
-        self.hubert.load_state_dict(checkpoint)
-        self.hubert.eval()
-        if device is not None:
-            self.hubert.to(device)
-
-    def forward(self, audio, n_samples=None):
-        """ :: (B, T) -> (B, 1, T) -> (B, Frame, Feat=256); `n_samples`: ragged batch (`HubertSoft.units`) """
-        return self.hubert.units(audio.unsqueeze(1), n_samples)
-
-
-class Units_Encoder:
-    """Reference `ddsp/vocoder.py:140-211` for `encoder='hubertsoft'`: resampling to the encoder's rate (`ddsp_resample`,
-    lowpass_filter_width=128, as the reference's torchaudio Resample), the encoder and the nearest-frame alignment
-    (`align_units`), all on the device.
-
-    Differences a caller can observe, all additive: audio (B,T) with B > 1 returns every row aligned (the reference
-    returns row 0 only); the other encoder names raise NotImplementedError - `hubertsoft` is the device encoder, and callers
-    that keep the reference's encoders can align their units on the device with `align_units`."""
-
-    def __init__(self, encoder, encoder_ckpt, encoder_sample_rate=16000, encoder_hop_size=320, device=None):
-        if encoder in ('hubertbase', 'hubertbase768', 'contentvec', 'contentvec768', 'xunit', 'yunit'):
-            raise NotImplementedError(
-                f"units encoder '{encoder}' has no device implementation: 'hubertsoft' is the device encoder; callers that "
-                "keep the reference's encoders can align their units on the device with ddsp.vocoder.align_units")
-        if encoder != 'hubertsoft':
-            raise ValueError(f" [x] Unknown units encoder: {encoder}")
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
-            device = "cuda"
-        if torch.device(device).type != "cuda":
-            raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback); got device=%r" % (device,))
-        self.device = device
-        self.model = Audio2HubertSoft(encoder_ckpt, device=device)
-        self.model = self.model.eval()
-        self.encoder_sample_rate = encoder_sample_rate
-        self.encoder_hop_size = encoder_hop_size
-
-    def encode(self, audio, sample_rate, hop_size, n_samples=None):
-        """audio (B,T) at `sample_rate` -> units (B, int(T // hop_size) + 1, 256) aligned to frames of `hop_size` samples
-        (a float hop keeps its fraction, like the reference's).
-        `n_samples` (a sequence of B ints or a CPU integer tensor (B,), counts at `sample_rate`): a RAGGED batch.  Row b is
-        encoded as audio[b, :n_samples[b]] alone - resampling, encoder and alignment each stop at the row's own end, and
-        what follows a row's samples may hold anything.  Returns (B, int(max(n_samples) // hop_size) + 1, 256); row b
-        carries int(n_samples[b] // hop_size) + 1 frames and zeros after them."""
-        if n_samples is not None:
-            return self._encode_ragged(audio, sample_rate, hop_size, n_samples)
-        if not audio.is_cuda:
-            raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
-        ctx = hipddsp.context_for(audio.device)
-        audio_res = audio if sample_rate == self.encoder_sample_rate else \
-            ctx.resample(audio, int(sample_rate), int(self.encoder_sample_rate), lowpass_filter_width=128)
-        units = self.model(audio_res)
-        return align_units(units, audio.size(-1), sample_rate, hop_size, self.encoder_sample_rate, self.encoder_hop_size)
-
-    def _encode_ragged(self, audio, sample_rate, hop_size, n_samples):
-        if audio.dim() != 2:
-            raise ValueError("Units_Encoder.encode: a ragged batch is (B, T) audio")
-        B, T = audio.shape
-        vals = hipddsp.check_n_samples(n_samples, B, T)
-        resampled = sample_rate != self.encoder_sample_rate
-        lib = hipddsp.load_library()
-        n16 = [int(lib.ddsp_resample_length(v, int(sample_rate), int(self.encoder_sample_rate))) for v in vals] \
-            if resampled else vals
-        T16 = int(lib.ddsp_resample_length(T, int(sample_rate), int(self.encoder_sample_rate))) if resampled else T
-        n16 = hipddsp.check_hubert_n_samples(n16, B, T16)     # (before any launch)
-        if not audio.is_cuda:
-            raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
-        ctx = hipddsp.context_for(audio.device)
-        n_units = [hipddsp.hubert_frames(v) for v in n16]
-        n_out = [int(v // hop_size) + 1 for v in vals]
-        # one upload for the four count vectors
-        dev = ctx.ragged_counts(vals + n16 + n_units + n_out).reshape(4, B)
-        audio_res = ctx.resample(audio, int(sample_rate), int(self.encoder_sample_rate), lowpass_filter_width=128,
-                                 n_dev=dev[0]) if resampled else audio
-        units = self.model(audio_res, RaggedCounts(n16, T16, dev[1]))
-        ratio = (hop_size / sample_rate) / (self.encoder_hop_size / self.encoder_sample_rate)
-        return ctx.align_units(units, max(n_out), ratio, n_units_dev=dev[2], n_out_dev=dev[3])
 
 
 class DotDict(dict):
@@ -425,10 +83,6 @@ def load_model(model_path, device="cpu"):
     model.load_state_dict(ckpt["model"])
     model.eval()
     return model, args
-
-
-def _seed_from_torch():
-    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
 class _SynthBase(torch.nn.Module):
@@ -483,14 +137,14 @@ class _SynthBase(torch.nn.Module):
 
     def _ragged_noise(self, ctx, n_dev, B, Fr, noise, noise_seed):
         """(unit-noise draw (B,T) with 0.5 - no excitation - past every row's end, EXC_UNIT_NOISE, 0)."""
-        seed = 0 if noise is not None else (_seed_from_torch() if noise_seed is None else int(noise_seed))
+        seed = 0 if noise is not None else (hipddsp.seed_from_torch() if noise_seed is None else int(noise_seed))
         return ctx.ragged_noise(noise, seed, n_dev, B, Fr, self._hop), EXC_UNIT_NOISE, 0
 
     @staticmethod
     def _noise_args(noise, noise_seed):
         if noise is not None:
             return noise.contiguous().float(), EXC_UNIT_NOISE, 0
-        return None, EXC_GENERATE, (_seed_from_torch() if noise_seed is None else int(noise_seed))
+        return None, EXC_GENERATE, (hipddsp.seed_from_torch() if noise_seed is None else int(noise_seed))
 
     def _phase_out(self, ctx, ps, n_dev=None):
         """The phase a forward returns - sample-rate where the model asks the scan for it (Sins), else frame-rate -, 0 over

@@ -641,12 +641,11 @@ class Enhancer:
         """Host integers a row of n_samples goes through in `enhance` at a working rate: (samples at the working rate,
         f0 frames asked of the re-timing, generator frames, generator samples, output samples at the enhancer's rate) -
         the resampler's length formula, `n // hop + 1`, `STFT.frame_count`, `* hop`, the resampler's again."""
-        length = hipddsp.load_library().ddsp_resample_length
         sr_e, hop_e = int(self.enhancer_sample_rate), int(self.enhancer_hop_size)
-        n_res = int(n_samples) if int(sample_rate) == int(work_rate) else int(length(int(n_samples), int(sample_rate), int(work_rate)))
+        n_res = hipddsp.resample_length(int(n_samples), sample_rate, work_rate)
         frames = self.enhancer.stft().frame_count(n_res)
         n_gen = frames * hop_e
-        n_out = n_gen if int(work_rate) == sr_e else int(length(n_gen, int(work_rate), sr_e))
+        n_out = hipddsp.resample_length(n_gen, work_rate, sr_e)
         return n_res, n_res // hop_e + 1, frames, n_gen, n_out
 
     def _enhance_rows(self, audio, sample_rate, f0, hop_size, n_samples, n_f0, key, rand_ini):

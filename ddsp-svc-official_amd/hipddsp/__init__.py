@@ -335,14 +335,46 @@ def check_n_frames(n_frames, B, Fr):
     return vals
 
 
-def check_n_samples(n_samples, B, T):
+def check_n_samples(n_samples, B, T, rule=None):
     """The per-row sample counts of a ragged batch of audio (B, T) as a list of B Python ints, 1 <= n <= T; anything else
-    raises ValueError (a host check: nothing is launched).  Accepted: what `check_n_frames` accepts."""
+    raises ValueError (a host check: nothing is launched).  Accepted: what `check_n_frames` accepts.  `rule`: an analyser's
+    row-length rule (`hubert_rule`, `crepe_rule`, `f0_ac_rule`, `volume_rule`), count -> None or why such a row is too short."""
     vals = _check_counts("n_samples", n_samples, B)
     for b, v in enumerate(vals):
         if not 1 <= v <= int(T):
             raise ValueError(f"n_samples[{b}] = {v} is outside 1..T={int(T)}")
+    for b, v in enumerate(vals if rule is not None else ()):
+        reason = rule(v)
+        if reason is not None:
+            raise ValueError(f"n_samples[{b}] = {v} {reason}")
     return vals
+
+
+def hubert_rule(n):
+    """The units encoder's row-length rule: a row must be long enough for the conv stack (`hubert_frames(n) >= 1`)."""
+    return None if hubert_frames(n) >= 1 else "samples are too short for the conv stack"
+
+
+def crepe_rule(hop=80):
+    """The CREPE f0 extractor's row-length rule (counts at 16 kHz): at least 3 CREPE frames, for the reflect-padded filters."""
+    def rule(n):
+        k = crepe_frames(n, hop)
+        return None if k >= 3 else f"samples at 16 kHz give {k} CREPE frames; the reflect-padded filters need at least 3"
+    return rule
+
+
+def f0_ac_rule(sr, hop, f0_min):
+    """The autocorrelation f0 extractor's row-length rule: a row must hold one analysis window of 3 / f0_min seconds."""
+    def rule(n):
+        return None if f0_ac_frames(n, sr, hop, f0_min) >= 1 else \
+            f"samples at {sr} Hz are shorter than one analysis window of 3 / f0_min = {3.0 / f0_min:.4f} s"
+    return rule
+
+
+def volume_rule(hop):
+    """The volume's row-length rule: a row must be longer than its reflect padding, n > (hop + 1) // 2."""
+    pad = (int(hop) + 1) // 2
+    return lambda n: None if n > pad else f"samples are not longer than the reflect padding {pad}"
 
 
 def check_loss_scales(n_samples, n_ffts):
@@ -354,45 +386,11 @@ def check_loss_scales(n_samples, n_ffts):
                              "samples)")
 
 
-def check_hubert_n_samples(n_samples, B, T):
-    """`check_n_samples` for the units encoder: every row must also be long enough for the conv stack
-    (`hubert_frames(n) >= 1`)."""
-    vals = check_n_samples(n_samples, B, T)
-    for b, v in enumerate(vals):
-        if hubert_frames(v) < 1:
-            raise ValueError(f"n_samples[{b}] = {v} samples are too short for the conv stack")
-    return vals
-
-
-def check_crepe_n_samples(n_samples, B, T, hop=80):
-    """`check_n_samples` for the f0 extractor (counts at 16 kHz): every row must also give at least 3 CREPE frames, which the
-    reflect-padded filters behind the decode need (`crepe_frames(n, hop) >= 3`)."""
-    vals = check_n_samples(n_samples, B, T)
-    for b, v in enumerate(vals):
-        if crepe_frames(v, hop) < 3:
-            raise ValueError(f"n_samples[{b}] = {v} samples at 16 kHz give {crepe_frames(v, hop)} CREPE frames; the "
-                             "reflect-padded filters need at least 3")
-    return vals
-
-
-def check_f0_ac_n_samples(n_samples, B, T, sr, hop, f0_min):
-    """`check_n_samples` for the autocorrelation f0 extractor: every row must hold one analysis window of 3 / f0_min seconds
-    (`f0_ac_frames(n, ...) >= 1`)."""
-    vals = check_n_samples(n_samples, B, T)
-    for b, v in enumerate(vals):
-        if f0_ac_frames(v, sr, hop, f0_min) < 1:
-            raise ValueError(f"n_samples[{b}] = {v} samples at {sr} Hz are shorter than one analysis window of 3 / f0_min = "
-                             f"{3.0 / f0_min:.4f} s")
-    return vals
-
-
-def check_volume_n_samples(n_samples, B, T, hop):
-    """`check_n_samples` for the volume: every row must be longer than its reflect padding, n > (hop + 1) // 2."""
-    vals = check_n_samples(n_samples, B, T)
-    for b, v in enumerate(vals):
-        if v <= (int(hop) + 1) // 2:
-            raise ValueError(f"n_samples[{b}] = {v} samples are not longer than the reflect padding {(int(hop) + 1) // 2}")
-    return vals
+# `check_n_samples` with each analyser's rule applied
+check_hubert_n_samples = lambda n_samples, B, T: check_n_samples(n_samples, B, T, hubert_rule)                       # noqa: E731
+check_crepe_n_samples = lambda n_samples, B, T, hop=80: check_n_samples(n_samples, B, T, crepe_rule(hop))           # noqa: E731
+check_f0_ac_n_samples = lambda n_samples, B, T, sr, hop, f0_min: check_n_samples(n_samples, B, T, f0_ac_rule(sr, hop, f0_min))  # noqa: E731
+check_volume_n_samples = lambda n_samples, B, T, hop: check_n_samples(n_samples, B, T, volume_rule(hop))            # noqa: E731
 
 
 MAX_MIX = 16                      # speakers in one mix (MixArgs of csrc/u2c.h; the K of a row-mix table)
@@ -812,7 +810,7 @@ class Context:
         B, T = audio.shape
         if n_samples is not None and not float(hop).is_integer():
             raise ValueError("volume_extract: a ragged batch needs an integral hop")
-        vals = None if n_samples is None else check_volume_n_samples(n_samples, B, T, int(hop))
+        vals = None if n_samples is None else check_volume_n_samples(n_samples, B, T, hop)
         if not float(hop).is_integer():
             hop = float(hop)
             out = torch.empty(B, int(T // hop) + 1, device=audio.device, dtype=torch.float32)
@@ -1458,6 +1456,17 @@ _override = threading.local()
 def next_dither_seed(seed):
     """The value `ddsp_crepe_decode_dseed` leaves in its seed word after a call that read `seed` (a host computation)."""
     return (int(seed) * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
+
+
+def seed_from_torch():
+    """A seed for an in-kernel generator, drawn from torch's default generator (so `torch.manual_seed` repeats a run)."""
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+def resample_length(n, sr_in, sr_out):
+    """n samples at `sr_in` as samples at `sr_out`: n itself at equal rates, else the resampler's length
+    (`ddsp_resample_length`; negative for a pair of rates it cannot convert)."""
+    return n if int(sr_in) == int(sr_out) else int(load_library().ddsp_resample_length(int(n), int(sr_in), int(sr_out)))
 
 
 def hubert_frames(T):

@@ -50,26 +50,23 @@ class _quiet_empty_mean:
 
 
 def _check_lengths(lengths, sample_rate, hop_size, units_encoder, f0_extractor=None):
-    """Every file must be long enough for each analyser; ValueError names the first one that is not.  The f0 extractor's
-    minimum is its own: 3 CREPE frames, or one analysis window for `F0_Extractor('ac')`."""
-    import hipddsp
-    lib = hipddsp.load_library()
-    enc_sr = int(getattr(units_encoder, "encoder_sample_rate", 16000))
+    """Every file must be long enough for each analyser (its `min_samples`); ValueError names the first one that is not, in
+    the analyser's words (`too_short`; without them, by its minimum).  One that states no minimum (None, a stand-in, one of
+    the reference's encoders) is held to the HuBERT-Soft rule at its `encoder_sample_rate`, or to the CREPE rule."""
+    from ddsp import analysis
 
-    def at(n, rate):
-        return n if int(sample_rate) == rate else int(lib.ddsp_resample_length(n, int(sample_rate), rate))
+    def need(analyser, default, *args):
+        if not hasattr(analyser, "min_samples"):
+            return default.min_samples(), default.too_short
+        lo, name = analyser.min_samples(*args), getattr(analyser, "f0_extractor", type(analyser).__name__)
+        return lo, getattr(analyser, "too_short", f"are fewer than the {lo} samples that {name!r} needs")
+    enc_sr = getattr(units_encoder, "encoder_sample_rate", analysis.HUBERT_RATE)
+    needs = (need(analysis.Volume_Extractor(hop_size), None), need(f0_extractor, analysis.crepe_rule(sample_rate)),
+             need(units_encoder, analysis.units_rule(sample_rate, enc_sr), sample_rate))
     for i, n in enumerate(lengths):
-        if n <= int((hop_size + 1) // 2):
-            raise ValueError(f"waves[{i}]: {n} samples are not longer than the volume's reflect padding "
-                             f"{int((hop_size + 1) // 2)}")
-        if getattr(f0_extractor, "f0_extractor", "crepe") == "ac":
-            if hipddsp.f0_ac_frames(n, f0_extractor.sample_rate, f0_extractor.hop_size, f0_extractor.f0_min) < 1:
-                raise ValueError(f"waves[{i}]: {n} samples are shorter than one analysis window of the 'ac' f0 extractor "
-                                 f"({f0_extractor.min_samples()} samples)")
-        elif hipddsp.crepe_frames(at(n, 16000)) < 3:
-            raise ValueError(f"waves[{i}]: {n} samples give fewer than 3 CREPE frames")
-        if hipddsp.hubert_frames(at(n, enc_sr)) < 1:
-            raise ValueError(f"waves[{i}]: {n} samples are too short for the units encoder's conv stack")
+        for lo, too_short in needs:
+            if n < lo:
+                raise ValueError(f"waves[{i}]: {n} samples {too_short}")
 
 
 def _record(f0, volume, units, use_vuv):

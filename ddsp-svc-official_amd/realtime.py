@@ -74,29 +74,26 @@ def phase_vocoder(a, b, fade_out, fade_in):
 
 def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop):
     """The analysis front end of `push_audio` as `name` (a class) is given it: both or neither; `f0_extractor` may be the
-    shorthand "crepe" or "ac", which `_crepe` builds once every refusal is made."""
+    shorthand "crepe" or "ac", which `_f0_extractor` builds once every refusal is made."""
     if (units_encoder is None) != (f0_extractor is None):
         raise ValueError(f"{name}: push_audio needs both units_encoder and f0_extractor (or neither)")
     if f0_extractor is None:
         return
-    crepe = isinstance(f0_extractor, str) and f0_extractor in ("crepe", "ac")
-    if not ((crepe or hasattr(f0_extractor, "extract")) and hasattr(units_encoder, "encode")):
+    shorthand = isinstance(f0_extractor, str) and f0_extractor in ("crepe", "ac")
+    if not ((shorthand or hasattr(f0_extractor, "extract")) and hasattr(units_encoder, "encode")):
         raise ValueError(f"{name}: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
-    if not crepe and (f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != hop):
+    if not shorthand and (f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != hop):
         raise ValueError(f"{name}: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
                          f"{f0_extractor.hop_size}; {window} at {samplerate} Hz with hop {hop}")
 
 
-def _crepe(f0_extractor, samplerate, hop, f0_min, f0_max, crepe_ckpt, device):
+def _f0_extractor(f0_extractor, samplerate, hop, f0_min, f0_max, crepe_ckpt, device):
     """gui.py:81-82,93-99: an extractor with these bounds at the device rate and the window's hop, for the shorthands "crepe"
-    and "ac" (the autocorrelation extractor: no checkpoint)."""
+    and "ac" (the autocorrelation extractor: it has no checkpoint and ignores `crepe_ckpt`)."""
     if not isinstance(f0_extractor, str):
         return f0_extractor
-    if f0_extractor == "ac":
-        from ddsp.vocoder import F0_Extractor
-        return F0_Extractor("ac", samplerate, hop, float(f0_min), float(f0_max), device=device)
     from ddsp.vocoder import F0_Extractor
-    return F0_Extractor("crepe", samplerate, hop, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt, device=device)
+    return F0_Extractor(f0_extractor, samplerate, hop, float(f0_min), float(f0_max), crepe_ckpt=crepe_ckpt, device=device)
 
 
 def _check_resample(name, out_sr, samplerate):
@@ -211,7 +208,7 @@ class StreamRenderer:
         self.spk_mix_dict = self._checked_mix(spk_mix_dict)
         self.features = features
         _check_analysers("StreamRenderer", "this renderer's window is", units_encoder, f0_extractor, samplerate, self.hop_size)
-        f0_extractor = _crepe(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
+        f0_extractor = _f0_extractor(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
         self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
         self.last_f0 = self.last_units = self.last_volume = None
         self.use_graph = bool(use_graph)
@@ -410,13 +407,12 @@ class StreamBank:
                                                      self.silence_front, enhancer_max_key)
         _check_resample("StreamBank", self.out_sr, samplerate)
         if enhancer is not None:
-            length = hipddsp.load_library().ddsp_resample_length
-            ends = [n if self.out_sr == int(samplerate) else int(length(n, self.out_sr, int(samplerate))) for n in self.enhancer_plan.n_out]
+            ends = [hipddsp.resample_length(n, self.out_sr, samplerate) for n in self.enhancer_plan.n_out]
             self.n_tail = self.block + self.xfade + self.search + self.delay
             if min(ends) < self.n_tail:
                 raise ValueError(f"StreamBank: the enhancer returns {min(ends)} samples at {samplerate} Hz for some key, the splice "
                                  f"needs {self.n_tail}")
-        f0_extractor = _crepe(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
+        f0_extractor = _f0_extractor(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
         self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
         dev = self.device
         self.windows = torch.zeros(self.S, self.n_in, device=dev)
