@@ -63,7 +63,7 @@ struct ddsp_ctx {
     uint64_t table_clock;
     // 8 KiB of zeros: the source of out-of-range conv taps in the LDS-DMA GEMM (a DMA cannot be predicated to zero)
     float* zero_page;
-    // device-side contract violations (a speaker id outside the table, a dataset triple outside its file): one int in host-mapped memory that kernels set
+    // device-side contract violations (a speaker id outside the table, a dataset triple outside its file, a chunk table too small): one int in host-mapped memory that kernels set
     // with a system-scope store; the next entry point that takes ids, or ddsp_ctx_poll_error, reports and clears it
     int* dev_error_host;
     int* dev_error_dev;
@@ -157,6 +157,7 @@ int ddsp_dev_error_ptr(ddsp_ctx* ctx, int** out);
 int ddsp_take_dev_error(ddsp_ctx* ctx);
 #define DDSP_DEV_ERR_SPK_ID 1
 #define DDSP_DEV_ERR_DATASET 2   // ddsp_dataset_gather: a (file, start_frame, unit_idx) triple outside its file
+#define DDSP_DEV_ERR_SLICER 3    // ddsp_slicer: a row with more chunks than the table's capacity
 
 // profiler hooks (ctx.hip): bracket ONE kernel launch (or a tight group) on `st` when the family is enabled
 void ddsp_prof_begin(ddsp_ctx* ctx, hipStream_t st, int id);

@@ -243,6 +243,9 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
     if (code == DDSP_DEV_ERR_DATASET)
         return ddsp_fail(ctx, DDSP_ERR_ARG, "a (file, start_frame, unit_idx) triple outside its file in an earlier ddsp_dataset_gather call",
                          "those rows were written as zeros and nothing was read for them");
+    if (code == DDSP_DEV_ERR_SLICER)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a row with more chunks than the table's capacity in an earlier ddsp_slicer call",
+                         "the table holds the chunks that fit");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

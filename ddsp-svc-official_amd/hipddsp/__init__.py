@@ -23,6 +23,7 @@ FIR_FP32, FIR_SPLIT_BF16 = 0, 3   # ddsp_ltv_fir `math` (include/ddsp_amd.h)
 ABI_VERSION = 7                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights, CrepeWeights)
 MATH_FP32, MATH_SPLIT_BF16 = 0, 3  # ddsp_ctx_set_math
 ATTENTION_CAUSAL = 200            # ddsp_performer_attention: causal_linear_attention (pcmer.py:170-188)
+SLICER_PAD = {"constant": 0, "reflect": 1}   # ddsp_slicer `pad_mode`: librosa >= 0.10 / older librosa
 ATTENTION_PAIR = 100              # ddsp_performer_attention: the split-bf16 key / query kernel pair instead of the fused kernel
 
 _c = ctypes
@@ -238,6 +239,9 @@ SIGNATURES = {
     "ddsp_f0_ac_frames": (_i64, [_i64, _int, _f64, _f64]),
     "ddsp_f0_ac": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _f64, _f64, _f64, _i64, _i64, _int, _vp, _vp]),
     "ddsp_f0_ac_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _f64, _f64, _i64, _int, _vp, _vp]),
+    "ddsp_slicer_frames": (_i64, [_i64, _i64, _i64]),
+    "ddsp_slicer": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64]),
+    "ddsp_slicer_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64]),
     "ddsp_profile_begin": (_int, [_vp, _u64]),
     "ddsp_profile_mask": (_int, [_vp, _u64]),
     "ddsp_profile_end": (_int, [_vp, _c.POINTER(ProfEntry), _int, _c.POINTER(_int)]),
@@ -338,7 +342,7 @@ def check_n_frames(n_frames, B, Fr):
 def check_n_samples(n_samples, B, T, rule=None):
     """The per-row sample counts of a ragged batch of audio (B, T) as a list of B Python ints, 1 <= n <= T; anything else
     raises ValueError (a host check: nothing is launched).  Accepted: what `check_n_frames` accepts.  `rule`: an analyser's
-    row-length rule (`hubert_rule`, `crepe_rule`, `f0_ac_rule`, `volume_rule`), count -> None or why such a row is too short."""
+    row-length rule (`hubert_rule`, `crepe_rule`, `f0_ac_rule`, `volume_rule`, `slicer_rule`), count -> None or why such a row is too short."""
     vals = _check_counts("n_samples", n_samples, B)
     for b, v in enumerate(vals):
         if not 1 <= v <= int(T):
@@ -375,6 +379,11 @@ def volume_rule(hop):
     """The volume's row-length rule: a row must be longer than its reflect padding, n > (hop + 1) // 2."""
     pad = (int(hop) + 1) // 2
     return lambda n: None if n > pad else f"samples are not longer than the reflect padding {pad}"
+
+
+def slicer_rule(n):
+    """The silence slicer's row-length rule: a row needs at least 1 sample (every such row has a frame)."""
+    return None if n >= 1 else "samples: the slicer needs at least 1"
 
 
 def check_loss_scales(n_samples, n_ffts):
@@ -1283,6 +1292,38 @@ class Context:
             self.call("ddsp_f0_ac", *head, *geo, int(start_frame), *tail)
         return (out, choice) if want_choice else out
 
+    def slicer(self, x, win, hop, threshold, min_length, min_interval, max_sil_kept, pad_mode="constant", n_dev=None,
+               capacity=None, out=None):
+        """audio x (B,T) -> (table (B, capacity, 3) int32 rows start_sample, end_sample, is_silence; count (B,) int32; rms
+        (B, slicer_frames(T, win, hop)) fp32): the reference's `Slicer.slice` per row - frame RMS over windows of `win`
+        samples every `hop` (pad_mode "constant": librosa >= 0.10, "reflect": older), then its tagging state machine with the
+        linear `threshold` and `min_length`, `min_interval`, `max_sil_kept` in frames.  Rows of the table from count[b] on
+        are zeros.  `n_dev` ((B,) int32 device tensor, `ragged_counts`): a RAGGED batch - row b is x[b, :n[b]] cut alone.
+        `capacity`: the table's rows, `slicer_capacity(...)` (always enough) when None; a row with more chunks than a smaller
+        one keeps what fits and raises ValueError from `poll_error()` after a synchronise or from the next call.  `out`: a
+        (table, count, rms) triple of preallocated contiguous tensors to write into.  Nothing is read back."""
+        x = x.contiguous().float()
+        B, T = x.shape
+        F = slicer_frames(T, win, hop)
+        cap = slicer_capacity(F, min_interval) if capacity is None else int(capacity)
+        shapes = (((B, cap, 3), torch.int32), ((B,), torch.int32), ((B, F), torch.float32))
+        if out is None:
+            out = tuple(torch.empty(shape, device=x.device, dtype=dt) for shape, dt in shapes)
+        else:
+            for t, (shape, dt) in zip(out, shapes):
+                if tuple(t.shape) != shape or t.dtype != dt:
+                    raise ValueError(f"slicer: `out` must hold {dt} of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+        table, count, rms = out
+        if pad_mode not in SLICER_PAD:
+            raise ValueError(f"slicer: pad_mode must be one of {sorted(SLICER_PAD)}, got {pad_mode!r}")
+        geo = (int(win), int(hop), float(threshold), int(min_length), int(min_interval), int(max_sil_kept), SLICER_PAD[pad_mode],
+               _ptr(rms), _ptr(table), _ptr(count), cap)
+        if B and n_dev is not None:
+            self.call("ddsp_slicer_ragged", _ptr(x), int(B), int(T), _ptr(self._counts_dev(n_dev, B)), *geo)
+        elif B:
+            self.call("ddsp_slicer", _ptr(x), int(B), int(T), *geo)
+        return table, count, rms
+
     # -- a10 -----------------------------------------------------------------------------------
     def sins_bank(self, ctrl2d, col0, n_harmonics, f0_frames, phase, B, Fr, hop, sr):
         out = torch.empty(B, Fr * hop, device=ctrl2d.device, dtype=torch.float32)
@@ -1489,6 +1530,23 @@ def f0_ac_frames(T, sr, hop, f0_min):
     if n < 0:
         raise ValueError(f"f0_ac_frames: bad length {T}, rate {sr}, hop {hop} or f0_min {f0_min}")
     return n
+
+
+def slicer_frames(n, win, hop):
+    """RMS frames of n samples for the silence slicer (`ddsp_slicer_frames`, a host computation):
+    1 + (n + 2 * (win // 2) - win) // hop."""
+    F = int(load_library().ddsp_slicer_frames(int(n), int(win), int(hop)))
+    if F < 0:
+        raise ValueError(f"slicer_frames: bad length {n}, window {win} or hop {hop}")
+    return F
+
+
+def slicer_capacity(F_max, min_interval):
+    """Rows of the slicer's chunk table that always suffice for rows of at most F_max frames (include/ddsp_amd.h): at most
+    F_max // min_interval tags with a silent run of their own, one more by the leading rule, and 2 K + 1 chunks for K tags."""
+    if int(min_interval) < 1 or int(F_max) < 0:
+        raise ValueError(f"slicer_capacity: bad frame count {F_max} or min_interval {min_interval} (frames)")
+    return 2 * (int(F_max) // int(min_interval) + 1) + 1
 
 
 def crepe_ragged_table(n16, hop=80):

@@ -6,14 +6,16 @@ per-slice `model(...)[0]`, the volume gate multiplied into the returned signal i
 cross-fade of slices; with `batch_frames=` the slices are rendered in ragged batches (`model(..., n_frames=)`) instead of
 one after the other, and with `enhancer_batch_samples=` they are enhanced in ragged batches too
 (`Enhancer.enhance_batch`).  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
-(`Units_Encoder`) on the device, then `render`.  Cutting the audio into slices (`slicer.Slicer`, a librosa-based silence
-detector) stays with the caller: `convert` takes the slice boundaries.
+(`Units_Encoder`) on the device, then `render`.  `split` cuts the audio into slices as `main.split` does, with the package's
+own `slicer.Slicer` (the reference's silence detector on the device); `convert(..., slices=None, ...)` calls it, or takes
+the slice boundaries of any other detector.
 """
 import numpy as np
 import torch
 
 import hipddsp
 from sharding import stack_rows
+from slicer import Slicer
 
 
 def cross_fade(a: np.ndarray, b: np.ndarray, idx: int):
@@ -157,12 +159,21 @@ def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, thresho
     return result, sr_o
 
 
+def split(audio, sample_rate, hop_size, db_thresh=-40, min_len=5000):
+    """The slicing of `main.split` (main.py:34-40): audio (T,) numpy array or tensor at `sample_rate` -> the list of
+    (start_sample, end_sample) of every chunk `Slicer(sr=sample_rate, threshold=db_thresh, min_length=min_len)` tags with
+    start != end - the silence chunks too: `main.split` does not look at the flag.  One read-back (chunk table and count).
+    The snapping to whole frames of `hop_size` (main.py:41-46) is `convert`'s."""
+    rows = Slicer(sr=sample_rate, threshold=db_thresh, min_length=min_len).chunk_rows(audio)
+    return [(int(a), int(b)) for a, b, _ in rows if a != b]
+
+
 @torch.no_grad()
 def convert(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, key=0, spk_mix_dict=None,
             threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None):
     """`main.py:88-174` from the raw audio: audio (T,) numpy array or device tensor at `sample_rate`; `slices` a list of
-    (start_sample, end_sample) as the reference's `Slicer` tags them (`split_time`) - the slicer itself is not part of this
-    package, any silence detector that yields sample ranges will do.  f0 of the whole file (uv_interp on) shifted by `key`
+    (start_sample, end_sample) as the reference's `Slicer` tags them (`split_time`) - what `split` returns, or the ranges of
+    any other silence detector - or None: `split(audio, sample_rate, hop_size)` with `main.py`'s defaults.  f0 of the whole file (uv_interp on) shifted by `key`
     semitones ONCE (the reference applies the shift twice), volume of the whole file at
     `hop_size = block_size * sample_rate / sampling_rate`, then per slice, snapped to whole frames as `main.split` does
     (main.py:41-46: start_frame = int(start // hop_size), end_frame = int(end // hop_size), audio[int(start_frame *
@@ -199,6 +210,8 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
     if key != 0:
         f0 = f0 * 2 ** (float(key) / 12)
     volume = hipddsp.context_for(dev).volume_extract(x[None], hop_size)
+    if slices is None:
+        slices = split(x, sample_rate, hop_size)
     segments = []
     for start, end in slices:
         start_frame, end_frame = int(int(start) // hop_size), int(int(end) // hop_size)

@@ -811,6 +811,38 @@ int ddsp_f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64
 int ddsp_f0_ac_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int sr,
                       double hop, double f0_min, double f0_max, int64_t n_frames, int uv_interp, float* out, int32_t* choice);
 
+/* ---- the silence slicer (reference: slicer.py `Slicer.slice`, the stage in front of main.py's per-slice loop) -------------
+ * Two kernels.  Frame RMS as librosa.feature.rms documents it: frame i of a row of n samples covers the samples
+ * [i * hop - win / 2, i * hop - win / 2 + win) (integer division), a sample outside [0, n) reads 0 (pad_mode
+ * DDSP_SLICER_PAD_CONSTANT, librosa >= 0.10) or the sample numpy's 'reflect' rule names (DDSP_SLICER_PAD_REFLECT, older
+ * librosa) - selected by a bounds test, never materialised - and the value is sqrt(sum(x^2) / win) with fp32 products summed
+ * in fp64.  Then one wave per row walks the row's values and reproduces the reference's tagging state machine and chunk
+ * assembly (slicer.py:32-111) exactly: `threshold` is the linear level a frame must stay below to be silent, `min_length`,
+ * `min_interval` and `max_sil_kept` are in FRAMES as the reference's constructor rounds them; a row with n <= min_length (a
+ * sample count against a frame count, as the reference compares) is one un-sliced chunk; every argmin returns the lowest index
+ * among equal minima.
+ * ddsp_slicer_frames: 1 + (n + 2 * (win / 2) - win) / hop, the frames of n samples (-1: bad arguments).  A host computation.
+ * ddsp_slicer: audio (B, T) -> rms (B, F), F = ddsp_slicer_frames(T, win, hop); table (B, capacity, 3) int32 rows
+ *   (start_sample, end_sample, is_silence) in the reference's order, zero-length silence chunks included, and count (B) int32;
+ *   the table's rows from count[b] on are zeros.
+ *   Capacity: a tag needs a silent run of its own of at least min_interval frames, or the leading rule, which fires once; K
+ *   tags give at most 2 K + 1 chunks (a voiced chunk in front of each tag and one behind the last).  So capacity =
+ *   2 * (F / min_interval + 1) + 1 rows always suffice.  A row that would exceed a smaller capacity writes the chunks that fit,
+ *   count[b] = capacity, and sets the context's device error word (DDSP_ERR_ARG from ddsp_ctx_poll_error or the next call that
+ *   takes it).
+ * ddsp_slicer_ragged: n_samples[b] in 1..T samples per row (a DEVICE array): row b is the row cut alone at its own length, bit
+ *   for bit; samples from n_samples[b] on are never read and rms[b][i] = 0 from the row's own frame count on.
+ * T + 4 * hop + win < 2^31, 1 <= win, 1 <= hop, 1 <= min_interval.  Neither call synchronises, allocates or reads back. */
+#define DDSP_SLICER_PAD_CONSTANT 0
+#define DDSP_SLICER_PAD_REFLECT 1
+int64_t ddsp_slicer_frames(int64_t n, int64_t win, int64_t hop);
+int ddsp_slicer(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int64_t win, int64_t hop,
+                double threshold, int64_t min_length, int64_t min_interval, int64_t max_sil_kept, int pad_mode, float* rms,
+                int32_t* table, int32_t* count, int64_t capacity);
+int ddsp_slicer_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
+                       int64_t win, int64_t hop, double threshold, int64_t min_length, int64_t min_interval,
+                       int64_t max_sil_kept, int pad_mode, float* rms, int32_t* table, int32_t* count, int64_t capacity);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream --------------------- */
 /* ddsp_profile_begin arms the families in `family_mask` (bit i = family i, see the name returned); while armed,
  * each kernel launch of such a family is bracketed by hipEventRecord on the caller's stream.  ddsp_profile_end
