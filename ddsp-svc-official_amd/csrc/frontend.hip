@@ -7,6 +7,8 @@
 // Both are HBM-bound streaming kernels: 4 B read per sample / 8 B per copied feature.
 #include "common.h"
 
+#include <algorithm>
+
 namespace {
 
 // one wavefront per (utterance, frame).  Block n is padded[int(n*h) : min(int((n+1)*h), Tp)] of the signal reflect-padded
@@ -211,6 +213,56 @@ extern "C" int ddsp_enhancer_keys(ddsp_ctx* ctx, void* stream, const float* f0, 
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     hipLaunchKernelGGL(enhancer_keys_kernel, dim3((unsigned)S), dim3(64), 0, st, f0, Fr, cut_frames, max_key, request, thresholds, key);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+// The conversion leg of validation (solver.py:46-54) without its host round trip: per row the target speaker follows from the
+// source id - (src + 1) % n_spk, and 0 becomes 1 - and the f0 is mapped between the two speakers' log-f0 statistics,
+// out = exp(lfo[tgt] * ln(f0) / lfo[src]) in fp32 in the reference's order of operations.  f0 == 0 (unvoiced) gives exactly 0
+// (there: exp(-inf)), frames at or after a row's count are written as 0 and not read.  A source id outside [1, n_spk] is not
+// used as an index: the row comes out as zeros with target 0 and the context's device error word is set.
+namespace {
+__global__ void __launch_bounds__(256) vc_f0_map_kernel(const float* __restrict__ f0, const int64_t* __restrict__ src,
+                                                        const float* __restrict__ lfo, int n_spk, int64_t Fr,
+                                                        const int32_t* __restrict__ n_frames, float* __restrict__ out,
+                                                        int64_t* __restrict__ tgt, int* __restrict__ err) {
+    const int64_t b = blockIdx.y;
+    const int64_t s = src[b];
+    const bool ok = s >= 1 && s <= n_spk;
+    int64_t t = ok ? (s + 1) % n_spk : 0;
+    if (ok && t == 0) t = 1;                       // 1 <= t <= max(1, n_spk - 1)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        tgt[b] = t;
+        if (!ok) __hip_atomic_store(err, DDSP_DEV_ERR_SPK_ID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    int64_t nb = n_frames ? (int64_t)n_frames[b] : Fr;
+    nb = !ok ? 0 : nb < 0 ? 0 : nb > Fr ? Fr : nb;
+    const float ls = ok ? lfo[s - 1] : 1.f, lt = ok ? lfo[t - 1] : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < Fr; i += (int64_t)gridDim.x * 256) {
+        float v = 0.f;
+        if (i < nb) {
+            const float f = f0[b * Fr + i];
+            if (f > 0.f) v = expf(__fdiv_rn(lt * logf(f), ls));
+        }
+        out[b * Fr + i] = v;
+    }
+}
+}  // namespace
+
+extern "C" int ddsp_vc_f0_map(ddsp_ctx* ctx, void* stream, const float* f0, const int64_t* src_spk, const float* lfo, int n_spk,
+                              int64_t B, int64_t Fr, const int32_t* n_frames, float* f0_out, int64_t* tgt_spk) {
+    DDSP_REQUIRE(ctx, ctx && f0 && src_spk && lfo && f0_out && tgt_spk, "ddsp_vc_f0_map: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && Fr >= 1 && n_spk >= 1, "ddsp_vc_f0_map: bad shape");
+    int rc;
+    if ((rc = ddsp_take_dev_error(ctx))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    int* dev_err = nullptr;
+    if ((rc = ddsp_dev_error_ptr(ctx, &dev_err))) return rc;
+    const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(Fr, 256), 64);
+    hipLaunchKernelGGL(vc_f0_map_kernel, dim3(gx, (unsigned)B), dim3(256), 0, st, f0, src_spk, lfo, n_spk, Fr, n_frames, f0_out,
+                       tgt_spk, dev_err);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

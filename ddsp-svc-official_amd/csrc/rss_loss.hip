@@ -230,6 +230,19 @@ __global__ void loss_combine_kernel(const double* __restrict__ stats, int B, dou
     loss[0] = (first ? 0.f : loss[0]) + (float)v;
 }
 
+// loss_rows[b] += weight * (sqrt(d2_b / s2_b) + alpha * l1_b / (F_b * Mb)): the loss of row b scored alone, from the same folded
+// statistics (validation: one value per utterance, no gradient).  The host has checked that every row has a frame (F_b >= 1).
+__global__ void loss_rows_kernel(const double* __restrict__ stats, int B, int Mb, double alpha, double weight,
+                                 float* __restrict__ loss_rows, int first, const int* __restrict__ n_samples, int64_t T, int N,
+                                 int hop, int F) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int Fb = row_stft_frames(n_samples, b, T, N, hop, F);
+    const double* o = stats + (int64_t)b * LS_CHUNKS * 3;
+    const double v = weight * (sqrt(o[0]) / sqrt(o[1]) + alpha * o[2] / ((double)Fb * Mb));
+    loss_rows[b] = (first ? 0.f : loss_rows[b]) + (float)v;
+}
+
 // dX[row][2f | 2f+1] = dL/dS_p * (re, im) / |X|
 __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ St, const float* __restrict__ Sp,
                                                         float* __restrict__ X, const double* __restrict__ stats, int B,
@@ -293,8 +306,9 @@ __global__ void __launch_bounds__(256) frames_ola_kernel(const float* __restrict
 // ns_host / ns_dev: the rows' sample counts on the host (checks, cell counts) and on the device (the kernels), or both null
 static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
                         const int* ns_host, const int* ns_dev, const int* n_ffts_host, const int* hops_host, int n_scale,
-                        float alpha, float eps, float* loss, float* grad_pred) {
-    DDSP_REQUIRE(ctx, ctx && x_pred && x_true && n_ffts_host && loss, "ddsp_rss_loss: null argument");
+                        float alpha, float eps, float* loss, float* grad_pred, float* loss_rows = nullptr) {
+    // loss_rows (device float[B], with counts and without grad_pred): one loss per row instead of the batch's scalar
+    DDSP_REQUIRE(ctx, ctx && x_pred && x_true && n_ffts_host && (loss || loss_rows), "ddsp_rss_loss: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 32768 && T >= 4 && n_scale >= 1 && n_scale <= 64, "ddsp_rss_loss: bad shape");
     DDSP_REQUIRE(ctx, T % 4 == 0 && ((uintptr_t)x_pred % 16) == 0 && ((uintptr_t)x_true % 16) == 0,
                  "ddsp_rss_loss: signals must be 16-byte aligned with T % 4 == 0");
@@ -314,6 +328,9 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
                 any = any || ns_host[b] >= N;
             }
             DDSP_REQUIRE(ctx, any, "ddsp_rss_loss_ragged: no row has a whole frame at one of the scales");
+            if (loss_rows)
+                for (int64_t b = 0; b < B; ++b)
+                    DDSP_REQUIRE(ctx, ns_host[b] >= N, "ddsp_rss_loss_rows: a row has no whole frame at one of the scales");
         }
         tabT_f = std::max(tabT_f, 2 * Mb * Kp);
         tab_f = std::max(tab_f, (size_t)N * Kb);
@@ -400,8 +417,12 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
         }
         hipLaunchKernelGGL(loss_stats_kernel, dim3((unsigned)B, LS_CHUNKS), dim3(256), 0, st, St, Sp, (int64_t)F * Mb, stats, ns_dev, T, N, hop, F);
         hipLaunchKernelGGL(loss_fold_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, stats, (int)B);
-        hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(64), 0, st, stats, (int)B, count, rows_ne,
-                           (double)alpha, weight, loss, s == 0 ? 1 : 0, ns_dev, T, N, hop, F);
+        if (loss_rows)
+            hipLaunchKernelGGL(loss_rows_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, stats, (int)B, Mb, (double)alpha,
+                               weight, loss_rows, s == 0 ? 1 : 0, ns_dev, T, N, hop, F);
+        else
+            hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(64), 0, st, stats, (int)B, count, rows_ne,
+                               (double)alpha, weight, loss, s == 0 ? 1 : 0, ns_dev, T, N, hop, F);
         flops += 2.0 * 2.0 * M * (double)N * 2 * Mb;
         if (grad_pred) {
             const int64_t total = M * Mb;
@@ -438,4 +459,12 @@ extern "C" int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_
     DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev, "ddsp_rss_loss_ragged: null n_samples");
     return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
                         n_scale, alpha, eps, loss, grad_pred);
+}
+
+extern "C" int ddsp_rss_loss_rows(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                                  const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host,
+                                  const int* hops_host, int n_scale, float alpha, float eps, float* loss_rows) {
+    DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev && loss_rows, "ddsp_rss_loss_rows: null argument");
+    return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
+                        n_scale, alpha, eps, nullptr, nullptr, loss_rows);
 }

@@ -220,6 +220,7 @@ class AudioDataset:
         self.duration = tables["duration"]
         self._frames, self._audio_len = tables["frames"], tables["audio_len"]
         self.next_valid = tables["next_valid"]
+        self.spk_ids = [int(v) for v in tables["spk_id"]]      # per file, on the host (validation names its speakers)
         self.crop = crop_frames(waveform_sec, hop_size, sample_rate)
         self.whole = [whole_frames(d, hop_size, sample_rate) for d in self.duration]
         self._upload(arenas, tables, device)
@@ -316,7 +317,9 @@ class AudioDataset:
         t = self._triples([[i, 0, int(k)] for i, k in zip(files, unit_idx)])
         lens = torch.tensor(n, dtype=torch.int32).to(self.device)
         got = self.ctx.dataset_gather(self.view, len(files), max(n), triples=t, len_rows=lens, out=out)
-        return _Batch(self._finish(got, n_frames=n), self.paths)
+        batch = _Batch(self._finish(got, n_frames=n), self.paths)
+        batch["name"] = [self.paths[i] for i in files]         # the files were named by the caller: no copy of `draws`
+        return batch
 
     def whole_batches(self, batch_frames):
         """Every file once, whole, grouped with `infer_offline.group_segments` so that a group's padded size (rows * longest)

@@ -14,6 +14,11 @@ rows that have a frame, each norm over the row's own frames; the log term is the
 sum_b F_b * (N // 2 + 1) cells that exist.  Nothing at or after sample (F_b - 1) * hop + N of a row is read into arithmetic
 (the kernels select), the gradient is exactly 0 from there on, and with every count equal to T value and gradient have the bits
 of the call without counts.  A scale at which no row has a frame raises ValueError before anything is launched.
+
+Additive: `RSSLoss.rows(x_pred, x_true, n_samples)` -> (B,), one loss per row and no gradient (validation, where every
+utterance counts once): row b is what `forward` returns for `x[b:b+1, :n_samples[b]]` alone, both terms over the row's own
+cells, from the same kernels up to the per-row statistics.  Every row needs a frame at every drawn scale (ValueError before
+anything is launched otherwise).
 """
 import torch
 import torch.nn as nn
@@ -90,19 +95,40 @@ class RSSLoss(nn.Module):
         """Use these scales for the next call instead of drawing (one-shot)."""
         self._pinned = [int(n) for n in n_ffts]
 
+    def _draw(self):
+        """The scales of one call: the pinned draw (used up) or `torch.randint` as the reference draws (`ddsp/loss.py:39`)."""
+        if self._pinned is not None:
+            n_ffts, self._pinned = self._pinned, None
+        else:
+            n_ffts = [int(v) for v in torch.randint(self.fft_min, self.fft_max, (self.n_scale,))]
+        self.last_scales = n_ffts
+        return n_ffts
+
     def forward(self, x_pred, x_true, n_samples=None):
         """`n_samples`: rows of different length (module docstring).  The scales are drawn (and a pinned draw is used up)
         before the counts are checked against them."""
         n_samples = _check(x_pred, x_true, self.overlap, n_samples)
         if n_samples is None:
             _need_device(x_pred)
-        if self._pinned is not None:
-            n_ffts, self._pinned = self._pinned, None
-        else:
-            n_ffts = [int(v) for v in torch.randint(self.fft_min, self.fft_max, (self.n_scale,))]
-        self.last_scales = n_ffts
+        n_ffts = self._draw()
         if n_samples is not None:
             hipddsp.check_loss_scales(n_samples, n_ffts)
             _need_device(x_pred)
         # cached training audio may be fp16 (reference data_loaders.py:81-83): promote the target
         return _SpectralLossFn.apply(x_pred, x_true.to(torch.float32), n_ffts, self.alpha, self.eps, self.overlap, n_samples)
+
+    def rows(self, x_pred, x_true, n_samples):
+        """One loss per row, (B,), without a gradient (module docstring).  The scales are drawn, or a pinned draw is used up,
+        exactly as in `forward`."""
+        if n_samples is None:
+            raise ValueError("rows: n_samples is required (the rows' lengths)")
+        n_samples = _check(x_pred, x_true, self.overlap, n_samples)
+        n_ffts = self._draw()
+        for b, n in enumerate(n_samples):
+            if n < max(n_ffts):
+                raise ValueError(f"n_samples[{b}] = {n}: the row holds no whole frame at scale n_fft = {max(n_ffts)}")
+        _need_device(x_pred)
+        hops = None if self.overlap == 0 else [_hop(n, self.overlap) for n in n_ffts]
+        loss, _ = hipddsp.context_for(x_pred.device).rss_loss(x_pred, x_true.to(torch.float32), n_ffts, self.alpha, self.eps,
+                                                              hops=hops, n_samples=n_samples, rows=True)
+        return loss

@@ -278,6 +278,9 @@ SIGNATURES = {
     "ddsp_ragged_frames_adjoint": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64]),
     "ddsp_rss_loss_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
                                     _int, _f32, _f32, _vp, _vp]),
+    "ddsp_rss_loss_rows": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
+                                  _int, _f32, _f32, _vp]),
+    "ddsp_vc_f0_map": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
     "ddsp_dataset_gather": (_int, [_vp, _vp, _c.POINTER(DatasetView), _vp, _vp, _i64, _i64, _u64, _vp, _i64, _f64, _i64, _i64,
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
 }
@@ -1352,10 +1355,11 @@ class Context:
         return d_ctrl
 
     # -- a13 -----------------------------------------------------------------------------------
-    def rss_loss(self, x_pred, x_true, n_ffts, alpha=1.0, eps=1e-7, want_grad=False, hops=None, n_samples=None):
+    def rss_loss(self, x_pred, x_true, n_ffts, alpha=1.0, eps=1e-7, want_grad=False, hops=None, n_samples=None, rows=False):
         """-> (loss (1,) device tensor, d loss/d x_pred (B,T) | None) for the given list of scales; `hops`: one hop per
         scale (default: hop = n_fft, the reference's overlap = 0).  `n_samples`: the list `check_n_samples` returned -
-        rows of different length (include/ddsp_amd.h: ddsp_rss_loss_ragged)."""
+        rows of different length (include/ddsp_amd.h: ddsp_rss_loss_ragged).  `rows` (with `n_samples`, without `want_grad`):
+        -> (loss per row (B,), None), every row scored alone (ddsp_rss_loss_rows)."""
         xp = x_pred.detach().contiguous().float()
         xt = x_true.detach().contiguous().float()
         B, T = xp.shape
@@ -1363,20 +1367,46 @@ class Context:
             raise ValueError(f"x_pred {tuple(xp.shape)} and x_true {tuple(xt.shape)} must have the same shape")
         if T % 4:
             raise ValueError("signal length must be a multiple of 4")
+        if rows and (n_samples is None or want_grad):
+            raise ValueError("rss_loss: rows=True takes n_samples and has no gradient")
         arr = (_int * len(n_ffts))(*[int(n) for n in n_ffts])
         if hops is not None and len(hops) != len(n_ffts):
             raise ValueError("one hop per scale")
         harr = (_int * len(n_ffts))(*[int(h) for h in hops]) if hops is not None else None
-        loss = torch.empty(1, device=xp.device, dtype=torch.float32)
+        loss = torch.empty(B if rows else 1, device=xp.device, dtype=torch.float32)
         grad = torch.empty_like(xp) if want_grad else None
         if n_samples is not None:
             ns = (_int * B)(*n_samples)
-            self.call("ddsp_rss_loss_ragged", _ptr(xp), _ptr(xt), B, T, ns, _ptr(self.ragged_counts(n_samples)), arr, harr,
-                      len(n_ffts), float(alpha), float(eps), _ptr(loss), _ptr(grad))
+            common = (_ptr(xp), _ptr(xt), B, T, ns, _ptr(self.ragged_counts(n_samples)), arr, harr, len(n_ffts), float(alpha),
+                      float(eps), _ptr(loss))
+            if rows:
+                self.call("ddsp_rss_loss_rows", *common)
+            else:
+                self.call("ddsp_rss_loss_ragged", *common, _ptr(grad))
         else:
             self.call("ddsp_rss_loss", _ptr(xp), _ptr(xt), B, T, arr, harr, len(n_ffts), float(alpha), float(eps), _ptr(loss),
                       _ptr(grad))
         return loss, grad
+
+    def vc_f0_map(self, f0_frames, spk_id, lfo, n_frames=None):
+        """Validation's conversion leg (`ddsp_vc_f0_map`): f0 (B, Fr[, 1]), spk_id (B[, 1]) int64 1-based and the table lfo
+        (n_spk,) fp32, on the device -> (mapped f0 in f0's shape, target ids in spk_id's shape): target = (src + 1) % n_spk, 0
+        becomes 1; f0 * -> exp(lfo[tgt] * ln(f0) / lfo[src]), 0 stays 0.  n_frames: the (B,) int32 device tensor of a ragged
+        batch (`ragged_counts`) - frames past a row's count come out 0."""
+        B = f0_frames.shape[0]
+        if spk_id.dtype != torch.int64 or spk_id.numel() != B:
+            raise ValueError("vc_f0_map: spk_id must hold B int64 ids")
+        if lfo.dtype != torch.float32 or lfo.dim() != 1 or lfo.numel() < 1:
+            raise ValueError("vc_f0_map: lfo must be an fp32 table (n_spk,)")
+        f0 = f0_frames.reshape(B, -1).contiguous().float()
+        Fr = f0.shape[1]
+        if n_frames is not None:
+            self._counts_dev(n_frames, B)
+        out = torch.empty_like(f0)
+        tgt = torch.empty(B, device=f0.device, dtype=torch.int64)
+        self.call("ddsp_vc_f0_map", _ptr(f0), _ptr(spk_id.contiguous()), _ptr(lfo.contiguous()), lfo.numel(), B, Fr, _ptr(n_frames),
+                  _ptr(out), _ptr(tgt))
+        return out.reshape(f0_frames.shape), tgt.reshape(spk_id.shape)
 
     # -- a14 -----------------------------------------------------------------------------------
     def sola(self, audio, sola_buffer, block, xfade, search, delay):

@@ -363,6 +363,21 @@ int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float*
 int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
                          const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host, const int* hops_host,
                          int n_scale, float alpha, float eps, float* loss, float* grad_pred);
+/* One loss per row instead of the batch's scalar (validation: every utterance counts once; no gradient): the arguments of
+ * ddsp_rss_loss_ragged, loss_rows a device float[B].  loss_rows[b] = mean_N (||S_t - S_p||_F / ||S_t + S_p||_F +
+ * alpha * mean|ln S_t - ln S_p|), both terms over row b's own F_b * (N/2 + 1) cells - the loss of x[b][0..n_b) scored alone.
+ * The framing, transform and statistics kernels are those of the calls above; only the last kernel differs.  A row without a
+ * frame at one of the scales (n_b < N): DDSP_ERR_ARG before anything is launched. */
+int ddsp_rss_loss_rows(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                       const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host, const int* hops_host,
+                       int n_scale, float alpha, float eps, float* loss_rows);
+/* The conversion leg of validation (reference solver.py:46-54) in one launch: f0 (B, Fr), src_spk (B) int64 1-based, lfo
+ * (n_spk) the per-speaker log-f0 statistic (f0_stats.npy, entry id - 1), all on the device.  tgt_spk[b] = (src + 1) % n_spk,
+ * and 0 becomes 1; f0_out[b][i] = exp(lfo[tgt] * ln(f0) / lfo[src]) in fp32, exactly 0 where f0 == 0, and 0 for
+ * i >= n_frames[b] (device int32 (B), or NULL: every row has Fr frames; nothing is read there).  A source id outside
+ * [1, n_spk] is not used as an index: the row is zeros, its target 0, and the context's device error word is set. */
+int ddsp_vc_f0_map(ddsp_ctx* ctx, void* stream, const float* f0, const int64_t* src_spk, const float* lfo, int n_spk, int64_t B,
+                   int64_t Fr, const int32_t* n_frames, float* f0_out, int64_t* tgt_spk);
 
 /* ---- a14: SOLA splice of the real-time path -------------------------------------------------- */
 /* replaces gui.py:405-430: within audio[-block-xfade-search-delay : -delay] find the lag (0..search) that
