@@ -246,6 +246,9 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
     if (code == DDSP_DEV_ERR_SLICER)
         return ddsp_fail(ctx, DDSP_ERR_ARG, "a row with more chunks than the table's capacity in an earlier ddsp_slicer call",
                          "the table holds the chunks that fit");
+    if (code == DDSP_DEV_ERR_GATE_ROWS)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a row whose frames lie outside [0, Fr] or its own row in an earlier ddsp_volume_gate_rows call",
+                         "those rows were left as they were");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

@@ -94,6 +94,26 @@ __global__ void __launch_bounds__(256) sola_splice_kernel(const float* __restric
     for (int i = threadIdx.x; i < xfade; i += 256) sola_buf[i] = src[block + i];
 }
 
+// upsample(dilate9(v > thr)) at sample j of frame m of the track v[0, Fr): the edge-replicated 9-frame maximum of the thresholded
+// frames m and m + 1 (the last frame stands for the one behind it), mixed linearly
+__device__ __forceinline__ float volume_gate_at(const float* __restrict__ v, int Fr, int m, int j, float thr, float inv_hop) {
+    float g[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        int mm = m + q;
+        if (mm > Fr - 1) mm = Fr - 1;
+        float mx = 0.f;
+        for (int d = -4; d <= 4; ++d) {  // edge-replicated 9-frame max
+            int f = mm + d;
+            f = f < 0 ? 0 : (f > Fr - 1 ? Fr - 1 : f);
+            mx = fmaxf(mx, v[f] > thr ? 1.0f : 0.0f);
+        }
+        g[q] = mx;
+    }
+    const float w1 = (float)j * inv_hop;
+    return fmaf(1.0f - w1, g[0], __fmul_rn(w1, g[1]));
+}
+
 // signal[b][t] *= upsample(dilate9(volume > thr))[t]
 __global__ void __launch_bounds__(256) volume_gate_kernel(float* __restrict__ signal, const float* __restrict__ volume,
                                                           float thr, int64_t B, int Fr, int hop) {
@@ -102,24 +122,29 @@ __global__ void __launch_bounds__(256) volume_gate_kernel(float* __restrict__ si
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = i / ((int64_t)Fr * hop);
         const int64_t t = i - b * (int64_t)Fr * hop;
-        const int m = (int)(t / hop), j = (int)(t % hop);
-        const float* v = volume + b * Fr;
-        float g[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            int mm = m + q;
-            if (mm > Fr - 1) mm = Fr - 1;
-            float mx = 0.f;
-            for (int d = -4; d <= 4; ++d) {  // edge-replicated 9-frame max
-                int f = mm + d;
-                f = f < 0 ? 0 : (f > Fr - 1 ? Fr - 1 : f);
-                mx = fmaxf(mx, v[f] > thr ? 1.0f : 0.0f);
-            }
-            g[q] = mx;
-        }
-        const float w1 = (float)j * inv_hop;
-        signal[i] *= fmaf(1.0f - w1, g[0], __fmul_rn(w1, g[1]));
+        signal[i] *= volume_gate_at(volume + b * Fr, Fr, (int)(t / hop), (int)(t % hop), thr, inv_hop);
     }
+}
+
+// The gate of one file for a ragged batch of its slices: signal[b][t] *= gate[start[b] * hop + t] for t < n[b] * hop, the rest
+// of the row untouched.  grid (x, B).  A row that does not lie inside the file's frames or its own T_max samples is skipped
+// whole (no index is formed from it) and raises the context's error word.
+__global__ void __launch_bounds__(256) volume_gate_rows_kernel(float* __restrict__ signal, const float* __restrict__ volume,
+                                                               const int32_t* __restrict__ start_frame,
+                                                               const int32_t* __restrict__ n_frames, float thr, int64_t T_max,
+                                                               int Fr, int hop, int* __restrict__ err) {
+    const int64_t b = blockIdx.y;
+    const int64_t s = start_frame[b], n = n_frames[b];
+    if (s < 0 || n < 0 || s + n > Fr || n * hop > T_max) {
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            __hip_atomic_store(err, DDSP_DEV_ERR_GATE_ROWS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    const float inv_hop = 1.0f / (float)hop;
+    float* __restrict__ row = signal + b * T_max;
+    const int64_t len = n * hop;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < len; t += (int64_t)gridDim.x * 256)
+        row[t] *= volume_gate_at(volume, Fr, (int)(s + t / hop), (int)(t % hop), thr, inv_hop);
 }
 
 // ---- phase-vocoder cross-fade (gui.py:14-31, optional `use_phase_vocoder` splice of gui.py:417-423) ----------------
@@ -305,6 +330,27 @@ extern "C" int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, cons
     hipLaunchKernelGGL(volume_gate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, signal, volume, threshold, B,
                        (int)Fr, hop);
     ddsp_prof_end(ctx, st, 0.0, 8.0 * total);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+extern "C" int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* start_frame,
+                                     const int32_t* n_frames, float threshold, int64_t B, int64_t T_max, int64_t Fr, int hop) {
+    DDSP_REQUIRE(ctx, ctx && signal && volume && start_frame && n_frames, "ddsp_volume_gate_rows: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && B <= 65535 && T_max >= 1 && hop >= 1 && (hop & (hop - 1)) == 0 && Fr >= 1 && Fr < (1ll << 31) / hop,
+                 "ddsp_volume_gate_rows: bad shape");
+    int rc;
+    if ((rc = ddsp_take_dev_error(ctx))) return rc;
+    if (B == 0) return DDSP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    int* dev_err = nullptr;
+    if ((rc = ddsp_dev_error_ptr(ctx, &dev_err))) return rc;
+    const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(T_max, 256), 1024);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(volume_gate_rows_kernel, dim3(gx, (unsigned)B), dim3(256), 0, st, signal, volume, start_frame, n_frames,
+                       threshold, T_max, (int)Fr, hop, dev_err);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * B * (double)T_max);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

@@ -183,6 +183,8 @@ SIGNATURES = {
     "ddsp_rss_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _int, _f32, _f32, _vp, _vp]),
     "ddsp_sola": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
     "ddsp_volume_gate": (_int, [_vp, _vp, _vp, _vp, _f32, _i64, _i64, _int]),
+    "ddsp_volume_gate_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
+    "ddsp_stitch": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
     "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "ddsp_volume_extract": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "ddsp_volume_extract_frac": (_int, [_vp, _vp, _vp, _i64, _i64, _f64, _vp]),
@@ -1469,6 +1471,39 @@ class Context:
         self.call("ddsp_volume_gate", _ptr(signal), _ptr(vol), float(10 ** (float(threshold_db) / 20)), B,
                   vol.shape[1], int(hop))
         return signal
+
+    def volume_gate_rows_(self, signal, volume, start_dev, n_dev, threshold_db, hop):
+        """In place, for a ragged batch of slices of ONE file: signal (B, T_max) fp32, row b's samples t < n[b] * hop times the
+        file's gate (`volume_gate_` of the whole `volume` (Fr,)) at start[b] * hop + t; the rest of a row is not touched.
+        start_dev, n_dev: (B,) int32 device tensors (`ragged_counts`).  One launch (`ddsp_volume_gate_rows`), nothing is read
+        back: a row outside the file's frames or its own row stays as it is and raises ValueError from `poll_error()` after a
+        synchronise or from the next call that takes the error word."""
+        if signal.dim() != 2 or signal.dtype != torch.float32 or not signal.is_contiguous():
+            raise ValueError("volume_gate_rows_: signal must be a contiguous fp32 (B, T_max) tensor (it is gated in place)")
+        B, T_max = signal.shape
+        vol = volume.reshape(-1).contiguous().float()
+        if B:
+            self.call("ddsp_volume_gate_rows", _ptr(signal), _ptr(vol), _ptr(self._counts_dev(start_dev, B)),
+                      _ptr(self._counts_dev(n_dev, B)), float(10 ** (float(threshold_db) / 20)), B, T_max, vol.numel(), int(hop))
+        return signal
+
+    # -- the stitch ----------------------------------------------------------------------------
+    def stitch(self, pieces, p, fade, total):
+        """pieces: S fp32 device tensors (views into ragged group tensors included; the samples of one piece contiguous);
+        p, fade: their first output sample and cross-faded length (`infer_offline.stitch_plan`, which has checked them);
+        -> the fp64 device tensor (total,) of `ddsp_stitch`: one table upload, one launch, no copy per piece."""
+        if not (len(pieces) == len(p) == len(fade)):
+            raise ValueError(f"stitch: {len(pieces)} pieces, {len(p)} positions and {len(fade)} fades")
+        rows = []
+        for i, (x, pi, fi) in enumerate(zip(pieces, p, fade)):
+            if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"stitch: piece {i} must be fp32 on {self.device} with its samples contiguous")
+            rows.append((x.data_ptr(), int(pi), x.numel(), int(fi)))
+        out = torch.empty(int(total), device=self.device, dtype=torch.float64)
+        if int(total):
+            table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).to(self.device)
+            self.call("ddsp_stitch", _ptr(table), len(rows), _ptr(out), int(total))
+        return out
 
 
 class ResamplePlan:

@@ -8,7 +8,9 @@ one after the other, and with `enhancer_batch_samples=` they are enhanced in rag
 (`Enhancer.enhance_batch`).  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
 (`Units_Encoder`) on the device, then `render`.  `split` cuts the audio into slices as `main.split` does, with the package's
 own `slicer.Slicer` (the reference's silence detector on the device); `convert(..., slices=None, ...)` calls it, or takes
-the slice boundaries of any other detector.
+the slice boundaries of any other detector.  `render_device` / `convert_device` are `render` / `convert_batched` with the end
+on the device too: one gate launch per ragged group (`ddsp_volume_gate_rows`), one launch for the stitch (`stitch_plan`,
+`stitch`: `ddsp_stitch`), the float64 waveform returned as a device tensor; `main.py` is the command line over them.
 """
 import numpy as np
 import torch
@@ -159,6 +161,91 @@ def render(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, thresho
     return result, sr_o
 
 
+def stitch_plan(starts, lengths, block, sr, sr_o):
+    """Where the stitch of `main.py:165-173` puts every piece -> (p, fade, total): piece i, rendered from start frame
+    starts[i] with lengths[i] samples at the output rate sr_o, begins at output sample p[i] = round(starts[i] * block * sr_o /
+    sr) (Python's `round` on that float expression, as the reference writes it), cross-fades its first fade[i] = max(0, end
+    of piece i-1 - p[i]) samples (`cross_fade`) and ends at p[i] + lengths[i]; total is the last end (0 without pieces).
+    Raises ValueError naming the piece when it has no samples, starts before its predecessor (`main.split` yields ascending
+    frames), or is shorter than its fade (the reference's `cross_fade` fails to broadcast there).  Host code only."""
+    if len(starts) != len(lengths):
+        raise ValueError(f"stitch_plan: {len(starts)} start frames for {len(lengths)} pieces")
+    p, fade, cur = [], [], 0
+    for i, (start, n) in enumerate(zip(starts, lengths)):
+        start, n = int(start), int(n)
+        at = round(start * block * sr_o / sr)
+        if n < 1:
+            raise ValueError(f"stitch_plan: piece {i} (start frame {start}) has no samples")
+        if p and at < p[-1]:
+            raise ValueError(f"stitch_plan: piece {i} starts at output sample {at}, before piece {i - 1} at {p[-1]}: the "
+                             "start frames must ascend")
+        f = max(0, cur - at)
+        if n < f:
+            raise ValueError(f"stitch_plan: piece {i} has {n} samples but overlaps the result so far by {f}: a piece must "
+                             "be at least as long as its cross-fade")
+        p.append(at)
+        fade.append(f)
+        cur = at + n
+    return p, fade, cur
+
+
+def stitch(pieces, plan, device=None):
+    """pieces: the rendered slices, fp32 device tensors of any shape holding lengths[i] contiguous samples (rows of a padded
+    group tensor are fine: nothing is packed); plan: `stitch_plan` of their start frames and lengths -> the stitched file as
+    an fp64 device tensor (total,), equal to the reference's host loop (`np.append` / `cross_fade` per slice) bit for bit,
+    from one `ddsp_stitch` launch.  An empty list gives a tensor of length 0 (on `device`, the current HIP device if None)."""
+    p, fade, total = plan
+    if not (len(pieces) == len(p) == len(fade)):
+        raise ValueError(f"stitch: {len(pieces)} pieces for a plan of {len(p)}")
+    cur = 0
+    for i, x in enumerate(pieces):   # the plan is the plan of THESE lengths
+        if x.numel() < 1 or fade[i] != max(0, cur - p[i]) or x.numel() < fade[i]:
+            raise ValueError(f"stitch: piece {i} has {x.numel()} samples, which is not what the plan was made for")
+        cur = p[i] + x.numel()
+    if cur != total:
+        raise ValueError(f"stitch: the pieces end at sample {cur}, the plan at {total}")
+    if not pieces:
+        return torch.zeros(0, dtype=torch.float64, device="cuda" if device is None else device)
+    return hipddsp.context_for(pieces[0].device).stitch(pieces, p, fade, total)
+
+
+@torch.no_grad()
+def render_device(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, threshold_db=-60, enhancer=None,
+                  enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None, enhancer_batch_samples=None):
+    """`render` with its keywords, the result left on the device -> (fp64 device tensor (total,), sample rate), equal to
+    `render`'s array.  Ragged groups through `model(..., n_frames=)`, ONE `ddsp_volume_gate_rows` per group on the group's
+    padded signal (no gate per slice, no whole-file `ones`), `_enhance_ragged` when there is an enhancer, one `stitch` of the
+    rows where they lie.  `batch_frames=None` / `enhancer_batch_samples=None`: one slice per group.  Nothing is read back
+    between the first forward and the returned tensor beyond what `Enhancer.enhance_batch` itself reads."""
+    block = int(args.data.block_size)
+    sr = int(args.data.sampling_rate)
+    ctx = hipddsp.context_for(f0.device)
+    lengths = [units.size(1) for _, units in segments]
+    for (start, _), n in zip(segments, lengths):
+        if start < 0 or start + n > f0.shape[1] or start + n > volume.shape[1]:
+            raise ValueError(f"render_device: the segment at frame {start} has {n} frames of units but f0 / volume cover "
+                             f"{f0.shape[1]} / {volume.shape[1]} frames of the file")
+    pieces = [None] * len(segments)
+    for group in group_segments(lengths, 0 if batch_frames is None else int(batch_frames)):
+        starts = [segments[i][0] for i in group]
+        u, counts = stack_rows([segments[i][1][0] for i in group])
+        f, _ = stack_rows([f0[0, s:s + n] for s, n in zip(starts, counts)])
+        v, _ = stack_rows([volume[0, s:s + n] for s, n in zip(starts, counts)])
+        kw = {} if noise_seed is None else {"noise_seed": noise_seed + min(starts)}
+        if noise is not None:
+            kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
+        signal = model(u, f, v, spk_id=spk_id, spk_mix_dict=spk_mix_dict, n_frames=counts, **kw)[0].contiguous()
+        ctx.volume_gate_rows_(signal, volume[0], ctx.ragged_counts(starts), ctx.ragged_counts(counts), threshold_db, block)
+        for j, i in enumerate(group):
+            pieces[i] = signal[j:j + 1, :counts[j] * block]
+    sr_o = sr
+    if enhancer is not None and segments:
+        pieces, sr_o = _enhance_ragged(enhancer, pieces, segments, f0, sr, block, enhancer_adaptive_key,
+                                       0 if enhancer_batch_samples is None else enhancer_batch_samples)
+    plan = stitch_plan([start for start, _ in segments], [x.shape[-1] for x in pieces], block, sr, sr_o)
+    return stitch(pieces, plan, device=f0.device), sr_o
+
+
 def split(audio, sample_rate, hop_size, db_thresh=-40, min_len=5000):
     """The slicing of `main.split` (main.py:34-40): audio (T,) numpy array or tensor at `sample_rate` -> the list of
     (start_sample, end_sample) of every chunk `Slicer(sr=sample_rate, threshold=db_thresh, min_length=min_len)` tags with
@@ -198,6 +285,28 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
     at most that many padded samples (at the model's rate); it stands before `units_batch_samples`, which
     tests/test_hubert_ragged_host.py pins as the last parameter.  (A function of its own and not a keyword of `convert`:
     tests/test_stream_audio_host.py pins `convert`'s parameter list.)"""
+    segments, f0, volume = _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples)
+    return render(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
+                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
+                  enhancer_batch_samples=enhancer_batch_samples)
+
+
+@torch.no_grad()
+def convert_device(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, batch_frames=None, key=0,
+                   spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
+                   enhancer_batch_samples=None, units_batch_samples=None):
+    """`convert_batched` ending in `render_device`: the same analysis, then ragged rendering, one gate launch per group, the
+    ragged enhancer and one stitch launch -> (fp64 device tensor (total,), sample rate), equal to `convert_batched`'s array.
+    One `.cpu()` of the result is the file's only read-back behind the slicer's chunk table."""
+    segments, f0, volume = _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples)
+    return render_device(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
+                         enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed,
+                         batch_frames=batch_frames, enhancer_batch_samples=enhancer_batch_samples)
+
+
+def _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples):
+    """The part of `convert` in front of the rendering -> (segments [(start_frame, units (1, Fr_seg, n_unit))], f0 (1, Fr, 1)
+    shifted by `key`, volume (1, Fr)), all on the device."""
     hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
     if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
         raise ValueError(f"convert: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop {f0_extractor.hop_size}; "
@@ -221,6 +330,4 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
                              units_encoder.encode(seg, sample_rate, hop_size)))
     if units_batch_samples is not None:
         segments = _encode_ragged(units_encoder, segments, sample_rate, hop_size, units_batch_samples)
-    return render(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
-                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
-                  enhancer_batch_samples=enhancer_batch_samples)
+    return segments, f0, volume

@@ -1,0 +1,91 @@
+"""The reference's offline command line (`main.py`) over `infer_offline.convert_device`: a file goes from raw audio to the
+stitched waveform on the device and is read back once.
+
+    python main.py -m <model.pt> -i <in.wav> -o <out.wav> [-id 1] [-mix None] [-k 0] [-e true] [-pe crepe] [-fmin 50]
+                   [-fmax 1100] [-th -60] [-eak 0] [-sr 44100]
+
+The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
+  * the key shift is applied once (the reference applies it twice);
+  * `-pe` takes 'crepe' and 'ac' (`F0_Extractor`); 'parselmouth', 'dio' and 'harvest' raise as `F0_Extractor` does;
+  * the input is read with `preprocess.load_wav` and, at another rate than `-sr`, resampled on the device with
+    `resample.Resample` as `preprocess` does (the reference's librosa resamples with its own filter);
+  * the output is 16-bit PCM through `scipy.io.wavfile.write` - what the reference's `sf.write` makes of a `.wav` by default;
+  * the reference's md5-keyed f0 cache is left out: the f0 of a file takes milliseconds on the device.
+"""
+import argparse
+from ast import literal_eval
+
+import numpy as np
+import torch
+
+# option, long name, type, default, help - the reference's table
+_OPTIONS = (
+    ("-m", "--model_path", str, None, "path to the model file"),
+    ("-i", "--input", str, None, "path to the input audio file"),
+    ("-o", "--output", str, None, "path to the output audio file"),
+    ("-id", "--spk_id", str, 1, "speaker id (for multi-speaker model) | default: 1"),
+    ("-mix", "--spk_mix_dict", str, "None", "mix-speaker dictionary (for multi-speaker model) | default: None"),
+    ("-k", "--key", str, 0, "key changed (number of semitones) | default: 0"),
+    ("-e", "--enhance", str, "true", "true or false | default: true"),
+    ("-pe", "--pitch_extractor", str, "crepe", "pitch extractor type: crepe (default), ac"),
+    ("-fmin", "--f0_min", str, 50, "min f0 (Hz) | default: 50"),
+    ("-fmax", "--f0_max", str, 1100, "max f0 (Hz) | default: 1100"),
+    ("-th", "--threhold", str, -60, "response threhold (dB) | default: -60"),
+    ("-eak", "--enhancer_adaptive_key", str, 0, "adapt the enhancer to a higher vocal range (number of semitones) | default: 0"),
+    ("-sr", "--sampling_rate", int, 44100, "Audio sampling rate"),
+)
+
+
+def parse_args(args=None, namespace=None):
+    """The reference's options with its defaults; `-m`, `-i` and `-o` are required."""
+    parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    for short, long, kind, default, text in _OPTIONS:
+        parser.add_argument(short, long, type=kind, required=default is None, default=default, help=text)
+    return parser.parse_args(args=args, namespace=namespace)
+
+
+def pcm16(wave):
+    """float waveform -> int16 as libsndfile writes a 16-bit file from floats: scaled by 2^15, rounded to nearest, clipped."""
+    return np.clip(np.rint(np.asarray(wave, dtype=np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+
+
+@torch.no_grad()
+def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda", batch_frames=4096,
+        enhancer_batch_samples=None, units_batch_samples=None):
+    """Converts `cmd.input` into `cmd.output` as the options say -> (fp64 device waveform, sample rate).  `units_encoder`,
+    `f0_extractor`, `enhancer`: objects to use in place of the ones the model's config and the options name (an encoder or
+    extractor built for `cmd.sampling_rate` and the model's hop at that rate).  The batching keywords are `convert_device`'s."""
+    from scipy.io import wavfile
+
+    from ddsp.vocoder import F0_Extractor, Units_Encoder, load_model
+    from infer_offline import convert_device
+    from preprocess import load_wav
+
+    model, args = load_model(cmd.model_path, device=device)
+    wave, rate = load_wav(cmd.input)
+    sr_i = int(cmd.sampling_rate)
+    audio = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(device)
+    if int(rate) != sr_i:
+        from resample import Resample
+        audio = Resample(int(rate), sr_i)(audio)
+    hop_size = int(args.data.block_size) * sr_i / int(args.data.sampling_rate)
+    if f0_extractor is None:
+        f0_extractor = F0_Extractor(cmd.pitch_extractor, sr_i, hop_size, float(cmd.f0_min), float(cmd.f0_max), device=device)
+    if units_encoder is None:
+        units_encoder = Units_Encoder(args.data.encoder, args.data.encoder_ckpt, args.data.encoder_sample_rate,
+                                      args.data.encoder_hop_size, device=device)
+    if enhancer is None and cmd.enhance == "true":
+        from enhancer import Enhancer
+        enhancer = Enhancer(args.enhancer.type, args.enhancer.ckpt, device=device)
+    spk_id = torch.tensor([[int(cmd.spk_id)]], dtype=torch.int64, device=device)
+    result, sr_o = convert_device(model, args, audio, sr_i, None, units_encoder, f0_extractor, spk_id, batch_frames=batch_frames,
+                                  key=float(cmd.key), spk_mix_dict=literal_eval(cmd.spk_mix_dict),
+                                  threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
+                                  enhancer_adaptive_key=float(cmd.enhancer_adaptive_key),
+                                  enhancer_batch_samples=enhancer_batch_samples, units_batch_samples=units_batch_samples)
+    wavfile.write(cmd.output, int(sr_o), pcm16(result.cpu().numpy()))   # the file's one read-back
+    return result, sr_o
+
+
+if __name__ == "__main__":
+    run(parse_args())

@@ -418,6 +418,37 @@ int ddsp_phase_vocoder_batch(ddsp_ctx* ctx, void* stream, const float* a, const 
  * in place (threshold = 10^(dB/20), linear); volume (B,Fr). */
 int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, float threshold, int64_t B,
                      int64_t Fr, int hop);
+/* The same gate for a RAGGED batch of slices of one file, in one launch: signal (B, T_max) in place, volume (Fr) of the WHOLE
+ * file, start_frame / n_frames (B) int32 DEVICE arrays.  Row b, sample t < n_frames[b] * hop, is multiplied by the file's gate
+ * at sample start_frame[b] * hop + t - the value ddsp_volume_gate computes there (one device function serves both kernels), so
+ * the dilation sees the slice's neighbours and the last frame of a slice interpolates towards the file's next frame.  Samples
+ * from n_frames[b] * hop on are not touched.  T_max >= 1; hop a power of two.  A row with start_frame < 0, n_frames < 0,
+ * start_frame + n_frames > Fr or n_frames * hop > T_max is left as it is and sets the context's device error word
+ * (DDSP_ERR_ARG from ddsp_ctx_poll_error or the next call that takes it). */
+int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* start_frame,
+                          const int32_t* n_frames, float threshold, int64_t B, int64_t T_max, int64_t Fr, int hop);
+
+/* ---- the stitch of an offline conversion (main.py:165-173 with `cross_fade`, main.py:50-57) ----------------------------
+ * Places S rendered pieces into one fp64 output in ONE launch.  `pieces` is a DEVICE table of S rows; piece i holds `len`
+ * fp32 samples at the device address `x` (a row of a ragged group tensor, or a tensor of its own: nothing is packed first),
+ * starts at output sample `p` and cross-fades its first `fade` samples with what the earlier pieces left there.  Output sample
+ * t is a fold over the pieces in order from v = 0: for each i with p <= t < p + len and j = t - p,
+ *     j <  fade:  v = (1 - k) * v + k * x[j],  k = numpy's linspace(0, 1, fade)[j] in fp64: j * (1 / (fade - 1)), the last
+ *                 element exactly 1, and 0 for fade == 1 (a one-sample fade keeps the earlier sample);
+ *     j >= fade:  v = x[j] converted to fp64.
+ * Every step of the blend is one rounded fp64 operation (nothing is contracted), so the output equals the reference's host
+ * loop bit for bit; a sample no piece covers is 0.
+ * The caller guarantees (the Python mirror's `stitch_plan` checks it on the host): len >= 1, p nondecreasing, fade =
+ * max(0, end of piece i-1 - p) <= len - so the ends p + len are nondecreasing too, and a workgroup finds its first piece by
+ * binary search on them - and total >= every end.  A table that breaks this gives wrong samples, but no write leaves
+ * out[0, total) and no read leaves x[0, len) of a piece.  out (total) fp64, 16-byte aligned; 16-byte stores, and 16-byte loads
+ * wherever four output samples lie inside one piece at a 16-byte aligned address (a scalar select elsewhere: no address outside
+ * a piece is formed).  total == 0 launches nothing.  Does not synchronise, allocate or read back. */
+typedef struct ddsp_stitch_piece {
+    const float* x;
+    int64_t p, len, fade;
+} ddsp_stitch_piece;
+int ddsp_stitch(ddsp_ctx* ctx, void* stream, const ddsp_stitch_piece* pieces, int64_t S, double* out, int64_t total);
 
 /* ---- the device-side steps immediately before the synthesis path ------------- */
 /* replaces ddsp/vocoder.py:116-137 `Volume_Extractor.extract`: audio (B,T) -> volume (B, T/hop + 1), the RMS of
