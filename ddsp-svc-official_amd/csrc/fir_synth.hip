@@ -15,10 +15,11 @@ namespace {
 
 // One wavefront per frame row.  REAL modes: out[f] = exp(ctrl[f]) * scale.
 // ALLPASS: gd = pi*tanh(ctrl); phi = cumsum_f(gd) (fp64 running sum rounded to fp32 per bin, as ATen's
-// CPU cumsum does); out = [cos(phi) | sin(phi)].
+// CPU cumsum does); out = [cos(phi) | sin(phi)], the two blocks Mp = ddsp_pad32(M) columns apart and zero from M to Mp
+// (each block a whole number of the GEMM's k-tiles: the product sums them apart, EpiEvenOdd).
 // split != 0: the row is written as bf16 hi/lo groups of 8 (A operand of the split-bf16 inverse-DFT GEMM, gemm A_split);
 // M % 8 == 0 then, and every lane of a group of 8 takes part in the exchange (values past M are zeros).
-__global__ void __launch_bounds__(256) fir_act_kernel(int mode, const float* __restrict__ ctrl, int64_t ld, int M,
+__global__ void __launch_bounds__(256) fir_act_kernel(int mode, const float* __restrict__ ctrl, int64_t ld, int M, int Mp,
                                                       int ldo, int64_t rows, float* __restrict__ out, int split) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -42,7 +43,7 @@ __global__ void __launch_bounds__(256) fir_act_kernel(int mode, const float* __r
     float* dst = out + row * ldo;
     const float pi_f = 3.14159274101257324f;
     double carry = 0.0;
-    for (int f0 = 0; f0 < M; f0 += 64) {
+    for (int f0 = 0; f0 < Mp; f0 += 64) {
         const int f = f0 + lane;
         const float gd = (f < M) ? __fmul_rn(pi_f, tanhf(src[f])) : 0.f;
         double incl = (double)gd;
@@ -59,13 +60,13 @@ __global__ void __launch_bounds__(256) fir_act_kernel(int mode, const float* __r
         if (f < M) sincosf(phi, &s, &c);
         if (split) {
             const uint32_t wc = ddsp_split1_group8(c, lane), ws = ddsp_split1_group8(s, lane);
-            if (f < M) {
+            if (f < Mp) {
                 ((uint32_t*)dst)[f] = wc;
-                ((uint32_t*)dst)[M + f] = ws;
+                ((uint32_t*)dst)[Mp + f] = ws;
             }
-        } else if (f < M) {
+        } else if (f < Mp) {
             dst[f] = c;
-            dst[M + f] = s;
+            dst[Mp + f] = s;
         }
     }
 }
@@ -117,6 +118,20 @@ struct EpiMirrorStore {  // row[k] = row[n-k] = acc
     }
 };
 
+// All-pass: the response exp(j phi) is not real, so the filter is not even - but it splits into an even part E (cos block
+// against the cos table) and an odd part O (sin block against the sin table): tap k = E[k] + O[k], tap n-k = E[k] - O[k].
+// The GEMM sums the two blocks apart (gemm kDual) over taps 0..n/2: half the products of the full-length transform.
+struct EpiEvenOdd {
+    float* ir;
+    int n;
+    static constexpr bool kDual = true;
+    __device__ __forceinline__ float col(int) const { return 0.f; }
+    __device__ __forceinline__ void operator()(int, int m, int k, float e, float o) const {
+        float* row = ir + (int64_t)m * n;
+        row[k] = e + o;
+        if (k > 0 && k < n / 2) row[n - k] = e - o;
+    }
+};
 
 // The same activations with several consecutive bins per lane (round 3): the kernel above gives a lane ONE bin per pass, so every
 // value of a split row costs an 8-lane exchange and every store is 4 bytes - 41 us per step for its three launches, at 0.53 of
@@ -149,7 +164,7 @@ __global__ void __launch_bounds__(256) fir_act_exp8_kernel(float scale, const fl
 }
 
 // ALLPASS with 4 bins per lane: gd = pi tanh(ctrl), phi = the fp64 running sum rounded to fp32 per bin (ATen's CPU cumsum), out =
-// [cos phi | sin phi].  A lane sums its four increments in fp64, the wave scans the lane totals once (row shifts and broadcasts of
+// [cos phi | sin phi] (blocks Mp columns apart, zero from M to Mp, as above).  A lane sums its four increments in fp64, the wave scans the lane totals once (row shifts and broadcasts of
 // the two halves of the fp64 value), chunks of 256 bins carry on.  One wavefront per row.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double act_dpp_d(double v) {
@@ -158,8 +173,8 @@ __device__ __forceinline__ double act_dpp_d(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, ROW_MASK, 0xf, false);
     return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
 }
-__global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __restrict__ ctrl, int64_t ld, int M, int ldo, int64_t rows,
-                                                               float* __restrict__ out, int split) {
+__global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __restrict__ ctrl, int64_t ld, int M, int Mp, int ldo,
+                                                               int64_t rows, float* __restrict__ out, int split) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -167,9 +182,9 @@ __global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __re
     float* dst = out + row * ldo;
     const float pi_f = 3.14159274101257324f;
     double carry = 0.0;
-    for (int f0 = 0; f0 < M; f0 += 256) {
+    for (int f0 = 0; f0 < Mp; f0 += 256) {
         const int f = f0 + 4 * lane;                    // M % 8 == 0: a lane's four bins are all inside the row or all outside
-        const bool in = f < M;
+        const bool in = f < M, st = f < Mp;             // (bins from M to Mp are stored as zeros)
         f32x4 x = {0.f, 0.f, 0.f, 0.f};
         if (in) x = *(const f32x4*)(src + f);
         double run = 0.0, loc[4];
@@ -204,13 +219,13 @@ __global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __re
         if (split) {
             // lanes 2j, 2j + 1 own one group of 8 bins (every lane takes part in the exchange)
             const ddsp_u32x4 pc = ddsp_split4_pair(c, (lane & 1) != 0, 1), ps = ddsp_split4_pair(sn, (lane & 1) != 0, 1);
-            if (in) {
+            if (st) {
                 *(ddsp_u32x4*)(dst + f) = pc;
-                *(ddsp_u32x4*)(dst + M + f) = ps;
+                *(ddsp_u32x4*)(dst + Mp + f) = ps;
             }
-        } else if (in) {
+        } else if (st) {
             *(f32x4*)(dst + f) = c;
-            *(f32x4*)(dst + M + f) = sn;
+            *(f32x4*)(dst + Mp + f) = sn;
         }
     }
 }
@@ -320,7 +335,8 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const int M = n_mag, n = 2 * (n_mag - 1);
-    const int K = (mode == DDSP_FIR_ALLPASS) ? 2 * M : M;
+    const int Mp = ddsp_pad32(M);   // all-pass: pitch of the cos and sin blocks (activations and table alike)
+    const int K = (mode == DDSP_FIR_ALLPASS) ? 2 * Mp : M;
     const int lda = ddsp_pad4(K);
     int rc = ddsp_scratch_reserve_bytes(ctx, (size_t)rows * lda * sizeof(float) + 4096);
     if (rc) return rc;
@@ -330,27 +346,33 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
     if (rc) return rc;
     float* tab = nullptr;
     const int kind = mode == DDSP_FIR_ALLPASS ? TAB_IRDFT_CPLX : (mode == DDSP_FIR_STATIC ? TAB_IRDFT_RE_HANN : TAB_IRDFT_RE);
-    // K a multiple of 32 (every shipped n_mag): the table is read tap-major, [n][K], so that both GEMM operands are
-    // k-contiguous and the product runs on the LDS-DMA kernel; otherwise frequency-major on the register-staged one
+    // K a multiple of 32 (every shipped n_mag, and the all-pass by its padded blocks): the table is read tap-major, [taps][K],
+    // so that both GEMM operands are k-contiguous and the product runs on the LDS-DMA kernel; otherwise frequency-major on the
+    // register-staged one
     const bool tap_major = K % 32 == 0;
     rc = ddsp_get_table(ctx, st, kind, M, tap_major ? 1 : 0, &tab);
     if (rc) return rc;
+    // split-bf16 products at the sizes that had them before the all-pass blocks were padded (2 n_mag a multiple of 32); the
+    // other all-pass sizes - no shipped n_mag - keep fp32 products, on whichever kernel gemm::launch picks
+    const bool bf16_ok = tap_major && (mode != DDSP_FIR_ALLPASS || M % 16 == 0);
     float* tab_split = nullptr;   // the same table already split into bf16 hi/lo (B operand of the split-bf16 GEMM)
-    if (tap_major && ctx->math != DDSP_MATH_FP32 && (rc = ddsp_get_table(ctx, st, kind, M, 2, &tab_split))) return rc;
+    if (bf16_ok && ctx->math != DDSP_MATH_FP32 && (rc = ddsp_get_table(ctx, st, kind, M, 2, &tab_split))) return rc;
 
     // large row counts with split-bf16 products: the activations are written as bf16 hi/lo groups and the GEMM reads both
     // operands already split (the DMA kernel is certain at these sizes; B = B_split makes a fallback fail loudly)
-    const bool presplit = tap_major && tab_split && rows >= 8192 && M % 8 == 0 && ctx->math != 4;
+    // (all-pass: K = 2 Mp may be too short for gemm::launch's small-problem DMA rule where n_mag alone decided before)
+    const bool presplit = tap_major && tab_split && rows >= 8192 && M % 8 == 0 && ctx->math != 4 &&
+                          (mode != DDSP_FIR_ALLPASS || K >= 256);
     ddsp_prof_begin(ctx, st, PF_FIR_ACT);
     const bool wide = M % 8 == 0 && ctrl_ld % 4 == 0 && lda % 8 == 0 && ((uintptr_t)ctrl % 16) == 0;
     if (wide && mode != DDSP_FIR_ALLPASS)
         hipLaunchKernelGGL(fir_act_exp8_kernel, dim3((unsigned)ceil_div64(rows * (M / 8), 256)), dim3(256), 0, st,
                            mode == DDSP_FIR_STATIC ? 1.0f / 128.0f : 1.0f, ctrl, ctrl_ld, M, lda, rows, act, presplit ? 1 : 0);
     else if (wide)
-        hipLaunchKernelGGL(fir_act_allpass4_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, ctrl, ctrl_ld, M, lda, rows,
-                           act, presplit ? 1 : 0);
+        hipLaunchKernelGGL(fir_act_allpass4_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, ctrl, ctrl_ld, M, Mp, lda,
+                           rows, act, presplit ? 1 : 0);
     else
-        hipLaunchKernelGGL(fir_act_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, mode, ctrl, ctrl_ld, M,
+        hipLaunchKernelGGL(fir_act_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, mode, ctrl, ctrl_ld, M, Mp,
                            lda, rows, act, presplit ? 1 : 0);
     ddsp_prof_end(ctx, st, 0.0, 4.0 * rows * (M + K));
     DDSP_LAUNCH_CHECK(ctx);
@@ -358,7 +380,7 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
 
     auto run = [&](gemm::Args g, const auto& epi) {
         // (split-bf16 products like the control network's inference GEMMs: the taps then carry ~4e-6 relative error)
-        g.math = tap_major ? (ctx->math == 4 ? DDSP_MATH_SPLIT_BF16 : ctx->math) : 0;   // ddsp_ctx_set_math
+        g.math = bf16_ok ? (ctx->math == 4 ? DDSP_MATH_SPLIT_BF16 : ctx->math) : 0;   // ddsp_ctx_set_math
         g.B_split = tab_split;
         if (presplit) {
             g.A_split = 1;
@@ -371,8 +393,9 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
     };
     const int64_t ldb = tap_major ? K : ddsp_pad4(n);
     if (mode == DDSP_FIR_ALLPASS) {
-        gemm::Args g = gemm::make(act, lda, tab, ldb, (int)rows, n, K);
-        run(g, gemm::EpiStore{ir, n, nullptr, 1, 0, 0});
+        // taps 0..n/2 as even and odd parts (k < Mp: cos block, k >= Mp: sin block), both stored by the epilogue
+        gemm::Args g = gemm::make(act, lda, tab, ldb, (int)rows, n / 2 + 1, K);
+        run(g, EpiEvenOdd{ir, n});
     } else {
         // even filter: taps 0..n/2 from the GEMM, the rest mirrored by the epilogue
         gemm::Args g = gemm::make(act, lda, tab, ldb, (int)rows, n / 2 + 1, K);
@@ -381,7 +404,9 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
         else
             run(g, EpiMirrorStore{ir, n});
     }
-    ddsp_prof_end(ctx, st, 2.0 * rows * (double)n * K, 4.0 * rows * (K + n));
+    // (all-pass: the products issued, two blocks of M frequencies over taps 0..n/2)
+    ddsp_prof_end(ctx, st, mode == DDSP_FIR_ALLPASS ? 2.0 * rows * (double)(n / 2 + 1) * 2 * M : 2.0 * rows * (double)n * K,
+                  4.0 * rows * (K + n));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

@@ -114,6 +114,15 @@ struct epi_is_rowpair : std::false_type {};
 template <class E>
 struct epi_is_rowpair<E, std::void_t<decltype(E::kRowPair)>> : std::true_type {};
 
+// An epilogue that declares `kDual` takes the two halves of the k range apart: K is a multiple of 64, the products of
+// k < K/2 and of k >= K/2 are summed into separate accumulators and the epilogue is called as epi(z, m, n, first, second).
+// (The all-pass filter synthesis: even part from the cos block, odd part from the sin block, taps k and n - k from their
+// sum and difference - half the products of the full-length transform.)
+template <class E, class = void>
+struct epi_is_dual : std::false_type {};
+template <class E>
+struct epi_is_dual<E, std::void_t<decltype(E::kDual)>> : std::true_type {};
+
 // 4x4 transpose across the four lanes of a quad: in x[i] = (row i, column q) for lane q; out x[k] = (row q, column k)
 __device__ __forceinline__ void quad_transpose(float (&x)[4], int q) {
     const bool odd = q & 1, hi = q & 2;
@@ -303,6 +312,8 @@ __global__ void __launch_bounds__(64 * NW) kernel(Args g, Epi epi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    constexpr bool DUAL = epi_is_dual<Epi>::value;
+    f32x16 acc1[DUAL ? TM : 1][DUAL ? TN : 1];   // kDual: the sums of the first half of the k range
     const int nk = (g.K + BK - 1) / BK;
     load_tiles(0);
     store_tiles(0);
@@ -342,6 +353,18 @@ __global__ void __launch_bounds__(64 * NW) kernel(Args g, Epi epi) {
                 for (int j = 0; j < TN; ++j) b[j] = bn[j];
             }
         }
+        if constexpr (DUAL) {
+            if (2 * (kt + 1) == nk) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        acc1[i][j] = acc[i][j];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                    }
+            }
+        }
         if (kt + 1 < nk) store_tiles(buf ^ 1);
         __syncthreads();
     }
@@ -358,7 +381,9 @@ __global__ void __launch_bounds__(64 * NW) kernel(Args g, Epi epi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if constexpr (epi_is_rowpair<Epi>::value) {
+                if constexpr (DUAL) {
+                    if (n_ok && m < g.M) epi(z, m, n, acc1[i][j][r], acc[i][j][r]);
+                } else if constexpr (epi_is_rowpair<Epi>::value) {
                     if ((r & 1) == 0 && n_ok && m < g.M) epi.pair(z, m, n, acc[i][j][r], acc[i][j][r + 1], cb);
                 } else if constexpr (epi_wants_pair<Epi>::value) {
                     // columns (2f, 2f+1) sit on adjacent lanes: hand each lane its neighbour's value too
@@ -536,6 +561,9 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    constexpr bool DUAL = epi_is_dual<Epi>::value;
+    f32x16 acc1[DUAL ? TM : 1][DUAL ? TN : 1];   // kDual: the sums of the first half of the k range
+
     int kt = 0, tile_i = 0;
     for (int step = 0; step < steps; ++step) {
         // step has landed once at most the next step's pieces of THIS wave are still in flight ...
@@ -636,6 +664,18 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][s >> 2][s & 3], bv[j][s >> 2][s & 3],
                                                                          acc[i][j], 0, 0, 0);
         }
+        if constexpr (DUAL) {
+            if (2 * (kt + 1) == nk) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        acc1[i][j] = acc[i][j];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                    }
+            }
+        }
         if (++kt == nk) {
             // ---- epilogue of this tile (stores drain while the next tile's MFMAs run) ----
             const int tile = tile_of(tile_i);
@@ -708,7 +748,9 @@ __global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : BM * BN <= 128 * 128 ?
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if constexpr (epi_is_rowpair<Epi>::value) {
+                        if constexpr (DUAL) {
+                            if (n_ok && m < g.M) epi(z, m, n, acc1[i][j][r], acc[i][j][r]);
+                        } else if constexpr (epi_is_rowpair<Epi>::value) {
                             if ((r & 1) == 0 && n_ok && m < g.M) epi.pair(z, m, n, acc[i][j][r], acc[i][j][r + 1], cb);
                         } else if constexpr (epi_wants_pair<Epi>::value) {
                             const float other = __shfl_xor(acc[i][j][r], 1, 64);

@@ -12,3 +12,4 @@ enum {
 
 // leading dimensions are padded to a multiple of 4 floats so that every row start is 16-byte aligned
 static inline int ddsp_pad4(int n) { return (n + 3) & ~3; }
+static inline int ddsp_pad32(int n) { return (n + 31) & ~31; }

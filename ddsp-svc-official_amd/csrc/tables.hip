@@ -12,25 +12,29 @@ constexpr double kTwoPi = 6.283185307179586476925286766559;
 // kind TAB_IRDFT_RE      : rows [0, M)            (real responses, no window)
 // kind TAB_IRDFT_RE_HANN : rows [0, M) times hann_periodic(n)[k]   (ddsp/core.py:262,272,276,287 folded)
 // kind TAB_IRDFT_CPLX    : rows [0, 2M)
-// n1 = 1 (key of the cache): the same table TAP-MAJOR, [n][rows], for the LDS-DMA GEMM of the forward filter synthesis
+// n1 = 1 (key of the cache): the same table TAP-MAJOR, [taps][rows], for the LDS-DMA GEMM of the forward filter synthesis
 // (both operands k-contiguous); the frequency-major layout stays for the backward pass.
-__global__ void irdft_table_kernel(float* __restrict__ tab, int M, int n, int ld, int rows, int hann, int tap_major) {
-    const int64_t total = tap_major ? (int64_t)n * rows : (int64_t)rows * ld;
+// Tap-major TAB_IRDFT_CPLX holds taps 0..n/2 only and keeps its two blocks `half` = ddsp_pad32(M) columns apart (zeros
+// between): T[M+f][n-k] = -T[M+f][k] and T[f][n-k] = T[f][k], so the forward product forms the even part (cos block) and
+// the odd part (sin block) of the taps separately and its epilogue stores their sum and difference (fir_synth.hip).
+__global__ void irdft_table_kernel(float* __restrict__ tab, int M, int n, int ld, int rows, int half, int taps, int hann,
+                                   int tap_major) {
+    const int64_t total = tap_major ? (int64_t)taps * rows : (int64_t)rows * ld;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (int64_t)gridDim.x * blockDim.x) {
         const int row = tap_major ? (int)(idx % rows) : (int)(idx / ld);
         const int k = tap_major ? (int)(idx / rows) : (int)(idx % ld);
-        if (k >= n) {
+        const int f = row < half ? row : row - half;
+        if (k >= n || f >= M) {
             tab[idx] = 0.f;
             continue;
         }
-        const int f = row < M ? row : row - M;
         const double cf = (f == 0 || f == M - 1) ? 1.0 : 2.0;
         int64_t r = ((int64_t)f * (k - n / 2)) % n;
         if (r < 0) r += n;
         const double ang = kTwoPi * (double)r / (double)n;
         double v;
-        if (row < M)
+        if (row < half)
             v = cf / n * cos(ang);
         else
             v = (f == 0 || f == M - 1) ? 0.0 : -cf / n * sin(ang);
@@ -144,7 +148,7 @@ int ddsp_get_table(ddsp_ctx* ctx, hipStream_t st, int kind, int n0, int n1, floa
             elems = n1 ? (size_t)n0 * 2 * (n0 - 1) : (size_t)n0 * ddsp_pad4(2 * (n0 - 1));
             break;
         case TAB_IRDFT_CPLX:
-            elems = n1 ? (size_t)2 * n0 * 2 * (n0 - 1) : (size_t)2 * n0 * ddsp_pad4(2 * (n0 - 1));
+            elems = n1 ? (size_t)n0 * 2 * ddsp_pad32(n0) : (size_t)2 * n0 * ddsp_pad4(2 * (n0 - 1));
             break;
         case TAB_RDFT_FWD_W:
             elems = (size_t)n0 * ddsp_pad4(2 * (n0 / 2 + 1));
@@ -161,9 +165,10 @@ int ddsp_get_table(ddsp_ctx* ctx, hipStream_t st, int kind, int n0, int n1, floa
     const unsigned blocks = (unsigned)((elems + 255) / 256 > 2048 ? 2048 : (elems + 255) / 256);
     if (kind == TAB_IRDFT_RE || kind == TAB_IRDFT_RE_HANN || kind == TAB_IRDFT_CPLX) {
         const int M = n0, n = 2 * (n0 - 1);
-        const int rows = kind == TAB_IRDFT_CPLX ? 2 * M : M;
-        hipLaunchKernelGGL(irdft_table_kernel, dim3(blocks), dim3(256), 0, st, dev, M, n, ddsp_pad4(n), rows,
-                           kind == TAB_IRDFT_RE_HANN ? 1 : 0, n1 ? 1 : 0);
+        const bool cplx = kind == TAB_IRDFT_CPLX;
+        const int half = cplx && n1 ? ddsp_pad32(M) : M;
+        hipLaunchKernelGGL(irdft_table_kernel, dim3(blocks), dim3(256), 0, st, dev, M, n, ddsp_pad4(n), cplx ? 2 * half : M, half,
+                           cplx ? n / 2 + 1 : n, kind == TAB_IRDFT_RE_HANN ? 1 : 0, n1 ? 1 : 0);
     } else {
         hipLaunchKernelGGL(rdft_w_table_kernel, dim3(blocks), dim3(256), 0, st, dev, n0,
                            ddsp_pad4(2 * (n0 / 2 + 1)), kind == TAB_RDFT_INV_W ? 1 : 0);
