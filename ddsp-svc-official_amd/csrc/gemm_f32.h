@@ -37,7 +37,7 @@
 
 namespace gemm {
 
-enum { A_PLAIN = 0, A_CONV3 = 1, A_FRAMES = 2, A_CONVK = 3 };
+enum { A_PLAIN = 0, A_CONV3 = 1, A_FRAMES = 2, A_CONVK = 3, A_DWCONV = 4 };   // (A_DWCONV: gemm_ln.h only)
 
 struct Args {
     const float* A;

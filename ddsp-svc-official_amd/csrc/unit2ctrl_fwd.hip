@@ -429,6 +429,9 @@ constexpr int KS_SPLITS = 4;
 constexpr int KS_MAX_ROWS = 256;   // up to 4 row tiles x 4 column tiles x 4 splits = 64 workgroups (344 rows measured slower than whole-K launches)
 // rows from which the inference forward writes its activations pre-split (with the fused-GLU 128x128 tiling)
 constexpr int64_t U2C_PRESPLIT_MIN_ROWS = 8192;
+// rows from which pw2 forms the depthwise convolution in its own operand stage (gemm_ln.h A_DWCONV).  Measured against the two
+// launches at 11008 rows only; between 8192 rows and this the pair stays, as tests/test_gpu_models.py pins it there
+constexpr int64_t U2C_DWCONV_FUSE_MIN_ROWS = 10240;
 // (utterance, head) pairs from which the non-causal inference attention runs on the fused split-bf16 kernel
 constexpr int64_t ATTN_BF16_MIN = 256;
 __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -1148,6 +1151,34 @@ int u2c_forward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w, const 
             PROF(PF_U2C_ROWWISE, 0, 12.0 * M * INNER,
                  hipLaunchKernelGGL(glu_kernel, dim3(grid_for(M * (INNER / 4))), dim3(256), 0, st, b.g1, M, b.glu));
         }
+        // Large batches on split operands: the convolution + SiLU is formed in pw2's own operand stage (gemm_ln.h A_DWCONV): no
+        // launch, no (M, 512) round trip.  Same bits.  Training, fp32 products, the register-pair switch, batches below
+        // U2C_DWCONV_FUSE_MIN_ROWS and batches of short utterances keep the two launches.
+        gemm::LnArgs dwl{};
+        bool dw_fused = false;
+        {
+            gemm::Args g = gemm::make(b.glu, INNER, L.cm_pw2_w, INNER, iM, D, INNER);
+            set_b(g, bf.wpw2 + (size_t)l * D * INNER, asplit);
+            const float* n_g = l + 1 < 3 ? w.layer[l + 1].norm_w : w.final_ln_w;
+            const float* n_b = l + 1 < 3 ? w.layer[l + 1].norm_b : w.final_ln_b;
+            dwl = ln_args(g, b.x_mid, b.x_out, L.cm_pw2_b, n_g, n_b, l + 1 < 3 ? bf.l[l + 1].y : bf.y_final);
+            dwl.Fr = (int)Fr;
+            dwl.zeros = zero_page;
+            dwl.dw_taps = bf.wdw + (size_t)l * DWK * INNER;
+            dwl.dw_bias = L.cm_dw_b;
+            dwl.n_frames = in.n_frames;
+            dwl.dw_left = w.causal ? DWK - 1 : DWK / 2;
+            dw_fused = asplit && dw_tiled && M >= U2C_DWCONV_FUSE_MIN_ROWS && B * ((Fr + 15) / 16) >= 512 && ln_fusable(g, dwl) && gemm::res_ln_dwconv_ok(dwl) &&
+                       gemm::res_ln_dwconv_fills(B, Fr);
+        }
+        if (dw_fused) {
+            PROF(PF_U2C_GEMM_LINEAR, 2.0 * M * D * INNER + 2.0 * M * INNER * DWK, 4.0 * M * (INNER + 4 * D),
+                 DDSP_HIP(ctx, gemm::launch_res_ln_dwconv(st, dwl)));
+            ln_done = true;
+            ln_src = b.x_out;
+            DDSP_LAUNCH_CHECK(ctx);
+            continue;
+        }
         PROF(PF_U2C_ROWWISE, 2.0 * M * INNER * DWK, 8.0 * M * INNER,
              if (!b.pre && dw_tiled && B * ((Fr + 15) / 16) >= 512)
                  // inference, large batches: LDS-staged tiles of 64 frames x 64 channels
@@ -1289,6 +1320,39 @@ static int unit2ctrl_fwd_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights
     plan_forward(a, bf, w, B, Fr, false, cached);
     if (a.rc) return a.rc;
     return u2c_forward(ctx, st, w, in, bf, ctrl);
+}
+
+extern "C" int ddsp_u2c_dwconv_pw2(ddsp_ctx* ctx, void* stream, const float* glu, const float* taps, const float* dw_bias,
+                                   const float* W_split, const float* bias, const float* res, const float* gamma,
+                                   const float* beta, const int* n_frames, int B, int Fr, int causal, int fused, float* scratch,
+                                   float* X, float* Y) {
+    DDSP_REQUIRE(ctx, ctx && glu && taps && dw_bias && W_split && bias && res && gamma && beta && X && Y && (fused || scratch),
+                 "ddsp_u2c_dwconv_pw2: null argument");
+    DDSP_REQUIRE(ctx, B >= 1 && Fr >= 1 && (int64_t)B * Fr < (1 << 26), "ddsp_u2c_dwconv_pw2: bad shape");
+    const float* zero_page = nullptr;
+    if (int rc = ddsp_zero_page(ctx, &zero_page)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = B * Fr, left = causal ? DWK - 1 : DWK / 2;
+    gemm::LnArgs a{fused ? glu : scratch, W_split, INNER, INNER, M, INNER, bias, res, X, gamma, beta, Y, 1};
+    a.Fr = Fr;
+    a.zeros = zero_page;
+    a.dw_taps = taps;
+    a.dw_bias = dw_bias;
+    a.n_frames = n_frames;
+    a.dw_left = left;
+    DDSP_REQUIRE(ctx, gemm::res_ln_dwconv_ok(a) && ((uintptr_t)glu % 16) == 0, "ddsp_u2c_dwconv_pw2: 16-byte aligned operands");
+    DDSP_ENTER_DEVICE(ctx);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    if (fused) {
+        DDSP_HIP(ctx, gemm::launch_res_ln_dwconv(st, a));
+    } else {
+        hipLaunchKernelGGL(dwconv_tile_kernel, dim3(INNER / DWT_C, (unsigned)(B * ((Fr + DWT_F - 1) / DWT_F))), dim3(256), 0, st, glu,
+                           taps, dw_bias, B, Fr, scratch, left, 1, n_frames);
+        DDSP_HIP(ctx, gemm::launch_res_ln(st, a, true));
+    }
+    ddsp_prof_end(ctx, st, 2.0 * M * (double)D * INNER + 2.0 * M * (double)INNER * DWK, 4.0 * M * (INNER + 4.0 * D));
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
 }
 
 extern "C" int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,

@@ -190,6 +190,7 @@ SIGNATURES = {
     "ddsp_volume_extract_frac": (_int, [_vp, _vp, _vp, _i64, _i64, _f64, _vp]),
     "ddsp_align_units": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
     "ddsp_gemm_res_ln": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _int]),
+    "ddsp_u2c_dwconv_pw2": (_int, [_vp] * 11 + [_int, _int, _int, _int, _vp, _vp, _vp]),
     "ddsp_conv1d_pair_supported": (_int, [_vp, _int, _int, _int]),
     "ddsp_conv1d_pair": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _f32, _vp, _vp]),
     "ddsp_retime_f0": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _f32, _f64, _i64, _vp]),
@@ -987,6 +988,20 @@ class Context:
         Y = torch.empty(M, 256, device=A_split.device, dtype=torch.float32)
         self.call("ddsp_gemm_res_ln", _ptr(A_split), _ptr(W_split), _ptr(bias), _ptr(res), _ptr(gamma), _ptr(beta), int(M), int(K),
                   _ptr(X), _ptr(Y), (1 if y_split else 0) | (2 if a_fp32 else 0))
+        return X, Y
+
+    def u2c_dwconv_pw2(self, glu, taps, dw_bias, W_split, bias, res, gamma, beta, B, n_frames=None, causal=False, fused=True):
+        """The conformer's depthwise conv k31 -> SiLU -> pw2 -> residual -> LayerNorm on split-bf16 operands: glu (B*Fr, 512) fp32,
+        taps (31, 512), W_split (256, 512) pre-split; n_frames: int32 device tensor of B frame counts or None.  fused: one launch
+        (the convolution in the GEMM's operand stage), else the depthwise kernel and then the GEMM.  Returns X, Y (split)."""
+        M = glu.shape[0]
+        if M % int(B):
+            raise ValueError("u2c_dwconv_pw2: glu must hold B utterances of equal padded length")
+        X = torch.empty(M, 256, device=glu.device, dtype=torch.float32)
+        Y = torch.empty(M, 256, device=glu.device, dtype=torch.float32)
+        scratch = None if fused else torch.empty(M, 512, device=glu.device, dtype=torch.float32)
+        self.call("ddsp_u2c_dwconv_pw2", _ptr(glu), _ptr(taps), _ptr(dw_bias), _ptr(W_split), _ptr(bias), _ptr(res), _ptr(gamma),
+                  _ptr(beta), _ptr(n_frames), int(B), M // int(B), 1 if causal else 0, 1 if fused else 0, _ptr(scratch), _ptr(X), _ptr(Y))
         return X, Y
 
     def conv1d_pair_supported(self, C, ktaps, dil):

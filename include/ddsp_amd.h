@@ -674,6 +674,17 @@ int ddsp_gemm_f32(ddsp_ctx* ctx, void* stream, const float* A, int64_t lda, int 
 int ddsp_gemm_res_ln(ddsp_ctx* ctx, void* stream, const float* A_split, const float* W_split, const float* bias,
                      const float* res, const float* gamma, const float* beta, int M, int K, float* X, float* Y, int y_split);
 
+/* The conformer's conv-module tail (pcmer.py:42-63: depthwise conv k31 -> SiLU -> pw2, then the residual and the next LayerNorm)
+ * on split-bf16 operands, as ddsp_unit2ctrl_fwd runs it at large batches: glu (B*Fr, 512) fp32 = the pw1 + GLU output, taps
+ * [31][512] and dw_bias [512] of the depthwise convolution, W_split (256, 512) pre-split, n_frames null or B frame counts
+ * (input frames at or behind a row's count read as zero), causal 0 / 1.  fused = 0: the depthwise kernel writes its split
+ * output to scratch (B*Fr, 512) and ddsp_gemm_res_ln's kernel reads it; fused = 1: one launch that convolves in the GEMM's
+ * operand stage (scratch unused, may be null).  X and Y (split) as in ddsp_gemm_res_ln; the same bits either way.
+ * Exposed for tests. */
+int ddsp_u2c_dwconv_pw2(ddsp_ctx* ctx, void* stream, const float* glu, const float* taps, const float* dw_bias,
+                        const float* W_split, const float* bias, const float* res, const float* gamma, const float* beta,
+                        const int* n_frames, int B, int Fr, int causal, int fused, float* scratch, float* X, float* Y);
+
 /* ---- building block: the linear attention of one PCmer layer without its Linear layers ------------------------------ */
 /* replaces ddsp/pcmer.py:69-77,123-159 (`softmax_kernel` feature maps + `linear_attention`, non-causal): q, k, v
  * (B*Fr, 512) = 8 heads x 64, proj (266, 64) the layer's `projection_matrix`; out (B*Fr, 512) = the merged heads before
