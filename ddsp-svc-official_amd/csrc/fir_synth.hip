@@ -136,10 +136,11 @@ struct EpiEvenOdd {
 // The same activations with several consecutive bins per lane (round 3): the kernel above gives a lane ONE bin per pass, so every
 // value of a split row costs an 8-lane exchange and every store is 4 bytes - 41 us per step for its three launches, at 0.53 of
 // the vector-issue rate.  REAL modes: 8 bins per lane (two 16-byte loads, the split group formed in the lane, two 16-byte stores).
-__global__ void __launch_bounds__(256) fir_act_exp8_kernel(float scale, const float* __restrict__ ctrl, int64_t ld, int M, int ldo,
-                                                           int64_t rows, float* __restrict__ out, int split) {
+// (`block`: the workgroup's index among those of this filter - the grouped launch below gives each filter a range of its blocks)
+__device__ __forceinline__ void fir_act_exp8_body(unsigned block, float scale, const float* __restrict__ ctrl, int64_t ld, int M, int ldo,
+                                                  int64_t rows, float* __restrict__ out, int split) {
     const int per_row = M / 8;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = (int64_t)block * 256 + threadIdx.x;
     if (i >= rows * per_row) return;
     const int64_t row = i / per_row;
     const int gq = (int)(i % per_row);
@@ -162,6 +163,10 @@ __global__ void __launch_bounds__(256) fir_act_exp8_kernel(float scale, const fl
         *(f32x4*)(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
     }
 }
+__global__ void __launch_bounds__(256) fir_act_exp8_kernel(float scale, const float* __restrict__ ctrl, int64_t ld, int M, int ldo,
+                                                           int64_t rows, float* __restrict__ out, int split) {
+    fir_act_exp8_body(blockIdx.x, scale, ctrl, ld, M, ldo, rows, out, split);
+}
 
 // ALLPASS with 4 bins per lane: gd = pi tanh(ctrl), phi = the fp64 running sum rounded to fp32 per bin (ATen's CPU cumsum), out =
 // [cos phi | sin phi] (blocks Mp columns apart, zero from M to Mp, as above).  A lane sums its four increments in fp64, the wave scans the lane totals once (row shifts and broadcasts of
@@ -173,10 +178,10 @@ __device__ __forceinline__ double act_dpp_d(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, ROW_MASK, 0xf, false);
     return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
 }
-__global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __restrict__ ctrl, int64_t ld, int M, int Mp, int ldo,
-                                                               int64_t rows, float* __restrict__ out, int split) {
+__device__ __forceinline__ void fir_act_allpass4_body(unsigned block, const float* __restrict__ ctrl, int64_t ld, int M, int Mp, int ldo,
+                                                      int64_t rows, float* __restrict__ out, int split) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t row = (int64_t)block * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* src = ctrl + row * ld;
     float* dst = out + row * ldo;
@@ -229,6 +234,46 @@ __global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __re
         }
     }
 }
+__global__ void __launch_bounds__(256) fir_act_allpass4_kernel(const float* __restrict__ ctrl, int64_t ld, int M, int Mp, int ldo,
+                                                               int64_t rows, float* __restrict__ out, int split) {
+    fir_act_allpass4_body(blockIdx.x, ctrl, ld, M, Mp, ldo, rows, out, split);
+}
+
+// The activations of up to three filters of one control matrix in ONE launch: blocks [first[i], first[i + 1]) run filter i's body
+// (split rows: the A operands of the grouped inverse-DFT launch, side by side in scratch).
+struct FirActGroup {
+    int n;
+    unsigned first[gemm::GROUP_MAX + 1];
+    int mode[gemm::GROUP_MAX], M[gemm::GROUP_MAX], lda[gemm::GROUP_MAX];
+    const float* ctrl[gemm::GROUP_MAX];   // column 0 of the filter's control values
+    float* act[gemm::GROUP_MAX];
+};
+__global__ void __launch_bounds__(256) fir_act_group_kernel(FirActGroup a, int64_t ld, int64_t rows) {
+    int i = 0;
+    while (i + 1 < a.n && blockIdx.x >= a.first[i + 1]) ++i;
+    const unsigned block = blockIdx.x - a.first[i];
+    if (a.mode[i] == DDSP_FIR_ALLPASS)
+        fir_act_allpass4_body(block, a.ctrl[i], ld, a.M[i], (a.M[i] + 31) & ~31, a.lda[i], rows, a.act[i], 1);   // ddsp_pad32
+    else
+        fir_act_exp8_body(block, a.mode[i] == DDSP_FIR_STATIC ? 1.0f / 128.0f : 1.0f, a.ctrl[i], ld, a.M[i], a.lda[i], rows, a.act[i], 1);
+}
+
+// the epilogues of a grouped launch (gemm::kernel_dma_group), one per problem in the table's order
+struct EpiFirGroup {
+    int mode[gemm::GROUP_MAX], n[gemm::GROUP_MAX];
+    float* ir[gemm::GROUP_MAX];
+    const float* f0[gemm::GROUP_MAX];
+    float sr15;
+    __device__ __forceinline__ bool dual(int p) const { return mode[p] == DDSP_FIR_ALLPASS; }
+    template <class F>
+    __device__ __forceinline__ void for_problem(int p, F&& f) const {
+        switch (mode[p]) {
+            case DDSP_FIR_ALLPASS: f(EpiEvenOdd{ir[p], n[p]}); break;
+            case DDSP_FIR_DYNAMIC: f(EpiDynWindow{ir[p], n[p], f0[p], sr15, 1}); break;
+            default: f(EpiMirrorStore{ir[p], n[p]}); break;
+        }
+    }
+};
 
 // ---- backward -----------------------------------------------------------------------------------------------
 // rows of n floats (n even: 8-byte aligned) -> rows of ld >= n floats, zero beyond n
@@ -407,6 +452,98 @@ extern "C" int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const f
     // (all-pass: the products issued, two blocks of M frequencies over taps 0..n/2)
     ddsp_prof_end(ctx, st, mode == DDSP_FIR_ALLPASS ? 2.0 * rows * (double)(n / 2 + 1) * 2 * M : 2.0 * rows * (double)n * K,
                   4.0 * rows * (K + n));
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
+
+// Up to three filters of one control matrix.  Where every one of them meets the conditions of the `presplit` case above (split-bf16
+// products, rows >= 8192, tap-major table, whole groups of 8 bins, the wide activation kernels), two launches: the activations
+// of all filters, then one grouped inverse-DFT launch (gemm::kernel_dma_group) with the epilogue of each - the bits of the single
+// calls.  Otherwise the single calls, in order.
+extern "C" int ddsp_fir_from_ctrl_group(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_t ctrl_ld, int64_t rows, int sr,
+                                        const ddsp_fir_problem* problems, int n_problems) {
+    DDSP_REQUIRE(ctx, ctx && ctrl && problems, "ddsp_fir_from_ctrl_group: null argument");
+    DDSP_REQUIRE(ctx, n_problems >= 1 && n_problems <= gemm::GROUP_MAX, "ddsp_fir_from_ctrl_group: one to three problems");
+    DDSP_REQUIRE(ctx, rows >= 0 && rows < (1 << 30), "ddsp_fir_from_ctrl_group: bad shape");
+    bool grouped = ctx->math == DDSP_MATH_SPLIT_BF16 && rows >= 8192 && ctrl_ld % 4 == 0;
+    int K[gemm::GROUP_MAX], Ms[gemm::GROUP_MAX], Ns[gemm::GROUP_MAX];
+    for (int i = 0; i < n_problems; ++i) {
+        const ddsp_fir_problem& p = problems[i];
+        DDSP_REQUIRE(ctx, p.ir, "ddsp_fir_from_ctrl_group: null argument");
+        DDSP_REQUIRE(ctx, p.mode >= 0 && p.mode <= 2, "ddsp_fir_from_ctrl_group: unknown mode");
+        DDSP_REQUIRE(ctx, p.n_mag >= 3 && p.n_mag <= 1024 && p.col >= 0 && (int64_t)p.col + p.n_mag <= ctrl_ld,
+                     "ddsp_fir_from_ctrl_group: bad shape");
+        DDSP_REQUIRE(ctx, p.mode != DDSP_FIR_DYNAMIC || p.f0_frames, "ddsp_fir_from_ctrl_group: DYNAMIC needs f0_frames");
+        const int M = p.n_mag;
+        K[i] = p.mode == DDSP_FIR_ALLPASS ? 2 * ddsp_pad32(M) : M;
+        Ms[i] = (int)rows;
+        Ns[i] = M;   // taps 0..n/2
+        grouped = grouped && M % 8 == 0 && K[i] % 32 == 0 && (p.mode != DDSP_FIR_ALLPASS || (M % 16 == 0 && K[i] >= 256)) &&
+                  ((uintptr_t)(ctrl + p.col) % 16) == 0;
+    }
+    if (rows == 0) return DDSP_OK;
+    if (!grouped) {
+        for (int i = 0; i < n_problems; ++i) {
+            const ddsp_fir_problem& p = problems[i];
+            const int rc = ddsp_fir_from_ctrl(ctx, stream, p.mode, ctrl + p.col, ctrl_ld, p.n_mag, p.f0_frames, rows, sr, p.ir);
+            if (rc) return rc;
+        }
+        return DDSP_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    DDSP_ENTER_DEVICE(ctx);
+    size_t act_bytes = 4096;
+    for (int i = 0; i < n_problems; ++i) act_bytes += (size_t)rows * K[i] * sizeof(float);
+    int rc = ddsp_scratch_reserve_bytes(ctx, act_bytes);
+    if (rc) return rc;
+    ddsp_scratch_reset(ctx);
+    FirActGroup a = {};
+    float* tab_split[gemm::GROUP_MAX];
+    a.n = n_problems;
+    a.first[0] = 0;
+    double act_traffic = 0.0, flops = 0.0, traffic = 0.0;
+    for (int i = 0; i < n_problems; ++i) {
+        const ddsp_fir_problem& p = problems[i];
+        const int M = p.n_mag, n = 2 * (M - 1);
+        if ((rc = ddsp_scratch_get(ctx, (size_t)rows * K[i] * sizeof(float), (void**)&a.act[i]))) return rc;
+        const int kind = p.mode == DDSP_FIR_ALLPASS ? TAB_IRDFT_CPLX : (p.mode == DDSP_FIR_STATIC ? TAB_IRDFT_RE_HANN : TAB_IRDFT_RE);
+        if ((rc = ddsp_get_table(ctx, st, kind, M, 2, &tab_split[i]))) return rc;
+        a.mode[i] = p.mode;
+        a.M[i] = M;
+        a.lda[i] = K[i];
+        a.ctrl[i] = ctrl + p.col;
+        a.first[i + 1] = a.first[i] + (unsigned)(p.mode == DDSP_FIR_ALLPASS ? ceil_div64(rows, 4) : ceil_div64(rows * (M / 8), 256));
+        // (the figures of the single calls, summed)
+        act_traffic += 4.0 * rows * (M + K[i]);
+        flops += p.mode == DDSP_FIR_ALLPASS ? 2.0 * rows * (double)(n / 2 + 1) * 2 * M : 2.0 * rows * (double)n * K[i];
+        traffic += 4.0 * rows * (K[i] + n);
+    }
+    ddsp_prof_begin(ctx, st, PF_FIR_ACT);
+    hipLaunchKernelGGL(fir_act_group_kernel, dim3(a.first[n_problems]), dim3(256), 0, st, a, ctrl_ld, rows);
+    ddsp_prof_end(ctx, st, 0.0, act_traffic);
+    DDSP_LAUNCH_CHECK(ctx);
+
+    gemm::GroupArgs ga;
+    EpiFirGroup epi;
+    // 64 x 64 tiles on 4 waves for all problems, the source filter's included: alone it loses 1.5 us to its 128 x 64 launch
+    // (34.9 against 33.4 us at 11008 rows), and the grouped launch on 128 x 64 tiles measured the same as on these (52.4 / 53.1 us)
+    ga.t = gemm::group_build(n_problems, Ms, Ns, K, 64, 64);
+    epi.sr15 = 1.5f * (float)sr;
+    for (int i = 0; i < gemm::GROUP_MAX; ++i) {
+        const int s = i < ga.t.n ? ga.t.p[i].src : ga.t.p[0].src;   // (unused slots repeat the first problem)
+        const ddsp_fir_problem& p = problems[s];
+        ga.g[i] = gemm::make(a.act[s], K[s], tab_split[s], K[s], (int)rows, Ns[s], K[s]);
+        ga.g[i].math = DDSP_MATH_SPLIT_BF16;
+        ga.g[i].A_split = 1;
+        ga.g[i].B_split = tab_split[s];
+        epi.mode[i] = p.mode;
+        epi.n[i] = 2 * (p.n_mag - 1);
+        epi.ir[i] = p.ir;
+        epi.f0[i] = p.f0_frames;
+    }
+    ddsp_prof_begin(ctx, st, PF_FIR_DFT_GEMM);
+    gemm::launch_dma_group<64, 64>(st, ga, epi);
+    ddsp_prof_end(ctx, st, flops, traffic);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }

@@ -31,6 +31,7 @@
 // matrix pipe (157.3 TFLOP/s dense peak, MI355X_MICROARCH "Matrix cores").
 #pragma once
 #include "common.h"
+#include "gemm_group.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -950,6 +951,197 @@ inline Args make(const float* A, int64_t lda, const float* B, int64_t ldb, int M
     g.xcd = -1;   // decided by dma_go from the product arithmetic (see there)
     g.kz = 0;
     return g;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Grouped form of kernel_dma: ONE persistent launch walks the tiles of up to GROUP_MAX problems (gemm_group.h: which tile a
+// workgroup takes next, XCD-aware within each problem, long tiles first).  Every problem brings its own Args (A_PLAIN, both
+// operands already split: what MATH = 8 reads), its own k-tile count and its own epilogue; the k-tiles of a workgroup's tiles
+// still form one DMA stream, so the ramp, the tail and the rounding of the tile count to the machine are paid once per launch
+// instead of once per problem.  Per output element the order of the partial sums is kernel_dma's (k ascending, the three piece
+// products of a k-step in the same order), whatever the tile: the results are those of the separate launches, bit for bit.
+// GEpi: `for_problem(p, f)` calls f with problem p's epilogue (a wave-uniform switch over the concrete types).
+struct GroupArgs {
+    GroupTable t;
+    Args g[GROUP_MAX];   // in the table's order
+};
+
+template <int BM, int BN, class GEpi, int NS = 3, int NW = 4>
+__global__ void __launch_bounds__(64 * NW, (NW == 4 ? 3 : 4)) kernel_dma_group(GroupArgs ga, GEpi epi) {
+    constexpr int WGM = NW / 2, WGN = 2;
+    constexpr int TM = BM / (32 * WGM), TN = BN / (32 * WGN);
+    constexpr int ROWS = BM + BN, STAGE = ROWS * 32, PIECES = ROWS / 8, PPW = PIECES / NW;
+    static_assert(PIECES % NW == 0, "stage must split evenly over the waves");
+    __shared__ __attribute__((aligned(1024))) float lds[NS * STAGE];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = (wave >> 1) * (BM / WGM), wn = (wave & 1) * (BN / WGN);
+    const int lr = lane & 31, lh = lane >> 5;
+    const int xx = (int)blockIdx.x & 7, xq0 = (int)blockIdx.x >> 3, xgs = (int)gridDim.x >> 3;
+    const int my_tiles = group_my_tiles(ga.t, (int)gridDim.x, (int)blockIdx.x);
+
+    struct Tile {
+        int p, m0, n0, nk;
+    };
+    auto tile_of = [&](int i) -> Tile {
+        int p = 0, mt = 0, nt = 0;
+        group_tile(ga.t, xx, xq0 + i * xgs, &p, &mt, &nt);
+        return Tile{p, mt * BM, nt * BN, ga.t.p[p].nk};
+    };
+    int steps = 0;
+    for (int i = 0; i < my_tiles; ++i) steps += tile_of(i).nk;
+
+    // the DMA side runs NS - 1 k-steps ahead of the products and keeps its own tile cursor
+    const float* src_cur[PPW];
+    auto tile_src = [&](const Tile& t) {
+        const Args& g = ga.g[t.p];
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+            const int piece = wave + NW * i;
+            const int row = piece * 8 + (lane >> 3);
+            const int slot = (lane & 7) ^ ((row >> 1) & 7);
+            if (row < BM) {
+                int m = t.m0 + row;
+                m = m < g.M ? m : g.M - 1;
+                src_cur[i] = g.A + (int64_t)m * g.lda + slot * 4;
+            } else {
+                int n = t.n0 + row - BM;
+                n = n < g.N ? n : g.N - 1;
+                src_cur[i] = g.B + (int64_t)n * g.ldb + slot * 4;
+            }
+        }
+    };
+    int issued = 0, issue_tile = 0, issue_kt = 0, issue_nk = 0;
+    if (my_tiles > 0) {
+        const Tile t = tile_of(0);
+        issue_nk = t.nk;
+        tile_src(t);
+    }
+    auto issue_next = [&]() {
+        if (issued >= steps) return;
+#pragma unroll
+        for (int i = 0; i < PPW; ++i)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_cur[i] + issue_kt * 32),
+                                             (__attribute__((address_space(3))) void*)(lds + (issued % NS) * STAGE + (wave + NW * i) * 256),
+                                             16, 0, 0);
+        ++issued;
+        if (++issue_kt == issue_nk) {
+            issue_kt = 0;
+            if (++issue_tile < my_tiles) {
+                const Tile t = tile_of(issue_tile);
+                issue_nk = t.nk;
+                tile_src(t);
+            }
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < NS - 1; ++i) issue_next();
+
+    f32x16 acc[TM][TN], acc1[TM][TN];   // acc1: a kDual problem's sums of the first half of its k range
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = acc1[i][j][r] = 0.f;
+
+    int kt = 0, tile_i = 0;
+    Tile cur = my_tiles > 0 ? tile_of(0) : Tile{0, 0, 0, 1};
+    for (int step = 0; step < steps; ++step) {
+        static_assert((NS - 2) * PPW <= 63, "vmcnt is a 6-bit counter");
+        if (NS > 2 && step + NS - 2 < steps)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * PPW) : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        issue_next();
+        const float* st = lds + (step % NS) * STAGE;
+        f32x4 av[TM][4], bv[TN][4];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int row = wm + 32 * i + lr;
+            const float* rp = st + row * 32;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) av[i][c] = *(const f32x4*)(rp + 4 * ((4 * lh + c) ^ ((row >> 1) & 7)));
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int row = BM + wn + 32 * j + lr;
+            const float* rp = st + row * 32;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) bv[j][c] = *(const f32x4*)(rp + 4 * ((4 * lh + c) ^ ((row >> 1) & 7)));
+        }
+        typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const bf16x8 ah = __builtin_bit_cast(bf16x8, av[i][2 * half]), al = __builtin_bit_cast(bf16x8, av[i][2 * half + 1]);
+                    const bf16x8 bh = __builtin_bit_cast(bf16x8, bv[j][2 * half]), bl = __builtin_bit_cast(bf16x8, bv[j][2 * half + 1]);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+                }
+        ++kt;
+        if (2 * kt == cur.nk && epi.dual(cur.p)) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    acc1[i][j] = acc[i][j];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                }
+        }
+        if (kt == cur.nk) {
+            const Args& g = ga.g[cur.p];
+            const int M = g.M, N = g.N;
+            epi.for_problem(cur.p, [&](const auto& e) {
+                constexpr bool DUAL = epi_is_dual<std::decay_t<decltype(e)>>::value;
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int n = cur.n0 + wn + 32 * j + lr;
+                        const bool n_ok = n < N;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int m = cur.m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                            if (n_ok && m < M) {
+                                if constexpr (DUAL)
+                                    e(0, m, n, acc1[i][j][r], acc[i][j][r]);
+                                else
+                                    e(0, m, n, acc[i][j][r], 0.f);
+                            }
+                        }
+                    }
+            });
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            kt = 0;
+            if (++tile_i < my_tiles) cur = tile_of(tile_i);
+        }
+    }
+}
+
+// resident workgroups of kernel_dma_group on 256 CUs (the rule of launch_dma)
+template <int BM, int BN, int NS, int NW>
+constexpr int group_max_grid() {
+    constexpr int by_lds = 160 * 1024 / (NS * (BM + BN) * 128), by_waves = 16 / NW;
+    return 256 * (by_lds < by_waves ? by_lds : by_waves);
+}
+
+template <int BM, int BN, class GEpi, int NS = 3, int NW = 4>
+inline void launch_dma_group(hipStream_t st, const GroupArgs& ga, const GEpi& epi) {
+    const int grid = group_grid(ga.t, group_max_grid<BM, BN, NS, NW>());
+    if (grid == 0) return;
+    hipLaunchKernelGGL((kernel_dma_group<BM, BN, GEpi, NS, NW>), dim3(grid), dim3(64 * NW), 0, st, ga, epi);
 }
 
 // ---- common epilogues -----------------------------------------------------------------------

@@ -135,6 +135,18 @@ class _SynthBase(torch.nn.Module):
         saved = [] if keep else None
         return self._crop(ctx, n_dev, Fr), saved, (saved.extend if keep else (lambda xs: None))
 
+    _GROUP_MIN_ROWS = 8192   # ddsp_fir_from_ctrl_group groups from here on
+
+    def _filters(self, ctx, c2, problems, rows, f0_frames, keep):
+        """Iterator over the filters of a chain, `problems` = [(mode, first column, n_mag)] in the order the chain uses them.
+        Large inference batches: all of them from one grouped call (two launches) up front.  Training, which saves them one
+        by one, and small batches, where the grouped call would run the single calls anyway: each when the chain asks for
+        it, just before the FIR launch that reads it."""
+        if keep or rows < self._GROUP_MIN_ROWS:
+            return (ctx.fir_from_ctrl(mode, c2, col, n_mag, rows, self._sr, f0_frames if mode == FIR_DYNAMIC else None)
+                    for mode, col, n_mag in problems)
+        return iter(ctx.fir_from_ctrl_group(c2, problems, rows, self._sr, f0_frames))
+
     def _ragged_noise(self, ctx, n_dev, B, Fr, noise, noise_seed):
         """(unit-noise draw (B,T) with 0.5 - no excitation - past every row's end, EXC_UNIT_NOISE, 0)."""
         seed = 0 if noise is not None else (hipddsp.seed_from_torch() if noise_seed is None else int(noise_seed))
@@ -323,15 +335,17 @@ class CombSub(_SynthBase):
         crop, saved, save = self._stages(ctx, n_dev, Fr, keep)
         comb = ps["comb"]
         crop(comb)
-        ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, 0, na, rows, sr)
+        firs = self._filters(ctx, c2, [(FIR_ALLPASS, 0, na), (FIR_DYNAMIC, na, nh), (FIR_STATIC, na + nh, nn_)], rows,
+                             f0_frames, keep)
+        ir = next(firs)
         h, _ = ctx.ltv_fir(comb, ir, B, Fr, hop, math=ctx.fir_math)
         crop(h)
         save((comb, h, ir))
-        ir = ctx.fir_from_ctrl(FIR_DYNAMIC, c2, na, nh, rows, sr, f0_frames)
+        ir = next(firs)
         harmonic, _ = ctx.ltv_fir(h, ir, B, Fr, hop, math=ctx.fir_math)
         crop(harmonic)
         save((ir,))
-        ir = ctx.fir_from_ctrl(FIR_STATIC, c2, na + nh, nn_, rows, sr)
+        ir = next(firs)
         nz, exc, seed = excitation()
         noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
                                         math=ctx.fir_math)
@@ -392,11 +406,12 @@ class Sins(_SynthBase):
         crop, saved, save = self._stages(ctx, n_dev, Fr, keep)
         sinusoids = ctx.sins_bank(c2, 0, nhm, f0_frames, ps["phase"], B, Fr, hop, sr)
         crop(sinusoids)
-        ir = ctx.fir_from_ctrl(FIR_ALLPASS, c2, nhm, na, rows, sr)
+        firs = self._filters(ctx, c2, [(FIR_ALLPASS, nhm, na), (FIR_STATIC, nhm + na, nn_)], rows, f0_frames, keep)
+        ir = next(firs)
         harmonic, _ = ctx.ltv_fir(sinusoids, ir, B, Fr, hop, math=ctx.fir_math)
         crop(harmonic)
         save((ps["phase"], sinusoids, ir))
-        ir = ctx.fir_from_ctrl(FIR_STATIC, c2, nhm + na, nn_, rows, sr)
+        ir = next(firs)
         nz, exc, seed = excitation()
         noise_out, signal = ctx.ltv_fir(nz, ir, B, Fr, hop, excitation=exc, noise_seed=seed, add_in=harmonic,
                                         math=ctx.fir_math)

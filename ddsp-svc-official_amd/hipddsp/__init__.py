@@ -136,6 +136,11 @@ class DatasetView(_c.Structure):
                 + [(n, _c.c_int32) for n in ("n_aunit", "n_unit", "hop", "sample_rate", "fp16")])
 
 
+class FirProblem(_c.Structure):
+    """Mirror of `ddsp_fir_problem`."""
+    _fields_ = [("mode", _int), ("col", _int), ("n_mag", _int), ("f0_frames", _vp), ("ir", _vp)]
+
+
 class ProfEntry(_c.Structure):
     """Mirror of `ddsp_prof_entry`."""
     _fields_ = [("family", _int), ("name", _c.c_char * 36), ("launches", _i64), ("ms_total", _c.c_double),
@@ -174,6 +179,7 @@ SIGNATURES = {
     "ddsp_upsample": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
     "ddsp_phase_scan": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "ddsp_fir_from_ctrl": (_int, [_vp, _vp, _int, _vp, _i64, _int, _vp, _i64, _int, _vp]),
+    "ddsp_fir_from_ctrl_group": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int]),
     "ddsp_ltv_fir_bwd": (_int, [_vp, _vp, _vp, _int, _u64, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     "ddsp_fir_from_ctrl_bwd": (_int, [_vp, _vp, _int, _vp, _i64, _int, _vp, _i64, _int, _vp, _vp, _i64]),
     "ddsp_sins_bank": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _i64, _i64, _int, _int, _vp]),
@@ -783,6 +789,17 @@ class Context:
         f0 = None if f0_frames is None else f0_frames.reshape(-1).contiguous().float()
         self.call("ddsp_fir_from_ctrl", int(mode), base, ld, int(n_mag), _ptr(f0), rows, int(sr), _ptr(ir))
         return ir
+
+    def fir_from_ctrl_group(self, ctrl2d, problems, rows, sr, f0_frames=None):
+        """`problems`: up to three (mode, col0, n_mag) of one control matrix -> their filters, the bits of `fir_from_ctrl`
+        each; at large inference batches in two launches (`ddsp_fir_from_ctrl_group`).  f0_frames: for the DYNAMIC ones."""
+        f0 = None if f0_frames is None else f0_frames.reshape(-1).contiguous().float()
+        irs = [torch.empty(rows, 2 * (n_mag - 1), device=ctrl2d.device, dtype=torch.float32) for _, _, n_mag in problems]
+        table = (FirProblem * len(problems))(*[
+            FirProblem(int(mode), int(col0), int(n_mag), _ptr(f0) if mode == FIR_DYNAMIC else None, _ptr(ir))
+            for (mode, col0, n_mag), ir in zip(problems, irs)])
+        self.call("ddsp_fir_from_ctrl_group", _ptr(ctrl2d), ctrl2d.shape[-1], rows, int(sr), table, len(problems))
+        return irs
 
     # -- a7 ------------------------------------------------------------------------------------
     def ltv_fir(self, audio, ir, B, Fr, hop, excitation=EXC_AUDIO, noise_seed=0, add_in=None, want_out=True,

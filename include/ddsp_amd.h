@@ -90,6 +90,21 @@ int ddsp_phase_scan(ddsp_ctx* ctx, void* stream, const float* f0_frames, const f
 int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const float* ctrl, int64_t ctrl_ld, int n_mag,
                        const float* f0_frames, int64_t rows, int sr, float* ir);
 
+/* Up to three filters of ONE control matrix in one call (the filters of a synthesiser's render chain).  Each problem is a
+ * ddsp_fir_from_ctrl call on the columns [col, col + n_mag) of ctrl and writes the same bits into its ir.  Inference at large
+ * row counts (split-bf16 products, rows >= 8192, every n_mag a multiple of 32 - all-pass: of 16 with 2*pad32(n_mag) >= 256 - and
+ * 16-byte aligned column blocks): two launches, one for all activations and one grouped inverse-DFT product.  Every other case
+ * runs the single calls in order. */
+typedef struct ddsp_fir_problem {
+    int mode;               /* DDSP_FIR_* */
+    int col;                /* first column of the filter's control values */
+    int n_mag;
+    const float* f0_frames; /* (rows), DYNAMIC only (else NULL) */
+    float* ir;              /* out (rows, 2*(n_mag-1)) */
+} ddsp_fir_problem;
+int ddsp_fir_from_ctrl_group(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_t ctrl_ld, int64_t rows, int sr,
+                             const ddsp_fir_problem* problems, int n_problems);
+
 /* ---- a7: frame-varying FIR (50%-overlap triangular cross-fade between frame filters) -------- */
 /* replaces ddsp/core.py:185-239 `_fft_convolve` (+ :147-182 crop): out[u] = sum over taps of
  * x[t]*((1-j/hop)*ir[m] + (j/hop)*ir[min(m+1,Fr-1)])[u + n/2 - t], t = m*hop + j.
