@@ -285,6 +285,11 @@ extern "C" int ddsp_sins_bank_bwd(ddsp_ctx* ctx, void* stream, const float* ctrl
                  "ddsp_sins_bank_bwd: bad harmonics");
     DDSP_REQUIRE(ctx, B >= 0 && B <= 65535 && Fr >= 1 && hop >= 1 && hop <= 1024 && (hop & (hop - 1)) == 0,
                  "ddsp_sins_bank_bwd: bad shape (hop must be a power of two <= 1024)");
+    // the generic partial kernel keeps [4 waves][2][H] sums in dynamic LDS: 32 * H bytes, 64 KiB (the most a launch gets
+    // without hipFuncAttributeMaxDynamicSharedMemorySize) at H = 2048; partial32 uses none
+    const bool partial32 = hop <= 512 && n_harmonics % 32 == 0;
+    DDSP_REQUIRE(ctx, partial32 || n_harmonics <= 2048,
+                 "ddsp_sins_bank_bwd: more than 2048 harmonics need hop <= 512 and n_harmonics % 32 == 0");
     if (B == 0) return DDSP_OK;
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
@@ -296,7 +301,7 @@ extern "C" int ddsp_sins_bank_bwd(ddsp_ctx* ctx, void* stream, const float* ctrl
     float* partial = nullptr;
     if ((rc = ddsp_scratch_get(ctx, pf * sizeof(float), (void**)&partial))) return rc;
     ddsp_prof_begin(ctx, st, PF_SINS_BANK);
-    if (hop <= 512 && n_harmonics % 32 == 0)
+    if (partial32)
         hipLaunchKernelGGL(sins_bank_bwd_partial32_kernel, dim3((unsigned)Fr, (unsigned)B), dim3(256), 0, st, phase, d_out,
                            n_harmonics, (int)Fr, hop, partial);
     else

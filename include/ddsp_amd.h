@@ -349,7 +349,9 @@ int ddsp_spectral_ola(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_t ct
                       float* out);
 
 /* Adjoints of a10 / a11 w.r.t. their control blocks (training of Sins / CombSubFast): d_out (B,T) -> d_ctrl written
- * to the same column block layout as the forward reads, at row stride d_ctrl_ld. */
+ * to the same column block layout as the forward reads, at row stride d_ctrl_ld.
+ * ddsp_sins_bank_bwd: hop a power of two <= 1024; n_harmonics <= 4096 when hop <= 512 and n_harmonics % 32 == 0,
+ * else n_harmonics <= 2048 (DDSP_ERR_ARG above it). */
 int ddsp_sins_bank_bwd(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_t ctrl_ld, int n_harmonics,
                        const float* f0_frames, const float* phase, const float* d_out, int64_t B, int64_t Fr, int hop,
                        int sr, float* d_ctrl, int64_t d_ctrl_ld);
