@@ -291,6 +291,11 @@ __global__ void __launch_bounds__(256) repack_rows_kernel(const float* __restric
     }
 }
 
+// d_ir *= window, the weight formed in fp64 and rounded once with the product.  The fp32 form of the forward (EpiDynWindow::window,
+// the reference's order of operations) rounds pi_f * w at |w| up to 9.3 and is up to 1.6e-6 from the weight - many ulp of it, and
+// more than the weight itself where (1 + cos(pi w)) / 2 cancels, near every odd w < 0.  cos^2(pi w / 2) is the same function
+// without the cancellation.  Which taps count as w > 1 (weight 1) is still decided by the forward's fp32 w: a tap must not
+// be inside the window on one side and outside on the other.
 __global__ void __launch_bounds__(256) dyn_window_scale_kernel(float* __restrict__ d_ir, const float* __restrict__ f0,
                                                                int n, int64_t rows, float sr15) {
     const int64_t total = rows * n;
@@ -298,9 +303,10 @@ __global__ void __launch_bounds__(256) dyn_window_scale_kernel(float* __restrict
         const int64_t m = i / n;
         const int k = (int)(i % n);
         const float hw = __fdiv_rn(sr15, __fadd_rn(f0[m], 1e-3f));
-        float w = __fdiv_rn((float)(k - n / 2), hw);
-        if (w > 1.0f) w = 0.0f;
-        d_ir[i] *= __fdiv_rn(__fadd_rn(1.0f, cosf(__fmul_rn(3.14159274101257324f, w))), 2.0f);
+        if (__fdiv_rn((float)(k - n / 2), hw) > 1.0f) continue;      // w := 0: weight 1
+        const double w = (double)(k - n / 2) / ((double)sr15 / ((double)f0[m] + 1e-3));
+        const double c = cos(1.57079632679489661923 * w);
+        d_ir[i] = (float)((double)d_ir[i] * (c * c));
     }
 }
 

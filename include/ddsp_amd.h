@@ -86,7 +86,11 @@ int ddsp_phase_scan(ddsp_ctx* ctx, void* stream, const float* f0_frames, const f
 #define DDSP_FIR_STATIC 2   /* mags = exp(ctrl)/128, periodic Hann (:523,546; ddsp/core.py:242-289)  */
 /* replaces the ctrl activation + ddsp/core.py:306-328 `_frequency_impulse_response`.
  * ctrl: (B*Fr) rows of `n_mag` values at row stride `ctrl_ld` (so a column block of the fused control
- * matrix can be passed in place); f0_frames (B*Fr) (DYNAMIC only); ir out (B*Fr, n = 2*(n_mag-1)). */
+ * matrix can be passed in place); f0_frames (B*Fr) (DYNAMIC only); ir out (B*Fr, n = 2*(n_mag-1)).
+ * ddsp_ctx_set_math: DDSP_MATH_FP32 forms fp32 products and the DYNAMIC window in IEEE form (two divisions and cosf per tap, the
+ * reference's order of operations); DDSP_MATH_SPLIT_BF16 forms split-bf16 products where n_mag is a multiple of 32 (all-pass: of
+ * 16) and there the fast DYNAMIC window (one reciprocal per row, v_cos_f32: ~1e-6 of the weight); every other n_mag keeps fp32
+ * products and the IEEE window in either mode. */
 int ddsp_fir_from_ctrl(ddsp_ctx* ctx, void* stream, int mode, const float* ctrl, int64_t ctrl_ld, int n_mag,
                        const float* f0_frames, int64_t rows, int sr, float* ir);
 
@@ -325,7 +329,8 @@ int ddsp_dataset_gather(ddsp_ctx* ctx, void* stream, const ddsp_dataset_view* ds
 int ddsp_ltv_fir_bwd(ddsp_ctx* ctx, void* stream, const float* audio, int excitation, uint64_t noise_seed,
                      const float* ir, const float* d_out, int64_t B, int64_t Fr, int hop, int n, float* d_audio,
                      float* d_ir);
-/* Adjoint of ddsp_fir_from_ctrl: d_ir (rows, n) [scaled in place by the dynamic window in DYNAMIC mode] ->
+/* Adjoint of ddsp_fir_from_ctrl: d_ir (rows, n) [scaled in place by the dynamic window in DYNAMIC mode; the weight is formed
+ * in fp64 and rounded once with the product: d_ir is within an fp32 ulp of d_ir x window, element by element] ->
  * d_ctrl, written to `n_mag` columns at row stride d_ctrl_ld (a column block of the control-gradient matrix). */
 int ddsp_fir_from_ctrl_bwd(ddsp_ctx* ctx, void* stream, int mode, const float* ctrl, int64_t ctrl_ld, int n_mag,
                            const float* f0_frames, int64_t rows, int sr, float* d_ir, float* d_ctrl,
