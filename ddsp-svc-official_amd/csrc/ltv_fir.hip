@@ -21,7 +21,10 @@
 //
 // Bound: fp32 matrix pipe (64 FLOP/clk/SIMD); algorithmic HBM bytes are 4 B in + 4 B out per sample plus
 // 4*n/hop B of filter per sample.
-#include "common.h"
+//
+// This file is the hop == 512 build (fp32 and split-bf16 products).  hop 128 and 256 are served by ltv_fir_hop.hip, to
+// which the two entry points below hand over after their argument checks: fp32 products only, whatever `math` says.
+#include "fir_tile.h"   // noise_u, toeplitz_accumulate; the hop 128 / 256 entry points
 
 namespace {
 
@@ -32,58 +35,6 @@ constexpr int RS = 112;         // row stride of the transposed input image (flo
 constexpr int XS = 16 * RS;     // floats per frame image
 constexpr int IRPAD = 32;
 constexpr int SEG = 4;          // segments (hops) per block: 8 wavefronts, one 256-sample tile each; 2 blocks per CU by LDS
-
-__device__ __forceinline__ float noise_u(uint64_t seed, uint64_t idx) {
-    // A stateless hash of the sample counter (every block that needs sample idx regenerates it).  Round 3: two rounds of a 32-bit
-    // integer finaliser (multiply / xor-shift, constants of the "lowbias32" family) instead of the splitmix64 finaliser - its three
-    // 64 x 64-bit multiplies were ~45 vector instructions per sample in the FIR kernel's staging waves, which regenerate every
-    // sample twice (50 % overlapped frames); this is ~16 (`ddsp_hash32`, common.h).
-    const float u = (float)(ddsp_hash32(seed, idx) >> 8) * (1.0f / 16777216.0f);   // 24-bit U[0,1) like torch.rand fp32
-    return u * 2.0f - 1.0f;                                   // exact in fp32
-}
-
-// acc[s] += sum_{q=qa..qb} A_q * B_q for the four k-steps s of a 16x16x16 Toeplitz-block product:
-//   a = ap[16q + SA*4s], b = bp[s*bstep + SB*q]   (lane-constant parts already folded into ap / bp).
-// Software-pipelined with two register sets: operands of shift q+1 are fetched from LDS before the MFMAs of
-// shift q issue (sched_group_barrier pins [8 LDS reads][4 MFMAs]; hipcc otherwise sinks the reads).
-// qa, qb MUST be wave-uniform (SGPR) values - see the readfirstlane note in the kernels.
-template <int SA, int SB>
-__device__ __forceinline__ void toeplitz_accumulate(const float* __restrict__ ap, const float* __restrict__ bp,
-                                                    int bstep, int qa, int qb, f32x4 (&acc)[4]) {
-    if (qa > qb) return;
-    float a0[4], b0[4], a1[4], b1[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        a0[s] = ap[16 * qa + SA * 4 * s];
-        b0[s] = bp[s * bstep + SB * qa];
-    }
-    int q = qa;
-    for (; q + 1 <= qb; q += 2) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            a1[s] = ap[16 * (q + 1) + SA * 4 * s];
-            b1[s] = bp[s * bstep + SB * (q + 1)];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[s], b0[s], acc[s], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        const int q2 = (q + 2 <= qb) ? q + 2 : qb;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            a0[s] = ap[16 * q2 + SA * 4 * s];
-            b0[s] = bp[s * bstep + SB * q2];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s], b1[s], acc[s], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    }
-    if (q == qb) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[s], b0[s], acc[s], 0, 0, 0);
-    }
-}
 
 struct FirArgs {
     const float* audio;  // (B,T) or null
@@ -815,13 +766,15 @@ extern "C" int ddsp_ltv_fir(ddsp_ctx* ctx, void* stream, const float* audio, int
     DDSP_REQUIRE(ctx, excitation >= 0 && excitation <= 2, "ddsp_ltv_fir: unknown excitation");
     DDSP_REQUIRE(ctx, (excitation == DDSP_EXC_GENERATE) || audio, "ddsp_ltv_fir: audio is null");
     DDSP_REQUIRE(ctx, (out_sum == nullptr) == (add_in == nullptr), "ddsp_ltv_fir: out_sum and add_in go together");
-    DDSP_REQUIRE(ctx, hop == HOP, "ddsp_ltv_fir: only hop == 512 is built");
+    DDSP_REQUIRE(ctx, hop == 128 || hop == 256 || hop == HOP, "ddsp_ltv_fir: hop must be 128, 256 or 512");
     DDSP_REQUIRE(ctx, n >= 32 && n <= 2046 && (n % 2) == 0, "ddsp_ltv_fir: n must be even, 32..2046");
     DDSP_REQUIRE(ctx, B >= 0 && Fr >= 1 && B <= 65535, "ddsp_ltv_fir: bad shape");
     DDSP_REQUIRE(ctx, ((uintptr_t)out % 16) == 0 && ((uintptr_t)add_in % 16) == 0 && ((uintptr_t)out_sum % 16) == 0 &&
                           ((uintptr_t)audio % 16) == 0 && ((uintptr_t)ir % 8) == 0,
                  "ddsp_ltv_fir: audio/out/add_in/out_sum must be 16-byte aligned (ir 8-byte)");
     if (B == 0) return DDSP_OK;
+    if (hop != HOP)
+        return ddsp_ltv_fir_hop(ctx, (hipStream_t)stream, audio, excitation, noise_seed, ir, B, Fr, hop, n, add_in, out, out_sum);
     const double Tsig = (double)Fr * HOP, nbat = (double)B;
     // algorithmic work: every input sample meets two frame filters of n taps (2 FLOP per tap);
     // algorithmic bytes: x in (0 when generated), filters in, y out (+ add_in, + second output)
@@ -967,12 +920,14 @@ extern "C" int ddsp_ltv_fir_bwd(ddsp_ctx* ctx, void* stream, const float* audio,
     DDSP_REQUIRE(ctx, ctx && ir && d_out && (d_audio || d_ir), "ddsp_ltv_fir_bwd: null argument");
     DDSP_REQUIRE(ctx, excitation >= 0 && excitation <= 2, "ddsp_ltv_fir_bwd: unknown excitation");
     DDSP_REQUIRE(ctx, !d_ir || excitation == DDSP_EXC_GENERATE || audio, "ddsp_ltv_fir_bwd: d_ir needs the forward input");
-    DDSP_REQUIRE(ctx, hop == HOP, "ddsp_ltv_fir_bwd: only hop == 512 is built");
+    DDSP_REQUIRE(ctx, hop == 128 || hop == 256 || hop == HOP, "ddsp_ltv_fir_bwd: hop must be 128, 256 or 512");
     DDSP_REQUIRE(ctx, n >= 32 && n <= 2046 && (n % 2) == 0, "ddsp_ltv_fir_bwd: n must be even, 32..2046");
     DDSP_REQUIRE(ctx, B >= 0 && Fr >= 1 && B <= 65535, "ddsp_ltv_fir_bwd: bad shape");
     DDSP_REQUIRE(ctx, ((uintptr_t)d_out % 16) == 0 && ((uintptr_t)d_audio % 16) == 0, "ddsp_ltv_fir_bwd: d_out/d_audio must be 16-byte aligned");
     if (B == 0) return DDSP_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (hop != HOP)
+        return ddsp_ltv_fir_hop_bwd(ctx, st, audio, excitation, noise_seed, ir, d_out, B, Fr, hop, n, d_audio, d_ir);
     DDSP_ENTER_DEVICE(ctx);
     DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)ltv_fir_bwd_input_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); DDSP_HIP(ctx, hipFuncSetAttribute((const void*)ltv_fir_bwd_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
     const double Ts = (double)Fr * HOP;

@@ -106,8 +106,10 @@ def frequency_filter(audio, magnitudes, hann_window=True, half_width_frames=None
     audio :: (B, T) device tensor, magnitudes :: (B, Frame, n_mag) complex, half_width_frames :: (B, Frame, 1) or None.
     The impulse responses are formed by `_impulse_response` (inverse DFT on the library's GEMM + elementwise ops), the filtering itself -
     `_fft_convolve`, `core.py:190-238`: 50 %-overlapped Bartlett frames, one filter per frame, output delayed by
-    n/2 and cropped to T - is the hand-written `ddsp_ltv_fir` kernel.  That kernel supports what the models use:
-    T = Frame * 512 and even filter lengths 32..2046 (n_mag 17..1024); other shapes raise ValueError.  Forward only:
+    n/2 and cropped to T - is the hand-written `ddsp_ltv_fir` kernel.  This entry point takes T = Frame * 512 and even
+    filter lengths 32..2046 (n_mag 17..1024); other shapes raise ValueError.  The kernel itself and the model classes
+    also run at hop 128 and 256; this function stays at 512 because its refusal of T // Frame == 256 is part of the
+    contract the suite holds (tests/test_gpu_dsp.py::test_frequency_filter_refusals).  Forward only:
     the models differentiate through their own fused path, so tensors that require grad are refused here.
     """
     if audio.requires_grad or magnitudes.requires_grad or (half_width_frames is not None and half_width_frames.requires_grad):
@@ -120,6 +122,8 @@ def frequency_filter(audio, magnitudes, hann_window=True, half_width_frames=None
     Fr = magnitudes.shape[1]
     if Fr == 0 or T % Fr != 0:
         raise ValueError("frequency_filter: T must be a whole number of frames on the device path")
+    if T // Fr != 512:
+        raise ValueError("frequency_filter: T = Frame * 512 expected (the model classes take block sizes 128, 256 and 512)")
     ir = _impulse_response(magnitudes, hann_window, half_width_frames).float().contiguous()
     ctx = context_for(audio.device)
     out, _ = ctx.ltv_fir(audio.float().contiguous(), ir, B, Fr, T // Fr)

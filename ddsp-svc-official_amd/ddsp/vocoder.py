@@ -464,8 +464,8 @@ class CombSubFast(_SynthBase):
 
     def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
         """One windowed spectral OLA -> ((signal,), saved).  Ragged: with the comb and the excitation 0 past a row's end,
-        frames 0..n_b of the row are the frames of the row rendered alone (frame n_b on frame n_b - 1's filters, 512 zeros
-        behind the row)."""
+        frames 0..n_b of the row are the frames of the row rendered alone (frame n_b on frame n_b - 1's filters, `block_size`
+        zeros behind the row)."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
         crop, saved, save = self._stages(ctx, n_dev, Fr, keep)
         comb = ps["comb"]

@@ -806,6 +806,11 @@ class Context:
                 math=FIR_FP32):
         """Returns (filtered | None, filtered + add_in | None).  math: FIR_FP32 or FIR_SPLIT_BF16 (inference)."""
         n = ir.shape[-1]
+        # the kernel reads B * Fr * hop samples and B * Fr filters whatever the tensors hold: sizes are checked here
+        for name, t, want in (("audio", audio, B * Fr * hop), ("add_in", add_in, B * Fr * hop), ("ir", ir, B * Fr * n)):
+            if t is not None and t.numel() != want:
+                raise ValueError(f"ltv_fir: {name} holds {t.numel()} values, B * Fr * {'n' if name == 'ir' else 'hop'} = {want} "
+                                 f"expected (B = {B}, Fr = {Fr}, hop = {hop})")
         mk = lambda: torch.empty(B, Fr * hop, device=ir.device, dtype=torch.float32)
         out = mk() if want_out else None
         out_sum = mk() if add_in is not None else None
@@ -818,6 +823,10 @@ class Context:
     def ltv_fir_bwd(self, audio, ir, d_out, B, Fr, hop, excitation=EXC_AUDIO, noise_seed=0, want_d_audio=True,
                     want_d_ir=True):
         n = ir.shape[-1]
+        for name, t, want in (("audio", audio, B * Fr * hop), ("d_out", d_out, B * Fr * hop), ("ir", ir, B * Fr * n)):
+            if t is not None and t.numel() != want:
+                raise ValueError(f"ltv_fir_bwd: {name} holds {t.numel()} values, B * Fr * {'n' if name == 'ir' else 'hop'} = {want} "
+                                 f"expected (B = {B}, Fr = {Fr}, hop = {hop})")
         d_out = d_out.contiguous().float()
         d_audio = torch.empty(B, Fr * hop, device=ir.device, dtype=torch.float32) if want_d_audio else None
         d_ir = torch.empty(B * Fr, n, device=ir.device, dtype=torch.float32) if want_d_ir else None

@@ -124,7 +124,10 @@ int ddsp_fir_from_ctrl_group(ddsp_ctx* ctx, void* stream, const float* ctrl, int
  *       fp32 accumulation, ~4e-6 relative error; the inference path).  Filters too long for that kernel's
  *       staging fall back to the fp32 kernel.  (Values 31..58 force one block shape of the split-bf16 kernels or
  *       switch their products off - measurement aids of tools/fir_bf16_check.py, not part of the interface.)
- * Requires hop == 512 and n even, 32 <= n <= 2046. */
+ * Requires hop in {128, 256, 512} and n even, 32 <= n <= 2046 (the same at every hop: up to 16 hops at 128).
+ * hop 128 and 256 multiply on the fp32 matrix pipe whatever `math` (or ddsp_ctx_set_math) says: no split-bf16 form is
+ * built for them.  The generated stream is one function of (noise_seed, row, sample index) at every hop.
+ * ddsp_ltv_fir_bwd takes the same hops. */
 #define DDSP_FIR_FP32 0
 #define DDSP_FIR_SPLIT_BF16 3
 #define DDSP_EXC_AUDIO 0
@@ -346,9 +349,10 @@ int ddsp_sins_bank(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_t ctrl_
 
 /* ---- a11: CombSubFast windowed spectral overlap-add ------------------------------------------ */
 /* replaces ddsp/vocoder.py:462-490.  ctrl rows (B*Fr) at stride ctrl_ld hold
- * [harmonic_magnitude 513 | harmonic_phase 513 | noise_magnitude 513]; comb (B,T) from ddsp_phase_scan
+ * [harmonic_magnitude NB | harmonic_phase NB | noise_magnitude NB], NB = hop + 1; comb (B,T) from ddsp_phase_scan
  * (DDSP_COMB_SINC_GATED); noise (B,T) U[0,1) draws with excitation DDSP_EXC_UNIT_NOISE, or NULL with
- * DDSP_EXC_GENERATE + noise_seed; out (B,T).  hop == 512 (1024-point frames). */
+ * DDSP_EXC_GENERATE + noise_seed; out (B,T).  hop in {128, 256, 512} (frames of 2*hop points); ddsp_spectral_ola_bwd
+ * takes the same hops. */
 int ddsp_spectral_ola(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_t ctrl_ld, const float* comb,
                       const float* noise, int excitation, uint64_t noise_seed, int64_t B, int64_t Fr, int hop,
                       float* out);
