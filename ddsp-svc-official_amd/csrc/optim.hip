@@ -1,5 +1,7 @@
 // a15: AdamW step (train.py:41 `torch.optim.AdamW`): one fused elementwise kernel per parameter tensor
 // (ddsp_adamw_step) or per batch of up to 24 tensors (ddsp_adamw_step_multi, what the optimizer class uses).
+// ddsp_adamw_step_multi_scaled: the same launch with every gradient multiplied by `grad_scale` as it is read - the 1 / world
+// of a data-parallel mean, applied to the summed bucket here instead of in a pass of its own over the gradients.
 #include "common.h"
 
 namespace {
@@ -36,8 +38,9 @@ struct AdamwBatch {
     int count;
 };
 
+template <bool SCALED>
 __global__ void __launch_bounds__(256) adamw_multi_kernel(AdamwBatch a, float lr, float beta1, float beta2, float eps,
-                                                          float wd, float bc1, float bc2_sqrt) {
+                                                          float wd, float bc1, float bc2_sqrt, float grad_scale) {
     const int b = blockIdx.x;
     int t = 0;
     while (t + 1 < a.count && b >= a.blk0[t + 1]) ++t;      // wave-uniform
@@ -49,7 +52,7 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(AdamwBatch a, float lr
     const int64_t lo = (int64_t)(b - a.blk0[t]) * ADAMW_CHUNK;
     const int64_t hi = lo + ADAMW_CHUNK < n ? lo + ADAMW_CHUNK : n;
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-        const float gi = g[i];
+        const float gi = SCALED ? g[i] * grad_scale : g[i];
         float pi = p[i] * (1.0f - lr * wd);                 // same arithmetic, in the same order, as adamw_kernel
         const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
         const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
@@ -62,10 +65,10 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(AdamwBatch a, float lr
 }
 }  // namespace
 
-extern "C" int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params,
-                                     const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                     const int64_t* numel, float lr, float beta1, float beta2, float eps,
-                                     float weight_decay, int64_t step) {
+template <bool SCALED>
+static int adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params, const float* const* grads,
+                            float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, int64_t step, float grad_scale) {
     DDSP_REQUIRE(ctx, ctx && n_tensors >= 0 && step >= 1, "ddsp_adamw_step_multi: bad count or step");
     if (n_tensors == 0) return DDSP_OK;
     DDSP_REQUIRE(ctx, params && grads && exp_avg && exp_avg_sq && numel, "ddsp_adamw_step_multi: null table");
@@ -106,12 +109,30 @@ extern "C" int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors,
         }
         if (a.count == 0) break;
         a.blk0[a.count] = blocks;
-        hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, lr, beta1, beta2, eps,
-                           weight_decay, (float)bc1, (float)sqrt(bc2));
+        hipLaunchKernelGGL(adamw_multi_kernel<SCALED>, dim3((unsigned)blocks), dim3(256), 0, st, a, lr, beta1, beta2, eps,
+                           weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
     }
     ddsp_prof_end(ctx, st, 12.0 * total, 28.0 * total);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params,
+                                     const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                     const int64_t* numel, float lr, float beta1, float beta2, float eps,
+                                     float weight_decay, int64_t step) {
+    return adamw_step_multi<false>(ctx, stream, n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps,
+                                   weight_decay, step, 1.0f);
+}
+
+extern "C" int ddsp_adamw_step_multi_scaled(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params,
+                                            const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                            const int64_t* numel, float lr, float beta1, float beta2, float eps,
+                                            float weight_decay, int64_t step, float grad_scale) {
+    DDSP_REQUIRE(ctx, ctx && grad_scale == grad_scale && grad_scale - grad_scale == 0.0f,
+                 "ddsp_adamw_step_multi_scaled: grad_scale must be finite");
+    return adamw_step_multi<true>(ctx, stream, n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps,
+                                  weight_decay, step, grad_scale);
 }
 
 extern "C" int ddsp_adamw_step(ddsp_ctx* ctx, void* stream, float* param, const float* grad, float* exp_avg,

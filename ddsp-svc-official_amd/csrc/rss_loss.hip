@@ -304,9 +304,14 @@ __global__ void __launch_bounds__(256) frames_ola_kernel(const float* __restrict
 }  // namespace
 
 // ns_host / ns_dev: the rows' sample counts on the host (checks, cell counts) and on the device (the kernels), or both null
+// gns_host (n_global counts, with ns_host; null: the local rows are the whole batch): the rows of the GLOBAL batch these B rows
+// are a part of.  Both denominators (the cells that exist, the rows with a frame) then come from the global counts and the
+// numerators from the local rows: the value is this rank's share of the global loss.  A scale at which no local row has a frame
+// (n_fft > T included) contributes nothing to the share and is not launched.
 static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
                         const int* ns_host, const int* ns_dev, const int* n_ffts_host, const int* hops_host, int n_scale,
-                        float alpha, float eps, float* loss, float* grad_pred, float* loss_rows = nullptr) {
+                        float alpha, float eps, float* loss, float* grad_pred, float* loss_rows = nullptr,
+                        const int* gns_host = nullptr, int64_t n_global = 0) {
     // loss_rows (device float[B], with counts and without grad_pred): one loss per row instead of the batch's scalar
     DDSP_REQUIRE(ctx, ctx && x_pred && x_true && n_ffts_host && (loss || loss_rows), "ddsp_rss_loss: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 32768 && T >= 4 && n_scale >= 1 && n_scale <= 64, "ddsp_rss_loss: bad shape");
@@ -315,19 +320,35 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
     auto hop_of = [&](int s) { return hops_host ? hops_host[s] : n_ffts_host[s]; };
     auto round32 = [](int v) { return (v + 31) & ~31; };
     size_t tabT_f = 0, tab_f = 0, xf_f = 0, s_f = 0, xp_f = 0;
+    // the rows this call scores at scale N: some local row has a frame (always, without global counts: checked below)
+    auto local_any = [&](int N) {
+        if (!ns_host) return true;
+        for (int64_t b = 0; b < B; ++b)
+            if (ns_host[b] >= N) return true;
+        return false;
+    };
+    if (gns_host) {
+        DDSP_REQUIRE(ctx, ns_host && n_global >= B && n_global <= 32768, "ddsp_rss_loss_share: the global batch holds the local rows");
+        for (int64_t b = 0; b < n_global; ++b)
+            DDSP_REQUIRE(ctx, gns_host[b] >= 1, "ddsp_rss_loss_share: global_n_samples must be positive");
+    }
     for (int s = 0; s < n_scale; ++s) {
         const int N = n_ffts_host[s], hop = hop_of(s);
-        DDSP_REQUIRE(ctx, N >= 8 && N <= T && N <= 8192, "ddsp_rss_loss: n_fft out of range");
+        DDSP_REQUIRE(ctx, N >= 8 && (N <= T || gns_host) && N <= 8192, "ddsp_rss_loss: n_fft out of range");
         DDSP_REQUIRE(ctx, hop >= 1 && hop <= N, "ddsp_rss_loss: hop must lie in [1, n_fft]");
+        if (ns_host)
+            for (int64_t b = 0; b < B; ++b)
+                DDSP_REQUIRE(ctx, ns_host[b] >= 1 && ns_host[b] <= T, "ddsp_rss_loss_ragged: n_samples outside 1..T");
+        if (gns_host) {
+            bool any = false;
+            for (int64_t b = 0; b < n_global; ++b) any = any || gns_host[b] >= N;
+            DDSP_REQUIRE(ctx, any, "ddsp_rss_loss_share: no global row has a whole frame at one of the scales");
+            if (!local_any(N)) continue;   // (n_fft > T ends here: every count is <= T)
+        }
         const size_t Mb = N / 2 + 1, Kp = round32(N), Kb = round32(2 * (int)Mb), M = (size_t)B * (size_t)((T - N) / hop + 1);
         DDSP_REQUIRE(ctx, M * Kp < ((size_t)1 << 31) && 2 * M < ((size_t)1 << 31), "ddsp_rss_loss: too many frames for one call");
         if (ns_host) {
-            bool any = false;
-            for (int64_t b = 0; b < B; ++b) {
-                DDSP_REQUIRE(ctx, ns_host[b] >= 1 && ns_host[b] <= T, "ddsp_rss_loss_ragged: n_samples outside 1..T");
-                any = any || ns_host[b] >= N;
-            }
-            DDSP_REQUIRE(ctx, any, "ddsp_rss_loss_ragged: no row has a whole frame at one of the scales");
+            DDSP_REQUIRE(ctx, local_any(N), "ddsp_rss_loss_ragged: no row has a whole frame at one of the scales");
             if (loss_rows)
                 for (int64_t b = 0; b < B; ++b)
                     DDSP_REQUIRE(ctx, ns_host[b] >= N, "ddsp_rss_loss_rows: a row has no whole frame at one of the scales");
@@ -341,6 +362,11 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
     if (!grad_pred) tab_f = xp_f = 0;
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
+    if (xf_f == 0) {   // a share none of whose rows has a frame at any scale: 0, with a zero gradient
+        DDSP_HIP(ctx, hipMemsetAsync(loss, 0, sizeof(float), st));
+        if (grad_pred) DDSP_HIP(ctx, hipMemsetAsync(grad_pred, 0, (size_t)B * T * sizeof(float), st));
+        return DDSP_OK;
+    }
     // scratch sized for the worst scale: the two tables, the framed copy of both signals, S_t, S_p, X_p
     // DDSP_LOSS_TABLE_1D=0: the direct table kernel (test_tables_from_1d_factors_are_bit_identical)
     static const bool table_1d = [] { const char* e = getenv("DDSP_LOSS_TABLE_1D"); return !(e && e[0] == '0'); }();
@@ -382,8 +408,10 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
     const int loss_bwd_math = ctx->math == DDSP_MATH_FP32 ? 0 : DDSP_MATH_SPLIT_BF16;
     ddsp_prof_begin(ctx, st, PF_RSS_LOSS);
     double flops = 0.0;
+    bool first = true;   // the first scale that is launched writes loss and gradient, the others add
     for (int s = 0; s < n_scale; ++s) {
         const int N = n_ffts_host[s], hop = hop_of(s), Mb = N / 2 + 1, Kp = round32(N), Kb = round32(2 * Mb);
+        if (gns_host && !local_any(N)) continue;
         const int F = (int)((T - N) / hop + 1);
         const int64_t M = B * F;
         const double weight = 1.0 / n_scale;
@@ -398,10 +426,19 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
                     frames += (ns_host[b] - N) / hop + 1;
                     ++rows_ne;
                 }
+            if (gns_host) {
+                frames = 0;
+                rows_ne = 0;
+                for (int64_t b = 0; b < n_global; ++b)
+                    if (gns_host[b] >= N) {
+                        frames += (gns_host[b] - N) / hop + 1;
+                        ++rows_ne;
+                    }
+            }
             count = (double)(frames * Mb);
         }
         if (use_1d) {
-            if (s == 0) hipLaunchKernelGGL(stft_table1d_kernel, dim3(8, (unsigned)n_scale), dim3(256), 0, st, t1a);
+            if (first) hipLaunchKernelGGL(stft_table1d_kernel, dim3(8, (unsigned)n_scale), dim3(256), 0, st, t1a);
             hipLaunchKernelGGL(stft_table_from1d_kernel, dim3(1024), dim3(256), 0, st, t1a.t1[s], tabT, tab, N, Kp, Kb);
         } else
             hipLaunchKernelGGL(stft_table_kernel, dim3(1024), dim3(256), 0, st, tabT, tab, N, Kp, Kb);
@@ -419,10 +456,10 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
         hipLaunchKernelGGL(loss_fold_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, stats, (int)B);
         if (loss_rows)
             hipLaunchKernelGGL(loss_rows_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, stats, (int)B, Mb, (double)alpha,
-                               weight, loss_rows, s == 0 ? 1 : 0, ns_dev, T, N, hop, F);
+                               weight, loss_rows, first ? 1 : 0, ns_dev, T, N, hop, F);
         else
             hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(64), 0, st, stats, (int)B, count, rows_ne,
-                               (double)alpha, weight, loss, s == 0 ? 1 : 0, ns_dev, T, N, hop, F);
+                               (double)alpha, weight, loss, first ? 1 : 0, ns_dev, T, N, hop, F);
         flops += 2.0 * 2.0 * M * (double)N * 2 * Mb;
         if (grad_pred) {
             const int64_t total = M * Mb;
@@ -437,9 +474,10 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
             gemm::EpiStore eg{Xf, Kp, nullptr, 1, 0, 0};
             gemm::launch<true, true, gemm::A_PLAIN>(st, gb, 1, eg);
             hipLaunchKernelGGL(frames_ola_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(B * T, 256), 16384)), dim3(256), 0,
-                               st, Xf, Kp, T, N, hop, F, B, s == 0 ? 0 : 1, grad_pred, ns_dev);
+                               st, Xf, Kp, T, N, hop, F, B, first ? 0 : 1, grad_pred, ns_dev);
             flops += 2.0 * M * (double)N * 2 * Mb;
         }
+        first = false;
     }
     ddsp_prof_end(ctx, st, flops, 4.0 * B * T * (2.0 * n_scale + (grad_pred ? 1.0 : 0.0)));
     DDSP_LAUNCH_CHECK(ctx);
@@ -459,6 +497,16 @@ extern "C" int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_
     DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev, "ddsp_rss_loss_ragged: null n_samples");
     return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
                         n_scale, alpha, eps, loss, grad_pred);
+}
+
+extern "C" int ddsp_rss_loss_share(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                                   const int* n_samples_host, const int32_t* n_samples_dev, const int* global_n_samples_host,
+                                   int64_t n_global, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha,
+                                   float eps, float* loss, float* grad_pred) {
+    DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev && global_n_samples_host && loss,
+                 "ddsp_rss_loss_share: null argument");
+    return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
+                        n_scale, alpha, eps, loss, grad_pred, nullptr, global_n_samples_host, n_global);
 }
 
 extern "C" int ddsp_rss_loss_rows(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,

@@ -22,7 +22,7 @@ import numpy as np
 
 from infer_offline import group_segments
 from preprocess import list_audio, load_wav
-from sharding import shard_rows
+from sharding import RaggedPlan, shard_rows
 
 AUDIO_ALIGN = 8     # elements: every file's first sample sits on 16 bytes in an fp32 and in an fp16 arena
 ARENA_ALIGN = 8     # total_frames * n_unit is a multiple of it: every units arena starts on 16 bytes
@@ -173,18 +173,31 @@ def pack_arenas(records, waveform_sec, fp16=False):
     return {"audio": audio, "units": units, "f0": f0, "volume": volume}, tables
 
 
-def epoch_plan(n_files, batch_size, rank=0, world=1):
+def epoch_plan(n_files, batch_size, rank=0, world=1, even=False):
     """What `DataLoader(shuffle=True)` does with one permutation of the files: [(cursor, rows)] per step - the global batch
     at [start, start + size) of the permutation, the last one shorter (no drop_last), of which `rank` takes its
-    `sharding.shard_rows` slice: `rows` rows from permutation index `cursor` on (rows may be 0 in a short last batch)."""
+    `sharding.shard_rows` slice: `rows` rows from permutation index `cursor` on (rows may be 0 in a short last batch).
+    even: a global batch keeps the largest multiple of `world` rows it holds (the training loop's form: equal shards, whose
+    mean loss is the global loss, and the same number of steps on every rank); a batch of fewer than `world` rows is left
+    out on every rank."""
     if batch_size < 1 or world < 1 or not 0 <= rank < world:
         raise ValueError(f"epoch_plan: batch_size {batch_size}, rank {rank} of {world}")
     plan = []
     for start in range(0, int(n_files), int(batch_size)):
         size = min(int(batch_size), int(n_files) - start)
+        if even:
+            size -= size % world
+            if size == 0:
+                continue
         lo, hi = shard_rows(size, world, rank)
         plan.append((start + lo, hi - lo))
     return plan
+
+
+def shard_whole(n_frames, rank, world):
+    """The rows (indices into `n_frames`) of a global group of whole utterances that `rank` trains on: the balanced deal of
+    `sharding.RaggedPlan`.  Over the ranks the lists are a partition of the group."""
+    return RaggedPlan(n_frames, world).local(rank)
 
 
 def epoch_seed(seed, epoch):
@@ -281,11 +294,12 @@ class AudioDataset:
                                           crop_frames=self.crop, waveform_sec=self.waveform_sec, out=out)
         return _Batch(self._finish(got), self.paths)
 
-    def batches(self, batch_size, seed=None, rank=0, world=1, epoch=None):
+    def batches(self, batch_size, seed=None, rank=0, world=1, epoch=None, even=False):
         """One epoch, as `DataLoader(shuffle=True)` walks it: a permutation of the files (made on the device with
         `torch.randperm`, nothing is synchronised), a batch per `batch_size` of it, the last one shorter.  Under data
         parallelism every rank passes the same `seed` and gets its `sharding.shard_rows` slice of each global batch.  Every
-        call is a new epoch (a new permutation and new crops from the same `seed`); `epoch` names one instead of counting."""
+        call is a new epoch (a new permutation and new crops from the same `seed`); `epoch` names one instead of counting.
+        `batch_size` is the GLOBAL batch; `even`: equal shards on every rank (`epoch_plan`)."""
         import torch
         if seed is None:
             if world > 1:
@@ -297,7 +311,7 @@ class AudioDataset:
         g = torch.Generator(device=self.device)
         g.manual_seed(s)
         perm = torch.randperm(len(self), device=self.device, generator=g).to(torch.int32)
-        for cursor, rows in epoch_plan(len(self), batch_size, rank, world):
+        for cursor, rows in epoch_plan(len(self), batch_size, rank, world, even):
             if rows:
                 yield self.batch(batch_size=rows, seed=s, perm=perm, cursor=cursor)
 
@@ -321,14 +335,34 @@ class AudioDataset:
         batch["name"] = [self.paths[i] for i in files]         # the files were named by the caller: no copy of `draws`
         return batch
 
-    def whole_batches(self, batch_frames):
-        """Every file once, whole, grouped with `infer_offline.group_segments` so that a group's padded size (rows * longest)
-        stays within `batch_frames` frames: padded batches with `n_frames`."""
+    def whole_groups(self, batch_frames):
+        """Every file once, grouped with `infer_offline.group_segments` so that a group's padded size (rows * longest) stays
+        within `batch_frames` frames -> the groups, lists of file indices (a pure function of the lengths: the same on
+        every rank)."""
         for i, k in enumerate(self.whole):
             if k < 1:
                 raise ValueError(f"{self.paths[i]}: a whole-audio row needs at least 1 frame")
-        for group in group_segments(self.whole, int(batch_frames)):
-            yield self.whole_batch(group)
+        return group_segments(self.whole, int(batch_frames))
+
+    def whole_batches(self, batch_frames, rank=0, world=1):
+        """The groups of `whole_groups` as padded batches with `n_frames`.  Under data parallelism (`world > 1`) every rank
+        walks the same global groups and gets its rows of each (`whole_shard`), with `global_n_frames`."""
+        for group in self.whole_groups(batch_frames):
+            batch = self.whole_batch(group) if world == 1 else self.whole_shard(group, rank, world)
+            if batch is not None:
+                yield batch
+
+    def whole_shard(self, group, rank, world):
+        """`rank`'s rows of the global group `group` (file indices): those `sharding.RaggedPlan(n_frames, world).local(rank)`
+        names, as a ragged batch that also carries `global_n_frames`, the frame counts of the whole group in the group's
+        order - the same list on every rank (`training.train_step` forms the loss's denominators from it).  A group of fewer
+        than `world` rows would leave a rank without a row: None, on every rank."""
+        n = [self.whole[i] for i in group]
+        if len(group) < world:
+            return None
+        batch = self.whole_batch([group[j] for j in shard_whole(n, rank, world)])
+        batch["global_n_frames"] = n
+        return batch
 
     def __getitem__(self, file_idx):
         """The reference's item (`data_loaders.py:88-146`): the dict of one file - after the skip of a file shorter than
@@ -379,10 +413,16 @@ class _Loader:
         return self._len() if hasattr(self, "_len") else len(self.dataset)
 
 
-def get_data_loaders(args, whole_audio=False):
+def get_data_loaders(args, whole_audio=False, rank=0, world=1):
     """-> (train, valid) as the reference's `get_data_loaders` (`data_loaders.py:12-24`), each iterable over batches:
     train: `batches(args.train.batch_size)` over args.data.train_path (whole files at batch 1 with `whole_audio`);
-    valid: whole files at batch 1, in file order, over args.data.valid_path."""
+    valid: whole files at batch 1, in file order, over args.data.valid_path.
+    Data parallel (`world > 1`): `args.train.batch_size` is the GLOBAL batch and must divide by `world` (ValueError);
+    `rank` gets its equal share of every global batch, permutation and crops from `args.train.seed` (default 0) on every
+    rank.  With `whole_audio` every rank walks the same global groups of `args.train.val_batch_frames` padded frames
+    (default `solver.VAL_BATCH_FRAMES`), longest first, and takes its rows of each with `global_n_frames`."""
+    if world > 1 and not whole_audio and int(args.train.batch_size) % world:
+        raise ValueError(f"train.batch_size = {args.train.batch_size} is the global batch: it must divide by the {world} ranks")
     common = dict(waveform_sec=args.data.duration, hop_size=args.data.block_size, sample_rate=args.data.sampling_rate,
                   n_spk=args.model.n_spk, n_aunit=args.data.n_aunit)
     data_train = AudioDataset(args.data.train_path, load_all_data=args.train.cache_all_data, whole_audio=whole_audio,
@@ -393,8 +433,16 @@ def get_data_loaders(args, whole_audio=False):
         order = ds._rng.permutation(len(ds)) if shuffle else range(len(ds))
         return (ds.whole_batch([i]) for i in order)
 
-    if whole_audio:
+    seed = int(args.train.seed or 0)
+    if whole_audio and world > 1:
+        frames = int(args.train.val_batch_frames or 8192)
+        train = _Loader(data_train, lambda: data_train.whole_batches(frames, rank, world))
+        train._len = lambda: sum(len(g) >= world for g in data_train.whole_groups(frames))
+    elif whole_audio:
         train = _Loader(data_train, lambda: one_by_one(data_train, True))
+    elif world > 1:
+        train = _Loader(data_train, lambda: data_train.batches(args.train.batch_size, seed, rank, world, even=True))
+        train._len = lambda: len(epoch_plan(len(data_train), int(args.train.batch_size), rank, world, even=True))
     else:
         train = _Loader(data_train, lambda: data_train.batches(args.train.batch_size))
         train._len = lambda: -(-len(data_train) // int(args.train.batch_size))

@@ -15,6 +15,16 @@ sum_b F_b * (N // 2 + 1) cells that exist.  Nothing at or after sample (F_b - 1)
 (the kernels select), the gradient is exactly 0 from there on, and with every count equal to T value and gradient have the bits
 of the call without counts.  A scale at which no row has a frame raises ValueError before anything is launched.
 
+Additive: `forward(..., n_samples=, global_n_samples=)` on both classes - the rows are ONE RANK'S SHARE of a global batch
+(data-parallel training on ragged shards).  `global_n_samples` is a sequence of ints (or a CPU integer tensor) with the sample
+counts of every rank's rows, the local rows somewhere among them; every entry is positive and at least one global row has a
+frame at every drawn scale (ValueError before anything is launched otherwise).  The two denominators - the rows with a frame
+and the cells that exist - are taken over the global rows, the sums over the local ones: the value is this rank's share of the
+global loss and the gradient the gradient of that share.  Shares summed over the ranks give the one-process loss; gradients
+summed over the ranks, WITHOUT a division by the number of ranks, its gradient.  A rank whose own rows have no frame at some
+scale is allowed; its share at that scale is 0.  With `global_n_samples` equal to `n_samples` value and gradient have the bits
+of the call without it.  A rectangular local batch in a ragged global batch passes `n_samples=[T] * B`.
+
 Additive: `RSSLoss.rows(x_pred, x_true, n_samples)` -> (B,), one loss per row and no gradient (validation, where every
 utterance counts once): row b is what `forward` returns for `x[b:b+1, :n_samples[b]]` alone, both terms over the row's own
 cells, from the same kernels up to the per-row statistics.  Every row needs a frame at every drawn scale (ValueError before
@@ -28,11 +38,12 @@ import hipddsp
 
 class _SpectralLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_pred, x_true, n_ffts, alpha, eps, overlap=0, n_samples=None):
+    def forward(ctx, x_pred, x_true, n_ffts, alpha, eps, overlap=0, n_samples=None, global_n_samples=None):
         c = hipddsp.context_for(x_pred.device)
         need = x_pred.requires_grad
         hops = None if overlap == 0 else [_hop(n, overlap) for n in n_ffts]
-        loss, grad = c.rss_loss(x_pred, x_true, n_ffts, alpha, eps, want_grad=need, hops=hops, n_samples=n_samples)
+        loss, grad = c.rss_loss(x_pred, x_true, n_ffts, alpha, eps, want_grad=need, hops=hops, n_samples=n_samples,
+                                global_n_samples=global_n_samples)
         ctx.grad = grad
         return loss.reshape(())
 
@@ -40,7 +51,7 @@ class _SpectralLossFn(torch.autograd.Function):
     def backward(ctx, g):
         grad = ctx.grad
         ctx.grad = None
-        return (grad * g if grad is not None else None), None, None, None, None, None, None
+        return (grad * g if grad is not None else None), None, None, None, None, None, None, None
 
 
 def _hop(n_fft, overlap):
@@ -59,6 +70,15 @@ def _check(x_pred, x_true, overlap, n_samples=None):
     return hipddsp.check_n_samples(n_samples, x_pred.shape[0], x_pred.shape[1])
 
 
+def _check_global(n_samples, global_n_samples):
+    """-> `global_n_samples` as a checked list (None: the local rows are the whole batch)."""
+    if global_n_samples is None:
+        return None
+    if n_samples is None:
+        raise ValueError("global_n_samples= needs n_samples= (a rectangular local batch passes n_samples=[T] * B)")
+    return hipddsp.check_global_n_samples(global_n_samples, n_samples)
+
+
 def _need_device(x_pred):
     if not x_pred.is_cuda:
         raise RuntimeError("the spectral loss runs on a HIP device only (no CPU fallback)")
@@ -71,14 +91,16 @@ class SSSLoss(nn.Module):
         super().__init__()
         self.n_fft, self.alpha, self.overlap, self.eps = int(n_fft), alpha, overlap, eps
 
-    def forward(self, x_true, x_pred, n_samples=None):
-        """`n_samples`: rows of different length (module docstring)."""
+    def forward(self, x_true, x_pred, n_samples=None, global_n_samples=None):
+        """`n_samples`: rows of different length; `global_n_samples`: the rows are one rank's share of a global batch
+        (module docstring)."""
         n_samples = _check(x_pred, x_true, self.overlap, n_samples)
+        global_n_samples = _check_global(n_samples, global_n_samples)
         if n_samples is not None:
-            hipddsp.check_loss_scales(n_samples, [self.n_fft])
+            hipddsp.check_loss_scales(n_samples if global_n_samples is None else global_n_samples, [self.n_fft])
         _need_device(x_pred)
         return _SpectralLossFn.apply(x_pred, x_true.to(x_pred.dtype), [self.n_fft], self.alpha, self.eps, self.overlap,
-                                     n_samples)
+                                     n_samples, global_n_samples)
 
 
 class RSSLoss(nn.Module):
@@ -104,18 +126,21 @@ class RSSLoss(nn.Module):
         self.last_scales = n_ffts
         return n_ffts
 
-    def forward(self, x_pred, x_true, n_samples=None):
-        """`n_samples`: rows of different length (module docstring).  The scales are drawn (and a pinned draw is used up)
-        before the counts are checked against them."""
+    def forward(self, x_pred, x_true, n_samples=None, global_n_samples=None):
+        """`n_samples`: rows of different length; `global_n_samples`: the rows are one rank's share of a global batch
+        (module docstring).  The scales are drawn (and a pinned draw is used up) before the counts are checked against
+        them."""
         n_samples = _check(x_pred, x_true, self.overlap, n_samples)
+        global_n_samples = _check_global(n_samples, global_n_samples)
         if n_samples is None:
             _need_device(x_pred)
         n_ffts = self._draw()
         if n_samples is not None:
-            hipddsp.check_loss_scales(n_samples, n_ffts)
+            hipddsp.check_loss_scales(n_samples if global_n_samples is None else global_n_samples, n_ffts)
             _need_device(x_pred)
         # cached training audio may be fp16 (reference data_loaders.py:81-83): promote the target
-        return _SpectralLossFn.apply(x_pred, x_true.to(torch.float32), n_ffts, self.alpha, self.eps, self.overlap, n_samples)
+        return _SpectralLossFn.apply(x_pred, x_true.to(torch.float32), n_ffts, self.alpha, self.eps, self.overlap, n_samples,
+                                     global_n_samples)
 
     def rows(self, x_pred, x_true, n_samples):
         """One loss per row, (B,), without a gradient (module docstring).  The scales are drawn, or a pinned draw is used up,

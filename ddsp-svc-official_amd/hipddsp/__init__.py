@@ -5,6 +5,7 @@ current HIP stream.  There is NO CPU fallback: without the shared library or wit
 calls raise.
 """
 import ctypes
+import math as _math
 import numbers
 import os
 import threading
@@ -287,6 +288,9 @@ SIGNATURES = {
     "ddsp_ragged_frames_adjoint": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64]),
     "ddsp_rss_loss_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
                                     _int, _f32, _f32, _vp, _vp]),
+    "ddsp_rss_loss_share": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _i64, _c.POINTER(_int),
+                                   _c.POINTER(_int), _int, _f32, _f32, _vp, _vp]),
+    "ddsp_adamw_step_multi_scaled": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i64, _f32]),
     "ddsp_rss_loss_rows": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
                                   _int, _f32, _f32, _vp]),
     "ddsp_vc_f0_map": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
@@ -405,6 +409,43 @@ def check_loss_scales(n_samples, n_ffts):
         if max(n_samples) < int(n):
             raise ValueError(f"n_samples: no row holds a whole frame at scale n_fft = {int(n)} (longest row: {max(n_samples)} "
                              "samples)")
+
+
+def loss_norms(n_samples, n_ffts, hops=None):
+    """The spectral loss's two denominators per scale over rows of `n_samples` samples: [(cells, rows_ne)], cells = sum_b F_b *
+    (n_fft // 2 + 1) with F_b = (n_b - n_fft) // hop + 1 frames (0 for a row shorter than n_fft), rows_ne the rows with a frame.
+    hops: one hop per scale (default: hop = n_fft).  What `ddsp_rss_loss_ragged` forms from the local rows and
+    `ddsp_rss_loss_share` from the rows of the global batch."""
+    hops = [int(n) for n in n_ffts] if hops is None else [int(h) for h in hops]
+    out = []
+    for n_fft, hop in zip((int(n) for n in n_ffts), hops):
+        frames = [(int(n) - n_fft) // hop + 1 for n in n_samples if int(n) >= n_fft]
+        out.append((sum(frames) * (n_fft // 2 + 1), len(frames)))
+    return out
+
+
+def check_global_n_samples(global_n_samples, n_samples):
+    """The sample counts of every rank's rows (`RSSLoss.forward(..., global_n_samples=)`) as a list of Python ints: a sequence
+    of ints or a CPU integer tensor, every entry positive, the local rows `n_samples` (a checked list) among them (as a
+    multiset; a global row may be longer than the local padded length).  ValueError otherwise, a host check."""
+    if isinstance(global_n_samples, torch.Tensor):
+        n = global_n_samples.numel() if global_n_samples.dim() == 1 else -1
+    else:
+        try:
+            global_n_samples = list(global_n_samples)
+        except TypeError:
+            raise ValueError("global_n_samples must be a sequence of ints or a CPU integer tensor") from None
+        n = len(global_n_samples)
+    vals = _check_counts("global_n_samples", global_n_samples, n)
+    for b, v in enumerate(vals):
+        if v < 1:
+            raise ValueError(f"global_n_samples[{b}] = {v} must be positive")
+    left = list(vals)
+    for b, v in enumerate(n_samples):
+        if v not in left:
+            raise ValueError(f"n_samples[{b}] = {v} is not among global_n_samples: the global batch holds every rank's rows")
+        left.remove(v)
+    return vals
 
 
 # `check_n_samples` with each analyser's rule applied
@@ -1129,9 +1170,12 @@ class Context:
         self.call("ddsp_adamw_step", _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr),
                   float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
 
-    def adamw_step_multi(self, params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2, eps, weight_decay, step):
+    def adamw_step_multi(self, params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
         """One AdamW update of a whole list of parameter tensors (shared hyper-parameters and step): the pointer
-        tables go to the library as host arrays, the library issues one launch per 24 tensors."""
+        tables go to the library as host arrays, the library issues one launch per 24 tensors.  grad_scale: every gradient is
+        multiplied by it as it is read (`ddsp_adamw_step_multi_scaled`); 1.0 calls `ddsp_adamw_step_multi`."""
+        if not _math.isfinite(float(grad_scale)):
+            raise ValueError("adamw_step_multi: grad_scale must be finite")
         n = len(params)
         if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n):
             raise ValueError("adamw_step_multi: lists of different length")
@@ -1143,8 +1187,12 @@ class Context:
                 raise ValueError("adamw_step_multi: a tensor and its state differ in size")
         arr = lambda ts: (_vp * n)(*[_ptr(t) for t in ts])
         numel = (_i64 * n)(*[p.numel() for p in params])
-        self.call("ddsp_adamw_step_multi", n, arr(params), arr(grads), arr(exp_avgs), arr(exp_avg_sqs), numel, float(lr),
-                  float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
+        common = (n, arr(params), arr(grads), arr(exp_avgs), arr(exp_avg_sqs), numel, float(lr), float(beta1), float(beta2),
+                  float(eps), float(weight_decay), int(step))
+        if float(grad_scale) == 1.0:
+            self.call("ddsp_adamw_step_multi", *common)
+        else:
+            self.call("ddsp_adamw_step_multi_scaled", *common, float(grad_scale))
 
     # -- building block ------------------------------------------------------------------------
     def gemm(self, A, B, bias=None, a_k_contig=True, b_k_contig=True, tile=0, variant=0, out=None):
@@ -1398,11 +1446,14 @@ class Context:
         return d_ctrl
 
     # -- a13 -----------------------------------------------------------------------------------
-    def rss_loss(self, x_pred, x_true, n_ffts, alpha=1.0, eps=1e-7, want_grad=False, hops=None, n_samples=None, rows=False):
+    def rss_loss(self, x_pred, x_true, n_ffts, alpha=1.0, eps=1e-7, want_grad=False, hops=None, n_samples=None, rows=False,
+                 global_n_samples=None):
         """-> (loss (1,) device tensor, d loss/d x_pred (B,T) | None) for the given list of scales; `hops`: one hop per
         scale (default: hop = n_fft, the reference's overlap = 0).  `n_samples`: the list `check_n_samples` returned -
         rows of different length (include/ddsp_amd.h: ddsp_rss_loss_ragged).  `rows` (with `n_samples`, without `want_grad`):
-        -> (loss per row (B,), None), every row scored alone (ddsp_rss_loss_rows)."""
+        -> (loss per row (B,), None), every row scored alone (ddsp_rss_loss_rows).  `global_n_samples` (with `n_samples`,
+        without `rows`): the list `check_global_n_samples` returned - the rows are one rank's share of that global batch
+        (ddsp_rss_loss_share)."""
         xp = x_pred.detach().contiguous().float()
         xt = x_true.detach().contiguous().float()
         B, T = xp.shape
@@ -1412,6 +1463,8 @@ class Context:
             raise ValueError("signal length must be a multiple of 4")
         if rows and (n_samples is None or want_grad):
             raise ValueError("rss_loss: rows=True takes n_samples and has no gradient")
+        if global_n_samples is not None and (n_samples is None or rows):
+            raise ValueError("rss_loss: global_n_samples takes n_samples and not rows=True")
         arr = (_int * len(n_ffts))(*[int(n) for n in n_ffts])
         if hops is not None and len(hops) != len(n_ffts):
             raise ValueError("one hop per scale")
@@ -1424,6 +1477,9 @@ class Context:
                       float(eps), _ptr(loss))
             if rows:
                 self.call("ddsp_rss_loss_rows", *common)
+            elif global_n_samples is not None:
+                gns = (_int * len(global_n_samples))(*global_n_samples)
+                self.call("ddsp_rss_loss_share", *common[:6], gns, len(global_n_samples), *common[6:], _ptr(grad))
             else:
                 self.call("ddsp_rss_loss_ragged", *common, _ptr(grad))
         else:

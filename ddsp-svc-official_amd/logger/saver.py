@@ -2,7 +2,10 @@
 `ddsp.vocoder.load_model` reads next to a checkpoint), `log_info.txt`, TensorBoard events under `logs/` and the checkpoints.
 
 TensorBoard is optional: without `torch.utils.tensorboard` scalars go to the log file only and audio is skipped, with one
-notice."""
+notice.
+
+Data parallel: `Saver(args, step, rank=r)` with r != 0 counts steps and time like rank 0 but writes NOTHING - no directory, no
+`config.yaml`, no log file, no TensorBoard events, no checkpoint - and prints nothing: one rank owns the experiment directory."""
 import datetime
 import os
 import time
@@ -21,11 +24,15 @@ def _plain(obj):
 
 
 class Saver(object):
-    def __init__(self, args, initial_global_step=-1):
+    def __init__(self, args, initial_global_step=-1, rank=0):
         self.expdir = args.env.expdir
         self.sample_rate = args.data.sampling_rate
         self.global_step = initial_global_step
         self.init_time = self.last_time = time.time()
+        self.writes = int(rank) == 0
+        self.writer = None
+        if not self.writes:
+            return
         os.makedirs(self.expdir, exist_ok=True)
         self.path_log_info = os.path.join(self.expdir, "log_info.txt")
         try:
@@ -41,13 +48,15 @@ class Saver(object):
         """A message, or a dict as `key: value` lines (ints with thousands separators), to stdout and `log_info.txt`."""
         if isinstance(msg, dict):
             msg = "\n".join(f"{k}: {v:,}" if isinstance(v, int) else f"{k}: {v}" for k, v in msg.items())
+        if not self.writes:
+            return
         print(msg)
         with open(self.path_log_info, "a") as fh:
             fh.write(msg + "\n")
 
     def log_value(self, dict):
         """Scalars at the current step: TensorBoard, or the log file without it."""
-        for k, v in dict.items():
+        for k, v in dict.items() if self.writes else ():
             if self.writer is not None:
                 self.writer.add_scalar(k, v, self.global_step)
             else:
@@ -72,7 +81,9 @@ class Saver(object):
         return str(datetime.timedelta(seconds=time.time() - self.init_time))[:-5]
 
     def save_model(self, model, optimizer, name="model", postfix=""):
-        """`<expdir>/<name>_<postfix>.pt` = {global_step, model: state_dict, optimizer: state_dict}."""
+        """`<expdir>/<name>_<postfix>.pt` = {global_step, model: state_dict, optimizer: state_dict} (rank 0 only)."""
+        if not self.writes:
+            return
         path_pt = os.path.join(self.expdir, f"{name}_{postfix}.pt")
         print(f" [*] model checkpoint saved: {path_pt}")
         torch.save({"global_step": self.global_step, "model": model.state_dict(), "optimizer": optimizer.state_dict()}, path_pt)

@@ -13,7 +13,15 @@ and their mean - every file counts once, the reference's `test_loss` - is return
 
 One divergence: the reference draws the loss's scales per FILE; here a draw serves a GROUP (all its rows are scored in one
 call), or, with `scales=`, one pinned draw serves the whole pass.  Pinning is the recommended use: the validation losses of
-different steps are then measured with the same yardstick and become comparable (`args.loss.val_scales` in the config)."""
+different steps are then measured with the same yardstick and become comparable (`args.loss.val_scales` in the config).
+
+Data parallel (`ranks=`, default `training.Ranks.current()`: the process group `train.py` initialised, or one process).  A
+training step all-reduces the summed gradient bucket and nothing else; the loss's scales and the noise seed of a step are pure
+functions of (`train.seed`, step[, rank]).  The global loss is formed (`training.global_loss`, one scalar all_reduce) on the
+steps that log, so a step that does not log synchronises with the host on no rank.  Validation deals the global groups to the
+ranks round robin, every rank scores its groups, the per-file losses are gathered once per pass and every rank returns the same
+mean over the files; the scales must be pinned (a draw would differ per group).  Rank 0 alone logs and writes checkpoints - the
+others wait at a barrier - and its "best" decision is broadcast so that every rank takes the same branch."""
 import time
 
 import numpy as np
@@ -21,7 +29,7 @@ import torch
 
 import hipddsp
 from logger.saver import Saver
-from training import GradBucket, train_step
+from training import GradBucket, Ranks, global_loss, step_noise_seed, step_scales, train_step
 
 VAL_BATCH_FRAMES = 8192     # padded frames of a validation group when nothing else is asked for (the forward sees twice that)
 
@@ -57,7 +65,7 @@ def check_validation_files(names, frames, hop, fft_max, spk_ids=None, table=None
                                      "writes it from the training set)")
 
 
-def validate(args, model, loss_func, dataset, saver=None, batch_frames=None, scales=None, noise=None, details=None):
+def validate(args, model, loss_func, dataset, saver=None, batch_frames=None, scales=None, noise=None, details=None, ranks=None):
     """The reference's `test` over `dataset` (a whole-audio `AudioDataset`) -> the mean of the per-file losses (module
     docstring).  batch_frames: a group's padded size in frames (default VAL_BATCH_FRAMES).  scales: one pinned draw of the
     loss's scales for the whole pass (default None: a fresh draw per group; the reference draws per file).  noise: {file
@@ -65,13 +73,17 @@ def validate(args, model, loss_func, dataset, saver=None, batch_frames=None, sca
     `noise=` on the synthesisers).  details: a dict that receives `names`, `losses` (float64 numpy, per file in that order),
     `rtf`.  With a `saver`, the ground truth, the reconstruction and the conversion of every file are logged under the
     reference's tags.  RTF is the wall time of the whole pass (gather, both legs, loss; one synchronisation at its end) over
-    the duration of the audio."""
+    the duration of the audio.  ranks: module docstring; `details` then holds every rank's files, in gathered order."""
+    ranks = Ranks.current() if ranks is None else ranks
+    if ranks.world > 1 and scales is None:
+        raise ValueError("validate: data-parallel validation needs pinned scales (loss.val_scales): a draw would differ per group")
     hop = dataset.hop_size
     check_validation_files(dataset.paths, dataset.whole, hop, loss_func.fft_max)
     lfo_stats = np.load(f"{args.data.train_path}/f0_stats.npy", allow_pickle=True).item()
     table = lfo_table(lfo_stats, args.model.n_spk)
     check_validation_files(dataset.paths, dataset.whole, hop, loss_func.fft_max, dataset.spk_ids, table)
-    print(f" [*] validating {len(dataset.paths)} files...")
+    if ranks.rank == 0:
+        print(f" [*] validating {len(dataset.paths)} files...")
     model.eval()
     ctx = hipddsp.context_for(dataset.device)
     lfo = torch.from_numpy(table).to(dataset.device)
@@ -79,7 +91,8 @@ def validate(args, model, loss_func, dataset, saver=None, batch_frames=None, sca
     names, losses, frames = [], [], 0
     st_time = time.time()
     with torch.no_grad():
-        for batch in dataset.whole_batches(VAL_BATCH_FRAMES if batch_frames is None else batch_frames):
+        groups = dataset.whole_groups(VAL_BATCH_FRAMES if batch_frames is None else batch_frames)
+        for batch in (dataset.whole_batch(g) for g in groups[ranks.rank::ranks.world]):
             n, group = batch["n_frames"], batch["name"]
             B = len(n)
             f0_vc, tgt = ctx.vc_f0_map(batch["f0"], batch["spk_id"], lfo, ctx.ragged_counts(n))
@@ -103,6 +116,8 @@ def validate(args, model, loss_func, dataset, saver=None, batch_frames=None, sca
                     end = n[b] * hop
                     saver.log_audio({fn + "/gt.wav": batch["audio"][b:b + 1, :end], fn + "/pred.wav": signal[b:b + 1, :end],
                                      f"{fn}/vc_{src}_to_{target_speaker(src, args.model.n_spk)}.wav": signal[B + b:B + b + 1, :end]})
+        if ranks.world > 1:
+            names, losses, frames = _gather_files(losses, groups, dataset, ranks)
         per_file = torch.cat(losses).cpu()              # the pass's one read-back: it waits for every group
     run_time = time.time() - st_time
     ctx.poll_error()
@@ -111,50 +126,95 @@ def validate(args, model, loss_func, dataset, saver=None, batch_frames=None, sca
     rtf = run_time / (frames * hop / args.data.sampling_rate)
     if details is not None:
         details.update(names=names, losses=per_file, rtf=rtf)
-    print(f" [*] validation loss {test_loss} | RTF {rtf} ({run_time} s for {frames * hop / args.data.sampling_rate} s of audio)")
+    if ranks.rank == 0:
+        print(f" [*] validation loss {test_loss} | RTF {rtf} ({run_time} s for {frames * hop / args.data.sampling_rate} s of audio)")
     return test_loss
 
 
-def test(args, model, loss_func, loader_test, saver):
+def _gather_files(losses, groups, dataset, ranks):
+    """The pass's one exchange: every rank's per-file losses in a slot of len(dataset) floats (all_gather), cut by the file
+    counts the round-robin deal gives each rank - a pure function of the lengths, so nothing but the losses travels."""
+    import torch.distributed as dist
+    mine = torch.cat(losses) if losses else torch.zeros(0, device=dataset.device)
+    slot = torch.zeros(len(dataset.paths), device=dataset.device)
+    slot[:mine.numel()] = mine
+    out = torch.empty(ranks.world * slot.numel(), device=dataset.device)
+    dist.all_gather_into_tensor(out, slot)
+    all_names, all_losses = [], []
+    for r in range(ranks.world):
+        files = [i for g in groups[r::ranks.world] for i in g]
+        all_names += [dataset.paths[i] for i in files]
+        all_losses.append(out[r * slot.numel():r * slot.numel() + len(files)])
+    return all_names, all_losses, sum(dataset.whole)
+
+
+def test(args, model, loss_func, loader_test, saver, ranks=None):
     """The reference's signature: `loader_test` is `get_data_loaders`' validation loader (its `.dataset` is walked in ragged
     groups).  `args.train.val_batch_frames` and `args.loss.val_scales` (both optional in the YAML) set the group size and
     pin the scales."""
     return validate(args, model, loss_func, loader_test.dataset, saver, batch_frames=args.train.val_batch_frames,
-                    scales=args.loss.val_scales)
+                    scales=args.loss.val_scales, ranks=ranks)
 
 
-def train(args, initial_global_step, model, optimizer, loss_func, loader_train, loader_test, max_steps=None, scales=None):
+def train(args, initial_global_step, model, optimizer, loss_func, loader_train, loader_test, max_steps=None, scales=None,
+          ranks=None):
     """The reference's loop (`solver.py:85-143`): a step per batch of `loader_train` for `args.train.epochs` epochs, a log line
     every `interval_log` steps, and every `interval_val` steps a validation, the checkpoint of that step and, if the validation
     loss improved, `model_best.pt`.  max_steps: return after that many steps of this call.  scales: pin the training loss's
-    draw (tests; default: drawn per step as the reference does)."""
-    saver = Saver(args, initial_global_step=initial_global_step)
+    draw (tests; default: drawn per step as the reference does - under data parallelism by `training.step_scales`).
+    ranks: module docstring."""
+    ranks = Ranks.current() if ranks is None else ranks
+    world = ranks.world
+    if world > 1 and not args.loss.val_scales:
+        raise ValueError("train: data-parallel training needs loss.val_scales (validation's pinned scales) in the config")
+    seed = int(args.train.seed or 0)
+    saver = Saver(args, initial_global_step=initial_global_step, rank=ranks.rank)
     bucket = GradBucket(model.parameters(), model)
     best_loss = np.inf
     num_batches = len(loader_train)
     model.train()
     done = 0
-    saver.log_info(f"training from step {initial_global_step}")
+    saver.log_info(f"training from step {initial_global_step}" + (f" on {world} ranks" if world > 1 else ""))
     for epoch in range(args.train.epochs):
         for batch_idx, data in enumerate(loader_train):
             saver.global_step_increment()
-            loss = train_step(model, optimizer, loss_func, data, scales=scales, bucket=bucket)
+            step_scale = scales
+            if world > 1:
+                if "noise" not in data:
+                    data["noise_seed"] = step_noise_seed(seed, saver.global_step, ranks.rank)
+                if scales is None:
+                    step_scale = step_scales(seed, saver.global_step, loss_func.fft_min, loss_func.fft_max, loss_func.n_scale)
+            loss = train_step(model, optimizer, loss_func, data, world=world, scales=step_scale, bucket=bucket)
             if saver.global_step % args.train.interval_log == 0:
-                value = loss.item()                     # the only read-back of a training step, and only when it is logged
+                # the only read-back of a training step, and only when it is logged (with it, the one scalar all_reduce)
+                value = global_loss(loss, world, shares="global_n_frames" in data).item()
                 saver.log_info(f"step {saver.global_step} | epoch {epoch} batch {batch_idx}/{num_batches} | {args.env.expdir} | "
                                f"{args.train.interval_log / saver.get_interval_time():.2f} batch/s | loss {value:.3f} | "
                                f"{saver.get_total_time()}")
                 saver.log_value({"train/loss": value})
             if saver.global_step % args.train.interval_val == 0:
-                test_loss = test(args, model, loss_func, loader_test, saver)
+                test_loss = test(args, model, loss_func, loader_test, saver if ranks.rank == 0 else None, ranks=ranks)
                 saver.log_info(f"step {saver.global_step} | validation loss {test_loss:.3f}")
                 saver.log_value({"validation/loss": test_loss})
                 saver.save_model(model, optimizer, postfix=f"{saver.global_step}")
-                if test_loss < best_loss:
+                if _rank0_decides(test_loss < best_loss, ranks):
                     saver.log_info(f"step {saver.global_step} | best validation loss so far: model_best.pt updated")
                     saver.save_model(model, optimizer, postfix="best")
                     best_loss = test_loss
+                if world > 1:
+                    import torch.distributed as dist
+                    dist.barrier()                      # the others wait here while rank 0 writes
                 model.train()
             done += 1
             if max_steps is not None and done >= max_steps:
                 return
+
+
+def _rank0_decides(flag, ranks):
+    """`flag` as rank 0 sees it, on every rank (one broadcast of a byte; one process: `flag`)."""
+    if ranks.world == 1:
+        return bool(flag)
+    import torch.distributed as dist
+    box = [bool(flag)]
+    dist.broadcast_object_list(box, src=0)
+    return box[0]

@@ -389,6 +389,18 @@ int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float*
 int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
                          const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host, const int* hops_host,
                          int n_scale, float alpha, float eps, float* loss, float* grad_pred);
+/* The rows as ONE RANK'S SHARE of a global batch (data-parallel training on ragged shards): the arguments of
+ * ddsp_rss_loss_ragged plus global_n_samples_host, the n_global >= B sample counts (each >= 1; they may exceed T, another rank
+ * pads to its own longest row) of every rank's rows, the local rows among them.  Both denominators - the rows with a frame and the
+ * cells that exist at scale N - are taken over the GLOBAL counts, the sums over the local rows: loss is this rank's share of the
+ * loss of the global batch and grad_pred the gradient of that share.  Shares summed over the ranks give the one-process loss;
+ * gradients summed over the ranks (no division by the number of ranks) its gradient.  A scale at which no GLOBAL row has a frame:
+ * DDSP_ERR_ARG before anything is launched.  A scale at which no LOCAL row has a frame (n_fft > T included) contributes 0 and is
+ * not launched.  With global_n_samples_host equal to n_samples_host the result has the bits of ddsp_rss_loss_ragged. */
+int ddsp_rss_loss_share(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                        const int* n_samples_host, const int32_t* n_samples_dev, const int* global_n_samples_host,
+                        int64_t n_global, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps,
+                        float* loss, float* grad_pred);
 /* One loss per row instead of the batch's scalar (validation: every utterance counts once; no gradient): the arguments of
  * ddsp_rss_loss_ragged, loss_rows a device float[B].  loss_rows[b] = mean_N (||S_t - S_p||_F / ||S_t + S_p||_F +
  * alpha * mean|ln S_t - ln S_p|), both terms over row b's own F_b * (N/2 + 1) cells - the loss of x[b][0..n_b) scored alone.
@@ -670,6 +682,11 @@ int ddsp_adamw_step(ddsp_ctx* ctx, void* stream, float* param, const float* grad
 int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params, const float* const* grads,
                           float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel, float lr,
                           float beta1, float beta2, float eps, float weight_decay, int64_t step);
+/* the same launches with every gradient multiplied by grad_scale (finite) as it is read: the 1 / world of a data-parallel mean
+ * applied to a bucket that holds the SUM over the ranks, without a pass of its own over the gradients.  grads are not written. */
+int ddsp_adamw_step_multi_scaled(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params, const float* const* grads,
+                                 float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale);
 
 /* ---- building block: fp32-in / fp32-accumulate MFMA GEMM ---------------------------------------- */
 /* C[m][n] = sum_k A(m,k) B(k,n) (+ bias[n]).  a_k_contig: A(m,k) = A[m*lda+k] else A[k*lda+m];
