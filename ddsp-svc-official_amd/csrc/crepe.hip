@@ -242,7 +242,7 @@ __device__ __forceinline__ void argmax_merge(double& v, int& i, double v2, int i
     }
 }
 
-// The dither seed of ddsp_crepe_decode_dseed moves to its successor (one 64-bit LCG step, Knuth's MMIX constants: full
+// The dither seed of ddsp_crepe_decode (seed_dev) moves to its successor (one 64-bit LCG step, Knuth's MMIX constants: full
 // period, both 32-bit halves change from call to call).  One thread, enqueued behind the decode that read the word.
 __global__ void seed_advance_kernel(uint64_t* __restrict__ seed) {
     *seed = *seed * 6364136223846793005ull + 1442695040888963407ull;
@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(VT) viterbi_kernel(const float* __restrict__ l
         Frb = nb < Fr ? nb : Fr;
         if (t0 >= Frb) return;
     }
-    // the dither seed: the argument, or (ddsp_crepe_decode_dseed) the device word a captured graph re-reads on every replay
+    // the dither seed: the argument, or (seed_dev) the device word a captured graph re-reads on every replay
     const uint64_t seed = seed_dev ? *seed_dev : seed_arg;
     __shared__ double band[BINS * BAND];        // logT[j + d - 11][j] at [j * 23 + d]; reused for back-pointer rows
     __shared__ double val[2][BINS];
@@ -609,10 +609,10 @@ void conv_gemm(hipStream_t st, gemm::Args g, const Epi& e) {
     }
 }
 
-// n16 / prefix / n_packed: a ragged batch (ddsp_crepe_activations_ragged) - the network runs over the n_packed real frames
-// of all rows, in passes that may hold frames of several rows; nullptr: the B * Fr frames of a rectangular batch.
+// n16 / prefix / n_packed: a ragged batch - the network runs over the n_packed real frames of all rows, in passes that may
+// hold frames of several rows; nullptr: the B * Fr frames of a rectangular batch.
 int crepe_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_crepe_weights* wp, const float* audio, int64_t B, int64_t T, int hop,
-              float* probs, const int32_t* n16 = nullptr, const int32_t* prefix = nullptr, int64_t n_packed = 0) {
+              float* probs, const int32_t* n16, const int32_t* prefix, int64_t n_packed) {
     DDSP_REQUIRE(ctx, ctx && wp && audio && probs, "ddsp_crepe_activations: null argument");
     DDSP_REQUIRE(ctx, weights_complete(*wp), "ddsp_crepe_activations: a weight pointer is null or not 16-byte aligned, or a width is not a multiple of 16");
     DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && hop >= 1, "ddsp_crepe_activations: bad shape");
@@ -726,23 +726,25 @@ extern "C" int64_t ddsp_crepe_frames(int64_t T16, int hop) {
     return 1 + T16 / hop;
 }
 
+// n_samples, frame_prefix and n_packed: all three (a ragged batch) or none (n_packed is then not read)
 extern "C" int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16, int64_t B,
-                                      int64_t T, int hop, float* probs) {
-    return crepe_run(ctx, (hipStream_t)stream, w, audio16, B, T, hop, probs);
-}
-
-extern "C" int ddsp_crepe_activations_ragged(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16,
-                                             int64_t B, int64_t T, const int32_t* n_samples, const int32_t* frame_prefix,
-                                             int64_t n_packed, int hop, float* probs) {
-    DDSP_REQUIRE(ctx, ctx && n_samples && frame_prefix, "ddsp_crepe_activations_ragged: null argument");
-    DDSP_REQUIRE(ctx, B >= 1 && B < ((int64_t)1 << 31) && hop >= 1 && T >= 0 && n_packed >= B && n_packed <= B * (1 + T / hop),
-                 "ddsp_crepe_activations_ragged: n_packed must lie in B..B * frames(T)");
+                                      int64_t T, const int32_t* n_samples, const int32_t* frame_prefix, int64_t n_packed, int hop,
+                                      float* probs) {
+    DDSP_REQUIRE(ctx, ctx && !n_samples == !frame_prefix,
+                 "ddsp_crepe_activations: n_samples and frame_prefix are given together or not at all");
+    DDSP_REQUIRE(ctx, !n_samples || (B >= 1 && B < ((int64_t)1 << 31) && hop >= 1 && T >= 0 && n_packed >= B &&
+                                     n_packed <= B * (1 + T / hop)),
+                 "ddsp_crepe_activations: n_packed must lie in B..B * frames(T)");
     return crepe_run(ctx, (hipStream_t)stream, w, audio16, B, T, hop, probs, n_samples, frame_prefix, n_packed);
 }
 
-static int crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
-                        int64_t segment, uint64_t dither_seed, uint64_t* seed_dev, int use_dither, float* f0, float* periodicity,
-                        int32_t* bins, const int32_t* n_frames = nullptr) {
+// n_frames: the rows' own frame counts, or null; seed_dev: the dither seed in device memory, or null (dither_seed by value)
+extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                 float fmin, float fmax, int64_t segment, uint64_t dither_seed, uint64_t* seed_dev, int use_dither,
+                                 float* f0, float* periodicity, int32_t* bins) {
+    DDSP_REQUIRE(ctx, ctx && ((uintptr_t)seed_dev & 7) == 0, "ddsp_crepe_decode: seed_dev not 8-byte aligned");
+    DDSP_REQUIRE(ctx, !(seed_dev && n_frames), "ddsp_crepe_decode: seed_dev is not available with n_frames (a ragged batch)");
+    if (seed_dev) dither_seed = 0;   // (not read by the kernels then)
     DDSP_REQUIRE(ctx, ctx && probs && f0 && periodicity, "ddsp_crepe_decode: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && Fr >= 1 && B * Fr < ((int64_t)1 << 31) / BINS, "ddsp_crepe_decode: bad shape");
     DDSP_REQUIRE(ctx, fmin > 0.f && fmax > 0.f && isfinite(fmin) && isfinite(fmax), "ddsp_crepe_decode: fmin, fmax > 0");
@@ -771,30 +773,12 @@ static int crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t
     return DDSP_OK;
 }
 
-extern "C" int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
-                                 int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity,
-                                 int32_t* bins) {
-    return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, dither_seed, nullptr, use_dither, f0, periodicity, bins);
-}
-
-extern "C" int ddsp_crepe_decode_ragged(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr,
-                                        const int32_t* n_frames, float fmin, float fmax, int64_t segment, uint64_t dither_seed,
-                                        int use_dither, float* f0, float* periodicity, int32_t* bins) {
-    DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_crepe_decode_ragged: null argument");
-    return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, dither_seed, nullptr, use_dither, f0, periodicity, bins,
-                        n_frames);
-}
-
-extern "C" int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin,
-                                       float fmax, int64_t segment, uint64_t* seed_dev, int use_dither, float* f0,
-                                       float* periodicity, int32_t* bins) {
-    DDSP_REQUIRE(ctx, ctx && seed_dev && ((uintptr_t)seed_dev & 7) == 0, "ddsp_crepe_decode_dseed: seed_dev null or not 8-byte aligned");
-    return crepe_decode(ctx, stream, probs, B, Fr, fmin, fmax, segment, 0, seed_dev, use_dither, f0, periodicity, bins);
-}
-
-static int f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr, double hop,
-                         int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min, float* out,
-                         const int32_t* n_crepe, const int32_t* n_out) {
+// n_crepe and n_out: both (a ragged batch, start_frame = 0) or neither
+extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr,
+                                  const int32_t* n_crepe, int sr, double hop, int64_t n_frames, int64_t start_frame,
+                                  const int32_t* n_out, float threshold, int uv_interp, float f0_min, float* out) {
+    DDSP_REQUIRE(ctx, ctx && !n_crepe == !n_out, "ddsp_f0_postfilter: n_crepe and n_out are given together or not at all");
+    DDSP_REQUIRE(ctx, !n_crepe || start_frame == 0, "ddsp_f0_postfilter: start_frame must be 0 with n_crepe / n_out (a ragged batch)");
     DDSP_REQUIRE(ctx, ctx && f0 && pd && out, "ddsp_f0_postfilter: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B < 65536 && Fr >= 3, "ddsp_f0_postfilter: B >= 1 and at least 3 frames (the reflect padding)");
     DDSP_REQUIRE(ctx, sr > 0 && hop > 0.0 && isfinite(hop), "ddsp_f0_postfilter: sr, hop > 0");
@@ -811,18 +795,4 @@ static int f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const flo
                        uv_interp ? 1 : 0, f0_min, (float*)arena, out, n_crepe, n_out);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-extern "C" int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr,
-                                  double hop, int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min,
-                                  float* out) {
-    return f0_postfilter(ctx, stream, f0, pd, B, Fr, sr, hop, n_frames, start_frame, threshold, uv_interp, f0_min, out, nullptr,
-                         nullptr);
-}
-
-extern "C" int ddsp_f0_postfilter_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr,
-                                         const int32_t* n_crepe, int sr, double hop, int64_t n_frames, const int32_t* n_out,
-                                         float threshold, int uv_interp, float f0_min, float* out) {
-    DDSP_REQUIRE(ctx, ctx && n_crepe && n_out, "ddsp_f0_postfilter_ragged: null argument");
-    return f0_postfilter(ctx, stream, f0, pd, B, Fr, sr, hop, n_frames, 0, threshold, uv_interp, f0_min, out, n_crepe, n_out);
 }

@@ -647,8 +647,19 @@ int get_table(ddsp_ctx* ctx, hipStream_t st, const Geo& g, float** out) {
     return DDSP_OK;
 }
 
-int f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int sr, double hop,
-          double f0_min, double f0_max, int64_t n_frames, int64_t start_frame, int uv_interp, float* out, int32_t* choice) {
+}  // namespace
+
+extern "C" int64_t ddsp_f0_ac_frames(int64_t T, int sr, double hop, double f0_min) {
+    if (T < 0 || sr < 1 || !(hop > 0.0) || !(f0_min > 0.0)) return -1;
+    const int64_t n = row_frames(T, 1.0 / sr, hop / sr, 3.0 / f0_min);
+    return n < 0 ? 0 : n;
+}
+
+// n_samples == nullptr: every row holds T samples; with counts start_frame is 0
+extern "C" int ddsp_f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int sr,
+                          double hop, double f0_min, double f0_max, int64_t n_frames, int64_t start_frame, int uv_interp, float* out,
+                          int32_t* choice) {
+    DDSP_REQUIRE(ctx, ctx && (!n_samples || start_frame == 0), "ddsp_f0_ac: start_frame must be 0 with n_samples (a ragged batch)");
     DDSP_REQUIRE(ctx, ctx && audio && out, "ddsp_f0_ac: null argument");
     Geo g;
     DDSP_REQUIRE(ctx, make_geo(sr, hop, f0_min, f0_max, g),
@@ -686,24 +697,4 @@ int f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
                        start_frame, uv_interp ? 1 : 0, out, choice);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t ddsp_f0_ac_frames(int64_t T, int sr, double hop, double f0_min) {
-    if (T < 0 || sr < 1 || !(hop > 0.0) || !(f0_min > 0.0)) return -1;
-    const int64_t n = row_frames(T, 1.0 / sr, hop / sr, 3.0 / f0_min);
-    return n < 0 ? 0 : n;
-}
-
-extern "C" int ddsp_f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int sr, double hop, double f0_min,
-                          double f0_max, int64_t n_frames, int64_t start_frame, int uv_interp, float* out, int32_t* choice) {
-    return f0_ac(ctx, stream, audio, B, T, nullptr, sr, hop, f0_min, f0_max, n_frames, start_frame, uv_interp, out, choice);
-}
-
-extern "C" int ddsp_f0_ac_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
-                                 int sr, double hop, double f0_min, double f0_max, int64_t n_frames, int uv_interp, float* out,
-                                 int32_t* choice) {
-    DDSP_REQUIRE(ctx, ctx && n_samples, "ddsp_f0_ac_ragged: null argument");
-    return f0_ac(ctx, stream, audio, B, T, n_samples, sr, hop, f0_min, f0_max, n_frames, 0, uv_interp, out, choice);
 }

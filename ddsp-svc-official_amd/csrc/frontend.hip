@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(256) retime_f0_kernel(const float* __restrict_
 
 }  // namespace
 
-// both retime entry points: ns == nd == nullptr is the solo call (B = 1, every knot and target)
+// ddsp_retime_f0 and its keyed form: ns == nd == nullptr is one track (B = 1, every knot and target)
 static int retime_f0_go(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* ns, double step_num,
                         double div, float scale, double step_dst, int64_t n_dst, const int32_t* nd, float* out,
                         const int32_t* key = nullptr, const double* div_tab = nullptr, const float* scale_tab = nullptr,
@@ -155,16 +155,12 @@ static int retime_f0_go(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B,
     return DDSP_OK;
 }
 
-extern "C" int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, double step_num, double div,
-                              float scale, double step_dst, int64_t n_dst, float* out) {
-    return retime_f0_go(ctx, stream, f0, 1, n_src, nullptr, step_num, div, scale, step_dst, n_dst, nullptr, out);
-}
-
-extern "C" int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
-                                     double step_num, double div, float scale, double step_dst, int64_t n_dst,
-                                     const int32_t* n_dst_rows, float* out) {
-    DDSP_REQUIRE(ctx, ctx && n_src_rows && n_dst_rows, "ddsp_retime_f0_ragged: null argument");
-    DDSP_REQUIRE(ctx, n_dst >= 1, "ddsp_retime_f0_ragged: bad shape or step");
+extern "C" int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
+                              double step_num, double div, float scale, double step_dst, int64_t n_dst, const int32_t* n_dst_rows,
+                              float* out) {
+    DDSP_REQUIRE(ctx, ctx && !n_src_rows == !n_dst_rows, "ddsp_retime_f0: n_src_rows and n_dst_rows are given together or not at all");
+    // (the kernel finds a row by its counts: without them there is one track)
+    DDSP_REQUIRE(ctx, n_src_rows ? n_dst >= 1 : B == 1, "ddsp_retime_f0: a batch needs n_dst >= 1 and its counts, one track B = 1");
     return retime_f0_go(ctx, stream, f0, B, n_src, n_src_rows, step_num, div, scale, step_dst, n_dst, n_dst_rows, out);
 }
 
@@ -291,26 +287,15 @@ static int volume_launch(ddsp_ctx* ctx, hipStream_t st, const float* audio, int6
     return DDSP_OK;
 }
 
-// both integral-hop entry points: n_samples == nullptr is the rectangular batch
-static int volume_extract_go(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int hop,
-                             float* volume) {
+// n_samples == nullptr is the rectangular batch
+extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
+                                   int hop, float* volume) {
     DDSP_REQUIRE(ctx, ctx && audio && volume, "ddsp_volume_extract: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && hop >= 1 && hop <= (1 << 20), "ddsp_volume_extract: bad shape");
     // numpy's reflect padding needs the pad (at most (hop+1)/2) to be smaller than the signal
     DDSP_REQUIRE(ctx, T > (hop + 1) / 2, "ddsp_volume_extract: signal shorter than the reflect padding");
     if (B == 0) return DDSP_OK;
     return volume_launch(ctx, (hipStream_t)stream, audio, B, T, (double)hop, T / hop + 1, hop / 2, (hop + 1) / 2, volume, n_samples);
-}
-
-extern "C" int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
-                                   float* volume) {
-    return volume_extract_go(ctx, stream, audio, B, T, nullptr, hop, volume);
-}
-
-extern "C" int ddsp_volume_extract_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
-                                          const int32_t* n_samples, int hop, float* volume) {
-    DDSP_REQUIRE(ctx, ctx && n_samples, "ddsp_volume_extract_ragged: null argument");
-    return volume_extract_go(ctx, stream, audio, B, T, n_samples, hop, volume);
 }
 
 extern "C" int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, double hop_size,
@@ -325,10 +310,11 @@ extern "C" int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float
     return volume_launch(ctx, (hipStream_t)stream, audio, B, T, hop_size, n_frames, pad_l, pad_r, volume, nullptr);
 }
 
-// both align entry points: n_units == n_out == nullptr is the rectangular batch
-static int align_units_go(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C, int64_t n_frames,
-                          float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
+// n_units == n_out == nullptr is the rectangular batch
+extern "C" int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
+                                int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
     DDSP_REQUIRE(ctx, ctx && units && out, "ddsp_align_units: null argument");
+    DDSP_REQUIRE(ctx, !n_units == !n_out, "ddsp_align_units: n_units and n_out are given together or not at all");
     DDSP_REQUIRE(ctx, B >= 0 && Lu >= 1 && C >= 1 && n_frames >= 0 && ratio >= 0.f && ratio == ratio,
                  "ddsp_align_units: bad shape or ratio");
     if (B == 0 || n_frames == 0) return DDSP_OK;
@@ -341,15 +327,4 @@ static int align_units_go(ddsp_ctx* ctx, void* stream, const float* units, int64
     ddsp_prof_end(ctx, st, 0.0, 8.0 * total * (double)C);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-extern "C" int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
-                                int64_t n_frames, float ratio, float* out) {
-    return align_units_go(ctx, stream, units, B, Lu, C, n_frames, ratio, nullptr, nullptr, out);
-}
-
-extern "C" int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
-                                       int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out) {
-    DDSP_REQUIRE(ctx, ctx && n_units && n_out, "ddsp_align_units_ragged: null argument");
-    return align_units_go(ctx, stream, units, B, Lu, C, n_frames, ratio, n_units, n_out, out);
 }

@@ -690,20 +690,21 @@ extern "C" int64_t ddsp_hubert_frames(int64_t T) {
     return frames_of(T, t);
 }
 
+// n_samples == nullptr is the rectangular batch
 extern "C" int ddsp_hubert_soft_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
-                                      int64_t T, float* units) {
-    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, 13, units);
+                                      int64_t T, const int32_t* n_samples, float* units) {
+    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, 13, units, n_samples);
 }
 
 extern "C" int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
-                                  int layer, float* out) {
+                                  const int32_t* n_samples, int layer, float* out) {
     DDSP_REQUIRE(ctx, layer >= -1 && layer <= 12, "ddsp_hubert_encode: layer must be -1 (conv stack) or 0..12");
-    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out);
+    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out, n_samples);
 }
 
-// both attention entry points: n_keys == nullptr attends over all L rows
-static int softmax_attention_go(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B, int64_t L,
-                                int heads, float* out, int math, const int32_t* n_keys) {
+// n_keys == nullptr attends over all L rows
+extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
+                                      int64_t L, int heads, float* out, int math, const int32_t* n_keys) {
     DDSP_REQUIRE(ctx, ctx && q && k && v && out, "ddsp_softmax_attention: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && L >= 0 && L < (1 << 30) && heads >= 1 && heads <= 4096, "ddsp_softmax_attention: bad shape");
     DDSP_REQUIRE(ctx, math == DDSP_MATH_FP32 || math == DDSP_MATH_SPLIT_BF16, "ddsp_softmax_attention: unknown math");
@@ -719,28 +720,4 @@ static int softmax_attention_go(ddsp_ctx* ctx, void* stream, const float* q, con
     ddsp_prof_end(ctx, st, 4.0 * B * heads * (double)L * L * HDH, 16.0 * B * L * heads * HDH);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-extern "C" int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
-                                      int64_t L, int heads, float* out, int math) {
-    return softmax_attention_go(ctx, stream, q, k, v, B, L, heads, out, math, nullptr);
-}
-
-extern "C" int ddsp_hubert_soft_units_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav,
-                                             int64_t B, int64_t T, const int32_t* n_samples, float* units) {
-    DDSP_REQUIRE(ctx, n_samples, "ddsp_hubert_soft_units_ragged: null n_samples");
-    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, 13, units, n_samples);
-}
-
-extern "C" int ddsp_hubert_encode_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
-                                         int64_t T, const int32_t* n_samples, int layer, float* out) {
-    DDSP_REQUIRE(ctx, n_samples, "ddsp_hubert_encode_ragged: null n_samples");
-    DDSP_REQUIRE(ctx, layer >= -1 && layer <= 12, "ddsp_hubert_encode_ragged: layer must be -1 (conv stack) or 0..12");
-    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out, n_samples);
-}
-
-extern "C" int ddsp_softmax_attention_ragged(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v,
-                                             int64_t B, int64_t L, int heads, float* out, int math, const int32_t* n_keys) {
-    DDSP_REQUIRE(ctx, ctx && n_keys, "ddsp_softmax_attention_ragged: null argument");
-    return softmax_attention_go(ctx, stream, q, k, v, B, L, heads, out, math, n_keys);
 }

@@ -1,6 +1,6 @@
 // SURVEY 8(f) rank 1 - the NSF-HiFiGAN post-net of the reference's `Enhancer` (enhancer.py:24-101, nsf_hifigan/models.py:
 // 106-276): harmonic source (SineGen + SourceModuleHnNSF), the generator's convolution stack, and the log-mel front end
-// (nsf_hifigan/nvSTFT.py:65-119).  Activations frame-major (T, C); the reference calls it with one utterance, the `_ragged`
+// (nsf_hifigan/nvSTFT.py:65-119).  Activations frame-major (T, C); the reference calls it with one utterance, the
 // entry points take B rows of different length as one padded batch, flattened on the time axis: (B * T, C), row b valid
 // for its first T_b = n[b] * scale frames (n: a DEVICE array of B int32, never read back).  ONE RULE keeps the rows apart:
 // every tensor a convolution reads is exactly 0 at t >= T_b, and every producer selects 0 there when it WRITES (bias, residual
@@ -1131,9 +1131,9 @@ extern "C" int ddsp_conv1d_pair_supported(ddsp_ctx* ctx, int C, int ktaps, int d
     }
     return 0;
 }
-static int conv1d_pair_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
-                          const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act,
-                          const int32_t* n_frames, int frame_scale) {
+extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
+                                const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil, float slope, float* out,
+                                float* out_act, const int32_t* n_frames, int frame_scale) {
     DDSP_REQUIRE(ctx, ctx && x && w1 && w2 && (out || out_act), "ddsp_conv1d_pair: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && T >= 1 && B * T < (1 << 30), "ddsp_conv1d_pair: bad length");
     DDSP_REQUIRE(ctx, frame_scale >= 1 && T % frame_scale == 0, "ddsp_conv1d_pair: T must be whole frames of frame_scale");
@@ -1185,19 +1185,11 @@ static int conv1d_pair_go(ddsp_ctx* ctx, void* stream, const float* x, const flo
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
-extern "C" int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
-                                const float* b2, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act) {
-    return conv1d_pair_go(ctx, stream, x, w1, b1, w2, b2, 1, T, C, ktaps, dil, slope, out, out_act, nullptr, 1);
-}
-extern "C" int ddsp_conv1d_pair_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1,
-                                       const float* w2, const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil,
-                                       float slope, float* out, float* out_act, const int32_t* n_frames, int frame_scale) {
-    return conv1d_pair_go(ctx, stream, x, w1, b1, w2, b2, B, T, C, ktaps, dil, slope, out, out_act, n_frames, frame_scale);
-}
 
-static int conv1d_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B, int64_t Tr,
-                     int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out,
-                     float* out_act, float act_slope, const float* w_split, int flags, const int32_t* n_frames, int frame_scale) {
+extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B,
+                           int64_t Tr, int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out,
+                           float* out_act, float act_slope, const float* w_split, int flags, const int32_t* n_frames,
+                           int frame_scale) {
     DDSP_REQUIRE(ctx, ctx && x && w_packed && (out || out_act), "ddsp_conv1d: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && Tr >= 1 && frame_scale >= 1 && Tr % frame_scale == 0, "ddsp_conv1d: bad batch (T must be whole frames of frame_scale)");
     const int64_t T = B * Tr;      // rows of the GEMM: the batch flattened on the time axis, taps wrap with m % Tr
@@ -1271,23 +1263,10 @@ static int conv1d_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
-extern "C" int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t T,
-                           int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out,
-                           float* out_act, float act_slope, const float* w_split, int flags) {
-    return conv1d_go(ctx, stream, x, w_packed, bias, 1, T, Cin, Cout, ktaps, dil, in_slope, residual, out, out_act, act_slope,
-                     w_split, flags, nullptr, 1);
-}
-extern "C" int ddsp_conv1d_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B,
-                                  int64_t T, int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual,
-                                  float* out, float* out_act, float act_slope, const float* w_split, int flags,
-                                  const int32_t* n_frames, int frame_scale) {
-    return conv1d_go(ctx, stream, x, w_packed, bias, B, T, Cin, Cout, ktaps, dil, in_slope, residual, out, out_act, act_slope,
-                     w_split, flags, n_frames, frame_scale);
-}
 
-static int nsf_source_go(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
-                         const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp, const int32_t* n_frames,
-                         float* out) {
+extern "C" int ddsp_nsf_source(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
+                               const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp, const int32_t* n_frames,
+                               float* out) {
     DDSP_REQUIRE(ctx, ctx && f0 && rand_ini && lin_w && lin_b && out, "ddsp_nsf_source: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && L >= 1 && B * L < (1 << 24) && upp >= 1 && upp <= 65536 && sr >= 1,
                  "ddsp_nsf_source: bad shape");
@@ -1307,18 +1286,9 @@ static int nsf_source_go(ddsp_ctx* ctx, void* stream, const float* f0, const flo
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
-extern "C" int ddsp_nsf_source(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
-                               const float* lin_b, int64_t L, int upp, int sr, float sine_amp, float* out) {
-    return nsf_source_go(ctx, stream, f0, rand_ini, lin_w, lin_b, 1, L, upp, sr, sine_amp, nullptr, out);
-}
-extern "C" int ddsp_nsf_source_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
-                                      const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp,
-                                      const int32_t* n_frames, float* out) {
-    return nsf_source_go(ctx, stream, f0, rand_ini, lin_w, lin_b, B, L, upp, sr, sine_amp, n_frames, out);
-}
 
-static int nsf_noise_conv_go(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
-                             const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
+extern "C" int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
+                                   const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
     DDSP_REQUIRE(ctx, ctx && src && w && b && out, "ddsp_nsf_noise_conv: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && T_src >= 1 && T_out >= 1 && C >= 1 && K >= 1 && stride >= 1 && pad >= 0 && T_out * C < ((int64_t)1 << 40),
                  "ddsp_nsf_noise_conv: bad shape");
@@ -1333,17 +1303,9 @@ static int nsf_noise_conv_go(ddsp_ctx* ctx, void* stream, const float* src, int6
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
-extern "C" int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src, int64_t T_src, const float* w,
-                                   const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
-    return nsf_noise_conv_go(ctx, stream, src, 1, T_src, w, b, C, K, stride, pad, T_out, out);
-}
-extern "C" int ddsp_nsf_noise_conv_ragged(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
-                                          const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out) {
-    return nsf_noise_conv_go(ctx, stream, src, B, T_src, w, b, C, K, stride, pad, T_out, out);
-}
 
-static int nsf_post_go(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T, int C,
-                       int K, float slope, float* out, const int32_t* n_frames, int frame_scale) {
+extern "C" int ddsp_nsf_post(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T, int C,
+                             int K, float slope, float* out, const int32_t* n_frames, int frame_scale) {
     DDSP_REQUIRE(ctx, ctx && x && w && b && out, "ddsp_nsf_post: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && T >= 1 && T < ((int64_t)1 << 31) && C >= 1 && K >= 1 && K % 2 == 1 && frame_scale >= 1 &&
                           T % frame_scale == 0,
@@ -1356,14 +1318,6 @@ static int nsf_post_go(ddsp_ctx* ctx, void* stream, const float* x, const float*
                        K, slope, out, use_lds, (const int*)n_frames, frame_scale);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-extern "C" int ddsp_nsf_post(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t T, int C, int K,
-                             float slope, float* out) {
-    return nsf_post_go(ctx, stream, x, w, b, 1, T, C, K, slope, out, nullptr, 1);
-}
-extern "C" int ddsp_nsf_post_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T,
-                                    int C, int K, float slope, float* out, const int32_t* n_frames, int frame_scale) {
-    return nsf_post_go(ctx, stream, x, w, b, B, T, C, K, slope, out, n_frames, frame_scale);
 }
 
 extern "C" int ddsp_nsf_mean(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* c, int n_terms, int64_t n,
@@ -1451,12 +1405,12 @@ __global__ void __launch_bounds__(256) nsf_stft_frames_kernel(const float* __res
 }
 }  // namespace
 
-extern "C" int ddsp_stft_frames_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
-                                       const int32_t* n_samples, int n_fft, int hop, int64_t L, float* out) {
-    DDSP_REQUIRE(ctx, ctx && audio && out, "ddsp_stft_frames_ragged: null argument");
+extern "C" int ddsp_stft_frames(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
+                                int n_fft, int hop, int64_t L, float* out) {
+    DDSP_REQUIRE(ctx, ctx && audio && out, "ddsp_stft_frames: null argument");
     DDSP_REQUIRE(ctx, B >= 1 && B <= 65535 && T >= 1 && n_fft >= 1 && hop >= 1 && hop <= n_fft && L >= 1 &&
                           B * L * n_fft < ((int64_t)1 << 40) && L * n_fft < ((int64_t)1 << 38),
-                 "ddsp_stft_frames_ragged: bad shape");
+                 "ddsp_stft_frames: bad shape");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     hipLaunchKernelGGL(nsf_stft_frames_kernel, dim3((unsigned)((L * n_fft + 255) / 256), (unsigned)B), dim3(256), 0, st, audio, T,

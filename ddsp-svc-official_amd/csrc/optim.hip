@@ -1,6 +1,6 @@
 // a15: AdamW step (train.py:41 `torch.optim.AdamW`): one fused elementwise kernel per parameter tensor
 // (ddsp_adamw_step) or per batch of up to 24 tensors (ddsp_adamw_step_multi, what the optimizer class uses).
-// ddsp_adamw_step_multi_scaled: the same launch with every gradient multiplied by `grad_scale` as it is read - the 1 / world
+// With a grad_scale other than 1: the same launch with every gradient multiplied by `grad_scale` as it is read - the 1 / world
 // of a data-parallel mean, applied to the summed bucket here instead of in a pass of its own over the gradients.
 #include "common.h"
 
@@ -117,22 +117,15 @@ static int adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* c
     return DDSP_OK;
 }
 
+// grad_scale exactly 1.0f launches the kernels that read the gradients as they are; any other finite value the ones that scale
 extern "C" int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params,
                                      const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                                      const int64_t* numel, float lr, float beta1, float beta2, float eps,
-                                     float weight_decay, int64_t step) {
-    return adamw_step_multi<false>(ctx, stream, n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps,
-                                   weight_decay, step, 1.0f);
-}
-
-extern "C" int ddsp_adamw_step_multi_scaled(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params,
-                                            const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                            const int64_t* numel, float lr, float beta1, float beta2, float eps,
-                                            float weight_decay, int64_t step, float grad_scale) {
+                                     float weight_decay, int64_t step, float grad_scale) {
     DDSP_REQUIRE(ctx, ctx && grad_scale == grad_scale && grad_scale - grad_scale == 0.0f,
-                 "ddsp_adamw_step_multi_scaled: grad_scale must be finite");
-    return adamw_step_multi<true>(ctx, stream, n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps,
-                                  weight_decay, step, grad_scale);
+                 "ddsp_adamw_step_multi: grad_scale must be finite");
+    return (grad_scale == 1.0f ? adamw_step_multi<false> : adamw_step_multi<true>)(
+        ctx, stream, n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, step, grad_scale);
 }
 
 extern "C" int ddsp_adamw_step(ddsp_ctx* ctx, void* stream, float* param, const float* grad, float* exp_avg,

@@ -240,9 +240,11 @@ __global__ void __launch_bounds__(256) concat_copy_kernel(const float* __restric
 
 }  // namespace
 
-// S rows of the phase-vocoder cross-fade: the two launches of the solo call with the row as the grid's second dimension
-static int phase_vocoder_rows(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
-                              const float* fade_in, int S, int n, float* out) {
+// S rows of the phase-vocoder cross-fade (S = 1: the reference's call): two launches with the row as the grid's second dimension
+extern "C" int ddsp_phase_vocoder(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
+                                  const float* fade_in, int S, int n, float* out) {
+    DDSP_REQUIRE(ctx, ctx && a && b && fade_out && fade_in && out, "ddsp_phase_vocoder: null argument");
+    DDSP_REQUIRE(ctx, n >= 2 && n <= (1 << 16) && S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_phase_vocoder: bad length or row count");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const int F = n / 2 + 1;
@@ -261,24 +263,16 @@ static int phase_vocoder_rows(ddsp_ctx* ctx, void* stream, const float* a, const
     return DDSP_OK;
 }
 
-extern "C" int ddsp_phase_vocoder(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
-                                  const float* fade_in, int n, float* out) {
-    DDSP_REQUIRE(ctx, ctx && a && b && fade_out && fade_in && out, "ddsp_phase_vocoder: null argument");
-    DDSP_REQUIRE(ctx, n >= 2 && n <= (1 << 16), "ddsp_phase_vocoder: bad length");
-    return phase_vocoder_rows(ctx, stream, a, b, fade_out, fade_in, 1, n, out);
-}
-
-extern "C" int ddsp_phase_vocoder_batch(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
-                                        const float* fade_in, int S, int n, float* out) {
-    DDSP_REQUIRE(ctx, ctx && a && b && fade_out && fade_in && out, "ddsp_phase_vocoder_batch: null argument");
-    DDSP_REQUIRE(ctx, n >= 2 && n <= (1 << 16) && S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_phase_vocoder_batch: bad length or row count");
-    return phase_vocoder_rows(ctx, stream, a, b, fade_out, fade_in, S, n, out);
-}
-
-// S rows of the splice: the two launches of the solo call, the stream as a grid dimension.  Each row has its own scores,
-// arg-max, buffer and tail hand-over; no workgroup reads another row.
-static int sola_rows(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade, int search,
-                     int delay, float* sola_buffer, float* emitted, int* shift) {
+// S rows of the splice (S = 1: the reference's call): two launches, the stream as a grid dimension.  Each row has its own
+// scores, arg-max, buffer and tail hand-over; no workgroup reads another row.
+extern "C" int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade, int search,
+                         int delay, float* sola_buffer, float* emitted, int* shift) {
+    DDSP_REQUIRE(ctx, ctx && audio && sola_buffer && emitted && shift, "ddsp_sola: null argument");
+    DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_sola: 1 <= S <= 4096");
+    DDSP_REQUIRE(ctx, block >= xfade && xfade >= 1 && search >= 0 && delay >= 1, "ddsp_sola: bad sizes");
+    DDSP_REQUIRE(ctx, n_audio >= (int64_t)block + xfade + search + delay, "ddsp_sola: window shorter than block+xfade+search+delay");
+    // (the bounds the one-row call never had stay off it)
+    DDSP_REQUIRE(ctx, S == 1 || (search < 65535 && n_audio < ((int64_t)1 << 31)), "ddsp_sola: S > 1 needs search < 65535 and n_audio < 2^31");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const size_t bytes = (size_t)S * (search + 1) * sizeof(float);
@@ -296,24 +290,6 @@ static int sola_rows(ddsp_ctx* ctx, void* stream, const float* audio, int S, int
     ddsp_prof_end(ctx, st, 4.0 * S * (search + 1) * xfade, 4.0 * S * ((double)block * 2 + xfade * 3 + search));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-extern "C" int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int64_t n_audio, int block, int xfade,
-                         int search, int delay, float* sola_buffer, float* emitted, int* shift) {
-    DDSP_REQUIRE(ctx, ctx && audio && sola_buffer && emitted && shift, "ddsp_sola: null argument");
-    DDSP_REQUIRE(ctx, block >= xfade && xfade >= 1 && search >= 0 && delay >= 1, "ddsp_sola: bad sizes");
-    DDSP_REQUIRE(ctx, n_audio >= (int64_t)block + xfade + search + delay, "ddsp_sola: window shorter than block+xfade+search+delay");
-    return sola_rows(ctx, stream, audio, 1, n_audio, block, xfade, search, delay, sola_buffer, emitted, shift);
-}
-
-extern "C" int ddsp_sola_batch(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade,
-                               int search, int delay, float* sola_buffer, float* emitted, int* shift) {
-    DDSP_REQUIRE(ctx, ctx && audio && sola_buffer && emitted && shift, "ddsp_sola_batch: null argument");
-    DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_sola_batch: 1 <= S <= 4096");
-    DDSP_REQUIRE(ctx, block >= xfade && xfade >= 1 && search >= 0 && search < 65535 && delay >= 1, "ddsp_sola_batch: bad sizes");
-    DDSP_REQUIRE(ctx, n_audio >= (int64_t)block + xfade + search + delay && n_audio < ((int64_t)1 << 31),
-                 "ddsp_sola_batch: rows shorter than block+xfade+search+delay");
-    return sola_rows(ctx, stream, audio, S, n_audio, block, xfade, search, delay, sola_buffer, emitted, shift);
 }
 
 extern "C" int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, float threshold,
@@ -359,7 +335,11 @@ extern "C" int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal,
 // one launch run in no order, so the kept parts go through the arena: launch 1 copies window[s][block:] out, launch 2 (stream
 // order: after every read of launch 1) writes them back to the front with the new blocks behind them.  No launch reads what it
 // writes.
-static int stream_push_rows(ddsp_ctx* ctx, void* stream, float* window, int S, int64_t n_in, const float* block_in, int64_t block) {
+extern "C" int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int S, int64_t n_in, const float* block_in, int64_t block) {
+    DDSP_REQUIRE(ctx, ctx && window && block_in, "ddsp_stream_push: null argument");
+    DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_stream_push: 1 <= S <= 4096");
+    DDSP_REQUIRE(ctx, block >= 1 && block < n_in && n_in < ((int64_t)1 << 31), "ddsp_stream_push: 1 <= block < n_in < 2^31");
+    DDSP_REQUIRE(ctx, block_in + S * block <= window || block_in >= window + S * n_in, "ddsp_stream_push: block_in lies inside the window");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const int64_t keep = n_in - block;
@@ -378,21 +358,4 @@ static int stream_push_rows(ddsp_ctx* ctx, void* stream, float* window, int S, i
     ddsp_prof_end(ctx, st, 0.0, 8.0 * S * (double)(keep + n_in));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-extern "C" int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int64_t n_in, const float* block_in, int64_t block) {
-    DDSP_REQUIRE(ctx, ctx && window && block_in, "ddsp_stream_push: null argument");
-    DDSP_REQUIRE(ctx, block >= 1 && block < n_in && n_in < ((int64_t)1 << 31), "ddsp_stream_push: 1 <= block < n_in < 2^31");
-    DDSP_REQUIRE(ctx, block_in + block <= window || block_in >= window + n_in, "ddsp_stream_push: block_in lies inside the window");
-    return stream_push_rows(ctx, stream, window, 1, n_in, block_in, block);
-}
-
-extern "C" int ddsp_stream_push_batch(ddsp_ctx* ctx, void* stream, float* windows, int S, int64_t n_in, const float* blocks,
-                                      int64_t block) {
-    DDSP_REQUIRE(ctx, ctx && windows && blocks, "ddsp_stream_push_batch: null argument");
-    DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS, "ddsp_stream_push_batch: 1 <= S <= 4096");
-    DDSP_REQUIRE(ctx, block >= 1 && block < n_in && n_in < ((int64_t)1 << 31), "ddsp_stream_push_batch: 1 <= block < n_in < 2^31");
-    DDSP_REQUIRE(ctx, blocks + S * block <= windows || blocks >= windows + S * n_in,
-                 "ddsp_stream_push_batch: blocks lie inside the windows");
-    return stream_push_rows(ctx, stream, windows, S, n_in, blocks, block);
 }

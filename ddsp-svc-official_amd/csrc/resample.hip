@@ -197,26 +197,24 @@ extern "C" int64_t ddsp_resample_length(int64_t T, int orig_freq, int new_freq) 
     return (n * T + o - 1) / o;
 }
 
-static int resample_run(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
-                        int lowpass_filter_width, float* out, const int32_t* ns) {
-    // (the messages name the entry point that was called)
-#define RS_MSG(text) (ns ? "ddsp_resample_ragged: " text : "ddsp_resample: " text)
-    DDSP_REQUIRE(ctx, ctx && x && out, RS_MSG("null argument"));
+// n_samples == nullptr is the rectangular batch
+extern "C" int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples,
+                             int orig_freq, int new_freq, int lowpass_filter_width, float* out) {
+    DDSP_REQUIRE(ctx, ctx && x && out, "ddsp_resample: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && T >= 1 && orig_freq >= 1 && new_freq >= 1 && lowpass_filter_width >= 1 &&
                           lowpass_filter_width <= 4096,
-                 RS_MSG("bad argument"));
+                 "ddsp_resample: bad argument");
     if (B == 0) return DDSP_OK;
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
     const int g = gcd_int(orig_freq, new_freq);
     const int orig = orig_freq / g, nw = new_freq / g;
-    DDSP_REQUIRE(ctx, orig < 65536 && nw < 65536, RS_MSG("rate ratio too fine (reduced rates must be < 65536)"));
+    DDSP_REQUIRE(ctx, orig < 65536 && nw < 65536, "ddsp_resample: rate ratio too fine (reduced rates must be < 65536)");
     const double rolloff = 0.99;
     const double base = (double)(orig < nw ? orig : nw) * rolloff;
     const int width = (int)ceil((double)lowpass_filter_width * (double)orig / base);
     const int K = 2 * width + orig;
-    DDSP_REQUIRE(ctx, (int64_t)nw * K < (1 << 28), RS_MSG("tap table too large"));
-#undef RS_MSG
+    DDSP_REQUIRE(ctx, (int64_t)nw * K < (1 << 28), "ddsp_resample: tap table too large");
     float* taps = nullptr;
     const int key0 = orig, key1 = nw * 8192 + lowpass_filter_width;
     const uint64_t now = ++ctx->table_clock;
@@ -262,24 +260,13 @@ static int resample_run(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, 
     const int64_t n_frames = (T_out + nw - 1) / nw;
     if (lds <= 64 * 1024 && B < 65536 && (n_frames + RS_RB - 1) / RS_RB < 65536)
         hipLaunchKernelGGL(resample_blocked_kernel, dim3((unsigned)((nw + 255) / 256), (unsigned)((n_frames + RS_RB - 1) / RS_RB), (unsigned)B),
-                           dim3(256), lds, st, x, taps, T, T_out, orig, nw, width, K, out, ns);
+                           dim3(256), lds, st, x, taps, T, T_out, orig, nw, width, K, out, n_samples);
     else
         hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, taps, T, T_out, orig, nw, width, K, total,
-                           out, ns);
+                           out, n_samples);
     ddsp_prof_end(ctx, st, 2.0 * total * K, 4.0 * (B * T + total));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-extern "C" int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
-                             int lowpass_filter_width, float* out) {
-    return resample_run(ctx, stream, x, B, T, orig_freq, new_freq, lowpass_filter_width, out, nullptr);
-}
-
-extern "C" int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples,
-                                    int orig_freq, int new_freq, int lowpass_filter_width, float* out) {
-    DDSP_REQUIRE(ctx, n_samples, "ddsp_resample_ragged: null n_samples");
-    return resample_run(ctx, stream, x, B, T, orig_freq, new_freq, lowpass_filter_width, out, n_samples);
 }
 
 // ---- keyed batches: one launch, a rate pair per row ---------------------------------------------------------------------------

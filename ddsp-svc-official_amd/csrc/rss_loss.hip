@@ -484,27 +484,15 @@ static int rss_loss_any(ddsp_ctx* ctx, void* stream, const float* x_pred, const 
     return DDSP_OK;
 }
 
-extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B,
-                             int64_t T, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps,
+// n_samples_host + n_samples_dev (both or neither) make the rows ragged; global_n_samples_host + n_global (with the local counts
+// only) make them one rank's share of a global batch.
+extern "C" int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                             const int* n_samples_host, const int32_t* n_samples_dev, const int* global_n_samples_host,
+                             int64_t n_global, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps,
                              float* loss, float* grad_pred) {
-    return rss_loss_any(ctx, stream, x_pred, x_true, B, T, nullptr, nullptr, n_ffts_host, hops_host, n_scale, alpha, eps, loss,
-                        grad_pred);
-}
-
-extern "C" int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
-                                    const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host,
-                                    const int* hops_host, int n_scale, float alpha, float eps, float* loss, float* grad_pred) {
-    DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev, "ddsp_rss_loss_ragged: null n_samples");
-    return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
-                        n_scale, alpha, eps, loss, grad_pred);
-}
-
-extern "C" int ddsp_rss_loss_share(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
-                                   const int* n_samples_host, const int32_t* n_samples_dev, const int* global_n_samples_host,
-                                   int64_t n_global, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha,
-                                   float eps, float* loss, float* grad_pred) {
-    DDSP_REQUIRE(ctx, ctx && n_samples_host && n_samples_dev && global_n_samples_host && loss,
-                 "ddsp_rss_loss_share: null argument");
+    DDSP_REQUIRE(ctx, ctx && !n_samples_host == !n_samples_dev,
+                 "ddsp_rss_loss: n_samples_host and n_samples_dev are given together or not at all");
+    DDSP_REQUIRE(ctx, !global_n_samples_host || n_samples_host, "ddsp_rss_loss: global_n_samples_host needs the local counts");
     return rss_loss_any(ctx, stream, x_pred, x_true, B, T, n_samples_host, (const int*)n_samples_dev, n_ffts_host, hops_host,
                         n_scale, alpha, eps, loss, grad_pred, nullptr, global_n_samples_host, n_global);
 }

@@ -266,9 +266,17 @@ __global__ void __launch_bounds__(64) slicer_tag_kernel(TagArgs a) {
     }
 }
 
-int slicer_run(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int64_t win,
-               int64_t hop, double threshold, int64_t min_length, int64_t min_interval, int64_t max_sil_kept, int pad_mode,
-               float* rms, int32_t* table, int32_t* count, int64_t capacity) {
+}  // namespace
+
+extern "C" int64_t ddsp_slicer_frames(int64_t n, int64_t win, int64_t hop) {
+    if (n < 0 || win < 1 || hop < 1 || n + 2 * (win / 2) < win) return -1;
+    return 1 + (n + 2 * (win / 2) - win) / hop;
+}
+
+// n_samples == nullptr: every row holds T samples
+extern "C" int ddsp_slicer(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
+                           int64_t win, int64_t hop, double threshold, int64_t min_length, int64_t min_interval,
+                           int64_t max_sil_kept, int pad_mode, float* rms, int32_t* table, int32_t* count, int64_t capacity) {
     DDSP_REQUIRE(ctx, ctx && audio && rms && table && count, "ddsp_slicer: null argument");
     DDSP_REQUIRE(ctx, B >= 0 && B <= 65535 && T >= 1 && win >= 1 && hop >= 1 && T + 4 * hop + win < (1ll << 31),
                  "ddsp_slicer: bad shape");
@@ -335,27 +343,4 @@ int slicer_run(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64
     ddsp_prof_end(ctx, st, 0.0, (double)B * ((double)F_max * 4.0 + (double)capacity * 12.0));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t ddsp_slicer_frames(int64_t n, int64_t win, int64_t hop) {
-    if (n < 0 || win < 1 || hop < 1 || n + 2 * (win / 2) < win) return -1;
-    return 1 + (n + 2 * (win / 2) - win) / hop;
-}
-
-extern "C" int ddsp_slicer(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int64_t win, int64_t hop,
-                           double threshold, int64_t min_length, int64_t min_interval, int64_t max_sil_kept, int pad_mode,
-                           float* rms, int32_t* table, int32_t* count, int64_t capacity) {
-    return slicer_run(ctx, stream, audio, B, T, nullptr, win, hop, threshold, min_length, min_interval, max_sil_kept, pad_mode,
-                      rms, table, count, capacity);
-}
-
-extern "C" int ddsp_slicer_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
-                                  const int32_t* n_samples, int64_t win, int64_t hop, double threshold, int64_t min_length,
-                                  int64_t min_interval, int64_t max_sil_kept, int pad_mode, float* rms, int32_t* table,
-                                  int32_t* count, int64_t capacity) {
-    DDSP_REQUIRE(ctx, n_samples, "ddsp_slicer_ragged: null n_samples");
-    return slicer_run(ctx, stream, audio, B, T, n_samples, win, hop, threshold, min_length, min_interval, max_sil_kept,
-                      pad_mode, rms, table, count, capacity);
 }

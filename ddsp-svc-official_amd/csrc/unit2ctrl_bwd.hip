@@ -1279,21 +1279,12 @@ static int u2c_backward(ddsp_ctx* ctx, hipStream_t st, const ddsp_u2c_weights& w
 
 }  // namespace
 
+// both entry points take the counts of a ragged batch (n_frames null: every row has Fr frames)
 extern "C" int ddsp_unit2ctrl_bwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                                   const float* f0_frames, const float* phase_frames, const float* volume,
                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                  const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const float* d_ctrl,
-                                  const ddsp_u2c_weights* grads_host, float* ctrl_out) {
-    return ddsp_unit2ctrl_bwd_ragged(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
-                                     n_mix, B, Fr, nullptr, d_ctrl, grads_host, ctrl_out);
-}
-
-// the two entry points with the counts of a ragged batch (n_frames null: every row has Fr frames)
-extern "C" int ddsp_unit2ctrl_bwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                         const float* f0_frames, const float* phase_frames, const float* volume,
-                                         const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                         const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                                         const float* d_ctrl, const ddsp_u2c_weights* grads_host, float* ctrl_out) {
+                                  const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                  const float* d_ctrl, const ddsp_u2c_weights* grads_host, float* ctrl_out) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
@@ -1309,18 +1300,9 @@ extern "C" int ddsp_unit2ctrl_bwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp
 extern "C" int ddsp_unit2ctrl_bwd_kept(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                                        const float* f0_frames, const float* phase_frames, const float* volume,
                                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep,
-                                       int64_t keep_bytes, const float* d_ctrl, const ddsp_u2c_weights* grads_host) {
-    return ddsp_unit2ctrl_bwd_kept_ragged(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host,
-                                          mix_w_host, n_mix, B, Fr, nullptr, keep, keep_bytes, d_ctrl, grads_host);
-}
-
-extern "C" int ddsp_unit2ctrl_bwd_kept_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                              const float* f0_frames, const float* phase_frames, const float* volume,
-                                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                                              void* keep, int64_t keep_bytes, const float* d_ctrl,
-                                              const ddsp_u2c_weights* grads_host) {
+                                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                       void* keep, int64_t keep_bytes, const float* d_ctrl,
+                                       const ddsp_u2c_weights* grads_host) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);

@@ -1270,7 +1270,7 @@ int check_inputs(ddsp_ctx* ctx, const ddsp_u2c_weights* wp, const float* units, 
 
 }  // namespace u2c
 
-// the inference forward behind ddsp_unit2ctrl_fwd (n_frames null) and ddsp_unit2ctrl_fwd_ragged: the same launches
+// the inference forward behind ddsp_unit2ctrl_fwd and ddsp_unit2ctrl_fwd_rowmix (n_frames null or the counts: the same launches)
 static int unit2ctrl_fwd_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                              const float* f0_frames, const float* phase_frames, const float* volume,
                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
@@ -1355,25 +1355,16 @@ extern "C" int ddsp_u2c_dwconv_pw2(ddsp_ctx* ctx, void* stream, const float* glu
     return DDSP_OK;
 }
 
+// n_frames (null: every row has Fr frames) makes the batch ragged: row b has n_frames[b] frames (device array, int32,
+// 1 <= n_frames[b] <= Fr) inside the padded (B, Fr, ...) inputs.  The places that look across frames stop at the row's own end:
+// the GroupNorm statistics, the zero padding of the second prenet convolution, the key sums and the context of the linear
+// attention, the depthwise convolution's input.  The first convolution reads its input as the caller left it: units of frames
+// >= n_frames[b] must be 0 (ddsp_ragged_frames).  Rows of ctrl past a row's count hold values that mean nothing.
 extern "C" int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                                   const float* f0_frames, const float* phase_frames, const float* volume,
                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                  const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, float* ctrl) {
-    return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
-                             n_mix, B, Fr, nullptr, ctrl);
-}
-
-// Ragged batch: row b has n_frames[b] frames (device array, int32, 1 <= n_frames[b] <= Fr) inside the padded (B, Fr, ...)
-// inputs.  The places that look across frames stop at the row's own end: the GroupNorm statistics, the zero padding of the
-// second prenet convolution, the key sums and the context of the linear attention, the depthwise convolution's input.
-// The first convolution reads its input as the caller left it: units of frames >= n_frames[b] must be 0
-// (ddsp_ragged_frames).  Rows of ctrl past a row's count hold values that mean nothing.
-extern "C" int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                         const float* f0_frames, const float* phase_frames, const float* volume,
-                                         const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                         const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                                         float* ctrl) {
-    DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_unit2ctrl_fwd_ragged: null n_frames");
+                                  const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                  float* ctrl) {
     return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                              n_mix, B, Fr, n_frames, ctrl);
 }
@@ -1381,33 +1372,16 @@ extern "C" int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp
 // A speaker mix per batch row from device tables (include/ddsp_amd.h): the launches of ddsp_unit2ctrl_fwd, whose embedding
 // epilogue reads row m / Fr of the tables.  check_inputs sees a one-slot host mix {1: 0} (the speaker path it then needs no
 // spk_id for); unit2ctrl_fwd_any replaces it by the tables.
-static int unit2ctrl_fwd_rowmix_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                    const float* f0_frames, const float* phase_frames, const float* volume,
-                                    const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
-                                    const int32_t* n_frames, float* ctrl) {
+extern "C" int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                         const float* f0_frames, const float* phase_frames, const float* volume,
+                                         const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                         const int32_t* n_frames, float* ctrl) {
     DDSP_REQUIRE(ctx, ctx && mix_ids_dev && mix_w_dev, "ddsp_unit2ctrl_fwd_rowmix: null mix table");
     DDSP_REQUIRE(ctx, K >= 1 && K <= 16, "ddsp_unit2ctrl_fwd_rowmix: 1 <= K <= 16 mixed speakers per row");
     const int64_t one_id = 1;
     const float zero_w = 0.f;
     return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, nullptr, 0, &one_id, &zero_w, 1, B, Fr,
                              n_frames, ctrl, mix_ids_dev, mix_w_dev, K);
-}
-
-extern "C" int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                         const float* f0_frames, const float* phase_frames, const float* volume,
-                                         const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
-                                         float* ctrl) {
-    return unit2ctrl_fwd_rowmix_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, mix_ids_dev, mix_w_dev, K, B, Fr,
-                                    nullptr, ctrl);
-}
-
-extern "C" int ddsp_unit2ctrl_fwd_rowmix_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                                const float* f0_frames, const float* phase_frames, const float* volume,
-                                                const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
-                                                const int32_t* n_frames, float* ctrl) {
-    DDSP_REQUIRE(ctx, ctx && n_frames, "ddsp_unit2ctrl_fwd_rowmix_ragged: null n_frames");
-    return unit2ctrl_fwd_rowmix_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, mix_ids_dev, mix_w_dev, K, B, Fr,
-                                    n_frames, ctrl);
 }
 
 // ---- a training step's pair: a forward that leaves its activations in a caller-owned region, a backward that starts from them ----
@@ -1419,22 +1393,13 @@ extern "C" int64_t ddsp_unit2ctrl_keep_bytes(const ddsp_u2c_weights* wp, int64_t
     return (int64_t)dry.total + 256;
 }
 
+// n_frames: the counts of a ragged batch, or null (every row has Fr frames); units of frames >= n_frames[b] must be 0, as for
+// ddsp_unit2ctrl_fwd.  Activations of the padding frames are kept too, finite and without meaning.
 extern "C" int ddsp_unit2ctrl_fwd_keep(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                                        const float* f0_frames, const float* phase_frames, const float* volume,
                                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep,
-                                       int64_t keep_bytes, float* ctrl) {
-    return ddsp_unit2ctrl_fwd_keep_ragged(ctx, stream, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host,
-                                          mix_w_host, n_mix, B, Fr, nullptr, keep, keep_bytes, ctrl);
-}
-
-// The same with the counts of a ragged batch (n_frames null: every row has Fr frames); units of frames >= n_frames[b] must be 0,
-// as for ddsp_unit2ctrl_fwd_ragged.  Activations of the padding frames are kept too, finite and without meaning.
-extern "C" int ddsp_unit2ctrl_fwd_keep_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
-                                              const float* f0_frames, const float* phase_frames, const float* volume,
-                                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                                              void* keep, int64_t keep_bytes, float* ctrl) {
+                                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
+                                       void* keep, int64_t keep_bytes, float* ctrl) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);

@@ -231,7 +231,7 @@ class F0_Extractor:
       * `extract(..., dither=True, seed=None)`: torchcrepe dithers the decoded pitch by a random triangular offset of up to
         +-20 cents (a bin is 20 cents); `dither=False` makes the output deterministic, `seed` fixes the draw (default: drawn
         from torch's generator); `seed_dev` (a (1,) int64 device tensor) holds the seed on the device instead and is advanced
-        by every call (`ddsp_crepe_decode_dseed`), so a call captured into a HIP graph dithers anew on every replay;
+        by every call (`seed_dev` of `ddsp_crepe_decode`), so a call captured into a HIP graph dithers anew on every replay;
       * `extract(audio (B,T), ..., n_samples=)`: a RAGGED batch of rows of different length (see `extract`);
       * 'parselmouth', 'dio' and 'harvest' (CPU libraries) raise NotImplementedError;
       * `f0_extractor='ac'`: the autocorrelation method of Boersma (1993) on the device (`ddsp_f0_ac`) - the algorithm behind

@@ -35,7 +35,7 @@ networks then share the captured context; each has a prepared-weight slot of its
 prepared inside the graph on every replay (in-place updates are honoured, as above); the two analysis networks (HuBERT-Soft,
 CREPE: inference only) are prepared once by the warm-up runs and the captured kernels read those copies
 (`ddsp_weight_slot_take(..., keep_in_capture)`), so a change of THEIR weights needs a new capture.  The CREPE dither seed lives
-in a device word that the decode advances (`ddsp_crepe_decode_dseed`): a seed passed by value would be frozen by the capture.
+in a device word that the decode advances (`seed_dev` of `ddsp_crepe_decode`): a seed passed by value would be frozen by the capture.
 
 `GraphedBankEnhancer` captures the enhancer stage of a `realtime.StreamBank` (`bank_enhancer_chain`: the per-row adaptive key
 decided on the device, the keyed resamplers, the ragged generator, the resampling to the device rate and the gather of every
@@ -226,7 +226,7 @@ class GraphedBlock(_Captured):
 def bank_enhancer_chain(ctx, enhancer, plan, sig, f0, request, rand_ini, model_sr, block_size, samplerate, n_end_by_key, tail_idx):
     """Steps 6-7 of the `StreamRenderer` chain over S rows, nothing read back: `enhancer.enhance_keyed` on the gated signal
     `sig` (S, Fr * block_size) and the shifted `f0` (S, Fr, 1) with the per-row key requests `request` (S,) int32 and the bank's
-    `plan` (`enhancer.KeyedPlan`); `ddsp_resample_ragged` from the enhancer's rate to `samplerate` on the device lengths; then
+    `plan` (`enhancer.KeyedPlan`); `ddsp_resample` from the enhancer's rate to `samplerate` on the device lengths; then
     every row's last `tail_idx.numel()` samples counted from the row's OWN end (`gui.py:405-406` slices from the end), the
     end being `n_end_by_key[key]`.  -> (tail (S, n_tail), key (S,) int32)."""
     out, sr_e, n_out, key = enhancer.enhance_keyed(sig, model_sr, f0, block_size, adaptive_key=request,

@@ -21,7 +21,7 @@ COMB_NONE, COMB_SINC, COMB_SINC_GATED = 0, 1, 2
 FIR_ALLPASS, FIR_DYNAMIC, FIR_STATIC = 0, 1, 2
 EXC_AUDIO, EXC_UNIT_NOISE, EXC_GENERATE = 0, 1, 2
 FIR_FP32, FIR_SPLIT_BF16 = 0, 3   # ddsp_ltv_fir `math` (include/ddsp_amd.h)
-ABI_VERSION = 7                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights, CrepeWeights)
+ABI_VERSION = 8                   # DDSP_ABI_VERSION of include/ddsp_amd.h (struct layouts: U2CWeights, HubertWeights, CrepeWeights)
 MATH_FP32, MATH_SPLIT_BF16 = 0, 3  # ddsp_ctx_set_math
 ATTENTION_CAUSAL = 200            # ddsp_performer_attention: causal_linear_attention (pcmer.py:170-188)
 SLICER_PAD = {"constant": 0, "reflect": 1}   # ddsp_slicer `pad_mode`: librosa >= 0.10 / older librosa
@@ -187,110 +187,73 @@ SIGNATURES = {
     "ddsp_spectral_ola": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _u64, _i64, _i64, _int, _vp]),
     "ddsp_sins_bank_bwd": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _i64]),
     "ddsp_spectral_ola_bwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _u64, _vp, _i64, _i64, _int, _vp, _i64]),
-    "ddsp_rss_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _int, _f32, _f32, _vp, _vp]),
-    "ddsp_sola": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "ddsp_rss_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _i64, _c.POINTER(_int),
+                             _c.POINTER(_int), _int, _f32, _f32, _vp, _vp]),
+    "ddsp_sola": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
     "ddsp_volume_gate": (_int, [_vp, _vp, _vp, _vp, _f32, _i64, _i64, _int]),
     "ddsp_volume_gate_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
     "ddsp_stitch": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
-    "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
-    "ddsp_volume_extract": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
+    "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "ddsp_volume_extract": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
     "ddsp_volume_extract_frac": (_int, [_vp, _vp, _vp, _i64, _i64, _f64, _vp]),
-    "ddsp_align_units": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
+    "ddsp_align_units": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
     "ddsp_gemm_res_ln": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _int]),
     "ddsp_u2c_dwconv_pw2": (_int, [_vp] * 11 + [_int, _int, _int, _int, _vp, _vp, _vp]),
     "ddsp_conv1d_pair_supported": (_int, [_vp, _int, _int, _int]),
-    "ddsp_conv1d_pair": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _f32, _vp, _vp]),
-    "ddsp_retime_f0": (_int, [_vp, _vp, _vp, _i64, _f64, _f64, _f32, _f64, _i64, _vp]),
+    "ddsp_conv1d_pair": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _f32, _vp, _vp, _vp, _int]),
+    "ddsp_retime_f0": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _f64, _f32, _f64, _i64, _vp, _vp]),
     "ddsp_resample_length": (_i64, [_i64, _int, _int]),
-    "ddsp_resample": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp]),
-    "ddsp_conv1d": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _f32, _vp, _vp, _vp, _f32, _vp, _int]),
-    "ddsp_nsf_source": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _f32, _vp]),
-    "ddsp_nsf_noise_conv": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _int, _i64, _vp]),
-    "ddsp_nsf_post": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _f32, _vp]),
+    "ddsp_resample": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _int, _vp]),
+    "ddsp_conv1d": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _f32, _vp, _vp, _vp, _f32, _vp, _int,
+                           _vp, _int]),
+    "ddsp_nsf_source": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp]),
+    "ddsp_nsf_noise_conv": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _int, _int, _int, _int, _i64, _vp]),
+    "ddsp_nsf_post": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp, _int]),
     "ddsp_nsf_mean": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp, _vp, _f32, _int]),
     "ddsp_log_mel": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _f32, _vp]),
     "ddsp_adamw_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64]),
-    "ddsp_adamw_step_multi": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i64]),
+    "ddsp_adamw_step_multi": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i64, _f32]),
     "ddsp_gemm_f32": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _i64, _int, _vp, _vp, _i64, _int, _int, _int, _int, _int]),
     "ddsp_performer_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _int]),
     "ddsp_hubert_frames": (_i64, [_i64]),
-    "ddsp_hubert_soft_units": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp]),
-    "ddsp_hubert_encode": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _int, _vp]),
-    "ddsp_softmax_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int]),
-    "ddsp_hubert_soft_units_ragged": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _vp]),
-    "ddsp_hubert_encode_ragged": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _int, _vp]),
-    "ddsp_softmax_attention_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp]),
-    "ddsp_resample_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _int, _vp]),
-    "ddsp_align_units_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
-    "ddsp_conv1d_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _f32, _vp, _vp, _vp, _f32, _vp, _int,
-                                  _vp, _int]),
-    "ddsp_conv1d_pair_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _f32, _vp, _vp, _vp, _int]),
-    "ddsp_nsf_source_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp]),
-    "ddsp_nsf_noise_conv_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _int, _int, _int, _int, _i64, _vp]),
-    "ddsp_nsf_post_ragged": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp, _int]),
-    "ddsp_stft_frames_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp]),
-    "ddsp_retime_f0_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _f64, _f32, _f64, _i64, _vp, _vp]),
+    "ddsp_hubert_soft_units": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _vp]),
+    "ddsp_hubert_encode": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _int, _vp]),
+    "ddsp_softmax_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp]),
+    "ddsp_stft_frames": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp]),
     "ddsp_retime_f0_keyed": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _vp, _int, _vp, _vp, _f64, _i64, _vp, _vp]),
     "ddsp_enhancer_keys": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "ddsp_resample_keyed_plan": (_int, [_vp, _vp, _int, _c.POINTER(_int), _c.POINTER(_int), _int, _c.POINTER(_vp)]),
     "ddsp_resample_keyed_plan_destroy": (None, [_vp]),
     "ddsp_resample_keyed_length": (_i64, [_vp, _i64]),
     "ddsp_resample_keyed": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
-    "ddsp_volume_extract_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
-    "ddsp_crepe_activations_ragged": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _vp, _vp, _i64, _int, _vp]),
-    "ddsp_crepe_decode_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
-    "ddsp_f0_postfilter_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _i64, _vp, _f32, _int, _f32, _vp]),
     "ddsp_crepe_frames": (_i64, [_i64, _int]),
-    "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _int, _vp]),
-    "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _u64, _int, _vp, _vp, _vp]),
-    "ddsp_crepe_decode_dseed": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _vp, _int, _vp, _vp, _vp]),
-    "ddsp_stream_push": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
-    "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _f64, _i64, _i64, _f32, _int, _f32, _vp]),
+    "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _vp, _vp, _i64, _int, _vp]),
+    "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _i64, _u64, _vp, _int, _vp, _vp, _vp]),
+    "ddsp_stream_push": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _i64]),
+    "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _i64, _i64, _vp, _f32, _int, _f32, _vp]),
     "ddsp_f0_ac_frames": (_i64, [_i64, _int, _f64, _f64]),
-    "ddsp_f0_ac": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _f64, _f64, _f64, _i64, _i64, _int, _vp, _vp]),
-    "ddsp_f0_ac_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _f64, _f64, _i64, _int, _vp, _vp]),
+    "ddsp_f0_ac": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _f64, _f64, _i64, _i64, _int, _vp, _vp]),
     "ddsp_slicer_frames": (_i64, [_i64, _i64, _i64]),
-    "ddsp_slicer": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64]),
-    "ddsp_slicer_ragged": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64]),
+    "ddsp_slicer": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64]),
     "ddsp_profile_begin": (_int, [_vp, _u64]),
     "ddsp_profile_mask": (_int, [_vp, _u64]),
     "ddsp_profile_end": (_int, [_vp, _c.POINTER(ProfEntry), _int, _c.POINTER(_int)]),
     "ddsp_unit2ctrl_fwd": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                  _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp]),
+                                  _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp]),
     "ddsp_unit2ctrl_bwd": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                  _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _c.POINTER(U2CWeights), _vp]),
-    "ddsp_unit2ctrl_fwd_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                         _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp]),
-    "ddsp_unit2ctrl_fwd_rowmix": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp]),
-    "ddsp_unit2ctrl_fwd_rowmix_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64,
-                                                _vp, _vp]),
-    "ddsp_stream_push_batch": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _i64]),
-    "ddsp_sola_batch": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
-    "ddsp_phase_vocoder_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+                                  _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _c.POINTER(U2CWeights), _vp]),
+    "ddsp_unit2ctrl_fwd_rowmix": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
     "ddsp_ragged_frames": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
     "ddsp_ragged_crop": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int]),
     "ddsp_ragged_noise": (_int, [_vp, _vp, _vp, _u64, _vp, _i64, _i64, _int, _vp]),
     "ddsp_ltv_fir": (_int, [_vp, _vp, _vp, _int, _u64, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _int]),
     "ddsp_unit2ctrl_keep_bytes": (_i64, [_c.POINTER(U2CWeights), _i64, _i64]),
     "ddsp_unit2ctrl_fwd_keep": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                       _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _i64, _vp]),
+                                       _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _i64, _vp]),
     "ddsp_unit2ctrl_bwd_kept": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                       _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _i64, _vp,
+                                       _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _i64, _vp,
                                        _c.POINTER(U2CWeights)]),
-    "ddsp_unit2ctrl_fwd_keep_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                              _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _i64, _vp]),
-    "ddsp_unit2ctrl_bwd_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                         _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp,
-                                         _c.POINTER(U2CWeights), _vp]),
-    "ddsp_unit2ctrl_bwd_kept_ragged": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
-                                              _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _i64, _vp,
-                                              _c.POINTER(U2CWeights)]),
     "ddsp_ragged_frames_adjoint": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64]),
-    "ddsp_rss_loss_ragged": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
-                                    _int, _f32, _f32, _vp, _vp]),
-    "ddsp_rss_loss_share": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _i64, _c.POINTER(_int),
-                                   _c.POINTER(_int), _int, _f32, _f32, _vp, _vp]),
-    "ddsp_adamw_step_multi_scaled": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _i64, _f32]),
     "ddsp_rss_loss_rows": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(_int), _vp, _c.POINTER(_int), _c.POINTER(_int),
                                   _int, _f32, _f32, _vp]),
     "ddsp_vc_f0_map": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
@@ -414,8 +377,8 @@ def check_loss_scales(n_samples, n_ffts):
 def loss_norms(n_samples, n_ffts, hops=None):
     """The spectral loss's two denominators per scale over rows of `n_samples` samples: [(cells, rows_ne)], cells = sum_b F_b *
     (n_fft // 2 + 1) with F_b = (n_b - n_fft) // hop + 1 frames (0 for a row shorter than n_fft), rows_ne the rows with a frame.
-    hops: one hop per scale (default: hop = n_fft).  What `ddsp_rss_loss_ragged` forms from the local rows and
-    `ddsp_rss_loss_share` from the rows of the global batch."""
+    hops: one hop per scale (default: hop = n_fft).  What `ddsp_rss_loss` forms from the local rows, or from the
+    rows of the global batch when it is given them."""
     hops = [int(n) for n in n_ffts] if hops is None else [int(h) for h in hops]
     out = []
     for n_fft, hop in zip((int(n) for n in n_ffts), hops):
@@ -656,17 +619,11 @@ class Context:
             ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
             frames = [units.contiguous().float()] + [t.reshape(B, Fr).contiguous().float() for t in (f0_frames, phase_frames, volume)]
             args = [_ptr(t) for t in frames] + [_ptr(ids), _ptr(w), K, B, Fr]
-            if n_frames is not None:
-                self.call("ddsp_unit2ctrl_fwd_rowmix_ragged", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
-            else:
-                self.call("ddsp_unit2ctrl_fwd_rowmix", ctypes.byref(weights), *args, _ptr(ctrl))
+            self.call("ddsp_unit2ctrl_fwd_rowmix", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
             return ctrl
         ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        if n_frames is not None:
-            self.call("ddsp_unit2ctrl_fwd_ragged", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
-        else:
-            self.call("ddsp_unit2ctrl_fwd", ctypes.byref(weights), *args, _ptr(ctrl))
+        self.call("ddsp_unit2ctrl_fwd", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
         return ctrl
 
     # -- ragged batches (include/ddsp_amd.h): held frames, cropped signals, the noise draw ---------
@@ -760,11 +717,8 @@ class Context:
         d_ctrl = d_ctrl.contiguous().float()
         ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32) if want_ctrl else None
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        if n_frames is not None:
-            self.call("ddsp_unit2ctrl_bwd_ragged", ctypes.byref(weights), *args, _ptr(self._counts_dev(n_frames, B)), _ptr(d_ctrl),
-                      ctypes.byref(grads), _ptr(ctrl))
-        else:
-            self.call("ddsp_unit2ctrl_bwd", ctypes.byref(weights), *args, _ptr(d_ctrl), ctypes.byref(grads), _ptr(ctrl))
+        n_dev = None if n_frames is None else self._counts_dev(n_frames, B)
+        self.call("ddsp_unit2ctrl_bwd", ctypes.byref(weights), *args, _ptr(n_dev), _ptr(d_ctrl), ctypes.byref(grads), _ptr(ctrl))
         return ctrl
 
     def _u2c_inputs(self, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict):
@@ -800,11 +754,8 @@ class Context:
         keep = torch.empty(nbytes, device=units.device, dtype=torch.uint8)
         ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        if n_frames is not None:
-            self.call("ddsp_unit2ctrl_fwd_keep_ragged", ctypes.byref(weights), *args, _ptr(self._counts_dev(n_frames, B)), _ptr(keep),
-                      nbytes, _ptr(ctrl))
-        else:
-            self.call("ddsp_unit2ctrl_fwd_keep", ctypes.byref(weights), *args, _ptr(keep), nbytes, _ptr(ctrl))
+        n_dev = None if n_frames is None else self._counts_dev(n_frames, B)
+        self.call("ddsp_unit2ctrl_fwd_keep", ctypes.byref(weights), *args, _ptr(n_dev), _ptr(keep), nbytes, _ptr(ctrl))
         return ctrl, keep
 
     def unit2ctrl_bwd_kept(self, weights, grads, units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict, keep, d_ctrl,
@@ -813,12 +764,9 @@ class Context:
         that call had it (`unit2ctrl_bwd` says what a ragged batch asks of the inputs)."""
         d_ctrl = d_ctrl.contiguous().float()
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
-        if n_frames is not None:
-            self.call("ddsp_unit2ctrl_bwd_kept_ragged", ctypes.byref(weights), *args, _ptr(self._counts_dev(n_frames, units.shape[0])),
-                      _ptr(keep), keep.numel(), _ptr(d_ctrl), ctypes.byref(grads))
-        else:
-            self.call("ddsp_unit2ctrl_bwd_kept", ctypes.byref(weights), *args, _ptr(keep), keep.numel(), _ptr(d_ctrl),
-                      ctypes.byref(grads))
+        n_dev = None if n_frames is None else self._counts_dev(n_frames, units.shape[0])
+        self.call("ddsp_unit2ctrl_bwd_kept", ctypes.byref(weights), *args, _ptr(n_dev), _ptr(keep), keep.numel(), _ptr(d_ctrl),
+                  ctypes.byref(grads))
 
     # -- a5-a6 ---------------------------------------------------------------------------------
     def fir_from_ctrl(self, mode, ctrl2d, col0, n_mag, rows, sr, f0_frames=None):
@@ -899,10 +847,9 @@ class Context:
             self.call("ddsp_volume_extract_frac", _ptr(audio), B, T, hop, _ptr(out))
             return out
         out = torch.empty(B, T // int(hop) + 1, device=audio.device, dtype=torch.float32)
-        if B and vals is not None:
-            self.call("ddsp_volume_extract_ragged", _ptr(audio), B, T, _ptr(self.ragged_counts(vals)), int(hop), _ptr(out))
-        elif B:
-            self.call("ddsp_volume_extract", _ptr(audio), B, T, int(hop), _ptr(out))
+        if B:
+            n_dev = None if vals is None else self.ragged_counts(vals)
+            self.call("ddsp_volume_extract", _ptr(audio), B, T, _ptr(n_dev), int(hop), _ptr(out))
         return out
 
     def align_units(self, units, n_frames, ratio, n_units_dev=None, n_out_dev=None):
@@ -916,11 +863,8 @@ class Context:
         out = torch.empty(B, int(n_frames), C, device=units.device, dtype=torch.float32)
         if B == 0 or int(n_frames) == 0:
             return out
-        args = (_ptr(units), B, Lu, C, int(n_frames), float(ratio))
-        if n_units_dev is not None:
-            self.call("ddsp_align_units_ragged", *args, _ptr(n_units_dev), _ptr(n_out_dev), _ptr(out))
-        else:
-            self.call("ddsp_align_units", *args, _ptr(out))
+        self.call("ddsp_align_units", _ptr(units), B, Lu, C, int(n_frames), float(ratio), _ptr(n_units_dev), _ptr(n_out_dev),
+                  _ptr(out))
         return out
 
     def retime_f0(self, f0, step_num, div, scale, step_dst, n_dst, n_src_dev=None, n_dst_dev=None, keyed=None):
@@ -944,17 +888,13 @@ class Context:
             self.call("ddsp_retime_f0_keyed", _ptr(f0), B, n_src, _ptr(n_src_dev), float(step_num), _ptr(self._counts_dev(key, B)),
                       div_tab.numel(), _ptr(div_tab), _ptr(scale_tab), float(step_dst), int(n_dst), _ptr(n_dst_dev), _ptr(out))
             return out
-        steps = (float(step_num), float(div), float(scale), float(step_dst), int(n_dst))
-        if n_src_dev is None:
-            f0 = f0.reshape(-1).contiguous().float()
-            out = torch.empty(int(n_dst), device=f0.device, dtype=torch.float32)
-            self.call("ddsp_retime_f0", _ptr(f0), f0.numel(), *steps, _ptr(out))
-            return out
-        f0 = f0.contiguous().float()
+        solo = n_src_dev is None
+        f0 = (f0.reshape(1, -1) if solo else f0).contiguous().float()
         B, n_src = f0.shape
         out = torch.empty(B, int(n_dst), device=f0.device, dtype=torch.float32)
-        self.call("ddsp_retime_f0_ragged", _ptr(f0), B, n_src, _ptr(n_src_dev), *steps, _ptr(n_dst_dev), _ptr(out))
-        return out
+        self.call("ddsp_retime_f0", _ptr(f0), B, n_src, _ptr(n_src_dev), float(step_num), float(div), float(scale), float(step_dst),
+                  int(n_dst), _ptr(n_dst_dev), _ptr(out))
+        return out[0] if solo else out
 
     # -- sample-rate conversion ---------------------------------------------
     def resample(self, audio, orig_freq, new_freq, lowpass_filter_width=6, n_dev=None):
@@ -970,11 +910,8 @@ class Context:
         if T_out < 0:
             raise ValueError("resample: bad rates")
         out = torch.empty(B, T_out, device=x.device, dtype=torch.float32)
-        rates = (int(orig_freq), int(new_freq), int(lowpass_filter_width))
-        if B and T and n_dev is not None:
-            self.call("ddsp_resample_ragged", _ptr(x), B, T, _ptr(n_dev), *rates, _ptr(out))
-        elif B and T:
-            self.call("ddsp_resample", _ptr(x), B, T, *rates, _ptr(out))
+        if B and T:
+            self.call("ddsp_resample", _ptr(x), B, T, _ptr(n_dev), int(orig_freq), int(new_freq), int(lowpass_filter_width), _ptr(out))
         return out[0] if flat else out
 
     def resample_plan(self, pairs, lowpass_filter_width=6):
@@ -1019,8 +956,16 @@ class Context:
     # -- NSF-HiFiGAN post-net building blocks --------------------------------
     # Ragged batches (include/ddsp_amd.h, "Ragged batches of the post-net"): `rows=(B, n_dev, scale)` runs a call over B rows
     # flattened on the time axis, (B * T, C), row b valid for n_dev[b] * scale frames (n_dev: (B,) int32 device tensor of
-    # `ragged_counts`, or None for a rectangular batch) and written as 0 after them; rows=None is one utterance, x (T, C), through
-    # the solo symbol - the same launches as rows=(1, None, 1).
+    # `ragged_counts`, or None for a rectangular batch) and written as 0 after them; rows=None is one utterance, x (T, C): the
+    # call and the launches of rows=(1, None, 1).
+    @staticmethod
+    def _rows(name, rows, T):
+        """`rows` of a post-net call over x (T, ...) -> (B, frames per row, n_dev, scale); None is (1, T, None, 1)."""
+        B, n_dev, scale = (1, None, 1) if rows is None else rows
+        if T % int(B):
+            raise ValueError(f"{name}: x must hold B rows of equal padded length")
+        return int(B), T // int(B), n_dev, int(scale)
+
     def conv1d(self, x, w_packed, bias, ktaps, dil, in_slope, residual=None, want_out=True, act_slope=None, w_split=None,
                x_split=False, act_split=False, rows=None):
         """x (T,Cin), w_packed (Cout, ktaps*Cin) -> y (T,Cout) = conv_same(leaky_relu(x, in_slope)) + bias (+ residual).
@@ -1036,15 +981,10 @@ class Context:
         if out is None and act is None:
             raise ValueError("conv1d: nothing to return")
         flags = (CONV_X_SPLIT if x_split else 0) | (CONV_ACT_SPLIT if act_split else 0)
-        geom = (Cin, Cout, int(ktaps), int(dil), float(in_slope), _ptr(residual), _ptr(out), _ptr(act),
-                float(act_slope if act_slope is not None else 1.0), _ptr(w_split), flags)
-        if rows is not None:
-            B, n_dev, scale = rows
-            if T % int(B):
-                raise ValueError("conv1d: x must hold B rows of equal padded length")
-            self.call("ddsp_conv1d_ragged", _ptr(x), _ptr(w_packed), _ptr(bias), int(B), T // int(B), *geom, _ptr(n_dev), int(scale))
-        else:
-            self.call("ddsp_conv1d", _ptr(x), _ptr(w_packed), _ptr(bias), T, *geom)
+        B, Tr, n_dev, scale = self._rows("conv1d", rows, T)
+        self.call("ddsp_conv1d", _ptr(x), _ptr(w_packed), _ptr(bias), B, Tr, Cin, Cout, int(ktaps), int(dil), float(in_slope),
+                  _ptr(residual), _ptr(out), _ptr(act), float(act_slope if act_slope is not None else 1.0), _ptr(w_split), flags,
+                  _ptr(n_dev), scale)
         return out if act_slope is None else (out, act)
 
     def gemm_res_ln(self, A_split, W_split, bias, res, gamma, beta, y_split=True, a_fp32=False):
@@ -1080,15 +1020,9 @@ class Context:
         T, C = x.shape
         out = torch.empty(T, C, device=x.device, dtype=torch.float32) if want_out else None
         act = torch.empty(T, C, device=x.device, dtype=torch.float32) if want_act else None
-        weights = (_ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2))
-        geom = (C, int(ktaps), int(dil), float(slope), _ptr(out), _ptr(act))
-        if rows is not None:
-            B, n_dev, scale = rows
-            if T % int(B):
-                raise ValueError("conv1d_pair: x must hold B rows of equal padded length")
-            self.call("ddsp_conv1d_pair_ragged", _ptr(x), *weights, int(B), T // int(B), *geom, _ptr(n_dev), int(scale))
-        else:
-            self.call("ddsp_conv1d_pair", _ptr(x), *weights, T, *geom)
+        B, Tr, n_dev, scale = self._rows("conv1d_pair", rows, T)
+        self.call("ddsp_conv1d_pair", _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), B, Tr, C, int(ktaps), int(dil), float(slope),
+                  _ptr(out), _ptr(act), _ptr(n_dev), scale)
         return out, act
 
     def nsf_source(self, f0, rand_ini, lin_w, lin_b, upp, sr, sine_amp=0.1, n_dev=None):
@@ -1103,12 +1037,8 @@ class Context:
         L = f0.shape[-1]
         rand_ini = rand_ini.contiguous().float()
         out = torch.empty(*f0.shape[:-1], L * int(upp), device=f0.device, dtype=torch.float32)
-        head = (_ptr(f0), _ptr(rand_ini), _ptr(lin_w), _ptr(lin_b))
-        tail = (L, int(upp), int(sr), float(sine_amp))
-        if solo:
-            self.call("ddsp_nsf_source", *head, *tail, _ptr(out))
-        else:
-            self.call("ddsp_nsf_source_ragged", *head, f0.shape[0], *tail, _ptr(n_dev), _ptr(out))
+        self.call("ddsp_nsf_source", _ptr(f0), _ptr(rand_ini), _ptr(lin_w), _ptr(lin_b), 1 if solo else f0.shape[0], L, int(upp),
+                  int(sr), float(sine_amp), _ptr(n_dev), _ptr(out))
         return out
 
     def nsf_noise_conv(self, src, w, b, K, stride, pad, T_out):
@@ -1116,26 +1046,17 @@ class Context:
         B, T_src = (1, src.numel()) if src.dim() == 1 else src.shape
         C = w.shape[0]
         out = torch.empty(B * int(T_out), C, device=src.device, dtype=torch.float32)
-        geom = (_ptr(w), _ptr(b), C, int(K), int(stride), int(pad), int(T_out), _ptr(out))
-        if src.dim() == 1:
-            self.call("ddsp_nsf_noise_conv", _ptr(src), T_src, *geom)
-        else:
-            self.call("ddsp_nsf_noise_conv_ragged", _ptr(src), B, T_src, *geom)
+        self.call("ddsp_nsf_noise_conv", _ptr(src), B, T_src, _ptr(w), _ptr(b), C, int(K), int(stride), int(pad), int(T_out), _ptr(out))
         return out
 
     def nsf_post(self, x, w, b, K, slope, rows=None):
         """x (T, C) -> (T,), or with `rows` (as in conv1d) x (B * T, C) -> (B, T), 0 past each row's end."""
         C = x.shape[1]
-        if rows is None:
-            out = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
-            self.call("ddsp_nsf_post", _ptr(x), _ptr(w), _ptr(b), x.shape[0], C, int(K), float(slope), _ptr(out))
-            return out
-        B, n_dev, scale = rows
+        B, n_dev, scale = (1, None, 1) if rows is None else rows
         T = x.shape[0] // int(B)
         out = torch.empty(int(B), T, device=x.device, dtype=torch.float32)
-        self.call("ddsp_nsf_post_ragged", _ptr(x), _ptr(w), _ptr(b), int(B), T, C, int(K), float(slope), _ptr(out), _ptr(n_dev),
-                  int(scale))
-        return out
+        self.call("ddsp_nsf_post", _ptr(x), _ptr(w), _ptr(b), int(B), T, C, int(K), float(slope), _ptr(out), _ptr(n_dev), int(scale))
+        return out[0] if rows is None else out
 
     def stft_frames(self, audio, n_dev, n_fft, hop, L):
         """audio (B, T) with n_dev[b] samples per row (None: every row whole) -> frames (B, L, n_fft) padded per row as
@@ -1143,7 +1064,7 @@ class Context:
         audio = audio.contiguous().float()
         B, T = audio.shape
         out = torch.empty(B, int(L), int(n_fft), device=audio.device, dtype=torch.float32)
-        self.call("ddsp_stft_frames_ragged", _ptr(audio), B, T, _ptr(n_dev), int(n_fft), int(hop), int(L), _ptr(out))
+        self.call("ddsp_stft_frames", _ptr(audio), B, T, _ptr(n_dev), int(n_fft), int(hop), int(L), _ptr(out))
         return out
 
     def nsf_mean(self, terms, want_out=True, act_slope=None, act_split=False):
@@ -1173,7 +1094,7 @@ class Context:
     def adamw_step_multi(self, params, grads, exp_avgs, exp_avg_sqs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
         """One AdamW update of a whole list of parameter tensors (shared hyper-parameters and step): the pointer
         tables go to the library as host arrays, the library issues one launch per 24 tensors.  grad_scale: every gradient is
-        multiplied by it as it is read (`ddsp_adamw_step_multi_scaled`); 1.0 calls `ddsp_adamw_step_multi`."""
+        multiplied by it as it is read; exactly 1.0 runs the kernel that does not multiply."""
         if not _math.isfinite(float(grad_scale)):
             raise ValueError("adamw_step_multi: grad_scale must be finite")
         n = len(params)
@@ -1187,12 +1108,8 @@ class Context:
                 raise ValueError("adamw_step_multi: a tensor and its state differ in size")
         arr = lambda ts: (_vp * n)(*[_ptr(t) for t in ts])
         numel = (_i64 * n)(*[p.numel() for p in params])
-        common = (n, arr(params), arr(grads), arr(exp_avgs), arr(exp_avg_sqs), numel, float(lr), float(beta1), float(beta2),
-                  float(eps), float(weight_decay), int(step))
-        if float(grad_scale) == 1.0:
-            self.call("ddsp_adamw_step_multi", *common)
-        else:
-            self.call("ddsp_adamw_step_multi_scaled", *common, float(grad_scale))
+        self.call("ddsp_adamw_step_multi", n, arr(params), arr(grads), arr(exp_avgs), arr(exp_avg_sqs), numel, float(lr), float(beta1),
+                  float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale))
 
     # -- building block ------------------------------------------------------------------------
     def gemm(self, A, B, bias=None, a_k_contig=True, b_k_contig=True, tile=0, variant=0, out=None):
@@ -1224,11 +1141,8 @@ class Context:
             out = torch.empty(B * L, heads * 64, device=q.device, dtype=torch.float32)
         elif out.dtype != torch.float32 or tuple(out.shape) != (B * L, heads * 64):
             raise ValueError("softmax_attention: `out` must be fp32 (B*L, heads*64)")
-        args = (_ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math))
-        if n_keys_dev is not None:
-            self.call("ddsp_softmax_attention_ragged", *args, _ptr(n_keys_dev))
-        else:
-            self.call("ddsp_softmax_attention", *args)
+        self.call("ddsp_softmax_attention", _ptr(q), _ptr(k), _ptr(v), int(B), int(L), int(heads), _ptr(out), int(math),
+                  _ptr(n_keys_dev))
         return out
 
     # -- units encoder -------------------------------------------------------------------------
@@ -1242,10 +1156,8 @@ class Context:
             raise ValueError(f"hubert: {T} samples are too short for the conv stack")
         wav = wav.contiguous().float()
         out = torch.empty(B, Fr, 256, device=wav.device, dtype=torch.float32)
-        if B and n_dev is not None:
-            self.call("ddsp_hubert_soft_units_ragged", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), _ptr(out))
-        elif B:
-            self.call("ddsp_hubert_soft_units", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(out))
+        if B:
+            self.call("ddsp_hubert_soft_units", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), _ptr(out))
         return out
 
     def hubert_encode(self, weights, wav, layer, n_dev=None):
@@ -1257,11 +1169,8 @@ class Context:
             raise ValueError(f"hubert: {T} samples are too short for the conv stack")
         wav = wav.contiguous().float()
         out = torch.empty(B, Fr, 512 if layer == -1 else 768, device=wav.device, dtype=torch.float32)
-        if B and n_dev is not None:
-            self.call("ddsp_hubert_encode_ragged", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), int(layer),
-                      _ptr(out))
-        elif B:
-            self.call("ddsp_hubert_encode", ctypes.byref(weights), _ptr(wav), int(B), int(T), int(layer), _ptr(out))
+        if B:
+            self.call("ddsp_hubert_encode", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), int(layer), _ptr(out))
         return out
 
     # -- f0 extractor (CREPE) --------------------------------------------------------------------
@@ -1283,11 +1192,9 @@ class Context:
             elif counts_dev.dtype != torch.int32 or counts_dev.numel() != 2 * B + 1 or not counts_dev.is_contiguous():
                 raise ValueError("crepe_activations: counts_dev must be the (2B + 1,) int32 upload of crepe_ragged_table")
         out = torch.empty(B, Fr, 360, device=x.device, dtype=torch.float32)
-        if B and n_samples is not None:
-            self.call("ddsp_crepe_activations_ragged", ctypes.byref(weights), _ptr(x), int(B), int(T), _ptr(counts_dev),
-                      _ptr(counts_dev) + 4 * B, int(table[-1]), int(hop), _ptr(out))
-        elif B:
-            self.call("ddsp_crepe_activations", ctypes.byref(weights), _ptr(x), int(B), int(T), int(hop), _ptr(out))
+        ragged = (None, None, 0) if n_samples is None else (_ptr(counts_dev), _ptr(counts_dev) + 4 * B, int(table[-1]))
+        if B:
+            self.call("ddsp_crepe_activations", ctypes.byref(weights), _ptr(x), int(B), int(T), *ragged, int(hop), _ptr(out))
         return out
 
     def crepe_decode(self, probs, fmin, fmax, segment=512, dither_seed=0, dither=False, want_bins=False, seed_dev=None,
@@ -1295,13 +1202,14 @@ class Context:
         """probs (B, Fr, 360) -> (f0 (B, Fr), periodicity (B, Fr)[, bins (B, Fr) int32]): the range mask, the Viterbi decode
         in independent pieces of `segment` frames (0: whole track), bins to Hz with the optional triangular dither.
         `seed_dev`: a (1,) int64 device tensor that holds the dither seed instead of `dither_seed` and is advanced to
-        `next_dither_seed` of its value by the call (`ddsp_crepe_decode_dseed`: what a captured graph needs).
+        `next_dither_seed` of its value by the call (what a captured graph needs).
         `n_frames` (a sequence of B ints or a CPU integer tensor (B,)): a RAGGED batch - row b is decoded over its own
         n_frames[b] frames as a call on probs[b:b+1, :n_frames[b]] with the same seed decodes it, bit for bit, and every
         output is 0 after them.  `counts_dev`: the (B,) int32 device tensor of the same counts when the caller has
         uploaded them already (`ragged_counts`); None uploads them here."""
         p = probs.contiguous().float()
         B, Fr, _ = p.shape
+        n_dev = None
         if n_frames is not None:
             if seed_dev is not None:
                 raise ValueError("crepe_decode: seed_dev is not available with n_frames (a ragged batch)")
@@ -1313,15 +1221,9 @@ class Context:
         if seed_dev is not None and (seed_dev.dtype != torch.int64 or seed_dev.numel() != 1 or seed_dev.device != p.device):
             raise ValueError("crepe_decode: seed_dev must be a (1,) int64 tensor on the device of probs")
         seed = int(dither_seed) & ((1 << 64) - 1)
-        if B and Fr and n_frames is not None:
-            self.call("ddsp_crepe_decode_ragged", _ptr(p), int(B), int(Fr), _ptr(n_dev), float(fmin), float(fmax), int(segment),
-                      seed, 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
-        elif B and Fr and seed_dev is not None:
-            self.call("ddsp_crepe_decode_dseed", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
+        if B and Fr:
+            self.call("ddsp_crepe_decode", _ptr(p), int(B), int(Fr), _ptr(n_dev), float(fmin), float(fmax), int(segment), seed,
                       _ptr(seed_dev), 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
-        elif B and Fr:
-            self.call("ddsp_crepe_decode", _ptr(p), int(B), int(Fr), float(fmin), float(fmax), int(segment),
-                      seed, 1 if dither else 0, _ptr(f0), _ptr(pd), _ptr(bins))
         return (f0, pd, bins) if want_bins else (f0, pd)
 
     def f0_postfilter(self, f0, pd, sr, hop, n_frames, start_frame=0, threshold=0.05, uv_interp=False, f0_min=65.0,
@@ -1340,6 +1242,7 @@ class Context:
             raise ValueError("f0_postfilter: f0 and pd must have the same shape")
         if (n_crepe is None) != (n_out is None):
             raise ValueError("f0_postfilter: a ragged batch needs both n_crepe and n_out")
+        nc = no = None
         if n_crepe is not None:
             if int(start_frame) != 0:
                 raise ValueError("f0_postfilter: start_frame must be 0 with n_crepe / n_out (a ragged batch)")
@@ -1354,13 +1257,9 @@ class Context:
             else:
                 nc, no = self.ragged_counts(vals[0] + vals[1]).reshape(2, B)
         out = torch.empty(B, int(n_frames), device=f0.device, dtype=torch.float32)
-        tail = (float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
-        if B and n_crepe is not None:
-            self.call("ddsp_f0_postfilter_ragged", _ptr(f0), _ptr(pd), int(B), int(Fr), _ptr(nc), int(sr), float(hop),
-                      int(n_frames), _ptr(no), *tail)
-        elif B:
-            self.call("ddsp_f0_postfilter", _ptr(f0), _ptr(pd), int(B), int(Fr), int(sr), float(hop), int(n_frames),
-                      int(start_frame), *tail)
+        if B:
+            self.call("ddsp_f0_postfilter", _ptr(f0), _ptr(pd), int(B), int(Fr), _ptr(nc), int(sr), float(hop), int(n_frames),
+                      int(start_frame), _ptr(no), float(threshold), 1 if uv_interp else 0, float(f0_min), _ptr(out))
         return out
 
     def f0_ac(self, audio, sr, hop, f0_min, f0_max, n_frames, start_frame=0, uv_interp=False, n_dev=None, want_choice=False):
@@ -1377,13 +1276,10 @@ class Context:
             raise ValueError("f0_ac: start_frame must be 0 with n_dev (a ragged batch)")
         out = torch.empty(B, int(n_frames), device=audio.device, dtype=torch.float32)
         choice = torch.empty(B, f0_ac_frames(T, sr, hop, f0_min), device=audio.device, dtype=torch.int32) if want_choice else None
-        head = (_ptr(audio), int(B), int(T))
-        geo = (int(sr), float(hop), float(f0_min), float(f0_max), int(n_frames))
-        tail = (1 if uv_interp else 0, _ptr(out), _ptr(choice) if want_choice else None)
-        if B and n_dev is not None:
-            self.call("ddsp_f0_ac_ragged", *head, _ptr(self._counts_dev(n_dev, B)), *geo, *tail)
-        elif B:
-            self.call("ddsp_f0_ac", *head, *geo, int(start_frame), *tail)
+        if B:
+            n_dev = None if n_dev is None else self._counts_dev(n_dev, B)
+            self.call("ddsp_f0_ac", _ptr(audio), int(B), int(T), _ptr(n_dev), int(sr), float(hop), float(f0_min), float(f0_max),
+                      int(n_frames), int(start_frame), 1 if uv_interp else 0, _ptr(out), _ptr(choice))
         return (out, choice) if want_choice else out
 
     def slicer(self, x, win, hop, threshold, min_length, min_interval, max_sil_kept, pad_mode="constant", n_dev=None,
@@ -1410,12 +1306,10 @@ class Context:
         table, count, rms = out
         if pad_mode not in SLICER_PAD:
             raise ValueError(f"slicer: pad_mode must be one of {sorted(SLICER_PAD)}, got {pad_mode!r}")
-        geo = (int(win), int(hop), float(threshold), int(min_length), int(min_interval), int(max_sil_kept), SLICER_PAD[pad_mode],
-               _ptr(rms), _ptr(table), _ptr(count), cap)
-        if B and n_dev is not None:
-            self.call("ddsp_slicer_ragged", _ptr(x), int(B), int(T), _ptr(self._counts_dev(n_dev, B)), *geo)
-        elif B:
-            self.call("ddsp_slicer", _ptr(x), int(B), int(T), *geo)
+        if B:
+            n_dev = None if n_dev is None else self._counts_dev(n_dev, B)
+            self.call("ddsp_slicer", _ptr(x), int(B), int(T), _ptr(n_dev), int(win), int(hop), float(threshold), int(min_length),
+                      int(min_interval), int(max_sil_kept), SLICER_PAD[pad_mode], _ptr(rms), _ptr(table), _ptr(count), cap)
         return table, count, rms
 
     # -- a10 -----------------------------------------------------------------------------------
@@ -1450,10 +1344,10 @@ class Context:
                  global_n_samples=None):
         """-> (loss (1,) device tensor, d loss/d x_pred (B,T) | None) for the given list of scales; `hops`: one hop per
         scale (default: hop = n_fft, the reference's overlap = 0).  `n_samples`: the list `check_n_samples` returned -
-        rows of different length (include/ddsp_amd.h: ddsp_rss_loss_ragged).  `rows` (with `n_samples`, without `want_grad`):
-        -> (loss per row (B,), None), every row scored alone (ddsp_rss_loss_rows).  `global_n_samples` (with `n_samples`,
-        without `rows`): the list `check_global_n_samples` returned - the rows are one rank's share of that global batch
-        (ddsp_rss_loss_share)."""
+        rows of different length (include/ddsp_amd.h: the counts of ddsp_rss_loss).  `rows` (with `n_samples`, without
+        `want_grad`): -> (loss per row (B,), None), every row scored alone (ddsp_rss_loss_rows).  `global_n_samples` (with
+        `n_samples`, without `rows`): the list `check_global_n_samples` returned - the rows are one rank's share of that
+        global batch."""
         xp = x_pred.detach().contiguous().float()
         xt = x_true.detach().contiguous().float()
         B, T = xp.shape
@@ -1471,20 +1365,14 @@ class Context:
         harr = (_int * len(n_ffts))(*[int(h) for h in hops]) if hops is not None else None
         loss = torch.empty(B if rows else 1, device=xp.device, dtype=torch.float32)
         grad = torch.empty_like(xp) if want_grad else None
-        if n_samples is not None:
-            ns = (_int * B)(*n_samples)
-            common = (_ptr(xp), _ptr(xt), B, T, ns, _ptr(self.ragged_counts(n_samples)), arr, harr, len(n_ffts), float(alpha),
-                      float(eps), _ptr(loss))
-            if rows:
-                self.call("ddsp_rss_loss_rows", *common)
-            elif global_n_samples is not None:
-                gns = (_int * len(global_n_samples))(*global_n_samples)
-                self.call("ddsp_rss_loss_share", *common[:6], gns, len(global_n_samples), *common[6:], _ptr(grad))
-            else:
-                self.call("ddsp_rss_loss_ragged", *common, _ptr(grad))
+        ns, n_dev = (None, None) if n_samples is None else ((_int * B)(*n_samples), self.ragged_counts(n_samples))
+        scales = (arr, harr, len(n_ffts), float(alpha), float(eps), _ptr(loss))
+        if rows:
+            self.call("ddsp_rss_loss_rows", _ptr(xp), _ptr(xt), B, T, ns, _ptr(n_dev), *scales)
         else:
-            self.call("ddsp_rss_loss", _ptr(xp), _ptr(xt), B, T, arr, harr, len(n_ffts), float(alpha), float(eps), _ptr(loss),
-                      _ptr(grad))
+            gns, n_global = (None, 0) if global_n_samples is None else ((_int * len(global_n_samples))(*global_n_samples),
+                                                                        len(global_n_samples))
+            self.call("ddsp_rss_loss", _ptr(xp), _ptr(xt), B, T, ns, _ptr(n_dev), gns, n_global, *scales, _ptr(grad))
         return loss, grad
 
     def vc_f0_map(self, f0_frames, spk_id, lfo, n_frames=None):
@@ -1512,33 +1400,26 @@ class Context:
         """audio (N,), sola_buffer (xfade,) updated in place -> (emitted (block,), shift int32 device tensor).
         S streams: audio (S, N), sola_buffer (S, xfade) -> (emitted (S, block), shift (S,)); row s is the solo call on row s."""
         audio = audio.contiguous().float()
-        if audio.dim() == 2:
-            S = audio.shape[0]
-            if tuple(sola_buffer.shape) != (S, int(xfade)) or sola_buffer.dtype != torch.float32:
-                raise ValueError(f"sola: {S} streams need an fp32 sola_buffer (S, xfade) = {(S, int(xfade))}")
-            emitted = torch.empty(S, int(block), device=audio.device, dtype=torch.float32)
-            shift = torch.empty(S, device=audio.device, dtype=torch.int32)
-            self.call("ddsp_sola_batch", _ptr(audio), S, audio.shape[1], int(block), int(xfade), int(search), int(delay),
-                      _ptr(sola_buffer), _ptr(emitted), _ptr(shift))
-            return emitted, shift
-        emitted = torch.empty(block, device=audio.device, dtype=torch.float32)
-        shift = torch.empty(1, device=audio.device, dtype=torch.int32)
-        self.call("ddsp_sola", _ptr(audio), audio.numel(), int(block), int(xfade), int(search), int(delay),
-                  _ptr(sola_buffer), _ptr(emitted), _ptr(shift))
+        rows = audio.dim() == 2
+        S, n_audio = audio.shape if rows else (1, audio.numel())
+        if rows and (tuple(sola_buffer.shape) != (S, int(xfade)) or sola_buffer.dtype != torch.float32):
+            raise ValueError(f"sola: {S} streams need an fp32 sola_buffer (S, xfade) = {(S, int(xfade))}")
+        emitted = torch.empty((S, int(block)) if rows else (block,), device=audio.device, dtype=torch.float32)
+        shift = torch.empty(S, device=audio.device, dtype=torch.int32)
+        self.call("ddsp_sola", _ptr(audio), S, n_audio, int(block), int(xfade), int(search), int(delay), _ptr(sola_buffer),
+                  _ptr(emitted), _ptr(shift))
         return emitted, shift
 
     def stream_push_(self, window, block_in):
         """In place: window (n_in,) = append(window[block:], block_in (block,)) (gui.py:373-374); the window keeps its
-        address (`ddsp_stream_push`)."""
+        address (`ddsp_stream_push`).  S streams: windows (S, n_in) take blocks (S, block), every row like the solo call."""
         if window.dtype == torch.float32 and block_in.dtype == torch.float32 and window.dim() == 2:
-            # S streams: windows (S, n_in) take blocks (S, block), every row like the solo call (`ddsp_stream_push_batch`)
             if block_in.dim() != 2 or block_in.shape[0] != window.shape[0]:
                 raise ValueError("stream_push_: (S, n_in) windows take (S, block) blocks")
-            self.call("ddsp_stream_push_batch", _ptr(window), window.shape[0], window.shape[1], _ptr(block_in), block_in.shape[1])
-            return window
-        if window.dtype != torch.float32 or block_in.dtype != torch.float32 or window.dim() != 1 or block_in.dim() != 1:
+        elif window.dtype != torch.float32 or block_in.dtype != torch.float32 or window.dim() != 1 or block_in.dim() != 1:
             raise ValueError("stream_push_: window and block_in must be 1-D fp32 tensors")
-        self.call("ddsp_stream_push", _ptr(window), window.numel(), _ptr(block_in), block_in.numel())
+        self.call("ddsp_stream_push", _ptr(window), window.shape[0] if window.dim() == 2 else 1, window.shape[-1], _ptr(block_in),
+                  block_in.shape[-1])
         return window
 
     def phase_vocoder(self, a, b, fade_out, fade_in):
@@ -1550,14 +1431,12 @@ class Context:
             S, n = a.shape
             if tuple(b.shape) != (S, n) or not (fo.numel() == fi.numel() == n):
                 raise ValueError("phase_vocoder: a and b must be (S, n) and the fade windows (n,)")
-            out = torch.empty(S, n, device=a.device, dtype=torch.float32)
-            self.call("ddsp_phase_vocoder_batch", _ptr(a), _ptr(b), _ptr(fo), _ptr(fi), S, n, _ptr(out))
-            return out
-        n = a.numel()
-        if not (b.numel() == fo.numel() == fi.numel() == n):
-            raise ValueError("phase_vocoder: a, b and the fade windows must have the same length")
-        out = torch.empty(n, device=a.device, dtype=torch.float32)
-        self.call("ddsp_phase_vocoder", _ptr(a), _ptr(b), _ptr(fo), _ptr(fi), n, _ptr(out))
+        else:
+            S, n = 1, a.numel()
+            if not (b.numel() == fo.numel() == fi.numel() == n):
+                raise ValueError("phase_vocoder: a, b and the fade windows must have the same length")
+        out = torch.empty((S, n) if a.dim() == 2 else (n,), device=a.device, dtype=torch.float32)
+        self.call("ddsp_phase_vocoder", _ptr(a), _ptr(b), _ptr(fo), _ptr(fi), S, n, _ptr(out))
         return out
 
     # -- a15 -----------------------------------------------------------------------------------
@@ -1657,7 +1536,7 @@ _override = threading.local()
 
 
 def next_dither_seed(seed):
-    """The value `ddsp_crepe_decode_dseed` leaves in its seed word after a call that read `seed` (a host computation)."""
+    """The value `ddsp_crepe_decode` leaves in its `seed_dev` word after a call that read `seed` (a host computation)."""
     return (int(seed) * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
 
 

@@ -346,7 +346,7 @@ class StreamBank:
     """S real-time streams of ONE geometry (device rate, block, cross-fade, window) on one GPU, all advanced by one block per
     call: the chain of `StreamRenderer` (its docstring, steps 1-8) with every step batched over the streams.  Under
     `push_audio` steps 1-5 of all rows are ONE linear HIP-graph replay (`graphed.GraphedBlock` over the S windows); then come
-    resampling to the device rate and the batched splice (a `Splicer(rows=S)` -> `ddsp_sola_batch`: every row's own arg-max,
+    resampling to the device rate and the batched splice (a `Splicer(rows=S)` -> `ddsp_sola` with S rows: every row's own arg-max,
     buffer and tail).
 
     With `enhancer=` (an `enhancer.Enhancer`) step 6 runs on all rows too, every row with an adaptive key of its own

@@ -174,18 +174,19 @@ typedef struct ddsp_u2c_weights {
  * {1, B} (the reference broadcasts a (1,1) id); speaker mixing (`spk_mix_dict`): n_mix > 0 host arrays
  * mix_ids_host (1-based) / mix_w_host replace spk_id (n_mix <= 16).  ctrl out (B,Fr,n_out), the fused
  * control matrix that `split_to_dict` (ddsp/unit2control.py:10-20) views.  The `weights` struct itself is a
- * HOST pointer. */
+ * HOST pointer.  n_frames: NULL, or the counts of a ragged batch (next section). */
 int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
                        const float* f0_frames, const float* phase_frames, const float* volume,
                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, float* ctrl);
+                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, float* ctrl);
 
-/* ---- ragged batches: rows of different length in one padded (B, Fr, ...) call (training: the _ragged forms further down) ----
+/* ---- ragged batches: rows of different length in one padded (B, Fr, ...) call ------------------------------------------------
  * n_frames: DEVICE array of B int32, 1 <= n_frames[b] <= Fr (the caller checks it; the kernels hold a value outside the range
- * at its nearest bound).  Row b comes out as if it had been computed alone with Fr = n_frames[b].
+ * at its nearest bound), or NULL: every row has Fr frames.  Row b comes out as if it had been computed alone with
+ * Fr = n_frames[b].
  *
- * ddsp_unit2ctrl_fwd_ragged is ddsp_unit2ctrl_fwd with the same launches, in which every place that looks across frames
- * stops at the row's own end: the GroupNorm statistics (count included), the zero padding of the second prenet convolution,
+ * With n_frames, ddsp_unit2ctrl_fwd runs the same launches, in which every place that looks across frames stops at the row's
+ * own end: the GroupNorm statistics (count included), the zero padding of the second prenet convolution,
  * the key sums and the context of the linear attention, the input of the depthwise convolution.  Its first convolution
  * reads `units` as they are: frames >= n_frames[b] must hold 0 (ddsp_ragged_frames, hold = 0).  Rows of ctrl past a row's
  * count carry no meaning.
@@ -202,11 +203,6 @@ int ddsp_unit2ctrl_fwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weig
  *                       alone is padded with) and every output.  hop % 4 == 0, 16-byte aligned buffers.
  *   ddsp_ragged_noise   out (B, Fr*hop) = the unit-noise draw U[0,1) for DDSP_EXC_UNIT_NOISE: inside a row noise[b][t], or
  *                       (noise == NULL) a counter hash of (noise_seed, b, t); 0.5 past the row's end (2u - 1 = 0 exactly). */
-int ddsp_unit2ctrl_fwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
-                              const float* f0_frames, const float* phase_frames, const float* volume,
-                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                              float* ctrl);
 int ddsp_ragged_frames(ddsp_ctx* ctx, void* stream, const float* src, const int32_t* n_frames, int64_t B, int64_t Fr,
                        int64_t C, int hold, float* dst);
 
@@ -218,15 +214,11 @@ int ddsp_ragged_frames(ddsp_ctx* ctx, void* stream, const float* src, const int3
  * speakers); the row {id, 1.0} is a plain speaker id.  An id outside [1, n_spk] is not used as an index: the call's device
  * error word is set (DDSP_ERR_ARG from the next call or ddsp_ctx_poll_error) and the slot adds nothing.  The tables are read
  * when the kernels run, so a captured HIP graph follows later writes to them: nothing of the mix is a kernel argument.
- * ddsp_unit2ctrl_fwd_rowmix_ragged adds n_frames as ddsp_unit2ctrl_fwd_ragged does.  The launches and tile choices are those of
- * ddsp_unit2ctrl_fwd. */
+ * n_frames (or NULL) as ddsp_unit2ctrl_fwd takes it.  The launches and tile choices are those of ddsp_unit2ctrl_fwd. */
 int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
                               const float* f0_frames, const float* phase_frames, const float* volume,
-                              const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr, float* ctrl);
-int ddsp_unit2ctrl_fwd_rowmix_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
-                                     const float* f0_frames, const float* phase_frames, const float* volume,
-                                     const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
-                                     const int32_t* n_frames, float* ctrl);
+                              const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                              const int32_t* n_frames, float* ctrl);
 int ddsp_ragged_crop(ddsp_ctx* ctx, void* stream, float* x0, float* x1, float* x2, const int32_t* n_frames, int64_t B,
                      int64_t Fr, int hop);
 int ddsp_ragged_noise(ddsp_ctx* ctx, void* stream, const float* noise, uint64_t noise_seed, const int32_t* n_frames,
@@ -236,11 +228,15 @@ int ddsp_ragged_noise(ddsp_ctx* ctx, void* stream, const float* noise, uint64_t 
  * re-runs the forward keeping its activations in the scratch arena, then back-propagates d_ctrl (B,Fr,n_out) to
  * every parameter.  `grads_host` has the layout of ddsp_u2c_weights; each pointer receives the gradient of the
  * like-named parameter (written, not accumulated; fast_attention.projection_matrix is a buffer: `proj` is ignored).
- * ctrl_out (B,Fr,n_out) or NULL additionally receives the forward result.  Inputs carry no gradient. */
+ * ctrl_out (B,Fr,n_out) or NULL additionally receives the forward result.  Inputs carry no gradient.
+ * Ragged training (all three training calls; n_frames as for ddsp_unit2ctrl_fwd, or NULL): the forward keeps or re-runs the
+ * ragged forward; units of frames >= n_frames[b] must hold 0 and f0, phase and volume finite values there (ddsp_ragged_frames),
+ * and d_ctrl must be 0 on those frames (ddsp_ragged_frames with hold = 0, or ddsp_ragged_frames_adjoint).  Every gradient is
+ * then the sum over rows of the gradient the row gives alone at its own length. */
 int ddsp_unit2ctrl_bwd(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
                        const float* f0_frames, const float* phase_frames, const float* volume,
                        const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const float* d_ctrl,
+                       const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, const float* d_ctrl,
                        const ddsp_u2c_weights* grads_host, float* ctrl_out);
 
 /* A training step without the second forward: ddsp_unit2ctrl_fwd_keep is ddsp_unit2ctrl_fwd in fp32 products that leaves
@@ -252,33 +248,13 @@ int64_t ddsp_unit2ctrl_keep_bytes(const ddsp_u2c_weights* w, int64_t B, int64_t 
 int ddsp_unit2ctrl_fwd_keep(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* w, const float* units,
                             const float* f0_frames, const float* phase_frames, const float* volume,
                             const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                            const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep, int64_t keep_bytes,
-                            float* ctrl);
+                            const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, void* keep,
+                            int64_t keep_bytes, float* ctrl);
 int ddsp_unit2ctrl_bwd_kept(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* w, const float* units,
                             const float* f0_frames, const float* phase_frames, const float* volume,
                             const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                            const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, void* keep, int64_t keep_bytes,
-                            const float* d_ctrl, const ddsp_u2c_weights* grads_host);
-
-/* Ragged training (n_frames as for ddsp_unit2ctrl_fwd_ragged, or NULL: the calls above).  The forward keeps or re-runs the
- * ragged forward; units of frames >= n_frames[b] must hold 0 and f0, phase and volume finite values there (ddsp_ragged_frames),
- * and d_ctrl must be 0 on those frames (ddsp_ragged_frames with hold = 0, or ddsp_ragged_frames_adjoint).  Every gradient is
- * then the sum over rows of the gradient the row gives alone at its own length. */
-int ddsp_unit2ctrl_fwd_keep_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* w, const float* units,
-                                   const float* f0_frames, const float* phase_frames, const float* volume,
-                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                   const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                                   void* keep, int64_t keep_bytes, float* ctrl);
-int ddsp_unit2ctrl_bwd_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
-                              const float* f0_frames, const float* phase_frames, const float* volume,
-                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                              const float* d_ctrl, const ddsp_u2c_weights* grads_host, float* ctrl_out);
-int ddsp_unit2ctrl_bwd_kept_ragged(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* w, const float* units,
-                                   const float* f0_frames, const float* phase_frames, const float* volume,
-                                   const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
-                                   const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames,
-                                   void* keep, int64_t keep_bytes, const float* d_ctrl, const ddsp_u2c_weights* grads_host);
+                            const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, void* keep,
+                            int64_t keep_bytes, const float* d_ctrl, const ddsp_u2c_weights* grads_host);
 /* Adjoint of ddsp_ragged_frames with hold = 1, in place on a gradient d (B, Fr, C): d[b][n_b - 1][:] += sum_{i >= n_b} d[b][i][:]
  * (i ascending: a fixed order), then d[b][i >= n_b][:] = 0.  ddsp_ragged_crop is its own adjoint. */
 int ddsp_ragged_frames_adjoint(ddsp_ctx* ctx, void* stream, float* d, const int32_t* n_frames, int64_t B, int64_t Fr, int64_t C);
@@ -376,33 +352,28 @@ int ddsp_spectral_ola_bwd(ddsp_ctx* ctx, void* stream, const float* ctrl, int64_
  * hop = N when hops_host is NULL (overlap = 0, what every reference caller uses); magnitude / sqrt(sum w^2) + eps;
  * L_N = mean_b ||S_t-S_p||_F/||S_t+S_p||_F + alpha*mean|ln S_t - ln S_p|; loss = mean_N.
  * x_pred, x_true (B,T) 16-byte aligned, T % 4 == 0; loss: device float[1]; grad_pred (B,T) or NULL receives
- * d loss / d x_pred (the caller's autograd scales it by the upstream gradient). */
+ * d loss / d x_pred (the caller's autograd scales it by the upstream gradient).
+ * Rows of different length: n_samples_host (B ints, 1 <= n <= T) and the same counts on the device (n_samples_dev, int32), both
+ * or neither (NULL: every row holds T samples).  Row b has F_b = (n_b - N) / hop + 1 frames at scale N (0 when n_b < N).  The
+ * convergence term is the mean over the rows with F_b > 0, each norm over the row's own frames; the log term the mean over the
+ * sum_b F_b * (N/2 + 1) cells that exist.  Samples from (F_b - 1) * hop + N on are not read into arithmetic (selection), and
+ * grad_pred is 0 there.  With every count == T the result has the bits of the call without counts.  A scale at which no row has
+ * a frame: DDSP_ERR_ARG before anything is launched.
+ * The rows as ONE RANK'S SHARE of a global batch (data-parallel training on ragged shards): global_n_samples_host (with the
+ * local counts only; NULL: the local rows are the whole batch, n_global is not read), the n_global >= B sample counts (each
+ * >= 1; they may exceed T, another rank pads to its own longest row) of every rank's rows, the local rows among them.  Both
+ * denominators - the rows with a frame and the cells that exist at scale N - are taken over the GLOBAL counts, the sums over the
+ * local rows: loss is this rank's share of the loss of the global batch and grad_pred the gradient of that share.  Shares summed
+ * over the ranks give the one-process loss; gradients summed over the ranks (no division by the number of ranks) its gradient.
+ * A scale at which no GLOBAL row has a frame: DDSP_ERR_ARG before anything is launched.  A scale at which no LOCAL row has a
+ * frame (n_fft > T included) contributes 0 and is not launched.  With global_n_samples_host equal to n_samples_host the result
+ * has the bits of the call without it. */
 int ddsp_rss_loss(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
+                  const int* n_samples_host, const int32_t* n_samples_dev, const int* global_n_samples_host, int64_t n_global,
                   const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps, float* loss,
                   float* grad_pred);
-/* The same for rows of different length: n_samples_host (B ints, 1 <= n <= T) and the same counts on the device
- * (n_samples_dev, int32).  Row b has F_b = (n_b - N) / hop + 1 frames at scale N (0 when n_b < N).  The convergence term is the
- * mean over the rows with F_b > 0, each norm over the row's own frames; the log term the mean over the sum_b F_b * (N/2 + 1)
- * cells that exist.  Samples from (F_b - 1) * hop + N on are not read into arithmetic (selection), and grad_pred is 0 there.
- * With every count == T the result has the bits of ddsp_rss_loss.  A scale at which no row has a frame: DDSP_ERR_ARG before
- * anything is launched. */
-int ddsp_rss_loss_ragged(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
-                         const int* n_samples_host, const int32_t* n_samples_dev, const int* n_ffts_host, const int* hops_host,
-                         int n_scale, float alpha, float eps, float* loss, float* grad_pred);
-/* The rows as ONE RANK'S SHARE of a global batch (data-parallel training on ragged shards): the arguments of
- * ddsp_rss_loss_ragged plus global_n_samples_host, the n_global >= B sample counts (each >= 1; they may exceed T, another rank
- * pads to its own longest row) of every rank's rows, the local rows among them.  Both denominators - the rows with a frame and the
- * cells that exist at scale N - are taken over the GLOBAL counts, the sums over the local rows: loss is this rank's share of the
- * loss of the global batch and grad_pred the gradient of that share.  Shares summed over the ranks give the one-process loss;
- * gradients summed over the ranks (no division by the number of ranks) its gradient.  A scale at which no GLOBAL row has a frame:
- * DDSP_ERR_ARG before anything is launched.  A scale at which no LOCAL row has a frame (n_fft > T included) contributes 0 and is
- * not launched.  With global_n_samples_host equal to n_samples_host the result has the bits of ddsp_rss_loss_ragged. */
-int ddsp_rss_loss_share(ddsp_ctx* ctx, void* stream, const float* x_pred, const float* x_true, int64_t B, int64_t T,
-                        const int* n_samples_host, const int32_t* n_samples_dev, const int* global_n_samples_host,
-                        int64_t n_global, const int* n_ffts_host, const int* hops_host, int n_scale, float alpha, float eps,
-                        float* loss, float* grad_pred);
 /* One loss per row instead of the batch's scalar (validation: every utterance counts once; no gradient): the arguments of
- * ddsp_rss_loss_ragged, loss_rows a device float[B].  loss_rows[b] = mean_N (||S_t - S_p||_F / ||S_t + S_p||_F +
+ * ddsp_rss_loss with both counts, loss_rows a device float[B].  loss_rows[b] = mean_N (||S_t - S_p||_F / ||S_t + S_p||_F +
  * alpha * mean|ln S_t - ln S_p|), both terms over row b's own F_b * (N/2 + 1) cells - the loss of x[b][0..n_b) scored alone.
  * The framing, transform and statistics kernels are those of the calls above; only the last kernel differs.  A row without a
  * frame at one of the scales (n_b < N): DDSP_ERR_ARG before anything is launched. */
@@ -418,39 +389,32 @@ int ddsp_vc_f0_map(ddsp_ctx* ctx, void* stream, const float* f0, const int64_t* 
                    int64_t Fr, const int32_t* n_frames, float* f0_out, int64_t* tgt_spk);
 
 /* ---- a14: SOLA splice of the real-time path -------------------------------------------------- */
+/* S streams of one geometry in one call (realtime.StreamBank; S = 1: the reference's single stream): every tensor has a leading
+ * dimension S (1 <= S <= DDSP_MAX_STREAMS), contiguous rows, with the stream as a grid dimension of the kernels.  Per row the
+ * arithmetic and the order of every reduction do not depend on S, so row s of every output equals the S = 1 call on row s bit
+ * for bit, and no row reads another row's audio, score or buffer. */
+#define DDSP_MAX_STREAMS 4096
 /* replaces gui.py:405-430: within audio[-block-xfade-search-delay : -delay] find the lag (0..search) that
  * maximises the energy-normalised correlation with sola_buffer (xfade,), cross-fade (sin^2 windows,
  * gui.py:349-351) the head with sola_buffer, emit `block` samples, and keep the next xfade samples in
- * sola_buffer (updated in place).  shift: device int32 (no host sync). */
-int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int64_t n_audio, int block, int xfade, int search,
+ * sola_buffer (updated in place).  audio (S, n_audio), sola_buffer (S, xfade), emitted (S, block), shift (S): device int32 (no
+ * host sync); each row splices at its own arg-max (first maximum) and hands over its own tail.  S > 1: search < 65535 and
+ * n_audio < 2^31. */
+int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade, int search,
               int delay, float* sola_buffer, float* emitted, int* shift);
 
 /* the sliding input window of the real-time callback (gui.py:373-374), in place on a buffer whose address never changes
- * (a captured graph reads it): window[:] = append(window[block:], block_in); window (n_in), block_in (block) outside the
- * window, 1 <= block < n_in (DDSP_ERR_ARG otherwise, nothing written).  The kept part is staged through the context's
- * scratch arena (two launches in stream order), so the overlapping shift is exact whatever order workgroups run in. */
-int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int64_t n_in, const float* block_in, int64_t block);
-
-/* ---- the same glue for S streams of one geometry in one call (realtime.StreamBank) ------------------------------------------
- * Every tensor gains a leading dimension S (1 <= S <= DDSP_MAX_STREAMS), contiguous rows.  The kernels are those of the solo
- * calls with the stream as a grid dimension: per row the arithmetic and the order of every reduction are the solo call's, so row
- * s of every output equals the solo call on row s bit for bit, and no row reads another row's audio, score or buffer.
- *   ddsp_stream_push_batch    windows (S, n_in) take blocks (S, block) in place, staged through the arena like ddsp_stream_push.
- *   ddsp_sola_batch           audio (S, n_audio), sola_buffer (S, xfade) in place, emitted (S, block), shift (S) int32: each row
- *                             splices at its own arg-max (first maximum) and hands over its own tail.
- *   ddsp_phase_vocoder_batch  a, b, out (S, n); the fade windows (n) are shared. */
-#define DDSP_MAX_STREAMS 4096
-int ddsp_stream_push_batch(ddsp_ctx* ctx, void* stream, float* windows, int S, int64_t n_in, const float* blocks, int64_t block);
-int ddsp_sola_batch(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_audio, int block, int xfade, int search,
-                    int delay, float* sola_buffer, float* emitted, int* shift);
+ * (a captured graph reads it): window[s][:] = append(window[s][block:], block_in[s]); window (S, n_in), block_in (S, block)
+ * outside the windows, 1 <= block < n_in (DDSP_ERR_ARG otherwise, nothing written).  The kept part is staged through the
+ * context's scratch arena (two launches in stream order), so the overlapping shift is exact whatever order workgroups run in. */
+int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int S, int64_t n_in, const float* block_in, int64_t block);
 
 /* ---- a15: volume gate ------------------------------------------------------------------------ */
 /* replaces gui.py:14-31 `phase_vocoder(a, b, fade_out, fade_in)` (the optional cross-fade of gui.py:417-423; SURVEY
- * 8(f) rank 3): a = kept tail, b = head of the new block, both (n), fade windows (n), out (n).  n <= 65536. */
+ * 8(f) rank 3): a = kept tail, b = head of the new block, out, all (S, n) as for ddsp_sola; the fade windows (n) are shared.
+ * n <= 65536. */
 int ddsp_phase_vocoder(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
-                       const float* fade_in, int n, float* out);
-int ddsp_phase_vocoder_batch(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* fade_out,
-                             const float* fade_in, int S, int n, float* out);
+                       const float* fade_in, int S, int n, float* out);
 
 /* replaces main.py:111-116,159 / gui.py:108-112,127: signal (B,T) *= upsample(dilate9(volume > threshold)),
  * in place (threshold = 10^(dB/20), linear); volume (B,Fr). */
@@ -491,14 +455,12 @@ int ddsp_stitch(ddsp_ctx* ctx, void* stream, const ddsp_stitch_piece* pieces, in
 /* ---- the device-side steps immediately before the synthesis path ------------- */
 /* replaces ddsp/vocoder.py:116-137 `Volume_Extractor.extract`: audio (B,T) -> volume (B, T/hop + 1), the RMS of
  * non-overlapping hop-sized blocks of the signal reflect-padded by (hop/2, (hop+1)/2) (numpy 'reflect': T must
- * exceed (hop+1)/2). */
-int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int hop,
+ * exceed (hop+1)/2).
+ * n_samples: NULL, or a ragged batch - a DEVICE array of B int32 (the caller checks (hop+1)/2 < n_samples[b] <= T); row b then
+ * reflects at its own ends (i >= n_b -> 2 (n_b - 1) - i), has n_samples[b] / hop + 1 frames and exact zeros after them;
+ * audio[b][i] for i >= n_samples[b] is never read. */
+int ddsp_volume_extract(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int hop,
                         float* volume);
-/* ddsp_volume_extract over a ragged batch: n_samples is a DEVICE array of B int32 (the caller checks (hop+1)/2 <
- * n_samples[b] <= T); row b reflects at its own ends (i >= n_b -> 2 (n_b - 1) - i), has n_samples[b] / hop + 1 frames
- * and exact zeros after them; audio[b][i] for i >= n_samples[b] is never read.  volume (B, T/hop + 1). */
-int ddsp_volume_extract_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T,
-                               const int32_t* n_samples, int hop, float* volume);
 /* ddsp_volume_extract at the non-integral hop `block_size * sample_rate / model_rate` that an input at another rate than the model's
  * gives (main.py:72,109, gui.py:94): volume (B, int(T // hop_size) + 1), block n = padded[int(n * hop_size) :
  * int((n + 1) * hop_size)] of the signal reflect-padded by (int(hop_size // 2), int((hop_size + 1) // 2)), all in fp64
@@ -508,29 +470,25 @@ int ddsp_volume_extract_frac(ddsp_ctx* ctx, void* stream, const float* audio, in
                              float* volume);
 /* replaces the alignment tail of ddsp/vocoder.py:201-211 `Units_Encoder.encode`: out[b][i][:] = units[b][j][:] with
  * j = min(rint(ratio * i), Lu - 1), ratio = (hop/sample_rate) / (encoder_hop/encoder_sample_rate) as fp32, rint =
- * round half to even (torch.round); units (B,Lu,C) -> out (B,n_frames,C). */
-int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
-                     int64_t n_frames, float ratio, float* out);
-/* ddsp_align_units over a ragged batch: row b has n_out[b] <= n_frames frames of its own, taken from its own n_units[b] <= Lu
- * unit rows (j = min(rint(ratio * i), n_units[b] - 1)), and exact zeros from frame n_out[b] on.  n_units, n_out: DEVICE arrays
- * of B int32. */
-int ddsp_align_units_ragged(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C,
-                            int64_t n_frames, float ratio, const int32_t* n_units, const int32_t* n_out, float* out);
+ * round half to even (torch.round); units (B,Lu,C) -> out (B,n_frames,C).
+ * n_units, n_out: both NULL, or (a ragged batch) DEVICE arrays of B int32: row b has n_out[b] <= n_frames frames of its own,
+ * taken from its own n_units[b] <= Lu unit rows (j = min(rint(ratio * i), n_units[b] - 1)), and exact zeros from frame n_out[b]
+ * on. */
+int ddsp_align_units(ddsp_ctx* ctx, void* stream, const float* units, int64_t B, int64_t Lu, int64_t C, int64_t n_frames,
+                     float ratio, const int32_t* n_units, const int32_t* n_out, float* out);
 
 /* replaces the host-side f0 re-timing of enhancer.py:56-62 (`f0_np *= real_factor`; `np.interp(time_frame, time_org, f0_np,
  * left=f0_np[0], right=f0_np[-1])`): out[i] = interp(i * step_dst) over the knots x_j = (step_num * j) / div with values
- * fl32(f0[j] * scale), evaluated in fp64 like numpy; f0 (n_src,) -> out (n_dst,).  No host copy of the track. */
-int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t n_src, double step_num, double div, float scale,
-                   double step_dst, int64_t n_dst, float* out);
-/* ddsp_retime_f0 over a ragged batch: f0 (B, n_src) -> out (B, n_dst); row b has n_src_rows[b] <= n_src knots and
- * n_dst_rows[b] <= n_dst targets of its own (DEVICE arrays of B int32): the ends are held at the row's own first and last
- * frame, f0 past the row's knots is never read, and the outputs from n_dst_rows[b] on are 0. */
-int ddsp_retime_f0_ragged(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
-                          double step_num, double div, float scale, double step_dst, int64_t n_dst, const int32_t* n_dst_rows,
-                          float* out);
-/* ddsp_retime_f0_ragged with the (div, scale) of row b taken from two DEVICE tables of n_keys entries by the row's key,
+ * fl32(f0[j] * scale), evaluated in fp64 like numpy; f0 (n_src,) -> out (n_dst,) with B = 1 and n_src_rows = n_dst_rows = NULL.
+ * No host copy of the track.
+ * A ragged batch (n_src_rows, n_dst_rows: both or neither, DEVICE arrays of B int32; n_dst >= 1): f0 (B, n_src) -> out (B, n_dst);
+ * row b has n_src_rows[b] <= n_src knots and n_dst_rows[b] <= n_dst targets of its own: the ends are held at the row's own first
+ * and last frame, f0 past the row's knots is never read, and the outputs from n_dst_rows[b] on are 0. */
+int ddsp_retime_f0(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
+                   double step_num, double div, float scale, double step_dst, int64_t n_dst, const int32_t* n_dst_rows, float* out);
+/* A ragged ddsp_retime_f0 with the (div, scale) of row b taken from two DEVICE tables of n_keys entries by the row's key,
  * key[b] (a DEVICE array of B int32, clamped into 0..n_keys-1 before it indexes anything): per row what
- * ddsp_retime_f0_ragged gives with div_by_key[key[b]] (fp64) and scale_by_key[key[b]] (fp32). */
+ * ddsp_retime_f0 gives with div_by_key[key[b]] (fp64) and scale_by_key[key[b]] (fp32). */
 int ddsp_retime_f0_keyed(ddsp_ctx* ctx, void* stream, const float* f0, int64_t B, int64_t n_src, const int32_t* n_src_rows,
                          double step_num, const int32_t* key, int n_keys, const double* div_by_key, const float* scale_by_key,
                          double step_dst, int64_t n_dst, const int32_t* n_dst_rows, float* out);
@@ -551,13 +509,11 @@ int ddsp_enhancer_keys(ddsp_ctx* ctx, void* stream, const float* f0, int64_t S, 
  * is not in the image, so parity at that boundary is unpinned): x (B,T) -> out (B, ddsp_resample_length(T, orig, new)).
  * The tap table of a rate pair is built on first use and cached in the context. */
 int64_t ddsp_resample_length(int64_t T, int orig_freq, int new_freq);
-int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, int orig_freq, int new_freq,
-                  int lowpass_filter_width, float* out);
-/* ddsp_resample over a ragged batch: n_samples is a DEVICE array of B int32, row b holds n_samples[b] <= T samples of its
- * own.  x[b][i] is selected as 0 for i >= n_samples[b] where it is loaded (the padding may hold anything), so the row's
+/* n_samples: NULL, or a ragged batch - a DEVICE array of B int32, row b holds n_samples[b] <= T samples of its own.
+ * x[b][i] is selected as 0 for i >= n_samples[b] where it is loaded (the padding may hold anything), so the row's
  * first ddsp_resample_length(n_samples[b], ...) outputs are those of the row resampled alone; the outputs after them are 0. */
-int ddsp_resample_ragged(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples,
-                         int orig_freq, int new_freq, int lowpass_filter_width, float* out);
+int ddsp_resample(ddsp_ctx* ctx, void* stream, const float* x, int64_t B, int64_t T, const int32_t* n_samples, int orig_freq,
+                  int new_freq, int lowpass_filter_width, float* out);
 /* Keyed batches: one launch in which row b is resampled with the rate pair key[b] of a set of up to 13 pairs with one lowpass
  * width (the enhancer's working rates, one per adaptive key).
  * ddsp_resample_keyed_plan builds the set: the tap tables of all its pairs, the ones ddsp_resample builds for each pair, in
@@ -580,8 +536,8 @@ int ddsp_resample_keyed(ddsp_ctx* ctx, void* stream, const ddsp_resample_plan* p
                         const int32_t* n_samples, const int32_t* key, float* out);
 
 /* ---- the NSF-HiFiGAN post-net (enhancer.py:24-101, nsf_hifigan/models.py:106-276, nvSTFT.py:65-119) ---- */
-/* One utterance per call, or - the `_ragged` entry points at the end of this section - a padded batch of rows of different
- * length; activations frame-major (T, C) fp32.
+/* One utterance per call (B = 1, n_frames = NULL, frame_scale = 1), or a padded batch of rows of different length ("Ragged
+ * batches of the post-net" below); activations frame-major (T, C) fp32.
  * ddsp_conv1d: replaces `Conv1d(Cin, Cout, k, dilation=d, padding="same")(leaky_relu(x, in_slope))` (+ residual): the
  *   resblock convolutions (models.py:45-77), conv_pre (:234) and - with weights packed as the host mirror's
  *   `_pack_conv_transpose` does - the ConvTranspose1d upsamplers (:240-243).  x (T,Cin), w_packed (Cout, k*Cin) with column
@@ -607,9 +563,9 @@ int ddsp_resample_keyed(ddsp_ctx* ctx, void* stream, const ddsp_resample_plan* p
  *   out (n_frames, n_mels) = log(max(mel . sqrt(re^2 + im^2 + 1e-9), clip)). */
 #define DDSP_CONV_X_SPLIT 1   /* x is in the split layout (written so by a producer with DDSP_CONV_ACT_SPLIT) */
 #define DDSP_CONV_ACT_SPLIT 2 /* write out_act in the split layout */
-int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t T, int Cin,
-                int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out, float* out_act,
-                float act_slope, const float* w_split, int flags);
+int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B, int64_t T,
+                int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out, float* out_act,
+                float act_slope, const float* w_split, int flags, const int32_t* n_frames, int frame_scale);
 /* One residual pair of `ResBlock1` (nsf_hifigan/models.py:41-90: xt = c1(leaky_relu(x)); xt = c2(leaky_relu(xt)); x = xt + x) of a
  * narrow stage in one launch: x (T,C) raw, c1 with `dil`, c2 with dilation 1, both `ktaps` taps, weights packed as for
  * ddsp_conv1d; out = the new x, out_act = leaky_relu(out, slope) (either may be null).  Only x is read and the results
@@ -617,14 +573,16 @@ int ddsp_conv1d(ddsp_ctx* ctx, void* stream, const float* x, const float* w_pack
  * ddsp_conv1d_pair_supported: 1 when (C, ktaps, dil) is a geometry the fused kernel takes (else use two ddsp_conv1d calls). */
 int ddsp_conv1d_pair_supported(ddsp_ctx* ctx, int C, int ktaps, int dil);
 int ddsp_conv1d_pair(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
-                     const float* b2, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act);
+                     const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil, float slope, float* out, float* out_act,
+                     const int32_t* n_frames, int frame_scale);
 
 int ddsp_nsf_source(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
-                    const float* lin_b, int64_t L, int upp, int sr, float sine_amp, float* out);
-int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src, int64_t T_src, const float* w, const float* b, int C,
-                        int K, int stride, int pad, int64_t T_out, float* out);
-int ddsp_nsf_post(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t T, int C, int K,
-                  float slope, float* out);
+                    const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp, const int32_t* n_frames,
+                    float* out);
+int ddsp_nsf_noise_conv(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w, const float* b,
+                        int C, int K, int stride, int pad, int64_t T_out, float* out);
+int ddsp_nsf_post(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T, int C, int K,
+                  float slope, float* out, const int32_t* n_frames, int frame_scale);
 int ddsp_nsf_mean(ddsp_ctx* ctx, void* stream, const float* a, const float* b, const float* c, int n_terms, int64_t n,
                   float* out, float* out_act, float act_slope, int flags);
 int ddsp_log_mel(ddsp_ctx* ctx, void* stream, const float* frames, const float* dft_table, const float* mel_basis,
@@ -638,38 +596,24 @@ int ddsp_log_mel(ddsp_ctx* ctx, void* stream, const float* frames, const float* 
  *   - every entry point WRITES exactly 0 at t >= T_b of each output, whatever bias, residual or source would put there.
  * A tap that leaves [0, T_b) then reads 0 as a solo call's "same" padding does, and no tap reaches a neighbouring row, so
  * row b of each output is, over [0, T_b), what the solo entry point returns for that row alone at its own length.  A caller
- * whose first input may hold anything past T_b zeroes it first (ddsp_ragged_frames with hold = 0).  Each solo entry point
- * above is the B = 1, n_frames = NULL case of its ragged form.
- * ddsp_conv1d_ragged: x (B*T, Cin), residual / out / out_act (B*T, Cout).  For a transposed convolution in its 3-tap form
+ * whose first input may hold anything past T_b zeroes it first (ddsp_ragged_frames with hold = 0).
+ * ddsp_conv1d: x (B*T, Cin), residual / out / out_act (B*T, Cout).  For a transposed convolution in its 3-tap form
  *   the (B*T, u*Cout) result is the (B*T*u, Cout) output, row t holding samples t*u .. t*u+u-1 of the same batch row: the mask
  *   stays per input row (frame_scale of the INPUT).
- * ddsp_conv1d_pair_ragged: windows are cut per batch row, halo reads stop at the row's own ends, and the intermediate
+ * ddsp_conv1d_pair: windows are cut per batch row, halo reads stop at the row's own ends, and the intermediate
  *   leaky_relu(c1(x) + b1) is zeroed at t >= T_b before c2 reads it.
- * ddsp_nsf_source_ragged: f0 (B, L), rand_ini (B, 9): one phase scan per row from the row's own initial phases; f0 past
+ * ddsp_nsf_source: f0 (B, L), rand_ini (B, 9): one phase scan per row from the row's own initial phases; f0 past
  *   n_frames[b] is never read; out (B, L*upp) is 0 from n_frames[b] * upp on.
- * ddsp_nsf_noise_conv_ragged: src (B, T_src) -> out (B*T_out, C), taps row-local (no counts: its consumer masks).
- * ddsp_nsf_post_ragged: x (B*T, C) -> out (B, T), tanh(. + b) replaced by 0 at t >= T_b.
+ * ddsp_nsf_noise_conv: src (B, T_src) -> out (B*T_out, C), taps row-local (no counts: its consumer masks).
+ * ddsp_nsf_post: x (B*T, C) -> out (B, T), tanh(. + b) replaced by 0 at t >= T_b.
  * (ddsp_nsf_mean needs no ragged form: the mean of masked tensors is masked.)
- * ddsp_stft_frames_ragged: the framing of `STFT.get_mel` (nvSTFT.py:88-98) for audio (B, T) with n_samples[b] <= T samples
+ * ddsp_stft_frames: the framing of `STFT.get_mel` (nvSTFT.py:88-98) for audio (B, T) with n_samples[b] <= T samples
  *   per row (DEVICE int32, NULL: T): per row pad_left = (n_fft - hop) / 2, pad_right = max((n_fft - hop + 1) / 2,
  *   n_fft - n_b - pad_left), reflect padding where pad_right < n_b and zeros otherwise - chosen PER ROW -, frames (B, L, n_fft)
  *   with L_b = (n_b + pad_left + pad_right - n_fft) / hop + 1 frames of the row and 0 in frames >= L_b.  Audio past n_b is
  *   never read.  ddsp_log_mel then runs on the B * L rows. */
-int ddsp_conv1d_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w_packed, const float* bias, int64_t B, int64_t T,
-                       int Cin, int Cout, int ktaps, int dil, float in_slope, const float* residual, float* out, float* out_act,
-                       float act_slope, const float* w_split, int flags, const int32_t* n_frames, int frame_scale);
-int ddsp_conv1d_pair_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w1, const float* b1, const float* w2,
-                            const float* b2, int64_t B, int64_t T, int C, int ktaps, int dil, float slope, float* out,
-                            float* out_act, const int32_t* n_frames, int frame_scale);
-int ddsp_nsf_source_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* rand_ini, const float* lin_w,
-                           const float* lin_b, int64_t B, int64_t L, int upp, int sr, float sine_amp, const int32_t* n_frames,
-                           float* out);
-int ddsp_nsf_noise_conv_ragged(ddsp_ctx* ctx, void* stream, const float* src, int64_t B, int64_t T_src, const float* w,
-                               const float* b, int C, int K, int stride, int pad, int64_t T_out, float* out);
-int ddsp_nsf_post_ragged(ddsp_ctx* ctx, void* stream, const float* x, const float* w, const float* b, int64_t B, int64_t T, int C,
-                         int K, float slope, float* out, const int32_t* n_frames, int frame_scale);
-int ddsp_stft_frames_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
-                            int n_fft, int hop, int64_t L, float* out);
+int ddsp_stft_frames(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int n_fft,
+                     int hop, int64_t L, float* out);
 
 /* ---- a15: optimiser step --------------------------------------------------------------------- */
 /* replaces one parameter's update of torch.optim.AdamW (train.py:41, solver.py:114): decoupled weight decay,
@@ -678,15 +622,13 @@ int ddsp_adamw_step(ddsp_ctx* ctx, void* stream, float* param, const float* grad
                     int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step);
 /* the same update for n_tensors parameters that share hyper-parameters and step (one optimizer.step() of
  * solver.py:114 over a param group), a handful of launches instead of one per tensor.  params / grads / exp_avg /
- * exp_avg_sq are HOST arrays of n_tensors device pointers, numel a host array of element counts (0 allowed). */
+ * exp_avg_sq are HOST arrays of n_tensors device pointers, numel a host array of element counts (0 allowed).
+ * grad_scale (finite): every gradient is multiplied by it as it is read - the 1 / world of a data-parallel mean applied to a
+ * bucket that holds the SUM over the ranks, without a pass of its own over the gradients; grads are not written.  Exactly 1.0f
+ * runs the kernel that does not multiply. */
 int ddsp_adamw_step_multi(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params, const float* const* grads,
                           float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel, float lr,
-                          float beta1, float beta2, float eps, float weight_decay, int64_t step);
-/* the same launches with every gradient multiplied by grad_scale (finite) as it is read: the 1 / world of a data-parallel mean
- * applied to a bucket that holds the SUM over the ranks, without a pass of its own over the gradients.  grads are not written. */
-int ddsp_adamw_step_multi_scaled(ddsp_ctx* ctx, void* stream, int n_tensors, float* const* params, const float* const* grads,
-                                 float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel, float lr,
-                                 float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale);
+                          float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale);
 
 /* ---- building block: fp32-in / fp32-accumulate MFMA GEMM ---------------------------------------- */
 /* C[m][n] = sum_k A(m,k) B(k,n) (+ bias[n]).  a_k_contig: A(m,k) = A[m*lda+k] else A[k*lda+m];
@@ -779,21 +721,22 @@ int64_t ddsp_hubert_frames(int64_t T);
 /* replaces `HubertSoft.units(wav (B,1,T))` (encoder/hubert/model.py): wav (B,T) 16 kHz -> units (B, Fr, 256),
  * Fr = ddsp_hubert_frames(T).  The GEMMs use the context's product arithmetic (ddsp_ctx_set_math); conv0, the norms and
  * the softmax attention run in fp32.  No host synchronisation once the scratch arena (and the prepared-weight slot) exist,
- * so the call can be captured into a HIP graph. */
+ * so the call can be captured into a HIP graph.  n_samples: NULL, or a ragged batch ("the units encoder over a ragged batch"). */
 int ddsp_hubert_soft_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
-                           float* units);
+                           const int32_t* n_samples, float* units);
 /* `Hubert.encode(wav, layer)` without the final projection, for tests and callers of intermediate features:
  * layer -1 = the conv stack's output (B, Fr, 512); 0..12 = the hidden state (B, Fr, 768) after that many transformer layers. */
 int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
-                       int layer, float* out);
+                       const int32_t* n_samples, int layer, float* out);
 /* building block: softmax attention softmax(q k^T / 8) v per (utterance, head), no mask, any L (online softmax: no L x L
  * matrix).  q, k, v, out (B*L, heads*64) rows, head h at columns 64h..64h+63.  math: DDSP_MATH_FP32 or
  * DDSP_MATH_SPLIT_BF16; both run fp32 products (the attention is ~3 % of the encoder's work at a 4.5 s window).  Exposed for
- * unit tests. */
+ * unit tests.  n_keys: NULL, or a DEVICE array of B int32 (held inside 0..L): utterance b attends over its first n_keys[b] rows,
+ * which are also the only rows of `out` that are written. */
 int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B, int64_t L,
-                           int heads, float* out, int math);
+                           int heads, float* out, int math, const int32_t* n_keys);
 
-/* ---- the units encoder over a ragged batch (inference only, like the encoder) ---------------------------------------------
+/* ---- the units encoder over a ragged batch (ddsp_hubert_soft_units / ddsp_hubert_encode with n_samples) -------------------
  * n_samples: DEVICE array of B int32, the 16 kHz samples of each row inside the padded (B, T) wav; the caller checks
  * 1 <= n_samples[b] <= T and ddsp_hubert_frames(n_samples[b]) >= 1 (the kernels hold a count inside 0..T).  The per-row frame
  * counts are derived on the device and nothing is read back, so the call can be captured like the rectangular one.
@@ -803,14 +746,6 @@ int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const fl
  * zero padding, the GroupNorm statistics (partitioned and divided as for the row alone), the zero edge of the positional
  * convolution, the keys of the softmax attention.  The GEMMs run over all B * Fr padded rows.  `units` / `out` must be
  * 16-byte aligned (DDSP_ERR_ARG otherwise). */
-int ddsp_hubert_soft_units_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
-                                  int64_t T, const int32_t* n_samples, float* units);
-int ddsp_hubert_encode_ragged(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
-                              const int32_t* n_samples, int layer, float* out);
-/* ddsp_softmax_attention with a per-utterance key count: n_keys is a DEVICE array of B int32 (held inside 0..L); utterance b
- * attends over its first n_keys[b] rows, which are also the only rows of `out` that are written. */
-int ddsp_softmax_attention_ragged(ddsp_ctx* ctx, void* stream, const float* q, const float* k, const float* v, int64_t B,
-                                  int64_t L, int heads, float* out, int math, const int32_t* n_keys);
 
 /* ---- the f0 extractor (CREPE, ddsp/vocoder.py:39-113 with torchcrepe.predict and librosa's Viterbi restated) ---------- */
 /* Device pointers into a CREPE state dict (torchcrepe's keys), fp32, dense: conv_w[i] = `conv{i+1}.weight` (Cout, Cin, k, 1),
@@ -837,57 +772,50 @@ int64_t ddsp_crepe_frames(int64_t T16, int hop);
  * activations, Fr = ddsp_crepe_frames(T, hop).  Each 1024-sample frame (zero padding of 512 on each side of the audio) is
  * normalised by its mean and unbiased standard deviation (fp64 statistics, divisor max(1e-10, std)).  The convolutions and
  * the classifier are GEMMs in the context's product arithmetic; ReLU, batch norm and the 2x1 max-pool are their epilogue.
- * No host synchronisation once the scratch arena (and the prepared-weight slot) exist. */
+ * No host synchronisation once the scratch arena (and the prepared-weight slot) exist.
+ * n_samples, frame_prefix, n_packed: all three, or NULL, NULL and an n_packed that is not read ("the f0 extractor over a ragged
+ * batch" below, like n_frames of the decode and n_crepe / n_out of the tail). */
 int ddsp_crepe_activations(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16, int64_t B, int64_t T,
-                           int hop, float* probs);
+                           const int32_t* n_samples, const int32_t* frame_prefix, int64_t n_packed, int hop, float* probs);
 /* torchcrepe.postprocess with the Viterbi decoder: bins [:minidx] and [maxidx:] of probs (B, Fr, 360) masked (minidx =
  * floor, maxidx = ceil of (1200 log2(f / 10) - 1997.3794084376191) / 20 in fp32, Python slice rules), emissions
  * log(softmax + fp32 tiny), transitions log(max(12 - |i - j|, 0) / row sum + tiny), uniform start, fp64 values, first index
  * on ties (librosa.sequence.viterbi).  The track is decoded in independent pieces of `segment` frames (torchcrepe.predict
  * decodes each batch of `batch_size` frames on its own; 0 = the whole track).  Outputs (B, Fr): f0 = 10 * 2^(cents / 1200),
  * cents = 20 * bin + 1997.3794084376191 (+ a triangular dither on (-20, 20) cents drawn from a counter hash of
- * `dither_seed` when use_dither != 0); periodicity = the masked activation at the chosen bin; bins (int32, may be null). */
-int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
-                      int64_t segment, uint64_t dither_seed, int use_dither, float* f0, float* periodicity, int32_t* bins);
-/* The same with the dither seed in device memory (8-byte aligned): the decode uses *seed_dev exactly as ddsp_crepe_decode uses
- * dither_seed (bit-identical outputs for the same value), and a one-thread kernel behind it replaces the word by
- * seed * 6364136223846793005 + 1442695040888963407 (mod 2^64), use_dither or not.  Captured into a HIP graph, every replay
- * therefore dithers with a new seed (a by-value seed would be frozen at its capture-time value). */
-int ddsp_crepe_decode_dseed(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, float fmin, float fmax,
-                            int64_t segment, uint64_t* seed_dev, int use_dither, float* f0, float* periodicity, int32_t* bins);
+ * `dither_seed` when use_dither != 0); periodicity = the masked activation at the chosen bin; bins (int32, may be null).
+ * seed_dev: NULL, or the dither seed in device memory (8-byte aligned; dither_seed is then not read): the decode uses *seed_dev
+ * exactly as it uses dither_seed (bit-identical outputs for the same value), and a one-thread kernel behind it replaces the word
+ * by seed * 6364136223846793005 + 1442695040888963407 (mod 2^64), use_dither or not.  Captured into a HIP graph, every replay
+ * therefore dithers with a new seed (a by-value seed would be frozen at its capture-time value).  Not together with n_frames
+ * (DDSP_ERR_ARG). */
+int ddsp_crepe_decode(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, const int32_t* n_frames, float fmin,
+                      float fmax, int64_t segment, uint64_t dither_seed, uint64_t* seed_dev, int use_dither, float* f0,
+                      float* periodicity, int32_t* bins);
 /* The crepe tail of F0_Extractor.extract (ddsp/vocoder.py:96-113): f0, pd (B, Fr) -> out (B, n_frames): MedianPool1d(pd, 4),
  * f0 = NaN where that is < threshold, MaskedAvgPool1d(f0, 4) (reflect padding (1, 2), Fr >= 3), the re-timing
  * out[start_frame + n] = f0[min(rint(n * hop / sr / 0.005), Fr - 1)] for n < n_frames - start_frame (fp64 index arithmetic,
  * hop may be fractional), zeros before start_frame, then with uv_interp != 0 numpy.interp over the zero frames (fp64, when
  * any frame is non-zero) and out = max(out, f0_min). */
-int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, int sr, double hop,
-                       int64_t n_frames, int64_t start_frame, float threshold, int uv_interp, float f0_min, float* out);
+int ddsp_f0_postfilter(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr, const int32_t* n_crepe,
+                       int sr, double hop, int64_t n_frames, int64_t start_frame, const int32_t* n_out, float threshold,
+                       int uv_interp, float f0_min, float* out);
 
 /* ---- the f0 extractor over a ragged batch --------------------------------------------------------------------------------
  * Every count is a DEVICE array of B int32 that the caller has checked and that is never read back; a kernel holds a value
  * outside its range at the nearest bound.  Row b of each result is what the rectangular call returns for the row alone at
  * its own length, and exactly 0 after it; what the inputs hold past a row's end (NaN included) is never read into arithmetic.
- * ddsp_crepe_activations_ragged: audio16 (B, T) with n_samples[b] <= T samples per row -> probs (B, Fr, 360), Fr =
+ * ddsp_crepe_activations: audio16 (B, T) with n_samples[b] <= T samples per row -> probs (B, Fr, 360), Fr =
  *   ddsp_crepe_frames(T, hop), row b with Fr_b = ddsp_crepe_frames(n_samples[b], hop) frames.  A frame depends on its own
  *   1024 samples only, so the network runs over the PACKED list of the rows' real frames: frame_prefix is the DEVICE array
  *   of B + 1 int32 exclusive prefix sums of Fr_b (frame_prefix[0] = 0) and n_packed = frame_prefix[B] its total, which the
  *   host knows.  A frame reads samples < 0 or >= n_samples[b] of its row as 0 by a bounds test.
- * ddsp_crepe_decode_ragged: probs (B, Fr, 360) with n_frames[b] <= Fr frames per row.  The pieces of `segment` frames are cut
+ * ddsp_crepe_decode: probs (B, Fr, 360) with n_frames[b] <= Fr frames per row.  The pieces of `segment` frames are cut
  *   per row, the last one ends at the row's own last frame, and the dither is drawn for the row-local frame: row b equals
  *   ddsp_crepe_decode of probs[b][:n_frames[b]] alone with the same seed, bit for bit.
- * ddsp_f0_postfilter_ragged: f0, pd (B, Fr) with n_crepe[b] in 3..Fr frames per row -> out (B, n_frames) with n_out[b] <=
- *   n_frames frames per row (start_frame = 0): the reflect windows and the re-timing clamp use n_crepe[b], and the
+ * ddsp_f0_postfilter: f0, pd (B, Fr) with n_crepe[b] in 3..Fr frames per row -> out (B, n_frames) with n_out[b] <=
+ *   n_frames frames per row (both counts or neither; with them start_frame must be 0, DDSP_ERR_ARG otherwise): the reflect windows and the re-timing clamp use n_crepe[b], and the
  *   uv_interp fill looks at the row's own n_out[b] frames only. */
-int ddsp_crepe_activations_ragged(ddsp_ctx* ctx, void* stream, const ddsp_crepe_weights* w, const float* audio16, int64_t B,
-                                  int64_t T, const int32_t* n_samples, const int32_t* frame_prefix, int64_t n_packed, int hop,
-                                  float* probs);
-int ddsp_crepe_decode_ragged(ddsp_ctx* ctx, void* stream, const float* probs, int64_t B, int64_t Fr, const int32_t* n_frames,
-                             float fmin, float fmax, int64_t segment, uint64_t dither_seed, int use_dither, float* f0,
-                             float* periodicity, int32_t* bins);
-int ddsp_f0_postfilter_ragged(ddsp_ctx* ctx, void* stream, const float* f0, const float* pd, int64_t B, int64_t Fr,
-                              const int32_t* n_crepe, int sr, double hop, int64_t n_frames, const int32_t* n_out,
-                              float threshold, int uv_interp, float f0_min, float* out);
-
 /* ---- the autocorrelation f0 extractor (Boersma 1993; the algorithm behind the reference's 'parselmouth' branch,
  * ddsp/vocoder.py:55-69,107-113, restated from the paper's formulae: Praat itself is not a dependency and agreement with it
  * is not pinned) -----------------------------------------------------------------------------------------------------------
@@ -902,14 +830,12 @@ int ddsp_f0_postfilter_ragged(ddsp_ctx* ctx, void* stream, const float* f0, cons
  *   ddsp_f0_ac_frames(T, ...) frames (0 where unvoiced), zeros after; with uv_interp != 0 numpy.interp over the zero frames
  *   (fp64, when any frame is non-zero) and out = max(out, f0_min).  `choice` (B, nF) int32, may be null: the chosen candidate
  *   of every analysis frame (0 = unvoiced).  T must hold one window; the FFT is at most 8192 points (DDSP_ERR_ARG otherwise).
- * ddsp_f0_ac_ragged: n_samples[b] <= T samples per row (a DEVICE array, as in the section above): row b is the row analysed
- *   alone at its own length, bit for bit, with floor(n_samples[b] / hop) + 1 frames and exactly 0 after them; `choice` is
- *   (B, ddsp_f0_ac_frames(T, ...)).  The caller has checked that every row holds one window. */
+ *   n_samples: NULL, or n_samples[b] <= T samples per row (a DEVICE array, as in the section above; start_frame must then be
+ *   0): row b is the row analysed alone at its own length, bit for bit, with floor(n_samples[b] / hop) + 1 frames and exactly 0
+ *   after them; `choice` is (B, ddsp_f0_ac_frames(T, ...)).  The caller has checked that every row holds one window. */
 int64_t ddsp_f0_ac_frames(int64_t T, int sr, double hop, double f0_min);
-int ddsp_f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int sr, double hop, double f0_min,
-               double f0_max, int64_t n_frames, int64_t start_frame, int uv_interp, float* out, int32_t* choice);
-int ddsp_f0_ac_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int sr,
-                      double hop, double f0_min, double f0_max, int64_t n_frames, int uv_interp, float* out, int32_t* choice);
+int ddsp_f0_ac(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int sr, double hop,
+               double f0_min, double f0_max, int64_t n_frames, int64_t start_frame, int uv_interp, float* out, int32_t* choice);
 
 /* ---- the silence slicer (reference: slicer.py `Slicer.slice`, the stage in front of main.py's per-slice loop) -------------
  * Two kernels.  Frame RMS as librosa.feature.rms documents it: frame i of a row of n samples covers the samples
@@ -930,18 +856,15 @@ int ddsp_f0_ac_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B
  *   2 * (F / min_interval + 1) + 1 rows always suffice.  A row that would exceed a smaller capacity writes the chunks that fit,
  *   count[b] = capacity, and sets the context's device error word (DDSP_ERR_ARG from ddsp_ctx_poll_error or the next call that
  *   takes it).
- * ddsp_slicer_ragged: n_samples[b] in 1..T samples per row (a DEVICE array): row b is the row cut alone at its own length, bit
- *   for bit; samples from n_samples[b] on are never read and rms[b][i] = 0 from the row's own frame count on.
- * T + 4 * hop + win < 2^31, 1 <= win, 1 <= hop, 1 <= min_interval.  Neither call synchronises, allocates or reads back. */
+ *   n_samples: NULL, or n_samples[b] in 1..T samples per row (a DEVICE array): row b is the row cut alone at its own length,
+ *   bit for bit; samples from n_samples[b] on are never read and rms[b][i] = 0 from the row's own frame count on.
+ * T + 4 * hop + win < 2^31, 1 <= win, 1 <= hop, 1 <= min_interval.  The call does not synchronise, allocate or read back. */
 #define DDSP_SLICER_PAD_CONSTANT 0
 #define DDSP_SLICER_PAD_REFLECT 1
 int64_t ddsp_slicer_frames(int64_t n, int64_t win, int64_t hop);
-int ddsp_slicer(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, int64_t win, int64_t hop,
-                double threshold, int64_t min_length, int64_t min_interval, int64_t max_sil_kept, int pad_mode, float* rms,
-                int32_t* table, int32_t* count, int64_t capacity);
-int ddsp_slicer_ragged(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples,
-                       int64_t win, int64_t hop, double threshold, int64_t min_length, int64_t min_interval,
-                       int64_t max_sil_kept, int pad_mode, float* rms, int32_t* table, int32_t* count, int64_t capacity);
+int ddsp_slicer(ddsp_ctx* ctx, void* stream, const float* audio, int64_t B, int64_t T, const int32_t* n_samples, int64_t win,
+                int64_t hop, double threshold, int64_t min_length, int64_t min_interval, int64_t max_sil_kept, int pad_mode,
+                float* rms, int32_t* table, int32_t* count, int64_t capacity);
 
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream --------------------- */
 /* ddsp_profile_begin arms the families in `family_mask` (bit i = family i, see the name returned); while armed,

@@ -35,7 +35,7 @@ def test_weight_struct_is_the_header_layout():
     import hipddsp
     assert ctypes.sizeof(hipddsp.CrepeWeights) == 8 * 38 + 4 * 6 + 8
     assert hipddsp.CrepeWeights.version.offset == 8 * 38 + 4 * 6
-    assert hipddsp.ABI_VERSION == 7
+    assert hipddsp.ABI_VERSION == 8
 
 
 def test_frame_count(lib_path):

@@ -14,8 +14,8 @@ from conftest import ROOT
 from oracle import enhancer as OE
 from oracle import resample as OR
 
-NEW = ["ddsp_conv1d_ragged", "ddsp_conv1d_pair_ragged", "ddsp_nsf_source_ragged", "ddsp_nsf_noise_conv_ragged",
-       "ddsp_nsf_post_ragged", "ddsp_stft_frames_ragged", "ddsp_retime_f0_ragged"]
+NEW = ["ddsp_conv1d", "ddsp_conv1d_pair", "ddsp_nsf_source", "ddsp_nsf_noise_conv", "ddsp_nsf_post", "ddsp_stft_frames",
+       "ddsp_retime_f0"]
 
 
 class _OnDevice(torch.Tensor):

@@ -148,7 +148,7 @@ def test_batch_of_one_and_rectangular_batch(ctx, dev, lib_path):
 
 
 def test_source_module_per_row(ctx, dev):
-    """`ddsp_nsf_source_ragged`: one phase scan per row from the row's own rand_ini, rows [40, 9, 1] at upp 512, against
+    """`ddsp_nsf_source` over a batch: one phase scan per row from the row's own rand_ini, rows [40, 9, 1] at upp 512, against
     `OE.sine_source` of each row alone (5e-6, the gate of test_source_module_against_reference for its long track)."""
     sd = _sd("narrow")
     upp, n = 512, [40, 9, 1]
@@ -273,7 +273,7 @@ def test_enhance_batch_end_to_end(dev, lib_path, tmp_path):
 
 
 def test_retime_f0_ragged_against_numpy(ctx, dev):
-    """`ddsp_retime_f0_ragged` per row against the numpy expression of test_retime_f0_against_numpy: rows with their own
+    """`ddsp_retime_f0` with counts, per row against the numpy expression of test_retime_f0_against_numpy: rows with their own
     source and target counts, a single-frame row, targets beyond both ends; ends held at the row's own last frame."""
     rng = np.random.Generator(np.random.PCG64(32))
     for hop, sr, factor, hop_e, sr_e in [(512, 44100, 1.0, 512, 44100), (441, 44100, 1.26, 32, 44100), (160, 16000, 0.7071, 512, 44100)]:

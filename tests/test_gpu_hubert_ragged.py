@@ -1,4 +1,4 @@
-"""Ragged HuBERT-Soft (`HubertSoft.units(wav, n_samples=)` -> ddsp_hubert_soft_units_ragged): every row of a padded batch
+"""Ragged HuBERT-Soft (`HubertSoft.units(wav, n_samples=)` -> ddsp_hubert_soft_units with n_samples): every row of a padded batch
 against the fp64 eager network (tests/hubert_cases.eager_units, the fixture's weight fill) run on THAT ROW ALONE at its own
 length on the CPU - never against a call of the library.  Gates: those of tests/test_gpu_hubert.py (relative rms 5e-6 with
 fp32 products, 1e-4 in split-bf16); the fp32 eager network is within 1.3e-6 of the fp64 one at every length used here.

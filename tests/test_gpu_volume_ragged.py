@@ -1,4 +1,4 @@
-"""Ragged volume (`Volume_Extractor.extract(audio (B,T), n_samples=)` -> ddsp_volume_extract_ragged): every row against the
+"""Ragged volume (`Volume_Extractor.extract(audio (B,T), n_samples=)` -> ddsp_volume_extract with n_samples): every row against the
 restatement behind tests/test_gpu_frontend.py (oracle.frontend.volume_extract) applied to THAT ROW ALONE, at that test's
 bound of 2e-6 relative; exact zeros after a row's frames; the padding (NaN, or noise) is never seen."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Ragged HuBERT-Soft, host side (no GPU): the new entry points are exported and bound, `n_samples=` is checked before any
+"""Ragged HuBERT-Soft, host side (no GPU): the entry points that take the counts are exported and bound, `n_samples=` is checked before any
 device work, `convert_batched` has its new keyword, and the grouping by sample length covers every slice exactly once."""
 import inspect
 
@@ -6,8 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-NEW = ["ddsp_hubert_soft_units_ragged", "ddsp_hubert_encode_ragged", "ddsp_softmax_attention_ragged", "ddsp_resample_ragged",
-       "ddsp_align_units_ragged"]
+NEW = ["ddsp_hubert_soft_units", "ddsp_hubert_encode", "ddsp_softmax_attention", "ddsp_resample", "ddsp_align_units"]
 T = 8000
 
 
@@ -22,7 +21,7 @@ def test_new_symbols_are_exported_and_bound(lib_path):
     for name in NEW:
         assert name in hipddsp.SIGNATURES, name
         assert getattr(lib, name).argtypes == hipddsp.SIGNATURES[name][1]
-    assert hipddsp.ABI_VERSION == 7 and lib.ddsp_abi_version() == 7
+    assert hipddsp.ABI_VERSION == 8 and lib.ddsp_abi_version() == 8
     for m in ("hubert_units", "hubert_encode"):
         assert "n_dev" in inspect.signature(getattr(hipddsp.Context, m)).parameters
     # one binding method per operation: the ragged form is an argument of the un-suffixed method

@@ -11,7 +11,7 @@ import pytest
 import slicer_cases as SC
 from conftest import GOLDEN, ROOT
 
-NEW = ["ddsp_slicer_frames", "ddsp_slicer", "ddsp_slicer_ragged"]
+NEW = ["ddsp_slicer_frames", "ddsp_slicer"]
 
 
 @pytest.fixture(scope="module")
@@ -96,7 +96,7 @@ def test_symbols_are_declared_exported_and_bound(lib_path):
         decl = re.search(r"\bint(?:64_t)? " + name + r"\(([^;]*)\);", header)
         assert decl, f"{name} is not declared in include/ddsp_amd.h"
         assert len(decl.group(1).split(",")) == len(hipddsp.SIGNATURES[name][1]), name
-    assert hipddsp.ABI_VERSION == 7 and lib.ddsp_abi_version() == 7
+    assert hipddsp.ABI_VERSION == 8 and lib.ddsp_abi_version() == 8
     # one binding method: the ragged form is an argument of it
     assert inspect.signature(hipddsp.Context.slicer).parameters["n_dev"].default is None
     assert not hasattr(hipddsp.Context, "slicer_ragged")

@@ -12,7 +12,7 @@ def test_new_entry_points_declared_exported_and_bound(lib_path):
     import hipddsp
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ddsp_amd.h")).read(), flags=re.S)
     lib = ctypes.CDLL(lib_path)
-    for name, n_args in (("ddsp_stream_push", 6), ("ddsp_crepe_decode_dseed", 13)):
+    for name, n_args in (("ddsp_stream_push", 7), ("ddsp_crepe_decode", 15)):
         decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, text)
         assert decl, f"{name} is not declared in include/ddsp_amd.h"
         assert len(decl.group(1).split(",")) == n_args
