@@ -158,7 +158,8 @@ int ddsp_take_dev_error(ddsp_ctx* ctx);
 #define DDSP_DEV_ERR_SPK_ID 1
 #define DDSP_DEV_ERR_DATASET 2   // ddsp_dataset_gather: a (file, start_frame, unit_idx) triple outside its file
 #define DDSP_DEV_ERR_SLICER 3    // ddsp_slicer: a row with more chunks than the table's capacity
-#define DDSP_DEV_ERR_GATE_ROWS 4 // ddsp_volume_gate_rows: a row whose frames lie outside the file's volume or its own row
+#define DDSP_DEV_ERR_GATE_ROWS 4 // ddsp_volume_gate_rows / ddsp_volume_gate_files: a row whose frames lie outside the file's volume or its own row
+#define DDSP_DEV_ERR_PIECES 5    // ddsp_pieces_gather: a piece whose range leaves its file or exceeds the output widths
 
 // profiler hooks (ctx.hip): bracket ONE kernel launch (or a tight group) on `st` when the family is enabled
 void ddsp_prof_begin(ddsp_ctx* ctx, hipStream_t st, int id);

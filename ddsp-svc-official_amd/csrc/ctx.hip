@@ -247,8 +247,11 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
         return ddsp_fail(ctx, DDSP_ERR_ARG, "a row with more chunks than the table's capacity in an earlier ddsp_slicer call",
                          "the table holds the chunks that fit");
     if (code == DDSP_DEV_ERR_GATE_ROWS)
-        return ddsp_fail(ctx, DDSP_ERR_ARG, "a row whose frames lie outside [0, Fr] or its own row in an earlier ddsp_volume_gate_rows call",
-                         "those rows were left as they were");
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a row whose frames lie outside [0, Fr] or its own row in an earlier ddsp_volume_gate_rows "
+                         "or ddsp_volume_gate_files call", "those rows were left as they were");
+    if (code == DDSP_DEV_ERR_PIECES)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a piece whose range leaves its file or exceeds the output widths in an earlier "
+                         "ddsp_pieces_gather call", "those rows were written as zeros and nothing was read for them");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

@@ -129,13 +129,29 @@ __global__ void __launch_bounds__(256) volume_gate_kernel(float* __restrict__ si
 // The gate of one file for a ragged batch of its slices: signal[b][t] *= gate[start[b] * hop + t] for t < n[b] * hop, the rest
 // of the row untouched.  grid (x, B).  A row that does not lie inside the file's frames or its own T_max samples is skipped
 // whole (no index is formed from it) and raises the context's error word.
+// `file` != null (ddsp_volume_gate_files): the rows come from F files, volume is (F, Fr) padded and row b is gated by the track
+// of file[b], which ends at that file's OWN file_frames[file[b]] frames - the dilation's edge and the last frame's
+// interpolation are those of the file alone; a file index outside [0, F) or a count outside [1, Fr] makes the row a bad one.
 __global__ void __launch_bounds__(256) volume_gate_rows_kernel(float* __restrict__ signal, const float* __restrict__ volume,
+                                                               const int32_t* __restrict__ file,
+                                                               const int32_t* __restrict__ file_frames, int64_t F,
                                                                const int32_t* __restrict__ start_frame,
                                                                const int32_t* __restrict__ n_frames, float thr, int64_t T_max,
                                                                int Fr, int hop, int* __restrict__ err) {
     const int64_t b = blockIdx.y;
     const int64_t s = start_frame[b], n = n_frames[b];
-    if (s < 0 || n < 0 || s + n > Fr || n * hop > T_max) {
+    int frames = Fr;
+    bool ok = true;
+    if (file) {
+        const int64_t f = file[b];
+        ok = f >= 0 && f < F;
+        if (ok) {
+            frames = file_frames[f];
+            ok = frames >= 1 && frames <= Fr;
+            volume += f * Fr;
+        }
+    }
+    if (!ok || s < 0 || n < 0 || s + n > frames || n * hop > T_max) {
         if (blockIdx.x == 0 && threadIdx.x == 0)
             __hip_atomic_store(err, DDSP_DEV_ERR_GATE_ROWS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
@@ -144,7 +160,7 @@ __global__ void __launch_bounds__(256) volume_gate_rows_kernel(float* __restrict
     float* __restrict__ row = signal + b * T_max;
     const int64_t len = n * hop;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < len; t += (int64_t)gridDim.x * 256)
-        row[t] *= volume_gate_at(volume, Fr, (int)(s + t / hop), (int)(t % hop), thr, inv_hop);
+        row[t] *= volume_gate_at(volume, frames, (int)(s + t / hop), (int)(t % hop), thr, inv_hop);
 }
 
 // ---- phase-vocoder cross-fade (gui.py:14-31, optional `use_phase_vocoder` splice of gui.py:417-423) ----------------
@@ -310,11 +326,10 @@ extern "C" int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, cons
     return DDSP_OK;
 }
 
-extern "C" int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* start_frame,
-                                     const int32_t* n_frames, float threshold, int64_t B, int64_t T_max, int64_t Fr, int hop) {
-    DDSP_REQUIRE(ctx, ctx && signal && volume && start_frame && n_frames, "ddsp_volume_gate_rows: null argument");
-    DDSP_REQUIRE(ctx, B >= 0 && B <= 65535 && T_max >= 1 && hop >= 1 && (hop & (hop - 1)) == 0 && Fr >= 1 && Fr < (1ll << 31) / hop,
-                 "ddsp_volume_gate_rows: bad shape");
+// the launch of both gate-of-rows entry points: file == null is the one-file form
+static int volume_gate_rows_launch(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* file,
+                                   const int32_t* file_frames, int64_t F, const int32_t* start_frame, const int32_t* n_frames,
+                                   float threshold, int64_t B, int64_t T_max, int64_t Fr, int hop) {
     int rc;
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
     if (B == 0) return DDSP_OK;
@@ -324,11 +339,32 @@ extern "C" int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal,
     if ((rc = ddsp_dev_error_ptr(ctx, &dev_err))) return rc;
     const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(T_max, 256), 1024);
     ddsp_prof_begin(ctx, st, PF_OTHER);
-    hipLaunchKernelGGL(volume_gate_rows_kernel, dim3(gx, (unsigned)B), dim3(256), 0, st, signal, volume, start_frame, n_frames,
-                       threshold, T_max, (int)Fr, hop, dev_err);
+    hipLaunchKernelGGL(volume_gate_rows_kernel, dim3(gx, (unsigned)B), dim3(256), 0, st, signal, volume, file, file_frames, F,
+                       start_frame, n_frames, threshold, T_max, (int)Fr, hop, dev_err);
     ddsp_prof_end(ctx, st, 0.0, 8.0 * B * (double)T_max);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* start_frame,
+                                     const int32_t* n_frames, float threshold, int64_t B, int64_t T_max, int64_t Fr, int hop) {
+    DDSP_REQUIRE(ctx, ctx && signal && volume && start_frame && n_frames, "ddsp_volume_gate_rows: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && B <= 65535 && T_max >= 1 && hop >= 1 && (hop & (hop - 1)) == 0 && Fr >= 1 && Fr < (1ll << 31) / hop,
+                 "ddsp_volume_gate_rows: bad shape");
+    return volume_gate_rows_launch(ctx, stream, signal, volume, nullptr, nullptr, 1, start_frame, n_frames, threshold, B, T_max, Fr,
+                                   hop);
+}
+
+extern "C" int ddsp_volume_gate_files(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* file_frames,
+                                      int64_t F, const int32_t* file, const int32_t* start_frame, const int32_t* n_frames,
+                                      float threshold, int64_t B, int64_t T_max, int64_t Fr_max, int hop) {
+    DDSP_REQUIRE(ctx, ctx && signal && volume && file_frames && file && start_frame && n_frames,
+                 "ddsp_volume_gate_files: null argument");
+    DDSP_REQUIRE(ctx, B >= 0 && B <= 65535 && F >= 1 && F < (1ll << 31) && T_max >= 1 && hop >= 1 && (hop & (hop - 1)) == 0 &&
+                          Fr_max >= 1 && Fr_max < (1ll << 31) / hop,
+                 "ddsp_volume_gate_files: bad shape");
+    return volume_gate_rows_launch(ctx, stream, signal, volume, file, file_frames, F, start_frame, n_frames, threshold, B, T_max,
+                                   Fr_max, hop);
 }
 
 // S windows take S blocks: window[s][:] = append(window[s][block:], block_in[s]).  The shift overlaps itself, and workgroups of

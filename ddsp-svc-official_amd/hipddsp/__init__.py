@@ -192,6 +192,8 @@ SIGNATURES = {
     "ddsp_sola": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _int, _vp, _vp, _vp]),
     "ddsp_volume_gate": (_int, [_vp, _vp, _vp, _vp, _f32, _i64, _i64, _int]),
     "ddsp_volume_gate_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
+    "ddsp_volume_gate_files": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
+    "ddsp_pieces_gather": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "ddsp_stitch": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
     "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "ddsp_volume_extract": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
@@ -1448,20 +1450,80 @@ class Context:
                   vol.shape[1], int(hop))
         return signal
 
-    def volume_gate_rows_(self, signal, volume, start_dev, n_dev, threshold_db, hop):
+    def volume_gate_rows_(self, signal, volume, start_dev, n_dev, threshold_db, hop, file_dev=None, file_frames_dev=None):
         """In place, for a ragged batch of slices of ONE file: signal (B, T_max) fp32, row b's samples t < n[b] * hop times the
         file's gate (`volume_gate_` of the whole `volume` (Fr,)) at start[b] * hop + t; the rest of a row is not touched.
         start_dev, n_dev: (B,) int32 device tensors (`ragged_counts`).  One launch (`ddsp_volume_gate_rows`), nothing is read
         back: a row outside the file's frames or its own row stays as it is and raises ValueError from `poll_error()` after a
-        synchronise or from the next call that takes the error word."""
+        synchronise or from the next call that takes the error word.
+        file_dev (B,) and file_frames_dev (F,) int32 device tensors, both or neither: the rows are slices of SEVERAL files,
+        `volume` is (F, Fr_max) fp32 contiguous and row b is gated by the track of file[b], which ends at that file's own frame
+        count (`ddsp_volume_gate_files`): each row as the one-file call on its file alone gates it."""
         if signal.dim() != 2 or signal.dtype != torch.float32 or not signal.is_contiguous():
             raise ValueError("volume_gate_rows_: signal must be a contiguous fp32 (B, T_max) tensor (it is gated in place)")
+        if (file_dev is None) != (file_frames_dev is None):
+            raise ValueError("volume_gate_rows_: file_dev and file_frames_dev come together or not at all")
         B, T_max = signal.shape
-        vol = volume.reshape(-1).contiguous().float()
+        thr = float(10 ** (float(threshold_db) / 20))
+        if file_dev is None:
+            vol = volume.reshape(-1).contiguous().float()
+            symbol, head, Fr = "ddsp_volume_gate_rows", (), vol.numel()
+        else:
+            if volume.dim() != 2 or volume.dtype != torch.float32 or not volume.is_contiguous():
+                raise ValueError("volume_gate_rows_: with file_dev, volume must be a contiguous fp32 (F, Fr_max) tensor")
+            vol, (F, Fr) = volume, volume.shape
+            symbol, head = "ddsp_volume_gate_files", (_ptr(self._counts_dev(file_frames_dev, F)), F, _ptr(self._counts_dev(file_dev, B)))
         if B:
-            self.call("ddsp_volume_gate_rows", _ptr(signal), _ptr(vol), _ptr(self._counts_dev(start_dev, B)),
-                      _ptr(self._counts_dev(n_dev, B)), float(10 ** (float(threshold_db) / 20)), B, T_max, vol.numel(), int(hop))
+            self.call(symbol, _ptr(signal), _ptr(vol), *head, _ptr(self._counts_dev(start_dev, B)),
+                      _ptr(self._counts_dev(n_dev, B)), thr, B, T_max, Fr, int(hop))
         return signal
+
+    # -- the rows of a ragged group from several files -------------------------------------------
+    def pieces_gather(self, table_dev, n_file_samples_dev, n_file_frames_dev, audio=None, S_max=0, f0=None, volume=None,
+                      key_factor=None, N_max=0):
+        """One launch (`ddsp_pieces_gather`) forms the R rows of a ragged group from a padded batch of F files.  table_dev
+        (R, 5) int32 device rows (file, start_frame, n_frames, start_sample, n_samples); n_file_samples_dev / n_file_frames_dev
+        (F,) int32 device.  audio (F, T_max) with S_max -> wav (R, S_max); f0, volume (F, Fr_max) and key_factor (F,) with N_max
+        -> f0_rows (the one rounded product f0 * key_factor[file]) and vol_rows (R, N_max; not made when `volume` is None);
+        exact zeros behind every piece.
+        Returns (wav, f0_rows, vol_rows), None for the half that was not asked for.  Nothing is read back: a piece outside its
+        file gives a row of zeros and raises ValueError from `poll_error()` after a synchronise or from the next call that takes
+        the error word."""
+        def dense(name, t, shape):
+            if not (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()
+                    and (shape is None or tuple(t.shape) == shape)):
+                raise ValueError(f"pieces_gather: {name} must be a contiguous fp32 tensor on {self.device}"
+                                 + (f" of shape {shape}" if shape else ""))
+            return t
+        if table_dev.dim() != 2 or table_dev.shape[1] != 5 or table_dev.dtype != torch.int32 or not table_dev.is_cuda \
+                or not table_dev.is_contiguous():
+            raise ValueError("pieces_gather: the table must be a contiguous (R, 5) int32 device tensor")
+        if audio is None and f0 is None:
+            raise ValueError("pieces_gather: pass audio, or f0 with key_factor (and volume), or both")
+        R, F = table_dev.shape[0], n_file_samples_dev.numel()
+        self._counts_dev(n_file_samples_dev, F)
+        self._counts_dev(n_file_frames_dev, F)
+        wav = f0_rows = vol_rows = None
+        T_max = Fr_max = 1
+        if audio is not None:
+            T_max = dense("audio", audio, None).shape[1] if audio.dim() == 2 and audio.shape[0] == F else -1
+            wav = torch.empty(R, int(S_max), device=self.device, dtype=torch.float32)
+        if f0 is not None:
+            Fr_max = dense("f0", f0, None).shape[1] if f0.dim() == 2 and f0.shape[0] == F else -1
+            dense("key_factor", key_factor, (F,))
+            f0_rows = torch.empty(R, int(N_max), device=self.device, dtype=torch.float32)
+            if volume is not None:
+                dense("volume", volume, (F, Fr_max))
+                vol_rows = torch.empty(R, int(N_max), device=self.device, dtype=torch.float32)
+        elif volume is not None:
+            raise ValueError("pieces_gather: volume goes with f0")
+        if T_max < 1 or Fr_max < 1:
+            raise ValueError(f"pieces_gather: audio must be (F, T_max) and f0 (F, Fr_max) with F = {F} files and at least a column")
+        if R:
+            self.call("ddsp_pieces_gather", _ptr(audio), _ptr(f0), _ptr(volume), _ptr(key_factor), _ptr(n_file_samples_dev),
+                      _ptr(n_file_frames_dev), F, T_max, Fr_max, _ptr(table_dev), R, int(S_max), int(N_max), _ptr(wav),
+                      _ptr(f0_rows), _ptr(vol_rows))
+        return wav, f0_rows, vol_rows
 
     # -- the stitch ----------------------------------------------------------------------------
     def stitch(self, pieces, p, fade, total):

@@ -11,7 +11,12 @@ own `slicer.Slicer` (the reference's silence detector on the device); `convert(.
 the slice boundaries of any other detector.  `render_device` / `convert_device` are `render` / `convert_batched` with the end
 on the device too: one gate launch per ragged group (`ddsp_volume_gate_rows`), one launch for the stitch (`stitch_plan`,
 `stitch`: `ddsp_stitch`), the float64 waveform returned as a device tensor; `main.py` is the command line over them.
+`analyse_many` / `render_many_device` / `convert_many_device` / `convert_many` take a LIST of files: one ragged analysis of all
+files, ragged groups over the slices of all files (rows formed by `ddsp_pieces_gather`, gated by `ddsp_volume_gate_files`), one
+stitch of every file into one tensor (`stitch_plan_many`), one read-back.
 """
+import numbers
+
 import numpy as np
 import torch
 
@@ -331,3 +336,278 @@ def _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key,
     if units_batch_samples is not None:
         segments = _encode_ragged(units_encoder, segments, sample_rate, hop_size, units_batch_samples)
     return segments, f0, volume
+
+
+# ---- several files in one call: ragged groups across files ---------------------------------------------------------------
+
+def piece_table(slices_per_file, hop_size):
+    """The pieces of several files as `ddsp_pieces_gather` takes them: `slices_per_file[k]` is file k's list of (start_sample,
+    end_sample) -> the list of (file, start_frame, n_frames, start_sample, n_samples), files in order and every file's slices in
+    theirs.  The snapping is `main.split`'s (main.py:41-46), formed here on the host because `hop_size` may be fractional:
+    start_frame = int(start // hop_size), end_frame = int(end // hop_size), start_sample = int(start_frame * hop_size),
+    n_samples = int(end_frame * hop_size) - start_sample; a slice with end_frame == start_frame is dropped.  n_frames =
+    int(n_samples // hop_size) + 1 is the number of unit frames `Units_Encoder.encode` gives the slice, which is what the slice
+    takes of its file's f0 and volume."""
+    rows = []
+    for k, slices in enumerate(slices_per_file):
+        for start, end in slices:
+            start_frame, end_frame = int(int(start) // hop_size), int(int(end) // hop_size)
+            if end_frame > start_frame:
+                start_sample = int(start_frame * hop_size)
+                n_samples = int(end_frame * hop_size) - start_sample
+                rows.append((k, start_frame, int(n_samples // hop_size) + 1, start_sample, n_samples))
+    return rows
+
+
+def stitch_plan_many(starts_per_file, lengths_per_file, block, sr, sr_o):
+    """`stitch_plan` for several files laid one after the other in ONE output -> (spans, p, fade, total): spans[k] = (base,
+    total) of file k, its samples out[base:base + total]; p, fade the table of all pieces, files in order, for one `ddsp_stitch`
+    launch; total the end of the last file.  File k's base is the end of the files before it rounded up to a multiple of 2
+    samples (16 bytes of fp64: every file starts where the kernel's stores are aligned), its pieces sit at base + their own p
+    with their own fades - 0 at a file's first piece, so nothing fades across files - and the gap the rounding leaves is covered
+    by no piece: exact zeros.  A file without pieces has total 0.  Raises `stitch_plan`'s ValueErrors, naming the file too."""
+    if len(starts_per_file) != len(lengths_per_file):
+        raise ValueError(f"stitch_plan_many: start frames of {len(starts_per_file)} files, lengths of {len(lengths_per_file)}")
+    spans, p, fade, end = [], [], [], 0
+    for k, (starts, lengths) in enumerate(zip(starts_per_file, lengths_per_file)):
+        try:
+            pk, fk, total = stitch_plan(starts, lengths, block, sr, sr_o)
+        except ValueError as e:
+            raise ValueError(f"stitch_plan_many: file {k}: {e}") from None
+        base = end + (end & 1)
+        spans.append((base, total))
+        p.extend(base + at for at in pk)
+        fade.extend(fk)
+        end = base + total
+    return spans, p, fade, end
+
+
+def group_pieces(pieces, budget, by_samples=False):
+    """`group_segments` over the pieces of ALL files (`piece_table` rows), by their frame counts or (by_samples) their sample
+    counts -> groups of indices into `pieces`; every (file, slice) is in exactly one group and a group may hold rows of
+    several files."""
+    return group_segments([row[4 if by_samples else 2] for row in pieces], budget)
+
+
+def _upload_pieces(ctx, pieces, groups):
+    """The piece table in the order the groups take it, uploaded once -> (table (P, 5) int32 device, its transpose (5, P),
+    [(first, last + 1)] of every group): a group's rows, and each of its columns, are contiguous views."""
+    order = [i for group in groups for i in group]
+    table = torch.tensor([pieces[i] for i in order], dtype=torch.int32).reshape(-1, 5).to(ctx.device)
+    bounds, at = [], 0
+    for group in groups:
+        bounds.append((at, at + len(group)))
+        at += len(group)
+    return table, table.t().contiguous(), bounds
+
+
+def _per_file(value, F, what):
+    """One value (a number, a numpy scalar, a tensor of one element such as `render_device`'s spk_id (1, 1)) or one per file
+    -> the list of F values."""
+    if isinstance(value, (torch.Tensor, np.ndarray)):
+        value = value.reshape(-1).tolist()
+        if len(value) == 1:
+            value = value[0]
+    if isinstance(value, numbers.Real):
+        return [value] * F
+    value = list(value)
+    if len(value) != F:
+        raise ValueError(f"{what}: one value or one per file ({F}), got {len(value)}")
+    return value
+
+
+@torch.no_grad()
+def analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys=0, units_batch_samples=None):
+    """`_analyse` for a list of files at one `sample_rate`: `audios[k]` a numpy array or tensor (T_k,).  ONE ragged
+    `F0_Extractor.extract(..., uv_interp=True, n_samples=)`, ONE ragged volume and - `slices` None - ONE ragged slicer call with
+    one read-back of the chunk tables cover all files (otherwise `slices[k]` is file k's list of (start_sample, end_sample));
+    the units of all slices of all files are encoded in `group_segments` groups over the global list of slices
+    (`units_batch_samples` padded samples per group; None: a slice per group), each group's audio rows formed by one
+    `ddsp_pieces_gather`.  `keys`: semitones, one number or one per file.  The ragged volume needs an integral hop
+    (`block_size * sample_rate / sampling_rate`): ValueError otherwise, before anything is launched.
+    -> the dict `render_many_device` takes: audio (F, T_max), f0 (F, Fr_max) NOT yet shifted, volume (F, Fr_max), key_factor
+    (F,) fp32 = 2 ** (key / 12), n_samples / n_frames (lists) and n_samples_dev / n_frames_dev, pieces (`piece_table`), units
+    (one (1, n_frames, n_unit) tensor per piece), hop_size, sample_rate, device.  `file_features` gives one file's part in
+    `_analyse`'s form."""
+    hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
+    if not float(hop_size).is_integer():
+        raise ValueError(f"analyse_many: the ragged volume (n_samples=) needs an integral hop, but block_size * sample_rate / "
+                         f"sampling_rate = {hop_size}; resample the files to the model's rate first")
+    if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
+        raise ValueError(f"analyse_many: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
+                         f"{f0_extractor.hop_size}; the audio is at {sample_rate} Hz with hop {hop_size}")
+    F = len(audios)
+    dev = next((a.device for a in audios if isinstance(a, torch.Tensor) and a.is_cuda), torch.device(f0_extractor.device))
+    files = {"hop_size": hop_size, "sample_rate": sample_rate, "device": dev, "pieces": [], "units": [], "n_samples": [],
+             "n_frames": []}
+    if F == 0:
+        return files
+    keys = _per_file(keys, F, "analyse_many: keys")
+    if slices is not None and len(slices) != F:
+        raise ValueError(f"analyse_many: slices of {len(slices)} files for {F} files")
+    counts = [int(a.shape[0]) if getattr(a, "ndim", 0) == 1 else -1 for a in audios]
+    if min(counts) < 1:
+        raise ValueError("analyse_many: every file must be mono audio of shape (T,) with T >= 1")
+    ctx = hipddsp.context_for(dev)
+    # The batch's width is the longest file's, rounded up to 4 samples: every file's row then starts on 16 bytes, and with the
+    # slice starts of an integral hop (multiples of it) the gather of the encoder's rows takes its 16-byte loads.  Not where
+    # the rounding would add a frame to the volume's width (the longest file within 3 samples of a hop multiple).
+    T_max = max(counts)
+    width = -(-T_max // 4) * 4
+    if width // int(hop_size) != T_max // int(hop_size):
+        width = T_max
+    if all(isinstance(a, np.ndarray) for a in audios):          # padded on the host: one upload
+        host = np.zeros((F, width), dtype=np.float32)
+        for k, a in enumerate(audios):
+            host[k, :counts[k]] = a
+        x = torch.from_numpy(host).to(dev)
+    else:
+        x = torch.zeros(F, width, device=dev)
+        for k, a in enumerate(audios):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
+            x[k, :counts[k]] = a.to(dev, torch.float32)
+    f0 = f0_extractor.extract(x, uv_interp=True, n_samples=counts)
+    volume = ctx.volume_extract(x, int(hop_size), counts)
+    if slices is None:
+        table, count, _ = Slicer(sr=sample_rate, threshold=-40, min_length=5000).chunks(x, n_samples=counts)
+        host = torch.cat([count, table.reshape(-1)]).cpu().numpy()     # the call's one read-back in front of the result
+        ctx.poll_error()
+        rows = host[F:].reshape(F, -1, 3)
+        slices = [[(int(a), int(b)) for a, b, _ in rows[k, :host[k]] if a != b] for k in range(F)]
+    n_frames = [n // int(hop_size) + 1 for n in counts]
+    pieces = piece_table(slices, hop_size)
+    for k, start_frame, n, start_sample, n_samples in pieces:
+        if start_sample < 0 or start_sample + n_samples > counts[k] or start_frame + n > n_frames[k]:
+            raise ValueError(f"analyse_many: file {k}: the slice at frame {start_frame} ({n} frames, samples {start_sample} to "
+                             f"{start_sample + n_samples}) leaves the file's {counts[k]} samples / {n_frames[k]} frames")
+    files.update(audio=x, f0=f0.contiguous(), volume=volume, n_samples=counts, n_frames=n_frames, pieces=pieces,
+                 key_factor=torch.tensor([2 ** (float(key) / 12) for key in keys], dtype=torch.float32).to(dev),
+                 n_samples_dev=ctx.ragged_counts(counts), n_frames_dev=ctx.ragged_counts(n_frames))
+    units = [None] * len(pieces)
+    groups = group_pieces(pieces, 0 if units_batch_samples is None else int(units_batch_samples), by_samples=True)
+    table, _, bounds = _upload_pieces(ctx, pieces, groups)
+    for group, (a, b) in zip(groups, bounds):
+        n_rows = [pieces[i][4] for i in group]
+        wav, _, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], audio=x, S_max=max(n_rows))
+        got = units_encoder.encode(wav, sample_rate, hop_size, n_samples=n_rows)
+        for j, i in enumerate(group):
+            units[i] = got[j:j + 1, :pieces[i][2]].clone()
+    files["units"] = units
+    return files
+
+
+def file_features(files, k):
+    """File k of `analyse_many`'s result in `_analyse`'s form -> (segments [(start_frame, units (1, n, n_unit))], f0 (1, Fr, 1)
+    shifted by the file's key, volume (1, Fr)): what `render_device` takes for that file alone."""
+    n = files["n_frames"][k]
+    segments = [(row[1], u) for row, u in zip(files["pieces"], files["units"]) if row[0] == k]
+    f0 = files["f0"][k:k + 1, :n, None] * files["key_factor"][k]
+    return segments, f0, files["volume"][k:k + 1, :n]
+
+
+@torch.no_grad()
+def render_many_device(model, args, files, spk_ids, spk_mix_rows=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0,
+                       noise_seed=None, batch_frames=None, noise=None, enhancer_batch_samples=None):
+    """`render_device` for the files of `analyse_many` in one pass -> (fp64 device tensor holding every file, [(base, total)]
+    per file, sample rate): file k is out[base:base + total], what `render_device` gives for it alone (`stitch_plan_many`
+    states the layout; the gaps in front of odd bases are exact zeros, a file without slices has total 0).
+    `group_segments` runs over the slices of ALL files (`batch_frames` padded frames per group; None: a slice per group), so
+    short files share their forwards.  Per group: one `ddsp_pieces_gather` (the rows' f0 times their file's key factor, and
+    volume), one ragged forward with every row's own speaker, one `ddsp_volume_gate_files`; then the enhancer in ragged groups
+    over all pieces (`enhancer_batch_samples`; one `enhancer_adaptive_key` serves the call, as `enhance_batch` takes it) and ONE
+    `ddsp_stitch`.
+    spk_ids: one speaker id or one per file (ints or a tensor).  spk_mix_rows: (ids (F, K) int32, w (F, K) fp32) device
+    tables, a speaker mix per FILE in place of `spk_ids`; every row takes its file's.
+    noise: noise[k][i] is the (n * block,) U[0,1) draw of file k's slice i, as `render_device`'s `noise` is per segment.
+    noise_seed: group g - the g-th group of `group_segments` over the pieces in `files['pieces']` order - draws with the seed
+    (noise_seed + g * 2**32) mod 2**64, and the in-kernel draw is a hash of (seed, row, sample).  The grouping depends on the
+    files' slice lengths and `batch_frames` alone, so the same call twice gives the same bits; two identical files in one call
+    lie in different rows or different groups, so their noise differs.  (The draws are not those of `render_device` per file.)"""
+    block = int(args.data.block_size)
+    sr = int(args.data.sampling_rate)
+    dev = files["device"]
+    F, pieces, units = len(files["n_samples"]), files["pieces"], files["units"]
+    if F == 0:
+        return torch.zeros(0, dtype=torch.float64, device=dev), [], sr
+    ctx = hipddsp.context_for(dev)
+    for k, start, n, _, _ in pieces:
+        if start < 0 or start + n > files["n_frames"][k]:
+            raise ValueError(f"render_many_device: file {k}: the segment at frame {start} has {n} frames of units but f0 / volume "
+                             f"cover {files['n_frames'][k]} frames of the file")
+    if noise is not None and ([len(x) for x in noise] != [sum(1 for row in pieces if row[0] == k) for k in range(F)]):
+        raise ValueError("render_many_device: noise must hold one list per file with one draw per slice")
+    flat_noise = None if noise is None else [x for per_file in noise for x in per_file]
+    groups = group_pieces(pieces, 0 if batch_frames is None else int(batch_frames))
+    table, cols, bounds = _upload_pieces(ctx, pieces, groups)
+    rows_file = cols[0].long()
+    if spk_mix_rows is not None:
+        ids, w = spk_mix_rows
+        if ids.shape[0] != F or w.shape[0] != F:
+            raise ValueError(f"render_many_device: spk_mix_rows must hold one row per file ({F})")
+        mix = (ids.index_select(0, rows_file).contiguous(), w.index_select(0, rows_file).contiguous())
+        spk = torch.ones(len(pieces), 1, dtype=torch.int64, device=dev)          # (not read: the mix stands in its place)
+    else:
+        spk = torch.tensor(_per_file(spk_ids, F, "render_many_device: spk_ids"), dtype=torch.int64).to(dev)
+        spk = spk.index_select(0, rows_file).reshape(-1, 1)
+    out = [None] * len(pieces)
+    for g, (group, (a, b)) in enumerate(zip(groups, bounds)):
+        counts = [pieces[i][2] for i in group]
+        u, _ = stack_rows([units[i][0] for i in group])
+        _, f, v = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
+                                    volume=files["volume"], key_factor=files["key_factor"], N_max=max(counts))
+        kw = {} if noise_seed is None else {"noise_seed": (int(noise_seed) + (g << 32)) & ((1 << 64) - 1)}
+        if flat_noise is not None:
+            kw["noise"] = stack_rows([flat_noise[i].reshape(-1) for i in group])[0]
+        if spk_mix_rows is not None:
+            kw["spk_mix_rows"] = (mix[0][a:b], mix[1][a:b])
+        signal = model(u, f[:, :, None], v, spk_id=spk[a:b], n_frames=counts, **kw)[0].contiguous()
+        ctx.volume_gate_rows_(signal, files["volume"], cols[1, a:b], cols[2, a:b], threshold_db, block,
+                              file_dev=cols[0, a:b], file_frames_dev=files["n_frames_dev"])
+        for j, i in enumerate(group):
+            out[i] = signal[j:j + 1, :counts[j] * block]
+    sr_o = sr
+    if enhancer is not None and pieces:
+        out, sr_o = _enhance_many(ctx, enhancer, out, files, sr, block, enhancer_adaptive_key,
+                                  0 if enhancer_batch_samples is None else enhancer_batch_samples)
+    per_file = [[i for i, row in enumerate(pieces) if row[0] == k] for k in range(F)]
+    spans, p, fade, total = stitch_plan_many([[pieces[i][1] for i in idx] for idx in per_file],
+                                             [[out[i].shape[-1] for i in idx] for idx in per_file], block, sr, sr_o)
+    return ctx.stitch(out, p, fade, total), spans, sr_o
+
+
+def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples):
+    """`_enhance_ragged` over the gated pieces of all files: one `Enhancer.enhance_batch` per group of `group_segments` over
+    the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group)."""
+    pieces = files["pieces"]
+    groups = group_segments([g.shape[-1] for g in gated], int(enhancer_batch_samples))
+    table, _, bounds = _upload_pieces(ctx, pieces, groups)
+    out, sr_o = [None] * len(gated), sr
+    for group, (a, b) in zip(groups, bounds):
+        wav, counts = stack_rows([gated[i][0] for i in group])
+        n_f0 = [pieces[i][2] for i in group]
+        _, tracks, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
+                                         key_factor=files["key_factor"], N_max=max(n_f0))
+        got, sr_o, n_out = enhancer.enhance_batch(wav, sr, tracks[:, :, None], block, counts, adaptive_key=adaptive_key, n_f0=n_f0)
+        for j, i in enumerate(group):
+            out[i] = got[j:j + 1, :n_out[j]]
+    return out, sr_o
+
+
+@torch.no_grad()
+def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, slices=None, keys=0,
+                        batch_frames=None, spk_mix_rows=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0,
+                        noise_seed=None, enhancer_batch_samples=None, units_batch_samples=None):
+    """`analyse_many` then `render_many_device`: a list of files from raw audio to one fp64 device tensor -> (out, [(base,
+    total)] per file, sample rate).  Files are batched within ONE call's sample rate, enhancer key and model."""
+    files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys, units_batch_samples)
+    return render_many_device(model, args, files, spk_ids, spk_mix_rows=spk_mix_rows, threshold_db=threshold_db, enhancer=enhancer,
+                              enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
+                              enhancer_batch_samples=enhancer_batch_samples)
+
+
+def convert_many(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, **kw):
+    """`convert_many_device` (its keywords) with ONE `.cpu()` of the whole result, split into the files -> ([float64 numpy
+    waveform per file], sample rate).  An empty list of files gives an empty list and launches nothing."""
+    out, spans, sr_o = convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, **kw)
+    host = out.cpu().numpy() if spans else np.zeros(0)
+    return [host[base:base + total].copy() for base, total in spans], sr_o

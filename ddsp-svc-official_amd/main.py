@@ -3,6 +3,7 @@ stitched waveform on the device and is read back once.
 
     python main.py -m <model.pt> -i <in.wav> -o <out.wav> [-id 1] [-mix None] [-k 0] [-e true] [-pe crepe] [-fmin 50]
                    [-fmax 1100] [-th -60] [-eak 0] [-sr 44100]
+    python main.py -m <model.pt> -i <folder of .wav> -o <output folder> ...     (every file in one `convert_many_device`)
 
 The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
   * the key shift is applied once (the reference applies it twice, SURVEY 0.3);
@@ -13,6 +14,7 @@ The options and their defaults are the reference's (`main.py:19-31`).  What diff
   * the reference's md5-keyed f0 cache is left out: the f0 of a file takes milliseconds on the device.
 """
 import argparse
+import os
 from ast import literal_eval
 
 import numpy as np
@@ -62,12 +64,16 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
     from preprocess import load_wav
 
     model, args = load_model(cmd.model_path, device=device)
-    wave, rate = load_wav(cmd.input)
     sr_i = int(cmd.sampling_rate)
-    audio = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(device)
-    if int(rate) != sr_i:
-        from resample import Resample
-        audio = Resample(int(rate), sr_i)(audio)
+
+    def load(path):
+        wave, rate = load_wav(path)
+        audio = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(device)
+        if int(rate) != sr_i:
+            from resample import Resample
+            audio = Resample(int(rate), sr_i)(audio)
+        return audio
+
     hop_size = int(args.data.block_size) * sr_i / int(args.data.sampling_rate)
     if f0_extractor is None:
         f0_extractor = F0_Extractor(cmd.pitch_extractor, sr_i, hop_size, float(cmd.f0_min), float(cmd.f0_max), device=device)
@@ -77,6 +83,10 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
     if enhancer is None and cmd.enhance == "true":
         from enhancer import Enhancer
         enhancer = Enhancer(args.enhancer.type, args.enhancer.ckpt, device=device)
+    if os.path.isdir(cmd.input):
+        return _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
+                           enhancer_batch_samples, units_batch_samples)
+    audio = load(cmd.input)
     spk_id = torch.tensor([[int(cmd.spk_id)]], dtype=torch.int64, device=device)
     result, sr_o = convert_device(model, args, audio, sr_i, None, units_encoder, f0_extractor, spk_id, batch_frames=batch_frames,
                                   key=float(cmd.key), spk_mix_dict=literal_eval(cmd.spk_mix_dict),
@@ -84,6 +94,34 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
                                   enhancer_adaptive_key=float(cmd.enhancer_adaptive_key),
                                   enhancer_batch_samples=enhancer_batch_samples, units_batch_samples=units_batch_samples)
     wavfile.write(cmd.output, int(sr_o), pcm16(result.cpu().numpy()))   # the file's one read-back
+    return result, sr_o
+
+
+def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
+                units_batch_samples):
+    """`run` for a directory: every `.wav` in `cmd.input` (sorted by name) through ONE `infer_offline.convert_many_device`, the
+    results written under the same names into the directory `cmd.output` (made if missing) after one read-back -> (the fp64
+    device tensor holding every file, sample rate).  `-id`, `-k` and `-mix` hold for every file; a mix becomes a table row per
+    file (`spk_mix_rows`).  The files are resampled to `-sr` like a single input; `-sr` must give the model an integral hop
+    (`analyse_many` refuses another one)."""
+    from scipy.io import wavfile
+
+    from infer_offline import convert_many_device
+    names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
+    audios = [load(os.path.join(cmd.input, n)) for n in names]
+    mix, rows = literal_eval(cmd.spk_mix_dict), None
+    if mix is not None:
+        rows = (torch.tensor([[int(k) for k in mix]] * len(names), dtype=torch.int32).reshape(len(names), -1).to(device),
+                torch.tensor([[float(v) for v in mix.values()]] * len(names), dtype=torch.float32).reshape(len(names), -1).to(device))
+    use = enhancer if cmd.enhance == "true" else None
+    result, spans, sr_o = convert_many_device(
+        model, args, audios, sr_i, units_encoder, f0_extractor, int(cmd.spk_id), keys=float(cmd.key), batch_frames=batch_frames,
+        spk_mix_rows=rows, threshold_db=float(cmd.threhold), enhancer=use, enhancer_adaptive_key=float(cmd.enhancer_adaptive_key),
+        enhancer_batch_samples=enhancer_batch_samples, units_batch_samples=units_batch_samples)
+    os.makedirs(cmd.output, exist_ok=True)
+    host = result.cpu().numpy()                                        # the folder's one read-back
+    for name, (base, total) in zip(names, spans):
+        wavfile.write(os.path.join(cmd.output, name), int(sr_o), pcm16(host[base:base + total]))
     return result, sr_o
 
 

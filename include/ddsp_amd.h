@@ -429,6 +429,37 @@ int ddsp_volume_gate(ddsp_ctx* ctx, void* stream, float* signal, const float* vo
  * (DDSP_ERR_ARG from ddsp_ctx_poll_error or the next call that takes it). */
 int ddsp_volume_gate_rows(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* start_frame,
                           const int32_t* n_frames, float threshold, int64_t B, int64_t T_max, int64_t Fr, int hop);
+/* The gate for a ragged batch whose rows are slices of SEVERAL files: volume (F, Fr_max) holds the files' tracks padded,
+ * file_frames (F) int32 DEVICE their own frame counts (1 <= file_frames[f] <= Fr_max), file (B) int32 DEVICE the file of every
+ * row.  Row b is gated as ddsp_volume_gate_rows gates it with file[b]'s track of file_frames[file[b]] frames alone (one kernel
+ * and one device function serve both calls): the 9-frame dilation and its edge padding stop at the file's OWN first and last
+ * frame, and the file's last frame interpolates as in a solo call; what lies behind a file's frames is never read.  A row with
+ * file[b] outside [0, F), a file count outside [1, Fr_max], or frames outside its file or its own row is left as it is and sets
+ * the context's device error word like a bad row of ddsp_volume_gate_rows. */
+int ddsp_volume_gate_files(ddsp_ctx* ctx, void* stream, float* signal, const float* volume, const int32_t* file_frames, int64_t F,
+                           const int32_t* file, const int32_t* start_frame, const int32_t* n_frames, float threshold, int64_t B,
+                           int64_t T_max, int64_t Fr_max, int hop);
+
+/* ---- the rows of a ragged group from several files (main.py:143-159, one slice of one file at a time there) -------------
+ * ONE launch forms R rows from a padded batch of F files: audio (F, T_max), f0 and volume (F, Fr_max), key_factor (F) fp32,
+ * n_file_samples / n_file_frames (F) int32 the files' own counts, table (R, 5) int32 rows (file, start_frame, n_frames,
+ * start_sample, n_samples), all DEVICE arrays.  The host forms the sample range (the hop may be fractional: int(start_frame *
+ * hop_size), as main.split snaps).
+ *   wav (R, S_max):      wav[r][j] = audio[file][start_sample + j] for j < n_samples, exactly 0 after;
+ *   f0_rows (R, N_max):  f0[file][start_frame + j] * key_factor[file] for j < n_frames - ONE rounded fp32 product per element,
+ *                        contracted with nothing -, exactly 0 after;
+ *   vol_rows (R, N_max): volume[file][start_frame + j] for j < n_frames, exactly 0 after.
+ * audio and wav may both be NULL (no sample rows: table columns 3, 4 are ignored), or f0, volume, key_factor, f0_rows and
+ * vol_rows all NULL (no frame rows: columns 1, 2 are ignored); volume and vol_rows alone may be NULL too (the f0 rows without
+ * the volume rows, as the enhancer takes them).  16-byte loads and stores where a run of four lies inside the
+ * piece (the row) at an aligned address, a scalar select elsewhere: no address outside a file's own row of audio, f0 or volume is
+ * formed.  A row with file outside [0, F), a negative number, a range that leaves its file's counts, n_samples > S_max or
+ * n_frames > N_max is written as zeros and sets the context's device error word (DDSP_ERR_ARG from ddsp_ctx_poll_error or the
+ * next call that takes it).  R <= 65535.  Does not synchronise, allocate or read back. */
+int ddsp_pieces_gather(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
+                       const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F,
+                       int64_t T_max, int64_t Fr_max, const int32_t* table, int64_t R, int64_t S_max, int64_t N_max, float* wav,
+                       float* f0_rows, float* vol_rows);
 
 /* ---- the stitch of an offline conversion (main.py:165-173 with `cross_fade`, main.py:50-57) ----------------------------
  * Places S rendered pieces into one fp64 output in ONE launch.  `pieces` is a DEVICE table of S rows; piece i holds `len`
