@@ -8,12 +8,12 @@ one after the other, and with `enhancer_batch_samples=` they are enhanced in rag
 (`Enhancer.enhance_batch`).  `convert` starts from the raw audio: f0 (`F0_Extractor`), volume and per-slice units
 (`Units_Encoder`) on the device, then `render`.  `split` cuts the audio into slices as `main.split` does, with the package's
 own `slicer.Slicer` (the reference's silence detector on the device); `convert(..., slices=None, ...)` calls it, or takes
-the slice boundaries of any other detector.  `render_device` / `convert_device` are `render` / `convert_batched` with the end
-on the device too: one gate launch per ragged group (`ddsp_volume_gate_rows`), one launch for the stitch (`stitch_plan`,
-`stitch`: `ddsp_stitch`), the float64 waveform returned as a device tensor; `main.py` is the command line over them.
-`analyse_many` / `render_many_device` / `convert_many_device` / `convert_many` take a LIST of files: one ragged analysis of all
-files, ragged groups over the slices of all files (rows formed by `ddsp_pieces_gather`, gated by `ddsp_volume_gate_files`), one
-stitch of every file into one tensor (`stitch_plan_many`), one read-back.
+the slice boundaries of any other detector: the reference-shaped statement the device path is held to sample for sample.
+The device path is ONE body over a LIST of files (`_analyse_files`, `_render_files`): one analysis of all files, ragged groups
+over the slices of all files (rows formed by `ddsp_pieces_gather`, gated by `ddsp_volume_gate_files`), one stitch of every
+file into one fp64 device tensor (`stitch_plan_many`, `ddsp_stitch`), one read-back: `analyse_many` / `render_many_device` /
+`convert_many_device` / `convert_many`.  `render_device` / `convert_device` - `render` / `convert_batched` with the end on the
+device - are that body on a list of one file, which is its own batch and keeps `render`'s seed and speaker rules.
 """
 import numbers
 
@@ -80,7 +80,8 @@ def _render_ragged(model, segments, f0, volume, spk_id, spk_mix_dict, noise_seed
 
 def _encode_ragged(units_encoder, pieces, sample_rate, hop_size, units_batch_samples):
     """pieces: [(start_frame, audio (1, n))] -> [(start_frame, units (1, int(n // hop_size) + 1, n_unit))] in the same order,
-    from one ragged `Units_Encoder.encode` per group of `group_segments` over the sample lengths."""
+    from one ragged `Units_Encoder.encode` per group of `group_segments` over the sample lengths.  The torch-slice statement
+    of what `_analyse_files` does with `ddsp_pieces_gather` rows (tests/test_hubert_ragged_host.py holds its grouping)."""
     lengths = [seg.shape[-1] for _, seg in pieces]
     out = [None] * len(pieces)
     for group in group_segments(lengths, int(units_batch_samples)):
@@ -93,7 +94,8 @@ def _encode_ragged(units_encoder, pieces, sample_rate, hop_size, units_batch_sam
 
 def _enhance_ragged(enhancer, gated, segments, f0, sr, block, adaptive_key, enhancer_batch_samples):
     """Every gated slice (1, n * block) enhanced, in the order of `segments`, from one `Enhancer.enhance_batch` per group of
-    `group_segments` over the sample lengths, each row with its own f0 slice -> ([(1, n_out)], enhancer sample rate)."""
+    `group_segments` over the sample lengths, each row with its own f0 slice -> ([(1, n_out)], enhancer sample rate).
+    Serves `render` alone: the device path enhances with `_enhance_many`."""
     lengths = [g.shape[-1] for g in gated]
     out, sr_o = [None] * len(gated), sr
     for group in group_segments(lengths, int(enhancer_batch_samples)):
@@ -214,44 +216,10 @@ def stitch(pieces, plan, device=None):
     return hipddsp.context_for(pieces[0].device).stitch(pieces, p, fade, total)
 
 
-@torch.no_grad()
-def render_device(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, threshold_db=-60, enhancer=None,
-                  enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None, enhancer_batch_samples=None):
-    """`render` with its keywords, the result left on the device -> (fp64 device tensor (total,), sample rate), equal to
-    `render`'s array.  Ragged groups through `model(..., n_frames=)`, ONE `ddsp_volume_gate_rows` per group on the group's
-    padded signal (no gate per slice, no whole-file `ones`), `_enhance_ragged` when there is an enhancer, one `stitch` of the
-    rows where they lie.  `batch_frames=None` / `enhancer_batch_samples=None`: one slice per group.  Nothing is read back
-    between the first forward and the returned tensor beyond what `Enhancer.enhance_batch` itself reads."""
-    block = int(args.data.block_size)
-    sr = int(args.data.sampling_rate)
-    ctx = hipddsp.context_for(f0.device)
-    lengths = [units.size(1) for _, units in segments]
-    for (start, _), n in zip(segments, lengths):
-        if start < 0 or start + n > f0.shape[1] or start + n > volume.shape[1]:
-            raise ValueError(f"render_device: the segment at frame {start} has {n} frames of units but f0 / volume cover "
-                             f"{f0.shape[1]} / {volume.shape[1]} frames of the file")
-    pieces = [None] * len(segments)
-    for group in group_segments(lengths, 0 if batch_frames is None else int(batch_frames)):
-        starts = [segments[i][0] for i in group]
-        u, counts = stack_rows([segments[i][1][0] for i in group])
-        f, _ = stack_rows([f0[0, s:s + n] for s, n in zip(starts, counts)])
-        v, _ = stack_rows([volume[0, s:s + n] for s, n in zip(starts, counts)])
-        kw = {} if noise_seed is None else {"noise_seed": noise_seed + min(starts)}
-        if noise is not None:
-            kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
-        signal = model(u, f, v, spk_id=spk_id, spk_mix_dict=spk_mix_dict, n_frames=counts, **kw)[0].contiguous()
-        ctx.volume_gate_rows_(signal, volume[0], ctx.ragged_counts(starts), ctx.ragged_counts(counts), threshold_db, block)
-        for j, i in enumerate(group):
-            pieces[i] = signal[j:j + 1, :counts[j] * block]
-    sr_o = sr
-    if enhancer is not None and segments:
-        pieces, sr_o = _enhance_ragged(enhancer, pieces, segments, f0, sr, block, enhancer_adaptive_key,
-                                       0 if enhancer_batch_samples is None else enhancer_batch_samples)
-    plan = stitch_plan([start for start, _ in segments], [x.shape[-1] for x in pieces], block, sr, sr_o)
-    return stitch(pieces, plan, device=f0.device), sr_o
+SLICER_DB_THRESH, SLICER_MIN_LEN = -40, 5000      # `main.py`'s slicer settings: `split`'s defaults and `slices=None`
 
 
-def split(audio, sample_rate, hop_size, db_thresh=-40, min_len=5000):
+def split(audio, sample_rate, hop_size, db_thresh=SLICER_DB_THRESH, min_len=SLICER_MIN_LEN):
     """The slicing of `main.split` (main.py:34-40): audio (T,) numpy array or tensor at `sample_rate` -> the list of
     (start_sample, end_sample) of every chunk `Slicer(sr=sample_rate, threshold=db_thresh, min_length=min_len)` tags with
     start != end - the silence chunks too: `main.split` does not look at the flag.  One read-back (chunk table and count).
@@ -296,49 +264,7 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
                   enhancer_batch_samples=enhancer_batch_samples)
 
 
-@torch.no_grad()
-def convert_device(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, batch_frames=None, key=0,
-                   spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
-                   enhancer_batch_samples=None, units_batch_samples=None):
-    """`convert_batched` ending in `render_device`: the same analysis, then ragged rendering, one gate launch per group, the
-    ragged enhancer and one stitch launch -> (fp64 device tensor (total,), sample rate), equal to `convert_batched`'s array.
-    One `.cpu()` of the result is the file's only read-back behind the slicer's chunk table."""
-    segments, f0, volume = _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples)
-    return render_device(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
-                         enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed,
-                         batch_frames=batch_frames, enhancer_batch_samples=enhancer_batch_samples)
-
-
-def _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples):
-    """The part of `convert` in front of the rendering -> (segments [(start_frame, units (1, Fr_seg, n_unit))], f0 (1, Fr, 1)
-    shifted by `key`, volume (1, Fr)), all on the device."""
-    hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
-    if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
-        raise ValueError(f"convert: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop {f0_extractor.hop_size}; "
-                         f"the audio is at {sample_rate} Hz with hop {hop_size}")
-    if isinstance(audio, np.ndarray):
-        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-    dev = audio.device if audio.is_cuda else torch.device(f0_extractor.device)
-    x = audio.reshape(-1).to(dev, torch.float32)
-    f0 = f0_extractor.extract(x, uv_interp=True)[None, :, None]
-    if key != 0:
-        f0 = f0 * 2 ** (float(key) / 12)
-    volume = hipddsp.context_for(dev).volume_extract(x[None], hop_size)
-    if slices is None:
-        slices = split(x, sample_rate, hop_size)
-    segments = []
-    for start, end in slices:
-        start_frame, end_frame = int(int(start) // hop_size), int(int(end) // hop_size)
-        if end_frame > start_frame:
-            seg = x[None, int(start_frame * hop_size):int(end_frame * hop_size)]
-            segments.append((start_frame, seg if units_batch_samples is not None else
-                             units_encoder.encode(seg, sample_rate, hop_size)))
-    if units_batch_samples is not None:
-        segments = _encode_ragged(units_encoder, segments, sample_rate, hop_size, units_batch_samples)
-    return segments, f0, volume
-
-
-# ---- several files in one call: ragged groups across files ---------------------------------------------------------------
+# ---- the device path: a list of files in one call, ragged groups across files ---------------------------------------------
 
 def piece_table(slices_per_file, hop_size):
     """The pieces of several files as `ddsp_pieces_gather` takes them: `slices_per_file[k]` is file k's list of (start_sample,
@@ -389,16 +315,21 @@ def group_pieces(pieces, budget, by_samples=False):
     return group_segments([row[4 if by_samples else 2] for row in pieces], budget)
 
 
-def _upload_pieces(ctx, pieces, groups):
-    """The piece table in the order the groups take it, uploaded once -> (table (P, 5) int32 device, its transpose (5, P),
-    [(first, last + 1)] of every group): a group's rows, and each of its columns, are contiguous views."""
-    order = [i for group in groups for i in group]
-    table = torch.tensor([pieces[i] for i in order], dtype=torch.int32).reshape(-1, 5).to(ctx.device)
+def _upload_pieces(ctx, files, groups):
+    """The piece table of `files` in the order the groups take it -> (table (P, 5) int32 device, its transpose (5, P),
+    [(first, last + 1)] of every group): a group's rows, and each of its columns, are contiguous views.  The upload is kept in
+    `files` and serves every later stage that asks for the same rows: the order of `group_segments` is the sort by length
+    whatever the budget, so the units (whole hops of samples), the forwards and the enhancer of one call share one upload.
+    A blocking copy in front of a stage would make the device wait while the host issues that stage's launches."""
+    rows = [files["pieces"][i] for group in groups for i in group]
+    if files.get("table_rows") != rows:
+        table = torch.tensor(rows, dtype=torch.int32).reshape(-1, 5).to(ctx.device)
+        files.update(table_rows=rows, table=table, table_cols=table.t().contiguous())
     bounds, at = [], 0
     for group in groups:
         bounds.append((at, at + len(group)))
         at += len(group)
-    return table, table.t().contiguous(), bounds
+    return files["table"], files["table_cols"], bounds
 
 
 def _per_file(value, F, what):
@@ -418,7 +349,7 @@ def _per_file(value, F, what):
 
 @torch.no_grad()
 def analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys=0, units_batch_samples=None):
-    """`_analyse` for a list of files at one `sample_rate`: `audios[k]` a numpy array or tensor (T_k,).  ONE ragged
+    """The analysis of a list of files at one `sample_rate`: `audios[k]` a numpy array or tensor (T_k,).  ONE ragged
     `F0_Extractor.extract(..., uv_interp=True, n_samples=)`, ONE ragged volume and - `slices` None - ONE ragged slicer call with
     one read-back of the chunk tables cover all files (otherwise `slices[k]` is file k's list of (start_sample, end_sample));
     the units of all slices of all files are encoded in `group_segments` groups over the global list of slices
@@ -433,30 +364,55 @@ def analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor,
     if not float(hop_size).is_integer():
         raise ValueError(f"analyse_many: the ragged volume (n_samples=) needs an integral hop, but block_size * sample_rate / "
                          f"sampling_rate = {hop_size}; resample the files to the model's rate first")
+    return _analyse_files(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys, units_batch_samples)
+
+
+def _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples):
+    """The part of `convert` in front of the rendering -> (segments [(start_frame, units (1, Fr_seg, n_unit))], f0 (1, Fr, 1)
+    shifted by `key`, volume (1, Fr)), all on the device: `_analyse_files` on the one file, as its own batch."""
+    return file_features(_analyse_files(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples,
+                                        solo=True), 0)
+
+
+def _analyse_files(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys, units_batch_samples, solo=False):
+    """The one analysis body -> `analyse_many`'s dict.  `solo`: `audios`, `slices` and `keys` are those of ONE file (`_analyse`),
+    which is a list of one file that is its own batch."""
+    if solo:
+        # A single file is its own batch: its row is the file itself, unpadded, and the analysers are called without counts -
+        # their solo form: its bits, its draw of the dither seed, the volume of a fractional hop - as is the encoder for a slice
+        # that is a group of its own; a given slice that reaches past the file's end is cut there, as a Python slice is.
+        audios, slices = [audios.reshape(-1)], None if slices is None else [slices]
+        who, batch_of_files, lone_slices = "convert", False, units_batch_samples is None
+    else:
+        who, batch_of_files, lone_slices = "analyse_many", True, False
+    hop_size = int(args.data.block_size) * sample_rate / int(args.data.sampling_rate)
     if f0_extractor.sample_rate != sample_rate or f0_extractor.hop_size != hop_size:
-        raise ValueError(f"analyse_many: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
-                         f"{f0_extractor.hop_size}; the audio is at {sample_rate} Hz with hop {hop_size}")
+        raise ValueError(f"{who}: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop {f0_extractor.hop_size}; "
+                         f"the audio is at {sample_rate} Hz with hop {hop_size}")
     F = len(audios)
     dev = next((a.device for a in audios if isinstance(a, torch.Tensor) and a.is_cuda), torch.device(f0_extractor.device))
     files = {"hop_size": hop_size, "sample_rate": sample_rate, "device": dev, "pieces": [], "units": [], "n_samples": [],
              "n_frames": []}
     if F == 0:
         return files
-    keys = _per_file(keys, F, "analyse_many: keys")
+    keys = _per_file(keys, F, f"{who}: keys")
     if slices is not None and len(slices) != F:
-        raise ValueError(f"analyse_many: slices of {len(slices)} files for {F} files")
+        raise ValueError(f"{who}: slices of {len(slices)} files for {F} files")
     counts = [int(a.shape[0]) if getattr(a, "ndim", 0) == 1 else -1 for a in audios]
     if min(counts) < 1:
-        raise ValueError("analyse_many: every file must be mono audio of shape (T,) with T >= 1")
+        raise ValueError(f"{who}: every file must be mono audio of shape (T,) with T >= 1")
     ctx = hipddsp.context_for(dev)
-    # The batch's width is the longest file's, rounded up to 4 samples: every file's row then starts on 16 bytes, and with the
-    # slice starts of an integral hop (multiples of it) the gather of the encoder's rows takes its 16-byte loads.  Not where
-    # the rounding would add a frame to the volume's width (the longest file within 3 samples of a hop multiple).
-    T_max = max(counts)
-    width = -(-T_max // 4) * 4
-    if width // int(hop_size) != T_max // int(hop_size):
-        width = T_max
-    if all(isinstance(a, np.ndarray) for a in audios):          # padded on the host: one upload
+    # The width of a batch of files is the longest file's, rounded up to 4 samples: every file's row then starts on 16 bytes, and
+    # with the slice starts of an integral hop (multiples of it) the gather of the encoder's rows takes its 16-byte loads.  Not
+    # where the rounding would add a frame to the volume's width (the longest file within 3 samples of a hop multiple).
+    width, ragged = max(counts), counts if batch_of_files else None
+    if batch_of_files and -(-width // 4) * 4 // int(hop_size) == width // int(hop_size):
+        width = -(-width // 4) * 4
+    if not batch_of_files:                                      # the file is the row
+        a = audios[0]
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
+        x = a.to(dev, torch.float32).contiguous()[None]
+    elif all(isinstance(a, np.ndarray) for a in audios):        # padded on the host: one upload
         host = np.zeros((F, width), dtype=np.float32)
         for k, a in enumerate(audios):
             host[k, :counts[k]] = a
@@ -466,30 +422,36 @@ def analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor,
         for k, a in enumerate(audios):
             a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) if isinstance(a, np.ndarray) else a
             x[k, :counts[k]] = a.to(dev, torch.float32)
-    f0 = f0_extractor.extract(x, uv_interp=True, n_samples=counts)
-    volume = ctx.volume_extract(x, int(hop_size), counts)
-    if slices is None:
-        table, count, _ = Slicer(sr=sample_rate, threshold=-40, min_length=5000).chunks(x, n_samples=counts)
+    if slices is None:                                                 # `split` of every row, in one call
+        table, count, _ = Slicer(sr=sample_rate, threshold=SLICER_DB_THRESH, min_length=SLICER_MIN_LEN).chunks(x, n_samples=ragged)
         host = torch.cat([count, table.reshape(-1)]).cpu().numpy()     # the call's one read-back in front of the result
         ctx.poll_error()
         rows = host[F:].reshape(F, -1, 3)
         slices = [[(int(a), int(b)) for a, b, _ in rows[k, :host[k]] if a != b] for k in range(F)]
-    n_frames = [n // int(hop_size) + 1 for n in counts]
+    n_frames = [int(n // hop_size) + 1 for n in counts]
     pieces = piece_table(slices, hop_size)
+    if not batch_of_files:                                      # the cut at the file's end: `audio[start:end]` of main.py:41-46
+        cut = [min(row[4], counts[0] - row[3]) for row in pieces]
+        pieces = [(0, row[1], int(ns // hop_size) + 1, row[3], ns) for row, ns in zip(pieces, cut)]
     for k, start_frame, n, start_sample, n_samples in pieces:
-        if start_sample < 0 or start_sample + n_samples > counts[k] or start_frame + n > n_frames[k]:
-            raise ValueError(f"analyse_many: file {k}: the slice at frame {start_frame} ({n} frames, samples {start_sample} to "
+        if start_sample < 0 or n_samples < 1 or start_sample + n_samples > counts[k] or start_frame + n > n_frames[k]:
+            raise ValueError(f"{who}: file {k}: the slice at frame {start_frame} ({n} frames, samples {start_sample} to "
                              f"{start_sample + n_samples}) leaves the file's {counts[k]} samples / {n_frames[k]} frames")
-    files.update(audio=x, f0=f0.contiguous(), volume=volume, n_samples=counts, n_frames=n_frames, pieces=pieces,
-                 key_factor=torch.tensor([2 ** (float(key) / 12) for key in keys], dtype=torch.float32).to(dev),
-                 n_samples_dev=ctx.ragged_counts(counts), n_frames_dev=ctx.ragged_counts(n_frames))
+    # Every upload of the call stands here, in front of its launches: a blocking copy behind them would hold the host until the
+    # device has caught up, and the device would then wait while the host issues the encoder and the forwards.
+    counts_dev = ctx.ragged_counts(counts + n_frames).reshape(2, F)
+    files.update(audio=x, n_samples=counts, n_frames=n_frames, pieces=pieces, n_samples_dev=counts_dev[0],
+                 n_frames_dev=counts_dev[1],
+                 key_factor=torch.tensor([2 ** (float(key) / 12) for key in keys], dtype=torch.float32).to(dev))
     units = [None] * len(pieces)
     groups = group_pieces(pieces, 0 if units_batch_samples is None else int(units_batch_samples), by_samples=True)
-    table, _, bounds = _upload_pieces(ctx, pieces, groups)
+    table, _, bounds = _upload_pieces(ctx, files, groups)
+    files.update(f0=f0_extractor.extract(x, uv_interp=True, n_samples=ragged).contiguous(),
+                 volume=ctx.volume_extract(x, hop_size, ragged))
     for group, (a, b) in zip(groups, bounds):
         n_rows = [pieces[i][4] for i in group]
         wav, _, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], audio=x, S_max=max(n_rows))
-        got = units_encoder.encode(wav, sample_rate, hop_size, n_samples=n_rows)
+        got = units_encoder.encode(wav, sample_rate, hop_size, n_samples=None if lone_slices else n_rows)
         for j, i in enumerate(group):
             units[i] = got[j:j + 1, :pieces[i][2]].clone()
     files["units"] = units
@@ -503,6 +465,22 @@ def file_features(files, k):
     segments = [(row[1], u) for row, u in zip(files["pieces"], files["units"]) if row[0] == k]
     f0 = files["f0"][k:k + 1, :n, None] * files["key_factor"][k]
     return segments, f0, files["volume"][k:k + 1, :n]
+
+
+def file_of_features(segments, f0, volume):
+    """The inverse of `file_features`: (segments, f0 (1, Fr, 1) already shifted, volume (1, Fr)) -> the dict of a list of one
+    file, as `_render_files` takes it.  The key factor is 1.0 (an exact product); a piece row is (0, start frame, frames of
+    units, 0, 0), the audio half unused.  n_frames is the volume's length (the gate's dilation ends where the given track
+    ends) and f0 is cut or zero-padded to it: a segment inside both tracks, which `render_device` checks first, reads neither."""
+    n = volume.shape[1]
+    track = f0[0, :n, 0].float()
+    if track.shape[0] < n:
+        track = torch.nn.functional.pad(track, (0, n - track.shape[0]))
+    counts = torch.tensor([[0], [n]], dtype=torch.int32).to(f0.device)          # (one upload)
+    return {"device": f0.device, "n_samples": [0], "n_frames": [n], "n_samples_dev": counts[0], "n_frames_dev": counts[1],
+            "f0": track[None].contiguous(), "volume": volume.float().contiguous(), "key_factor": torch.ones(1, device=f0.device),
+            "pieces": [(0, int(start), units.size(1), 0, 0) for start, units in segments],
+            "units": [units for _, units in segments]}
 
 
 @torch.no_grad()
@@ -523,44 +501,90 @@ def render_many_device(model, args, files, spk_ids, spk_mix_rows=None, threshold
     (noise_seed + g * 2**32) mod 2**64, and the in-kernel draw is a hash of (seed, row, sample).  The grouping depends on the
     files' slice lengths and `batch_frames` alone, so the same call twice gives the same bits; two identical files in one call
     lie in different rows or different groups, so their noise differs.  (The draws are not those of `render_device` per file.)"""
-    block = int(args.data.block_size)
-    sr = int(args.data.sampling_rate)
-    dev = files["device"]
-    F, pieces, units = len(files["n_samples"]), files["pieces"], files["units"]
+    F, pieces, dev = len(files["n_frames"]), files["pieces"], files["device"]
+    if F and noise is not None and ([len(x) for x in noise] != [sum(1 for row in pieces if row[0] == k) for k in range(F)]):
+        raise ValueError("render_many_device: noise must hold one list per file with one draw per slice")
+
+    def speaker(file_of_row):                             # every row takes its file's speaker, or its file's mix
+        rows = file_of_row.long()
+        if spk_mix_rows is None:
+            spk = torch.tensor(_per_file(spk_ids, F, "render_many_device: spk_ids"), dtype=torch.int64).to(dev)
+            spk, mix = spk.index_select(0, rows).reshape(-1, 1), None
+        else:
+            if spk_mix_rows[0].shape[0] != F or spk_mix_rows[1].shape[0] != F:
+                raise ValueError(f"render_many_device: spk_mix_rows must hold one row per file ({F})")
+            mix = [t.index_select(0, rows).contiguous() for t in spk_mix_rows]
+            spk = torch.ones(len(pieces), 1, dtype=torch.int64, device=dev)      # (not read: the mix stands in its place)
+
+        def of_group(a, b):
+            return {"spk_id": spk[a:b]} if mix is None else {"spk_id": spk[a:b], "spk_mix_rows": (mix[0][a:b], mix[1][a:b])}
+        return of_group
+
+    def seed_of_group(g, starts):
+        return (int(noise_seed) + (g << 32)) & ((1 << 64) - 1)
+    return _render_files(model, args, files, speaker, None if noise_seed is None else seed_of_group,
+                         None if noise is None else [x for per_file in noise for x in per_file], threshold_db=threshold_db,
+                         enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, batch_frames=batch_frames,
+                         enhancer_batch_samples=enhancer_batch_samples)
+
+
+@torch.no_grad()
+def render_device(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, threshold_db=-60, enhancer=None,
+                  enhancer_adaptive_key=0, noise_seed=None, batch_frames=None, noise=None, enhancer_batch_samples=None):
+    """`render` with its keywords, the result left on the device -> (fp64 device tensor (total,), sample rate), equal to
+    `render`'s array: `_render_files` on `file_of_features(segments, f0, volume)`, a list of one file, under `render`'s rules - a
+    group draws with the seed noise_seed + its smallest start frame, `spk_id` and `spk_mix_dict` go to the model untouched (one
+    speaker for every row).  `batch_frames=None` / `enhancer_batch_samples=None`: one slice per group.  Nothing is read back
+    between the first forward and the returned tensor beyond what `Enhancer.enhance_batch` itself reads."""
+    for start, units in segments:
+        n = units.size(1)
+        if start < 0 or start + n > f0.shape[1] or start + n > volume.shape[1]:
+            raise ValueError(f"render_device: the segment at frame {start} has {n} frames of units but f0 / volume cover "
+                             f"{f0.shape[1]} / {volume.shape[1]} frames of the file")
+    return _render_file(model, args, file_of_features(segments, f0, volume), spk_id, spk_mix_dict, noise_seed, noise,
+                        threshold_db=threshold_db, enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key,
+                        batch_frames=batch_frames, enhancer_batch_samples=enhancer_batch_samples)
+
+
+def _render_file(model, args, files, spk_id, spk_mix_dict, noise_seed, noise, **stages):
+    """`_render_files` (`stages`: its keywords) on a list of one file under `render`'s seed and speaker rules -> (out, rate)."""
+    def speaker(file_of_row):
+        return lambda a, b: {"spk_id": spk_id, "spk_mix_dict": spk_mix_dict}
+
+    def seed_of_group(g, starts):
+        return noise_seed + min(starts)
+    out, _, sr_o = _render_files(model, args, files, speaker, None if noise_seed is None else seed_of_group, noise, **stages)
+    return out, sr_o
+
+
+def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshold_db, enhancer, enhancer_adaptive_key,
+                  batch_frames, enhancer_batch_samples):
+    """The one render body, as `render_many_device` states it.  What its callers differ in is passed in.  speaker: called once
+    with the file of every row (int32 device, rows in the groups' order) -> a function of a group's row range (a, b) giving the
+    model's speaker keywords.  seed_of_group: None (the model draws its seed) or a function of the group's number and its rows'
+    start frames -> the group's noise seed.  noise: None or one draw per piece, in `pieces` order."""
+    block, sr, dev = int(args.data.block_size), int(args.data.sampling_rate), files["device"]
+    F, pieces, units = len(files["n_frames"]), files["pieces"], files["units"]
     if F == 0:
         return torch.zeros(0, dtype=torch.float64, device=dev), [], sr
     ctx = hipddsp.context_for(dev)
     for k, start, n, _, _ in pieces:
         if start < 0 or start + n > files["n_frames"][k]:
-            raise ValueError(f"render_many_device: file {k}: the segment at frame {start} has {n} frames of units but f0 / volume "
+            raise ValueError(f"offline render: file {k}: the segment at frame {start} has {n} frames of units but f0 / volume "
                              f"cover {files['n_frames'][k]} frames of the file")
-    if noise is not None and ([len(x) for x in noise] != [sum(1 for row in pieces if row[0] == k) for k in range(F)]):
-        raise ValueError("render_many_device: noise must hold one list per file with one draw per slice")
-    flat_noise = None if noise is None else [x for per_file in noise for x in per_file]
     groups = group_pieces(pieces, 0 if batch_frames is None else int(batch_frames))
-    table, cols, bounds = _upload_pieces(ctx, pieces, groups)
-    rows_file = cols[0].long()
-    if spk_mix_rows is not None:
-        ids, w = spk_mix_rows
-        if ids.shape[0] != F or w.shape[0] != F:
-            raise ValueError(f"render_many_device: spk_mix_rows must hold one row per file ({F})")
-        mix = (ids.index_select(0, rows_file).contiguous(), w.index_select(0, rows_file).contiguous())
-        spk = torch.ones(len(pieces), 1, dtype=torch.int64, device=dev)          # (not read: the mix stands in its place)
-    else:
-        spk = torch.tensor(_per_file(spk_ids, F, "render_many_device: spk_ids"), dtype=torch.int64).to(dev)
-        spk = spk.index_select(0, rows_file).reshape(-1, 1)
+    table, cols, bounds = _upload_pieces(ctx, files, groups)
+    speaker_of_rows = speaker(cols[0])
     out = [None] * len(pieces)
     for g, (group, (a, b)) in enumerate(zip(groups, bounds)):
         counts = [pieces[i][2] for i in group]
         u, _ = stack_rows([units[i][0] for i in group])
         _, f, v = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
                                     volume=files["volume"], key_factor=files["key_factor"], N_max=max(counts))
-        kw = {} if noise_seed is None else {"noise_seed": (int(noise_seed) + (g << 32)) & ((1 << 64) - 1)}
-        if flat_noise is not None:
-            kw["noise"] = stack_rows([flat_noise[i].reshape(-1) for i in group])[0]
-        if spk_mix_rows is not None:
-            kw["spk_mix_rows"] = (mix[0][a:b], mix[1][a:b])
-        signal = model(u, f[:, :, None], v, spk_id=spk[a:b], n_frames=counts, **kw)[0].contiguous()
+        kw = {} if seed_of_group is None else {"noise_seed": seed_of_group(g, [pieces[i][1] for i in group])}
+        if noise is not None:
+            kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
+        signal = model(u, f[:, :, None], v, n_frames=counts, **speaker_of_rows(a, b), **kw)[0].contiguous()
         ctx.volume_gate_rows_(signal, files["volume"], cols[1, a:b], cols[2, a:b], threshold_db, block,
                               file_dev=cols[0, a:b], file_frames_dev=files["n_frames_dev"])
         for j, i in enumerate(group):
@@ -576,11 +600,11 @@ def render_many_device(model, args, files, spk_ids, spk_mix_rows=None, threshold
 
 
 def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples):
-    """`_enhance_ragged` over the gated pieces of all files: one `Enhancer.enhance_batch` per group of `group_segments` over
-    the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group)."""
+    """The device path's enhancer loop over the gated pieces of all files: one `Enhancer.enhance_batch` per group of
+    `group_segments` over the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group)."""
     pieces = files["pieces"]
     groups = group_segments([g.shape[-1] for g in gated], int(enhancer_batch_samples))
-    table, _, bounds = _upload_pieces(ctx, pieces, groups)
+    table, _, bounds = _upload_pieces(ctx, files, groups)
     out, sr_o = [None] * len(gated), sr
     for group, (a, b) in zip(groups, bounds):
         wav, counts = stack_rows([gated[i][0] for i in group])
@@ -603,6 +627,19 @@ def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extr
     return render_many_device(model, args, files, spk_ids, spk_mix_rows=spk_mix_rows, threshold_db=threshold_db, enhancer=enhancer,
                               enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
                               enhancer_batch_samples=enhancer_batch_samples)
+
+
+@torch.no_grad()
+def convert_device(model, args, audio, sample_rate, slices, units_encoder, f0_extractor, spk_id, batch_frames=None, key=0,
+                   spk_mix_dict=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
+                   enhancer_batch_samples=None, units_batch_samples=None):
+    """`convert_batched` ending as `render_device` does: `_analyse`'s analysis, its dict handed on as it is, then ragged
+    rendering, one gate launch per group, the ragged enhancer and one stitch launch -> (fp64 device tensor (total,), sample
+    rate), equal to `convert_batched`'s array.  One `.cpu()` of the result is the file's only read-back behind the slicer's."""
+    files = _analyse_files(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples, solo=True)
+    return _render_file(model, args, files, spk_id, spk_mix_dict, noise_seed, None, threshold_db=threshold_db, enhancer=enhancer,
+                        enhancer_adaptive_key=enhancer_adaptive_key, batch_frames=batch_frames,
+                        enhancer_batch_samples=enhancer_batch_samples)
 
 
 def convert_many(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, **kw):

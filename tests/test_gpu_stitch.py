@@ -182,12 +182,8 @@ def _fades_of(segments, lengths, sr_o):
     return infer_offline.stitch_plan([s for s, _ in segments], lengths, HOP, SR, sr_o)
 
 
-@pytest.mark.parametrize("with_enhancer", [False, True])
-def test_render_device_equals_render(dev, lib_path, tmp_path, with_enhancer):
-    """Four slices of 9, 3, 5 and 7 frames (the second overlaps the first by a frame: a cross-fade; gaps behind the second and
-    third), injected noise, volume shut over frames 20-31 so the gate bites inside the last slice; `batch_frames` and
-    `enhancer_batch_samples` the same on both sides."""
-    import infer_offline
+def _four_slices(dev):
+    """-> (the positional arguments of `render`, segments, their frame counts, keywords with the injected noise)."""
     from ddsp.vocoder import DotDict
     starts, lens = [0, 8, 13, 19], [9, 3, 5, 7]
     model, _ = synthetic.build_model("CombSub", seed=8, device=dev)
@@ -197,10 +193,19 @@ def test_render_device_equals_render(dev, lib_path, tmp_path, with_enhancer):
     segments = [(s, torch.from_numpy(rng.standard_normal((1, n, 256), dtype=np.float32)).to(dev)) for s, n in zip(starts, lens)]
     noise = [torch.from_numpy(rng.random(n * HOP, dtype=np.float32)).to(dev) for n in lens]
     args = DotDict({"data": {"block_size": HOP, "sampling_rate": SR}})
-    kw = dict(noise=noise, batch_frames=16)
+    common = (model, args, segments, whole["f0"].to(dev), whole["volume"].to(dev), whole["spk_id"].to(dev))
+    return common, segments, lens, dict(noise=noise, batch_frames=16)
+
+
+@pytest.mark.parametrize("with_enhancer", [False, True])
+def test_render_device_equals_render(dev, lib_path, tmp_path, with_enhancer):
+    """Four slices of 9, 3, 5 and 7 frames (the second overlaps the first by a frame: a cross-fade; gaps behind the second and
+    third), injected noise, volume shut over frames 20-31 so the gate bites inside the last slice; `batch_frames` and
+    `enhancer_batch_samples` the same on both sides."""
+    import infer_offline
+    common, segments, lens, kw = _four_slices(dev)
     if with_enhancer:
         kw.update(enhancer=_fixed_enhancer(tmp_path, dev), enhancer_batch_samples=8000)
-    common = (model, args, segments, whole["f0"].to(dev), whole["volume"].to(dev), whole["spk_id"].to(dev))
     want, sr_w = infer_offline.render(*common, **kw)
     got, sr_o = infer_offline.render_device(*common, **kw)
     assert sr_o == sr_w and got.is_cuda and got.dtype == torch.float64 and float(np.abs(want).max()) > 1e-3
@@ -213,6 +218,20 @@ def test_render_device_equals_render(dev, lib_path, tmp_path, with_enhancer):
         # equality, as if none were inside a fade
         p, fade = [], []
     _assert_stitched(got.cpu().numpy(), want, p, fade, f"render_device (enhancer {with_enhancer})")
+
+
+def test_render_device_passes_the_speaker_mix_to_the_model(dev, lib_path):
+    """`spk_mix_dict` goes through the one render body untouched: the four slices with a mix of two speakers, against `render`
+    with the same dictionary; the mix is not the call's `spk_id` alone."""
+    import infer_offline
+    common, segments, lens, kw = _four_slices(dev)
+    mix = {1: 0.5, 2: 0.5}
+    want, sr_w = infer_offline.render(*common, spk_mix_dict=mix, **kw)
+    got, sr_o = infer_offline.render_device(*common, spk_mix_dict=mix, **kw)
+    plain, _ = infer_offline.render_device(*common, **kw)
+    assert sr_o == sr_w == SR and float(np.abs(want).max()) > 1e-3 and not torch.equal(got, plain)
+    p, fade, _ = _fades_of(segments, [n * HOP for n in lens], sr_o)
+    _assert_stitched(got.cpu().numpy(), want, p, fade, "render_device (speaker mix)")
 
 
 def _voiced(n, f_lo, seed):
@@ -267,6 +286,60 @@ def test_convert_device_equals_convert_batched(dev, lib_path, encoder, slices):
         p, fade, total = infer_offline.stitch_plan([s for s, _ in frames], [n * HOP for _, n in frames], HOP, SR, SR)
         assert fade == [0, 0, 5 * HOP] and total == len(want)
     _assert_stitched(got.cpu().numpy(), want, p, fade, f"convert_device (slices {'given' if slices else 'None'})")
+
+
+@pytest.mark.parametrize("units_batch_samples", [None, 60000])
+def test_convert_device_at_a_fractional_hop(dev, lib_path, encoder, units_batch_samples):
+    """1 s at 48 kHz into a 44.1 kHz / 512 model: the hop is 557.28 samples, legal for ONE file.  The second slice starts at
+    sample 23962, no multiple of 4, so the gather of the encoder's rows takes its unaligned loads; both slices share a group."""
+    import infer_offline
+    from ddsp.vocoder import DotDict, F0_Extractor
+    sr_in, slices = 48000, [(0, 20000), (24000, 48000)]
+    hop = HOP * sr_in / SR
+    pieces = infer_offline.piece_table([slices], hop)
+    assert not float(hop).is_integer() and [row[1:] for row in pieces] == [(0, 35, 0, 19504), (43, 44, 23962, 23963)]
+    extractor = F0_Extractor("ac", sr_in, hop, 65.0, 800.0, device=dev)
+    model, _ = synthetic.build_model("CombSub", seed=8, device=dev)
+    args = DotDict({"data": {"block_size": HOP, "sampling_rate": SR}})
+    spk = torch.full((1, 1), 2, dtype=torch.int64, device=dev)
+    common = (model, args, _voiced(sr_in, 110.0, 31).astype(np.float32), sr_in, slices, encoder, extractor, spk, 96)
+    kw = dict(key=3, noise_seed=5, units_batch_samples=units_batch_samples)
+    want, sr_w = infer_offline.convert_batched(*common, **kw)
+    got, sr_o = infer_offline.convert_device(*common, **kw)
+    assert sr_o == sr_w == SR and float(np.abs(want).max()) > 1e-3
+    p, fade, total = infer_offline.stitch_plan([row[1] for row in pieces], [row[2] * HOP for row in pieces], HOP, SR, SR)
+    assert total == len(want) == 87 * HOP
+    _assert_stitched(got.cpu().numpy(), want, p, fade, f"convert_device (hop {hop:.2f}, units_batch_samples {units_batch_samples})")
+    if units_batch_samples is None:                       # the gather at unaligned starts, against the encoder on torch slices
+        x = torch.from_numpy(common[2]).to(dev)
+        segments, _, _ = infer_offline._analyse(args, common[2], sr_in, slices, encoder, extractor, 3, None)
+        for (start, units), (_, start_frame, n, at, n_samples) in zip(segments, pieces):
+            assert start == start_frame and units.shape[1] == n
+            assert torch.equal(units, encoder.encode(x[None, at:at + n_samples], sr_in, hop)), start
+
+
+def test_a_given_slice_that_reaches_past_the_file_is_cut_at_its_end(dev, lib_path, encoder):
+    """A detector's last slice rounded past T (3 s, 132300 samples; the slice ends at 135300): the one-file calls cut it at the
+    file's end as the Python slice of main.py:41-46 does - 44748 samples from 87552, 88 frames of units, the file's last frame
+    included - and do not refuse it.  The units against the encoder on the torch slice, bit for bit; then the whole chain."""
+    import infer_offline
+    from ddsp.vocoder import DotDict, F0_Extractor
+    extractor = F0_Extractor("ac", SR, HOP, 65.0, 800.0, device=dev)
+    model, _ = synthetic.build_model("CombSub", seed=8, device=dev)
+    args = DotDict({"data": {"block_size": HOP, "sampling_rate": SR}})
+    spk = torch.full((1, 1), 2, dtype=torch.int64, device=dev)
+    audio = _voiced(3 * SR, 110.0, 31).astype(np.float32)
+    slices = [(0, 40000), (88000, len(audio) + 3000)]
+    x = torch.from_numpy(audio).to(dev)
+    segments, f0, _ = infer_offline._analyse(args, audio, SR, slices, encoder, extractor, 0, None)
+    assert [(s, u.shape[1]) for s, u in segments] == [(0, 79), (171, 88)] and f0.shape[1] == 259
+    assert torch.equal(segments[1][1], encoder.encode(x[None, 171 * HOP:], SR, HOP))
+    common = (model, args, audio, SR, slices, encoder, extractor, spk, 96)
+    kw = dict(key=3, noise_seed=5, units_batch_samples=60000)
+    want, _ = infer_offline.convert_batched(*common, **kw)
+    got, _ = infer_offline.convert_device(*common, **kw)
+    assert len(want) == 259 * HOP and float(np.abs(want).max()) > 1e-3
+    _assert_stitched(got.cpu().numpy(), want, [], [], "convert_device (a slice past the end)")
 
 
 def test_main_run_writes_the_converted_file(dev, lib_path, encoder, tmp_path):

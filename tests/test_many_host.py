@@ -37,6 +37,29 @@ def test_stitch_plan_many_equals_the_per_file_plans():
         assert all(a <= b for a, b in zip(p, p[1:]))             # one table for one ddsp_stitch launch
 
 
+def test_a_file_is_a_list_of_one_file():
+    """`file_of_features` is the inverse of `file_features` (CPU tensors: nothing is launched), and the plan of a list of one
+    file is the file's own plan at span (0, total)."""
+    import torch
+
+    from infer_offline import file_features, file_of_features
+    g = torch.Generator().manual_seed(3)
+    starts, lens = [0, 8, 13, 19], [9, 3, 5, 7]
+    segments = [(s, torch.randn(1, n, 6, generator=g)) for s, n in zip(starts, lens)]
+    f0, volume = 100.0 + 300.0 * torch.rand(1, 40, 1, generator=g), torch.rand(1, 40, generator=g)
+    files = file_of_features(segments, f0, volume)
+    assert files["n_frames"] == [40] and files["pieces"] == [(0, s, n, 0, 0) for s, n in zip(starts, lens)]
+    assert files["f0"].shape == files["volume"].shape == (1, 40) and files["f0"].is_contiguous() and files["volume"].is_contiguous()
+    assert files["key_factor"].tolist() == [1.0] and files["n_frames_dev"].tolist() == [40] and files["n_frames_dev"].dtype == torch.int32
+    got_segments, got_f0, got_volume = file_features(files, 0)
+    assert [s for s, _ in got_segments] == starts and all(u is v for (_, u), (_, v) in zip(got_segments, segments))
+    assert torch.equal(got_f0, f0) and torch.equal(got_volume, volume) and got_f0.shape == f0.shape
+    lengths = [9 * BLOCK + 1, 3 * BLOCK, 5 * BLOCK + 3, 7 * BLOCK]
+    for sr_o in (SR, 48000):
+        p, fade, total = stitch_plan(starts, lengths, BLOCK, SR, sr_o)
+        assert stitch_plan_many([starts], [lengths], BLOCK, SR, sr_o) == ([(0, total)], p, fade, total) and fade[1] > 0
+
+
 def test_stitch_plan_many_of_nothing():
     assert stitch_plan_many([], [], BLOCK, SR, SR) == ([], [], [], 0)
     assert stitch_plan_many([[], []], [[], []], BLOCK, SR, SR) == ([(0, 0), (0, 0)], [], [], 0)
