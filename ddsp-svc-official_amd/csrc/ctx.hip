@@ -3,7 +3,7 @@
 
 #include <stdlib.h>
 
-#define DDSP_ABI_VERSION 8   // (new entry points beside unchanged ones do not bump it: tests pin it); 2: ddsp_rss_loss takes the hops; 3: ddsp_conv1d / ddsp_nsf_mean emit activated (split) copies, kept-activation entry points; 4: ddsp_retime_f0; 5: ddsp_u2c_weights::version (prepared-weight cache); 6: ddsp_hubert_weights; 7: ddsp_crepe_weights; 8: one symbol per operation - the _ragged / _batch / _scaled / _dseed / _share twins are folded into the un-suffixed names, whose optional parts are NULL / 1 (INTEGRATION.md has the old-name table)
+#define DDSP_ABI_VERSION 8   // (new entry points beside unchanged ones do not bump it: tests pin it - ddsp_bank_gather / ddsp_bank_scatter were added at 8); 2: ddsp_rss_loss takes the hops; 3: ddsp_conv1d / ddsp_nsf_mean emit activated (split) copies, kept-activation entry points; 4: ddsp_retime_f0; 5: ddsp_u2c_weights::version (prepared-weight cache); 6: ddsp_hubert_weights; 7: ddsp_crepe_weights; 8: one symbol per operation - the _ragged / _batch / _scaled / _dseed / _share twins are folded into the un-suffixed names, whose optional parts are NULL / 1 (INTEGRATION.md has the old-name table)
 
 extern "C" int ddsp_abi_version(void) { return DDSP_ABI_VERSION; }
 

@@ -143,7 +143,7 @@ class GraphedSynth(_Captured):
 
 
 def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, samplerate, hop_size, silence_front, pitch,
-                threshold_db, block_size, speaker, noise=None, f0_dither=True, seed_dev=None):
+                threshold_db, block_size, speaker, noise=None, f0_dither=True, seed_dev=None, push=None):
     """One block of the reference's callback from the raw audio to the gated model output (gui.py:373-374 and
     `gui.SvcDDSP.infer`, gui.py:87-127), every step on the device, nothing read back: `window` takes `block_in` in place,
     then volume, f0 (uv_interp, silent front), the pitch shift, units, the synthesiser and the gate.
@@ -152,8 +152,14 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     call.  The window keeps the rank it comes with down to the library, so each form reaches its own kernels.
     `speaker`: the speaker term as the model's keyword arguments, {"spk_id": (1, 1) int64, "spk_mix_dict": dict or None} or
     {"spk_id": None, "spk_mix_rows": (ids (S, K) int32, w (S, K) fp32)}.
+    `push(ctx, window, block_in)`: the step that brings `window` up to date, `ctx.stream_push_` unless given.  The compact rows of
+    a bank's active set (`realtime.StreamBank`, `active=`) are the S-stream form with `Context.bank_gather_` as this step: it pushes
+    the blocks into the named slots' own windows and fills `window`, `pitch` and the mix tables (the compact ones) from them.
     -> (signal (rows, Fr * block_size), f0 (rows, Fr, 1) after the shift, units (rows, Fr, C), volume (rows, Fr)), rows = 1 or S."""
-    ctx.stream_push_(window, block_in)
+    if push is None:
+        ctx.stream_push_(window, block_in)
+    else:
+        push(ctx, window, block_in)
     audio = window if window.dim() == 2 else window[None]
     volume = ctx.volume_extract(audio, hop_size)
     f0 = f0_extractor.extract(window, uv_interp=True, silence_front=silence_front, dither=f0_dither, seed_dev=seed_dev)
@@ -175,11 +181,12 @@ class GraphedBlock(_Captured):
     leaves its contents as it found them.  With `mix_rows=(mix_ids, mix_w)` these tables and a device `pitch` (S,) are the
     caller's too (`realtime.StreamBank`'s state): the graph reads them at their fixed addresses, so a write to a row between two
     replays is all a speaker, mix or pitch change takes.  Without it the speaker is the static input `spk_id` and the captured
-    `spk_mix_dict`, and `pitch` a host factor.  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
+    `spk_mix_dict`, and `pitch` a host factor.  `push`: `block_chain`'s; what it changes besides `window` it must leave alone
+    while the capture runs (the bank's row table is all padding then).  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
     next replay): `sig`, `f0`, `units`, `volume`."""
 
     def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch,
-                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3):
+                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None):
         if mix_rows is not None and spk_mix_dict is not None:
             raise ValueError("GraphedBlock: mix_rows and spk_mix_dict are mutually exclusive")
         p = next(model.parameters())
@@ -190,7 +197,7 @@ class GraphedBlock(_Captured):
         self.device = dev = p.device
         self.units_encoder, self.f0_extractor, self.window, self.pitch = units_encoder, f0_extractor, window, pitch
         self.args = (samplerate, hop_size, silence_front, float(threshold_db))
-        self.f0_dither = bool(f0_dither)
+        self.f0_dither, self.push = bool(f0_dither), push
         rows = window.shape[:-1]                                     # () or (S,)
         frames = int(window.shape[-1] // hop_size) + 1
         self.block_size = int(model.block_size)
@@ -209,7 +216,7 @@ class GraphedBlock(_Captured):
         samplerate, hop_size, silence_front, threshold_db = self.args
         return block_chain(self.ctx, self.model, self.units_encoder, self.f0_extractor, self.window, self.block_in, samplerate,
                            hop_size, silence_front, self.pitch, threshold_db, self.block_size, self.speaker, self.noise,
-                           self.f0_dither, self.seed)
+                           self.f0_dither, self.seed, self.push)
 
     @torch.no_grad()
     def __call__(self, block_in, spk_id=None, noise=None):

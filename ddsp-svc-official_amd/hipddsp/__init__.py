@@ -232,6 +232,9 @@ SIGNATURES = {
     "ddsp_crepe_activations": (_int, [_vp, _vp, _c.POINTER(CrepeWeights), _vp, _i64, _i64, _vp, _vp, _i64, _int, _vp]),
     "ddsp_crepe_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _i64, _u64, _vp, _int, _vp, _vp, _vp]),
     "ddsp_stream_push": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _i64]),
+    "ddsp_bank_gather": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                _vp, _vp, _vp]),
+    "ddsp_bank_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp]),
     "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _i64, _i64, _vp, _f32, _int, _f32, _vp]),
     "ddsp_f0_ac_frames": (_i64, [_i64, _int, _f64, _f64]),
     "ddsp_f0_ac": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _f64, _f64, _i64, _i64, _int, _vp, _vp]),
@@ -1423,6 +1426,40 @@ class Context:
         self.call("ddsp_stream_push", _ptr(window), window.shape[0] if window.dim() == 2 else 1, window.shape[-1], _ptr(block_in),
                   block_in.shape[-1])
         return window
+
+    def bank_gather_(self, rows, block_in, windows, cwindows, sola_buffer, csola, mix, cmix, pitch, cpitch, request=None,
+                     crequest=None):
+        """The active set of a stream bank into its compact rows (`ddsp_bank_gather`): rows (W,) int32 device, entry r the slot
+        of compact row r or -1 for padding.  In place: windows (S, n_in)[rows[r]] takes block_in (W, block)[r]; then cwindows
+        (W, n_in), csola (W, xfade), cmix = (ids (W, K) int32, w (W, K)), cpitch (W,) and crequest (W,) int32 take the rows of
+        windows, sola_buffer (S, xfade), mix, pitch (S,) and request (S,) int32 (both None: a bank without an enhancer).  A
+        padding row gets zeros, speaker 1 with weight 1, pitch 1, request 0.  -> cwindows."""
+        W, (S, n_in) = rows.numel(), windows.shape
+        K = check_mix_rows(mix[0], mix[1], S)
+        shapes = ((rows, (W,)), (block_in, (W, block_in.shape[-1])), (cwindows, (W, n_in)), (sola_buffer, (S, sola_buffer.shape[-1])),
+                  (csola, (W, sola_buffer.shape[-1])), (pitch, (S,)), (cpitch, (W,)))
+        if rows.dtype != torch.int32 or windows.dim() != 2 or any(tuple(t.shape) != s for t, s in shapes) or check_mix_rows(*cmix, W) != K:
+            raise ValueError("bank_gather_: S rows of the bank, W compact rows and a (W,) int32 row table")
+        if any(t.dtype != torch.float32 for t in (block_in, windows, cwindows, sola_buffer, csola, pitch, cpitch)):
+            raise ValueError("bank_gather_: windows, blocks, buffers and pitch must be fp32")
+        if (request is None) != (crequest is None) or (request is not None and (
+                request.dtype != torch.int32 or crequest.dtype != torch.int32 or tuple(request.shape) != (S,) or tuple(crequest.shape) != (W,))):
+            raise ValueError("bank_gather_: request (S,) and crequest (W,) int32, or neither")
+        self.call("ddsp_bank_gather", _ptr(rows), W, S, _ptr(windows), n_in, _ptr(block_in), block_in.shape[-1], _ptr(cwindows),
+                  _ptr(sola_buffer), sola_buffer.shape[-1], _ptr(csola), _ptr(mix[0]), _ptr(mix[1]), K, _ptr(cmix[0]), _ptr(cmix[1]),
+                  _ptr(pitch), _ptr(cpitch), _ptr(request), _ptr(crequest))
+        return cwindows
+
+    def bank_scatter_(self, rows, csola, sola_buffer):
+        """After the splice of the compact rows (`ddsp_bank_scatter`): sola_buffer (S, xfade)[rows[r]] = csola (W, xfade)[r] for
+        every row of rows (W,) int32 that is no padding.  -> sola_buffer."""
+        W, xfade = csola.shape
+        if rows.dtype != torch.int32 or tuple(rows.shape) != (W,) or sola_buffer.dim() != 2 or sola_buffer.shape[1] != xfade:
+            raise ValueError("bank_scatter_: csola (W, xfade), sola_buffer (S, xfade) and a (W,) int32 row table")
+        if csola.dtype != torch.float32 or sola_buffer.dtype != torch.float32:
+            raise ValueError("bank_scatter_: the buffers must be fp32")
+        self.call("ddsp_bank_scatter", _ptr(rows), W, sola_buffer.shape[0], _ptr(csola), xfade, _ptr(sola_buffer))
+        return sola_buffer
 
     def phase_vocoder(self, a, b, fade_out, fade_in):
         """gui.py:14-31: cross-fade of the kept tail `a` into the new head `b` (both (n,)) with a phase-interpolated

@@ -342,6 +342,84 @@ class StreamRenderer:
         return self.splicer.push(_to_device_rate(self._resamplers, sig, rate, self.samplerate)[0])
 
 
+def active_width(A, widths):
+    """The batch width at which a `StreamBank` call with A active slots runs: the smallest W >= A of the bank's ladder `widths`
+    (sorted).  Rows A..W-1 of the compact batch are padding.  ValueError when no width holds A rows."""
+    if isinstance(A, bool) or not isinstance(A, int) or A < 1:
+        raise ValueError(f"active_width: a call names at least one slot, got {A!r}")
+    for W in widths:
+        if W >= A:
+            return int(W)
+    raise ValueError(f"active_width: {A} active slots, the widest batch of the ladder {tuple(widths)} holds {max(widths, default=0)}")
+
+
+def _check_active_widths(active_widths, S):
+    """`StreamBank(active_widths=)` -> the ladder: the sorted distinct ints in 1..S as given, with S behind them if missing."""
+    widths = tuple(active_widths) if isinstance(active_widths, (tuple, list)) else None
+    if widths is None or any(isinstance(w, bool) or not isinstance(w, int) or not 1 <= w <= S for w in widths) or \
+            any(a >= b for a, b in zip(widths, widths[1:])):
+        raise ValueError(f"StreamBank: active_widths must be a sorted tuple of distinct ints in 1..{S}, got {active_widths!r}")
+    return widths if widths and widths[-1] == S else widths + (S,)
+
+
+class _Rows:
+    """What the chain of a `StreamBank` runs on at one batch width W: `windows` (W, n_in), the `splicer` with its (W, xfade)
+    buffer, the tables `spk_ids` / `spk_w` (W, K), `pitch` (W,) and `request` (W,) (the enhancer's key requests, or None), and
+    under `use_graph` the captures over them.  The bank's own state is the width-S instance; its window push is
+    `ddsp_stream_push`.  A compact instance (`active_widths`) has tensors of its own and a device row table `rows` (W,) int32,
+    entry r the slot of row r or -1 for padding, all padding until a call names its slots: its push is `ddsp_bank_gather` from the
+    bank's state, and `scatter` (`ddsp_bank_scatter`) brings the spliced buffers back to the slots."""
+
+    def __init__(self, bank, W, compact):
+        self.bank, self.W, self.A = bank, int(W), int(W)
+        self.graph = self.bank_graph = self.enhancer_graph = None
+        self.rows = self.request = None
+        if not compact:
+            self.windows, self.splicer, self.spk_ids, self.spk_w, self.pitch = bank.windows, bank.splicer, bank.spk_ids, bank.spk_w, bank.pitch
+            if bank.enhancer is not None:
+                self.request = bank.enhancer_request
+            return
+        dev = bank.device
+        self.rows = torch.full((self.W,), -1, dtype=torch.int32, device=dev)
+        self.windows = torch.zeros(self.W, bank.n_in, device=dev)
+        self.splicer = Splicer(*bank._splicer_args, rows=self.W)
+        self.spk_ids = torch.ones(self.W, bank.max_mix, dtype=torch.int32, device=dev)
+        self.spk_w = torch.zeros(self.W, bank.max_mix, device=dev)
+        self.spk_w[:, 0] = 1.0
+        self.pitch = torch.ones(self.W, device=dev)
+        if bank.enhancer is not None:
+            self.request = torch.zeros(self.W, dtype=torch.int32, device=dev)
+
+    def select(self, active):
+        """The slots of this call: one small upload into the row table, whose address the captured kernels hold."""
+        if self.rows is not None:
+            self.A = len(active)
+            self.rows.copy_(torch.tensor(list(active) + [-1] * (self.W - self.A), dtype=torch.int32))
+
+    def push(self, ctx, windows, blocks):
+        """`graphed.block_chain`'s push step: `windows` (this instance's) come up to date with `blocks` (W, block)."""
+        if self.rows is None:
+            return ctx.stream_push_(windows, blocks)
+        b = self.bank
+        return ctx.bank_gather_(self.rows, blocks, b.windows, windows, b.sola_buffer, self.splicer.buffer, (b.spk_ids, b.spk_w),
+                                (self.spk_ids, self.spk_w), b.pitch, self.pitch, None if self.request is None else b.enhancer_request,
+                                self.request)
+
+    def scatter(self):
+        if self.rows is not None:
+            hipddsp.context_for(self.bank.device).bank_scatter_(self.rows, self.splicer.buffer, self.bank.sola_buffer)
+
+    def pad(self, t, fill=0.0):
+        """Per-row input (A, ...) -> (W, ...): the padding rows behind the real ones."""
+        if t.shape[0] == self.W:
+            return t
+        return torch.cat([t, t.new_full((self.W - t.shape[0], *t.shape[1:]), fill)])
+
+    def real(self, *ts):
+        """Per-row results (W, ...) -> the A real rows of each."""
+        return ts if self.A == self.W else tuple(t[:self.A] for t in ts)
+
+
 class StreamBank:
     """S real-time streams of ONE geometry (device rate, block, cross-fade, window) on one GPU, all advanced by one block per
     call: the chain of `StreamRenderer` (its docstring, steps 1-8) with every step batched over the streams.  Under
@@ -370,17 +448,36 @@ class StreamBank:
     `last_signal` (S, N), the gated and resampled signal the splice consumed, hold that block's values (under the graph:
     static tensors, valid until the next block).
 
-    Idle slots: there is no activity mask.  An idle slot is a slot that is fed zeros; its rows are computed like every other
-    row, and its output is zero through the volume gate.  Not in the bank: streams of different geometry, skipping idle rows
-    (DESIGN section 7)."""
+    Active sets (`active_widths=`, a sorted tuple of distinct ints in 1..S; S is appended if missing; None: the feature is off
+    and nothing of it is allocated or captured).  A push call with `active=`, a strictly increasing sequence of A slot ints,
+    advances only those slots: its per-row arguments (`blocks` (A, block), `units`, `f0`, `noise`, a 2-D `rand_ini`), its result
+    and every `last_*` tensor have A rows, row r belonging to slot active[r], and `last_active` holds the slots.  The A rows run as
+    a compact batch of width W = `active_width(A, active_widths)`, the smallest width of the ladder that holds them: the same
+    chain on tensors of that width (`_Rows`), with `ddsp_bank_gather` as the window push - it pushes the blocks into the named
+    slots' own windows and copies their windows, SOLA buffers, mixes, pitches and key requests to the compact rows - and
+    `ddsp_bank_scatter` after the splice, which returns the spliced buffers.  Both read a device row table (W,) int32 that one
+    small upload rewrites before the call, so under `use_graph` every width is captured once, at construction: `graph_builds` is
+    1 + len(active_widths) (the appended S counted) for the life of the bank, the chain and the enhancer stage of a width
+    counting as one build as they do for the full width.  Rows A..W-1 are padding: a zero window, speaker 1 with weight 1, pitch 1
+    and key request 0; they are computed, never written back to a slot and never returned.
+    PAUSED SLOTS: a slot that a call does not name keeps its rows of `windows`, `sola_buffer`, `spk_ids`, `spk_w`, `pitch` and
+    `enhancer_request` bit for bit, and a caller that is named again carries on where it stopped; `reset(slot)` remains the way
+    to hand a slot to someone new.  A call without `active` is the full-width call on its own graph, on a bank with
+    `active_widths` too: there an idle slot is a slot that is fed zeros; its rows are computed like every other row, and its
+    output is zero through the volume gate.  Every refusal of a call (`active` on a bank without `active_widths`, an empty,
+    unsorted or repeated `active`, a slot outside [0, S), a bool or non-int slot, per-row arguments that do not have A rows) is a
+    ValueError raised before anything is uploaded or launched.  Not in the bank: streams of different geometry (DESIGN
+    section 7)."""
 
     def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
-                 f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12):
+                 f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
+                 active_widths=None):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
             raise ValueError(f"StreamBank: n_streams must be at least 1, got {n_streams}")
+        self.active_widths = None if active_widths is None else _check_active_widths(active_widths, self.S)
         self.max_mix = int(max_mix)
         if not 1 <= self.max_mix <= hipddsp.MAX_MIX:
             raise ValueError(f"StreamBank: max_mix must be in 1..{hipddsp.MAX_MIX}, got {max_mix}")
@@ -416,7 +513,8 @@ class StreamBank:
         self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
         dev = self.device
         self.windows = torch.zeros(self.S, self.n_in, device=dev)
-        self.splicer = Splicer(samplerate, block_time, crossfade_time, dev, use_phase_vocoder=use_phase_vocoder, rows=self.S)
+        self._splicer_args = (samplerate, block_time, crossfade_time, dev, 0.01, 0.02, use_phase_vocoder)
+        self.splicer = Splicer(*self._splicer_args, rows=self.S)
         self.sola_buffer = self.splicer.buffer                       # (S, xfade): the very tensor the splice updates
         self.spk_ids = torch.ones(self.S, self.max_mix, dtype=torch.int32, device=dev)   # every slot starts as speaker 1
         self.spk_w = torch.zeros(self.S, self.max_mix, device=dev)
@@ -433,20 +531,56 @@ class StreamBank:
         self.bank_graph = None           # the whole-block graph of `push_audio`
         self.enhancer_graph = None       # the enhancer stage, replayed right after either of them
         self.graph_builds = 0
+        self.last_active = None          # the slots of the last call that named them (`active=`)
+        self._full = _Rows(self, self.S, compact=False)
+        self._compact = {W: _Rows(self, W, compact=True) for W in self.active_widths or ()}
         if self.use_graph:
-            import graphed
-            if self.f0_extractor is not None:
-                self.bank_graph = graphed.GraphedBlock(
-                    self.model, self.units_encoder, self.f0_extractor, self.windows, self.block, self.samplerate, self.hop_size,
-                    self.silence_front, self.pitch, self.threshold_db, mix_rows=(self.spk_ids, self.spk_w),
-                    f0_dither=self.f0_dither)
-            else:
-                self.graph = graphed.GraphedSynth(self.model, self.S, self.frames, spk_mix_rows=(self.spk_ids, self.spk_w))
-            if enhancer is not None:
-                self.enhancer_graph = graphed.GraphedBankEnhancer(
-                    enhancer, self.enhancer_plan, self.S, self.enhancer_request, self.model_sr, self.block_size, self.samplerate,
-                    self._n_end_by_key, self._tail_idx)
-            self.graph_builds = 1
+            self._capture(self._full)
+            self.graph, self.bank_graph, self.enhancer_graph = self._full.graph, self._full.bank_graph, self._full.enhancer_graph
+            for rows in self._compact.values():
+                self._capture(rows)
+
+    def _capture(self, rows):
+        """The chain at the width of `rows` as its graphs: the block (or the synthesis alone) and the enhancer stage together
+        count as one build."""
+        import graphed
+        if self.f0_extractor is not None:
+            rows.bank_graph = graphed.GraphedBlock(
+                self.model, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
+                self.silence_front, rows.pitch, self.threshold_db, mix_rows=(rows.spk_ids, rows.spk_w),
+                f0_dither=self.f0_dither, push=rows.push)
+        else:
+            rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=(rows.spk_ids, rows.spk_w))
+        if self.enhancer is not None:
+            rows.enhancer_graph = graphed.GraphedBankEnhancer(
+                self.enhancer, self.enhancer_plan, rows.W, rows.request, self.model_sr, self.block_size, self.samplerate,
+                self._n_end_by_key, self._tail_idx)
+        self.graph_builds += 1
+
+    def _rows_for(self, active):
+        """`active` of a push call -> (the rows the call runs on, A, the slots as a tuple or None): every refusal, on the host."""
+        if active is None:
+            return self._full, self.S, None
+        if self.active_widths is None:
+            raise ValueError("StreamBank: active= needs a bank built with active_widths=")
+        try:
+            active = list(active)
+        except TypeError:
+            raise ValueError(f"StreamBank: active must be a sequence of slots, got {active!r}") from None
+        if not active:
+            raise ValueError("StreamBank: active names at least one slot (an empty call advances nothing)")
+        if any(isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.S for s in active):
+            raise ValueError(f"StreamBank: active holds slot ints in [0, {self.S}), got {active!r}")
+        if any(a >= b for a, b in zip(active, active[1:])):
+            raise ValueError(f"StreamBank: active must be strictly increasing, got {active!r}")
+        return self._compact[active_width(len(active), self.active_widths)], len(active), tuple(active)
+
+    def _check_draws(self, noise, rand_ini, A):
+        """`noise` / `rand_ini` of a call with `active`: compact like every per-row argument."""
+        if noise is not None and tuple(noise.shape) != (A, self.frames * self.block_size):
+            raise ValueError(f"StreamBank: noise (A, Fr * block_size) = {(A, self.frames * self.block_size)}, got {tuple(noise.shape)}")
+        if rand_ini is not None and tuple(rand_ini.shape) not in ((9,), (A, 9)):
+            raise ValueError(f"StreamBank: rand_ini (9,) or (A, 9) = {(A, 9)}, got {tuple(rand_ini.shape)}")
 
     def _slot(self, slot):
         if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.S:
@@ -491,76 +625,94 @@ class StreamBank:
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
 
-    def _blocks(self, blocks):
-        if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (self.S, self.block):
+    def _check_blocks(self, blocks, A, rows="S"):
+        if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
             got = tuple(blocks.shape) if isinstance(blocks, torch.Tensor) else type(blocks).__name__
-            raise ValueError(f"StreamBank: a call takes blocks of shape (S, block) = {(self.S, self.block)}, got {got}")
-        return blocks.to(self.device, torch.float32).contiguous()
+            raise ValueError(f"StreamBank: a call takes blocks of shape ({rows}, block) = {(A, self.block)}, got {got}")
 
-    def _enhanced_tail(self, sig, f0, rand_ini):
-        """Steps 6-7 with the enhancer: -> every row's own tail (S, block + xfade + search + delay) at the device rate."""
-        if self.enhancer_graph is not None:
-            tail, self.last_key = self.enhancer_graph(sig, f0, rand_ini)
-            return tail
-        import graphed
-        if rand_ini is None:
-            rand_ini = torch.rand(self.S, 9, device=self.device)
-        tail, self.last_key = graphed.bank_enhancer_chain(
-            hipddsp.context_for(self.device), self.enhancer, self.enhancer_plan, sig, f0, self.enhancer_request,
-            rand_ini.to(self.device), self.model_sr, self.block_size, self.samplerate, self._n_end_by_key, self._tail_idx)
+    def _enhanced_tail(self, rows, sig, f0, rand_ini):
+        """Steps 6-7 with the enhancer: -> every row's own tail (W, block + xfade + search + delay) at the device rate."""
+        if rows.enhancer_graph is not None:
+            tail, key = rows.enhancer_graph(sig, f0, rand_ini)
+        else:
+            import graphed
+            if rand_ini is None:
+                rand_ini = torch.rand(rows.W, 9, device=self.device)
+            tail, key = graphed.bank_enhancer_chain(
+                hipddsp.context_for(self.device), self.enhancer, self.enhancer_plan, sig, f0, rows.request,
+                rand_ini.to(self.device), self.model_sr, self.block_size, self.samplerate, self._n_end_by_key, self._tail_idx)
+        self.last_key, = rows.real(key)
         return tail
 
-    def _splice(self, sig, f0=None, rand_ini=None):
-        """Steps 6-8 over the rows: (S, Fr * block_size) at the model's rate -> (S, block) samples to play."""
+    def _splice(self, rows, sig, f0=None, rand_ini=None):
+        """Steps 6-8 over the rows: (W, Fr * block_size) at the model's rate -> (A, block) samples to play; the spliced buffers
+        of a compact batch go back to their slots."""
+        if rand_ini is not None and rows.rows is not None and rand_ini.dim() == 2:
+            rand_ini = rows.pad(rand_ini.to(self.device))
         if self.enhancer is not None:
-            sig = self._enhanced_tail(sig, f0, rand_ini).contiguous()
+            sig = self._enhanced_tail(rows, sig, f0, rand_ini).contiguous()
         else:
             sig = _to_device_rate(self._resamplers, sig, self.model_sr, self.samplerate).contiguous()
-        self.last_signal = sig
-        emitted = self.splicer.push(sig)
-        self.last_shift = self.splicer.last_shift
+        emitted = rows.splicer.push(sig)
+        rows.scatter()
+        self.last_signal, self.last_shift, emitted = rows.real(sig, rows.splicer.last_shift, emitted)
         return emitted
 
     @torch.no_grad()
-    def push_audio(self, blocks, noise=None, rand_ini=None):
+    def push_audio(self, blocks, noise=None, rand_ini=None, active=None):
         """blocks (S, block) raw samples at the device rate, one block per stream -> (S, block) samples to play.  `noise`
         (S, Fr * block_size) in [0, 1) replaces the fresh draw and `rand_ini` (9,) or (S, 9) the enhancer's source phases
-        (parity tests)."""
+        (parity tests).  With `active` (A slots, strictly increasing) every per-row argument and the result have A rows, row r
+        belonging to slot active[r]; the other slots stay as they are (class docstring)."""
         if self.f0_extractor is None:
             raise ValueError("StreamBank: push_audio needs units_encoder= and f0_extractor= at construction")
-        blocks = self._blocks(blocks)
-        if self.bank_graph is not None:
-            sig, f0, units, volume = self.bank_graph(blocks, noise=noise)
+        rows, A, active = self._rows_for(active)
+        self._check_blocks(blocks, A, "S" if active is None else "A")
+        if active is not None:
+            self._check_draws(noise, rand_ini, A)
+            noise = None if noise is None else rows.pad(noise.to(self.device))
+        blocks = rows.pad(blocks.to(self.device, torch.float32).contiguous())
+        rows.select(active)
+        if rows.bank_graph is not None:
+            sig, f0, units, volume = rows.bank_graph(blocks, noise=noise)
         else:
             import graphed
             sig, f0, units, volume = graphed.block_chain(
-                hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, self.windows, blocks,
-                self.samplerate, self.hop_size, self.silence_front, self.pitch, self.threshold_db, self.hop,
-                {"spk_id": None, "spk_mix_rows": (self.spk_ids, self.spk_w)}, noise, self.f0_dither)
-        self.last_f0, self.last_units, self.last_volume = f0, units, volume
-        return self._splice(sig, f0, rand_ini)
+                hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, rows.windows, blocks,
+                self.samplerate, self.hop_size, self.silence_front, rows.pitch, self.threshold_db, self.hop,
+                {"spk_id": None, "spk_mix_rows": (rows.spk_ids, rows.spk_w)}, noise, self.f0_dither, push=rows.push)
+        self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
+        self.last_active = active
+        return self._splice(rows, sig, f0, rand_ini)
 
     @torch.no_grad()
-    def push_block(self, blocks, units, f0, noise=None, rand_ini=None):
+    def push_block(self, blocks, units, f0, noise=None, rand_ini=None, active=None):
         """The analysis-free form: blocks (S, block), and `units` (S, Fr, C) and `f0` (S, Fr, 1) of the CURRENT windows from the
-        caller (before the pitch factor, which is applied here) -> (S, block) samples to play."""
-        blocks = self._blocks(blocks)
+        caller (before the pitch factor, which is applied here) -> (S, block) samples to play.  `active`: as in `push_audio`."""
+        rows, A, active = self._rows_for(active)
+        self._check_blocks(blocks, A, "S" if active is None else "A")
         if self.f0_extractor is not None:
             raise ValueError("StreamBank: this bank was built for push_audio; build one without units_encoder / f0_extractor "
                              "for push_block (one capture per bank)")
-        if tuple(units.shape[:2]) != (self.S, self.frames) or tuple(f0.shape) != (self.S, self.frames, 1):
-            raise ValueError(f"StreamBank: units (S, Fr, C) and f0 (S, Fr, 1) with (S, Fr) = {(self.S, self.frames)}, got "
+        if tuple(units.shape[:2]) != (A, self.frames) or tuple(f0.shape) != (A, self.frames, 1):
+            raise ValueError(f"StreamBank: units (S, Fr, C) and f0 (S, Fr, 1) with (S, Fr) = {(A, self.frames)}, got "
                              f"{tuple(units.shape)} and {tuple(f0.shape)}")
+        if active is not None:
+            self._check_draws(noise, rand_ini, A)
+            noise = None if noise is None else rows.pad(noise.to(self.device))
+        blocks = rows.pad(blocks.to(self.device, torch.float32).contiguous())
         ctx = hipddsp.context_for(self.device)
-        ctx.stream_push_(self.windows, blocks)
-        units = units.to(self.device)
-        f0 = f0.to(self.device, torch.float32) * self.pitch[:, None, None]
-        volume = ctx.volume_extract(self.windows, self.hop_size)
-        if self.graph is not None:
-            sig = self.graph(units, f0, volume, None, noise=noise)[0]
+        rows.select(active)
+        rows.push(ctx, rows.windows, blocks)
+        units = rows.pad(units.to(self.device))
+        f0 = rows.pad(f0.to(self.device, torch.float32)) * rows.pitch[:, None, None]
+        volume = ctx.volume_extract(rows.windows, self.hop_size)
+        if rows.graph is not None:
+            sig = rows.graph(units, f0, volume, None, noise=noise)[0]
         else:
             kw = {} if noise is None else {"noise": noise}
-            sig = self.model(units, f0, volume, None, spk_mix_rows=(self.spk_ids, self.spk_w), **kw)[0]
+            sig = self.model(units, f0, volume, None, spk_mix_rows=(rows.spk_ids, rows.spk_w), **kw)[0]
         ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
-        self.last_f0, self.last_units, self.last_volume = f0, units, volume
-        return self._splice(sig, f0, rand_ini)
+        self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
+        self.last_active = active
+        return self._splice(rows, sig, f0, rand_ini)

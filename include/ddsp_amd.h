@@ -409,6 +409,29 @@ int ddsp_sola(ddsp_ctx* ctx, void* stream, const float* audio, int S, int64_t n_
  * context's scratch arena (two launches in stream order), so the overlapping shift is exact whatever order workgroups run in. */
 int ddsp_stream_push(ddsp_ctx* ctx, void* stream, float* window, int S, int64_t n_in, const float* block_in, int64_t block);
 
+/* The row movers of a bank's active set (realtime.StreamBank, `active=`): a call that advances A of the S slots runs them as a
+ * compact batch of W rows, A <= W <= S.  rows (W) int32 DEVICE: entry r is the slot of compact row r, or -1 for a padding row;
+ * it is read when the kernels run, so a captured graph follows a table that the host rewrites between replays.  An entry is
+ * tested against [0, S) before it forms an address, and one outside is a padding row.  No slot may be named twice (the caller
+ * checks it: two rows of one slot would race for its window).  A slot that `rows` does not name is neither read nor written.
+ * ddsp_bank_gather, for every compact row r with slot s = rows[r]:
+ *   window[s][:] = append(window[s][block:], block_in[r]) in place, as ddsp_stream_push does it and as exact: launch 1 writes
+ *   the pushed window to cwindow[r] (W, n_in), outside the windows, launch 2 (stream order) copies it back to window[s], so no
+ *   launch reads what it writes;  csola[r] = sola_buffer[s] (xfade);  cmix_ids[r] / cmix_w[r] = mix_ids[s] / mix_w[s] (K, the
+ *   speaker mix of ddsp_unit2ctrl_fwd_rowmix, 1 <= K <= 16);  cpitch[r] = pitch[s];  crequest[r] = request[s] (the enhancer's
+ *   key request; both NULL for a bank without one).
+ * A padding row gets a zero window and buffer, speaker 1 with weight 1, pitch 1 and request 0.  block_in (W, block); window
+ * (S, n_in), sola_buffer (S, xfade) and the tables have S rows, their compact forms W.  Rows move by 16-byte vector accesses when
+ * n_in and block are multiples of 4 and the bases are 16-byte aligned, else by single words.  DDSP_ERR_ARG, and nothing written,
+ * for W > S, S > DDSP_MAX_STREAMS, block >= n_in, a null pointer, or compact rows that overlap the bank's.
+ * ddsp_bank_scatter, after the splice: sola_buffer[rows[r]] = csola[r] for every row that is no padding. */
+int ddsp_bank_gather(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, float* window, int64_t n_in,
+                     const float* block_in, int64_t block, float* cwindow, const float* sola_buffer, int xfade, float* csola,
+                     const int32_t* mix_ids, const float* mix_w, int K, int32_t* cmix_ids, float* cmix_w, const float* pitch,
+                     float* cpitch, const int32_t* request, int32_t* crequest);
+int ddsp_bank_scatter(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, const float* csola, int xfade,
+                      float* sola_buffer);
+
 /* ---- a15: volume gate ------------------------------------------------------------------------ */
 /* replaces gui.py:14-31 `phase_vocoder(a, b, fade_out, fade_in)` (the optional cross-fade of gui.py:417-423; SURVEY
  * 8(f) rank 3): a = kept tail, b = head of the new block, out, all (S, n) as for ddsp_sola; the fade windows (n) are shared.

@@ -20,7 +20,11 @@ stage, every solo renderer eagerly with its one read-back per block.  The solo l
 
     python tools/rt_bank_time.py --baseline-tree <parent checkout> [--blocks 200] [--warmup 10] [--shapes config5]
                                  [--out profiles/rt_bank_time.json]
-    python tools/rt_bank_time.py --enhancer [--out profiles/rt_bank_enhancer_time.json]"""
+    python tools/rt_bank_time.py --enhancer [--out profiles/rt_bank_enhancer_time.json]
+
+`--active A` times a bank of S slots of which A are active: the bank leg builds its banks with `active_widths=(A,)` and pushes
+(A, block) blocks with `active=` (A slots spread evenly over the S), the solo leg pushes A solo renderers; cases with S < A are
+left out, and every row carries `"active": A`."""
 import argparse
 import contextlib
 import json
@@ -41,7 +45,7 @@ SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16
                    num_mels=128, hop_size=512, n_fft=2048, win_size=2048)
 
 
-def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES)):
+def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), active=None):
     """One leg in this process: `which` = 'bank' | 'solo', the package taken from `tree`.  Prints one JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -79,17 +83,23 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES)):
         if shape not in shapes or (with_enhancer and shape != "config5"):
             continue
         for S in STREAMS:
+            if active is not None and S < active:
+                continue
+            A = S if active is None else active
+            slots = None if active is None else [(r * S) // A for r in range(A)]
             kw = dict(buffer_num=buffer_num, threshold_db=-60.0, use_graph=True, units_encoder=encoder, f0_extractor="crepe",
                       crepe_ckpt=crepe)
             if with_enhancer:
                 kw.update(enhancer=enh, enhancer_adaptive_key="auto")
             with contextlib.redirect_stdout(sys.stderr):
                 if which == "bank":
+                    if active is not None:
+                        kw.update(active_widths=(A,))
                     bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
                     block, frames = bank.block, bank.frames
-                    push = bank.push_audio
+                    push = bank.push_audio if active is None else (lambda blocks: bank.push_audio(blocks, active=slots))
                 else:
-                    solo = [realtime.StreamRenderer(model, DEVICE_SR, block_time, xfade_time, dev, spk_id=1, **kw) for _ in range(S)]
+                    solo = [realtime.StreamRenderer(model, DEVICE_SR, block_time, xfade_time, dev, spk_id=1, **kw) for _ in range(A)]
                     block, frames = solo[0].block, solo[0].frames
 
                     def push(blocks):
@@ -97,8 +107,8 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES)):
             rng = np.random.Generator(np.random.PCG64(3))
             t = np.arange(8 * block) / DEVICE_SR
             rows = [0.2 * np.sin(2 * np.pi * TONES[s % len(TONES)] * (1 + s // len(TONES)) * t) + 0.01 * rng.standard_normal(t.size)
-                    for s in range(S)]
-            pcm = torch.from_numpy(np.stack(rows).astype(np.float32)).to(dev).reshape(S, 8, block).transpose(0, 1).contiguous()
+                    for s in range(A)]
+            pcm = torch.from_numpy(np.stack(rows).astype(np.float32)).to(dev).reshape(A, 8, block).transpose(0, 1).contiguous()
             times = []
             for i in range(warmup + blocks):
                 torch.cuda.synchronize()
@@ -108,7 +118,7 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES)):
                 if i >= warmup:
                     times.append((time.perf_counter() - t0) * 1e3)
             ts = np.array(times)
-            print(json.dumps({"leg": which, "shape": shape, "streams": S, "enhancer": bool(with_enhancer), "block_ms": block_time * 1e3, "frames": frames,
+            print(json.dumps({**({} if active is None else {"active": A}), "leg": which, "shape": shape, "streams": S, "enhancer": bool(with_enhancer), "block_ms": block_time * 1e3, "frames": frames,
                               "mean_ms": float(ts.mean()), "p99_ms": float(np.percentile(ts, 99)), "blocks": len(ts),
                               "device": torch.cuda.get_device_name(0)}), flush=True)
             del push
@@ -129,11 +139,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rt_bank_time.json"))
     ap.add_argument("--enhancer", action="store_true", help="both legs with the NSF-HiFiGAN enhancer, key 'auto' (config5 only)")
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES), help="the timings to run (default: both)")
+    ap.add_argument("--active", type=int, default=None, help="time banks of S slots with this many active rows (S >= A only)")
     ap.add_argument("--leg", default=None, choices=["bank", "solo"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
-        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer, a.shapes)
+        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer, a.shapes, a.active)
     if a.enhancer and not a.baseline_tree:
         a.baseline_tree = ROOT
     if not a.baseline_tree or not os.path.isdir(os.path.join(a.baseline_tree, "ddsp-svc-official_amd")):
@@ -143,7 +154,8 @@ def main():
     for rep in range(a.repeats):
         for which in ("bank", "solo"):
             cmd = ["timeout", "-k", "10", str(a.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", which, "--tree",
-                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)] + (["--enhancer"] if a.enhancer else []) + ["--shapes", *a.shapes]
+                   trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)] + (["--enhancer"] if a.enhancer else []) + \
+                  (["--active", str(a.active)] if a.active else []) + ["--shapes", *a.shapes]
             p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
             if p.returncode != 0:   # a fault, an abort or the time limit: nothing more is started on the device
                 raise SystemExit(f"rt_bank_time: leg {which} of repeat {rep} ended with status {p.returncode}; stopping")
@@ -156,6 +168,8 @@ def main():
     cases = []
     for shape in (["config5"] if a.enhancer else a.shapes):
         for S in STREAMS:
+            if a.active is not None and S < a.active:
+                continue
             pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
             bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
             med = lambda v: sorted(v)[len(v) // 2]
@@ -163,7 +177,7 @@ def main():
                           "solo_p99_ms": pick("solo", "p99_ms"), "bank_spread_ms": max(bm) - min(bm),
                           "solo_spread_ms": max(sm) - min(sm), "bank_median_ms": med(bm), "solo_median_ms": med(sm),
                           "solo_over_bank": med(sm) / med(bm)})
-    out = {"enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
+    out = {**({} if a.active is None else {"active": a.active}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
            "what": "ms per block period for all S streams: bank = one StreamBank.push_audio; solo = S StreamRenderer.push_audio "
                    "of the baseline tree one after the other", "cases": cases, "rows": repeats}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
