@@ -6,6 +6,12 @@
 // so the active set changes by one small upload, and nothing is ever read back.
 // An entry is bounds-tested against S before it forms an address; one outside [0, S) is padding.  A slot not named in `rows`
 // is neither read nor written.
+//
+// The row movers of a bank with a model per slot (`models=`): the analysis runs once over the call's R rows, then every model
+// renders its own rows as a compact batch of W rows.  Here `rows` (W) indexes the CALL'S row batch, not slots.
+// ddsp_bank_features_gather copies the units, f0, volume, injected noise and speaker mix of the named rows to the compact
+// tensors in one launch (padding: zeros, speaker 1 with weight 1); ddsp_bank_signal_scatter writes the gated signal of every
+// real compact row into the call's (R, T) signal.
 #include "common.h"
 
 #include <algorithm>
@@ -81,10 +87,60 @@ __global__ void __launch_bounds__(256) bank_rows_back_kernel(const int32_t* __re
     row_copy<V>(row + s * n, crow + r * n, n);
 }
 
+// n floats of one row: dst = src, or zeros when src is null (a padding row); 16-byte accesses when `vec` (the entry point
+// decides per segment), single words otherwise
+__device__ __forceinline__ void seg_move(float* __restrict__ dst, const float* __restrict__ src, int64_t n, bool vec) {
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (vec) {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        for (int64_t i = first; i < n / 4; i += step) ((f32x4*)dst)[i] = src ? ((const f32x4*)src)[i] : zero;
+    } else {
+        for (int64_t i = first; i < n; i += step) dst[i] = src ? src[i] : 0.f;
+    }
+}
+
+enum { VEC_UNITS = 1, VEC_FRAMES = 2, VEC_NOISE = 4 };
+
+// The one launch of the features gather (grid (x, W)): compact row r takes what the synthesiser reads of row s = rows[r] of the
+// call's batch.  The compact tensors lie outside the batch (the entry point checks it), so nothing is read that is written.
+__global__ void __launch_bounds__(256) bank_features_gather_kernel(
+    const int32_t* __restrict__ rows, int R, int64_t n_units, int64_t Fr, int64_t T, int vec, const float* __restrict__ units,
+    const float* __restrict__ f0, const float* __restrict__ volume, const float* __restrict__ noise,
+    const int32_t* __restrict__ mix_ids, const float* __restrict__ mix_w, int K, float* __restrict__ cunits,
+    float* __restrict__ cf0, float* __restrict__ cvolume, float* __restrict__ cnoise, int32_t* __restrict__ cmix_ids,
+    float* __restrict__ cmix_w) {
+    const int r = blockIdx.y;
+    const int s = bank_slot(rows, r, R);                         // tested before any address of the batch is formed
+    const bool real = s >= 0;
+    seg_move(cunits + r * n_units, real ? units + s * n_units : nullptr, n_units, vec & VEC_UNITS);
+    seg_move(cf0 + r * Fr, real ? f0 + s * Fr : nullptr, Fr, vec & VEC_FRAMES);
+    seg_move(cvolume + r * Fr, real ? volume + s * Fr : nullptr, Fr, vec & VEC_FRAMES);
+    if (cnoise) seg_move(cnoise + r * T, real ? noise + s * T : nullptr, T, vec & VEC_NOISE);
+    if (blockIdx.x == 0 && (int)threadIdx.x < K) {
+        cmix_ids[r * K + threadIdx.x] = real ? mix_ids[s * K + threadIdx.x] : 1;
+        cmix_w[r * K + threadIdx.x] = real ? mix_w[s * K + threadIdx.x] : (threadIdx.x == 0 ? 1.f : 0.f);
+    }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // [a, a + na) and [b, b + nb) share no element
 bool apart(const float* a, int64_t na, const float* b, int64_t nb) { return a + na <= b || b + nb <= a; }
+
+// row[rows[r]] = crow[r] (n floats each) for every compact row that is no padding: the body of both scatters
+int rows_back(ddsp_ctx* ctx, hipStream_t st, const int32_t* rows, int W, int S, const float* crow, int64_t n, float* row) {
+    DDSP_ENTER_DEVICE(ctx);
+    const bool vec = n % 4 == 0 && aligned16(crow) && aligned16(row);
+    const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(n, vec ? 1024 : 256), 1024);
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    if (vec)
+        hipLaunchKernelGGL(bank_rows_back_kernel<4>, dim3(gx, W), dim3(256), 0, st, rows, S, crow, n, row);
+    else
+        hipLaunchKernelGGL(bank_rows_back_kernel<1>, dim3(gx, W), dim3(256), 0, st, rows, S, crow, n, row);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * W * (double)n);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}
 
 }  // namespace
 
@@ -126,16 +182,45 @@ extern "C" int ddsp_bank_scatter(ddsp_ctx* ctx, void* stream, const int32_t* row
     DDSP_REQUIRE(ctx, S >= 1 && S <= DDSP_MAX_STREAMS && W >= 1 && W <= S && xfade >= 1, "ddsp_bank_scatter: 1 <= W <= S <= 4096, xfade >= 1");
     DDSP_REQUIRE(ctx, apart(csola, (int64_t)W * xfade, sola_buffer, (int64_t)S * xfade),
                  "ddsp_bank_scatter: the compact buffers lie outside the bank's");
+    return rows_back(ctx, (hipStream_t)stream, rows, W, S, csola, xfade, sola_buffer);
+}
+
+extern "C" int ddsp_bank_features_gather(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int R, int64_t Fr, int64_t C,
+                                         int64_t T, const float* units, const float* f0, const float* volume, const float* noise,
+                                         const int32_t* mix_ids, const float* mix_w, int K, float* cunits, float* cf0,
+                                         float* cvolume, float* cnoise, int32_t* cmix_ids, float* cmix_w) {
+    DDSP_REQUIRE(ctx, ctx && rows && units && f0 && volume && mix_ids && mix_w && cunits && cf0 && cvolume && cmix_ids && cmix_w &&
+                          (noise == nullptr) == (cnoise == nullptr),
+                 "ddsp_bank_features_gather: null argument");
+    DDSP_REQUIRE(ctx, R >= 1 && R <= DDSP_MAX_STREAMS && W >= 1 && W <= DDSP_MAX_STREAMS, "ddsp_bank_features_gather: 1 <= W, R <= 4096");
+    DDSP_REQUIRE(ctx, Fr >= 1 && C >= 1 && T >= 1 && Fr * C < ((int64_t)1 << 31) && T < ((int64_t)1 << 31),
+                 "ddsp_bank_features_gather: 1 <= Fr * C, T < 2^31");
+    DDSP_REQUIRE(ctx, K >= 1 && K <= 16, "ddsp_bank_features_gather: 1 <= K <= 16");
+    const int64_t n_units = Fr * C;
+    DDSP_REQUIRE(ctx, apart(cunits, W * n_units, units, R * n_units) && apart(cf0, W * Fr, f0, R * Fr) &&
+                          apart(cvolume, W * Fr, volume, R * Fr) && (!noise || apart(cnoise, W * T, noise, R * T)) &&
+                          apart(cmix_w, (int64_t)W * K, mix_w, (int64_t)R * K) &&
+                          apart((const float*)cmix_ids, (int64_t)W * K, (const float*)mix_ids, (int64_t)R * K),
+                 "ddsp_bank_features_gather: the compact tensors lie outside the batch's");
     hipStream_t st = (hipStream_t)stream;
     DDSP_ENTER_DEVICE(ctx);
-    const bool vec = xfade % 4 == 0 && aligned16(csola) && aligned16(sola_buffer);
-    const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(xfade, vec ? 1024 : 256), 1024);
+    const int vec = (n_units % 4 == 0 && aligned16(units) && aligned16(cunits) ? VEC_UNITS : 0) |
+                    (Fr % 4 == 0 && aligned16(f0) && aligned16(cf0) && aligned16(volume) && aligned16(cvolume) ? VEC_FRAMES : 0) |
+                    (noise && T % 4 == 0 && aligned16(noise) && aligned16(cnoise) ? VEC_NOISE : 0);
+    const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(std::max(n_units, noise ? T : (int64_t)0), 1024), 1024);
     ddsp_prof_begin(ctx, st, PF_OTHER);
-    if (vec)
-        hipLaunchKernelGGL(bank_rows_back_kernel<4>, dim3(gx, W), dim3(256), 0, st, rows, S, csola, (int64_t)xfade, sola_buffer);
-    else
-        hipLaunchKernelGGL(bank_rows_back_kernel<1>, dim3(gx, W), dim3(256), 0, st, rows, S, csola, (int64_t)xfade, sola_buffer);
-    ddsp_prof_end(ctx, st, 0.0, 8.0 * W * (double)xfade);
+    hipLaunchKernelGGL(bank_features_gather_kernel, dim3(gx, W), dim3(256), 0, st, rows, R, n_units, Fr, T, vec, units, f0, volume,
+                       noise, mix_ids, mix_w, K, cunits, cf0, cvolume, cnoise, cmix_ids, cmix_w);
+    ddsp_prof_end(ctx, st, 0.0, 8.0 * W * (double)(n_units + 2 * Fr + (noise ? T : 0)));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_bank_signal_scatter(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int R, const float* csig, int64_t T,
+                                        float* sig) {
+    DDSP_REQUIRE(ctx, ctx && rows && csig && sig, "ddsp_bank_signal_scatter: null argument");
+    DDSP_REQUIRE(ctx, R >= 1 && R <= DDSP_MAX_STREAMS && W >= 1 && W <= DDSP_MAX_STREAMS && T >= 1 && T < ((int64_t)1 << 31),
+                 "ddsp_bank_signal_scatter: 1 <= W, R <= 4096, 1 <= T < 2^31");
+    DDSP_REQUIRE(ctx, apart(csig, W * T, sig, R * T), "ddsp_bank_signal_scatter: the compact signal lies outside the batch's");
+    return rows_back(ctx, (hipStream_t)stream, rows, W, R, csig, T, sig);
 }

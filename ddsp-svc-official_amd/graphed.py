@@ -1,12 +1,13 @@
 """HIP-graph replay of the real-time forwards for one fixed shape: the synthesiser alone (`GraphedSynth`), the whole block from
-the raw audio on (`GraphedBlock`) and the enhancer stage of a bank (`GraphedBankEnhancer`).
+the raw audio on (`GraphedBlock`), one model's rows of a bank with a model per slot (`GraphedModelRows`) and the enhancer stage
+of a bank (`GraphedBankEnhancer`).
 
 The real-time caller (`gui.py:360-430`: one 0.2 s block at a time, B = 1, 87 frames) is launch-bound: ~50 kernels of
 a few microseconds each, paced by Python + ctypes + hipLaunch on the host.  A capture records the whole call once
 (`torch.cuda.graph`: stream capture also records the kernels libddsp_amd launches on that stream) and replays it with one
 host call per block.
 
-What makes the capture safe is one protocol, `_Captured._capture`, that all three classes go through; its ORDER is the rule:
+What makes the capture safe is one protocol, `_Captured._capture`, that all these classes go through; its ORDER is the rule:
   1. the captured library calls go through a `hipddsp.Context` of their own (`hipddsp.use_context`): the captured kernels
      point into THAT context's scratch arena, tables and zero page;
   2. those are sized by eager warm-up runs of `_run()` on a side stream (after a `wait_stream` on the caller's, and waited for
@@ -42,6 +43,8 @@ decided on the device, the keyed resamplers, the ragged generator, the resamplin
 row's own tail) as a second linear graph that is replayed right after the first.  That it can be captured at all is the proof
 that nothing in the stage asks the host: a row whose pitch crosses a key boundary changes device data, not the graph.
 """
+import gc
+
 import torch
 
 import hipddsp
@@ -64,8 +67,17 @@ class _Captured:
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
-        with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
-            out = self._run()
+        # The cyclic collector stays off while the stream captures: a dead cycle that holds an older capture (a bank and its
+        # rows) would otherwise be collected whenever `_run()` allocates, and destroying a graph synchronises the device, which
+        # a capturing stream refuses - from a destructor, that ends the process.
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with hipddsp.use_context(self.ctx), torch.no_grad(), torch.cuda.graph(self.graph):
+                out = self._run()
+        finally:
+            if collecting:
+                gc.enable()
         self.ctx.freeze()
         for t, k in zip(keep, kept):
             t.copy_(k)
@@ -81,9 +93,10 @@ def _refill(static, value):
 
 
 class GraphedSynth(_Captured):
-    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None):
+    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None, capture=True):
         """`spk_mix_rows`: None / False; True (K = 4 slots per row) or a K for static mix tables of the graph's own; or the
-        caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses."""
+        caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses.
+        `capture=False` (a subclass that also runs eagerly, `GraphedModelRows`): the static tensors alone, `graph` is None."""
         rows = spk_mix_rows is not None and spk_mix_rows is not False
         if rows and spk_mix_dict is not None:
             raise ValueError("GraphedSynth: spk_mix_rows and spk_mix_dict are mutually exclusive")
@@ -95,7 +108,7 @@ class GraphedSynth(_Captured):
             if rows and not 1 <= K <= hipddsp.MAX_MIX:
                 raise ValueError(f"GraphedSynth: 1 to {hipddsp.MAX_MIX} slots per mix row, got {K}")
         p = next(model.parameters())
-        if not p.is_cuda:
+        if capture and not p.is_cuda:
             raise RuntimeError("GraphedSynth needs the model on a HIP device (no CPU fallback)")
         self.model = model.eval()
         self.device = p.device
@@ -117,7 +130,8 @@ class GraphedSynth(_Captured):
             self.mix_w = torch.zeros(B, K, device=dev) if K else None
             if K:
                 self.mix_w[:, 0] = 1.0
-        self.out = self._capture(dev, warmup)
+        self.graph = None
+        self.out = self._capture(dev, warmup) if capture else None
 
     def _run(self):
         if self.mix_ids is not None:
@@ -142,6 +156,51 @@ class GraphedSynth(_Captured):
         return self.out
 
 
+class GraphedModelRows(GraphedSynth):
+    """The compact synthesis chain of ONE model of a `realtime.StreamBank(models=...)` at one width W: `GraphedSynth`'s static
+    tensors and forward (with a mix per row) between the two row movers of csrc/bank_rows.hip.  `_run()` gathers the features
+    of this model's rows out of the call's row batch (`ddsp_bank_features_gather`), runs the model, gates the signal with the
+    gathered volume and scatters every real row into the call's signal (`ddsp_bank_signal_scatter`).
+    `batch`: the bank's staging tensors of the call's rows, {"units" (R, Fr, C), "f0" (R, Fr, 1), "volume" (R, Fr), "noise"
+    (R, Fr * block_size), "mix": (ids (R, K) int32, w (R, K))}, and `sig` (R, Fr * block_size), all the caller's and read or
+    written at their fixed addresses.  `table` (W,) int32 is this chain's device row table: entry r the row of the batch behind
+    compact row r, -1 for padding (zero units, f0 0, volume 0, speaker 1 with weight 1; computed, never scattered).  It is all
+    padding while the capture runs, so a capture writes nothing of `sig`.  A call uploads the table only when it differs from the
+    one on the device.  `replays` counts the calls.  With `capture=False` the same `_run()` runs eagerly."""
+
+    def __init__(self, model, W, Fr, batch, sig, threshold_db, warmup=3, capture=True):
+        self.batch, self.sig, self.threshold_db = batch, sig, float(threshold_db)
+        self.hop = int(model.block_size)                             # (a host int before the capture: no read-back inside it)
+        self.table = torch.full((int(W),), -1, dtype=torch.int32, device=sig.device)
+        self.named = ()                                              # the real rows of `table`, as the host knows them
+        self.replays = 0
+        super().__init__(model, W, Fr, warmup=warmup, spk_mix_rows=int(batch["mix"][0].shape[1]), capture=capture)
+
+    def _run(self):
+        ctx, b = hipddsp.context_for(self.device), self.batch       # (under capture: the captured context, `use_context`)
+        ctx.bank_features_gather_(self.table, b["units"], b["f0"], b["volume"], b["mix"], self.units, self.f0, self.volume,
+                                  (self.mix_ids, self.mix_w), b["noise"], self.noise)
+        out = super()._run()
+        ctx.volume_gate_(out[0], self.volume, self.threshold_db, self.hop)
+        ctx.bank_signal_scatter_(self.table, out[0], self.sig)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, named):
+        """`named`: the rows of the batch that this model renders, 1 to W ints in [0, R), no row twice."""
+        named = tuple(named)
+        if not 1 <= len(named) <= self.B:
+            raise ValueError(f"GraphedModelRows captured for {self.B} rows, got {len(named)}")
+        if named != self.named:
+            self.table.copy_(torch.tensor(list(named) + [-1] * (self.B - len(named)), dtype=torch.int32))
+            self.named = named
+        self.replays += 1
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._run()
+
+
 def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, samplerate, hop_size, silence_front, pitch,
                 threshold_db, block_size, speaker, noise=None, f0_dither=True, seed_dev=None, push=None):
     """One block of the reference's callback from the raw audio to the gated model output (gui.py:373-374 and
@@ -155,6 +214,8 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     `push(ctx, window, block_in)`: the step that brings `window` up to date, `ctx.stream_push_` unless given.  The compact rows of
     a bank's active set (`realtime.StreamBank`, `active=`) are the S-stream form with `Context.bank_gather_` as this step: it pushes
     the blocks into the named slots' own windows and fills `window`, `pitch` and the mix tables (the compact ones) from them.
+    `model=None` stops after the features: the signal is None, and the synthesis and the gate are the caller's (a bank with a
+    model per slot renders every model's rows on their own, `GraphedModelRows`); `speaker`, `noise` and `block_size` are unused.
     -> (signal (rows, Fr * block_size), f0 (rows, Fr, 1) after the shift, units (rows, Fr, C), volume (rows, Fr)), rows = 1 or S."""
     if push is None:
         ctx.stream_push_(window, block_in)
@@ -169,6 +230,8 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     elif pitch != 1:
         f0 = f0 * pitch
     units = units_encoder.encode(audio, samplerate, hop_size)
+    if model is None:
+        return None, f0, units, volume
     kw = {} if noise is None else {"noise": noise}
     sig = model(units, f0, volume, **speaker, **kw)[0]
     ctx.volume_gate_(sig, volume, threshold_db, block_size)          # (`block_size`: the model's, as a host int - no read-back)
@@ -182,32 +245,32 @@ class GraphedBlock(_Captured):
     caller's too (`realtime.StreamBank`'s state): the graph reads them at their fixed addresses, so a write to a row between two
     replays is all a speaker, mix or pitch change takes.  Without it the speaker is the static input `spk_id` and the captured
     `spk_mix_dict`, and `pitch` a host factor.  `push`: `block_chain`'s; what it changes besides `window` it must leave alone
-    while the capture runs (the bank's row table is all padding then).  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
+    while the capture runs (the bank's row table is all padding then).  `model=None`: the features alone (`block_chain`), `sig` is None and there is no `noise`.  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
     next replay): `sig`, `f0`, `units`, `volume`."""
 
     def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch,
                  threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None):
         if mix_rows is not None and spk_mix_dict is not None:
             raise ValueError("GraphedBlock: mix_rows and spk_mix_dict are mutually exclusive")
-        p = next(model.parameters())
+        dev = window.device if model is None else next(model.parameters()).device
         state = [window, *(mix_rows or ())] + ([pitch] if isinstance(pitch, torch.Tensor) else [])
-        if not p.is_cuda or any(t.device != p.device for t in state):
+        if dev.type != "cuda" or any(t.device != dev for t in state):
             raise RuntimeError("GraphedBlock needs the model and the caller's tensors on one HIP device (no CPU fallback)")
-        self.model = model.eval()
-        self.device = dev = p.device
+        self.model = None if model is None else model.eval()
+        self.device = dev
         self.units_encoder, self.f0_extractor, self.window, self.pitch = units_encoder, f0_extractor, window, pitch
         self.args = (samplerate, hop_size, silence_front, float(threshold_db))
         self.f0_dither, self.push = bool(f0_dither), push
         rows = window.shape[:-1]                                     # () or (S,)
         frames = int(window.shape[-1] // hop_size) + 1
-        self.block_size = int(model.block_size)
+        self.block_size = None if model is None else int(model.block_size)
         self.block_in = torch.zeros(*rows, int(block), device=dev)
         self.spk_id = torch.ones(1, 1, dtype=torch.int64, device=dev) if mix_rows is None else None
         if mix_rows is None:
             self.speaker = {"spk_id": self.spk_id, "spk_mix_dict": None if spk_mix_dict is None else dict(spk_mix_dict)}
         else:
             self.speaker = {"spk_id": None, "spk_mix_rows": tuple(mix_rows)}
-        self.noise = torch.rand(*(rows or (1,)), frames * self.block_size, device=dev)
+        self.noise = None if model is None else torch.rand(*(rows or (1,)), frames * self.block_size, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.sig, self.f0, self.units, self.volume = self._capture(dev, warmup, keep=[window])
         self.seed.random_(0, 2 ** 62)
@@ -225,7 +288,8 @@ class GraphedBlock(_Captured):
         self.block_in.copy_(block_in.reshape(self.block_in.shape))
         if self.spk_id is not None:
             self.spk_id.copy_(spk_id.reshape(self.spk_id.shape))
-        _refill(self.noise, noise)
+        if self.noise is not None:
+            _refill(self.noise, noise)
         self.graph.replay()
         return self.sig, self.f0, self.units, self.volume
 

@@ -235,6 +235,9 @@ SIGNATURES = {
     "ddsp_bank_gather": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp,
                                 _vp, _vp, _vp]),
     "ddsp_bank_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp]),
+    "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
+                                         _vp, _vp, _vp, _vp]),
+    "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
     "ddsp_f0_postfilter": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _i64, _i64, _vp, _f32, _int, _f32, _vp]),
     "ddsp_f0_ac_frames": (_i64, [_i64, _int, _f64, _f64]),
     "ddsp_f0_ac": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _f64, _f64, _f64, _i64, _i64, _int, _vp, _vp]),
@@ -1460,6 +1463,41 @@ class Context:
             raise ValueError("bank_scatter_: the buffers must be fp32")
         self.call("ddsp_bank_scatter", _ptr(rows), W, sola_buffer.shape[0], _ptr(csola), xfade, _ptr(sola_buffer))
         return sola_buffer
+
+    def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
+        """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row
+        of the batch behind compact row r, -1 (or anything outside [0, R)) for padding.  In place: cunits (W, Fr, C), cf0 (W, Fr, 1)
+        or (W, Fr), cvolume (W, Fr), cmix = (ids (W, K) int32, w (W, K)) and cnoise (W, T) take the named rows of units (R, Fr, C),
+        f0, volume, mix and noise (R, T) (noise and cnoise both None: no injected noise).  A padding row gets zeros and speaker 1
+        with weight 1.  -> cunits."""
+        W, (R, Fr, C) = rows.numel(), units.shape
+        K = check_mix_rows(mix[0], mix[1], R)
+        floats = [units, f0, volume, cunits, cf0, cvolume] + ([] if noise is None else [noise, cnoise])
+        if (noise is None) != (cnoise is None) or rows.dtype != torch.int32 or rows.dim() != 1 or check_mix_rows(*cmix, W) != K or \
+                any(t.dtype != torch.float32 or not t.is_contiguous() for t in floats):
+            raise ValueError("bank_features_gather_: contiguous fp32 tensors, a (W,) int32 row table and mix tables of one K")
+        sizes = ((cunits, W, Fr * C), (f0, R, Fr), (cf0, W, Fr), (volume, R, Fr), (cvolume, W, Fr))   # (f0 may carry a last 1)
+        if any(t.shape[0] != n or t.numel() != n * m for t, n, m in sizes):
+            raise ValueError("bank_features_gather_: R rows of the batch (units (R, Fr, C), f0, volume (R, Fr)) and W compact rows")
+        T = 1
+        if noise is not None:
+            T = noise.shape[-1]
+            if tuple(noise.shape) != (R, T) or tuple(cnoise.shape) != (W, T):
+                raise ValueError("bank_features_gather_: noise (R, T) and cnoise (W, T)")
+        self.call("ddsp_bank_features_gather", _ptr(rows), W, R, Fr, C, T, _ptr(units), _ptr(f0), _ptr(volume), _ptr(noise),
+                  _ptr(mix[0]), _ptr(mix[1]), K, _ptr(cunits), _ptr(cf0), _ptr(cvolume), _ptr(cnoise), _ptr(cmix[0]), _ptr(cmix[1]))
+        return cunits
+
+    def bank_signal_scatter_(self, rows, csig, sig):
+        """The gated signal of one model's compact rows into the call's signal (`ddsp_bank_signal_scatter`): sig (R, T)[rows[r]] =
+        csig (W, T)[r] for every row of rows (W,) int32 that is no padding; the other rows of sig stay.  -> sig."""
+        W, T = csig.shape
+        if rows.dtype != torch.int32 or tuple(rows.shape) != (W,) or sig.dim() != 2 or sig.shape[1] != T:
+            raise ValueError("bank_signal_scatter_: csig (W, T), sig (R, T) and a (W,) int32 row table")
+        if csig.dtype != torch.float32 or sig.dtype != torch.float32 or not (csig.is_contiguous() and sig.is_contiguous()):
+            raise ValueError("bank_signal_scatter_: the signals must be contiguous fp32")
+        self.call("ddsp_bank_signal_scatter", _ptr(rows), W, sig.shape[0], _ptr(csig), T, _ptr(sig))
+        return sig
 
     def phase_vocoder(self, a, b, fade_out, fade_in):
         """gui.py:14-31: cross-fade of the kept tail `a` into the new head `b` (both (n,)) with a phase-interpolated

@@ -353,13 +353,50 @@ def active_width(A, widths):
     raise ValueError(f"active_width: {A} active slots, the widest batch of the ladder {tuple(widths)} holds {max(widths, default=0)}")
 
 
-def _check_active_widths(active_widths, S):
-    """`StreamBank(active_widths=)` -> the ladder: the sorted distinct ints in 1..S as given, with S behind them if missing."""
+def _check_active_widths(active_widths, S, name="active_widths"):
+    """`StreamBank(active_widths=)` (or `model_widths=`, as `name`) -> the ladder: the sorted distinct ints in 1..S as given, with S
+    behind them if missing."""
     widths = tuple(active_widths) if isinstance(active_widths, (tuple, list)) else None
     if widths is None or any(isinstance(w, bool) or not isinstance(w, int) or not 1 <= w <= S for w in widths) or \
             any(a >= b for a, b in zip(widths, widths[1:])):
-        raise ValueError(f"StreamBank: active_widths must be a sorted tuple of distinct ints in 1..{S}, got {active_widths!r}")
+        raise ValueError(f"StreamBank: {name} must be a sorted tuple of distinct ints in 1..{S}, got {active_widths!r}")
     return widths if widths and widths[-1] == S else widths + (S,)
+
+
+def default_model_widths(S):
+    """The ladder of `StreamBank(models=...)` when `model_widths` is not given: the powers of two up to S, and S."""
+    return tuple(w for w in (1 << i for i in range(int(S).bit_length())) if w < S) + (int(S),)
+
+
+MODEL_FIELDS = ("sampling_rate", "block_size", "n_unit", "device")
+
+
+def _model_field(model, field):
+    if field == "n_unit":
+        return int(model.unit2ctrl.n_unit)
+    if field == "device":
+        return next(model.parameters()).device
+    host = getattr(model, {"sampling_rate": "_sr", "block_size": "_hop"}[field], None)   # (the synthesisers' host copies:
+    return int(getattr(model, field) if host is None else host)                          # the buffers would be read back)
+
+
+def _check_models(model, models):
+    """`StreamBank(model, ..., models=)` -> the list of models: host comparisons only.  The models of a bank share the analysis, the
+    enhancer stage and the splice, so they agree in `MODEL_FIELDS`; class, weights, `n_spk` and `c` are each model's own."""
+    if models is None:
+        return [model]
+    models = list(models) if isinstance(models, (tuple, list)) else []
+    if not models:
+        raise ValueError("StreamBank: models must be a non-empty list of synthesisers")
+    if model is not None and model is not models[0]:
+        raise ValueError("StreamBank: with models= the positional model is None or models[0] itself (it names model 0)")
+    for k, m in enumerate(models[1:], 1):
+        for field in MODEL_FIELDS:
+            a, b = _model_field(models[0], field), _model_field(m, field)
+            if a != b:
+                raise ValueError(f"StreamBank: models[{k}].{field} is {b}, models[0].{field} is {a}: the models of a bank agree in "
+                                 f"{', '.join(MODEL_FIELDS)}")
+    return models
 
 
 class _Rows:
@@ -466,22 +503,51 @@ class StreamBank:
     `active_widths` too: there an idle slot is a slot that is fed zeros; its rows are computed like every other row, and its
     output is zero through the volume gate.  Every refusal of a call (`active` on a bank without `active_widths`, an empty,
     unsorted or repeated `active`, a slot outside [0, S), a bool or non-int slot, per-row arguments that do not have A rows) is a
-    ValueError raised before anything is uploaded or launched.  Not in the bank: streams of different geometry (DESIGN
-    section 7)."""
+    ValueError raised before anything is uploaded or launched.
+
+    A model per slot (`models=[m0, m1, ...]`; without it nothing of this is allocated or captured, and `StreamBank(model)` is the
+    bank above, bit for bit).  The positional `model` is then None or `models[0]` itself: it names model 0, anything else is
+    refused.  The models may differ in class (CombSub, Sins, CombSubFast), weights, `n_spk` and `c`; they agree in
+    `sampling_rate`, `block_size` and unit width and sit on one device (ValueError naming the model and the field, before any
+    device call).  `set_model(slot, k, spk_id=1, spk_mix_dict=None)` gives a slot its model (`model_of_slot`, host state) and a
+    speaker valid for it; `set_speaker` checks ids against the slot's own model's `n_spk`; `reset` keeps the model.  Per call the
+    window push and the analysis (volume, f0, units) run ONCE over the call's rows - the full width, or the compact width of
+    `active=` - as the same chain stopped after the features (`graphed.block_chain(model=None)`).  Then every model that owns a
+    row of the call renders its rows as a compact batch (`graphed.GraphedModelRows`, one per model and width of `model_widths`:
+    a sorted tuple of distinct ints in 1..S, S appended if missing; default the powers of two up to S, and S):
+    `ddsp_bank_features_gather` by a device row table over the call's rows, the model's forward with mix rows, the gate, and
+    `ddsp_bank_signal_scatter` into the call's (rows, T) signal; the smallest width that holds the model's rows is replayed, a
+    model without rows is not.  Padding rows of such a batch compute on zero units, f0 0, volume 0 and speaker 1, and are never
+    scattered.  Enhancer stage (one generator for all models), resampling and splice follow over all rows as above.  Every chain
+    is captured at construction: `graph_builds` is the count above plus len(models) * len(model_widths), and a change of
+    assignment captures nothing.  The paused-slot rule holds as it stands.
+
+    Not in the bank: streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
+    grows after construction; a weight set per row inside the control network's kernels; an enhancer per model (DESIGN section
+    7)."""
 
     def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
-                 active_widths=None):
+                 active_widths=None, models=None, model_widths=None):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
             raise ValueError(f"StreamBank: n_streams must be at least 1, got {n_streams}")
         self.active_widths = None if active_widths is None else _check_active_widths(active_widths, self.S)
+        if models is None and model_widths is not None:
+            raise ValueError("StreamBank: model_widths= needs models=")
+        self.model_widths = None
+        if models is not None:
+            self.model_widths = default_model_widths(self.S) if model_widths is None else \
+                _check_active_widths(model_widths, self.S, "model_widths")
+        self.models = [m.eval() for m in _check_models(model, models)]
+        self.model_of_slot = [0] * self.S                            # host state: the model of every slot (`set_model`)
+        model = self.models[0]
         self.max_mix = int(max_mix)
         if not 1 <= self.max_mix <= hipddsp.MAX_MIX:
             raise ValueError(f"StreamBank: max_mix must be in 1..{hipddsp.MAX_MIX}, got {max_mix}")
-        self.model = model.eval()
+        self.model = model
         self.device = torch.device(device)
         self.block_size = int(model.block_size)
         self.model_sr = int(model.sampling_rate)
@@ -534,6 +600,17 @@ class StreamBank:
         self.last_active = None          # the slots of the last call that named them (`active=`)
         self._full = _Rows(self, self.S, compact=False)
         self._compact = {W: _Rows(self, W, compact=True) for W in self.active_widths or ()}
+        self._batch = self._sig = self._model_rows = None            # a bank with `models=`: see `_render_models`
+        if self.model_widths is not None:
+            import graphed
+            T, n_unit = self.frames * self.block_size, int(model.unit2ctrl.n_unit)
+            self._batch = {"units": torch.zeros(self.S, self.frames, n_unit, device=dev), "f0": torch.zeros(self.S, self.frames, 1, device=dev),
+                           "volume": torch.zeros(self.S, self.frames, device=dev), "noise": torch.zeros(self.S, T, device=dev),
+                           "mix": (torch.ones(self.S, self.max_mix, dtype=torch.int32, device=dev), torch.zeros(self.S, self.max_mix, device=dev))}
+            self._sig = torch.zeros(self.S, T, device=dev)
+            self._model_rows = [{W: graphed.GraphedModelRows(m, W, self.frames, self._batch, self._sig, self.threshold_db,
+                                                             capture=self.use_graph) for W in self.model_widths} for m in self.models]
+            self.graph_builds += len(self.models) * len(self.model_widths) * int(self.use_graph)
         if self.use_graph:
             self._capture(self._full)
             self.graph, self.bank_graph, self.enhancer_graph = self._full.graph, self._full.bank_graph, self._full.enhancer_graph
@@ -544,12 +621,13 @@ class StreamBank:
         """The chain at the width of `rows` as its graphs: the block (or the synthesis alone) and the enhancer stage together
         count as one build."""
         import graphed
+        shared = self.model_widths is None                           # (with `models=` the synthesis is `_render_models`'s)
         if self.f0_extractor is not None:
             rows.bank_graph = graphed.GraphedBlock(
-                self.model, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
+                self.model if shared else None, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
                 self.silence_front, rows.pitch, self.threshold_db, mix_rows=(rows.spk_ids, rows.spk_w),
                 f0_dither=self.f0_dither, push=rows.push)
-        else:
+        elif shared:
             rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=(rows.spk_ids, rows.spk_w))
         if self.enhancer is not None:
             rows.enhancer_graph = graphed.GraphedBankEnhancer(
@@ -593,17 +671,36 @@ class StreamBank:
         slot = self._slot(slot)
         if (spk_id is None) == (spk_mix_dict is None):
             raise ValueError("StreamBank.set_speaker: pass spk_id or spk_mix_dict (one of them)")
+        self._write_mix(slot, *self._mix_tables(self.model_of_slot[slot], spk_id, spk_mix_dict))
+
+    def _mix_tables(self, k, spk_id, spk_mix_dict):
+        """The mix row of a slot on model `k` as CPU tables (ids (1, K), w (1, K)); ids are checked against THAT model's `n_spk`."""
+        n_spk = int(self.models[k].unit2ctrl.n_spk)
         if spk_mix_dict is not None:
-            mix = {int(k): float(v) for k, v in spk_mix_dict.items()}
+            mix = {int(i): float(v) for i, v in spk_mix_dict.items()}
             if not 1 <= len(mix) <= self.max_mix:
                 raise ValueError(f"StreamBank: a speaker mix holds 1 to max_mix = {self.max_mix} ids, got {len(mix)}")
         else:
             mix = {int(spk_id): 1.0}
-        if any(not 1 <= k <= self.n_spk for k in mix):
-            raise ValueError(f"StreamBank: speaker ids must be in [1, {self.n_spk}], got {sorted(mix)}")
-        ids, w = hipddsp.mix_rows([mix], self.max_mix, self.n_spk)
+        if any(not 1 <= i <= n_spk for i in mix):
+            raise ValueError(f"StreamBank: speaker ids must be in [1, {n_spk}], got {sorted(mix)}")
+        return hipddsp.mix_rows([mix], self.max_mix, n_spk)
+
+    def _write_mix(self, slot, ids, w):
         self.spk_ids[slot].copy_(ids[0])
         self.spk_w[slot].copy_(w[0])
+
+    def set_model(self, slot, k, spk_id=1, spk_mix_dict=None):
+        """Slot `slot` is rendered by `models[k]` from the next block on, as speaker `spk_id` of that model or as `spk_mix_dict`
+        (which then replaces `spk_id`): ids are checked against that model's `n_spk`, and the slot's old speaker does not carry
+        over (it may not exist there).  Host state (`model_of_slot`) and one write to the slot's mix rows; nothing is captured.
+        Window, SOLA buffer, pitch and key request stay, as does the model under `reset(slot)`."""
+        slot = self._slot(slot)
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < len(self.models):
+            raise ValueError(f"StreamBank.set_model: k must be an int in [0, {len(self.models)}), got {k!r}")
+        tables = self._mix_tables(k, spk_id, spk_mix_dict)
+        self.model_of_slot[slot] = k
+        self._write_mix(slot, *tables)
 
     def set_pitch(self, slot, semitones):
         """Slot `slot` is shifted by `semitones` from the next block on (f0 * 2 ** (semitones / 12)): one device write."""
@@ -620,7 +717,7 @@ class StreamBank:
         self.enhancer_request[slot:slot + 1].fill_(request)
 
     def reset(self, slot):
-        """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (speaker and pitch stay as set)."""
+        """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set)."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
@@ -643,6 +740,26 @@ class StreamBank:
                 rand_ini.to(self.device), self.model_sr, self.block_size, self.samplerate, self._n_end_by_key, self._tail_idx)
         self.last_key, = rows.real(key)
         return tail
+
+    def _render_models(self, rows, slots, units, f0, volume, noise):
+        """Step 4-5 of a bank with `models=`: the features of the call's rows (W, ...) go to the bank's staging tensors, then
+        every model that owns a row of the call renders its rows: one replay of its compact chain (`graphed.GraphedModelRows`:
+        gather by a device row table, forward with mix rows, gate, scatter) at the smallest width of `model_widths` that holds
+        them.  A model without rows in the call is not replayed.  -> the gated signal (W, Fr * block_size) of the call.  Padding
+        rows of the call belong to no model: their rows of the signal are whatever an earlier call left there."""
+        import graphed
+        b, W = self._batch, rows.W
+        for name, t in (("units", units), ("f0", f0), ("volume", volume)):
+            b[name][:W].copy_(t.reshape(b[name][:W].shape))
+        graphed._refill(b["noise"][:W], noise)
+        b["mix"][0][:W].copy_(rows.spk_ids)
+        b["mix"][1][:W].copy_(rows.spk_w)
+        owned = {}
+        for r, slot in enumerate(range(self.S) if slots is None else slots):
+            owned.setdefault(self.model_of_slot[slot], []).append(r)
+        for k in sorted(owned):
+            self._model_rows[k][active_width(len(owned[k]), self.model_widths)](owned[k])
+        return self._sig[:W]
 
     def _splice(self, rows, sig, f0=None, rand_ini=None):
         """Steps 6-8 over the rows: (W, Fr * block_size) at the model's rate -> (A, block) samples to play; the spliced buffers
@@ -678,9 +795,12 @@ class StreamBank:
         else:
             import graphed
             sig, f0, units, volume = graphed.block_chain(
-                hipddsp.context_for(self.device), self.model, self.units_encoder, self.f0_extractor, rows.windows, blocks,
-                self.samplerate, self.hop_size, self.silence_front, rows.pitch, self.threshold_db, self.hop,
-                {"spk_id": None, "spk_mix_rows": (rows.spk_ids, rows.spk_w)}, noise, self.f0_dither, push=rows.push)
+                hipddsp.context_for(self.device), self.model if self._model_rows is None else None, self.units_encoder,
+                self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch,
+                self.threshold_db, self.hop, {"spk_id": None, "spk_mix_rows": (rows.spk_ids, rows.spk_w)}, noise, self.f0_dither,
+                push=rows.push)
+        if self._model_rows is not None:
+            sig = self._render_models(rows, active, units, f0, volume, noise)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
         self.last_active = active
         return self._splice(rows, sig, f0, rand_ini)
@@ -707,12 +827,15 @@ class StreamBank:
         units = rows.pad(units.to(self.device))
         f0 = rows.pad(f0.to(self.device, torch.float32)) * rows.pitch[:, None, None]
         volume = ctx.volume_extract(rows.windows, self.hop_size)
-        if rows.graph is not None:
-            sig = rows.graph(units, f0, volume, None, noise=noise)[0]
+        if self._model_rows is not None:
+            sig = self._render_models(rows, active, units, f0, volume, noise)
         else:
-            kw = {} if noise is None else {"noise": noise}
-            sig = self.model(units, f0, volume, None, spk_mix_rows=(rows.spk_ids, rows.spk_w), **kw)[0]
-        ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
+            if rows.graph is not None:
+                sig = rows.graph(units, f0, volume, None, noise=noise)[0]
+            else:
+                kw = {} if noise is None else {"noise": noise}
+                sig = self.model(units, f0, volume, None, spk_mix_rows=(rows.spk_ids, rows.spk_w), **kw)[0]
+            ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
         self.last_active = active
         return self._splice(rows, sig, f0, rand_ini)

@@ -432,6 +432,28 @@ int ddsp_bank_gather(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, in
 int ddsp_bank_scatter(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, const float* csola, int xfade,
                       float* sola_buffer);
 
+/* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
+ * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
+ * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)
+ * before it forms an address; -1 or any other entry outside is a padding row: never a fault, and the error word stays clear.
+ * ddsp_bank_features_gather, one launch: for every compact row r with s = rows[r], cunits[r] = units[s] (Fr * C), cf0[r] =
+ *   f0[s] (Fr), cvolume[r] = volume[s] (Fr), cnoise[r] = noise[s] (T, the injected excitation; both NULL: none), cmix_ids[r] /
+ *   cmix_w[r] = mix_ids[s] / mix_w[s] (K, 1 <= K <= 16).  A padding row gets zero units, f0 0, volume 0, noise 0 and speaker 1
+ *   with weight 1.  The batch's tensors have R rows, the compact ones W, and the compact ones lie outside the batch's, so the
+ *   launch reads nothing that it writes.  Each segment moves by 16-byte vector accesses when its row length is a multiple of 4
+ *   floats and its two bases are 16-byte aligned (Fr * C with C % 4 == 0 and T usually are, Fr alone often is not), else by
+ *   single words.
+ * ddsp_bank_signal_scatter: sig[rows[r]] = csig[r] (T) for every compact row that is no padding; csig (W, T), sig (R, T).  No
+ *   row of the batch may be named twice (every row belongs to one model; the caller sees to it).  A row that `rows` does not
+ *   name is not written.
+ * DDSP_ERR_ARG, and nothing written, for W or R outside [1, DDSP_MAX_STREAMS], a null pointer, or overlapping tensors. */
+int ddsp_bank_features_gather(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int R, int64_t Fr, int64_t C, int64_t T,
+                              const float* units, const float* f0, const float* volume, const float* noise,
+                              const int32_t* mix_ids, const float* mix_w, int K, float* cunits, float* cf0, float* cvolume,
+                              float* cnoise, int32_t* cmix_ids, float* cmix_w);
+int ddsp_bank_signal_scatter(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int R, const float* csig, int64_t T,
+                             float* sig);
+
 /* ---- a15: volume gate ------------------------------------------------------------------------ */
 /* replaces gui.py:14-31 `phase_vocoder(a, b, fade_out, fade_in)` (the optional cross-fade of gui.py:417-423; SURVEY
  * 8(f) rank 3): a = kept tail, b = head of the new block, out, all (S, n) as for ddsp_sola; the fade windows (n) are shared.

@@ -24,7 +24,17 @@ stage, every solo renderer eagerly with its one read-back per block.  The solo l
 
 `--active A` times a bank of S slots of which A are active: the bank leg builds its banks with `active_widths=(A,)` and pushes
 (A, block) blocks with `active=` (A slots spread evenly over the S), the solo leg pushes A solo renderers; cases with S < A are
-left out, and every row carries `"active": A`."""
+left out, and every row carries `"active": A`.
+
+`--models M` times a bank whose S slots are dealt round-robin over M distinct models (CombSub, seeds 1..M): the bank leg builds
+`StreamBank(models=...)` with the default `model_widths` and gives slot s model s % M, the solo leg pushes S solo renderers of
+the baseline tree, renderer s over model s % M - the only way the parent commit serves M models.  With M = 1 a third leg,
+`plain`, times the ordinary single-model bank of this tree beside the one-model bank that goes through the per-model path.
+Cases with S < M are left out; `--streams` picks the S to run; every row carries `"models": M`.  Combines with `--enhancer` and
+`--active`.
+
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> --models 4 --streams 16 --shapes config5
+                                 [--out profiles/rt_bank_models_time.json]"""
 import argparse
 import contextlib
 import json
@@ -45,8 +55,8 @@ SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16
                    num_mels=128, hop_size=512, n_fft=2048, win_size=2048)
 
 
-def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), active=None):
-    """One leg in this process: `which` = 'bank' | 'solo', the package taken from `tree`.  Prints one JSON row per case."""
+def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), active=None, models=None, streams=STREAMS):
+    """One leg in this process: `which` = 'bank' | 'solo' | 'plain', the package taken from `tree`.  Prints one JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import numpy as np
@@ -63,7 +73,8 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
         raise SystemExit("rt_bank_time needs a HIP device")
     dev = torch.device("cuda:0")
     with contextlib.redirect_stdout(sys.stderr), tempfile.TemporaryDirectory() as tmp:
-        model, _ = synthetic.build_model("CombSub", seed=1, device=dev)
+        pool = [synthetic.build_model("CombSub", seed=1 + k, device=dev)[0] for k in range(models or 1)]
+        model = pool[0]
         crepe = Crepe("full")
         crepe.load_state_dict(CC.fill("full"))
         crepe = crepe.to(dev).eval()
@@ -82,8 +93,8 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
     for shape, (block_time, xfade_time, buffer_num) in SHAPES.items():
         if shape not in shapes or (with_enhancer and shape != "config5"):
             continue
-        for S in STREAMS:
-            if active is not None and S < active:
+        for S in streams:
+            if (active is not None and S < active) or (models is not None and S < models):
                 continue
             A = S if active is None else active
             slots = None if active is None else [(r * S) // A for r in range(A)]
@@ -92,14 +103,20 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
             if with_enhancer:
                 kw.update(enhancer=enh, enhancer_adaptive_key="auto")
             with contextlib.redirect_stdout(sys.stderr):
-                if which == "bank":
+                if which in ("bank", "plain"):
                     if active is not None:
                         kw.update(active_widths=(A,))
+                    if models is not None and which == "bank":
+                        kw.update(models=pool)
                     bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
+                    for s in range(S if "models" in kw else 0):
+                        bank.set_model(s, s % len(pool))
                     block, frames = bank.block, bank.frames
                     push = bank.push_audio if active is None else (lambda blocks: bank.push_audio(blocks, active=slots))
                 else:
-                    solo = [realtime.StreamRenderer(model, DEVICE_SR, block_time, xfade_time, dev, spk_id=1, **kw) for _ in range(A)]
+                    owners = range(S) if slots is None else slots
+                    solo = [realtime.StreamRenderer(pool[s % len(pool)], DEVICE_SR, block_time, xfade_time, dev, spk_id=1, **kw)
+                            for s in owners]
                     block, frames = solo[0].block, solo[0].frames
 
                     def push(blocks):
@@ -118,11 +135,11 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
                 if i >= warmup:
                     times.append((time.perf_counter() - t0) * 1e3)
             ts = np.array(times)
-            print(json.dumps({**({} if active is None else {"active": A}), "leg": which, "shape": shape, "streams": S, "enhancer": bool(with_enhancer), "block_ms": block_time * 1e3, "frames": frames,
+            print(json.dumps({**({} if active is None else {"active": A}), **({} if models is None else {"models": models}), "leg": which, "shape": shape, "streams": S, "enhancer": bool(with_enhancer), "block_ms": block_time * 1e3, "frames": frames,
                               "mean_ms": float(ts.mean()), "p99_ms": float(np.percentile(ts, 99)), "blocks": len(ts),
                               "device": torch.cuda.get_device_name(0)}), flush=True)
             del push
-            if which == "bank":
+            if which != "solo":
                 del bank
             else:
                 del solo
@@ -140,22 +157,26 @@ def main():
     ap.add_argument("--enhancer", action="store_true", help="both legs with the NSF-HiFiGAN enhancer, key 'auto' (config5 only)")
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES), help="the timings to run (default: both)")
     ap.add_argument("--active", type=int, default=None, help="time banks of S slots with this many active rows (S >= A only)")
-    ap.add_argument("--leg", default=None, choices=["bank", "solo"], help=argparse.SUPPRESS)
+    ap.add_argument("--models", type=int, default=None, help="deal the S slots round-robin over this many distinct models (S >= M only)")
+    ap.add_argument("--streams", type=int, nargs="+", default=list(STREAMS), help="the stream counts S to run")
+    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
-        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer, a.shapes, a.active)
+        return leg(a.leg, a.tree, a.blocks, a.warmup, a.enhancer, a.shapes, a.active, a.models, a.streams)
     if a.enhancer and not a.baseline_tree:
         a.baseline_tree = ROOT
     if not a.baseline_tree or not os.path.isdir(os.path.join(a.baseline_tree, "ddsp-svc-official_amd")):
         raise SystemExit("rt_bank_time: --baseline-tree must be a checkout of the parent commit (with ddsp-svc-official_amd/)")
-    trees = {"bank": ROOT, "solo": os.path.abspath(a.baseline_tree)}
+    trees = {"bank": ROOT, "plain": ROOT, "solo": os.path.abspath(a.baseline_tree)}
+    legs = ("bank", "solo", "plain") if a.models == 1 else ("bank", "solo")
     repeats = []
     for rep in range(a.repeats):
-        for which in ("bank", "solo"):
+        for which in legs:
             cmd = ["timeout", "-k", "10", str(a.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", which, "--tree",
                    trees[which], "--blocks", str(a.blocks), "--warmup", str(a.warmup)] + (["--enhancer"] if a.enhancer else []) + \
-                  (["--active", str(a.active)] if a.active else []) + ["--shapes", *a.shapes]
+                  (["--active", str(a.active)] if a.active else []) + (["--models", str(a.models)] if a.models else []) + \
+                  ["--streams", *map(str, a.streams)] + ["--shapes", *a.shapes]
             p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
             if p.returncode != 0:   # a fault, an abort or the time limit: nothing more is started on the device
                 raise SystemExit(f"rt_bank_time: leg {which} of repeat {rep} ended with status {p.returncode}; stopping")
@@ -167,8 +188,8 @@ def main():
     # per case: every repeat's mean, the spread of each leg between its repeats, the S-fold solo time against the bank
     cases = []
     for shape in (["config5"] if a.enhancer else a.shapes):
-        for S in STREAMS:
-            if a.active is not None and S < a.active:
+        for S in a.streams:
+            if (a.active is not None and S < a.active) or (a.models is not None and S < a.models):
                 continue
             pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
             bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
@@ -177,7 +198,10 @@ def main():
                           "solo_p99_ms": pick("solo", "p99_ms"), "bank_spread_ms": max(bm) - min(bm),
                           "solo_spread_ms": max(sm) - min(sm), "bank_median_ms": med(bm), "solo_median_ms": med(sm),
                           "solo_over_bank": med(sm) / med(bm)})
-    out = {**({} if a.active is None else {"active": a.active}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
+            if "plain" in legs:   # the single-model bank of this tree beside the one-model bank through the per-model path
+                pm = pick("plain", "mean_ms")
+                cases[-1].update(plain_mean_ms=pm, plain_median_ms=med(pm), plain_spread_ms=max(pm) - min(pm))
+    out = {**({} if a.active is None else {"active": a.active}), **({} if a.models is None else {"models": a.models}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
            "what": "ms per block period for all S streams: bank = one StreamBank.push_audio; solo = S StreamRenderer.push_audio "
                    "of the baseline tree one after the other", "cases": cases, "rows": repeats}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
