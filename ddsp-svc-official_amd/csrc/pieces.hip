@@ -11,6 +11,11 @@
 // element goes through a bounds SELECT (as in stitch_kernel), so no address outside a file's own row is formed.  A row whose
 // range leaves its file, or whose counts exceed the output widths, is written as zeros and sets the context's error word.
 // HBM-bound: 4 B read and 4 B written per element.
+//
+// ddsp_pieces_gather_jobs is the same launch over rows of SIX columns: the sixth names the row's JOB - one conversion of the
+// file to one voice and key.  The file still names the source of audio, f0 and volume, so J jobs over one file read that file's
+// features in place; the job names the key factor, key_factor (J).  A job outside [0, J) is a bad row like a file outside [0, F):
+// it is tested before key_factor is indexed.
 #include "common.h"
 
 namespace {
@@ -22,8 +27,9 @@ struct PiecesArgs {
     const float* key_factor;       // (F)
     const int32_t* n_file_samples; // (F)
     const int32_t* n_file_frames;  // (F)
-    const int32_t* table;          // (R, 5)
+    const int32_t* table;          // (R, cols)
     int64_t F, T_max, Fr_max, S_max, N_max;
+    int64_t cols, J;               // cols 5: key_factor (F) by file; cols 6: key_factor (J) by the row's sixth column
     float* wav;                    // (R, S_max)
     float* f0_rows;                // (R, N_max)
     float* vol_rows;               // (R, N_max)
@@ -59,10 +65,11 @@ __device__ __forceinline__ void copy4(const float* __restrict__ src, int64_t n_c
 
 __global__ void __launch_bounds__(256) pieces_gather_kernel(PiecesArgs a) {
     const int64_t r = blockIdx.y;
-    const int32_t* __restrict__ row = a.table + 5 * r;
+    const int32_t* __restrict__ row = a.table + a.cols * r;
     const int64_t file = row[0], sf = row[1], ss = row[3];
+    const int64_t key_of = a.cols == 6 ? row[5] : file;   // whose key factor the row takes: its job's, or its file's
     int64_t nf = row[2], ns = row[4];
-    bool ok = file >= 0 && file < a.F;
+    bool ok = file >= 0 && file < a.F && key_of >= 0 && key_of < (a.cols == 6 ? a.J : a.F);
     if (ok) {
         // every half is held to its own columns and widths: those of a half that was not asked for mean nothing
         const int64_t file_samples = a.n_file_samples[file], file_frames = a.n_file_frames[file];
@@ -78,7 +85,7 @@ __global__ void __launch_bounds__(256) pieces_gather_kernel(PiecesArgs a) {
     }
     // sources: formed only for a checked row (counts of 0 otherwise: nothing is read through them)
     const int64_t a_off = ok ? file * a.T_max + ss : 0, f_off = ok ? file * a.Fr_max + sf : 0;
-    const float scale = (ok && a.f0) ? a.key_factor[file] : 1.0f;
+    const float scale = (ok && a.f0) ? a.key_factor[key_of] : 1.0f;
     const int64_t nW = a.audio ? (a.S_max + 3) / 4 : 0, nN = a.f0 ? (a.N_max + 3) / 4 : 0;
     const int64_t total = nW + (a.volume ? 2 : 1) * nN;   // (no volume: the f0 rows alone, as the enhancer takes them)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -90,10 +97,11 @@ __global__ void __launch_bounds__(256) pieces_gather_kernel(PiecesArgs a) {
 
 }  // namespace
 
-extern "C" int ddsp_pieces_gather(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
-                                  const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames,
-                                  int64_t F, int64_t T_max, int64_t Fr_max, const int32_t* table, int64_t R, int64_t S_max,
-                                  int64_t N_max, float* wav, float* f0_rows, float* vol_rows) {
+// the one body of both entries: `cols` 5 (key_factor by file, J unused) or 6 (key_factor (J) by job)
+static int pieces_gather(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
+                         const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F,
+                         int64_t T_max, int64_t Fr_max, int64_t cols, int64_t J, const int32_t* table, int64_t R, int64_t S_max,
+                         int64_t N_max, float* wav, float* f0_rows, float* vol_rows) {
     DDSP_REQUIRE(ctx, ctx && n_file_samples && n_file_frames && (R == 0 || table), "ddsp_pieces_gather: null argument");
     DDSP_REQUIRE(ctx, (audio != nullptr) == (wav != nullptr), "ddsp_pieces_gather: audio and wav come together or not at all");
     DDSP_REQUIRE(ctx, (f0 != nullptr) == (key_factor != nullptr) && (f0 != nullptr) == (f0_rows != nullptr),
@@ -124,6 +132,8 @@ extern "C" int ddsp_pieces_gather(ddsp_ctx* ctx, void* stream, const float* audi
     a.Fr_max = Fr_max;
     a.S_max = audio ? S_max : 0;
     a.N_max = f0 ? N_max : 0;
+    a.cols = cols;
+    a.J = J;
     a.wav = wav;
     a.f0_rows = f0_rows;
     a.vol_rows = vol_rows;
@@ -141,4 +151,21 @@ extern "C" int ddsp_pieces_gather(ddsp_ctx* ctx, void* stream, const float* audi
     ddsp_prof_end(ctx, st, 0.0, 8.0 * (double)R * ((double)a.S_max + (double)n_tracks * (double)a.N_max));
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
+}
+
+extern "C" int ddsp_pieces_gather(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
+                                  const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames,
+                                  int64_t F, int64_t T_max, int64_t Fr_max, const int32_t* table, int64_t R, int64_t S_max,
+                                  int64_t N_max, float* wav, float* f0_rows, float* vol_rows) {
+    return pieces_gather(ctx, stream, audio, f0, volume, key_factor, n_file_samples, n_file_frames, F, T_max, Fr_max, 5, 0, table,
+                         R, S_max, N_max, wav, f0_rows, vol_rows);
+}
+
+extern "C" int ddsp_pieces_gather_jobs(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
+                                       const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames,
+                                       int64_t F, int64_t T_max, int64_t Fr_max, int64_t J, const int32_t* table, int64_t R,
+                                       int64_t S_max, int64_t N_max, float* wav, float* f0_rows, float* vol_rows) {
+    DDSP_REQUIRE(ctx, ctx && J >= 1 && J < (1ll << 31), "ddsp_pieces_gather_jobs: J must be in [1, 2^31)");
+    return pieces_gather(ctx, stream, audio, f0, volume, key_factor, n_file_samples, n_file_frames, F, T_max, Fr_max, 6, J, table,
+                         R, S_max, N_max, wav, f0_rows, vol_rows);
 }

@@ -194,7 +194,9 @@ SIGNATURES = {
     "ddsp_volume_gate_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
     "ddsp_volume_gate_files": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
     "ddsp_pieces_gather": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "ddsp_pieces_gather_jobs": (_int, [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "ddsp_stitch": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
+    "ddsp_pcm16": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "ddsp_volume_extract": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp]),
     "ddsp_volume_extract_frac": (_int, [_vp, _vp, _vp, _i64, _i64, _f64, _vp]),
@@ -1561,6 +1563,8 @@ class Context:
         (F,) int32 device.  audio (F, T_max) with S_max -> wav (R, S_max); f0, volume (F, Fr_max) and key_factor (F,) with N_max
         -> f0_rows (the one rounded product f0 * key_factor[file]) and vol_rows (R, N_max; not made when `volume` is None);
         exact zeros behind every piece.
+        A table of (R, 6) rows holds the rows of JOBS (`ddsp_pieces_gather_jobs`): the sixth column is the row's job, the file
+        still names the source, and key_factor is (J,), one per job - J jobs over one file read that file's features in place.
         Returns (wav, f0_rows, vol_rows), None for the half that was not asked for.  Nothing is read back: a piece outside its
         file gives a row of zeros and raises ValueError from `poll_error()` after a synchronise or from the next call that takes
         the error word."""
@@ -1570,9 +1574,10 @@ class Context:
                 raise ValueError(f"pieces_gather: {name} must be a contiguous fp32 tensor on {self.device}"
                                  + (f" of shape {shape}" if shape else ""))
             return t
-        if table_dev.dim() != 2 or table_dev.shape[1] != 5 or table_dev.dtype != torch.int32 or not table_dev.is_cuda \
+        if table_dev.dim() != 2 or table_dev.shape[1] not in (5, 6) or table_dev.dtype != torch.int32 or not table_dev.is_cuda \
                 or not table_dev.is_contiguous():
-            raise ValueError("pieces_gather: the table must be a contiguous (R, 5) int32 device tensor")
+            raise ValueError("pieces_gather: the table must be a contiguous (R, 5) int32 device tensor ((R, 6): rows of jobs)")
+        by_job = table_dev.shape[1] == 6
         if audio is None and f0 is None:
             raise ValueError("pieces_gather: pass audio, or f0 with key_factor (and volume), or both")
         R, F = table_dev.shape[0], n_file_samples_dev.numel()
@@ -1585,7 +1590,7 @@ class Context:
             wav = torch.empty(R, int(S_max), device=self.device, dtype=torch.float32)
         if f0 is not None:
             Fr_max = dense("f0", f0, None).shape[1] if f0.dim() == 2 and f0.shape[0] == F else -1
-            dense("key_factor", key_factor, (F,))
+            dense("key_factor", key_factor, (key_factor.numel(),) if by_job and isinstance(key_factor, torch.Tensor) else (F,))
             f0_rows = torch.empty(R, int(N_max), device=self.device, dtype=torch.float32)
             if volume is not None:
                 dense("volume", volume, (F, Fr_max))
@@ -1594,9 +1599,12 @@ class Context:
             raise ValueError("pieces_gather: volume goes with f0")
         if T_max < 1 or Fr_max < 1:
             raise ValueError(f"pieces_gather: audio must be (F, T_max) and f0 (F, Fr_max) with F = {F} files and at least a column")
+        # (a table of jobs with the sample half alone has no key factors: J = 1 lets only job 0 pass, and nothing reads it)
+        symbol, jobs = ("ddsp_pieces_gather_jobs", (1 if key_factor is None else key_factor.numel(),)) if by_job else \
+            ("ddsp_pieces_gather", ())
         if R:
-            self.call("ddsp_pieces_gather", _ptr(audio), _ptr(f0), _ptr(volume), _ptr(key_factor), _ptr(n_file_samples_dev),
-                      _ptr(n_file_frames_dev), F, T_max, Fr_max, _ptr(table_dev), R, int(S_max), int(N_max), _ptr(wav),
+            self.call(symbol, _ptr(audio), _ptr(f0), _ptr(volume), _ptr(key_factor), _ptr(n_file_samples_dev),
+                      _ptr(n_file_frames_dev), F, T_max, Fr_max, *jobs, _ptr(table_dev), R, int(S_max), int(N_max), _ptr(wav),
                       _ptr(f0_rows), _ptr(vol_rows))
         return wav, f0_rows, vol_rows
 
@@ -1617,6 +1625,36 @@ class Context:
             table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).to(self.device)
             self.call("ddsp_stitch", _ptr(table), len(rows), _ptr(out), int(total))
         return out
+
+    def pcm16(self, x, spans=None):
+        """x: a contiguous fp64 device waveform (n,) (a view from any element of a larger tensor is fine); spans: None - the one
+        span (0, n) - or [(base, total)] ascending and disjoint with even bases, as `infer_offline.stitch_plan_many` lays files
+        out (ValueError otherwise, before anything is launched) -> (int16 device tensor (n,), peak (J,) fp64 device, clipped
+        (J,) int64 device) from one `ddsp_pcm16` launch: `clip(rint(x * 32768), -32768, 32767)` bit for bit as numpy computes it
+        on the host (`main.pcm16`), exact zeros between the spans, and per span the largest |x| and the number of clipped
+        samples.  2 bytes per sample to read back in place of 8.  Nothing is read back here."""
+        if not (isinstance(x, torch.Tensor) and x.dim() == 1 and x.dtype == torch.float64 and x.device == self.device
+                and x.is_contiguous()):
+            raise ValueError(f"pcm16: x must be a contiguous fp64 (n,) tensor on {self.device}")
+        n = x.numel()
+        table, J = None, 1
+        if spans is not None:
+            rows, end = [(int(base), int(total)) for base, total in spans], 0
+            for j, (base, total) in enumerate(rows):
+                if base < end or base % 2 or total < 0 or base + total > n:
+                    raise ValueError(f"pcm16: span {j} ({base}, {total}) must start at an even sample at or behind the end of the "
+                                     f"span before it ({end}) and end inside the {n} samples")
+                end = base + total
+            J = len(rows)
+            table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(self.device)
+        peak = torch.zeros(J, device=self.device, dtype=torch.float64)
+        clipped = torch.zeros(J, device=self.device, dtype=torch.int64)
+        if J == 0:                       # no span covers anything (an empty table has no address to pass)
+            return torch.zeros(n, device=self.device, dtype=torch.int16), peak, clipped
+        out = torch.empty(n, device=self.device, dtype=torch.int16)
+        if n:
+            self.call("ddsp_pcm16", _ptr(x), n, _ptr(table), J, _ptr(out), _ptr(peak), _ptr(clipped))
+        return out, peak, clipped
 
 
 class ResamplePlan:

@@ -14,6 +14,10 @@ over the slices of all files (rows formed by `ddsp_pieces_gather`, gated by `dds
 file into one fp64 device tensor (`stitch_plan_many`, `ddsp_stitch`), one read-back: `analyse_many` / `render_many_device` /
 `convert_many_device` / `convert_many`.  `render_device` / `convert_device` - `render` / `convert_batched` with the end on the
 device - are that body on a list of one file, which is its own batch and keeps `render`'s seed and speaker rules.
+The same body renders JOBS (`convert_many_device(jobs=, models=)`, `render_jobs_device`, `job_table`): a job is a file, a model, a
+speaker or mix and a key; the files are analysed once whatever the number of jobs, a row names its file for the source and its
+job for key, speaker and output span, and the groups are formed model by model.  `to_pcm16` turns the result into 16-bit PCM on
+the device (`ddsp_pcm16`), so the read-back is 2 bytes per sample.
 """
 import numbers
 
@@ -315,15 +319,86 @@ def group_pieces(pieces, budget, by_samples=False):
     return group_segments([row[4 if by_samples else 2] for row in pieces], budget)
 
 
-def _upload_pieces(ctx, files, groups):
+def job_table(pieces, n_files, jobs, models):
+    """The tables of a conversion of `jobs` over analysed files, made and checked on the host (nothing is launched).  pieces:
+    `piece_table` rows of the `n_files` files; jobs: a sequence of (file, model_index, spk, key) - spk a 1-based speaker id or a
+    mix dict {id: weight}, key in semitones; models: the synthesisers, which share the analysis and the stitch and so agree in
+    sampling rate, block size, unit width and device.  -> a dict:
+      rows          [(file, start_frame, n_frames, start_sample, n_samples, job)]: job after job, each with ALL pieces of its file
+                    in the file's order - the SAME source columns for every job over that file, which `ddsp_pieces_gather_jobs`
+                    reads in place; the sixth column names whose key factor (and speaker, and output span) the row takes;
+      piece_of_row  for every row, its index in `pieces` (whose units it takes);
+      model_of_job, speakers (an int or a dict per job), key_factor (2 ** (key / 12) per job, Python floats);
+      starts_per_job  the start frames of every job's rows, as `stitch_plan_many` takes them with jobs in the place of files.
+    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4-tuple, a file or
+    model index out of range, a speaker id outside [1, n_spk] of the JOB's model, or a mix with no or too many speakers."""
+    from realtime import MODEL_FIELDS, _model_field
+    models = list(models) if isinstance(models, (tuple, list)) else []
+    if not models:
+        raise ValueError("job_table: models must be a non-empty list of synthesisers")
+    for k, m in enumerate(models[1:], 1):
+        for field in MODEL_FIELDS:
+            a, b = _model_field(models[0], field), _model_field(m, field)
+            if a != b:
+                raise ValueError(f"job_table: models[{k}].{field} is {b}, models[0].{field} is {a}: the models of one call agree "
+                                 f"in {', '.join(MODEL_FIELDS)}")
+    per_file = [[i for i, row in enumerate(pieces) if row[0] == k] for k in range(int(n_files))]
+    table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": []}
+    for j, job in enumerate(jobs):
+        if not (isinstance(job, (tuple, list)) and len(job) == 4):
+            raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key), got {job!r}")
+        file, m, spk, key = job
+        if not (isinstance(file, numbers.Integral) and 0 <= file < int(n_files)):
+            raise ValueError(f"job_table: job {j}: file {file!r} is outside the {int(n_files)} files of the call")
+        if not (isinstance(m, numbers.Integral) and 0 <= m < len(models)):
+            raise ValueError(f"job_table: job {j}: model index {m!r} is outside the {len(models)} models of the call")
+        n_spk = int(models[m].unit2ctrl.n_spk)
+        if isinstance(spk, dict):
+            if not 1 <= len(spk) <= hipddsp.MAX_MIX:
+                raise ValueError(f"job_table: job {j}: a speaker mix holds 1 to {hipddsp.MAX_MIX} ids, got {len(spk)}")
+            ids = list(spk)
+            spk = {int(i): float(w) for i, w in spk.items()}
+        else:
+            if not isinstance(spk, numbers.Integral):
+                raise ValueError(f"job_table: job {j}: spk must be a speaker id or a mix dict, got {spk!r}")
+            ids = [spk]
+            spk = int(spk)
+        for i in ids:
+            if not (isinstance(i, numbers.Integral) and 1 <= i <= n_spk):
+                raise ValueError(f"job_table: job {j}: speaker id {i!r} is outside [1, {n_spk}] of models[{m}]")
+        if not isinstance(key, numbers.Real):
+            raise ValueError(f"job_table: job {j}: key must be a number of semitones, got {key!r}")
+        table["rows"].extend(tuple(pieces[i]) + (j,) for i in per_file[file])
+        table["piece_of_row"].extend(per_file[file])
+        table["starts_per_job"].append([pieces[i][1] for i in per_file[file]])
+        table["model_of_job"].append(int(m))
+        table["speakers"].append(spk)
+        table["key_factor"].append(2 ** (float(key) / 12))
+    return table
+
+
+def job_groups(table, n_models, batch_frames):
+    """The ragged render groups of `job_table`'s rows -> [(model_index, [row indices])]: model after model in `models` order,
+    `group_segments` over the frame counts of the rows of that model's jobs (a model without jobs has no group).  The position
+    in this list is the group's number g of the `noise_seed` rule (seed + g * 2**32)."""
+    out = []
+    for m in range(int(n_models)):
+        idx = [i for i, row in enumerate(table["rows"]) if table["model_of_job"][row[5]] == m]
+        out.extend((m, [idx[i] for i in group]) for group in group_segments([table["rows"][i][2] for i in idx], batch_frames))
+    return out
+
+
+def _upload_pieces(ctx, files, groups, rows=None):
     """The piece table of `files` in the order the groups take it -> (table (P, 5) int32 device, its transpose (5, P),
     [(first, last + 1)] of every group): a group's rows, and each of its columns, are contiguous views.  The upload is kept in
     `files` and serves every later stage that asks for the same rows: the order of `group_segments` is the sort by length
     whatever the budget, so the units (whole hops of samples), the forwards and the enhancer of one call share one upload.
-    A blocking copy in front of a stage would make the device wait while the host issues that stage's launches."""
-    rows = [files["pieces"][i] for group in groups for i in group]
+    A blocking copy in front of a stage would make the device wait while the host issues that stage's launches.
+    rows: the rows the groups index in place of `files['pieces']` - `job_table`'s, of six columns."""
+    width = 5 if rows is None else 6
+    rows = [(files["pieces"] if rows is None else rows)[i] for group in groups for i in group]
     if files.get("table_rows") != rows:
-        table = torch.tensor(rows, dtype=torch.int32).reshape(-1, 5).to(ctx.device)
+        table = torch.tensor(rows, dtype=torch.int32).reshape(-1, width).to(ctx.device)
         files.update(table_rows=rows, table=table, table_cols=table.t().contiguous())
     bounds, at = [], 0
     for group in groups:
@@ -505,7 +580,7 @@ def render_many_device(model, args, files, spk_ids, spk_mix_rows=None, threshold
     if F and noise is not None and ([len(x) for x in noise] != [sum(1 for row in pieces if row[0] == k) for k in range(F)]):
         raise ValueError("render_many_device: noise must hold one list per file with one draw per slice")
 
-    def speaker(file_of_row):                             # every row takes its file's speaker, or its file's mix
+    def speaker(file_of_row, order):                      # every row takes its file's speaker, or its file's mix
         rows = file_of_row.long()
         if spk_mix_rows is None:
             spk = torch.tensor(_per_file(spk_ids, F, "render_many_device: spk_ids"), dtype=torch.int64).to(dev)
@@ -548,7 +623,7 @@ def render_device(model, args, segments, f0, volume, spk_id, spk_mix_dict=None, 
 
 def _render_file(model, args, files, spk_id, spk_mix_dict, noise_seed, noise, **stages):
     """`_render_files` (`stages`: its keywords) on a list of one file under `render`'s seed and speaker rules -> (out, rate)."""
-    def speaker(file_of_row):
+    def speaker(file_of_row, order):
         return lambda a, b: {"spk_id": spk_id, "spk_mix_dict": spk_mix_dict}
 
     def seed_of_group(g, starts):
@@ -558,75 +633,183 @@ def _render_file(model, args, files, spk_id, spk_mix_dict, noise_seed, noise, **
 
 
 def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshold_db, enhancer, enhancer_adaptive_key,
-                  batch_frames, enhancer_batch_samples):
+                  batch_frames, enhancer_batch_samples, jobs=None):
     """The one render body, as `render_many_device` states it.  What its callers differ in is passed in.  speaker: called once
-    with the file of every row (int32 device, rows in the groups' order) -> a function of a group's row range (a, b) giving the
-    model's speaker keywords.  seed_of_group: None (the model draws its seed) or a function of the group's number and its rows'
-    start frames -> the group's noise seed.  noise: None or one draw per piece, in `pieces` order."""
+    with the file of every row (int32 device, rows in the groups' order) and the rows' indices in that order -> a function of a
+    group's row range (a, b) giving the model's speaker keywords.  seed_of_group: None (the model draws its seed) or a function
+    of the group's number and its rows' start frames -> the group's noise seed.  noise: None or one draw per row, in row order.
+    jobs: None - a row is a piece of `files`, an output is a file, `model` renders every group - or (models, `job_table`'s dict
+    with its key factors uploaded as 'key_factor_dev'): a row is a piece of a job's file (six columns: `ddsp_pieces_gather_jobs`
+    reads the file's features in place and takes the JOB's key factor), an output is a job, the groups are `job_groups`' and
+    each is rendered by its model.  The gate takes a row's file either way."""
     block, sr, dev = int(args.data.block_size), int(args.data.sampling_rate), files["device"]
     F, pieces, units = len(files["n_frames"]), files["pieces"], files["units"]
-    if F == 0:
+    if F == 0 or (jobs is not None and not jobs[1]["model_of_job"]):
         return torch.zeros(0, dtype=torch.float64, device=dev), [], sr
     ctx = hipddsp.context_for(dev)
     for k, start, n, _, _ in pieces:
         if start < 0 or start + n > files["n_frames"][k]:
             raise ValueError(f"offline render: file {k}: the segment at frame {start} has {n} frames of units but f0 / volume "
                              f"cover {files['n_frames'][k]} frames of the file")
-    groups = group_pieces(pieces, 0 if batch_frames is None else int(batch_frames))
-    table, cols, bounds = _upload_pieces(ctx, files, groups)
-    speaker_of_rows = speaker(cols[0])
-    out = [None] * len(pieces)
+    budget = 0 if batch_frames is None else int(batch_frames)
+    if jobs is None:
+        rows, unit_of, owner, n_out, key_factor = pieces, range(len(pieces)), 0, F, files["key_factor"]
+        groups = group_pieces(pieces, budget)
+        model_of_group = [model] * len(groups)
+    else:
+        models, table = jobs
+        rows, unit_of, owner, n_out, key_factor = table["rows"], table["piece_of_row"], 5, len(table["model_of_job"]), table["key_factor_dev"]
+        numbered = job_groups(table, len(models), budget)
+        groups, model_of_group = [group for _, group in numbered], [models[m] for m, _ in numbered]
+    given = None if jobs is None else rows
+    table, cols, bounds = _upload_pieces(ctx, files, groups, given)
+    speaker_of_rows = speaker(cols[0], [i for group in groups for i in group])
+    out = [None] * len(rows)
     for g, (group, (a, b)) in enumerate(zip(groups, bounds)):
-        counts = [pieces[i][2] for i in group]
-        u, _ = stack_rows([units[i][0] for i in group])
+        counts = [rows[i][2] for i in group]
+        u, _ = stack_rows([units[unit_of[i]][0] for i in group])
         _, f, v = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
-                                    volume=files["volume"], key_factor=files["key_factor"], N_max=max(counts))
-        kw = {} if seed_of_group is None else {"noise_seed": seed_of_group(g, [pieces[i][1] for i in group])}
+                                    volume=files["volume"], key_factor=key_factor, N_max=max(counts))
+        kw = {} if seed_of_group is None else {"noise_seed": seed_of_group(g, [rows[i][1] for i in group])}
         if noise is not None:
             kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
-        signal = model(u, f[:, :, None], v, n_frames=counts, **speaker_of_rows(a, b), **kw)[0].contiguous()
+        signal = model_of_group[g](u, f[:, :, None], v, n_frames=counts, **speaker_of_rows(a, b), **kw)[0].contiguous()
         ctx.volume_gate_rows_(signal, files["volume"], cols[1, a:b], cols[2, a:b], threshold_db, block,
                               file_dev=cols[0, a:b], file_frames_dev=files["n_frames_dev"])
         for j, i in enumerate(group):
             out[i] = signal[j:j + 1, :counts[j] * block]
     sr_o = sr
-    if enhancer is not None and pieces:
+    if enhancer is not None and rows:
         out, sr_o = _enhance_many(ctx, enhancer, out, files, sr, block, enhancer_adaptive_key,
-                                  0 if enhancer_batch_samples is None else enhancer_batch_samples)
-    per_file = [[i for i, row in enumerate(pieces) if row[0] == k] for k in range(F)]
-    spans, p, fade, total = stitch_plan_many([[pieces[i][1] for i in idx] for idx in per_file],
-                                             [[out[i].shape[-1] for i in idx] for idx in per_file], block, sr, sr_o)
+                                  0 if enhancer_batch_samples is None else enhancer_batch_samples, given, key_factor)
+    per_out = [[i for i, row in enumerate(rows) if row[owner] == k] for k in range(n_out)]
+    spans, p, fade, total = stitch_plan_many([[rows[i][1] for i in idx] for idx in per_out],
+                                             [[out[i].shape[-1] for i in idx] for idx in per_out], block, sr, sr_o)
     return ctx.stitch(out, p, fade, total), spans, sr_o
 
 
-def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples):
+def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples, rows=None, key_factor=None):
     """The device path's enhancer loop over the gated pieces of all files: one `Enhancer.enhance_batch` per group of
-    `group_segments` over the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group)."""
-    pieces = files["pieces"]
+    `group_segments` over the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group).
+    rows, key_factor: `job_table`'s rows and the jobs' key factors in place of the files' (one enhancer serves all models)."""
+    pieces = files["pieces"] if rows is None else rows
+    key_factor = files["key_factor"] if key_factor is None else key_factor
     groups = group_segments([g.shape[-1] for g in gated], int(enhancer_batch_samples))
-    table, _, bounds = _upload_pieces(ctx, files, groups)
+    table, _, bounds = _upload_pieces(ctx, files, groups, rows)
     out, sr_o = [None] * len(gated), sr
     for group, (a, b) in zip(groups, bounds):
         wav, counts = stack_rows([gated[i][0] for i in group])
         n_f0 = [pieces[i][2] for i in group]
         _, tracks, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
-                                         key_factor=files["key_factor"], N_max=max(n_f0))
+                                         key_factor=key_factor, N_max=max(n_f0))
         got, sr_o, n_out = enhancer.enhance_batch(wav, sr, tracks[:, :, None], block, counts, adaptive_key=adaptive_key, n_f0=n_f0)
         for j, i in enumerate(group):
             out[i] = got[j:j + 1, :n_out[j]]
     return out, sr_o
 
 
+def _models_of(who, model, models):
+    """`models=` and the positional model -> the list of models (`StreamBank`'s rule: with `models`, `model` is None or
+    models[0] itself; without, the list of that one model)."""
+    if models is None:
+        return [model]
+    if not (isinstance(models, (tuple, list)) and len(models)):
+        raise ValueError(f"{who}: models must be a non-empty list of synthesisers")
+    if model is not None and model is not models[0]:
+        raise ValueError(f"{who}: with models= the positional model is None or models[0] itself (it names model 0)")
+    return list(models)
+
+
 @torch.no_grad()
-def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, slices=None, keys=0,
+def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
+                       batch_frames=None, noise=None, enhancer_batch_samples=None):
+    """`render_many_device` for JOBS over the files of ONE `analyse_many` (analysed with keys=0: the key is the job's) -> (fp64
+    device tensor holding every job, [(base, total)] per job in job order, sample rate).  jobs: a sequence of (file,
+    model_index, spk, key) into `files` and `models` (`job_table` states and checks them: ValueError before any launch).  Job j
+    is out[base:base + total], what `render_many_device` gives for that file alone with that model, speaker and key.
+    The groups are formed per model over the slices of that model's jobs (`job_groups`), each one ragged forward of its model:
+    a row reads its file's f0 and volume in place through the six-column table (`ddsp_pieces_gather_jobs`) - f0 times its
+    JOB's key factor - takes its job's speaker, and is gated by its FILE's volume.  The units of a file's slices serve every
+    job over it.  A model whose jobs all name a plain id gets `spk_id` rows; one with a mix among its jobs gets `spk_mix_rows`
+    for all of them (a plain id is the row {id: 1.0}).  The enhancer - one for all models, one `enhancer_adaptive_key` per
+    call - takes ragged groups over the rows of all jobs, and ONE `ddsp_stitch` places every job (`stitch_plan_many` over jobs:
+    even bases, no fade across jobs).
+    noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
+    `models` order - draws with (noise_seed + g * 2**32) mod 2**64."""
+    models = _models_of("render_jobs_device", None, models)
+    dev, pieces, n_files = files["device"], files["pieces"], len(files["n_frames"])
+    table = job_table(pieces, n_files, jobs, models)
+    J = len(table["model_of_job"])
+    if J and noise is not None and [len(x) for x in noise] != [len(s) for s in table["starts_per_job"]]:
+        raise ValueError("render_jobs_device: noise must hold one list per job with one draw per slice of its file")
+    if J:
+        table["key_factor_dev"] = torch.tensor(table["key_factor"], dtype=torch.float32).to(dev)
+
+    def speaker(file_of_row, order):
+        # Every row takes its job's speaker, from host tables uploaded once in front of the launches (the job of a row is known
+        # here: nothing indexes with a device column).  The rows of a model are contiguous: the groups are numbered model by model.
+        jobs_in_order = [table["rows"][i][5] for i in order]
+        spk = torch.tensor([s if isinstance(s, int) else 1 for s in (table["speakers"][j] for j in jobs_in_order)],
+                           dtype=torch.int64).reshape(-1, 1).to(dev)
+        mixes = {}
+        for m, model in enumerate(models):
+            mine = [a for a, j in enumerate(jobs_in_order) if table["model_of_job"][j] == m]
+            of_rows = [table["speakers"][jobs_in_order[a]] for a in mine]
+            if any(isinstance(s, dict) for s in of_rows):
+                ids, w = hipddsp.mix_rows(of_rows, max(len(s) if isinstance(s, dict) else 1 for s in of_rows),
+                                          int(model.unit2ctrl.n_spk))
+                mixes[m] = (mine[0], ids.to(dev), w.to(dev))
+
+        def of_group(a, b):
+            m = table["model_of_job"][jobs_in_order[a]]
+            if m not in mixes:
+                return {"spk_id": spk[a:b]}
+            first, ids, w = mixes[m]
+            return {"spk_id": spk[a:b], "spk_mix_rows": (ids[a - first:b - first], w[a - first:b - first])}
+        return of_group
+
+    def seed_of_group(g, starts):
+        return (int(noise_seed) + (g << 32)) & ((1 << 64) - 1)
+    return _render_files(None, args, files, speaker, None if noise_seed is None else seed_of_group,
+                         None if noise is None else [x for per_job in noise for x in per_job], threshold_db=threshold_db,
+                         enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, batch_frames=batch_frames,
+                         enhancer_batch_samples=enhancer_batch_samples, jobs=(models, table))
+
+
+@torch.no_grad()
+def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids=None, slices=None, keys=0,
                         batch_frames=None, spk_mix_rows=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0,
-                        noise_seed=None, enhancer_batch_samples=None, units_batch_samples=None):
+                        noise_seed=None, enhancer_batch_samples=None, units_batch_samples=None, jobs=None, models=None,
+                        noise=None):
     """`analyse_many` then `render_many_device`: a list of files from raw audio to one fp64 device tensor -> (out, [(base,
-    total)] per file, sample rate).  Files are batched within ONE call's sample rate, enhancer key and model."""
-    files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys, units_batch_samples)
-    return render_many_device(model, args, files, spk_ids, spk_mix_rows=spk_mix_rows, threshold_db=threshold_db, enhancer=enhancer,
+    total)] per file, sample rate).  Files are batched within ONE call's sample rate and enhancer key.
+    jobs: None - one model (`model`), one speaker (`spk_ids`, required then) and one key per file, as above - or a sequence of
+    (file, model_index, spk, key): every file is analysed ONCE, whatever the number of jobs over it, and rendered once per job
+    (`render_jobs_device`) -> one span per job, in job order.  models: the synthesisers the jobs index (None: [model]; with it,
+    `model` is None or models[0]).  With `jobs`, the speaker and the key are the job's: `spk_ids`, `spk_mix_rows` and `keys`
+    must be left at their defaults (ValueError), and all tables are checked before anything is analysed (`job_table`).  An
+    empty list of jobs gives an empty tensor and no spans, and analyses nothing.
+    noise: `render_many_device`'s (per file) or `render_jobs_device`'s (per job) injected draws."""
+    if jobs is None:
+        if models is not None:
+            raise ValueError("convert_many_device: models= goes with jobs=; without jobs the one model is the positional one")
+        if spk_ids is None and spk_mix_rows is None:
+            raise ValueError("convert_many_device: spk_ids (or spk_mix_rows) is required without jobs=")
+        files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys, units_batch_samples)
+        return render_many_device(model, args, files, spk_ids, spk_mix_rows=spk_mix_rows, threshold_db=threshold_db,
+                                  enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed,
+                                  batch_frames=batch_frames, noise=noise, enhancer_batch_samples=enhancer_batch_samples)
+    if spk_ids is not None or spk_mix_rows is not None or not (isinstance(keys, numbers.Real) and keys == 0):
+        raise ValueError("convert_many_device: with jobs= the speaker and the key are each job's: leave spk_ids, spk_mix_rows and "
+                         "keys at their defaults")
+    models, jobs = _models_of("convert_many_device", model, models), list(jobs)
+    job_table([], len(audios), jobs, models)                # every refusal of the tables, before anything is analysed
+    if not jobs:
+        return torch.zeros(0, dtype=torch.float64, device=next(models[0].parameters()).device), [], int(args.data.sampling_rate)
+    files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, 0, units_batch_samples)
+    return render_jobs_device(models, args, files, jobs, threshold_db=threshold_db, enhancer=enhancer,
                               enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
-                              enhancer_batch_samples=enhancer_batch_samples)
+                              noise=noise, enhancer_batch_samples=enhancer_batch_samples)
 
 
 @torch.no_grad()
@@ -642,9 +825,20 @@ def convert_device(model, args, audio, sample_rate, slices, units_encoder, f0_ex
                         enhancer_batch_samples=enhancer_batch_samples)
 
 
-def convert_many(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, **kw):
-    """`convert_many_device` (its keywords) with ONE `.cpu()` of the whole result, split into the files -> ([float64 numpy
-    waveform per file], sample rate).  An empty list of files gives an empty list and launches nothing."""
+def convert_many(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids=None, **kw):
+    """`convert_many_device` (its keywords, `jobs=` and `models=` among them) with ONE `.cpu()` of the whole result, split into
+    the files - the jobs, with `jobs=` - -> ([float64 numpy waveform per file or job], sample rate).  An empty list of files
+    gives an empty list and launches nothing."""
     out, spans, sr_o = convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids, **kw)
     host = out.cpu().numpy() if spans else np.zeros(0)
     return [host[base:base + total].copy() for base, total in spans], sr_o
+
+
+def to_pcm16(result, spans):
+    """The fp64 device tensor and spans of `convert_many_device` / `render_many_device` (or (0, n) of a single file's tensor)
+    -> (int16 device tensor of the same layout, peak (len(spans),) fp64, clipped (len(spans),) int64, both on the device): one
+    `ddsp_pcm16` launch, `main.pcm16` of every span bit for bit, zeros in the gaps, the largest |x| and the number of clipped
+    samples of every span.  Reading the int16 tensor back moves 2 bytes per sample, not 8."""
+    if not result.is_cuda:
+        raise ValueError("to_pcm16: the result must be a device tensor (`main.pcm16` is the host statement)")
+    return hipddsp.context_for(result.device).pcm16(result, spans)

@@ -4,6 +4,12 @@ stitched waveform on the device and is read back once.
     python main.py -m <model.pt> -i <in.wav> -o <out.wav> [-id 1] [-mix None] [-k 0] [-e true] [-pe crepe] [-fmin 50]
                    [-fmax 1100] [-th -60] [-eak 0] [-sr 44100]
     python main.py -m <model.pt> -i <folder of .wav> -o <output folder> ...     (every file in one `convert_many_device`)
+    python main.py -m <model.pt> -i <folder> -o <folder> --jobs <jobs.yaml> ... (every file to every voice of the list)
+
+`--jobs` names a YAML list of entries {model: <model.pt, default -m>, id: <speaker id, default 1> | mix: {id: weight}, key:
+<semitones, default 0>, suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
+give `name_s.wav`.  All of it is ONE `convert_many_device(jobs=...)` - every file analysed once - and one read-back; `-id`,
+`-mix` and `-k` are then unused.
 
 The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
   * the key shift is applied once (the reference applies it twice, SURVEY 0.3);
@@ -11,6 +17,8 @@ The options and their defaults are the reference's (`main.py:19-31`).  What diff
   * the input is read with `preprocess.load_wav` and, at another rate than `-sr`, resampled on the device with
     `resample.Resample` as `preprocess` does (the reference's librosa resamples with its own filter);
   * the output is 16-bit PCM through `scipy.io.wavfile.write` - what the reference's `sf.write` makes of a `.wav` by default;
+    it is quantised on the device (`infer_offline.to_pcm16`; `pcm16` below is the host statement of the same numbers), so the
+    read-back is the int16 samples, and an output with clipped samples is reported in one line;
   * the reference's md5-keyed f0 cache is left out: the f0 of a file takes milliseconds on the device.
 """
 import argparse
@@ -43,6 +51,9 @@ def parse_args(args=None, namespace=None):
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     for short, long, kind, default, text in _OPTIONS:
         parser.add_argument(short, long, type=kind, required=default is None, default=default, help=text)
+    # (absent from the namespace unless given: the reference's options are the namespace of a plain call)
+    parser.add_argument("--jobs", type=str, default=argparse.SUPPRESS, help="YAML list of {model, id | mix, key, suffix}: every entry is applied "
+                        "to every .wav of the input folder")
     return parser.parse_args(args=args, namespace=namespace)
 
 
@@ -51,14 +62,29 @@ def pcm16(wave):
     return np.clip(np.rint(np.asarray(wave, dtype=np.float64) * 32768.0), -32768, 32767).astype(np.int16)
 
 
+def _write_pcm(result, spans, paths, sr_o):
+    """The waveforms out[base:base + total] of `spans` as 16-bit files at `paths`: quantised on the device, ONE read-back of the
+    int16 tensor with the spans' peak and clipped counts behind it, a warning line per output that clipped."""
+    from scipy.io import wavfile
+
+    from infer_offline import to_pcm16
+    pcm, peak, clipped = to_pcm16(result, spans)
+    tail = torch.cat([peak.view(torch.int16), clipped.view(torch.int16)])
+    host = torch.cat([pcm, tail]).cpu().numpy()                    # the one read-back
+    stats = host[pcm.numel():].copy()                              # (aligned for the 8-byte views, whatever the length)
+    peak, clipped = stats[:4 * len(spans)].view(np.float64), stats[4 * len(spans):].view(np.int64)
+    for path, (base, total), top, n in zip(paths, spans, peak, clipped):
+        wavfile.write(path, int(sr_o), host[base:base + total])
+        if n:
+            print(f" [Warning] {path}: {int(n)} of {total} samples clipped (peak {float(top):.3f})")
+
+
 @torch.no_grad()
 def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda", batch_frames=4096,
         enhancer_batch_samples=None, units_batch_samples=None):
     """Converts `cmd.input` into `cmd.output` as the options say -> (fp64 device waveform, sample rate).  `units_encoder`,
     `f0_extractor`, `enhancer`: objects to use in place of the ones the model's config and the options name (an encoder or
     extractor built for `cmd.sampling_rate` and the model's hop at that rate).  The batching keywords are `convert_device`'s."""
-    from scipy.io import wavfile
-
     from ddsp.vocoder import F0_Extractor, Units_Encoder, load_model
     from infer_offline import convert_device
     from preprocess import load_wav
@@ -83,6 +109,11 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
     if enhancer is None and cmd.enhance == "true":
         from enhancer import Enhancer
         enhancer = Enhancer(args.enhancer.type, args.enhancer.ckpt, device=device)
+    if getattr(cmd, "jobs", None) is not None:
+        if not os.path.isdir(cmd.input):
+            raise ValueError("--jobs goes with a folder as -i (and a folder as -o)")
+        return _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
+                         enhancer_batch_samples, units_batch_samples)
     if os.path.isdir(cmd.input):
         return _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                            enhancer_batch_samples, units_batch_samples)
@@ -93,19 +124,18 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
                                   threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
                                   enhancer_adaptive_key=float(cmd.enhancer_adaptive_key),
                                   enhancer_batch_samples=enhancer_batch_samples, units_batch_samples=units_batch_samples)
-    wavfile.write(cmd.output, int(sr_o), pcm16(result.cpu().numpy()))   # the file's one read-back
+    _write_pcm(result, [(0, result.numel())], [cmd.output], sr_o)
     return result, sr_o
 
 
 def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
                 units_batch_samples):
     """`run` for a directory: every `.wav` in `cmd.input` (sorted by name) through ONE `infer_offline.convert_many_device`, the
-    results written under the same names into the directory `cmd.output` (made if missing) after one read-back -> (the fp64
+    results written under the same names into the directory `cmd.output` (made if missing) after one read-back of their 16-bit
+    samples -> (the fp64
     device tensor holding every file, sample rate).  `-id`, `-k` and `-mix` hold for every file; a mix becomes a table row per
     file (`spk_mix_rows`).  The files are resampled to `-sr` like a single input; `-sr` must give the model an integral hop
     (`analyse_many` refuses another one)."""
-    from scipy.io import wavfile
-
     from infer_offline import convert_many_device
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
     audios = [load(os.path.join(cmd.input, n)) for n in names]
@@ -119,9 +149,47 @@ def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhan
         spk_mix_rows=rows, threshold_db=float(cmd.threhold), enhancer=use, enhancer_adaptive_key=float(cmd.enhancer_adaptive_key),
         enhancer_batch_samples=enhancer_batch_samples, units_batch_samples=units_batch_samples)
     os.makedirs(cmd.output, exist_ok=True)
-    host = result.cpu().numpy()                                        # the folder's one read-back
-    for name, (base, total) in zip(names, spans):
-        wavfile.write(os.path.join(cmd.output, name), int(sr_o), pcm16(host[base:base + total]))
+    _write_pcm(result, spans, [os.path.join(cmd.output, name) for name in names], sr_o)
+    return result, sr_o
+
+
+def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
+              units_batch_samples):
+    """`run` with `--jobs`: every entry of the list applied to every `.wav` of `cmd.input` (sorted by name), file after file and
+    entry after entry, through ONE `infer_offline.convert_many_device(jobs=...)` - one analysis per file - and one read-back ->
+    (the fp64 device tensor holding every output, sample rate).  The models are loaded once each, `-m` first (it is model 0 and
+    gives the configuration); they must agree as `job_table` says."""
+    import yaml
+
+    from ddsp.vocoder import load_model
+    from infer_offline import convert_many_device
+    with open(cmd.jobs) as fh:
+        entries = yaml.safe_load(fh)
+    if not (isinstance(entries, list) and entries and all(isinstance(e, dict) for e in entries)):
+        raise ValueError(f"--jobs: {cmd.jobs} must hold a non-empty list of {{model, id | mix, key, suffix}} entries")
+    paths, models, voices = [os.path.abspath(cmd.model_path)], [model], []
+    for n, e in enumerate(entries):
+        unknown = set(e) - {"model", "id", "mix", "key", "suffix"}
+        if unknown or ("id" in e and "mix" in e) or not str(e.get("suffix", "")):
+            raise ValueError(f"--jobs: entry {n} takes model, id or mix, key and a non-empty suffix, got {e!r}")
+        path = os.path.abspath(e.get("model", cmd.model_path))
+        if path not in paths:
+            paths.append(path)
+            models.append(load_model(path, device=device)[0])
+        voices.append((paths.index(path), e["mix"] if "mix" in e else int(e.get("id", 1)), float(e.get("key", 0)), str(e["suffix"])))
+    if len({v[3] for v in voices}) != len(voices):
+        raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
+    names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
+    audios = [load(os.path.join(cmd.input, n)) for n in names]
+    jobs = [(k, m, spk, key) for k in range(len(names)) for m, spk, key, _ in voices]
+    out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{suffix}.wav") for name in names for _, _, _, suffix in voices]
+    result, spans, sr_o = convert_many_device(
+        None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=models, batch_frames=batch_frames,
+        threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
+        enhancer_adaptive_key=float(cmd.enhancer_adaptive_key), enhancer_batch_samples=enhancer_batch_samples,
+        units_batch_samples=units_batch_samples)
+    os.makedirs(cmd.output, exist_ok=True)
+    _write_pcm(result, spans, out_paths, sr_o)
     return result, sr_o
 
 

@@ -505,6 +505,15 @@ int ddsp_pieces_gather(ddsp_ctx* ctx, void* stream, const float* audio, const fl
                        const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F,
                        int64_t T_max, int64_t Fr_max, const int32_t* table, int64_t R, int64_t S_max, int64_t N_max, float* wav,
                        float* f0_rows, float* vol_rows);
+/* The same launch for the rows of JOBS - a job is one conversion of a file to one voice and key, and several jobs may share
+ * a file: table (R, 6) int32 rows (file, start_frame, n_frames, start_sample, n_samples, job) and key_factor (J) fp32 by JOB.
+ * The file names the source of audio, f0 and volume - read in place, never copied per job -, the job names the key factor:
+ * f0_rows[r][j] = f0[file][start_frame + j] * key_factor[job].  A job outside [0, J) is a bad row like a file outside [0, F)
+ * (tested before key_factor is indexed): zeros and the device error word.  Everything else as above. */
+int ddsp_pieces_gather_jobs(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
+                            const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F,
+                            int64_t T_max, int64_t Fr_max, int64_t J, const int32_t* table, int64_t R, int64_t S_max,
+                            int64_t N_max, float* wav, float* f0_rows, float* vol_rows);
 
 /* ---- the stitch of an offline conversion (main.py:165-173 with `cross_fade`, main.py:50-57) ----------------------------
  * Places S rendered pieces into one fp64 output in ONE launch.  `pieces` is a DEVICE table of S rows; piece i holds `len`
@@ -527,6 +536,20 @@ typedef struct ddsp_stitch_piece {
     int64_t p, len, fade;
 } ddsp_stitch_piece;
 int ddsp_stitch(ddsp_ctx* ctx, void* stream, const ddsp_stitch_piece* pieces, int64_t S, double* out, int64_t total);
+
+/* ---- 16-bit PCM of a stitched waveform (what the offline command line writes into a .wav) --------------------------------
+ * ONE pass over x (n) fp64: out[t] = clip(rint(x[t] * 32768), -32768, 32767) as int16, rint rounding half to even - numpy's
+ * `np.clip(np.rint(x * 32768.0), -32768, 32767).astype(np.int16)` bit for bit for every finite x (NaN is out of contract, as
+ * numpy's cast is undefined there).  spans (J, 2) int64 DEVICE rows (base, total), ascending and disjoint (the layout of
+ * `stitch_plan_many`: bases even), or NULL: the one span (0, n), J ignored.  A sample inside no span is written as 0.
+ * peak (J) fp64 and clipped (J) int64, each or both NULL: per span the largest |x| and the number of samples whose
+ * rint(x * 32768) lies outside [-32768, 32767]; the call zeroes them on the stream first, then every workgroup adds its part
+ * with one atomic max and one atomic add per span it touches (wave shuffles and an LDS step in front).  x needs 8-byte
+ * alignment only: 16-byte loads where four samples lie before n at a 16-byte aligned address, 8-byte words elsewhere.  A span
+ * entry decides which samples count, never an address: whatever the table holds, nothing outside x[0, n) and out[0, n) is
+ * touched.  n == 0 launches nothing.  Does not synchronise, allocate or read back. */
+int ddsp_pcm16(ddsp_ctx* ctx, void* stream, const double* x, int64_t n, const int64_t* spans, int64_t J, int16_t* out,
+               double* peak, int64_t* clipped);
 
 /* ---- the device-side steps immediately before the synthesis path ------------- */
 /* replaces ddsp/vocoder.py:116-137 `Volume_Extractor.extract`: audio (B,T) -> volume (B, T/hop + 1), the RMS of
