@@ -123,13 +123,15 @@ namespace u2c {
 
 // speaker mix of a call (up to 16 table rows and their weights; n == 0: the spk_id path).  One mix for the whole batch travels
 // by value in ids / w; a mix per batch row (ddsp_unit2ctrl_fwd_rowmix, inference) lives in two device tables of n columns,
-// ids_dev (B, n) 1-based and w_dev (B, n), and ids / w are then unused.
+// ids_dev (B, n) 1-based and w_dev (B, n), and ids / w are then unused.  per_frame (ddsp_unit2ctrl_fwd_framemix): w_dev is
+// (B * Fr, n), a row of weights for every frame; ids_dev stays one row per batch row.
 struct MixArgs {
     int n;
     long long ids[16];
     float w[16];
     const int* ids_dev = nullptr;
     const float* w_dev = nullptr;
+    int per_frame = 0;
 };
 
 // ---- buffers of one forward pass --------------------------------------------------------------------------------

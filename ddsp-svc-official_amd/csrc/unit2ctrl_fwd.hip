@@ -321,9 +321,9 @@ struct EpiEmbed {
         v += fmaf(lf0, w.f0_w[n], w.f0_b[n]);
         v += fmaf(ph, w.phase_w[n], w.phase_b[n]);
         v += fmaf(vol[m], w.volume_w[n], w.volume_b[n]);
-        if (mix.ids_dev) {   // the row's own mix from the device tables, terms in slot order
+        if (mix.ids_dev) {   // the row's own mix from the device tables (weights per row or per frame), terms in slot order
             const int* ri = mix.ids_dev + (int64_t)(m / Fr) * mix.n;
-            const float* rw = mix.w_dev + (int64_t)(m / Fr) * mix.n;
+            const float* rw = mix.w_dev + (int64_t)(mix.per_frame ? m : m / Fr) * mix.n;   // weights of the frame, or of the row
             for (int k = 0; k < mix.n; ++k) {
                 const int id = ri[k];
                 if (id >= 1 && id <= w.n_spk)
@@ -372,7 +372,7 @@ struct EpiEmbed {
         }
         if (mix.ids_dev) {
             const int* ri = mix.ids_dev + (int64_t)(m / Fr) * mix.n;
-            const float* rw = mix.w_dev + (int64_t)(m / Fr) * mix.n;
+            const float* rw = mix.w_dev + (int64_t)(mix.per_frame ? m : m / Fr) * mix.n;   // weights of the frame, or of the row
             for (int k = 0; k < mix.n; ++k) {
                 const int id = ri[k];
                 if (id >= 1 && id <= w.n_spk) {
@@ -1270,12 +1270,13 @@ int check_inputs(ddsp_ctx* ctx, const ddsp_u2c_weights* wp, const float* units, 
 
 }  // namespace u2c
 
-// the inference forward behind ddsp_unit2ctrl_fwd and ddsp_unit2ctrl_fwd_rowmix (n_frames null or the counts: the same launches)
+// the inference forward behind ddsp_unit2ctrl_fwd, ddsp_unit2ctrl_fwd_rowmix and ddsp_unit2ctrl_fwd_framemix (n_frames null or the counts: the same launches)
 static int unit2ctrl_fwd_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
                              const float* f0_frames, const float* phase_frames, const float* volume,
                              const int64_t* spk_id, int64_t n_spk_id, const int64_t* mix_ids_host,
                              const float* mix_w_host, int n_mix, int64_t B, int64_t Fr, const int32_t* n_frames, float* ctrl,
-                             const int32_t* mix_ids_dev = nullptr, const float* mix_w_dev = nullptr, int K = 0) {
+                             const int32_t* mix_ids_dev = nullptr, const float* mix_w_dev = nullptr, int K = 0,
+                             int mix_per_frame = 0) {
     U2CInputs in;
     int rc = check_inputs(ctx, wp, units, f0_frames, phase_frames, volume, spk_id, n_spk_id, mix_ids_host, mix_w_host,
                           n_mix, B, Fr, in);
@@ -1285,6 +1286,7 @@ static int unit2ctrl_fwd_any(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights
         in.mix.n = K;
         in.mix.ids_dev = (const int*)mix_ids_dev;
         in.mix.w_dev = mix_w_dev;
+        in.mix.per_frame = mix_per_frame;   // mix_w_dev is (B, Fr, K): weights of every frame
     }
     DDSP_REQUIRE(ctx, ctrl, "ddsp_unit2ctrl_fwd: null ctrl");
     if ((rc = ddsp_take_dev_error(ctx))) return rc;
@@ -1382,6 +1384,20 @@ extern "C" int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp
     const float zero_w = 0.f;
     return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, nullptr, 0, &one_id, &zero_w, 1, B, Fr,
                              n_frames, ctrl, mix_ids_dev, mix_w_dev, K);
+}
+
+// A speaker mix per FRAME (include/ddsp_amd.h): the row-mix call whose weight table has a row for every frame, mix_w_dev
+// (B, Fr, K); the epilogue reads the weights at row m of the GEMM, the ids still at m / Fr.
+extern "C" int ddsp_unit2ctrl_fwd_framemix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* wp, const float* units,
+                                           const float* f0_frames, const float* phase_frames, const float* volume,
+                                           const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                           const int32_t* n_frames, float* ctrl) {
+    DDSP_REQUIRE(ctx, ctx && mix_ids_dev && mix_w_dev, "ddsp_unit2ctrl_fwd_framemix: null mix table");
+    DDSP_REQUIRE(ctx, K >= 1 && K <= 16, "ddsp_unit2ctrl_fwd_framemix: 1 <= K <= 16 mixed speakers per frame");
+    const int64_t one_id = 1;
+    const float zero_w = 0.f;
+    return unit2ctrl_fwd_any(ctx, stream, wp, units, f0_frames, phase_frames, volume, nullptr, 0, &one_id, &zero_w, 1, B, Fr,
+                             n_frames, ctrl, mix_ids_dev, mix_w_dev, K, 1);
 }
 
 // ---- a training step's pair: a forward that leaves its activations in a caller-owned region, a backward that starts from them ----

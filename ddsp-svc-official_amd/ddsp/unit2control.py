@@ -20,6 +20,39 @@ N_FEATURES = int(HEAD_DIM * math.log(HEAD_DIM))  # 266 random features (referenc
 DW_KERNEL = 31
 
 
+def is_frame_mix(spk_mix_rows):
+    """True for the per-FRAME form of `spk_mix_rows`: a pair (ids (B, K), w (B, Fr, K)) - the weights have a frame axis."""
+    return isinstance(spk_mix_rows, (tuple, list)) and len(spk_mix_rows) == 2 and isinstance(spk_mix_rows[1], torch.Tensor) \
+        and spk_mix_rows[1].dim() == 3
+
+
+def mix_frames_of_dict(spk_mix_dict, B, Fr, device, n_spk):
+    """The reference's `spk_mix_dict` with TENSOR values -> the per-frame tables (ids (B, K) int32, w (B, Fr, K) fp32) on
+    `device`, or None for a dict whose values are all numbers (the one host mix of the batch, handled as ever).  A value is a
+    tensor of shape (B, Fr, 1), (1, Fr, 1), (B, Fr), (1, Fr) or (Fr,) - what broadcasts against the reference's (B, Fr, 256)
+    activations, with (Fr,) read as one weight per frame - or a number, constant over the call.  Slots are in dict order, as
+    the reference's loop adds them.  ValueError for another shape, no or more than `hipddsp.MAX_MIX` ids, an id outside
+    [1, n_spk]."""
+    if not isinstance(spk_mix_dict, dict) or not any(isinstance(v, torch.Tensor) and v.dim() >= 1 for v in spk_mix_dict.values()):
+        return None
+    if not 1 <= len(spk_mix_dict) <= hipddsp.MAX_MIX:
+        raise ValueError(f"spk_mix_dict: a speaker mix holds 1 to {hipddsp.MAX_MIX} ids, got {len(spk_mix_dict)}")
+    cols = []
+    for i, v in spk_mix_dict.items():
+        if not 1 <= int(i) <= int(n_spk):
+            raise ValueError(f"spk_mix_dict: speaker id {i} is outside [1, {int(n_spk)}]")
+        if not (isinstance(v, torch.Tensor) and v.dim() >= 1):
+            cols.append(torch.full((B, Fr), float(v), dtype=torch.float32, device=device))
+            continue
+        shape = tuple(v.shape)
+        if shape not in ((B, Fr, 1), (1, Fr, 1), (B, Fr), (1, Fr), (Fr,)):
+            raise ValueError(f"spk_mix_dict: the weights of speaker {i} have shape {shape}; a per-frame weight is (B, Fr, 1), "
+                             f"(1, Fr, 1) or (Fr,) with B = {B}, Fr = {Fr}")
+        cols.append(v.to(device=device, dtype=torch.float32).reshape(-1, Fr).expand(B, Fr))
+    ids = torch.tensor([[int(i) for i in spk_mix_dict]] * B, dtype=torch.int32).to(device)
+    return ids, torch.stack(cols, dim=2).contiguous()
+
+
 class _Slot(nn.Module):
     """Placeholder keeping the index of a parameter-free layer inside an nn.Sequential."""
 
@@ -231,12 +264,16 @@ class Unit2Control(nn.Module):
     def forward_flat(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, n_frames=None, spk_mix_rows=None):
         """(B, Fr, n_out) fused control matrix (the split views are taken by `forward`).
         `spk_mix_rows` (ids (B, K) int32, w (B, K) fp32, device tensors): a speaker mix per row in place of `spk_id` /
-        `spk_mix_dict` (`hipddsp.check_mix_rows`; inference only, the callers check that).
+        `spk_mix_dict` (`hipddsp.check_mix_rows`; inference only, the callers check that).  With w (B, Fr, K) the pair is a mix
+        per FRAME (`hipddsp.check_mix_frames`): frame i of row b adds sum_k w[b, i, k] * spk_embed[ids[b, k] - 1].  A
+        `spk_mix_dict` with tensor values ((B, Fr, 1), (1, Fr, 1) or (Fr,), the reference's broadcast) is turned into that form
+        (`mix_frames_of_dict`); both refuse a network that wants gradients (NotImplementedError).
         `n_frames` (a sequence of B ints or a CPU integer tensor (B,), 1 <= n_frames[b] <= Fr): a ragged batch - the first
         n_frames[b] rows of ctrl[b] are what the network gives for that row alone at its own length, whatever the padding of
         the inputs holds; the rows after them carry no meaning.  Inference only: this call records nothing for autograd
         (NotImplementedError with grad mode on and a parameter that wants a gradient); the training pair of a ragged batch is
         `forward_ragged_keep` / `backward_flat(n_frames= | n_dev=)`."""
+        spk_mix_dict, spk_mix_rows = self.frame_mix(spk_mix_dict, spk_mix_rows, units.shape[0], units.shape[1], units.device)
         if n_frames is not None:
             vals = self.check_ragged(n_frames, units.shape[0], units.shape[1])
             if self.wants_grad():
@@ -245,10 +282,42 @@ class Unit2Control(nn.Module):
             ctx = hipddsp.context_for(units.device)
             n_dev, units, f0, phase, volume = self.hold_ragged(ctx, vals, units, f0, phase, volume)
             return self.forward_ragged(ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=False,
-                                       spk_mix_rows=spk_mix_rows)
+                                       spk_mix_rows=self.hold_frame_mix(ctx, spk_mix_rows, n_dev))
         ctx = hipddsp.context_for(units.device)
+        return self._control(ctx, units, f0, phase, volume, spk_id, spk_mix_dict, None, spk_mix_rows)
+
+    def frame_mix(self, spk_mix_dict, spk_mix_rows, B, Fr, device):
+        """Head of a call that may carry a mix per frame, before anything is launched -> (spk_mix_dict, spk_mix_rows) as the
+        rest of the call takes them: a `spk_mix_dict` with tensor values becomes the pair (ids, w (B, Fr, K)) and the dict
+        None; a per-frame pair is checked (`hipddsp.check_mix_frames`, ValueError) and refused with a dict beside it or on a
+        network that wants gradients (inference only, as the row mix); everything else passes through."""
+        made = mix_frames_of_dict(spk_mix_dict, B, Fr, device, self.n_spk) if spk_mix_rows is None else None
+        if made is not None:
+            spk_mix_dict, spk_mix_rows = None, made
+        if is_frame_mix(spk_mix_rows):
+            if spk_mix_dict is not None:
+                raise ValueError("a speaker mix per frame (device tables) and spk_mix_dict (one host mix for the batch) are "
+                                 "mutually exclusive")
+            hipddsp.check_mix_frames(spk_mix_rows[0], spk_mix_rows[1], B, Fr)
+            if self.wants_grad():
+                raise NotImplementedError("a speaker mix per frame is inference only: the training entries take spk_id or a "
+                                          "spk_mix_dict of numbers; call the model under torch.no_grad()")
+        return spk_mix_dict, spk_mix_rows
+
+    @staticmethod
+    def hold_frame_mix(ctx, spk_mix_rows, n_dev):
+        """The weights of a per-frame mix 0 past every row's count, like the other frame-rate inputs of a ragged call
+        (`hold_ragged`): what their padding holds never reaches arithmetic.  Another `spk_mix_rows` passes through."""
+        if not is_frame_mix(spk_mix_rows):
+            return spk_mix_rows
+        return spk_mix_rows[0], ctx.ragged_frames(spk_mix_rows[1], n_dev, hold=False)
+
+    def _control(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, spk_mix_rows):
+        """The one library call of an inference forward: the per-frame mix has a binding method of its own."""
         w, keep = self._weights_struct()
-        return ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, mix_dev=spk_mix_rows)
+        if is_frame_mix(spk_mix_rows):
+            return ctx.unit2ctrl_framemix(w, units, f0, phase, volume, spk_mix_rows[0], spk_mix_rows[1], self.n_out, n_frames=n_dev)
+        return ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, n_frames=n_dev, mix_dev=spk_mix_rows)
 
     def wants_grad(self):
         """True when a call must be recorded for autograd (grad mode on and some parameter wants a gradient)."""
@@ -274,9 +343,9 @@ class Unit2Control(nn.Module):
     def forward_ragged(self, ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, hold=True, spk_mix_rows=None):
         """The control matrix of a ragged batch whose counts are on the device (`Context.ragged_counts`) and whose units are 0
         past every row's count.  hold: every row's last control frame is repeated over its padding - the form in which the
-        DSP kernels take a ragged batch (`csrc/ragged.hip`)."""
-        w, keep = self._weights_struct()
-        ctrl = ctx.unit2ctrl(w, units, f0, phase, volume, spk_id, spk_mix_dict, self.n_out, n_frames=n_dev, mix_dev=spk_mix_rows)
+        DSP kernels take a ragged batch (`csrc/ragged.hip`).  The weights of a per-frame `spk_mix_rows` are finite past every
+        row's count (`hold_frame_mix`)."""
+        ctrl = self._control(ctx, units, f0, phase, volume, spk_id, spk_mix_dict, n_dev, spk_mix_rows)
         return ctx.ragged_frames(ctrl, n_dev, hold=True, out=ctrl) if hold else ctrl
 
     def forward_flat_keep(self, units, f0, phase, volume, spk_id, spk_mix_dict=None, ctx=None):

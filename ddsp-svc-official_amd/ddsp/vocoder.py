@@ -28,6 +28,13 @@ Differences a caller can observe, all additive:
     (`graphed.GraphedSynth(..., spk_mix_rows=True)`, `realtime.StreamBank`).  Works with and without `n_frames=`.
     Inference only (NotImplementedError under grad mode).  An id outside [1, n_spk] in a device table is reported by the
     kernel through the context's device error word (ValueError from the next library call).
+  * A speaker mix PER FRAME (a voice that glides inside a call): the pair (ids (B, K) int32, w (B, Fr, K) fp32) - the row
+    mix with a frame axis in its weights; frame i of row b adds sum_k w[b, i, k] * spk_embed[ids[b, k] - 1].  It is passed
+    as `spk_mix_rows=` (every model) or as `spk_mix_frames=` (`CombSub`, `CombSubFast`, which take extra keywords; `Sins`
+    keeps the reference's closed parameter list).  A `spk_mix_dict` whose values are tensors of shape (B, Fr, 1), (1, Fr, 1)
+    or (Fr,) - what the reference broadcasts in `x + v * spk_embed(id - 1)` - is turned into that form, slots in dict
+    order; a dict of numbers behaves as ever.  With `n_frames=` the weights past a row's count do not matter.  Inference
+    only, device error word and graph capture as for the row mix.
 """
 import os
 
@@ -41,7 +48,7 @@ from hipddsp import (COMB_SINC, COMB_SINC_GATED, COMB_NONE, EXC_AUDIO, EXC_GENER
 # the analysers live in ddsp/analysis.py; their names stay importable from here
 from .analysis import (Audio2HubertSoft, F0_Extractor, Units_Encoder, Volume_Extractor,  # noqa: F401
                        _find_torchcrepe_checkpoint, align_units)
-from .unit2control import Unit2Control
+from .unit2control import Unit2Control, is_frame_mix
 
 
 class DotDict(dict):
@@ -180,6 +187,19 @@ class _SynthBase(torch.nn.Module):
         z = lambda n: torch.zeros(0, n, device=f0_frames.device)
         return self._result(z(T if self._front_wants.get("want_phase") else Fr), [z(T) for _ in range(self._n_outs)])
 
+    @staticmethod
+    def _mix_keyword(spk_mix_rows, kwargs):
+        """`spk_mix_frames=(ids (B, K), w (B, Fr, K))` among a forward's extra keywords -> what `_forward` takes as
+        `spk_mix_rows` (the per-frame form is that pair with a frame axis in w); ValueError with `spk_mix_rows` beside it."""
+        frames = kwargs.get("spk_mix_frames")
+        if frames is None:
+            return spk_mix_rows
+        if spk_mix_rows is not None:
+            raise ValueError("spk_mix_frames= (a mix per frame) and spk_mix_rows= (a mix per row) are mutually exclusive")
+        if not (isinstance(frames, (tuple, list)) and len(frames) == 2 and is_frame_mix(tuple(frames))):
+            raise ValueError("spk_mix_frames must be a pair (ids (B, K) int32, w (B, Fr, K) fp32)")
+        return tuple(frames)
+
     def _check_mix_rows(self, spk_mix_dict, spk_mix_rows, B):
         """`forward(..., spk_mix_rows=(ids, w))`: refusals before anything is launched (shapes and dtypes on the host;
         the ids of device tables are checked by the kernel that reads them, through the context's device error word)."""
@@ -199,7 +219,8 @@ class _SynthBase(torch.nn.Module):
         f0 and volume;] the phase scan; the control network; the model's chain; [ragged: the padding of the returned phase
         cleared].  A call that autograd records is the same sequence inside `_SynthTrainFn.forward`."""
         B, Fr = units_frames.shape[0], units_frames.shape[1]
-        if spk_mix_rows is not None:
+        spk_mix_dict, spk_mix_rows = self.unit2ctrl.frame_mix(spk_mix_dict, spk_mix_rows, B, Fr, units_frames.device)
+        if spk_mix_rows is not None and not is_frame_mix(spk_mix_rows):
             self._check_mix_rows(spk_mix_dict, spk_mix_rows, B)
         if B == 0:
             return self._empty_result(f0_frames)
@@ -218,7 +239,7 @@ class _SynthBase(torch.nn.Module):
             f0 = f0.reshape(B, Fr, 1)
             ps = self._scan(ctx, f0, initial_phase, infer)
             ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], volume, spk_id, spk_mix_dict, n_dev,
-                                                 spk_mix_rows=spk_mix_rows)
+                                                 spk_mix_rows=self.unit2ctrl.hold_frame_mix(ctx, spk_mix_rows, n_dev))
             excitation = lambda: self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
         else:
             n_dev, f0 = None, f0_frames
@@ -377,9 +398,9 @@ class CombSub(_SynthBase):
                 infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None, **kwargs):
         """units (B,Fr,n_unit), f0 (B,Fr,1) Hz, volume (B,Fr), spk_id (B,1)|(1,1) int64 1-based ->
         (signal (B,T), phase_frames (B,Fr,1), (harmonic (B,T), noise (B,T))).  `n_frames`: ragged batch,
-        `spk_mix_rows`: a speaker mix per row (module docstring)."""
+        `spk_mix_rows`: a speaker mix per row, `spk_mix_frames=`: one per frame (module docstring)."""
         return self._forward(units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
-                             noise_seed, n_frames, spk_mix_rows)
+                             noise_seed, n_frames, self._mix_keyword(spk_mix_rows, kwargs))
 
 
 class Sins(_SynthBase):
@@ -487,6 +508,6 @@ class CombSubFast(_SynthBase):
                 infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None, **kwargs):
         """Returns (signal, phase_frames (B,Fr,1), (signal, signal)) - the same tensor three times, like the
         reference (`ddsp/vocoder.py:492`).  `n_frames`: ragged batch,
-        `spk_mix_rows`: a speaker mix per row (module docstring)."""
+        `spk_mix_rows`: a speaker mix per row, `spk_mix_frames=`: one per frame (module docstring)."""
         return self._forward(units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
-                             noise_seed, n_frames, spk_mix_rows)
+                             noise_seed, n_frames, self._mix_keyword(spk_mix_rows, kwargs))

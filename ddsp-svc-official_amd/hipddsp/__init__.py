@@ -253,6 +253,8 @@ SIGNATURES = {
     "ddsp_unit2ctrl_bwd": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _i64,
                                   _c.POINTER(_i64), _c.POINTER(_f32), _int, _i64, _i64, _vp, _vp, _c.POINTER(U2CWeights), _vp]),
     "ddsp_unit2ctrl_fwd_rowmix": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+    "ddsp_unit2ctrl_fwd_framemix": (_int, [_vp, _vp, _c.POINTER(U2CWeights), _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+    "ddsp_mix_timeline": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _int, _i64, _vp, _vp]),
     "ddsp_ragged_frames": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
     "ddsp_ragged_crop": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int]),
     "ddsp_ragged_noise": (_int, [_vp, _vp, _vp, _u64, _vp, _i64, _i64, _int, _vp]),
@@ -454,6 +456,27 @@ def check_mix_rows(ids, w, B, n_spk=None):
     return K
 
 
+def check_mix_frames(ids, w, B, Fr):
+    """The per-frame speaker-mix tables of `unit2ctrl_framemix`: ids (B, K) int32 (1-based) and w (B, Fr, K) fp32, contiguous
+    tensors on one device, 1 <= K <= 16; anything else raises ValueError (a host check of shapes and dtypes, as
+    `check_mix_rows`: nothing is launched or read back; the ids of device tables are the kernel's to check).  -> K."""
+    if not (isinstance(ids, torch.Tensor) and isinstance(w, torch.Tensor)):
+        raise ValueError("a frame mix is a pair of tensors (ids (B, K) int32, w (B, Fr, K) fp32)")
+    if ids.dtype != torch.int32 or w.dtype != torch.float32:
+        raise ValueError(f"a frame mix holds int32 ids and fp32 weights, got {ids.dtype} and {w.dtype}")
+    if ids.dim() != 2 or ids.shape[0] != int(B) or tuple(w.shape) != (int(B), int(Fr), ids.shape[1]):
+        raise ValueError(f"a frame mix holds ids (B={int(B)}, K) and weights (B={int(B)}, Fr={int(Fr)}, K), got "
+                         f"{tuple(ids.shape)} and {tuple(w.shape)}")
+    K = int(ids.shape[1])
+    if not 1 <= K <= MAX_MIX:
+        raise ValueError(f"a frame mix holds 1 to {MAX_MIX} speakers per frame, got K = {K}")
+    if ids.device != w.device:
+        raise ValueError("the two tables of a frame mix must live on one device")
+    if not (ids.is_contiguous() and w.is_contiguous()):
+        raise ValueError("the two tables of a frame mix must be contiguous")
+    return K
+
+
 def mix_rows(mixes, K, n_spk=None):
     """[{speaker id: weight} | int id, ...] -> CPU tables (ids (B, K) int32, w (B, K) fp32) in each dict's own order, short rows
     padded with {id 1, weight 0}; a plain id is the row {id: 1.0}.  ValueError for a row with no or more than K speakers, or an
@@ -635,6 +658,50 @@ class Context:
         hold, args = self._u2c_inputs(units, f0_frames, phase_frames, volume, spk_id, spk_mix_dict)
         self.call("ddsp_unit2ctrl_fwd", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
         return ctrl
+
+    def unit2ctrl_framemix(self, weights, units, f0_frames, phase_frames, volume, ids, w, n_out, n_frames=None):
+        """`unit2ctrl(mix_dev=)` with the weights of every FRAME: ids (B, K) int32 and w (B, Fr, K) fp32 device tables
+        (`check_mix_frames`); frame i of row b adds sum_k w[b, i, k] * spk_embed[ids[b, k] - 1] in slot order.  n_frames as
+        `unit2ctrl` takes it.  The kernels read the tables when they run (a captured graph follows edits); an id outside
+        [1, n_spk] sets the device error word."""
+        B, Fr, _ = units.shape
+        K = check_mix_frames(ids, w, B, Fr)
+        if not ids.is_cuda or ids.device != units.device:
+            raise ValueError("unit2ctrl_framemix: the mix tables must be on the units' device")
+        ctrl = torch.empty(B, Fr, n_out, device=units.device, dtype=torch.float32)
+        frames = [units.contiguous().float()] + [t.reshape(B, Fr).contiguous().float() for t in (f0_frames, phase_frames, volume)]
+        args = [_ptr(t) for t in frames] + [_ptr(ids), _ptr(w), K, B, Fr]
+        self.call("ddsp_unit2ctrl_fwd_framemix", ctypes.byref(weights), *args, _ptr(n_frames), _ptr(ctrl))
+        return ctrl
+
+    def mix_timeline(self, table_dev, bp_off, bp_frame, bp_w, job_ids, N_max):
+        """One launch (`ddsp_mix_timeline`): the speaker timelines of J jobs -> the per-frame mix tables of a render group.
+        table_dev (R, 6) int32 device rows of `infer_offline.job_table`; bp_off (J + 1,) int32, bp_frame (P,) int32 (file
+        frames), bp_w (P, K) fp32, job_ids (J, K) int32, all contiguous on the device -> (ids (R, K) int32, w (R, N_max, K)
+        fp32): the piecewise-linear interpolation of each row's job at its file frames, exact zeros past a row's count, and a
+        padding row (ids 1, weights 0) for a job outside [0, J).  Nothing is read back."""
+        def table(name, t, dtype, dim):
+            if not (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim
+                    and t.is_contiguous()):
+                raise ValueError(f"mix_timeline: {name} must be a contiguous {dim}-d {dtype} tensor on {self.device}")
+            return t
+        table("the table", table_dev, torch.int32, 2)
+        table("bp_off", bp_off, torch.int32, 1)
+        table("bp_frame", bp_frame, torch.int32, 1)
+        table("bp_w", bp_w, torch.float32, 2)
+        table("job_ids", job_ids, torch.int32, 2)
+        R, J, P, K = table_dev.shape[0], job_ids.shape[0], bp_frame.numel(), job_ids.shape[1]
+        if table_dev.shape[1] != 6 or bp_off.numel() != J + 1 or tuple(bp_w.shape) != (P, K) or J < 1 or P < 1 or \
+                not 1 <= K <= MAX_MIX or int(N_max) < 1:
+            raise ValueError(f"mix_timeline: a table (R, 6), bp_off (J + 1,), bp_frame (P,), bp_w (P, K) and job_ids (J, K) with "
+                             f"J, P, N_max >= 1 and 1 <= K <= {MAX_MIX}; got {tuple(table_dev.shape)}, {tuple(bp_off.shape)}, "
+                             f"{tuple(bp_frame.shape)}, {tuple(bp_w.shape)}, {tuple(job_ids.shape)}, N_max = {N_max}")
+        ids = torch.empty(R, K, device=self.device, dtype=torch.int32)
+        w = torch.empty(R, int(N_max), K, device=self.device, dtype=torch.float32)
+        if R:
+            self.call("ddsp_mix_timeline", _ptr(table_dev), R, J, _ptr(bp_off), _ptr(bp_frame), _ptr(bp_w), P, _ptr(job_ids), K,
+                      int(N_max), _ptr(ids), _ptr(w))
+        return ids, w
 
     # -- ragged batches (include/ddsp_amd.h): held frames, cropped signals, the noise draw ---------
     def ragged_counts(self, counts):

@@ -319,10 +319,78 @@ def group_pieces(pieces, budget, by_samples=False):
     return group_segments([row[4 if by_samples else 2] for row in pieces], budget)
 
 
+class SpeakerTimeline:
+    """The speaker of a job as a function of FILE time: a voice that glides inside a file.  points: a non-empty list of
+    (seconds, id | {id: weight}), times non-negative and ascending; between two points the weights of every id are interpolated
+    linearly, before the first and after the last they stay (an id a point does not name has weight 0 there; weights are not
+    normalised, as the reference's `spk_mix_dict` values are not).  `ids`: the distinct ids in order of first appearance, at most
+    `hipddsp.MAX_MIX` - the slots of the per-frame mix.  ValueError for anything else."""
+
+    def __init__(self, points):
+        if not (isinstance(points, (list, tuple)) and len(points)):
+            raise ValueError("SpeakerTimeline: points must be a non-empty list of (seconds, id | {id: weight})")
+        self.points, self.ids, last = [], [], 0.0
+        for n, point in enumerate(points):
+            if not (isinstance(point, (tuple, list)) and len(point) == 2):
+                raise ValueError(f"SpeakerTimeline: point {n} must be (seconds, id | {{id: weight}}), got {point!r}")
+            t, spk = point
+            if not (isinstance(t, numbers.Real) and not isinstance(t, bool) and t >= 0 and t == t and t != float("inf")):
+                raise ValueError(f"SpeakerTimeline: point {n}: the time must be a finite number of seconds >= 0, got {t!r}")
+            if t < last:
+                raise ValueError(f"SpeakerTimeline: point {n}: times must ascend, {t!r} follows {last!r}")
+            last = t
+            mix = spk if isinstance(spk, dict) else {spk: 1.0}
+            if not mix or not all(isinstance(i, numbers.Integral) and not isinstance(i, bool) and i >= 1 and
+                                  isinstance(w, numbers.Real) for i, w in mix.items()):
+                raise ValueError(f"SpeakerTimeline: point {n}: a speaker is an id >= 1 or a non-empty {{id: weight}}, got {spk!r}")
+            self.points.append((float(t), {int(i): float(w) for i, w in mix.items()}))
+            self.ids.extend(int(i) for i in mix if int(i) not in self.ids)
+        if len(self.ids) > hipddsp.MAX_MIX:
+            raise ValueError(f"SpeakerTimeline: at most {hipddsp.MAX_MIX} distinct ids, got {len(self.ids)}")
+
+    def frames(self, sampling_rate, block_size):
+        """-> (breakpoint frames, weights [point][slot of `ids`]): a point's frame is int(round(t * sampling_rate /
+        block_size)); ValueError when two points land on one frame (a jump has no slope: move one of them by a frame)."""
+        at = [int(round(t * sampling_rate / block_size)) for t, _ in self.points]
+        for n in range(1, len(at)):
+            if at[n] <= at[n - 1]:
+                raise ValueError(f"SpeakerTimeline: points {n - 1} and {n} ({self.points[n - 1][0]} s, {self.points[n][0]} s) both "
+                                 f"land on frame {at[n]} at {sampling_rate} Hz and block size {block_size}")
+        return at, [[mix.get(i, 0.0) for i in self.ids] for _, mix in self.points]
+
+
+def timeline_tables(speakers, mine, sampling_rate, block_size):
+    """The tables `ddsp_mix_timeline` takes for the jobs `mine` (indices into `speakers`, one model's jobs) -> CPU tensors
+    (bp_off (J + 1,) int32, bp_frame (P,) int32, bp_w (P, K) fp32, job_ids (J, K) int32) over ALL J jobs - a row names its job
+    by its number in the call -, K the most slots of a job among `mine`.  A `SpeakerTimeline` gives its breakpoints; an id or a
+    mix dict is the one breakpoint at frame 0 (a constant mix); a job outside `mine` owns no breakpoint.  Short rows are padded
+    with {id 1, weight 0}."""
+    per_job = {}
+    for j in mine:
+        s = speakers[j]
+        if isinstance(s, SpeakerTimeline):
+            at, w = s.frames(sampling_rate, block_size)
+            per_job[j] = (list(s.ids), at, w)
+        else:
+            mix = s if isinstance(s, dict) else {s: 1.0}
+            per_job[j] = ([int(i) for i in mix], [0], [[float(v) for v in mix.values()]])
+    K = max(len(ids) for ids, _, _ in per_job.values())
+    off, frame, w, job_ids = [0], [], [], []
+    for j in range(len(speakers)):
+        ids, at, rows = per_job.get(j, ([], [], []))
+        frame.extend(at)
+        w.extend(row + [0.0] * (K - len(row)) for row in rows)
+        job_ids.append(ids + [1] * (K - len(ids)))
+        off.append(len(frame))
+    return (torch.tensor(off, dtype=torch.int32), torch.tensor(frame, dtype=torch.int32),
+            torch.tensor(w, dtype=torch.float32).reshape(-1, K), torch.tensor(job_ids, dtype=torch.int32).reshape(-1, K))
+
+
 def job_table(pieces, n_files, jobs, models):
     """The tables of a conversion of `jobs` over analysed files, made and checked on the host (nothing is launched).  pieces:
-    `piece_table` rows of the `n_files` files; jobs: a sequence of (file, model_index, spk, key) - spk a 1-based speaker id or a
-    mix dict {id: weight}, key in semitones; models: the synthesisers, which share the analysis and the stitch and so agree in
+    `piece_table` rows of the `n_files` files; jobs: a sequence of (file, model_index, spk, key) - spk a 1-based speaker id, a
+    mix dict {id: weight} or a `SpeakerTimeline` (a voice that changes over the file; it stands in `speakers` as it is, its ids
+    checked against the job's model and its points against that model's frame rate), key in semitones; models: the synthesisers, which share the analysis and the stitch and so agree in
     sampling rate, block size, unit width and device.  -> a dict:
       rows          [(file, start_frame, n_frames, start_sample, n_samples, job)]: job after job, each with ALL pieces of its file
                     in the file's order - the SAME source columns for every job over that file, which `ddsp_pieces_gather_jobs`
@@ -353,7 +421,13 @@ def job_table(pieces, n_files, jobs, models):
         if not (isinstance(m, numbers.Integral) and 0 <= m < len(models)):
             raise ValueError(f"job_table: job {j}: model index {m!r} is outside the {len(models)} models of the call")
         n_spk = int(models[m].unit2ctrl.n_spk)
-        if isinstance(spk, dict):
+        if isinstance(spk, SpeakerTimeline):
+            ids = spk.ids               # (at most MAX_MIX: the timeline checked that)
+            try:
+                spk.frames(_model_field(models[m], "sampling_rate"), _model_field(models[m], "block_size"))
+            except ValueError as e:
+                raise ValueError(f"job_table: job {j}: {e}") from None
+        elif isinstance(spk, dict):
             if not 1 <= len(spk) <= hipddsp.MAX_MIX:
                 raise ValueError(f"job_table: job {j}: a speaker mix holds 1 to {hipddsp.MAX_MIX} ids, got {len(spk)}")
             ids = list(spk)
@@ -731,7 +805,9 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     a row reads its file's f0 and volume in place through the six-column table (`ddsp_pieces_gather_jobs`) - f0 times its
     JOB's key factor - takes its job's speaker, and is gated by its FILE's volume.  The units of a file's slices serve every
     job over it.  A model whose jobs all name a plain id gets `spk_id` rows; one with a mix among its jobs gets `spk_mix_rows`
-    for all of them (a plain id is the row {id: 1.0}).  The enhancer - one for all models, one `enhancer_adaptive_key` per
+    for all of them (a plain id is the row {id: 1.0}); one with a `SpeakerTimeline` among its jobs renders ALL its groups with
+    a mix per frame - one `ddsp_mix_timeline` launch per group turns the jobs' breakpoints (file time) into the weights of the
+    group's rows, wherever in their files the rows lie, and its id and dict jobs are timelines of one breakpoint.  The enhancer - one for all models, one `enhancer_adaptive_key` per
     call - takes ragged groups over the rows of all jobs, and ONE `ddsp_stitch` places every job (`stitch_plan_many` over jobs:
     even bases, no fade across jobs).
     noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
@@ -749,19 +825,28 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
         # Every row takes its job's speaker, from host tables uploaded once in front of the launches (the job of a row is known
         # here: nothing indexes with a device column).  The rows of a model are contiguous: the groups are numbered model by model.
         jobs_in_order = [table["rows"][i][5] for i in order]
+        ctx = hipddsp.context_for(dev)
         spk = torch.tensor([s if isinstance(s, int) else 1 for s in (table["speakers"][j] for j in jobs_in_order)],
                            dtype=torch.int64).reshape(-1, 1).to(dev)
-        mixes = {}
+        mixes, timelines = {}, {}
         for m, model in enumerate(models):
             mine = [a for a, j in enumerate(jobs_in_order) if table["model_of_job"][j] == m]
             of_rows = [table["speakers"][jobs_in_order[a]] for a in mine]
-            if any(isinstance(s, dict) for s in of_rows):
+            if any(isinstance(s, SpeakerTimeline) for s in of_rows):
+                # a model with a timeline among its jobs: the per-frame mix for ALL its groups, its id and dict jobs as constant
+                # timelines; the tables go up once, every group's weights come from one `ddsp_mix_timeline` launch
+                jobs_of_m = [j for j, mj in enumerate(table["model_of_job"]) if mj == m]
+                timelines[m] = [t.to(dev) for t in timeline_tables(table["speakers"], jobs_of_m, model._sr, model._hop)]
+            elif any(isinstance(s, dict) for s in of_rows):
                 ids, w = hipddsp.mix_rows(of_rows, max(len(s) if isinstance(s, dict) else 1 for s in of_rows),
                                           int(model.unit2ctrl.n_spk))
                 mixes[m] = (mine[0], ids.to(dev), w.to(dev))
 
         def of_group(a, b):
             m = table["model_of_job"][jobs_in_order[a]]
+            if m in timelines:
+                N_max = max(table["rows"][i][2] for i in order[a:b])
+                return {"spk_id": spk[a:b], "spk_mix_rows": ctx.mix_timeline(files["table"][a:b], *timelines[m], N_max)}
             if m not in mixes:
                 return {"spk_id": spk[a:b]}
             first, ids, w = mixes[m]

@@ -6,8 +6,9 @@ stitched waveform on the device and is read back once.
     python main.py -m <model.pt> -i <folder of .wav> -o <output folder> ...     (every file in one `convert_many_device`)
     python main.py -m <model.pt> -i <folder> -o <folder> --jobs <jobs.yaml> ... (every file to every voice of the list)
 
-`--jobs` names a YAML list of entries {model: <model.pt, default -m>, id: <speaker id, default 1> | mix: {id: weight}, key:
-<semitones, default 0>, suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
+`--jobs` names a YAML list of entries {model: <model.pt, default -m>, id: <speaker id, default 1> | mix: {id: weight} |
+timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...] (a voice that glides over the file,
+`infer_offline.SpeakerTimeline`), key: <semitones, default 0>, suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
 give `name_s.wav`.  All of it is ONE `convert_many_device(jobs=...)` - every file analysed once - and one read-back; `-id`,
 `-mix` and `-k` are then unused.
 
@@ -169,14 +170,15 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
         raise ValueError(f"--jobs: {cmd.jobs} must hold a non-empty list of {{model, id | mix, key, suffix}} entries")
     paths, models, voices = [os.path.abspath(cmd.model_path)], [model], []
     for n, e in enumerate(entries):
-        unknown = set(e) - {"model", "id", "mix", "key", "suffix"}
-        if unknown or ("id" in e and "mix" in e) or not str(e.get("suffix", "")):
-            raise ValueError(f"--jobs: entry {n} takes model, id or mix, key and a non-empty suffix, got {e!r}")
+        unknown = set(e) - {"model", "id", "mix", "timeline", "key", "suffix"}
+        if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or not str(e.get("suffix", "")):
+            raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key and a non-empty suffix, got {e!r}")
         path = os.path.abspath(e.get("model", cmd.model_path))
         if path not in paths:
             paths.append(path)
             models.append(load_model(path, device=device)[0])
-        voices.append((paths.index(path), e["mix"] if "mix" in e else int(e.get("id", 1)), float(e.get("key", 0)), str(e["suffix"])))
+        spk = _timeline(n, e["timeline"]) if "timeline" in e else e["mix"] if "mix" in e else int(e.get("id", 1))
+        voices.append((paths.index(path), spk, float(e.get("key", 0)), str(e["suffix"])))
     if len({v[3] for v in voices}) != len(voices):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
@@ -191,6 +193,14 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
     os.makedirs(cmd.output, exist_ok=True)
     _write_pcm(result, spans, out_paths, sr_o)
     return result, sr_o
+
+
+def _timeline(n, points):
+    """An entry's `timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...]` -> `SpeakerTimeline`."""
+    from infer_offline import SpeakerTimeline
+    if not (isinstance(points, list) and points and all(isinstance(p, dict) and set(p) in ({"at", "id"}, {"at", "mix"}) for p in points)):
+        raise ValueError(f"--jobs: entry {n}: timeline is a non-empty list of {{at, id}} or {{at, mix}} points, got {points!r}")
+    return SpeakerTimeline([(p["at"], p["id"] if "id" in p else p["mix"]) for p in points])
 
 
 if __name__ == "__main__":

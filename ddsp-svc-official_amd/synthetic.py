@@ -54,13 +54,16 @@ MODEL_CFG = {
 }
 
 
-def build_model(name, seed=BASE_SEED, device="cpu", n_unit=None):
+def build_model(name, seed=BASE_SEED, device="cpu", n_unit=None, n_spk=None):
     """Constructs the product module with seeded random weights (reference state-dict shapes).  `n_unit` overrides the
-    encoder width (configs/combsub_xunit.yaml: 4, combsub_yunit.yaml: 512, reference `data.encoder_out_channels`)."""
+    encoder width (configs/combsub_xunit.yaml: 4, combsub_yunit.yaml: 512, reference `data.encoder_out_channels`), `n_spk`
+    the rows of the speaker table."""
     from ddsp.vocoder import CombSub, CombSubFast, Sins
     cfg = dict(MODEL_CFG[name])
     if n_unit is not None:
         cfg["n_unit"] = int(n_unit)
+    if n_spk is not None:
+        cfg["n_spk"] = int(n_spk)
     gen_state = torch.random.get_rng_state()
     torch.manual_seed(seed)
     try:

@@ -219,6 +219,14 @@ int ddsp_unit2ctrl_fwd_rowmix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weight
                               const float* f0_frames, const float* phase_frames, const float* volume,
                               const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
                               const int32_t* n_frames, float* ctrl);
+/* The same call with the weights of every FRAME: mix_w_dev is (B, Fr, K), mix_ids_dev stays (B, K).  Frame i of row b adds
+ *   sum_k mix_w_dev[b][i][k] * spk_table[mix_ids_dev[b][k] - 1]   (slot order, after the f0, phase and volume terms)
+ * - the reference's `spk_mix_dict` with (B, Frame, 1) tensors as values, a voice that changes inside a call.  Ids, the error
+ * word, n_frames and the launches as for ddsp_unit2ctrl_fwd_rowmix; weights constant over a row's frames give its bits. */
+int ddsp_unit2ctrl_fwd_framemix(ddsp_ctx* ctx, void* stream, const ddsp_u2c_weights* weights_host, const float* units,
+                                const float* f0_frames, const float* phase_frames, const float* volume,
+                                const int32_t* mix_ids_dev, const float* mix_w_dev, int K, int64_t B, int64_t Fr,
+                                const int32_t* n_frames, float* ctrl);
 int ddsp_ragged_crop(ddsp_ctx* ctx, void* stream, float* x0, float* x1, float* x2, const int32_t* n_frames, int64_t B,
                      int64_t Fr, int hop);
 int ddsp_ragged_noise(ddsp_ctx* ctx, void* stream, const float* noise, uint64_t noise_seed, const int32_t* n_frames,
@@ -514,6 +522,18 @@ int ddsp_pieces_gather_jobs(ddsp_ctx* ctx, void* stream, const float* audio, con
                             const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F,
                             int64_t T_max, int64_t Fr_max, int64_t J, const int32_t* table, int64_t R, int64_t S_max,
                             int64_t N_max, float* wav, float* f0_rows, float* vol_rows);
+/* The speaker timelines of jobs -> the per-frame mix of one render group (ddsp_unit2ctrl_fwd_framemix's tables), one launch.
+ * table (R, 6) as above.  Job j owns the breakpoints bp_off[j] .. bp_off[j + 1] - 1 (bp_off (J + 1) int32, a prefix table):
+ * bp_frame (P) int32 their positions in FILE frames, strictly increasing inside a job; bp_w (P, K) fp32 the weights of the
+ * job's K slots there; job_ids (J, K) int32 the slots' 1-based speaker ids.  ids_rows (R, K) = job_ids[job]; w_rows
+ * (R, N_max, K): frame t < n_frames of row r is file frame f = start_frame + t and gets the piecewise-linear interpolation of
+ * its job's breakpoints at f - constant before the first and after the last, so one breakpoint is a constant mix -, computed
+ * in fp64 as w0 + (w1 - w0) * ((f - f0) / (f1 - f0)) and rounded to fp32; frames t >= n_frames get exact zeros.  A job outside
+ * [0, J), or a breakpoint range that is empty or leaves [0, P), is tested before it forms an address: such a row is a padding
+ * row, ids 1 and weights 0 (no error word).  R <= 65535, 1 <= K <= 16.  Does not synchronise, allocate or read back. */
+int ddsp_mix_timeline(ddsp_ctx* ctx, void* stream, const int32_t* table, int64_t R, int64_t J, const int32_t* bp_off,
+                      const int32_t* bp_frame, const float* bp_w, int64_t P, const int32_t* job_ids, int K, int64_t N_max,
+                      int32_t* ids_rows, float* w_rows);
 
 /* ---- the stitch of an offline conversion (main.py:165-173 with `cross_fade`, main.py:50-57) ----------------------------
  * Places S rendered pieces into one fp64 output in ONE launch.  `pieces` is a DEVICE table of S rows; piece i holds `len`
