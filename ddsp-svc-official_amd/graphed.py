@@ -95,13 +95,16 @@ def _refill(static, value):
 class GraphedSynth(_Captured):
     def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None, capture=True):
         """`spk_mix_rows`: None / False; True (K = 4 slots per row) or a K for static mix tables of the graph's own; or the
-        caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses.
+        caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses; with
+        w (B, Fr, K) they are a mix per FRAME (`hipddsp.check_mix_frames`), which reaches the control network's framemix entry.
         `capture=False` (a subclass that also runs eagerly, `GraphedModelRows`): the static tensors alone, `graph` is None."""
         rows = spk_mix_rows is not None and spk_mix_rows is not False
         if rows and spk_mix_dict is not None:
             raise ValueError("GraphedSynth: spk_mix_rows and spk_mix_dict are mutually exclusive")
         tables = spk_mix_rows if isinstance(spk_mix_rows, (tuple, list)) else None
-        if tables is not None:
+        if tables is not None and isinstance(tables[1], torch.Tensor) and tables[1].dim() == 3:
+            K = hipddsp.check_mix_frames(tables[0], tables[1], B, Fr)   # a mix per FRAME: w (B, Fr, K)
+        elif tables is not None:
             K = hipddsp.check_mix_rows(tables[0], tables[1], B, int(model.unit2ctrl.n_spk))
         else:
             K = 0 if not rows else (4 if spk_mix_rows is True else int(spk_mix_rows))
@@ -245,13 +248,17 @@ class GraphedBlock(_Captured):
     caller's too (`realtime.StreamBank`'s state): the graph reads them at their fixed addresses, so a write to a row between two
     replays is all a speaker, mix or pitch change takes.  Without it the speaker is the static input `spk_id` and the captured
     `spk_mix_dict`, and `pitch` a host factor.  `push`: `block_chain`'s; what it changes besides `window` it must leave alone
-    while the capture runs (the bank's row table is all padding then).  `model=None`: the features alone (`block_chain`), `sig` is None and there is no `noise`.  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
+    while the capture runs (the bank's row table is all padding then), or name in `keep`: tensors of the caller's that the
+    capture's runs change in place and that are put back as they were found, like `window` (a gliding bank's clocks).  With
+    w (S, Fr, K) in `mix_rows` the mix is one per FRAME, and `push` fills it (`ddsp_bank_glide`).  `model=None`: the features alone (`block_chain`), `sig` is None and there is no `noise`.  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
     next replay): `sig`, `f0`, `units`, `volume`."""
 
     def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch,
-                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None):
+                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None, keep=()):
         if mix_rows is not None and spk_mix_dict is not None:
             raise ValueError("GraphedBlock: mix_rows and spk_mix_dict are mutually exclusive")
+        if mix_rows is not None and mix_rows[1].dim() == 3:          # a mix per FRAME: w (S, Fr, K), filled by `push`
+            hipddsp.check_mix_frames(mix_rows[0], mix_rows[1], window.shape[0], int(window.shape[-1] // hop_size) + 1)
         dev = window.device if model is None else next(model.parameters()).device
         state = [window, *(mix_rows or ())] + ([pitch] if isinstance(pitch, torch.Tensor) else [])
         if dev.type != "cuda" or any(t.device != dev for t in state):
@@ -272,7 +279,7 @@ class GraphedBlock(_Captured):
             self.speaker = {"spk_id": None, "spk_mix_rows": tuple(mix_rows)}
         self.noise = None if model is None else torch.rand(*(rows or (1,)), frames * self.block_size, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sig, self.f0, self.units, self.volume = self._capture(dev, warmup, keep=[window])
+        self.sig, self.f0, self.units, self.volume = self._capture(dev, warmup, keep=[window, *keep])
         self.seed.random_(0, 2 ** 62)
 
     def _run(self):

@@ -237,6 +237,7 @@ SIGNATURES = {
     "ddsp_bank_gather": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp,
                                 _vp, _vp, _vp]),
     "ddsp_bank_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp]),
+    "ddsp_bank_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _i64, _i64, _i64, _f64, _vp]),
     "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
     "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
@@ -1532,6 +1533,33 @@ class Context:
             raise ValueError("bank_scatter_: the buffers must be fp32")
         self.call("ddsp_bank_scatter", _ptr(rows), W, sola_buffer.shape[0], _ptr(csola), xfade, _ptr(sola_buffer))
         return sola_buffer
+
+    def bank_glide_(self, rows, clock, bp_n, bp_t, bp_w, spk_w, w_frames, n_in, block, hop):
+        """The per-frame mix weights of one call's rows from the slots' glide state, and the advance of those slots' clocks
+        (`ddsp_bank_glide`): rows (W,) int32 device, entry r the slot of row r (anything outside [0, S): a padding row, weights
+        (1, 0, ...)), or None for row r = slot r (W is then w_frames' row count).  In place: w_frames (W, Fr, K) takes, for frame
+        t of a real row, the slot's breakpoints bp_t (S, P_max) int64 / bp_w (S, P_max, K) - the first bp_n (S,) int32 of them -
+        interpolated at tau = clock[s] + block - n_in + t * hop, or spk_w (S, K) when the slot has none; then clock (S,) int64
+        advances by `block` for the named slots alone.  No slot may be named twice.  -> w_frames."""
+        if not (isinstance(w_frames, torch.Tensor) and w_frames.dim() == 3 and isinstance(clock, torch.Tensor) and clock.dim() == 1 and
+                isinstance(bp_t, torch.Tensor) and bp_t.dim() == 2):
+            raise ValueError("bank_glide_: w_frames (W, Fr, K), clock (S,) and bp_t (S, P_max)")
+        (W, Fr, K), S, P_max = w_frames.shape, clock.numel(), bp_t.shape[1]
+        tables = ((clock, torch.int64, (S,)), (bp_n, torch.int32, (S,)), (bp_t, torch.int64, (S, P_max)),
+                  (bp_w, torch.float32, (S, P_max, K)), (spk_w, torch.float32, (S, K)), (w_frames, torch.float32, (W, Fr, K)))
+        if rows is not None:
+            tables += ((rows, torch.int32, (W,)),)
+        if any(not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or
+               t.device != w_frames.device for t, dtype, shape in tables):
+            raise ValueError("bank_glide_: contiguous tensors on one device: clock (S,) int64, bp_n (S,) int32, bp_t (S, P_max) int64, "
+                             "bp_w (S, P_max, K) fp32, spk_w (S, K) fp32, w_frames (W, Fr, K) fp32 and rows (W,) int32 or None")
+        if not (1 <= K <= MAX_MIX and 1 <= P_max <= 64 and S >= 1 and Fr >= 1 and W <= 65535 and int(block) >= 1 and int(n_in) >= 1 and
+                float(hop) > 0):
+            raise ValueError(f"bank_glide_: 1 <= K <= {MAX_MIX}, 1 <= P_max <= 64, W <= 65535, Fr, block, n_in >= 1 and hop > 0")
+        if W:
+            self.call("ddsp_bank_glide", _ptr(rows), W, S, _ptr(clock), _ptr(bp_n), _ptr(bp_t), _ptr(bp_w), P_max, _ptr(spk_w), K, Fr,
+                      int(n_in), int(block), float(hop), _ptr(w_frames))
+        return w_frames
 
     def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
         """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row

@@ -369,6 +369,7 @@ def default_model_widths(S):
 
 
 MODEL_FIELDS = ("sampling_rate", "block_size", "n_unit", "device")
+MAX_GLIDE_POINTS = 64             # breakpoints of one slot's speaker timeline (`ddsp_bank_glide`'s P_max)
 
 
 def _model_field(model, field):
@@ -405,12 +406,18 @@ class _Rows:
     under `use_graph` the captures over them.  The bank's own state is the width-S instance; its window push is
     `ddsp_stream_push`.  A compact instance (`active_widths`) has tensors of its own and a device row table `rows` (W,) int32,
     entry r the slot of row r or -1 for padding, all padding until a call names its slots: its push is `ddsp_bank_gather` from the
-    bank's state, and `scatter` (`ddsp_bank_scatter`) brings the spliced buffers back to the slots."""
+    bank's state, and `scatter` (`ddsp_bank_scatter`) brings the spliced buffers back to the slots.  On a bank with
+    `glide_breakpoints` every instance has a static `w_frames` (W, Fr, K) too: its push ends with `ddsp_bank_glide`, which fills
+    it from the SLOTS' glide state through the row table, and `mix` - what the synthesis takes as its speaker term - is then the
+    per-frame pair (`spk_ids`, `w_frames`) instead of the row pair (`spk_ids`, `spk_w`)."""
 
     def __init__(self, bank, W, compact):
         self.bank, self.W, self.A = bank, int(W), int(W)
         self.graph = self.bank_graph = self.enhancer_graph = None
-        self.rows = self.request = None
+        self.rows = self.request = self.w_frames = None
+        if bank.glide_breakpoints is not None:
+            self.w_frames = torch.zeros(self.W, bank.frames, bank.max_mix, device=bank.device)
+            self.w_frames[:, :, 0] = 1.0
         if not compact:
             self.windows, self.splicer, self.spk_ids, self.spk_w, self.pitch = bank.windows, bank.splicer, bank.spk_ids, bank.spk_w, bank.pitch
             if bank.enhancer is not None:
@@ -433,14 +440,25 @@ class _Rows:
             self.A = len(active)
             self.rows.copy_(torch.tensor(list(active) + [-1] * (self.W - self.A), dtype=torch.int32))
 
+    @property
+    def mix(self):
+        """The speaker term of this instance's synthesis (`spk_mix_rows=`): a mix per row, or per frame on a bank that glides."""
+        return self.spk_ids, (self.spk_w if self.w_frames is None else self.w_frames)
+
     def push(self, ctx, windows, blocks):
-        """`graphed.block_chain`'s push step: `windows` (this instance's) come up to date with `blocks` (W, block)."""
-        if self.rows is None:
-            return ctx.stream_push_(windows, blocks)
+        """`graphed.block_chain`'s push step: `windows` (this instance's) come up to date with `blocks` (W, block); on a bank
+        with `glide_breakpoints` the weights of the block's frames follow, and the clocks of the call's slots advance."""
         b = self.bank
-        return ctx.bank_gather_(self.rows, blocks, b.windows, windows, b.sola_buffer, self.splicer.buffer, (b.spk_ids, b.spk_w),
-                                (self.spk_ids, self.spk_w), b.pitch, self.pitch, None if self.request is None else b.enhancer_request,
-                                self.request)
+        if self.rows is None:
+            ctx.stream_push_(windows, blocks)
+        else:
+            ctx.bank_gather_(self.rows, blocks, b.windows, windows, b.sola_buffer, self.splicer.buffer, (b.spk_ids, b.spk_w),
+                             (self.spk_ids, self.spk_w), b.pitch, self.pitch, None if self.request is None else b.enhancer_request,
+                             self.request)
+        if self.w_frames is not None:
+            ctx.bank_glide_(self.rows, b.glide_clock, b.glide_n, b.glide_t, b.glide_w, b.spk_w, self.w_frames, b.n_in, b.block,
+                            b.hop_size)
+        return windows
 
     def scatter(self):
         if self.rows is not None:
@@ -498,7 +516,7 @@ class StreamBank:
     counting as one build as they do for the full width.  Rows A..W-1 are padding: a zero window, speaker 1 with weight 1, pitch 1
     and key request 0; they are computed, never written back to a slot and never returned.
     PAUSED SLOTS: a slot that a call does not name keeps its rows of `windows`, `sola_buffer`, `spk_ids`, `spk_w`, `pitch` and
-    `enhancer_request` bit for bit, and a caller that is named again carries on where it stopped; `reset(slot)` remains the way
+    `enhancer_request` (and of the glide state, below) bit for bit, and a caller that is named again carries on where it stopped; `reset(slot)` remains the way
     to hand a slot to someone new.  A call without `active` is the full-width call on its own graph, on a bank with
     `active_widths` too: there an idle slot is a slot that is fed zeros; its rows are computed like every other row, and its
     output is zero through the volume gate.  Every refusal of a call (`active` on a bank without `active_widths`, an empty,
@@ -522,18 +540,42 @@ class StreamBank:
     is captured at construction: `graph_builds` is the count above plus len(models) * len(model_widths), and a change of
     assignment captures nothing.  The paused-slot rule holds as it stands.
 
+    A voice that glides (`glide_breakpoints=P_max`, an int in 1..64; None: nothing of this is allocated, captured or launched,
+    and the bank is the bank above, bit for bit).  Every slot then has a clock and a speaker timeline on the device:
+    `glide_clock` (S,) int64, the device samples pushed into the slot since its timeline started; `glide_n` (S,) int32, its
+    breakpoint count, 0 = none; `glide_t` (S, P_max) int64, the breakpoint times in device samples; `glide_w` (S, P_max, K) their
+    weights.  `set_timeline(slot, timeline, at=0.0)` writes them from an `infer_offline.SpeakerTimeline`, time 0 being the first
+    sample pushed after the call.  Every push ends with one launch of `ddsp_bank_glide` over the call's rows: frame t of a window
+    has stream time clock + block - n_in + t * hop_size, its weights are the timeline interpolated there (the slot's `spk_w` row
+    where it has none, the padding speaker on a padding row), and the clocks of the call's slots advance by one block.  The
+    synthesis of every chain takes the per-frame pair (`spk_ids`, those weights) where it took (`spk_ids`, `spk_w`); a constant
+    mix renders to the same bits either way.  Under `push_audio` the launch is part of the captured block, so a glide is device
+    data like everything else: `graph_builds` is what it was, and setting, clearing or running a timeline captures nothing.
+    `set_speaker` ends a slot's glide, `reset` restarts its clock and keeps its timeline, `last_mix_w` (A, Fr, K) holds the
+    block's weights.  The paused-slot rule covers `glide_clock`, `glide_n`, `glide_t` and `glide_w`: a paused slot's voice stands
+    still and goes on from there when the slot is named again.  Refused: `glide_breakpoints` with `models=`; `set_timeline` on
+    a bank without `glide_breakpoints`, with more points than it, two points on one sample, more ids than `max_mix` or an id
+    outside the slot's model.
+
     Not in the bank: streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
-    grows after construction; a weight set per row inside the control network's kernels; an enhancer per model (DESIGN section
-    7)."""
+    grows after construction; a weight set per row inside the control network's kernels; an enhancer per model; a glide on a
+    bank with `models=`; a pitch timeline."""
 
     def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
-                 active_widths=None, models=None, model_widths=None):
+                 active_widths=None, models=None, model_widths=None, glide_breakpoints=None):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
             raise ValueError(f"StreamBank: n_streams must be at least 1, got {n_streams}")
+        if glide_breakpoints is not None:
+            if isinstance(glide_breakpoints, bool) or not isinstance(glide_breakpoints, int) or not 1 <= glide_breakpoints <= MAX_GLIDE_POINTS:
+                raise ValueError(f"StreamBank: glide_breakpoints must be an int in 1..{MAX_GLIDE_POINTS}, got {glide_breakpoints!r}")
+            if models is not None:
+                raise ValueError("StreamBank: glide_breakpoints= with models= is not supported (the per-model row gather moves a mix "
+                                 "per row, not per frame)")
+        self.glide_breakpoints = glide_breakpoints
         self.active_widths = None if active_widths is None else _check_active_widths(active_widths, self.S)
         if models is None and model_widths is not None:
             raise ValueError("StreamBank: model_widths= needs models=")
@@ -586,8 +628,15 @@ class StreamBank:
         self.spk_w = torch.zeros(self.S, self.max_mix, device=dev)
         self.spk_w[:, 0] = 1.0
         self.pitch = torch.ones(self.S, device=dev)
+        self.glide_clock = self.glide_n = self.glide_t = self.glide_w = None
+        if glide_breakpoints is not None:                            # a clock and a timeline per slot (`set_timeline`)
+            self.glide_clock = torch.zeros(self.S, dtype=torch.int64, device=dev)
+            self.glide_n = torch.zeros(self.S, dtype=torch.int32, device=dev)
+            self.glide_t = torch.zeros(self.S, glide_breakpoints, dtype=torch.int64, device=dev)
+            self.glide_w = torch.zeros(self.S, glide_breakpoints, self.max_mix, device=dev)
         self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
+        self.last_mix_w = None           # (A, Fr, max_mix): the block's per-frame weights on a bank with `glide_breakpoints`
         if enhancer is not None:
             self.enhancer_request = torch.full((self.S,), request, dtype=torch.int32, device=dev)   # -1 = 'auto', per slot
             self._n_end_by_key = torch.tensor(ends, dtype=torch.int32).to(dev)
@@ -625,10 +674,10 @@ class StreamBank:
         if self.f0_extractor is not None:
             rows.bank_graph = graphed.GraphedBlock(
                 self.model if shared else None, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
-                self.silence_front, rows.pitch, self.threshold_db, mix_rows=(rows.spk_ids, rows.spk_w),
-                f0_dither=self.f0_dither, push=rows.push)
+                self.silence_front, rows.pitch, self.threshold_db, mix_rows=rows.mix, f0_dither=self.f0_dither, push=rows.push,
+                keep=() if self.glide_clock is None else (self.glide_clock,))   # (the capture's runs advance the clocks)
         elif shared:
-            rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=(rows.spk_ids, rows.spk_w))
+            rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix)
         if self.enhancer is not None:
             rows.enhancer_graph = graphed.GraphedBankEnhancer(
                 self.enhancer, self.enhancer_plan, rows.W, rows.request, self.model_sr, self.block_size, self.samplerate,
@@ -689,6 +738,51 @@ class StreamBank:
     def _write_mix(self, slot, ids, w):
         self.spk_ids[slot].copy_(ids[0])
         self.spk_w[slot].copy_(w[0])
+        if self.glide_n is not None:                                 # a plain speaker ends a glide
+            self.glide_n[slot:slot + 1].zero_()
+
+    def set_timeline(self, slot, timeline, at=0.0):
+        """Slot `slot` glides along `timeline` (an `infer_offline.SpeakerTimeline`) from the next block on, in STREAM time: time 0
+        is the first sample pushed after this call, or `at` seconds into the timeline with `at=`.  Breakpoint n sits at
+        int(round(seconds * samplerate)) device samples.  Frames of the window that are older than time 0 hold the first
+        breakpoint's weights, frames behind the last breakpoint its weights.  Writes the slot's `spk_ids` row (the timeline's `ids`,
+        padded with id 1), its rows of `glide_t` / `glide_w`, `glide_n` and `glide_clock`: device rows only, no capture.
+        ValueError, before any write: a bank built without `glide_breakpoints`, more points than it, two points on one sample,
+        more ids than `max_mix`, an id outside [1, n_spk] of the slot's model."""
+        from infer_offline import SpeakerTimeline
+        if self.glide_breakpoints is None:
+            raise ValueError("StreamBank.set_timeline: this bank was built without glide_breakpoints=")
+        slot = self._slot(slot)
+        if not isinstance(timeline, SpeakerTimeline):
+            raise ValueError(f"StreamBank.set_timeline: timeline must be an infer_offline.SpeakerTimeline, got {type(timeline).__name__}")
+        if isinstance(at, bool) or not isinstance(at, (int, float)) or at != at or abs(at) == float("inf"):
+            raise ValueError(f"StreamBank.set_timeline: at must be a finite number of seconds, got {at!r}")
+        times = [int(round(t * self.samplerate)) for t, _ in timeline.points]
+        if len(times) > self.glide_breakpoints:
+            raise ValueError(f"StreamBank.set_timeline: {len(times)} points, the bank holds glide_breakpoints = {self.glide_breakpoints} "
+                             f"per slot")
+        for n in range(1, len(times)):
+            if times[n] <= times[n - 1]:
+                raise ValueError(f"StreamBank.set_timeline: points {n - 1} and {n} ({timeline.points[n - 1][0]} s, "
+                                 f"{timeline.points[n][0]} s) both land on sample {times[n]} at {self.samplerate} Hz")
+        ids = list(timeline.ids)
+        if len(ids) > self.max_mix:
+            raise ValueError(f"StreamBank.set_timeline: the timeline names {len(ids)} ids, a mix holds max_mix = {self.max_mix}")
+        n_spk = int(self.models[self.model_of_slot[slot]].unit2ctrl.n_spk)
+        if any(not 1 <= i <= n_spk for i in ids):
+            raise ValueError(f"StreamBank.set_timeline: speaker ids must be in [1, {n_spk}], got {sorted(ids)}")
+        P, K = self.glide_breakpoints, self.max_mix
+        row_ids = torch.tensor(ids + [1] * (K - len(ids)), dtype=torch.int32)
+        row_t = torch.tensor(times + [0] * (P - len(times)), dtype=torch.int64)
+        row_w = torch.zeros(P, K)
+        for n, (_, mix) in enumerate(timeline.points):
+            for k, i in enumerate(ids):
+                row_w[n, k] = mix.get(i, 0.0)
+        self.spk_ids[slot].copy_(row_ids)
+        self.glide_t[slot].copy_(row_t)
+        self.glide_w[slot].copy_(row_w)
+        self.glide_n[slot:slot + 1].fill_(len(times))
+        self.glide_clock[slot:slot + 1].fill_(int(round(at * self.samplerate)))
 
     def set_model(self, slot, k, spk_id=1, spk_mix_dict=None):
         """Slot `slot` is rendered by `models[k]` from the next block on, as speaker `spk_id` of that model or as `spk_mix_dict`
@@ -717,10 +811,13 @@ class StreamBank:
         self.enhancer_request[slot:slot + 1].fill_(request)
 
     def reset(self, slot):
-        """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set)."""
+        """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set).  On
+        a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
+        if self.glide_clock is not None:
+            self.glide_clock[slot:slot + 1].zero_()
 
     def _check_blocks(self, blocks, A, rows="S"):
         if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
@@ -797,11 +894,13 @@ class StreamBank:
             sig, f0, units, volume = graphed.block_chain(
                 hipddsp.context_for(self.device), self.model if self._model_rows is None else None, self.units_encoder,
                 self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch,
-                self.threshold_db, self.hop, {"spk_id": None, "spk_mix_rows": (rows.spk_ids, rows.spk_w)}, noise, self.f0_dither,
+                self.threshold_db, self.hop, {"spk_id": None, "spk_mix_rows": rows.mix}, noise, self.f0_dither,
                 push=rows.push)
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
+        if rows.w_frames is not None:
+            self.last_mix_w, = rows.real(rows.w_frames)
         self.last_active = active
         return self._splice(rows, sig, f0, rand_ini)
 
@@ -834,8 +933,10 @@ class StreamBank:
                 sig = rows.graph(units, f0, volume, None, noise=noise)[0]
             else:
                 kw = {} if noise is None else {"noise": noise}
-                sig = self.model(units, f0, volume, None, spk_mix_rows=(rows.spk_ids, rows.spk_w), **kw)[0]
+                sig = self.model(units, f0, volume, None, spk_mix_rows=rows.mix, **kw)[0]
             ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
+        if rows.w_frames is not None:
+            self.last_mix_w, = rows.real(rows.w_frames)
         self.last_active = active
         return self._splice(rows, sig, f0, rand_ini)

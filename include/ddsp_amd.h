@@ -440,6 +440,27 @@ int ddsp_bank_gather(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, in
 int ddsp_bank_scatter(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, const float* csola, int xfade,
                       float* sola_buffer);
 
+/* The speaker glide of a bank (realtime.StreamBank, `glide_breakpoints=`): the per-frame mix weights of one call's W rows
+ * (ddsp_unit2ctrl_fwd_framemix's w) from per-SLOT state, and the advance of those slots' clocks, one launch per block.  Per slot
+ * s < S, all DEVICE: clock[s] int64, the device samples pushed into the slot since its timeline started (read AND written);
+ * bp_n[s] int32, its breakpoint count, clamped to [0, P_max], 0 = no timeline; bp_t[s] (P_max) int64, the breakpoint times in
+ * device samples, strictly increasing; bp_w[s] (P_max, K) fp32, the weights there; spk_w[s] (K) fp32, the slot's row mix.
+ * rows (W) int32 DEVICE as for ddsp_bank_gather, or NULL: row r is slot r.  Row r belongs to slot s = rows ? rows[r] : r, tested
+ * against [0, S) before it forms an address.  An s outside is a padding row: every frame gets (1, 0, ..., 0), no clock is read
+ * or written and no error word is set.  For a real row c = clock[s] + block is the stream position just behind the window's
+ * newest sample, and frame t < Fr of the window (n_in samples, frames `hop` samples apart, hop possibly fractional) has time
+ * tau = (double)(c - n_in) + t * hop.  With bp_n[s] == 0 every frame gets spk_w[s].  With a timeline the weights are its
+ * breakpoints interpolated at tau as ddsp_mix_timeline interpolates: the first breakpoint's before it, the last one's after it,
+ * between two w0 + (w1 - w0) * ((tau - t0) / (t1 - t0)) in fp64, rounded to fp32 (at a breakpoint exactly its fp32 value).
+ * Then clock[s] = c: one workgroup per row reads the clock in every thread, meets behind its last frame and stores once.  No
+ * slot may be named twice (the caller checks it: two rows would race for the clock).  PAUSED SLOTS: a slot that `rows` does not
+ * name has no address of clock, bp_n, bp_t, bp_w or spk_w formed for it.  w_frames (W, Fr, K) fp32.  DDSP_ERR_ARG, and nothing
+ * written, for a null pointer (rows excepted), W > 65535, K outside [1, 16], P_max outside [1, 64], Fr < 1 or block < 1.  Does not
+ * synchronise, allocate or read back. */
+int ddsp_bank_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, int64_t* clock, const int32_t* bp_n,
+                    const int64_t* bp_t, const float* bp_w, int P_max, const float* spk_w, int K, int64_t Fr, int64_t n_in,
+                    int64_t block, double hop, float* w_frames);
+
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
  * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)

@@ -34,7 +34,15 @@ Cases with S < M are left out; `--streams` picks the S to run; every row carries
 `--active`.
 
     python tools/rt_bank_time.py --baseline-tree <parent checkout> --models 4 --streams 16 --shapes config5
-                                 [--out profiles/rt_bank_models_time.json]"""
+                                 [--out profiles/rt_bank_models_time.json]
+
+`--glide` times what a voice that glides costs a bank: three legs, all banks, alternating as above - `parent`, the bank of the
+baseline tree; `plain`, the bank of this tree built without `glide_breakpoints` (the same launches as the parent's: a difference
+beyond the session's run-to-run spread is a finding); `glide`, the bank of this tree with `glide_breakpoints=4` and a timeline on
+every slot that ramps through the whole run (one more launch per block, and the per-frame weights in the prenet's epilogue).
+
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> --glide --streams 16 --shapes config5
+                                 [--out profiles/rt_bank_glide_time.json]"""
 import argparse
 import contextlib
 import json
@@ -56,7 +64,8 @@ SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16
 
 
 def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), active=None, models=None, streams=STREAMS):
-    """One leg in this process: `which` = 'bank' | 'solo' | 'plain', the package taken from `tree`.  Prints one JSON row per case."""
+    """One leg in this process: `which` = 'bank' | 'solo' | 'plain' | 'parent' | 'glide', the package taken from `tree`.  Prints one
+    JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import numpy as np
@@ -103,14 +112,22 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
             if with_enhancer:
                 kw.update(enhancer=enh, enhancer_adaptive_key="auto")
             with contextlib.redirect_stdout(sys.stderr):
-                if which in ("bank", "plain"):
+                if which != "solo":
                     if active is not None:
                         kw.update(active_widths=(A,))
                     if models is not None and which == "bank":
                         kw.update(models=pool)
+                    if which == "glide":
+                        kw.update(glide_breakpoints=4)
                     bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
                     for s in range(S if "models" in kw else 0):
                         bank.set_model(s, s % len(pool))
+                    if which == "glide":    # every slot ramps between two voices for the whole run, each at its own pace
+                        from infer_offline import SpeakerTimeline
+                        span = (warmup + blocks) * block_time
+                        for s in range(S):
+                            at = [span * n / (3 + s % 3) for n in range(4)]
+                            bank.set_timeline(s, SpeakerTimeline([(t, {1 + s % 7: 1.0 - n % 2, 8 + s % 5: float(n % 2)}) for n, t in enumerate(at)]))
                     block, frames = bank.block, bank.frames
                     push = bank.push_audio if active is None else (lambda blocks: bank.push_audio(blocks, active=slots))
                 else:
@@ -159,7 +176,8 @@ def main():
     ap.add_argument("--active", type=int, default=None, help="time banks of S slots with this many active rows (S >= A only)")
     ap.add_argument("--models", type=int, default=None, help="deal the S slots round-robin over this many distinct models (S >= M only)")
     ap.add_argument("--streams", type=int, nargs="+", default=list(STREAMS), help="the stream counts S to run")
-    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain"], help=argparse.SUPPRESS)
+    ap.add_argument("--glide", action="store_true", help="three bank legs: the parent's, this tree's without and with a glide on every slot")
+    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain", "parent", "glide"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
@@ -168,8 +186,10 @@ def main():
         a.baseline_tree = ROOT
     if not a.baseline_tree or not os.path.isdir(os.path.join(a.baseline_tree, "ddsp-svc-official_amd")):
         raise SystemExit("rt_bank_time: --baseline-tree must be a checkout of the parent commit (with ddsp-svc-official_amd/)")
-    trees = {"bank": ROOT, "plain": ROOT, "solo": os.path.abspath(a.baseline_tree)}
-    legs = ("bank", "solo", "plain") if a.models == 1 else ("bank", "solo")
+    if a.glide and (a.models or a.enhancer):
+        raise SystemExit("rt_bank_time: --glide does not combine with --models (such a bank refuses a glide) or --enhancer")
+    trees = {"bank": ROOT, "plain": ROOT, "glide": ROOT, "solo": os.path.abspath(a.baseline_tree), "parent": os.path.abspath(a.baseline_tree)}
+    legs = ("parent", "plain", "glide") if a.glide else ("bank", "solo", "plain") if a.models == 1 else ("bank", "solo")
     repeats = []
     for rep in range(a.repeats):
         for which in legs:
@@ -192,8 +212,18 @@ def main():
             if (a.active is not None and S < a.active) or (a.models is not None and S < a.models):
                 continue
             pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
-            bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
             med = lambda v: sorted(v)[len(v) // 2]
+            if a.glide:   # three banks: every repeat's mean, each leg's median and spread, and the two differences of the medians
+                case = {"shape": shape, "streams": S}
+                for which in legs:
+                    m = pick(which, "mean_ms")
+                    case.update({f"{which}_mean_ms": m, f"{which}_p99_ms": pick(which, "p99_ms"), f"{which}_median_ms": med(m),
+                                 f"{which}_spread_ms": max(m) - min(m)})
+                case.update(plain_minus_parent_ms=case["plain_median_ms"] - case["parent_median_ms"],
+                            glide_minus_plain_ms=case["glide_median_ms"] - case["plain_median_ms"])
+                cases.append(case)
+                continue
+            bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
             cases.append({"shape": shape, "streams": S, "bank_mean_ms": bm, "solo_mean_ms": sm, "bank_p99_ms": pick("bank", "p99_ms"),
                           "solo_p99_ms": pick("solo", "p99_ms"), "bank_spread_ms": max(bm) - min(bm),
                           "solo_spread_ms": max(sm) - min(sm), "bank_median_ms": med(bm), "solo_median_ms": med(sm),
@@ -201,13 +231,21 @@ def main():
             if "plain" in legs:   # the single-model bank of this tree beside the one-model bank through the per-model path
                 pm = pick("plain", "mean_ms")
                 cases[-1].update(plain_mean_ms=pm, plain_median_ms=med(pm), plain_spread_ms=max(pm) - min(pm))
-    out = {**({} if a.active is None else {"active": a.active}), **({} if a.models is None else {"models": a.models}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks, "warmup": a.warmup, "repeats": a.repeats,
-           "what": "ms per block period for all S streams: bank = one StreamBank.push_audio; solo = S StreamRenderer.push_audio "
-                   "of the baseline tree one after the other", "cases": cases, "rows": repeats}
+    what = "ms per block period for all S streams: bank = one StreamBank.push_audio; solo = S StreamRenderer.push_audio of the " \
+           "baseline tree one after the other"
+    if a.glide:
+        what = "ms per block period of one StreamBank.push_audio for all S streams: parent = the baseline tree's bank; plain = this " \
+               "tree's bank without glide_breakpoints; glide = this tree's bank with glide_breakpoints=4 and a timeline on every slot"
+    out = {**({} if a.active is None else {"active": a.active}), **({} if a.models is None else {"models": a.models}),
+           **({"glide": True} if a.glide else {}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks,
+           "warmup": a.warmup, "repeats": a.repeats, "what": what, "cases": cases, "rows": repeats}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
-    for c in cases:
+    for c in cases if a.glide else ():
+        print(f"{c['shape']:8s} S={c['streams']:2d}: " + ", ".join(f"{w} {c[w + '_median_ms']:.3f} ms (spread {c[w + '_spread_ms']:.3f})" for w in legs) +
+              f"; plain - parent {c['plain_minus_parent_ms']:+.3f} ms, glide - plain {c['glide_minus_plain_ms']:+.3f} ms")
+    for c in () if a.glide else cases:
         print(f"{c['shape']:8s} S={c['streams']:2d}: bank {c['bank_median_ms']:8.3f} ms (spread {c['bank_spread_ms']:.3f}), "
               f"solo x S {c['solo_median_ms']:8.3f} ms (spread {c['solo_spread_ms']:.3f}), ratio {c['solo_over_bank']:.2f}")
 
