@@ -1,4 +1,8 @@
-// HuBERT-Soft units encoder (reference encoder/hubert/model.py `HubertSoft.units`, ddsp/vocoder.py:140-229) on gfx950.
+// HuBERT units encoders on gfx950: HuBERT-Soft (reference encoder/hubert/model.py `HubertSoft.units`, ddsp/vocoder.py:140-229)
+// and the HuBERT-base form of fairseq (`extract_features(..., output_layer=n)` with or without `final_proj`: the reference's
+// ContentVec / HuBERT-base classes, ddsp/vocoder.py:231-332).  One network, one body (hubert_run); the base form differs in
+// three run-time choices: no input padding, the number of transformer layers, and its attention projections, which arrive
+// as three matrices per layer and are packed into the QKV operand with the other prepared weights.
 //
 // Activations are frame-major (frames x channels) fp32 throughout.  Every contraction but conv0 and the attention is a call of
 // the library's GEMM (gemm_f32.h) in the context's product arithmetic:
@@ -26,7 +30,7 @@ constexpr int POS_K = 128, POS_G = 16, POS_C = 48;   // positional conv: taps, g
 constexpr int POS_KK = POS_K * POS_C;                // its GEMM K
 constexpr int GN_PARTS = 1024;                       // frame ranges of the GroupNorm statistics (blocks of conv0_kernel per utterance)
 constexpr int CONV_TAPS[6] = {3, 3, 3, 3, 2, 2};
-constexpr int HPAD = 40;                             // (400 - 320) / 2 zeros on each side of the audio
+constexpr int HPAD = 40;                             // HuBERT-Soft: (400 - 320) / 2 zeros on each side of the audio (the base form: 0)
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
@@ -69,14 +73,14 @@ struct EpiPos {
 // cnt[b][0] = the row's own samples (held inside 0..T), cnt[b][1..7] = the frames after conv0 and after each strided
 // convolution (frames_of on the device; a row too short for the stack, which the caller refuses, counts 0 from there on)
 constexpr int HCNT = 8;
-__global__ void hub_counts_kernel(const int32_t* __restrict__ n_samples, int64_t B, int64_t T, int32_t* __restrict__ cnt) {
+__global__ void hub_counts_kernel(const int32_t* __restrict__ n_samples, int64_t B, int64_t T, int pad, int32_t* __restrict__ cnt) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     int64_t n = n_samples[b];
     n = n < 0 ? 0 : (n > T ? T : n);
     int32_t* c = cnt + b * HCNT;
     c[0] = (int32_t)n;
-    int64_t f = (n + 2 * HPAD - 10) / 5 + 1;   // n >= 0: at least 15
+    int64_t f = n + 2 * pad < 10 ? 0 : (n + 2 * pad - 10) / 5 + 1;   // (pad 40: at least 15)
     c[1] = (int32_t)f;
     for (int i = 0; i < 6; ++i) {
         const int kt = i < 4 ? 3 : 2;
@@ -89,14 +93,15 @@ __global__ void hub_counts_kernel(const int32_t* __restrict__ n_samples, int64_t
 // grid (GN_PARTS, B), block 512 = one channel per thread; the block walks frames [T0*p/P, T0*(p+1)/P) and writes the
 // fp64 sum and sum of squares of its channel over them (reduced in a fixed order by gn_finalize_kernel)
 // RAGGED (cnt != nullptr): samples past the row's own n_b are SELECTED as 0 (the padding may hold NaN), so the 40 zeros
-// a solo call pads with fall out of the same bounds test; the block walks the row's own t0_b frames partitioned as a solo
+// a solo call pads with fall out of the same bounds test (`pad` zeros on each side, uniform over the launch: 40, or 0 for
+// the base form, where only the row's end is selected); the block walks the row's own t0_b frames partitioned as a solo
 // call partitions them (the fp64 sums then add in the same order, empty partitions included).  Frames t0_b..T0-1 of the
 // padded buffer, which no frame of the row ever reads, are written by the blocks' second loop so that everything
 // downstream of them is finite; they stay out of the statistics.
 template <bool RAGGED>
 __global__ void __launch_bounds__(512) conv0_kernel(const float* __restrict__ wav, int64_t T, const float* __restrict__ w0,
                                                     float* __restrict__ y, int64_t T0, double* __restrict__ part,
-                                                    const int32_t* __restrict__ cnt) {
+                                                    const int32_t* __restrict__ cnt, int pad) {
     const int b = blockIdx.y, p = blockIdx.x, c = threadIdx.x;
     float w[10];
 #pragma unroll
@@ -110,7 +115,7 @@ __global__ void __launch_bounds__(512) conv0_kernel(const float* __restrict__ wa
         float acc = 0.f;
 #pragma unroll
         for (int t = 0; t < 10; ++t) {
-            const int64_t i = f * 5 + t - HPAD;
+            const int64_t i = f * 5 + t - pad;
             const float xv = (i >= 0 && i < n) ? x[i] : 0.f;
             acc = fmaf(w[t], xv, acc);
         }
@@ -264,6 +269,24 @@ __global__ void __launch_bounds__(256) pos_weight_kernel(const float* __restrict
         const int kk = (int)(i % POS_KK), t = kk / POS_C, ci = kk % POS_C;
         out[i] = v[(co * POS_C + ci) * POS_K + t] * scale[t];
     }
+}
+
+// fairseq keeps the attention's input projections apart: q_proj, k_proj, v_proj (768, 768) with a bias each.  The QKV GEMM reads
+// one (2304, 768) operand and one (2304) bias per layer: rows q, then k, then v, as nn.MultiheadAttention's in_proj.
+// p[layer] = {q_w, k_w, v_w, q_b, k_b, v_b}.  grid (blocks, 12), a copy.
+struct HubQkv {
+    const float* p[12][6];
+};
+__global__ void __launch_bounds__(256) qkv_pack_kernel(HubQkv s, float* __restrict__ wout, float* __restrict__ bout) {
+    const int ly = blockIdx.y;
+    constexpr int NW = HD * HD;
+    float* w = wout + (int64_t)ly * 3 * NW;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < 3 * NW; i += gridDim.x * 256) {
+        const int part = i / NW;
+        w[i] = s.p[ly][part][i - part * NW];
+    }
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < 3 * HD; i += 256) bout[ly * 3 * HD + i] = s.p[ly][3 + i / HD][i % HD];
 }
 
 // ---- softmax attention (flash form: online softmax, no L x L matrix) ---------------------------------------------
@@ -450,9 +473,9 @@ void hub_gemm(hipStream_t st, int math, const float* A, int64_t lda, int64_t sA,
     gemm::launch<true, true, gemm::A_PLAIN>(st, g, batch, e);
 }
 
-int64_t frames_of(int64_t T, int64_t (&t)[7]) {
+int64_t frames_of(int64_t T, int64_t (&t)[7], int pad) {
     if (T < 0) return -1;
-    int64_t n = T + 2 * HPAD;
+    int64_t n = T + 2 * pad;
     if (n < 10) return 0;
     n = (n - 10) / 5 + 1;
     t[0] = n;
@@ -469,16 +492,22 @@ struct HubPlan {
     size_t off[16];
     size_t total;
 };
-enum { S_Y0, S_Y1, S_PART, S_AFF, S_Z, S_X, S_Y, S_QKV, S_CTX, S_H, S_XG, S_WCONV, S_WPOS, S_PSCALE, S_CNT, S_N };
+enum { S_Y0, S_Y1, S_PART, S_AFF, S_Z, S_X, S_Y, S_QKV, S_CTX, S_H, S_XG, S_WCONV, S_WPOS, S_PSCALE, S_CNT, S_WQKV, S_BQKV, S_N };
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// bytes of the prepared weights: the six repacked conv matrices, the folded positional weights, the tap scales
+// bytes of the prepared weights: the six repacked conv matrices, the folded positional weights, the tap scales and, for the
+// base form, the packed QKV operands and biases of the 12 layers behind them
 size_t wconv_floats() { return (size_t)HC * HC * (3 * 4 + 2 * 2); }
 size_t wpos_floats() { return (size_t)HD * POS_KK; }
-size_t prep_bytes() { return align256(wconv_floats() * 4) + align256(wpos_floats() * 4) + align256(POS_K * 4); }
+size_t wqkv_floats() { return (size_t)12 * 3 * HD * HD; }
+size_t bqkv_floats() { return (size_t)12 * 3 * HD; }
+size_t prep_bytes(bool base) {
+    return align256(wconv_floats() * 4) + align256(wpos_floats() * 4) + align256(POS_K * 4) +
+           (base ? align256(wqkv_floats() * 4) + align256(bqkv_floats() * 4) : 0);
+}
 
-HubPlan plan(int64_t B, const int64_t (&t)[7]) {
+HubPlan plan(int64_t B, const int64_t (&t)[7], bool base) {
     const int64_t L = t[6];
     size_t sz[S_N];
     sz[S_Y0] = (size_t)B * t[0] * HC * 4;
@@ -496,6 +525,8 @@ HubPlan plan(int64_t B, const int64_t (&t)[7]) {
     sz[S_WPOS] = wpos_floats() * 4;
     sz[S_PSCALE] = POS_K * 4;
     sz[S_CNT] = (size_t)B * HCNT * 4;
+    sz[S_WQKV] = base ? wqkv_floats() * 4 : 0;
+    sz[S_BQKV] = base ? bqkv_floats() * 4 : 0;
     HubPlan p;
     size_t o = 0;
     for (int i = 0; i < S_N; ++i) {
@@ -506,7 +537,8 @@ HubPlan plan(int64_t B, const int64_t (&t)[7]) {
     return p;
 }
 
-int prepare_weights(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights& w, float* wconv, float* wpos, float* pscale) {
+int prepare_weights(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights& w, float* wconv, float* wpos, float* pscale,
+                    const HubQkv* qkv, float* wqkv, float* bqkv) {
     size_t o = 0;
     for (int i = 0; i < 6; ++i) {
         const int64_t n = (int64_t)HC * HC * CONV_TAPS[i];
@@ -516,47 +548,61 @@ int prepare_weights(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights& w,
     }
     hipLaunchKernelGGL(pos_norm_kernel, dim3(POS_K), dim3(256), 0, st, w.pos_v, w.pos_g, pscale);
     hipLaunchKernelGGL(pos_weight_kernel, dim3(4096), dim3(256), 0, st, w.pos_v, pscale, wpos);
+    if (qkv) hipLaunchKernelGGL(qkv_pack_kernel, dim3(512, 12), dim3(256), 0, st, *qkv, wqkv, bqkv);
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
 
-bool weights_complete(const ddsp_hubert_weights& w) {
+// every pointer in front of `version` is set (both weight structs are pointers up to there)
+template <class W>
+bool weights_complete(const W& w) {
     const float* const* p = (const float* const*)&w;
-    const size_t n = offsetof(ddsp_hubert_weights, version) / sizeof(const float*);
+    const size_t n = offsetof(W, version) / sizeof(const float*);
     for (size_t i = 0; i < n; ++i)
         if (!p[i]) return false;
     return true;
 }
 
-// stop: -1 = conv stack output (B, Fr, 512); 0..12 = hidden state after that many transformer layers (B, Fr, 768);
-// 13 = units (B, Fr, 256).  n_samples: nullptr, or the DEVICE array of a ragged batch's B sample counts (never read back:
-// the per-row frame counts are derived on the device); the launches are the rectangular call's plus the counts kernel and
-// the final crop, over the padded shapes.
-int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, const float* wav, int64_t B, int64_t T, int stop,
-               float* out, const int32_t* n_samples = nullptr) {
-    // ("ddsp_hubert" / "ddsp_hubert_ragged": the family of entry points that was called)
-#define HUB_MSG(text) (n_samples ? "ddsp_hubert_ragged: " text : "ddsp_hubert: " text)
-    DDSP_REQUIRE(ctx, ctx && wp && wav && out, HUB_MSG("null argument"));
-    DDSP_REQUIRE(ctx, weights_complete(*wp), HUB_MSG("a weight pointer is null"));
-    DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && stop >= -1 && stop <= 13, HUB_MSG("bad shape or layer"));
+// What differs between the two forms of the network.  `key`: the caller's struct, whose bytes in front of its version name
+// the prepared weights in the context's slot.  `qkv`: nullptr (HuBERT-Soft: `w` holds in_proj) or the base form's separate
+// projections, which prepare_weights packs; hubert_run then points in_proj of its copy of `w` at the packed operands.
+struct HubForm {
+    int pad;
+    const void* key;
+    size_t key_bytes;
+    const HubQkv* qkv;
+};
+
+// nl transformer layers (0..12), then `tail`.  n_samples: nullptr, or the DEVICE array of a ragged batch's B sample counts
+// (never read back: the per-row frame counts are derived on the device); the launches are the rectangular call's plus the
+// counts kernel and the final crop, over the padded shapes.
+enum { TAIL_CONV, TAIL_HIDDEN, TAIL_UNITS };   // conv stack output (B, Fr, 512) | hidden state (B, Fr, 768) | its projection (B, Fr, 256)
+int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights& w0, const HubForm& form, const float* wav, int64_t B,
+               int64_t T, int nl, int tail, float* out, const int32_t* n_samples) {
+    // ("ddsp_hubert" / "ddsp_hubert_ragged" / "ddsp_hubert_base": the family of entry points that was called)
+    const bool is_base = form.qkv != nullptr;
+#define HUB_MSG(text) (is_base ? "ddsp_hubert_base: " text : n_samples ? "ddsp_hubert_ragged: " text : "ddsp_hubert: " text)
+    DDSP_REQUIRE(ctx, wav && out, HUB_MSG("null argument"));
+    DDSP_REQUIRE(ctx, B >= 1 && T >= 0 && nl >= 0 && nl <= 12, HUB_MSG("bad shape or layer"));
     // the final crop of a ragged batch moves 16 bytes at a time
-    DDSP_REQUIRE(ctx, !n_samples || ((uintptr_t)out % 16) == 0, "ddsp_hubert_ragged: the output must be 16-byte aligned");
+    DDSP_REQUIRE(ctx, !n_samples || ((uintptr_t)out % 16) == 0, HUB_MSG("the output of a ragged batch must be 16-byte aligned"));
     int64_t t[7];
-    const int64_t Fr = frames_of(T, t);
-    DDSP_REQUIRE(ctx, Fr >= 1, HUB_MSG("audio too short for the conv stack (ddsp_hubert_frames(T) == 0)"));
+    const int64_t Fr = frames_of(T, t, form.pad);
+    DDSP_REQUIRE(ctx, Fr >= 1, HUB_MSG("audio too short for the conv stack (its frame rule gives 0)"));
     DDSP_REQUIRE(ctx, B * t[0] < ((int64_t)1 << 31) && B * Fr * HFF < ((int64_t)1 << 31), HUB_MSG("input too long"));
 #undef HUB_MSG
-    const ddsp_hubert_weights w = *wp;
+    ddsp_hubert_weights w = w0;
     DDSP_ENTER_DEVICE(ctx);
     const int L = (int)Fr;
     const int64_t rows = B * Fr;
     const int math = ctx->math;
+    const int pad = form.pad;
 
     // prepared weights: the context's slot (state bit 0: prepared), else scratch
     const float *wconv = nullptr, *wpos = nullptr;
+    float *wqkv = nullptr, *bqkv = nullptr;
     ddsp_weight_slot* slot;
-    int rc = ddsp_weight_slot_take(ctx, st, ctx->hubert_slot, &w, offsetof(ddsp_hubert_weights, version), w.version, prep_bytes(),
-                                   &slot, true);
+    int rc = ddsp_weight_slot_take(ctx, st, ctx->hubert_slot, form.key, form.key_bytes, w.version, prep_bytes(is_base), &slot, true);
     if (rc) return rc;
     const bool cached = slot != nullptr;
     if (cached) {
@@ -564,13 +610,17 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
         wconv = (const float*)base;
         wpos = (const float*)(base + align256(wconv_floats() * 4));
         float* pscale = (float*)(base + align256(wconv_floats() * 4) + align256(wpos_floats() * 4));
+        if (is_base) {
+            wqkv = pscale + align256(POS_K * 4) / 4;
+            bqkv = wqkv + align256(wqkv_floats() * 4) / 4;
+        }
         if (!(slot->state & 1)) {
-            if ((rc = prepare_weights(ctx, st, w, (float*)wconv, (float*)wpos, pscale))) return rc;
+            if ((rc = prepare_weights(ctx, st, w, (float*)wconv, (float*)wpos, pscale, form.qkv, wqkv, bqkv))) return rc;
             slot->state = 1;
         }
     }
     // (the arena always has room for the prepared weights: a capture after cached warm-up calls must not have to grow it)
-    const HubPlan p = plan(B, t);
+    const HubPlan p = plan(B, t, is_base);
     rc = ddsp_scratch_reserve_bytes(ctx, p.total + 4096);
     if (rc) return rc;
     ddsp_scratch_reset(ctx);
@@ -581,8 +631,15 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     if (!cached) {
         wconv = buf(S_WCONV);
         wpos = buf(S_WPOS);
-        if ((rc = prepare_weights(ctx, st, w, buf(S_WCONV), buf(S_WPOS), buf(S_PSCALE)))) return rc;
+        wqkv = buf(S_WQKV);
+        bqkv = buf(S_BQKV);
+        if ((rc = prepare_weights(ctx, st, w, buf(S_WCONV), buf(S_WPOS), buf(S_PSCALE), form.qkv, wqkv, bqkv))) return rc;
     }
+    if (is_base)
+        for (int li = 0; li < 12; ++li) {
+            w.layer[li].in_proj_w = wqkv + (size_t)li * 3 * HD * HD;
+            w.layer[li].in_proj_b = bqkv + (size_t)li * 3 * HD;
+        }
 
     // ---- feature extractor ----
     float* y0 = buf(S_Y0);
@@ -590,12 +647,12 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     const bool ragged = n_samples != nullptr;
     int32_t* cnt = ragged ? (int32_t*)buf(S_CNT) : nullptr;
     if (ragged) {
-        hipLaunchKernelGGL(hub_counts_kernel, dim3((unsigned)ceil_div64(B, 256)), dim3(256), 0, st, n_samples, B, T, cnt);
+        hipLaunchKernelGGL(hub_counts_kernel, dim3((unsigned)ceil_div64(B, 256)), dim3(256), 0, st, n_samples, B, T, pad, cnt);
         hipLaunchKernelGGL(conv0_kernel<true>, dim3(GN_PARTS, (unsigned)B), dim3(512), 0, st, wav, T, w.conv0_w, y0, t[0],
-                           (double*)buf(S_PART), (const int32_t*)cnt);
+                           (double*)buf(S_PART), (const int32_t*)cnt, pad);
     } else {
         hipLaunchKernelGGL(conv0_kernel<false>, dim3(GN_PARTS, (unsigned)B), dim3(512), 0, st, wav, T, w.conv0_w, y0, t[0],
-                           (double*)buf(S_PART), (const int32_t*)nullptr);
+                           (double*)buf(S_PART), (const int32_t*)nullptr, pad);
     }
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(HC / 64, (unsigned)B), dim3(1024), 0, st, (const double*)buf(S_PART), t[0], w.norm0_w, w.norm0_b,
                        buf(S_AFF), (const int32_t*)cnt);
@@ -625,7 +682,7 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
         hipLaunchKernelGGL(hub_crop_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, st, src, out,
                            Fr, C / 4, n4, (const int32_t*)cnt);
     };
-    if (stop == -1) {
+    if (tail == TAIL_CONV) {
         if (ragged)
             crop(cur, HC);
         else
@@ -652,7 +709,6 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
     float* qkv = buf(S_QKV);
     float* cx = buf(S_CTX);
     float* hh = buf(S_H);
-    const int nl = stop >= 12 ? 12 : stop;
     for (int li = 0; li < nl; ++li) {
         const ddsp_hubert_layer& ly = w.layer[li];
         hub_gemm(st, math, X, HD, 0, ly.in_proj_w, HD, 0, (int)rows, 3 * HD, HD, 1, 1, gemm::EpiStore{qkv, 3 * HD, ly.in_proj_b, 1, 0, 0});
@@ -670,7 +726,7 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
         hub_gemm(st, math, hh, HFF, 0, ly.linear2_w, HFF, 0, (int)rows, HD, HFF, 1, 1, gemm::EpiResidual{Y, X, HD, ly.linear2_b});
         hipLaunchKernelGGL(layernorm_kernel<HD>, dim3(ln_grid), dim3(256), 0, st, Y, nullptr, ly.norm2_w, ly.norm2_b, X, rows);
     }
-    if (stop <= 12) {
+    if (tail == TAIL_HIDDEN) {
         if (ragged)
             crop(X, HD);
         else
@@ -687,19 +743,65 @@ int hubert_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* wp, con
 
 extern "C" int64_t ddsp_hubert_frames(int64_t T) {
     int64_t t[7];
-    return frames_of(T, t);
+    return frames_of(T, t, HPAD);
 }
+
+extern "C" int64_t ddsp_hubert_base_frames(int64_t T) {
+    int64_t t[7];
+    return frames_of(T, t, 0);
+}
+
+namespace {
+int hubert_soft_run(ddsp_ctx* ctx, hipStream_t st, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T, int nl,
+                    int tail, float* out, const int32_t* n_samples) {
+    DDSP_REQUIRE(ctx, ctx && w, n_samples ? "ddsp_hubert_ragged: null argument" : "ddsp_hubert: null argument");
+    DDSP_REQUIRE(ctx, weights_complete(*w), n_samples ? "ddsp_hubert_ragged: a weight pointer is null" : "ddsp_hubert: a weight pointer is null");
+    const HubForm form{HPAD, w, offsetof(ddsp_hubert_weights, version), nullptr};
+    return hubert_run(ctx, st, *w, form, wav, B, T, nl, tail, out, n_samples);
+}
+}  // namespace
 
 // n_samples == nullptr is the rectangular batch
 extern "C" int ddsp_hubert_soft_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B,
                                       int64_t T, const int32_t* n_samples, float* units) {
-    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, 13, units, n_samples);
+    return hubert_soft_run(ctx, (hipStream_t)stream, w, wav, B, T, 12, TAIL_UNITS, units, n_samples);
 }
 
 extern "C" int ddsp_hubert_encode(ddsp_ctx* ctx, void* stream, const ddsp_hubert_weights* w, const float* wav, int64_t B, int64_t T,
                                   const int32_t* n_samples, int layer, float* out) {
     DDSP_REQUIRE(ctx, layer >= -1 && layer <= 12, "ddsp_hubert_encode: layer must be -1 (conv stack) or 0..12");
-    return hubert_run(ctx, (hipStream_t)stream, w, wav, B, T, layer, out, n_samples);
+    return hubert_soft_run(ctx, (hipStream_t)stream, w, wav, B, T, layer < 0 ? 0 : layer, layer < 0 ? TAIL_CONV : TAIL_HIDDEN, out,
+                           n_samples);
+}
+
+// the base form: the struct's fields that both forms share go into a ddsp_hubert_weights whose in_proj hubert_run fills in
+extern "C" int ddsp_hubert_base_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_base_weights* bw, const float* wav, int64_t B,
+                                      int64_t T, const int32_t* n_samples, int n_layers, int project, float* out) {
+    DDSP_REQUIRE(ctx, ctx && bw, "ddsp_hubert_base: null argument");
+    DDSP_REQUIRE(ctx, weights_complete(*bw), "ddsp_hubert_base: a weight pointer is null");
+    DDSP_REQUIRE(ctx, n_layers >= 1 && n_layers <= 12 && (project == 0 || project == 1),
+                 "ddsp_hubert_base: n_layers must be 1..12 and project 0 or 1");
+    ddsp_hubert_weights w{};
+    w.conv0_w = bw->conv0_w; w.norm0_w = bw->norm0_w; w.norm0_b = bw->norm0_b;
+    for (int i = 0; i < 6; ++i) w.conv_w[i] = bw->conv_w[i];
+    w.fp_norm_w = bw->fp_norm_w; w.fp_norm_b = bw->fp_norm_b; w.fp_proj_w = bw->fp_proj_w; w.fp_proj_b = bw->fp_proj_b;
+    w.pos_b = bw->pos_b; w.pos_g = bw->pos_g; w.pos_v = bw->pos_v;
+    w.norm_w = bw->norm_w; w.norm_b = bw->norm_b;
+    HubQkv qkv;
+    for (int i = 0; i < 12; ++i) {
+        const ddsp_hubert_base_layer& s = bw->layer[i];
+        ddsp_hubert_layer& d = w.layer[i];
+        const float* six[6] = {s.q_w, s.k_w, s.v_w, s.q_b, s.k_b, s.v_b};
+        for (int j = 0; j < 6; ++j) qkv.p[i][j] = six[j];
+        d.out_proj_w = s.out_w; d.out_proj_b = s.out_b;
+        d.norm1_w = s.ln1_w; d.norm1_b = s.ln1_b;
+        d.linear1_w = s.fc1_w; d.linear1_b = s.fc1_b; d.linear2_w = s.fc2_w; d.linear2_b = s.fc2_b;
+        d.norm2_w = s.ln2_w; d.norm2_b = s.ln2_b;
+    }
+    w.proj_w = bw->proj_w; w.proj_b = bw->proj_b;
+    w.version = bw->version;
+    const HubForm form{0, bw, offsetof(ddsp_hubert_base_weights, version), &qkv};
+    return hubert_run(ctx, (hipStream_t)stream, w, form, wav, B, T, n_layers, project ? TAIL_UNITS : TAIL_HIDDEN, out, n_samples);
 }
 
 // n_keys == nullptr attends over all L rows

@@ -1,5 +1,5 @@
 """Drop-in for the analysis half of the reference's `ddsp/vocoder.py` (:18-229): `Volume_Extractor`, `F0_Extractor`,
-`Units_Encoder`, `Audio2HubertSoft`, plus `align_units`, executed by hand-written gfx950 kernels through libddsp_amd (no CPU
+`Units_Encoder`, `Audio2HubertSoft`, `Audio2CVec`, `Audio2CVec768`, plus `align_units`, executed by hand-written gfx950 kernels through libddsp_amd (no CPU
 fallback).  `ddsp.vocoder` re-exports every name, so `from ddsp.vocoder import F0_Extractor` keeps working.
 
 What the three analysers share is written once here: `_batch_of` (numpy / (T,) / (B, T) in, the caller's rank and type
@@ -93,9 +93,11 @@ def volume_rule(hop_size):
                     f"are not longer than the volume's reflect padding {(int(hop_size) + 1) // 2}")
 
 
-def units_rule(sample_rate, encoder_sample_rate=HUBERT_RATE):
-    """The HuBERT-Soft rule for rows at `sample_rate`."""
-    return _RowRule(hipddsp.hubert_rule, "are too short for the units encoder's conv stack", sample_rate, encoder_sample_rate)
+def units_rule(sample_rate, encoder_sample_rate=HUBERT_RATE, padded=True):
+    """The units encoder's rule for rows at `sample_rate`: HuBERT-Soft's, which pads 40 samples on each side, or with
+    `padded=False` that of the base form ('cvec', 'cvec768'), which does not."""
+    return _RowRule(hipddsp.hubert_rule if padded else hipddsp.hubert_base_rule,
+                    "are too short for the units encoder's conv stack", sample_rate, encoder_sample_rate)
 
 
 def crepe_rule(sample_rate):
@@ -331,6 +333,51 @@ class Audio2HubertSoft(torch.nn.Module):
         return self.hubert.units(audio.unsqueeze(1), n_samples)
 
 
+class _Audio2Base(torch.nn.Module):
+    """A fairseq HuBERT-base checkpoint (`ddsp.hubert.read_fairseq_checkpoint`: a plain state dict, or one under "model")
+    behind `forward(audio (B,T)) -> units (B, Frame, n_unit)`, executed by libddsp_amd (`ddsp.hubert.HubertBase`): transformer
+    layer 9, as every base-form class of the reference (`ddsp/vocoder.py:231-332`).  Unlike the reference's ContentVec
+    classes, whose `view(1, -1)` glues a batch into one row, every row is encoded on its own and every row is returned."""
+    n_unit, project, label = None, None, None
+
+    def __init__(self, path, h_sample_rate=16000, h_hop_size=320, device=None):
+        super().__init__()
+        from .hubert import HubertBase, read_fairseq_checkpoint
+        print(' [Encoder Model] ' + self.label)
+        self.hubert = HubertBase()
+        print(' [Loading] ' + path)
+        self.hubert.load_state_dict(read_fairseq_checkpoint(path))
+        self.hubert.eval()
+        if device is not None:
+            self.hubert.to(device)
+
+    def forward(self, audio, n_samples=None):
+        """ :: (B, T) -> (B, 1, T) -> (B, Frame, n_unit); `n_samples`: ragged batch (`HubertBase.units`) """
+        return self.hubert.units(audio.unsqueeze(1), n_samples, layer=9, project=self.project)
+
+
+class Audio2CVec(_Audio2Base):
+    """'cvec': layer 9 then `final_proj`, 256 channels - what the reference's `Audio2ContentVec` and `Audio2HubertBase`
+    compute (the two differ in the checkpoint only)."""
+    n_unit, project, label = 256, True, "HuBERT-base / ContentVec, layer 9, final_proj (256)"
+
+
+class Audio2CVec768(_Audio2Base):
+    """'cvec768': the layer-9 hidden state, 768 channels - the reference's `Audio2ContentVec768` and `Audio2HubertBase768`."""
+    n_unit, project, label = 768, False, "HuBERT-base / ContentVec, layer 9 (768)"
+
+
+def check_units_width(name, units_encoder, *models):
+    """The encoder's channels against every model's `n_unit`, before anything is launched: ValueError on a mismatch.  An
+    encoder that does not state its width (a stand-in), or a model without `unit2ctrl`, is not checked."""
+    width = getattr(units_encoder, "n_unit", None)
+    for m in models:
+        n_unit = getattr(getattr(m, "unit2ctrl", None), "n_unit", None)
+        if width is not None and n_unit is not None and int(width) != int(n_unit):
+            raise ValueError(f"{name}: the units encoder '{getattr(units_encoder, 'encoder', '?')}' gives {int(width)} channels "
+                             f"and the model was built for n_unit = {int(n_unit)} (config: encoder_out_channels)")
+
+
 class Units_Encoder:
     """Reference `ddsp/vocoder.py:140-211` for `encoder='hubertsoft'`: resampling to the encoder's rate (`ddsp_resample`,
     lowpass_filter_width=128, as the reference's torchaudio Resample), the encoder and the nearest-frame alignment
@@ -338,38 +385,61 @@ class Units_Encoder:
 
     Differences a caller can observe, all additive: audio (B,T) with B > 1 returns every row aligned (the reference
     returns row 0 only); the other encoder names raise NotImplementedError - `hubertsoft` is the device encoder, and callers
-    that keep the reference's encoders can align their units on the device with `align_units`."""
+    that keep the reference's encoders can align their units on the device with `align_units`.
+
+    `encoder='cvec'` / `'cvec768'`: fairseq's HuBERT-base network (ContentVec and HuBERT-base checkpoints) on the device, layer
+    9 with `final_proj` (256 channels) or without (768) - what the reference computes under 'contentvec' / 'hubertbase' and
+    'contentvec768' / 'hubertbase768'.  They carry names of their own because the reference's names keep raising here (fairseq
+    is no dependency, and loading a released checkpoint file is not pinned by a test).  Resampler, alignment and ragged
+    batches are those of 'hubertsoft'; the frame rule is the encoder's own (no padding: 400 samples at 16 kHz give the first
+    frame), and every row of a batch is encoded on its own (the reference's ContentVec classes glue a batch into one row).
+    `n_unit`: the channels of `encode`'s result."""
+
+    # encoder -> (module, channels, whether the encoder pads its input)
+    _MODELS = {'hubertsoft': (Audio2HubertSoft, 256, True), 'cvec': (Audio2CVec, 256, False), 'cvec768': (Audio2CVec768, 768, False)}
+    encoder, n_unit, padded = 'hubertsoft', 256, True        # (of an instance made without the constructor)
 
     def __init__(self, encoder, encoder_ckpt, encoder_sample_rate=16000, encoder_hop_size=320, device=None):
         if encoder in ('hubertbase', 'hubertbase768', 'contentvec', 'contentvec768', 'xunit', 'yunit'):
+            hint = "" if encoder in ('xunit', 'yunit') else (
+                f"  The network behind '{encoder}' runs on the device as '{'cvec768' if encoder.endswith('768') else 'cvec'}' "
+                "('cvec': layer 9 and final_proj, 256 channels; 'cvec768': layer 9, 768 channels), given the fairseq "
+                "checkpoint's state dict.")
             raise NotImplementedError(
-                f"units encoder '{encoder}' has no device implementation: 'hubertsoft' is the device encoder; callers that "
-                "keep the reference's encoders can align their units on the device with ddsp.vocoder.align_units")
-        if encoder != 'hubertsoft':
+                f"units encoder '{encoder}' has no device implementation under that name: 'hubertsoft' is the device encoder "
+                "of the reference's names; callers that keep the reference's encoders can align their units on the device with "
+                "ddsp.vocoder.align_units." + hint)
+        if encoder not in self._MODELS:
             raise ValueError(f" [x] Unknown units encoder: {encoder}")
+        cls, self.n_unit, self.padded = self._MODELS[encoder]
+        self.encoder = encoder
         self.device = _hip_device("Units_Encoder", device)
-        self.model = Audio2HubertSoft(encoder_ckpt, device=self.device).eval()
+        self.model = cls(encoder_ckpt, device=self.device).eval()
         self.encoder_sample_rate = encoder_sample_rate
         self.encoder_hop_size = encoder_hop_size
 
     too_short = units_rule(None).too_short
 
+    def rule(self, sample_rate):
+        """This encoder's row-length rule for rows at `sample_rate`."""
+        return units_rule(sample_rate, self.encoder_sample_rate, self.padded)
+
     def min_samples(self, sample_rate):
         """The shortest row `encode` accepts, in samples at `sample_rate`."""
-        return units_rule(sample_rate, self.encoder_sample_rate).min_samples()
+        return self.rule(sample_rate).min_samples()
 
     def encode(self, audio, sample_rate, hop_size, n_samples=None):
-        """audio (B,T) at `sample_rate` -> units (B, int(T // hop_size) + 1, 256) aligned to frames of `hop_size` samples
+        """audio (B,T) at `sample_rate` -> units (B, int(T // hop_size) + 1, n_unit) aligned to frames of `hop_size` samples
         (a float hop keeps its fraction, like the reference's).
         `n_samples` (a sequence of B ints or a CPU integer tensor (B,), counts at `sample_rate`): a RAGGED batch.  Row b is
         encoded as audio[b, :n_samples[b]] alone - resampling, encoder and alignment each stop at the row's own end, and
-        what follows a row's samples may hold anything.  Returns (B, int(max(n_samples) // hop_size) + 1, 256); row b
+        what follows a row's samples may hold anything.  Returns (B, int(max(n_samples) // hop_size) + 1, n_unit); row b
         carries int(n_samples[b] // hop_size) + 1 frames and zeros after them."""
         enc_sr = self.encoder_sample_rate
         if n_samples is not None:
             if audio.dim() != 2:
                 raise ValueError("Units_Encoder.encode: a ragged batch is (B, T) audio")
-            vals, n16, T16 = units_rule(sample_rate, enc_sr).counts(n_samples, *audio.shape)     # (before any launch)
+            vals, n16, T16 = self.rule(sample_rate).counts(n_samples, *audio.shape)     # (before any launch)
         if not audio.is_cuda:
             raise RuntimeError("Units_Encoder runs on a HIP device only (no CPU fallback)")
         ctx = hipddsp.context_for(audio.device)
@@ -377,7 +447,8 @@ class Units_Encoder:
         if n_samples is not None:
             n_out = [int(v // hop_size) + 1 for v in vals]
             # one upload for the four count vectors
-            dev = ctx.ragged_counts(vals + n16 + [hipddsp.hubert_frames(v) for v in n16] + n_out).reshape(4, -1)
+            frames = hipddsp.hubert_frames if self.padded else hipddsp.hubert_base_frames
+            dev = ctx.ragged_counts(vals + n16 + [frames(v) for v in n16] + n_out).reshape(4, -1)
             n_dev, rows, n_frames = dev[0], RaggedCounts(n16, T16, dev[1]), max(n_out)
             aligned = dict(n_units_dev=dev[2], n_out_dev=dev[3])
         audio_res = audio if sample_rate == enc_sr else \

@@ -46,8 +46,8 @@ from hipddsp import (COMB_SINC, COMB_SINC_GATED, COMB_NONE, EXC_AUDIO, EXC_GENER
                      FIR_DYNAMIC, FIR_STATIC, FIR_SPLIT_BF16)
 
 # the analysers live in ddsp/analysis.py; their names stay importable from here
-from .analysis import (Audio2HubertSoft, F0_Extractor, Units_Encoder, Volume_Extractor,  # noqa: F401
-                       _find_torchcrepe_checkpoint, align_units)
+from .analysis import (Audio2CVec, Audio2CVec768, Audio2HubertSoft, F0_Extractor, Units_Encoder,  # noqa: F401
+                       Volume_Extractor, _find_torchcrepe_checkpoint, align_units)
 from .unit2control import Unit2Control, is_frame_mix
 
 

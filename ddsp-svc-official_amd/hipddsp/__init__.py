@@ -62,6 +62,22 @@ class HubertWeights(_c.Structure):
     )
 
 
+HUBERT_BASE_LAYER_FIELDS = ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "out_w", "out_b", "ln1_w", "ln1_b", "fc1_w", "fc1_b",
+                            "fc2_w", "fc2_b", "ln2_w", "ln2_b")
+
+
+class HubertBaseWeights(_c.Structure):
+    """Mirror of `ddsp_hubert_base_weights` (include/ddsp_amd.h): device pointers into a fairseq HubertModel state dict."""
+    _fields_ = (
+        [(n, _vp) for n in ("conv0_w", "norm0_w", "norm0_b")]
+        + [(f"conv{i + 1}_w", _vp) for i in range(6)]
+        + [(n, _vp) for n in ("fp_norm_w", "fp_norm_b", "fp_proj_w", "fp_proj_b", "pos_b", "pos_g", "pos_v", "norm_w", "norm_b")]
+        + [(f"l{i}_{n}", _vp) for i in range(12) for n in HUBERT_BASE_LAYER_FIELDS]
+        + [(n, _vp) for n in ("proj_w", "proj_b")]
+        + [("version", _c.c_uint64)]     # change counter of the weight values (0: prepare the weights on every call)
+    )
+
+
 class CrepeWeights(_c.Structure):
     """Mirror of `ddsp_crepe_weights` (include/ddsp_amd.h): device pointers into a CREPE state dict (torchcrepe's keys) and the
     output channels of its six convolutions."""
@@ -75,7 +91,7 @@ class CrepeWeights(_c.Structure):
 
 
 class WeightTable:
-    """The weight struct (U2CWeights, HubertWeights) of one model, built from `named_tensors(module)` -> [(field, tensor)].
+    """The weight struct (U2CWeights, HubertWeights, HubertBaseWeights) of one model, built from `named_tensors(module)` -> [(field, tensor)].
 
     The library keeps the weights it prepares from the struct while its pointers, integers and `version` stand.  `version` is
     a per-model nonce (two models whose tensors the allocator placed at the same addresses differ in it) plus the sum of
@@ -222,6 +238,8 @@ SIGNATURES = {
     "ddsp_hubert_frames": (_i64, [_i64]),
     "ddsp_hubert_soft_units": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _vp]),
     "ddsp_hubert_encode": (_int, [_vp, _vp, _c.POINTER(HubertWeights), _vp, _i64, _i64, _vp, _int, _vp]),
+    "ddsp_hubert_base_frames": (_i64, [_i64]),
+    "ddsp_hubert_base_units": (_int, [_vp, _vp, _c.POINTER(HubertBaseWeights), _vp, _i64, _i64, _vp, _int, _int, _vp]),
     "ddsp_softmax_attention": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _vp]),
     "ddsp_stft_frames": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp]),
     "ddsp_retime_f0_keyed": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _vp, _int, _vp, _vp, _f64, _i64, _vp, _vp]),
@@ -334,7 +352,7 @@ def check_n_frames(n_frames, B, Fr):
 def check_n_samples(n_samples, B, T, rule=None):
     """The per-row sample counts of a ragged batch of audio (B, T) as a list of B Python ints, 1 <= n <= T; anything else
     raises ValueError (a host check: nothing is launched).  Accepted: what `check_n_frames` accepts.  `rule`: an analyser's
-    row-length rule (`hubert_rule`, `crepe_rule`, `f0_ac_rule`, `volume_rule`, `slicer_rule`), count -> None or why such a row is too short."""
+    row-length rule (`hubert_rule`, `hubert_base_rule`, `crepe_rule`, `f0_ac_rule`, `volume_rule`, `slicer_rule`), count -> None or why such a row is too short."""
     vals = _check_counts("n_samples", n_samples, B)
     for b, v in enumerate(vals):
         if not 1 <= v <= int(T):
@@ -349,6 +367,11 @@ def check_n_samples(n_samples, B, T, rule=None):
 def hubert_rule(n):
     """The units encoder's row-length rule: a row must be long enough for the conv stack (`hubert_frames(n) >= 1`)."""
     return None if hubert_frames(n) >= 1 else "samples are too short for the conv stack"
+
+
+def hubert_base_rule(n):
+    """The row-length rule of the base-form units encoder, which does not pad its input (`hubert_base_frames(n) >= 1`)."""
+    return None if hubert_base_frames(n) >= 1 else "samples are too short for the conv stack"
 
 
 def crepe_rule(hop=80):
@@ -426,6 +449,7 @@ def check_global_n_samples(global_n_samples, n_samples):
 
 # `check_n_samples` with each analyser's rule applied
 check_hubert_n_samples = lambda n_samples, B, T: check_n_samples(n_samples, B, T, hubert_rule)                       # noqa: E731
+check_hubert_base_n_samples = lambda n_samples, B, T: check_n_samples(n_samples, B, T, hubert_base_rule)             # noqa: E731
 check_crepe_n_samples = lambda n_samples, B, T, hop=80: check_n_samples(n_samples, B, T, crepe_rule(hop))           # noqa: E731
 check_f0_ac_n_samples = lambda n_samples, B, T, sr, hop, f0_min: check_n_samples(n_samples, B, T, f0_ac_rule(sr, hop, f0_min))  # noqa: E731
 check_volume_n_samples = lambda n_samples, B, T, hop: check_n_samples(n_samples, B, T, volume_rule(hop))            # noqa: E731
@@ -1251,6 +1275,23 @@ class Context:
             self.call("ddsp_hubert_encode", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), int(layer), _ptr(out))
         return out
 
+    def hubert_base_units(self, weights, wav, n_layers=9, project=True, n_dev=None):
+        """weights: a HubertBaseWeights struct; wav (B,T) 16 kHz fp32, not padded -> the hidden state after `n_layers` (1..12)
+        transformer layers (B, Fr, 768), or with `project` its final projection (B, Fr, 256).  n_dev: as in `hubert_units`,
+        the counts checked with `check_hubert_base_n_samples`."""
+        B, T = wav.shape
+        Fr = hubert_base_frames(T)
+        if Fr <= 0:
+            raise ValueError(f"hubert: {T} samples are too short for the conv stack")
+        if not 1 <= int(n_layers) <= 12:
+            raise ValueError("hubert_base_units: n_layers in 1..12")
+        wav = wav.contiguous().float()
+        out = torch.empty(B, Fr, 256 if project else 768, device=wav.device, dtype=torch.float32)
+        if B:
+            self.call("ddsp_hubert_base_units", ctypes.byref(weights), _ptr(wav), int(B), int(T), _ptr(n_dev), int(n_layers),
+                      int(bool(project)), _ptr(out))
+        return out
+
     # -- f0 extractor (CREPE) --------------------------------------------------------------------
     def crepe_activations(self, weights, audio16, hop=80, n_samples=None, counts_dev=None):
         """weights: a CrepeWeights struct; audio16 (B,T) 16 kHz fp32 -> sigmoid activations (B, 1 + T // hop, 360).
@@ -1819,6 +1860,11 @@ def resample_length(n, sr_in, sr_out):
     """n samples at `sr_in` as samples at `sr_out`: n itself at equal rates, else the resampler's length
     (`ddsp_resample_length`; negative for a pair of rates it cannot convert)."""
     return n if int(sr_in) == int(sr_out) else int(load_library().ddsp_resample_length(int(n), int(sr_in), int(sr_out)))
+
+
+def hubert_base_frames(T):
+    """Frames of T samples in the base-form units encoder, which does not pad (`ddsp_hubert_base_frames`): 0 when too short."""
+    return int(load_library().ddsp_hubert_base_frames(int(T)))
 
 
 def hubert_frames(T):

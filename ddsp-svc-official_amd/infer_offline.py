@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 import hipddsp
+from ddsp.analysis import check_units_width
 from sharding import stack_rows
 from slicer import Slicer
 
@@ -262,6 +263,7 @@ def convert_batched(model, args, audio, sample_rate, slices, units_encoder, f0_e
     at most that many padded samples (at the model's rate); it stands before `units_batch_samples`, which
     tests/test_hubert_ragged_host.py pins as the last parameter.  (A function of its own and not a keyword of `convert`:
     tests/test_stream_audio_host.py pins `convert`'s parameter list.)"""
+    check_units_width("convert", units_encoder, model)
     segments, f0, volume = _analyse(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples)
     return render(model, args, segments, f0, volume, spk_id, spk_mix_dict=spk_mix_dict, threshold_db=threshold_db,
                   enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
@@ -880,6 +882,7 @@ def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extr
             raise ValueError("convert_many_device: models= goes with jobs=; without jobs the one model is the positional one")
         if spk_ids is None and spk_mix_rows is None:
             raise ValueError("convert_many_device: spk_ids (or spk_mix_rows) is required without jobs=")
+        check_units_width("convert_many_device", units_encoder, model)
         files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, keys, units_batch_samples)
         return render_many_device(model, args, files, spk_ids, spk_mix_rows=spk_mix_rows, threshold_db=threshold_db,
                                   enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed,
@@ -889,6 +892,7 @@ def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extr
                          "keys at their defaults")
     models, jobs = _models_of("convert_many_device", model, models), list(jobs)
     job_table([], len(audios), jobs, models)                # every refusal of the tables, before anything is analysed
+    check_units_width("convert_many_device", units_encoder, *models)
     if not jobs:
         return torch.zeros(0, dtype=torch.float64, device=next(models[0].parameters()).device), [], int(args.data.sampling_rate)
     files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, 0, units_batch_samples)
@@ -904,6 +908,7 @@ def convert_device(model, args, audio, sample_rate, slices, units_encoder, f0_ex
     """`convert_batched` ending as `render_device` does: `_analyse`'s analysis, its dict handed on as it is, then ragged
     rendering, one gate launch per group, the ragged enhancer and one stitch launch -> (fp64 device tensor (total,), sample
     rate), equal to `convert_batched`'s array.  One `.cpu()` of the result is the file's only read-back behind the slicer's."""
+    check_units_width("convert_device", units_encoder, model)
     files = _analyse_files(args, audio, sample_rate, slices, units_encoder, f0_extractor, key, units_batch_samples, solo=True)
     return _render_file(model, args, files, spk_id, spk_mix_dict, noise_seed, None, threshold_db=threshold_db, enhancer=enhancer,
                         enhancer_adaptive_key=enhancer_adaptive_key, batch_frames=batch_frames,

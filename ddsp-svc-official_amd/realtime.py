@@ -72,9 +72,10 @@ def phase_vocoder(a, b, fade_out, fade_in):
     return hipddsp.context_for(a.device).phase_vocoder(a, b, fade_out, fade_in)
 
 
-def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop):
+def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop, models=()):
     """The analysis front end of `push_audio` as `name` (a class) is given it: both or neither; `f0_extractor` may be the
-    shorthand "crepe" or "ac", which `_f0_extractor` builds once every refusal is made."""
+    shorthand "crepe" or "ac", which `_f0_extractor` builds once every refusal is made.  `models`: the synthesisers the units
+    go to, each built for the encoder's channels (`ddsp.analysis.check_units_width`)."""
     if (units_encoder is None) != (f0_extractor is None):
         raise ValueError(f"{name}: push_audio needs both units_encoder and f0_extractor (or neither)")
     if f0_extractor is None:
@@ -82,6 +83,8 @@ def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop)
     shorthand = isinstance(f0_extractor, str) and f0_extractor in ("crepe", "ac")
     if not ((shorthand or hasattr(f0_extractor, "extract")) and hasattr(units_encoder, "encode")):
         raise ValueError(f"{name}: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
+    from ddsp.analysis import check_units_width
+    check_units_width(name, units_encoder, *models)
     if not shorthand and (f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != hop):
         raise ValueError(f"{name}: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
                          f"{f0_extractor.hop_size}; {window} at {samplerate} Hz with hop {hop}")
@@ -207,7 +210,8 @@ class StreamRenderer:
         self.spk_id = torch.full((1, 1), int(spk_id), dtype=torch.int64, device=self.device)
         self.spk_mix_dict = self._checked_mix(spk_mix_dict)
         self.features = features
-        _check_analysers("StreamRenderer", "this renderer's window is", units_encoder, f0_extractor, samplerate, self.hop_size)
+        _check_analysers("StreamRenderer", "this renderer's window is", units_encoder, f0_extractor, samplerate, self.hop_size,
+                         (self.model,))
         f0_extractor = _f0_extractor(f0_extractor, samplerate, self.hop_size, f0_min, f0_max, crepe_ckpt, self.device)
         self.units_encoder, self.f0_extractor, self.f0_dither = units_encoder, f0_extractor, bool(f0_dither)
         self.last_f0 = self.last_units = self.last_volume = None
@@ -600,7 +604,8 @@ class StreamBank:
         self.block, self.xfade, self.search, self.delay = z["block"], z["xfade"], z["search"], z["delay"]
         self.n_in, self.hop_size, self.frames, self.silence_front = z["n_in"], z["hop_size"], z["frames"], z["silence_front"]
         self.threshold_db = float(threshold_db)
-        _check_analysers("StreamBank", "this bank's windows are", units_encoder, f0_extractor, samplerate, self.hop_size)
+        _check_analysers("StreamBank", "this bank's windows are", units_encoder, f0_extractor, samplerate, self.hop_size,
+                         self.models)
         self.enhancer, self.enhancer_max_key, self.enhancer_plan = enhancer, enhancer_max_key, None
         self.out_sr = output_rate(self.model_sr, enhancer)
         if enhancer is not None:

@@ -887,6 +887,46 @@ int ddsp_softmax_attention(ddsp_ctx* ctx, void* stream, const float* q, const fl
  * convolution, the keys of the softmax attention.  The GEMMs run over all B * Fr padded rows.  `units` / `out` must be
  * 16-byte aligned (DDSP_ERR_ARG otherwise). */
 
+/* ---- the units encoder in fairseq's HuBERT-base form (ContentVec, HuBERT-base: ddsp/vocoder.py:231-332) -----------------
+ * fairseq's `HubertModel.extract_features(source, padding_mask = all False, output_layer = n_layers)`, optionally followed by
+ * `final_proj`.  It is the network above with three differences: the audio is NOT padded, the transformer stops after
+ * n_layers layers, and the attention's input projections are three (768, 768) matrices with a bias each.  The library packs
+ * them into the (2304, 768) operand of its QKV GEMM when it prepares the weights (with the conv repacking and the
+ * weight-norm fold), into the same per-context slot under the same rule: prepared again whenever a pointer or `version`
+ * differs, on every call for version 0.  The two forms share that slot, so alternating them on one context prepares anew.
+ * Device pointers into a fairseq HubertModel state dict, fp32, dense:
+ *   conv0_w, conv_w[i]  feature_extractor.conv_layers.{0, i+1}.0.weight     norm0_w/_b  feature_extractor.conv_layers.0.2.*
+ *   fp_norm_w/_b  layer_norm (512)      fp_proj_w/_b  post_extract_proj (768,512), (768)
+ *   pos_b, pos_g, pos_v  encoder.pos_conv.0.{bias, weight_g (1,1,128), weight_v (768,48,128)}     norm_w/_b  encoder.layer_norm
+ *   layer[i]  encoder.layers.i.{self_attn.q_proj, .k_proj, .v_proj, .out_proj (each weight (768,768) and bias),
+ *             self_attn_layer_norm (ln1), fc1 (3072,768), fc2 (768,3072), final_layer_norm (ln2)}
+ *   proj_w/_b  final_proj (256,768), (256) */
+typedef struct ddsp_hubert_base_layer {
+    const float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *out_w, *out_b;
+    const float *ln1_w, *ln1_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ln2_w, *ln2_b;
+} ddsp_hubert_base_layer;
+
+typedef struct ddsp_hubert_base_weights {
+    const float *conv0_w, *norm0_w, *norm0_b;
+    const float* conv_w[6];
+    const float *fp_norm_w, *fp_norm_b, *fp_proj_w, *fp_proj_b;
+    const float *pos_b, *pos_g, *pos_v;
+    const float *norm_w, *norm_b;
+    ddsp_hubert_base_layer layer[12];
+    const float *proj_w, *proj_b;
+    uint64_t version;
+} ddsp_hubert_base_weights;
+
+/* Frames of T unpadded samples: (T - 10) / 5 + 1, then (n - 3) / 2 + 1 four times and (n - 2) / 2 + 1 twice (400 samples give
+ * the first frame, 720 the second); 0 when the audio is too short for the conv stack, -1 for T < 0.  Host only. */
+int64_t ddsp_hubert_base_frames(int64_t T);
+/* wav (B,T) 16 kHz -> out (B, Fr, 768) for project = 0: the hidden state after n_layers (1..12) transformer layers; or
+ * (B, Fr, 256) for project = 1: `final_proj` of it.  Fr = ddsp_hubert_base_frames(T).  n_samples: NULL, or a ragged batch
+ * exactly as for ddsp_hubert_soft_units (counts checked against ddsp_hubert_base_frames; `out` 16-byte aligned).  Product
+ * arithmetic, capture and read-backs (none) as for ddsp_hubert_soft_units. */
+int ddsp_hubert_base_units(ddsp_ctx* ctx, void* stream, const ddsp_hubert_base_weights* w, const float* wav, int64_t B, int64_t T,
+                           const int32_t* n_samples, int n_layers, int project, float* out);
+
 /* ---- the f0 extractor (CREPE, ddsp/vocoder.py:39-113 with torchcrepe.predict and librosa's Viterbi restated) ---------- */
 /* Device pointers into a CREPE state dict (torchcrepe's keys), fp32, dense: conv_w[i] = `conv{i+1}.weight` (Cout, Cin, k, 1),
  * conv_b[i] = `conv{i+1}.bias`, bn_*[i] = `conv{i+1}_BN.{weight,bias,running_mean,running_var}`, cls_w / cls_b =
