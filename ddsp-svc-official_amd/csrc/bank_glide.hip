@@ -109,3 +109,85 @@ extern "C" int ddsp_bank_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows,
     DDSP_LAUNCH_CHECK(ctx);
     return DDSP_OK;
 }
+
+// The KEY glide of a stream bank (`pitch_breakpoints=`): the per-frame f0 factors of one call's rows from per-slot state, and the
+// advance of those slots' key clocks - the launch above with a key timeline (key_timeline.h) in place of the mix weights.  A slot
+// owns key_clock[s], key_n[s] (0: no timeline), key_t[s] (P_max) in device samples, strictly increasing, and key_semi[s] /
+// key_fac[s] (P_max), the breakpoints' semitones and host-formed factors.  Rows, padding rows (factor 1 in every frame, no
+// clock touched), the frame times and the clock's read-before / store-after the barrier are those of bank_glide_kernel.  Without
+// a timeline every frame gets pitch[s], the slot's one factor.
+#include "key_timeline.h"
+
+namespace {
+
+struct KeyGlideArgs {
+    const int32_t* rows;      // (W) or null
+    int64_t* clock;           // (S)
+    const int32_t* key_n;     // (S)
+    const int64_t* key_t;     // (S, P_max)
+    const float* key_semi;    // (S, P_max)
+    const float* key_fac;     // (S, P_max)
+    const float* pitch;       // (S)
+    int S, P_max;
+    int64_t Fr, n_in, block;
+    double hop;
+    float* pitch_frames;      // (W, Fr)
+};
+
+__global__ void __launch_bounds__(256) bank_key_glide_kernel(KeyGlideArgs a) {
+    const int64_t r = blockIdx.x;
+    float* __restrict__ out = a.pitch_frames + r * a.Fr;
+    const int64_t s = a.rows ? (int64_t)a.rows[r] : r;
+    if (s < 0 || s >= a.S) {                                      // a padding row: no shift
+        for (int64_t t = threadIdx.x; t < a.Fr; t += 256) out[t] = 1.f;
+        return;
+    }
+    const int64_t c = a.clock[s] + a.block;                      // every thread: read before the barrier, stored after it
+    int n = a.key_n[s];
+    n = n < 0 ? 0 : (n > a.P_max ? a.P_max : n);
+    const int64_t* __restrict__ bt = a.key_t + s * a.P_max;
+    const float* __restrict__ semi = a.key_semi + s * a.P_max;
+    const float* __restrict__ fac = a.key_fac + s * a.P_max;
+    const float one = a.pitch[s];
+    const double first = (double)(c - a.n_in);
+    for (int64_t t = threadIdx.x; t < a.Fr; t += 256)
+        out[t] = n == 0 ? one : keytl::factor_at(bt, semi, fac, n, first + (double)t * a.hop);
+    __syncthreads();
+    if (threadIdx.x == 0) a.clock[s] = c;
+}
+
+}  // namespace
+
+extern "C" int ddsp_bank_key_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, int64_t* key_clock,
+                                   const int32_t* key_n, const int64_t* key_t, const float* key_semi, const float* key_fac,
+                                   int P_max, const float* pitch, int64_t Fr, int64_t n_in, int64_t block, double hop,
+                                   float* pitch_frames) {
+    DDSP_REQUIRE(ctx, ctx && key_clock && key_n && key_t && key_semi && key_fac && pitch && (W == 0 || pitch_frames),
+                 "ddsp_bank_key_glide: null argument");
+    DDSP_REQUIRE(ctx, W >= 0 && W <= 65535 && S >= 1 && P_max >= 1 && P_max <= 64 && Fr >= 1 && Fr < ((int64_t)1 << 26) &&
+                          block >= 1 && n_in >= 1 && hop > 0.0,
+                 "ddsp_bank_key_glide: bad shape (W <= 65535, 1 <= P_max <= 64, Fr >= 1, block >= 1)");
+    if (W == 0) return DDSP_OK;
+    DDSP_ENTER_DEVICE(ctx);
+    KeyGlideArgs a;
+    a.rows = rows;
+    a.clock = key_clock;
+    a.key_n = key_n;
+    a.key_t = key_t;
+    a.key_semi = key_semi;
+    a.key_fac = key_fac;
+    a.pitch = pitch;
+    a.S = S;
+    a.P_max = P_max;
+    a.Fr = Fr;
+    a.n_in = n_in;
+    a.block = block;
+    a.hop = hop;
+    a.pitch_frames = pitch_frames;
+    hipStream_t st = (hipStream_t)stream;
+    ddsp_prof_begin(ctx, st, PF_OTHER);
+    hipLaunchKernelGGL(bank_key_glide_kernel, dim3((unsigned)W), dim3(256), 0, st, a);
+    ddsp_prof_end(ctx, st, 0.0, 4.0 * (double)W * (double)Fr);
+    DDSP_LAUNCH_CHECK(ctx);
+    return DDSP_OK;
+}

@@ -210,8 +210,8 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     `gui.SvcDDSP.infer`, gui.py:87-127), every step on the device, nothing read back: `window` takes `block_in` in place,
     then volume, f0 (uv_interp, silent front), the pitch shift, units, the synthesiser and the gate.
     One stream: `window` (n_in,), `block_in` (block,), `pitch` a host factor (no multiply at exactly 1).  S streams of one
-    geometry: `window` (S, n_in), `block_in` (S, block), `pitch` a device (S,) tensor of factors; every step is then one batched
-    call.  The window keeps the rank it comes with down to the library, so each form reaches its own kernels.
+    geometry: `window` (S, n_in), `block_in` (S, block), `pitch` a device (S,) tensor of factors - or (S, Fr), a factor per FRAME,
+    which `push` fills (`ddsp_bank_key_glide`) -; every step is then one batched call.  The window keeps the rank it comes with down to the library, so each form reaches its own kernels.
     `speaker`: the speaker term as the model's keyword arguments, {"spk_id": (1, 1) int64, "spk_mix_dict": dict or None} or
     {"spk_id": None, "spk_mix_rows": (ids (S, K) int32, w (S, K) fp32)}.
     `push(ctx, window, block_in)`: the step that brings `window` up to date, `ctx.stream_push_` unless given.  The compact rows of
@@ -229,7 +229,7 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     f0 = f0_extractor.extract(window, uv_interp=True, silence_front=silence_front, dither=f0_dither, seed_dev=seed_dev)
     f0 = f0.reshape(-1, f0.shape[-1])[:, :, None]
     if isinstance(pitch, torch.Tensor):
-        f0 = f0 * pitch[:, None, None]
+        f0 = f0 * (pitch[:, :, None] if pitch.dim() == 2 else pitch[:, None, None])    # a factor per frame, or one per row
     elif pitch != 1:
         f0 = f0 * pitch
     units = units_encoder.encode(audio, samplerate, hop_size)

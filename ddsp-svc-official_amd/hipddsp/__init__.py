@@ -211,6 +211,7 @@ SIGNATURES = {
     "ddsp_volume_gate_files": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _i64, _i64, _i64, _int]),
     "ddsp_pieces_gather": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "ddsp_pieces_gather_jobs": (_int, [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "ddsp_pieces_gather_keys": (_int, [_vp] * 9 + [_i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "ddsp_stitch": (_int, [_vp, _vp, _vp, _i64, _vp, _i64]),
     "ddsp_pcm16": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "ddsp_phase_vocoder": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
@@ -256,6 +257,7 @@ SIGNATURES = {
                                 _vp, _vp, _vp]),
     "ddsp_bank_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp]),
     "ddsp_bank_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _i64, _i64, _i64, _f64, _vp]),
+    "ddsp_bank_key_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _f64, _vp]),
     "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
     "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
@@ -1602,6 +1604,34 @@ class Context:
                       int(n_in), int(block), float(hop), _ptr(w_frames))
         return w_frames
 
+    def bank_key_glide_(self, rows, key_clock, key_n, key_t, key_semi, key_fac, pitch, pitch_frames, n_in, block, hop):
+        """The per-frame f0 factors of one call's rows from the slots' key timelines, and the advance of those slots' key clocks
+        (`ddsp_bank_key_glide`): `bank_glide_` with a key timeline in place of the weights.  rows (W,) int32 device or None as
+        there.  In place: pitch_frames (W, Fr) takes, for frame t of a real row, the slot's breakpoints key_t (S, P_max) int64 /
+        key_semi, key_fac (S, P_max) fp32 - the first key_n (S,) int32 of them - at tau = key_clock[s] + block - n_in + t * hop
+        by the key timeline rule (include/ddsp_amd.h), or pitch (S,)[s] when the slot has none, 1.0 on a padding row; then
+        key_clock (S,) int64 advances by `block` for the named slots alone.  No slot may be named twice.  -> pitch_frames."""
+        if not (isinstance(pitch_frames, torch.Tensor) and pitch_frames.dim() == 2 and isinstance(key_clock, torch.Tensor) and
+                key_clock.dim() == 1 and isinstance(key_t, torch.Tensor) and key_t.dim() == 2):
+            raise ValueError("bank_key_glide_: pitch_frames (W, Fr), key_clock (S,) and key_t (S, P_max)")
+        (W, Fr), S, P_max = pitch_frames.shape, key_clock.numel(), key_t.shape[1]
+        tables = ((key_clock, torch.int64, (S,)), (key_n, torch.int32, (S,)), (key_t, torch.int64, (S, P_max)),
+                  (key_semi, torch.float32, (S, P_max)), (key_fac, torch.float32, (S, P_max)), (pitch, torch.float32, (S,)),
+                  (pitch_frames, torch.float32, (W, Fr)))
+        if rows is not None:
+            tables += ((rows, torch.int32, (W,)),)
+        if any(not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or
+               t.device != pitch_frames.device for t, dtype, shape in tables):
+            raise ValueError("bank_key_glide_: contiguous tensors on one device: key_clock (S,) int64, key_n (S,) int32, key_t "
+                             "(S, P_max) int64, key_semi, key_fac (S, P_max) fp32, pitch (S,) fp32, pitch_frames (W, Fr) fp32 and "
+                             "rows (W,) int32 or None")
+        if not (1 <= P_max <= 64 and S >= 1 and Fr >= 1 and W <= 65535 and int(block) >= 1 and int(n_in) >= 1 and float(hop) > 0):
+            raise ValueError("bank_key_glide_: 1 <= P_max <= 64, W <= 65535, Fr, block, n_in >= 1 and hop > 0")
+        if W:
+            self.call("ddsp_bank_key_glide", _ptr(rows), W, S, _ptr(key_clock), _ptr(key_n), _ptr(key_t), _ptr(key_semi),
+                      _ptr(key_fac), P_max, _ptr(pitch), Fr, int(n_in), int(block), float(hop), _ptr(pitch_frames))
+        return pitch_frames
+
     def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
         """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row
         of the batch behind compact row r, -1 (or anything outside [0, R)) for padding.  In place: cunits (W, Fr, C), cf0 (W, Fr, 1)
@@ -1693,7 +1723,7 @@ class Context:
 
     # -- the rows of a ragged group from several files -------------------------------------------
     def pieces_gather(self, table_dev, n_file_samples_dev, n_file_frames_dev, audio=None, S_max=0, f0=None, volume=None,
-                      key_factor=None, N_max=0):
+                      key_factor=None, N_max=0, key_timeline=None):
         """One launch (`ddsp_pieces_gather`) forms the R rows of a ragged group from a padded batch of F files.  table_dev
         (R, 5) int32 device rows (file, start_frame, n_frames, start_sample, n_samples); n_file_samples_dev / n_file_frames_dev
         (F,) int32 device.  audio (F, T_max) with S_max -> wav (R, S_max); f0, volume (F, Fr_max) and key_factor (F,) with N_max
@@ -1701,6 +1731,11 @@ class Context:
         exact zeros behind every piece.
         A table of (R, 6) rows holds the rows of JOBS (`ddsp_pieces_gather_jobs`): the sixth column is the row's job, the file
         still names the source, and key_factor is (J,), one per job - J jobs over one file read that file's features in place.
+        key_timeline=(bp_off (J + 1,) int32, bp_frame (P,) int32, bp_semi (P,) fp32, bp_fac (P,) fp32), contiguous device tensors,
+        in place of `key_factor` (which stays None) with a table of (R, 6) rows: the jobs' keys move over their files
+        (`ddsp_pieces_gather_keys`).  Job j owns the breakpoints bp_off[j] .. bp_off[j + 1] - 1, in file frames; f0_rows is f0
+        times the factor at every frame's own file frame (include/ddsp_amd.h states the rule), a job with one breakpoint the
+        bits of `key_factor`.  A job whose range is empty or leaves [0, P) gives a row of zeros and the error word.
         Returns (wav, f0_rows, vol_rows), None for the half that was not asked for.  Nothing is read back: a piece outside its
         file gives a row of zeros and raises ValueError from `poll_error()` after a synchronise or from the next call that takes
         the error word."""
@@ -1714,6 +1749,20 @@ class Context:
                 or not table_dev.is_contiguous():
             raise ValueError("pieces_gather: the table must be a contiguous (R, 5) int32 device tensor ((R, 6): rows of jobs)")
         by_job = table_dev.shape[1] == 6
+        if key_timeline is not None:
+            if not by_job or key_factor is not None or not (isinstance(key_timeline, (tuple, list)) and len(key_timeline) == 4):
+                raise ValueError("pieces_gather: key_timeline=(bp_off, bp_frame, bp_semi, bp_fac) goes with a table of (R, 6) rows "
+                                 "and without key_factor")
+            bp_off, bp_frame, bp_semi, bp_fac = key_timeline
+            P = bp_frame.numel() if isinstance(bp_frame, torch.Tensor) else 0
+            for t, dtype in ((bp_off, torch.int32), (bp_frame, torch.int32), (bp_semi, torch.float32), (bp_fac, torch.float32)):
+                if not (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == 1 and
+                        t.is_contiguous()):
+                    raise ValueError(f"pieces_gather: key_timeline holds contiguous 1-d tensors on {self.device}: bp_off, bp_frame "
+                                     "int32, bp_semi, bp_fac fp32")
+            if bp_off.numel() < 2 or P < 1 or bp_semi.numel() != P or bp_fac.numel() != P:
+                raise ValueError("pieces_gather: key_timeline: bp_off (J + 1,) with J >= 1 and bp_frame, bp_semi, bp_fac (P,) with "
+                                 "P >= 1")
         if audio is None and f0 is None:
             raise ValueError("pieces_gather: pass audio, or f0 with key_factor (and volume), or both")
         R, F = table_dev.shape[0], n_file_samples_dev.numel()
@@ -1726,7 +1775,8 @@ class Context:
             wav = torch.empty(R, int(S_max), device=self.device, dtype=torch.float32)
         if f0 is not None:
             Fr_max = dense("f0", f0, None).shape[1] if f0.dim() == 2 and f0.shape[0] == F else -1
-            dense("key_factor", key_factor, (key_factor.numel(),) if by_job and isinstance(key_factor, torch.Tensor) else (F,))
+            if key_timeline is None:
+                dense("key_factor", key_factor, (key_factor.numel(),) if by_job and isinstance(key_factor, torch.Tensor) else (F,))
             f0_rows = torch.empty(R, int(N_max), device=self.device, dtype=torch.float32)
             if volume is not None:
                 dense("volume", volume, (F, Fr_max))
@@ -1738,10 +1788,13 @@ class Context:
         # (a table of jobs with the sample half alone has no key factors: J = 1 lets only job 0 pass, and nothing reads it)
         symbol, jobs = ("ddsp_pieces_gather_jobs", (1 if key_factor is None else key_factor.numel(),)) if by_job else \
             ("ddsp_pieces_gather", ())
+        key = (_ptr(key_factor),)
+        if key_timeline is not None:
+            symbol, jobs = "ddsp_pieces_gather_keys", (bp_off.numel() - 1,)
+            key = (_ptr(bp_off), _ptr(bp_frame), _ptr(bp_semi), _ptr(bp_fac), P)
         if R:
-            self.call(symbol, _ptr(audio), _ptr(f0), _ptr(volume), _ptr(key_factor), _ptr(n_file_samples_dev),
-                      _ptr(n_file_frames_dev), F, T_max, Fr_max, *jobs, _ptr(table_dev), R, int(S_max), int(N_max), _ptr(wav),
-                      _ptr(f0_rows), _ptr(vol_rows))
+            self.call(symbol, _ptr(audio), _ptr(f0), _ptr(volume), *key, _ptr(n_file_samples_dev), _ptr(n_file_frames_dev), F, T_max,
+                      Fr_max, *jobs, _ptr(table_dev), R, int(S_max), int(N_max), _ptr(wav), _ptr(f0_rows), _ptr(vol_rows))
         return wav, f0_rows, vol_rows
 
     # -- the stitch ----------------------------------------------------------------------------

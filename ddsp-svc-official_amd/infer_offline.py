@@ -16,7 +16,8 @@ file into one fp64 device tensor (`stitch_plan_many`, `ddsp_stitch`), one read-b
 device - are that body on a list of one file, which is its own batch and keeps `render`'s seed and speaker rules.
 The same body renders JOBS (`convert_many_device(jobs=, models=)`, `render_jobs_device`, `job_table`): a job is a file, a model, a
 speaker or mix and a key; the files are analysed once whatever the number of jobs, a row names its file for the source and its
-job for key, speaker and output span, and the groups are formed model by model.  `to_pcm16` turns the result into 16-bit PCM on
+job for key, speaker and output span, and the groups are formed model by model.  A job's speaker may be a `SpeakerTimeline` and
+its key a `KeyTimeline`: a voice, or a key, that moves over the file (`ddsp_mix_timeline`, `ddsp_pieces_gather_keys`).  `to_pcm16` turns the result into 16-bit PCM on
 the device (`ddsp_pcm16`), so the read-back is 2 bytes per sample.
 """
 import numbers
@@ -388,17 +389,70 @@ def timeline_tables(speakers, mine, sampling_rate, block_size):
             torch.tensor(w, dtype=torch.float32).reshape(-1, K), torch.tensor(job_ids, dtype=torch.int32).reshape(-1, K))
 
 
+class KeyTimeline:
+    """The key of a job as a function of FILE time (of a bank's slot: of stream time, `StreamBank.set_pitch_timeline`): a key
+    that moves.  points: a non-empty list of (seconds, semitones), times finite, non-negative and ascending, semitones finite.
+    The key is linear IN SEMITONES between two points and stays before the first and after the last; the f0 factor is
+    2 ** (key / 12).  A timeline of one point is a constant key, with that key's bits (include/ddsp_amd.h states the rule at
+    `ddsp_pieces_gather_keys`).  ValueError for anything else."""
+
+    def __init__(self, points):
+        if not (isinstance(points, (list, tuple)) and len(points)):
+            raise ValueError("KeyTimeline: points must be a non-empty list of (seconds, semitones)")
+        self.points, last = [], 0.0
+        for n, point in enumerate(points):
+            if not (isinstance(point, (tuple, list)) and len(point) == 2):
+                raise ValueError(f"KeyTimeline: point {n} must be (seconds, semitones), got {point!r}")
+            t, key = point
+            if not (isinstance(t, numbers.Real) and not isinstance(t, bool) and t >= 0 and t == t and t != float("inf")):
+                raise ValueError(f"KeyTimeline: point {n}: the time must be a finite number of seconds >= 0, got {t!r}")
+            if t < last:
+                raise ValueError(f"KeyTimeline: point {n}: times must ascend, {t!r} follows {last!r}")
+            last = t
+            if not (isinstance(key, numbers.Real) and not isinstance(key, bool) and key == key and abs(key) != float("inf")):
+                raise ValueError(f"KeyTimeline: point {n}: the key must be a finite number of semitones, got {key!r}")
+            self.points.append((float(t), float(key)))
+
+    def frames(self, sampling_rate, block_size):
+        """-> (breakpoint frames, semitones): `SpeakerTimeline.frames`' rule - a point's frame is int(round(t * sampling_rate /
+        block_size)); ValueError when two points land on one frame (a jump has no slope: move one of them by a frame)."""
+        at = [int(round(t * sampling_rate / block_size)) for t, _ in self.points]
+        for n in range(1, len(at)):
+            if at[n] <= at[n - 1]:
+                raise ValueError(f"KeyTimeline: points {n - 1} and {n} ({self.points[n - 1][0]} s, {self.points[n][0]} s) both "
+                                 f"land on frame {at[n]} at {sampling_rate} Hz and block size {block_size}")
+        return at, [key for _, key in self.points]
+
+
+def key_tables(keys, sampling_rate, block_size):
+    """The tables `ddsp_pieces_gather_keys` takes for the J jobs whose keys are `keys` (a number of semitones or a `KeyTimeline`
+    each) -> CPU tensors (bp_off (J + 1,) int32, bp_frame (P,) int32, bp_semi (P,) fp32, bp_fac (P,) fp32).  A `KeyTimeline`
+    gives its breakpoints in file frames; a number is the one breakpoint at frame 0.  Every breakpoint's factor is
+    2 ** (float(key) / 12), a Python float stored to fp32: `job_table`'s `key_factor` of a constant key."""
+    off, frame, semi = [0], [], []
+    for key in keys:
+        at, values = key.frames(sampling_rate, block_size) if isinstance(key, KeyTimeline) else ([0], [float(key)])
+        frame.extend(at)
+        semi.extend(values)
+        off.append(len(frame))
+    return (torch.tensor(off, dtype=torch.int32), torch.tensor(frame, dtype=torch.int32), torch.tensor(semi, dtype=torch.float32),
+            torch.tensor([2 ** (float(k) / 12) for k in semi], dtype=torch.float32))
+
+
 def job_table(pieces, n_files, jobs, models):
     """The tables of a conversion of `jobs` over analysed files, made and checked on the host (nothing is launched).  pieces:
     `piece_table` rows of the `n_files` files; jobs: a sequence of (file, model_index, spk, key) - spk a 1-based speaker id, a
     mix dict {id: weight} or a `SpeakerTimeline` (a voice that changes over the file; it stands in `speakers` as it is, its ids
-    checked against the job's model and its points against that model's frame rate), key in semitones; models: the synthesisers, which share the analysis and the stitch and so agree in
+    checked against the job's model and its points against that model's frame rate), key in semitones, a number or a `KeyTimeline`
+    (a key that moves over the file; its points are checked against the job's model's frame rate); models: the synthesisers, which share the analysis and the stitch and so agree in
     sampling rate, block size, unit width and device.  -> a dict:
       rows          [(file, start_frame, n_frames, start_sample, n_samples, job)]: job after job, each with ALL pieces of its file
                     in the file's order - the SAME source columns for every job over that file, which `ddsp_pieces_gather_jobs`
                     reads in place; the sixth column names whose key factor (and speaker, and output span) the row takes;
       piece_of_row  for every row, its index in `pieces` (whose units it takes);
-      model_of_job, speakers (an int or a dict per job), key_factor (2 ** (key / 12) per job, Python floats);
+      model_of_job, speakers (an int or a dict per job), key_factor (2 ** (key / 12) per job, Python floats; None for a job
+                    whose key is a `KeyTimeline`);
+      keys          every job's key as `key_tables` takes it: a float, or the `KeyTimeline` as it is;
       starts_per_job  the start frames of every job's rows, as `stitch_plan_many` takes them with jobs in the place of files.
     ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4-tuple, a file or
     model index out of range, a speaker id outside [1, n_spk] of the JOB's model, or a mix with no or too many speakers."""
@@ -413,7 +467,8 @@ def job_table(pieces, n_files, jobs, models):
                 raise ValueError(f"job_table: models[{k}].{field} is {b}, models[0].{field} is {a}: the models of one call agree "
                                  f"in {', '.join(MODEL_FIELDS)}")
     per_file = [[i for i, row in enumerate(pieces) if row[0] == k] for k in range(int(n_files))]
-    table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": []}
+    table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": [],
+             "keys": []}
     for j, job in enumerate(jobs):
         if not (isinstance(job, (tuple, list)) and len(job) == 4):
             raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key), got {job!r}")
@@ -442,14 +497,20 @@ def job_table(pieces, n_files, jobs, models):
         for i in ids:
             if not (isinstance(i, numbers.Integral) and 1 <= i <= n_spk):
                 raise ValueError(f"job_table: job {j}: speaker id {i!r} is outside [1, {n_spk}] of models[{m}]")
-        if not isinstance(key, numbers.Real):
-            raise ValueError(f"job_table: job {j}: key must be a number of semitones, got {key!r}")
+        if isinstance(key, KeyTimeline):
+            try:
+                key.frames(_model_field(models[m], "sampling_rate"), _model_field(models[m], "block_size"))
+            except ValueError as e:
+                raise ValueError(f"job_table: job {j}: {e}") from None
+        elif not isinstance(key, numbers.Real):
+            raise ValueError(f"job_table: job {j}: key must be a number of semitones or a KeyTimeline, got {key!r}")
         table["rows"].extend(tuple(pieces[i]) + (j,) for i in per_file[file])
         table["piece_of_row"].extend(per_file[file])
         table["starts_per_job"].append([pieces[i][1] for i in per_file[file]])
         table["model_of_job"].append(int(m))
         table["speakers"].append(spk)
-        table["key_factor"].append(2 ** (float(key) / 12))
+        table["key_factor"].append(None if isinstance(key, KeyTimeline) else 2 ** (float(key) / 12))
+        table["keys"].append(key if isinstance(key, KeyTimeline) else float(key))
     return table
 
 
@@ -729,12 +790,13 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
                              f"cover {files['n_frames'][k]} frames of the file")
     budget = 0 if batch_frames is None else int(batch_frames)
     if jobs is None:
-        rows, unit_of, owner, n_out, key_factor = pieces, range(len(pieces)), 0, F, files["key_factor"]
+        rows, unit_of, owner, n_out, key = pieces, range(len(pieces)), 0, F, {"key_factor": files["key_factor"]}
         groups = group_pieces(pieces, budget)
         model_of_group = [model] * len(groups)
     else:
         models, table = jobs
-        rows, unit_of, owner, n_out, key_factor = table["rows"], table["piece_of_row"], 5, len(table["model_of_job"]), table["key_factor_dev"]
+        rows, unit_of, owner, n_out = table["rows"], table["piece_of_row"], 5, len(table["model_of_job"])
+        key = {"key_timeline": table["key_tables_dev"]} if "key_tables_dev" in table else {"key_factor": table["key_factor_dev"]}
         numbered = job_groups(table, len(models), budget)
         groups, model_of_group = [group for _, group in numbered], [models[m] for m, _ in numbered]
     given = None if jobs is None else rows
@@ -745,7 +807,7 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
         counts = [rows[i][2] for i in group]
         u, _ = stack_rows([units[unit_of[i]][0] for i in group])
         _, f, v = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
-                                    volume=files["volume"], key_factor=key_factor, N_max=max(counts))
+                                    volume=files["volume"], N_max=max(counts), **key)
         kw = {} if seed_of_group is None else {"noise_seed": seed_of_group(g, [rows[i][1] for i in group])}
         if noise is not None:
             kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
@@ -757,19 +819,20 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
     sr_o = sr
     if enhancer is not None and rows:
         out, sr_o = _enhance_many(ctx, enhancer, out, files, sr, block, enhancer_adaptive_key,
-                                  0 if enhancer_batch_samples is None else enhancer_batch_samples, given, key_factor)
+                                  0 if enhancer_batch_samples is None else enhancer_batch_samples, given, key)
     per_out = [[i for i, row in enumerate(rows) if row[owner] == k] for k in range(n_out)]
     spans, p, fade, total = stitch_plan_many([[rows[i][1] for i in idx] for idx in per_out],
                                              [[out[i].shape[-1] for i in idx] for idx in per_out], block, sr, sr_o)
     return ctx.stitch(out, p, fade, total), spans, sr_o
 
 
-def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples, rows=None, key_factor=None):
+def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples, rows=None, key=None):
     """The device path's enhancer loop over the gated pieces of all files: one `Enhancer.enhance_batch` per group of
     `group_segments` over the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group).
-    rows, key_factor: `job_table`'s rows and the jobs' key factors in place of the files' (one enhancer serves all models)."""
+    rows, key: `job_table`'s rows and the jobs' keys - `pieces_gather`'s keyword `key_factor` or `key_timeline` with its value -
+    in place of the files' (one enhancer serves all models)."""
     pieces = files["pieces"] if rows is None else rows
-    key_factor = files["key_factor"] if key_factor is None else key_factor
+    key = {"key_factor": files["key_factor"]} if key is None else key
     groups = group_segments([g.shape[-1] for g in gated], int(enhancer_batch_samples))
     table, _, bounds = _upload_pieces(ctx, files, groups, rows)
     out, sr_o = [None] * len(gated), sr
@@ -777,7 +840,7 @@ def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer
         wav, counts = stack_rows([gated[i][0] for i in group])
         n_f0 = [pieces[i][2] for i in group]
         _, tracks, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
-                                         key_factor=key_factor, N_max=max(n_f0))
+                                         N_max=max(n_f0), **key)
         got, sr_o, n_out = enhancer.enhance_batch(wav, sr, tracks[:, :, None], block, counts, adaptive_key=adaptive_key, n_f0=n_f0)
         for j, i in enumerate(group):
             out[i] = got[j:j + 1, :n_out[j]]
@@ -798,7 +861,7 @@ def _models_of(who, model, models):
 
 @torch.no_grad()
 def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
-                       batch_frames=None, noise=None, enhancer_batch_samples=None):
+                       batch_frames=None, noise=None, enhancer_batch_samples=None, key_tables_always=False):
     """`render_many_device` for JOBS over the files of ONE `analyse_many` (analysed with keys=0: the key is the job's) -> (fp64
     device tensor holding every job, [(base, total)] per job in job order, sample rate).  jobs: a sequence of (file,
     model_index, spk, key) into `files` and `models` (`job_table` states and checks them: ValueError before any launch).  Job j
@@ -812,6 +875,11 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     group's rows, wherever in their files the rows lie, and its id and dict jobs are timelines of one breakpoint.  The enhancer - one for all models, one `enhancer_adaptive_key` per
     call - takes ragged groups over the rows of all jobs, and ONE `ddsp_stitch` places every job (`stitch_plan_many` over jobs:
     even bases, no fade across jobs).
+    A job's key may be a `KeyTimeline`, a key that moves over the file.  Without one among the jobs the call is the call above,
+    bit for bit.  With one, EVERY gather of the call - the render groups and the enhancer's f0 - goes through
+    `ddsp_pieces_gather_keys` with the `key_tables` of all jobs, uploaded once: a row's f0 is its file's times the factor at
+    every frame's own file frame, a numeric key is the one breakpoint at frame 0 and keeps its bits, and the enhancer
+    (`enhancer_adaptive_key='auto'` too) sees the same moving f0.  key_tables_always: take that path whatever the keys are.
     noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
     `models` order - draws with (noise_seed + g * 2**32) mod 2**64."""
     models = _models_of("render_jobs_device", None, models)
@@ -820,7 +888,12 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     J = len(table["model_of_job"])
     if J and noise is not None and [len(x) for x in noise] != [len(s) for s in table["starts_per_job"]]:
         raise ValueError("render_jobs_device: noise must hold one list per job with one draw per slice of its file")
-    if J:
+    if J and (key_tables_always or any(isinstance(k, KeyTimeline) for k in table["keys"])):
+        # a key that moves: the breakpoint tables of ALL jobs go up once and serve every gather of the call
+        from realtime import _model_field
+        rate = (_model_field(models[0], "sampling_rate"), _model_field(models[0], "block_size"))
+        table["key_tables_dev"] = tuple(t.to(dev) for t in key_tables(table["keys"], *rate))
+    elif J:
         table["key_factor_dev"] = torch.tensor(table["key_factor"], dtype=torch.float32).to(dev)
 
     def speaker(file_of_row, order):

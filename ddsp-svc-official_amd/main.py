@@ -8,7 +8,8 @@ stitched waveform on the device and is read back once.
 
 `--jobs` names a YAML list of entries {model: <model.pt, default -m>, id: <speaker id, default 1> | mix: {id: weight} |
 timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...] (a voice that glides over the file,
-`infer_offline.SpeakerTimeline`), key: <semitones, default 0>, suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
+`infer_offline.SpeakerTimeline`), key: <semitones, default 0> | key_timeline: [{at: <seconds>, key: <semitones>}, ...] (a key
+that moves over the file, `infer_offline.KeyTimeline`), suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
 give `name_s.wav`.  All of it is ONE `convert_many_device(jobs=...)` - every file analysed once - and one read-back; `-id`,
 `-mix` and `-k` are then unused.
 
@@ -170,15 +171,12 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
         raise ValueError(f"--jobs: {cmd.jobs} must hold a non-empty list of {{model, id | mix, key, suffix}} entries")
     paths, models, voices = [os.path.abspath(cmd.model_path)], [model], []
     for n, e in enumerate(entries):
-        unknown = set(e) - {"model", "id", "mix", "timeline", "key", "suffix"}
-        if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or not str(e.get("suffix", "")):
-            raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key and a non-empty suffix, got {e!r}")
+        spk, key = _job_entry(n, e)
         path = os.path.abspath(e.get("model", cmd.model_path))
         if path not in paths:
             paths.append(path)
             models.append(load_model(path, device=device)[0])
-        spk = _timeline(n, e["timeline"]) if "timeline" in e else e["mix"] if "mix" in e else int(e.get("id", 1))
-        voices.append((paths.index(path), spk, float(e.get("key", 0)), str(e["suffix"])))
+        voices.append((paths.index(path), spk, key, str(e["suffix"])))
     if len({v[3] for v in voices}) != len(voices):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
@@ -195,12 +193,34 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
     return result, sr_o
 
 
+def _job_entry(n, e):
+    """Entry n of the `--jobs` list -> (spk, key) as `infer_offline.job_table` takes them: the speaker from `id`, `mix` or
+    `timeline` (at most one of them; default id 1), the key from `key` or `key_timeline` (not both; default 0).  ValueError for an
+    unknown field, two speakers, two keys or a missing suffix."""
+    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "suffix"}
+    if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or ("key" in e and "key_timeline" in e) or \
+            not str(e.get("suffix", "")):
+        raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key or key_timeline and a non-empty suffix, "
+                         f"got {e!r}")
+    spk = _timeline(n, e["timeline"]) if "timeline" in e else e["mix"] if "mix" in e else int(e.get("id", 1))
+    key = _key_timeline(n, e["key_timeline"]) if "key_timeline" in e else float(e.get("key", 0))
+    return spk, key
+
+
 def _timeline(n, points):
     """An entry's `timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...]` -> `SpeakerTimeline`."""
     from infer_offline import SpeakerTimeline
     if not (isinstance(points, list) and points and all(isinstance(p, dict) and set(p) in ({"at", "id"}, {"at", "mix"}) for p in points)):
         raise ValueError(f"--jobs: entry {n}: timeline is a non-empty list of {{at, id}} or {{at, mix}} points, got {points!r}")
     return SpeakerTimeline([(p["at"], p["id"] if "id" in p else p["mix"]) for p in points])
+
+
+def _key_timeline(n, points):
+    """An entry's `key_timeline: [{at: <seconds>, key: <semitones>}, ...]` -> `KeyTimeline`."""
+    from infer_offline import KeyTimeline
+    if not (isinstance(points, list) and points and all(isinstance(p, dict) and set(p) == {"at", "key"} for p in points)):
+        raise ValueError(f"--jobs: entry {n}: key_timeline is a non-empty list of {{at, key}} points, got {points!r}")
+    return KeyTimeline([(p["at"], p["key"]) for p in points])
 
 
 if __name__ == "__main__":

@@ -418,7 +418,9 @@ class _Rows:
     def __init__(self, bank, W, compact):
         self.bank, self.W, self.A = bank, int(W), int(W)
         self.graph = self.bank_graph = self.enhancer_graph = None
-        self.rows = self.request = self.w_frames = None
+        self.rows = self.request = self.w_frames = self.pitch_frames = None
+        if bank.pitch_breakpoints is not None:
+            self.pitch_frames = torch.ones(self.W, bank.frames, device=bank.device)
         if bank.glide_breakpoints is not None:
             self.w_frames = torch.zeros(self.W, bank.frames, bank.max_mix, device=bank.device)
             self.w_frames[:, :, 0] = 1.0
@@ -449,9 +451,15 @@ class _Rows:
         """The speaker term of this instance's synthesis (`spk_mix_rows=`): a mix per row, or per frame on a bank that glides."""
         return self.spk_ids, (self.spk_w if self.w_frames is None else self.w_frames)
 
+    @property
+    def pitch_term(self):
+        """The pitch term of this instance's chain: a factor per row, or per frame on a bank with `pitch_breakpoints`."""
+        return self.pitch if self.pitch_frames is None else self.pitch_frames
+
     def push(self, ctx, windows, blocks):
         """`graphed.block_chain`'s push step: `windows` (this instance's) come up to date with `blocks` (W, block); on a bank
-        with `glide_breakpoints` the weights of the block's frames follow, and the clocks of the call's slots advance."""
+        with `glide_breakpoints` the weights of the block's frames follow, and the clocks of the call's slots advance; on one
+        with `pitch_breakpoints` the f0 factors of the block's frames and the key clocks likewise."""
         b = self.bank
         if self.rows is None:
             ctx.stream_push_(windows, blocks)
@@ -462,6 +470,9 @@ class _Rows:
         if self.w_frames is not None:
             ctx.bank_glide_(self.rows, b.glide_clock, b.glide_n, b.glide_t, b.glide_w, b.spk_w, self.w_frames, b.n_in, b.block,
                             b.hop_size)
+        if self.pitch_frames is not None:
+            ctx.bank_key_glide_(self.rows, b.key_clock, b.key_n, b.key_t, b.key_semi, b.key_fac, b.pitch, self.pitch_frames, b.n_in,
+                                b.block, b.hop_size)
         return windows
 
     def scatter(self):
@@ -561,14 +572,30 @@ class StreamBank:
     a bank without `glide_breakpoints`, with more points than it, two points on one sample, more ids than `max_mix` or an id
     outside the slot's model.
 
+    A key that glides (`pitch_breakpoints=P_max`, an int in 1..64; None: nothing of this is allocated, captured or launched, and
+    the bank is the bank above, bit for bit).  Independent of `glide_breakpoints`, and allowed with `models=`, `active_widths=`
+    and the enhancer: the pitch is applied to f0 in the shared analysis of a block, in front of every per-model row gather.
+    Every slot then has `key_clock` (S,) int64, `key_n` (S,) int32 (0 = no timeline), `key_t` (S, P_max) int64 in device samples
+    and `key_semi` / `key_fac` (S, P_max) fp32, the breakpoints' semitones and their factors 2 ** (key / 12) formed on the host
+    as `set_pitch` forms its one.  `set_pitch_timeline(slot, infer_offline.KeyTimeline, at=0.0)` writes them.  Every push ends
+    with one launch of `ddsp_bank_key_glide` over the call's rows (beside `ddsp_bank_glide` when both are on): frame t of a
+    window has stream time key_clock + block - n_in + t * hop_size and gets the timeline's factor there - linear in semitones
+    between two points, a point's stored factor at and outside the points and on constant stretches, so a constant timeline
+    emits the bits of `set_pitch` -, the slot's `pitch` where it has no timeline and 1 on a padding row; the key clocks of the
+    call's slots advance by one block.  The chain multiplies f0 with these per-frame factors (`_Rows.pitch_frames` (W, Fr))
+    where it multiplied with `pitch`.  Part of the captured block under `push_audio`: `graph_builds` is what it was, and
+    setting, ending (`set_pitch`) or restarting (`reset`) a timeline captures nothing.  `last_pitch` (A, Fr) holds the block's
+    factors.  The paused-slot rule covers `key_clock`, `key_n`, `key_t`, `key_semi` and `key_fac`.  Refused:
+    `set_pitch_timeline` on a bank without `pitch_breakpoints`, with more points than it, or two points on one sample.
+
     Not in the bank: streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
     grows after construction; a weight set per row inside the control network's kernels; an enhancer per model; a glide on a
-    bank with `models=`; a pitch timeline."""
+    bank with `models=`."""
 
     def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
-                 active_widths=None, models=None, model_widths=None, glide_breakpoints=None):
+                 active_widths=None, models=None, model_widths=None, glide_breakpoints=None, pitch_breakpoints=None):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
@@ -579,7 +606,10 @@ class StreamBank:
             if models is not None:
                 raise ValueError("StreamBank: glide_breakpoints= with models= is not supported (the per-model row gather moves a mix "
                                  "per row, not per frame)")
-        self.glide_breakpoints = glide_breakpoints
+        if pitch_breakpoints is not None and (isinstance(pitch_breakpoints, bool) or not isinstance(pitch_breakpoints, int) or
+                                              not 1 <= pitch_breakpoints <= MAX_GLIDE_POINTS):
+            raise ValueError(f"StreamBank: pitch_breakpoints must be an int in 1..{MAX_GLIDE_POINTS}, got {pitch_breakpoints!r}")
+        self.glide_breakpoints, self.pitch_breakpoints = glide_breakpoints, pitch_breakpoints
         self.active_widths = None if active_widths is None else _check_active_widths(active_widths, self.S)
         if models is None and model_widths is not None:
             raise ValueError("StreamBank: model_widths= needs models=")
@@ -639,9 +669,17 @@ class StreamBank:
             self.glide_n = torch.zeros(self.S, dtype=torch.int32, device=dev)
             self.glide_t = torch.zeros(self.S, glide_breakpoints, dtype=torch.int64, device=dev)
             self.glide_w = torch.zeros(self.S, glide_breakpoints, self.max_mix, device=dev)
+        self.key_clock = self.key_n = self.key_t = self.key_semi = self.key_fac = None
+        if pitch_breakpoints is not None:                            # a clock and a key timeline per slot (`set_pitch_timeline`)
+            self.key_clock = torch.zeros(self.S, dtype=torch.int64, device=dev)
+            self.key_n = torch.zeros(self.S, dtype=torch.int32, device=dev)
+            self.key_t = torch.zeros(self.S, pitch_breakpoints, dtype=torch.int64, device=dev)
+            self.key_semi = torch.zeros(self.S, pitch_breakpoints, device=dev)
+            self.key_fac = torch.ones(self.S, pitch_breakpoints, device=dev)
         self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
         self.last_mix_w = None           # (A, Fr, max_mix): the block's per-frame weights on a bank with `glide_breakpoints`
+        self.last_pitch = None           # (A, Fr): the block's per-frame f0 factors on a bank with `pitch_breakpoints`
         if enhancer is not None:
             self.enhancer_request = torch.full((self.S,), request, dtype=torch.int32, device=dev)   # -1 = 'auto', per slot
             self._n_end_by_key = torch.tensor(ends, dtype=torch.int32).to(dev)
@@ -679,8 +717,8 @@ class StreamBank:
         if self.f0_extractor is not None:
             rows.bank_graph = graphed.GraphedBlock(
                 self.model if shared else None, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
-                self.silence_front, rows.pitch, self.threshold_db, mix_rows=rows.mix, f0_dither=self.f0_dither, push=rows.push,
-                keep=() if self.glide_clock is None else (self.glide_clock,))   # (the capture's runs advance the clocks)
+                self.silence_front, rows.pitch_term, self.threshold_db, mix_rows=rows.mix, f0_dither=self.f0_dither, push=rows.push,
+                keep=[c for c in (self.glide_clock, self.key_clock) if c is not None])   # (the capture's runs advance the clocks)
         elif shared:
             rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix)
         if self.enhancer is not None:
@@ -802,9 +840,45 @@ class StreamBank:
         self._write_mix(slot, *tables)
 
     def set_pitch(self, slot, semitones):
-        """Slot `slot` is shifted by `semitones` from the next block on (f0 * 2 ** (semitones / 12)): one device write."""
+        """Slot `slot` is shifted by `semitones` from the next block on (f0 * 2 ** (semitones / 12)): one device write.  On a bank
+        with `pitch_breakpoints` it ends the slot's key timeline."""
         slot = self._slot(slot)
         self.pitch[slot:slot + 1].fill_(2 ** (float(semitones) / 12))
+        if self.key_n is not None:
+            self.key_n[slot:slot + 1].zero_()
+
+    def set_pitch_timeline(self, slot, timeline, at=0.0):
+        """Slot `slot`'s key follows `timeline` (an `infer_offline.KeyTimeline`) from the next block on, in STREAM time, as
+        `set_timeline` has it for the voice: time 0 is the first sample pushed after this call, or `at` seconds into the timeline
+        with `at=`; a point at t seconds sits at int(round(t * samplerate)) device samples.  Frames of the window older than the
+        first point hold its key, frames behind the last point the last one's; between two the key is linear in semitones.
+        Writes the slot's rows of `key_t` / `key_semi` / `key_fac`, `key_n` and `key_clock`: device rows only, no capture.
+        `set_pitch` ends the timeline.  ValueError, before any write: a bank built without `pitch_breakpoints`, more points than
+        it, two points on one sample."""
+        from infer_offline import KeyTimeline
+        if self.pitch_breakpoints is None:
+            raise ValueError("StreamBank.set_pitch_timeline: this bank was built without pitch_breakpoints=")
+        slot = self._slot(slot)
+        if not isinstance(timeline, KeyTimeline):
+            raise ValueError(f"StreamBank.set_pitch_timeline: timeline must be an infer_offline.KeyTimeline, got "
+                             f"{type(timeline).__name__}")
+        if isinstance(at, bool) or not isinstance(at, (int, float)) or at != at or abs(at) == float("inf"):
+            raise ValueError(f"StreamBank.set_pitch_timeline: at must be a finite number of seconds, got {at!r}")
+        times = [int(round(t * self.samplerate)) for t, _ in timeline.points]
+        if len(times) > self.pitch_breakpoints:
+            raise ValueError(f"StreamBank.set_pitch_timeline: {len(times)} points, the bank holds pitch_breakpoints = "
+                             f"{self.pitch_breakpoints} per slot")
+        for n in range(1, len(times)):
+            if times[n] <= times[n - 1]:
+                raise ValueError(f"StreamBank.set_pitch_timeline: points {n - 1} and {n} ({timeline.points[n - 1][0]} s, "
+                                 f"{timeline.points[n][0]} s) both land on sample {times[n]} at {self.samplerate} Hz")
+        pad = self.pitch_breakpoints - len(times)
+        keys = [key for _, key in timeline.points]
+        self.key_t[slot].copy_(torch.tensor(times + [0] * pad, dtype=torch.int64))
+        self.key_semi[slot].copy_(torch.tensor(keys + [0.0] * pad, dtype=torch.float32))
+        self.key_fac[slot].copy_(torch.tensor([2 ** (float(k) / 12) for k in keys] + [1.0] * pad, dtype=torch.float32))
+        self.key_n[slot:slot + 1].fill_(len(times))
+        self.key_clock[slot:slot + 1].fill_(int(round(at * self.samplerate)))
 
     def set_enhancer_key(self, slot, key):
         """Slot `slot` is enhanced with the adaptive key `key` (a whole number in 0..enhancer_max_key) or by the 'auto' rule from
@@ -817,12 +891,15 @@ class StreamBank:
 
     def reset(self, slot):
         """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set).  On
-        a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning."""
+        a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning;
+        on one with `pitch_breakpoints` the key clock and the key timeline likewise."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
         if self.glide_clock is not None:
             self.glide_clock[slot:slot + 1].zero_()
+        if self.key_clock is not None:
+            self.key_clock[slot:slot + 1].zero_()
 
     def _check_blocks(self, blocks, A, rows="S"):
         if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
@@ -898,7 +975,7 @@ class StreamBank:
             import graphed
             sig, f0, units, volume = graphed.block_chain(
                 hipddsp.context_for(self.device), self.model if self._model_rows is None else None, self.units_encoder,
-                self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch,
+                self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch_term,
                 self.threshold_db, self.hop, {"spk_id": None, "spk_mix_rows": rows.mix}, noise, self.f0_dither,
                 push=rows.push)
         if self._model_rows is not None:
@@ -906,6 +983,8 @@ class StreamBank:
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
         if rows.w_frames is not None:
             self.last_mix_w, = rows.real(rows.w_frames)
+        if rows.pitch_frames is not None:
+            self.last_pitch, = rows.real(rows.pitch_frames)
         self.last_active = active
         return self._splice(rows, sig, f0, rand_ini)
 
@@ -929,7 +1008,8 @@ class StreamBank:
         rows.select(active)
         rows.push(ctx, rows.windows, blocks)
         units = rows.pad(units.to(self.device))
-        f0 = rows.pad(f0.to(self.device, torch.float32)) * rows.pitch[:, None, None]
+        f0 = rows.pad(f0.to(self.device, torch.float32)) * \
+            (rows.pitch[:, None, None] if rows.pitch_frames is None else rows.pitch_frames[:, :, None])
         volume = ctx.volume_extract(rows.windows, self.hop_size)
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)
@@ -943,5 +1023,7 @@ class StreamBank:
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
         if rows.w_frames is not None:
             self.last_mix_w, = rows.real(rows.w_frames)
+        if rows.pitch_frames is not None:
+            self.last_pitch, = rows.real(rows.pitch_frames)
         self.last_active = active
         return self._splice(rows, sig, f0, rand_ini)

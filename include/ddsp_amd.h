@@ -460,6 +460,19 @@ int ddsp_bank_scatter(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, i
 int ddsp_bank_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, int64_t* clock, const int32_t* bp_n,
                     const int64_t* bp_t, const float* bp_w, int P_max, const float* spk_w, int K, int64_t Fr, int64_t n_in,
                     int64_t block, double hop, float* w_frames);
+/* The KEY glide of a bank (realtime.StreamBank, `pitch_breakpoints=`): the per-frame f0 factors of one call's W rows from
+ * per-SLOT state, and the advance of those slots' key clocks, one launch per block: ddsp_bank_glide's launch with a key
+ * timeline (the rule stated at ddsp_pieces_gather_keys) in place of the weights.  Per slot s < S, all DEVICE: key_clock[s] int64
+ * (read AND written); key_n[s] int32, clamped to [0, P_max], 0 = no timeline; key_t[s] (P_max) int64, the breakpoint times in
+ * device samples, strictly increasing; key_semi[s], key_fac[s] (P_max) fp32, their semitones and host-formed factors; pitch[s]
+ * fp32, the slot's one factor.  rows, padding rows, c = key_clock[s] + block, tau = (double)(c - n_in) + t * hop, the clock's
+ * store behind the barrier and the paused-slot rule are ddsp_bank_glide's.  pitch_frames (W, Fr) fp32: a padding row gets 1 in
+ * every frame; a slot with key_n[s] == 0 gets pitch[s]; a slot with a timeline the rule's factor at tau.  DDSP_ERR_ARG, and
+ * nothing written, for a null pointer (rows excepted), W > 65535, P_max outside [1, 64], Fr < 1 or block < 1.  Does not
+ * synchronise, allocate or read back. */
+int ddsp_bank_key_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W, int S, int64_t* key_clock, const int32_t* key_n,
+                        const int64_t* key_t, const float* key_semi, const float* key_fac, int P_max, const float* pitch,
+                        int64_t Fr, int64_t n_in, int64_t block, double hop, float* pitch_frames);
 
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
@@ -543,6 +556,27 @@ int ddsp_pieces_gather_jobs(ddsp_ctx* ctx, void* stream, const float* audio, con
                             const float* key_factor, const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F,
                             int64_t T_max, int64_t Fr_max, int64_t J, const int32_t* table, int64_t R, int64_t S_max,
                             int64_t N_max, float* wav, float* f0_rows, float* vol_rows);
+/* The rows of jobs whose KEY moves over the file: ddsp_pieces_gather_jobs with a breakpoint range per job in place of
+ * key_factor (J).  THE KEY TIMELINE RULE (csrc/key_timeline.h; ddsp_bank_key_glide applies it too): a timeline is n >= 1
+ * breakpoints with times strictly increasing, each with its key in semitones (fp32) and the f0 factor the host formed for it,
+ * 2 ** (key / 12) stored to fp32 - what key_factor holds for a constant key.  The key at time tau is linear in semitones between
+ * two breakpoints, the first one's before them and the last one's after them.  The STORED factor of a breakpoint is used where no
+ * slope is at work: tau before the first breakpoint (the first one's), behind the last (the last one's), exactly on a breakpoint
+ * (its own), or between two of equal semitones (the earlier one's).  Elsewhere the factor is
+ * exp2((s0 + (s1 - s0) * ((tau - t0) / (t1 - t0))) / 12.0) in fp64, every step one rounded operation, rounded to fp32.  So a
+ * one-breakpoint timeline, and every constant stretch, multiplies with the bits of the constant key.
+ * Job j owns the breakpoints bp_off[j] .. bp_off[j + 1] - 1 (bp_off (J + 1) int32, a prefix table): bp_frame (P) int32 their
+ * positions in FILE frames, strictly increasing inside a job, bp_semi (P) and bp_fac (P) fp32.  Frame t < n_frames of row r is
+ * file frame start_frame + t: f0_rows[r][t] = f0[file][start_frame + t] * factor(start_frame + t), one rounded fp32 product;
+ * exact zeros behind n_frames.  wav and vol_rows are ddsp_pieces_gather_jobs' bits.  A job outside [0, J), or one whose
+ * breakpoint range is empty or leaves [0, P), is tested before any address is formed from it: zeros and the device error word,
+ * like a file outside [0, F).  f0, f0_rows (and volume, vol_rows) may be NULL as above; the breakpoint tables never.  1 <= P <
+ * 2^31.  Everything else as above. */
+int ddsp_pieces_gather_keys(ddsp_ctx* ctx, void* stream, const float* audio, const float* f0, const float* volume,
+                            const int32_t* bp_off, const int32_t* bp_frame, const float* bp_semi, const float* bp_fac, int64_t P,
+                            const int32_t* n_file_samples, const int32_t* n_file_frames, int64_t F, int64_t T_max,
+                            int64_t Fr_max, int64_t J, const int32_t* table, int64_t R, int64_t S_max, int64_t N_max, float* wav,
+                            float* f0_rows, float* vol_rows);
 /* The speaker timelines of jobs -> the per-frame mix of one render group (ddsp_unit2ctrl_fwd_framemix's tables), one launch.
  * table (R, 6) as above.  Job j owns the breakpoints bp_off[j] .. bp_off[j + 1] - 1 (bp_off (J + 1) int32, a prefix table):
  * bp_frame (P) int32 their positions in FILE frames, strictly increasing inside a job; bp_w (P, K) fp32 the weights of the

@@ -42,7 +42,14 @@ beyond the session's run-to-run spread is a finding); `glide`, the bank of this 
 every slot that ramps through the whole run (one more launch per block, and the per-frame weights in the prenet's epilogue).
 
     python tools/rt_bank_time.py --baseline-tree <parent checkout> --glide --streams 16 --shapes config5
-                                 [--out profiles/rt_bank_glide_time.json]"""
+                                 [--out profiles/rt_bank_glide_time.json]
+
+`--pitch-glide` times what a key that glides costs a bank, the same way: `parent`, the bank of the baseline tree; `unused`, the
+bank of this tree with `pitch_breakpoints=4` and no timeline set (one more launch per block, which copies each slot's one
+factor to its frames); `pitch`, the same bank with a key timeline on every slot that ramps through the whole run.
+
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> --pitch-glide --streams 16 --shapes config5
+                                 [--out profiles/rt_bank_pitch_time.json]"""
 import argparse
 import contextlib
 import json
@@ -64,7 +71,7 @@ SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16
 
 
 def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), active=None, models=None, streams=STREAMS):
-    """One leg in this process: `which` = 'bank' | 'solo' | 'plain' | 'parent' | 'glide', the package taken from `tree`.  Prints one
+    """One leg in this process: `which` = 'bank' | 'solo' | 'plain' | 'parent' | 'glide' | 'unused' | 'pitch', the package taken from `tree`.  Prints one
     JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -119,6 +126,8 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
                         kw.update(models=pool)
                     if which == "glide":
                         kw.update(glide_breakpoints=4)
+                    if which in ("unused", "pitch"):
+                        kw.update(pitch_breakpoints=4)
                     bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
                     for s in range(S if "models" in kw else 0):
                         bank.set_model(s, s % len(pool))
@@ -128,6 +137,12 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
                         for s in range(S):
                             at = [span * n / (3 + s % 3) for n in range(4)]
                             bank.set_timeline(s, SpeakerTimeline([(t, {1 + s % 7: 1.0 - n % 2, 8 + s % 5: float(n % 2)}) for n, t in enumerate(at)]))
+                    if which == "pitch":    # every slot's key ramps up and down for the whole run, each at its own pace
+                        from infer_offline import KeyTimeline
+                        span = (warmup + blocks) * block_time
+                        for s in range(S):
+                            at = [span * n / (3 + s % 3) for n in range(4)]
+                            bank.set_pitch_timeline(s, KeyTimeline([(t, (-3.0, 4.0)[n % 2] + s % 5) for n, t in enumerate(at)]))
                     block, frames = bank.block, bank.frames
                     push = bank.push_audio if active is None else (lambda blocks: bank.push_audio(blocks, active=slots))
                 else:
@@ -177,7 +192,9 @@ def main():
     ap.add_argument("--models", type=int, default=None, help="deal the S slots round-robin over this many distinct models (S >= M only)")
     ap.add_argument("--streams", type=int, nargs="+", default=list(STREAMS), help="the stream counts S to run")
     ap.add_argument("--glide", action="store_true", help="three bank legs: the parent's, this tree's without and with a glide on every slot")
-    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain", "parent", "glide"], help=argparse.SUPPRESS)
+    ap.add_argument("--pitch-glide", action="store_true", help="three bank legs: the parent's, this tree's with pitch_breakpoints unused and with a "
+                    "key timeline on every slot")
+    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain", "parent", "glide", "unused", "pitch"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
@@ -188,8 +205,11 @@ def main():
         raise SystemExit("rt_bank_time: --baseline-tree must be a checkout of the parent commit (with ddsp-svc-official_amd/)")
     if a.glide and (a.models or a.enhancer):
         raise SystemExit("rt_bank_time: --glide does not combine with --models (such a bank refuses a glide) or --enhancer")
-    trees = {"bank": ROOT, "plain": ROOT, "glide": ROOT, "solo": os.path.abspath(a.baseline_tree), "parent": os.path.abspath(a.baseline_tree)}
-    legs = ("parent", "plain", "glide") if a.glide else ("bank", "solo", "plain") if a.models == 1 else ("bank", "solo")
+    if a.pitch_glide and (a.glide or a.models or a.enhancer):
+        raise SystemExit("rt_bank_time: --pitch-glide is a run of its own (no --glide, --models or --enhancer)")
+    three = ("parent", "plain", "glide") if a.glide else ("parent", "unused", "pitch") if a.pitch_glide else None
+    trees = {"bank": ROOT, "plain": ROOT, "glide": ROOT, "unused": ROOT, "pitch": ROOT, "solo": os.path.abspath(a.baseline_tree), "parent": os.path.abspath(a.baseline_tree)}
+    legs = three if three else ("bank", "solo", "plain") if a.models == 1 else ("bank", "solo")
     repeats = []
     for rep in range(a.repeats):
         for which in legs:
@@ -213,14 +233,14 @@ def main():
                 continue
             pick = lambda which, key: [r[key] for r in repeats if (r["leg"], r["shape"], r["streams"]) == (which, shape, S)]
             med = lambda v: sorted(v)[len(v) // 2]
-            if a.glide:   # three banks: every repeat's mean, each leg's median and spread, and the two differences of the medians
+            if three:     # three banks: every repeat's mean, each leg's median and spread, and the two differences of the medians
                 case = {"shape": shape, "streams": S}
                 for which in legs:
                     m = pick(which, "mean_ms")
                     case.update({f"{which}_mean_ms": m, f"{which}_p99_ms": pick(which, "p99_ms"), f"{which}_median_ms": med(m),
                                  f"{which}_spread_ms": max(m) - min(m)})
-                case.update(plain_minus_parent_ms=case["plain_median_ms"] - case["parent_median_ms"],
-                            glide_minus_plain_ms=case["glide_median_ms"] - case["plain_median_ms"])
+                case.update({f"{three[1]}_minus_{three[0]}_ms": case[f"{three[1]}_median_ms"] - case[f"{three[0]}_median_ms"],
+                             f"{three[2]}_minus_{three[1]}_ms": case[f"{three[2]}_median_ms"] - case[f"{three[1]}_median_ms"]})
                 cases.append(case)
                 continue
             bm, sm = pick("bank", "mean_ms"), pick("solo", "mean_ms")
@@ -236,16 +256,20 @@ def main():
     if a.glide:
         what = "ms per block period of one StreamBank.push_audio for all S streams: parent = the baseline tree's bank; plain = this " \
                "tree's bank without glide_breakpoints; glide = this tree's bank with glide_breakpoints=4 and a timeline on every slot"
+    if a.pitch_glide:
+        what = "ms per block period of one StreamBank.push_audio for all S streams: parent = the baseline tree's bank; unused = this " \
+               "tree's bank with pitch_breakpoints=4 and no timeline; pitch = the same bank with a key timeline on every slot"
     out = {**({} if a.active is None else {"active": a.active}), **({} if a.models is None else {"models": a.models}),
-           **({"glide": True} if a.glide else {}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks,
+           **({"glide": True} if a.glide else {}), **({"pitch_glide": True} if a.pitch_glide else {}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks,
            "warmup": a.warmup, "repeats": a.repeats, "what": what, "cases": cases, "rows": repeats}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
-    for c in cases if a.glide else ():
+    for c in cases if three else ():
         print(f"{c['shape']:8s} S={c['streams']:2d}: " + ", ".join(f"{w} {c[w + '_median_ms']:.3f} ms (spread {c[w + '_spread_ms']:.3f})" for w in legs) +
-              f"; plain - parent {c['plain_minus_parent_ms']:+.3f} ms, glide - plain {c['glide_minus_plain_ms']:+.3f} ms")
-    for c in () if a.glide else cases:
+              f"; {three[1]} - {three[0]} {c[f'{three[1]}_minus_{three[0]}_ms']:+.3f} ms, "
+              f"{three[2]} - {three[1]} {c[f'{three[2]}_minus_{three[1]}_ms']:+.3f} ms")
+    for c in () if three else cases:
         print(f"{c['shape']:8s} S={c['streams']:2d}: bank {c['bank_median_ms']:8.3f} ms (spread {c['bank_spread_ms']:.3f}), "
               f"solo x S {c['solo_median_ms']:8.3f} ms (spread {c['solo_spread_ms']:.3f}), ratio {c['solo_over_bank']:.2f}")
 
