@@ -252,6 +252,9 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
     if (code == DDSP_DEV_ERR_PIECES)
         return ddsp_fail(ctx, DDSP_ERR_ARG, "a piece whose range leaves its file or exceeds the output widths in an earlier "
                          "ddsp_pieces_gather call", "those rows were written as zeros and nothing was read for them");
+    if (code == DDSP_DEV_ERR_FORMANT)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a formant factor that is not finite or not > 0 in an earlier ddsp_ctrl_warp call",
+                         "the segments of those rows were left as they were");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

@@ -35,6 +35,17 @@ Differences a caller can observe, all additive:
     or (Fr,) - what the reference broadcasts in `x + v * spk_embed(id - 1)` - is turned into that form, slots in dict
     order; a dict of numbers behaves as ever.  With `n_frames=` the weights past a row's count do not matter.  Inference
     only, device error word and graph capture as for the row mix.
+  * `forward_formant(units_frames, f0_frames, volume_frames, spk_id, formant, ...)`: `forward` with a FORMANT SHIFT - the
+    spectral-envelope columns of the control matrix are stretched along the frequency axis between the control network and the
+    filter synthesis (`ddsp_ctrl_warp`, one launch; DESIGN section 7 states the rule), so the timbre reads as a brighter or
+    darker vocal tract at the same pitch.  `formant`: a number of semitones (|s| <= 24; positive raises the formants; the
+    factor is 2 ** (s / 12) stored to fp32) or a fp32 device tensor of FACTORS, (B,) one per row or (B, Fr) one per frame; a
+    pair (factors (S,), slot_of_row (B,) int32) reads row b's factor at factors[slot_of_row[b]] (an entry outside [0, S): a
+    padding row, no shift - `realtime.StreamBank`).  Warped: `harmonic_magnitude` and `noise_magnitude` (CombSub, CombSubFast),
+    `amplitudes` and `noise_magnitude` (Sins); `group_delay` and `harmonic_phase` are not.  The other parameters and the
+    returned tuple are `forward`'s (`Sins`: without `max_upsample_dim`); 0 semitones and factors of 1 give `forward`'s bits.
+    Inference only (NotImplementedError under grad mode); a factor that is not finite or not > 0 leaves its frames unshifted
+    and is reported through the context's device error word.
 """
 import os
 
@@ -213,11 +224,58 @@ class _SynthBase(torch.nn.Module):
             raise NotImplementedError("spk_mix_rows= is inference only: the training entries take spk_id or spk_mix_dict; call "
                                       "the model under torch.no_grad()")
 
+    MAX_FORMANT = 24.0   # semitones, either way
+
+    def _formant_segments(self):
+        """[(first column, n, origin)] of the control row that a formant shift warps: origin 0 for magnitude bins, 1 for
+        harmonics (`ddsp_ctrl_warp`)."""
+        raise NotImplementedError
+
+    def _warp(self, ctx, ctrl, formant, n_dev):
+        """In place on the control matrix (B, Fr, sum): the formant shift, `formant` = (factors, slot_of_row | None)."""
+        B, Fr = ctrl.shape[0], ctrl.shape[1]
+        ctx.ctrl_warp_(ctrl.reshape(B * Fr, -1), self._formant_segments(), formant[0], Fr, slot_of_row=formant[1], n_dev=n_dev)
+
+    def _formant_factors(self, formant, B, Fr, device):
+        """`forward_formant`'s `formant` -> (factors fp32 device tensor, slot_of_row | None) or None (0 semitones: nothing to
+        launch).  ValueError before anything is launched for a shift outside +-24 semitones or a tensor of another shape, dtype
+        or device; the VALUES of a device tensor are the kernel's to check."""
+        if isinstance(formant, (tuple, list)):
+            if not (len(formant) == 2 and all(isinstance(t, torch.Tensor) for t in formant)):
+                raise ValueError("formant: a pair is (factors (S,) fp32, slot_of_row (B,) int32), device tensors")
+            factors, rows = formant
+            if not (factors.dtype == torch.float32 and factors.dim() == 1 and factors.numel() >= 1 and rows.dtype == torch.int32 and
+                    tuple(rows.shape) == (B,) and factors.device == rows.device == device):
+                raise ValueError(f"formant: a pair is (factors (S,) fp32, slot_of_row (B = {B},) int32) on {device}")
+            return factors.contiguous(), rows.contiguous()
+        if isinstance(formant, torch.Tensor):
+            if formant.dtype != torch.float32 or formant.device != device or tuple(formant.shape) not in ((B,), (B, Fr)):
+                raise ValueError(f"formant: a tensor holds fp32 FACTORS on {device}, (B,) = ({B},) or (B, Fr) = ({B}, {Fr}); got "
+                                 f"{formant.dtype} {tuple(formant.shape)} on {formant.device}")
+            return formant.contiguous(), None
+        factor = hipddsp.formant_factor(formant, self.MAX_FORMANT)
+        if factor == 1.0:
+            return None
+        return torch.full((B,), factor, dtype=torch.float32, device=device), None
+
+    def forward_formant(self, units_frames, f0_frames, volume_frames, spk_id, formant, spk_mix_dict=None, initial_phase=None,
+                        infer=True, noise=None, noise_seed=None, n_frames=None, spk_mix_rows=None):
+        """`forward` with a formant shift (module docstring): `formant` semitones (a number, |s| <= 24) or fp32 device FACTORS
+        (B,) / (B, Fr) / (factors (S,), slot_of_row (B,) int32); returns `forward`'s tuple.  Inference only."""
+        if self.unit2ctrl.wants_grad():
+            raise NotImplementedError("formant= is inference only: the warp has no adjoint; call the model under torch.no_grad()")
+        B, Fr = units_frames.shape[0], units_frames.shape[1]
+        return self._forward(units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
+                             noise_seed, n_frames, spk_mix_rows, formant=self._formant_factors(formant, B, Fr, f0_frames.device))
+
     def _forward(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict, initial_phase, infer, noise,
-                 noise_seed, n_frames, spk_mix_rows):
+                 noise_seed, n_frames, spk_mix_rows, formant=None):
         """The body of every model's `forward`.  Launches, in order: [ragged: the counts' upload and the held form of units,
-        f0 and volume;] the phase scan; the control network; the model's chain; [ragged: the padding of the returned phase
-        cleared].  A call that autograd records is the same sequence inside `_SynthTrainFn.forward`."""
+        f0 and volume;] the phase scan; the control network; [`formant`: the warp;] the model's chain; [ragged: the padding of
+        the returned phase cleared].  A call that autograd records is the same sequence inside `_SynthTrainFn.forward`.
+        `formant`: None or `_formant_factors`' (factors, slot_of_row | None).  Ragged, the warp sits between the control network
+        and the hold of its last frame over the padding: the kernel leaves the frames past a row's count alone, and the hold
+        then gives the chain the held form of the WARPED matrix."""
         B, Fr = units_frames.shape[0], units_frames.shape[1]
         spk_mix_dict, spk_mix_rows = self.unit2ctrl.frame_mix(spk_mix_dict, spk_mix_rows, B, Fr, units_frames.device)
         if spk_mix_rows is not None and not is_frame_mix(spk_mix_rows):
@@ -229,6 +287,8 @@ class _SynthBase(torch.nn.Module):
             raise NotImplementedError("n_frames= (ragged batches) on a model in eval mode is inference only: call the model "
                                       "under torch.no_grad(), or put it into training mode (model.train()) to have the ragged "
                                       "call recorded for autograd")
+        if formant is not None and self.unit2ctrl.wants_grad():
+            raise NotImplementedError("formant= is inference only: the warp has no adjoint; call the model under torch.no_grad()")
         if self.unit2ctrl.wants_grad():
             phase, *outs = _SynthTrainFn.apply(self, units_frames, f0_frames, volume_frames, spk_id, spk_mix_dict,
                                                initial_phase, infer, noise, noise_seed, vals, *self.unit2ctrl.parameters())
@@ -239,7 +299,11 @@ class _SynthBase(torch.nn.Module):
             f0 = f0.reshape(B, Fr, 1)
             ps = self._scan(ctx, f0, initial_phase, infer)
             ctrl = self.unit2ctrl.forward_ragged(ctx, units, f0, ps["phase_frames"], volume, spk_id, spk_mix_dict, n_dev,
+                                                 hold=formant is None,
                                                  spk_mix_rows=self.unit2ctrl.hold_frame_mix(ctx, spk_mix_rows, n_dev))
+            if formant is not None:
+                self._warp(ctx, ctrl, formant, n_dev)
+                ctx.ragged_frames(ctrl, n_dev, hold=True, out=ctrl)
             excitation = lambda: self._ragged_noise(ctx, n_dev, B, Fr, noise, noise_seed)
         else:
             n_dev, f0 = None, f0_frames
@@ -247,6 +311,8 @@ class _SynthBase(torch.nn.Module):
             ps = self._scan(ctx, f0, initial_phase, infer)
             ctrl = self.unit2ctrl.forward_flat(units_frames, f0, ps["phase_frames"], volume_frames, spk_id, spk_mix_dict,
                                                spk_mix_rows=spk_mix_rows)
+            if formant is not None:
+                self._warp(ctx, ctrl, formant, None)
             excitation = lambda: self._noise_args(noise, noise_seed)
         outs, _ = self._render(ctx, ctrl, ps, f0, excitation, n_dev)
         return self._result(self._phase_out(ctx, ps, n_dev), outs)
@@ -346,6 +412,10 @@ class CombSub(_SynthBase):
     _front_wants = {}
     _n_outs = 3
 
+    def _formant_segments(self):
+        na, nh, nn_ = self.n_mags
+        return [(na, nh, 0), (na + nh, nn_, 0)]                  # harmonic_magnitude, noise_magnitude; group_delay stays
+
     def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
         """Combtooth -> all-pass -> harmonic filter, + filtered noise -> ((signal, harmonic, noise), saved).  Ragged: the
         all-pass output is cropped too, as the reference crops per call."""
@@ -418,6 +488,10 @@ class Sins(_SynthBase):
     _front_wants = {"want_phase": True}
     _n_outs = 3
 
+    def _formant_segments(self):
+        nhm, na, nn_ = self.n_mags
+        return [(0, nhm, 1), (nhm + na, nn_, 0)]                 # amplitudes (harmonic j + 1), noise_magnitude; group_delay stays
+
     def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
         """Sinusoid bank on the sample-rate phase -> all-pass, + filtered noise -> ((signal, harmonic, noise), saved)."""
         B, Fr = ctrl.shape[0], ctrl.shape[1]
@@ -482,6 +556,10 @@ class CombSubFast(_SynthBase):
     _comb_mode = COMB_SINC_GATED
     _front_wants = {}
     _n_outs = 1
+
+    def _formant_segments(self):
+        nb = self._hop + 1
+        return [(0, nb, 0), (2 * nb, nb, 0)]                     # harmonic_magnitude, noise_magnitude; harmonic_phase stays
 
     def _render(self, ctx, ctrl, ps, f0_frames, excitation, n_dev=None, keep=False):
         """One windowed spectral OLA -> ((signal,), saved).  Ragged: with the comb and the excitation 0 past a row's end,

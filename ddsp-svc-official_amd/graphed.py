@@ -93,8 +93,10 @@ def _refill(static, value):
 
 
 class GraphedSynth(_Captured):
-    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None, capture=True):
-        """`spk_mix_rows`: None / False; True (K = 4 slots per row) or a K for static mix tables of the graph's own; or the
+    def __init__(self, model, B, Fr, warmup=3, spk_mix_dict=None, spk_mix_rows=None, capture=True, formant=None):
+        """`formant`: None, or the caller's device factors as `forward_formant` takes them - (B,) fp32, or the pair (factors (S,),
+        slot_of_row (B,) int32) -, read by the captured warp at their fixed addresses (`realtime.StreamBank(formant=True)`).
+        `spk_mix_rows`: None / False; True (K = 4 slots per row) or a K for static mix tables of the graph's own; or the
         caller's device tables (ids (B, K) int32, w (B, K) fp32), which the graph then reads at their fixed addresses; with
         w (B, Fr, K) they are a mix per FRAME (`hipddsp.check_mix_frames`), which reaches the control network's framemix entry.
         `capture=False` (a subclass that also runs eagerly, `GraphedModelRows`): the static tensors alone, `graph` is None."""
@@ -133,10 +135,15 @@ class GraphedSynth(_Captured):
             self.mix_w = torch.zeros(B, K, device=dev) if K else None
             if K:
                 self.mix_w[:, 0] = 1.0
+        self.formant = formant
         self.graph = None
         self.out = self._capture(dev, warmup) if capture else None
 
     def _run(self):
+        if self.formant is not None:
+            return self.model.forward_formant(self.units, self.f0, self.volume, self.spk_id, self.formant, noise=self.noise,
+                                              **({"spk_mix_dict": self.spk_mix_dict} if self.mix_ids is None else
+                                                 {"spk_mix_rows": (self.mix_ids, self.mix_w)}))
         if self.mix_ids is not None:
             return self.model(self.units, self.f0, self.volume, self.spk_id, spk_mix_rows=(self.mix_ids, self.mix_w),
                               noise=self.noise)
@@ -212,7 +219,8 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     One stream: `window` (n_in,), `block_in` (block,), `pitch` a host factor (no multiply at exactly 1).  S streams of one
     geometry: `window` (S, n_in), `block_in` (S, block), `pitch` a device (S,) tensor of factors - or (S, Fr), a factor per FRAME,
     which `push` fills (`ddsp_bank_key_glide`) -; every step is then one batched call.  The window keeps the rank it comes with down to the library, so each form reaches its own kernels.
-    `speaker`: the speaker term as the model's keyword arguments, {"spk_id": (1, 1) int64, "spk_mix_dict": dict or None} or
+    `speaker`: the speaker term as the model's keyword arguments - with a "formant" among them (`forward_formant`'s device
+    factors) the synthesiser is entered through `forward_formant` -, {"spk_id": (1, 1) int64, "spk_mix_dict": dict or None} or
     {"spk_id": None, "spk_mix_rows": (ids (S, K) int32, w (S, K) fp32)}.
     `push(ctx, window, block_in)`: the step that brings `window` up to date, `ctx.stream_push_` unless given.  The compact rows of
     a bank's active set (`realtime.StreamBank`, `active=`) are the S-stream form with `Context.bank_gather_` as this step: it pushes
@@ -236,7 +244,7 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     if model is None:
         return None, f0, units, volume
     kw = {} if noise is None else {"noise": noise}
-    sig = model(units, f0, volume, **speaker, **kw)[0]
+    sig = (model.forward_formant if "formant" in speaker else model)(units, f0, volume, **speaker, **kw)[0]
     ctx.volume_gate_(sig, volume, threshold_db, block_size)          # (`block_size`: the model's, as a host int - no read-back)
     return sig, f0, units, volume
 
@@ -254,7 +262,7 @@ class GraphedBlock(_Captured):
     next replay): `sig`, `f0`, `units`, `volume`."""
 
     def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch,
-                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None, keep=()):
+                 threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None, keep=(), formant=None):
         if mix_rows is not None and spk_mix_dict is not None:
             raise ValueError("GraphedBlock: mix_rows and spk_mix_dict are mutually exclusive")
         if mix_rows is not None and mix_rows[1].dim() == 3:          # a mix per FRAME: w (S, Fr, K), filled by `push`
@@ -277,6 +285,8 @@ class GraphedBlock(_Captured):
             self.speaker = {"spk_id": self.spk_id, "spk_mix_dict": None if spk_mix_dict is None else dict(spk_mix_dict)}
         else:
             self.speaker = {"spk_id": None, "spk_mix_rows": tuple(mix_rows)}
+        if formant is not None:                                      # the caller's device factors (`forward_formant`), read at replay
+            self.speaker["formant"] = formant
         self.noise = None if model is None else torch.rand(*(rows or (1,)), frames * self.block_size, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.sig, self.f0, self.units, self.volume = self._capture(dev, warmup, keep=[window, *keep])

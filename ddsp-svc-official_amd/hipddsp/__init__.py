@@ -258,6 +258,7 @@ SIGNATURES = {
     "ddsp_bank_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _int, _vp]),
     "ddsp_bank_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _i64, _i64, _i64, _f64, _vp]),
     "ddsp_bank_key_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _f64, _vp]),
+    "ddsp_ctrl_warp": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp, _int, _i64, _vp, _i64, _vp]),
     "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
     "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
@@ -520,6 +521,15 @@ def mix_rows(mixes, K, n_spk=None):
                 raise ValueError(f"row {b}: speaker id {i} is outside [1, {n_spk}]")
             ids[b, k], w[b, k] = int(i), float(v)
     return ids, w
+
+
+def formant_factor(semitones, bound=24.0):
+    """A formant shift in semitones -> its factor, 2 ** (float(s) / 12) as a Python float (the rule of a key: stored to fp32
+    where it is used).  ValueError for anything but a finite number with |s| <= bound."""
+    if isinstance(semitones, bool) or not isinstance(semitones, (int, float)) or not _math.isfinite(semitones) or \
+            abs(semitones) > bound:
+        raise ValueError(f"formant must be a finite number of semitones with |formant| <= {bound:g}, got {semitones!r}")
+    return 2 ** (float(semitones) / 12)
 
 
 def _ptr(t):
@@ -1631,6 +1641,58 @@ class Context:
             self.call("ddsp_bank_key_glide", _ptr(rows), W, S, _ptr(key_clock), _ptr(key_n), _ptr(key_t), _ptr(key_semi),
                       _ptr(key_fac), P_max, _ptr(pitch), Fr, int(n_in), int(block), float(hop), _ptr(pitch_frames))
         return pitch_frames
+
+    def ctrl_warp_(self, ctrl2d, segments, factor, Fr, slot_of_row=None, n_dev=None):
+        """The formant shift (`ddsp_ctrl_warp`; include/ddsp_amd.h states the rule): in place on the control matrix ctrl2d
+        (rows, sum) fp32, rows = B * Fr, up to three `segments` (first column, n, origin) - origin 0: magnitude bins, 1: harmonics -
+        are read at f / factor.  factor: fp32 device FACTORS, (B * Fr,) or (B, Fr) one per frame, (B,) one per batch row, or
+        - with slot_of_row (B,) int32 device - (S,) read as factor[slot_of_row[b]], an entry outside [0, S) being a padding row
+        (factor 1).  n_dev (B,) int32 device: the counts of a ragged batch, frames at or past them keep their bits.  Shapes and
+        dtypes are refused here, before the launch; a factor that is not finite or not > 0 leaves its row as it was and raises
+        ValueError from `poll_error()` after a synchronise or from the next call that takes the error word.  -> ctrl2d."""
+        if not (isinstance(ctrl2d, torch.Tensor) and ctrl2d.dtype == torch.float32 and ctrl2d.dim() == 2 and ctrl2d.is_contiguous()):
+            raise ValueError("ctrl_warp_: ctrl2d must be a contiguous (rows, sum) fp32 tensor")
+        rows, width = ctrl2d.shape
+        Fr = int(Fr)
+        if Fr < 1 or rows % Fr:
+            raise ValueError(f"ctrl_warp_: rows = {rows} must be a multiple of Fr = {Fr} >= 1")
+        B = rows // Fr
+        segments = [tuple(seg) for seg in segments] if isinstance(segments, (list, tuple)) else None
+        if not segments or len(segments) > 3 or any(len(seg) != 3 or any(isinstance(v, bool) or not isinstance(v, int) for v in seg)
+                                                    for seg in segments):
+            raise ValueError("ctrl_warp_: segments is a list of 1 to 3 triples (first column, n, origin) of ints")
+        for first, n, origin in segments:
+            if not (first >= 0 and 1 <= n <= 4096 and first + n <= width and origin in (0, 1)):
+                raise ValueError(f"ctrl_warp_: segment {(first, n, origin)} must lie inside the row of {width} columns with "
+                                 "1 <= n <= 4096 and origin 0 or 1")
+        if not (isinstance(factor, torch.Tensor) and factor.dtype == torch.float32 and factor.is_contiguous() and
+                factor.device == ctrl2d.device):
+            raise ValueError("ctrl_warp_: factor must be a contiguous fp32 tensor on the matrix's device")
+        S = 0
+        if slot_of_row is not None:
+            if not (isinstance(slot_of_row, torch.Tensor) and slot_of_row.dtype == torch.int32 and tuple(slot_of_row.shape) == (B,)
+                    and slot_of_row.is_contiguous() and slot_of_row.device == ctrl2d.device):
+                raise ValueError(f"ctrl_warp_: slot_of_row must be a contiguous (B = {B},) int32 tensor on the matrix's device")
+            if factor.dim() != 1 or factor.numel() < 1:
+                raise ValueError("ctrl_warp_: with slot_of_row the factors are (S,), one per slot, S >= 1")
+            per_frame, S = 0, factor.numel()
+        elif tuple(factor.shape) in ((rows,), (B, Fr)) and Fr > 1:
+            per_frame = 1
+        elif tuple(factor.shape) == (B,):
+            per_frame = 0
+        elif tuple(factor.shape) == (B, 1):         # (Fr == 1: a factor per frame is a factor per row)
+            per_frame = 0
+        else:
+            raise ValueError(f"ctrl_warp_: factor must be (B * Fr,) = ({rows},), (B, Fr) = ({B}, {Fr}) or (B,) = ({B},), got "
+                             f"{tuple(factor.shape)}")
+        if n_dev is not None and not (isinstance(n_dev, torch.Tensor) and n_dev.dtype == torch.int32 and n_dev.numel() == B and
+                                      n_dev.is_contiguous() and n_dev.device == ctrl2d.device):
+            raise ValueError(f"ctrl_warp_: n_dev must be a contiguous (B = {B},) int32 tensor on the matrix's device")
+        if rows:
+            table = (_c.c_int32 * (3 * len(segments)))(*[int(v) for seg in segments for v in seg])
+            self.call("ddsp_ctrl_warp", _ptr(ctrl2d), rows, width, table, len(segments), _ptr(factor), per_frame, Fr,
+                      _ptr(slot_of_row), S, _ptr(n_dev))
+        return ctrl2d
 
     def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
         """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row

@@ -439,6 +439,62 @@ def key_tables(keys, sampling_rate, block_size):
             torch.tensor([2 ** (float(k) / 12) for k in semi], dtype=torch.float32))
 
 
+MAX_FORMANT = 24.0   # semitones, either way (`ddsp.vocoder` holds a numeric shift to the same bound)
+
+
+class FormantTimeline(KeyTimeline):
+    """The formant shift of a job as a function of FILE time: points (seconds, semitones) under `KeyTimeline`'s validation and
+    frame rule, |semitones| <= 24.  The shift is linear in semitones between two points and held outside them; the factor of a
+    frame is the key timeline rule's (include/ddsp_amd.h at `ddsp_pieces_gather_keys`) - what that kernel multiplies onto an f0
+    of 1.0 at that file frame.  It is a job's fifth entry, never its key.  ValueError for anything else."""
+
+    def __init__(self, points):
+        try:
+            super().__init__(points)
+        except ValueError as e:
+            raise ValueError(str(e).replace("KeyTimeline", "FormantTimeline").replace("the key must", "the shift must")) from None
+        for n, (_, semi) in enumerate(self.points):
+            if abs(semi) > MAX_FORMANT:
+                raise ValueError(f"FormantTimeline: point {n}: the shift must lie within +-{MAX_FORMANT:g} semitones, got {semi!r}")
+
+    def frames(self, sampling_rate, block_size):
+        try:
+            return super().frames(sampling_rate, block_size)
+        except ValueError as e:
+            raise ValueError(str(e).replace("KeyTimeline", "FormantTimeline")) from None
+
+
+def job_formants(jobs):
+    """The formant shift of every job of a `job_table` call, in job order: None (a 4-tuple, or a fifth entry of None), a float of
+    semitones or the `FormantTimeline` as it is.  `job_table` has checked them."""
+    out = []
+    for job in jobs:
+        formant = job[4] if len(job) == 5 else None
+        out.append(formant if formant is None or isinstance(formant, FormantTimeline) else float(formant))
+    return out
+
+
+def formant_tables(formants, sampling_rate, block_size):
+    """`key_tables` for `job_formants`' list: a job without a shift is the one breakpoint of 0 semitones, factor 1."""
+    return key_tables([0.0 if f is None else f for f in formants], sampling_rate, block_size)
+
+
+def _check_formant(j, formant, model):
+    from realtime import _model_field
+    if isinstance(formant, FormantTimeline):
+        try:
+            formant.frames(_model_field(model, "sampling_rate"), _model_field(model, "block_size"))
+        except ValueError as e:
+            raise ValueError(f"job_table: job {j}: {e}") from None
+    elif formant is not None:
+        if isinstance(formant, KeyTimeline):
+            raise ValueError(f"job_table: job {j}: formant must be a number of semitones or a FormantTimeline, got a KeyTimeline")
+        try:
+            hipddsp.formant_factor(formant, MAX_FORMANT)
+        except ValueError as e:
+            raise ValueError(f"job_table: job {j}: {e}") from None
+
+
 def job_table(pieces, n_files, jobs, models):
     """The tables of a conversion of `jobs` over analysed files, made and checked on the host (nothing is launched).  pieces:
     `piece_table` rows of the `n_files` files; jobs: a sequence of (file, model_index, spk, key) - spk a 1-based speaker id, a
@@ -454,8 +510,11 @@ def job_table(pieces, n_files, jobs, models):
                     whose key is a `KeyTimeline`);
       keys          every job's key as `key_tables` takes it: a float, or the `KeyTimeline` as it is;
       starts_per_job  the start frames of every job's rows, as `stitch_plan_many` takes them with jobs in the place of files.
-    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4-tuple, a file or
-    model index out of range, a speaker id outside [1, n_spk] of the JOB's model, or a mix with no or too many speakers."""
+    A job may carry a fifth entry, its FORMANT shift: a number of semitones (|s| <= 24), a `FormantTimeline` or None.  It is
+    checked here and stands in no table of the dict: `job_formants(jobs)` lists it, `formant_tables` makes its breakpoints.
+    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4- or 5-tuple, a file
+    or model index out of range, a speaker id outside [1, n_spk] of the JOB's model, a mix with no or too many speakers, or a
+    formant shift that is no finite number within +-24 semitones and no `FormantTimeline` that fits the model's frame rate."""
     from realtime import MODEL_FIELDS, _model_field
     models = list(models) if isinstance(models, (tuple, list)) else []
     if not models:
@@ -470,9 +529,10 @@ def job_table(pieces, n_files, jobs, models):
     table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": [],
              "keys": []}
     for j, job in enumerate(jobs):
-        if not (isinstance(job, (tuple, list)) and len(job) == 4):
-            raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key), got {job!r}")
-        file, m, spk, key = job
+        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5)):
+            raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key) or (file, model_index, spk, key, formant), "
+                             f"got {job!r}")
+        file, m, spk, key = job[:4]
         if not (isinstance(file, numbers.Integral) and 0 <= file < int(n_files)):
             raise ValueError(f"job_table: job {j}: file {file!r} is outside the {int(n_files)} files of the call")
         if not (isinstance(m, numbers.Integral) and 0 <= m < len(models)):
@@ -497,6 +557,10 @@ def job_table(pieces, n_files, jobs, models):
         for i in ids:
             if not (isinstance(i, numbers.Integral) and 1 <= i <= n_spk):
                 raise ValueError(f"job_table: job {j}: speaker id {i!r} is outside [1, {n_spk}] of models[{m}]")
+        if isinstance(key, FormantTimeline):
+            raise ValueError(f"job_table: job {j}: key must be a number of semitones or a KeyTimeline, got a FormantTimeline")
+        if len(job) == 5:
+            _check_formant(j, job[4], models[m])
         if isinstance(key, KeyTimeline):
             try:
                 key.frames(_model_field(models[m], "sampling_rate"), _model_field(models[m], "block_size"))
@@ -799,7 +863,9 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
         key = {"key_timeline": table["key_tables_dev"]} if "key_tables_dev" in table else {"key_factor": table["key_factor_dev"]}
         numbered = job_groups(table, len(models), budget)
         groups, model_of_group = [group for _, group in numbered], [models[m] for m, _ in numbered]
+        table_models = [m for m, _ in numbered]
     given = None if jobs is None else rows
+    formant = None if jobs is None else jobs[1].get("formant")       # (models with a formant among their jobs, tables, f0 of ones)
     table, cols, bounds = _upload_pieces(ctx, files, groups, given)
     speaker_of_rows = speaker(cols[0], [i for group in groups for i in group])
     out = [None] * len(rows)
@@ -811,7 +877,15 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
         kw = {} if seed_of_group is None else {"noise_seed": seed_of_group(g, [rows[i][1] for i in group])}
         if noise is not None:
             kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
-        signal = model_of_group[g](u, f[:, :, None], v, n_frames=counts, **speaker_of_rows(a, b), **kw)[0].contiguous()
+        if formant is not None and table_models[g] in formant[0]:
+            # the rows' factors per frame: the key timeline rule on an f0 of ones, one launch (0 past a row's count, where the
+            # warp reads no factor)
+            _, fac, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=formant[2],
+                                          N_max=max(counts), key_timeline=formant[1])
+            signal = model_of_group[g].forward_formant(u, f[:, :, None], v, formant=fac, n_frames=counts, **speaker_of_rows(a, b),
+                                                       **kw)[0].contiguous()
+        else:
+            signal = model_of_group[g](u, f[:, :, None], v, n_frames=counts, **speaker_of_rows(a, b), **kw)[0].contiguous()
         ctx.volume_gate_rows_(signal, files["volume"], cols[1, a:b], cols[2, a:b], threshold_db, block,
                               file_dev=cols[0, a:b], file_frames_dev=files["n_frames_dev"])
         for j, i in enumerate(group):
@@ -880,6 +954,10 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     `ddsp_pieces_gather_keys` with the `key_tables` of all jobs, uploaded once: a row's f0 is its file's times the factor at
     every frame's own file frame, a numeric key is the one breakpoint at frame 0 and keeps its bits, and the enhancer
     (`enhancer_adaptive_key='auto'` too) sees the same moving f0.  key_tables_always: take that path whatever the keys are.
+    A job may be a 5-tuple (file, model_index, spk, key, formant): a FORMANT shift in semitones, a number or a
+    `FormantTimeline`.  A model with a formant among its jobs renders all its groups through `forward_formant` with a factor per
+    frame - the key timeline rule at every frame's own file frame, one `ddsp_pieces_gather_keys` launch per group over an f0 of
+    ones -; a model without one takes the path above, bit for bit.  The enhancer is not told of the shift: it follows f0.
     noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
     `models` order - draws with (noise_seed + g * 2**32) mod 2**64."""
     models = _models_of("render_jobs_device", None, models)
@@ -895,6 +973,15 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
         table["key_tables_dev"] = tuple(t.to(dev) for t in key_tables(table["keys"], *rate))
     elif J:
         table["key_factor_dev"] = torch.tensor(table["key_factor"], dtype=torch.float32).to(dev)
+    formants = job_formants(jobs)
+    if any(f is not None for f in formants):
+        # a formant among the jobs: its model renders ALL its groups through `forward_formant`; the breakpoint tables of all jobs
+        # (a job without a shift: 0 semitones, factor 1) go up once, with an f0 of ones that `ddsp_pieces_gather_keys` turns into
+        # every group's factor rows
+        from realtime import _model_field
+        tabs = formant_tables(formants, _model_field(models[0], "sampling_rate"), _model_field(models[0], "block_size"))
+        table["formant"] = ({table["model_of_job"][j] for j, f in enumerate(formants) if f is not None},
+                            tuple(t.to(dev) for t in tabs), torch.ones_like(files["f0"]))
 
     def speaker(file_of_row, order):
         # Every row takes its job's speaker, from host tables uploaded once in front of the launches (the job of a row is known

@@ -9,9 +9,14 @@ stitched waveform on the device and is read back once.
 `--jobs` names a YAML list of entries {model: <model.pt, default -m>, id: <speaker id, default 1> | mix: {id: weight} |
 timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...] (a voice that glides over the file,
 `infer_offline.SpeakerTimeline`), key: <semitones, default 0> | key_timeline: [{at: <seconds>, key: <semitones>}, ...] (a key
-that moves over the file, `infer_offline.KeyTimeline`), suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
+that moves over the file, `infer_offline.KeyTimeline`), formant: <semitones, default 0> | formant_timeline: [{at: <seconds>,
+formant: <semitones>}, ...] (a formant shift, `infer_offline.FormantTimeline`), suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
 give `name_s.wav`.  All of it is ONE `convert_many_device(jobs=...)` - every file analysed once - and one read-back; `-id`,
 `-mix` and `-k` are then unused.
+
+`--formant_shift_key S` (long option only, default 0) shifts the formants of the file or folder by S semitones at the same pitch
+(`forward_formant`); it runs through the jobs path, one job per file, and with `--jobs` it is the shift of the entries that
+name none.
 
 The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
   * the key shift is applied once (the reference applies it twice, SURVEY 0.3);
@@ -54,6 +59,8 @@ def parse_args(args=None, namespace=None):
     for short, long, kind, default, text in _OPTIONS:
         parser.add_argument(short, long, type=kind, required=default is None, default=default, help=text)
     # (absent from the namespace unless given: the reference's options are the namespace of a plain call)
+    parser.add_argument("--formant_shift_key", type=str, default=argparse.SUPPRESS, help="formant shift (number of semitones, "
+                        "positive: brighter) for the file or folder | default: 0")
     parser.add_argument("--jobs", type=str, default=argparse.SUPPRESS, help="YAML list of {model, id | mix, key, suffix}: every entry is applied "
                         "to every .wav of the input folder")
     return parser.parse_args(args=args, namespace=namespace)
@@ -116,6 +123,9 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
             raise ValueError("--jobs goes with a folder as -i (and a folder as -o)")
         return _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                          enhancer_batch_samples, units_batch_samples)
+    if float(getattr(cmd, "formant_shift_key", 0)) != 0:
+        return _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
+                            enhancer_batch_samples, units_batch_samples)
     if os.path.isdir(cmd.input):
         return _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                            enhancer_batch_samples, units_batch_samples)
@@ -155,6 +165,27 @@ def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhan
     return result, sr_o
 
 
+def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
+                 units_batch_samples):
+    """`run` with `--formant_shift_key S` and no `--jobs`: the file, or every `.wav` of the folder, as one job each - `-id` or
+    `-mix`, `-k` and the shift - through ONE `infer_offline.convert_many_device(jobs=...)`; outputs as `run` names them."""
+    from infer_offline import convert_many_device
+    folder = os.path.isdir(cmd.input)
+    names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav")) if folder else [None]
+    audios = [load(os.path.join(cmd.input, n) if folder else cmd.input) for n in names]
+    mix = literal_eval(cmd.spk_mix_dict)
+    jobs = [(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), float(cmd.formant_shift_key)) for k in range(len(names))]
+    result, spans, sr_o = convert_many_device(
+        None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=[model], batch_frames=batch_frames,
+        threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
+        enhancer_adaptive_key=float(cmd.enhancer_adaptive_key), enhancer_batch_samples=enhancer_batch_samples,
+        units_batch_samples=units_batch_samples)
+    if folder:
+        os.makedirs(cmd.output, exist_ok=True)
+    _write_pcm(result, spans, [os.path.join(cmd.output, n) for n in names] if folder else [cmd.output], sr_o)
+    return result, sr_o
+
+
 def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
               units_batch_samples):
     """`run` with `--jobs`: every entry of the list applied to every `.wav` of `cmd.input` (sorted by name), file after file and
@@ -170,19 +201,21 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
     if not (isinstance(entries, list) and entries and all(isinstance(e, dict) for e in entries)):
         raise ValueError(f"--jobs: {cmd.jobs} must hold a non-empty list of {{model, id | mix, key, suffix}} entries")
     paths, models, voices = [os.path.abspath(cmd.model_path)], [model], []
+    shift = float(getattr(cmd, "formant_shift_key", 0))          # the shift of the entries that name none
     for n, e in enumerate(entries):
         spk, key = _job_entry(n, e)
         path = os.path.abspath(e.get("model", cmd.model_path))
         if path not in paths:
             paths.append(path)
             models.append(load_model(path, device=device)[0])
-        voices.append((paths.index(path), spk, key, str(e["suffix"])))
+        voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift)))
     if len({v[3] for v in voices}) != len(voices):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
     audios = [load(os.path.join(cmd.input, n)) for n in names]
-    jobs = [(k, m, spk, key) for k in range(len(names)) for m, spk, key, _ in voices]
-    out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{suffix}.wav") for name in names for _, _, _, suffix in voices]
+    jobs = [(k, m, spk, key) + (() if formant is None else (formant,)) for k in range(len(names))
+            for m, spk, key, _, formant in voices]
+    out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{v[3]}.wav") for name in names for v in voices]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=models, batch_frames=batch_frames,
         threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
@@ -197,7 +230,7 @@ def _job_entry(n, e):
     """Entry n of the `--jobs` list -> (spk, key) as `infer_offline.job_table` takes them: the speaker from `id`, `mix` or
     `timeline` (at most one of them; default id 1), the key from `key` or `key_timeline` (not both; default 0).  ValueError for an
     unknown field, two speakers, two keys or a missing suffix."""
-    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "suffix"}
+    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "formant", "formant_timeline", "suffix"}
     if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or ("key" in e and "key_timeline" in e) or \
             not str(e.get("suffix", "")):
         raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key or key_timeline and a non-empty suffix, "
@@ -205,6 +238,21 @@ def _job_entry(n, e):
     spk = _timeline(n, e["timeline"]) if "timeline" in e else e["mix"] if "mix" in e else int(e.get("id", 1))
     key = _key_timeline(n, e["key_timeline"]) if "key_timeline" in e else float(e.get("key", 0))
     return spk, key
+
+
+def _job_formant(n, e, default=0.0):
+    """Entry n's formant shift as a job's fifth entry: `formant: <semitones>`, `formant_timeline: [{at: <seconds>, formant:
+    <semitones>}, ...]` (`infer_offline.FormantTimeline`) - not both -, else `default` (`--formant_shift_key`); None for no shift."""
+    from infer_offline import FormantTimeline
+    if "formant" in e and "formant_timeline" in e:
+        raise ValueError(f"--jobs: entry {n} takes formant or formant_timeline, not both, got {e!r}")
+    if "formant_timeline" in e:
+        points = e["formant_timeline"]
+        if not (isinstance(points, list) and points and all(isinstance(p, dict) and set(p) == {"at", "formant"} for p in points)):
+            raise ValueError(f"--jobs: entry {n}: formant_timeline is a non-empty list of {{at, formant}} points, got {points!r}")
+        return FormantTimeline([(p["at"], p["formant"]) for p in points])
+    shift = float(e.get("formant", default))
+    return None if shift == 0 else shift
 
 
 def _timeline(n, points):

@@ -452,6 +452,14 @@ class _Rows:
         return self.spk_ids, (self.spk_w if self.w_frames is None else self.w_frames)
 
     @property
+    def formant_term(self):
+        """The formant term of this instance's synthesis (`forward_formant`'s `formant`): None on a bank without `formant`; the
+        slots' row of factors at the full width; with the width's row table behind it on a compact instance, so a row reads
+        its SLOT's factor and a padding row none."""
+        f = self.bank.formant
+        return None if f is None else (f if self.rows is None else (f, self.rows))
+
+    @property
     def pitch_term(self):
         """The pitch term of this instance's chain: a factor per row, or per frame on a bank with `pitch_breakpoints`."""
         return self.pitch if self.pitch_frames is None else self.pitch_frames
@@ -588,14 +596,25 @@ class StreamBank:
     factors.  The paused-slot rule covers `key_clock`, `key_n`, `key_t`, `key_semi` and `key_fac`.  Refused:
     `set_pitch_timeline` on a bank without `pitch_breakpoints`, with more points than it, or two points on one sample.
 
-    Not in the bank: streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
+    A formant shift per slot (`formant=True`; the default False allocates, captures and launches nothing of this, and the bank
+    is the bank above, bit for bit).  Every slot then has a row of `formant` (S,) fp32, a FACTOR, initially 1;
+    `set_formant(slot, semitones)` writes 2 ** (semitones / 12) there (|semitones| <= 24) and `reset(slot)` puts 1 back: device
+    rows only, `graph_builds` stays what it was.  Every chain of such a bank enters the synthesiser through `forward_formant` with
+    the slots' row - at a compact width with the width's row table behind it, so a row reads its slot's factor and a padding
+    row none -: one `ddsp_ctrl_warp` launch between the control network and the filter synthesis, inside the captured block.  The
+    kernels only read the row, so a paused slot's factor stays as it is.  Works with `glide_breakpoints`, `pitch_breakpoints`,
+    `active_widths` and the enhancer (which is not told of the shift: it follows f0).  Refused: `formant=True` with `models=`;
+    `set_formant` on a bank without it.
+
+    Not in the bank: a formant shift on a bank with `models=`, or one that moves along a timeline; streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
     grows after construction; a weight set per row inside the control network's kernels; an enhancer per model; a glide on a
     bank with `models=`."""
 
     def __init__(self, model, n_streams, samplerate, block_time, crossfade_time, device, buffer_num=4, threshold_db=-45.0,
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
-                 active_widths=None, models=None, model_widths=None, glide_breakpoints=None, pitch_breakpoints=None):
+                 active_widths=None, models=None, model_widths=None, glide_breakpoints=None, pitch_breakpoints=None,
+                 formant=False):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
@@ -609,6 +628,11 @@ class StreamBank:
         if pitch_breakpoints is not None and (isinstance(pitch_breakpoints, bool) or not isinstance(pitch_breakpoints, int) or
                                               not 1 <= pitch_breakpoints <= MAX_GLIDE_POINTS):
             raise ValueError(f"StreamBank: pitch_breakpoints must be an int in 1..{MAX_GLIDE_POINTS}, got {pitch_breakpoints!r}")
+        if not isinstance(formant, bool):
+            raise ValueError(f"StreamBank: formant must be True or False, got {formant!r}")
+        if formant and models is not None:
+            raise ValueError("StreamBank: formant=True with models= is not supported (the per-model row mover indexes the call's "
+                             "rows, the formant row is indexed by slot)")
         self.glide_breakpoints, self.pitch_breakpoints = glide_breakpoints, pitch_breakpoints
         self.active_widths = None if active_widths is None else _check_active_widths(active_widths, self.S)
         if models is None and model_widths is not None:
@@ -676,6 +700,7 @@ class StreamBank:
             self.key_t = torch.zeros(self.S, pitch_breakpoints, dtype=torch.int64, device=dev)
             self.key_semi = torch.zeros(self.S, pitch_breakpoints, device=dev)
             self.key_fac = torch.ones(self.S, pitch_breakpoints, device=dev)
+        self.formant = torch.ones(self.S, device=dev) if formant else None    # a factor per slot (`set_formant`)
         self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
         self.last_mix_w = None           # (A, Fr, max_mix): the block's per-frame weights on a bank with `glide_breakpoints`
@@ -718,9 +743,11 @@ class StreamBank:
             rows.bank_graph = graphed.GraphedBlock(
                 self.model if shared else None, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
                 self.silence_front, rows.pitch_term, self.threshold_db, mix_rows=rows.mix, f0_dither=self.f0_dither, push=rows.push,
-                keep=[c for c in (self.glide_clock, self.key_clock) if c is not None])   # (the capture's runs advance the clocks)
+                keep=[c for c in (self.glide_clock, self.key_clock) if c is not None],   # (the capture's runs advance the clocks)
+                **({} if self.formant is None else {"formant": rows.formant_term}))
         elif shared:
-            rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix)
+            rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix,
+                                              **({} if self.formant is None else {"formant": rows.formant_term}))
         if self.enhancer is not None:
             rows.enhancer_graph = graphed.GraphedBankEnhancer(
                 self.enhancer, self.enhancer_plan, rows.W, rows.request, self.model_sr, self.block_size, self.samplerate,
@@ -847,6 +874,15 @@ class StreamBank:
         if self.key_n is not None:
             self.key_n[slot:slot + 1].zero_()
 
+    def set_formant(self, slot, semitones):
+        """Slot `slot`'s formants are shifted by `semitones` (|s| <= 24, positive: brighter) at the same pitch from the next block
+        on: one write of 2 ** (semitones / 12) to the slot's row of `formant`, no capture.  ValueError on a bank built without
+        `formant=True`, or for a shift that is no finite number within +-24."""
+        if self.formant is None:
+            raise ValueError("StreamBank.set_formant: this bank was built without formant=True")
+        slot = self._slot(slot)
+        self.formant[slot:slot + 1].fill_(hipddsp.formant_factor(semitones))
+
     def set_pitch_timeline(self, slot, timeline, at=0.0):
         """Slot `slot`'s key follows `timeline` (an `infer_offline.KeyTimeline`) from the next block on, in STREAM time, as
         `set_timeline` has it for the voice: time 0 is the first sample pushed after this call, or `at` seconds into the timeline
@@ -892,7 +928,8 @@ class StreamBank:
     def reset(self, slot):
         """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set).  On
         a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning;
-        on one with `pitch_breakpoints` the key clock and the key timeline likewise."""
+        on one with `pitch_breakpoints` the key clock and the key timeline likewise.  On a bank with `formant` the slot's formant
+        factor goes back to 1."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
@@ -900,6 +937,8 @@ class StreamBank:
             self.glide_clock[slot:slot + 1].zero_()
         if self.key_clock is not None:
             self.key_clock[slot:slot + 1].zero_()
+        if self.formant is not None:
+            self.formant[slot:slot + 1].fill_(1.0)
 
     def _check_blocks(self, blocks, A, rows="S"):
         if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
@@ -976,8 +1015,9 @@ class StreamBank:
             sig, f0, units, volume = graphed.block_chain(
                 hipddsp.context_for(self.device), self.model if self._model_rows is None else None, self.units_encoder,
                 self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch_term,
-                self.threshold_db, self.hop, {"spk_id": None, "spk_mix_rows": rows.mix}, noise, self.f0_dither,
-                push=rows.push)
+                self.threshold_db, self.hop,
+                {"spk_id": None, "spk_mix_rows": rows.mix, **({} if self.formant is None else {"formant": rows.formant_term})},
+                noise, self.f0_dither, push=rows.push)
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
@@ -1018,7 +1058,10 @@ class StreamBank:
                 sig = rows.graph(units, f0, volume, None, noise=noise)[0]
             else:
                 kw = {} if noise is None else {"noise": noise}
-                sig = self.model(units, f0, volume, None, spk_mix_rows=rows.mix, **kw)[0]
+                if self.formant is not None:
+                    kw["formant"] = rows.formant_term
+                sig = (self.model if self.formant is None else self.model.forward_formant)(
+                    units, f0, volume, None, spk_mix_rows=rows.mix, **kw)[0]
             ctx.volume_gate_(sig, volume, self.threshold_db, self.hop)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
         if rows.w_frames is not None:

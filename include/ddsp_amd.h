@@ -474,6 +474,32 @@ int ddsp_bank_key_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W,
                         const int64_t* key_t, const float* key_semi, const float* key_fac, int P_max, const float* pitch,
                         int64_t Fr, int64_t n_in, int64_t block, double hop, float* pitch_frames);
 
+/* The FORMANT SHIFT: a warp of spectral-envelope columns of the control matrix ctrl (rows, sum) fp32 along the frequency axis,
+ * IN PLACE, between the control network and the filter synthesis; one launch, one pass over the warped columns.  A definition of
+ * this project (the reference has no such control).
+ * THE RULE.  A segment is n consecutive columns of a row with an origin o: 0 for magnitude bins (bin j lies at j * df), 1 for
+ * harmonics (column j is harmonic j + 1).  For a factor a > 0 the warped segment is the envelope read at f / a, in fp32 with one
+ * rounding per operation and nothing contracted:
+ *     p  = fl(fl(float(j + o) / a) - float(o));   p = min(max(p, 0), float(n - 1))
+ *     i0 = (int)floor(p);  i1 = min(i0 + 1, n - 1);  t = p - float(i0)                 (exact)
+ *     out[j] = (t == 0) ? in[i0] : fl(in[i0] + fl(fl(in[i1] - in[i0]) * t))
+ * t == 0 is a SELECTION: a == 1, every exact hit and every clamped end return the input's bits (-0.0, inf, NaN included); a
+ * segment with n == 1 is copied.  The columns are the network's raw outputs, log-magnitudes, so the interpolation is geometric in
+ * magnitude; a = 2 ** (s / 12) raises the formants by s semitones.
+ * segments: HOST array of n_seg <= 3 triples (first column, n, origin), read during the call; 1 <= n <= 4096, inside the row,
+ * origin 0 or 1.  rows = B * Fr.  The factor of a row, all DEVICE, read when the kernel runs: factor[row] (per_frame != 0,
+ * factor (rows)), factor[row / Fr] (per_frame == 0, factor (B)), or - slot_of_row (B) int32 given, per_frame == 0 -
+ * factor[slot_of_row[row / Fr]] with factor (S); the table's entry is tested against [0, S) before it forms an address and one
+ * outside it is a padding row, factor 1.  n_frames (B) int32 DEVICE or NULL: a frame at or past its row's count (held in
+ * [1, Fr]) has factor 1 whatever the array holds.  A factor that is not finite or not > 0 leaves the row as it was and raises
+ * the device error word (DDSP_ERR_ARG from the next call that takes it, or ddsp_ctx_poll_error): no address depends on the
+ * factor's value.  A row is staged per segment in the LDS before its first store and belongs to one workgroup.  Row strides are
+ * arbitrary (16-byte vectors are used only where the row's own address allows).  DDSP_ERR_ARG, and nothing launched, for a null
+ * pointer, rows not a multiple of Fr, a bad segment, or a row table beside a factor per frame.  Does not synchronise, allocate
+ * or read back; graph-capturable. */
+int ddsp_ctrl_warp(ddsp_ctx* ctx, void* stream, float* ctrl, int64_t rows, int64_t sum, const int32_t* segments, int n_seg,
+                   const float* factor, int per_frame, int64_t Fr, const int32_t* slot_of_row, int64_t S, const int32_t* n_frames);
+
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
  * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)
