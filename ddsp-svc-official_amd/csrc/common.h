@@ -161,6 +161,7 @@ int ddsp_take_dev_error(ddsp_ctx* ctx);
 #define DDSP_DEV_ERR_GATE_ROWS 4 // ddsp_volume_gate_rows / ddsp_volume_gate_files: a row whose frames lie outside the file's volume or its own row
 #define DDSP_DEV_ERR_PIECES 5    // ddsp_pieces_gather: a piece whose range leaves its file or exceeds the output widths
 #define DDSP_DEV_ERR_FORMANT 6   // ddsp_ctrl_warp: a formant factor that is not finite or not > 0
+#define DDSP_DEV_ERR_TUNE 7      // ddsp_f0_tune: a pitch-correction setting with a bad a4, strength or alpha
 
 // profiler hooks (ctx.hip): bracket ONE kernel launch (or a tight group) on `st` when the family is enabled
 void ddsp_prof_begin(ddsp_ctx* ctx, hipStream_t st, int id);

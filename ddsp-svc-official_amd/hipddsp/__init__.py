@@ -259,6 +259,7 @@ SIGNATURES = {
     "ddsp_bank_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _i64, _i64, _i64, _f64, _vp]),
     "ddsp_bank_key_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _f64, _vp]),
     "ddsp_ctrl_warp": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp, _int, _i64, _vp, _i64, _vp]),
+    "ddsp_f0_tune": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
     "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
@@ -1693,6 +1694,37 @@ class Context:
             self.call("ddsp_ctrl_warp", _ptr(ctrl2d), rows, width, table, len(segments), _ptr(factor), per_frame, Fr,
                       _ptr(slot_of_row), S, _ptr(n_dev))
         return ctrl2d
+
+    def f0_tune_(self, f0, mask, param, n_frames=None, owner=None, corr=None):
+        """Pitch correction (`ddsp_f0_tune`; include/ddsp_amd.h states the rule): in place on f0, fp32 (B, Fr) or (B, Fr, 1), every
+        voiced frame is pulled toward the nearest note that its owner's setting allows.  All device tensors: mask (J,) int32 and
+        param (J, 3) fp64 (a4, strength, alpha) are the J settings (`infer_offline.PitchTune.setting`); owner (B,) int32 names
+        the setting of every row - one outside [0, J) is a padding row, left as it is -, None: row b takes setting b; n_frames (B,)
+        int32: the counts of a ragged batch; corr (B, Fr) fp64: receives the correction c_t in semitones, 0 where nothing is
+        corrected.  Shapes, dtypes and devices are refused here, before the launch; a bad setting leaves its rows as they were
+        and raises ValueError from `poll_error()` after a synchronise or from the next call that takes the error word.  -> f0."""
+        if not (isinstance(f0, torch.Tensor) and f0.dtype == torch.float32 and f0.is_contiguous() and f0.is_cuda and
+                (f0.dim() == 2 or (f0.dim() == 3 and f0.shape[2] == 1)) and f0.shape[0] >= 1 and f0.shape[1] >= 1):
+            raise ValueError("f0_tune_: f0 must be a contiguous (B, Fr) or (B, Fr, 1) fp32 device tensor with B, Fr >= 1")
+        B, Fr = int(f0.shape[0]), int(f0.shape[1])
+
+        def on_device(t, dtype, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and \
+                t.device == f0.device
+
+        if not (isinstance(mask, torch.Tensor) and mask.dim() == 1 and mask.numel() >= 1 and on_device(mask, torch.int32, tuple(mask.shape))):
+            raise ValueError("f0_tune_: mask must be a contiguous (J,) int32 tensor on f0's device, J >= 1")
+        J = int(mask.numel())
+        if not on_device(param, torch.float64, (J, 3)):
+            raise ValueError(f"f0_tune_: param must be a contiguous (J = {J}, 3) fp64 tensor on f0's device")
+        if n_frames is not None and not on_device(n_frames, torch.int32, (B,)):
+            raise ValueError(f"f0_tune_: n_frames must be a contiguous (B = {B},) int32 tensor on f0's device")
+        if owner is not None and not on_device(owner, torch.int32, (B,)):
+            raise ValueError(f"f0_tune_: owner must be a contiguous (B = {B},) int32 tensor on f0's device")
+        if corr is not None and not on_device(corr, torch.float64, (B, Fr)):
+            raise ValueError(f"f0_tune_: corr must be a contiguous (B = {B}, Fr = {Fr}) fp64 tensor on f0's device")
+        self.call("ddsp_f0_tune", _ptr(f0), B, Fr, _ptr(n_frames), _ptr(owner), J, _ptr(mask), _ptr(param), _ptr(corr))
+        return f0
 
     def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
         """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row

@@ -20,6 +20,7 @@ job for key, speaker and output span, and the groups are formed model by model. 
 its key a `KeyTimeline`: a voice, or a key, that moves over the file (`ddsp_mix_timeline`, `ddsp_pieces_gather_keys`).  `to_pcm16` turns the result into 16-bit PCM on
 the device (`ddsp_pcm16`), so the read-back is 2 bytes per sample.
 """
+import math
 import numbers
 
 import numpy as np
@@ -469,7 +470,7 @@ def job_formants(jobs):
     semitones or the `FormantTimeline` as it is.  `job_table` has checked them."""
     out = []
     for job in jobs:
-        formant = job[4] if len(job) == 5 else None
+        formant = job[4] if len(job) >= 5 else None
         out.append(formant if formant is None or isinstance(formant, FormantTimeline) else float(formant))
     return out
 
@@ -477,6 +478,95 @@ def job_formants(jobs):
 def formant_tables(formants, sampling_rate, block_size):
     """`key_tables` for `job_formants`' list: a job without a shift is the one breakpoint of 0 semitones, factor 1."""
     return key_tables([0.0 if f is None else f for f in formants], sampling_rate, block_size)
+
+
+NOTE_NAMES = {"C": 0, "D": 2, "E": 4, "F": 5, "G": 7, "A": 9, "B": 11}
+SCALES = {"major": (0, 2, 4, 5, 7, 9, 11), "minor": (0, 2, 3, 5, 7, 8, 10), "chromatic": tuple(range(12)),
+          "major_pentatonic": (0, 2, 4, 7, 9), "minor_pentatonic": (0, 3, 5, 7, 10)}
+
+
+def pitch_class(note):
+    """A pitch class 0..11 (C = 0) as it is, or a note name - a letter A-G, then any number of '#' or 'b' - as its class.
+    ValueError for anything else."""
+    if isinstance(note, numbers.Integral) and not isinstance(note, bool) and 0 <= note <= 11:
+        return int(note)
+    if isinstance(note, str) and note and note[0].upper() in NOTE_NAMES and set(note[1:]) <= {"#", "b"}:
+        return (NOTE_NAMES[note[0].upper()] + note.count("#") - note[1:].count("b")) % 12
+    raise ValueError(f"a note is a pitch class 0..11 or a name such as 'A', 'F#' or 'Bb', got {note!r}")
+
+
+class PitchTune:
+    """Pitch correction of a job (its sixth entry) or of a bank's slot (`StreamBank.set_tune`): the sung f0 is pulled toward the
+    nearest allowed note (include/ddsp_amd.h states the rule at `ddsp_f0_tune`).  notes: an iterable of pitch classes 0..11
+    (C = 0) or note names, at least one; strength in [0, 1]: the share of the correction that is applied; retune: seconds, the
+    time constant at which the correction follows a new note (0: at once - with strength 1 that is hard tuning); a4: the Hz of
+    A4.  ValueError for an empty note set, a strength outside [0, 1], a negative or non-finite retune, or an a4 that is not a
+    finite number > 0."""
+
+    def __init__(self, notes, strength=1.0, retune=0.05, a4=440.0):
+        if isinstance(notes, (str, numbers.Number)):
+            raise ValueError(f"PitchTune: notes must be an iterable of pitch classes or note names, got {notes!r}")
+        try:
+            classes = sorted({pitch_class(n) for n in notes})
+        except TypeError:
+            raise ValueError(f"PitchTune: notes must be an iterable of pitch classes or note names, got {notes!r}") from None
+        except ValueError as e:
+            raise ValueError(f"PitchTune: {e}") from None
+        if not classes:
+            raise ValueError("PitchTune: the note set is empty")
+
+        def real(x):
+            return isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x)
+        if not (real(strength) and 0 <= strength <= 1):
+            raise ValueError(f"PitchTune: strength must be a number in [0, 1], got {strength!r}")
+        if not (real(retune) and retune >= 0):
+            raise ValueError(f"PitchTune: retune must be a finite number of seconds >= 0, got {retune!r}")
+        if not (real(a4) and a4 > 0):
+            raise ValueError(f"PitchTune: a4 must be a finite number of Hz > 0, got {a4!r}")
+        self.notes, self.strength, self.retune, self.a4 = tuple(classes), float(strength), float(retune), float(a4)
+        self.mask = sum(1 << p for p in classes)
+
+    @classmethod
+    def scale(cls, tonic, kind="major", **kw):
+        """The scale of `kind` - major, minor (natural), chromatic, major_pentatonic, minor_pentatonic - on `tonic` (a pitch
+        class or a note name); the keywords are the constructor's."""
+        if kind not in SCALES:
+            raise ValueError(f"PitchTune.scale: kind must be one of {', '.join(SCALES)}, got {kind!r}")
+        try:
+            root = pitch_class(tonic)
+        except ValueError as e:
+            raise ValueError(f"PitchTune.scale: {e}") from None
+        return cls([(root + step) % 12 for step in SCALES[kind]], **kw)
+
+    @classmethod
+    def named(cls, text, **kw):
+        """'A minor', 'F# major_pentatonic', 'C' (major): `scale` from one string, as main.py's options take it."""
+        words = text.split() if isinstance(text, str) else []
+        if not 1 <= len(words) <= 2:
+            raise ValueError(f"PitchTune.named: a scale is '<tonic> [<kind>]' such as 'A minor', got {text!r}")
+        return cls.scale(words[0], *words[1:], **kw)
+
+    def setting(self, hop_seconds):
+        """-> (mask, (a4, strength, alpha)) as `ddsp_f0_tune` takes them for frames `hop_seconds` apart:
+        alpha = 1 - exp(-hop_seconds / retune), 1 for a retune of 0 (and where the quotient is so large that exp gives 0)."""
+        if not (isinstance(hop_seconds, numbers.Real) and math.isfinite(hop_seconds) and hop_seconds > 0):
+            raise ValueError(f"PitchTune.setting: hop_seconds must be a finite number > 0, got {hop_seconds!r}")
+        alpha = 1.0 if self.retune == 0 else -math.expm1(-float(hop_seconds) / self.retune)
+        return self.mask, (self.a4, self.strength, alpha)
+
+
+def job_tunes(jobs):
+    """The pitch correction of every job of a `job_table` call, in job order: the `PitchTune` of a 6-tuple, else None."""
+    return [job[5] if len(job) == 6 else None for job in jobs]
+
+
+def tune_tables(tunes, sampling_rate, block_size):
+    """The settings `ddsp_f0_tune` takes for `job_tunes`' list at the model's frame rate -> CPU tensors (mask (J,) int32, param
+    (J, 3) fp64: a4, strength, alpha); a job without a tune is off: mask 0, (440, 0, 1)."""
+    hop = float(block_size) / float(sampling_rate)
+    settings = [(0, (440.0, 0.0, 1.0)) if t is None else t.setting(hop) for t in tunes]
+    return (torch.tensor([m for m, _ in settings], dtype=torch.int32),
+            torch.tensor([list(p) for _, p in settings], dtype=torch.float64).reshape(-1, 3))
 
 
 def _check_formant(j, formant, model):
@@ -512,9 +602,12 @@ def job_table(pieces, n_files, jobs, models):
       starts_per_job  the start frames of every job's rows, as `stitch_plan_many` takes them with jobs in the place of files.
     A job may carry a fifth entry, its FORMANT shift: a number of semitones (|s| <= 24), a `FormantTimeline` or None.  It is
     checked here and stands in no table of the dict: `job_formants(jobs)` lists it, `formant_tables` makes its breakpoints.
-    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4- or 5-tuple, a file
-    or model index out of range, a speaker id outside [1, n_spk] of the JOB's model, a mix with no or too many speakers, or a
-    formant shift that is no finite number within +-24 semitones and no `FormantTimeline` that fits the model's frame rate."""
+    A sixth entry is its PITCH CORRECTION, a `PitchTune` or None (the formant may then be None too): `job_tunes(jobs)` lists
+    it, `tune_tables` makes its settings.
+    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4-, 5- or 6-tuple, a
+    file or model index out of range, a speaker id outside [1, n_spk] of the JOB's model, a mix with no or too many speakers, a
+    formant shift that is no finite number within +-24 semitones and no `FormantTimeline` that fits the model's frame rate, or
+    a tune that is no `PitchTune`."""
     from realtime import MODEL_FIELDS, _model_field
     models = list(models) if isinstance(models, (tuple, list)) else []
     if not models:
@@ -529,9 +622,10 @@ def job_table(pieces, n_files, jobs, models):
     table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": [],
              "keys": []}
     for j, job in enumerate(jobs):
-        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5)):
-            raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key) or (file, model_index, spk, key, formant), "
-                             f"got {job!r}")
+        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5, 6) and (len(job) < 6 or job[5] is None or
+                                                                             isinstance(job[5], PitchTune))):
+            raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key), (file, model_index, spk, key, formant) or "
+                             f"(file, model_index, spk, key, formant, tune) with tune a PitchTune or None, got {job!r}")
         file, m, spk, key = job[:4]
         if not (isinstance(file, numbers.Integral) and 0 <= file < int(n_files)):
             raise ValueError(f"job_table: job {j}: file {file!r} is outside the {int(n_files)} files of the call")
@@ -559,7 +653,7 @@ def job_table(pieces, n_files, jobs, models):
                 raise ValueError(f"job_table: job {j}: speaker id {i!r} is outside [1, {n_spk}] of models[{m}]")
         if isinstance(key, FormantTimeline):
             raise ValueError(f"job_table: job {j}: key must be a number of semitones or a KeyTimeline, got a FormantTimeline")
-        if len(job) == 5:
+        if len(job) >= 5:
             _check_formant(j, job[4], models[m])
         if isinstance(key, KeyTimeline):
             try:
@@ -866,6 +960,7 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
         table_models = [m for m, _ in numbered]
     given = None if jobs is None else rows
     formant = None if jobs is None else jobs[1].get("formant")       # (models with a formant among their jobs, tables, f0 of ones)
+    tune = None if jobs is None else jobs[1].get("tune")             # (the settings of all jobs, when one of them has a tune)
     table, cols, bounds = _upload_pieces(ctx, files, groups, given)
     speaker_of_rows = speaker(cols[0], [i for group in groups for i in group])
     out = [None] * len(rows)
@@ -874,6 +969,8 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
         u, _ = stack_rows([units[unit_of[i]][0] for i in group])
         _, f, v = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
                                     volume=files["volume"], N_max=max(counts), **key)
+        if tune is not None:                                         # behind the key: the output lands in the scale
+            ctx.f0_tune_(f, *tune, n_frames=cols[2, a:b], owner=cols[5, a:b])
         kw = {} if seed_of_group is None else {"noise_seed": seed_of_group(g, [rows[i][1] for i in group])}
         if noise is not None:
             kw["noise"] = stack_rows([noise[i].reshape(-1) for i in group])[0]
@@ -893,28 +990,31 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
     sr_o = sr
     if enhancer is not None and rows:
         out, sr_o = _enhance_many(ctx, enhancer, out, files, sr, block, enhancer_adaptive_key,
-                                  0 if enhancer_batch_samples is None else enhancer_batch_samples, given, key)
+                                  0 if enhancer_batch_samples is None else enhancer_batch_samples, given, key, tune)
     per_out = [[i for i, row in enumerate(rows) if row[owner] == k] for k in range(n_out)]
     spans, p, fade, total = stitch_plan_many([[rows[i][1] for i in idx] for idx in per_out],
                                              [[out[i].shape[-1] for i in idx] for idx in per_out], block, sr, sr_o)
     return ctx.stitch(out, p, fade, total), spans, sr_o
 
 
-def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples, rows=None, key=None):
+def _enhance_many(ctx, enhancer, gated, files, sr, block, adaptive_key, enhancer_batch_samples, rows=None, key=None, tune=None):
     """The device path's enhancer loop over the gated pieces of all files: one `Enhancer.enhance_batch` per group of
     `group_segments` over the sample lengths, every row with its own file's shifted f0 (one `ddsp_pieces_gather` per group).
     rows, key: `job_table`'s rows and the jobs' keys - `pieces_gather`'s keyword `key_factor` or `key_timeline` with its value -
-    in place of the files' (one enhancer serves all models)."""
+    in place of the files' (one enhancer serves all models).  tune: the jobs' pitch-correction settings (`tune_tables` on the
+    device) or None: every row's f0 is corrected as the render corrected it - the same kernel on the same row."""
     pieces = files["pieces"] if rows is None else rows
     key = {"key_factor": files["key_factor"]} if key is None else key
     groups = group_segments([g.shape[-1] for g in gated], int(enhancer_batch_samples))
-    table, _, bounds = _upload_pieces(ctx, files, groups, rows)
+    table, cols, bounds = _upload_pieces(ctx, files, groups, rows)
     out, sr_o = [None] * len(gated), sr
     for group, (a, b) in zip(groups, bounds):
         wav, counts = stack_rows([gated[i][0] for i in group])
         n_f0 = [pieces[i][2] for i in group]
         _, tracks, _ = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
                                          N_max=max(n_f0), **key)
+        if tune is not None:
+            ctx.f0_tune_(tracks, *tune, n_frames=cols[2, a:b], owner=cols[5, a:b])
         got, sr_o, n_out = enhancer.enhance_batch(wav, sr, tracks[:, :, None], block, counts, adaptive_key=adaptive_key, n_f0=n_f0)
         for j, i in enumerate(group):
             out[i] = got[j:j + 1, :n_out[j]]
@@ -958,6 +1058,11 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     `FormantTimeline`.  A model with a formant among its jobs renders all its groups through `forward_formant` with a factor per
     frame - the key timeline rule at every frame's own file frame, one `ddsp_pieces_gather_keys` launch per group over an f0 of
     ones -; a model without one takes the path above, bit for bit.  The enhancer is not told of the shift: it follows f0.
+    A job may be a 6-tuple (file, model_index, spk, key, formant, tune): PITCH CORRECTION, a `PitchTune` or None (the formant may
+    be None as well).  With a tune among the jobs the settings of all jobs go up once (`tune_tables`) and every gather of f0 -
+    the render groups and the enhancer's - is followed by one `ddsp_f0_tune` launch on the group's rows, behind the key, with
+    the rows' jobs as their owners: the rows of a job without a tune keep their bits, and the enhancer sees the corrected f0.
+    The correction restarts at every slice.  Without a tune among the jobs nothing is launched: the call above, bit for bit.
     noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
     `models` order - draws with (noise_seed + g * 2**32) mod 2**64."""
     models = _models_of("render_jobs_device", None, models)
@@ -982,6 +1087,12 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
         tabs = formant_tables(formants, _model_field(models[0], "sampling_rate"), _model_field(models[0], "block_size"))
         table["formant"] = ({table["model_of_job"][j] for j, f in enumerate(formants) if f is not None},
                             tuple(t.to(dev) for t in tabs), torch.ones_like(files["f0"]))
+
+    tunes = job_tunes(jobs)
+    if any(t is not None for t in tunes):
+        from realtime import _model_field
+        table["tune"] = tuple(t.to(dev) for t in tune_tables(tunes, _model_field(models[0], "sampling_rate"),
+                                                             _model_field(models[0], "block_size")))
 
     def speaker(file_of_row, order):
         # Every row takes its job's speaker, from host tables uploaded once in front of the launches (the job of a row is known

@@ -10,13 +10,19 @@ stitched waveform on the device and is read back once.
 timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...] (a voice that glides over the file,
 `infer_offline.SpeakerTimeline`), key: <semitones, default 0> | key_timeline: [{at: <seconds>, key: <semitones>}, ...] (a key
 that moves over the file, `infer_offline.KeyTimeline`), formant: <semitones, default 0> | formant_timeline: [{at: <seconds>,
-formant: <semitones>}, ...] (a formant shift, `infer_offline.FormantTimeline`), suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
+formant: <semitones>}, ...] (a formant shift, `infer_offline.FormantTimeline`), tune: {scale: "A minor" | notes: [<pitch class or
+name>, ...], strength: <0..1, default 1>, retune_ms: <default 50>, a4: <Hz, default 440>} (pitch correction,
+`infer_offline.PitchTune`), suffix: <text>}.  Every entry is applied to every `.wav` of the folder: file `name.wav` and suffix `s`
 give `name_s.wav`.  All of it is ONE `convert_many_device(jobs=...)` - every file analysed once - and one read-back; `-id`,
 `-mix` and `-k` are then unused.
 
 `--formant_shift_key S` (long option only, default 0) shifts the formants of the file or folder by S semitones at the same pitch
 (`forward_formant`); it runs through the jobs path, one job per file, and with `--jobs` it is the shift of the entries that
 name none.
+
+`--tune_scale "A minor"` (long options only; with `--tune_strength`, `--tune_retune_ms` and `--tune_a4`, defaults 1, 50 and 440)
+pulls the sung f0 toward the notes of that scale (`infer_offline.PitchTune`, behind the key shift); it runs through the jobs
+path like `--formant_shift_key`, and with `--jobs` it is the tune of the entries that name none.
 
 The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
   * the key shift is applied once (the reference applies it twice, SURVEY 0.3);
@@ -61,6 +67,11 @@ def parse_args(args=None, namespace=None):
     # (absent from the namespace unless given: the reference's options are the namespace of a plain call)
     parser.add_argument("--formant_shift_key", type=str, default=argparse.SUPPRESS, help="formant shift (number of semitones, "
                         "positive: brighter) for the file or folder | default: 0")
+    parser.add_argument("--tune_scale", type=str, default=argparse.SUPPRESS, help="pitch correction toward the notes of a scale, "
+                        "'<tonic> [major | minor | chromatic | major_pentatonic | minor_pentatonic]' such as 'A minor' | default: off")
+    parser.add_argument("--tune_strength", type=str, default=argparse.SUPPRESS, help="share of the correction applied, 0..1 | default: 1")
+    parser.add_argument("--tune_retune_ms", type=str, default=argparse.SUPPRESS, help="retune time in milliseconds, 0: at once | default: 50")
+    parser.add_argument("--tune_a4", type=str, default=argparse.SUPPRESS, help="the Hz of A4 | default: 440")
     parser.add_argument("--jobs", type=str, default=argparse.SUPPRESS, help="YAML list of {model, id | mix, key, suffix}: every entry is applied "
                         "to every .wav of the input folder")
     return parser.parse_args(args=args, namespace=namespace)
@@ -123,7 +134,7 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
             raise ValueError("--jobs goes with a folder as -i (and a folder as -o)")
         return _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                          enhancer_batch_samples, units_batch_samples)
-    if float(getattr(cmd, "formant_shift_key", 0)) != 0:
+    if float(getattr(cmd, "formant_shift_key", 0)) != 0 or _cmd_tune(cmd) is not None:
         return _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                             enhancer_batch_samples, units_batch_samples)
     if os.path.isdir(cmd.input):
@@ -167,14 +178,16 @@ def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhan
 
 def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
                  units_batch_samples):
-    """`run` with `--formant_shift_key S` and no `--jobs`: the file, or every `.wav` of the folder, as one job each - `-id` or
-    `-mix`, `-k` and the shift - through ONE `infer_offline.convert_many_device(jobs=...)`; outputs as `run` names them."""
+    """`run` with `--formant_shift_key S` or `--tune_scale` and no `--jobs`: the file, or every `.wav` of the folder, as one job
+    each - `-id` or `-mix`, `-k`, the shift and the tune - through ONE `infer_offline.convert_many_device(jobs=...)`; outputs as `run` names them."""
     from infer_offline import convert_many_device
     folder = os.path.isdir(cmd.input)
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav")) if folder else [None]
     audios = [load(os.path.join(cmd.input, n) if folder else cmd.input) for n in names]
     mix = literal_eval(cmd.spk_mix_dict)
-    jobs = [(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), float(cmd.formant_shift_key)) for k in range(len(names))]
+    shift, tune = float(getattr(cmd, "formant_shift_key", 0)), _cmd_tune(cmd)
+    jobs = [(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), shift if shift != 0 else None) +
+            (() if tune is None else (tune,)) for k in range(len(names))]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=[model], batch_frames=batch_frames,
         threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
@@ -208,13 +221,13 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
         if path not in paths:
             paths.append(path)
             models.append(load_model(path, device=device)[0])
-        voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift)))
+        voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift), _job_tune(n, e, _cmd_tune(cmd))))
     if len({v[3] for v in voices}) != len(voices):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
     audios = [load(os.path.join(cmd.input, n)) for n in names]
-    jobs = [(k, m, spk, key) + (() if formant is None else (formant,)) for k in range(len(names))
-            for m, spk, key, _, formant in voices]
+    jobs = [(k, m, spk, key) + ((formant, tune) if tune is not None else () if formant is None else (formant,))
+            for k in range(len(names)) for m, spk, key, _, formant, tune in voices]
     out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{v[3]}.wav") for name in names for v in voices]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=models, batch_frames=batch_frames,
@@ -230,7 +243,7 @@ def _job_entry(n, e):
     """Entry n of the `--jobs` list -> (spk, key) as `infer_offline.job_table` takes them: the speaker from `id`, `mix` or
     `timeline` (at most one of them; default id 1), the key from `key` or `key_timeline` (not both; default 0).  ValueError for an
     unknown field, two speakers, two keys or a missing suffix."""
-    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "formant", "formant_timeline", "suffix"}
+    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "formant", "formant_timeline", "tune", "suffix"}
     if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or ("key" in e and "key_timeline" in e) or \
             not str(e.get("suffix", "")):
         raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key or key_timeline and a non-empty suffix, "
@@ -253,6 +266,34 @@ def _job_formant(n, e, default=0.0):
         return FormantTimeline([(p["at"], p["formant"]) for p in points])
     shift = float(e.get("formant", default))
     return None if shift == 0 else shift
+
+
+def _tune(where, scale=None, notes=None, strength=1.0, retune_ms=50.0, a4=440.0):
+    """`infer_offline.PitchTune` from a scale ('A minor') or a list of notes - one of them - with the retune time in milliseconds."""
+    from infer_offline import PitchTune
+    if (scale is None) == (notes is None):
+        raise ValueError(f"{where}: a tune takes scale or notes, one of them")
+    kw = {"strength": float(strength), "retune": float(retune_ms) / 1000.0, "a4": float(a4)}
+    return PitchTune.named(scale, **kw) if notes is None else PitchTune(notes, **kw)
+
+
+def _cmd_tune(cmd):
+    """`--tune_scale` with `--tune_strength`, `--tune_retune_ms` and `--tune_a4` -> a PitchTune, None without `--tune_scale`."""
+    if getattr(cmd, "tune_scale", None) is None:
+        return None
+    return _tune("--tune_scale", scale=cmd.tune_scale, strength=getattr(cmd, "tune_strength", 1.0),
+                 retune_ms=getattr(cmd, "tune_retune_ms", 50.0), a4=getattr(cmd, "tune_a4", 440.0))
+
+
+def _job_tune(n, e, default=None):
+    """Entry n's pitch correction as a job's sixth entry: `tune: {scale | notes, strength, retune_ms, a4}`, else `default`
+    (`--tune_scale`)."""
+    if "tune" not in e:
+        return default
+    t = e["tune"]
+    if not (isinstance(t, dict) and set(t) <= {"scale", "notes", "strength", "retune_ms", "a4"}):
+        raise ValueError(f"--jobs: entry {n}: tune is {{scale | notes, strength, retune_ms, a4}}, got {t!r}")
+    return _tune(f"--jobs: entry {n}", **t)
 
 
 def _timeline(n, points):

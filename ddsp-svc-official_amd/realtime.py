@@ -460,6 +460,13 @@ class _Rows:
         return None if f is None else (f if self.rows is None else (f, self.rows))
 
     @property
+    def tune_term(self):
+        """The pitch-correction term of this instance's chain (`graphed.block_chain`'s `tune`): None on a bank without `tune`;
+        the slots' settings, with the width's row table as the owner of every row on a compact instance (a padding row has none)."""
+        b = self.bank
+        return None if b.tune_mask is None else (b.tune_mask, b.tune_param, self.rows)
+
+    @property
     def pitch_term(self):
         """The pitch term of this instance's chain: a factor per row, or per frame on a bank with `pitch_breakpoints`."""
         return self.pitch if self.pitch_frames is None else self.pitch_frames
@@ -606,6 +613,18 @@ class StreamBank:
     `active_widths` and the enhancer (which is not told of the shift: it follows f0).  Refused: `formant=True` with `models=`;
     `set_formant` on a bank without it.
 
+    Pitch correction per slot (`tune=True`; the default False allocates, captures and launches nothing of this, and the bank is
+    the bank above, bit for bit).  Every slot then has a row of `tune_mask` (S,) int32 and `tune_param` (S, 3) fp64 (a4, strength,
+    alpha), initially off (mask 0); `set_tune(slot, PitchTune | None)` writes the slot's setting with
+    hop_seconds = hop_size / samplerate and `reset(slot)` switches it off: device rows only, `graph_builds` stays what it was.
+    Every chain of such a bank runs one `ddsp_f0_tune` launch right behind the pitch multiply (include/ddsp_amd.h states the
+    rule) - inside the captured block under `push_audio`, behind the multiply of `push_block` -, at a compact width with the
+    width's row table as the owner of every row.  It sits in the shared analysis, so it works with `models=` as well as with
+    `active_widths`, `pitch_breakpoints`, `glide_breakpoints`, `formant` and the enhancer, which sees the corrected f0.
+    DIVERGENCE: the correction's recurrence restarts at the first frame of the re-rendered window in every block; the window
+    is at least a second long, only its tail is spliced and the cross-fade hides the rest.  The bank carries no state for it,
+    so a paused slot has none to keep.  Refused: `set_tune` on a bank without it.
+
     Not in the bank: a formant shift on a bank with `models=`, or one that moves along a timeline; streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
     grows after construction; a weight set per row inside the control network's kernels; an enhancer per model; a glide on a
     bank with `models=`."""
@@ -614,7 +633,7 @@ class StreamBank:
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
                  active_widths=None, models=None, model_widths=None, glide_breakpoints=None, pitch_breakpoints=None,
-                 formant=False):
+                 formant=False, tune=False):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
@@ -630,6 +649,8 @@ class StreamBank:
             raise ValueError(f"StreamBank: pitch_breakpoints must be an int in 1..{MAX_GLIDE_POINTS}, got {pitch_breakpoints!r}")
         if not isinstance(formant, bool):
             raise ValueError(f"StreamBank: formant must be True or False, got {formant!r}")
+        if not isinstance(tune, bool):
+            raise ValueError(f"StreamBank: tune must be True or False, got {tune!r}")
         if formant and models is not None:
             raise ValueError("StreamBank: formant=True with models= is not supported (the per-model row mover indexes the call's "
                              "rows, the formant row is indexed by slot)")
@@ -701,6 +722,10 @@ class StreamBank:
             self.key_semi = torch.zeros(self.S, pitch_breakpoints, device=dev)
             self.key_fac = torch.ones(self.S, pitch_breakpoints, device=dev)
         self.formant = torch.ones(self.S, device=dev) if formant else None    # a factor per slot (`set_formant`)
+        self.tune_mask = self.tune_param = None                      # a setting per slot (`set_tune`), off: no bit of the mask
+        if tune:
+            self.tune_mask = torch.zeros(self.S, dtype=torch.int32, device=dev)
+            self.tune_param = torch.tensor([[440.0, 0.0, 1.0]] * self.S, dtype=torch.float64).to(dev)
         self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
         self.last_mix_w = None           # (A, Fr, max_mix): the block's per-frame weights on a bank with `glide_breakpoints`
@@ -744,7 +769,8 @@ class StreamBank:
                 self.model if shared else None, self.units_encoder, self.f0_extractor, rows.windows, self.block, self.samplerate, self.hop_size,
                 self.silence_front, rows.pitch_term, self.threshold_db, mix_rows=rows.mix, f0_dither=self.f0_dither, push=rows.push,
                 keep=[c for c in (self.glide_clock, self.key_clock) if c is not None],   # (the capture's runs advance the clocks)
-                **({} if self.formant is None else {"formant": rows.formant_term}))
+                **({} if self.formant is None else {"formant": rows.formant_term}),
+                **({} if self.tune_mask is None else {"tune": rows.tune_term}))
         elif shared:
             rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix,
                                               **({} if self.formant is None else {"formant": rows.formant_term}))
@@ -883,6 +909,20 @@ class StreamBank:
         slot = self._slot(slot)
         self.formant[slot:slot + 1].fill_(hipddsp.formant_factor(semitones))
 
+    def set_tune(self, slot, tune):
+        """Slot `slot`'s f0 is pulled toward the notes of `tune` (an `infer_offline.PitchTune`) from the next block on, None
+        switches it off: one write to the slot's rows of `tune_mask` and `tune_param`, no capture.  ValueError on a bank built
+        without `tune=True`, or for anything but a PitchTune or None."""
+        if self.tune_mask is None:
+            raise ValueError("StreamBank.set_tune: this bank was built without tune=True")
+        from infer_offline import PitchTune
+        if tune is not None and not isinstance(tune, PitchTune):
+            raise ValueError(f"StreamBank.set_tune: tune must be an infer_offline.PitchTune or None, got {tune!r}")
+        slot = self._slot(slot)
+        mask, param = (0, (440.0, 0.0, 1.0)) if tune is None else tune.setting(self.hop_size / self.samplerate)
+        self.tune_mask[slot:slot + 1].fill_(mask)
+        self.tune_param[slot:slot + 1].copy_(torch.tensor([param], dtype=torch.float64))
+
     def set_pitch_timeline(self, slot, timeline, at=0.0):
         """Slot `slot`'s key follows `timeline` (an `infer_offline.KeyTimeline`) from the next block on, in STREAM time, as
         `set_timeline` has it for the voice: time 0 is the first sample pushed after this call, or `at` seconds into the timeline
@@ -929,7 +969,7 @@ class StreamBank:
         """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set).  On
         a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning;
         on one with `pitch_breakpoints` the key clock and the key timeline likewise.  On a bank with `formant` the slot's formant
-        factor goes back to 1."""
+        factor goes back to 1, on one with `tune` the slot's pitch correction is switched off."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
@@ -939,6 +979,8 @@ class StreamBank:
             self.key_clock[slot:slot + 1].zero_()
         if self.formant is not None:
             self.formant[slot:slot + 1].fill_(1.0)
+        if self.tune_mask is not None:
+            self.tune_mask[slot:slot + 1].zero_()
 
     def _check_blocks(self, blocks, A, rows="S"):
         if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
@@ -1017,7 +1059,7 @@ class StreamBank:
                 self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch_term,
                 self.threshold_db, self.hop,
                 {"spk_id": None, "spk_mix_rows": rows.mix, **({} if self.formant is None else {"formant": rows.formant_term})},
-                noise, self.f0_dither, push=rows.push)
+                noise, self.f0_dither, push=rows.push, **({} if self.tune_mask is None else {"tune": rows.tune_term}))
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)
@@ -1050,6 +1092,8 @@ class StreamBank:
         units = rows.pad(units.to(self.device))
         f0 = rows.pad(f0.to(self.device, torch.float32)) * \
             (rows.pitch[:, None, None] if rows.pitch_frames is None else rows.pitch_frames[:, :, None])
+        if self.tune_mask is not None:
+            ctx.f0_tune_(f0, *rows.tune_term[:2], owner=rows.rows)
         volume = ctx.volume_extract(rows.windows, self.hop_size)
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)

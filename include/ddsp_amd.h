@@ -500,6 +500,39 @@ int ddsp_bank_key_glide(ddsp_ctx* ctx, void* stream, const int32_t* rows, int W,
 int ddsp_ctrl_warp(ddsp_ctx* ctx, void* stream, float* ctrl, int64_t rows, int64_t sum, const int32_t* segments, int n_seg,
                    const float* factor, int per_frame, int64_t Fr, const int32_t* slot_of_row, int64_t S, const int32_t* n_frames);
 
+/* PITCH CORRECTION: the f0 of a row, f0 (B, Fr) fp32 IN PLACE, is pulled toward the notes of a scale, with a strength and a
+ * retune speed; it runs between the analysis (after the key) and the synthesiser.  A definition of this project (the reference
+ * has no such control).  One launch; every pointer is a DEVICE pointer, read when the kernel runs.
+ * THE SETTING of an owner (a job offline, a slot live), J of them: mask (J) int32 - bit p in 0..11 allows pitch class p, C = 0,
+ * MIDI note n has class n mod 12; only those twelve bits count and none of them set means OFF -; param (J, 3) fp64: a4 in Hz,
+ * the strength s in [0, 1], alpha in (0, 1].  The host forms alpha = 1 - exp(-hop_seconds / retune_seconds), 1 for a retune of 0.
+ * The owner of row b is owner[b] (int32), or b for owner == NULL; n_frames (B) int32 or NULL are the rows' counts n_b, held in
+ * [1, Fr].
+ * THE RULE.  A frame is VOICED when its f0 is finite and > 0.  For t = 0 .. n_b - 1, all in fp64 with one rounding per operation
+ * and nothing contracted:
+ *     m_t = 69 + 12 * log2(f_t / a4)
+ *     n_t = the integer n with bit (n mod 12) of mask set that minimises |n - m_t|; a tie takes the smaller n
+ *     d_t = n_t - m_t        (|d_t| <= 6; 0 where m_t is not finite, which takes an a4 beyond 1e+-260)
+ *     c_t = d_t                                  if t is the row's first voiced frame, or frame t-1 is unvoiced   (a RESET)
+ *     c_t = (1 - alpha) * c_(t-1) + alpha * d_t  otherwise
+ *     out_t = (s * c_t == 0) ? f_t (its bits) : (float)((double)f_t * exp2(s * c_t / 12))
+ * alpha == 1 with s == 1 is hard tuning; a small alpha low-passes the correction, so vibrato survives and note changes glide.
+ * The recurrence restarts at every row start: the kernel carries no state from one call to the next.
+ * UNTOUCHED, by selection and not by arithmetic, so their bits stay: unvoiced frames; frames at or past the row's count; rows
+ * whose owner is off (no bit of the mask, or s == 0); rows whose owner index lies outside [0, J) - padding: the index is tested
+ * before any address is formed and the error word is not set.
+ * A BAD SETTING - a mask with a4 not finite or not > 0, s outside [0, 1] or alpha outside (0, 1] - leaves its rows untouched
+ * and raises the device error word (DDSP_ERR_ARG from the next call that takes it, or ddsp_ctx_poll_error); a setting without a
+ * mask is off and is not judged, nor is one that no row names.  No address depends on a setting's value.
+ * corr (B, Fr) fp64 or NULL: c_t, and 0 where nothing is corrected (every element of the array is written).
+ * One wave per row steps over the row 64 frames at a time: an inclusive wavefront scan of the affine maps c -> A * c + B
+ * ((1 - alpha, alpha * d), (0, d) on a reset, (0, 0) unvoiced), the carry handed from step to step.  Its grouping differs from
+ * the serial order by rounding alone (some 1e-15 a composition, |c| <= 6); with alpha == 1 it is bit for bit.
+ * DDSP_ERR_ARG, and nothing launched, for a null f0, mask or param or B, Fr or J < 1.  Does not synchronise, allocate or read
+ * back; graph-capturable. */
+int ddsp_f0_tune(ddsp_ctx* ctx, void* stream, float* f0, int64_t B, int64_t Fr, const int32_t* n_frames, const int32_t* owner,
+                 int64_t J, const int32_t* mask, const double* param, double* corr);
+
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
  * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)

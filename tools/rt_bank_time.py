@@ -49,7 +49,14 @@ bank of this tree with `pitch_breakpoints=4` and no timeline set (one more launc
 factor to its frames); `pitch`, the same bank with a key timeline on every slot that ramps through the whole run.
 
     python tools/rt_bank_time.py --baseline-tree <parent checkout> --pitch-glide --streams 16 --shapes config5
-                                 [--out profiles/rt_bank_pitch_time.json]"""
+                                 [--out profiles/rt_bank_pitch_time.json]
+
+`--tune` times what pitch correction costs a bank, the same way: `parent`, the bank of the baseline tree; `plain`, the bank of
+this tree built without `tune=True` (the same launches as the parent's); `tune`, the bank of this tree with `tune=True` and a
+scale on every slot (one more launch per block, `ddsp_f0_tune`, inside the captured block).
+
+    python tools/rt_bank_time.py --baseline-tree <parent checkout> --tune --streams 16 --shapes config5
+                                 [--out profiles/rt_bank_tune_time.json]"""
 import argparse
 import contextlib
 import json
@@ -71,7 +78,7 @@ SHIPPED_NSF = dict(upsample_rates=[8, 8, 2, 2, 2], upsample_kernel_sizes=[16, 16
 
 
 def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), active=None, models=None, streams=STREAMS):
-    """One leg in this process: `which` = 'bank' | 'solo' | 'plain' | 'parent' | 'glide' | 'unused' | 'pitch', the package taken from `tree`.  Prints one
+    """One leg in this process: `which` = 'bank' | 'solo' | 'plain' | 'parent' | 'glide' | 'unused' | 'pitch' | 'tune', the package taken from `tree`.  Prints one
     JSON row per case."""
     sys.path.insert(0, os.path.join(tree, "ddsp-svc-official_amd"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -128,7 +135,13 @@ def leg(which, tree, blocks, warmup, with_enhancer=False, shapes=tuple(SHAPES), 
                         kw.update(glide_breakpoints=4)
                     if which in ("unused", "pitch"):
                         kw.update(pitch_breakpoints=4)
+                    if which == "tune":
+                        kw.update(tune=True)
                     bank = realtime.StreamBank(model, S, DEVICE_SR, block_time, xfade_time, dev, **kw)
+                    if which == "tune":     # every slot in a scale of its own, at 50 ms
+                        from infer_offline import PitchTune
+                        for s in range(S):
+                            bank.set_tune(s, PitchTune.scale(s % 12, ("major", "minor", "major_pentatonic")[s % 3]))
                     for s in range(S if "models" in kw else 0):
                         bank.set_model(s, s % len(pool))
                     if which == "glide":    # every slot ramps between two voices for the whole run, each at its own pace
@@ -194,7 +207,8 @@ def main():
     ap.add_argument("--glide", action="store_true", help="three bank legs: the parent's, this tree's without and with a glide on every slot")
     ap.add_argument("--pitch-glide", action="store_true", help="three bank legs: the parent's, this tree's with pitch_breakpoints unused and with a "
                     "key timeline on every slot")
-    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain", "parent", "glide", "unused", "pitch"], help=argparse.SUPPRESS)
+    ap.add_argument("--tune", action="store_true", help="three bank legs: the parent's, this tree's without tune=True and with a scale on every slot")
+    ap.add_argument("--leg", default=None, choices=["bank", "solo", "plain", "parent", "glide", "unused", "pitch", "tune"], help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.leg:
@@ -207,8 +221,11 @@ def main():
         raise SystemExit("rt_bank_time: --glide does not combine with --models (such a bank refuses a glide) or --enhancer")
     if a.pitch_glide and (a.glide or a.models or a.enhancer):
         raise SystemExit("rt_bank_time: --pitch-glide is a run of its own (no --glide, --models or --enhancer)")
-    three = ("parent", "plain", "glide") if a.glide else ("parent", "unused", "pitch") if a.pitch_glide else None
-    trees = {"bank": ROOT, "plain": ROOT, "glide": ROOT, "unused": ROOT, "pitch": ROOT, "solo": os.path.abspath(a.baseline_tree), "parent": os.path.abspath(a.baseline_tree)}
+    if a.tune and (a.glide or a.pitch_glide or a.models or a.enhancer):
+        raise SystemExit("rt_bank_time: --tune is a run of its own (no --glide, --pitch-glide, --models or --enhancer)")
+    three = ("parent", "plain", "glide") if a.glide else ("parent", "unused", "pitch") if a.pitch_glide else \
+        ("parent", "plain", "tune") if a.tune else None
+    trees = {"tune": ROOT, "bank": ROOT, "plain": ROOT, "glide": ROOT, "unused": ROOT, "pitch": ROOT, "solo": os.path.abspath(a.baseline_tree), "parent": os.path.abspath(a.baseline_tree)}
     legs = three if three else ("bank", "solo", "plain") if a.models == 1 else ("bank", "solo")
     repeats = []
     for rep in range(a.repeats):
@@ -259,8 +276,11 @@ def main():
     if a.pitch_glide:
         what = "ms per block period of one StreamBank.push_audio for all S streams: parent = the baseline tree's bank; unused = this " \
                "tree's bank with pitch_breakpoints=4 and no timeline; pitch = the same bank with a key timeline on every slot"
+    if a.tune:
+        what = "ms per block period of one StreamBank.push_audio for all S streams: parent = the baseline tree's bank; plain = this " \
+               "tree's bank without tune=True; tune = this tree's bank with tune=True and a scale on every slot"
     out = {**({} if a.active is None else {"active": a.active}), **({} if a.models is None else {"models": a.models}),
-           **({"glide": True} if a.glide else {}), **({"pitch_glide": True} if a.pitch_glide else {}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks,
+           **({"glide": True} if a.glide else {}), **({"pitch_glide": True} if a.pitch_glide else {}), **({"tune": True} if a.tune else {}), "enhancer": bool(a.enhancer), "device_sr": DEVICE_SR, "blocks": a.blocks,
            "warmup": a.warmup, "repeats": a.repeats, "what": what, "cases": cases, "rows": repeats}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
