@@ -67,6 +67,7 @@ struct ddsp_ctx {
     // with a system-scope store; the next entry point that takes ids, or ddsp_ctx_poll_error, reports and clears it
     int* dev_error_host;
     int* dev_error_dev;
+    int cu_count;   // compute units of `device`, asked for once (ddsp_units_retrieve's chunk rule); 0: not asked yet
 };
 
 static inline int ddsp_fail(ddsp_ctx* ctx, int code, const char* what, const char* detail) {
@@ -162,6 +163,7 @@ int ddsp_take_dev_error(ddsp_ctx* ctx);
 #define DDSP_DEV_ERR_PIECES 5    // ddsp_pieces_gather: a piece whose range leaves its file or exceeds the output widths
 #define DDSP_DEV_ERR_FORMANT 6   // ddsp_ctrl_warp: a formant factor that is not finite or not > 0
 #define DDSP_DEV_ERR_TUNE 7      // ddsp_f0_tune: a pitch-correction setting with a bad a4, strength or alpha
+#define DDSP_DEV_ERR_RETRIEVE 8  // ddsp_units_retrieve: a row that names an index with a ratio that is not finite or outside [0, 1]
 
 // profiler hooks (ctx.hip): bracket ONE kernel launch (or a tight group) on `st` when the family is enabled
 void ddsp_prof_begin(ddsp_ctx* ctx, hipStream_t st, int id);

@@ -258,6 +258,9 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
     if (code == DDSP_DEV_ERR_TUNE)
         return ddsp_fail(ctx, DDSP_ERR_ARG, "a pitch-correction setting whose a4 is not finite or not > 0, whose strength is outside "
                          "[0, 1] or whose alpha is outside (0, 1] in an earlier ddsp_f0_tune call", "the rows of that owner were left as they were");
+    if (code == DDSP_DEV_ERR_RETRIEVE)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "a retrieval ratio that is not finite or outside [0, 1] on a row that names an index in an "
+                         "earlier ddsp_units_retrieve call", "the units of those rows were left as they were");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

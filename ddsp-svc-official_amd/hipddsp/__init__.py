@@ -260,6 +260,10 @@ SIGNATURES = {
     "ddsp_bank_key_glide": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _f64, _vp]),
     "ddsp_ctrl_warp": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _vp, _int, _i64, _vp, _i64, _vp]),
     "ddsp_f0_tune": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ddsp_units_retrieve": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _int,
+                                   _vp, _i64, _vp, _vp]),
+    "ddsp_units_retrieve_workspace": (_int, [_vp, _i64, _i64, _int, _i64, _vp]),
+    "ddsp_units_index_norms": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
     "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
@@ -460,6 +464,7 @@ check_volume_n_samples = lambda n_samples, B, T, hop: check_n_samples(n_samples,
 
 
 MAX_MIX = 16                      # speakers in one mix (MixArgs of csrc/u2c.h; the K of a row-mix table)
+MAX_RETRIEVE_K = 16               # neighbours of one frame in `Context.units_retrieve_` (RT_KMAX of csrc/retrieve.hip)
 
 
 def check_mix_rows(ids, w, B, n_spk=None):
@@ -1725,6 +1730,69 @@ class Context:
             raise ValueError(f"f0_tune_: corr must be a contiguous (B = {B}, Fr = {Fr}) fp64 tensor on f0's device")
         self.call("ddsp_f0_tune", _ptr(f0), B, Fr, _ptr(n_frames), _ptr(owner), J, _ptr(mask), _ptr(param), _ptr(corr))
         return f0
+
+    def units_index_norms(self, vec):
+        """nrm (N,) fp32 = the squared norms of the index entries vec (N, C) fp32 (`ddsp_units_index_norms`): the derived row of
+        an index, formed once when it goes up."""
+        if not (isinstance(vec, torch.Tensor) and vec.dtype == torch.float32 and vec.dim() == 2 and vec.is_cuda and
+                vec.is_contiguous() and vec.shape[0] >= 1 and 4 <= vec.shape[1] <= 1024 and vec.shape[1] % 4 == 0):
+            raise ValueError("units_index_norms: vec must be a contiguous (N, C) fp32 device tensor, N >= 1, C a multiple of 4 in 4..1024")
+        nrm = torch.empty(vec.shape[0], dtype=torch.float32, device=vec.device)
+        self.call("ddsp_units_index_norms", _ptr(vec), int(vec.shape[0]), int(vec.shape[1]), _ptr(nrm))
+        return nrm
+
+    def units_retrieve_workspace(self, rows, Fr, k, N_max):
+        """Bytes of the workspace of a `units_retrieve_` call of this shape (`ddsp_units_retrieve_workspace`)."""
+        n = _i64()
+        self._check(self.lib.ddsp_units_retrieve_workspace(self.handle, int(rows), int(Fr), int(k), int(N_max), ctypes.byref(n)),
+                    "ddsp_units_retrieve_workspace")
+        return int(n.value)
+
+    def units_retrieve_(self, units, bank, index_of_row, ratio_of_row, k=8, n_frames=None, nn_id=None, nn_dist=None, owner=None):
+        """Unit retrieval (`ddsp_units_retrieve`; include/ddsp_amd.h states the rule): in place on units (rows, Fr, C) fp32, every
+        frame of a row that names an index is blended with the weighted mean of its k nearest entries of that index.  bank: an
+        `infer_offline.UnitIndexBank` on units' device (off, vec, nrm, `workspace(rows, Fr, k)`); index_of_row (rows,) int32 - -1
+        or anything outside [0, X): none, the row keeps its bits -, ratio_of_row (rows,) fp32 in [0, 1]; n_frames (rows,) int32:
+        the counts of a ragged batch; nn_id (rows, Fr, k) int32 and nn_dist (rows, Fr, k) fp32 receive the selected entry ids
+        (-1: unused) and their squared distances.  owner (rows,) int32: index_of_row and ratio_of_row are then J SETTINGS (a
+        bank's slots) and row b takes setting owner[b] - one outside [0, J) is a padding row, left as it is.  Shapes, dtypes and devices are refused here, before the launch; a bad ratio
+        leaves its row as it was and raises ValueError from `poll_error()` after a synchronise or from the next call that
+        takes the error word.  -> units."""
+        if not (isinstance(units, torch.Tensor) and units.dtype == torch.float32 and units.dim() == 3 and units.is_cuda and
+                units.is_contiguous() and units.shape[0] >= 1 and units.shape[1] >= 1):
+            raise ValueError("units_retrieve_: units must be a contiguous (rows, Fr, C) fp32 device tensor with rows, Fr >= 1")
+        rows, Fr, C = (int(n) for n in units.shape)
+        if not all(hasattr(bank, a) for a in ("off", "vec", "nrm", "n_max", "workspace")):
+            raise ValueError(f"units_retrieve_: bank must be an infer_offline.UnitIndexBank, got {type(bank).__name__}")
+        if bank.vec.device != units.device or int(bank.vec.shape[1]) != C:
+            raise ValueError(f"units_retrieve_: the bank holds {int(bank.vec.shape[1])} channels on {bank.vec.device}, units has "
+                             f"{C} on {units.device}")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_RETRIEVE_K:
+            raise ValueError(f"units_retrieve_: k must be an int in 1..{MAX_RETRIEVE_K}, got {k!r}")
+
+        def on_device(t, dtype, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and \
+                t.device == units.device
+
+        if owner is not None and not on_device(owner, torch.int32, (rows,)):
+            raise ValueError(f"units_retrieve_: owner must be a contiguous (rows = {rows},) int32 tensor on units' device")
+        J = int(index_of_row.numel()) if isinstance(index_of_row, torch.Tensor) and owner is not None else rows
+        if J < 1 or not on_device(index_of_row, torch.int32, (J,)):
+            raise ValueError(f"units_retrieve_: index_of_row must be a contiguous ({J},) int32 tensor on units' device (one per row, "
+                             f"or one per setting with owner=)")
+        if not on_device(ratio_of_row, torch.float32, (J,)):
+            raise ValueError(f"units_retrieve_: ratio_of_row must be a contiguous ({J},) fp32 tensor on units' device")
+        if n_frames is not None and not on_device(n_frames, torch.int32, (rows,)):
+            raise ValueError(f"units_retrieve_: n_frames must be a contiguous (rows = {rows},) int32 tensor on units' device")
+        if nn_id is not None and not on_device(nn_id, torch.int32, (rows, Fr, k)):
+            raise ValueError(f"units_retrieve_: nn_id must be a contiguous ({rows}, {Fr}, k = {k}) int32 tensor on units' device")
+        if nn_dist is not None and not on_device(nn_dist, torch.float32, (rows, Fr, k)):
+            raise ValueError(f"units_retrieve_: nn_dist must be a contiguous ({rows}, {Fr}, k = {k}) fp32 tensor on units' device")
+        ws = bank.workspace(rows, Fr, k)                  # (the bank's own, allocated at construction for its declared shape)
+        self.call("ddsp_units_retrieve", _ptr(units), rows, Fr, C, _ptr(n_frames), _ptr(owner), J, _ptr(index_of_row),
+                  _ptr(ratio_of_row), int(bank.off.numel()) - 1, _ptr(bank.off), _ptr(bank.vec), _ptr(bank.nrm), int(bank.vec.shape[0]), int(bank.n_max),
+                  k, _ptr(ws), int(ws.numel()) * ws.element_size(), _ptr(nn_id), _ptr(nn_dist))
+        return units
 
     def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
         """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row

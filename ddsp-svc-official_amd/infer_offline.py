@@ -22,6 +22,7 @@ the device (`ddsp_pcm16`), so the read-back is 2 bytes per sample.
 """
 import math
 import numbers
+import os
 
 import numpy as np
 import torch
@@ -557,7 +558,7 @@ class PitchTune:
 
 def job_tunes(jobs):
     """The pitch correction of every job of a `job_table` call, in job order: the `PitchTune` of a 6-tuple, else None."""
-    return [job[5] if len(job) == 6 else None for job in jobs]
+    return [job[5] if len(job) >= 6 else None for job in jobs]
 
 
 def tune_tables(tunes, sampling_rate, block_size):
@@ -567,6 +568,138 @@ def tune_tables(tunes, sampling_rate, block_size):
     settings = [(0, (440.0, 0.0, 1.0)) if t is None else t.setting(hop) for t in tunes]
     return (torch.tensor([m for m, _ in settings], dtype=torch.int32),
             torch.tensor([list(p) for _, p in settings], dtype=torch.float64).reshape(-1, 3))
+
+
+class UnitIndex:
+    """The stored units of one voice, for unit retrieval (include/ddsp_amd.h states the rule at `ddsp_units_retrieve`): vectors
+    (N, C) fp32 on the host, N >= 1, C a multiple of 4 and at most 1024, every value finite.  An index is the aligned units of a
+    speaker's training files (`from_units_dir`); k-means or IVF reduction of a large index is not here."""
+
+    def __init__(self, vectors):
+        v = torch.as_tensor(np.asarray(vectors) if not isinstance(vectors, torch.Tensor) else vectors)
+        if not (v.dim() == 2 and v.shape[0] >= 1 and 4 <= v.shape[1] <= 1024 and v.shape[1] % 4 == 0 and v.is_floating_point()):
+            raise ValueError(f"UnitIndex: vectors must be (N, C) floating point with N >= 1 and C a multiple of 4 in 4..1024, got "
+                             f"{tuple(v.shape)} {v.dtype}")
+        v = v.detach().to("cpu", torch.float32).contiguous()
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("UnitIndex: vectors must be finite")
+        self.vectors = v
+
+    def __len__(self):
+        return int(self.vectors.shape[0])
+
+    @property
+    def channels(self):
+        return int(self.vectors.shape[1])
+
+    @classmethod
+    def from_units_dir(cls, path, spk=None, max_entries=None):
+        """The index of the `units/` tree that `preprocess.py` wrote under `path` (<path>/units/<spk>/<name>.0.npy, each (n, C)):
+        every file of speaker folder `spk` (None: of all folders), sorted by relative name, frame after frame.  max_entries: a
+        deterministic evenly strided subset of that many rows (row floor(i * N / max_entries)) when there are more."""
+        root = os.path.join(path, "units")
+        if spk is not None:
+            root = os.path.join(root, str(spk))
+        names = sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs if f.endswith(".npy"))
+        if not names:
+            raise ValueError(f"UnitIndex.from_units_dir: no .npy under {root}")
+        files = [np.load(os.path.join(root, n)) for n in names]
+        rows = np.concatenate([f.astype(np.float32).reshape(-1, f.shape[-1]) for f in files])
+        if max_entries is not None:
+            if isinstance(max_entries, bool) or not isinstance(max_entries, numbers.Integral) or max_entries < 1:
+                raise ValueError(f"UnitIndex.from_units_dir: max_entries must be an int >= 1, got {max_entries!r}")
+            if len(rows) > max_entries:
+                rows = rows[(np.arange(int(max_entries), dtype=np.int64) * len(rows)) // int(max_entries)]
+        return cls(rows)
+
+    def save(self, path):
+        """A plain tensor file: torch.save of {'vectors': (N, C) fp32}."""
+        torch.save({"vectors": self.vectors}, path)
+
+    @classmethod
+    def load(cls, path):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not (isinstance(d, dict) and isinstance(d.get("vectors"), torch.Tensor)):
+            raise ValueError(f"UnitIndex.load: {path} holds no {{'vectors': tensor}}")
+        return cls(d["vectors"])
+
+
+class UnitIndexBank:
+    """X indices in one device arena, as `ddsp_units_retrieve` takes them: off (X + 1,) int64 row offsets, vec (N_total, C)
+    fp32, nrm (N_total,) fp32 (formed once here by `ddsp_units_index_norms`), `n_max` the largest N.  The workspace of the
+    search is the bank's: allocated here for calls of up to `rows` rows of `frames` frames at `k` neighbours - the size
+    `ddsp_units_retrieve_workspace` gives grows with the rows, so every call of fewer rows is served too -, and `workspace(rows,
+    Fr, k)` refuses a larger call (nothing is allocated at a launch; `reserve` grows it outside a capture).
+    ONE STREAM AT A TIME: the one workspace is written by every `units_retrieve_` call through this bank, so two consumers that
+    launch on different streams - two StreamBanks, or a StreamBank and an offline render - race on it; give each a
+    `UnitIndexBank` of its own (the vectors are the `UnitIndex`'s and are not copied on the host).
+    ValueError for an empty list, an entry that is no `UnitIndex`, or indices of different widths."""
+
+    def __init__(self, indices, device="cuda", rows=16, frames=256, k=8):
+        indices = list(indices) if isinstance(indices, (list, tuple)) else None
+        if not indices or not all(isinstance(i, UnitIndex) for i in indices):
+            raise ValueError("UnitIndexBank: indices must be a non-empty list of UnitIndex")
+        if len({i.channels for i in indices}) != 1:
+            raise ValueError(f"UnitIndexBank: the indices of a bank agree in width, got {[i.channels for i in indices]}")
+        for name, v in (("rows", rows), ("frames", frames)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+                raise ValueError(f"UnitIndexBank: {name} must be an int >= 1, got {v!r}")
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= hipddsp.MAX_RETRIEVE_K:
+            raise ValueError(f"UnitIndexBank: k must be an int in 1..{hipddsp.MAX_RETRIEVE_K}, got {k!r}")
+        self.sizes = [len(i) for i in indices]
+        self.n_max, self.channels = max(self.sizes), indices[0].channels
+        self.device = torch.device(device)
+        ctx = hipddsp.context_for(self.device)              # (refuses a device that is no HIP device)
+        self.off = torch.tensor(np.concatenate([[0], np.cumsum(self.sizes)]), dtype=torch.int64).to(self.device)
+        self.vec = torch.cat([i.vectors for i in indices]).to(self.device).contiguous()
+        self.device = self.vec.device                       # (with its number: 'cuda' is 'cuda:0' here)
+        self.nrm = ctx.units_index_norms(self.vec)
+        self._ctx = ctx
+        self._ws = None
+        self.reserve(rows, frames, k)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def reserve(self, rows, frames, k):
+        """Grow the workspace to serve calls of rows x frames queries at k neighbours (an allocation: never inside a capture)."""
+        need = max(self._ctx.units_retrieve_workspace(int(rows), int(frames), int(k), self.n_max), 8)
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device)
+
+    def workspace(self, rows, Fr, k):
+        need = self._ctx.units_retrieve_workspace(rows, Fr, k, self.n_max)
+        if self._ws.numel() * 4 < need:
+            raise ValueError(f"UnitIndexBank: a call of {rows} x {Fr} frames at k = {k} needs a workspace of {need} bytes, this bank "
+                             f"holds {self._ws.numel() * 4}: `reserve(rows, frames, k)` outside any capture")
+        return self._ws
+
+
+def job_indices(jobs):
+    """The retrieval setting of every job of a `job_table` call, in job order: (index_number, ratio) of a 7-tuple, else None."""
+    return [job[6] if len(job) == 7 else None for job in jobs]
+
+
+def index_tables(settings):
+    """`job_indices`' list -> CPU tensors (index_of_job (J,) int32, -1 for a job without one; ratio_of_job (J,) fp32, 0 there)."""
+    return (torch.tensor([-1 if s is None else int(s[0]) for s in settings], dtype=torch.int32),
+            torch.tensor([0.0 if s is None else float(s[1]) for s in settings], dtype=torch.float32))
+
+
+def check_job_index(who, setting, n_indices=None):
+    """A job's seventh entry: None or (index_number, ratio) with an int >= 0 (and < n_indices where the bank is known) and a
+    finite ratio in [0, 1]; ValueError otherwise."""
+    if setting is None:
+        return
+    ok = isinstance(setting, (tuple, list)) and len(setting) == 2
+    if ok:
+        i, r = setting
+        ok = isinstance(i, numbers.Integral) and not isinstance(i, bool) and i >= 0 and (n_indices is None or i < n_indices) and \
+            isinstance(r, numbers.Real) and not isinstance(r, bool) and math.isfinite(r) and 0 <= r <= 1
+    if not ok:
+        bank = "" if n_indices is None else f" of the {n_indices} indices of the call"
+        raise ValueError(f"{who}: index must be None or (index_number, ratio) with index_number >= 0{bank} and ratio in [0, 1], "
+                         f"got {setting!r}")
 
 
 def _check_formant(j, formant, model):
@@ -585,7 +718,7 @@ def _check_formant(j, formant, model):
             raise ValueError(f"job_table: job {j}: {e}") from None
 
 
-def job_table(pieces, n_files, jobs, models):
+def job_table(pieces, n_files, jobs, models, n_indices=None):
     """The tables of a conversion of `jobs` over analysed files, made and checked on the host (nothing is launched).  pieces:
     `piece_table` rows of the `n_files` files; jobs: a sequence of (file, model_index, spk, key) - spk a 1-based speaker id, a
     mix dict {id: weight} or a `SpeakerTimeline` (a voice that changes over the file; it stands in `speakers` as it is, its ids
@@ -604,7 +737,11 @@ def job_table(pieces, n_files, jobs, models):
     checked here and stands in no table of the dict: `job_formants(jobs)` lists it, `formant_tables` makes its breakpoints.
     A sixth entry is its PITCH CORRECTION, a `PitchTune` or None (the formant may then be None too): `job_tunes(jobs)` lists
     it, `tune_tables` makes its settings.
-    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4-, 5- or 6-tuple, a
+    A seventh entry is its UNIT RETRIEVAL, (index_number, ratio) or None (formant and tune may then be None too): the index of a
+    `UnitIndexBank` and the blend ratio in [0, 1]; `job_indices(jobs)` lists it, `index_tables` makes its rows.  n_indices: the
+    size of the call's bank where it is known (an index number at or past it is refused).
+    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4- to 7-tuple, an
+    index entry that is no (int >= 0, ratio in [0, 1]), a
     file or model index out of range, a speaker id outside [1, n_spk] of the JOB's model, a mix with no or too many speakers, a
     formant shift that is no finite number within +-24 semitones and no `FormantTimeline` that fits the model's frame rate, or
     a tune that is no `PitchTune`."""
@@ -622,10 +759,13 @@ def job_table(pieces, n_files, jobs, models):
     table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": [],
              "keys": []}
     for j, job in enumerate(jobs):
-        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5, 6) and (len(job) < 6 or job[5] is None or
-                                                                             isinstance(job[5], PitchTune))):
+        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5, 6, 7) and (len(job) < 6 or job[5] is None or
+                                                                                isinstance(job[5], PitchTune))):
             raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key), (file, model_index, spk, key, formant) or "
-                             f"(file, model_index, spk, key, formant, tune) with tune a PitchTune or None, got {job!r}")
+                             f"(file, model_index, spk, key, formant, tune) with tune a PitchTune or None, or those six with "
+                             f"(index_number, ratio) or None behind them, got {job!r}")
+        if len(job) == 7:
+            check_job_index(f"job_table: job {j}", job[6], n_indices)
         file, m, spk, key = job[:4]
         if not (isinstance(file, numbers.Integral) and 0 <= file < int(n_files)):
             raise ValueError(f"job_table: job {j}: file {file!r} is outside the {int(n_files)} files of the call")
@@ -961,12 +1101,18 @@ def _render_files(model, args, files, speaker, seed_of_group, noise, *, threshol
     given = None if jobs is None else rows
     formant = None if jobs is None else jobs[1].get("formant")       # (models with a formant among their jobs, tables, f0 of ones)
     tune = None if jobs is None else jobs[1].get("tune")             # (the settings of all jobs, when one of them has a tune)
+    retrieve = None if jobs is None else jobs[1].get("retrieve")     # (bank, index and ratio of all jobs, k: when one names an index)
     table, cols, bounds = _upload_pieces(ctx, files, groups, given)
     speaker_of_rows = speaker(cols[0], [i for group in groups for i in group])
     out = [None] * len(rows)
     for g, (group, (a, b)) in enumerate(zip(groups, bounds)):
         counts = [rows[i][2] for i in group]
         u, _ = stack_rows([units[unit_of[i]][0] for i in group])
+        if retrieve is not None:                                     # behind the encoder: the group's stacked units, in place
+            bank, index_of_job, ratio_of_job, k = retrieve
+            job_of_row = cols[5, a:b].long()
+            bank.reserve(u.shape[0], u.shape[1], k)
+            ctx.units_retrieve_(u, bank, index_of_job[job_of_row], ratio_of_job[job_of_row], k=k, n_frames=cols[2, a:b].contiguous())
         _, f, v = ctx.pieces_gather(table[a:b], files["n_samples_dev"], files["n_frames_dev"], f0=files["f0"],
                                     volume=files["volume"], N_max=max(counts), **key)
         if tune is not None:                                         # behind the key: the output lands in the scale
@@ -1035,7 +1181,8 @@ def _models_of(who, model, models):
 
 @torch.no_grad()
 def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0, noise_seed=None,
-                       batch_frames=None, noise=None, enhancer_batch_samples=None, key_tables_always=False):
+                       batch_frames=None, noise=None, enhancer_batch_samples=None, key_tables_always=False, indices=None,
+                       retrieve_k=8):
     """`render_many_device` for JOBS over the files of ONE `analyse_many` (analysed with keys=0: the key is the job's) -> (fp64
     device tensor holding every job, [(base, total)] per job in job order, sample rate).  jobs: a sequence of (file,
     model_index, spk, key) into `files` and `models` (`job_table` states and checks them: ValueError before any launch).  Job j
@@ -1063,12 +1210,30 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     the render groups and the enhancer's - is followed by one `ddsp_f0_tune` launch on the group's rows, behind the key, with
     the rows' jobs as their owners: the rows of a job without a tune keep their bits, and the enhancer sees the corrected f0.
     The correction restarts at every slice.  Without a tune among the jobs nothing is launched: the call above, bit for bit.
+    A job may be a 7-tuple (file, model_index, spk, key, formant, tune, index): UNIT RETRIEVAL, (index_number, ratio) into
+    `indices` (a `UnitIndexBank` on the files' device) or None.  With an index among the jobs the rows' settings go up once
+    (`index_tables`) and every render group's stacked units pass through one `Context.units_retrieve_` (k = `retrieve_k`) with
+    the group's frame counts, right where the encoder's units enter the synthesiser: the rows of a job without an index keep
+    their bits.  Without an index among the jobs nothing is launched: the call above, bit for bit.  ValueError for an index
+    among the jobs without `indices`, an index number outside the bank, or a bank whose width is not the units'.
     noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
     `models` order - draws with (noise_seed + g * 2**32) mod 2**64."""
     models = _models_of("render_jobs_device", None, models)
     dev, pieces, n_files = files["device"], files["pieces"], len(files["n_frames"])
-    table = job_table(pieces, n_files, jobs, models)
+    if indices is not None and not isinstance(indices, UnitIndexBank):
+        raise ValueError(f"render_jobs_device: indices must be a UnitIndexBank, got {type(indices).__name__}")
+    table = job_table(pieces, n_files, jobs, models, None if indices is None else len(indices))
     J = len(table["model_of_job"])
+    settings = job_indices(jobs)
+    if any(s is not None for s in settings):
+        if indices is None:
+            raise ValueError("render_jobs_device: a job names an index, but the call has no indices=")
+        if files["units"] and (indices.device != files["units"][0].device or indices.channels != int(files["units"][0].shape[-1])):
+            raise ValueError(f"render_jobs_device: the bank holds {indices.channels} channels on {indices.device}, the files' units "
+                             f"are on {dev}")
+        if isinstance(retrieve_k, bool) or not isinstance(retrieve_k, int) or not 1 <= retrieve_k <= hipddsp.MAX_RETRIEVE_K:
+            raise ValueError(f"render_jobs_device: retrieve_k must be an int in 1..{hipddsp.MAX_RETRIEVE_K}, got {retrieve_k!r}")
+        table["retrieve"] = (indices, *(t.to(dev) for t in index_tables(settings)), retrieve_k)
     if J and noise is not None and [len(x) for x in noise] != [len(s) for s in table["starts_per_job"]]:
         raise ValueError("render_jobs_device: noise must hold one list per job with one draw per slice of its file")
     if J and (key_tables_always or any(isinstance(k, KeyTimeline) for k in table["keys"])):
@@ -1138,7 +1303,7 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
 def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extractor, spk_ids=None, slices=None, keys=0,
                         batch_frames=None, spk_mix_rows=None, threshold_db=-60, enhancer=None, enhancer_adaptive_key=0,
                         noise_seed=None, enhancer_batch_samples=None, units_batch_samples=None, jobs=None, models=None,
-                        noise=None):
+                        noise=None, indices=None, retrieve_k=8):
     """`analyse_many` then `render_many_device`: a list of files from raw audio to one fp64 device tensor -> (out, [(base,
     total)] per file, sample rate).  Files are batched within ONE call's sample rate and enhancer key.
     jobs: None - one model (`model`), one speaker (`spk_ids`, required then) and one key per file, as above - or a sequence of
@@ -1147,8 +1312,11 @@ def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extr
     `model` is None or models[0]).  With `jobs`, the speaker and the key are the job's: `spk_ids`, `spk_mix_rows` and `keys`
     must be left at their defaults (ValueError), and all tables are checked before anything is analysed (`job_table`).  An
     empty list of jobs gives an empty tensor and no spans, and analyses nothing.
-    noise: `render_many_device`'s (per file) or `render_jobs_device`'s (per job) injected draws."""
+    noise: `render_many_device`'s (per file) or `render_jobs_device`'s (per job) injected draws.
+    indices, retrieve_k: `render_jobs_device`'s bank of unit indices for jobs with a seventh entry; they go with jobs=."""
     if jobs is None:
+        if indices is not None:
+            raise ValueError("convert_many_device: indices= goes with jobs= (a job's seventh entry names its index)")
         if models is not None:
             raise ValueError("convert_many_device: models= goes with jobs=; without jobs the one model is the positional one")
         if spk_ids is None and spk_mix_rows is None:
@@ -1162,14 +1330,19 @@ def convert_many_device(model, args, audios, sample_rate, units_encoder, f0_extr
         raise ValueError("convert_many_device: with jobs= the speaker and the key are each job's: leave spk_ids, spk_mix_rows and "
                          "keys at their defaults")
     models, jobs = _models_of("convert_many_device", model, models), list(jobs)
-    job_table([], len(audios), jobs, models)                # every refusal of the tables, before anything is analysed
+    if indices is not None and not isinstance(indices, UnitIndexBank):
+        raise ValueError(f"convert_many_device: indices must be a UnitIndexBank, got {type(indices).__name__}")
+    # every refusal of the tables, before anything is analysed
+    job_table([], len(audios), jobs, models, None if indices is None else len(indices))
+    if indices is None and any(s is not None for s in job_indices(jobs)):
+        raise ValueError("convert_many_device: a job names an index, but the call has no indices=")
     check_units_width("convert_many_device", units_encoder, *models)
     if not jobs:
         return torch.zeros(0, dtype=torch.float64, device=next(models[0].parameters()).device), [], int(args.data.sampling_rate)
     files = analyse_many(args, audios, sample_rate, slices, units_encoder, f0_extractor, 0, units_batch_samples)
     return render_jobs_device(models, args, files, jobs, threshold_db=threshold_db, enhancer=enhancer,
                               enhancer_adaptive_key=enhancer_adaptive_key, noise_seed=noise_seed, batch_frames=batch_frames,
-                              noise=noise, enhancer_batch_samples=enhancer_batch_samples)
+                              noise=noise, enhancer_batch_samples=enhancer_batch_samples, indices=indices, retrieve_k=retrieve_k)
 
 
 @torch.no_grad()

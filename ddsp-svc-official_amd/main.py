@@ -23,6 +23,9 @@ name none.
 `--tune_scale "A minor"` (long options only; with `--tune_strength`, `--tune_retune_ms` and `--tune_a4`, defaults 1, 50 and 440)
 pulls the sung f0 toward the notes of that scale (`infer_offline.PitchTune`, behind the key shift); it runs through the jobs
 path like `--formant_shift_key`, and with `--jobs` it is the tune of the entries that name none.
+`--index <file>` (an `infer_offline.UnitIndex.save` file; with `--index_ratio R`, default 0.5) blends every frame's units with
+their nearest stored units of that voice (`ddsp_units_retrieve`); it runs through the jobs path too, and with `--jobs` it is the
+index of the entries that name none - an entry names its own with `index: <file>` and `index_ratio: <0..1>`.
 
 The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
   * the key shift is applied once (the reference applies it twice, SURVEY 0.3);
@@ -72,6 +75,8 @@ def parse_args(args=None, namespace=None):
     parser.add_argument("--tune_strength", type=str, default=argparse.SUPPRESS, help="share of the correction applied, 0..1 | default: 1")
     parser.add_argument("--tune_retune_ms", type=str, default=argparse.SUPPRESS, help="retune time in milliseconds, 0: at once | default: 50")
     parser.add_argument("--tune_a4", type=str, default=argparse.SUPPRESS, help="the Hz of A4 | default: 440")
+    parser.add_argument("--index", type=str, default=argparse.SUPPRESS, help="unit retrieval: a UnitIndex file of the target voice")
+    parser.add_argument("--index_ratio", type=str, default=argparse.SUPPRESS, help="share of the retrieved units, 0..1 | default: 0.5")
     parser.add_argument("--jobs", type=str, default=argparse.SUPPRESS, help="YAML list of {model, id | mix, key, suffix}: every entry is applied "
                         "to every .wav of the input folder")
     return parser.parse_args(args=args, namespace=namespace)
@@ -134,7 +139,7 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
             raise ValueError("--jobs goes with a folder as -i (and a folder as -o)")
         return _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                          enhancer_batch_samples, units_batch_samples)
-    if float(getattr(cmd, "formant_shift_key", 0)) != 0 or _cmd_tune(cmd) is not None:
+    if float(getattr(cmd, "formant_shift_key", 0)) != 0 or _cmd_tune(cmd) is not None or getattr(cmd, "index", None) is not None:
         return _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                             enhancer_batch_samples, units_batch_samples)
     if os.path.isdir(cmd.input):
@@ -178,7 +183,7 @@ def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhan
 
 def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
                  units_batch_samples):
-    """`run` with `--formant_shift_key S` or `--tune_scale` and no `--jobs`: the file, or every `.wav` of the folder, as one job
+    """`run` with `--formant_shift_key S`, `--tune_scale` or `--index` and no `--jobs`: the file, or every `.wav` of the folder, as one job
     each - `-id` or `-mix`, `-k`, the shift and the tune - through ONE `infer_offline.convert_many_device(jobs=...)`; outputs as `run` names them."""
     from infer_offline import convert_many_device
     folder = os.path.isdir(cmd.input)
@@ -186,10 +191,13 @@ def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enha
     audios = [load(os.path.join(cmd.input, n) if folder else cmd.input) for n in names]
     mix = literal_eval(cmd.spk_mix_dict)
     shift, tune = float(getattr(cmd, "formant_shift_key", 0)), _cmd_tune(cmd)
-    jobs = [(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), shift if shift != 0 else None) +
-            (() if tune is None else (tune,)) for k in range(len(names))]
+    files = _IndexFiles(device)
+    index = files.setting("--index", getattr(cmd, "index", None), getattr(cmd, "index_ratio", 0.5))
+    jobs = [_job_tuple(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), shift if shift != 0 else None, tune, index,
+                       at_least=5) for k in range(len(names))]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=[model], batch_frames=batch_frames,
+        indices=files.bank(),
         threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
         enhancer_adaptive_key=float(cmd.enhancer_adaptive_key), enhancer_batch_samples=enhancer_batch_samples,
         units_batch_samples=units_batch_samples)
@@ -215,22 +223,27 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
         raise ValueError(f"--jobs: {cmd.jobs} must hold a non-empty list of {{model, id | mix, key, suffix}} entries")
     paths, models, voices = [os.path.abspath(cmd.model_path)], [model], []
     shift = float(getattr(cmd, "formant_shift_key", 0))          # the shift of the entries that name none
+    files = _IndexFiles(device)
     for n, e in enumerate(entries):
         spk, key = _job_entry(n, e)
         path = os.path.abspath(e.get("model", cmd.model_path))
         if path not in paths:
             paths.append(path)
             models.append(load_model(path, device=device)[0])
-        voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift), _job_tune(n, e, _cmd_tune(cmd))))
+        index = files.setting(f"--jobs: entry {n}", e.get("index", getattr(cmd, "index", None)),
+                              e.get("index_ratio", getattr(cmd, "index_ratio", 0.5)))
+        voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift), _job_tune(n, e, _cmd_tune(cmd)),
+                       index))
     if len({v[3] for v in voices}) != len(voices):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
     audios = [load(os.path.join(cmd.input, n)) for n in names]
-    jobs = [(k, m, spk, key) + ((formant, tune) if tune is not None else () if formant is None else (formant,))
-            for k in range(len(names)) for m, spk, key, _, formant, tune in voices]
+    jobs = [_job_tuple(k, m, spk, key, formant, tune, index)
+            for k in range(len(names)) for m, spk, key, _, formant, tune, index in voices]
     out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{v[3]}.wav") for name in names for v in voices]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=models, batch_frames=batch_frames,
+        indices=files.bank(),
         threshold_db=float(cmd.threhold), enhancer=enhancer if cmd.enhance == "true" else None,
         enhancer_adaptive_key=float(cmd.enhancer_adaptive_key), enhancer_batch_samples=enhancer_batch_samples,
         units_batch_samples=units_batch_samples)
@@ -239,11 +252,45 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
     return result, sr_o
 
 
+def _job_tuple(file, model, spk, key, formant=None, tune=None, index=None, at_least=4):
+    """A job as `infer_offline.job_table` takes it, as short as what it carries allows: four entries, a fifth with a formant,
+    a sixth with a tune, a seventh with an index (the entries in front of the last one given may be None); `at_least` entries."""
+    job = (file, model, spk, key, formant, tune, index)
+    n = 7 if index is not None else 6 if tune is not None else 5 if formant is not None else 4
+    return job[:max(n, at_least)]
+
+
+class _IndexFiles:
+    """The `UnitIndex` files a run names, each loaded once and numbered in the order it is first named; `bank()` is their
+    `UnitIndexBank` on the device, None when no file was named."""
+
+    def __init__(self, device):
+        self.device, self.paths, self.indices = device, [], []
+
+    def setting(self, where, path, ratio):
+        """-> a job's seventh entry (index_number, ratio), None without a file."""
+        if path is None:
+            return None
+        from infer_offline import UnitIndex, check_job_index
+        path = os.path.abspath(str(path))
+        if path not in self.paths:
+            self.indices.append(UnitIndex.load(path))
+            self.paths.append(path)
+        setting = (self.paths.index(path), float(ratio))
+        check_job_index(where, setting)
+        return setting
+
+    def bank(self):
+        from infer_offline import UnitIndexBank
+        return UnitIndexBank(self.indices, device=self.device) if self.indices else None
+
+
 def _job_entry(n, e):
     """Entry n of the `--jobs` list -> (spk, key) as `infer_offline.job_table` takes them: the speaker from `id`, `mix` or
     `timeline` (at most one of them; default id 1), the key from `key` or `key_timeline` (not both; default 0).  ValueError for an
     unknown field, two speakers, two keys or a missing suffix."""
-    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "formant", "formant_timeline", "tune", "suffix"}
+    unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "formant", "formant_timeline", "tune", "index",
+                        "index_ratio", "suffix"}
     if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or ("key" in e and "key_timeline" in e) or \
             not str(e.get("suffix", "")):
         raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key or key_timeline and a non-empty suffix, "

@@ -467,6 +467,14 @@ class _Rows:
         return None if b.tune_mask is None else (b.tune_mask, b.tune_param, self.rows)
 
     @property
+    def retrieve_term(self):
+        """The unit-retrieval term of this instance's chain (`graphed.block_chain`'s `retrieve`): None on a bank without
+        `indices`; the bank of indices and the slots' rows, with the width's row table as the owner of every row on a compact
+        instance (a padding row has none)."""
+        b = self.bank
+        return None if b.indices is None else (b.indices, b.index_of_slot, b.ratio_of_slot, b.retrieve_k, self.rows)
+
+    @property
     def pitch_term(self):
         """The pitch term of this instance's chain: a factor per row, or per frame on a bank with `pitch_breakpoints`."""
         return self.pitch if self.pitch_frames is None else self.pitch_frames
@@ -625,6 +633,20 @@ class StreamBank:
     is at least a second long, only its tail is spliced and the cross-fade hides the rest.  The bank carries no state for it,
     so a paused slot has none to keep.  Refused: `set_tune` on a bank without it.
 
+    Unit retrieval per slot (`indices=UnitIndexBank`, `retrieve_k`; the default None allocates, captures and launches nothing
+    of this, and the bank is the bank above, bit for bit).  Every slot then has a row of `index_of_slot` (S,) int32, -1 at first,
+    and `ratio_of_slot` (S,) fp32; `set_index(slot, i | None, ratio=0.5)` writes them and `reset(slot)` switches the slot off:
+    device rows only, `graph_builds` stays what it was.  Every `push_audio` chain of such a bank runs `ddsp_units_retrieve` (two
+    launches; include/ddsp_amd.h states the rule) right behind `units_encoder.encode` - inside the captured block, and on the
+    eager path alike -, at a compact width with the width's row table as the owner of every row.  The kernels only read the
+    slots' rows, so a paused slot keeps everything.  It sits in the shared analysis, in front of the per-model row gather, so it
+    works with `models=` as well as with `active_widths` and the enhancer.  The bank's workspace is reserved here, before any
+    capture, for S rows of the window's frames: `ddsp_units_retrieve_workspace` grows with the rows, so that size serves every
+    narrower width of the ladder.  The `UnitIndexBank`'s one workspace serves one stream at a time: banks that push on different
+    streams take a `UnitIndexBank` each.  Refused: `set_index` on a bank without indices; an index number outside the bank;
+    a bank of indices on another device or of another unit width than the encoder's.  `push_block` takes the caller's units
+    as they are.
+
     Not in the bank: a formant shift on a bank with `models=`, or one that moves along a timeline; streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
     grows after construction; a weight set per row inside the control network's kernels; an enhancer per model; a glide on a
     bank with `models=`."""
@@ -633,7 +655,7 @@ class StreamBank:
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
                  active_widths=None, models=None, model_widths=None, glide_breakpoints=None, pitch_breakpoints=None,
-                 formant=False, tune=False):
+                 formant=False, tune=False, indices=None, retrieve_k=8):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
@@ -651,6 +673,15 @@ class StreamBank:
             raise ValueError(f"StreamBank: formant must be True or False, got {formant!r}")
         if not isinstance(tune, bool):
             raise ValueError(f"StreamBank: tune must be True or False, got {tune!r}")
+        if indices is not None:
+            from infer_offline import UnitIndexBank
+            if not isinstance(indices, UnitIndexBank):
+                raise ValueError(f"StreamBank: indices must be an infer_offline.UnitIndexBank or None, got {type(indices).__name__}")
+            if isinstance(retrieve_k, bool) or not isinstance(retrieve_k, int) or not 1 <= retrieve_k <= hipddsp.MAX_RETRIEVE_K:
+                raise ValueError(f"StreamBank: retrieve_k must be an int in 1..{hipddsp.MAX_RETRIEVE_K}, got {retrieve_k!r}")
+            n_unit = _model_field(models[0] if model is None and isinstance(models, (tuple, list)) and models else model, "n_unit")
+            if indices.channels != n_unit:
+                raise ValueError(f"StreamBank: the indices hold units of {indices.channels} channels, the model takes {n_unit}")
         if formant and models is not None:
             raise ValueError("StreamBank: formant=True with models= is not supported (the per-model row mover indexes the call's "
                              "rows, the formant row is indexed by slot)")
@@ -726,6 +757,14 @@ class StreamBank:
         if tune:
             self.tune_mask = torch.zeros(self.S, dtype=torch.int32, device=dev)
             self.tune_param = torch.tensor([[440.0, 0.0, 1.0]] * self.S, dtype=torch.float64).to(dev)
+        self.indices, self.retrieve_k = indices, int(retrieve_k)     # the voices' stored units (`set_index`), every slot off at first
+        self.index_of_slot = self.ratio_of_slot = None
+        if indices is not None:
+            if indices.device != torch.device(dev) and indices.device != torch.zeros(0, device=dev).device:
+                raise ValueError(f"StreamBank: the indices live on {indices.device}, the bank on {dev}")
+            self.index_of_slot = torch.full((self.S,), -1, dtype=torch.int32, device=dev)
+            self.ratio_of_slot = torch.zeros(self.S, dtype=torch.float32, device=dev)
+            indices.reserve(self.S, self.frames, self.retrieve_k)    # (an allocation: in front of every capture)
         self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
         self.last_mix_w = None           # (A, Fr, max_mix): the block's per-frame weights on a bank with `glide_breakpoints`
@@ -770,7 +809,8 @@ class StreamBank:
                 self.silence_front, rows.pitch_term, self.threshold_db, mix_rows=rows.mix, f0_dither=self.f0_dither, push=rows.push,
                 keep=[c for c in (self.glide_clock, self.key_clock) if c is not None],   # (the capture's runs advance the clocks)
                 **({} if self.formant is None else {"formant": rows.formant_term}),
-                **({} if self.tune_mask is None else {"tune": rows.tune_term}))
+                **({} if self.tune_mask is None else {"tune": rows.tune_term}),
+                **({} if self.indices is None else {"retrieve": rows.retrieve_term}))
         elif shared:
             rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix,
                                               **({} if self.formant is None else {"formant": rows.formant_term}))
@@ -923,6 +963,20 @@ class StreamBank:
         self.tune_mask[slot:slot + 1].fill_(mask)
         self.tune_param[slot:slot + 1].copy_(torch.tensor([param], dtype=torch.float64))
 
+    def set_index(self, slot, index, ratio=0.5):
+        """Slot `slot`'s units are blended with their nearest stored units of index number `index` of the bank's `indices`
+        from the next block on, at `ratio` in [0, 1]; None switches it off: one write to the slot's rows of `index_of_slot` and
+        `ratio_of_slot`, no capture.  ValueError on a bank built without `indices=`, for an index number outside the bank or a
+        ratio that is not a finite number in [0, 1]."""
+        if self.indices is None:
+            raise ValueError("StreamBank.set_index: this bank was built without indices=")
+        from infer_offline import check_job_index
+        if index is not None:
+            check_job_index("StreamBank.set_index", (index, ratio), len(self.indices))
+        slot = self._slot(slot)
+        self.index_of_slot[slot:slot + 1].fill_(-1 if index is None else int(index))
+        self.ratio_of_slot[slot:slot + 1].fill_(0.0 if index is None else float(ratio))
+
     def set_pitch_timeline(self, slot, timeline, at=0.0):
         """Slot `slot`'s key follows `timeline` (an `infer_offline.KeyTimeline`) from the next block on, in STREAM time, as
         `set_timeline` has it for the voice: time 0 is the first sample pushed after this call, or `at` seconds into the timeline
@@ -969,7 +1023,8 @@ class StreamBank:
         """A new caller takes slot `slot`: its window and its SOLA buffer are zeroed (model, speaker and pitch stay as set).  On
         a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning;
         on one with `pitch_breakpoints` the key clock and the key timeline likewise.  On a bank with `formant` the slot's formant
-        factor goes back to 1, on one with `tune` the slot's pitch correction is switched off."""
+        factor goes back to 1, on one with `tune` the slot's pitch correction is switched off, on one with `indices` its
+        unit retrieval."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
@@ -981,6 +1036,9 @@ class StreamBank:
             self.formant[slot:slot + 1].fill_(1.0)
         if self.tune_mask is not None:
             self.tune_mask[slot:slot + 1].zero_()
+        if self.indices is not None:
+            self.index_of_slot[slot:slot + 1].fill_(-1)
+            self.ratio_of_slot[slot:slot + 1].zero_()
 
     def _check_blocks(self, blocks, A, rows="S"):
         if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
@@ -1059,7 +1117,8 @@ class StreamBank:
                 self.f0_extractor, rows.windows, blocks, self.samplerate, self.hop_size, self.silence_front, rows.pitch_term,
                 self.threshold_db, self.hop,
                 {"spk_id": None, "spk_mix_rows": rows.mix, **({} if self.formant is None else {"formant": rows.formant_term})},
-                noise, self.f0_dither, push=rows.push, **({} if self.tune_mask is None else {"tune": rows.tune_term}))
+                noise, self.f0_dither, push=rows.push, **({} if self.tune_mask is None else {"tune": rows.tune_term}),
+                **({} if self.indices is None else {"retrieve": rows.retrieve_term}))
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)

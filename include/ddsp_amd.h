@@ -533,6 +533,53 @@ int ddsp_ctrl_warp(ddsp_ctx* ctx, void* stream, float* ctrl, int64_t rows, int64
 int ddsp_f0_tune(ddsp_ctx* ctx, void* stream, float* f0, int64_t B, int64_t Fr, const int32_t* n_frames, const int32_t* owner,
                  int64_t J, const int32_t* mask, const double* param, double* corr);
 
+/* UNIT RETRIEVAL: every frame's unit vector, units (rows, Fr, C) fp32 IN PLACE, is blended with a weighted mean of its nearest
+ * stored units of a voice's index; it runs between the units encoder and the synthesiser.  A definition of this project (the
+ * reference has no such control; RVC calls the blend weight the "index rate").  Every pointer is a DEVICE pointer, read when
+ * the kernels run.
+ * AN INDEX is vec (N, C) fp32, row-major, N >= 1, C a multiple of 4 and at most 1024, with the derived row
+ * nrm[i] = sum_c vec[i][c]^2, formed once by ddsp_units_index_norms in fp32 in a fixed order.  AN INDEX BANK is X indices in one
+ * arena: off (X + 1) int64 row offsets, vec (N_total, C), nrm (N_total); N_max is the largest N of the bank (a host number: it
+ * sizes the grid and the workspace and forms no address).
+ * THE SETTING of a row (a slice offline, a slot's window live), J of them: index_of_row (J) int32 - -1 or anything outside
+ * [0, X): none - and ratio_of_row (J) fp32.  Row b takes setting owner[b] (int32; outside [0, J): a padding row, it has none and
+ * is not judged), or setting b for owner == NULL (J >= rows then).  One k per call, 1 <= k <= 16; k_eff = min(k, N_x).  n_frames (rows) int32 or NULL: the rows'
+ * counts, held in [1, Fr].
+ * THE RULE, for a frame x of a row with index x_i and ratio r:
+ *     t_i = nrm[i] - 2 * <x, vec[i]>                  the score: it ranks as the squared distance does, |x|^2 being common
+ *     the k_eff entries with the smallest t are selected, equal t goes to the smaller entry id; they are ordered by (t, id)
+ *     s_j = sum_c (x[c] - vec[j][c])^2                recomputed directly in fp32 in the blend pass, not derived from the score
+ *     w_j = 1 / max(s_j, 1e-12)^2, normalised to sum 1   (RVC's inverse square of the squared distance; the floor makes an
+ *                                                      exact hit a large finite weight and not a NaN)
+ *     y = sum_j w_j vec[j],  out = x + r * (y - x)     in fp32, nothing contracted
+ * UNTOUCHED, by selection and not by arithmetic, so their bits stay: rows with no index; rows with r == 0; frames at or past a
+ * row's count.  A row's setting is judged only if the row names an index: one with r not finite or outside [0, 1] keeps its
+ * bits and raises the device error word (DDSP_ERR_ARG from the next call that takes it, or ddsp_ctx_poll_error).  The index id,
+ * the two offsets behind it (0 <= off[x] < off[x+1] <= N_total, else the row has no index) and every entry id are tested before
+ * they form an address.
+ * nn_id (rows, Fr, k) int32 or NULL: the selected entry ids, local to the row's index, -1 in unused places (all k of an
+ * untouched frame); nn_dist (rows, Fr, k) fp32 or NULL: the recomputed s_j, 0 in unused places.  Every element is written.
+ * TWO LAUNCHES.  Search: a workgroup takes a tile of 32 query frames of one row and one chunk of the row's index, streams the
+ * chunk through the LDS, forms the scores with fp32 MFMA and keeps a running top-k by (t, id) per query; it writes k candidates
+ * per (query, chunk) to `workspace`.  The chunk count follows from N_max and the device's CU count.  Merge and blend: one wave
+ * per query merges the chunks' candidates by (t, id), gathers the k vectors with 16-byte loads, and stores out, nn_id, nn_dist.
+ * workspace: the caller's, at least ddsp_units_retrieve_workspace(R, Fr, k, N_max) bytes for some R >= rows, 16-byte aligned.
+ * DDSP_ERR_ARG, and nothing launched, for a null units, index_of_row, ratio_of_row, off, vec, nrm or workspace, rows, Fr or X < 1,
+ * rows * Fr or N_total >= 2^31, N_max outside [1, N_total], k outside [1, 16], C no multiple of 4 in 4..1024, or a workspace
+ * that is too small.  Does not synchronise, allocate or read back; graph-capturable. */
+int ddsp_units_retrieve(ddsp_ctx* ctx, void* stream, float* units, int64_t rows, int64_t Fr, int64_t C, const int32_t* n_frames,
+                        const int32_t* owner, int64_t J, const int32_t* index_of_row, const float* ratio_of_row, int64_t X, const int64_t* off, const float* vec,
+                        const float* nrm, int64_t N_total, int64_t N_max, int k, void* workspace, int64_t workspace_bytes,
+                        int32_t* nn_id, float* nn_dist);
+/* *bytes = a workspace that serves every ddsp_units_retrieve call of AT MOST `rows` rows at this Fr, k and N_max on the
+ * context's device (a host computation).  It is an upper bound that grows with rows - the exact need, rows * Fr * chunks * k * 8
+ * with chunks = ceil(2 CUs / (rows * ceil(Fr / 32))) capped at ceil(N_max / 128), does not, because of the ceil -, so one
+ * workspace sized for a bank's S slots serves every narrower width of its ladder. */
+int ddsp_units_retrieve_workspace(ddsp_ctx* ctx, int64_t rows, int64_t Fr, int k, int64_t N_max, int64_t* bytes);
+/* nrm (N) fp32 = the squared norms of vec (N, C) fp32: one wave per entry, a lane adds the squares of its 16-byte pieces in
+ * ascending channel order, then a butterfly over the wave.  One launch; DDSP_ERR_ARG for a null pointer, N < 1 or a bad C. */
+int ddsp_units_index_norms(ddsp_ctx* ctx, void* stream, const float* vec, int64_t N, int64_t C, float* nrm);
+
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
  * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)
