@@ -455,6 +455,174 @@ __device__ __forceinline__ void fir_bf16_products2(const FirBfArgs& g, const uin
     fir_bf16_run1(ah, al, bh + 128, bl + 128, b0 + 1 > a1 ? b0 + 1 : a1, b1, acc1);
 }
 
+// ---- march kernel, paired product waves: step-invariant shift ranges ------------------------------------------
+// In the march kernel J0 = HOPC*(s0 + seg) and m = s0 + m_off + f, so zt = HOP*(1 - m_off - d) with d = f - seg: the
+// step's first segment cancels, and the clipped ranges of fir_bf16_products2 depend on the tap count and on d alone.
+// For a tap count fixed at compile time they are constants, the same in every step, block and batch row.
+// FirTaps<N> holds them, and the (frame, piece, shift) sequence of a product wave as a table: the wave whose parity
+// (seg ^ odd) & 1 is PAR takes the frames d = PAR, PAR + 2, ..., each as fir_bf16_products2 runs it (first tile alone,
+// both tiles, second tile alone, shifts ascending).
+template <int N>
+struct FirTaps {
+    static constexpr int C = N / 2;
+    static constexpr int Q_LO = -((C + 15) / 32), Q_HI = (N + 30 - C) / 32;          // as ddsp_ltv_fir sets them
+    static constexpr int M_OFF = -((C - 1 + HOP - 1) / HOP);
+    static constexpr int EXTRA = (C - 1) / HOP + 1 - M_OFF + 1;
+    static constexpr int FD = ((N + FPL + FPR) / 2 + 4 + 15) / 32 * 32 + 16;
+    static constexpr int FSTRIDE = 4 * FD + 2 * XPLANE;
+    static constexpr int D_SCAN = 16;                                                 // frames d looked at (far beyond any that count)
+
+    static constexpr int fdiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+    static constexpr int zt(int d) { return HOP * (1 - M_OFF - d); }
+    static constexpr int qa(int z) { const int q = -fdiv(1023 - z, 32); return q < Q_LO ? Q_LO : q; }   // fir_bf16_range
+    static constexpr int qb(int z) { const int q = fdiv(z + 271, 32); return q > Q_HI ? Q_HI : q; }
+    // piece p of frame d: 0 = first tile alone, 1 = both tiles, 2 = second tile alone
+    static constexpr int lo(int d, int p) {
+        const int a0 = qa(zt(d)), b0 = qb(zt(d)), a1 = qa(zt(d) + 256);
+        return p == 0 ? a0 : p == 1 ? a1 : (b0 + 1 > a1 ? b0 + 1 : a1);
+    }
+    static constexpr int hi(int d, int p) {
+        const int b0 = qb(zt(d)), a1 = qa(zt(d) + 256), b1 = qb(zt(d) + 256);
+        return p == 0 ? (b0 < a1 - 1 ? b0 : a1 - 1) : p == 1 ? b0 : b1;
+    }
+    static constexpr int len(int d, int p) { return hi(d, p) >= lo(d, p) ? hi(d, p) - lo(d, p) + 1 : 0; }
+    static constexpr int frame_len(int d) { return len(d, 0) + len(d, 1) + len(d, 2); }
+    static constexpr int d_last() {
+        int r = -1;
+        for (int d = 0; d < D_SCAN; ++d)
+            if (frame_len(d) > 0) r = d;
+        return r;
+    }
+    static constexpr bool none_before(int segb) {   // frames f < seg (d < 0) contribute nothing
+        for (int d = 1 - segb; d < 0; ++d)
+            if (frame_len(d) > 0) return false;
+        return true;
+    }
+    static constexpr int list_len(int par) { return d_last() >= par ? (d_last() - par) / 2 + 1 : 0; }
+    static constexpr int stream_len(int par, int nf) {
+        int r = 0;
+        for (int j = 0; j < nf; ++j) r += frame_len(par + 2 * j);
+        return r;
+    }
+    struct Stage { int j, piece, Q; };               // frame of the list, piece, shift
+    static constexpr Stage stage(int par, int nf, int i) {
+        for (int j = 0; j < nf; ++j)
+            for (int p = 0; p < 3; ++p) {
+                const int l = len(par + 2 * j, p);
+                if (i < l) return Stage{j, p, lo(par + 2 * j, p) + i};
+                i -= l;
+            }
+        return Stage{0, 0, 0};
+    }
+};
+
+struct FirPairOps { u32x4 ah, al, bh0, bl0, bh1, bl1; };
+
+// pa = frame + a_off, pb = frame + 4*fd + lb: every other part of the addresses of fir_bf16_run1 / run2 is a constant here
+template <class R, int D, int PIECE, int Q>
+__device__ __forceinline__ void fir_bf16_fetch_at(const uint32_t* pa, const uint32_t* pb, FirPairOps& o) {
+    const uint32_t* ah = pa - 16 * Q;
+    const uint32_t* al = ah + 2 * R::FD;
+    const uint32_t* bh = pb + ((XPAD + R::zt(D)) / 2 - 16 * Q);
+    o.ah = (u32x4){ah[0], ah[1], ah[2], ah[3]};
+    o.al = (u32x4){al[0], al[1], al[2], al[3]};
+    if constexpr (PIECE != 2) {
+        o.bh0 = *(const u32x4*)bh;
+        o.bl0 = *(const u32x4*)(bh + XPLANE);
+    }
+    if constexpr (PIECE != 0) {
+        o.bh1 = *(const u32x4*)(bh + 128);
+        o.bl1 = *(const u32x4*)(bh + 128 + XPLANE);
+    }
+}
+
+template <int PIECE>
+__device__ __forceinline__ void fir_bf16_mm_at(const FirPairOps& o, f32x4 (&acc0)[3], f32x4 (&acc1)[3]) {
+    const bf16x8 a_h = __builtin_bit_cast(bf16x8, o.ah), a_l = __builtin_bit_cast(bf16x8, o.al);
+    const bf16x8 b_h0 = __builtin_bit_cast(bf16x8, o.bh0), b_l0 = __builtin_bit_cast(bf16x8, o.bl0);
+    const bf16x8 b_h1 = __builtin_bit_cast(bf16x8, o.bh1), b_l1 = __builtin_bit_cast(bf16x8, o.bl1);
+    if constexpr (PIECE != 2) acc0[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h, b_h0, acc0[0], 0, 0, 0);
+    if constexpr (PIECE != 0) acc1[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h, b_h1, acc1[0], 0, 0, 0);
+    if constexpr (PIECE != 2) acc0[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_l, b_h0, acc0[1], 0, 0, 0);
+    if constexpr (PIECE != 0) acc1[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_l, b_h1, acc1[1], 0, 0, 0);
+    if constexpr (PIECE != 2) acc0[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h, b_l0, acc0[2], 0, 0, 0);
+    if constexpr (PIECE != 0) acc1[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h, b_l1, acc1[2], 0, 0, 0);
+}
+
+template <class R, int PAR, int NF, int I>
+__device__ __forceinline__ void fir_bf16_stream_fetch(const uint32_t* (&pa)[NF], const uint32_t* (&pb)[NF], FirPairOps (&o)[3]) {
+    constexpr typename R::Stage s = R::stage(PAR, NF, I);
+    fir_bf16_fetch_at<R, PAR + 2 * s.j, s.piece, s.Q>(pa[s.j], pb[s.j], o[I % 3]);
+}
+
+// Stages I.. of the stream over the first NF frames of the list: one software pipeline with three operand sets in
+// rotation, the reads of stage I + 2 issued before the MFMAs of stage I, across pieces and frames alike.
+template <class R, int PAR, int NF, int I>
+__device__ __forceinline__ void fir_bf16_stream(const uint32_t* (&pa)[NF], const uint32_t* (&pb)[NF], FirPairOps (&o)[3],
+                                                f32x4 (&acc0)[3], f32x4 (&acc1)[3]) {
+    constexpr int LEN = R::stream_len(PAR, NF);
+    if constexpr (I < LEN) {
+        constexpr typename R::Stage s = R::stage(PAR, NF, I);
+        if constexpr (I + 2 < LEN) fir_bf16_stream_fetch<R, PAR, NF, I + 2>(pa, pb, o);
+        fir_bf16_mm_at<s.piece>(o[I % 3], acc0, acc1);
+        if constexpr (I + 2 < LEN) __builtin_amdgcn_sched_group_barrier(0x100, R::stage(PAR, NF, I + 2).piece == 1 ? 8 : 6, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, s.piece == 1 ? 6 : 3, 0);
+        fir_bf16_stream<R, PAR, NF, I + 1>(pa, pb, o, acc0, acc1);
+    }
+}
+
+template <class R, int PAR, int NF>
+__device__ __forceinline__ void fir_bf16_stream_run(const uint32_t* (&fr)[NF], int a_off, int lb,
+                                                    f32x4 (&acc0)[3], f32x4 (&acc1)[3]) {
+    const uint32_t* pa[NF];
+    const uint32_t* pb[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+        pa[j] = fr[j] + a_off;
+        pb[j] = fr[j] + 4 * R::FD + lb;
+    }
+    FirPairOps o[3];
+    if constexpr (R::stream_len(PAR, NF) > 0) fir_bf16_stream_fetch<R, PAR, NF, 0>(pa, pb, o);
+    if constexpr (R::stream_len(PAR, NF) > 1) fir_bf16_stream_fetch<R, PAR, NF, 1>(pa, pb, o);
+    fir_bf16_stream<R, PAR, NF, 0>(pa, pb, o, acc0, acc1);
+}
+
+// One step of a product wave of parity PAR: the frames f = seg + PAR, seg + PAR + 2, ... of the step, whose first frame
+// sits in ring slot r0.  All of them there (every step but a block's first and last): the one stream; the last one
+// beyond the step's NFR frames (the highest segments of a step): the stream without it; anything else: false, and the
+// caller goes frame by frame with fir_bf16_products2.  Per accumulator the MFMAs are those of fir_bf16_products2 in
+// its order, whichever way.
+template <class R, int SEGB, int PAR>
+__device__ __forceinline__ bool fir_bf16_pair_step(const FirBfArgs& g, const uint32_t* ldsw, int r0, int seg, int s0, int a_off,
+                                                   int lb, f32x4 (&acc0)[3], f32x4 (&acc1)[3]) {
+    constexpr int NFR = SEGB + R::EXTRA, RING = NFR + SEGB, NL = R::list_len(PAR);
+    static_assert(NL >= 1 && NL <= 4 && R::none_before(SEGB), "fir_bf16_pair_step: frame list");
+    constexpr bool SHORT = PAR + 2 * (NL - 1) + SEGB - 1 >= NFR;   // some segment's last list frame is not one of the step's
+    const uint32_t* fr[NL];
+    int here = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        const int f = seg + PAR + 2 * j, m = s0 + R::M_OFF + f;
+        int r = r0 + f;
+        if (r >= RING) r -= RING;
+        fr[j] = ldsw + r * R::FSTRIDE;
+        if (f < NFR && m >= 0 && m <= g.Fr) here |= 1 << j;
+    }
+    if (here == (1 << NL) - 1) {
+        fir_bf16_stream_run<R, PAR, NL>(fr, a_off, lb, acc0, acc1);
+    } else if (SHORT && NL > 1 && here == (1 << (NL - 1)) - 1) {
+        if constexpr (SHORT && NL > 1) {
+            const uint32_t* frs[NL - 1];
+#pragma unroll
+            for (int j = 0; j < NL - 1; ++j) frs[j] = fr[j];
+            fir_bf16_stream_run<R, PAR, NL - 1>(frs, a_off, lb, acc0, acc1);
+        }
+    } else {
+        return false;
+    }
+    return true;
+}
+
 // C/D map of the 16x16 MFMA: col = lane & 15, row = 4*(lane >> 4) + reg  ->  one float4 per lane
 __device__ __forceinline__ void fir_bf16_store(const FirBfArgs& g, int b, int J0, int li, int lk, const f32x4 (&acc)[3]) {
     const int64_t T = (int64_t)g.Fr * HOP;
@@ -504,8 +672,11 @@ __global__ void __launch_bounds__(64 * 2 * SEGB, (SEGB <= 4 ? 4 : 3)) ltv_fir_bf
 // PAIR = false: a product wavefront owns one 256-sample tile.  PAIR = true: two product wavefronts own one segment (two
 // neighbouring tiles sharing the filter operand), one taking the even, the other the odd frames of the step; the odd one
 // hands its partial sums over through the LDS.  Either way 2*SEGB product wavefronts.
-template <int SEGB, int SW, bool PAIR>
+// NTAP != 0 (PAIR only): the tap count, known at compile time; a product wave's step is then one pipelined stream over
+// constant shift ranges (fir_bf16_pair_step) instead of a range computation and three loops per frame.  Same sums.
+template <int SEGB, int SW, bool PAIR, int NTAP = 0>
 __global__ void __launch_bounds__(64 * (2 + SW) * SEGB) ltv_fir_bf16_march_kernel(FirBfArgs g) {
+    static_assert(NTAP == 0 || PAIR, "ltv_fir_bf16_march_kernel: a tap class needs paired product waves");
     extern __shared__ __align__(16) uint32_t ldsw[];
     constexpr int NCOMP = 2 * SEGB, NWAVE = (2 + SW) * SEGB;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -529,6 +700,7 @@ __global__ void __launch_bounds__(64 * (2 + SW) * SEGB) ltv_fir_bf16_march_kerne
     const int li = lane & 15, lk = lane >> 4;
     const int y00 = FPL + g.n - 1 - g.n / 2 - li + 8 * lk;
     const int a_off = (y00 & 1) * g.fd + (y00 >> 1);
+    int r0 = 0;                                   // NTAP: ring slot of the step's first frame, (s0 - hop0) mod ring
     for (int s0 = hop0; s0 < hop_end; s0 += SEGB) {
         f32x4 acc[PAIR ? 2 : 1][3];
         const int seg = wave >> 1, odd = wave & 1;          // PAIR: the wave's segment of the step and its share of the frames
@@ -538,18 +710,29 @@ __global__ void __launch_bounds__(64 * (2 + SW) * SEGB) ltv_fir_bf16_march_kerne
             // staging wavefronts: frame j of the SEGB frames the next step adds (part = filter / image when SW == 2)
             const int sw = wave - NCOMP;
             const int m = s0 + g.m_off + g.nfr + sw / SW;
+            int sl = lane;
+            // NTAP: the stream needs the registers that the staging code's lane constants (window, addresses) would hold
+            // for the whole loop if they were hoisted out of it: the lane number is made opaque, so they are formed here
+            if constexpr (NTAP != 0) asm volatile("" : "+v"(sl));
             if (s0 + SEGB < hop_end && m >= 0 && m <= g.Fr)
-                fir_bf16_stage(g, b, m, slot(m), lane, SW == 1 ? (STAGE_FILTER | STAGE_IMAGE) : (sw % SW ? STAGE_IMAGE : STAGE_FILTER));
+                fir_bf16_stage(g, b, m, slot(m), sl, SW == 1 ? (STAGE_FILTER | STAGE_IMAGE) : (sw % SW ? STAGE_IMAGE : STAGE_FILTER));
         } else if (mine) {
 #pragma unroll
             for (int t = 0; t < (PAIR ? 2 : 1); ++t)
 #pragma unroll
                 for (int x = 0; x < 3; ++x) acc[t][x] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if constexpr (PAIR) {
-                for (int f = odd; f < g.nfr; f += 2) {
-                    const int m = s0 + g.m_off + f;
-                    if (m < 0 || m > g.Fr) continue;
-                    fir_bf16_products2(g, slot(m), m, J0, a_off, 8 * li + 4 * lk, acc[0], acc[1]);
+                bool done = false;
+                if constexpr (NTAP != 0) {
+                    done = ((seg ^ odd) & 1) ? fir_bf16_pair_step<FirTaps<NTAP>, SEGB, 1>(g, ldsw, r0, seg, s0, a_off, 8 * li + 4 * lk, acc[0], acc[1])
+                                             : fir_bf16_pair_step<FirTaps<NTAP>, SEGB, 0>(g, ldsw, r0, seg, s0, a_off, 8 * li + 4 * lk, acc[0], acc[1]);
+                }
+                if (!done) {
+                    for (int f = odd; f < g.nfr; f += 2) {
+                        const int m = s0 + g.m_off + f;
+                        if (m < 0 || m > g.Fr) continue;
+                        fir_bf16_products2(g, slot(m), m, J0, a_off, 8 * li + 4 * lk, acc[0], acc[1]);
+                    }
                 }
                 if (odd) {
 #pragma unroll
@@ -575,7 +758,19 @@ __global__ void __launch_bounds__(64 * (2 + SW) * SEGB) ltv_fir_bf16_march_kerne
             }
         }
         __syncthreads();
+        if constexpr (NTAP != 0) {
+            r0 += SEGB;
+            if (r0 >= SEGB + SEGB + FirTaps<NTAP>::EXTRA) r0 -= SEGB + SEGB + FirTaps<NTAP>::EXTRA;
+        }
     }
+}
+
+// the compile-time constants of FirTaps<N> are what ddsp_ltv_fir worked out for this call
+template <int N, int SEGB>
+bool fir_taps_match(const FirBfArgs& g) {
+    using R = FirTaps<N>;
+    return g.n == N && g.Q_lo == R::Q_LO && g.Q_hi == R::Q_HI && g.m_off == R::M_OFF && g.fd == R::FD && g.nfr == SEGB + R::EXTRA &&
+           g.ring == g.nfr + SEGB;
 }
 
 template <int SEGB>
@@ -586,10 +781,10 @@ int launch_fir_bf16(ddsp_ctx* ctx, hipStream_t st, FirBfArgs g, int64_t B, int64
     return DDSP_OK;
 }
 
-template <int SEGB, int SW, bool PAIR>
+template <int SEGB, int SW, bool PAIR, int NTAP = 0>
 int launch_fir_bf16_march(ddsp_ctx* ctx, hipStream_t st, FirBfArgs g, int64_t B, int nchunks, size_t lds_bytes) {
-    DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)ltv_fir_bf16_march_kernel<SEGB, SW, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
-    hipLaunchKernelGGL((ltv_fir_bf16_march_kernel<SEGB, SW, PAIR>), dim3((unsigned)nchunks, (unsigned)B),
+    DDSP_ONCE_PER_DEVICE(ctx, DDSP_HIP(ctx, hipFuncSetAttribute((const void*)ltv_fir_bf16_march_kernel<SEGB, SW, PAIR, NTAP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
+    hipLaunchKernelGGL((ltv_fir_bf16_march_kernel<SEGB, SW, PAIR, NTAP>), dim3((unsigned)nchunks, (unsigned)B),
                        dim3(64 * (2 + SW) * SEGB), lds_bytes, st, g);
     return DDSP_OK;
 }
@@ -837,7 +1032,11 @@ extern "C" int ddsp_ltv_fir(ddsp_ctx* ctx, void* stream, const float* audio, int
                     ddsp_prof_begin(ctx, (hipStream_t)stream, PF_LTV_FIR);
                     int rc;
                     hipStream_t st = (hipStream_t)stream;
-                    switch (mc) {
+                    // the flagship's two tap counts have a form of their own (math 3 only: a forced shape is the generic kernel)
+                    const int ntap = math == 3 && mc == 7 && fir_taps_match<510, 4>(g) ? 510 : math == 3 && mc == 6 && fir_taps_match<1022, 3>(g) ? 1022 : 0;
+                    if (ntap == 510) rc = launch_fir_bf16_march<4, 1, true, 510>(ctx, st, g, B, nchunks, lds_bytes);
+                    else if (ntap == 1022) rc = launch_fir_bf16_march<3, 2, true, 1022>(ctx, st, g, B, nchunks, lds_bytes);
+                    else switch (mc) {
                         case 1: rc = launch_fir_bf16_march<3, 1, false>(ctx, st, g, B, nchunks, lds_bytes); break;
                         case 2: rc = launch_fir_bf16_march<3, 2, false>(ctx, st, g, B, nchunks, lds_bytes); break;
                         case 3: rc = launch_fir_bf16_march<4, 1, false>(ctx, st, g, B, nchunks, lds_bytes); break;
