@@ -30,6 +30,7 @@
 // (ids are unique, so the order is total), then the k vectors are gathered with 16-byte loads twice - once for s_j, once for
 // the weighted mean - and out, nn_id and nn_dist are stored.
 #include "common.h"
+#include "unit_order.h"
 
 #include <cfloat>
 #include <climits>
@@ -76,8 +77,6 @@ __device__ __forceinline__ RowIndex retrieve_row(int64_t row, const int32_t* __r
     ri.r = r;
     return ri;
 }
-
-__device__ __forceinline__ bool before(float t, int i, float t2, int i2) { return t < t2 || (t == t2 && i < i2); }
 
 __global__ void __launch_bounds__(RT_THREADS) retrieve_search_kernel(
     const float* __restrict__ units, int Fr, int C, int qtiles, const int32_t* __restrict__ n_frames,

@@ -264,6 +264,8 @@ SIGNATURES = {
                                    _vp, _i64, _vp, _vp]),
     "ddsp_units_retrieve_workspace": (_int, [_vp, _i64, _i64, _int, _i64, _vp]),
     "ddsp_units_index_norms": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "ddsp_units_kmeans_assign": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "ddsp_units_kmeans_update": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _i64]),
     "ddsp_bank_features_gather": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
     "ddsp_bank_signal_scatter": (_int, [_vp, _vp, _vp, _int, _int, _vp, _i64, _vp]),
@@ -1793,6 +1795,61 @@ class Context:
                   _ptr(ratio_of_row), int(bank.off.numel()) - 1, _ptr(bank.off), _ptr(bank.vec), _ptr(bank.nrm), int(bank.vec.shape[0]), int(bank.n_max),
                   k, _ptr(ws), int(ws.numel()) * ws.element_size(), _ptr(nn_id), _ptr(nn_dist))
         return units
+
+    @staticmethod
+    def _kmeans_shapes(name, vec, cen, others):
+        """The checks the two k-means calls share: vec (N, C) and cen (K, C) fp32, K <= N, both 16-byte aligned (the kernels read
+        them 16 bytes at a time: a view that starts at an odd element is refused), and `others` = [(what, tensor, dtype,
+        shape)], all contiguous on vec's device -> (N, C, K)."""
+        def ok(t, dtype, shape=None):
+            return isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda and t.is_contiguous() and \
+                (shape is None or tuple(t.shape) == shape) and (t is vec or t.device == vec.device)
+
+        if not (ok(vec, torch.float32) and vec.dim() == 2 and 1 <= vec.shape[0] < 2 ** 31 and 4 <= vec.shape[1] <= 1024 and
+                vec.shape[1] % 4 == 0 and vec.data_ptr() % 16 == 0):
+            raise ValueError(f"{name}: vec must be a contiguous, 16-byte aligned (N, C) fp32 device tensor, 1 <= N < 2^31, C a multiple "
+                             f"of 4 in 4..1024")
+        N, C = int(vec.shape[0]), int(vec.shape[1])
+        if not (ok(cen, torch.float32) and cen.dim() == 2 and int(cen.shape[1]) == C and 1 <= cen.shape[0] <= N and
+                cen.data_ptr() % 16 == 0):
+            raise ValueError(f"{name}: cen must be a contiguous, 16-byte aligned (K, C = {C}) fp32 tensor on vec's device with "
+                             f"1 <= K <= N = {N}")
+        K = int(cen.shape[0])
+        for what, t, dtype, shape in others:
+            shape = tuple(K if n == "K" else N if n == "N" else n for n in shape)
+            if not ok(t, dtype, shape):
+                raise ValueError(f"{name}: {what} must be a contiguous {shape} {str(dtype)[6:]} tensor on vec's device")
+        return N, C, K
+
+    def units_kmeans_assign_(self, vec, cen, cnrm, assign, moved):
+        """The assignment step of the index reduction (`ddsp_units_kmeans_assign`; include/ddsp_amd.h states the rule): every
+        entry of vec (N, C) fp32 goes to the centre of cen (K, C) with the smallest (cnrm[j] - 2 <x, cen[j]>, j), cnrm (K,) fp32
+        the centres' norms (`units_index_norms`).  In place: assign (N,) int32 is read as the previous assignment and
+        overwritten, moved (1,) int32 grows by the number of entries that changed.  -> assign."""
+        N, C, K = self._kmeans_shapes("units_kmeans_assign_", vec, cen, [("cnrm", cnrm, torch.float32, ("K",)),
+                                                                          ("assign", assign, torch.int32, ("N",)),
+                                                                          ("moved", moved, torch.int32, (1,))])
+        self.call("ddsp_units_kmeans_assign", _ptr(vec), N, C, _ptr(cen), _ptr(cnrm), K, _ptr(assign), _ptr(moved))
+        return assign
+
+    def units_kmeans_update_(self, vec, assign, cen, count, shift, workspace):
+        """The update step of the index reduction (`ddsp_units_kmeans_update`): in place, centre j of cen (K, C) fp32 becomes the
+        mean of the entries of vec (N, C) with assign (N,) int32 == j, formed exactly in 64-bit fixed point at `shift` (an int:
+        62 - E - L of the rule, from the host); a centre without entries keeps its bits, an assignment outside [0, K) belongs to
+        no centre.  count (K,) int32 receives the entries of every centre; workspace: at least K * C * 8 bytes on vec's device,
+        any dtype, zeroed by the call.  -> cen."""
+        N, C, K = self._kmeans_shapes("units_kmeans_update_", vec, cen, [("assign", assign, torch.int32, ("N",)),
+                                                                          ("count", count, torch.int32, ("K",))])
+        if isinstance(shift, bool) or not isinstance(shift, int) or not -97 <= shift <= 210:
+            raise ValueError(f"units_kmeans_update_: shift must be an int in -97..210 (62 - E - L of the rule), got {shift!r}")
+        if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == vec.device and
+                workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= K * C * 8 and
+                workspace.data_ptr() % 16 == 0):
+            raise ValueError(f"units_kmeans_update_: workspace must be a contiguous, 16-byte aligned tensor of at least K * C * 8 = "
+                             f"{K * C * 8} bytes on vec's device")
+        self.call("ddsp_units_kmeans_update", _ptr(vec), N, C, _ptr(assign), K, shift, _ptr(cen), _ptr(count), _ptr(workspace),
+                  int(workspace.numel()) * workspace.element_size())
+        return cen
 
     def bank_features_gather_(self, rows, units, f0, volume, mix, cunits, cf0, cvolume, cmix, noise=None, cnoise=None):
         """The rows of one model out of a call's row batch (`ddsp_bank_features_gather`): rows (W,) int32 device, entry r the row

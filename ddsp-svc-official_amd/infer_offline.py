@@ -573,7 +573,9 @@ def tune_tables(tunes, sampling_rate, block_size):
 class UnitIndex:
     """The stored units of one voice, for unit retrieval (include/ddsp_amd.h states the rule at `ddsp_units_retrieve`): vectors
     (N, C) fp32 on the host, N >= 1, C a multiple of 4 and at most 1024, every value finite.  An index is the aligned units of a
-    speaker's training files (`from_units_dir`); k-means or IVF reduction of a large index is not here."""
+    speaker's training files (`from_units_dir`); a large one is reduced to k-means centres on the device before it is served
+    (`reduce`, `from_units_dir(centres=)`; include/ddsp_amd.h states that rule at `ddsp_units_kmeans_assign`).  IVF or any other
+    approximate search is not here."""
 
     def __init__(self, vectors):
         v = torch.as_tensor(np.asarray(vectors) if not isinstance(vectors, torch.Tensor) else vectors)
@@ -592,11 +594,64 @@ class UnitIndex:
     def channels(self):
         return int(self.vectors.shape[1])
 
+    @staticmethod
+    def fixed_shift(vectors):
+        """S = 62 - E - L of the reduction's fixed point: max|vectors| < 2^E (the frexp exponent; 0 for an all-zero index) and
+        L = (N - 1).bit_length(), so the int64 sum of N values rint(x * 2^S) stays within 2^62."""
+        top = float(vectors.abs().max())
+        return 62 - (math.frexp(top)[1] if top > 0 else 0) - (int(vectors.shape[0]) - 1).bit_length()
+
+    def reduce(self, centres, iters=10, device="cuda", report=False):
+        """The index reduced to at most `centres` k-means centres on `device` (include/ddsp_amd.h states the rule at
+        `ddsp_units_kmeans_assign`; it is deterministic): the centres start as the `max_entries` subset, `iters` full Lloyd
+        iterations of (`ddsp_units_index_norms`, `ddsp_units_kmeans_assign`, `ddsp_units_kmeans_update`) run on one stream with
+        no read-back between them, and the centres that hold entries in the last iteration are kept, in id order.  One upload,
+        one read-back.  `centres >= len(self)`: self, unchanged.  report=True -> (index, {"moved": entries that changed centre in
+        every iteration, "count": (K,) int32 entries of every centre in the last one, "dropped": the empty centres left out,
+        "shift": the fixed point's S}).  ValueError for a `centres` that is no int >= 1 or an `iters` that is no int >= 0."""
+        if isinstance(centres, bool) or not isinstance(centres, numbers.Integral) or centres < 1:
+            raise ValueError(f"UnitIndex.reduce: centres must be an int >= 1, got {centres!r}")
+        if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or iters < 0:
+            raise ValueError(f"UnitIndex.reduce: iters must be an int >= 0, got {iters!r}")
+        N, K, iters = len(self), int(centres), int(iters)
+        shift = self.fixed_shift(self.vectors)
+        if K >= N:
+            rep = {"moved": [], "count": np.ones(N, dtype=np.int32), "dropped": 0, "shift": shift}
+            return (self, rep) if report else self
+        start = self.vectors[(torch.arange(K, dtype=torch.int64) * N) // K]
+        if iters == 0:
+            rep = {"moved": [], "count": np.ones(K, dtype=np.int32), "dropped": 0, "shift": shift}
+            return (UnitIndex(start), rep) if report else UnitIndex(start)
+        dev = torch.device(device)
+        ctx = hipddsp.context_for(dev)                      # (refuses a device that is no HIP device)
+        vec = self.vectors.to(dev)
+        cen = start.to(dev)
+        assign = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        moved = torch.zeros(iters, dtype=torch.int32, device=dev)
+        count = torch.empty(K, dtype=torch.int32, device=dev)
+        ws = torch.empty(K * self.channels, dtype=torch.int64, device=dev)
+        for it in range(iters):
+            cnrm = ctx.units_index_norms(cen)
+            ctx.units_kmeans_assign_(vec, cen, cnrm, assign, moved[it:it + 1])
+            ctx.units_kmeans_update_(vec, assign, cen, count, shift, ws)
+        back = torch.cat([cen.view(torch.int32).reshape(-1), count, moved]).cpu()                  # the one read-back
+        cen_h = back[:K * self.channels].view(torch.float32).reshape(K, self.channels)
+        count_h = back[K * self.channels:K * self.channels + K]
+        out = UnitIndex(cen_h[count_h > 0])
+        if not report:
+            return out
+        return out, {"moved": back[K * self.channels + K:].tolist(), "count": count_h.numpy().copy(),
+                     "dropped": int((count_h == 0).sum()), "shift": shift}
+
     @classmethod
-    def from_units_dir(cls, path, spk=None, max_entries=None):
+    def from_units_dir(cls, path, spk=None, max_entries=None, centres=None, iters=10, device="cuda"):
         """The index of the `units/` tree that `preprocess.py` wrote under `path` (<path>/units/<spk>/<name>.0.npy, each (n, C)):
         every file of speaker folder `spk` (None: of all folders), sorted by relative name, frame after frame.  max_entries: a
-        deterministic evenly strided subset of that many rows (row floor(i * N / max_entries)) when there are more."""
+        deterministic evenly strided subset of that many rows (row floor(i * N / max_entries)) when there are more.  centres: the
+        rows - what max_entries left of them - are then reduced to that many k-means centres by `reduce(centres, iters, device)`."""
+        for name, v, low in (("centres", centres, 1), ("iters", iters, 0)):
+            if (v is not None or name == "iters") and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < low):
+                raise ValueError(f"UnitIndex.from_units_dir: {name} must be an int >= {low}, got {v!r}")
         root = os.path.join(path, "units")
         if spk is not None:
             root = os.path.join(root, str(spk))
@@ -610,7 +665,8 @@ class UnitIndex:
                 raise ValueError(f"UnitIndex.from_units_dir: max_entries must be an int >= 1, got {max_entries!r}")
             if len(rows) > max_entries:
                 rows = rows[(np.arange(int(max_entries), dtype=np.int64) * len(rows)) // int(max_entries)]
-        return cls(rows)
+        index = cls(rows)
+        return index if centres is None else index.reduce(centres, iters=iters, device=device)
 
     def save(self, path):
         """A plain tensor file: torch.save of {'vectors': (N, C) fp32}."""

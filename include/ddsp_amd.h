@@ -580,6 +580,47 @@ int ddsp_units_retrieve_workspace(ddsp_ctx* ctx, int64_t rows, int64_t Fr, int k
  * ascending channel order, then a butterfly over the wave.  One launch; DDSP_ERR_ARG for a null pointer, N < 1 or a bad C. */
 int ddsp_units_index_norms(ddsp_ctx* ctx, void* stream, const float* vec, int64_t N, int64_t C, float* nrm);
 
+/* UNIT INDEX REDUCTION: a large index vec (N, C) fp32, finite, is reduced to at most K k-means centres before it is served
+ * (`infer_offline.UnitIndex.reduce`).  A definition of this project, like the retrieval rule (RVC reduces with scikit-learn's
+ * MiniBatchKMeans, which draws at random; this rule is deterministic); tests/kmeans_cases.py states it in numpy fp64 and Python
+ * integers.  C a multiple of 4 in 4..1024, 1 <= K <= N < 2^31, iters >= 0.  Every pointer is a DEVICE pointer; vec and cen are
+ * 16-byte aligned (the kernels read them 16 bytes at a time).
+ * INITIAL CENTRES: cen[j] = vec[floor(j * N / K)], bit for bit - the `max_entries` subset, so iters = 0 is max_entries = K.
+ * ONE ITERATION is three calls on one stream:
+ *   1. cnrm = ddsp_units_index_norms(cen)
+ *   2. ddsp_units_kmeans_assign: t_ij = cnrm[j] - 2 * <x_i, cen[j]> in fp32 on the fp32 matrix pipe (the retrieval score),
+ *      a_i = the j with the smallest (t_ij, j): equal scores go to the smaller centre id.  *moved += the number of entries
+ *      whose a_i differs from the value `assign` held before the call (all -1 before the first iteration: N then).
+ *   3. ddsp_units_kmeans_update: exact, order-free sums in 64-bit fixed point, so integer atomics give the same bits on every
+ *      run.  The HOST forms shift = 62 - E - L with max|vec| < 2^E (the frexp exponent; 0 for an all-zero index) and
+ *      L = bit_length(N - 1);  q_ic = (int64) rint(ldexp((double) x_ic, shift));  sum_jc = the sum of q_ic over a_i == j
+ *      (|sum| <= 2^62);  n_j = their count.  n_j > 0: cen[j][c] = (float) ldexp((double) sum_jc / (double) n_j, -shift) - the
+ *      int64 -> double conversion rounds to nearest even, one fp64 division, one rounding to fp32.  n_j == 0: the centre
+ *      keeps its bits.
+ * RESULT of iters >= 1 iterations: the centres with n_j > 0 in the last one, in id order; of iters == 0: the K strided rows.
+ * No early stop, no read-back between iterations.
+ *
+ * ddsp_units_kmeans_assign, one launch: assign (N) int32 is READ as the previous assignment and overwritten; moved: one int32,
+ * added to.  A workgroup owns a tile of 128 entries and marches over ALL centres in stages of 128 centres x 32 channels through
+ * the LDS; every wave forms 64 entries x 64 centres of scores with v_mfma_f32_32x32x2_f32 (centres as A, entries as B: a
+ * lane's accumulators are centres of ONE entry) and keeps the entry's running (t, id) minimum in registers.  No candidate
+ * lists, no workspace, no merge launch: four lanes see an entry, one thread merges them, stores the int32 and the workgroup
+ * adds its moved count with one atomic.  An entry whose every score is NaN (inputs that are not finite) gets -1.
+ * DDSP_ERR_ARG, and nothing launched, for a null pointer, N or K < 1, K > N, N >= 2^31, a bad C, or a vec or cen that is not
+ * 16-byte aligned. */
+int ddsp_units_kmeans_assign(ddsp_ctx* ctx, void* stream, const float* vec, int64_t N, int64_t C, const float* cen,
+                             const float* cnrm, int64_t K, int32_t* assign, int32_t* moved);
+/* Step 3.  cen (K, C) is updated IN PLACE; count (K) int32 is written, every element.  workspace: at least K * C * 8 bytes,
+ * 16-byte aligned; the call zeroes it itself.  Two launches behind two clears: accumulate - a group of C / 4 threads walks a run
+ * of neighbouring entries (neighbouring frames, which often share a centre), sums runs of equal assignment in registers and adds
+ * each run with 64-bit integer vector atomics - then finalise.  An assignment outside [0, K) is tested before it forms an
+ * address: its entry belongs to no centre (-1 is the defined "none").
+ * DDSP_ERR_ARG, and nothing launched, for a null pointer, N or K < 1, K > N, N >= 2^31, a bad C, a shift outside [-97, 210]
+ * (what the rule can give), a workspace that is too small, or a vec, cen or workspace that is not 16-byte aligned.
+ * Neither call synchronises, allocates or reads back; both are graph-capturable. */
+int ddsp_units_kmeans_update(ddsp_ctx* ctx, void* stream, const float* vec, int64_t N, int64_t C, const int32_t* assign,
+                             int64_t K, int shift, float* cen, int32_t* count, void* workspace, int64_t workspace_bytes);
+
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
  * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)
