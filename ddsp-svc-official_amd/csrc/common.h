@@ -164,6 +164,7 @@ int ddsp_take_dev_error(ddsp_ctx* ctx);
 #define DDSP_DEV_ERR_FORMANT 6   // ddsp_ctrl_warp: a formant factor that is not finite or not > 0
 #define DDSP_DEV_ERR_TUNE 7      // ddsp_f0_tune: a pitch-correction setting with a bad a4, strength or alpha
 #define DDSP_DEV_ERR_RETRIEVE 8  // ddsp_units_retrieve: a row that names an index with a ratio that is not finite or outside [0, 1]
+#define DDSP_DEV_ERR_ENVELOPE 9  // ddsp_envelope_rms / ddsp_envelope_apply: a bad rate, owner, source row or count, or a span that leaves the tensor
 
 // profiler hooks (ctx.hip): bracket ONE kernel launch (or a tight group) on `st` when the family is enabled
 void ddsp_prof_begin(ddsp_ctx* ctx, hipStream_t st, int id);

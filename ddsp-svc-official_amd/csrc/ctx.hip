@@ -261,6 +261,10 @@ int ddsp_take_dev_error(ddsp_ctx* ctx) {
     if (code == DDSP_DEV_ERR_RETRIEVE)
         return ddsp_fail(ctx, DDSP_ERR_ARG, "a retrieval ratio that is not finite or outside [0, 1] on a row that names an index in an "
                          "earlier ddsp_units_retrieve call", "the units of those rows were left as they were");
+    if (code == DDSP_DEV_ERR_ENVELOPE)
+        return ddsp_fail(ctx, DDSP_ERR_ARG, "an envelope-mix rate that is not finite or outside [0, 1], an owner or source row outside "
+                         "its table, a source count < 1 or a span that leaves the tensor in an earlier ddsp_envelope_rms or "
+                         "ddsp_envelope_apply call", "those rows were left as they were (their envelope is 0)");
     if (code) return ddsp_fail(ctx, DDSP_ERR_ARG, "device-side contract violation in an earlier call", "");
     return DDSP_OK;
 }

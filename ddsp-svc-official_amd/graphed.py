@@ -212,8 +212,8 @@ class GraphedModelRows(GraphedSynth):
 
 
 def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, samplerate, hop_size, silence_front, pitch,
-                threshold_db, block_size, speaker, noise=None, f0_dither=True, seed_dev=None, push=None, tune=None,
-                retrieve=None):
+                threshold_db, block_size, speaker, noise=None, f0_dither=True, seed_dev=None, push=None, envelope=None,
+                tune=None, retrieve=None):
     """One block of the reference's callback from the raw audio to the gated model output (gui.py:373-374 and
     `gui.SvcDDSP.infer`, gui.py:87-127), every step on the device, nothing read back: `window` takes `block_in` in place,
     then volume, f0 (uv_interp, silent front), the pitch shift, units, the synthesiser and the gate.
@@ -234,6 +234,10 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
     `retrieve`: None, or the unit retrieval of the rows (bank - an `infer_offline.UnitIndexBank` -, index_of_slot (S,) int32,
     ratio_of_slot (S,) fp32, k, slot_of_row (rows,) int32 or None: row b is slot b): one `Context.units_retrieve_` right behind
     `units_encoder.encode`, in place on its result, so the synthesiser - or every model's row gather - sees the blended units.
+    `envelope`: None, or the envelope mix of the rows (rate_of_slot (S,) fp64 device, hop_in, hop_out, m, slot_of_row (rows,)
+    int32 or None: row b is slot b): right behind the gate, `Context.envelope_rms` of the window at the device rate (hop_in),
+    `Context.envelope_rms` of the gated signal at the model's rate (hop_out) and one `Context.envelope_mix_`, in place on the
+    signal (RVC's `change_rms`; include/ddsp_amd.h states the rule).  A row whose rate is 1 keeps its bits.  Not with model=None.
     -> (signal (rows, Fr * block_size), f0 (rows, Fr, 1) after the shift, units (rows, Fr, C), volume (rows, Fr)), rows = 1 or S."""
     if push is None:
         ctx.stream_push_(window, block_in)
@@ -254,10 +258,16 @@ def block_chain(ctx, model, units_encoder, f0_extractor, window, block_in, sampl
         bank, index_of_slot, ratio_of_slot, k, slot_of_row = retrieve
         units = ctx.units_retrieve_(units.contiguous(), bank, index_of_slot, ratio_of_slot, k=k, owner=slot_of_row)
     if model is None:
+        if envelope is not None:
+            raise ValueError("block_chain: envelope= needs the model (the signal is rendered here)")
         return None, f0, units, volume
     kw = {} if noise is None else {"noise": noise}
     sig = (model.forward_formant if "formant" in speaker else model)(units, f0, volume, **speaker, **kw)[0]
     ctx.volume_gate_(sig, volume, threshold_db, block_size)          # (`block_size`: the model's, as a host int - no read-back)
+    if envelope is not None:
+        rate_of_slot, hop_in, hop_out, m, slot_of_row = envelope
+        ctx.envelope_mix_(sig, ctx.envelope_rms(audio, hop_in, m), rate_of_slot, ctx.envelope_rms(sig, hop_out, m), hop_out, hop_in,
+                          int(audio.shape[1]), owner=slot_of_row)
     return sig, f0, units, volume
 
 
@@ -271,11 +281,11 @@ class GraphedBlock(_Captured):
     while the capture runs (the bank's row table is all padding then), or name in `keep`: tensors of the caller's that the
     capture's runs change in place and that are put back as they were found, like `window` (a gliding bank's clocks).  With
     w (S, Fr, K) in `mix_rows` the mix is one per FRAME, and `push` fills it (`ddsp_bank_glide`).  `model=None`: the features alone (`block_chain`), `sig` is None and there is no `noise`.  Static inputs: `block_in`, `noise`, `seed`; static outputs (valid until the
-    next replay): `sig`, `f0`, `units`, `volume`.  `tune`, `retrieve`: `block_chain`'s, the caller's device tensors, read at replay."""
+    next replay): `sig`, `f0`, `units`, `volume`.  `tune`, `retrieve`, `envelope`: `block_chain`'s, the caller's device tensors, read at replay."""
 
     def __init__(self, model, units_encoder, f0_extractor, window, block, samplerate, hop_size, silence_front, pitch,
                  threshold_db, spk_mix_dict=None, mix_rows=None, f0_dither=True, warmup=3, push=None, keep=(), formant=None,
-                 tune=None, retrieve=None):
+                 envelope=None, tune=None, retrieve=None):
         if mix_rows is not None and spk_mix_dict is not None:
             raise ValueError("GraphedBlock: mix_rows and spk_mix_dict are mutually exclusive")
         if mix_rows is not None and mix_rows[1].dim() == 3:          # a mix per FRAME: w (S, Fr, K), filled by `push`
@@ -288,7 +298,7 @@ class GraphedBlock(_Captured):
         self.device = dev
         self.units_encoder, self.f0_extractor, self.window, self.pitch = units_encoder, f0_extractor, window, pitch
         self.args = (samplerate, hop_size, silence_front, float(threshold_db))
-        self.f0_dither, self.push, self.tune, self.retrieve = bool(f0_dither), push, tune, retrieve
+        self.f0_dither, self.push, self.tune, self.retrieve, self.envelope = bool(f0_dither), push, tune, retrieve, envelope
         rows = window.shape[:-1]                                     # () or (S,)
         frames = int(window.shape[-1] // hop_size) + 1
         self.block_size = None if model is None else int(model.block_size)
@@ -309,7 +319,7 @@ class GraphedBlock(_Captured):
         samplerate, hop_size, silence_front, threshold_db = self.args
         return block_chain(self.ctx, self.model, self.units_encoder, self.f0_extractor, self.window, self.block_in, samplerate,
                            hop_size, silence_front, self.pitch, threshold_db, self.block_size, self.speaker, self.noise,
-                           self.f0_dither, self.seed, self.push, self.tune, self.retrieve)
+                           self.f0_dither, self.seed, self.push, envelope=self.envelope, tune=self.tune, retrieve=self.retrieve)
 
     @torch.no_grad()
     def __call__(self, block_in, spk_id=None, noise=None):

@@ -263,6 +263,9 @@ SIGNATURES = {
     "ddsp_units_retrieve": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _int,
                                    _vp, _i64, _vp, _vp]),
     "ddsp_units_retrieve_workspace": (_int, [_vp, _i64, _i64, _int, _i64, _vp]),
+    "ddsp_envelope_rms": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _int, _i64, _vp, _vp]),
+    "ddsp_envelope_apply": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
+                                   _i64, _vp, _vp, _vp, _i64]),
     "ddsp_units_index_norms": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "ddsp_units_kmeans_assign": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "ddsp_units_kmeans_update": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _i64]),
@@ -1795,6 +1798,120 @@ class Context:
                   _ptr(ratio_of_row), int(bank.off.numel()) - 1, _ptr(bank.off), _ptr(bank.vec), _ptr(bank.nrm), int(bank.vec.shape[0]), int(bank.n_max),
                   k, _ptr(ws), int(ws.numel()) * ws.element_size(), _ptr(nn_id), _ptr(nn_dist))
         return units
+
+    # -- the envelope mix ------------------------------------------------------------------------
+    @staticmethod
+    def _envelope_rows(name, x, counts, spans, n_max):
+        """The checks the two envelope calls share -> (form, R, width): x is the MATRIX form - fp32 (R, T) with counts (R,) int32
+        or None - or the SPANS form - fp64 (total,) with spans (R, 2) int64 and n_max, the longest count, a host int."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.numel() >= 1):
+            raise ValueError(f"{name}: the signal must be a contiguous, non-empty device tensor")
+
+        def on_device(t, dtype, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and \
+                t.device == x.device
+
+        if x.dtype == torch.float32 and x.dim() == 2:
+            if spans is not None or n_max is not None:
+                raise ValueError(f"{name}: an fp32 (R, T) matrix takes counts, not spans")
+            R, T = int(x.shape[0]), int(x.shape[1])
+            if counts is not None and not on_device(counts, torch.int32, (R,)):
+                raise ValueError(f"{name}: the counts must be a contiguous (R = {R},) int32 tensor on the signal's device")
+            form, width = "matrix", T
+        elif x.dtype == torch.float64 and x.dim() == 1:
+            if counts is not None:
+                raise ValueError(f"{name}: an fp64 tensor takes spans, not counts")
+            if not (isinstance(spans, torch.Tensor) and spans.dim() == 2 and on_device(spans, torch.int64, (spans.shape[0], 2))
+                    and spans.shape[0] >= 1):
+                raise ValueError(f"{name}: spans must be a contiguous (R, 2) int64 tensor of (base, count) on the signal's device")
+            if isinstance(n_max, bool) or not isinstance(n_max, int) or not 1 <= n_max <= x.numel():
+                raise ValueError(f"{name}: n_max, the longest span, must be an int in 1..{x.numel()}, got {n_max!r}")
+            form, R, width = "spans", int(spans.shape[0]), n_max
+        else:
+            raise ValueError(f"{name}: the signal must be an fp32 (R, T) matrix or an fp64 (total,) tensor with spans")
+        if not 1 <= R <= 65535:
+            raise ValueError(f"{name}: 1 to 65535 rows, got {R}")
+        return form, R, width
+
+    @staticmethod
+    def _envelope_hop(name, what, hop):
+        if isinstance(hop, bool) or not isinstance(hop, int) or not 1 <= hop <= 2 ** 27:
+            raise ValueError(f"{name}: {what} must be an int in 1..2**27, got {hop!r}")
+        return hop
+
+    def envelope_rms(self, x, hop, m=2, n_samples=None, spans=None, n_max=None):
+        """Frame RMS of ragged rows (`ddsp_envelope_rms`; include/ddsp_amd.h states the rule: librosa.feature.rms with
+        center=True, 'constant' padding, win = m * hop) -> env (R, N_max) fp64, N = 1 + n // hop frames per row and 0 behind them.
+        x: fp32 (R, T) with n_samples (R,) int32 device or None (N_max = 1 + T // hop), or fp64 (total,) with spans (R, 2) int64
+        device rows of (base, count) and n_max, the longest count as a host int (N_max = 1 + n_max // hop).  m: 2, 4, 6 or 8.
+        Shapes, dtypes, devices, m and hop are refused here, before the launch; a span that leaves the tensor or exceeds n_max
+        gets a zero envelope and raises ValueError from `poll_error()` or the next call that takes the error word."""
+        form, R, width = self._envelope_rows("envelope_rms", x, n_samples, spans, n_max)
+        hop = self._envelope_hop("envelope_rms", "hop", hop)
+        if isinstance(m, bool) or m not in (2, 4, 6, 8):
+            raise ValueError(f"envelope_rms: m must be 2, 4, 6 or 8 (win = m * hop), got {m!r}")
+        N_max = 1 + width // hop
+        blocks = torch.empty(R, N_max, dtype=torch.float64, device=x.device)
+        env = torch.empty(R, N_max, dtype=torch.float64, device=x.device)
+        if form == "matrix":
+            self.call("ddsp_envelope_rms", _ptr(x), width, _ptr(n_samples), None, 0, None, R, hop, m, N_max, _ptr(blocks), _ptr(env))
+        else:
+            self.call("ddsp_envelope_rms", None, 0, None, _ptr(x), int(x.numel()), _ptr(spans), R, hop, m, N_max, _ptr(blocks),
+                      _ptr(env))
+        return env
+
+    def envelope_mix_(self, out, src, rate, env_out, hop_out, hop_src, src_samples, n_out=None, spans=None, n_max=None,
+                      src_of_row=None, owner=None):
+        """The envelope mix (`ddsp_envelope_apply`; include/ddsp_amd.h states the rule, RVC's `change_rms`): in place on the rows
+        of `out`, out[t] *= e1^(1 - rate) * max(e2, 1e-6)^(rate - 1) with both envelopes interpolated to the row's length.
+        out: fp32 (R, T) with n_out (R,) int32 or None, or fp64 (total,) with spans (R, 2) int64 and n_max (`envelope_rms`'s forms);
+        env_out (R, >= 1 + width // hop_out) fp64: `envelope_rms` of `out` at hop_out; src (R_src, N_src) fp64: `envelope_rms` of
+        the SOURCE rows at hop_src; src_samples: the sources' counts, (R_src,) int32 device or one host int for all; src_of_row
+        (R,) int32 or None (row r's source is row r); rate (J,) fp64 device; owner (R,) int32 names the rate of every row (-1: a
+        padding row, left alone) or None (row r takes rate r).  Rows with rate == 1 keep their bits.  Shapes, dtypes, devices
+        and hops are refused here, before the launch; a bad rate, owner, source or span leaves its row and raises ValueError from
+        `poll_error()` or the next call that takes the error word.  -> out."""
+        form, R, width = self._envelope_rows("envelope_mix_", out, n_out, spans, n_max)
+        hop_out = self._envelope_hop("envelope_mix_", "hop_out", hop_out)
+        hop_src = self._envelope_hop("envelope_mix_", "hop_src", hop_src)
+
+        def on_device(t, dtype, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and \
+                t.device == out.device
+
+        if not (isinstance(env_out, torch.Tensor) and env_out.dim() == 2 and on_device(env_out, torch.float64, (R, env_out.shape[1]))
+                and env_out.shape[1] >= 1 + width // hop_out):
+            raise ValueError(f"envelope_mix_: env_out must be a contiguous (R = {R}, >= {1 + width // hop_out}) fp64 tensor on out's "
+                             f"device (`envelope_rms` of out at hop_out)")
+        if not (isinstance(src, torch.Tensor) and src.dim() == 2 and src.shape[0] >= 1 and src.shape[1] >= 1 and
+                on_device(src, torch.float64, tuple(src.shape))):
+            raise ValueError("envelope_mix_: src must be a contiguous (R_src, N_src) fp64 tensor on out's device (`envelope_rms` of "
+                             "the source rows at hop_src)")
+        R_src, N_src = int(src.shape[0]), int(src.shape[1])
+        if isinstance(src_samples, torch.Tensor):
+            if not on_device(src_samples, torch.int32, (R_src,)):
+                raise ValueError(f"envelope_mix_: src_samples must be a contiguous (R_src = {R_src},) int32 tensor on out's device")
+            n_src, n_src_all = src_samples, 0
+        else:
+            if isinstance(src_samples, bool) or not isinstance(src_samples, int) or src_samples < 1 or \
+                    1 + src_samples // hop_src > N_src:
+                raise ValueError(f"envelope_mix_: src_samples must be a device tensor of counts or an int >= 1 whose frames "
+                                 f"src holds, got {src_samples!r}")
+            n_src, n_src_all = None, src_samples
+        if not (isinstance(rate, torch.Tensor) and rate.dim() == 1 and rate.numel() >= 1 and
+                on_device(rate, torch.float64, tuple(rate.shape))):
+            raise ValueError("envelope_mix_: rate must be a contiguous (J,) fp64 tensor on out's device, J >= 1")
+        if src_of_row is not None and not on_device(src_of_row, torch.int32, (R,)):
+            raise ValueError(f"envelope_mix_: src_of_row must be a contiguous (R = {R},) int32 tensor on out's device")
+        if owner is not None and not on_device(owner, torch.int32, (R,)):
+            raise ValueError(f"envelope_mix_: owner must be a contiguous (R = {R},) int32 tensor on out's device")
+        tail = (R, width, _ptr(env_out), int(env_out.shape[1]), hop_out, _ptr(src), R_src, N_src, hop_src, _ptr(n_src), n_src_all,
+                _ptr(src_of_row), _ptr(owner), _ptr(rate), int(rate.numel()))
+        if form == "matrix":
+            self.call("ddsp_envelope_apply", None, 0, None, _ptr(out), width, _ptr(n_out), *tail)
+        else:
+            self.call("ddsp_envelope_apply", _ptr(out), int(out.numel()), _ptr(spans), None, 0, None, *tail)
+        return out
 
     @staticmethod
     def _kmeans_shapes(name, vec, cen, others):

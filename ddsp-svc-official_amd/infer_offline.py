@@ -733,7 +733,7 @@ class UnitIndexBank:
 
 def job_indices(jobs):
     """The retrieval setting of every job of a `job_table` call, in job order: (index_number, ratio) of a 7-tuple, else None."""
-    return [job[6] if len(job) == 7 else None for job in jobs]
+    return [job[6] if len(job) >= 7 else None for job in jobs]
 
 
 def index_tables(settings):
@@ -756,6 +756,54 @@ def check_job_index(who, setting, n_indices=None):
         bank = "" if n_indices is None else f" of the {n_indices} indices of the call"
         raise ValueError(f"{who}: index must be None or (index_number, ratio) with index_number >= 0{bank} and ratio in [0, 1], "
                          f"got {setting!r}")
+
+
+class EnvelopeMix:
+    """The envelope mix of a job (its eighth entry) or of a bank's slot: the converted output is held to the SOURCE's loudness
+    envelope - RVC's `rms_mix_rate` (`change_rms`), so-vits-svc's "loudness envelope adjustment"; include/ddsp_amd.h states the
+    rule at `ddsp_envelope_rms`.  rate in [0, 1]: the share of the output's OWN envelope that is kept - 1 changes nothing, 0
+    gives the output the source's envelope.  hop_seconds > 0: the distance of the RMS frames (RVC: half a second offline, 10 ms
+    live); frames: the window in hops, 2, 4, 6 or 8 (RVC: 2 offline, 4 live).  A silent source silences the output (the gain
+    is e1^(1 - rate) * e2^(rate - 1), and e1 is 0 there), as in RVC.  ValueError for anything else."""
+
+    def __init__(self, rate, hop_seconds=0.5, frames=2):
+        def real(x):
+            return isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x)
+        if not (real(rate) and 0 <= rate <= 1):
+            raise ValueError(f"EnvelopeMix: rate must be a number in [0, 1], got {rate!r}")
+        if not (real(hop_seconds) and hop_seconds > 0):
+            raise ValueError(f"EnvelopeMix: hop_seconds must be a finite number of seconds > 0, got {hop_seconds!r}")
+        if isinstance(frames, bool) or not isinstance(frames, numbers.Integral) or frames not in (2, 4, 6, 8):
+            raise ValueError(f"EnvelopeMix: frames must be 2, 4, 6 or 8 (the window in hops), got {frames!r}")
+        self.rate, self.hop_seconds, self.frames = float(rate), float(hop_seconds), int(frames)
+
+    def setting(self, sr):
+        """-> the hop in samples at `sr` Hz, int(sr * hop_seconds): RVC's sr // 2 at the default.  ValueError for a rate at
+        which the hop is no sample long."""
+        if not (isinstance(sr, numbers.Real) and not isinstance(sr, bool) and math.isfinite(sr) and sr > 0):
+            raise ValueError(f"EnvelopeMix.setting: sr must be a finite number of Hz > 0, got {sr!r}")
+        hop = int(sr * self.hop_seconds)
+        if not 1 <= hop <= 2 ** 27:
+            raise ValueError(f"EnvelopeMix.setting: a hop of {self.hop_seconds} s at {sr} Hz is {hop} samples, outside 1..2**27")
+        return hop
+
+
+def job_envelopes(jobs):
+    """The envelope mix of every job of a `job_table` call, in job order: the `EnvelopeMix` of an 8-tuple, else None."""
+    return [job[7] if len(job) >= 8 else None for job in jobs]
+
+
+def envelope_tables(envelopes):
+    """`job_envelopes`' list -> (rate (J,) fp64 CPU tensor - 1, which is off, for a job without one -, hop_seconds, frames),
+    the last two None when no job has one.  All jobs of a call share `hop_seconds` and `frames` (one RMS launch serves them)
+    and differ in `rate`: ValueError for two that disagree."""
+    given = [e for e in envelopes if e is not None]
+    shape = {(e.hop_seconds, e.frames) for e in given}
+    if len(shape) > 1:
+        raise ValueError(f"envelope_tables: the jobs of one call share hop_seconds and frames and differ in rate, got "
+                         f"{sorted(shape)}")
+    rate = torch.tensor([1.0 if e is None else e.rate for e in envelopes], dtype=torch.float64)
+    return (rate, *(next(iter(shape)) if shape else (None, None)))
 
 
 def _check_formant(j, formant, model):
@@ -796,7 +844,11 @@ def job_table(pieces, n_files, jobs, models, n_indices=None):
     A seventh entry is its UNIT RETRIEVAL, (index_number, ratio) or None (formant and tune may then be None too): the index of a
     `UnitIndexBank` and the blend ratio in [0, 1]; `job_indices(jobs)` lists it, `index_tables` makes its rows.  n_indices: the
     size of the call's bank where it is known (an index number at or past it is refused).
-    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4- to 7-tuple, an
+    An eighth entry is its ENVELOPE MIX, an `EnvelopeMix` (the three in front may be None; a job WITHOUT the control is the
+    shorter tuple - None in the eighth place is refused, as every 8-tuple was before the control -, and `EnvelopeMix(1.0)` is a
+    job that has it switched off): `job_envelopes(jobs)` lists it, None for the shorter jobs, `envelope_tables` makes its rates; the jobs of one call share its `hop_seconds` and `frames` and differ in `rate`.
+    ValueError - before any launch - names the first model that disagrees with models[0], a job that is no 4- to 8-tuple, an
+    envelope that is no `EnvelopeMix`, two envelopes of different hop or window, an
     index entry that is no (int >= 0, ratio in [0, 1]), a
     file or model index out of range, a speaker id outside [1, n_spk] of the JOB's model, a mix with no or too many speakers, a
     formant shift that is no finite number within +-24 semitones and no `FormantTimeline` that fits the model's frame rate, or
@@ -811,17 +863,28 @@ def job_table(pieces, n_files, jobs, models, n_indices=None):
             if a != b:
                 raise ValueError(f"job_table: models[{k}].{field} is {b}, models[0].{field} is {a}: the models of one call agree "
                                  f"in {', '.join(MODEL_FIELDS)}")
+    try:                                 # (the jobs of a call share the envelope's hop and window)
+        envelope_tables([job[7] if isinstance(job, (tuple, list)) and len(job) == 8 and isinstance(job[7], EnvelopeMix) else None
+                         for job in jobs])
+    except ValueError as e:
+        raise ValueError(f"job_table: {e}") from None
     per_file = [[i for i, row in enumerate(pieces) if row[0] == k] for k in range(int(n_files))]
     table = {"rows": [], "piece_of_row": [], "model_of_job": [], "speakers": [], "key_factor": [], "starts_per_job": [],
              "keys": []}
     for j, job in enumerate(jobs):
-        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5, 6, 7) and (len(job) < 6 or job[5] is None or
-                                                                                isinstance(job[5], PitchTune))):
+        # (an eighth entry is an EnvelopeMix itself: a job without one is the shorter tuple, and eight entries ending in None
+        # stay refused as before the envelope mix)
+        if not (isinstance(job, (tuple, list)) and len(job) in (4, 5, 6, 7, 8) and (len(job) < 6 or job[5] is None or
+                                                                                   isinstance(job[5], PitchTune)) and
+                (len(job) < 8 or job[7] is not None)):
             raise ValueError(f"job_table: job {j} must be (file, model_index, spk, key), (file, model_index, spk, key, formant) or "
                              f"(file, model_index, spk, key, formant, tune) with tune a PitchTune or None, or those six with "
-                             f"(index_number, ratio) or None behind them, got {job!r}")
-        if len(job) == 7:
+                             f"(index_number, ratio) or None behind them, or those seven with an EnvelopeMix behind them "
+                             f"(a job without one is the shorter tuple), got {job!r}")
+        if len(job) >= 7:
             check_job_index(f"job_table: job {j}", job[6], n_indices)
+        if len(job) == 8 and not isinstance(job[7], EnvelopeMix):
+            raise ValueError(f"job_table: job {j}: envelope must be an EnvelopeMix, got {job[7]!r}")
         file, m, spk, key = job[:4]
         if not (isinstance(file, numbers.Integral) and 0 <= file < int(n_files)):
             raise ValueError(f"job_table: job {j}: file {file!r} is outside the {int(n_files)} files of the call")
@@ -1272,6 +1335,12 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
     the group's frame counts, right where the encoder's units enter the synthesiser: the rows of a job without an index keep
     their bits.  Without an index among the jobs nothing is launched: the call above, bit for bit.  ValueError for an index
     among the jobs without `indices`, an index number outside the bank, or a bank whose width is not the units'.
+    A job may be an 8-tuple (file, model_index, spk, key, formant, tune, index, envelope): the ENVELOPE MIX, an `EnvelopeMix`
+    (a job without one is the shorter tuple; RVC's `rms_mix_rate`; include/ddsp_amd.h states the rule).  With an envelope among the jobs three launches follow
+    the stitch: the frame RMS of the files' audio, the frame RMS of the job spans of the stitched tensor - at the OUTPUT's rate,
+    the enhancer's when there is one - and the apply, in place, every job with its own rate and its file as the source.  The
+    span of a job without an envelope keeps its bits, the spans themselves do not move, and `to_pcm16` sees the matched
+    output.  Without an envelope among the jobs nothing is launched: the call above, bit for bit.
     noise: noise[j][i] is the draw of job j's slice i.  noise_seed: group g of `job_groups` - numbered model by model, in
     `models` order - draws with (noise_seed + g * 2**32) mod 2**64."""
     models = _models_of("render_jobs_device", None, models)
@@ -1308,6 +1377,14 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
         tabs = formant_tables(formants, _model_field(models[0], "sampling_rate"), _model_field(models[0], "block_size"))
         table["formant"] = ({table["model_of_job"][j] for j, f in enumerate(formants) if f is not None},
                             tuple(t.to(dev) for t in tabs), torch.ones_like(files["f0"]))
+
+    envelope = None
+    if J and any(e is not None for e in job_envelopes(jobs)):
+        if "audio" not in files:
+            raise ValueError("render_jobs_device: an envelope among the jobs needs the files' audio (`analyse_many`'s dict)")
+        rate, hop_seconds, frames = envelope_tables(job_envelopes(jobs))
+        EnvelopeMix(1.0, hop_seconds, frames).setting(files["sample_rate"])      # (a hop below one sample: refused here)
+        envelope = (rate.to(dev), hop_seconds, frames)
 
     tunes = job_tunes(jobs)
     if any(t is not None for t in tunes):
@@ -1349,10 +1426,36 @@ def render_jobs_device(models, args, files, jobs, threshold_db=-60, enhancer=Non
 
     def seed_of_group(g, starts):
         return (int(noise_seed) + (g << 32)) & ((1 << 64) - 1)
-    return _render_files(None, args, files, speaker, None if noise_seed is None else seed_of_group,
-                         None if noise is None else [x for per_job in noise for x in per_job], threshold_db=threshold_db,
-                         enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key, batch_frames=batch_frames,
-                         enhancer_batch_samples=enhancer_batch_samples, jobs=(models, table))
+    result, spans, sr_o = _render_files(None, args, files, speaker, None if noise_seed is None else seed_of_group,
+                                        None if noise is None else [x for per_job in noise for x in per_job],
+                                        threshold_db=threshold_db, enhancer=enhancer, enhancer_adaptive_key=enhancer_adaptive_key,
+                                        batch_frames=batch_frames, enhancer_batch_samples=enhancer_batch_samples,
+                                        jobs=(models, table))
+    if envelope is not None:
+        _envelope_mix_jobs(files, jobs, envelope, result, spans, sr_o)
+    return result, spans, sr_o
+
+
+def _envelope_mix_jobs(files, jobs, envelope, result, spans, sr_o):
+    """The envelope mix of a jobs call, in place on the stitched tensor: three launches behind the stitch.  One
+    `Context.envelope_rms` over the files' audio at the files' sample rate, one over the job spans of `result` at `sr_o` (the
+    enhancer's rate when there is one: the hop is taken from it), one `Context.envelope_mix_` with every job as the owner of
+    its span and the job's file as its source.  envelope: (`envelope_tables`' rates on the device, hop_seconds, frames)."""
+    rate, hop_seconds, frames = envelope
+    named = [j for j, (_, total) in enumerate(spans) if total >= 1]          # (a job over a file without a slice has no samples)
+    if not named:
+        return
+    dev = files["device"]
+    ctx = hipddsp.context_for(dev)
+    one = EnvelopeMix(1.0, hop_seconds, frames)
+    hop_in, hop_out = one.setting(files["sample_rate"]), one.setting(sr_o)
+    n_max = max(spans[j][1] for j in named)
+    table = torch.tensor([[spans[j][0], spans[j][1], j, jobs[j][0]] for j in named], dtype=torch.int64).to(dev)   # one upload
+    rows, owner, source = table[:, :2].contiguous(), table[:, 2].int(), table[:, 3].int()
+    src = ctx.envelope_rms(files["audio"], hop_in, frames, n_samples=files["n_samples_dev"])
+    env = ctx.envelope_rms(result, hop_out, frames, spans=rows, n_max=n_max)
+    ctx.envelope_mix_(result, src, rate, env, hop_out, hop_in, files["n_samples_dev"], spans=rows, n_max=n_max, src_of_row=source,
+                      owner=owner)
 
 
 @torch.no_grad()

@@ -26,6 +26,11 @@ path like `--formant_shift_key`, and with `--jobs` it is the tune of the entries
 `--index <file>` (an `infer_offline.UnitIndex.save` file; with `--index_ratio R`, default 0.5) blends every frame's units with
 their nearest stored units of that voice (`ddsp_units_retrieve`); it runs through the jobs path too, and with `--jobs` it is the
 index of the entries that name none - an entry names its own with `index: <file>` and `index_ratio: <0..1>`.
+`--rms_mix_rate R` (0..1, RVC's option of that name) holds the output to the source's loudness envelope: R is the share of the
+output's own envelope that is kept, 1 changes nothing (`infer_offline.EnvelopeMix`, RVC's `change_rms` behind the stitch).  It
+runs through the jobs path too, and with `--jobs` it is the envelope of the entries that name none - an entry names its own
+with `envelope: <rate>` or `envelope: {rate: <0..1>, hop_ms: <default 500>, frames: <2, 4, 6 or 8, default 2>}`; the entries of
+one run share hop_ms and frames.
 
 The options and their defaults are the reference's (`main.py:19-31`).  What differs, and why:
   * the key shift is applied once (the reference applies it twice, SURVEY 0.3);
@@ -77,6 +82,8 @@ def parse_args(args=None, namespace=None):
     parser.add_argument("--tune_a4", type=str, default=argparse.SUPPRESS, help="the Hz of A4 | default: 440")
     parser.add_argument("--index", type=str, default=argparse.SUPPRESS, help="unit retrieval: a UnitIndex file of the target voice")
     parser.add_argument("--index_ratio", type=str, default=argparse.SUPPRESS, help="share of the retrieved units, 0..1 | default: 0.5")
+    parser.add_argument("--rms_mix_rate", type=str, default=argparse.SUPPRESS, help="envelope mix: the share of the output's own "
+                        "loudness envelope that is kept, 0..1; 0 gives it the source's | default: off (1)")
     parser.add_argument("--jobs", type=str, default=argparse.SUPPRESS, help="YAML list of {model, id | mix, key, suffix}: every entry is applied "
                         "to every .wav of the input folder")
     return parser.parse_args(args=args, namespace=namespace)
@@ -139,7 +146,8 @@ def run(cmd, units_encoder=None, f0_extractor=None, enhancer=None, device="cuda"
             raise ValueError("--jobs goes with a folder as -i (and a folder as -o)")
         return _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                          enhancer_batch_samples, units_batch_samples)
-    if float(getattr(cmd, "formant_shift_key", 0)) != 0 or _cmd_tune(cmd) is not None or getattr(cmd, "index", None) is not None:
+    if float(getattr(cmd, "formant_shift_key", 0)) != 0 or _cmd_tune(cmd) is not None or getattr(cmd, "index", None) is not None or \
+            _cmd_envelope(cmd) is not None:
         return _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames,
                             enhancer_batch_samples, units_batch_samples)
     if os.path.isdir(cmd.input):
@@ -183,7 +191,7 @@ def _run_folder(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhan
 
 def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhancer, device, batch_frames, enhancer_batch_samples,
                  units_batch_samples):
-    """`run` with `--formant_shift_key S`, `--tune_scale` or `--index` and no `--jobs`: the file, or every `.wav` of the folder, as one job
+    """`run` with `--formant_shift_key S`, `--tune_scale`, `--index` or `--rms_mix_rate` and no `--jobs`: the file, or every `.wav` of the folder, as one job
     each - `-id` or `-mix`, `-k`, the shift and the tune - through ONE `infer_offline.convert_many_device(jobs=...)`; outputs as `run` names them."""
     from infer_offline import convert_many_device
     folder = os.path.isdir(cmd.input)
@@ -194,7 +202,7 @@ def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enha
     files = _IndexFiles(device)
     index = files.setting("--index", getattr(cmd, "index", None), getattr(cmd, "index_ratio", 0.5))
     jobs = [_job_tuple(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), shift if shift != 0 else None, tune, index,
-                       at_least=5) for k in range(len(names))]
+                       at_least=5, envelope=_cmd_envelope(cmd)) for k in range(len(names))]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=[model], batch_frames=batch_frames,
         indices=files.bank(),
@@ -233,13 +241,13 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
         index = files.setting(f"--jobs: entry {n}", e.get("index", getattr(cmd, "index", None)),
                               e.get("index_ratio", getattr(cmd, "index_ratio", 0.5)))
         voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift), _job_tune(n, e, _cmd_tune(cmd)),
-                       index))
+                       index, _job_envelope(n, e, _cmd_envelope(cmd))))
     if len({v[3] for v in voices}) != len(voices):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
     audios = [load(os.path.join(cmd.input, n)) for n in names]
-    jobs = [_job_tuple(k, m, spk, key, formant, tune, index)
-            for k in range(len(names)) for m, spk, key, _, formant, tune, index in voices]
+    jobs = [_job_tuple(k, m, spk, key, formant, tune, index, envelope=envelope)
+            for k in range(len(names)) for m, spk, key, _, formant, tune, index, envelope in voices]
     out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{v[3]}.wav") for name in names for v in voices]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=models, batch_frames=batch_frames,
@@ -252,11 +260,12 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
     return result, sr_o
 
 
-def _job_tuple(file, model, spk, key, formant=None, tune=None, index=None, at_least=4):
+def _job_tuple(file, model, spk, key, formant=None, tune=None, index=None, at_least=4, envelope=None):
     """A job as `infer_offline.job_table` takes it, as short as what it carries allows: four entries, a fifth with a formant,
-    a sixth with a tune, a seventh with an index (the entries in front of the last one given may be None); `at_least` entries."""
-    job = (file, model, spk, key, formant, tune, index)
-    n = 7 if index is not None else 6 if tune is not None else 5 if formant is not None else 4
+    a sixth with a tune, a seventh with an index, an eighth with an envelope (the entries in front of the last one given may be
+    None); `at_least` entries."""
+    job = (file, model, spk, key, formant, tune, index, envelope)
+    n = 8 if envelope is not None else 7 if index is not None else 6 if tune is not None else 5 if formant is not None else 4
     return job[:max(n, at_least)]
 
 
@@ -290,7 +299,7 @@ def _job_entry(n, e):
     `timeline` (at most one of them; default id 1), the key from `key` or `key_timeline` (not both; default 0).  ValueError for an
     unknown field, two speakers, two keys or a missing suffix."""
     unknown = set(e) - {"model", "id", "mix", "timeline", "key", "key_timeline", "formant", "formant_timeline", "tune", "index",
-                        "index_ratio", "suffix"}
+                        "index_ratio", "envelope", "suffix"}
     if unknown or sum(k in e for k in ("id", "mix", "timeline")) > 1 or ("key" in e and "key_timeline" in e) or \
             not str(e.get("suffix", "")):
         raise ValueError(f"--jobs: entry {n} takes model, id or mix or timeline, key or key_timeline and a non-empty suffix, "
@@ -341,6 +350,37 @@ def _job_tune(n, e, default=None):
     if not (isinstance(t, dict) and set(t) <= {"scale", "notes", "strength", "retune_ms", "a4"}):
         raise ValueError(f"--jobs: entry {n}: tune is {{scale | notes, strength, retune_ms, a4}}, got {t!r}")
     return _tune(f"--jobs: entry {n}", **t)
+
+
+def _envelope(where, rate, hop_ms=500.0, frames=2):
+    """`infer_offline.EnvelopeMix` from a rate, the hop in milliseconds and the window in hops."""
+    from infer_offline import EnvelopeMix
+    try:
+        return EnvelopeMix(float(rate), float(hop_ms) / 1000.0, frames)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{where}: {e}") from None
+
+
+def _cmd_envelope(cmd):
+    """`--rms_mix_rate R` -> an EnvelopeMix at RVC's offline hop and window, None without the option."""
+    if getattr(cmd, "rms_mix_rate", None) is None:
+        return None
+    return _envelope("--rms_mix_rate", cmd.rms_mix_rate)
+
+
+def _job_envelope(n, e, default=None):
+    """Entry n's envelope mix as a job's eighth entry: `envelope: <rate>` or `envelope: {rate, hop_ms, frames}`, else `default`
+    (`--rms_mix_rate`)."""
+    if "envelope" not in e:
+        return default
+    v = e["envelope"]
+    if isinstance(v, dict):
+        if "rate" not in v or not set(v) <= {"rate", "hop_ms", "frames"}:
+            raise ValueError(f"--jobs: entry {n}: envelope is a rate or {{rate, hop_ms, frames}}, got {v!r}")
+        return _envelope(f"--jobs: entry {n}", **v)
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(f"--jobs: entry {n}: envelope is a rate or {{rate, hop_ms, frames}}, got {v!r}")
+    return _envelope(f"--jobs: entry {n}", v)
 
 
 def _timeline(n, points):

@@ -475,6 +475,14 @@ class _Rows:
         return None if b.indices is None else (b.indices, b.index_of_slot, b.ratio_of_slot, b.retrieve_k, self.rows)
 
     @property
+    def envelope_term(self):
+        """The envelope-mix term of this instance's chain (`graphed.block_chain`'s `envelope`): None on a bank without
+        `envelope`; the slots' rates, the two hops and the window, with the width's row table as the owner of every row on a
+        compact instance (a padding row has none)."""
+        b = self.bank
+        return None if b.rate_of_slot is None else (b.rate_of_slot, *b.envelope_setting, self.rows)
+
+    @property
     def pitch_term(self):
         """The pitch term of this instance's chain: a factor per row, or per frame on a bank with `pitch_breakpoints`."""
         return self.pitch if self.pitch_frames is None else self.pitch_frames
@@ -647,7 +655,22 @@ class StreamBank:
     a bank of indices on another device or of another unit width than the encoder's.  `push_block` takes the caller's units
     as they are.
 
-    Not in the bank: a formant shift on a bank with `models=`, or one that moves along a timeline; streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
+    Envelope mix per slot (`envelope=True`, `envelope_hop_seconds`, `envelope_frames`; the default False allocates, captures and
+    launches nothing of this, and the bank is the bank above, bit for bit).  RVC's `rms_mix_rate` in its real-time form: the
+    rendered signal is held to the loudness envelope of the slot's INPUT window (include/ddsp_amd.h states the rule at
+    `ddsp_envelope_rms`), frames `envelope_hop_seconds` apart (RVC: 10 ms) with a window of `envelope_frames` hops (RVC: 4).
+    Every slot has a row of `rate_of_slot` (S,) fp64, 1 at first, which is off; `set_envelope(slot, rate | None)` writes it
+    and `reset(slot)` switches the slot off: a device row only, `graph_builds` stays what it was.  Every `push_audio` chain of
+    such a bank runs three calls right behind the gate - the frame RMS of the windows at the device rate, the frame RMS of the
+    gated signal at the model's rate, the apply in place - inside the captured block and on the eager path alike, at a compact
+    width with the width's row table as the owner of every row.  A slot whose rate is 1 is selected around: with every slot off
+    the bank emits the bits of a bank without the feature.  The kernels only read the slots' rows, so a paused slot keeps its
+    rate.  It works with `active_widths`, `tune`, `indices`, the glides, `formant` and the enhancer.  DIVERGENCE: the enhancer
+    stage FOLLOWS the matched signal (RVC and the offline jobs match the final output); a silent input window silences the
+    slot, as in RVC.  Refused: `envelope=True` with `models=` (the signal is rendered per model, behind the block), or on a bank
+    without analysers (`push_block`); `set_envelope` on a bank without it.
+
+    Not in the bank: an envelope mix on a bank with `models=`; a formant shift on a bank with `models=`, or one that moves along a timeline; streams of different geometry; models of different sampling rate, block size or unit width; a ladder that
     grows after construction; a weight set per row inside the control network's kernels; an enhancer per model; a glide on a
     bank with `models=`."""
 
@@ -655,7 +678,8 @@ class StreamBank:
                  use_graph=True, use_phase_vocoder=False, units_encoder=None, f0_extractor=None, f0_min=50, f0_max=1100,
                  f0_dither=True, crepe_ckpt=None, max_mix=4, enhancer=None, enhancer_adaptive_key="auto", enhancer_max_key=12,
                  active_widths=None, models=None, model_widths=None, glide_breakpoints=None, pitch_breakpoints=None,
-                 formant=False, tune=False, indices=None, retrieve_k=8):
+                 formant=False, tune=False, indices=None, retrieve_k=8, envelope=False, envelope_hop_seconds=0.01,
+                 envelope_frames=4):
         # every refusal comes before anything is allocated or launched on the device
         self.S = int(n_streams)
         if self.S < 1:
@@ -682,6 +706,22 @@ class StreamBank:
             n_unit = _model_field(models[0] if model is None and isinstance(models, (tuple, list)) and models else model, "n_unit")
             if indices.channels != n_unit:
                 raise ValueError(f"StreamBank: the indices hold units of {indices.channels} channels, the model takes {n_unit}")
+        if not isinstance(envelope, bool):
+            raise ValueError(f"StreamBank: envelope must be True or False, got {envelope!r}")
+        self.envelope_setting = None
+        if envelope:
+            if models is not None:
+                raise ValueError("StreamBank: envelope=True with models= is not supported (the signal is rendered per model, "
+                                 "behind the block that holds the envelope mix)")
+            if units_encoder is None or f0_extractor is None:
+                raise ValueError("StreamBank: envelope=True needs units_encoder= and f0_extractor= (the mix runs in push_audio's "
+                                 "block)")
+            from infer_offline import EnvelopeMix
+            try:
+                one = EnvelopeMix(1.0, envelope_hop_seconds, envelope_frames)
+                self.envelope_setting = (one.setting(samplerate), one.setting(_model_field(model, "sampling_rate")), one.frames)
+            except ValueError as e:
+                raise ValueError(f"StreamBank: {e}") from None
         if formant and models is not None:
             raise ValueError("StreamBank: formant=True with models= is not supported (the per-model row mover indexes the call's "
                              "rows, the formant row is indexed by slot)")
@@ -765,6 +805,8 @@ class StreamBank:
             self.index_of_slot = torch.full((self.S,), -1, dtype=torch.int32, device=dev)
             self.ratio_of_slot = torch.zeros(self.S, dtype=torch.float32, device=dev)
             indices.reserve(self.S, self.frames, self.retrieve_k)    # (an allocation: in front of every capture)
+        # the envelope mix: a rate per slot (`set_envelope`), 1: off
+        self.rate_of_slot = torch.ones(self.S, dtype=torch.float64, device=dev) if envelope else None
         self._resamplers = {}
         self.last_f0 = self.last_units = self.last_volume = self.last_shift = self.last_signal = self.last_key = None
         self.last_mix_w = None           # (A, Fr, max_mix): the block's per-frame weights on a bank with `glide_breakpoints`
@@ -810,7 +852,8 @@ class StreamBank:
                 keep=[c for c in (self.glide_clock, self.key_clock) if c is not None],   # (the capture's runs advance the clocks)
                 **({} if self.formant is None else {"formant": rows.formant_term}),
                 **({} if self.tune_mask is None else {"tune": rows.tune_term}),
-                **({} if self.indices is None else {"retrieve": rows.retrieve_term}))
+                **({} if self.indices is None else {"retrieve": rows.retrieve_term}),
+                **({} if self.rate_of_slot is None else {"envelope": rows.envelope_term}))
         elif shared:
             rows.graph = graphed.GraphedSynth(self.model, rows.W, self.frames, spk_mix_rows=rows.mix,
                                               **({} if self.formant is None else {"formant": rows.formant_term}))
@@ -963,6 +1006,21 @@ class StreamBank:
         self.tune_mask[slot:slot + 1].fill_(mask)
         self.tune_param[slot:slot + 1].copy_(torch.tensor([param], dtype=torch.float64))
 
+    def set_envelope(self, slot, rate):
+        """Slot `slot`'s output keeps the share `rate` in [0, 1] of its own loudness envelope and takes the rest from its input's
+        from the next block on (RVC's `rms_mix_rate`); None - or 1 - switches it off: one write to the slot's row of
+        `rate_of_slot`, no capture.  ValueError on a bank built without `envelope=True`, or for a rate outside [0, 1]."""
+        if self.rate_of_slot is None:
+            raise ValueError("StreamBank.set_envelope: this bank was built without envelope=True")
+        if rate is not None:
+            from infer_offline import EnvelopeMix
+            try:
+                rate = EnvelopeMix(rate).rate
+            except ValueError as e:
+                raise ValueError(f"StreamBank.set_envelope: {e}") from None
+        slot = self._slot(slot)
+        self.rate_of_slot[slot:slot + 1].fill_(1.0 if rate is None else rate)
+
     def set_index(self, slot, index, ratio=0.5):
         """Slot `slot`'s units are blended with their nearest stored units of index number `index` of the bank's `indices`
         from the next block on, at `ratio` in [0, 1]; None switches it off: one write to the slot's rows of `index_of_slot` and
@@ -1024,7 +1082,7 @@ class StreamBank:
         a bank with `glide_breakpoints` the slot's clock is zeroed too and its timeline stays: the glide starts from its beginning;
         on one with `pitch_breakpoints` the key clock and the key timeline likewise.  On a bank with `formant` the slot's formant
         factor goes back to 1, on one with `tune` the slot's pitch correction is switched off, on one with `indices` its
-        unit retrieval."""
+        unit retrieval, on one with `envelope` its envelope mix."""
         slot = self._slot(slot)
         self.windows[slot].zero_()
         self.sola_buffer[slot].zero_()
@@ -1039,6 +1097,8 @@ class StreamBank:
         if self.indices is not None:
             self.index_of_slot[slot:slot + 1].fill_(-1)
             self.ratio_of_slot[slot:slot + 1].zero_()
+        if self.rate_of_slot is not None:
+            self.rate_of_slot[slot:slot + 1].fill_(1.0)
 
     def _check_blocks(self, blocks, A, rows="S"):
         if not isinstance(blocks, torch.Tensor) or tuple(blocks.shape) != (A, self.block):
@@ -1118,7 +1178,8 @@ class StreamBank:
                 self.threshold_db, self.hop,
                 {"spk_id": None, "spk_mix_rows": rows.mix, **({} if self.formant is None else {"formant": rows.formant_term})},
                 noise, self.f0_dither, push=rows.push, **({} if self.tune_mask is None else {"tune": rows.tune_term}),
-                **({} if self.indices is None else {"retrieve": rows.retrieve_term}))
+                **({} if self.indices is None else {"retrieve": rows.retrieve_term}),
+                **({} if self.rate_of_slot is None else {"envelope": rows.envelope_term}))
         if self._model_rows is not None:
             sig = self._render_models(rows, active, units, f0, volume, noise)
         self.last_f0, self.last_units, self.last_volume = rows.real(f0, units, volume)

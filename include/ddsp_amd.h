@@ -621,6 +621,64 @@ int ddsp_units_kmeans_assign(ddsp_ctx* ctx, void* stream, const float* vec, int6
 int ddsp_units_kmeans_update(ddsp_ctx* ctx, void* stream, const float* vec, int64_t N, int64_t C, const int32_t* assign,
                              int64_t K, int shift, float* cen, int32_t* count, void* workspace, int64_t workspace_bytes);
 
+/* ENVELOPE MIX: the converted output is held to the SOURCE's loudness envelope (`infer_offline.EnvelopeMix`, a job's eighth
+ * entry, realtime.StreamBank(envelope=True)).  Not a definition of this project: it restates RVC's
+ * `change_rms(data1, sr1, data2, sr2, rate)` (its `rms_mix_rate`; so-vits-svc's "loudness envelope adjustment"), eight lines of
+ * librosa and torch.  data1 is the source, data2 the converted output, rate in [0, 1] the share of the OUTPUT's own envelope
+ * that is kept: 1 leaves the output as it is, 0 gives it the source's envelope.  tests/envelope_cases.py is the same in numpy fp64.
+ * THE RULE, all in fp64, one rounding per operation as written, nothing contracted:
+ *   1. FRAME RMS as librosa.feature.rms documents it with center=True: a row of n samples has N = 1 + n / hop frames (integer
+ *      division); frame i covers [i * hop - win / 2, i * hop + win / 2), samples outside [0, n) count as 0 ('constant' padding);
+ *      rms[i] = sqrt(sum x^2 / win).  win = m * hop with m even, 2 <= m <= 8: RVC's offline frame_length = sr / 2 * 2,
+ *      hop_length = sr / 2 is m = 2, hop = sr / 2; its real-time path is hop = sr / 100, m = 4.  The squares of an fp32 source
+ *      are exact in fp64.
+ *   2. LINEAR INTERPOLATION to the output's length n2, as F.interpolate(mode="linear", align_corners=False) does, of BOTH
+ *      envelopes - the source's from its own n1, hop1, N1, the output's from n2, hop2, N2.  For output sample t:
+ *          x = max((t + 0.5) * N / n2 - 0.5, 0);  i0 = min(floor(x), N - 1);  i1 = min(i0 + 1, N - 1);  lam = x - i0
+ *          e = (1 - lam) * env[i0] + lam * env[i1]
+ *   3. GAIN: e2 = max(e2, 1e-6) behind the interpolation, as RVC has it; g = e1^(1 - rate) * e2^(rate - 1);
+ *      out[t] = data2[t] * g.
+ * Nothing is added: no smoothing, no cap on the gain (a quiet output frame under a loud source frame is raised by up to
+ * (e1 * 1e6)^(1 - rate)).  e1 == 0 with rate < 1 gives a gain of exactly 0: a SILENT SOURCE SILENCES THE OUTPUT, as in RVC.
+ *
+ * THE ROWS of both calls come in one of two forms.  MATRIX: an fp32 matrix (R, T) with counts n (R) int32 DEVICE or NULL (T for
+ * every row); a count is held inside [0, T].  SPANS: an fp64 tensor of `total` elements with a DEVICE table spans (R, 2) int64
+ * of (base, count) per row - the job spans of a stitched tensor.  A span with base < 0, count < 1 or base + count > total, or
+ * with more samples than the call's width (N_max frames, n_max samples) is refused on the device: the error word is raised,
+ * nothing of it is read or written (its envelope is 0).  Exactly one of the two data pointers is non-NULL.  R <= 65535.
+ *
+ * ddsp_envelope_rms: env (R, N_max) fp64 = the frame RMS of every row, 0 at and behind frame N of a row; blocks (R, N_max) fp64
+ * is the caller's workspace.  MATRIX needs N_max >= 1 + T / hop.  Two kernels, no allocation: win = m * hop, so a frame is the
+ * sum of m consecutive hop-blocks [k * hop, (k + 1) * hop); the first kernel forms one fp64 sum of squares per (row, block) with
+ * every sample read from memory once - 16-byte loads wherever the whole vector lies inside the block at an aligned address, a
+ * bounds select at its ends; the padding behind a count and between spans is never read -, the second sums the m blocks of a
+ * frame in ascending order.  From hop >= 2048 a workgroup strides one block, below a wave does and a workgroup takes 16 blocks.
+ * The order of every sum is fixed by that shape (strided terms per lane, a shuffle butterfly, a tree over the waves; no
+ * floating-point atomics): the same input gives the same bits on every run.  It differs from numpy's pairwise order by at most
+ * terms * 2^-53 relative.
+ *
+ * ddsp_envelope_apply: in place on the output rows (y64 with spans, or y32 (R, T) with n_out), steps 2 and 3.  env_out
+ * (R, N_out_max) and env_src (R_src, N_src_max) are ddsp_envelope_rms results at hop_out and hop_src; N_out_max >= 1 + n_max /
+ * hop_out, n_max the longest output row (T for MATRIX).  The source of row r is src_of_row[r] (int32) or r; its count n1 is
+ * n_src[source] (int32) or n_src_all for NULL; its frames N1 = 1 + n1 / hop_src are held to N_src_max.  The rate of row r is
+ * rate[owner[r]] (fp64, J of them; owner int32) or rate[r] for owner == NULL - a job offline, a slot live.
+ * UNTOUCHED, by selection and not by arithmetic, so their bits stay: rows whose rate is exactly 1 (0^0 is never formed); rows
+ * whose owner is -1 (padding: no error); elements outside every span or behind a row's count.
+ * REFUSED on the device - the row keeps its bits, the error word is raised (DDSP_ERR_ARG from the next call that takes it, or
+ * ddsp_ctx_poll_error), the other rows are done -: a rate that is not finite or outside [0, 1]; an owner other than -1 outside
+ * [0, J); a source row outside [0, R_src); n1 < 1; a bad span.  Every row index, base and count is tested before it forms an
+ * address.  An element reads its one or two entries of each envelope from memory (a few KB per row, shared by the lanes of a
+ * wave: they stay in the cache; nothing is staged in the LDS).
+ * Both: DDSP_ERR_ARG, and nothing launched, for a null pointer, both or neither data pointer, a hop outside [1, 2^27], an m
+ * other than 2, 4, 6, 8 or widths that do not fit.  They do not synchronise, allocate or read back; graph-capturable. */
+int ddsp_envelope_rms(ddsp_ctx* ctx, void* stream, const float* x32, int64_t T, const int32_t* n_samples, const double* x64,
+                      int64_t total, const int64_t* spans, int64_t R, int64_t hop, int m, int64_t N_max, double* blocks,
+                      double* env);
+int ddsp_envelope_apply(ddsp_ctx* ctx, void* stream, double* y64, int64_t total, const int64_t* spans, float* y32, int64_t T,
+                        const int32_t* n_out, int64_t R, int64_t n_max, const double* env_out, int64_t N_out_max, int64_t hop_out,
+                        const double* env_src, int64_t R_src, int64_t N_src_max, int64_t hop_src, const int32_t* n_src,
+                        int64_t n_src_all, const int32_t* src_of_row, const int32_t* owner, const double* rate, int64_t J);
+
 /* The row movers of a bank with a model per slot (realtime.StreamBank, `models=`): the analysis of a call runs once over its row
  * batch of R rows, then every model renders its own rows as a compact batch of W rows.  rows (W) int32 DEVICE, read when the
  * kernels run: entry r is the row OF THE CALL'S BATCH (not a slot) behind compact row r.  An entry is tested against [0, R)
