@@ -10,6 +10,8 @@ centre in the last iteration."""
 import argparse
 import sys
 
+from controls import UnitIndex
+
 
 def parse_args(args=None):
     parser = argparse.ArgumentParser(description="unit index of a voice for main.py --index, reduced to k-means centres")
@@ -30,7 +32,6 @@ def parse_args(args=None):
 
 def build(cmd):
     """-> (the index written to cmd.output, entries in, the reduction's report)."""
-    from infer_offline import UnitIndex
     full = UnitIndex.from_units_dir(cmd.input, spk=cmd.spk, max_entries=cmd.max_entries)
     index, report = full.reduce(cmd.centres, iters=cmd.iters, device=cmd.device, report=True)
     index.save(cmd.output)

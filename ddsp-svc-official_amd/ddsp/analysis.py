@@ -378,6 +378,18 @@ def check_units_width(name, units_encoder, *models):
                              f"and the model was built for n_unit = {int(n_unit)} (config: encoder_out_channels)")
 
 
+MODEL_FIELDS = ("sampling_rate", "block_size", "n_unit", "device")      # what the models of one call, or of one bank, agree in
+
+
+def _model_field(model, field):
+    if field == "n_unit":
+        return int(model.unit2ctrl.n_unit)
+    if field == "device":
+        return next(model.parameters()).device
+    host = getattr(model, {"sampling_rate": "_sr", "block_size": "_hop"}[field], None)   # (the synthesisers' host copies:
+    return int(getattr(model, field) if host is None else host)                          # the buffers would be read back)
+
+
 class Units_Encoder:
     """Reference `ddsp/vocoder.py:140-211` for `encoder='hubertsoft'`: resampling to the encoder's rate (`ddsp_resample`,
     lowpass_filter_width=128, as the reference's torchaudio Resample), the encoder and the nearest-frame alignment

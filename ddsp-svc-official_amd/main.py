@@ -43,11 +43,15 @@ The options and their defaults are the reference's (`main.py:19-31`).  What diff
   * the reference's md5-keyed f0 cache is left out: the f0 of a file takes milliseconds on the device.
 """
 import argparse
+import dataclasses
 import os
 from ast import literal_eval
 
 import numpy as np
 import torch
+
+from controls import (EnvelopeMix, FormantTimeline, Job, KeyTimeline, PitchTune, SpeakerTimeline, UnitIndex, UnitIndexBank,
+                      check_job_index)
 
 # option, long name, type, default, help - the reference's table
 _OPTIONS = (
@@ -201,8 +205,8 @@ def _run_formant(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enha
     shift, tune = float(getattr(cmd, "formant_shift_key", 0)), _cmd_tune(cmd)
     files = _IndexFiles(device)
     index = files.setting("--index", getattr(cmd, "index", None), getattr(cmd, "index_ratio", 0.5))
-    jobs = [_job_tuple(k, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key), shift if shift != 0 else None, tune, index,
-                       at_least=5, envelope=_cmd_envelope(cmd)) for k in range(len(names))]
+    jobs = _file_jobs(len(names), [Job(None, 0, int(cmd.spk_id) if mix is None else mix, float(cmd.key),
+                                       shift if shift != 0 else None, tune, index, _cmd_envelope(cmd))])
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=[model], batch_frames=batch_frames,
         indices=files.bank(),
@@ -229,7 +233,7 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
         entries = yaml.safe_load(fh)
     if not (isinstance(entries, list) and entries and all(isinstance(e, dict) for e in entries)):
         raise ValueError(f"--jobs: {cmd.jobs} must hold a non-empty list of {{model, id | mix, key, suffix}} entries")
-    paths, models, voices = [os.path.abspath(cmd.model_path)], [model], []
+    paths, models, voices, suffixes = [os.path.abspath(cmd.model_path)], [model], [], []
     shift = float(getattr(cmd, "formant_shift_key", 0))          # the shift of the entries that name none
     files = _IndexFiles(device)
     for n, e in enumerate(entries):
@@ -240,15 +244,15 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
             models.append(load_model(path, device=device)[0])
         index = files.setting(f"--jobs: entry {n}", e.get("index", getattr(cmd, "index", None)),
                               e.get("index_ratio", getattr(cmd, "index_ratio", 0.5)))
-        voices.append((paths.index(path), spk, key, str(e["suffix"]), _job_formant(n, e, shift), _job_tune(n, e, _cmd_tune(cmd)),
-                       index, _job_envelope(n, e, _cmd_envelope(cmd))))
-    if len({v[3] for v in voices}) != len(voices):
+        suffixes.append(str(e["suffix"]))
+        voices.append(Job(None, paths.index(path), spk, key, _job_formant(n, e, shift), _job_tune(n, e, _cmd_tune(cmd)), index,
+                          _job_envelope(n, e, _cmd_envelope(cmd))))
+    if len(set(suffixes)) != len(suffixes):
         raise ValueError("--jobs: two entries share a suffix, so they would write the same files")
     names = sorted(n for n in os.listdir(cmd.input) if n.lower().endswith(".wav"))
     audios = [load(os.path.join(cmd.input, n)) for n in names]
-    jobs = [_job_tuple(k, m, spk, key, formant, tune, index, envelope=envelope)
-            for k in range(len(names)) for m, spk, key, _, formant, tune, index, envelope in voices]
-    out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{v[3]}.wav") for name in names for v in voices]
+    jobs = _file_jobs(len(names), voices)
+    out_paths = [os.path.join(cmd.output, f"{os.path.splitext(name)[0]}_{suffix}.wav") for name in names for suffix in suffixes]
     result, spans, sr_o = convert_many_device(
         None, args, audios, sr_i, units_encoder, f0_extractor, jobs=jobs, models=models, batch_frames=batch_frames,
         indices=files.bank(),
@@ -260,13 +264,9 @@ def _run_jobs(cmd, model, args, load, sr_i, units_encoder, f0_extractor, enhance
     return result, sr_o
 
 
-def _job_tuple(file, model, spk, key, formant=None, tune=None, index=None, at_least=4, envelope=None):
-    """A job as `infer_offline.job_table` takes it, as short as what it carries allows: four entries, a fifth with a formant,
-    a sixth with a tune, a seventh with an index, an eighth with an envelope (the entries in front of the last one given may be
-    None); `at_least` entries."""
-    job = (file, model, spk, key, formant, tune, index, envelope)
-    n = 8 if envelope is not None else 7 if index is not None else 6 if tune is not None else 5 if formant is not None else 4
-    return job[:max(n, at_least)]
+def _file_jobs(n_files, voices):
+    """Every voice - a `Job` whose file is still None - applied to every file -> the jobs, file after file and voice after voice."""
+    return [dataclasses.replace(voice, file=k) for k in range(n_files) for voice in voices]
 
 
 class _IndexFiles:
@@ -280,7 +280,6 @@ class _IndexFiles:
         """-> a job's seventh entry (index_number, ratio), None without a file."""
         if path is None:
             return None
-        from infer_offline import UnitIndex, check_job_index
         path = os.path.abspath(str(path))
         if path not in self.paths:
             self.indices.append(UnitIndex.load(path))
@@ -290,7 +289,6 @@ class _IndexFiles:
         return setting
 
     def bank(self):
-        from infer_offline import UnitIndexBank
         return UnitIndexBank(self.indices, device=self.device) if self.indices else None
 
 
@@ -312,7 +310,6 @@ def _job_entry(n, e):
 def _job_formant(n, e, default=0.0):
     """Entry n's formant shift as a job's fifth entry: `formant: <semitones>`, `formant_timeline: [{at: <seconds>, formant:
     <semitones>}, ...]` (`infer_offline.FormantTimeline`) - not both -, else `default` (`--formant_shift_key`); None for no shift."""
-    from infer_offline import FormantTimeline
     if "formant" in e and "formant_timeline" in e:
         raise ValueError(f"--jobs: entry {n} takes formant or formant_timeline, not both, got {e!r}")
     if "formant_timeline" in e:
@@ -326,7 +323,6 @@ def _job_formant(n, e, default=0.0):
 
 def _tune(where, scale=None, notes=None, strength=1.0, retune_ms=50.0, a4=440.0):
     """`infer_offline.PitchTune` from a scale ('A minor') or a list of notes - one of them - with the retune time in milliseconds."""
-    from infer_offline import PitchTune
     if (scale is None) == (notes is None):
         raise ValueError(f"{where}: a tune takes scale or notes, one of them")
     kw = {"strength": float(strength), "retune": float(retune_ms) / 1000.0, "a4": float(a4)}
@@ -354,7 +350,6 @@ def _job_tune(n, e, default=None):
 
 def _envelope(where, rate, hop_ms=500.0, frames=2):
     """`infer_offline.EnvelopeMix` from a rate, the hop in milliseconds and the window in hops."""
-    from infer_offline import EnvelopeMix
     try:
         return EnvelopeMix(float(rate), float(hop_ms) / 1000.0, frames)
     except (TypeError, ValueError) as e:
@@ -385,7 +380,6 @@ def _job_envelope(n, e, default=None):
 
 def _timeline(n, points):
     """An entry's `timeline: [{at: <seconds>, id: n} | {at: <seconds>, mix: {id: weight}}, ...]` -> `SpeakerTimeline`."""
-    from infer_offline import SpeakerTimeline
     if not (isinstance(points, list) and points and all(isinstance(p, dict) and set(p) in ({"at", "id"}, {"at", "mix"}) for p in points)):
         raise ValueError(f"--jobs: entry {n}: timeline is a non-empty list of {{at, id}} or {{at, mix}} points, got {points!r}")
     return SpeakerTimeline([(p["at"], p["id"] if "id" in p else p["mix"]) for p in points])
@@ -393,7 +387,6 @@ def _timeline(n, points):
 
 def _key_timeline(n, points):
     """An entry's `key_timeline: [{at: <seconds>, key: <semitones>}, ...]` -> `KeyTimeline`."""
-    from infer_offline import KeyTimeline
     if not (isinstance(points, list) and points and all(isinstance(p, dict) and set(p) == {"at", "key"} for p in points)):
         raise ValueError(f"--jobs: entry {n}: key_timeline is a non-empty list of {{at, key}} points, got {points!r}")
     return KeyTimeline([(p["at"], p["key"]) for p in points])

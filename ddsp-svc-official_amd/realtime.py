@@ -6,6 +6,8 @@ import numpy as np
 import torch
 
 import hipddsp
+from controls import EnvelopeMix, KeyTimeline, PitchTune, SpeakerTimeline, UnitIndexBank, check_job_index
+from ddsp.analysis import MODEL_FIELDS, _model_field, check_units_width  # noqa: F401  (the two model names stay importable from here)
 
 
 # ---- the size and key arithmetic of the reference's callback that does not touch audio ------------------------------------
@@ -83,7 +85,6 @@ def _check_analysers(name, window, units_encoder, f0_extractor, samplerate, hop,
     shorthand = isinstance(f0_extractor, str) and f0_extractor in ("crepe", "ac")
     if not ((shorthand or hasattr(f0_extractor, "extract")) and hasattr(units_encoder, "encode")):
         raise ValueError(f"{name}: units_encoder / f0_extractor must be ddsp.vocoder.Units_Encoder / F0_Extractor")
-    from ddsp.analysis import check_units_width
     check_units_width(name, units_encoder, *models)
     if not shorthand and (f0_extractor.sample_rate != samplerate or f0_extractor.hop_size != hop):
         raise ValueError(f"{name}: the f0 extractor works at {f0_extractor.sample_rate} Hz with hop "
@@ -372,17 +373,7 @@ def default_model_widths(S):
     return tuple(w for w in (1 << i for i in range(int(S).bit_length())) if w < S) + (int(S),)
 
 
-MODEL_FIELDS = ("sampling_rate", "block_size", "n_unit", "device")
 MAX_GLIDE_POINTS = 64             # breakpoints of one slot's speaker timeline (`ddsp_bank_glide`'s P_max)
-
-
-def _model_field(model, field):
-    if field == "n_unit":
-        return int(model.unit2ctrl.n_unit)
-    if field == "device":
-        return next(model.parameters()).device
-    host = getattr(model, {"sampling_rate": "_sr", "block_size": "_hop"}[field], None)   # (the synthesisers' host copies:
-    return int(getattr(model, field) if host is None else host)                          # the buffers would be read back)
 
 
 def _check_models(model, models):
@@ -698,7 +689,6 @@ class StreamBank:
         if not isinstance(tune, bool):
             raise ValueError(f"StreamBank: tune must be True or False, got {tune!r}")
         if indices is not None:
-            from infer_offline import UnitIndexBank
             if not isinstance(indices, UnitIndexBank):
                 raise ValueError(f"StreamBank: indices must be an infer_offline.UnitIndexBank or None, got {type(indices).__name__}")
             if isinstance(retrieve_k, bool) or not isinstance(retrieve_k, int) or not 1 <= retrieve_k <= hipddsp.MAX_RETRIEVE_K:
@@ -716,7 +706,6 @@ class StreamBank:
             if units_encoder is None or f0_extractor is None:
                 raise ValueError("StreamBank: envelope=True needs units_encoder= and f0_extractor= (the mix runs in push_audio's "
                                  "block)")
-            from infer_offline import EnvelopeMix
             try:
                 one = EnvelopeMix(1.0, envelope_hop_seconds, envelope_frames)
                 self.envelope_setting = (one.setting(samplerate), one.setting(_model_field(model, "sampling_rate")), one.frames)
@@ -928,7 +917,6 @@ class StreamBank:
         padded with id 1), its rows of `glide_t` / `glide_w`, `glide_n` and `glide_clock`: device rows only, no capture.
         ValueError, before any write: a bank built without `glide_breakpoints`, more points than it, two points on one sample,
         more ids than `max_mix`, an id outside [1, n_spk] of the slot's model."""
-        from infer_offline import SpeakerTimeline
         if self.glide_breakpoints is None:
             raise ValueError("StreamBank.set_timeline: this bank was built without glide_breakpoints=")
         slot = self._slot(slot)
@@ -998,7 +986,6 @@ class StreamBank:
         without `tune=True`, or for anything but a PitchTune or None."""
         if self.tune_mask is None:
             raise ValueError("StreamBank.set_tune: this bank was built without tune=True")
-        from infer_offline import PitchTune
         if tune is not None and not isinstance(tune, PitchTune):
             raise ValueError(f"StreamBank.set_tune: tune must be an infer_offline.PitchTune or None, got {tune!r}")
         slot = self._slot(slot)
@@ -1013,7 +1000,6 @@ class StreamBank:
         if self.rate_of_slot is None:
             raise ValueError("StreamBank.set_envelope: this bank was built without envelope=True")
         if rate is not None:
-            from infer_offline import EnvelopeMix
             try:
                 rate = EnvelopeMix(rate).rate
             except ValueError as e:
@@ -1028,7 +1014,6 @@ class StreamBank:
         ratio that is not a finite number in [0, 1]."""
         if self.indices is None:
             raise ValueError("StreamBank.set_index: this bank was built without indices=")
-        from infer_offline import check_job_index
         if index is not None:
             check_job_index("StreamBank.set_index", (index, ratio), len(self.indices))
         slot = self._slot(slot)
@@ -1043,7 +1028,6 @@ class StreamBank:
         Writes the slot's rows of `key_t` / `key_semi` / `key_fac`, `key_n` and `key_clock`: device rows only, no capture.
         `set_pitch` ends the timeline.  ValueError, before any write: a bank built without `pitch_breakpoints`, more points than
         it, two points on one sample."""
-        from infer_offline import KeyTimeline
         if self.pitch_breakpoints is None:
             raise ValueError("StreamBank.set_pitch_timeline: this bank was built without pitch_breakpoints=")
         slot = self._slot(slot)

@@ -152,10 +152,18 @@ def test_main_takes_an_envelope():
     for bad in ("0.5", [0.5], True, {"hop_ms": 10}, {"rate": 0.5, "hop": 10}, {"rate": 1.5}, {"rate": 0.5, "frames": 3}, 2):
         with pytest.raises(ValueError, match="entry 3"):
             main._job_envelope(3, {"envelope": bad})
-    # the job as job_table takes it: as short as what it carries allows
-    assert main._job_tuple(0, 1, 2, 3.0) == (0, 1, 2, 3.0) and main._job_tuple(0, 1, 2, 3.0, envelope=e) == (0, 1, 2, 3.0, None, None, None, e)
-    assert len(main._job_tuple(0, 1, 2, 3.0, None, None, (1, 0.5))) == 7 and len(main._job_tuple(0, 1, 2, 3.0, at_least=5)) == 5
-    job_table([(0, 0, 10, 0, 5120)], 1, [main._job_tuple(0, 0, 1, 0.0, envelope=e)], [bank_model("CombSub", 2, 43, "cpu")])
+    # the job as job_table takes it: a record per file, with None for every control the voice does not carry
+    Job = main.Job
+    bare, indexed, mixed = Job(None, 1, 2, 3.0), Job(None, 1, 2, 3.0, index=(1, 0.5)), Job(None, 1, 2, 3.0, envelope=e)
+    assert main._file_jobs(2, [bare, mixed]) == [Job(0, 1, 2, 3.0), Job(0, 1, 2, 3.0, None, None, None, e),
+                                                  Job(1, 1, 2, 3.0), Job(1, 1, 2, 3.0, None, None, None, e)]
+    (job,) = main._file_jobs(1, [bare])
+    assert (job.file, job.model, job.spk, job.key) == (0, 1, 2, 3.0) and (job.formant, job.tune, job.index, job.envelope) == (None,) * 4
+    (job,) = main._file_jobs(1, [indexed])
+    assert (job.formant, job.tune, job.index, job.envelope) == (None, None, (1, 0.5), None)
+    (job,) = main._file_jobs(1, [mixed])
+    assert (job.formant, job.tune, job.index) == (None, None, None) and job.envelope is e
+    job_table([(0, 0, 10, 0, 5120)], 1, main._file_jobs(1, [Job(None, 0, 1, 0.0, envelope=e)]), [bank_model("CombSub", 2, 43, "cpu")])
 
 
 # ---- the bank, the entry points and the symbols --------------------------------------------------------------------------------------

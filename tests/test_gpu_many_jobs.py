@@ -178,6 +178,37 @@ def test_the_feature_is_there(lib_path):
     assert "jobs" in inspect.signature(infer_offline.convert_many_device).parameters and hasattr(hipddsp.Context, "pcm16")
 
 
+def test_tuples_and_records_render_the_same_bits(dev, lib_path, models, encoder, extractor):  # noqa: F811
+    """Every control once - a speaker timeline, a key timeline, a numeric formant, a tune, an index, an envelope - and a plain
+    job, over two short files of three and two slices and two models, in groups of one and two rows: the list as tuples and as
+    `Job` records through `render_jobs_device`, the same seed.  The same launches on the same tables: equal bits, spans, rate."""
+    import infer_offline
+    from controls import EnvelopeMix, Job, KeyTimeline, PitchTune, SpeakerTimeline, UnitIndex, UnitIndexBank
+    audios = [_voiced(22 * HOP + 100, 150.0, 31), _voiced(15 * HOP + 3, 210.0, 32)]
+    slices = [[(0, 9 * HOP), (9 * HOP, 15 * HOP), (15 * HOP, 22 * HOP + 100)], [(0, 6 * HOP), (8 * HOP, 15 * HOP + 3)]]
+    rng = np.random.default_rng(33)
+    bank = UnitIndexBank([UnitIndex(rng.standard_normal((n, 256)).astype(np.float32)) for n in (5, 7)], device=dev, k=3)
+    jobs = [(0, 0, SpeakerTimeline([(0.0, 1), (0.2, {1: 0.25, 2: 0.75})]), 0.0), (1, 1, 2, KeyTimeline([(0.0, 0.0), (0.15, 3.0)])),
+            (0, 1, 1, 1.0, 2), (1, 0, MIX, 0.0, None, PitchTune.scale("A", "minor", retune=0.02)),
+            (0, 0, 2, -2.0, None, None, (1, 0.5)), (1, 1, 1, 0.0, None, None, None, EnvelopeMix(0.25, 0.01, 4)), (1, 0, 1, 0.0)]
+    records = [Job.of(j, job) for j, job in enumerate(jobs)]
+    assert [len(job) for job in jobs] == [4, 4, 5, 6, 7, 8, 4] and all(isinstance(r, Job) for r in records)
+    files = infer_offline.analyse_many(_args(), audios, SR, slices, encoder, extractor, 0, None)
+    table = infer_offline.job_table(files["pieces"], 2, records, models[:2], len(bank))
+    groups = infer_offline.job_groups(table, 2, 16)
+    assert [row[2] for row in files["pieces"]] == [10, 7, 8, 7, 8]
+    assert min(sum(1 for m, _ in groups if m == k) for k in (0, 1)) >= 2 and {len(g) for _, g in groups} == {1, 2}
+    kw = dict(batch_frames=16, noise_seed=5, indices=bank, retrieve_k=3)
+    got, spans, sr_o = infer_offline.render_jobs_device(models[:2], _args(), files, jobs, **kw)
+    again, spans_again, sr_again = infer_offline.render_jobs_device(models[:2], _args(), files, records, **kw)
+    torch.cuda.synchronize()
+    infer_offline.hipddsp.context_for(dev).poll_error()
+    assert spans == spans_again and len(spans) == len(jobs) and sr_o == sr_again == SR
+    assert got.dtype == torch.float64 and bool(torch.isfinite(got).all()) and torch.equal(got, again)
+    for j, (base, total) in enumerate(spans):
+        assert total > 0 and float(got[base:base + total].abs().max()) > 1e-3, j
+
+
 # ---- the six-column gather -------------------------------------------------------------------------------------------------
 
 N_SAMPLES, N_FRAMES, JOB_KEYS = [700, 2051], [11, 33], [0, 3, -12, 5]

@@ -139,14 +139,22 @@ def test_main_takes_an_index(tmp_path):
     for bad in (1.5, -0.1, float("nan")):
         with pytest.raises(ValueError, match="entry 4: index"):
             files.setting("--jobs: entry 4", a, bad)
-    # the job as job_table takes it: as short as what it carries allows
-    tune = PitchTune(["A"])
-    assert main._job_tuple(0, 1, 2, 3.0) == (0, 1, 2, 3.0) and main._job_tuple(0, 1, 2, 3.0, 1.0) == (0, 1, 2, 3.0, 1.0)
-    assert main._job_tuple(0, 1, 2, 3.0, None, tune) == (0, 1, 2, 3.0, None, tune)
-    assert main._job_tuple(0, 1, 2, 3.0, None, None, (1, 0.5)) == (0, 1, 2, 3.0, None, None, (1, 0.5))
-    assert main._job_tuple(0, 1, 2, 3.0, at_least=5) == (0, 1, 2, 3.0, None) and len(main._job_tuple(0, 1, 2, 3.0, 1.0, tune, at_least=5)) == 6
+    # the job as job_table takes it: a record per file, with None for every control the voice does not carry
+    tune, Job = PitchTune(["A"]), main.Job
+    e = main._cmd_envelope(main.parse_args(base + ["--rms_mix_rate", "0.25"]))
+
+    def fields(voice):
+        (job,) = main._file_jobs(1, [voice])
+        return (job.file, job.model, job.spk, job.key, job.formant, job.tune, job.index, job.envelope)
+    assert fields(Job(None, 1, 2, 3.0)) == (0, 1, 2, 3.0, None, None, None, None)
+    assert fields(Job(None, 1, 2, 3.0, 1.0)) == (0, 1, 2, 3.0, 1.0, None, None, None)
+    assert fields(Job(None, 1, 2, 3.0, None, tune)) == (0, 1, 2, 3.0, None, tune, None, None)
+    assert fields(Job(None, 1, 2, 3.0, index=(1, 0.5))) == (0, 1, 2, 3.0, None, None, (1, 0.5), None)
+    assert fields(Job(None, 1, 2, 3.0, envelope=e)) == (0, 1, 2, 3.0, None, None, None, e)
+    assert [j.file for j in main._file_jobs(3, [Job(None, 0, 1, 0.0), Job(None, 0, 2, 0.0)])] == [0, 0, 1, 1, 2, 2]
     models = [bank_model("CombSub", 2, 43, "cpu")]
-    jobs = [main._job_tuple(0, 0, 1, 0.0, None, None, files.setting("x", a, 0.25)), main._job_tuple(0, 0, 2, 1.0, 2.0, tune, None)]
+    jobs = main._file_jobs(1, [Job(None, 0, 1, 0.0, None, None, files.setting("x", a, 0.25)), Job(None, 0, 2, 1.0, 2.0, tune, None),
+                               Job(None, 0, 1, 0.0), Job(None, 0, 1, 0.0, envelope=e)])
     job_table([(0, 0, 10, 0, 5120)], 1, jobs, models, len(files.indices))
 
 
